@@ -18,7 +18,9 @@ own source size (64 x 1080 x 1920 BGR frames per step: bilinear letterbox to 384
 `cfg3` / `cfg4` / `cfg5` carry BASELINE.json's remaining configurations in the same driver-run line (MiniLM 512 x 128 +
 flat kNN over 1 M x 384; YOLOv8m objects + yolov8n-face on 64 x 1080p; IVF-PQ over a 12.5 M x 384 shard per GPU).
 `python bench.py --gpus N` without WORLD_SIZE starts its own N ranks (a child `python -m torch.distributed.run`, spawned
-before anything touches the GPU) and relays their line.  See DESIGN.md "Measurement".
+before anything touches the GPU) and relays their line.  `--dump-outputs DIR` writes what the headline run returned in
+its last timed step to DIR/<name>.npy (same arguments, same inputs: two builds compare output for output).  See DESIGN.md
+"Measurement".
 """
 from __future__ import annotations
 
@@ -73,7 +75,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-cfg5", action="store_true", help="skip the cfg5 block (IVF-PQ over a 12.5 M x 384 shard per GPU)")
     ap.add_argument("--ivfpq-n", type=int, default=12_500_000, help="rows per GPU of the cfg5 index (100 M / 8)")
     ap.add_argument("--cfg-steps", type=int, default=40, help="timed steps of the cfg4 frame runs")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline frames run returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64) for output-for-output comparison of two builds")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launcher_decision(gpus: int, env) -> str:
@@ -263,6 +271,44 @@ class Pipeline:
         alg = 3.0 * self.h * self.w * self.batch  # 3*W*H bytes per frame
         return {"kernel": "k_hsv_sums", "bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
                 "alg_total": alg * cnt, "scale": 1e9, "ms_total": ms, "launches": cnt, "alg_per_step": alg}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(pipe, outdir):
+    """The arrays the last timed step handed back (``Pipeline.last``: the detections a caller receives in that step, the
+    K2 / K1 scene sums of its batch) and the embeddings of its segments, as ``outdir/<name>.npy``.  Detection rows past a
+    frame's count are zeroed (their contents are not part of the result); integer results are stored as float32 /
+    float64, exactly.  Call after the timed region's closing synchronize."""
+    import numpy as np
+
+    from eioku_amd import detect
+
+    arrays = {}
+    scene = [t for t in pipe.last if not isinstance(t, tuple)]
+    for dets, counts, *_ in (t for t in pipe.last if isinstance(t, tuple)):
+        n, max_det = int(dets.shape[0]), int(dets.shape[1])
+        d = dets.cpu().numpy().view(detect.DET_DTYPE).reshape(n, max_det).copy()
+        c = counts.cpu().numpy().astype(np.int64)
+        d[np.arange(max_det)[None, :] >= c[:, None]] = np.zeros((), detect.DET_DTYPE)
+        arrays["det_boxes_xyxy"] = np.stack([d["x1"], d["y1"], d["x2"], d["y2"]], -1).astype(np.float32)
+        arrays["det_conf"] = d["conf"].astype(np.float32)
+        arrays["det_cls"] = d["cls"].astype(np.float32)
+        arrays["det_anchor"] = d["anchor"].astype(np.float32)
+        arrays["det_counts"] = c.astype(np.float32)
+    for name, t in zip(("scene_hsv_sums", "scene_luma_sad"), scene):  # Pipeline.step's order; uint64 bits in int64
+        arrays[name] = t.cpu().numpy().view(np.uint64).astype(np.float64)
+    if pipe.embedded:
+        arrays["embeddings"] = np.concatenate([e.cpu().numpy() for e in pipe.embedded]).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs exceed {DUMP_LIMIT_BYTES}")
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    print(f"dumped {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} to {out}", file=sys.stderr)
 
 
 def knn_part(args, device, rank, world):
@@ -566,8 +612,9 @@ def main():
             return i == args.steps // 2
         return args.prof_every > 0 and i % args.prof_every == 0
 
-    def run_frames(height, width, args=args):
-        """warm-up, then EXACTLY args.steps timed steps between barrier + synchronize pairs; max over ranks."""
+    def run_frames(height, width, args=args, dump_dir=None):
+        """warm-up, then EXACTLY args.steps timed steps between barrier + synchronize pairs; max over ranks.  dump_dir:
+        rank 0 writes the last timed step's outputs there (dump_outputs), after the timing."""
         pipe = Pipeline(args, device, rank, height, width)
         for i in range(args.warmup):
             pipe.step(i)
@@ -591,6 +638,8 @@ def main():
         if pipe.batcher is not None:
             assert pipe.batcher.encoded - seg0 == args.segments * args.steps, "every step's segments are encoded in the timed region"
         _lib.prof_enable(False)
+        if dump_dir is not None and rank == 0:
+            dump_outputs(pipe, dump_dir)
         pipe.prof_steps = sum(1 for i in range(args.steps) if profiled(i, args))
         if world > 1:
             t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -636,7 +685,7 @@ def main():
         torch.cuda.empty_cache()
         return res, stages
 
-    head, stages = run_frames(args.height, args.width)
+    head, stages = run_frames(args.height, args.width, dump_dir=args.dump_outputs)
     out = {
         "metric": "frames/sec (scene+detect+embed) per node",
         "value": head["value"],
