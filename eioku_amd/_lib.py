@@ -140,6 +140,23 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_void_p]),
     "eioku_resnet18_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_iresnet_create": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "eioku_iresnet_destroy": (None, [C.c_void_p]),
+    "eioku_iresnet_num_convs": (C.c_int, [C.c_void_p]),
+    "eioku_iresnet_num_blocks": (C.c_int, [C.c_void_p]),
+    "eioku_iresnet_conv_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eioku_iresnet_set_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eioku_iresnet_set_prelu": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_iresnet_set_bn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eioku_iresnet_set_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_iresnet_crop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_void_p]),
+    "eioku_iresnet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_iresnet_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_void_p]),
+    "eioku_iresnet_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_dbscan_cosine": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "eioku_ivfpq_lists_aux": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eioku_ivfpq_lists_workspace": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]),

@@ -314,6 +314,14 @@ class PipelinedDetector:
         n, max_det = int(dets.shape[0]), int(dets.shape[1])
         return dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy()
 
+    def result_with_frames(self):
+        """``result()`` plus the device copy of that batch's frames (CUDA uint8 ``(n,h,w,3)``, the tensor the detector read;
+        complete: the batch's event has been waited for) - the face-clustering crops read it instead of a second upload."""
+        dets, counts, ev, f = self._pending.pop(0)
+        ev.synchronize()
+        n, max_det = int(dets.shape[0]), int(dets.shape[1])
+        return dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy(), f
+
     def result_on_device(self):
         """Oldest submitted batch as the raw CUDA tensors plus the event that marks them complete."""
         dets, counts, ev, _ = self._pending.pop(0)

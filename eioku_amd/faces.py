@@ -1,0 +1,387 @@
+"""Face clustering: ArcFace embeddings (insightface ``arcface_torch`` IResNet) and cosine DBSCAN on the HIP kernels of
+``csrc/faces.hip``.
+
+Fills the ``cluster_id`` that ``ModelManager.detect_faces`` returns (``cluster_faces`` config key).  Per face the device
+crops a square of side ``max(w, h, 1)`` centred on the detector's box, resamples it bilinearly to 112 x 112 (K13a),
+normalises it as arcface_torch's inference does (``(v / 255 - 0.5) / 0.5``) and runs the IResNet (K13b) to a unit
+512-vector; once per video the vectors are clustered by DBSCAN on cosine distance with scikit-learn's labels (K14).
+There is no landmark alignment: the face detector exposes no keypoints.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from pathlib import Path
+
+import numpy as np
+
+from . import _lib
+from ._buffers import current_stream, on_device, ptr
+
+CROP = 112
+FEAT = 512
+TAP_BITS = 11
+WIDTHS = (64, 128, 256, 512)
+_BN_EPS = 1e-5
+DEPTHS = {"r18": (2, 2, 2, 2), "r34": (3, 4, 6, 3), "r50": (3, 4, 14, 3), "r100": (3, 13, 30, 3)}
+
+
+# ---- host side of K13a ---------------------------------------------------------------------------------------------
+def axis_taps(lo: float, hi: float, side: float, size: int):
+    """One axis of a crop (float64, as ``faces.hip`` axis_taps): ``(first source index int64 (112,), weight of the second
+    tap in 1/2048 int64 (112,))`` for output pixel centres over ``[centre - side / 2, centre + side / 2]``; the index is
+    clamped to ``[-2, size]`` (taps outside the frame read 0 either way)."""
+    left = (lo + hi) * 0.5 - side * 0.5
+    step = side / CROP
+    src = left + (np.arange(CROP, dtype=np.float64) + 0.5) * step - 0.5
+    f = np.floor(src)
+    w1 = np.floor((src - f) * (1 << TAP_BITS) + 0.5).astype(np.int64)
+    x0 = f.astype(np.int64)
+    carry = w1 == (1 << TAP_BITS)
+    x0 = np.where(carry, x0 + 1, x0)
+    w1 = np.where(carry, 0, w1)
+    return np.clip(x0, -2, size), w1
+
+
+def crop_taps(box, h: int, w: int):
+    """``box = (x1, y1, x2, y2)`` -> ``(x0, wx1, y0, wy1)``: the square of side ``max(w, h, 1)`` centred on the box."""
+    x1, y1, x2, y2 = (float(np.float32(v)) for v in box)
+    side = max(max(x2 - x1, y2 - y1), 1.0)
+    return (*axis_taps(x1, x2, side, w), *axis_taps(y1, y2, side, h))
+
+
+# ---- arcface_torch state dict -> folded parameters -------------------------------------------------------------------
+def depths_from_state(sd: dict) -> tuple:
+    """Blocks per stage from the ``layer<L>.<b>.conv1.weight`` keys (r18 [2,2,2,2], r50 [3,4,14,3], r100 [3,13,30,3])."""
+    depths = []
+    for li in range(1, 5):
+        b = 0
+        while f"layer{li}.{b}.conv1.weight" in sd:
+            b += 1
+        if b == 0:
+            raise KeyError(f"state dict has no layer{li}.0.conv1.weight (not an arcface_torch iresnet)")
+        depths.append(b)
+    return tuple(depths)
+
+
+def _np_state(state_dict: dict) -> dict:
+    sd = state_dict.get("state_dict", state_dict)
+    return {k.replace("module.", ""): np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in sd.items()}
+
+
+def _bn(sd, name, c):
+    out = []
+    for f in ("weight", "bias", "running_mean", "running_var"):
+        key = f"{name}.{f}"
+        if key not in sd:
+            raise KeyError(f"state dict has no {key}")
+        v = sd[key].astype(np.float64)
+        if v.shape != (c,):
+            raise ValueError(f"{key}: expected shape {(c,)}, got {v.shape}")
+        out.append(v)
+    g, b, mu, var = out
+    s = g / np.sqrt(var + _BN_EPS)
+    return s, b - mu * s
+
+
+def _tensor(sd, key, shape):
+    if key not in sd:
+        raise KeyError(f"state dict has no {key}")
+    v = sd[key]
+    if tuple(v.shape) != tuple(shape):
+        raise ValueError(f"{key}: expected shape {tuple(shape)}, got {tuple(v.shape)}")
+    return v.astype(np.float64)
+
+
+def fold_state(state_dict: dict) -> dict:
+    """arcface_torch ``iresnet`` state dict (optionally under ``"state_dict"`` / with ``module.`` prefixes) ->
+    ``{"depths", "convs": {name: (w, b)}, "prelu": [stem, block 0, ...], "bn": [(scale, shift) per block], "head": (w, b)}``
+    with every BatchNorm that follows a conv folded into it, and ``bn2 -> fc -> features`` folded into one fc whose
+    columns are permuted from torch's NCHW flatten (``c * 49 + y * 7 + x``) to the device's NHWC (``(y * 7 + x) * 512 + c``).
+    A missing or misshapen tensor raises."""
+    sd = _np_state(state_dict)
+    depths = depths_from_state(sd)
+    convs, prelu, bns = {}, [], []
+
+    def fold(conv, bn, cout, cin, k):
+        w = _tensor(sd, conv + ".weight", (cout, cin, k, k))
+        s, t = _bn(sd, bn, cout)
+        return (w * s[:, None, None, None]).astype(np.float32), t.astype(np.float32)
+
+    convs["conv1"] = fold("conv1", "bn1", 64, 3, 3)
+    prelu.append(_tensor(sd, "prelu.weight", (64,)).astype(np.float32))
+    inplanes = 64
+    for li, (planes, depth) in enumerate(zip(WIDTHS, depths), start=1):
+        for b in range(depth):
+            p = f"layer{li}.{b}"
+            cin = inplanes if b == 0 else planes
+            s, t = _bn(sd, p + ".bn1", cin)
+            bns.append((s.astype(np.float32), t.astype(np.float32)))
+            convs[p + ".conv1"] = fold(p + ".conv1", p + ".bn2", planes, cin, 3)
+            prelu.append(_tensor(sd, p + ".prelu.weight", (planes,)).astype(np.float32))
+            convs[p + ".conv2"] = fold(p + ".conv2", p + ".bn3", planes, planes, 3)
+            if b == 0:
+                convs[p + ".downsample.0"] = fold(p + ".downsample.0", p + ".downsample.1", planes, cin, 1)
+        inplanes = planes
+    # fc(bn2(x)) = W (s2 * x + t2) + b, then features: a * (z - mu) + beta  (all exact: no padding is involved)
+    s2, t2 = _bn(sd, "bn2", 512)
+    W = _tensor(sd, "fc.weight", (FEAT, 512 * 49))
+    fb = _tensor(sd, "fc.bias", (FEAT,))
+    sf, tf = _bn(sd, "features", FEAT)
+    s2x = np.repeat(s2, 49)  # NCHW flatten: channel c covers columns c * 49 .. c * 49 + 48
+    t2x = np.repeat(t2, 49)
+    Wf = sf[:, None] * (W * s2x[None, :])
+    bf = sf * (W @ t2x + fb) + tf
+    return {"depths": depths, "convs": convs, "prelu": prelu, "bn": bns,
+            "head": (nchw_to_nhwc_columns(Wf).astype(np.float32), bf.astype(np.float32))}
+
+
+def nchw_to_nhwc_columns(w: np.ndarray) -> np.ndarray:
+    """fc weight ``[out][c * 49 + y * 7 + x]`` -> ``[out][(y * 7 + x) * 512 + c]`` (the device's NHWC activations)."""
+    return np.ascontiguousarray(w.reshape(w.shape[0], 512, 49).transpose(0, 2, 1).reshape(w.shape[0], 512 * 49))
+
+
+def random_state_dict(seed: int = 3, depths=DEPTHS["r18"]) -> dict:
+    """Seeded random arcface_torch-shaped state dict (float32 numpy), BatchNorm running statistics randomised too:
+    benchmarks and tests (no checkpoint is reachable offline)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(name, cout, cin, k, gain=1.0):
+        sd[name + ".weight"] = (gain * rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
+
+    def bn(name, c):
+        sd[name + ".weight"] = rng.uniform(0.7, 1.3, c).astype(np.float32)
+        sd[name + ".bias"] = (0.1 * rng.standard_normal(c)).astype(np.float32)
+        sd[name + ".running_mean"] = (0.1 * rng.standard_normal(c)).astype(np.float32)
+        sd[name + ".running_var"] = rng.uniform(0.6, 1.4, c).astype(np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(0, np.int64)
+
+    def prelu(name, c):
+        sd[name + ".weight"] = rng.uniform(0.15, 0.35, c).astype(np.float32)
+
+    conv("conv1", 64, 3, 3, 1.4)
+    bn("bn1", 64)
+    prelu("prelu", 64)
+    inplanes = 64
+    for li, (planes, depth) in enumerate(zip(WIDTHS, depths), start=1):
+        for b in range(depth):
+            p = f"layer{li}.{b}"
+            cin = inplanes if b == 0 else planes
+            bn(p + ".bn1", cin)
+            conv(p + ".conv1", planes, cin, 3, 1.4)
+            bn(p + ".bn2", planes)
+            prelu(p + ".prelu", planes)
+            conv(p + ".conv2", planes, planes, 3, 0.5)
+            bn(p + ".bn3", planes)
+            if b == 0:
+                conv(p + ".downsample.0", planes, cin, 1)
+                bn(p + ".downsample.1", planes)
+        inplanes = planes
+    bn("bn2", 512)
+    sd["fc.weight"] = (rng.standard_normal((FEAT, 512 * 49)) / np.sqrt(512 * 49)).astype(np.float32)
+    sd["fc.bias"] = (0.01 * rng.standard_normal(FEAT)).astype(np.float32)
+    bn("features", FEAT)
+    sd["features.weight"] = np.ones(FEAT, np.float32)  # arcface_torch: constant 1, not trained
+    return sd
+
+
+def load_checkpoint(path) -> dict:
+    """``backbone.pth`` (arcface_torch's released state dict) -> folded state (torch's restricted unpickler: tensors only)."""
+    import torch
+
+    return fold_state(torch.load(str(path), map_location="cpu", weights_only=True))
+
+
+# ---- K14 ---------------------------------------------------------------------------------------------------------
+def dbscan_cosine(embeddings, eps: float, min_samples: int):
+    """scikit-learn ``DBSCAN(eps, min_samples=min_samples, metric="cosine").fit(embeddings).labels_`` on unit-norm rows,
+    on the device: float32 ``(n, d)`` (numpy or CUDA tensor; d % 32 == 0, n <= 65536, eps in [0, 2]) -> int32 ``(n,)``
+    labels on the same side (-1 = noise)."""
+    lib = _lib.load()
+    _lib.init()
+    dev = on_device(embeddings)
+    if dev:
+        e = embeddings.contiguous()
+        import torch
+
+        labels = torch.empty((int(e.shape[0]),), dtype=torch.int32, device=e.device)
+    else:
+        e = np.ascontiguousarray(embeddings, dtype=np.float32)
+        labels = np.empty(int(e.shape[0]), np.int32)
+    if len(e.shape) != 2:
+        raise ValueError("expected (n, d) embeddings")
+    n, d = int(e.shape[0]), int(e.shape[1])
+    _lib.check(lib.eioku_dbscan_cosine(ptr(e) if n else None, n, d, float(eps), int(min_samples), ptr(labels) if n else None,
+                                       _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(e) if dev else None),
+               "eioku_dbscan_cosine")
+    return labels
+
+
+def cluster_ids(labels) -> list:
+    """DBSCAN labels -> the artifact's ``cluster_id`` strings: ``face_cluster_001`` for label 0, ``None`` for noise."""
+    return [None if int(v) < 0 else f"face_cluster_{int(v) + 1:03d}" for v in labels]
+
+
+class FaceEmbedder:
+    """arcface_torch ``iresnet`` (``backbone.pth``) + the crop / normalisation of its inference script, on the device."""
+
+    def __init__(self, state: dict):
+        self._lib = _lib.load()
+        _lib.init()
+        self.depths = tuple(int(v) for v in state["depths"])
+        h = C.c_void_p()
+        _lib.check(self._lib.eioku_iresnet_create((C.c_int * 4)(*self.depths), C.byref(h)), "eioku_iresnet_create")
+        self._h = h
+        for i in range(self._lib.eioku_iresnet_num_convs(h)):
+            name = C.create_string_buffer(64)
+            co, ci, k, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+            _lib.check(self._lib.eioku_iresnet_conv_info(h, i, name, 64, C.byref(co), C.byref(ci), C.byref(k), C.byref(s)),
+                       "eioku_iresnet_conv_info")
+            n = name.value.decode()
+            if n not in state["convs"]:
+                raise KeyError(f"state has no weights for {n}")
+            w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state["convs"][n])
+            if w.shape != (co.value, ci.value, k.value, k.value) or b.shape != (co.value,):
+                raise ValueError(f"{n}: expected weight {(co.value, ci.value, k.value, k.value)}, got {w.shape}")
+            _lib.check(self._lib.eioku_iresnet_set_conv(h, i, ptr(w), ptr(b)), f"eioku_iresnet_set_conv({n})")
+        nb = self._lib.eioku_iresnet_num_blocks(h)
+        if len(state["prelu"]) != nb + 1 or len(state["bn"]) != nb:
+            raise ValueError(f"state has {len(state['prelu'])} PReLUs / {len(state['bn'])} bn1s for {nb} blocks")
+        for u, a in enumerate(state["prelu"]):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            _lib.check(self._lib.eioku_iresnet_set_prelu(h, u, ptr(a)), "eioku_iresnet_set_prelu")
+        for b, (s, t) in enumerate(state["bn"]):
+            s, t = np.ascontiguousarray(s, dtype=np.float32), np.ascontiguousarray(t, dtype=np.float32)
+            _lib.check(self._lib.eioku_iresnet_set_bn(h, b, ptr(s), ptr(t)), "eioku_iresnet_set_bn")
+        w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state["head"])
+        if w.shape != (FEAT, 512 * 49) or b.shape != (FEAT,):
+            raise ValueError(f"head: expected weight {(FEAT, 512 * 49)}, got {w.shape}")
+        _lib.check(self._lib.eioku_iresnet_set_head(h, ptr(w), ptr(b)), "eioku_iresnet_set_head")
+
+    @classmethod
+    def from_cache(cls, cache_dir, model_name: str = "arcface_r18.pth", seed: int | None = None):
+        """Weights from ``<cache>/insightface/<model_name>`` (an arcface_torch ``backbone.pth`` state dict).  A missing file
+        is an error unless a ``seed`` asks for seeded random r18 weights (the ``Places365Classifier.from_cache`` rule)."""
+        path = Path(cache_dir) / "insightface" / model_name
+        if path.exists():
+            return cls(load_checkpoint(path))
+        if seed is None:
+            raise FileNotFoundError(f"{path} not found (no weights to embed faces with)")
+        return cls(fold_state(random_state_dict(seed)))
+
+    @staticmethod
+    def _boxes(boxes):
+        b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 5)
+        return b
+
+    def crop(self, frames_bgr, boxes):
+        """K13a alone: BGR uint8 ``(n,h,w,3)`` + float32 ``(m,5)`` (slot, x1, y1, x2, y2) -> fp16 ``(m,112,112,8)`` CUDA."""
+        import torch
+
+        n, h, w, _ = (int(s) for s in frames_bgr.shape)
+        b = self._boxes(boxes)
+        dev = frames_bgr.device if on_device(frames_bgr) else torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((len(b), CROP, CROP, 8), dtype=torch.float16, device=dev)
+        src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr, dtype=np.uint8)
+        _lib.check(self._lib.eioku_iresnet_crop(self._h, ptr(src), n, h, w, ptr(b), len(b), ptr(out),
+                                                _lib.MEM_DEVICE if on_device(src) else _lib.MEM_HOST, current_stream(out)),
+                   "eioku_iresnet_crop")
+        return out
+
+    def forward_raw(self, crops, upto_block: int = -1):
+        """fp16 ``(m,112,112,8)`` CUDA crops (m <= 256) -> float32 ``(m,512)`` embeddings, or (``upto_block >= 0``) that
+        block's NHWC fp16 output (CUDA)."""
+        import torch
+
+        m = int(crops.shape[0])
+        crops = crops.contiguous()
+        if upto_block >= 0:
+            hw, c = CROP, 64
+            k = 0
+            for li, d in enumerate(self.depths):
+                hw //= 2
+                c = WIDTHS[li]
+                if upto_block < k + d:
+                    break
+                k += d
+            out = torch.empty((m, hw, hw, c), dtype=torch.float16, device=crops.device)
+            _lib.check(self._lib.eioku_iresnet_forward(self._h, ptr(crops), m, int(upto_block), ptr(out), None, current_stream(crops)),
+                       "eioku_iresnet_forward")
+            return out
+        out = torch.empty((m, FEAT), dtype=torch.float32, device=crops.device)
+        _lib.check(self._lib.eioku_iresnet_forward(self._h, ptr(crops), m, -1, None, ptr(out), current_stream(crops)),
+                   "eioku_iresnet_forward")
+        return out
+
+    def embed(self, frames_bgr, boxes) -> np.ndarray:
+        """BGR uint8 ``(n,h,w,3)`` frames (numpy: staged once; CUDA tensor: read in place) + ``boxes`` float32 ``(m,5)``
+        rows ``(frame slot, x1, y1, x2, y2)`` -> float32 ``(m,512)`` unit embeddings (numpy)."""
+        n, h, w, c = (int(s) for s in frames_bgr.shape)
+        if c != 3:
+            raise ValueError("expected (n,h,w,3) BGR frames")
+        b = self._boxes(boxes)
+        out = np.empty((len(b), FEAT), np.float32)
+        if len(b) == 0:
+            return out
+        src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr, dtype=np.uint8)
+        if on_device(src):
+            import torch
+
+            dout = torch.empty((len(b), FEAT), dtype=torch.float32, device=src.device)
+            _lib.check(self._lib.eioku_iresnet_embed(self._h, ptr(src), n, h, w, ptr(b), len(b), ptr(dout), _lib.MEM_DEVICE,
+                                                     current_stream(src)), "eioku_iresnet_embed")
+            return dout.cpu().numpy()
+        _lib.check(self._lib.eioku_iresnet_embed(self._h, ptr(src), n, h, w, ptr(b), len(b), ptr(out), _lib.MEM_HOST, None),
+                   "eioku_iresnet_embed")
+        return out
+
+    def cluster(self, embeddings, eps: float, min_samples: int):
+        """DBSCAN on cosine distance (``dbscan_cosine``) -> int32 labels, numpy."""
+        labels = dbscan_cosine(embeddings, eps, min_samples)
+        return labels.cpu().numpy() if on_device(labels) else labels
+
+    def last_flops(self) -> float:
+        f = C.c_double(0)
+        _lib.check(self._lib.eioku_iresnet_last_flops(self._h, C.byref(f)), "eioku_iresnet_last_flops")
+        return f.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.eioku_iresnet_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FaceClusterer:
+    """Per-video collector shared by ``detect_faces`` and ``analyze_video``: embeddings of the faces that pass the face
+    path's confidence filter, batch by batch, then one DBSCAN at the end that fills each face's ``cluster_id``."""
+
+    def __init__(self, embedder, eps: float, min_samples: int):
+        self.embedder = embedder
+        self.eps = float(eps)
+        self.min_samples = int(min_samples)
+        self._dets: list[dict] = []
+        self._emb: list[np.ndarray] = []
+
+    def add(self, frames_bgr, boxes, dets: list) -> None:
+        """``frames_bgr`` the batch the detector saw (device copy or host), ``boxes`` ``(slot, x1, y1, x2, y2)`` rows for
+        ``dets`` (the detection dicts, in emission order)."""
+        if not dets:
+            return
+        self._emb.append(np.asarray(self.embedder.embed(frames_bgr, np.asarray(boxes, np.float32).reshape(-1, 5)), np.float32))
+        self._dets.extend(dets)
+
+    def embeddings(self) -> np.ndarray:
+        return np.concatenate(self._emb) if self._emb else np.zeros((0, FEAT), np.float32)
+
+    def finish(self) -> None:
+        if not self._dets:
+            return
+        labels = self.embedder.cluster(self.embeddings(), self.eps, self.min_samples)
+        for det, cid in zip(self._dets, cluster_ids(labels)):
+            det["cluster_id"] = cid

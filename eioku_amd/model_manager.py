@@ -5,7 +5,9 @@ ffmpeg / OpenCV / Ultralytics on the CPU.
 
     detect_objects(video_path, config) -> {"detections": [{frame_index, timestamp_ms, label,
                                            confidence, bbox{x,y,width,height}}]}       (ref :215-306)
-    detect_faces(video_path, config)   -> same + "cluster_id": None, label "face"      (ref :308-407)
+    detect_faces(video_path, config)   -> same + "cluster_id", label "face"            (ref :308-407)
+                                          (None, or with config["cluster_faces"] the face's DBSCAN
+                                          cluster of ArcFace embeddings: "face_cluster_001", ...)
     detect_scenes(video_path, config)  -> {"scenes": [{scene_index, start_ms, end_ms,
                                            duration_ms}]}                              (ref :715-835)
 
@@ -33,11 +35,13 @@ class ModelManager:
     """Manages model lifecycle and inference for the hot-path task types."""
 
     def __init__(self, cache_dir: str = "/models", *, frame_source=None, detector_factory=None, batch_size: int = 64,
-                 random_init_seed: int | None = None, place_classifier_factory=None):
+                 random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
-        weights of the right shapes when no checkpoint can exist (offline benchmarks)."""
+        weights of the right shapes when no checkpoint can exist (offline benchmarks);
+        ``face_embedder_factory(cache_dir, model_name) -> embedder`` with ``embed(frames, boxes)`` and
+        ``cluster(embeddings, eps, min_samples)`` (``cluster_faces``)."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -45,6 +49,7 @@ class ModelManager:
         self._frame_source = frame_source
         self._detector_factory = detector_factory
         self._place_classifier_factory = place_classifier_factory  # (cache_dir) -> object with classify(frames, top_k), labels
+        self._face_embedder_factory = face_embedder_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -132,9 +137,36 @@ class ModelManager:
             self._lane_streams[task] = [torch.cuda.Stream(priority=-1) for _ in range(depth)]
         return self._lane_streams[task]
 
+    # ---- face clustering (opt-in: config["cluster_faces"]) ---------------------------------------------
+    CLUSTER_EPS = 0.5         # cosine distance (1 - similarity) of two unit ArcFace embeddings; INTEGRATION.md
+    CLUSTER_MIN_SAMPLES = 3   # faces (the point itself included) that make a core point
+
+    def _face_clusterer(self, config: dict):
+        """The per-video ``FaceClusterer`` of a face-detection config, or None without ``cluster_faces`` (then no
+        embedder is loaded and every ``cluster_id`` stays None, as in the reference)."""
+        if not config.get("cluster_faces", False):
+            return None
+        from .faces import FaceClusterer
+
+        model_name = config.get("face_embedding_model", "arcface_r18.pth")
+        if self._face_embedder_factory is not None:
+            embedder = self._face_embedder_factory(self.cache_dir, model_name)
+        else:
+            from .faces import FaceEmbedder
+
+            embedder = FaceEmbedder.from_cache(self.cache_dir, model_name, seed=self._seed)
+        return FaceClusterer(embedder, config.get("cluster_eps", self.CLUSTER_EPS),
+                             config.get("cluster_min_samples", self.CLUSTER_MIN_SAMPLES))
+
+    @staticmethod
+    def _close_clusterer(cluster):
+        close = getattr(cluster.embedder, "close", None) if cluster is not None else None
+        if close:
+            close()
+
     # ---- objects / faces: one skeleton, as in the reference --------------------------------------------
     def _detect_loop(self, video_path: str, model_name: str, confidence_threshold: float,
-                     frame_interval_seconds: float, face: bool) -> list[dict]:
+                     frame_interval_seconds: float, face: bool, cluster=None) -> list[dict]:
         cap = self._open(video_path)
         fps = cap.fps or 30
         total_frames = int(cap.total_frames)
@@ -158,8 +190,9 @@ class ModelManager:
                 if isinstance(detector, Yolov8Detector) else None)
         metas: list[list[tuple[int, int]]] = []
 
-        def emit(meta, dets, counts):
-            for (frame_idx, timestamp_ms), row, cnt in zip(meta, dets, counts):
+        def emit(meta, dets, counts, frames=None):
+            boxes, batch = [], []
+            for slot, ((frame_idx, timestamp_ms), row, cnt) in enumerate(zip(meta, dets, counts)):
                 for d in row[: int(cnt)]:
                     x1, y1, x2, y2 = (np.float32(d[k]) for k in ("x1", "y1", "x2", "y2"))
                     confidence = float(np.float32(d["conf"]))  # float32 -> Python float, as float(tensor)
@@ -175,18 +208,27 @@ class ModelManager:
                     }
                     if face:
                         det["cluster_id"] = None
+                        if cluster is not None:
+                            boxes.append((slot, x1, y1, x2, y2))
+                            batch.append(det)
                     detections.append(det)
+            if cluster is not None:
+                cluster.add(frames, boxes, batch)
 
         def drain(keep: int):
             while pipe is not None and pipe.in_flight() > keep:
-                emit(metas.pop(0), *pipe.result())
+                if cluster is not None:
+                    dets, counts, frames = pipe.result_with_frames()
+                    emit(metas.pop(0), dets, counts, frames)
+                else:
+                    emit(metas.pop(0), *pipe.result())
 
         def flush():
             if not pend_frames:
                 return
             batch = np.stack(pend_frames)
             if pipe is None:
-                emit(list(pend_meta), *detector.detect(batch, conf=confidence_threshold))
+                emit(list(pend_meta), *detector.detect(batch, conf=confidence_threshold), batch)
             else:
                 pipe.submit(batch, conf=confidence_threshold)
                 metas.append(list(pend_meta))
@@ -211,11 +253,14 @@ class ModelManager:
                 frame_idx += 1
             flush()
             drain(0)
+            if cluster is not None:
+                cluster.finish()
         finally:
             cap.release()
             close = pipe.close if pipe is not None else getattr(detector, "close", None)
             if close:
                 close()
+            self._close_clusterer(cluster)
         return detections
 
     # ---- places: Places365 ResNet18 (reference :560-713) ---------------------------------------------------
@@ -302,13 +347,18 @@ class ModelManager:
             raise
 
     async def detect_faces(self, video_path: str, config: dict) -> dict:
-        """Detect faces in video using YOLOv8-face on the HIP path (reference: :308-407)."""
+        """Detect faces in video using YOLOv8-face on the HIP path (reference: :308-407).  With
+        ``config["cluster_faces"]`` every face that passes the confidence filter is embedded (ArcFace IResNet,
+        ``face_embedding_model`` under ``<cache>/insightface/``) and the video's faces are clustered once by cosine DBSCAN
+        (``cluster_eps``, ``cluster_min_samples``): ``cluster_id`` = ``face_cluster_001``, ... or None for noise."""
         try:
             model_name = config.get("model_name", "yolov8n-face.pt")
             confidence_threshold = config.get("confidence_threshold", 0.7)
             frame_interval_seconds = config.get("frame_interval", 3)
             logger.info(f"Face detection: {video_path} (device: {self._get_device()})")
-            detections = self._detect_loop(video_path, model_name, confidence_threshold, frame_interval_seconds, True)
+            cluster = self._face_clusterer(config)
+            detections = self._detect_loop(video_path, model_name, confidence_threshold, frame_interval_seconds, True,
+                                           cluster)
             logger.info(f"✅ Face detection complete: {len(detections)} detections")
             return {"detections": detections}
         except Exception as e:
@@ -364,7 +414,7 @@ class ModelManager:
             lanes[task] = {"face": face, "conf": cfg.get("confidence_threshold", dflt_conf),
                            "interval": max(1, int(fps * cfg.get("frame_interval", dflt_sec))), "names": detector.names,
                            "pipe": PipelinedDetector(detector, depth=2, streams=self._lanes(task)), "frames": [], "meta": [],
-                           "metas": [], "out": []}
+                           "metas": [], "out": [], "cluster": self._face_clusterer(cfg) if face else None}
         want_scenes = "scene_detection" in configs
         scfg = configs.get("scene_detection") or {}
         content = scfg.get("detector", "ffmpeg") == "content"
@@ -372,8 +422,9 @@ class ModelManager:
         pinned = [None, None]
         copied = [None, None]  # events: the chunk's upload has left the pinned buffer
 
-        def emit(lane, meta, dets, counts):
-            for (frame_idx, timestamp_ms), row, cnt in zip(meta, dets, counts):
+        def emit(lane, meta, dets, counts, frames=None):
+            boxes, batch = [], []
+            for slot, ((frame_idx, timestamp_ms), row, cnt) in enumerate(zip(meta, dets, counts)):
                 for d in row[: int(cnt)]:
                     x1, y1, x2, y2 = (np.float32(d[k]) for k in ("x1", "y1", "x2", "y2"))
                     confidence = float(np.float32(d["conf"]))
@@ -385,11 +436,20 @@ class ModelManager:
                                     "height": float(np.float32(y2 - y1))}}
                     if lane["face"]:
                         det["cluster_id"] = None
+                        if lane["cluster"] is not None:
+                            boxes.append((slot, x1, y1, x2, y2))
+                            batch.append(det)
                     lane["out"].append(det)
+            if lane["cluster"] is not None:
+                lane["cluster"].add(frames, boxes, batch)
 
         def drain(lane, keep):
             while lane["pipe"].in_flight() > keep:
-                emit(lane, lane["metas"].pop(0), *lane["pipe"].result())
+                if lane["cluster"] is not None:
+                    dets, counts, frames = lane["pipe"].result_with_frames()
+                    emit(lane, lane["metas"].pop(0), dets, counts, frames)
+                else:
+                    emit(lane, lane["metas"].pop(0), *lane["pipe"].result())
 
         def flush(lane):
             if not lane["frames"]:
@@ -469,10 +529,13 @@ class ModelManager:
             for lane in lanes.values():
                 flush(lane)
                 drain(lane, 0)
+                if lane.get("cluster") is not None:
+                    lane["cluster"].finish()
         finally:
             src.release()
             for lane in lanes.values():
                 lane["pipe"].close()
+                self._close_clusterer(lane.get("cluster"))
         out = {}
         for task, lane in lanes.items():
             out[task] = {"detections": lane["out"]}

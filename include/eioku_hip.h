@@ -409,6 +409,45 @@ int eioku_resnet18_classify(eioku_resnet_t* r, const uint8_t* bgr, int n, int h,
                             float* prob_out, int32_t* class_out, float* logits_out, int mem, void* stream);
 int eioku_resnet18_last_flops(const eioku_resnet_t* r, double* flops);
 
+/* ---- face clustering: ArcFace IResNet embeddings + cosine DBSCAN (csrc/faces.hip) ------------------------------------
+ * Fills the cluster_id of ModelManager.detect_faces.  The embedder is insightface arcface_torch's `iresnet` (112 x 112
+ * input, stem conv3x3 + BN + PReLU, four stages 64 / 128 / 256 / 512 each opening with a stride 2, IBasicBlock =
+ * bn1 -> conv3x3 -> bn2 -> PReLU -> conv3x3(stride) -> bn3 + identity or 1x1 / s2 conv + BN, head bn2 -> fc -> features).
+ * depths = blocks per stage ([2,2,2,2] r18, [3,4,14,3] r50, [3,13,30,3] r100).  Convolutions are named as the
+ * state dict's prefixes ("conv1", "layer1.0.conv1", "layer1.0.downsample.0", ...) and take BatchNorm folded in (conv1 <-
+ * bn1, block conv1 <- bn2, conv2 <- bn3, downsample.0 <- downsample.1).  PReLU unit 0 is the stem's, unit 1 + b block
+ * b's; set_bn takes block b's leading bn1 as per-channel (scale, shift).  set_head: bn2, fc and features folded into
+ * weight [512][25088] (columns in NHWC order: (y * 7 + x) * 512 + c) and bias [512].  Boxes: HOST fp32 [m][5] = (frame
+ * slot, x1, y1, x2, y2); the crop is a square of side max(w, h, 1) centred on the box, bilinear to 112 x 112.
+ * fp16 storage, fp32 accumulation.  All calls are synchronous. */
+typedef struct eioku_iresnet eioku_iresnet_t;
+int eioku_iresnet_create(const int* depths, eioku_iresnet_t** out);
+void eioku_iresnet_destroy(eioku_iresnet_t* r);
+int eioku_iresnet_num_convs(const eioku_iresnet_t* r);
+int eioku_iresnet_num_blocks(const eioku_iresnet_t* r);
+int eioku_iresnet_conv_info(const eioku_iresnet_t* r, int idx, char* name, size_t name_cap, int* cout, int* cin, int* ksize,
+                            int* stride);
+int eioku_iresnet_set_conv(eioku_iresnet_t* r, int idx, const float* weight_oihw, const float* bias);
+int eioku_iresnet_set_prelu(eioku_iresnet_t* r, int unit, const float* slope);
+int eioku_iresnet_set_bn(eioku_iresnet_t* r, int block, const float* scale, const float* shift);
+int eioku_iresnet_set_head(eioku_iresnet_t* r, const float* weight, const float* bias);
+/* crop only: out_f16 [m][112][112][8] fp16 (R, G, B as (v / 255 - 0.5) / 0.5, 5 zero channels), DEVICE */
+int eioku_iresnet_crop(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const float* boxes, int m, void* out_f16,
+                       int mem, void* stream);
+/* the raw network on crops (DEVICE, m <= 256) -> emb_out [m][512]; upto_block >= 0: that block's NHWC fp16 output to
+ * act_out instead */
+int eioku_iresnet_forward(eioku_iresnet_t* r, const void* in_f16, int m, int upto_block, void* act_out, float* emb_out,
+                          void* stream);
+/* n BGR frames (host or device) + m boxes -> out [m][512] fp32 unit vectors on the side `mem` names */
+int eioku_iresnet_embed(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const float* boxes, int m, float* out,
+                        int mem, void* stream);
+int eioku_iresnet_last_flops(const eioku_iresnet_t* r, double* flops);
+/* scikit-learn DBSCAN(eps, min_samples, metric="cosine") on unit-norm rows emb [n][d] fp32: j is a neighbour of i iff
+ * 1 - e_i . e_j <= eps (i is its own), core iff >= min_samples neighbours, clusters = components of the core-core graph
+ * numbered by smallest core index, a border point takes the smallest label among its core neighbours, -1 = noise.
+ * n <= 65536, d % 32 == 0, eps in [0, 2], min_samples >= 1; labels_out [n] int32 on the side `mem` names. */
+int eioku_dbscan_cosine(const float* emb, int n, int d, float eps, int min_samples, int32_t* labels_out, int mem, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
