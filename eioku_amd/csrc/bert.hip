@@ -6,14 +6,14 @@
 // (v = hi + lo to 2^-18, round to nearest) and runs a.w ~ a_hi.w_hi + a_lo.w_hi + a_hi.w_lo on the bf16 matrix cores with
 // fp32 accumulation; LayerNorm / softmax / GELU(erf) are fp32.  Embeddings land at 7-10 % of the 1e-4 bar against the
 // float64 oracle (tools/embed_margin.py).  The exact-fp32 kernels stay reachable for the cross-check test
-// (EIOKU_GEMM_BF16=0, EIOKU_GEMM_S=0, EIOKU_ATTN_MFMA=0, EIOKU_ATTN_BF16=0).
+// (EIOKU_GEMM_BF16=0, EIOKU_GEMM_S=0, EIOKU_ATTN_MFMA=0).
 //
 //   k_embed_ln        word + position + token_type(0) embedding gather, LayerNorm -> fp32 x + bf16 hi / lo planes
 //   k_gemm_bf_s       C = A . W^T + bias [, GELU] on split bf16: A and W arrive as planes, 128x128 (M >= 8192) or
 //                     64x64 tiles, 64-deep register-staged stages, XCD-aware tile order, straight-line epilogue that
 //                     writes fp32 or planes
 //   k_attention_bf    per (segment, head), S <= 128: S^T = K Q^T and O^T = V^T P^T on split bf16, softmax in registers
-//   k_attention_mfma / k_attention8 / k_attention   the exact-fp32 and longer-sequence variants
+//   k_attention8 / k_attention   the exact-fp32 route (EIOKU_ATTN_MFMA=0) and the longer-sequence variants
 //   k_add_ln_fixed    LayerNorm(sum of split-K planes + bias + residual) -> fp32 x + planes
 //   k_pool_norm       attention-mask weighted mean over tokens, then x / max(|x|, 1e-12)
 //   k_gemm_f32*       exact-fp32 MFMA GEMMs (v_mfma_f32_32x32x2_f32): the fallback route
@@ -316,133 +316,14 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f32(const float* __restrict__ A
 // attention: grid (B, heads), PARTS lanes per query (each owns the keys j = part mod PARTS), block =
 // PARTS*S threads rounded to 64, head_dim == 32.  qkv: [B*S][3H] = Q | K | V; ctx: [B*S][H]
 // ---------------------------------------------------------------------------------------------
-// S <= 128: the whole (segment, head) on the exact-fp32 matrix core, one workgroup of 4 waves x 32 queries.
-// The scores are computed TRANSPOSED, S^T = K . Q^T (v_mfma_f32_32x32x2_f32: A = 32 keys x 2 dims, B = 2 dims x 32
-// queries), so that a lane ends up with one query (its column) and 64 of that query's 128 keys in its accumulator
-// registers, the other 64 in lane ^ 32: the softmax reductions are in-register plus ONE cross-lane exchange.  And
-// the accumulator registers are then already the B operand of O^T = V^T . P^T -- the k axis of an MFMA may be
-// summed in any order, so step r pairs exactly the two keys that register r holds in the two half-waves: no
-// transposition, no LDS round trip for P.  128 MFMAs per wave instead of ~12 k scalar FMAs per lane: 21 -> ~8 us.
-// Q / K columns are XOR-swizzled by the row in LDS (a column read is then conflict-free); rows >= S are zero, mask 0.
-__global__ __launch_bounds__(256) void k_attention_mfma(const float* __restrict__ qkv, const uint8_t* __restrict__ mask, int S,
-                                                        int H, float* __restrict__ ctx, unsigned short* __restrict__ chi,
-                                                        unsigned short* __restrict__ clo) {
-  constexpr int SP = 128, QS = 32;
-  __shared__ __attribute__((aligned(16))) float sQ[SP * QS];
-  __shared__ __attribute__((aligned(16))) float sK[SP * QS];
-  __shared__ float sV[SP * 32];
-  __shared__ float sM[SP];
-  const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const size_t row0 = (size_t)b * S;
-  for (int i0 = 0; i0 < SP * 8; i0 += 4 * 256) {
-    f32x4 qq[4], kk[4], vv[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int i = i0 + t * 256 + tid;
-      const int j = (i >> 3) < S ? (i >> 3) : S - 1;
-      const float* base = qkv + (row0 + j) * (size_t)(3 * H) + h * 32 + (i & 7) * 4;
-      qq[t] = *reinterpret_cast<const f32x4*>(base);
-      kk[t] = *reinterpret_cast<const f32x4*>(base + H);
-      vv[t] = *reinterpret_cast<const f32x4*>(base + 2 * H);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int i = i0 + t * 256 + tid;
-      const int j = i >> 3, u = i & 7;
-      const bool in = j < S;
-      // element (j, d) of Q / K lives at column d ^ (j & 31): a column read over 32 consecutive rows then touches 32
-      // different banks, and an aligned group of 4 dims stays one (permuted) 16-byte store
-      const int pj = j & 3, gu = (u ^ ((j >> 2) & 7)) * 4;
-      f32x4 qp, kp;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        qp[e] = in ? qq[t][e ^ pj] : 0.f;
-        kp[e] = in ? kk[t][e ^ pj] : 0.f;
-      }
-      *reinterpret_cast<f32x4*>(&sQ[j * QS + gu]) = qp;
-      *reinterpret_cast<f32x4*>(&sK[j * QS + gu]) = kp;
-      *reinterpret_cast<f32x4*>(&sV[j * 32 + u * 4]) = in ? vv[t] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  for (int j = tid; j < SP; j += 256) sM[j] = (j < S && mask[row0 + j]) ? 1.f : 0.f;
-  __syncthreads();
-  const int c = lane & 31, half = lane >> 5, q0 = wave * 32;
-  if (q0 >= S) return;  // a whole wave of padding queries (no barrier below)
-  float bq[16];
-#pragma unroll
-  for (int t = 0; t < 16; ++t) bq[t] = sQ[(q0 + c) * QS + ((2 * t + half) ^ c)];  // (q0 + c) & 31 == c
-  f32x16 sc[4];
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sc[kt][r] = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-      sc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[(kt * 32 + c) * QS + ((2 * t + half) ^ c)], bq[t], sc[kt], 0, 0, 0);
-  }
-  // sc[kt][r] = <k_key, q_query>, key = kt*32 + (r & 3) + 8*(r >> 2) + 4*half, query = q0 + c
-  const float rinv = 0.17677669529663687f;  // 1 / sqrt(32)
-  float mx = -INFINITY;
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      const float s = sM[key] != 0.f ? sc[kt][r] * rinv : -INFINITY;
-      sc[kt][r] = s;
-      mx = fmaxf(mx, s);
-    }
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float l = 0.f;
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float e = sc[kt][r] != -INFINITY ? expf(sc[kt][r] - mx) : 0.f;
-      sc[kt][r] = e;
-      l += e;
-    }
-  l += __shfl_xor(l, 32, 64);
-  f32x16 o;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) o[r] = 0.f;
-#pragma unroll
-  for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      o = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[key * 32 + c], sc[kt][r], o, 0, 0, 0);
-    }
-  // o[r] = O[query][dim], dim = (r & 3) + 8*(r >> 2) + 4*half
-  const int qi = q0 + c;
-  if (qi >= S) return;
-  const float rl = l > 0.f ? 1.0f / l : 0.f;  // fully masked segment -> zeros (its pooled vector is 0 anyway)
-  const size_t o0 = (row0 + qi) * (size_t)H + h * 32;
-  if (chi) {  // the out-projection GEMM is the only reader: hand it the two bf16 terms instead of fp32 (same bytes)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      unsigned h0, l0, h1, l1;
-      split_bf16_pair(o[4 * g] * rl, o[4 * g + 1] * rl, h0, l0);
-      split_bf16_pair(o[4 * g + 2] * rl, o[4 * g + 3] * rl, h1, l1);
-      *reinterpret_cast<u32x2b*>(chi + o0 + 8 * g + 4 * half) = u32x2b{h0, h1};
-      *reinterpret_cast<u32x2b*>(clo + o0 + 8 * g + 4 * half) = u32x2b{l0, l1};
-    }
-    return;
-  }
-  float* op = ctx + o0;
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-    *reinterpret_cast<f32x4*>(op + 8 * g + 4 * half) = f32x4{o[4 * g] * rl, o[4 * g + 1] * rl, o[4 * g + 2] * rl, o[4 * g + 3] * rl};
-}
-
-// r3: the same (segment, head) attention on split bf16 (v = hi + lo, three product terms, fp32 accumulate - the GEMMs'
-// scheme).  The fp32 matrix pipe (64 cycles per 32x32x2 step) made k_attention_mfma matrix-bound: 8192 MFMA cycles per
-// wave; here QK^T and PV are 24 + 24 v_mfma_f32_32x32x16_bf16 = 1536 cycles.  Same structure: scores transposed
-// (S^T = K Q^T), so a lane owns one query and the softmax is in-register plus one cross-lane exchange, and the
-// accumulator registers of a key tile are, eight at a time, the B operand of O^T = V^T P^T: registers 8g..8g+7 of the two
-// half-waves hold the 16 keys 16g..16g+15 of the tile, and V^T sits in LDS with its keys in exactly that order, so that a
-// lane's A operand is one 16-byte read.  LDS: Q / K rows of 64 B (4 slots, slot ^= (row >> 2) & 3), V^T rows of 256 B
-// (16 slots, slot ^= dim & 15): every ds_read_b128 lane group touches 16 different bank quads.
+// S <= 128: the whole (segment, head) in one workgroup of 4 waves x 32 queries, on split bf16 (v = hi + lo, three
+// product terms, fp32 accumulate - the GEMMs' scheme).  QK^T and PV are 24 + 24 v_mfma_f32_32x32x16_bf16 = 1536 cycles
+// per wave (r3; the exact-fp32 matrix pipe, 64 cycles per 32x32x2 step, needed 8192).  The scores are computed
+// TRANSPOSED (S^T = K Q^T), so a lane owns one query and the softmax is in-register plus one cross-lane exchange, and
+// the accumulator registers of a key tile are, eight at a time, the B operand of O^T = V^T P^T: registers 8g..8g+7 of
+// the two half-waves hold the 16 keys 16g..16g+15 of the tile, and V^T sits in LDS with its keys in exactly that order,
+// so that a lane's A operand is one 16-byte read.  LDS: Q / K rows of 64 B (4 slots, slot ^= (row >> 2) & 3), V^T rows
+// of 256 B (16 slots, slot ^= dim & 15): every ds_read_b128 lane group touches 16 different bank quads.
 __global__ __launch_bounds__(256) void k_attention_bf(const float* __restrict__ qkv, const uint8_t* __restrict__ mask, int S,
                                                       int H, float* __restrict__ ctx, unsigned short* __restrict__ chi,
                                                       unsigned short* __restrict__ clo) {
@@ -1216,13 +1097,18 @@ struct Planes {  // an activation tensor as its two bf16 terms, [rows][ld] each
   unsigned short* lo = nullptr;
 };
 
-bool env_on(const char* name) { return !(getenv(name) && atoi(getenv(name)) == 0); }
+// EIOKU_GEMM_S=0 / EIOKU_GEMM_BF16=0: the exact-fp32 GEMM kernels instead of the split-bf16 k_gemm_bf_s
+bool gemm_s_on() {
+  static const bool on = !env_off("EIOKU_GEMM_S");
+  return on;
+}
+bool gemm_bf16_on() {
+  static const bool on = !env_off("EIOKU_GEMM_BF16");
+  return on;
+}
 
 // true when gemm() runs this shape on k_gemm_bf_s with pre-split weights: the kernels that take / write planes
-bool gemm_takes_planes(int K, int splits) {
-  static const bool on = env_on("EIOKU_GEMM_BF16") && env_on("EIOKU_GEMM_S");
-  return on && K % (128 * splits) == 0;
-}
+bool gemm_takes_planes(int K, int splits) { return gemm_bf16_on() && gemm_s_on() && K % (128 * splits) == 0; }
 
 template <int EPI, int WMT, int WNT, bool AS, int WGM = 2>
 void launch_bf64(dim3 grid, size_t lds, hipStream_t stream, const float* A, int lda, const float* W, const unsigned short* whi,
@@ -1248,8 +1134,8 @@ int gemm(const float* A, int lda, const float* W, const float* bias, float* C, i
   EIOKU_REQUIRE(splits >= 1 && (K / kBK) % splits == 0 && (splits == 1 || epi == 0), "bad split-K %d", splits);
   const int kchunks = K / kBK / splits;
   if (splits > 1) bias = nullptr;
-  const bool s_route = K % (128 * splits) == 0 && env_on("EIOKU_GEMM_S");
-  const bool bf = env_on("EIOKU_GEMM_BF16");
+  const bool s_route = K % (128 * splits) == 0 && gemm_s_on();
+  const bool bf = gemm_bf16_on();
   const unsigned short* whi = ws ? ws->hi : nullptr;
   const unsigned short* wlo = ws ? ws->lo : nullptr;
   EIOKU_REQUIRE(!(ap || cp) || (s_route && bf && whi && (!cp || splits == 1)), "planes on a GEMM route that has none");
@@ -1471,7 +1357,7 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
   const int sp_o = pick_splits(T, H, H), sp_f = pick_splits(T, H, m->ffn);
   // EIOKU_GEMM_PLANES=0: activations stay fp32 and the GEMMs split them in their staging threads (the r2 route; same
   // function of the same values, so the embeddings must be the same bytes: tests/test_bert_gpu.py)
-  static const bool planes_on = env_on("EIOKU_GEMM_PLANES");
+  static const bool planes_on = !env_off("EIOKU_GEMM_PLANES");
   const bool planes = planes_on && gemm_takes_planes(H, 1) && gemm_takes_planes(H, sp_o) && gemm_takes_planes(m->ffn, sp_f);
   if ((rc = grow(&m->x, &m->x_cap, (size_t)T * H * 4))) return rc;
   if ((rc = grow(&m->y, &m->y_cap, (size_t)kMaxSplit * T * H * 4))) return rc;
@@ -1487,7 +1373,8 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
   } else {
     if ((rc = grow(&m->mid, &m->mid_cap, (size_t)T * m->ffn * 4))) return rc;
   }
-  const bool amfma = env_on("EIOKU_ATTN_MFMA") && S <= 128 && H == m->heads * 32;
+  static const bool amfma_on = !env_off("EIOKU_ATTN_MFMA");
+  const bool amfma = amfma_on && S <= 128 && H == m->heads * 32;
   // the other attention kernels write fp32 ctx (split afterwards by k_split_planes when the GEMMs take planes)
   if (!planes || !amfma)
     if ((rc = grow(&m->ctx, &m->ctx_cap, (size_t)T * H * 4))) return rc;
@@ -1517,11 +1404,8 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
     const std::string p = "encoder.layer." + std::to_string(l) + ".";
     if ((rc = gemm(m->x, H, tp(m, p + "attention.self.query.weight"), tp(m, p + "attention.self.query.bias"), m->qkv,
                    3 * H, T, 3 * H, H, 0, 1, stream, &m->wsplit[(size_t)4 * l + 0], xa))) return rc;
-    static const bool abf = env_on("EIOKU_ATTN_BF16");  // 0: the exact-fp32 matrix pipe (k_attention_mfma)
-    if (amfma && abf) {
+    if (amfma) {
       hipLaunchKernelGGL(k_attention_bf, dim3(B, m->heads), dim3(256), 0, stream, m->qkv, d_mask, S, H, m->ctx, cP.hi, cP.lo);
-    } else if (amfma) {
-      hipLaunchKernelGGL(k_attention_mfma, dim3(B, m->heads), dim3(256), 0, stream, m->qkv, d_mask, S, H, m->ctx, cP.hi, cP.lo);
     } else {
       if (parts == 4)
         hipLaunchKernelGGL(k_attention8, dim3(B, m->heads, qsplit), dim3(256), alds, stream, m->qkv, d_mask, S, H, m->ctx);

@@ -26,6 +26,12 @@ void prof_start(int tag, hipStream_t stream);
 void prof_stop(int tag, hipStream_t stream);
 bool prof_enabled();
 
+// Environment switches ("r3 — switches").  env_off(X): X is set to a value atoi() reads as 0 -- the one form
+// of an off switch; env_num(X, d): X as a number, d when unset.  Callers keep the result in a function-local static:
+// every switch is read once per process.
+bool env_off(const char* name);
+double env_num(const char* name, double dflt);
+
 }  // namespace eioku
 
 #define EIOKU_HIP_CHECK(expr)                                                                  \

@@ -73,7 +73,7 @@ int conv_forward(const ConvWeights& cw, Slice in, int N, int H, int W, Slice out
 // Two chained 3x3 stride-1 layers with 16 / 32 channels (a C2f Bottleneck) as one launch: out = act_b(B(act_a(A(in))))
 // [+ in when `residual`]; the intermediate tensor stays in LDS.  Bit-identical to the two separate launches.
 bool conv_chain_ok(const ConvWeights& a, const ConvWeights& b);
-// `cat_w` (conv_chain_cat_ok: the 16-channel C2f with one Bottleneck): the C2f's closing 1x1 over the concat runs in
+// `cat_w` (conv_chain_cat_ok: YOLOv8n's shallow C2fs with one Bottleneck): the C2f's closing 1x1 over the concat runs in
 // the same launch; `cat_in` = the concat buffer (its leading chunks are read from memory, the Bottleneck's output
 // stays on chip and `out` may be empty), `cat_out` = the 1x1's output slice.
 bool conv_chain_cat_ok(const ConvWeights& a, const ConvWeights& b, const ConvWeights& c2);

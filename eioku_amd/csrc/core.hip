@@ -1,6 +1,7 @@
 // Lifecycle, error reporting and scratch memory of libeioku_hip.so.
 #include "common.h"
 
+#include <cstdlib>
 #include <string>
 #include <utility>
 #include <vector>
@@ -46,6 +47,16 @@ void set_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+bool env_off(const char* name) {
+  const char* v = getenv(name);
+  return v && atoi(v) == 0;
+}
+
+double env_num(const char* name, double dflt) {
+  const char* v = getenv(name);
+  return v ? atof(v) : dflt;
 }
 
 bool initialised() { return g_init; }

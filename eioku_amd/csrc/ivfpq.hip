@@ -813,7 +813,6 @@ struct LScanArgs {
   unsigned* wl;               // [gridDim.x][wl_cap][2]  (slot, code position)
   int* wl_cnt;                // [gridDim.x]
   int wl_cap;
-  int ablate;                 // measurement builds only (EIOKU_LSCAN_ABLATE): 1 = no table gathers, 2 = no products
 };
 
 // NS = d / 16 k-steps (dsub = 8: m = 2 NS); NW waves x RT 32-code tiles per workgroup and work item
@@ -893,7 +892,7 @@ __global__ __launch_bounds__(NW * 64) void k_lscan(LScanArgs a) {
       hxmin[i] = h;
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        const unsigned byte = (a.ablate & 1) ? (unsigned)col : (cw[s >> 1] >> (16 * (s & 1) + 8 * half)) & 0xFFu;
+        const unsigned byte = (cw[s >> 1] >> (16 * (s & 1) + 8 * half)) & 0xFFu;
         xh[i][s] = a.pqh[(2 * s + half) * 256 + byte];
       }
     }
@@ -924,7 +923,6 @@ __global__ __launch_bounds__(NW * 64) void k_lscan(LScanArgs a) {
       u32x4k bh[PF];
 #pragma unroll
       for (int s = 0; s < PF; ++s) bh[s] = qb[s * 64 + lane];
-      if (!(a.ablate & 2)) {
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         const bf16x8 ch = __builtin_bit_cast(bf16x8, bh[s % PF]);
@@ -932,10 +930,6 @@ __global__ __launch_bounds__(NW * 64) void k_lscan(LScanArgs a) {
         for (int i = 0; i < RT; ++i)
           acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, xh[i][s]), ch, acc[i], 0, 0, 0);
         if (s + PF < NS) bh[s % PF] = qb[(s + PF) * 64 + lane];
-      }
-      } else {
-#pragma unroll
-        for (int i = 0; i < RT; ++i) acc[i][0] = __uint_as_float(xh[i][0][0] ^ xh[i][NS - 1][3] ^ bh[0][0]);
       }
       // filter (as k_l2_scan): tile maximum against the tile's smallest hx first, per row only where that passes
 #pragma unroll
@@ -1169,11 +1163,9 @@ __global__ __launch_bounds__(64) void k_probe_merge(const float* __restrict__ pd
   }
 }
 
-constexpr int kLRT = 2;  // 32-code tiles per wave; a work item = NW x RT x 32 codes
-inline int lscan_nw() {  // waves per workgroup: 8 (one workgroup per CU) or 4 (two: one's operand gathers beside the other's products)
-  static const int nw = getenv("EIOKU_LSCAN_NW") ? atoi(getenv("EIOKU_LSCAN_NW")) : 8;
-  return nw == 4 ? 4 : 8;
-}
+// workgroup = 8 waves x 2 tiles = 512 codes per work item, one workgroup per CU (r3: two 4-wave workgroups per CU
+// were measured and not kept)
+constexpr int kLNW = 8, kLRT = 2, kLSeg = kLNW * kLRT * 32;
 
 inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -1189,9 +1181,8 @@ LWork lwork(int nq, int d, int nprobe, int nlist, int k, int cap, long long ntot
   w.K = k <= 16 ? 16 : 32;
   w.cap = cap;
   w.nslots = (int)(npairs + 31 * (npairs < (size_t)nlist ? npairs : (size_t)nlist));
-  w.grid = num_cus() * (8 / lscan_nw());
-  const int seg = lscan_nw() * kLRT * 32;
-  w.max_items = (int)(ntotal / seg + nlist);  // sum over lists of ceil(size / seg)
+  w.grid = num_cus();
+  w.max_items = (int)(ntotal / kLSeg + nlist);  // sum over lists of ceil(size / kLSeg)
   long long wl_cap = ((64ll << 20) / 8) / w.grid;
   if (cap < 64) wl_cap = cap;  // tests shrink both kinds of list to force the overflow path
   w.wl_cap = (int)wl_cap;
@@ -1223,21 +1214,17 @@ LWork lwork(int nq, int d, int nprobe, int nlist, int k, int cap, long long ntot
   return w;
 }
 
-template <int NS, int NW>
-int launch_lscan1(const LScanArgs& a, int grid, hipStream_t stream) {
-  const size_t lds = (size_t)2 * NS * 64 * 16 + (size_t)NW * kLRT * 32 * 4 + 16;
-  static bool attr = false;
-  if (!attr) {
-    EIOKU_HIP_CHECK(hipFuncSetAttribute((const void*)k_lscan<NS, NW, kLRT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = true;
-  }
-  hipLaunchKernelGGL((k_lscan<NS, NW, kLRT>), dim3((unsigned)grid), dim3(NW * 64), lds, stream, a);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
-}
 template <int NS>
 int launch_lscan(const LScanArgs& a, int grid, hipStream_t stream) {
-  return lscan_nw() == 4 ? launch_lscan1<NS, 4>(a, grid, stream) : launch_lscan1<NS, 8>(a, grid, stream);
+  const size_t lds = (size_t)2 * NS * 64 * 16 + (size_t)kLSeg * 4 + 16;
+  static bool attr = false;
+  if (!attr) {
+    EIOKU_HIP_CHECK(hipFuncSetAttribute((const void*)k_lscan<NS, kLNW, kLRT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
+  hipLaunchKernelGGL((k_lscan<NS, kLNW, kLRT>), dim3((unsigned)grid), dim3(kLNW * 64), lds, stream, a);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
 }
 
 bool lists_geometry_ok(int d, int m) { return m * 8 == d && (d == 64 || d == 128 || d == 256 || d == 384); }
@@ -1330,18 +1317,17 @@ int eioku_ivfpq_search_lists(const float* q_dev, int nq, int d, int m, const lon
                      tprobe);
   // ... of its first kTauRows rows: the k-th best of ANY k codes is a bound, and the whole list (9.9 k rows on average at
   // 10 M rows) cost 0.30 ms per search for a bound that left 35 candidates per query; 1024 rows: see DESIGN.md
-  static const int tau_rows = getenv("EIOKU_LSCAN_TAU_ROWS") ? atoi(getenv("EIOKU_LSCAN_TAU_ROWS")) : 1024;
+  static const int tau_rows = (int)env_num("EIOKU_LSCAN_TAU_ROWS", 1024);
   int rc = scan_launch(q_dev, nq, d, m, tprobe, 1, coarse_dev, pq_dev, offsets_dev, sizes_dev, list_codes_dev,
                        list_ids_dev, k, pd, pi, list_tables_dev, query_tables_dev, stream_, 1, nullptr,
                        tau_rows > k ? tau_rows : k);
   if (rc) return rc;
   hipLaunchKernelGGL(k_lq_fill, dim3((unsigned)std::min(1024, (w.nslots + 255) / 256)), dim3(256), 0, stream, lq_q, lq_thr, w.nslots);
   hipLaunchKernelGGL(k_inv_count, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, probes_dev, npairs, sizes_dev, lcnt);
-  const int seg = lscan_nw() * kLRT * 32;
   int4* items = (int4*)(ws + w.items);
-  hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, stream, lcnt, sizes_dev, nlist, seg, loff, woff, cursor, nwork);
+  hipLaunchKernelGGL(k_inv_scan, dim3(1), dim3(1024), 0, stream, lcnt, sizes_dev, nlist, kLSeg, loff, woff, cursor, nwork);
   hipLaunchKernelGGL(k_inv_items, dim3((unsigned)((w.max_items + 255) / 256)), dim3(256), 0, stream, woff, loff, offsets_dev,
-                     sizes_dev, nlist, seg, w.max_items, items);
+                     sizes_dev, nlist, kLSeg, w.max_items, items);
   hipLaunchKernelGGL(k_inv_scatter, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, probes_dev, npairs, nprobe,
                      sizes_dev, loff, cursor, t1, pd, w.K, k, qn, pmax2_dev, lq_q, lq_p, lq_thr);
   EIOKU_LAUNCH_CHECK();
@@ -1357,8 +1343,6 @@ int eioku_ivfpq_search_lists(const float* q_dev, int nq, int d, int m, const lon
   a.wl = wl;
   a.wl_cnt = wl_cnt;
   a.wl_cap = w.wl_cap;
-  static const int ablate = getenv("EIOKU_LSCAN_ABLATE") ? atoi(getenv("EIOKU_LSCAN_ABLATE")) : 0;
-  a.ablate = ablate;
   prof_start(EIOKU_PROF_IVFPQ, stream);
   switch (d / 16) {
     case 4: rc = launch_lscan<4>(a, w.grid, stream); break;

@@ -360,6 +360,8 @@ int record_pass_rate(eioku_yolo* y, int n, int A, hipStream_t stream) {
 
 int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedInput* fused, double* flops_out,
             bool clsmax = false, bool lazybox = false, bool lazydeep = false) {
+  // EIOKU_UP_FUSE=0: upsample2x writes the upsampled tensor and the 1x1 reads it (byte-identity test of the fusion)
+  static const bool up_off = env_off("EIOKU_UP_FUSE");
   double flops = 0;
   bool skip_next = false;
   int pool_skip = 0, front_skip = 0;
@@ -470,7 +472,6 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
         for (int l = 0; l < 3; ++l) skip = skip || oi == y->deep_idx[l][0] || oi == y->deep_idx[l][1];
         if (skip) continue;
       }
-      static const bool up_off = getenv("EIOKU_UP_FUSE") && atoi(getenv("EIOKU_UP_FUSE")) == 0;
       if (op.up_from >= 0 && !up_off && (long long)n * H * W < (1ll << 24)) {
         const Op& uo = y->ops[op.up_from];
         UpSource us{Slice{y->bufs[uo.in_buf].ptr, y->bufs[uo.in_buf].ch, uo.in_off}, uo.in_ch};
@@ -508,9 +509,8 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
       }
     } else {
       const Buf& ob = y->bufs[op.out_buf];
-      static const bool up_off2 = getenv("EIOKU_UP_FUSE") && atoi(getenv("EIOKU_UP_FUSE")) == 0;
       // the consumer's pixel count (4x this op's) decides, exactly as in the conv branch above
-      if (op.up_consumer >= 0 && !up_off2 && (long long)n * H * W * 4 < (1ll << 24)) continue;
+      if (op.up_consumer >= 0 && !up_off && (long long)n * H * W * 4 < (1ll << 24)) continue;
       rc = upsample2x_forward(in, Slice{ob.ptr, ob.ch, op.out_off}, n, H, W, op.in_ch, stream);
     }
     if (rc) return rc;
@@ -713,7 +713,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   }
   FusedInput fi{d_bgr, p.src_h, p.src_w, p.new_h, p.new_w, p.top, p.left, step > 1 ? 0 : p.mode, step, off};
   const Op& op0 = y->ops.front();
-  static const bool no_fuse = getenv("EIOKU_STEM_FUSE") && atoi(getenv("EIOKU_STEM_FUSE")) == 0;
+  static const bool no_fuse = env_off("EIOKU_STEM_FUSE");
   const bool fuse = !no_fuse && op0.kind == kConv && op0.in_buf == y->in_buf && op0.res_buf < 0 && op0.f32_out < 0 &&
                     fused_input_ok(y->weights[op0.conv], fi, Slice{}, nullptr);
   if (!fuse) {
@@ -727,7 +727,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
     if (op.kind == kConv && op.f32_out >= 3) cm = cm && conv_clsmax_ok(y->weights[op.conv], op.act);
   // ... and then only the anchors that pass the threshold need their 64 DFL logits: the box branch's last 1x1 conv
   // is evaluated by decode for those (one 64-row weight tile, whole 32-channel chunks)
-  static const bool lazy_off = getenv("EIOKU_LAZY_BOX") && atoi(getenv("EIOKU_LAZY_BOX")) == 0;
+  static const bool lazy_off = env_off("EIOKU_LAZY_BOX");
   bool lazy = cm && !lazy_off;
   LazyBox lbx{};
   for (const Op& op : y->ops)
@@ -744,7 +744,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   // Deep: with few anchors passing (the usual case at conf >= 0.25) the branch's two 3x3 layers are evaluated only
   // where decode needs them.  Which way to go is decided from the previous call's pass rate (<= 3 %): a wrong guess
   // costs time, never correctness.
-  static const float deep_frac = getenv("EIOKU_LAZY_DEEP_FRAC") ? (float)atof(getenv("EIOKU_LAZY_DEEP_FRAC")) : 0.03f;
+  static const float deep_frac = (float)env_num("EIOKU_LAZY_DEEP_FRAC", 0.03);
   bool deep = lazy && deep_frac > 0.f;
   int Hq[3], Wq[3], Aq = 0;
   for (int l = 0; l < 3; ++l) {

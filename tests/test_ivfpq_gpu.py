@@ -263,8 +263,8 @@ def test_list_major_scan_is_bit_identical_to_query_major(gpu, d, m, nlist, n, nq
 
 
 def test_list_major_results_do_not_depend_on_its_launch_knobs(gpu, tmp_path):
-    """EIOKU_LSCAN_NW (waves per workgroup) and EIOKU_LSCAN_TAU_ROWS (rows of the bound pass) are read once per process:
-    each value in its own process, same index, same queries - distances and ids must be the default's bytes."""
+    """EIOKU_LSCAN_TAU_ROWS (rows of the bound pass) is read once per process: each value in its own process, same
+    index, same queries - distances and ids must be the default's bytes."""
     import os
     import subprocess
     import sys
@@ -285,7 +285,7 @@ def test_list_major_results_do_not_depend_on_its_launch_knobs(gpu, tmp_path):
         "np.savez(sys.argv[1], D=D.cpu().numpy(), I=I.cpu().numpy())\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),)
     outs = {}
-    for name, env in {"default": {}, "nw4": {"EIOKU_LSCAN_NW": "4"}, "tau128": {"EIOKU_LSCAN_TAU_ROWS": "128"},
+    for name, env in {"default": {}, "tau128": {"EIOKU_LSCAN_TAU_ROWS": "128"},
                       "tau8192": {"EIOKU_LSCAN_TAU_ROWS": "8192"}}.items():
         path = tmp_path / f"{name}.npz"
         subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=dict(os.environ, **env), timeout=300)

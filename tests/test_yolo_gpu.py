@@ -301,8 +301,8 @@ def test_detect_fusion_switches_leave_the_detections_byte_identical(gpu, tmp_pat
     """Every detect()-level fusion the library keeps a switch for (each read once per process): the one-launch
     YOLOv8n front end (EIOKU_STEM_CHAIN), the stem reading the BGR frames itself (EIOKU_STEM_FUSE), the class head
     writing {max logit, argmax} words instead of 80 logits (EIOKU_CLSMAX) and the lazily evaluated box branch
-    (EIOKU_LAZY_BOX), plus the XCD-contiguous tile order of the persistent conv kernels (EIOKU_XCD_TILES, r3).  640-wide
-    copy-mode sources so that all of them are eligible; the detections of every variant must be the all-on bytes."""
+    (EIOKU_LAZY_BOX).  640-wide copy-mode sources so that all of them are eligible; the detections of every variant
+    must be the all-on bytes."""
     import os
     import subprocess
     import sys
@@ -323,7 +323,7 @@ def test_detect_fusion_switches_leave_the_detections_byte_identical(gpu, tmp_pat
         "np.savez(sys.argv[1], *out)\n"
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),)
     outs = {}
-    for name in ("all_on", "EIOKU_STEM_CHAIN", "EIOKU_STEM_FUSE", "EIOKU_CLSMAX", "EIOKU_LAZY_BOX", "EIOKU_XCD_TILES"):
+    for name in ("all_on", "EIOKU_STEM_CHAIN", "EIOKU_STEM_FUSE", "EIOKU_CLSMAX", "EIOKU_LAZY_BOX"):
         path = tmp_path / f"dets_{name}.npz"
         env = dict(os.environ) if name == "all_on" else dict(os.environ, **{name: "0"})
         subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=env, timeout=300)
@@ -399,13 +399,6 @@ def test_fused_3x3_1x1_pairs_are_bit_identical_to_separate_launches(gpu, variant
     assert len(outs["1"]) == 6
     for a, b in zip(outs["1"], outs["0"]):
         assert a.dtype == np.float32 and np.array_equal(a, b)
-    # the opt-in register-stationary Bottleneck pairs (k_conv3x3_pair_rs: 64-channel pairs at 40 x 40): same bytes too
-    path = tmp_path / "heads_rs.npz"
-    env = dict(os.environ, EIOKU_CONV_PAIR_RS="1")
-    subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=env, timeout=300)
-    with np.load(path) as z:
-        for k, b in zip(z.files, outs["0"]):
-            assert np.array_equal(z[k], b)
 
 
 @pytest.mark.parametrize("variant,h,w", [("n", 640, 640), ("m", 1080, 1920), ("n", 1080, 1920)])
