@@ -22,6 +22,8 @@ from pathlib import Path
 
 import numpy as np
 
+from ._buffers import is_torch
+
 
 class EndOfStream(RuntimeError):
     """A container's header promised more frames than its stream holds (CAP_PROP_FRAME_COUNT is an estimate)."""
@@ -163,12 +165,14 @@ class Y4mSource(FrameSource):
         raise RuntimeError("y4m sources carry no BGR frames here; use them for scene detection")
 
 
-def bgr_to_luma_bt601(frames_bgr: np.ndarray) -> np.ndarray:
+def bgr_to_luma_bt601(frames_bgr):
     """OpenCV's 8-bit ``COLOR_BGR2YUV_I420`` luma (``RGB2YUV420p``: BT.601 studio range, 20-bit fixed
-    point, ``Y = (269484 R + 528482 G + 102760 B + (16 << 20) + (1 << 19)) >> 20``) [PUBLIC-LIB]."""
-    f = frames_bgr.astype(np.int64)
+    point, ``Y = (269484 R + 528482 G + 102760 B + (16 << 20) + (1 << 19)) >> 20``) [PUBLIC-LIB].
+    ``frames_bgr``: uint8 ndarray or torch tensor; the uint8 luma comes back as the same type, on the same side."""
+    torch_in = is_torch(frames_bgr)
+    f = frames_bgr.long() if torch_in else frames_bgr.astype(np.int64)
     y = (269484 * f[..., 2] + 528482 * f[..., 1] + 102760 * f[..., 0] + (16 << 20) + (1 << 19)) >> 20
-    return y.astype(np.uint8)
+    return y.byte() if torch_in else y.astype(np.uint8)
 
 
 class Cv2FrameSource(FrameSource):

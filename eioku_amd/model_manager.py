@@ -30,6 +30,121 @@ logger = logging.getLogger(__name__)
 
 OUT_OF_SCOPE = "is outside the MI355X hot path (SURVEY.md §8): delegate to the reference ModelManager"
 
+# detection task -> (model_name, confidence_threshold, frame_interval seconds, face): the reference's defaults (:230-232,
+# :324-326), read by detect_objects / detect_faces and analyze_video alike
+_DETECT_DEFAULTS = {"object_detection": ("yolov8n.pt", 0.5, 1, False),
+                    "face_detection": ("yolov8n-face.pt", 0.7, 3, True)}
+
+
+def _detect_settings(task: str, config: dict):
+    model_name, conf, seconds, face = _DETECT_DEFAULTS[task]
+    return (config.get("model_name", model_name), config.get("confidence_threshold", conf),
+            config.get("frame_interval", seconds), face)
+
+
+def _frame_interval(fps, seconds) -> int:
+    """The sampling rule of every frame loop (ref :243 / :337): every ``max(1, int(fps * seconds))``-th frame."""
+    return max(1, int(fps * seconds))
+
+
+def _timestamp_ms(frame_idx: int, fps) -> int:
+    return int((frame_idx / fps) * 1000)
+
+
+def _sampled_batches(cap, fps, interval: int, batch_size: int):
+    """The reference's frame loop, batched: ``read()`` the sampled frames, ``grab()`` the others, stop at the first
+    failure.  Yields ``(meta, frames)`` with ``meta`` the ``(frame_index, timestamp_ms)`` of each frame, a full batch
+    before the next frame is read, then the rest."""
+    meta, frames = [], []
+    frame_idx = 0
+    while True:
+        if frame_idx % interval == 0:
+            ret, frame = cap.read()
+            if not ret:
+                break
+            frames.append(frame)
+            meta.append((frame_idx, _timestamp_ms(frame_idx, fps)))
+            if len(frames) >= batch_size:
+                yield meta, frames
+                meta, frames = [], []
+        elif not cap.grab():
+            break
+        frame_idx += 1
+    if frames:
+        yield meta, frames
+
+
+def _stack_rows(rows):
+    """Device frame rows of the uploaded chunks -> one contiguous batch (a single row: a view, no copy)."""
+    import torch
+
+    return (torch.stack(rows) if len(rows) > 1 else rows[0][None]).contiguous()
+
+
+class _DetectionLane:
+    """One detection task's output, shared by ``detect_objects`` / ``detect_faces`` and ``analyze_video``: batches go in
+    through ``submit``, detection dicts (the reference's float widening, the face path's confidence filter,
+    ``cluster_id``) come out in ``out``.  With a ``PipelinedDetector`` two batches are in flight and results are taken in
+    submission order, so the list is the one the synchronous ``detector.detect`` path produces."""
+
+    def __init__(self, detector, face: bool, conf: float, pipe=None, cluster=None):
+        self.detector, self.pipe = detector, pipe
+        self.face, self.conf, self.names = face, conf, detector.names
+        self.cluster = cluster  # FaceClusterer or None
+        self.metas: list[list[tuple[int, int]]] = []  # the batches in flight, oldest first
+        self.out: list[dict] = []
+
+    def submit(self, meta, frames) -> None:
+        """``frames``: the stacked batch (host ndarray or device tensor), ``meta``: its ``(frame_index, timestamp_ms)``."""
+        if self.pipe is None:
+            self._emit(meta, *self.detector.detect(frames, conf=self.conf), frames)
+            return
+        self.pipe.submit(frames, conf=self.conf)
+        self.metas.append(meta)
+        self._drain(self.pipe.depth - 1)
+
+    def finish(self) -> list[dict]:
+        """Drain every batch in flight, cluster the faces; the detection list."""
+        if self.pipe is not None:
+            self._drain(0)
+        if self.cluster is not None:
+            self.cluster.finish()
+        return self.out
+
+    def close(self) -> None:
+        close = self.pipe.close if self.pipe is not None else getattr(self.detector, "close", None)
+        if close:
+            close()
+        close = getattr(self.cluster.embedder, "close", None) if self.cluster is not None else None
+        if close:
+            close()
+
+    def _drain(self, keep: int) -> None:
+        while self.pipe.in_flight() > keep:  # the clusterer crops the faces from the batch's device copy
+            result = self.pipe.result_with_frames() if self.cluster is not None else self.pipe.result()
+            self._emit(self.metas.pop(0), *result)
+
+    def _emit(self, meta, dets, counts, frames=None) -> None:
+        boxes, batch = [], []
+        for slot, ((frame_idx, timestamp_ms), row, cnt) in enumerate(zip(meta, dets, counts)):
+            for d in row[: int(cnt)]:
+                x1, y1, x2, y2 = (np.float32(d[k]) for k in ("x1", "y1", "x2", "y2"))
+                confidence = float(np.float32(d["conf"]))  # float32 -> Python float, as float(tensor)
+                if self.face and confidence < self.conf:
+                    continue  # the face path's extra safety filter (ref :375-377)
+                det = {"frame_index": frame_idx, "timestamp_ms": timestamp_ms,
+                       "label": "face" if self.face else self.names[int(d["cls"])], "confidence": confidence,
+                       "bbox": {"x": float(x1), "y": float(y1),
+                                "width": float(np.float32(x2 - x1)), "height": float(np.float32(y2 - y1))}}
+                if self.face:
+                    det["cluster_id"] = None
+                    if self.cluster is not None:
+                        boxes.append((slot, x1, y1, x2, y2))
+                        batch.append(det)
+                self.out.append(det)
+        if self.cluster is not None:
+            self.cluster.add(frames, boxes, batch)
+
 
 class ModelManager:
     """Manages model lifecycle and inference for the hot-path task types."""
@@ -158,110 +273,41 @@ class ModelManager:
         return FaceClusterer(embedder, config.get("cluster_eps", self.CLUSTER_EPS),
                              config.get("cluster_min_samples", self.CLUSTER_MIN_SAMPLES))
 
-    @staticmethod
-    def _close_clusterer(cluster):
-        close = getattr(cluster.embedder, "close", None) if cluster is not None else None
-        if close:
-            close()
-
     # ---- objects / faces: one skeleton, as in the reference --------------------------------------------
-    def _detect_loop(self, video_path: str, model_name: str, confidence_threshold: float,
-                     frame_interval_seconds: float, face: bool, cluster=None) -> list[dict]:
-        cap = self._open(video_path)
-        fps = cap.fps or 30
-        total_frames = int(cap.total_frames)
-        logger.info(f"Video FPS: {fps}, Total frames: {total_frames}")
-        frame_interval = max(1, int(fps * frame_interval_seconds))
-        frames_to_process = (total_frames + frame_interval - 1) // frame_interval
-        logger.info(f"Processing every {frame_interval} frames (every {frame_interval_seconds}s at {fps} FPS, "
-                    f"~{frames_to_process} frames to process)")
-        detector = self._load_detector(model_name)
-        names = detector.names
-
-        detections: list[dict] = []
-        pend_frames: list[np.ndarray] = []
-        pend_meta: list[tuple[int, int]] = []
-
-        # Two batches in flight on the HIP path (PipelinedDetector: second handle + stream); results are consumed
-        # in submission order, so the detection list is the one the synchronous loop produces.
-        from .detect import PipelinedDetector, Yolov8Detector
-
-        pipe = (PipelinedDetector(detector, depth=2, streams=self._lanes("face_detection" if face else "object_detection"))
-                if isinstance(detector, Yolov8Detector) else None)
-        metas: list[list[tuple[int, int]]] = []
-
-        def emit(meta, dets, counts, frames=None):
-            boxes, batch = [], []
-            for slot, ((frame_idx, timestamp_ms), row, cnt) in enumerate(zip(meta, dets, counts)):
-                for d in row[: int(cnt)]:
-                    x1, y1, x2, y2 = (np.float32(d[k]) for k in ("x1", "y1", "x2", "y2"))
-                    confidence = float(np.float32(d["conf"]))  # float32 -> Python float, as float(tensor)
-                    if face and confidence < confidence_threshold:
-                        continue  # the face path's extra safety filter (ref :375-377)
-                    det = {
-                        "frame_index": frame_idx,
-                        "timestamp_ms": timestamp_ms,
-                        "label": "face" if face else names[int(d["cls"])],
-                        "confidence": confidence,
-                        "bbox": {"x": float(x1), "y": float(y1),
-                                 "width": float(np.float32(x2 - x1)), "height": float(np.float32(y2 - y1))},
-                    }
-                    if face:
-                        det["cluster_id"] = None
-                        if cluster is not None:
-                            boxes.append((slot, x1, y1, x2, y2))
-                            batch.append(det)
-                    detections.append(det)
-            if cluster is not None:
-                cluster.add(frames, boxes, batch)
-
-        def drain(keep: int):
-            while pipe is not None and pipe.in_flight() > keep:
-                if cluster is not None:
-                    dets, counts, frames = pipe.result_with_frames()
-                    emit(metas.pop(0), dets, counts, frames)
-                else:
-                    emit(metas.pop(0), *pipe.result())
-
-        def flush():
-            if not pend_frames:
-                return
-            batch = np.stack(pend_frames)
-            if pipe is None:
-                emit(list(pend_meta), *detector.detect(batch, conf=confidence_threshold), batch)
-            else:
-                pipe.submit(batch, conf=confidence_threshold)
-                metas.append(list(pend_meta))
-                drain(pipe.depth - 1)
-            pend_frames.clear()
-            pend_meta.clear()
-
-        frame_idx = 0
+    def _detect_loop(self, task: str, video_path: str, config: dict) -> dict:
+        what = "Face detection" if task == "face_detection" else "Object detection"
         try:
-            while True:
-                if frame_idx % frame_interval == 0:
-                    ret, frame = cap.read()
-                    if not ret:
-                        break
-                    pend_frames.append(frame)
-                    pend_meta.append((frame_idx, int((frame_idx / fps) * 1000)))
-                    if len(pend_frames) >= self._batch_size:
-                        flush()
-                else:
-                    if not cap.grab():
-                        break
-                frame_idx += 1
-            flush()
-            drain(0)
-            if cluster is not None:
-                cluster.finish()
-        finally:
-            cap.release()
-            close = pipe.close if pipe is not None else getattr(detector, "close", None)
-            if close:
-                close()
-            self._close_clusterer(cluster)
-        return detections
+            model_name, confidence_threshold, frame_interval_seconds, face = _detect_settings(task, config)
+            logger.info(f"{what}: {video_path} (device: {self._get_device()})")
+            cluster = self._face_clusterer(config) if face else None
+            cap = self._open(video_path)
+            fps = cap.fps or 30
+            total_frames = int(cap.total_frames)
+            logger.info(f"Video FPS: {fps}, Total frames: {total_frames}")
+            frame_interval = _frame_interval(fps, frame_interval_seconds)
+            frames_to_process = (total_frames + frame_interval - 1) // frame_interval
+            logger.info(f"Processing every {frame_interval} frames (every {frame_interval_seconds}s at {fps} FPS, "
+                        f"~{frames_to_process} frames to process)")
+            detector = self._load_detector(model_name)
+
+            # Two batches in flight on the HIP path (PipelinedDetector: second handle + stream); test stubs run synchronously
+            from .detect import PipelinedDetector, Yolov8Detector
+
+            pipe = (PipelinedDetector(detector, depth=2, streams=self._lanes(task))
+                    if isinstance(detector, Yolov8Detector) else None)
+            lane = _DetectionLane(detector, face, confidence_threshold, pipe, cluster)
+            try:
+                for meta, frames in _sampled_batches(cap, fps, frame_interval, self._batch_size):
+                    lane.submit(meta, np.stack(frames))
+                detections = lane.finish()
+            finally:
+                cap.release()
+                lane.close()
+            logger.info(f"✅ {what} complete: {len(detections)} detections")
+            return {"detections": detections}
+        except Exception as e:
+            logger.error(f"{what} failed: {e}", exc_info=True)
+            raise
 
     # ---- places: Places365 ResNet18 (reference :560-713) ---------------------------------------------------
     def _load_place_classifier(self):
@@ -285,42 +331,19 @@ class ModelManager:
             total_frames = int(cap.total_frames)
             frame_interval_seconds = config.get("frame_interval", 1)
             top_k = config.get("top_k", 5)
-            frame_interval = max(1, int(fps * frame_interval_seconds))
+            frame_interval = _frame_interval(fps, frame_interval_seconds)
             frames_to_process = (total_frames + frame_interval - 1) // frame_interval
             logger.info(f"Video FPS: {fps}, Total frames: {total_frames}, Processing every {frame_interval} frames "
                         f"(every {frame_interval_seconds}s, ~{frames_to_process} frames to process)")
             classifications: list[dict] = []
-            pend_frames: list[np.ndarray] = []
-            pend_meta: list[tuple[int, int]] = []
-
-            def flush():
-                if not pend_frames:
-                    return
-                probs, idx = classifier.classify(np.stack(pend_frames), top_k)
-                for (frame_idx, timestamp_ms), p, i in zip(pend_meta, probs, idx):
-                    # `for j, i in enumerate(idx[:top_k])`: float(probs[j]) widens the float32 (ref :677-683)
-                    classifications.append({"frame_index": frame_idx, "timestamp_ms": timestamp_ms,
-                                            "predictions": [{"label": classes[int(c)], "confidence": float(np.float32(v))}
-                                                            for v, c in zip(p, i)]})
-                pend_frames.clear()
-                pend_meta.clear()
-
-            frame_idx = 0
             try:
-                while True:
-                    if frame_idx % frame_interval == 0:
-                        ret, frame = cap.read()
-                        if not ret:
-                            break
-                        pend_frames.append(frame)
-                        pend_meta.append((frame_idx, int((frame_idx / fps) * 1000)))
-                        if len(pend_frames) >= self._batch_size:
-                            flush()
-                    else:
-                        if not cap.grab():
-                            break
-                    frame_idx += 1
-                flush()
+                for meta, frames in _sampled_batches(cap, fps, frame_interval, self._batch_size):
+                    probs, idx = classifier.classify(np.stack(frames), top_k)
+                    for (frame_idx, timestamp_ms), p, i in zip(meta, probs, idx):
+                        # `for j, i in enumerate(idx[:top_k])`: float(probs[j]) widens the float32 (ref :677-683)
+                        classifications.append({"frame_index": frame_idx, "timestamp_ms": timestamp_ms,
+                                                "predictions": [{"label": classes[int(c)], "confidence": float(np.float32(v))}
+                                                                for v, c in zip(p, i)]})
             finally:
                 cap.release()
                 close = getattr(classifier, "close", None)
@@ -334,36 +357,14 @@ class ModelManager:
 
     async def detect_objects(self, video_path: str, config: dict) -> dict:
         """Detect objects in video using YOLOv8 on the HIP path (reference: :215-306)."""
-        try:
-            model_name = config.get("model_name", "yolov8n.pt")
-            confidence_threshold = config.get("confidence_threshold", 0.5)
-            frame_interval_seconds = config.get("frame_interval", 1)
-            logger.info(f"Object detection: {video_path} (device: {self._get_device()})")
-            detections = self._detect_loop(video_path, model_name, confidence_threshold, frame_interval_seconds, False)
-            logger.info(f"✅ Object detection complete: {len(detections)} detections")
-            return {"detections": detections}
-        except Exception as e:
-            logger.error(f"Object detection failed: {e}", exc_info=True)
-            raise
+        return self._detect_loop("object_detection", video_path, config)
 
     async def detect_faces(self, video_path: str, config: dict) -> dict:
         """Detect faces in video using YOLOv8-face on the HIP path (reference: :308-407).  With
         ``config["cluster_faces"]`` every face that passes the confidence filter is embedded (ArcFace IResNet,
         ``face_embedding_model`` under ``<cache>/insightface/``) and the video's faces are clustered once by cosine DBSCAN
         (``cluster_eps``, ``cluster_min_samples``): ``cluster_id`` = ``face_cluster_001``, ... or None for noise."""
-        try:
-            model_name = config.get("model_name", "yolov8n-face.pt")
-            confidence_threshold = config.get("confidence_threshold", 0.7)
-            frame_interval_seconds = config.get("frame_interval", 3)
-            logger.info(f"Face detection: {video_path} (device: {self._get_device()})")
-            cluster = self._face_clusterer(config)
-            detections = self._detect_loop(video_path, model_name, confidence_threshold, frame_interval_seconds, True,
-                                           cluster)
-            logger.info(f"✅ Face detection complete: {len(detections)} detections")
-            return {"detections": detections}
-        except Exception as e:
-            logger.error(f"Face detection failed: {e}", exc_info=True)
-            raise
+        return self._detect_loop("face_detection", video_path, config)
 
     # ---- single pass: one decode, one upload, three stages (SURVEY.md 8f rank 1) ------------------------------
     async def analyze_video(self, video_path: str, configs: dict) -> dict:
@@ -386,6 +387,7 @@ class ModelManager:
 
         from . import scene
         from .detect import PipelinedDetector
+        from .frames import bgr_to_luma_bt601
 
         unknown = set(configs) - {"scene_detection", "object_detection", "face_detection", "decode"}
         if unknown:
@@ -404,63 +406,23 @@ class ModelManager:
         if getattr(src, "yuv_layout", None) is None and hasattr(src, "try_yuv") and configs.get("decode", {}).get("planes", True):
             src.try_yuv()
         yuv = getattr(src, "yuv_layout", None)
-        lanes = {}  # task -> detection lane state
-        for task, face, dflt_model, dflt_conf, dflt_sec in (("object_detection", False, "yolov8n.pt", 0.5, 1),
-                                                            ("face_detection", True, "yolov8n-face.pt", 0.7, 3)):
+        lanes = {}  # task -> (lane, sampling interval, meta and device frame rows of the batch being gathered)
+        for task in _DETECT_DEFAULTS:
             if task not in configs:
                 continue
             cfg = configs[task] or {}
-            detector = self._load_detector(cfg.get("model_name", dflt_model))
-            lanes[task] = {"face": face, "conf": cfg.get("confidence_threshold", dflt_conf),
-                           "interval": max(1, int(fps * cfg.get("frame_interval", dflt_sec))), "names": detector.names,
-                           "pipe": PipelinedDetector(detector, depth=2, streams=self._lanes(task)), "frames": [], "meta": [],
-                           "metas": [], "out": [], "cluster": self._face_clusterer(cfg) if face else None}
+            model_name, conf, seconds, face = _detect_settings(task, cfg)
+            detector = self._load_detector(model_name)
+            interval = _frame_interval(fps, seconds)
+            pipe = PipelinedDetector(detector, depth=2, streams=self._lanes(task))
+            lanes[task] = (_DetectionLane(detector, face, conf, pipe, self._face_clusterer(cfg) if face else None),
+                           interval, [], [])
         want_scenes = "scene_detection" in configs
         scfg = configs.get("scene_detection") or {}
         content = scfg.get("detector", "ffmpeg") == "content"
         sums, prev_dev, npx = [], None, 1
         pinned = [None, None]
         copied = [None, None]  # events: the chunk's upload has left the pinned buffer
-
-        def emit(lane, meta, dets, counts, frames=None):
-            boxes, batch = [], []
-            for slot, ((frame_idx, timestamp_ms), row, cnt) in enumerate(zip(meta, dets, counts)):
-                for d in row[: int(cnt)]:
-                    x1, y1, x2, y2 = (np.float32(d[k]) for k in ("x1", "y1", "x2", "y2"))
-                    confidence = float(np.float32(d["conf"]))
-                    if lane["face"] and confidence < lane["conf"]:
-                        continue
-                    det = {"frame_index": frame_idx, "timestamp_ms": timestamp_ms,
-                           "label": "face" if lane["face"] else lane["names"][int(d["cls"])], "confidence": confidence,
-                           "bbox": {"x": float(x1), "y": float(y1), "width": float(np.float32(x2 - x1)),
-                                    "height": float(np.float32(y2 - y1))}}
-                    if lane["face"]:
-                        det["cluster_id"] = None
-                        if lane["cluster"] is not None:
-                            boxes.append((slot, x1, y1, x2, y2))
-                            batch.append(det)
-                    lane["out"].append(det)
-            if lane["cluster"] is not None:
-                lane["cluster"].add(frames, boxes, batch)
-
-        def drain(lane, keep):
-            while lane["pipe"].in_flight() > keep:
-                if lane["cluster"] is not None:
-                    dets, counts, frames = lane["pipe"].result_with_frames()
-                    emit(lane, lane["metas"].pop(0), dets, counts, frames)
-                else:
-                    emit(lane, lane["metas"].pop(0), *lane["pipe"].result())
-
-        def flush(lane):
-            if not lane["frames"]:
-                return
-            batch = torch.stack(lane["frames"]) if len(lane["frames"]) > 1 else lane["frames"][0][None]
-            lane["pipe"].submit(batch.contiguous(), conf=lane["conf"])
-            lane["metas"].append(list(lane["meta"]))
-            lane["frames"].clear()
-            lane["meta"].clear()
-            drain(lane, lane["pipe"].depth - 1)
-
         frame_idx, slot = 0, 0
         try:
             done = False
@@ -509,53 +471,34 @@ class ModelManager:
                     elif npx % 4 == 0:
                         sums.append(scene.luma_sad_bgr(chunk, prev_dev, keep_on_device=True))
                     else:  # odd pixel counts: luma plane on the device, then K1
-                        c = chunk.to(torch.int64)
-                        y = ((269484 * c[..., 2] + 528482 * c[..., 1] + 102760 * c[..., 0] + (16 << 20) + (1 << 19)) >> 20).to(torch.uint8)
-                        py = None
-                        if prev_dev is not None:
-                            p = prev_dev.to(torch.int64)
-                            py = ((269484 * p[..., 2] + 528482 * p[..., 1] + 102760 * p[..., 0] + (16 << 20) + (1 << 19)) >> 20).to(torch.uint8)
+                        y = bgr_to_luma_bt601(chunk)
+                        py = bgr_to_luma_bt601(prev_dev) if prev_dev is not None else None
                         sums.append(scene.luma_sad(y.contiguous(), py.contiguous() if py is not None else None, keep_on_device=True))
                     prev_dev = chunk[n - 1]
-                for lane in lanes.values():
+                for lane, interval, meta, rows in lanes.values():
                     for i in range(n):
                         idx = frame_idx + i
-                        if idx % lane["interval"] == 0:
-                            lane["frames"].append(chunk[i])
-                            lane["meta"].append((idx, int((idx / fps) * 1000)))
-                            if len(lane["frames"]) >= self._batch_size:
-                                flush(lane)
+                        if idx % interval == 0:
+                            rows.append(chunk[i])
+                            meta.append((idx, _timestamp_ms(idx, fps)))
+                            if len(rows) >= self._batch_size:
+                                lane.submit(list(meta), _stack_rows(rows))
+                                meta.clear()
+                                rows.clear()
                 frame_idx += n
-            for lane in lanes.values():
-                flush(lane)
-                drain(lane, 0)
-                if lane.get("cluster") is not None:
-                    lane["cluster"].finish()
+            for lane, _, meta, rows in lanes.values():
+                if rows:
+                    lane.submit(meta, _stack_rows(rows))
+                lane.finish()
         finally:
             src.release()
-            for lane in lanes.values():
-                lane["pipe"].close()
-                self._close_clusterer(lane.get("cluster"))
-        out = {}
-        for task, lane in lanes.items():
-            out[task] = {"detections": lane["out"]}
+            for lane, *_ in lanes.values():
+                lane.close()
+        out = {task: {"detections": lane.out} for task, (lane, *_) in lanes.items()}
         if want_scenes:
-            tb_num, tb_den = src.time_base
-            duration_ms = None if src.duration_s is None else int(float(src.duration_s) * 1000)
             s_all = torch.cat(sums).cpu().numpy() if sums else np.zeros((0, 3) if content else (0,), np.uint64)
-            if content:
-                scores = scene.content_scores(s_all, npx)
-                cuts = scene.content_cuts(scores, float(scfg.get("content_threshold", 27.0)), int(scfg.get("min_scene_len", 15)),
-                                          scfg.get("filter_mode", "legacy"))
-                ts = [0] + [int(float(scene.pts_time_string(c, tb_num, tb_den)) * 1000) for c in cuts]
-                end = duration_ms if duration_ms is not None else (ts[-1] + 1000)
-                out["scene_detection"] = {"scenes": [{"scene_index": i, "start_ms": a, "end_ms": b, "duration_ms": b - a}
-                                                     for i, (a, b) in enumerate(zip(ts, ts[1:] + [end]))]}
-            else:
-                _, score = scene.ffmpeg_scene_scores(s_all, npx)
-                cut_ms = [int(float(scene.pts_time_string(int(c), tb_num, tb_den)) * 1000)
-                          for c in np.nonzero(score > float(scfg.get("threshold", 0.7)))[0]]
-                out["scene_detection"] = {"scenes": scene.build_scenes(cut_ms, duration_ms)}
+            scene_list = scene.content_scene_list if content else scene.ffmpeg_scene_list
+            out["scene_detection"] = {"scenes": scene_list(s_all, npx, scfg, src.time_base, src.duration_s)}
         logger.info(f"✅ Single-pass analysis complete: {frame_idx} frames (header: {total_frames}), "
                     + ", ".join(f"{k}: {len(v.get('detections', v.get('scenes', [])))}" for k, v in out.items()))
         return out
@@ -570,12 +513,9 @@ class ModelManager:
             from . import scene
 
             logger.info(f"Scene detection: {video_path}")
-            threshold = config.get("threshold", 0.7)
             src = self._open(video_path)
             try:
                 n = int(src.total_frames)
-                tb_num, tb_den = src.time_base
-                duration_ms = None if src.duration_s is None else int(float(src.duration_s) * 1000)
                 chunk = 64
                 if config.get("detector", "ffmpeg") == "content":
                     sums = []
@@ -586,14 +526,7 @@ class ModelManager:
                         prev = frames[-1]
                     sums = np.concatenate(sums) if sums else np.zeros((0, 3), np.uint64)
                     h, w = (frames.shape[1], frames.shape[2]) if n else (1, 1)
-                    scores = scene.content_scores(sums, h * w)
-                    cuts = scene.content_cuts(scores, float(config.get("content_threshold", 27.0)),
-                                              int(config.get("min_scene_len", 15)), config.get("filter_mode", "legacy"))
-                    ts = [0] + [int(float(scene.pts_time_string(c, tb_num, tb_den)) * 1000) for c in cuts]
-                    end = duration_ms if duration_ms is not None else (ts[-1] + 1000)
-                    scenes = [{"scene_index": i, "start_ms": a, "end_ms": b, "duration_ms": b - a}
-                              for i, (a, b) in enumerate(zip(ts, ts[1:] + [end]))]
-                    return {"scenes": scenes}
+                    return {"scenes": scene.content_scene_list(sums, h * w, config, src.time_base, src.duration_s)}
                 from .frames import EndOfStream
 
                 sad = []
@@ -613,11 +546,8 @@ class ModelManager:
                         break
                 sad = np.concatenate(sad) if sad else np.zeros(0, np.uint64)
                 count = int(y.shape[1] * y.shape[2]) if y is not None else 1
-                _, score = scene.ffmpeg_scene_scores(sad, count)
-                cut_ms = [int(float(scene.pts_time_string(int(c), tb_num, tb_den)) * 1000)
-                          for c in np.nonzero(score > float(threshold))[0]]
-                scenes = scene.build_scenes(cut_ms, duration_ms)
-                if len(cut_ms) == 0:
+                scenes = scene.ffmpeg_scene_list(sad, count, config, src.time_base, src.duration_s)
+                if scenes[-1]["scene_index"] == 0:  # the last scene's index is the number of cuts
                     logger.info(f"No scene cuts detected. Created single scene for entire video ({scenes[0]['end_ms']}ms)")
                 logger.info(f"✅ Scene detection complete: {len(scenes)} scenes")
                 return {"scenes": scenes}

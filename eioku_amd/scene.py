@@ -232,3 +232,27 @@ def build_scenes(cut_timestamps_ms, duration_ms: int | None) -> list[dict]:
     else:
         scenes.append({"scene_index": 0, "start_ms": 0, "end_ms": duration_ms, "duration_ms": duration_ms})
     return scenes
+
+
+def _cut_ms(frame_index, time_base) -> int:
+    return int(float(pts_time_string(int(frame_index), *time_base)) * 1000)
+
+
+def content_scene_list(sums, num_pixels: int, config: dict, time_base, duration_s) -> list[dict]:
+    """The scene list of the ContentDetector route from K2's ``(n,3)`` sums: scores, cuts (``content_threshold``,
+    ``min_scene_len``, ``filter_mode`` of ``config``), then one scene from each cut to the next, the first from 0 and
+    the last to the duration (last cut + 1000 without one).  ``time_base`` / ``duration_s`` as a ``FrameSource`` has them."""
+    cuts = content_cuts(content_scores(sums, num_pixels), float(config.get("content_threshold", 27.0)),
+                        int(config.get("min_scene_len", 15)), config.get("filter_mode", "legacy"))
+    ts = [0] + [_cut_ms(c, time_base) for c in cuts]
+    end = int(float(duration_s) * 1000) if duration_s is not None else (ts[-1] + 1000)
+    return [{"scene_index": i, "start_ms": a, "end_ms": b, "duration_ms": b - a}
+            for i, (a, b) in enumerate(zip(ts, ts[1:] + [end]))]
+
+
+def ffmpeg_scene_list(sad, num_pixels: int, config: dict, time_base, duration_s) -> list[dict]:
+    """The scene list of the ffmpeg route from K1's luma SAD sums: libavfilter's score, a cut wherever it exceeds
+    ``config["threshold"]``, then ``build_scenes`` (so the last scene's index is the number of cuts)."""
+    _, score = ffmpeg_scene_scores(sad, num_pixels)
+    cut_ms = [_cut_ms(c, time_base) for c in np.nonzero(score > float(config.get("threshold", 0.7)))[0]]
+    return build_scenes(cut_ms, None if duration_s is None else int(float(duration_s) * 1000))
