@@ -10,6 +10,8 @@ ffmpeg / OpenCV / Ultralytics on the CPU.
                                           cluster of ArcFace embeddings: "face_cluster_001", ...)
     detect_scenes(video_path, config)  -> {"scenes": [{scene_index, start_ms, end_ms,
                                            duration_ms}]}                              (ref :715-835)
+    extract_ocr(video_path, config)    -> {"detections": [{frame_index, timestamp_ms, text, confidence,
+                                           language, polygon}], "language"}           (ref :469-558)
 
 What changes underneath (and nothing else): sampled frames are detected in batches instead of one
 ``model(frame)`` call each, and the scene score is computed by K1/K2 instead of an ffmpeg child
@@ -150,13 +152,15 @@ class ModelManager:
     """Manages model lifecycle and inference for the hot-path task types."""
 
     def __init__(self, cache_dir: str = "/models", *, frame_source=None, detector_factory=None, batch_size: int = 64,
-                 random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None):
+                 random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
+                 ocr_reader_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
         weights of the right shapes when no checkpoint can exist (offline benchmarks);
         ``face_embedder_factory(cache_dir, model_name) -> embedder`` with ``embed(frames, boxes)`` and
-        ``cluster(embeddings, eps, min_samples)`` (``cluster_faces``)."""
+        ``cluster(embeddings, eps, min_samples)`` (``cluster_faces``); ``ocr_reader_factory(cache_dir) -> reader`` with
+        ``readtext_batch(frames) -> per frame [(box, text, confidence)]``."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -165,6 +169,7 @@ class ModelManager:
         self._detector_factory = detector_factory
         self._place_classifier_factory = place_classifier_factory  # (cache_dir) -> object with classify(frames, top_k), labels
         self._face_embedder_factory = face_embedder_factory
+        self._ocr_reader_factory = ocr_reader_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -217,7 +222,60 @@ class ModelManager:
         raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")
 
     async def extract_ocr(self, video_path: str, config: dict) -> dict:
-        raise NotImplementedError(f"extract_ocr {OUT_OF_SCOPE}")
+        """On-screen text with EasyOCR's CRAFT + english_g2 on the HIP path (reference: :469-558): every
+        ``max(1, int(fps * frame_interval))``-th frame -> ``readtext`` detections ``{frame_index, timestamp_ms, text,
+        confidence, language, polygon: [{x, y}]}``.  English only: another language raises ``ValueError``."""
+        try:
+            logger.info(f"OCR: {video_path} (GPU: {self.gpu_available})")
+            # 'language' (singular) first, then the legacy 'languages' list (ref :489-499)
+            language = config.get("language")
+            if language:
+                languages = [language]
+            else:
+                languages = config.get("languages", ["en"])
+                if isinstance(languages, str):
+                    languages = [languages]
+                language = languages[0] if languages else "en"
+            from .ocr import SUPPORTED_LANGUAGES
+
+            unsupported = [lang for lang in languages if lang not in SUPPORTED_LANGUAGES]
+            if unsupported:
+                raise ValueError(f"OCR languages {unsupported} are not supported (supported: {list(SUPPORTED_LANGUAGES)})")
+            frame_interval_seconds = config.get("frame_interval", 2)
+            reader = self._load_ocr_reader()
+            cap = self._open(video_path)
+            fps = cap.fps or 30
+            total_frames = int(cap.total_frames)
+            frame_interval = _frame_interval(fps, frame_interval_seconds)
+            frames_to_process = (total_frames + frame_interval - 1) // frame_interval
+            logger.info(f"Video FPS: {fps}, Total frames: {total_frames}, Processing every {frame_interval} frames "
+                        f"(every {frame_interval_seconds}s, ~{frames_to_process} frames to process)")
+            detections: list[dict] = []
+            try:
+                for meta, frames in _sampled_batches(cap, fps, frame_interval, self._batch_size):
+                    for (frame_idx, timestamp_ms), results in zip(meta, reader.readtext_batch(np.stack(frames))):
+                        for bbox, text, confidence in results:
+                            detections.append({"frame_index": frame_idx, "timestamp_ms": timestamp_ms, "text": text,
+                                               "confidence": confidence, "language": language,
+                                               "polygon": [{"x": float(p[0]), "y": float(p[1])} for p in bbox]})
+            finally:
+                cap.release()
+                close = getattr(reader, "close", None)
+                if close:
+                    close()
+            logger.info(f"✅ OCR complete: {len(detections)} detections")
+            return {"detections": detections, "language": language}
+        except Exception as e:
+            logger.error(f"OCR failed: {e}", exc_info=True)
+            raise
+
+    def _load_ocr_reader(self):
+        """``easyocr.Reader(languages)`` (ref :507) from ``<cache>/easyocr/model``, per job like the reference."""
+        if self._ocr_reader_factory is not None:
+            return self._ocr_reader_factory(self.cache_dir)
+        from .ocr import OcrReader
+
+        return OcrReader.from_cache(self.cache_dir, seed=self._seed)
 
     async def extract_metadata(self, video_path: str, config: dict) -> dict:
         raise NotImplementedError(f"extract_metadata {OUT_OF_SCOPE}")

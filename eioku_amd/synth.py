@@ -86,3 +86,33 @@ def bytes_u8(seed: int, n: int, device):
     out = torch.empty((n,), dtype=torch.uint8, device=device)
     _lib.check(lib.eioku_synth_bytes(seed, n, ptr(out), current_stream(out)), "eioku_synth_bytes")
     return out
+
+
+def ocr_frames(seed: int, n: int, h: int, w: int) -> np.ndarray:
+    """Host BGR uint8 (n, h, w, 3) frames for the OCR bench and tests: a smooth shaded background with six dark bars
+    (text-like strokes) per frame, so CRAFT's maps have structure."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = np.empty((n, h, w, 3), np.uint8)
+    for i in range(n):
+        base = 128 + 60 * np.sin(xx / (17 + i) + rng.random() * 6) * np.cos(yy / 23)
+        img = np.repeat(base[..., None], 3, 2) + rng.normal(0, 6, (h, w, 3))
+        for _ in range(6):
+            y0, x0 = rng.integers(0, h - h // 8), rng.integers(0, w - w // 4)
+            img[y0:y0 + h // 16, x0:x0 + w // 5] = 20
+        out[i] = np.clip(img, 0, 255).astype(np.uint8)
+    return out
+
+
+def ocr_crops(seed: int, widths) -> list:
+    """Recogniser inputs: per padded width a random grey crop of half that width with dark columns, through
+    ``ocr.align_collate`` -> float32 (64, width)."""
+    from .ocr import align_collate
+
+    rng = np.random.default_rng(seed)
+    out = []
+    for wdt in widths:
+        img = rng.integers(0, 256, (64, wdt // 2), dtype=np.uint8)
+        img[:, ::7] = 0
+        out.append(align_collate(img, wdt))
+    return out

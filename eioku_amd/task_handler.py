@@ -12,6 +12,7 @@ storage go through two small hooks carried in the arq ``ctx`` dict.
     ctx["task_store"]   optional object with mark_running / mark_completed / mark_failed /
                         mark_cancelled (task_id[, error])            (ref :68-78, 422-425, 437-469)
     ctx["artifact_sink"] optional callable(list[ArtifactEnvelope])   (ref :344-404)
+    ctx["gpu_ocr"]      true: run ``ocr`` on the HIP path (ModelManager.extract_ocr); otherwise it is refused as before
 """
 
 from __future__ import annotations
@@ -28,9 +29,9 @@ logger = logging.getLogger(__name__)
 
 TASK_TO_ARTIFACT_TYPE = {"object_detection": "object.detection", "face_detection": "face.detection",
                          "scene_detection": "scene", "segment_embedding": "segment.embedding",
-                         "place_detection": "place.classification"}
+                         "place_detection": "place.classification", "ocr": "ocr.text"}
 TASK_TO_RESULT_KEY = {"object_detection": "detections", "face_detection": "detections", "scene_detection": "scenes",
-                      "segment_embedding": "embeddings", "place_detection": "classifications"}
+                      "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections"}
 # the reference's seven (task_handler.py:92-127) + the one its semantic-search design adds after transcription
 # (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them
 KNOWN_TASK_TYPES = ("object_detection", "face_detection", "transcription", "ocr", "place_detection",
@@ -155,6 +156,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             result = await model_manager.detect_scenes(video_path, config or {})
         elif task_type == "place_detection":
             result = await model_manager.classify_places(video_path, config or {})
+        elif task_type == "ocr" and ctx.get("gpu_ocr"):  # opt-in: without it ocr stays with the reference worker
+            result = await model_manager.extract_ocr(video_path, config or {})
         elif task_type == "segment_embedding":
             # segments: the transcription task's output for this video.  The reference would read them back from its
             # artifact table; without a database they arrive in the job config or through ctx["segment_source"](video_id)

@@ -448,6 +448,39 @@ int eioku_iresnet_last_flops(const eioku_iresnet_t* r, double* flops);
  * n <= 65536, d % 32 == 0, eps in [0, 2], min_samples >= 1; labels_out [n] int32 on the side `mem` names. */
 int eioku_dbscan_cosine(const float* emb, int n, int d, float eps, int min_samples, int32_t* labels_out, int mem, void* stream);
 
+/* ---- OCR: EasyOCR's CRAFT detector and english_g2 CRNN recogniser (csrc/ocr.hip) -------------------------------------
+ * Fills ModelManager.extract_ocr.  Convolutions are named as the state dicts' prefixes ("basenet.slice1.0", ...,
+ * "upconv1.conv.0", "conv_cls.8"; "FeatureExtraction.ConvNet.0", ..., "Prediction") and take the following BatchNorm
+ * folded in.  fc6 ("basenet.slice5.1") is the 3x3 / dilation 6 conv.  craft_forward: n BGR u8 frames (host or device per
+ * mem) -> text / link score maps [n][H/2][W/2] fp32 and their (text > low_text) | (link > link_threshold) u8 map, DEVICE
+ * and each optional, H x W = the canvas (frame, or INTER_LINEAR to canvas_size on the long side, padded to multiples of
+ * 32).  crnn_forward: m normalised grey crops imgs HOST fp32 [64][widths[i]] (packed) -> per sequence step (T_i =
+ * widths[i] / 4 - 1, rows in crop order) the argmax class and its probability after softmax with the `ignore` classes
+ * zeroed and renormalised, HOST; logits_out optional; at most 262,144 steps per call.  CRAFT and the recogniser's VGG store
+ * fp16 and accumulate in fp32; the recogniser is fp32 from its row mean on (GEMMs, BiLSTMs, logits).
+ * All calls are synchronous. */
+typedef struct eioku_craft eioku_craft_t;
+int eioku_craft_create(eioku_craft_t** out);
+void eioku_craft_destroy(eioku_craft_t* r);
+int eioku_craft_num_convs(const eioku_craft_t* r);
+int eioku_craft_conv_info(const eioku_craft_t* r, int idx, char* name, size_t name_cap, int* cout, int* cin, int* ksize);
+int eioku_craft_set_conv(eioku_craft_t* r, int idx, const float* weight_oihw, const float* bias);
+int eioku_craft_forward(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int w, int canvas_size, float low_text,
+                        float link_threshold, float* text_out, float* link_out, uint8_t* bin_out, int mem, void* stream);
+int eioku_craft_last_flops(const eioku_craft_t* r, double* flops);
+typedef struct eioku_crnn eioku_crnn_t;
+int eioku_crnn_create(int num_class, eioku_crnn_t** out);
+void eioku_crnn_destroy(eioku_crnn_t* r);
+int eioku_crnn_num_convs(const eioku_crnn_t* r);
+int eioku_crnn_conv_info(const eioku_crnn_t* r, int idx, char* name, size_t name_cap, int* cout, int* cin, int* ksize);
+int eioku_crnn_set_conv(eioku_crnn_t* r, int idx, const float* weight_oihw, const float* bias);
+/* BiLSTM layer 0 / 1: w_ih, w_hh [2][1024][256] and b_ih, b_hh [2][1024] (forward, reverse), w_lin [256][512], b_lin [256] */
+int eioku_crnn_set_lstm(eioku_crnn_t* r, int layer, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                        const float* w_lin, const float* b_lin);
+int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, int m, const uint8_t* ignore, int32_t* idx_out,
+                       float* prob_out, float* logits_out, void* stream);
+int eioku_crnn_last_flops(const eioku_crnn_t* r, double* flops);
+
 #ifdef __cplusplus
 }
 #endif
