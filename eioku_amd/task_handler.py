@@ -29,13 +29,15 @@ logger = logging.getLogger(__name__)
 
 TASK_TO_ARTIFACT_TYPE = {"object_detection": "object.detection", "face_detection": "face.detection",
                          "scene_detection": "scene", "segment_embedding": "segment.embedding",
-                         "place_detection": "place.classification", "ocr": "ocr.text"}
+                         "place_detection": "place.classification", "ocr": "ocr.text", "topic_extraction": "topic"}
 TASK_TO_RESULT_KEY = {"object_detection": "detections", "face_detection": "detections", "scene_detection": "scenes",
-                      "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections"}
+                      "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections",
+                      "topic_extraction": "topics"}
 # the reference's seven (task_handler.py:92-127) + the one its semantic-search design adds after transcription
-# (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them
+# (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them; and the topic stage its
+# worker configs schedule (config/*.json "topic_extraction"; tasks.md 12.1-12.3): KeyBERT keywords of the segments
 KNOWN_TASK_TYPES = ("object_detection", "face_detection", "transcription", "ocr", "place_detection",
-                    "scene_detection", "metadata_extraction", "segment_embedding")
+                    "scene_detection", "metadata_extraction", "segment_embedding", "topic_extraction")
 
 
 @dataclass
@@ -158,18 +160,23 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             result = await model_manager.classify_places(video_path, config or {})
         elif task_type == "ocr" and ctx.get("gpu_ocr"):  # opt-in: without it ocr stays with the reference worker
             result = await model_manager.extract_ocr(video_path, config or {})
-        elif task_type == "segment_embedding":
+        elif task_type in ("segment_embedding", "topic_extraction"):
             # segments: the transcription task's output for this video.  The reference would read them back from its
             # artifact table; without a database they arrive in the job config or through ctx["segment_source"](video_id)
             segments = (config or {}).get("segments")
             if segments is None and ctx.get("segment_source"):
                 segments = ctx["segment_source"](video_id)
             if segments is None:
-                raise ValueError("segment_embedding needs config['segments'] or ctx['segment_source']")
+                raise ValueError(f"{task_type} needs config['segments'] or ctx['segment_source']")
             engine = ctx.get("search_engine")
             if engine is None:
-                raise ValueError("segment_embedding needs ctx['search_engine'] (eioku_amd.semantic.SemanticSearchEngine)")
-            result = embed_segments(engine, video_id, segments)
+                raise ValueError(f"{task_type} needs ctx['search_engine'] (eioku_amd.semantic.SemanticSearchEngine)")
+            if task_type == "segment_embedding":
+                result = embed_segments(engine, video_id, segments)
+            else:  # one "topic" envelope per topic; segment_keywords are returned, not emitted
+                from .topics import TopicExtractor
+
+                result = TopicExtractor(engine.generator).extract(segments, config)
         else:
             raise NotImplementedError(f"task type {task_type} is outside the MI355X hot path; route it to the "
                                       "reference worker")

@@ -481,6 +481,20 @@ int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, in
                        float* prob_out, float* logits_out, void* stream);
 int eioku_crnn_last_flops(const eioku_crnn_t* r, double* flops);
 
+/* ---- topics: KeyBERT keyword selection (csrc/topics.hip, K17) -------------------------------------------------------
+ * Fills the topic_extraction stage the reference schedules but never built.  rows: x [n_rows][d] fp32; terms [n_terms][d]
+ * fp32 (both unit vectors, 16-byte aligned); CSR row_ptr [n_rows+1], cand [nnz] int32 (term ids, read at
+ * cand[row_ptr[r] .. row_ptr[r+1])).  s = dot(x, w_t).  diversity < 0: plain, the min(top_n, |row|) largest s; else MMR
+ * with lambda = diversity (<= 1): argmax s, then argmax (1 - lambda) * s_t - lambda * max_k dot(w_t, w_k) over the picked
+ * k, in fp32.  Every argmax breaks ties by the smaller term id.  -> idx [n_rows][top_n] int32 (picked term ids ordered
+ * by s descending, ties by the smaller id; -1 pad), score [n_rows][top_n] fp32 (their s; 0 pad), count [n_rows] int32.
+ * 1 <= top_n <= 32, d % 4 == 0, d <= 1024, else EIOKU_EINVAL before the device is touched; a term id outside
+ * [0, n_terms) is EIOKU_EINVAL after the launch.  Fixed summation order, no atomics: repeated calls, and host- and
+ * device-memory calls, give the same bytes.  Synchronous: returns after the outputs are written. */
+int eioku_keyword_select(const float* x, int n_rows, const float* terms, int n_terms, int d, const int32_t* row_ptr,
+                         const int32_t* cand, int top_n, float diversity, int32_t* idx, float* score, int32_t* count,
+                         int mem, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
