@@ -88,6 +88,10 @@ SIGNATURES = {
                                      C.c_void_p]),
     "eioku_index_search_after": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_index_search_sel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_index_remove_ids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    "eioku_index_nlive": (C.c_longlong, [C.c_void_p]),
     "eioku_index_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_longlong]),
     "eioku_topk_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

@@ -78,6 +78,10 @@ struct KnnArgs {
   const long long* lbi;
   long long slab_stride;     // rows between slab starts (== rows_per_block for a full search; larger = strided sample)
   const int* gate;           // optional device word: the launch is a no-op when *gate == 0 (scan-path fallback)
+  // K9f row selector (SEL != 0 instantiations only, see k_sel_words / k_sel_list)
+  const unsigned* sel;       // [ceil(n/32)] effective words: bit r % 32 of word r / 32 set = row r is a candidate
+  const int* list;           // SEL == 2: numbers of the non-empty tiles, ascending
+  const int* meta;           // SEL == 2: meta[0] = entries of `list`
 };
 
 // Query tile (32 x d) in registers, DB streamed through LDS.
@@ -89,7 +93,16 @@ struct KnnArgs {
 // The (row tile, chunk) sequence is flat: the next chunk - also the first chunk of the next row tile -
 // is in flight (registers) while the current one is multiplied; row norms ride along with chunk 0 so
 // the epilogue issues no global load that would drain the in-order vmcnt queue.
-template <int K, int D, bool WIDE>
+//
+// SEL (K9f, row selector; a template parameter so that SEL == 0 compiles to the kernel it was before selectors existed):
+//   1  masked walk: the same slabs, but a tile whose selector word is zero is stepped over before anything of it is
+//      staged, and a row enters a lane's top-K only if its bit is set.  One word = one 32-row tile, wave-uniform.
+//   2  tile list: blockIdx.x owns a contiguous share of `list` (the non-empty tiles, ascending, from k_sel_list) and
+//      stages only those tiles; work follows the eligible rows, not N.  Partial ids are global rows (slab0 = 0), the
+//      merge that follows adds nothing to them.
+// Both resolve a tile's row and word one tile before it is staged (the list / word loads sit a whole tile of MFMAs
+// ahead of their first use).  Lists stay ascending, so a lane still meets its rows in increasing id order.
+template <int K, int D, bool WIDE, int SEL = 0>
 __global__ __launch_bounds__(256, 1) void k_flat_l2(KnnArgs a) {
   if (a.gate && *a.gate == 0) return;  // uniform
   constexpr int KC = D < 128 ? D : 128;  // dims per LDS chunk (<= 512 B per row)
@@ -130,8 +143,8 @@ __global__ __launch_bounds__(256, 1) void k_flat_l2(KnnArgs a) {
   TopK<K> top;
   top.init();
 
-  const long long slab0 = (long long)blockIdx.x * a.slab_stride;
-  const long long slab1 = min(a.n, slab0 + a.rows_per_block);
+  const long long slab0 = SEL == 2 ? 0 : (long long)blockIdx.x * a.slab_stride;
+  const long long slab1 = SEL == 2 ? a.n : min(a.n, slab0 + a.rows_per_block);
   float4* my = lds + (WIDE ? 0 : wave) * (2 * TILE_U);
   float* mynorm = lnorm + (WIDE ? 0 : wave) * (2 * kRT);
   const int sid = WIDE ? tid : lane;            // staging id inside the staging group
@@ -173,8 +186,38 @@ __global__ __launch_bounds__(256, 1) void k_flat_l2(KnnArgs a) {
     }
   };
 
+  // selector cursor: tile_from(r, w) = first tile at or after row r (SEL 1) / next list entry (SEL 2) of this wave's
+  // sequence and its selector word; slab1 when there is none.  Indices are wave-uniform: read through the scalar unit.
+  int lj = 0, lj1 = 0;
+  if constexpr (SEL == 2) {
+    const int cnt = a.meta[0];
+    const int per = (cnt + (int)gridDim.x - 1) / (int)gridDim.x;
+    lj = (int)blockIdx.x * per + (WIDE ? 0 : wave) - (WIDE ? 1 : kWaves);  // tile_from advances first
+    lj1 = min(cnt, ((int)blockIdx.x + 1) * per);
+  }
+  auto tile_from = [&](long long r, unsigned& w) -> long long {
+    if constexpr (SEL == 1) {
+      while (r < slab1) {
+        w = a.sel[__builtin_amdgcn_readfirstlane((int)(r >> 5))];
+        if (w) break;
+        r += tile_step;
+      }
+      return r < slab1 ? r : slab1;
+    } else if constexpr (SEL == 2) {
+      lj += WIDE ? 1 : kWaves;
+      if (lj >= lj1) return slab1;
+      const int t = a.list[__builtin_amdgcn_readfirstlane(lj)];
+      w = a.sel[__builtin_amdgcn_readfirstlane(t)];
+      return (long long)t * kRT;
+    } else {
+      return r;
+    }
+  };
+  unsigned word = 0, nword = 0;
+
   // flat (tile, chunk) walk
-  long long row0 = first;
+  long long row0 = SEL ? tile_from(first, word) : first;
+  long long nxt = SEL && row0 < slab1 ? tile_from(row0 + tile_step, nword) : slab1;
   int buf = 0, nbuf = 0;  // data buffer / norm buffer parity
   if (row0 < slab1) {
     issue(row0, 0);
@@ -185,10 +228,12 @@ __global__ __launch_bounds__(256, 1) void k_flat_l2(KnnArgs a) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   while (row0 < slab1) {
+    unsigned nnword = 0;
+    const long long nn = SEL && nxt < slab1 ? tile_from(nxt + tile_step, nnword) : slab1;  // two tiles ahead
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
       const bool last = ch == NCH - 1;
-      const long long nrow = last ? row0 + tile_step : row0;
+      const long long nrow = last ? (SEL ? nxt : row0 + tile_step) : row0;
       const int nch = last ? 0 : ch + 1;
       const bool more = nrow < slab1;
       if (more) issue(nrow, nch);  // in flight during the MFMAs below
@@ -220,7 +265,7 @@ __global__ __launch_bounds__(256, 1) void k_flat_l2(KnnArgs a) {
         for (int r = 0; r < 16; ++r) {
           const int lr = (r & 3) + 8 * (r >> 2) + 4 * half;
           const long long row = row0 + lr;
-          if (row < slab1) {
+          if (row < slab1 && (SEL == 0 || ((word >> lr) & 1u))) {
             float dist = (qn + mynorm[nbuf * kRT + lr]) - 2.0f * acc[r];
             dist = dist < 0.f ? 0.f : dist;
             const int id = (int)(row - slab0);  // slab-local, fits 31 bits
@@ -235,7 +280,14 @@ __global__ __launch_bounds__(256, 1) void k_flat_l2(KnnArgs a) {
       buf ^= 1;
       if (last) nbuf ^= 1;
     }
-    row0 += tile_step;
+    if constexpr (SEL == 0) {
+      row0 += tile_step;
+    } else {
+      row0 = nxt;
+      word = nword;
+      nxt = nn;
+      nword = nnword;
+    }
   }
 
   // ---- merge the lists of each query inside the workgroup ----
@@ -723,7 +775,10 @@ __global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ 
     const long long row = tile * 32 + r;
     const float nn = row < n ? norms[row] : 0.f;
     if (threadIdx.x < 32) hnorm[tile * 32 + r] = row < n ? 0.5f * nn : __builtin_inff();
-    float m = sqrtf(nn);
+    // a removed row's norm is +inf (k_remove_ids): its half norm above is +inf too, which is what keeps it out of the
+    // scan, but the tile's max |x| is taken over live rows only (an infinite margin would make the filter's
+    // threshold inf - inf)
+    float m = nn < __builtin_inff() ? sqrtf(nn) : 0.f;
 #pragma unroll
     for (int off = 16; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     if (threadIdx.x == 0) tmax[tile] = m;
@@ -1087,6 +1142,87 @@ __global__ __launch_bounds__(256) void k_scan_select(const float* __restrict__ d
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K9f pre-pass (device side, no host round trip): selector words -> effective words, ordered list of the non-empty
+// tiles, its length and the route.  Two small launches of ceil(words / 1024) workgroups: an ORDERED compaction needs
+// every block's count before any block knows where its entries go, and the per-lane top-K's tie rule needs the order.
+//   k_sel_words: ew[i] = sel[i] & live[i] & (bits of rows < n); bcount[b] = non-empty words of block b
+//   k_sel_list:  list[sum(bcount[0..b)) + rank] = i for the non-empty words of block b, ascending; the last block
+//                writes meta = {entries, take the tile-list route, take the masked route}
+// Nothing reads sel or live at or beyond ceil(n/32) words; every later kernel reads ew only.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_sel_words(const unsigned* __restrict__ sel, const unsigned* __restrict__ live,
+                                                    long long n, int nwords, unsigned* __restrict__ ew,
+                                                    int* __restrict__ bcount) {
+  __shared__ int s_cnt;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  const int i = blockIdx.x * 1024 + threadIdx.x;
+  unsigned w = 0;
+  if (i < nwords) {
+    w = sel ? sel[i] : 0xFFFFFFFFu;
+    if (live) w &= live[i];
+    const long long rem = n - (long long)i * 32;  // >= 1 rows in this word
+    if (rem < 32) w &= (1u << (int)rem) - 1u;
+    ew[i] = w;
+  }
+  const unsigned long long b = __ballot(w != 0);
+  if ((threadIdx.x & 63) == 0 && b) atomicAdd(&s_cnt, __popcll(b));
+  __syncthreads();
+  if (threadIdx.x == 0) bcount[blockIdx.x] = s_cnt;
+}
+
+__global__ __launch_bounds__(1024) void k_sel_list(const unsigned* __restrict__ ew, const int* __restrict__ bcount, int nwords,
+                                                   int* __restrict__ list, int* __restrict__ meta, long long ppm) {
+  __shared__ int s_part[16], s_wc[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int s = 0;
+  for (int b = tid; b < (int)blockIdx.x; b += 1024) s += bcount[b];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  const int i = blockIdx.x * 1024 + tid;
+  const bool nz = i < nwords && ew[i] != 0;
+  const unsigned long long b = __ballot(nz);
+  if (lane == 0) {
+    s_part[wave] = s;
+    s_wc[wave] = __popcll(b);
+  }
+  __syncthreads();
+  int base = 0, before = 0, mine = 0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) {
+    base += s_part[w];
+    before += w < wave ? s_wc[w] : 0;
+    mine += s_wc[w];
+  }
+  if (nz) list[base + before + __popcll(b & ((1ull << lane) - 1ull))] = i;
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+    const int total = base + mine;
+    const bool use_list = (long long)total * 1000000ll <= ppm * (long long)nwords;
+    meta[0] = total;
+    meta[1] = use_list ? 1 : 0;
+    meta[2] = use_list ? 0 : 1;
+  }
+}
+
+// Removal: a removed row's norm (register-tile kernels) and half norm (scan path) become +inf, which no candidate test
+// passes (inf < FLT_MAX is false); its bit in `live` goes, which keeps nlive, the tile list and add() consistent.
+__global__ __launch_bounds__(256) void k_remove_ids(const long long* __restrict__ ids, long long n_ids, long long n,
+                                                    long long planes_n, unsigned* __restrict__ live, float* __restrict__ norms,
+                                                    float* __restrict__ hnorm, int* __restrict__ removed) {
+  const long long i = blockIdx.x * 256ll + threadIdx.x;
+  if (i >= n_ids) return;
+  const long long id = ids[i];
+  if (id < 0 || id >= n) return;  // unknown ids are ignored
+  const unsigned bit = 1u << (int)(id & 31);
+  const unsigned old = atomicAnd(live + (id >> 5), ~bit);
+  if (old & bit) {  // a repeated id finds the bit gone
+    atomicAdd(removed, 1);
+    norms[id] = __builtin_inff();
+    if (hnorm && id < planes_n) hnorm[id] = __builtin_inff();
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
@@ -1132,6 +1268,18 @@ struct eioku_index {
                                // against 0.32 / 0.41 ms (tools/knn_nq_sweep.py, profiles/r02_knn_nq_sweep.jsonl)
   int scan_prescan = 32;       // stride of the pre-scan's row tiles (0: no pre-scan, the sample alone bounds the scan)
   int scan_rt = 2;             // row tiles per wave: 2 (8 waves per workgroup; 2-3 % faster at 10 M x 384) or 1 (12 waves)
+  // K9f: removal and row selectors
+  unsigned* live = nullptr; size_t live_words = 0;  // NULL until the first removal: every row is live
+  int* removed_dev = nullptr;                       // [1] rows removed so far
+  long long removed = 0;                            // its host copy (eioku_index_remove_ids drains the stream)
+  long long* idbuf = nullptr; size_t idcap = 0;     // staged host ids
+  unsigned* selbuf = nullptr; size_t selcap = 0;    // staged host selector
+  unsigned* ew = nullptr; size_t ewcap = 0;         // effective words of the running search
+  int* tlist = nullptr; size_t tlcap = 0;           // its non-empty tiles
+  int* bcount = nullptr; size_t bccap = 0;
+  int* meta = nullptr;                              // [4] {entries, gate of the tile-list route, gate of the masked route}
+  int sel_list_ppm = 32000;    // tile-list route when non-empty tiles * 1e6 <= sel_list_ppm * tiles: the crossover of
+                               // profiles/knn_filtered.json at 10 M x 384 (DESIGN.md K9f has the table)
 };
 
 namespace {
@@ -1172,14 +1320,14 @@ int launch_search_bf(int d, const KnnArgs& a, dim3 grid, hipStream_t stream) {
   return EIOKU_OK;
 }
 
-template <int K, bool WIDE>
+template <int K, bool WIDE, int SEL = 0>
 int launch_search_k(int d, const KnnArgs& a, dim3 grid, hipStream_t stream) {
   switch (d) {
-    case 64: hipLaunchKernelGGL((k_flat_l2<K, 64, WIDE>), grid, dim3(256), 0, stream, a); break;
-    case 128: hipLaunchKernelGGL((k_flat_l2<K, 128, WIDE>), grid, dim3(256), 0, stream, a); break;
-    case 256: hipLaunchKernelGGL((k_flat_l2<K, 256, WIDE>), grid, dim3(256), 0, stream, a); break;
-    case 384: hipLaunchKernelGGL((k_flat_l2<K, 384, WIDE>), grid, dim3(256), 0, stream, a); break;
-    case 512: hipLaunchKernelGGL((k_flat_l2<K, 512, WIDE>), grid, dim3(256), 0, stream, a); break;
+    case 64: hipLaunchKernelGGL((k_flat_l2<K, 64, WIDE, SEL>), grid, dim3(256), 0, stream, a); break;
+    case 128: hipLaunchKernelGGL((k_flat_l2<K, 128, WIDE, SEL>), grid, dim3(256), 0, stream, a); break;
+    case 256: hipLaunchKernelGGL((k_flat_l2<K, 256, WIDE, SEL>), grid, dim3(256), 0, stream, a); break;
+    case 384: hipLaunchKernelGGL((k_flat_l2<K, 384, WIDE, SEL>), grid, dim3(256), 0, stream, a); break;
+    case 512: hipLaunchKernelGGL((k_flat_l2<K, 512, WIDE, SEL>), grid, dim3(256), 0, stream, a); break;
     default:
       set_error("dimension %d not supported (64, 128, 256, 384, 512)", d);
       return EIOKU_EINVAL;
@@ -1208,7 +1356,8 @@ void eioku_index_destroy(eioku_index* ix) {
   (void)hipDeviceSynchronize();
   if (ix->x && !ix->attached) (void)hipFree(ix->x);
   void* bufs[] = {ix->norms, ix->qbuf, ix->qnorm, ix->pd, ix->pi, ix->dout, ix->iout, ix->xh, ix->hnorm,
-                  ix->tmax, ix->xmax, ix->qh, ix->wl, ix->wl_cnt, ix->tau, ix->tau_i, ix->tau1, ix->tau1_i, ix->cand_i, ix->cnt};
+                  ix->tmax, ix->xmax, ix->qh, ix->wl, ix->wl_cnt, ix->tau, ix->tau_i, ix->tau1, ix->tau1_i, ix->cand_i, ix->cnt,
+                  ix->live, ix->removed_dev, ix->idbuf, ix->selbuf, ix->ew, ix->tlist, ix->bcount, ix->meta};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete ix;
@@ -1216,8 +1365,30 @@ void eioku_index_destroy(eioku_index* ix) {
 
 long long eioku_index_ntotal(const eioku_index* ix) { return ix ? ix->n : 0; }
 
+long long eioku_index_nlive(const eioku_index* ix) { return ix ? ix->n - ix->removed : 0; }
+
+}  // extern "C"
+
+namespace {
+
+// every id is live again (reset / attach): the next removal starts from an all-ones array
+void forget_removals(eioku_index* ix) {
+  if (ix->live) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(ix->live);
+    ix->live = nullptr;
+    ix->live_words = 0;
+  }
+  ix->removed = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 int eioku_index_reset(eioku_index* ix) {
   EIOKU_REQUIRE(ix, "NULL index");
+  forget_removals(ix);
   if (ix->attached) {
     ix->x = nullptr;
     ix->attached = false;
@@ -1254,9 +1425,26 @@ int eioku_index_add(eioku_index* ix, const float* x, long long n, int mem, void*
       EIOKU_HIP_CHECK(hipMemcpyAsync(nx, ix->x, (size_t)ix->n * ix->d * sizeof(float), hipMemcpyDeviceToDevice, stream));
       EIOKU_HIP_CHECK(hipMemcpyAsync(nn, ix->norms, (size_t)ix->n * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
+    unsigned* nl = nullptr;
+    const size_t nlw = (size_t)((ncap + 31) / 32);
+    if (ix->live) {  // rows were removed: the live words grow with the rows, new rows are live (bits beyond n stay set)
+      if (hipMalloc((void**)&nl, nlw * sizeof(unsigned)) != hipSuccess) {
+        (void)hipFree(nx);
+        (void)hipFree(nn);
+        set_error("hipMalloc of %zu live words failed", nlw);
+        return EIOKU_ENOMEM;
+      }
+      EIOKU_HIP_CHECK(hipMemsetAsync(nl, 0xFF, nlw * sizeof(unsigned), stream));
+      EIOKU_HIP_CHECK(hipMemcpyAsync(nl, ix->live, ix->live_words * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+    }
     EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
     if (ix->x) (void)hipFree(ix->x);
     if (ix->norms) (void)hipFree(ix->norms);
+    if (nl) {
+      (void)hipFree(ix->live);
+      ix->live = nl;
+      ix->live_words = nlw;
+    }
     ix->x = nx;
     ix->norms = nn;
     ix->norms_cap = ncap;
@@ -1277,6 +1465,7 @@ int eioku_index_attach(eioku_index* ix, float* x_dev, long long n, void* stream_
   EIOKU_REQUIRE(ix && x_dev && n >= 0, "bad argument");
   EIOKU_REQUIRE(((uintptr_t)x_dev & 15) == 0, "attached buffer must be 16-byte aligned");
   if (ix->x && !ix->attached) (void)hipFree(ix->x);
+  forget_removals(ix);
   ix->x = x_dev;
   ix->attached = true;
   ix->n = n;
@@ -1298,10 +1487,13 @@ namespace {
 // The register-tile kernels (k_flat_l2 / k_flat_l2_bf) + k_topk_merge over rows of the index: a full search
 // (sample_slabs == 0) or an exact search of `sample_slabs` strided slabs of `sample_rows` rows each (the scan
 // path's bound).  All pointers are device pointers.  gate (optional): device word, the launches are no-ops when 0.
+// sel_route (K9f): 0 = no selector; 1 = masked walk over ix->ew; 2 = the tile list ix->tlist / ix->meta.
 int legacy_search(eioku_index* ix, const float* dq, int nq, int k, const float* lbd, const long long* lbi, float* dD,
-                  long long* dI, const int* gate, int sample_slabs, long long sample_rows, bool prof, hipStream_t stream) {
+                  long long* dI, const int* gate, int sample_slabs, long long sample_rows, bool prof, hipStream_t stream,
+                  int sel_route = 0) {
   const int d = ix->d;
-  const int K = k == 1 ? 1 : (k <= 16 ? 16 : 32);  // k == 1: coarse assignment (k-means / IVF), a single compare per row
+  // k == 1: coarse assignment (k-means / IVF), a single compare per row; it is never given a selector
+  const int K = k == 1 && !sel_route ? 1 : (k <= 16 ? 16 : 32);
   const int qtiles = (nq + kQT - 1) / kQT;
   // wide: 4 query tiles share every staged row tile (one HBM pass per 128 queries)
   // two query tiles: two narrow passes (all 4 waves of every workgroup busy, 2 x 3.6 ms at 10 M x 384) beat one
@@ -1313,6 +1505,17 @@ int legacy_search(eioku_index* ix, const float* dq, int nq, int k, const float* 
     rpb = sample_rows;
     slabs = sample_slabs;
     stride = ix->n / sample_slabs;
+  } else if (sel_route == 2) {
+    // shares of the tile list, not slabs of rows: at most 64 of them, so that the merge is the heads-only one (the
+    // route is for selectors that leave few tiles; partial ids are global rows: stride 0)
+    const long long tiles = (ix->n + kRT - 1) / kRT;
+    slabs = (long long)num_cus() * 2 / ygroups;
+    if (slabs > 64) slabs = 64;
+    const long long per_wg = wide ? 1 : kWaves;
+    if (slabs > (tiles + per_wg - 1) / per_wg) slabs = (tiles + per_wg - 1) / per_wg;
+    if (slabs < 1) slabs = 1;
+    rpb = ix->n;
+    stride = 0;
   } else {
     // One workgroup is resident per CU (the query tile fills the register file), and a slab that is too
     // short never leaves the phase where most rows still enter some lane's top-K (the insertion path runs
@@ -1347,13 +1550,24 @@ int legacy_search(eioku_index* ix, const float* dq, int nq, int k, const float* 
   a.lbi = lbi;
   a.slab_stride = stride;
   a.gate = gate;
+  a.sel = sel_route ? ix->ew : nullptr;
+  a.list = sel_route == 2 ? ix->tlist : nullptr;
+  a.meta = sel_route == 2 ? ix->meta : nullptr;
   dim3 grid((unsigned)slabs, (unsigned)ygroups);
   if (prof) prof_start(EIOKU_PROF_KNN, stream);
   // wide searches (nq > 64) with k <= 16 over d in {128, 256, 384}: split-bf16 kernel (see k_flat_l2_bf); a bounded
   // search (lbd) stays on the exact-fp32 kernels so that successive rounds see bit-identical distances
   rc = -1;
-  if (wide && K == 16 && !lbd) rc = launch_search_bf<16>(d, a, grid, stream);
+  if (wide && K == 16 && !lbd && !sel_route) rc = launch_search_bf<16>(d, a, grid, stream);
   if (rc != -1) {
+  } else if (sel_route) {  // exact-fp32 kernels, selector instantiations
+    if (sel_route == 1) {
+      if (wide) rc = K == 16 ? launch_search_k<16, true, 1>(d, a, grid, stream) : launch_search_k<32, true, 1>(d, a, grid, stream);
+      else rc = K == 16 ? launch_search_k<16, false, 1>(d, a, grid, stream) : launch_search_k<32, false, 1>(d, a, grid, stream);
+    } else {
+      if (wide) rc = K == 16 ? launch_search_k<16, true, 2>(d, a, grid, stream) : launch_search_k<32, true, 2>(d, a, grid, stream);
+      else rc = K == 16 ? launch_search_k<16, false, 2>(d, a, grid, stream) : launch_search_k<32, false, 2>(d, a, grid, stream);
+    }
   } else if (K == 1) rc = wide ? launch_search_k<1, true>(d, a, grid, stream) : launch_search_k<1, false>(d, a, grid, stream);
   else if (wide) rc = K == 16 ? launch_search_k<16, true>(d, a, grid, stream) : launch_search_k<32, true>(d, a, grid, stream);
   else rc = K == 16 ? launch_search_k<16, false>(d, a, grid, stream) : launch_search_k<32, false>(d, a, grid, stream);
@@ -1604,8 +1818,36 @@ int scan_search(eioku_index* ix, const float* dq, int nq, int k, float* dD, long
   return legacy_search(ix, dq, nq, k, nullptr, nullptr, dD, dI, overflow, 0, 0, false, stream);
 }
 
+// K9f: sel (host or device per sel_mem) -> ix->ew, ix->tlist, ix->meta on the stream
+int prepare_selector(eioku_index* ix, const unsigned* sel, int sel_mem, hipStream_t stream) {
+  const int nwords = (int)((ix->n + 31) / 32);
+  const int nblocks = (nwords + 1023) / 1024;
+  int rc;
+  const unsigned* dsel = sel;
+  if (sel_mem == EIOKU_MEM_HOST) {
+    rc = grow(&ix->selbuf, &ix->selcap, (size_t)nwords * sizeof(unsigned));
+    if (rc) return rc;
+    EIOKU_HIP_CHECK(hipMemcpyAsync(ix->selbuf, sel, (size_t)nwords * sizeof(unsigned), hipMemcpyHostToDevice, stream));
+    dsel = ix->selbuf;
+  }
+  rc = grow(&ix->ew, &ix->ewcap, (size_t)nwords * sizeof(unsigned));
+  if (rc) return rc;
+  rc = grow(&ix->tlist, &ix->tlcap, (size_t)nwords * sizeof(int));
+  if (rc) return rc;
+  rc = grow(&ix->bcount, &ix->bccap, (size_t)nblocks * sizeof(int));
+  if (rc) return rc;
+  if (!ix->meta) EIOKU_HIP_CHECK(hipMalloc((void**)&ix->meta, 4 * sizeof(int)));
+  hipLaunchKernelGGL(k_sel_words, dim3(nblocks), dim3(1024), 0, stream, dsel, (const unsigned*)ix->live, ix->n, nwords, ix->ew,
+                     ix->bcount);
+  EIOKU_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_sel_list, dim3(nblocks), dim3(1024), 0, stream, (const unsigned*)ix->ew, (const int*)ix->bcount, nwords,
+                     ix->tlist, ix->meta, (long long)ix->sel_list_ppm);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
 int search_impl(eioku_index* ix, const float* q, int nq, int k, const float* lbD, const int64_t* lbI, float* D,
-                int64_t* I, int mem, void* stream_) {
+                int64_t* I, int mem, void* stream_, const unsigned* sel = nullptr, int sel_mem = EIOKU_MEM_DEVICE) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(ix && nq >= 0 && k >= 1, "bad argument");
   EIOKU_REQUIRE(k <= 32, "k=%d not supported (k <= 32)", k);
@@ -1651,9 +1893,26 @@ int search_impl(eioku_index* ix, const float* q, int nq, int k, const float* lbD
     dD = ix->dout;
     dI = ix->iout;
   }
-  const bool scan = ix->scan_mode != 0 && !dlbD && nq >= ix->scan_min_nq && k <= 32 && ix->n >= ix->scan_min_rows &&
-                    (d == 128 || d == 256 || d == 384);
-  if (scan) {
+  const bool filtered = sel != nullptr && ix->n > 0;
+  const bool scan = ix->scan_mode != 0 && !dlbD && !filtered && nq >= ix->scan_min_nq && k <= 32 &&
+                    ix->n >= ix->scan_min_rows && (d == 128 || d == 256 || d == 384);
+  if (filtered) {
+    // K9f.  The scan path is not taken: its bound tau_q is the k-th best of a SAMPLE of the rows, and a bound taken
+    // over ineligible rows is no bound for the eligible ones.  Both routes run the exact-fp32 kernels, so a selector
+    // composes with the search_after bound and successive rounds see bit-identical distances.  Which route runs is
+    // decided on the device (k_sel_list -> meta[1], meta[2]): both are queued, one of them finds its gate at 0.
+    rc = prepare_selector(ix, sel, sel_mem, stream);
+    if (rc) return rc;
+    const int ppm = ix->sel_list_ppm;
+    if (ppm > 0) {
+      rc = legacy_search(ix, dq, nq, k, dlbD, dlbI, dD, dI, ppm >= 1000000 ? nullptr : ix->meta + 1, 0, 0, true, stream, 2);
+      if (rc) return rc;
+    }
+    if (ppm < 1000000) {
+      rc = legacy_search(ix, dq, nq, k, dlbD, dlbI, dD, dI, ppm <= 0 ? nullptr : ix->meta + 2, 0, 0, ppm <= 0, stream, 1);
+      if (rc) return rc;
+    }
+  } else if (scan) {
     // groups of <= 1024 queries: their planes (<= 1.5 MB) stay in every XCD's L2 while the rows stream past
     for (int q0 = 0; q0 < nq; q0 += 1024) {
       const int g = nq - q0 < 1024 ? nq - q0 : 1024;
@@ -1691,9 +1950,50 @@ int eioku_index_search_after(eioku_index* ix, const float* q, int nq, int k, con
   return search_impl(ix, q, nq, k, after_D, after_I, D, I, mem, stream_);
 }
 
+int eioku_index_search_sel(eioku_index* ix, const float* q, int nq, int k, const uint32_t* sel_words, int sel_mem,
+                           const float* after_D, const int64_t* after_I, float* D, int64_t* I, int mem, void* stream_) {
+  EIOKU_REQUIRE(!sel_words || sel_mem == EIOKU_MEM_HOST || sel_mem == EIOKU_MEM_DEVICE, "bad selector mem flag %d", sel_mem);
+  return search_impl(ix, q, nq, k, after_D, after_I, D, I, mem, stream_, (const unsigned*)sel_words, sel_mem);
+}
+
+int eioku_index_remove_ids(eioku_index* ix, const int64_t* ids, long long n_ids, int mem, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(ix && n_ids >= 0 && (ids || n_ids == 0), "bad argument");
+  EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
+  if (n_ids == 0 || ix->n == 0) return EIOKU_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ix->live) {
+    const long long rows = ix->cap > ix->n ? ix->cap : ix->n;
+    const size_t words = (size_t)((rows + 31) / 32);
+    EIOKU_HIP_CHECK(hipMalloc((void**)&ix->live, words * sizeof(unsigned)));
+    ix->live_words = words;
+    EIOKU_HIP_CHECK(hipMemsetAsync(ix->live, 0xFF, words * sizeof(unsigned), stream));
+  }
+  if (!ix->removed_dev) EIOKU_HIP_CHECK(hipMalloc((void**)&ix->removed_dev, sizeof(int)));
+  EIOKU_HIP_CHECK(hipMemsetAsync(ix->removed_dev, 0, sizeof(int), stream));
+  const long long* dids = (const long long*)ids;
+  if (mem == EIOKU_MEM_HOST) {
+    int rc = grow(&ix->idbuf, &ix->idcap, (size_t)n_ids * sizeof(long long));
+    if (rc) return rc;
+    EIOKU_HIP_CHECK(hipMemcpyAsync(ix->idbuf, ids, (size_t)n_ids * sizeof(long long), hipMemcpyHostToDevice, stream));
+    dids = ix->idbuf;
+  }
+  hipLaunchKernelGGL(k_remove_ids, dim3((unsigned)((n_ids + 255) / 256)), dim3(256), 0, stream, dids, n_ids, ix->n,
+                     ix->planes_n, ix->live, ix->norms, ix->hnorm, ix->removed_dev);
+  EIOKU_LAUNCH_CHECK();
+  int now = 0;
+  EIOKU_HIP_CHECK(hipMemcpyAsync(&now, ix->removed_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
+  EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
+  ix->removed += now;
+  return EIOKU_OK;
+}
+
 int eioku_index_set_param(eioku_index* ix, const char* name, long long value) {
   EIOKU_REQUIRE(ix && name, "bad argument");
-  if (!strcmp(name, "scan_mode")) {
+  if (!strcmp(name, "sel_list_ppm")) {
+    EIOKU_REQUIRE(value >= 0 && value <= 1000000, "sel_list_ppm must be in [0, 1000000] (0: never the tile list, 1000000: always)");
+    ix->sel_list_ppm = (int)value;
+  } else if (!strcmp(name, "scan_mode")) {
     EIOKU_REQUIRE(value == 0 || value == 1, "scan_mode is 0 (register-tile kernels only) or 1 (scan path for wide searches)");
     ix->scan_mode = (int)value;
   } else if (!strcmp(name, "scan_cap")) {

@@ -249,6 +249,8 @@ class Yolov8Detector:
         if dev and not keep_on_device:
             dets = dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det)
             counts = counts.cpu().numpy()
+        if not (dev and keep_on_device):
+            _clear_unused_rows(dets, counts)
         return dets, counts
 
 
@@ -353,6 +355,13 @@ def letterbox_f16(frames_bgr, imgsz: int = 640):
     return out, plan
 
 
+def _clear_unused_rows(dets: np.ndarray, counts: np.ndarray) -> None:
+    """K7 writes ``counts[i]`` rows per image and nothing else: rows past the count are whatever the buffer held (a
+    recycled ``torch.empty`` block is not zero).  Host-side results carry zeros there, as the host staging path's do."""
+    for i, c in enumerate(counts):
+        dets[i, int(c):] = 0
+
+
 def postprocess(box_maps, cls_maps, plan: LetterboxPlan, conf: float, iou: float = 0.7, max_det: int = 300):
     """K6+K7 alone on CUDA fp32 Detect maps (NHWC) -> (dets structured array, counts)."""
     import torch
@@ -371,4 +380,6 @@ def postprocess(box_maps, cls_maps, plan: LetterboxPlan, conf: float, iou: float
     _lib.check(lib.eioku_yolo_postprocess(bp, cp, n, hl, wl, nc, float(conf), float(iou), int(max_det),
                                           float(np.float32(plan.gain)), plan.pad_x, plan.pad_y, plan.src_w, plan.src_h,
                                           ptr(dets), ptr(counts), current_stream(box_maps[0])), "eioku_yolo_postprocess")
-    return dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy()
+    dets, counts = dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy()
+    _clear_unused_rows(dets, counts)
+    return dets, counts

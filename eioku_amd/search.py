@@ -21,6 +21,48 @@ from . import _lib
 from ._buffers import current_stream, on_device, ptr
 
 
+class RowSelector:
+    """Which rows a search may return: ``ceil(n/32)`` little-endian 32-bit words, bit ``r % 32`` of word ``r // 32`` set =
+    row ``r`` eligible (one word = one 32-row MFMA tile of the kNN kernels).  Packed on the host with numpy; one
+    selector serves all queries of a call (FAISS ``SearchParameters.sel``)."""
+
+    def __init__(self, words: np.ndarray, n: int):
+        words = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        if words.shape[0] != (int(n) + 31) // 32:
+            raise ValueError(f"a selector over {n} rows has {(int(n) + 31) // 32} words, got {words.shape[0]}")
+        self.words, self.n = words, int(n)
+
+    @classmethod
+    def from_mask(cls, mask) -> "RowSelector":
+        mask = np.asarray(mask, dtype=bool).reshape(-1)
+        n = mask.shape[0]
+        padded = np.zeros(((n + 31) // 32) * 32, dtype=bool)
+        padded[:n] = mask
+        return cls(np.packbits(padded, bitorder="little").view(np.uint32), n)
+
+    @classmethod
+    def from_ids(cls, ids, n: int) -> "RowSelector":
+        """Ids outside ``[0, n)`` are ignored; repeats are harmless."""
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        mask = np.zeros(int(n), dtype=bool)
+        mask[ids[(ids >= 0) & (ids < n)]] = True
+        return cls.from_mask(mask)
+
+    @classmethod
+    def from_ranges(cls, ranges, n: int) -> "RowSelector":
+        """Half-open row ranges ``[(lo, hi), ...]``, clipped to ``[0, n)``."""
+        mask = np.zeros(int(n), dtype=bool)
+        for lo, hi in ranges:
+            mask[max(0, int(lo)):max(0, min(int(n), int(hi)))] = True
+        return cls.from_mask(mask)
+
+    def to_mask(self) -> np.ndarray:
+        return np.unpackbits(self.words.view(np.uint8), bitorder="little")[:self.n].astype(bool)
+
+    def count(self) -> int:
+        return int(self.to_mask().sum())
+
+
 class IndexFlatL2:
     """Exact squared-L2 index resident in HBM (d in {64,128,256,384,512}, k <= 32)."""
 
@@ -37,6 +79,57 @@ class IndexFlatL2:
     @property
     def ntotal(self) -> int:
         return int(self._lib.eioku_index_ntotal(self._h))
+
+    @property
+    def nlive(self) -> int:
+        """Rows a search can return: ``ntotal`` minus the rows taken out by :meth:`remove_ids`."""
+        return int(self._lib.eioku_index_nlive(self._h))
+
+    def remove_ids(self, ids) -> int:
+        """Take rows out of every later search without rebuilding anything; returns how many were live until now.
+
+        Ids never shift (unlike FAISS ``remove_ids``): ``ntotal`` stays, later ``add()`` calls continue with fresh ids.
+        Unknown and repeated ids are ignored.  ``ids``: int64 numpy array / sequence, or a CUDA int64 tensor."""
+        before = self.nlive
+        if on_device(ids):
+            import torch
+
+            ids = ids.to(torch.int64).contiguous().view(-1)
+            n_ids, mem = int(ids.numel()), _lib.MEM_DEVICE
+        else:
+            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+            n_ids, mem = int(ids.shape[0]), _lib.MEM_HOST
+        if n_ids:
+            _lib.check(self._lib.eioku_index_remove_ids(self._h, ptr(ids), n_ids, mem, current_stream(ids)),
+                       "eioku_index_remove_ids")
+        return before - self.nlive
+
+    def _selector(self, sel, q):
+        """-> (keep-alive object, pointer, mem flag) of a selector argument, length-checked against ``ntotal``."""
+        if sel is None:
+            return None, None, _lib.MEM_HOST
+        nwords = (self.ntotal + 31) // 32
+        if isinstance(sel, RowSelector):
+            if sel.n != self.ntotal:
+                raise ValueError(f"selector covers {sel.n} rows, the index holds {self.ntotal}")
+            sel = sel.words
+        if on_device(sel):
+            import torch
+
+            if sel.dtype not in (torch.int32, torch.uint32) or sel.dim() != 1 or not sel.is_contiguous():
+                raise ValueError("a device selector is a contiguous 1-d int32 / uint32 tensor of packed words")
+            if int(sel.numel()) != nwords:
+                raise ValueError(f"a selector over {self.ntotal} rows has {nwords} words, got {int(sel.numel())}")
+            return sel, ptr(sel), _lib.MEM_DEVICE
+        sel = np.asarray(sel)
+        if sel.dtype != np.uint32 or sel.ndim != 1:
+            raise ValueError("a host selector is a 1-d uint32 array of packed words (see RowSelector)")
+        if sel.shape[0] != nwords:
+            raise ValueError(f"a selector over {self.ntotal} rows has {nwords} words, got {sel.shape[0]}")
+        sel = np.ascontiguousarray(sel)
+        if nwords == 0:
+            return None, None, _lib.MEM_HOST
+        return sel, ptr(sel), _lib.MEM_HOST
 
     def add(self, x) -> None:
         """Append vectors: float32 ``(n,d)`` numpy (staged over PCIe) or CUDA tensor (device copy)."""
@@ -60,14 +153,18 @@ class IndexFlatL2:
         _lib.check(self._lib.eioku_index_reset(self._h), "eioku_index_reset")
         self._attached = None
 
-    def search(self, q, k: int):
+    def search(self, q, k: int, sel=None):
         """``(D, I)``: float32 ``(nq,k)`` squared distances ascending, int64 ``(nq,k)`` ids (-1 = none).
 
         numpy queries -> numpy results (synchronous); CUDA queries -> CUDA results (asynchronous).
+        ``sel``: optional :class:`RowSelector` or packed ``uint32`` words (numpy, or a CUDA int32 / uint32 tensor): only
+        live rows whose bit is set are candidates.
         """
         nq, d = (int(s) for s in q.shape)
         if d != self.d:
             raise ValueError(f"expected dimension {self.d}, got {d}")
+        if sel is not None:
+            return self._search_sel(q, k, sel, None, None)
         if on_device(q):
             import torch
 
@@ -83,12 +180,42 @@ class IndexFlatL2:
                    "eioku_index_search")
         return D, I
 
-    def search_after(self, q, k: int, after_D, after_I):
+    def _search_sel(self, q, k: int, sel, after_D, after_I):
+        """``eioku_index_search_sel``: selector and (optional) ``search_after`` bound in one call."""
+        nq = int(q.shape[0])
+        keep, sel_ptr, sel_mem = self._selector(sel, q)
+        if on_device(q):
+            import torch
+
+            D = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+            I = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+            if after_D is not None:
+                after_D = after_D.to(torch.float32).contiguous()
+                after_I = after_I.to(torch.int64).contiguous()
+            mem = _lib.MEM_DEVICE
+        else:
+            q = np.ascontiguousarray(q, dtype=np.float32)
+            if after_D is not None:
+                after_D = np.ascontiguousarray(after_D, dtype=np.float32)
+                after_I = np.ascontiguousarray(after_I, dtype=np.int64)
+            D = np.empty((nq, k), dtype=np.float32)
+            I = np.empty((nq, k), dtype=np.int64)
+            mem = _lib.MEM_HOST
+        _lib.check(self._lib.eioku_index_search_sel(self._h, ptr(q), nq, int(k), sel_ptr, sel_mem,
+                                                    None if after_D is None else ptr(after_D),
+                                                    None if after_I is None else ptr(after_I), ptr(D), ptr(I), mem,
+                                                    current_stream(q)), "eioku_index_search_sel")
+        del keep
+        return D, I
+
+    def search_after(self, q, k: int, after_D, after_I, sel=None):
         """The next ``k`` results after a previous answer: rows with ``(distance, id) > (after_D[q], after_I[q])``
-        in the result order (``after_*``: shape ``(nq,)``, same side of PCIe as ``q``)."""
+        in the result order (``after_*``: shape ``(nq,)``, same side of PCIe as ``q``); ``sel`` as in :meth:`search`."""
         nq, d = (int(s) for s in q.shape)
         if d != self.d:
             raise ValueError(f"expected dimension {self.d}, got {d}")
+        if sel is not None:
+            return self._search_sel(q, k, sel, after_D, after_I)
         if on_device(q):
             import torch
 
@@ -108,18 +235,18 @@ class IndexFlatL2:
                                                       ptr(I), mem, current_stream(q)), "eioku_index_search_after")
         return D, I
 
-    def search_many(self, q, k: int):
+    def search_many(self, q, k: int, sel=None):
         """``search`` for any ``k``: rounds of at most 32 results chained with :meth:`search_after`."""
         if k <= 32:
-            return self.search(q, k)
+            return self.search(q, k, sel)
         parts_d, parts_i = [], []
         got = 0
         while got < k:
             kk = min(32, k - got)
             if not parts_d:
-                D, I = self.search_after(q, kk, *self._before_everything(q))
+                D, I = self.search_after(q, kk, *self._before_everything(q), sel=sel)
             else:
-                D, I = self.search_after(q, kk, parts_d[-1][:, -1], parts_i[-1][:, -1])
+                D, I = self.search_after(q, kk, parts_d[-1][:, -1], parts_i[-1][:, -1], sel=sel)
             parts_d.append(D)
             parts_i.append(I)
             got += kk
@@ -140,7 +267,7 @@ class IndexFlatL2:
         return np.full((nq,), -1.0, np.float32), np.full((nq,), -1, np.int64)
 
     def set_param(self, name: str, value: int) -> None:
-        """Knobs of the wide-search path (``eioku_index_set_param``): scan_mode, scan_cap, scan_min_rows, ..."""
+        """Knobs of the search paths (``eioku_index_set_param``): scan_mode, scan_cap, scan_min_rows, ..., sel_list_ppm."""
         _lib.check(self._lib.eioku_index_set_param(self._h, name.encode(), int(value)), f"eioku_index_set_param({name})")
 
     def close(self):

@@ -13,11 +13,15 @@ from the ``tokenizers`` library (no network: the vocabulary file ships with the 
 from __future__ import annotations
 
 import json
+import logging
 import struct
 from dataclasses import asdict, dataclass
+from datetime import datetime, timezone
 from pathlib import Path
 
 import numpy as np
+
+logger = logging.getLogger(__name__)
 
 MAGIC = b"EIOKUIDX1\n"
 
@@ -101,86 +105,214 @@ class SearchResult:
     thumbnail_path: str | None = None
 
 
+FILTER_KEYS = ("video_id", "created_from", "created_to", "min_duration", "max_duration", "start_time", "end_time")
+
+
+def _epoch(value, end_of_day: bool = False) -> float:
+    """ISO-8601 date / datetime string (or epoch seconds) -> epoch seconds; NaN when it cannot be read.  A naive value is
+    UTC.  ``end_of_day``: a date without a time stands for its last instant (an inclusive upper bound covers the day)."""
+    if value is None:
+        return float("nan")
+    if isinstance(value, (int, float)):
+        return float(value)
+    try:
+        text = str(value).strip()
+        dt = datetime.fromisoformat(text[:-1] + "+00:00" if text.endswith(("Z", "z")) else text)
+    except ValueError:
+        return float("nan")
+    if dt.tzinfo is None:
+        dt = dt.replace(tzinfo=timezone.utc)
+    t = dt.timestamp()
+    if end_of_day and len(text) <= 10:
+        t += 86400.0 - 1e-3
+    return t
+
+
+def _number(value) -> float:
+    try:
+        return float(value)
+    except (TypeError, ValueError):
+        return float("nan")
+
+
 class VectorStore:
     """design.md 2.2 + "single .index file per library" (design.md:37): embeddings and segment metadata.
 
-    The authoritative copy lives on the host (fp32 rows + metadata, what the file holds); the HIP index over it is
-    (re)built lazily before a search, so indexing / deleting / persistence need no GPU."""
+    The authoritative copy lives on the host (fp32 rows + metadata, what the file holds) and is COMPACT: live rows only,
+    in insertion order.  The HIP index over it is built lazily by the first search; from then on ``index_segment(s)``
+    appends to it (``IndexFlatL2.add``) and ``delete_by_video_id`` takes rows out of it (``remove_ids``: device ids never
+    shift), so the store keeps the device row of every host row.  When removed device rows outnumber the live ones the
+    device index is dropped once and rebuilt compactly by the next search: a search streams dead rows too, and this
+    policy keeps that within 2x of a compact index.  Indexing / deleting / persistence need no GPU before the first
+    search.
 
-    def __init__(self, d: int = 384):
+    ``filters`` (all optional, combined with AND; a row whose metadata lacks a filtered key does not match):
+    ``video_id`` (id or list of ids); ``created_from`` / ``created_to`` (ISO-8601 date or datetime strings, inclusive,
+    against metadata ``file_created_at``); ``min_duration`` / ``max_duration`` (seconds, inclusive, against metadata
+    ``video_duration``); ``start_time`` / ``end_time`` (seconds: the segment's own span overlaps ``[start_time,
+    end_time]``).  Unknown keys are ignored with a logged warning.  The filter is evaluated on host columns, packed
+    into one :class:`eioku_amd.search.RowSelector` and applied inside ONE ``search_many`` call on the GPU."""
+
+    def __init__(self, d: int = 384, index_factory=None):
         self.d = d
         self._rows: list[np.ndarray] = []
         self._meta: list[dict] = []
+        # host columns beside _meta (what filters are evaluated on)
+        self._vid: list[int] = []          # video ordinal
+        self._created: list[float] = []    # file_created_at, epoch seconds (NaN: absent)
+        self._duration: list[float] = []   # video_duration, seconds (NaN: absent)
+        self._span: list[tuple[float, float]] = []  # the segment's own start / end
+        self._video_ord: dict = {}
+        self._cols = None                  # numpy views of the columns, rebuilt after a change
+        # device side
+        self._index_factory = index_factory
         self._index = None
+        self._dev_row: list[int] = []      # device row of every host row (valid while _index is not None)
+        self._dev_removed = 0              # device rows taken out by remove_ids
 
     def __len__(self) -> int:
         return len(self._meta)
 
-    def index_segment(self, segment_id: str, embedding, metadata: dict) -> bool:
-        e = np.asarray(embedding, dtype=np.float32).reshape(-1)
-        if e.shape[0] != self.d:
-            raise ValueError(f"expected a {self.d}-d embedding, got {e.shape[0]}")
+    def _append_host(self, segment_id: str, e: np.ndarray, metadata: dict) -> None:
+        m = dict(metadata, segment_id=segment_id)
         self._rows.append(e)
-        self._meta.append(dict(metadata, segment_id=segment_id))
-        self._drop_index()
-        return True
+        self._meta.append(m)
+        self._vid.append(self._video_ord.setdefault(m.get("video_id"), len(self._video_ord)) if m.get("video_id") is not None else -1)
+        self._created.append(_epoch(m.get("file_created_at")))
+        self._duration.append(_number(m.get("video_duration")) if m.get("video_duration") is not None else float("nan"))
+        self._span.append((_number(m.get("start_time")) if m.get("start_time") is not None else float("nan"),
+                           _number(m.get("end_time")) if m.get("end_time") is not None else float("nan")))
+        self._cols = None
+
+    def index_segment(self, segment_id: str, embedding, metadata: dict) -> bool:
+        return self.index_segments([segment_id], np.asarray(embedding, dtype=np.float32).reshape(1, -1), [metadata]) == 1
 
     def index_segments(self, segment_ids: list[str], embeddings, metadata: list[dict]) -> int:
-        for s, e, m in zip(segment_ids, np.asarray(embeddings, dtype=np.float32), metadata):
-            self.index_segment(s, e, m)
+        emb = np.asarray(embeddings, dtype=np.float32)
+        emb = emb.reshape(len(segment_ids), -1) if len(segment_ids) else emb.reshape(0, self.d)
+        if emb.shape[1] != self.d:
+            raise ValueError(f"expected a {self.d}-d embedding, got {emb.shape[1]}")
+        for s, e, m in zip(segment_ids, emb, metadata):
+            self._append_host(s, e.copy(), m)
+        if self._index is not None and len(segment_ids):  # one upload of the new rows; the rest of the index stays
+            base = int(self._index.ntotal)
+            self._index.add(np.ascontiguousarray(emb))
+            self._dev_row.extend(range(base, base + len(segment_ids)))
         return len(segment_ids)
 
     def delete_by_video_id(self, video_id: str) -> bool:
-        keep = [i for i, m in enumerate(self._meta) if m.get("video_id") != video_id]
-        removed = len(keep) != len(self._meta)
-        self._rows = [self._rows[i] for i in keep]
-        self._meta = [self._meta[i] for i in keep]
-        self._drop_index()
-        return removed
+        gone = [i for i, m in enumerate(self._meta) if m.get("video_id") == video_id]
+        if not gone:
+            return False
+        if self._index is not None:
+            self._index.remove_ids(np.asarray([self._dev_row[i] for i in gone], dtype=np.int64))
+            self._dev_removed += len(gone)
+        dead = set(gone)
+        for name in ("_rows", "_meta", "_vid", "_created", "_duration", "_span") + (("_dev_row",) if self._index is not None else ()):
+            col = getattr(self, name)
+            setattr(self, name, [v for i, v in enumerate(col) if i not in dead])
+        self._cols = None
+        if self._index is not None and self._dev_removed > len(self._meta):
+            self._drop_index()  # more dead rows than live ones: rebuild compactly at the next search
+        return True
 
     def _drop_index(self):
         if self._index is not None:
             self._index.close()
             self._index = None
+        self._dev_row = []
+        self._dev_removed = 0
+
+    def _ensure_index(self):
+        if self._index is None:
+            if self._index_factory is not None:
+                self._index = self._index_factory(self.d)
+            else:
+                from .search import IndexFlatL2
+
+                self._index = IndexFlatL2(self.d)
+            self._index.add(self.matrix())
+            self._dev_row = list(range(len(self._meta)))
+            self._dev_removed = 0
+        return self._index
+
+    def device_to_host_rows(self) -> np.ndarray:
+        """int64 ``[device rows]``: the host row of every device row, -1 for rows that were removed."""
+        n_dev = len(self._dev_row) + self._dev_removed
+        out = np.full(n_dev, -1, np.int64)
+        out[np.asarray(self._dev_row, dtype=np.int64)] = np.arange(len(self._dev_row), dtype=np.int64)
+        return out
 
     def matrix(self) -> np.ndarray:
         return np.stack(self._rows).astype(np.float32) if self._rows else np.zeros((0, self.d), np.float32)
 
+    def _columns(self):
+        if self._cols is None:
+            span = np.asarray(self._span, dtype=np.float64).reshape(-1, 2)
+            self._cols = (np.asarray(self._vid, dtype=np.int64), np.asarray(self._created, dtype=np.float64),
+                          np.asarray(self._duration, dtype=np.float64), span[:, 0], span[:, 1])
+        return self._cols
+
+    def eligible_rows(self, filters: dict | None):
+        """Boolean mask over the host rows that ``filters`` admits, or ``None`` when nothing is filtered."""
+        if not filters:
+            return None
+        for key in filters:
+            if key not in FILTER_KEYS:
+                logger.warning("VectorStore.search: unknown filter key %r ignored (known: %s)", key, ", ".join(FILTER_KEYS))
+        active = {k: v for k, v in filters.items() if k in FILTER_KEYS and v is not None}
+        if not active:
+            return None
+        vid, created, duration, seg_start, seg_end = self._columns()
+        ok = np.ones(len(self._meta), dtype=bool)
+        with np.errstate(invalid="ignore"):  # NaN (absent metadata) compares false: the row does not match
+            if "video_id" in active:
+                v = active["video_id"]
+                wanted = v if isinstance(v, (list, tuple, set)) else [v]
+                ords = [self._video_ord[w] for w in wanted if w in self._video_ord]
+                ok &= np.isin(vid, np.asarray(ords, dtype=np.int64))
+            if "created_from" in active:
+                ok &= created >= _epoch(active["created_from"])
+            if "created_to" in active:
+                ok &= created <= _epoch(active["created_to"], end_of_day=True)
+            if "min_duration" in active:
+                ok &= duration >= float(active["min_duration"])
+            if "max_duration" in active:
+                ok &= duration <= float(active["max_duration"])
+            if "start_time" in active:
+                ok &= seg_end >= float(active["start_time"])
+            if "end_time" in active:
+                ok &= seg_start <= float(active["end_time"])
+        return ok
+
     def search(self, query_embedding, top_k: int = 10, filters: dict | None = None) -> list[tuple[float, dict]]:
         """``[(squared L2 distance, metadata)]`` ascending, up to ``top_k`` entries (any ``top_k``: rounds of 32 chained by
-        ``IndexFlatL2.search_many``).  ``filters``: ``{"video_id": id or [ids]}``; the fetch grows until ``top_k`` rows of
-        the wanted videos are found or the index is exhausted, so a narrow filter still returns what the videos hold."""
+        ``IndexFlatL2.search_many``).  ``filters``: see the class; the matching rows become a row selector and the GPU
+        returns the exact top-k of those rows in one ``search_many`` call, however narrow the filter is."""
         if top_k < 1:
             raise ValueError(f"top_k must be >= 1, got {top_k}")
         if not self._meta:
             return []
-        if self._index is None:
-            from .search import IndexFlatL2
-
-            self._index = IndexFlatL2(self.d)
-            self._index.add(self.matrix())
+        ok = self.eligible_rows(filters)
+        n_ok = len(self._meta) if ok is None else int(ok.sum())
+        if n_ok == 0:
+            return []
+        index = self._ensure_index()
         q = np.asarray(query_embedding, dtype=np.float32).reshape(1, self.d)
-        allowed = None
-        if filters and filters.get("video_id") is not None:
-            v = filters["video_id"]
-            allowed = set(v) if isinstance(v, (list, tuple, set)) else {v}
-        n = len(self._meta)
-        fetch = min(n, top_k if allowed is None else max(32, 4 * top_k))
-        while True:
-            D, I = self._index.search_many(q, fetch)
-            out = []
-            for dist, i in zip(D[0], I[0]):
-                if i < 0:
-                    break
-                m = self._meta[int(i)]
-                if allowed is not None and m.get("video_id") not in allowed:
-                    continue
-                out.append((float(dist), m))
-                if len(out) == top_k:
-                    break
-            if len(out) == top_k or fetch >= n:
-                return out
-            fetch = min(n, fetch * 4)
+        if ok is None:
+            D, I = index.search_many(q, min(n_ok, top_k))
+        else:
+            from .search import RowSelector
+
+            dev_rows = np.asarray(self._dev_row, dtype=np.int64)[ok]
+            D, I = index.search_many(q, min(n_ok, top_k), sel=RowSelector.from_ids(dev_rows, int(index.ntotal)))
+        host = self.device_to_host_rows() if self._dev_removed else None
+        out = []
+        for dist, i in zip(D[0], I[0]):
+            if i < 0:
+                break
+            out.append((float(dist), self._meta[int(i) if host is None else int(host[int(i)])]))
+        return out
 
     # ---- the .index file -----------------------------------------------------------------------------
     def save(self, path: str | Path) -> None:
@@ -204,8 +336,8 @@ class VectorStore:
         if len(meta) != n:
             raise ValueError(f"{path}: {n} rows but {len(meta)} metadata records")
         st = cls(d)
-        st._rows = [r.copy() for r in x]
-        st._meta = meta
+        for r, m in zip(x, meta):
+            st._append_host(m.get("segment_id"), r.copy(), m)
         return st
 
 
@@ -217,7 +349,8 @@ class SemanticSearchEngine:
 
     def index_transcript(self, video_id: str, segments: list[dict]) -> int:
         """``segments``: what ``transcribe_video`` returns (``model_manager.py:409-467``): dicts with ``text`` and
-        ``start`` / ``end`` seconds (or ``start_ms`` / ``end_ms``)."""
+        ``start`` / ``end`` seconds (or ``start_ms`` / ``end_ms``); optional ``file_created_at`` / ``video_duration`` make
+        the segment filterable by date and duration (see :class:`VectorStore`)."""
         texts = [s["text"] for s in segments]
         emb = self.generator.generate_batch_embeddings(texts)
         meta = []
@@ -226,6 +359,9 @@ class SemanticSearchEngine:
             end = s["end_ms"] / 1000.0 if "end_ms" in s else float(s.get("end", start))
             meta.append({"video_id": video_id, "start_time": start, "end_time": end, "text": s["text"],
                          "thumbnail_path": s.get("thumbnail_path")})
+            for key in ("file_created_at", "video_duration"):
+                if s.get(key) is not None:
+                    meta[-1][key] = s[key]
         return self.store.index_segments([f"{video_id}_seg{i}" for i in range(len(segments))], emb, meta)
 
     def search(self, query: str, filters: dict | None = None, top_k: int = 10) -> list[SearchResult]:

@@ -111,9 +111,11 @@ def result_to_envelopes(result_dict: dict, task_id: str, task_type: str, video_i
     return envelopes
 
 
-def embed_segments(engine, video_id: str, segments: list[dict]) -> dict:
+def embed_segments(engine, video_id: str, segments: list[dict], config: dict | None = None) -> dict:
     """The ``segment_embedding`` task body: K8 over the transcript segments, vectors into the store, one result row per
-    segment (span = the segment's, payload = text + 384 floats) for the artifact table."""
+    segment (span = the segment's, payload = text + 384 floats) for the artifact table.  ``file_created_at`` /
+    ``video_duration`` of a segment dict, else of the job config, travel into the store's metadata when present (the
+    search filters ``created_from`` / ``created_to`` / ``min_duration`` / ``max_duration`` compare against them)."""
     texts = [s["text"] for s in segments]
     emb = engine.generator.generate_batch_embeddings(texts)
     engine.store.delete_by_video_id(video_id)  # a re-run replaces the video's vectors, it does not duplicate them
@@ -123,6 +125,10 @@ def embed_segments(engine, video_id: str, segments: list[dict]) -> dict:
         end_ms = int(s["end_ms"]) if "end_ms" in s else int(float(s.get("end", start_ms / 1000.0)) * 1000)
         meta.append({"video_id": video_id, "start_time": start_ms / 1000.0, "end_time": end_ms / 1000.0, "text": s["text"],
                      "thumbnail_path": s.get("thumbnail_path")})
+        for key in ("file_created_at", "video_duration"):
+            value = s.get(key, (config or {}).get(key))
+            if value is not None:
+                meta[-1][key] = value
         rows.append({"start_ms": start_ms, "end_ms": end_ms, "text": s["text"], "embedding": [float(v) for v in e]})
     engine.store.index_segments([f"{video_id}_seg{i}" for i in range(len(segments))], emb, meta)
     return {"embeddings": rows}
@@ -172,7 +178,7 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             if engine is None:
                 raise ValueError(f"{task_type} needs ctx['search_engine'] (eioku_amd.semantic.SemanticSearchEngine)")
             if task_type == "segment_embedding":
-                result = embed_segments(engine, video_id, segments)
+                result = embed_segments(engine, video_id, segments, config)
             else:  # one "topic" envelope per topic; segment_keywords are returned, not emitted
                 from .topics import TopicExtractor
 

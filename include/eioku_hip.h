@@ -256,7 +256,30 @@ int eioku_index_search(eioku_index_t* ix, const float* q, int nq, int k, float* 
  * the k <= 32 of one search: successive rounds on the exact-fp32 kernels see bit-identical distances). */
 int eioku_index_search_after(eioku_index_t* ix, const float* q, int nq, int k, const float* after_D,
                              const int64_t* after_I, float* D, int64_t* I, int mem, void* stream);
-/* Tuning / test knobs of the wide-search ("scan") path, see csrc/knn.hip: "scan_mode" 0 = register-tile kernels only,
+/* Row selectors and removal (K9f, see csrc/knn.hip).  Eligible rows of a search = live rows AND selector; the answer
+ * is the exact top-k of the eligible rows in the conventions above (-1 / FLT_MAX padding when fewer than k are eligible).
+ * sel_words: ceil(ntotal/32) 32-bit words, bit r % 32 of word r / 32 set = row r eligible (one word = one 32-row MFMA
+ *   tile); bits at or beyond ntotal are ignored and no word at or beyond ceil(ntotal/32) is read.  One selector per call,
+ *   shared by all nq queries (FAISS SearchParameters.sel).  sel_mem: EIOKU_MEM_HOST (staged) or EIOKU_MEM_DEVICE,
+ *   independently of `mem`.  NULL = every live row.
+ * after_D / after_I: the exclusive lower bound of eioku_index_search_after, both NULL = none; k up to 32 per call, so a
+ *   filtered top_k > 32 chains calls exactly as the unfiltered one does.
+ * Selector searches run on the exact-fp32 register-tile kernels: a tile-list route that stages only the non-empty
+ * tiles when at most "sel_list_ppm" millionths of the tiles are non-empty (decided on the device, no host round trip),
+ * else a masked walk over all rows.  They never take the scan path (its bound would have to be taken over eligible
+ * rows only). */
+int eioku_index_search_sel(eioku_index_t* ix, const float* q, int nq, int k, const uint32_t* sel_words, int sel_mem,
+                           const float* after_D, const int64_t* after_I, float* D, int64_t* I, int mem, void* stream);
+/* Take rows out of every later search.  Ids NEVER shift (unlike FAISS remove_ids): eioku_index_ntotal keeps counting
+ * the rows ever added (ids are < ntotal), later add() calls continue with fresh ids, eioku_index_nlive counts what a
+ * search can still return.  Nothing is rebuilt: the rows' norms become +inf, which no candidate test of any kernel
+ * passes.  Unknown (< 0, >= ntotal) and repeated ids are ignored.  Allowed on an attached buffer (the norms are the
+ * index' own; the buffer is not written).  ids: int64, host or device per `mem`.  Returns after the stream has drained.
+ * eioku_index_reset makes every id available again. */
+int eioku_index_remove_ids(eioku_index_t* ix, const int64_t* ids, long long n_ids, int mem, void* stream);
+long long eioku_index_nlive(const eioku_index_t* ix);
+/* Tuning / test knobs, see csrc/knn.hip.  "sel_list_ppm": selector searches take the tile-list route when
+ * non-empty tiles * 1e6 <= sel_list_ppm * tiles (0 = never, 1000000 = always).  The wide-search ("scan") path: "scan_mode" 0 = register-tile kernels only,
  * 1 (default) = searches of >= "scan_min_nq" (default 1) queries over >= "scan_min_rows" rows keep row tiles stationary, filter with one bf16
  * product term and re-rank the candidates in fp32; "scan_cap" candidate slots per query (a list that overflows falls
  * back to the register-tile kernels); "scan_sample" rows of the bounding sample (0 = automatic); "scan_prescan" stride of the row tiles the
