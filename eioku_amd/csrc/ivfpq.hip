@@ -1376,3 +1376,193 @@ int eioku_ivfpq_search_lists(const float* q_dev, int nq, int d, int m, const lon
 }
 
 }  // extern "C"
+
+// =====================================================================================================================
+// K10f: the SELECTED VIEW of the probed lists (row selectors and removed rows for IVF-PQ).
+//
+// Inverted lists are ordered by list position, selector / removal bits by row id.  This pre-pass joins the two for the
+// lists that THIS call's probes touch and writes a compact copy of them - v_offsets / v_sizes / v_codes / v_ids / v_hx -
+// that holds exactly the rows whose bit in `keep` (= selector AND NOT removed, one 32-bit word per 32 ids) is set, in
+// their original order within each list; v_sizes[l] = 0 for lists that nobody probes.  The scans above then run
+// UNCHANGED on the view's pointers: the bound pass sees the view's sizes (so tau comes from the first probed list with
+// >= k ELIGIBLE rows), pmax2 stays the full list's (a maximum over a superset: the filter margin stays rigorous), and a
+// row's distance is the same sum in the same order wherever the row sits, so its D bits do not depend on the selector.
+//
+//   k_sv_mark     v_sizes[l] <- 1 for every probed list (plain stores of the same value: no order to depend on)
+//   k_sv_count    one workgroup per marked list: v_sizes[l] <- rows of the list whose keep bit is set
+//   k_sv_scan     one workgroup: v_offsets <- exclusive prefix of v_sizes; a total beyond the caller's capacity empties
+//                 the view (all sizes 0) and raises status[0] instead of writing past the end
+//   k_sv_compact  one workgroup per list, 256 positions per step: wave ballot + prefix popcount gives the rank inside
+//                 the wave, the four wave totals (LDS) the rank inside the step, a running base the rank inside the
+//                 list.  No atomics: the view is deterministic bytes.
+//
+// Alignment of the view's arbitrary row offsets (nothing in the scans assumes a list starts on more than a row):
+// k_lscan loads a row's codes from (pos0 + row) * M with 8-byte (M = 8) or 16-byte (M = 16, 32, 48) vector loads - M is
+// a multiple of the load size, so every row start is aligned whatever pos0 is; k_lrerank's 8-byte loads at row * m + j0
+// (m, j0 multiples of 8) likewise; k_ivfpq_scan takes its 16-byte path only when m % 16 == 0 AND tests (off * m) % 16
+// itself, which then always holds; hx and ids are indexed per element.  All of it rests on the base pointers being
+// 16-byte aligned, which the allocator guarantees (256 bytes).  Reads past a list's end are clamped to its last row by
+// every scan (ii < sz ? ii : sz - 1; rowc = nrows - 1), so a view sized to the eligible rows is never over-read.
+//
+// Loads of ids are unconditional from clamped positions (DESIGN.md "What the ISA said"); the row copy is a gather that
+// only eligible lanes perform: its loads are batched four deep ahead of the stores.
+// =====================================================================================================================
+namespace {
+
+__device__ __forceinline__ bool sv_keep(const unsigned* __restrict__ keep, long long id, long long ntotal) {
+  const bool in = id >= 0 && id < ntotal;
+  const long long c = in ? id : 0;  // clamped: the word load itself is unconditional
+  return in && ((keep[c >> 5] >> (unsigned)(c & 31)) & 1u);
+}
+
+__global__ __launch_bounds__(256) void k_sv_mark(const long long* __restrict__ probes, int npairs, int nlist,
+                                                 int* __restrict__ v_sizes) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= npairs) return;
+  const long long l = probes[p];
+  if (l >= 0 && l < nlist) v_sizes[l] = 1;
+}
+
+__global__ __launch_bounds__(256) void k_sv_count(const int* __restrict__ offsets, const int* __restrict__ sizes,
+                                                  const long long* __restrict__ list_ids,
+                                                  const unsigned* __restrict__ keep, long long ntotal,
+                                                  int* __restrict__ v_sizes) {
+  __shared__ int s_w[4];
+  const int l = blockIdx.x, tid = threadIdx.x;
+  if (v_sizes[l] == 0) return;  // uniform: nobody probes this list
+  const int off = offsets[l], sz = sizes[l];
+  int c = 0;  // wave-uniform
+  for (int i0 = 0; i0 < sz; i0 += 256) {
+    const int i = i0 + tid;
+    const long long id = list_ids[off + (i < sz ? i : sz - 1)];
+    c += __popcll(__ballot(i < sz && sv_keep(keep, id, ntotal)));
+  }
+  if ((tid & 63) == 0) s_w[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) v_sizes[l] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// status[0] = 1 when the eligible rows exceed cap_rows (the view is then EMPTY: all sizes 0), status[1] = their number
+__global__ __launch_bounds__(1024) void k_sv_scan(int* __restrict__ v_sizes, int nlist, long long cap_rows,
+                                                  int* __restrict__ v_offsets, int* __restrict__ status) {
+  __shared__ int s_a[1024];
+  const int tid = threadIdx.x;
+  const int per = (nlist + 1023) / 1024;
+  const int lo = min(nlist, tid * per), hi = min(nlist, lo + per);
+  int sa = 0;
+  for (int l = lo; l < hi; ++l) sa += v_sizes[l];
+  s_a[tid] = sa;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int va = tid >= o ? s_a[tid - o] : 0;
+    __syncthreads();
+    s_a[tid] += va;
+    __syncthreads();
+  }
+  const int total = s_a[1023];
+  const bool ok = (long long)total <= cap_rows;
+  int run = s_a[tid] - sa;  // exclusive
+  for (int l = lo; l < hi; ++l) {
+    const int c = v_sizes[l];
+    v_offsets[l] = ok ? run : 0;
+    if (!ok) v_sizes[l] = 0;
+    run += c;
+  }
+  if (tid == 0) {
+    status[0] = ok ? 0 : 1;
+    status[1] = total;
+  }
+}
+
+// U: the copy unit of a code row (m % sizeof(U) == 0, so every row start is a multiple of it)
+template <typename U>
+__global__ __launch_bounds__(256) void k_sv_compact(const int* __restrict__ offsets, const int* __restrict__ sizes,
+                                                    const uint8_t* __restrict__ list_codes,
+                                                    const long long* __restrict__ list_ids, const float* __restrict__ hx,
+                                                    const unsigned* __restrict__ keep, long long ntotal, int m,
+                                                    const int* __restrict__ v_offsets, const int* __restrict__ v_sizes,
+                                                    uint8_t* __restrict__ v_codes, long long* __restrict__ v_ids,
+                                                    float* __restrict__ v_hx) {
+  __shared__ int s_w[2][4];
+  const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (v_sizes[l] == 0) return;  // uniform: unprobed, nothing eligible, or the view was emptied for lack of room
+  const int off = offsets[l], sz = sizes[l], voff = v_offsets[l];
+  const int nu = m / (int)sizeof(U);
+  int run = 0;  // eligible rows of the list before this step
+  for (int i0 = 0, par = 0; i0 < sz; i0 += 256, par ^= 1) {
+    const int i = i0 + tid;
+    const int ic = i < sz ? i : sz - 1;
+    const long long id = list_ids[off + ic];
+    const float h = hx ? hx[off + ic] : 0.f;
+    const bool on = i < sz && sv_keep(keep, id, ntotal);
+    const unsigned long long b = __ballot(on);
+    if (lane == 0) s_w[par][wave] = __popcll(b);
+    __syncthreads();  // the buffers alternate, so one meeting per step is enough
+    const int w0 = s_w[par][0], w1 = s_w[par][1], w2 = s_w[par][2], w3 = s_w[par][3];
+    const int wbase = wave == 0 ? 0 : (wave == 1 ? w0 : (wave == 2 ? w0 + w1 : w0 + w1 + w2));
+    const int dst = voff + run + wbase + __popcll(b & ((1ull << lane) - 1ull));
+    if (on) {
+      v_ids[dst] = id;
+      if (v_hx) v_hx[dst] = h;
+      const U* src = reinterpret_cast<const U*>(list_codes + (size_t)(off + i) * m);
+      U* out = reinterpret_cast<U*>(v_codes + (size_t)dst * m);
+      for (int j0 = 0; j0 < nu; j0 += 4) {
+        U r[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) r[u] = src[j0 + u < nu ? j0 + u : nu - 1];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (j0 + u < nu) out[j0 + u] = r[u];
+      }
+    }
+    run += (w0 + w1) + (w2 + w3);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The selected view of the probed lists (K10f; all pointers DEVICE, asynchronous on `stream`).  keep: one bit per row
+// id, (ntotal + 31) / 32 words.  hx / v_hx come together (NULL when no list-major scan follows).  The v_* arrays hold
+// nlist ints (offsets, sizes) and cap_rows rows (codes [cap_rows][m], ids, hx).  status_out: 2 ints, see k_sv_scan.
+int eioku_ivfpq_select_view(const long long* probes_dev, int nq, int nprobe, int nlist, int m, long long ntotal,
+                            const int* offsets_dev, const int* sizes_dev, const uint8_t* list_codes_dev,
+                            const long long* list_ids_dev, const float* hx_dev, const uint32_t* keep_dev,
+                            long long cap_rows, int* v_offsets_dev, int* v_sizes_dev, uint8_t* v_codes_dev,
+                            long long* v_ids_dev, float* v_hx_dev, int* status_out_dev, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(keep_dev, "NULL keep: an unfiltered search takes the lists as they are");
+  EIOKU_REQUIRE(probes_dev && offsets_dev && sizes_dev && list_codes_dev && list_ids_dev && v_offsets_dev && v_sizes_dev &&
+                    v_codes_dev && v_ids_dev && status_out_dev,
+                "NULL buffer");
+  EIOKU_REQUIRE((hx_dev == nullptr) == (v_hx_dev == nullptr), "hx and v_hx come together");
+  EIOKU_REQUIRE(nq >= 0 && nprobe > 0 && nlist > 0 && m > 0 && ntotal > 0 && ntotal < (1ll << 31) && cap_rows >= 0,
+                "bad argument");
+  EIOKU_REQUIRE((long long)nq * nprobe < (1ll << 30), "nq x nprobe too large for one call");
+  hipStream_t stream = (hipStream_t)stream_;
+  const int npairs = nq * nprobe;
+  EIOKU_HIP_CHECK(hipMemsetAsync(v_sizes_dev, 0, (size_t)nlist * 4, stream));
+  if (npairs > 0) {
+    hipLaunchKernelGGL(k_sv_mark, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, probes_dev, npairs, nlist,
+                       v_sizes_dev);
+    hipLaunchKernelGGL(k_sv_count, dim3((unsigned)nlist), dim3(256), 0, stream, offsets_dev, sizes_dev, list_ids_dev,
+                       keep_dev, ntotal, v_sizes_dev);
+  }
+  hipLaunchKernelGGL(k_sv_scan, dim3(1), dim3(1024), 0, stream, v_sizes_dev, nlist, cap_rows, v_offsets_dev, status_out_dev);
+  EIOKU_LAUNCH_CHECK();
+  if (npairs == 0) return EIOKU_OK;
+#define EIOKU_SV(U_)                                                                                                   \
+  hipLaunchKernelGGL((k_sv_compact<U_>), dim3((unsigned)nlist), dim3(256), 0, stream, offsets_dev, sizes_dev,          \
+                     list_codes_dev, list_ids_dev, hx_dev, keep_dev, ntotal, m, v_offsets_dev, v_sizes_dev, v_codes_dev, \
+                     v_ids_dev, v_hx_dev)
+  if (m % 16 == 0) EIOKU_SV(u32x4k);
+  else if (m % 8 == 0) EIOKU_SV(u32x2k);
+  else if (m % 4 == 0) EIOKU_SV(unsigned);
+  else EIOKU_SV(uint8_t);
+#undef EIOKU_SV
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,11 @@ Multi-GPU build (BASELINE cfg5: 100M x 384 over 8 GPUs): ``t
 quantisers on the union of every rank's rows with one integer all-reduce per k-means iteration; ``add`` /
 ``search`` stay local to the rank's row shard, and ``search.ShardedFlatL2(local=this index, id_base=...)`` merges
 the per-rank results with the single all-gather of the flat index.
+
+Row selectors and removal (K10f): ``search(q, k, sel=...)``, ``search_many``, ``remove_ids`` / ``nlive`` and ``close()`` have
+the semantics of ``search.IndexFlatL2``; a filtered search scans a compact view of the probed lists that holds only the
+eligible rows (``eioku_ivfpq_select_view``) with the scans of the unfiltered one.  ``store_index_factory`` puts the index
+behind ``semantic.VectorStore``.
 """
 
 from __future__ import annotations
@@ -23,9 +28,11 @@ import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, ptr
-from .search import IndexFlatL2
+from .search import IndexFlatL2, RowSelector
 
 NITER = 25
+MAX_K = 32  # results per query of one search (the partial lists of the scans are 16 or 32 wide)
+_POP8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(1).astype(np.int64)  # bits set per byte
 MAX_POINTS_PER_CENTROID = 256
 
 
@@ -147,6 +154,11 @@ class IndexIVFPQ:
         self._ws = None
         self.last_stats = None              # device int32[6] after a list-major search: overflow bits, work items, largest candidate list, candidates in all, its query, its size
         self.allreduce_calls = 0
+        # row selectors and removal (K10f): see search()
+        self._live = None                   # device int32 words by id, bit set = not removed; None until remove_ids()
+        self._nremoved = 0
+        self._view = None                   # (capacity in rows, v_offsets, v_sizes, v_codes, v_ids, v_hx, status): kept and grown like _ws
+        self.last_view = None               # (v_offsets, v_sizes, v_codes, v_ids) of the last filtered search, None after an unfiltered one
 
     # ---- training ------------------------------------------------------------------------------
     def _allreduce(self, packed, group):
@@ -249,6 +261,10 @@ class IndexIVFPQ:
         self.ntotal += n
         self._packed = None
         self._aux = None
+        if self._live is not None:  # fresh ids are live; the bits beyond ntotal in the last word are kept set
+            grow = (self.ntotal + 31) // 32 - int(self._live.numel())
+            if grow > 0:
+                self._live = torch.cat([self._live, torch.full((grow,), -1, dtype=torch.int32, device=self.device)])
 
     def _pack(self):
         """Counting sort of everything added so far into contiguous inverted lists."""
@@ -272,13 +288,93 @@ class IndexIVFPQ:
         self._packed = (offsets, counts.contiguous(), list_codes, list_ids)
         return self._packed
 
-    def search(self, q, k: int):
-        """(D, I) CUDA tensors: approximate squared L2 (ADC) ascending, int64 ids (-1 = fewer than k found)."""
+    # ---- row selectors and removal (K10f) ---------------------------------------------------------------
+    @property
+    def nlive(self) -> int:
+        """Rows a search can return: ``ntotal`` minus the rows taken out by :meth:`remove_ids`."""
+        return self.ntotal - self._nremoved
+
+    def remove_ids(self, ids) -> int:
+        """Take rows out of every later search; returns how many were live until now (as ``IndexFlatL2.remove_ids``).
+
+        Ids never shift: ``ntotal`` stays, later ``add()`` calls continue with fresh ids.  Unknown and repeated ids are
+        ignored.  Removal is a bitmap by id on the device: nothing is re-encoded or re-packed, and a later ``add()``
+        (which re-packs the lists) leaves it as it is.  ``ids``: int64 numpy array / sequence, or a CUDA int64 tensor."""
+        import torch
+
+        if not torch.is_tensor(ids):
+            ids = torch.from_numpy(np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1)))
+        ids = ids.to(self.device, torch.int64).reshape(-1)
+        ids = torch.unique(ids[(ids >= 0) & (ids < self.ntotal)])
+        if ids.numel() == 0:
+            return 0
+        nwords = (self.ntotal + 31) // 32
+        if self._live is None:
+            self._live = torch.full((nwords,), -1, dtype=torch.int32, device=self.device)
+        word, bit = ids >> 5, ids & 31
+        gone = int(((self._live[word].to(torch.int64) >> bit) & 1).sum())
+        # distinct bits of one word add up without carries: the sum IS their OR
+        clear = torch.zeros((nwords,), dtype=torch.int64, device=self.device).index_add_(0, word, torch.ones_like(bit) << bit)
+        clear = torch.where(clear >= 2 ** 31, clear - 2 ** 32, clear).to(torch.int32)
+        self._live = self._live & ~clear
+        self._nremoved += gone
+        return gone
+
+    def _keep(self, sel):
+        """-> (device int32 words ``selector AND NOT removed`` by id, capacity in rows of the view), or ``(None, 0)``
+        when every row is eligible.  The capacity is what the host knows without asking the device: the bits set in a host
+        selector, else ``ntotal``."""
+        import torch
+
+        # the selector forms and the ValueError texts of the flat index
+        words, _, mem = IndexFlatL2._selector(self, sel, None)
+        if words is None or self.ntotal == 0:
+            return (self._live, self.ntotal) if self._live is not None and self.ntotal else (None, 0)
+        cap = self.ntotal
+        if mem == _lib.MEM_HOST:
+            cap = min(cap, int(_POP8[words.view(np.uint8)].sum()))
+            words = torch.from_numpy(words.view(np.int32)).to(self.device)
+        elif words.dtype != torch.int32:
+            words = words.view(torch.int32)
+        return (words if self._live is None else words & self._live), cap
+
+    def _select_view(self, q, probes, nprobe, pack, keep, cap, hx):
+        """``eioku_ivfpq_select_view``: the eligible rows of the probed lists as a compact pack (+ their ``hx``)."""
+        import torch
+
+        if self._view is None or self._view[0] < cap or self._view[3].shape[1] != self.m or self._view[1].numel() != self.nlist:
+            rows = max(cap, 1)
+            self._view = (cap, torch.empty((self.nlist,), dtype=torch.int32, device=self.device),
+                          torch.empty((self.nlist,), dtype=torch.int32, device=self.device),
+                          torch.empty((rows, self.m), dtype=torch.uint8, device=self.device),
+                          torch.empty((rows,), dtype=torch.int64, device=self.device),
+                          torch.empty((rows,), dtype=torch.float32, device=self.device),
+                          torch.zeros((2,), dtype=torch.int32, device=self.device))
+        _, v_offsets, v_sizes, v_codes, v_ids, v_hx, status = self._view
+        offsets, sizes, list_codes, list_ids = pack
+        _lib.check(self._lib.eioku_ivfpq_select_view(ptr(probes), int(q.shape[0]), nprobe, self.nlist, self.m, self.ntotal,
+                                                     ptr(offsets), ptr(sizes), ptr(list_codes), ptr(list_ids),
+                                                     None if hx is None else ptr(hx), ptr(keep), cap, ptr(v_offsets),
+                                                     ptr(v_sizes), ptr(v_codes), ptr(v_ids), None if hx is None else ptr(v_hx),
+                                                     ptr(status), current_stream(q)), "eioku_ivfpq_select_view")
+        self.last_view = (v_offsets, v_sizes, v_codes, v_ids)
+        return (v_offsets, v_sizes, v_codes, v_ids), (None if hx is None else v_hx)
+
+    def search(self, q, k: int, sel=None):
+        """(D, I) CUDA tensors: approximate squared L2 (ADC) ascending, int64 ids (-1 = fewer than k found).
+
+        ``sel``: optional :class:`eioku_amd.search.RowSelector`, packed ``uint32`` host words or a contiguous CUDA int32 /
+        uint32 tensor over ``ntotal`` rows (what ``IndexFlatL2.search`` accepts; one selector serves all queries).  The
+        probes are chosen as without it; the answer is the k best by (distance, id) among the rows of the probed lists
+        whose bit is set and which were not removed, ``(FLT_MAX, -1)`` padding.  A row's distance bits do not depend on
+        the selector.  With a selector or after :meth:`remove_ids` the scan of the current ``scan_mode`` runs on the
+        selected view of the probed lists (``last_view``); otherwise on the lists as they are (``last_view`` is None)."""
         import torch
 
         q = torch.as_tensor(q, dtype=torch.float32).to(self.device).contiguous()
         nq = q.shape[0]
         nprobe = min(self.nprobe, self.nlist)
+        keep, cap = self._keep(sel)
         offsets, sizes, list_codes, list_ids = self._pack()
         _, probes = self._quantizer.search_many(q, nprobe)  # nprobe > 32: chained rounds of 32 (search_after)
         probes = probes.contiguous()
@@ -298,8 +394,17 @@ class IndexIVFPQ:
             qt = torch.empty((nq, self.m, 256), dtype=torch.float32, device=self.device)
             _lib.check(self._lib.eioku_ivfpq_tables(ptr(q), nq, self.d, self.m, ptr(self.pq), 0.0, -2.0, ptr(qt),
                                                     current_stream(q)), "eioku_ivfpq_tables")
+        hx = None
+        if keep is None:
+            self.last_view = None
+        else:  # the scans below run unchanged on the eligible rows of the probed lists
             if lists:
-                return self._search_lists(q, k, probes, nprobe, qt, offsets, sizes, list_codes, list_ids)
+                hx = self._lists_aux(q, offsets, sizes, list_codes)[1]
+            (offsets, sizes, list_codes, list_ids), hx = self._select_view(q, probes, nprobe, (offsets, sizes, list_codes, list_ids),
+                                                                           keep, cap, hx)
+        if self.use_precomputed_table:
+            if lists:
+                return self._search_lists(q, k, probes, nprobe, qt, offsets, sizes, list_codes, list_ids, hx)
             _lib.check(self._lib.eioku_ivfpq_scan_tables(ptr(q), nq, self.d, self.m, ptr(probes), nprobe, ptr(self.coarse),
                                                          ptr(self.pq), ptr(offsets), ptr(sizes), ptr(list_codes), ptr(list_ids),
                                                          ptr(self._list_tables), ptr(qt), k, ptr(pd), ptr(pi),
@@ -314,11 +419,34 @@ class IndexIVFPQ:
                    "eioku_topk_merge_ex")
         return D, I
 
-    def _search_lists(self, q, k, probes, nprobe, qt, offsets, sizes, list_codes, list_ids):
-        """The list-major scan (``eioku_ivfpq_search_lists``): one C call enqueues the whole search."""
+    def search_many(self, q, k: int, sel=None):
+        """:meth:`search` behind the protocol ``VectorStore`` speaks (``IndexFlatL2.search_many``): numpy queries give
+        numpy results and the call is synchronous, CUDA queries give CUDA results.  ``k`` is at most 32: chained rounds
+        are not built for IVF-PQ."""
+        if k > MAX_K:
+            raise ValueError(f"IndexIVFPQ returns at most {MAX_K} results per query (k <= {MAX_K}), got k = {k}")
         import torch
 
-        nq = int(q.shape[0])
+        host = not torch.is_tensor(q)
+        D, I = self.search(q, k, sel)
+        if not host:
+            return D, I
+        D, I = D.cpu().numpy(), I.cpu().numpy()
+        if self.last_view is not None and int(self._view[6][0]) != 0:
+            raise _lib.EiokuHipError(f"eioku_ivfpq_select_view: {int(self._view[6][1])} eligible rows do not fit the "
+                                     f"view's {self._view[0]}")
+        return D, I
+
+    def close(self) -> None:
+        """Release the coarse quantiser's handle; idempotent."""
+        if self._quantizer is not None:
+            self._quantizer.close()
+            self._quantizer = None
+
+    def _lists_aux(self, q, offsets, sizes, list_codes):
+        """(pqh, hx, pmax2) of the current pack (``eioku_ivfpq_lists_aux``), built once per pack / codebook change."""
+        import torch
+
         if self._aux is None:
             pqh = torch.empty((self.m * 256, 4), dtype=torch.int32, device=self.device)
             hx = torch.empty((max(self.ntotal, 1),), dtype=torch.float32, device=self.device)
@@ -327,7 +455,19 @@ class IndexIVFPQ:
                                                        ptr(self._list_tables), ptr(self.pq), ptr(pqh), ptr(hx), ptr(pmax2),
                                                        current_stream(q)), "eioku_ivfpq_lists_aux")
             self._aux = (pqh, hx, pmax2)
-        pqh, hx, pmax2 = self._aux
+        return self._aux
+
+    def _search_lists(self, q, k, probes, nprobe, qt, offsets, sizes, list_codes, list_ids, view_hx=None):
+        """The list-major scan (``eioku_ivfpq_search_lists``): one C call enqueues the whole search.  ``view_hx``: the
+        lists are a selected view and this is its ``hx`` (``pqh`` and ``pmax2`` stay the pack's)."""
+        import torch
+
+        nq = int(q.shape[0])
+        if view_hx is None:
+            pqh, hx, pmax2 = self._lists_aux(q, offsets, sizes, list_codes)
+        else:
+            pqh, _, pmax2 = self._aux
+            hx = view_hx
         need = int(self._lib.eioku_ivfpq_lists_workspace(nq, self.d, nprobe, self.nlist, self.ntotal, k, self.cand_cap))
         if need < 0:
             raise _lib.EiokuHipError("eioku_ivfpq_lists_workspace: bad argument")
@@ -343,3 +483,37 @@ class IndexIVFPQ:
                                                       current_stream(q)), "eioku_ivfpq_search_lists")
         self.last_stats = stats
         return D, I
+
+
+class _StoreIVFPQ(IndexIVFPQ):
+    """What :func:`store_index_factory` builds: an :class:`IndexIVFPQ` that trains on the rows of its first ``add``."""
+
+    def add(self, x) -> None:
+        if not self.is_trained:
+            self.train(x)  # ValueError when there are fewer than max(nlist, 256) rows
+        super().add(x)
+
+
+def store_index_factory(nlist: int, m: int, nprobe: int, seed: int = 1234):
+    """``d -> index`` for ``VectorStore(index_factory=...)``: an IVF-PQ index (``nlist`` inverted lists, ``m`` 8-bit
+    sub-quantisers, ``nprobe`` lists scanned per query) behind the protocol the store speaks - ``add(numpy)``, ``ntotal``,
+    ``remove_ids``, ``search_many(numpy q, k, sel=RowSelector)`` (k <= 32) and ``close()``.
+
+    The index is untrained when the store builds it and trains on the rows of its first ``add`` - the store adds its
+    whole matrix first, so that is the library; fewer than ``max(nlist, 256)`` rows raise ``train``'s ``ValueError``.
+    When the store rebuilds its device index (removed rows outnumber the live ones) the new index trains again."""
+    for name, v in (("nlist", nlist), ("m", m), ("nprobe", nprobe)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    if nprobe > nlist:
+        raise ValueError(f"nprobe = {nprobe} exceeds nlist = {nlist}")
+    nlist, m, nprobe, seed = int(nlist), int(m), int(nprobe), int(seed)
+
+    def build(d: int):
+        if d % m or d // m not in (4, 8, 16):
+            raise ValueError(f"d/m must be 4, 8 or 16 (d = {d}, m = {m})")
+        ix = _StoreIVFPQ(int(d), nlist, m, seed=seed)
+        ix.nprobe = nprobe
+        return ix
+
+    return build

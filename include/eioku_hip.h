@@ -402,6 +402,25 @@ int eioku_ivfpq_search_lists(const float* q_dev, int nq, int d, int m, const lon
                              const float* pmax2_dev, int k, int cand_cap, void* workspace_dev, long long workspace_bytes,
                              float* D_dev, long long* I_dev, int* stats_out_dev, void* stream);
 
+/* Row selectors and removed rows for IVF-PQ (K10f): the SELECTED VIEW of the probed lists.  keep [(ntotal + 31) / 32]
+ * little-endian 32-bit words by row id (bit set = the row may be returned: selector AND NOT removed; NULL is an error,
+ * an unfiltered search takes the lists as they are).  For the lists that probes [nq][nprobe] touch, the call writes a
+ * compact copy holding exactly their rows whose bit is set, in their order within the list: v_offsets / v_sizes [nlist]
+ * ints (v_sizes[l] = 0 for a list nobody probes), v_codes [cap_rows][m], v_ids [cap_rows], and v_hx [cap_rows] from hx
+ * (eioku_ivfpq_lists_aux; both NULL when no list-major scan follows).  eioku_ivfpq_scan, eioku_ivfpq_scan_tables and
+ * eioku_ivfpq_search_lists (with the UNCHANGED pmax2) then run on the v_* pointers in place of the pack's: same
+ * distance bits per row as an unfiltered search, k best of the eligible rows.  No atomics: the view is deterministic.
+ * cap_rows: rows the v_* arrays hold; min(ntotal, bits set in the selector) always suffices.  The eligible rows are
+ * known on the device only: when they exceed cap_rows nothing is written past the end - the view comes out EMPTY (all
+ * sizes 0) and status_out[0] = 1; status_out (device, 2 ints) = {1 if the capacity was too small else 0, eligible rows
+ * of the probed lists}.  EIOKU_EINVAL: NULL buffer, hx without v_hx, ntotal outside [1, 2^31), nq x nprobe >= 2^30.
+ * All pointers are DEVICE pointers; asynchronous on `stream`. */
+int eioku_ivfpq_select_view(const long long* probes_dev, int nq, int nprobe, int nlist, int m, long long ntotal,
+                            const int* offsets_dev, const int* sizes_dev, const uint8_t* list_codes_dev,
+                            const long long* list_ids_dev, const float* hx_dev, const uint32_t* keep_dev,
+                            long long cap_rows, int* v_offsets_dev, int* v_sizes_dev, uint8_t* v_codes_dev,
+                            long long* v_ids_dev, float* v_hx_dev, int* status_out_dev, void* stream);
+
 /* ---- place classification: Places365 ResNet18 (csrc/resnet.hip) --------------------------------------------------
  * Replaces the per-frame arithmetic of ModelManager.classify_places
  * (/root/reference/ml-service/src/services/model_manager.py:560-713): `transforms.Resize((224, 224))` on the PIL image
