@@ -17,10 +17,18 @@
 #include "conv.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
 namespace eioku {
+
+namespace {
+std::atomic<unsigned> g_route_counts[kRouteSlots];
+}
+void route_hit(int id) {
+  if (id >= 0 && id < kRouteSlots) g_route_counts[id].fetch_add(1u, std::memory_order_relaxed);
+}
 
 namespace {
 
@@ -246,18 +254,20 @@ __global__ __launch_bounds__(64 * NWV) void k_conv1x1(ConvArgs a, long long npix
     for (int m = 0; m < 2; ++m) {
       long long p = grp * 32 + m * 16 + r;
       if (p >= npix) p = npix - 1;
-      const __half* src = a.in + (size_t)p * a.in_cs + u * 8;
+      const __half* src = a.in + (size_t)p * a.in_cs;
       const __half* src2 = src;
       if (UP) {  // pixel (n, y, x) -> (n, y/2, x/2) of the half-resolution source
         const int pi = (int)p;
         const int n = fast_div(pi, HWf, r_hw), rem = pi - n * HWf;
         const int y = fast_div(rem, a.W, r_w), x = rem - y * a.W;
-        src2 = a.in2 + ((size_t)(n * (a.H >> 1) + (y >> 1)) * (a.W >> 1) + (x >> 1)) * a.in2_cs + u * 8;
+        src2 = a.in2 + ((size_t)(n * (a.H >> 1) + (y >> 1)) * (a.W >> 1) + (x >> 1)) * a.in2_cs;
       }
 #pragma unroll
       for (int j = 0; j < KB; ++j) {
-        int c = (kb * KB + j) * 32;
-        if (c + u * 8 >= a.Cin) c = 0;  // past Cin: any in-range address; zeroed below / never multiplied
+        int c = (kb * KB + j) * 32 + u * 8;  // this lane's 8 channels of the chunk
+        // past Cin: any in-range address (zeroed below / never multiplied).  The pixel's first unit, not this lane's unit of
+        // chunk 0: with Cin < 32 that unit is past the pixel too, and on the last pixel past the tensor
+        if (c >= a.Cin) c = 0;
         const __half* base = (UP && c < a.c_split) ? src2 : src;
         b[j][m] = LDG(u32x4, base + c, (UP && c < a.c_split) ? a.x_in2 : a.x_in);
       }
@@ -1791,6 +1801,7 @@ int launch_c8(const ConvArgs& a, const FusedSrc& fs, int ntiles, hipStream_t str
   int bx = num_cus() * 6 / ntiles;  // small LDS footprint: ~6 workgroups per CU keep the byte loads in flight
   if (bx < 1) bx = 1;
   if (bx > total) bx = total;
+  route_hit(route_id(kRouteC8, NF, S, SRC));
   hipLaunchKernelGGL((k_conv3x3_c8<NF, S, SRC>), dim3((unsigned)bx, (unsigned)ntiles), dim3(256), lds, stream, a, fs, total);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
@@ -1850,6 +1861,7 @@ int launch_persist(const ConvArgs& a_in, int ntiles, hipStream_t stream) {
   int bx = num_cus() * per_cu / ntiles;
   if (bx < 1) bx = 1;
   if (bx > total) bx = total;
+  route_hit(route_id(kRoutePersist, NF, S, NCH, DB, POST, NWV));
   hipLaunchKernelGGL((k_conv3x3_persist<NF, S, NCH, DB, POST, NWV>), dim3((unsigned)bx, (unsigned)ntiles), dim3(64 * NWV), lds,
                      stream, a, total);
   EIOKU_LAUNCH_CHECK();
@@ -1921,6 +1933,7 @@ int launch_chain(const ConvArgs& a, const ChainCat& cc, hipStream_t stream) {
   if (per_cu > occ) per_cu = occ;
   int bx = num_cus() * per_cu;
   if (bx > total) bx = total;
+  route_hit(route_id(kRouteChain, NF, DB, CAT, NF2));
   hipLaunchKernelGGL((k_conv3x3_chain<NF, DB, CAT, NF2>), dim3((unsigned)bx), dim3(256), lds, stream, a, cc, total);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
@@ -1958,6 +1971,7 @@ int launch_flat(const ConvArgs& a, const FlatGeom& g, int ntiles, hipStream_t st
   }
   const int npix = a.N * a.Ho * a.Wo;
   const int tpx = 64 * MT;
+  route_hit(route_id(kRouteFlat, NF, S, MT, NS));
   hipLaunchKernelGGL((k_conv3x3_flat<NF, S, MT, NS>), dim3((unsigned)((npix + tpx - 1) / tpx), (unsigned)ntiles),
                      dim3(256), g.lds, stream, a, npix, g.PR, g.PW);
   EIOKU_LAUNCH_CHECK();
@@ -2002,6 +2016,7 @@ int launch(const ConvArgs& a, int ntiles, hipStream_t stream) {
     attr_set = true;
   }
   dim3 grid((unsigned)(a.tiles_w * a.tiles_h * a.N), (unsigned)ntiles);
+  route_hit(route_id(kRouteIgemm, NF, KS, S));
   hipLaunchKernelGGL((k_conv_igemm<NF, KS, S>), grid, dim3(256), lds, stream, a);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
@@ -2037,6 +2052,7 @@ int launch1x1_impl(const ConvArgs& a, int ntiles, int wg_cu, hipStream_t stream)
   const long long cap = (long long)num_cus() * wg_cu / ntiles;  // grid-stride beyond that many workgroups per CU
   if (bx > cap) bx = cap;
   if (bx < 1) bx = 1;
+  route_hit(route_id(kRoute1x1, NF, UP, NWV, a.clsmax != nullptr));
   hipLaunchKernelGGL((k_conv1x1<NF, UP, NWV>), dim3((unsigned)bx, (unsigned)ntiles), dim3(64 * NWV), lds, stream, a, npix);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
@@ -2342,6 +2358,7 @@ int conv_stem_chain_forward(const ConvWeights& stem, const ConvWeights& c1, cons
   int bx = num_cus() * per_cu;
   if (bx > total) bx = total;
   prof_start(EIOKU_PROF_CONV, stream);
+  route_hit(route_id(kRouteStemChain, f.mode == 2 ? 2 : (f.step > 1 ? 1 : 0)));
   if (f.mode == 2) hipLaunchKernelGGL(k_conv_stem_chain<2>, dim3((unsigned)bx), dim3(256), kStemChainLds, stream, a, st, fs, total);
   else if (f.step > 1) hipLaunchKernelGGL(k_conv_stem_chain<1>, dim3((unsigned)bx), dim3(256), kStemChainLds, stream, a, st, fs, total);
   else hipLaunchKernelGGL(k_conv_stem_chain<0>, dim3((unsigned)bx), dim3(256), kStemChainLds, stream, a, st, fs, total);
@@ -2528,6 +2545,41 @@ int eioku_debug_bounds(int* violations, int* line, int reset, int selftest) {
   *violations = -1;
   *line = 0;
 #endif
+  return EIOKU_OK;
+}
+
+// Route log: one line "family<FIELDvalue,...> count" per conv-family instantiation launched in this process since the
+// last reset.  Host counters only: needs no device and no eioku_init.
+int eioku_debug_conv_routes(char* buf, size_t cap, int reset) {
+  EIOKU_REQUIRE(buf || cap == 0, "NULL buffer");
+  size_t pos = 0;
+  bool fits = true;
+  for (int fam = 0; fam < kNumRouteFamilies; ++fam) {
+    const RouteFamilyDesc& d = kRouteFamilies[fam];
+    const int base = route_family_base(fam), slots = route_family_slots(fam);
+    for (int i = 0; i < slots; ++i) {
+      const unsigned c = reset ? g_route_counts[base + i].exchange(0u, std::memory_order_relaxed)
+                               : g_route_counts[base + i].load(std::memory_order_relaxed);
+      if (!c || !buf) continue;
+      char line[160];
+      int n = snprintf(line, sizeof line, "%s", d.name);
+      int vals[6], rest = i;
+      for (int f = d.nfields - 1; f >= 0; --f) {
+        vals[f] = rest % d.radix[f];
+        rest /= d.radix[f];
+      }
+      for (int f = 0; f < d.nfields; ++f) n += snprintf(line + n, sizeof line - n, "%s%s%d", f ? "," : "<", d.field[f], vals[f]);
+      n += snprintf(line + n, sizeof line - n, "%s %u\n", d.nfields ? ">" : "", c);
+      if (pos + (size_t)n + 1 > cap) {
+        fits = false;
+        continue;
+      }
+      memcpy(buf + pos, line, (size_t)n);
+      pos += (size_t)n;
+    }
+  }
+  if (cap) buf[pos] = 0;
+  EIOKU_REQUIRE(fits, "route log does not fit %zu bytes", cap);
   return EIOKU_OK;
 }
 

@@ -826,7 +826,9 @@ int decode_lazy_forward(float* const box[3], const unsigned long long* const cls
       g1.l[l] = GConv{lb.c1[l].in, lb.c1[l].wgt, lb.c1[l].bias, lb.c1[l].out, lb.flat1[l], lb.fcnt + l, Hl[l], Wl[l],
                       lb.c1[l].in_cs, lb.c1[l].out_cs, lb.c1[l].nchunks, lb.c1[l].rows_tile};
     }
+    route_hit(route_id(kRouteGather));
     hipLaunchKernelGGL(k_conv3x3_gather, dim3(512, 3), dim3(256), 0, stream, g0);
+    route_hit(route_id(kRouteGather));
     hipLaunchKernelGGL(k_conv3x3_gather, dim3(128, 3), dim3(256), 0, stream, g1);
   }
   hipLaunchKernelGGL(k_box_gather, dim3((unsigned)((amax + 127) / 128), (unsigned)(N * 3)), dim3(256), 0, stream, a);

@@ -170,6 +170,14 @@ int eioku_conv2d_f16(const void* in_nhwc, int n, int h, int w, int in_cstride, i
  * counted, not performed).  violations = -1 in the regular library.  selftest != 0: first make 3 violations on purpose. */
 int eioku_debug_bounds(int* violations, int* line, int reset, int selftest);
 
+/* Route log of the conv family: one line per distinct kernel instantiation launched in this process since the last
+ * reset, "family<FIELDvalue,...> count\n" with the launching template's own arguments, e.g.
+ * "persist<NF3,S1,NCH3,DB0,POST0,NWV8> 4" (families: igemm, flat, persist, chain, c8, stem_chain, 1x1, gather).  The
+ * launch sites bump a host counter; nothing is formatted and no device work is added until this call.  buf receives
+ * the NUL-terminated text (EIOKU_EINVAL when cap is too small; buf NULL with cap 0 only resets); reset != 0 clears the
+ * counters after reading them.  Thread safe; needs no eioku_init. */
+int eioku_debug_conv_routes(char* buf, size_t cap, int reset);
+
 /* YOLOv8 detector handle.  Replaces `YOLO(model_path); model.to(device)` + `model(frame, conf=..)`
  * of ModelManager.detect_objects / detect_faces (model_manager.py:252-254,270-275 / :346-348,
  * :364-369).  The graph is the Ultralytics yolov8 layout parameterised by its backbone widths

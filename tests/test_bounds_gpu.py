@@ -1,7 +1,7 @@
 """GPU: the regression net for round 2's fault class (an over-read past a tensor's end that only faults on a page
 boundary).  libeioku_hip_bc.so is the same library with conv.hip compiled -DEIOKU_BOUNDS_CHECK: every
 global access of an activation / residual / image / output tensor is compared with the tensor's extent and a violation
-is counted (not performed).  A child process runs tests/test_conv_gpu.py's CASES, whole v8n / v8s / v8m forwards at
+is counted (not performed).  A child process runs tests/test_conv_gpu.py's CASES and EPILOGUE_CASES, whole v8n / v8s / v8m forwards at
 96 x 160, detect() on five source geometries and the Places365 ResNet18 through it; the count must stay 0."""
 import ctypes as C
 import json
@@ -32,5 +32,6 @@ def test_no_access_of_the_conv_family_leaves_its_tensor(gpu):
     assert out["library"].endswith("libeioku_hip_bc.so")
     assert out["selftest"] == 3, out            # the net catches an out-of-extent load before, after and a store
     assert out["after_cases"] == 0, out
+    assert out["after_epilogues"] == 0, out
     assert out["violations"] == 0, f"{out['violations']} out-of-extent accesses, last at conv.hip:{out['line']}"
-    assert out["launches"] > 40
+    assert out["launches"] > 300  # both tables of tests/test_conv_gpu.py, the forwards and detect() calls

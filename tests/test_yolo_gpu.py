@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 import wellcond
-from eioku_amd import detect as D, weights as W
+from eioku_amd import detect as D, ops, weights as W
 from oracle import prng, yolo as oy
 
 pytestmark = pytest.mark.gpu
@@ -261,6 +261,26 @@ def test_detect_end_to_end_exact_on_margin_stable_detections(gpu, variant, nc, h
     det.close()
 
 
+# what a child process of the byte-identity tests appends to its script: its own route log (ops.conv_routes) next to its output
+ROUTES_DUMP = "from eioku_amd import ops; import json; json.dump(ops.conv_routes(), open(sys.argv[1] + '.routes.json', 'w'))\n"
+
+
+def _child_routes(path):
+    import json
+
+    with open(str(path) + ".routes.json") as f:
+        return json.load(f)
+
+
+# source geometry -> the stem launch of detect(): the one-launch front end (MODE 0 copy, 1 decimating copy, 2 exact half),
+# the stem alone reading the frames (c8: SRC 1 copy by bytes, 2 exact half, 3 copy by 12-byte groups) when the rows or the
+# padding are not 4-pixel aligned, or the unfused stem (SRC0) behind a bilinear letterbox
+STEM_ROUTE = {(470, 640): "stem_chain<MODE0>", (640, 470): "c8<NF1,S2,SRC1>", (640, 472): "stem_chain<MODE0>",
+              (940, 1280): "stem_chain<MODE2>", (1280, 940): "c8<NF1,S2,SRC2>", (96, 160): "c8<NF1,S2,SRC0>",
+              (1080, 1920): "stem_chain<MODE1>", (1920, 1080): "stem_chain<MODE1>", (960, 1920): "stem_chain<MODE1>",
+              (1605, 1920): "stem_chain<MODE1>"}
+
+
 def test_lazy_and_dense_box_branch_give_identical_detections(gpu, tmp_path):
     """detect() evaluates the box branch's 3x3 layers lazily (only around passing anchors) when the previous
     call's pass rate was low, densely otherwise; the choice depends on history that arrives asynchronously.  Both
@@ -284,14 +304,18 @@ def test_lazy_and_dense_box_branch_give_identical_detections(gpu, tmp_path):
         "    torch.cuda.synchronize()\n"
         "    out += [d.view(np.uint8).reshape(len(c), -1)[i, :32 * c[i]] for i in range(len(c))] + [c]\n"
         "np.savez(sys.argv[1], *out)\n"
+        + ROUTES_DUMP
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),)
-    outs = {}
+    outs, routes = {}, {}
     for frac in ("0", "0.5"):  # never lazy-deep / lazy-deep whenever <= 50 % of the anchors passed last time
         path = tmp_path / f"dets_{frac}.npz"
         subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=dict(os.environ, EIOKU_LAZY_DEEP_FRAC=frac),
                        timeout=300)
         with np.load(path) as z:
             outs[frac] = [z[k] for k in z.files]
+        routes[frac] = _child_routes(path)
+    # the comparison is between two routes only if the lazy process did launch the gathered 3x3 and the dense one did not
+    assert "gather" in routes["0.5"] and "gather" not in routes["0"], routes
     assert len(outs["0"]) == len(outs["0.5"]) and sum(int(a.size) for a in outs["0"]) > 15 * 32
     for a, b in zip(outs["0"], outs["0.5"]):
         assert np.array_equal(a, b)
@@ -321,15 +345,30 @@ def test_detect_fusion_switches_leave_the_detections_byte_identical(gpu, tmp_pat
         "    torch.cuda.synchronize()\n"
         "    out += [d.view(np.uint8).reshape(len(c), -1)[i, :32 * c[i]] for i in range(len(c))] + [c]\n"
         "np.savez(sys.argv[1], *out)\n"
+        + ROUTES_DUMP
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),)
-    outs = {}
+    outs, routes = {}, {}
     for name in ("all_on", "EIOKU_STEM_CHAIN", "EIOKU_STEM_FUSE", "EIOKU_CLSMAX", "EIOKU_LAZY_BOX"):
         path = tmp_path / f"dets_{name}.npz"
         env = dict(os.environ) if name == "all_on" else dict(os.environ, **{name: "0"})
         subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=env, timeout=300)
         with np.load(path) as z:
             outs[name] = [z[k] for k in z.files]
+        routes[name] = _child_routes(path)
     assert sum(int(a.size) for a in outs["all_on"]) > 15 * 32
+    # Not vacuous: the all-on process launched the instantiation every switch stands for, and the process with a switch
+    # off launched none of that switch's.
+    fused = {"EIOKU_STEM_CHAIN": lambda r: r.startswith("stem_chain<"),
+             "EIOKU_STEM_FUSE": lambda r: r.startswith("stem_chain<") or (r.startswith("c8<") and not r.endswith("SRC0>")),
+             "EIOKU_CLSMAX": lambda r: r.endswith("CLSMAX1>") or r == "gather",
+             "EIOKU_LAZY_BOX": lambda r: r == "gather"}
+    on = routes["all_on"]
+    assert "stem_chain<MODE0>" in on and "gather" in on and any(r.startswith("1x1<") and r.endswith("CLSMAX1>") for r in on), on
+    for name, is_fused in fused.items():
+        assert any(is_fused(r) for r in on), (name, on)
+        assert not any(is_fused(r) for r in routes[name]), (name, routes[name])
+    # without the one-launch front end the stem still reads the frames itself (12-byte group loads: SRC3)
+    assert "c8<NF1,S2,SRC3>" in routes["EIOKU_STEM_CHAIN"], routes["EIOKU_STEM_CHAIN"]
     for name, got in outs.items():
         assert len(got) == len(outs["all_on"]), name
         for a, b in zip(got, outs["all_on"]):
@@ -346,9 +385,14 @@ def test_fused_stem_equals_letterbox_then_network(gpu, h, w):
     frames = _dev(prng.synth_frames_bgr(33, 3, h, w), gpu)
     det = D.Yolov8Detector("n", 80, W.random_state("n", 80, seed=3))
     det.calibrate_random_head(frames, frac=0.02)
+    ops.conv_routes(reset=True)
     dets, counts = det.detect(frames, conf=0.25)
+    # which front end detect() took for this geometry: the comparison below is between two routes only if it is the fused one
+    stem = sorted(r for r in ops.conv_routes(reset=True) if r.startswith(("stem_chain<", "c8<")))
+    assert stem == [STEM_ROUTE[(h, w)]], stem
     x, plan = D.letterbox_f16(frames)
     box, cls = det.forward_raw(x)
+    assert "c8<NF1,S2,SRC0>" in ops.conv_routes()  # the unfused stem on the materialised network input
     dets2, counts2 = D.postprocess(box, cls, plan, 0.25, 0.7, 300)
     assert counts.sum() > 0
     assert np.array_equal(counts, counts2)
@@ -364,7 +408,12 @@ def test_fused_stem_equals_letterbox_then_network(gpu, h, w):
     det.close()
 
 
-@pytest.mark.parametrize("variant", ["n", "s"])
+# the graph-level fusions each model size launches at this commit, from its route log (YOLOv8s: its only chain also holds
+# the C2f's closing 1x1; YOLOv8m: no pair and no chain, only its neck reads upsamples in place)
+PAIR_FUSIONS = {"n": ("POST", "UP", "CAT", "chain"), "s": ("POST", "UP", "CAT"), "m": ("UP",)}
+
+
+@pytest.mark.parametrize("variant", ["n", "s", "m"])
 def test_fused_3x3_1x1_pairs_are_bit_identical_to_separate_launches(gpu, variant, tmp_path):
     """model.1 -> model.2.cv1 and model.3 -> model.4.cv1 run as ONE launch (the 1x1 consumes the 3x3's tile on chip),
     the shallow C2f Bottlenecks (3x3 -> 3x3 + x, 16 / 32 channels) run as one launch with the intermediate in LDS
@@ -385,8 +434,9 @@ def test_fused_3x3_1x1_pairs_are_bit_identical_to_separate_launches(gpu, variant
         "x, _ = D.letterbox_f16(f)\n"
         "box, cls = det.forward_raw(x)\n"
         "np.savez(sys.argv[1], *[t.cpu().numpy() for t in box + cls])\n"
+        + ROUTES_DUMP
     ) % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), variant, variant)
-    outs = {}
+    outs, routes = {}, {}
     for flag in ("1", "0"):
         path = tmp_path / f"heads_{flag}.npz"
         # every graph-level fusion on / off
@@ -396,7 +446,17 @@ def test_fused_3x3_1x1_pairs_are_bit_identical_to_separate_launches(gpu, variant
         subprocess.run([sys.executable, "-c", code, str(path)], check=True, env=env, timeout=300)
         with np.load(path) as z:
             outs[flag] = [z[k] for k in z.files]
+        routes[flag] = _child_routes(path)
     assert len(outs["1"]) == 6
+    # Not vacuous: the fused process launched what the switches stand for, the other one none of it.
+    kinds = {"POST": lambda r: r.startswith("persist<") and "POST1" in r,       # a 3x3 + 1x1 pair
+             "UP": lambda r: r.startswith("1x1<") and "UP1" in r,               # an upsample read in place
+             "CAT": lambda r: r.startswith("chain<") and "CAT0" not in r,       # a Bottleneck chain with the closing 1x1
+             "chain": lambda r: r.startswith("chain<") and "CAT0" in r}         # a Bottleneck chain alone
+    for kind in PAIR_FUSIONS[variant]:
+        assert any(kinds[kind](r) for r in routes["1"]), (kind, routes["1"])
+    for kind, is_fused in kinds.items():
+        assert not any(is_fused(r) for r in routes["0"]), (kind, routes["0"])
     for a, b in zip(outs["1"], outs["0"]):
         assert a.dtype == np.float32 and np.array_equal(a, b)
 

@@ -1,5 +1,5 @@
 """GPU box, run with EIOKU_HIP_LIB=eioku_amd/libeioku_hip_bc.so (tests/test_bounds_gpu.py starts it as a child process):
-the conv family's test cases, whole forwards of three model sizes and detect() on four source geometries through the
+the conv family's test cases (parity and epilogue tables), whole forwards of three model sizes and detect() on four source geometries through the
 bounds-check build; prints one JSON line {"selftest": ..., "violations": ..., "line": ..., "launches": ...}."""
 import ctypes as C
 import json
@@ -32,7 +32,7 @@ def main():
     assert bounds(reset=True)[0] == 0
     launches = 0
     # 1. the parity cases of tests/test_conv_gpu.py: every kernel family, ragged shapes, slices, residuals
-    from test_conv_gpu import CASES
+    from test_conv_gpu import CASES, EPILOGUE_CASES, launch_epilogue
 
     rng = np.random.default_rng(0)
     for (n, h, w, cin, cout, k, stride) in CASES:
@@ -48,6 +48,11 @@ def main():
                            residual=torch.from_numpy(r).to(gpu) if res else None)
             launches += 1
     out["after_cases"] = bounds()[0]
+    # the epilogue table: every route writing a ragged cout tile into a slice, residual slices, odd couts, fp32 output
+    for item in EPILOGUE_CASES:
+        launch_epilogue(gpu, item)
+        launches += 1
+    out["after_epilogues"] = bounds()[0]
     # 2. whole forwards at 96 x 160 (every layer of v8n / v8s / v8m incl. the fused pairs, chains, flat and generic kernels)
     from eioku_amd import weights as W
 
