@@ -194,6 +194,14 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eioku_keyword_select": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_thumbs_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "eioku_thumbs_destroy": (None, [C.c_void_p]),
+    "eioku_thumbs_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eioku_thumbs_jpeg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_uint64), C.c_void_p]),
+    "eioku_thumbs_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "eioku_thumbs_last_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

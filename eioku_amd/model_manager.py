@@ -12,6 +12,8 @@ ffmpeg / OpenCV / Ultralytics on the CPU.
                                            duration_ms}]}                              (ref :715-835)
     extract_ocr(video_path, config)    -> {"detections": [{frame_index, timestamp_ms, text, confidence,
                                            language, polygon}], "language"}           (ref :469-558)
+    generate_thumbnails(video_path, config) -> {"thumbnails": [{scene_index, start_ms, end_ms, timestamp_ms,
+                                           frame_index, width, height, thumbnail_path, bytes}]}   (design only)
 
 What changes underneath (and nothing else): sampled frames are detected in batches instead of one
 ``model(frame)`` call each, and the scene score is computed by K1/K2 instead of an ffmpeg child
@@ -613,6 +615,86 @@ class ModelManager:
                 src.release()
         except Exception as e:
             logger.error(f"Scene detection failed: {e}", exc_info=True)
+            raise
+
+    # ---- thumbnails: one JPEG per scene (K18) -----------------------------------------------------------------
+    async def generate_thumbnails(self, video_path: str, config: dict) -> dict:
+        """One thumbnail per scene, resized and JPEG-encoded on the HIP path (``eioku_amd.thumbs``): the stage the
+        reference's design schedules behind scene detection.  ``config``: ``scenes`` (the list ``detect_scenes`` returned;
+        absent: ``detect_scenes`` is called with ``config["scene_detection"]``), ``size`` (bounding box, default
+        ``(320, 180)``), ``quality`` (75), ``position`` (``"start"`` / ``"middle"``: which frame of the scene) and
+        ``output_dir`` (required).  One sequential pass over the file uploads only the wanted frames; the files are
+        ``<output_dir>/scene_<scene_index:04d>.jpg``."""
+        try:
+            from . import scene as scene_mod
+            from .thumbs import MAX_BATCH, ThumbnailEncoder, scene_frame_index, thumbnail_size
+
+            if not config.get("output_dir"):
+                raise ValueError("generate_thumbnails needs config['output_dir']")
+            out_dir = Path(config["output_dir"])
+            position = config.get("position", "start")
+            scenes = config.get("scenes")
+            if scenes is None:
+                scenes = (await self.detect_scenes(video_path, config.get("scene_detection", {})))["scenes"]
+            logger.info(f"Thumbnail generation: {video_path} ({len(scenes)} scenes, device: {self._get_device()})")
+            src = self._open(video_path)
+            fps = src.fps or 30
+            total_frames = int(src.total_frames)
+            wanted: dict[int, list[dict]] = {}  # frame index -> the scenes it illustrates
+            for sc in scenes:
+                wanted.setdefault(scene_frame_index(sc, fps, total_frames, position), []).append(sc)
+            if getattr(src, "yuv_layout", None) is None and hasattr(src, "try_yuv"):
+                src.try_yuv()
+            yuv = getattr(src, "yuv_layout", None)
+            encoder = ThumbnailEncoder(config.get("size", (320, 180)), config.get("quality", 75))
+            out_dir.mkdir(parents=True, exist_ok=True)
+            rows: list[dict] = []
+            batch = max(1, min(self._batch_size, MAX_BATCH))
+
+            def flush(indices, frames):
+                host = np.stack(frames)
+                if yuv:  # decoder planes: 1.5 bytes per pixel cross PCIe, BGR is made on the device
+                    import torch
+
+                    h = host.shape[1] * 2 // 3
+                    host = scene_mod.yuv420_to_bgr(torch.from_numpy(host).to(torch.device("cuda", torch.cuda.current_device())),
+                                                   h, host.shape[2], yuv)
+                h, w = int(host.shape[1]), int(host.shape[2])
+                tw, th = thumbnail_size(w, h, encoder.size)
+                for idx, data in zip(indices, encoder.encode(host)):
+                    for sc in wanted[idx]:
+                        path = out_dir / f"scene_{int(sc['scene_index']):04d}.jpg"
+                        path.write_bytes(data)
+                        rows.append({"scene_index": int(sc["scene_index"]), "start_ms": int(sc["start_ms"]),
+                                     "end_ms": int(sc["end_ms"]), "timestamp_ms": _timestamp_ms(idx, fps), "frame_index": idx,
+                                     "width": tw, "height": th, "thumbnail_path": str(path), "bytes": len(data)})
+
+            try:
+                indices, frames = [], []
+                last = max(wanted) if wanted else -1
+                for frame_idx in range(last + 1):
+                    if frame_idx in wanted:
+                        ret, frame = src.read_yuv() if yuv else src.read()
+                        if not ret:
+                            break
+                        indices.append(frame_idx)
+                        frames.append(frame)
+                        if len(frames) >= batch:
+                            flush(indices, frames)
+                            indices, frames = [], []
+                    elif not src.grab():
+                        break
+                if frames:
+                    flush(indices, frames)
+            finally:
+                src.release()
+                encoder.close()
+            by_scene = {r["scene_index"]: r for r in rows}  # rows in the order of the scene list (a stream that ended
+            rows = [by_scene[int(sc["scene_index"])] for sc in scenes if int(sc["scene_index"]) in by_scene]  # early: fewer)
+            logger.info(f"✅ Thumbnail generation complete: {len(rows)} thumbnails")
+            return {"thumbnails": rows}
+        except Exception as e:
+            logger.error(f"Thumbnail generation failed: {e}", exc_info=True)
             raise
 
     @staticmethod

@@ -29,15 +29,18 @@ logger = logging.getLogger(__name__)
 
 TASK_TO_ARTIFACT_TYPE = {"object_detection": "object.detection", "face_detection": "face.detection",
                          "scene_detection": "scene", "segment_embedding": "segment.embedding",
-                         "place_detection": "place.classification", "ocr": "ocr.text", "topic_extraction": "topic"}
+                         "place_detection": "place.classification", "ocr": "ocr.text", "topic_extraction": "topic",
+                         "thumbnail_generation": "scene.thumbnail"}
 TASK_TO_RESULT_KEY = {"object_detection": "detections", "face_detection": "detections", "scene_detection": "scenes",
                       "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections",
-                      "topic_extraction": "topics"}
+                      "topic_extraction": "topics", "thumbnail_generation": "thumbnails"}
 # the reference's seven (task_handler.py:92-127) + the one its semantic-search design adds after transcription
 # (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them; and the topic stage its
-# worker configs schedule (config/*.json "topic_extraction"; tasks.md 12.1-12.3): KeyBERT keywords of the segments
+# worker configs schedule (config/*.json "topic_extraction"; tasks.md 12.1-12.3): KeyBERT keywords of the segments; and the
+# thumbnail worker the design runs behind scene detection (design.md:276-297): one JPEG per scene
 KNOWN_TASK_TYPES = ("object_detection", "face_detection", "transcription", "ocr", "place_detection",
-                    "scene_detection", "metadata_extraction", "segment_embedding", "topic_extraction")
+                    "scene_detection", "metadata_extraction", "segment_embedding", "topic_extraction",
+                    "thumbnail_generation")
 
 
 @dataclass
@@ -166,6 +169,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             result = await model_manager.classify_places(video_path, config or {})
         elif task_type == "ocr" and ctx.get("gpu_ocr"):  # opt-in: without it ocr stays with the reference worker
             result = await model_manager.extract_ocr(video_path, config or {})
+        elif task_type == "thumbnail_generation":  # one "scene.thumbnail" envelope per scene, spanning the scene
+            result = await model_manager.generate_thumbnails(video_path, config or {})
         elif task_type in ("segment_embedding", "topic_extraction"):
             # segments: the transcription task's output for this video.  The reference would read them back from its
             # artifact table; without a database they arrive in the job config or through ctx["segment_source"](video_id)

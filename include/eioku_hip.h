@@ -545,6 +545,31 @@ int eioku_keyword_select(const float* x, int n_rows, const float* terms, int n_t
                          const int32_t* cand, int top_n, float diversity, int32_t* idx, float* score, int32_t* count,
                          int mem, void* stream);
 
+/* ---- thumbnails: Pillow's bicubic resize and libjpeg's baseline encoder (csrc/thumbs.hip, K18) ------------------------
+ * Fills the thumbnail_generation stage.  Every image pointer is a DEVICE pointer, every table a HOST pointer.  At most 64
+ * images per call and 1024 pixels per thumbnail side, else EIOKU_EINVAL before the device is touched (the handle stays
+ * usable).  All stages are integer arithmetic: the results are the bytes Pillow 12 / libjpeg-turbo produce.
+ * resize: n BGR u8 frames [n][h][w][3] -> rgb_out [n][th][tw][3] (RGB), Image.resize((tw, th), BICUBIC): horizontal pass,
+ *   8-bit intermediate, vertical pass.  Tables from the host (eioku_amd/thumbs.py: bicubic_tables): bounds [out][2] =
+ *   {first input index, taps}, k [out][ksize] int32 taps x 2^22.  Asynchronous on `stream`.
+ * jpeg: n RGB u8 images [n][th][tw][3] -> per image the 4:2:0 baseline scan's quantised coefficients (coef_out, HOST,
+ *   optional: [n][mcus][6][64] int16, per 16x16 MCU in scan order Y00 Y01 Y10 Y11 Cb Cr, zigzag) and its Huffman-coded
+ *   bitstream without padding, byte stuffing and markers, kept on the device.  qtab: [2][64] luma / chroma divisors in
+ *   natural order, each 1..255.  nbits_out [n]: bits per image; *bytes_out: size of the packed streams, where image i
+ *   starts at the byte offset sum_{j<i} 4 * ceil(nbits[j] / 32) and unused trailing bits are 0.  Synchronous.
+ * read: the packed streams of the last jpeg call -> out (HOST, cap >= *bytes_out).  Synchronous.
+ * last_ms: device milliseconds of the last resize, block stage, entropy stage and read (0 for a stage not yet run). */
+typedef struct eioku_thumbs eioku_thumbs_t;
+int eioku_thumbs_create(eioku_thumbs_t** out);
+void eioku_thumbs_destroy(eioku_thumbs_t* t);
+int eioku_thumbs_resize(eioku_thumbs_t* t, const uint8_t* bgr, int n, int h, int w, int th, int tw, const int32_t* xbounds,
+                        const int32_t* xk, int kx, const int32_t* ybounds, const int32_t* yk, int ky, uint8_t* rgb_out,
+                        void* stream);
+int eioku_thumbs_jpeg(eioku_thumbs_t* t, const uint8_t* rgb, int n, int th, int tw, const uint16_t* qtab, int16_t* coef_out,
+                      uint32_t* nbits_out, uint64_t* bytes_out, void* stream);
+int eioku_thumbs_read(eioku_thumbs_t* t, uint8_t* out, size_t cap, void* stream);
+int eioku_thumbs_last_ms(eioku_thumbs_t* t, double* ms4);
+
 #ifdef __cplusplus
 }
 #endif
