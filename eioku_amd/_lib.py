@@ -202,7 +202,35 @@ SIGNATURES = {
                                     C.POINTER(C.c_uint64), C.c_void_p]),
     "eioku_thumbs_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "eioku_thumbs_last_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "eioku_whisper_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "eioku_whisper_destroy": (None, [C.c_void_p]),
+    "eioku_whisper_num_tensors": (C.c_int, [C.c_void_p]),
+    "eioku_whisper_tensor_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int)]),
+    "eioku_whisper_set_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "eioku_whisper_set_audio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong]),
+    "eioku_whisper_logmel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_whisper_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "eioku_whisper_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_whisper_forced_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "eioku_whisper_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "eioku_whisper_encoder_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "eioku_whisper_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_whisper_last_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
+
+
+class WhisperCfg(C.Structure):
+    """``eioku_whisper_cfg_t`` (include/eioku_hip.h)."""
+
+    _fields_ = [(n, C.c_int) for n in (
+        "n_mels", "d_model", "heads", "enc_layers", "dec_layers", "enc_ffn", "dec_ffn", "vocab", "max_source_positions",
+        "max_target_positions", "eot", "no_timestamps", "timestamp_begin", "no_speech", "max_initial_timestamp_index",
+        "n_suppress", "n_begin_suppress", "n_langs")] + [
+        ("suppress", C.c_void_p), ("begin_suppress", C.c_void_p), ("lang_ids", C.c_void_p), ("mel_filters", C.c_void_p)]
+
 
 _lib = None
 _lock = threading.Lock()

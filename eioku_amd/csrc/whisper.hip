@@ -1,0 +1,1104 @@
+// K19 / K20: Whisper transcription on gfx950 (DESIGN.md "K19 / K20").
+//   K19  k_mel_frames / k_mel_max / k_mel_finish   log-mel spectrogram, DFT and mel product in fp64
+//   K20  k_gemm         C = A . W^T on v_mfma_f32_16x16x32_f16: 16 weight rows per wave against MT tiles of 16 activation
+//                       rows.  MT = 4 for the encoder (M = B * ctx), MT = 1 for the decoder step (M = B <= 16: every
+//                       weight element is read once and used once per lane: a weight-streaming GEMM)
+//        k_attn         softmax(q k^T / 8) v for head dimension 64 and any number of keys (encoder self-attention over ctx
+//                       keys, decoder self-attention against the KV cache, cross-attention), scores in LDS, fp32
+//        k_logits       logits against the tied embedding, the logit rules, and per-workgroup partials (max / argmax over
+//                       text and timestamp ids, log-sum-exp over all and over timestamp ids); the vocab-wide logits are
+//                       written only for the debug entry points
+//        k_select       combines the partials, applies the timestamp-mass rule, picks the token, updates the lane state
+// Precision points (tests/whisper_oracle.py, fp16=True, rounds at the same places): weights of every linear / conv layer
+// and the token embedding are fp16; biases, LayerNorm parameters and both position tables fp32; the residual stream is
+// fp32; LayerNorm outputs, q / k / v, attention outputs, GELU outputs and the mel input are rounded to fp16.
+#include "common.h"
+
+#include <hip/hip_fp16.h>
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace eioku;
+
+namespace {
+
+typedef _Float16 h16;
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float float4v __attribute__((ext_vector_type(4)));
+
+constexpr int kNfft = 400, kHop = 160, kBins = 201, kPad = 200;
+constexpr float kNegInf = -INFINITY;
+
+// ---- K19 ---------------------------------------------------------------------------------------------------------------
+// grid (T, B), 256 threads.  Frame t of window b: the window's chunk is samples[off .. off + T * hop) (zeros past the end
+// of the audio), reflect-padded by 200; x[n] = chunk[t * hop + n - 200] * hann[n].  Threads k < 201 compute the DFT bin k
+// with the twiddles tw[(k n) mod 400]; threads m < n_mels the mel row m.  out: log10(max(mel, 1e-10)) [B][n_mels][T] fp64.
+__global__ __launch_bounds__(256) void k_mel_frames(const float* __restrict__ samples, long long n_samples,
+                                                    const long long* __restrict__ offsets, int T, int n_mels,
+                                                    const double* __restrict__ hann, const double* __restrict__ tw_cos,
+                                                    const double* __restrict__ tw_sin, const double* __restrict__ filt,
+                                                    double* __restrict__ out) {
+  __shared__ double x[kNfft];
+  __shared__ double pw[kBins];
+  const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const long long off = offsets[b];
+  const long long N = (long long)T * kHop;
+  for (int n = tid; n < kNfft; n += 256) {
+    long long i = (long long)t * kHop + n - kPad;
+    if (i < 0) i = -i;
+    if (i >= N) i = 2 * (N - 1) - i;
+    const long long g = off + i;
+    const double s = (g >= 0 && g < n_samples) ? (double)samples[g] : 0.0;
+    x[n] = s * hann[n];
+  }
+  __syncthreads();
+  if (tid < kBins) {
+    double re = 0.0, im = 0.0;
+    int idx = 0;
+    for (int n = 0; n < kNfft; ++n) {
+      re += x[n] * tw_cos[idx];
+      im -= x[n] * tw_sin[idx];
+      idx += tid;
+      if (idx >= kNfft) idx -= kNfft;
+    }
+    pw[tid] = re * re + im * im;
+  }
+  __syncthreads();
+  for (int m = tid; m < n_mels; m += 256) {
+    double a = 0.0;
+    const double* f = filt + (size_t)m * kBins;
+    for (int k = 0; k < kBins; ++k) a += f[k] * pw[k];
+    out[((size_t)b * n_mels + m) * T + t] = log10(fmax(a, 1e-10));
+  }
+}
+
+__global__ __launch_bounds__(256) void k_mel_max(const double* __restrict__ v, long long per_window, double* __restrict__ mx) {
+  __shared__ double red[256];
+  const double* p = v + (size_t)blockIdx.x * per_window;
+  double m = -INFINITY;
+  for (long long i = threadIdx.x; i < per_window; i += 256) m = fmax(m, p[i]);
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) mx[blockIdx.x] = red[0];
+}
+
+__global__ __launch_bounds__(256) void k_mel_finish(const double* __restrict__ v, long long per_window, const double* __restrict__ mx,
+                                                    long long total, float* __restrict__ out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const double floor_ = mx[i / per_window] - 8.0;
+  out[i] = (float)((fmax(v[i], floor_) + 4.0) / 4.0);
+}
+
+// ---- weight conversion -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cvt_f16(const float* __restrict__ src, size_t n, h16* __restrict__ dst) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = (h16)src[i];
+}
+
+// conv weight [rows][cin][3] fp32 -> [rows][ldk] fp16 with column tap * cin + c (columns past 3 cin stay 0)
+__global__ __launch_bounds__(256) void k_cvt_conv(const float* __restrict__ src, int rows, int cin, int ldk, h16* __restrict__ dst) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)rows * ldk) return;
+  const int n = (int)(i / ldk), col = (int)(i % ldk);
+  float v = 0.f;
+  if (col < 3 * cin) {
+    const int tap = col / cin, c = col % cin;
+    v = src[((size_t)n * cin + c) * 3 + tap];
+  }
+  dst[i] = (h16)v;
+}
+
+// ---- im2col for the two k3 p1 convolutions ------------------------------------------------------------------------------
+// mel [B][C][Tin] fp32 -> col [B * Tin][ldk] fp16, col[(b, t)][tap * C + c] = mel[b][c][t + tap - 1]
+__global__ __launch_bounds__(256) void k_im2col_mel(const float* __restrict__ mel, int B, int C, int Tin, int ldk, h16* __restrict__ col) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)B * Tin * ldk) return;
+  const int k = (int)(i % ldk);
+  const size_t row = i / ldk;
+  const int t = (int)(row % Tin), b = (int)(row / Tin);
+  float v = 0.f;
+  if (k < 3 * C) {
+    const int tap = k / C, c = k % C, ts = t + tap - 1;
+    if (ts >= 0 && ts < Tin) v = mel[((size_t)b * C + c) * Tin + ts];
+  }
+  col[i] = (h16)v;
+}
+
+// h [B][Tin][C] fp16 -> col [B * Tout][3 C], col[(b, t)][tap * C + c] = h[b][2 t + tap - 1][c]  (stride 2, Tout = Tin / 2)
+__global__ __launch_bounds__(256) void k_im2col_s2(const h16* __restrict__ h, int B, int C, int Tin, h16* __restrict__ col) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const int Tout = Tin / 2, K = 3 * C;
+  if (i >= (size_t)B * Tout * K) return;
+  const int k = (int)(i % K);
+  const size_t row = i / K;
+  const int t = (int)(row % Tout), b = (int)(row / Tout);
+  const int tap = k / C, c = k % C, ts = 2 * t + tap - 1;
+  col[i] = (ts >= 0 && ts < Tin) ? h[((size_t)b * Tin + ts) * C + c] : (h16)0.f;
+}
+
+// ---- GEMM ---------------------------------------------------------------------------------------------------------------
+enum { EPI_F16 = 0, EPI_GELU_F16 = 1, EPI_RESID = 2, EPI_GELU_POS = 3 };
+
+__device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+
+// out[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]).  grid (ceil(N / 64), ceil(M / (16 MT))), 4 waves: wave w owns weight
+// rows n0 = 64 bx + 16 w .. + 15.  MFMA 16x16x32: A operand = weight rows (lane (r, u): row r, k 8u .. 8u + 7), B operand =
+// activation rows; lane holds D[n0 + 4u + t][m0 + r].  K % 32 == 0, lda / ldw % 8 == 0.  Each output element is one
+// k-ordered sum whatever M is, so a lane's result does not depend on the batch around it.
+//   EPI_F16      out fp16 [m * ldc + n]            EPI_GELU_F16  the same after GELU
+//   EPI_RESID    out fp32 [m * ldc + n] += value   EPI_GELU_POS  out fp32 = GELU(value) + pos[m % pos_rows][n]
+template <int MT, int EPI>
+__global__ __launch_bounds__(256) void k_gemm(const h16* __restrict__ A, int lda, const h16* __restrict__ W, int ldw,
+                                              const float* __restrict__ bias, int M, int N, int K, void* __restrict__ out,
+                                              long long ldc, const float* __restrict__ pos, int pos_rows) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, u = lane >> 4;
+  const int n0 = (blockIdx.x * 4 + wave) * 16, m0 = blockIdx.y * 16 * MT;
+  if (n0 >= N) return;
+  const bool wl = n0 + r < N;
+  const h16* wr = W + (size_t)(wl ? n0 + r : 0) * ldw + 8 * u;
+  const h16* ar[MT];
+  bool al[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const int mm = m0 + 16 * i + r;
+    al[i] = mm < M;
+    ar[i] = A + (size_t)(al[i] ? mm : 0) * lda + 8 * u;
+  }
+  float4v acc[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) acc[i] = float4v{0.f, 0.f, 0.f, 0.f};
+  const half8 zero = {};
+  for (int k = 0; k < K; k += 32) {
+    const half8 w = wl ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(wr + k)) : zero;
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const half8 a = al[i] ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(ar[i] + k)) : zero;
+      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, a, acc[i], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const int mm = m0 + 16 * i + r;
+    if (mm >= M) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int n = n0 + 4 * u + t;
+      if (n >= N) continue;
+      const float v = acc[i][t] + (bias ? bias[n] : 0.f);
+      const size_t o = (size_t)mm * (size_t)ldc + n;
+      if (EPI == EPI_F16) reinterpret_cast<h16*>(out)[o] = (h16)v;
+      if (EPI == EPI_GELU_F16) reinterpret_cast<h16*>(out)[o] = (h16)gelu(v);
+      if (EPI == EPI_RESID) reinterpret_cast<float*>(out)[o] += v;
+      if (EPI == EPI_GELU_POS) reinterpret_cast<float*>(out)[o] = gelu(v) + pos[(size_t)(mm % pos_rows) * N + n];
+    }
+  }
+}
+
+// ---- LayerNorm: fp32 row -> fp16, one wave per row ------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ln(const float* __restrict__ x, int M, int d, const float* __restrict__ g,
+                                            const float* __restrict__ b, h16* __restrict__ out) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const float* xr = x + (size_t)row * d;
+  float s = 0.f;
+  for (int i = lane; i < d; i += 64) s += xr[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const float mean = s / (float)d;
+  float q = 0.f;
+  for (int i = lane; i < d; i += 64) {
+    const float c = xr[i] - mean;
+    q += c * c;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  const float inv = 1.f / sqrtf(q / (float)d + 1e-5f);
+  for (int i = lane; i < d; i += 64) out[(size_t)row * d + i] = (h16)((xr[i] - mean) * inv * g[i] + b[i]);
+}
+
+// decoder input: x[b] = embed[token][:] + pos[s][:].  token = toks ? toks[b * tstride] : uniform
+__global__ __launch_bounds__(256) void k_embed(const int* __restrict__ toks, int tstride, int uniform, int vocab, int d, int s,
+                                               const h16* __restrict__ emb, const float* __restrict__ pos, float* __restrict__ x) {
+  const int b = blockIdx.x;
+  int tok = toks ? toks[(size_t)b * tstride] : uniform;
+  tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
+  for (int i = threadIdx.x; i < d; i += 256) x[(size_t)b * d + i] = (float)emb[(size_t)tok * d + i] + pos[(size_t)s * d + i];
+}
+
+// ---- attention ----------------------------------------------------------------------------------------------------------
+// grid (ceil(n_q / (4 QPW)), heads, B), 4 waves, each wave QPW query rows against all n_keys keys of its head.  Pass 1: lane
+// j takes keys j, j + 64, ...: score = (q . k) / 8 into LDS, running max.  Pass 2: exp and sum.  Pass 3: lane = output
+// dimension, o = sum_j p_j v[j][lane] (a 128-byte row per key).  Dynamic LDS: 4 QPW (n_keys + 64) floats.
+template <int QPW>
+__global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long long q_bs, int q_rs, const h16* __restrict__ Kc,
+                                              const h16* __restrict__ Vc, long long kv_bs, int kv_rs, int n_q, int n_keys,
+                                              h16* __restrict__ O, long long o_bs, int o_rs) {
+  extern __shared__ float smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, head = blockIdx.y, b = blockIdx.z;
+  const int q0 = (blockIdx.x * 4 + wave) * QPW;
+  float* sc = smem + (size_t)wave * QPW * n_keys;
+  float* qs = smem + (size_t)4 * QPW * n_keys + wave * QPW * 64;
+#pragma unroll
+  for (int i = 0; i < QPW; ++i) {
+    const int qi = q0 + i;
+    qs[i * 64 + lane] = qi < n_q ? (float)Q[(size_t)b * q_bs + (size_t)qi * q_rs + head * 64 + lane] : 0.f;
+  }
+  __syncthreads();
+  const h16* kb = Kc + (size_t)b * kv_bs + head * 64;
+  const h16* vb = Vc + (size_t)b * kv_bs + head * 64;
+  float mx[QPW], sum[QPW], o[QPW];
+#pragma unroll
+  for (int i = 0; i < QPW; ++i) mx[i] = kNegInf, sum[i] = 0.f, o[i] = 0.f;
+  for (int j = lane; j < n_keys; j += 64) {
+    const uint4* kr = reinterpret_cast<const uint4*>(kb + (size_t)j * kv_rs);
+    float s[QPW];
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) s[i] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const half8 kk = __builtin_bit_cast(half8, kr[c]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float kf = (float)kk[e];
+#pragma unroll
+        for (int i = 0; i < QPW; ++i) s[i] += qs[i * 64 + c * 8 + e] * kf;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) {
+      s[i] *= 0.125f;
+      sc[(size_t)i * n_keys + j] = s[i];
+      mx[i] = fmaxf(mx[i], s[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < QPW; ++i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], off, 64));
+    for (int j = lane; j < n_keys; j += 64) {
+      const float p = expf(sc[(size_t)i * n_keys + j] - mx[i]);
+      sc[(size_t)i * n_keys + j] = p;
+      sum[i] += p;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum[i] += __shfl_xor(sum[i], off, 64);
+  }
+  __syncthreads();
+  for (int j = 0; j < n_keys; ++j) {
+    const float vf = (float)vb[(size_t)j * kv_rs + lane];
+#pragma unroll
+    for (int i = 0; i < QPW; ++i) o[i] += sc[(size_t)i * n_keys + j] * vf;
+  }
+#pragma unroll
+  for (int i = 0; i < QPW; ++i) {
+    const int qi = q0 + i;
+    if (qi < n_q) O[(size_t)b * o_bs + (size_t)qi * o_rs + head * 64 + lane] = (h16)(o[i] / sum[i]);
+  }
+}
+
+// ---- token selection ----------------------------------------------------------------------------------------------------
+struct SelCfg {
+  int vocab, eot, no_ts, tb, no_speech, max_init;
+};
+struct LaneState {  // per decode lane, on the device
+  int n;            // tokens sampled so far
+  int last, penult; // the last two sampled tokens (-1: none)
+  int last_ts;      // the last sampled timestamp id (-1: none)
+  int done;
+  float sum;        // sum of the sampled tokens' log-probabilities
+};
+// per (lane, workgroup) partial over the workgroup's 64 vocabulary ids
+constexpr int kNP = 10;  // max_text, arg_text, max_ts, arg_ts, m_all, s_all, s_ts (relative to max_ts), m_raw, s_raw, unused
+constexpr int kFlagSuppress = 1, kFlagBegin = 2;  // flags[id]: bit 0 / 1, language index + 1 in bits 2..
+
+__device__ __forceinline__ bool rule_masks(int n, const SelCfg& c, unsigned flag, const LaneState& st) {
+  const bool is_ts = n >= c.tb;
+  bool mask = (flag & kFlagSuppress) != 0 || n == c.no_ts;
+  if (st.n == 0) {
+    mask = mask || (flag & kFlagBegin) != 0 || !is_ts;
+    if (c.max_init >= 0 && n > c.tb + c.max_init) mask = true;
+  }
+  const bool last_ts = st.n >= 1 && st.last >= c.tb;
+  const bool pen_ts = st.n < 2 || st.penult >= c.tb;
+  if (last_ts) {
+    if (pen_ts) mask = mask || is_ts;
+    else mask = mask || n < c.eot;
+  }
+  if (st.last_ts >= 0) {
+    const int limit = (last_ts && !pen_ts) ? st.last_ts : st.last_ts + 1;
+    if (is_ts && n < limit) mask = true;
+  }
+  return mask;
+}
+
+// grid ceil(vocab / 64), 4 waves; wave w computes ids v0 + 16 w .. + 15 for 16 lanes at a time on the MFMA (or reads the
+// supplied logits), masks them, and parks raw and masked values in LDS; thread b < 16 then folds the 64 ids of its lane
+// in id order.  rules = 0: no masking (teacher-forced positions).
+template <bool SUPPLIED>
+__global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d, const h16* __restrict__ E,
+                                                const float* __restrict__ supplied, int B, SelCfg c,
+                                                const uint16_t* __restrict__ flags, const LaneState* __restrict__ st, int rules,
+                                                float* __restrict__ partial, int nblk, float* __restrict__ raw_out,
+                                                long long raw_ld, float* __restrict__ masked_out, float* __restrict__ info,
+                                                int nlang) {
+  __shared__ float raw[64][17];
+  __shared__ float msk[64][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, u = lane >> 4;
+  const int v0 = blockIdx.x * 64, n0 = v0 + wave * 16;
+  for (int bt = 0; bt < B; bt += 16) {
+    const int b = bt + r;
+    float vals[4];
+    if (SUPPLIED) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int n = n0 + 4 * u + t;
+        vals[t] = (b < B && n < c.vocab) ? supplied[(size_t)b * c.vocab + n] : 0.f;
+      }
+    } else {
+      const bool wl = n0 + r < c.vocab, al = b < B;
+      const h16* wr = E + (size_t)(wl ? n0 + r : 0) * d + 8 * u;
+      const h16* ar = H + (size_t)(al ? b : 0) * d + 8 * u;
+      float4v acc = {0.f, 0.f, 0.f, 0.f};
+      const half8 zero = {};
+      for (int k = 0; k < d; k += 32) {
+        const half8 w = wl ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(wr + k)) : zero;
+        const half8 a = al ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(ar + k)) : zero;
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, a, acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) vals[t] = acc[t];
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int n = n0 + 4 * u + t, row = wave * 16 + 4 * u + t;
+      float rv = kNegInf, mv = kNegInf;
+      if (b < B && n < c.vocab) {
+        rv = vals[t];
+        const unsigned f = flags[n];
+        mv = (rules && rule_masks(n, c, f, st[b])) ? kNegInf : rv;
+        if (raw_out) raw_out[(size_t)b * raw_ld + n] = rv;
+        if (masked_out) masked_out[(size_t)b * c.vocab + n] = mv;
+        if (info) {
+          if (n == c.no_speech) info[(size_t)b * (1 + nlang)] = rv;
+          if ((f >> 2) > 0) info[(size_t)b * (1 + nlang) + (f >> 2)] = rv;
+        }
+      }
+      raw[row][r] = rv;
+      msk[row][r] = mv;
+    }
+    __syncthreads();
+    if (tid < 16 && bt + tid < B) {
+      float max_text = kNegInf, max_ts = kNegInf, m_raw = kNegInf;
+      int arg_text = -1, arg_ts = -1;
+      for (int i = 0; i < 64; ++i) {
+        const int n = v0 + i;
+        const float mv = msk[i][tid];
+        m_raw = fmaxf(m_raw, raw[i][tid]);
+        if (n < c.tb) {
+          if (mv > max_text) max_text = mv, arg_text = n;
+        } else if (mv > max_ts) {
+          max_ts = mv, arg_ts = n;
+        }
+      }
+      const float m_all = fmaxf(max_text, max_ts);
+      float s_all = 0.f, s_ts = 0.f, s_raw = 0.f;
+      for (int i = 0; i < 64; ++i) {
+        const float mv = msk[i][tid], rv = raw[i][tid];
+        if (mv > kNegInf) {
+          s_all += expf(mv - m_all);
+          if (v0 + i >= c.tb) s_ts += expf(mv - max_ts);
+        }
+        if (rv > kNegInf) s_raw += expf(rv - m_raw);
+      }
+      float* p = partial + ((size_t)(bt + tid) * nblk + blockIdx.x) * kNP;
+      p[0] = max_text, p[1] = __int_as_float(arg_text), p[2] = max_ts, p[3] = __int_as_float(arg_ts);
+      p[4] = m_all, p[5] = s_all, p[6] = s_ts, p[7] = m_raw, p[8] = s_raw, p[9] = 0.f;
+    }
+    __syncthreads();
+  }
+}
+
+struct Acc {
+  float max_text, max_ts, m_all, s_all, s_ts, m_raw, s_raw;
+  int arg_text, arg_ts;
+};
+
+__device__ __forceinline__ void lse_merge(float& m, float& s, float pm, float ps) {
+  if (pm == kNegInf) return;
+  if (pm > m) {
+    s = (m == kNegInf ? 0.f : s * expf(m - pm)) + ps;
+    m = pm;
+  } else {
+    s += ps * expf(pm - m);
+  }
+}
+
+__device__ __forceinline__ void acc_merge(Acc& a, const Acc& p) {
+  if (p.max_text > a.max_text || (p.max_text == a.max_text && p.arg_text >= 0 && (a.arg_text < 0 || p.arg_text < a.arg_text)))
+    a.max_text = p.max_text, a.arg_text = p.arg_text;
+  lse_merge(a.m_all, a.s_all, p.m_all, p.s_all);
+  lse_merge(a.m_raw, a.s_raw, p.m_raw, p.s_raw);
+  // the timestamp sum is kept relative to the running timestamp max
+  float mt = a.max_ts, st = a.s_ts;
+  lse_merge(mt, st, p.max_ts, p.s_ts);
+  if (p.max_ts > a.max_ts || (p.max_ts == a.max_ts && p.arg_ts >= 0 && (a.arg_ts < 0 || p.arg_ts < a.arg_ts))) a.arg_ts = p.arg_ts;
+  a.max_ts = mt, a.s_ts = st;
+}
+
+// grid B, one wave: lanes fold the workgroup partials blk = lane, lane + 64, ...; thread 0 folds the 64 lanes in order and
+// decides.  sample: pick a token, update the lane state, store it at tokens[b][idx].  do_info: no-speech probability and
+// language argmax from the unmasked logits (prompt position 0).
+__global__ __launch_bounds__(64) void k_select(const float* __restrict__ partial, int nblk, SelCfg c, LaneState* __restrict__ st,
+                                               int sample, int idx, int do_info, const float* __restrict__ info, int nlang,
+                                               const int* __restrict__ lang_ids, int* __restrict__ tokens, int tok_ld,
+                                               int* __restrict__ cur_tok, float* __restrict__ nsp, int* __restrict__ lang_out,
+                                               float* __restrict__ logprob_out) {
+  __shared__ Acc sh[64];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  Acc a = {kNegInf, kNegInf, kNegInf, 0.f, 0.f, kNegInf, 0.f, -1, -1};
+  for (int k = lane; k < nblk; k += 64) {
+    const float* p = partial + ((size_t)b * nblk + k) * kNP;
+    const Acc q = {p[0], p[2], p[4], p[5], p[6], p[7], p[8], __float_as_int(p[1]), __float_as_int(p[3])};
+    acc_merge(a, q);
+  }
+  sh[lane] = a;
+  __syncthreads();
+  if (lane != 0) return;
+  for (int i = 1; i < 64; ++i) acc_merge(a, sh[i]);
+  if (do_info) {
+    const float lse_raw = a.m_raw + logf(a.s_raw);
+    const float* inf = info + (size_t)b * (1 + nlang);
+    nsp[b] = expf(inf[0] - lse_raw);
+    int best = -1;
+    float bv = kNegInf;
+    for (int i = 0; i < nlang; ++i)
+      if (inf[1 + i] > bv) bv = inf[1 + i], best = i;
+    lang_out[b] = best >= 0 ? lang_ids[best] : -1;
+  }
+  if (!sample) return;
+  LaneState s = st[b];
+  int tok = c.eot;
+  float lp = 0.f;
+  if (!s.done) {
+    const float lse_all = a.m_all + logf(a.s_all);
+    const float lse_ts = a.max_ts > kNegInf ? a.max_ts + logf(a.s_ts) : kNegInf;
+    if (lse_ts > a.max_text) {
+      tok = a.arg_ts, lp = a.max_ts - lse_ts;
+    } else if (a.max_ts > a.max_text) {
+      tok = a.arg_ts, lp = a.max_ts - lse_all;
+    } else {
+      tok = a.arg_text, lp = a.max_text - lse_all;
+    }
+    if (tok < 0) tok = c.eot, lp = 0.f;  // every id masked: cannot happen under the rules, end the lane
+    s.sum += lp;
+    s.penult = s.last;
+    s.last = tok;
+    if (tok >= c.tb) s.last_ts = tok;
+    s.n += 1;
+    if (tok == c.eot) s.done = 1;
+    st[b] = s;
+  }
+  if (tokens) tokens[(size_t)b * tok_ld + idx] = tok;
+  if (cur_tok) cur_tok[b] = tok;
+  if (logprob_out) logprob_out[b] = lp;
+}
+
+// ---- the model ------------------------------------------------------------------------------------------------------------
+enum { T_F16 = 0, T_F32 = 1, T_CONV = 2 };
+
+struct Tensor {
+  std::string name;
+  int rows = 0, cols = 0, kind = T_F16, cin = 0, ldk = 0;
+  void* dev = nullptr;
+  bool set = false;
+  size_t numel() const { return (size_t)rows * cols; }
+};
+
+struct Attn { int q, qb, k, v, vb, o, ob, ln_g, ln_b; };
+struct Layer { Attn self, cross; int fc1, fc1b, fc2, fc2b, ln_g, ln_b; };
+
+int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+}  // namespace
+
+struct eioku_whisper {
+  eioku_whisper_cfg_t cfg{};
+  SelCfg sel{};
+  std::vector<Tensor> tensors;
+  std::vector<Layer> enc, dec;
+  int conv1 = 0, conv1b = 0, conv2 = 0, conv2b = 0, enc_pos = 0, enc_ln_g = 0, enc_ln_b = 0;
+  int emb = 0, dec_pos = 0, dec_ln_g = 0, dec_ln_b = 0;
+  int nlang = 0, nblk = 0, k1pad = 0;
+  // constants
+  double *hann = nullptr, *tw_cos = nullptr, *tw_sin = nullptr, *filt = nullptr;
+  uint16_t* flags = nullptr;
+  int* lang_ids = nullptr;
+  // audio + mel
+  float* samples = nullptr;
+  long long n_samples = 0;
+  long long* d_off = nullptr;
+  double *mel64 = nullptr, *mel_mx = nullptr;
+  float* mel32 = nullptr;
+  // encoder workspace (capacity cap windows)
+  int cap = 0, enc_B = 0;
+  h16 *col1 = nullptr, *h1 = nullptr, *col2 = nullptr, *eh = nullptr, *eq = nullptr, *ek = nullptr, *ev = nullptr, *ea = nullptr,
+      *emid = nullptr, *enc_out = nullptr, *crossK = nullptr, *crossV = nullptr;
+  float* ex = nullptr;
+  // decoder workspace
+  h16 *dh = nullptr, *dq = nullptr, *da = nullptr, *dmid = nullptr, *selfK = nullptr, *selfV = nullptr;
+  float *dx = nullptr, *partial = nullptr, *info = nullptr, *nsp = nullptr, *d_logprob = nullptr;
+  LaneState* state = nullptr;
+  int *tokens = nullptr, *cur_tok = nullptr, *lang_out = nullptr, *d_ids = nullptr;
+  double flops = 0;
+  int launches = 0, steps = 0;
+
+  const h16* H(int i) const { return (const h16*)tensors[i].dev; }
+  const float* F(int i) const { return i < 0 ? nullptr : (const float*)tensors[i].dev; }
+};
+
+namespace {
+
+template <typename T>
+int dalloc(T** p, size_t n) {
+  if (*p) {
+    (void)hipFree(*p);
+    *p = nullptr;
+  }
+  if (hipMalloc((void**)p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
+    set_error("hipMalloc of %zu bytes failed", n * sizeof(T));
+    return EIOKU_ENOMEM;
+  }
+  return EIOKU_OK;
+}
+
+#define W_TRY(expr)                \
+  do {                             \
+    const int _rc = (expr);        \
+    if (_rc != EIOKU_OK) return _rc; \
+  } while (0)
+
+template <int MT, int EPI>
+int gemm(eioku_whisper* m, const h16* A, int lda, const h16* W, int ldw, const float* bias, int M, int N, int K, void* out,
+         long long ldc, const float* pos = nullptr, int pos_rows = 1) {
+  EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0 && ldw % 8 == 0, "GEMM K %d / lda %d / ldw %d misaligned", K, lda, ldw);
+  const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
+  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, 0, A, lda, W, ldw, bias, M, N, K, out, ldc, pos, pos_rows);
+  EIOKU_LAUNCH_CHECK();
+  m->flops += 2.0 * M * N * K;
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+int ln(eioku_whisper* m, const float* x, int M, int d, int g, int b, h16* out) {
+  hipLaunchKernelGGL(k_ln, dim3((M + 3) / 4), dim3(256), 0, 0, x, M, d, m->F(g), m->F(b), out);
+  EIOKU_LAUNCH_CHECK();
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+template <int QPW>
+int attn(eioku_whisper* m, const h16* Q, long long q_bs, int q_rs, const h16* K, const h16* V, long long kv_bs, int kv_rs, int n_q,
+         int n_keys, int B, h16* O, long long o_bs, int o_rs) {
+  const size_t lds = (size_t)4 * QPW * (n_keys + 64) * sizeof(float);
+  EIOKU_REQUIRE(lds <= 64 * 1024, "attention over %d keys needs %zu bytes of LDS", n_keys, lds);
+  const dim3 grid((n_q + 4 * QPW - 1) / (4 * QPW), m->cfg.heads, B);
+  hipLaunchKernelGGL((k_attn<QPW>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs, o_rs);
+  EIOKU_LAUNCH_CHECK();
+  m->flops += 4.0 * B * m->cfg.heads * (double)n_q * n_keys * 64;
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+int ensure_capacity(eioku_whisper* m, int B) {
+  if (B <= m->cap) return EIOKU_OK;
+  const auto& c = m->cfg;
+  const size_t T2 = 2 * (size_t)c.max_source_positions, ctx = c.max_source_positions, d = c.d_model, Tm = c.max_target_positions;
+  const size_t ffn = c.enc_ffn > c.dec_ffn ? c.enc_ffn : c.dec_ffn;
+  m->cap = 0;
+  W_TRY(dalloc(&m->d_off, (size_t)B));
+  W_TRY(dalloc(&m->mel64, B * c.n_mels * T2));
+  W_TRY(dalloc(&m->mel_mx, (size_t)B));
+  W_TRY(dalloc(&m->mel32, B * c.n_mels * T2));
+  W_TRY(dalloc(&m->col1, B * T2 * m->k1pad));
+  W_TRY(dalloc(&m->h1, B * T2 * d));
+  W_TRY(dalloc(&m->col2, B * ctx * 3 * d));
+  W_TRY(dalloc(&m->ex, B * ctx * d));
+  W_TRY(dalloc(&m->eh, B * ctx * d));
+  W_TRY(dalloc(&m->eq, B * ctx * d));
+  W_TRY(dalloc(&m->ek, B * ctx * d));
+  W_TRY(dalloc(&m->ev, B * ctx * d));
+  W_TRY(dalloc(&m->ea, B * ctx * d));
+  W_TRY(dalloc(&m->emid, B * ctx * ffn));
+  W_TRY(dalloc(&m->enc_out, B * ctx * d));
+  W_TRY(dalloc(&m->crossK, c.dec_layers * B * ctx * d));
+  W_TRY(dalloc(&m->crossV, c.dec_layers * B * ctx * d));
+  W_TRY(dalloc(&m->dx, B * d));
+  W_TRY(dalloc(&m->dh, B * d));
+  W_TRY(dalloc(&m->dq, B * d));
+  W_TRY(dalloc(&m->da, B * d));
+  W_TRY(dalloc(&m->dmid, B * ffn));
+  W_TRY(dalloc(&m->selfK, c.dec_layers * B * Tm * d));
+  W_TRY(dalloc(&m->selfV, c.dec_layers * B * Tm * d));
+  W_TRY(dalloc(&m->partial, (size_t)B * m->nblk * kNP));
+  W_TRY(dalloc(&m->info, (size_t)B * (1 + m->nlang)));
+  W_TRY(dalloc(&m->nsp, (size_t)B));
+  W_TRY(dalloc(&m->d_logprob, (size_t)B));
+  W_TRY(dalloc(&m->state, (size_t)B));
+  W_TRY(dalloc(&m->tokens, B * Tm));
+  W_TRY(dalloc(&m->cur_tok, (size_t)B));
+  W_TRY(dalloc(&m->lang_out, (size_t)B));
+  W_TRY(dalloc(&m->d_ids, B * Tm));
+  m->cap = B;
+  m->enc_B = 0;
+  return EIOKU_OK;
+}
+
+int check_weights(const eioku_whisper* m) {
+  for (const auto& t : m->tensors) EIOKU_REQUIRE(t.set, "tensor %s has no weights", t.name.c_str());
+  return EIOKU_OK;
+}
+
+// one decoder position s for B lanes: embedding -> layers -> final LayerNorm into m->dh
+int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, int uniform) {
+  const auto& c = m->cfg;
+  const int d = c.d_model, ctx = c.max_source_positions, Tm = c.max_target_positions;
+  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, 0, toks, tstride, uniform, c.vocab, d, s, m->H(m->emb), m->F(m->dec_pos), m->dx);
+  EIOKU_LAUNCH_CHECK();
+  m->launches += 1;
+  for (int l = 0; l < c.dec_layers; ++l) {
+    const Layer& L = m->dec[l];
+    h16* sk = m->selfK + (size_t)l * m->cap * Tm * d;
+    h16* sv = m->selfV + (size_t)l * m->cap * Tm * d;
+    const h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
+    const h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
+    W_TRY(ln(m, m->dx, B, d, L.self.ln_g, L.self.ln_b, m->dh));
+    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.q), d, m->F(L.self.qb), B, d, d, m->dq, d)));
+    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.k), d, nullptr, B, d, d, sk + (size_t)s * d, (long long)Tm * d)));
+    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.v), d, m->F(L.self.vb), B, d, d, sv + (size_t)s * d, (long long)Tm * d)));
+    W_TRY((attn<1>(m, m->dq, d, d, sk, sv, (long long)Tm * d, d, 1, s + 1, B, m->da, d, d)));
+    W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.self.o), d, m->F(L.self.ob), B, d, d, m->dx, d)));
+    W_TRY(ln(m, m->dx, B, d, L.cross.ln_g, L.cross.ln_b, m->dh));
+    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.cross.q), d, m->F(L.cross.qb), B, d, d, m->dq, d)));
+    W_TRY((attn<1>(m, m->dq, d, d, ck, cv, (long long)ctx * d, d, 1, ctx, B, m->da, d, d)));
+    W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.cross.o), d, m->F(L.cross.ob), B, d, d, m->dx, d)));
+    W_TRY(ln(m, m->dx, B, d, L.ln_g, L.ln_b, m->dh));
+    W_TRY((gemm<1, EPI_GELU_F16>(m, m->dh, d, m->H(L.fc1), d, m->F(L.fc1b), B, c.dec_ffn, d, m->dmid, c.dec_ffn)));
+    W_TRY((gemm<1, EPI_RESID>(m, m->dmid, c.dec_ffn, m->H(L.fc2), c.dec_ffn, m->F(L.fc2b), B, d, c.dec_ffn, m->dx, d)));
+  }
+  return ln(m, m->dx, B, d, m->dec_ln_g, m->dec_ln_b, m->dh);
+}
+
+int logits(eioku_whisper* m, int B, int rules, float* raw_out, long long raw_ld, bool info) {
+  hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, B, m->sel,
+                     m->flags, m->state, rules, m->partial, m->nblk, raw_out, raw_ld, nullptr, info ? m->info : nullptr, m->nlang);
+  EIOKU_LAUNCH_CHECK();
+  m->flops += 2.0 * B * m->cfg.vocab * m->cfg.d_model;
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper** out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(cfg && out, "NULL argument");
+  const eioku_whisper_cfg_t& c = *cfg;
+  EIOKU_REQUIRE(c.d_model > 0 && c.d_model % 64 == 0 && c.heads * 64 == c.d_model, "head_dim must be 64 (d_model %d / heads %d)",
+                c.d_model, c.heads);
+  EIOKU_REQUIRE(c.enc_ffn > 0 && c.dec_ffn > 0 && c.enc_ffn % 32 == 0 && c.dec_ffn % 32 == 0, "ffn sizes must be multiples of 32");
+  EIOKU_REQUIRE(c.n_mels > 0 && c.enc_layers > 0 && c.dec_layers > 0 && c.vocab > 0 && c.max_source_positions > 0 &&
+                    c.max_target_positions > 0, "bad config");
+  EIOKU_REQUIRE((size_t)4 * 2 * (c.max_source_positions + 64) * sizeof(float) <= 64 * 1024, "max_source_positions %d too large",
+                c.max_source_positions);
+  EIOKU_REQUIRE(c.eot >= 0 && c.eot < c.vocab && c.timestamp_begin > c.eot && c.timestamp_begin <= c.vocab &&
+                    c.no_timestamps >= 0 && c.no_timestamps < c.vocab && c.no_speech >= 0 && c.no_speech < c.vocab,
+                "special token ids outside the vocabulary");
+  EIOKU_REQUIRE(c.n_suppress >= 0 && c.n_begin_suppress >= 0 && c.n_langs >= 0 && c.n_langs < 16000 && c.mel_filters, "bad lists");
+  auto* m = new eioku_whisper();
+  m->cfg = c;
+  m->cfg.suppress = m->cfg.begin_suppress = m->cfg.lang_ids = nullptr;
+  m->cfg.mel_filters = nullptr;
+  m->sel = SelCfg{c.vocab, c.eot, c.no_timestamps, c.timestamp_begin, c.no_speech, c.max_initial_timestamp_index};
+  m->nlang = c.n_langs;
+  m->nblk = (c.vocab + 63) / 64;
+  m->k1pad = round_up(3 * c.n_mels, 32);
+  const int d = c.d_model;
+  auto add = [&](const std::string& n, int rows, int cols, int kind, int cin = 0) {
+    Tensor t;
+    t.name = n, t.rows = rows, t.cols = cols, t.kind = kind, t.cin = cin;
+    t.ldk = kind == T_CONV ? round_up(cols, 32) : cols;
+    m->tensors.push_back(t);
+    return (int)m->tensors.size() - 1;
+  };
+  auto add_attn = [&](const std::string& p, const std::string& lnp) {
+    Attn a;
+    a.q = add(p + "q_proj.weight", d, d, T_F16);
+    a.qb = add(p + "q_proj.bias", d, 1, T_F32);
+    a.k = add(p + "k_proj.weight", d, d, T_F16);
+    a.v = add(p + "v_proj.weight", d, d, T_F16);
+    a.vb = add(p + "v_proj.bias", d, 1, T_F32);
+    a.o = add(p + "out_proj.weight", d, d, T_F16);
+    a.ob = add(p + "out_proj.bias", d, 1, T_F32);
+    a.ln_g = add(lnp + ".weight", d, 1, T_F32);
+    a.ln_b = add(lnp + ".bias", d, 1, T_F32);
+    return a;
+  };
+  m->conv1 = add("model.encoder.conv1.weight", d, c.n_mels * 3, T_CONV, c.n_mels);
+  m->conv1b = add("model.encoder.conv1.bias", d, 1, T_F32);
+  m->conv2 = add("model.encoder.conv2.weight", d, d * 3, T_CONV, d);
+  m->conv2b = add("model.encoder.conv2.bias", d, 1, T_F32);
+  m->enc_pos = add("model.encoder.embed_positions.weight", c.max_source_positions, d, T_F32);
+  for (int l = 0; l < c.enc_layers + c.dec_layers; ++l) {
+    const bool is_dec = l >= c.enc_layers;
+    const std::string p = std::string("model.") + (is_dec ? "decoder" : "encoder") + ".layers." +
+                          std::to_string(is_dec ? l - c.enc_layers : l) + ".";
+    const int ffn = is_dec ? c.dec_ffn : c.enc_ffn;
+    Layer L{};
+    L.self = add_attn(p + "self_attn.", p + "self_attn_layer_norm");
+    if (is_dec) L.cross = add_attn(p + "encoder_attn.", p + "encoder_attn_layer_norm");
+    L.fc1 = add(p + "fc1.weight", ffn, d, T_F16);
+    L.fc1b = add(p + "fc1.bias", ffn, 1, T_F32);
+    L.fc2 = add(p + "fc2.weight", d, ffn, T_F16);
+    L.fc2b = add(p + "fc2.bias", d, 1, T_F32);
+    L.ln_g = add(p + "final_layer_norm.weight", d, 1, T_F32);
+    L.ln_b = add(p + "final_layer_norm.bias", d, 1, T_F32);
+    (is_dec ? m->dec : m->enc).push_back(L);
+    if (l == c.enc_layers - 1) {
+      m->enc_ln_g = add("model.encoder.layer_norm.weight", d, 1, T_F32);
+      m->enc_ln_b = add("model.encoder.layer_norm.bias", d, 1, T_F32);
+      m->emb = add("model.decoder.embed_tokens.weight", c.vocab, d, T_F16);
+      m->dec_pos = add("model.decoder.embed_positions.weight", c.max_target_positions, d, T_F32);
+    }
+  }
+  m->dec_ln_g = add("model.decoder.layer_norm.weight", d, 1, T_F32);
+  m->dec_ln_b = add("model.decoder.layer_norm.bias", d, 1, T_F32);
+  auto fail = [&](int rc) {
+    eioku_whisper_destroy(m);
+    return rc;
+  };
+  for (auto& t : m->tensors) {
+    const size_t bytes = (size_t)t.rows * t.ldk * (t.kind == T_F32 ? 4 : 2);
+    if (hipMalloc(&t.dev, bytes) != hipSuccess) {
+      set_error("hipMalloc failed for %s", t.name.c_str());
+      return fail(EIOKU_ENOMEM);
+    }
+  }
+  // constants: periodic Hann window, DFT twiddles, mel filterbank, per-id flags
+  std::vector<double> hann(kNfft), tc(kNfft), ts(kNfft);
+  const double two_pi = 6.283185307179586476925286766559;
+  for (int n = 0; n < kNfft; ++n) {
+    hann[n] = 0.5 - 0.5 * std::cos(two_pi * n / kNfft);
+    tc[n] = std::cos(two_pi * n / kNfft);
+    ts[n] = std::sin(two_pi * n / kNfft);
+  }
+  std::vector<uint16_t> flags(c.vocab, 0);
+  for (int i = 0; i < c.n_suppress; ++i)
+    if (c.suppress[i] >= 0 && c.suppress[i] < c.vocab) flags[c.suppress[i]] |= kFlagSuppress;
+  for (int i = 0; i < c.n_begin_suppress; ++i)
+    if (c.begin_suppress[i] >= 0 && c.begin_suppress[i] < c.vocab) flags[c.begin_suppress[i]] |= kFlagBegin;
+  for (int i = 0; i < c.n_langs; ++i) {
+    if (c.lang_ids[i] < 0 || c.lang_ids[i] >= c.vocab) {
+      set_error("language id %d outside the vocabulary", c.lang_ids[i]);
+      return fail(EIOKU_EINVAL);
+    }
+    flags[c.lang_ids[i]] |= (uint16_t)((i + 1) << 2);
+  }
+  if (dalloc(&m->hann, kNfft) || dalloc(&m->tw_cos, kNfft) || dalloc(&m->tw_sin, kNfft) ||
+      dalloc(&m->filt, (size_t)c.n_mels * kBins) || dalloc(&m->flags, (size_t)c.vocab) || dalloc(&m->lang_ids, (size_t)c.n_langs))
+    return fail(EIOKU_ENOMEM);
+  if (hipMemcpy(m->hann, hann.data(), kNfft * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(m->tw_cos, tc.data(), kNfft * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(m->tw_sin, ts.data(), kNfft * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(m->filt, c.mel_filters, (size_t)c.n_mels * kBins * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(m->flags, flags.data(), (size_t)c.vocab * 2, hipMemcpyHostToDevice) != hipSuccess ||
+      (c.n_langs && hipMemcpy(m->lang_ids, c.lang_ids, (size_t)c.n_langs * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+    set_error("hipMemcpy of the Whisper constants failed");
+    return fail(EIOKU_EHIP);
+  }
+  *out = m;
+  return EIOKU_OK;
+}
+
+void eioku_whisper_destroy(eioku_whisper* m) {
+  if (!m) return;
+  (void)hipDeviceSynchronize();
+  for (auto& t : m->tensors)
+    if (t.dev) (void)hipFree(t.dev);
+  void* bufs[] = {m->hann, m->tw_cos, m->tw_sin, m->filt, m->flags, m->lang_ids, m->samples, m->d_off, m->mel64, m->mel_mx, m->mel32,
+                  m->col1, m->h1, m->col2, m->eh, m->eq, m->ek, m->ev, m->ea, m->emid, m->enc_out, m->crossK, m->crossV, m->ex,
+                  m->dh, m->dq, m->da, m->dmid, m->selfK, m->selfV, m->dx, m->partial, m->info, m->nsp, m->d_logprob, m->state,
+                  m->tokens, m->cur_tok, m->lang_out, m->d_ids};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  delete m;
+}
+
+int eioku_whisper_num_tensors(const eioku_whisper* m) { return m ? (int)m->tensors.size() : 0; }
+
+int eioku_whisper_tensor_info(const eioku_whisper* m, int idx, char* name, size_t cap, int* rows, int* cols) {
+  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size(), "bad tensor index %d", idx);
+  const auto& t = m->tensors[idx];
+  if (name && cap) snprintf(name, cap, "%s", t.name.c_str());
+  if (rows) *rows = t.rows;
+  if (cols) *cols = t.cols;
+  return EIOKU_OK;
+}
+
+int eioku_whisper_set_tensor(eioku_whisper* m, int idx, const float* host, size_t numel) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size() && host, "bad argument");
+  auto& t = m->tensors[idx];
+  EIOKU_REQUIRE(numel == t.numel(), "%s: expected %zu elements, got %zu", t.name.c_str(), t.numel(), numel);
+  if (t.kind == T_F32) {
+    EIOKU_HIP_CHECK(hipMemcpy(t.dev, host, numel * sizeof(float), hipMemcpyHostToDevice));
+  } else {
+    float* stage = nullptr;
+    W_TRY(dalloc(&stage, numel));
+    hipError_t e = hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      if (t.kind == T_F16) {
+        hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage, numel, (h16*)t.dev);
+      } else {
+        const size_t n = (size_t)t.rows * t.ldk;
+        hipLaunchKernelGGL(k_cvt_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage, t.rows, t.cin, t.ldk, (h16*)t.dev);
+      }
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+    (void)hipFree(stage);
+    EIOKU_HIP_CHECK(e);
+  }
+  t.set = true;
+  return EIOKU_OK;
+}
+
+int eioku_whisper_set_audio(eioku_whisper* m, const float* samples, long long n) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && n >= 0 && (samples || n == 0), "bad argument");
+  W_TRY(dalloc(&m->samples, (size_t)n));
+  m->n_samples = n;
+  if (n) EIOKU_HIP_CHECK(hipMemcpy(m->samples, samples, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  return EIOKU_OK;
+}
+
+int eioku_whisper_logmel(eioku_whisper* m, const long long* offsets, int B, float* out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && offsets && B > 0 && B <= 64, "bad argument (1 <= B <= 64)");
+  EIOKU_REQUIRE(m->samples, "no audio: call eioku_whisper_set_audio first");
+  for (int b = 0; b < B; ++b) EIOKU_REQUIRE(offsets[b] >= 0, "negative window offset");
+  W_TRY(ensure_capacity(m, B));
+  const auto& c = m->cfg;
+  const int T = 2 * c.max_source_positions;
+  const long long per = (long long)c.n_mels * T, total = per * B;
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_off, offsets, (size_t)B * sizeof(long long), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_mel_frames, dim3(T, B), dim3(256), 0, 0, m->samples, m->n_samples, m->d_off, T, c.n_mels, m->hann, m->tw_cos,
+                     m->tw_sin, m->filt, m->mel64);
+  EIOKU_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_mel_max, dim3(B), dim3(256), 0, 0, m->mel64, per, m->mel_mx);
+  EIOKU_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_mel_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, m->mel64, per, m->mel_mx, total, m->mel32);
+  EIOKU_LAUNCH_CHECK();
+  if (out) EIOKU_HIP_CHECK(hipMemcpy(out, m->mel32, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+  else EIOKU_HIP_CHECK(hipDeviceSynchronize());
+  return EIOKU_OK;
+}
+
+int eioku_whisper_encode(eioku_whisper* m, const float* mel, int B) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && B > 0 && B <= 64, "bad argument (1 <= B <= 64)");
+  W_TRY(check_weights(m));
+  EIOKU_REQUIRE(mel || B <= m->cap, "no log-mel result for %d windows", B);
+  W_TRY(ensure_capacity(m, B));
+  const auto& c = m->cfg;
+  const int d = c.d_model, ctx = c.max_source_positions, T2 = 2 * ctx, M = B * ctx;
+  if (mel) EIOKU_HIP_CHECK(hipMemcpy(m->mel32, mel, (size_t)B * c.n_mels * T2 * sizeof(float), hipMemcpyHostToDevice));
+  m->flops = 0;
+  m->launches = 0;
+  m->enc_B = 0;
+  {
+    const size_t n1 = (size_t)B * T2 * m->k1pad, n2 = (size_t)M * 3 * d;
+    hipLaunchKernelGGL(k_im2col_mel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, 0, m->mel32, B, c.n_mels, T2, m->k1pad, m->col1);
+    EIOKU_LAUNCH_CHECK();
+    W_TRY((gemm<4, EPI_GELU_F16>(m, m->col1, m->k1pad, m->H(m->conv1), m->k1pad, m->F(m->conv1b), B * T2, d, m->k1pad, m->h1, d)));
+    hipLaunchKernelGGL(k_im2col_s2, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, 0, m->h1, B, d, T2, m->col2);
+    EIOKU_LAUNCH_CHECK();
+    W_TRY((gemm<4, EPI_GELU_POS>(m, m->col2, 3 * d, m->H(m->conv2), 3 * d, m->F(m->conv2b), M, d, 3 * d, m->ex, d, m->F(m->enc_pos), ctx)));
+  }
+  for (int l = 0; l < c.enc_layers; ++l) {
+    const Layer& L = m->enc[l];
+    W_TRY(ln(m, m->ex, M, d, L.self.ln_g, L.self.ln_b, m->eh));
+    W_TRY((gemm<4, EPI_F16>(m, m->eh, d, m->H(L.self.q), d, m->F(L.self.qb), M, d, d, m->eq, d)));
+    W_TRY((gemm<4, EPI_F16>(m, m->eh, d, m->H(L.self.k), d, nullptr, M, d, d, m->ek, d)));
+    W_TRY((gemm<4, EPI_F16>(m, m->eh, d, m->H(L.self.v), d, m->F(L.self.vb), M, d, d, m->ev, d)));
+    W_TRY((attn<2>(m, m->eq, (long long)ctx * d, d, m->ek, m->ev, (long long)ctx * d, d, ctx, ctx, B, m->ea, (long long)ctx * d, d)));
+    W_TRY((gemm<4, EPI_RESID>(m, m->ea, d, m->H(L.self.o), d, m->F(L.self.ob), M, d, d, m->ex, d)));
+    W_TRY(ln(m, m->ex, M, d, L.ln_g, L.ln_b, m->eh));
+    W_TRY((gemm<4, EPI_GELU_F16>(m, m->eh, d, m->H(L.fc1), d, m->F(L.fc1b), M, c.enc_ffn, d, m->emid, c.enc_ffn)));
+    W_TRY((gemm<4, EPI_RESID>(m, m->emid, c.enc_ffn, m->H(L.fc2), c.enc_ffn, m->F(L.fc2b), M, d, c.enc_ffn, m->ex, d)));
+  }
+  W_TRY(ln(m, m->ex, M, d, m->enc_ln_g, m->enc_ln_b, m->enc_out));
+  for (int l = 0; l < c.dec_layers; ++l) {  // cross-attention keys and values, once per window
+    const Layer& L = m->dec[l];
+    h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
+    h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
+    W_TRY((gemm<4, EPI_F16>(m, m->enc_out, d, m->H(L.cross.k), d, nullptr, M, d, d, ck, d)));
+    W_TRY((gemm<4, EPI_F16>(m, m->enc_out, d, m->H(L.cross.v), d, m->F(L.cross.vb), M, d, d, cv, d)));
+  }
+  EIOKU_HIP_CHECK(hipDeviceSynchronize());
+  m->enc_B = B;
+  return EIOKU_OK;
+}
+
+int eioku_whisper_encoder_output(eioku_whisper* m, void* out_f16, size_t numel) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && out_f16 && m->enc_B > 0, "no encoder result");
+  EIOKU_REQUIRE(numel == (size_t)m->enc_B * m->cfg.max_source_positions * m->cfg.d_model, "expected %zu elements",
+                (size_t)m->enc_B * m->cfg.max_source_positions * m->cfg.d_model);
+  EIOKU_HIP_CHECK(hipMemcpy(out_f16, m->enc_out, numel * sizeof(h16), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
+}
+
+int eioku_whisper_decode(eioku_whisper* m, const int32_t* prompt, int prompt_len, int B, int max_new, int sync_every,
+                         int32_t* tokens_out, int32_t* n_out, float* sum_logprob, float* no_speech_prob, int32_t* lang_out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && prompt && prompt_len >= 1 && max_new >= 0, "bad argument");
+  EIOKU_REQUIRE(B > 0 && B == m->enc_B, "decode of %d lanes needs an encode of the same %d windows first", B, m->enc_B);
+  EIOKU_REQUIRE(prompt_len + max_new <= m->cfg.max_target_positions, "prompt %d + %d new tokens exceed max_target_positions %d",
+                prompt_len, max_new, m->cfg.max_target_positions);
+  EIOKU_REQUIRE(max_new == 0 || (tokens_out && n_out && sum_logprob), "NULL output");
+  for (int i = 0; i < prompt_len; ++i) EIOKU_REQUIRE(prompt[i] >= 0 && prompt[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompt[i]);
+  if (sync_every < 1) sync_every = 1;
+  const int Tm = m->cfg.max_target_positions;
+  m->flops = 0;
+  m->launches = 0;
+  m->steps = 0;
+  std::vector<LaneState> st(B, LaneState{0, -1, -1, -1, 0, 0.f});
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
+  const int last_step = max_new > 0 ? prompt_len - 1 + max_new - 1 : 0;
+  for (int s = 0; s <= last_step; ++s) {
+    const bool forced = s < prompt_len;  // the input token is a prompt token
+    W_TRY(decoder_step(m, B, s, forced ? nullptr : m->cur_tok, 1, forced ? prompt[s] : 0));
+    m->steps += 1;
+    const int idx = s - (prompt_len - 1);  // index of the token this step samples
+    const bool sample = idx >= 0 && max_new > 0, info = s == 0;
+    if (!sample && !info) continue;
+    W_TRY(logits(m, B, sample ? 1 : 0, nullptr, 0, info));
+    hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, sample ? 1 : 0, sample ? idx : 0,
+                       info ? 1 : 0, m->info, m->nlang, m->lang_ids, m->tokens, Tm, m->cur_tok, m->nsp, m->lang_out, (float*)nullptr);
+    EIOKU_LAUNCH_CHECK();
+    m->launches += 1;
+    if (sample && (idx + 1) % sync_every == 0 && s < last_step) {  // read the lane states back: stop once every lane is done
+      EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)B * sizeof(LaneState), hipMemcpyDeviceToHost));
+      bool all = true;
+      for (int b = 0; b < B; ++b) all = all && st[b].done;
+      if (all) {  // the rest of every lane is EOT
+        std::vector<int> row(Tm, m->cfg.eot);
+        for (int b = 0; b < B; ++b)
+          EIOKU_HIP_CHECK(hipMemcpy(m->tokens + (size_t)b * Tm + idx + 1, row.data(), (size_t)(max_new - idx - 1) * sizeof(int),
+                                    hipMemcpyHostToDevice));
+        break;
+      }
+    }
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)B * sizeof(LaneState), hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b) {
+    if (max_new > 0) {
+      EIOKU_HIP_CHECK(hipMemcpy(tokens_out + (size_t)b * max_new, m->tokens + (size_t)b * Tm, (size_t)max_new * sizeof(int),
+                                hipMemcpyDeviceToHost));
+      n_out[b] = st[b].n;
+      sum_logprob[b] = st[b].sum;
+    }
+  }
+  if (no_speech_prob) EIOKU_HIP_CHECK(hipMemcpy(no_speech_prob, m->nsp, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
+  if (lang_out) EIOKU_HIP_CHECK(hipMemcpy(lang_out, m->lang_out, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
+}
+
+int eioku_whisper_forced_logits(eioku_whisper* m, const int32_t* ids, int T, int B, float* out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && ids && out && T >= 1 && T <= m->cfg.max_target_positions, "bad argument");
+  EIOKU_REQUIRE(B > 0 && B == m->enc_B, "forced_logits of %d lanes needs an encode of the same %d windows first", B, m->enc_B);
+  const int V = m->cfg.vocab;
+  for (size_t i = 0; i < (size_t)B * T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < V, "id %d outside the vocabulary", ids[i]);
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, ids, (size_t)B * T * sizeof(int), hipMemcpyHostToDevice));
+  float* d_out = nullptr;
+  W_TRY(dalloc(&d_out, (size_t)B * T * V));
+  std::vector<LaneState> st(B, LaneState{0, -1, -1, -1, 0, 0.f});
+  int rc = EIOKU_OK;
+  if (hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice) != hipSuccess) rc = EIOKU_EHIP;
+  for (int s = 0; s < T && rc == EIOKU_OK; ++s) {
+    rc = decoder_step(m, B, s, m->d_ids + s, T, 0);
+    if (rc == EIOKU_OK) rc = logits(m, B, 0, d_out + (size_t)s * V, (long long)T * V, false);
+  }
+  if (rc == EIOKU_OK && hipMemcpy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("hipMemcpy of the logits failed: %s", hipGetErrorString(hipGetLastError()));
+    rc = EIOKU_EHIP;
+  }
+  (void)hipFree(d_out);
+  return rc;
+}
+
+int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const int32_t* prefix, int prefix_cap,
+                         const int32_t* prefix_len, int32_t* token_out, float* logprob_out, float* masked_out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && logits_in && B > 0 && B <= 64 && prefix_len && token_out && logprob_out && prefix_cap >= 0, "bad argument");
+  W_TRY(ensure_capacity(m, B));
+  const int V = m->cfg.vocab;
+  std::vector<LaneState> st(B);
+  for (int b = 0; b < B; ++b) {
+    const int n = prefix_len[b];
+    EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
+    LaneState s{n, -1, -1, -1, 0, 0.f};
+    for (int i = 0; i < n; ++i) {
+      const int t = prefix[(size_t)b * prefix_cap + i];
+      s.penult = s.last;
+      s.last = t;
+      if (t >= m->cfg.timestamp_begin) s.last_ts = t;
+    }
+    st[b] = s;
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
+  float *d_in = nullptr, *d_msk = nullptr;
+  W_TRY(dalloc(&d_in, (size_t)B * V));
+  int rc = masked_out ? dalloc(&d_msk, (size_t)B * V) : EIOKU_OK;
+  hipError_t e = rc == EIOKU_OK ? hipMemcpy(d_in, logits_in, (size_t)B * V * sizeof(float), hipMemcpyHostToDevice) : hipSuccess;
+  if (rc == EIOKU_OK && e == hipSuccess) {
+    hipLaunchKernelGGL((k_logits<true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in, B, m->sel,
+                       m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, d_msk, (float*)nullptr, m->nlang);
+    hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, 0, 0, m->info, m->nlang,
+                       m->lang_ids, (int*)nullptr, 0, m->cur_tok, m->nsp, m->lang_out, m->d_logprob);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(token_out, m->cur_tok, (size_t)B * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(logprob_out, m->d_logprob, (size_t)B * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && masked_out) e = hipMemcpy(masked_out, d_msk, (size_t)B * V * sizeof(float), hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d_in);
+  if (d_msk) (void)hipFree(d_msk);
+  W_TRY(rc);
+  EIOKU_HIP_CHECK(e);
+  return EIOKU_OK;
+}
+
+int eioku_whisper_last_flops(const eioku_whisper* m, double* flops) {
+  EIOKU_REQUIRE(m && flops, "NULL argument");
+  *flops = m->flops;
+  return EIOKU_OK;
+}
+
+int eioku_whisper_last_launches(const eioku_whisper* m, int* launches, int* steps) {
+  EIOKU_REQUIRE(m && launches && steps, "NULL argument");
+  *launches = m->launches;
+  *steps = m->steps;
+  return EIOKU_OK;
+}
+
+}  // extern "C"

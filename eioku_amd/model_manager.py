@@ -155,14 +155,17 @@ class ModelManager:
 
     def __init__(self, cache_dir: str = "/models", *, frame_source=None, detector_factory=None, batch_size: int = 64,
                  random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
-                 ocr_reader_factory=None):
+                 ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
         weights of the right shapes when no checkpoint can exist (offline benchmarks);
         ``face_embedder_factory(cache_dir, model_name) -> embedder`` with ``embed(frames, boxes)`` and
         ``cluster(embeddings, eps, min_samples)`` (``cluster_faces``); ``ocr_reader_factory(cache_dir) -> reader`` with
-        ``readtext_batch(frames) -> per frame [(box, text, confidence)]``."""
+        ``readtext_batch(frames) -> per frame [(box, text, confidence)]``.  ``gpu_transcription=True`` enables
+        ``transcribe_video`` on the HIP path (Whisper, ``eioku_amd.transcribe``); ``audio_source(path) -> (float32 mono
+        samples, sample_rate)`` and ``transcriber_factory(cache_dir, model_name) -> object with transcribe(samples, language,
+        window_mode=, batch_windows=)`` are its seams."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -172,6 +175,9 @@ class ModelManager:
         self._place_classifier_factory = place_classifier_factory  # (cache_dir) -> object with classify(frames, top_k), labels
         self._face_embedder_factory = face_embedder_factory
         self._ocr_reader_factory = ocr_reader_factory
+        self._gpu_transcription = bool(gpu_transcription)
+        self._audio_source = audio_source
+        self._transcriber_factory = transcriber_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -221,7 +227,33 @@ class ModelManager:
         raise NotImplementedError(f"verify_model {OUT_OF_SCOPE}")
 
     async def transcribe_video(self, video_path: str, config: dict) -> dict:
-        raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")
+        """Whisper on the HIP path when the manager was built with ``gpu_transcription=True`` (reference: :406-467, which
+        calls faster-whisper on the CPU); otherwise refused as before.  Result: ``{"segments": [{start_ms, end_ms, text,
+        language, confidence: None, words: None}]}``.  Greedy decoding; the deviations from the reference's call are listed
+        in INTEGRATION.md §3."""
+        if not self._gpu_transcription:
+            raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")
+        try:
+            from .transcribe import WhisperTranscriber, transcribe_video
+
+            config = config or {}
+            model_name = config.get("model_name", "base")
+            logger.info(f"Transcription: {video_path} with whisper {model_name} (GPU: {self.gpu_available})")
+            if self._transcriber_factory is not None:
+                transcriber = self._transcriber_factory(self.cache_dir, model_name)
+            else:
+                transcriber = WhisperTranscriber.from_cache(self.cache_dir, model_name, seed=self._seed)
+            try:
+                result = transcribe_video(video_path, config, transcriber=transcriber, audio_source=self._audio_source)
+            finally:
+                close = getattr(transcriber, "close", None)
+                if close:
+                    close()
+            logger.info(f"✅ Transcription complete: {len(result['segments'])} segments")
+            return result
+        except Exception as e:
+            logger.error(f"Transcription failed: {e}", exc_info=True)
+            raise
 
     async def extract_ocr(self, video_path: str, config: dict) -> dict:
         """On-screen text with EasyOCR's CRAFT + english_g2 on the HIP path (reference: :469-558): every

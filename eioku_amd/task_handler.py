@@ -13,6 +13,8 @@ storage go through two small hooks carried in the arq ``ctx`` dict.
                         mark_cancelled (task_id[, error])            (ref :68-78, 422-425, 437-469)
     ctx["artifact_sink"] optional callable(list[ArtifactEnvelope])   (ref :344-404)
     ctx["gpu_ocr"]      true: run ``ocr`` on the HIP path (ModelManager.extract_ocr); otherwise it is refused as before
+    ctx["gpu_transcription"]  true: run ``transcription`` on the HIP path (ModelManager(gpu_transcription=True)
+                        .transcribe_video, one "transcript.segment" envelope per segment); otherwise refused as before
 """
 
 from __future__ import annotations
@@ -30,10 +32,10 @@ logger = logging.getLogger(__name__)
 TASK_TO_ARTIFACT_TYPE = {"object_detection": "object.detection", "face_detection": "face.detection",
                          "scene_detection": "scene", "segment_embedding": "segment.embedding",
                          "place_detection": "place.classification", "ocr": "ocr.text", "topic_extraction": "topic",
-                         "thumbnail_generation": "scene.thumbnail"}
+                         "thumbnail_generation": "scene.thumbnail", "transcription": "transcript.segment"}
 TASK_TO_RESULT_KEY = {"object_detection": "detections", "face_detection": "detections", "scene_detection": "scenes",
                       "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections",
-                      "topic_extraction": "topics", "thumbnail_generation": "thumbnails"}
+                      "topic_extraction": "topics", "thumbnail_generation": "thumbnails", "transcription": "segments"}
 # the reference's seven (task_handler.py:92-127) + the one its semantic-search design adds after transcription
 # (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them; and the topic stage its
 # worker configs schedule (config/*.json "topic_extraction"; tasks.md 12.1-12.3): KeyBERT keywords of the segments; and the
@@ -155,7 +157,10 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
 
         model_cache_dir = os.getenv("MODEL_CACHE_DIR", "/models")
         factory = ctx.get("model_manager_factory", ModelManager)
-        model_manager = factory(cache_dir=model_cache_dir)
+        if task_type == "transcription" and ctx.get("gpu_transcription"):  # opt-in: the manager is built with the HIP path on
+            model_manager = factory(cache_dir=model_cache_dir, gpu_transcription=True)
+        else:
+            model_manager = factory(cache_dir=model_cache_dir)
         if task_type not in KNOWN_TASK_TYPES:
             raise ValueError(f"Unknown task type: {task_type}")
         logger.info(f"🎬 Starting {task_type} inference on {video_path}")
@@ -169,6 +174,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             result = await model_manager.classify_places(video_path, config or {})
         elif task_type == "ocr" and ctx.get("gpu_ocr"):  # opt-in: without it ocr stays with the reference worker
             result = await model_manager.extract_ocr(video_path, config or {})
+        elif task_type == "transcription" and ctx.get("gpu_transcription"):
+            result = await model_manager.transcribe_video(video_path, config or {})
         elif task_type == "thumbnail_generation":  # one "scene.thumbnail" envelope per scene, spanning the scene
             result = await model_manager.generate_thumbnails(video_path, config or {})
         elif task_type in ("segment_embedding", "topic_extraction"):

@@ -1,0 +1,493 @@
+"""Transcription on the HIP path: Whisper log-mel (K19) and greedy decode with timestamp rules (K20).
+
+The reference calls ``faster_whisper.WhisperModel.transcribe`` (``model_manager.py:406-467``), which has no ROCm backend.
+This module keeps its result dict and replaces the arithmetic: the audio goes up once, ``csrc/whisper.hip`` computes the
+log-mel windows, the encoder, and the decoder steps with token selection on the device; the host only cuts the token
+lists into segments (Whisper's seek rule) and turns ids into text (byte-level BPE from ``vocab.json``).
+
+Deviations from the reference's call are listed in INTEGRATION.md §3: greedy instead of ``beam_size=5``, no temperature
+fallback, no compression-ratio check, no conditioning on previous text, ``vad_filter`` accepted but not applied, integer
+millisecond times.  There is no CPU fallback: without the library or a gfx950 device every compute call raises.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import json
+import logging
+import math
+import struct
+import wave
+from pathlib import Path
+
+import numpy as np
+
+logger = logging.getLogger(__name__)
+
+SAMPLE_RATE = 16000
+HOP = 160                 # samples per mel frame (10 ms)
+N_BINS = 201
+MS_PER_FRAME = 10
+MS_PER_TIMESTAMP = 20     # one timestamp id = two mel frames
+NO_SPEECH_THRESHOLD = 0.6
+LOGPROB_THRESHOLD = -1.0
+
+
+# ---- audio input ----------------------------------------------------------------------------------------------------------
+def read_wav(path: str | Path) -> tuple[np.ndarray, int]:
+    """PCM16 WAV -> (float32 mono samples in [-1, 1], sample rate); stereo is downmixed by mean."""
+    with wave.open(str(path), "rb") as w:
+        if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+            raise ValueError(f"{path}: only 16-bit PCM WAV is read (sample width {w.getsampwidth()}, {w.getcomptype()})")
+        channels, rate = w.getnchannels(), w.getframerate()
+        data = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+    samples = data.astype(np.float32) / 32768.0
+    if channels > 1:
+        samples = samples.reshape(-1, channels).mean(axis=1, dtype=np.float32)
+    return np.ascontiguousarray(samples, dtype=np.float32), rate
+
+
+def default_audio_source(path: str | Path) -> tuple[np.ndarray, int]:
+    """``path`` itself when it is a ``.wav`` / ``.npy`` (16 kHz samples), otherwise the sibling ``<stem>.wav``.  Audio
+    decoding (ffmpeg) is outside this path, as video decoding is."""
+    p = Path(path)
+    if p.suffix.lower() not in (".wav", ".npy"):
+        p = p.with_suffix(".wav")
+    if not p.exists():
+        raise FileNotFoundError(f"no audio for {path}: {p} does not exist (audio decoding is not part of the HIP path)")
+    if p.suffix.lower() == ".npy":
+        samples = np.load(p)
+        if samples.ndim == 2:
+            samples = samples.mean(axis=1 if samples.shape[1] <= 8 else 0)
+        return np.ascontiguousarray(samples, dtype=np.float32), SAMPLE_RATE
+    return read_wav(p)
+
+
+def check_rate(rate: int) -> None:
+    if int(rate) != SAMPLE_RATE:
+        raise ValueError(f"audio is {rate} Hz: Whisper needs {SAMPLE_RATE} Hz and resampling is not built")
+
+
+# ---- mel filterbank (host, float64) ---------------------------------------------------------------------------------------
+def mel_filter_bank(n_mels: int, sr: int = SAMPLE_RATE) -> np.ndarray:
+    """Slaney-scale, Slaney-normalised triangular filters [n_mels][201] in float64 (``WhisperFeatureExtractor``'s
+    ``mel_filter_bank(norm="slaney", mel_scale="slaney")``, whisper's ``mel_filters.npz``)."""
+    f_sp, min_log_hz = 200.0 / 3.0, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, math.log(6.4) / 27.0
+    mel_max = min_log_mel + math.log((sr / 2.0) / min_log_hz) / logstep if sr / 2.0 >= min_log_hz else (sr / 2.0) / f_sp
+    mels = np.linspace(0.0, mel_max, n_mels + 2)
+    hz = np.where(mels >= min_log_mel, min_log_hz * np.exp(logstep * (mels - min_log_mel)), f_sp * mels)
+    freqs = np.linspace(0.0, sr / 2.0, N_BINS)
+    ramps = hz[:, None] - freqs[None, :]
+    fdiff = np.diff(hz)
+    w = np.maximum(0.0, np.minimum(-ramps[:-2] / fdiff[:-1, None], ramps[2:] / fdiff[1:, None]))
+    return np.ascontiguousarray(w * (2.0 / (hz[2:] - hz[:-2]))[:, None], dtype=np.float64)
+
+
+# ---- token -> text ----------------------------------------------------------------------------------------------------------
+def _gpt2_byte_table() -> dict[str, int]:
+    """GPT-2's printable stand-ins for the 256 byte values, inverted (character -> byte)."""
+    keep = list(range(ord("!"), ord("~") + 1)) + list(range(0xA1, 0xAC + 1)) + list(range(0xAE, 0xFF + 1))
+    chars, n = keep[:], 0
+    for b in range(256):
+        if b not in keep:
+            keep.append(b)
+            chars.append(256 + n)
+            n += 1
+    return {chr(c): b for b, c in zip(keep, chars)}
+
+
+class ByteDecoder:
+    """Byte-level BPE decode: ids -> vocabulary strings -> bytes (GPT-2 table) -> utf-8 with ``errors="replace"``."""
+
+    def __init__(self, vocab: dict[str, int]):
+        self._tokens = {int(i): s for s, i in vocab.items()}
+        self._bytes = _gpt2_byte_table()
+
+    def decode(self, ids) -> str:
+        raw = bytearray()
+        for i in ids:
+            s = self._tokens.get(int(i))
+            if s is None:
+                continue  # special tokens are not in vocab.json
+            for ch in s:
+                b = self._bytes.get(ch)
+                if b is None:
+                    raw.extend(ch.encode("utf-8"))
+                else:
+                    raw.append(b)
+        return raw.decode("utf-8", errors="replace")
+
+
+# ---- segment cutting and the seek rule ------------------------------------------------------------------------------------
+def cut_window(tokens, eot: int, timestamp_begin: int, window_start_ms: int, window_frames: int):
+    """Whisper's segment and seek rule for one window.  ``tokens``: the sampled ids (anything from the first EOT on is
+    dropped).  Returns (``[(start_ms, end_ms, text_ids)]``, frames to advance).
+
+    Segments are cut at consecutive timestamp pairs.  When the window ends on a single unpaired timestamp, everything up
+    to it is one more segment and seek advances by the whole window; otherwise seek advances to the last pair's timestamp.
+    With no pair at all there is one segment up to the last timestamp, or up to the window's end."""
+    toks = []
+    for t in tokens:
+        if int(t) == eot:
+            break
+        toks.append(int(t))
+    is_ts = [t >= timestamp_begin for t in toks]
+    single_ending = len(toks) >= 2 and is_ts[-1] and not is_ts[-2]  # Whisper's test: the last two flags are [False, True]
+    cuts = [i + 1 for i in range(len(toks) - 1) if is_ts[i] and is_ts[i + 1]]
+    segments = []
+
+    def ms(tok):
+        return window_start_ms + MS_PER_TIMESTAMP * (tok - timestamp_begin)
+
+    if cuts:
+        if single_ending:
+            cuts.append(len(toks))
+        last = 0
+        for cut in cuts:
+            piece = toks[last:cut]
+            segments.append((ms(piece[0]), ms(piece[-1]), [t for t in piece if t < eot]))
+            last = cut
+        if single_ending:
+            advance = window_frames
+        else:
+            advance = 2 * (toks[last - 1] - timestamp_begin)
+    else:
+        end_ms = window_start_ms + MS_PER_FRAME * window_frames
+        stamps = [t for t in toks if t >= timestamp_begin]
+        if stamps and stamps[-1] != timestamp_begin:
+            end_ms = ms(stamps[-1])
+        segments.append((window_start_ms, end_ms, [t for t in toks if t < eot]))
+        advance = window_frames
+    return segments, advance
+
+
+def skip_window(no_speech_prob: float, sum_logprob: float, n_text_tokens: int) -> bool:
+    """The no-speech rule: skip when ``no_speech_prob > 0.6`` and the average log-probability is ``< -1.0`` (the average
+    runs over the sampled tokens and the closing EOT, as in Whisper)."""
+    return no_speech_prob > NO_SPEECH_THRESHOLD and sum_logprob / (n_text_tokens + 1) < LOGPROB_THRESHOLD
+
+
+# ---- checkpoint files -----------------------------------------------------------------------------------------------------
+_ST_DTYPES = {"F32": np.float32, "F16": np.float16, "F64": np.float64}
+
+
+def read_safetensors(path: str | Path) -> dict[str, np.ndarray]:
+    """Minimal safetensors reader (8-byte header length, JSON header, raw little-endian data); fp32 arrays out."""
+    buf = Path(path).read_bytes()
+    (hlen,) = struct.unpack("<Q", buf[:8])
+    header = json.loads(buf[8:8 + hlen])
+    out = {}
+    for name, meta in header.items():
+        if name == "__metadata__":
+            continue
+        a, b = meta["data_offsets"]
+        raw = buf[8 + hlen + a:8 + hlen + b]
+        if meta["dtype"] == "BF16":
+            arr = (np.frombuffer(raw, dtype="<u2").astype(np.uint32) << 16).view(np.float32)
+        elif meta["dtype"] in _ST_DTYPES:
+            arr = np.frombuffer(raw, dtype=_ST_DTYPES[meta["dtype"]]).astype(np.float32)
+        else:
+            raise ValueError(f"{path}: tensor {name} has unsupported dtype {meta['dtype']}")
+        out[name] = arr.reshape(meta["shape"])
+    return out
+
+
+def whisper_dims(config: dict, generation_config: dict) -> dict:
+    """The dimensions and special ids the library needs, from ``config.json`` and ``generation_config.json``."""
+    gen = generation_config
+    d, heads = int(config["d_model"]), int(config["encoder_attention_heads"])
+    if int(config.get("decoder_attention_heads", heads)) != heads:
+        raise ValueError("encoder and decoder head counts differ")
+    lang_to_id = gen.get("lang_to_id") or {}
+    langs = sorted(lang_to_id.items(), key=lambda kv: kv[1])
+    no_ts = int(gen["no_timestamps_token_id"])
+    task_to_id = gen.get("task_to_id") or {}
+    return {
+        "n_mels": int(config.get("num_mel_bins", 80)), "d_model": d, "heads": heads,
+        "enc_layers": int(config["encoder_layers"]), "dec_layers": int(config["decoder_layers"]),
+        "enc_ffn": int(config["encoder_ffn_dim"]), "dec_ffn": int(config["decoder_ffn_dim"]),
+        "vocab": int(config["vocab_size"]), "max_source_positions": int(config["max_source_positions"]),
+        "max_target_positions": int(config["max_target_positions"]),
+        "sot": int(gen.get("decoder_start_token_id", config.get("decoder_start_token_id"))),
+        "eot": int(gen.get("eos_token_id", config.get("eos_token_id"))),
+        "transcribe": int(task_to_id["transcribe"]) if "transcribe" in task_to_id else None,
+        "no_timestamps": no_ts, "timestamp_begin": no_ts + 1,
+        # <|nospeech|> sits right before <|notimestamps|> in every Whisper vocabulary
+        "no_speech": int(gen.get("no_speech_token_id", no_ts - 1)),
+        "max_initial_timestamp_index": int(gen.get("max_initial_timestamp_index", 50)),
+        "suppress": [int(t) for t in gen.get("suppress_tokens") or []],
+        "begin_suppress": [int(t) for t in gen.get("begin_suppress_tokens") or []],
+        "lang_ids": [int(i) for _, i in langs],
+        "lang_codes": [k.strip("<|>") for k, _ in langs],
+    }
+
+
+def seeded_weights(dims: dict, seed: int):
+    """Random weights for the benchmark (never a substitute for a checkpoint): name, shape -> fp32 array."""
+    rng = np.random.default_rng(seed)
+
+    def make(name: str, rows: int, cols: int) -> np.ndarray:
+        if name.endswith("layer_norm.weight"):
+            return np.ones(rows * cols, dtype=np.float32)
+        if name.endswith(".bias"):
+            return np.zeros(rows * cols, dtype=np.float32)
+        std = 0.1 if "embed" in name else math.sqrt(2.0 / cols)
+        return (rng.standard_normal(rows * cols, dtype=np.float32) * np.float32(std)).astype(np.float32)
+
+    return make
+
+
+# ---- the device model -----------------------------------------------------------------------------------------------------
+class WhisperTranscriber:
+    """One Whisper checkpoint on the device: log-mel, encoder, greedy decoder, and the host loop around them.
+
+    ``dims``: the dict of :func:`whisper_dims`.  ``weights``: ``{HF tensor name: array}`` or a callable
+    ``(name, rows, cols) -> array``.  ``vocab``: ``vocab.json`` as a dict (may be empty: ids then decode to "")."""
+
+    def __init__(self, dims: dict, weights, vocab: dict | None = None, *, sync_every: int = 8):
+        from . import _lib
+
+        self._lib_mod = _lib
+        self.lib = _lib.load()
+        _lib.init()
+        self.dims = dict(dims)
+        self.sync_every = int(sync_every)
+        self.decoder = ByteDecoder(vocab or {})
+        d = self.dims
+        self._keep = [np.asarray(d["suppress"], dtype=np.int32), np.asarray(d["begin_suppress"], dtype=np.int32),
+                      np.asarray(d["lang_ids"], dtype=np.int32), mel_filter_bank(d["n_mels"])]
+        cfg = _lib.WhisperCfg()
+        for k in ("n_mels", "d_model", "heads", "enc_layers", "dec_layers", "enc_ffn", "dec_ffn", "vocab",
+                  "max_source_positions", "max_target_positions", "eot", "no_timestamps", "timestamp_begin", "no_speech"):
+            setattr(cfg, k, int(d[k]))
+        mi = d.get("max_initial_timestamp_index")
+        cfg.max_initial_timestamp_index = -1 if mi is None else int(mi)
+        cfg.n_suppress, cfg.n_begin_suppress, cfg.n_langs = (len(a) for a in self._keep[:3])
+        cfg.suppress, cfg.begin_suppress, cfg.lang_ids, cfg.mel_filters = (a.ctypes.data for a in self._keep)
+        handle = C.c_void_p()
+        _lib.check(self.lib.eioku_whisper_create(C.byref(cfg), C.byref(handle)), "eioku_whisper_create")
+        self._h = handle
+        self.window_frames = 2 * d["max_source_positions"]
+        self._load(weights)
+
+    def _load(self, weights) -> None:
+        lib, check = self.lib, self._lib_mod.check
+        name = C.create_string_buffer(256)
+        rows, cols = C.c_int(0), C.c_int(0)
+        for i in range(lib.eioku_whisper_num_tensors(self._h)):
+            check(lib.eioku_whisper_tensor_info(self._h, i, name, 256, C.byref(rows), C.byref(cols)), "eioku_whisper_tensor_info")
+            n = name.value.decode()
+            if callable(weights):
+                arr = weights(n, rows.value, cols.value)
+            elif n in weights:
+                arr = weights[n]
+            else:
+                raise KeyError(f"checkpoint has no tensor {n}")
+            arr = np.ascontiguousarray(np.asarray(arr, dtype=np.float32)).reshape(-1)
+            if arr.size != rows.value * cols.value:
+                raise ValueError(f"{n}: expected {rows.value * cols.value} elements, checkpoint has {arr.size}")
+            check(lib.eioku_whisper_set_tensor(self._h, i, arr.ctypes.data, arr.size), f"eioku_whisper_set_tensor({n})")
+
+    @classmethod
+    def from_cache(cls, cache_dir: str | Path, model_name: str = "base", seed: int | None = None, **kw):
+        """``<cache>/whisper/<model_name>/{config.json, generation_config.json, model.safetensors, vocab.json}`` (the
+        Hugging Face ``openai/whisper-*`` files; ctranslate2 ``model.bin`` is not read).  ``seed``: random weights, for
+        the benchmark only - the three JSON files are still required."""
+        root = Path(cache_dir) / "whisper" / model_name
+        need = ["config.json", "generation_config.json", "vocab.json"] + ([] if seed is not None else ["model.safetensors"])
+        missing = [f for f in need if not (root / f).exists()]
+        if missing:
+            raise FileNotFoundError(f"Whisper checkpoint {root} is missing {missing} (Hugging Face format; a ctranslate2 "
+                                    "model.bin is not read)")
+        dims = whisper_dims(json.loads((root / "config.json").read_text()),
+                            json.loads((root / "generation_config.json").read_text()))
+        vocab = json.loads((root / "vocab.json").read_text())
+        if seed is not None:
+            weights = seeded_weights(dims, seed)
+        else:
+            weights = read_safetensors(root / "model.safetensors")
+            if "proj_out.weight" in weights and "model.decoder.embed_tokens.weight" not in weights:
+                weights["model.decoder.embed_tokens.weight"] = weights["proj_out.weight"]
+        return cls(dims, weights, vocab, **kw)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self.lib.eioku_whisper_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # noqa: D105
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    # -- device calls
+    def set_audio(self, samples: np.ndarray) -> None:
+        self._samples = np.ascontiguousarray(samples, dtype=np.float32)
+        self._lib_mod.check(self.lib.eioku_whisper_set_audio(self._h, self._samples.ctypes.data, self._samples.size),
+                            "eioku_whisper_set_audio")
+
+    def logmel(self, offsets, fetch: bool = True):
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        out = np.empty((len(off), self.dims["n_mels"], self.window_frames), dtype=np.float32) if fetch else None
+        self._lib_mod.check(self.lib.eioku_whisper_logmel(self._h, off.ctypes.data, len(off), out.ctypes.data if fetch else None),
+                            "eioku_whisper_logmel")
+        return out
+
+    def encode(self, n_windows: int, mel: np.ndarray | None = None) -> None:
+        if mel is not None:
+            mel = np.ascontiguousarray(mel, dtype=np.float32)
+            if mel.shape != (n_windows, self.dims["n_mels"], self.window_frames):
+                raise ValueError(f"mel must be {(n_windows, self.dims['n_mels'], self.window_frames)}, got {mel.shape}")
+        self._lib_mod.check(self.lib.eioku_whisper_encode(self._h, mel.ctypes.data if mel is not None else None, n_windows),
+                            "eioku_whisper_encode")
+
+    def encoder_output(self, n_windows: int) -> np.ndarray:
+        out = np.empty((n_windows, self.dims["max_source_positions"], self.dims["d_model"]), dtype=np.float16)
+        self._lib_mod.check(self.lib.eioku_whisper_encoder_output(self._h, out.ctypes.data, out.size), "eioku_whisper_encoder_output")
+        return out
+
+    def decode(self, prompt, n_windows: int, max_new_tokens: int, sync_every: int | None = None) -> dict:
+        p = np.ascontiguousarray(prompt, dtype=np.int32)
+        B, n = int(n_windows), int(max_new_tokens)
+        tokens = np.zeros((B, max(n, 1)), dtype=np.int32)
+        n_out = np.zeros(B, dtype=np.int32)
+        lang = np.zeros(B, dtype=np.int32)
+        total = np.zeros(B, dtype=np.float32)
+        nsp = np.zeros(B, dtype=np.float32)
+        self._lib_mod.check(self.lib.eioku_whisper_decode(
+            self._h, p.ctypes.data, len(p), B, n, int(sync_every or self.sync_every), tokens.ctypes.data, n_out.ctypes.data,
+            total.ctypes.data, nsp.ctypes.data, lang.ctypes.data), "eioku_whisper_decode")
+        return {"tokens": tokens[:, :n], "n": n_out, "sum_logprob": total, "no_speech_prob": nsp, "lang": lang}
+
+    def forced_logits(self, ids) -> np.ndarray:
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        out = np.empty(ids.shape + (self.dims["vocab"],), dtype=np.float32)
+        self._lib_mod.check(self.lib.eioku_whisper_forced_logits(self._h, ids.ctypes.data, ids.shape[1], ids.shape[0], out.ctypes.data),
+                            "eioku_whisper_forced_logits")
+        return out
+
+    def select(self, logits, prefixes) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Debug: rules + argmax on supplied logits [B][vocab]; ``prefixes``: per lane the tokens sampled so far."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        B, cap = logits.shape[0], max(1, max(len(p) for p in prefixes))
+        pre = np.zeros((B, cap), dtype=np.int32)
+        for b, p in enumerate(prefixes):
+            pre[b, :len(p)] = p
+        plen = np.asarray([len(p) for p in prefixes], dtype=np.int32)
+        tok, lp, masked = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32), np.empty_like(logits)
+        self._lib_mod.check(self.lib.eioku_whisper_select(self._h, logits.ctypes.data, B, pre.ctypes.data, cap, plen.ctypes.data,
+                                                          tok.ctypes.data, lp.ctypes.data, masked.ctypes.data), "eioku_whisper_select")
+        return tok, lp, masked
+
+    def last_launches(self) -> tuple[int, int]:
+        a, b = C.c_int(0), C.c_int(0)
+        self._lib_mod.check(self.lib.eioku_whisper_last_launches(self._h, C.byref(a), C.byref(b)), "eioku_whisper_last_launches")
+        return a.value, b.value
+
+    def last_flops(self) -> float:
+        f = C.c_double(0)
+        self._lib_mod.check(self.lib.eioku_whisper_last_flops(self._h, C.byref(f)), "eioku_whisper_last_flops")
+        return f.value
+
+    # -- the host loop
+    def _language_token(self, language: str | None):
+        d = self.dims
+        if language is None:
+            return None
+        code = language.strip("<|>").lower()
+        if code not in d["lang_codes"]:
+            raise ValueError(f"language {language!r} is not in the checkpoint's generation_config ({len(d['lang_codes'])} codes)")
+        return d["lang_ids"][d["lang_codes"].index(code)]
+
+    def _prompt(self, lang_id: int | None) -> list[int]:
+        d = self.dims
+        prompt = [d["sot"]]
+        if lang_id is not None:
+            prompt.append(lang_id)
+        if d.get("transcribe") is not None:
+            prompt.append(d["transcribe"])
+        return prompt
+
+    def transcribe(self, samples: np.ndarray, language: str | None = None, *, window_mode: str = "seek",
+                   batch_windows: int = 8, max_new_tokens: int | None = None) -> dict:
+        """-> ``{"segments": [{start_ms, end_ms, text, language, confidence: None, words: None}], "language": code}``.
+
+        ``window_mode="seek"``: one window at a time, the next one starts where Whisper's seek rule says.
+        ``window_mode="fixed"``: independent back-to-back windows, up to ``batch_windows`` decoded in lockstep; a segment
+        cannot span a window edge."""
+        if window_mode not in ("seek", "fixed"):
+            raise ValueError(f"window_mode must be 'seek' or 'fixed', got {window_mode!r}")
+        d = self.dims
+        samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        content_frames = len(samples) // HOP
+        max_new = int(max_new_tokens) if max_new_tokens is not None else d["max_target_positions"] // 2
+        max_new = min(max_new, d["max_target_positions"] - 3)
+        segments: list[dict] = []
+        lang_id = self._language_token(language)
+        if content_frames == 0:
+            return {"segments": [], "language": language}
+        self.set_audio(samples)
+
+        def run(seeks: list[int]) -> dict:
+            nonlocal lang_id
+            self.logmel([s * HOP for s in seeks], fetch=False)
+            self.encode(len(seeks))
+            if lang_id is None and d["lang_ids"]:  # language of the first window: argmax over the language ids after SOT
+                lang_id = int(self.decode([d["sot"]], len(seeks), 0)["lang"][0])
+            return self.decode(self._prompt(lang_id), len(seeks), max_new)
+
+        def emit(res: dict, lane: int, seek: int) -> int:
+            size = min(self.window_frames, content_frames - seek)
+            toks = [int(t) for t in res["tokens"][lane]]
+            n_text = toks.index(d["eot"]) if d["eot"] in toks else len(toks)
+            if skip_window(float(res["no_speech_prob"][lane]), float(res["sum_logprob"][lane]), n_text):
+                return size
+            pieces, advance = cut_window(toks, d["eot"], d["timestamp_begin"], seek * MS_PER_FRAME, size)
+            code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
+            for start_ms, end_ms, ids in pieces:
+                text = self.decoder.decode(ids)
+                if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
+                    continue  # faster-whisper drops empty and zero-length segments
+                segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code,
+                                 "confidence": None, "words": None, "tokens": ids})
+            return max(1, min(advance, size)) if window_mode == "seek" else size
+
+        if window_mode == "seek":
+            seek = 0
+            while seek < content_frames:
+                seek += emit(run([seek]), 0, seek)
+        else:
+            starts = list(range(0, content_frames, self.window_frames))
+            for i in range(0, len(starts), max(1, int(batch_windows))):
+                batch = starts[i:i + max(1, int(batch_windows))]
+                res = run(batch)
+                for lane, s in enumerate(batch):
+                    emit(res, lane, s)
+        code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
+        return {"segments": segments, "language": code}
+
+
+def transcribe_result(raw: dict) -> dict:
+    """The reference's result dict (``model_manager.py:449-463``): exactly its six keys per segment."""
+    keys = ("start_ms", "end_ms", "text", "language", "confidence", "words")
+    return {"segments": [{k: s[k] for k in keys} for s in raw["segments"]]}
+
+
+def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None) -> dict:
+    """``ModelManager.transcribe_video`` body.  Config keys consumed: ``languages`` (string or list: the first entry; None =
+    detect), ``vad_filter`` (accepted, not applied), ``window_mode``, ``batch_windows``; ``model_name`` picks the
+    checkpoint in the caller."""
+    config = config or {}
+    languages = config.get("languages")
+    if isinstance(languages, (list, tuple)):
+        languages = languages[0] if languages else None
+    if config.get("vad_filter"):
+        logger.info("vad_filter is accepted but not applied: Silero VAD is not built; the no-speech rule skips silence")
+    samples, rate = (audio_source or default_audio_source)(path)
+    check_rate(rate)
+    raw = transcriber.transcribe(np.asarray(samples, dtype=np.float32), languages,
+                                 window_mode=config.get("window_mode", "seek"),
+                                 batch_windows=int(config.get("batch_windows", 8)))
+    return transcribe_result(raw)

@@ -570,6 +570,56 @@ int eioku_thumbs_jpeg(eioku_thumbs_t* t, const uint8_t* rgb, int n, int th, int 
 int eioku_thumbs_read(eioku_thumbs_t* t, uint8_t* out, size_t cap, void* stream);
 int eioku_thumbs_last_ms(eioku_thumbs_t* t, double* ms4);
 
+/* ---- transcription: Whisper log-mel front end (K19) and greedy decode (K20), csrc/whisper.hip --------------------------
+ * Fills ModelManager.transcribe_video (the reference calls faster_whisper.WhisperModel.transcribe on the CPU).  fp16
+ * weights and activations, fp32 accumulation, fp32 residual stream / LayerNorm / softmax; head dimension 64.  All data
+ * pointers are HOST pointers, every call is synchronous on the null stream.  Every dimension and every special-token id
+ * comes from the config struct (config.json / generation_config.json of the checkpoint).
+ * create: d_model % 64 == 0, d_model == 64 * heads, ffn % 32 == 0, else EIOKU_EINVAL.  suppress / begin_suppress / lang_ids
+ *   are copied.  Tensors carry the Hugging Face WhisperForConditionalGeneration names; tensor_info gives rows x cols with
+ *   rows * cols = numel (conv weights: rows = out channels, cols = in channels * 3); set_tensor takes fp32 in the
+ *   checkpoint's own layout and converts on the device.  mel_filters: [n_mels][201] float64 (Slaney, made by the host).
+ * set_audio: fp32 mono 16 kHz samples, uploaded once per video.
+ * logmel: B windows starting at sample offsets[b] -> [B][n_mels][2 * max_source_positions] fp32, kept on the device for
+ *   encode and copied to `out` when it is not NULL.  DFT and mel product in fp64.
+ * encode: the encoder and the cross-attention K/V of every decoder layer for B windows; mel NULL = the last logmel result.
+ * decode: greedy, temperature 0, timestamp rules, B lanes in lockstep over the last encode.  prompt_ids [prompt_len] is
+ *   shared by the lanes.  tokens_out [B][max_new_tokens] (EOT-filled after a lane ends), n_out [B] = tokens sampled up to
+ *   and including EOT, sum_logprob [B] over those, no_speech_prob [B] and lang_out [B] from the logits at prompt position
+ *   0.  Tokens are read back at most every sync_every sampled steps (the loop ends early once every lane is done).
+ * forced_logits (tests): teacher-forced, rule-free logits [B][T][vocab] for ids [B][T].
+ * select (tests): the rule + argmax stage on supplied logits [B][vocab]; prefix [B][prefix_cap] with prefix_len [B] are the
+ *   tokens sampled so far.  token_out [B], logprob_out [B], masked_out [B][vocab] (rules 1-6 applied; may be NULL).
+ * encoder_output (tests): the final-LayerNorm output of the last encode, raw fp16 [B][ctx][d_model].
+ * last_launches: kernel launches of the last decode and its number of decoder steps. */
+typedef struct {
+  int n_mels, d_model, heads, enc_layers, dec_layers, enc_ffn, dec_ffn, vocab, max_source_positions, max_target_positions;
+  int eot, no_timestamps, timestamp_begin, no_speech, max_initial_timestamp_index;
+  int n_suppress, n_begin_suppress, n_langs;
+  const int32_t* suppress;
+  const int32_t* begin_suppress;
+  const int32_t* lang_ids;
+  const double* mel_filters;
+} eioku_whisper_cfg_t;
+typedef struct eioku_whisper eioku_whisper_t;
+int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper_t** out);
+void eioku_whisper_destroy(eioku_whisper_t* m);
+int eioku_whisper_num_tensors(const eioku_whisper_t* m);
+int eioku_whisper_tensor_info(const eioku_whisper_t* m, int idx, char* name, size_t name_cap, int* rows, int* cols);
+int eioku_whisper_set_tensor(eioku_whisper_t* m, int idx, const float* host_data, size_t numel);
+int eioku_whisper_set_audio(eioku_whisper_t* m, const float* samples, long long n_samples);
+int eioku_whisper_logmel(eioku_whisper_t* m, const long long* offsets, int B, float* out);
+int eioku_whisper_encode(eioku_whisper_t* m, const float* mel, int B);
+int eioku_whisper_decode(eioku_whisper_t* m, const int32_t* prompt_ids, int prompt_len, int B, int max_new_tokens,
+                         int sync_every, int32_t* tokens_out, int32_t* n_out, float* sum_logprob, float* no_speech_prob,
+                         int32_t* lang_out);
+int eioku_whisper_forced_logits(eioku_whisper_t* m, const int32_t* ids, int T, int B, float* logits_out);
+int eioku_whisper_select(eioku_whisper_t* m, const float* logits, int B, const int32_t* prefix, int prefix_cap,
+                         const int32_t* prefix_len, int32_t* token_out, float* logprob_out, float* masked_out);
+int eioku_whisper_encoder_output(eioku_whisper_t* m, void* out_f16, size_t numel);
+int eioku_whisper_last_flops(const eioku_whisper_t* m, double* flops);
+int eioku_whisper_last_launches(const eioku_whisper_t* m, int* launches, int* steps);
+
 #ifdef __cplusplus
 }
 #endif

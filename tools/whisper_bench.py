@@ -1,0 +1,128 @@
+#!/usr/bin/env python
+"""Whisper on the HIP path: device time of the log-mel front end, the encoder and a decoder step, with seeded weights.
+
+    python tools/whisper_bench.py [--shapes base small] [--windows 64] [--out profiles/whisper.json]
+
+For each shape (the openai `base` and `small` dimensions, vocabulary 51865, ctx 1500): log-mel over `--windows` windows of
+30 s, the encoder per window at batch 8, a decoder step at B = 1, 8 and 32 (greedy, 32 sampled tokens, lanes never end
+early with random weights unless EOT wins), kernel launches per step, and the CPU oracle (tests/whisper_oracle.py, fp32,
+torch-CPU) on the same box for one window and a few steps.  Calls are synchronous, so wall-clock time around them is device
+time plus one launch-queue drain.  No number here is an acceptance bar.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+SHAPES = {"base": (512, 8, 6, 2048), "small": (768, 12, 12, 3072)}
+
+
+def dims_for(name: str) -> dict:
+    d, heads, layers, ffn = SHAPES[name]
+    return {"n_mels": 80, "d_model": d, "heads": heads, "enc_layers": layers, "dec_layers": layers, "enc_ffn": ffn, "dec_ffn": ffn,
+            "vocab": 51865, "max_source_positions": 1500, "max_target_positions": 448, "sot": 50258, "eot": 50257,
+            "transcribe": 50359, "translate": 50358, "no_speech": 50362, "no_timestamps": 50363, "timestamp_begin": 50364,
+            "max_initial_timestamp_index": 50, "suppress": [50258, 50358, 50359, 50360, 50361, 50362],
+            "begin_suppress": [220, 50257], "lang_ids": list(range(50259, 50358)), "lang_codes": [f"l{i}" for i in range(99)]}
+
+
+def timed(fn, reps: int = 3) -> float:
+    fn()
+    best = float("inf")
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        best = min(best, time.perf_counter() - t0)
+    return best * 1e3
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", nargs="+", default=["base", "small"], choices=sorted(SHAPES))
+    ap.add_argument("--windows", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "whisper.json"))
+    args = ap.parse_args()
+
+    from eioku_amd import _lib
+    from eioku_amd.transcribe import WhisperTranscriber, seeded_weights
+
+    info = _lib.device_info()
+    rng = np.random.default_rng(0)
+    audio = (0.1 * rng.standard_normal(args.windows * 480000)).astype(np.float32)
+    result = {"what": "tools/whisper_bench.py on one MI355X: seeded weights, wall-clock ms around synchronous calls (best of 3 "
+                      "after a warm-up); no number is an acceptance bar", "device": info, "windows": args.windows, "shapes": []}
+    for name in args.shapes:
+        dims = dims_for(name)
+        t = WhisperTranscriber(dims, seeded_weights(dims, 1))
+        t.set_audio(audio)
+        row = {"shape": name, "d_model": dims["d_model"], "layers": dims["enc_layers"]}
+        offsets = [i * 480000 for i in range(args.windows)]
+        row["logmel_ms_per_window"] = timed(lambda: [t.logmel(offsets[i:i + 8], fetch=False) for i in range(0, len(offsets), 8)]) / args.windows
+        t.logmel(offsets[:8], fetch=False)
+        row["encoder_ms_per_window_b8"] = timed(lambda: t.encode(8)) / 8
+        row["encoder_tflops_b8"] = t.last_flops() / (row["encoder_ms_per_window_b8"] * 8 * 1e-3) / 1e12
+        prompt = [dims["sot"], dims["lang_ids"][0], dims["transcribe"]]
+        for b in (1, 8, 32):
+            t.logmel(offsets[:b], fetch=False)
+            t.encode(b)
+            holder = {}
+
+            def run():
+                holder["res"] = t.decode(prompt, b, args.steps, sync_every=args.steps)
+
+            ms = timed(run)
+            launches, steps = t.last_launches()
+            row[f"decode_ms_per_step_b{b}"] = ms / steps
+            row[f"decode_steps_b{b}"] = steps
+            row["launches_per_step"] = launches / steps
+        if not args.no_cpu:
+            import torch
+            import whisper_oracle as wo
+
+            weights = {}
+            make = seeded_weights(dims, 1)
+            import ctypes as C
+
+            nm, rows, cols = C.create_string_buffer(256), C.c_int(0), C.c_int(0)
+            for i in range(t.lib.eioku_whisper_num_tensors(t._h)):
+                t.lib.eioku_whisper_tensor_info(t._h, i, nm, 256, C.byref(rows), C.byref(cols))
+                n = nm.value.decode()
+                arr = torch.from_numpy(make(n, rows.value, cols.value).copy())
+                if "conv" in n and n.endswith(".weight"):
+                    arr = arr.view(rows.value, cols.value // 3, 3)
+                elif not (n.endswith(".bias") or "layer_norm" in n):
+                    arr = arr.view(rows.value, cols.value)
+                weights[n] = arr
+            oracle = wo.Oracle(dims, weights, fp16=False)
+            mel = wo.log_mel(audio, 0, 3000, 80)[None]
+            t0 = time.perf_counter()
+            wo.log_mel(audio, 0, 3000, 80)
+            row["cpu_logmel_ms_per_window"] = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            enc = oracle.encode(mel)
+            row["cpu_encoder_ms_per_window"] = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            oracle.greedy(enc, prompt, 4)
+            row["cpu_decode_ms_per_step_b1"] = (time.perf_counter() - t0) * 1e3 / 4
+            row["cpu_threads"] = torch.get_num_threads()
+        t.close()
+        print(json.dumps(row))
+        result["shapes"].append(row)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
