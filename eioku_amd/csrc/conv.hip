@@ -25,6 +25,7 @@ namespace eioku {
 
 namespace {
 std::atomic<unsigned> g_route_counts[kRouteSlots];
+std::atomic<unsigned> g_epi_launches{0};  // k_conv3x3_flat launches that took the straight-line epilogue (eioku_debug_conv_epi)
 }
 void route_hit(int id) {
   if (id >= 0 && id < kRouteSlots) g_route_counts[id].fetch_add(1u, std::memory_order_relaxed);
@@ -98,6 +99,8 @@ struct ConvArgs {
   int Ho, Wo, Cout, out_cs;
   int res_cs;
   int tiles_w, tiles_h, nchunks, act;
+  // k_conv3x3_flat may take its straight-line epilogue (conv_epi_on(): EIOKU_CONV_EPI=0 clears it)
+  int epi = 0;
   // fused following 1x1 (persistent kernel, POST): out2 = act2(W2 . act(conv3x3) + b2); `out` is then unused
   const uint4* post_w;
   const float* post_bias;
@@ -217,6 +220,53 @@ __device__ __forceinline__ void store_frag(const ConvArgs& a, const float4v& acc
         }
         STG(_Float16, reinterpret_cast<_Float16*>(a.out) + (size_t)(opix * (unsigned)a.out_cs + (unsigned)(c0 + j)), o, a.x_out);
       }
+  }
+}
+
+// ---- straight-line epilogue of k_conv3x3_flat (r4) -----------------------------------------------------------------
+// The common layer - fp16 output, the whole cout tile inside Cout, SiLU or no activation, no residual or a vector
+// residual - does store_frag's arithmetic in store_frag's order (bias add, silu4, RNE, fp16(fp16(y) + x)) with nothing
+// decided per fragment: the variant (with / without residual) is a compile-time tag chosen once per launch by a uniform
+// branch, SiLU or not is one uniform test per row of NF fragments with no memory access behind it, the row's address
+// and its `pixel exists` test are computed once per row, and a fragment is a compile-time offset from the row.
+// kEpiGeneric = store_frag (ragged tile, fp32 output, ReLU modes, Cout < 4, EIOKU_CONV_EPI=0).  k_conv3x3_persist does
+// NOT use it: three copies of its tile loop in one kernel cost 30-90 VGPRs (a wave of occupancy on most instantiations,
+// scratch on the S2 NCH3 ones); DESIGN.md, "Round-4 findings".
+enum { kEpiGeneric = 0, kEpiPlain = 1, kEpiRes = 2 };
+template <int E>
+using EpiTag = std::integral_constant<int, E>;
+__device__ __forceinline__ int epi_variant(const ConvArgs& a, int c_end, bool res_vec) {
+  if (!a.epi || a.out_f32 || c_end > a.Cout || (a.Cout & 3) != 0 || (a.res && !res_vec)) return kEpiGeneric;
+  if (a.act != kActSiLU && a.act != kActNone) return kEpiGeneric;
+  return a.res ? kEpiRes : kEpiPlain;
+}
+// The NF fragments of one output row of the lane: every value first, then - behind the row's one test - nothing but the
+// NF stores at immediate offsets from `row` (= the lane's first cout of the tile at the row's pixel).  The empty asm pins
+// the values in front of the test, so that the exec-masked block behind it holds the stores and nothing else.
+template <int E, int NF>
+__device__ __forceinline__ void epi_store_row(const ConvArgs& a, const float4v (&acc)[NF], const float4 (&b)[NF],
+                                              const u32x2 (&r)[NF], __half* row, bool ok) {
+  float4v v[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) v[f] = acc[f] + float4v{b[f].x, b[f].y, b[f].z, b[f].w};
+  if (a.act == kActSiLU) {
+#pragma unroll
+    for (int f = 0; f < NF; ++f) v[f] = silu4(v[f]);
+  }
+  u32x2 h[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    f16x4 h4 = __builtin_convertvector(v[f], f16x4);  // RNE
+    if (E == kEpiRes) {
+      const float4v sum = __builtin_convertvector(h4, float4v) + __builtin_convertvector(__builtin_bit_cast(f16x4, r[f]), float4v);
+      h4 = __builtin_convertvector(sum, f16x4);
+    }
+    h[f] = __builtin_bit_cast(u32x2, h4);
+    asm volatile("" : "+v"(h[f]));
+  }
+  if (ok) {
+#pragma unroll
+    for (int f = 0; f < NF; ++f) STG(u32x2, row + f * 16, h[f], a.x_out);
   }
 }
 
@@ -690,6 +740,38 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_flat(ConvArgs a, int npix, i
     __syncthreads();
   }
 
+  // ---- epilogue: one uniform choice, then (r4) MT rows of NF straight-line stores.  A residual is loaded for all
+  // MT * NF fragments up front (pixels past the end re-read the last one): one round trip per workgroup where
+  // store_frag's load -> vmcnt(0) -> add -> store made it one per fragment ----
+  const int c_first = co_tile * 16 * NF + (lane >> 4) * 4;
+  auto fast = [&](auto tag) {
+    constexpr int E = decltype(tag)::value;
+    float4 b[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) b[f] = *reinterpret_cast<const float4*>(a.bias + c_first + f * 16);
+    u32x2 r[MT][NF];
+    unsigned Pc[MT];
+    bool ok[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int P = P0 + (wave * MT + m) * 16 + (lane & 15);
+      ok[m] = P <= Plast;
+      Pc[m] = (unsigned)(ok[m] ? P : Plast);
+#pragma unroll
+      for (int f = 0; f < NF; ++f) {
+        r[m][f] = u32x2{0, 0};
+        if (E == kEpiRes) r[m][f] = LDG(u32x2, a.res + (size_t)(Pc[m] * (unsigned)a.res_cs + (unsigned)(c_first + f * 16)), a.x_res);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+      epi_store_row<E, NF>(a, acc[m], b, r[m], a.out + (size_t)(Pc[m] * (unsigned)a.out_cs + (unsigned)c_first), ok[m]);
+  };
+  switch (epi_variant(a, (co_tile + 1) * 16 * NF, a.res != nullptr && a.Cout >= 4)) {
+    case kEpiPlain: fast(EpiTag<kEpiPlain>{}); return;
+    case kEpiRes: fast(EpiTag<kEpiRes>{}); return;
+    default: break;
+  }
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     const int P = P0 + (wave * MT + m) * 16 + (lane & 15);
@@ -844,8 +926,9 @@ __global__ __launch_bounds__(64 * NWV) void k_conv3x3_persist(ConvArgs a, int to
     __syncthreads();  // also orders the weight copy before the first tile
     const int tn = nx_n, tth = nx_th, ttw = nx_tw;
     const int ow = ttw * kTW + (lane & 15);
-    // residual of THIS tile first, then the next tile's patch: the epilogue then waits only for the
-    // older loads (vmcnt is in order) and the prefetch stays in flight across it
+    // residual of THIS tile first, then the next tile's patch, so that the residual loads are the older entries of the
+    // in-order vmcnt queue.  (That alone does not keep the prefetch in flight: store_frag's run-time branches hide the
+    // count from the compiler, and the ISA waits with vmcnt(0) - prefetch included - before the first residual add.)
     u32x2 resv[2][NF];
     if (res_vec) {
 #pragma unroll
@@ -1972,6 +2055,9 @@ int launch_flat(const ConvArgs& a, const FlatGeom& g, int ntiles, hipStream_t st
   const int npix = a.N * a.Ho * a.Wo;
   const int tpx = 64 * MT;
   route_hit(route_id(kRouteFlat, NF, S, MT, NS));
+  // the kernel's own test (epi_variant) for the first cout tile: this launch runs the straight-line epilogue somewhere
+  if (a.epi && !a.out_f32 && (a.Cout & 3) == 0 && a.Cout >= 16 * NF && (a.act == kActSiLU || a.act == kActNone))
+    g_epi_launches.fetch_add(1u, std::memory_order_relaxed);
   hipLaunchKernelGGL((k_conv3x3_flat<NF, S, MT, NS>), dim3((unsigned)((npix + tpx - 1) / tpx), (unsigned)ntiles),
                      dim3(256), g.lds, stream, a, npix, g.PR, g.PW);
   EIOKU_LAUNCH_CHECK();
@@ -2165,6 +2251,13 @@ void conv_weights_destroy(ConvWeights* cw) {
   if (cw->d_b) (void)hipFree(cw->d_b);
   cw->d_w = nullptr;
   cw->d_b = nullptr;
+}
+
+// EIOKU_CONV_EPI=0: k_conv3x3_flat runs store_frag's generic epilogue everywhere (byte-identity tests,
+// tools/ab_bench.sh)
+static bool conv_epi_on() {
+  static const bool off = env_off("EIOKU_CONV_EPI");
+  return !off;
 }
 
 bool conv_clsmax_ok(const ConvWeights& cw, int act) {
@@ -2419,6 +2512,7 @@ int conv_forward(const ConvWeights& cw, Slice in, int N, int H, int W, Slice out
   a.tiles_h = (a.Ho + kTH - 1) / kTH;
   a.nchunks = cw.nchunks;
   a.act = act;
+  a.epi = conv_epi_on() ? 1 : 0;
   a.post_w = post ? reinterpret_cast<const uint4*>(post->d_w) : nullptr;
   a.post_bias = post ? post->d_b : nullptr;
   a.post_out = post ? a.out : nullptr;  // `out` is the 1x1's output slice
@@ -2580,6 +2674,14 @@ int eioku_debug_conv_routes(char* buf, size_t cap, int reset) {
   }
   if (cap) buf[pos] = 0;
   EIOKU_REQUIRE(fits, "route log does not fit %zu bytes", cap);
+  return EIOKU_OK;
+}
+
+// Launches, since the last reset, of a kernel whose straight-line epilogue (EIOKU_CONV_EPI) was taken by at least its first
+// cout tile: lets a test see that the comparison "switch on against switch off" compares two different loops.
+int eioku_debug_conv_epi(int* launches, int reset) {
+  EIOKU_REQUIRE(launches, "NULL argument");
+  *launches = (int)(reset ? g_epi_launches.exchange(0u, std::memory_order_relaxed) : g_epi_launches.load(std::memory_order_relaxed));
   return EIOKU_OK;
 }
 

@@ -56,3 +56,11 @@ def conv_routes(reset: bool = False) -> dict[str, int]:
         name, count = line.rsplit(" ", 1)
         routes[name] = int(count)
     return routes
+
+
+def conv_epi_launches(reset: bool = False) -> int:
+    """Launches of k_conv3x3_flat in this process since the last reset that took the straight-line epilogue on at least
+    their first cout tile (``eioku_debug_conv_epi``); 0 with ``EIOKU_CONV_EPI=0``."""
+    n = C.c_int(0)
+    _lib.check(_lib.load().eioku_debug_conv_epi(C.byref(n), int(reset)), "eioku_debug_conv_epi")
+    return n.value

@@ -177,6 +177,8 @@ int eioku_debug_bounds(int* violations, int* line, int reset, int selftest);
  * the NUL-terminated text (EIOKU_EINVAL when cap is too small; buf NULL with cap 0 only resets); reset != 0 clears the
  * counters after reading them.  Thread safe; needs no eioku_init. */
 int eioku_debug_conv_routes(char* buf, size_t cap, int reset);
+/* k_conv3x3_flat launches since the last reset whose straight-line epilogue (EIOKU_CONV_EPI) ran on at least the first cout tile */
+int eioku_debug_conv_epi(int* launches, int reset);
 
 /* YOLOv8 detector handle.  Replaces `YOLO(model_path); model.to(device)` + `model(frame, conf=..)`
  * of ModelManager.detect_objects / detect_faces (model_manager.py:252-254,270-275 / :346-348,

@@ -53,6 +53,15 @@ def main():
         launch_epilogue(gpu, item)
         launches += 1
     out["after_epilogues"] = bounds()[0]
+    # the straight-line epilogues of the persistent / flat 3x3 kernels: the table of tests/conv_epilogue_cases.py
+    import conv_epilogue_cases as cec
+
+    for _, shape, act, res, f32 in cec.all_cases():
+        cec.launch(gpu, shape, act, res, f32)
+        launches += 1
+    cec.launch_steady(gpu)
+    launches += 3
+    out["after_conv_epilogue"] = bounds()[0]
     # 2. whole forwards at 96 x 160 (every layer of v8n / v8s / v8m incl. the fused pairs, chains, flat and generic kernels)
     from eioku_amd import weights as W
 

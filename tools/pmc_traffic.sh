@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 declare -A TOT
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pm
-  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d /tmp/pm -- python3 "$@" > /tmp/pm.log 2>&1
+  timeout -k 10 400 rocprofv3 --pmc $c --output-format csv -d /tmp/pm -- python3 "$@" > /tmp/pm.log 2>&1 || { tail -5 /tmp/pm.log; exit 1; }  # nothing more on the GPU after a failed pass
   F=$(ls /tmp/pm/*/*counter_collection.csv 2>/dev/null | head -1)
   TOT[$c]=$(python3 - "$F" "$KSUB" <<'PY'
 import csv, sys
