@@ -9,6 +9,9 @@
 //                       text and timestamp ids, log-sum-exp over all and over timestamp ids); the vocab-wide logits are
 //                       written only for the debug entry points
 //        k_select       combines the partials, applies the timestamp-mass rule, picks the token, updates the lane state
+//   K20b k_logits<., true> / k_beam_select   beam search: per-block top W + 1 text and timestamp ids next to the partials,
+//                       then per window the per-beam merge, the cross-beam walk, and the permuted lane state, ancestry
+//                       table, token history and finished records (DESIGN.md "K20b beam search")
 // Precision points (tests/whisper_oracle.py, fp16=True, rounds at the same places): weights of every linear / conv layer
 // and the token embedding are fp16; biases, LayerNorm parameters and both position tables fp32; the residual stream is
 // fp32; LayerNorm outputs, q / k / v, attention outputs, GELU outputs and the mel input are rounded to fp16.
@@ -236,10 +239,13 @@ __global__ __launch_bounds__(256) void k_embed(const int* __restrict__ toks, int
 // grid (ceil(n_q / (4 QPW)), heads, B), 4 waves, each wave QPW query rows against all n_keys keys of its head.  Pass 1: lane
 // j takes keys j, j + 64, ...: score = (q . k) / 8 into LDS, running max.  Pass 2: exp and sum.  Pass 3: lane = output
 // dimension, o = sum_j p_j v[j][lane] (a 128-byte row per key).  Dynamic LDS: 4 QPW (n_keys + 64) floats.
-template <int QPW>
+// Query batch b reads the keys of batch b / kv_div (beam search: the W lanes of a window share its cross-attention K / V).
+// ANC: key j of batch b is row j of batch anc[b * anc_ld + j] (beam search: the lane whose step j is in b's history).
+template <int QPW, bool ANC = false>
 __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long long q_bs, int q_rs, const h16* __restrict__ Kc,
                                               const h16* __restrict__ Vc, long long kv_bs, int kv_rs, int n_q, int n_keys,
-                                              h16* __restrict__ O, long long o_bs, int o_rs) {
+                                              h16* __restrict__ O, long long o_bs, int o_rs, int kv_div,
+                                              const uint8_t* __restrict__ anc, int anc_ld) {
   extern __shared__ float smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, head = blockIdx.y, b = blockIdx.z;
   const int q0 = (blockIdx.x * 4 + wave) * QPW;
@@ -251,13 +257,15 @@ __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long lo
     qs[i * 64 + lane] = qi < n_q ? (float)Q[(size_t)b * q_bs + (size_t)qi * q_rs + head * 64 + lane] : 0.f;
   }
   __syncthreads();
-  const h16* kb = Kc + (size_t)b * kv_bs + head * 64;
-  const h16* vb = Vc + (size_t)b * kv_bs + head * 64;
+  const size_t kvb = ANC ? 0 : (size_t)(b / kv_div);
+  const h16* kb = Kc + kvb * kv_bs + head * 64;
+  const h16* vb = Vc + kvb * kv_bs + head * 64;
+  const uint8_t* an = ANC ? anc + (size_t)b * anc_ld : nullptr;
   float mx[QPW], sum[QPW], o[QPW];
 #pragma unroll
   for (int i = 0; i < QPW; ++i) mx[i] = kNegInf, sum[i] = 0.f, o[i] = 0.f;
   for (int j = lane; j < n_keys; j += 64) {
-    const uint4* kr = reinterpret_cast<const uint4*>(kb + (size_t)j * kv_rs);
+    const uint4* kr = reinterpret_cast<const uint4*>(kb + (ANC ? (size_t)an[j] * kv_bs : 0) + (size_t)j * kv_rs);
     float s[QPW];
 #pragma unroll
     for (int i = 0; i < QPW; ++i) s[i] = 0.f;
@@ -292,7 +300,7 @@ __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long lo
   }
   __syncthreads();
   for (int j = 0; j < n_keys; ++j) {
-    const float vf = (float)vb[(size_t)j * kv_rs + lane];
+    const float vf = (float)vb[(ANC ? (size_t)an[j] * kv_bs : 0) + (size_t)j * kv_rs + lane];
 #pragma unroll
     for (int i = 0; i < QPW; ++i) o[i] += sc[(size_t)i * n_keys + j] * vf;
   }
@@ -317,6 +325,9 @@ struct LaneState {  // per decode lane, on the device
 // per (lane, workgroup) partial over the workgroup's 64 vocabulary ids
 constexpr int kNP = 10;  // max_text, arg_text, max_ts, arg_ts, m_all, s_all, s_ts (relative to max_ts), m_raw, s_raw, unused
 constexpr int kFlagSuppress = 1, kFlagBegin = 2;  // flags[id]: bit 0 / 1, language index + 1 in bits 2..
+// beam search: a beam partial is the kNP values above, then the block's best text ids and best timestamp ids as (value, id)
+// pairs, kNC of each, best first, (-inf, -1) where there are fewer
+constexpr int kMaxBeam = 8, kNC = kMaxBeam + 1, kMaxFinish = 16, kNPB = kNP + 4 * kNC;
 
 __device__ __forceinline__ bool rule_masks(int n, const SelCfg& c, unsigned flag, const LaneState& st) {
   const bool is_ts = n >= c.tb;
@@ -341,15 +352,21 @@ __device__ __forceinline__ bool rule_masks(int n, const SelCfg& c, unsigned flag
 // grid ceil(vocab / 64), 4 waves; wave w computes ids v0 + 16 w .. + 15 for 16 lanes at a time on the MFMA (or reads the
 // supplied logits), masks them, and parks raw and masked values in LDS; thread b < 16 then folds the 64 ids of its lane
 // in id order.  rules = 0: no masking (teacher-forced positions).
-template <bool SUPPLIED>
+// BEAM: partials of kNPB values; the nc best masked text ids and the nc best masked timestamp ids of the block follow the
+// kNP values.  Thread (lane tid & 15, ids 4 (tid >> 4) ..+ 3) ranks its ids within their class by (value, lower id first):
+// an id's rank is the number of ids of its class that beat it, so every rank is written once and no order of threads matters.
+template <bool SUPPLIED, bool BEAM = false>
 __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d, const h16* __restrict__ E,
                                                 const float* __restrict__ supplied, int B, SelCfg c,
                                                 const uint16_t* __restrict__ flags, const LaneState* __restrict__ st, int rules,
                                                 float* __restrict__ partial, int nblk, float* __restrict__ raw_out,
                                                 long long raw_ld, float* __restrict__ masked_out, float* __restrict__ info,
-                                                int nlang) {
+                                                int nlang, int nc) {
   __shared__ float raw[64][17];
   __shared__ float msk[64][17];
+  __shared__ float topv[BEAM ? 16 : 1][2][kNC];
+  __shared__ int topi[BEAM ? 16 : 1][2][kNC];
+  constexpr int NP = BEAM ? kNPB : kNP;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, u = lane >> 4;
   const int v0 = blockIdx.x * 64, n0 = v0 + wave * 16;
   for (int bt = 0; bt < B; bt += 16) {
@@ -394,6 +411,31 @@ __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d
       msk[row][r] = mv;
     }
     __syncthreads();
+    if constexpr (BEAM) {
+      for (int i = tid; i < 16 * 2 * kNC; i += 256) (&topv[0][0][0])[i] = kNegInf, (&topi[0][0][0])[i] = -1;
+      __syncthreads();
+      const int bl = tid & 15, g = tid >> 4, split = c.tb - v0;  // block ids i < split are text
+      if (bt + bl < B) {
+        float mine[4];
+        int rank[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) mine[t] = msk[4 * g + t][bl];
+        for (int i = 0; i < 64; ++i) {
+          const float o = msk[i][bl];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const int me = 4 * g + t;
+            if ((i >= split) == (me >= split) && (o > mine[t] || (o == mine[t] && i < me))) rank[t] += 1;
+          }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int me = 4 * g + t;
+          if (mine[t] > kNegInf && rank[t] < nc) topv[bl][me >= split][rank[t]] = mine[t], topi[bl][me >= split][rank[t]] = v0 + me;
+        }
+      }
+      __syncthreads();
+    }
     if (tid < 16 && bt + tid < B) {
       float max_text = kNegInf, max_ts = kNegInf, m_raw = kNegInf;
       int arg_text = -1, arg_ts = -1;
@@ -417,9 +459,14 @@ __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d
         }
         if (rv > kNegInf) s_raw += expf(rv - m_raw);
       }
-      float* p = partial + ((size_t)(bt + tid) * nblk + blockIdx.x) * kNP;
+      float* p = partial + ((size_t)(bt + tid) * nblk + blockIdx.x) * NP;
       p[0] = max_text, p[1] = __int_as_float(arg_text), p[2] = max_ts, p[3] = __int_as_float(arg_ts);
       p[4] = m_all, p[5] = s_all, p[6] = s_ts, p[7] = m_raw, p[8] = s_raw, p[9] = 0.f;
+      if constexpr (BEAM) {
+        for (int q = 0; q < 2; ++q)
+          for (int r = 0; r < kNC; ++r)
+            p[kNP + 2 * (q * kNC + r)] = topv[tid][q][r], p[kNP + 2 * (q * kNC + r) + 1] = __int_as_float(topi[tid][q][r]);
+      }
     }
     __syncthreads();
   }
@@ -510,6 +557,203 @@ __global__ __launch_bounds__(64) void k_select(const float* __restrict__ partial
   if (logprob_out) logprob_out[b] = lp;
 }
 
+// ---- beam search (K20b) ----------------------------------------------------------------------------------------------------
+// Candidate order everywhere: the larger value first, the lower id on equal values.  (-inf, -1) is an empty entry.
+__device__ __forceinline__ bool cand_better(float v, int i, float w, int k) { return v > w || (v == w && i < k); }
+
+// sorted insert into a register-resident list of kNC entries (statically indexed: the loop is fully unrolled)
+__device__ __forceinline__ void top_insert(float (&v)[kNC], int (&id)[kNC], float x, int xi) {
+#pragma unroll
+  for (int r = 0; r < kNC; ++r) {
+    if (cand_better(x, xi, v[r], id[r])) {
+      const float tv = v[r];
+      const int ti = id[r];
+      v[r] = x, id[r] = xi, x = tv, xi = ti;
+    }
+  }
+}
+
+// The wave's kNC best entries of 64 sorted per-thread lists, best first, into out_v / out_i [kNC] (LDS).  Round r: the best
+// head of the wave by a butterfly over a total order (ids are unique, so every lane sees the same winner); its owner pops.
+__device__ __forceinline__ void wave_top(float (&v)[kNC], int (&id)[kNC], int lane, float* out_v, int* out_i) {
+#pragma unroll
+  for (int r = 0; r < kNC; ++r) {
+    float hv = v[0];
+    int hi = id[0];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(hv, off, 64);
+      const int oi = __shfl_xor(hi, off, 64);
+      if (cand_better(ov, oi, hv, hi)) hv = ov, hi = oi;
+    }
+    if (hi >= 0 && id[0] == hi) {
+#pragma unroll
+      for (int q = 0; q + 1 < kNC; ++q) v[q] = v[q + 1], id[q] = id[q + 1];
+      v[kNC - 1] = kNegInf, id[kNC - 1] = -1;
+    }
+    if (lane == r) out_v[r] = hv, out_i[r] = hi;
+  }
+}
+
+// grid B (windows), W waves: wave j is beam slot j, lane b W + j.
+//  1. the wave folds its lane's block partials (threads take blocks lane, lane + 64, ... in order, thread 0 then folds the
+//     64 threads in order: the fold of k_select) and merges the blocks' best text and timestamp ids into the lane's best
+//     nc = W + 1 of each class;
+//  2. thread 0 of the wave decides the timestamp-mass rule and lists the slot's candidates (sum + log-probability, id),
+//     best first; a dead slot (sum = -inf) has none;
+//  3. thread 0 of the workgroup walks the candidates of all slots in (score, slot, id) order: EOT candidates finish, the
+//     others fill the next slots, until W slots are filled;
+//  4. all threads write the next lane states, input tokens, ancestry rows, token histories and the finished records.
+// A complete window carries its slots over unchanged (identity permutation, no token, nothing recorded).
+// s: the key row this step wrote; idx: the index of the token this step samples.  anc / hist may be NULL (test entry).
+__global__ __launch_bounds__(64 * kMaxBeam) void k_beam_select(
+    const float* __restrict__ partial, int nblk, SelCfg c, int W, int C, int s, int idx, LaneState* __restrict__ st,
+    int* __restrict__ cur_tok, const uint8_t* __restrict__ anc, uint8_t* __restrict__ anc_next, int anc_ld,
+    const int* __restrict__ hist, int* __restrict__ hist_next, int hist_ld, int* __restrict__ fin_tok, float* __restrict__ fin_sum,
+    int* __restrict__ fin_n, int* __restrict__ fin_count, int* __restrict__ complete, int* __restrict__ out_src,
+    int* __restrict__ out_tok, float* __restrict__ out_sum, int* __restrict__ out_nlive, int* __restrict__ out_fsrc,
+    float* __restrict__ out_fsum, int* __restrict__ out_nfin) {
+  __shared__ Acc sh[kMaxBeam][64];
+  __shared__ float lv[kMaxBeam][2][kNC];
+  __shared__ int li[kMaxBeam][2][kNC];
+  __shared__ float cs[kMaxBeam][kNC];
+  __shared__ int ct[kMaxBeam][kNC];
+  __shared__ int cn[kMaxBeam], head[kMaxBeam];
+  __shared__ LaneState old[kMaxBeam];
+  __shared__ int n_src[kMaxBeam], n_tok[kMaxBeam], f_src[kMaxBeam];
+  __shared__ float n_sum[kMaxBeam], f_sum[kMaxBeam];
+  __shared__ int n_live, n_fin, fc_old, fc_new, carry;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, j = tid >> 6, nc = W + 1, L0 = b * W;
+  if (tid < W) old[tid] = st[L0 + tid];
+  // 1
+  Acc a = {kNegInf, kNegInf, kNegInf, 0.f, 0.f, kNegInf, 0.f, -1, -1};
+  float tv[kNC], sv[kNC];
+  int ti[kNC], si[kNC];
+#pragma unroll
+  for (int r = 0; r < kNC; ++r) tv[r] = sv[r] = kNegInf, ti[r] = si[r] = -1;
+  for (int k = lane; k < nblk; k += 64) {
+    const float* p = partial + ((size_t)(L0 + j) * nblk + k) * kNPB;
+    const Acc q = {p[0], p[2], p[4], p[5], p[6], p[7], p[8], __float_as_int(p[1]), __float_as_int(p[3])};
+    acc_merge(a, q);
+#pragma unroll
+    for (int r = 0; r < kNC; ++r) {
+      const float x = p[kNP + 2 * r], y = p[kNP + 2 * (kNC + r)];
+      if (x > kNegInf) top_insert(tv, ti, x, __float_as_int(p[kNP + 2 * r + 1]));
+      if (y > kNegInf) top_insert(sv, si, y, __float_as_int(p[kNP + 2 * (kNC + r) + 1]));
+    }
+  }
+  sh[j][lane] = a;
+  wave_top(tv, ti, lane, lv[j][0], li[j][0]);
+  wave_top(sv, si, lane, lv[j][1], li[j][1]);
+  __syncthreads();
+  // 2
+  if (lane == 0) {
+    for (int i = 1; i < 64; ++i) acc_merge(a, sh[j][i]);
+    const float lse_all = a.m_all + logf(a.s_all);
+    const float lse_ts = a.max_ts > kNegInf ? a.max_ts + logf(a.s_ts) : kNegInf;
+    const bool ts_only = lse_ts > a.max_text;
+    const float lse = ts_only ? lse_ts : lse_all, sum = old[j].sum;
+    int n = 0, pt = ts_only ? nc : 0, ps = 0;
+    while (sum > kNegInf && n < nc) {
+      const float x = pt < nc ? lv[j][0][pt] : kNegInf, y = ps < nc ? lv[j][1][ps] : kNegInf;
+      if (!(x > kNegInf) && !(y > kNegInf)) break;
+      const bool text = x >= y;  // a text id is below every timestamp id
+      const float v = text ? x : y;
+      ct[j][n] = text ? li[j][0][pt] : li[j][1][ps];
+      cs[j][n] = sum + (v - lse);
+      if (text) ++pt;
+      else ++ps;
+      ++n;
+    }
+    cn[j] = n;
+    head[j] = 0;
+  }
+  __syncthreads();
+  // 3
+  if (tid == 0) {
+    const int was = complete[b];
+    int nl = 0, nf = 0;
+    fc_old = fin_count[b];
+    while (!was && nl < W) {
+      int best = -1;
+      float bs = kNegInf;
+      for (int q = 0; q < W; ++q)
+        if (head[q] < cn[q] && (best < 0 || cs[q][head[q]] > bs)) best = q, bs = cs[q][head[q]];
+      if (best < 0) break;
+      const int t = ct[best][head[best]];
+      head[best] += 1;
+      if (t == c.eot) {
+        // a slot lists EOT at most once, so at most W <= kMaxBeam EOT candidates are walked: the guard never drops one
+        if (nf < kMaxBeam) f_src[nf] = best, f_sum[nf] = bs, ++nf;
+      } else {
+        n_src[nl] = best, n_tok[nl] = t, n_sum[nl] = bs, ++nl;
+      }
+    }
+    n_live = nl, n_fin = nf, carry = was;
+    fc_new = was ? fc_old : (fc_old + nf < C ? fc_old + nf : C);
+  }
+  __syncthreads();
+  // 4
+  const int nl = n_live, cy = carry;
+  if (tid < W) {
+    const bool live = !cy && tid < nl;
+    const int src = live ? n_src[tid] : tid;
+    if (!cy) {
+      LaneState ns = old[src];
+      if (live) {
+        ns.penult = ns.last;
+        ns.last = n_tok[tid];
+        if (n_tok[tid] >= c.tb) ns.last_ts = n_tok[tid];
+        ns.n += 1;
+        ns.sum = n_sum[tid];
+        ns.done = 0;
+      } else {
+        ns.sum = kNegInf;
+        ns.done = 1;
+      }
+      st[L0 + tid] = ns;
+    }
+    cur_tok[L0 + tid] = live ? n_tok[tid] : c.eot;
+    if (out_src) {
+      out_src[L0 + tid] = live ? src : -1;
+      out_tok[L0 + tid] = live ? n_tok[tid] : c.eot;
+      out_sum[L0 + tid] = live ? n_sum[tid] : kNegInf;
+      out_fsrc[L0 + tid] = tid < n_fin ? f_src[tid] : -1;
+      out_fsum[L0 + tid] = tid < n_fin ? f_sum[tid] : kNegInf;
+    }
+  }
+  const int nt = 64 * W;
+  if (anc) {
+    for (int e = tid; e < W * (s + 1); e += nt) {
+      const int q = e / (s + 1), t = e % (s + 1);
+      const int src = (!cy && q < nl) ? n_src[q] : q;
+      anc_next[(size_t)(L0 + q) * anc_ld + t] = anc[(size_t)(L0 + src) * anc_ld + t];
+    }
+  }
+  if (hist) {
+    for (int e = tid; e < W * (idx + 1); e += nt) {
+      const int q = e / (idx + 1), t = e % (idx + 1);
+      const bool live = !cy && q < nl;
+      const int src = live ? n_src[q] : q;
+      hist_next[(size_t)(L0 + q) * hist_ld + t] = (t == idx && live) ? n_tok[q] : hist[(size_t)(L0 + src) * hist_ld + t];
+    }
+    const int add = fc_new - fc_old;  // finished records: the history of the source slot, its score, its length
+    for (int e = tid; e < add * (idx + 1); e += nt) {
+      const int q = e / (idx + 1), t = e % (idx + 1);
+      const size_t row = (size_t)b * kMaxFinish + fc_old + q;
+      if (t < idx) fin_tok[row * hist_ld + t] = hist[(size_t)(L0 + f_src[q]) * hist_ld + t];
+      else fin_sum[row] = f_sum[q], fin_n[row] = idx;
+    }
+  }
+  if (tid == 0) {
+    if (!cy) {
+      fin_count[b] = fc_new;
+      complete[b] = (fc_new >= C || nl == 0) ? 1 : 0;
+    }
+    if (out_nlive) out_nlive[b] = cy ? 0 : nl, out_nfin[b] = n_fin;
+  }
+}
+
 // ---- the model ------------------------------------------------------------------------------------------------------------
 enum { T_F16 = 0, T_F32 = 1, T_CONV = 2 };
 
@@ -556,6 +800,13 @@ struct eioku_whisper {
   float *dx = nullptr, *partial = nullptr, *info = nullptr, *nsp = nullptr, *d_logprob = nullptr;
   LaneState* state = nullptr;
   int *tokens = nullptr, *cur_tok = nullptr, *lang_out = nullptr, *d_ids = nullptr;
+  // beam search: lanes = windows * beam; ancestry table and token history double-buffered; finished records per window
+  int dcap = 0;  // capacity of the decoder workspace in lanes (>= cap)
+  int beam_lanes = 0, beam_windows = 0;  // capacity of the beam buffers (0 until the first beam call)
+  float *bpartial = nullptr, *fin_sum = nullptr, *b_sum = nullptr, *b_fsum = nullptr;
+  uint8_t* anc[2] = {nullptr, nullptr};
+  int *hist[2] = {nullptr, nullptr}, *fin_tok = nullptr, *fin_n = nullptr, *fin_count = nullptr, *complete = nullptr;
+  int *b_src = nullptr, *b_tok = nullptr, *b_fsrc = nullptr, *b_nlive = nullptr, *b_nfin = nullptr, *tr_src = nullptr, *tr_tok = nullptr;
   double flops = 0;
   int launches = 0, steps = 0;
 
@@ -605,21 +856,90 @@ int ln(eioku_whisper* m, const float* x, int M, int d, int g, int b, h16* out) {
 
 template <int QPW>
 int attn(eioku_whisper* m, const h16* Q, long long q_bs, int q_rs, const h16* K, const h16* V, long long kv_bs, int kv_rs, int n_q,
-         int n_keys, int B, h16* O, long long o_bs, int o_rs) {
+         int n_keys, int B, h16* O, long long o_bs, int o_rs, int kv_div = 1, const uint8_t* anc = nullptr, int anc_ld = 0) {
   const size_t lds = (size_t)4 * QPW * (n_keys + 64) * sizeof(float);
   EIOKU_REQUIRE(lds <= 64 * 1024, "attention over %d keys needs %zu bytes of LDS", n_keys, lds);
   const dim3 grid((n_q + 4 * QPW - 1) / (4 * QPW), m->cfg.heads, B);
-  hipLaunchKernelGGL((k_attn<QPW>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs, o_rs);
+  if (anc)
+    hipLaunchKernelGGL((k_attn<QPW, true>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs, o_rs,
+                       kv_div, anc, anc_ld);
+  else
+    hipLaunchKernelGGL((k_attn<QPW, false>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs, o_rs,
+                       kv_div, (const uint8_t*)nullptr, 0);
   EIOKU_LAUNCH_CHECK();
   m->flops += 4.0 * B * m->cfg.heads * (double)n_q * n_keys * 64;
   m->launches += 1;
   return EIOKU_OK;
 }
 
-int ensure_capacity(eioku_whisper* m, int B) {
-  if (B <= m->cap) return EIOKU_OK;
+// the decoder workspace for L lanes (greedy: one lane per window; beam search: beam lanes per window).  Growing it keeps
+// the encoder's results.
+int ensure_lanes(eioku_whisper* m, int L) {
+  if (L <= m->dcap) return EIOKU_OK;
   const auto& c = m->cfg;
-  const size_t T2 = 2 * (size_t)c.max_source_positions, ctx = c.max_source_positions, d = c.d_model, Tm = c.max_target_positions;
+  const size_t d = c.d_model, Tm = c.max_target_positions, ffn = c.dec_ffn, B = (size_t)L;
+  m->dcap = 0;
+  W_TRY(dalloc(&m->dx, B * d));
+  W_TRY(dalloc(&m->dh, B * d));
+  W_TRY(dalloc(&m->dq, B * d));
+  W_TRY(dalloc(&m->da, B * d));
+  W_TRY(dalloc(&m->dmid, B * ffn));
+  W_TRY(dalloc(&m->selfK, c.dec_layers * B * Tm * d));
+  W_TRY(dalloc(&m->selfV, c.dec_layers * B * Tm * d));
+  W_TRY(dalloc(&m->partial, B * m->nblk * kNP));
+  W_TRY(dalloc(&m->info, B * (1 + m->nlang)));
+  W_TRY(dalloc(&m->nsp, B));
+  W_TRY(dalloc(&m->d_logprob, B));
+  W_TRY(dalloc(&m->state, B));
+  W_TRY(dalloc(&m->tokens, B * Tm));
+  W_TRY(dalloc(&m->cur_tok, B));
+  W_TRY(dalloc(&m->lang_out, B));
+  W_TRY(dalloc(&m->d_ids, B * Tm));
+  m->dcap = L;
+  return EIOKU_OK;
+}
+
+// beam search only: the decoder workspace for L lanes and the beam buffers for L lanes / B windows, made on the first beam
+// call and grown as needed
+int ensure_beam(eioku_whisper* m, int B, int L) {
+  W_TRY(ensure_lanes(m, L));
+  const size_t Tm = m->cfg.max_target_positions;
+  if (L > m->beam_lanes) {
+    const size_t n = (size_t)L;
+    m->beam_lanes = 0;
+    W_TRY(dalloc(&m->bpartial, n * m->nblk * kNPB));
+    for (int i = 0; i < 2; ++i) {
+      W_TRY(dalloc(&m->anc[i], n * Tm));
+      W_TRY(dalloc(&m->hist[i], n * Tm));
+    }
+    W_TRY(dalloc(&m->b_src, n));
+    W_TRY(dalloc(&m->b_tok, n));
+    W_TRY(dalloc(&m->b_sum, n));
+    W_TRY(dalloc(&m->b_fsrc, n));
+    W_TRY(dalloc(&m->b_fsum, n));
+    W_TRY(dalloc(&m->tr_src, n * Tm));
+    W_TRY(dalloc(&m->tr_tok, n * Tm));
+    m->beam_lanes = L;
+  }
+  if (B > m->beam_windows) {
+    const size_t n = (size_t)B;
+    m->beam_windows = 0;
+    W_TRY(dalloc(&m->fin_tok, n * kMaxFinish * Tm));
+    W_TRY(dalloc(&m->fin_sum, n * kMaxFinish));
+    W_TRY(dalloc(&m->fin_n, n * kMaxFinish));
+    W_TRY(dalloc(&m->fin_count, n));
+    W_TRY(dalloc(&m->complete, n));
+    W_TRY(dalloc(&m->b_nlive, n));
+    W_TRY(dalloc(&m->b_nfin, n));
+    m->beam_windows = B;
+  }
+  return EIOKU_OK;
+}
+
+int ensure_capacity(eioku_whisper* m, int B) {
+  if (B <= m->cap) return ensure_lanes(m, B);
+  const auto& c = m->cfg;
+  const size_t T2 = 2 * (size_t)c.max_source_positions, ctx = c.max_source_positions, d = c.d_model;
   const size_t ffn = c.enc_ffn > c.dec_ffn ? c.enc_ffn : c.dec_ffn;
   m->cap = 0;
   W_TRY(dalloc(&m->d_off, (size_t)B));
@@ -639,25 +959,9 @@ int ensure_capacity(eioku_whisper* m, int B) {
   W_TRY(dalloc(&m->enc_out, B * ctx * d));
   W_TRY(dalloc(&m->crossK, c.dec_layers * B * ctx * d));
   W_TRY(dalloc(&m->crossV, c.dec_layers * B * ctx * d));
-  W_TRY(dalloc(&m->dx, B * d));
-  W_TRY(dalloc(&m->dh, B * d));
-  W_TRY(dalloc(&m->dq, B * d));
-  W_TRY(dalloc(&m->da, B * d));
-  W_TRY(dalloc(&m->dmid, B * ffn));
-  W_TRY(dalloc(&m->selfK, c.dec_layers * B * Tm * d));
-  W_TRY(dalloc(&m->selfV, c.dec_layers * B * Tm * d));
-  W_TRY(dalloc(&m->partial, (size_t)B * m->nblk * kNP));
-  W_TRY(dalloc(&m->info, (size_t)B * (1 + m->nlang)));
-  W_TRY(dalloc(&m->nsp, (size_t)B));
-  W_TRY(dalloc(&m->d_logprob, (size_t)B));
-  W_TRY(dalloc(&m->state, (size_t)B));
-  W_TRY(dalloc(&m->tokens, B * Tm));
-  W_TRY(dalloc(&m->cur_tok, (size_t)B));
-  W_TRY(dalloc(&m->lang_out, (size_t)B));
-  W_TRY(dalloc(&m->d_ids, B * Tm));
   m->cap = B;
   m->enc_B = 0;
-  return EIOKU_OK;
+  return ensure_lanes(m, B);
 }
 
 int check_weights(const eioku_whisper* m) {
@@ -665,8 +969,10 @@ int check_weights(const eioku_whisper* m) {
   return EIOKU_OK;
 }
 
-// one decoder position s for B lanes: embedding -> layers -> final LayerNorm into m->dh
-int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, int uniform) {
+// one decoder position s for B lanes: embedding -> layers -> final LayerNorm into m->dh.  Beam search: kv_div lanes share a
+// window's cross-attention K / V, and self-attention reads key t of a lane from the lane anc[lane][t].
+int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, int uniform, int kv_div = 1,
+                 const uint8_t* anc = nullptr) {
   const auto& c = m->cfg;
   const int d = c.d_model, ctx = c.max_source_positions, Tm = c.max_target_positions;
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, 0, toks, tstride, uniform, c.vocab, d, s, m->H(m->emb), m->F(m->dec_pos), m->dx);
@@ -674,19 +980,19 @@ int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, i
   m->launches += 1;
   for (int l = 0; l < c.dec_layers; ++l) {
     const Layer& L = m->dec[l];
-    h16* sk = m->selfK + (size_t)l * m->cap * Tm * d;
-    h16* sv = m->selfV + (size_t)l * m->cap * Tm * d;
+    h16* sk = m->selfK + (size_t)l * m->dcap * Tm * d;
+    h16* sv = m->selfV + (size_t)l * m->dcap * Tm * d;
     const h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
     const h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
     W_TRY(ln(m, m->dx, B, d, L.self.ln_g, L.self.ln_b, m->dh));
     W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.q), d, m->F(L.self.qb), B, d, d, m->dq, d)));
     W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.k), d, nullptr, B, d, d, sk + (size_t)s * d, (long long)Tm * d)));
     W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.v), d, m->F(L.self.vb), B, d, d, sv + (size_t)s * d, (long long)Tm * d)));
-    W_TRY((attn<1>(m, m->dq, d, d, sk, sv, (long long)Tm * d, d, 1, s + 1, B, m->da, d, d)));
+    W_TRY((attn<1>(m, m->dq, d, d, sk, sv, (long long)Tm * d, d, 1, s + 1, B, m->da, d, d, 1, anc, Tm)));
     W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.self.o), d, m->F(L.self.ob), B, d, d, m->dx, d)));
     W_TRY(ln(m, m->dx, B, d, L.cross.ln_g, L.cross.ln_b, m->dh));
     W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.cross.q), d, m->F(L.cross.qb), B, d, d, m->dq, d)));
-    W_TRY((attn<1>(m, m->dq, d, d, ck, cv, (long long)ctx * d, d, 1, ctx, B, m->da, d, d)));
+    W_TRY((attn<1>(m, m->dq, d, d, ck, cv, (long long)ctx * d, d, 1, ctx, B, m->da, d, d, kv_div)));
     W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.cross.o), d, m->F(L.cross.ob), B, d, d, m->dx, d)));
     W_TRY(ln(m, m->dx, B, d, L.ln_g, L.ln_b, m->dh));
     W_TRY((gemm<1, EPI_GELU_F16>(m, m->dh, d, m->H(L.fc1), d, m->F(L.fc1b), B, c.dec_ffn, d, m->dmid, c.dec_ffn)));
@@ -697,11 +1003,31 @@ int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, i
 
 int logits(eioku_whisper* m, int B, int rules, float* raw_out, long long raw_ld, bool info) {
   hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, B, m->sel,
-                     m->flags, m->state, rules, m->partial, m->nblk, raw_out, raw_ld, nullptr, info ? m->info : nullptr, m->nlang);
+                     m->flags, m->state, rules, m->partial, m->nblk, raw_out, raw_ld, nullptr, info ? m->info : nullptr, m->nlang, 0);
   EIOKU_LAUNCH_CHECK();
   m->flops += 2.0 * B * m->cfg.vocab * m->cfg.d_model;
   m->launches += 1;
   return EIOKU_OK;
+}
+
+// beam search: masked logits of L lanes into the beam partials (the block's nc best text and timestamp ids included)
+int logits_beam(eioku_whisper* m, int L, int nc) {
+  hipLaunchKernelGGL((k_logits<false, true>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, L, m->sel,
+                     m->flags, m->state, 1, m->bpartial, m->nblk, nullptr, 0LL, nullptr, nullptr, m->nlang, nc);
+  EIOKU_LAUNCH_CHECK();
+  m->flops += 2.0 * L * m->cfg.vocab * m->cfg.d_model;
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+LaneState state_of_prefix(const int32_t* prefix, int n, int tb) {
+  LaneState s{n, -1, -1, -1, 0, 0.f};
+  for (int i = 0; i < n; ++i) {
+    s.penult = s.last;
+    s.last = prefix[i];
+    if (prefix[i] >= tb) s.last_ts = prefix[i];
+  }
+  return s;
 }
 
 }  // namespace
@@ -836,7 +1162,9 @@ void eioku_whisper_destroy(eioku_whisper* m) {
   void* bufs[] = {m->hann, m->tw_cos, m->tw_sin, m->filt, m->flags, m->lang_ids, m->samples, m->d_off, m->mel64, m->mel_mx, m->mel32,
                   m->col1, m->h1, m->col2, m->eh, m->eq, m->ek, m->ev, m->ea, m->emid, m->enc_out, m->crossK, m->crossV, m->ex,
                   m->dh, m->dq, m->da, m->dmid, m->selfK, m->selfV, m->dx, m->partial, m->info, m->nsp, m->d_logprob, m->state,
-                  m->tokens, m->cur_tok, m->lang_out, m->d_ids};
+                  m->tokens, m->cur_tok, m->lang_out, m->d_ids, m->bpartial, m->fin_sum, m->b_sum, m->b_fsum, m->anc[0], m->anc[1],
+                  m->hist[0], m->hist[1], m->fin_tok, m->fin_n, m->fin_count, m->complete, m->b_src, m->b_tok, m->b_fsrc,
+                  m->b_nlive, m->b_nfin, m->tr_src, m->tr_tok};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete m;
@@ -1057,14 +1385,7 @@ int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const 
   for (int b = 0; b < B; ++b) {
     const int n = prefix_len[b];
     EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
-    LaneState s{n, -1, -1, -1, 0, 0.f};
-    for (int i = 0; i < n; ++i) {
-      const int t = prefix[(size_t)b * prefix_cap + i];
-      s.penult = s.last;
-      s.last = t;
-      if (t >= m->cfg.timestamp_begin) s.last_ts = t;
-    }
-    st[b] = s;
+    st[b] = state_of_prefix(n ? prefix + (size_t)b * prefix_cap : nullptr, n, m->cfg.timestamp_begin);
   }
   EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
   float *d_in = nullptr, *d_msk = nullptr;
@@ -1073,7 +1394,7 @@ int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const 
   hipError_t e = rc == EIOKU_OK ? hipMemcpy(d_in, logits_in, (size_t)B * V * sizeof(float), hipMemcpyHostToDevice) : hipSuccess;
   if (rc == EIOKU_OK && e == hipSuccess) {
     hipLaunchKernelGGL((k_logits<true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in, B, m->sel,
-                       m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, d_msk, (float*)nullptr, m->nlang);
+                       m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, d_msk, (float*)nullptr, m->nlang, 0);
     hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, 0, 0, m->info, m->nlang,
                        m->lang_ids, (int*)nullptr, 0, m->cur_tok, m->nsp, m->lang_out, m->d_logprob);
     e = hipGetLastError();
@@ -1084,6 +1405,193 @@ int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const 
   (void)hipFree(d_in);
   if (d_msk) (void)hipFree(d_msk);
   W_TRY(rc);
+  EIOKU_HIP_CHECK(e);
+  return EIOKU_OK;
+}
+
+namespace {
+
+int beam_args(const eioku_whisper* m, int B, int W, int C) {
+  EIOKU_REQUIRE(W >= 1 && W <= kMaxBeam, "beam size %d outside 1..%d", W, kMaxBeam);
+  EIOKU_REQUIRE(C >= 1 && C <= kMaxFinish, "%d finished hypotheses outside 1..%d (round(beam * patience))", C, kMaxFinish);
+  EIOKU_REQUIRE(B > 0 && B * W <= 64, "%d windows x beam %d = %d lanes: at most 64 lanes decode in lockstep", B, W, B * W);
+  return EIOKU_OK;
+}
+
+void launch_beam_select(eioku_whisper* m, int B, int W, int C, int s, int idx, const uint8_t* anc, uint8_t* anc_next,
+                        const int* hist, int* hist_next, int* out_src, int* out_tok) {
+  const int Tm = m->cfg.max_target_positions;  // out_src / out_tok NULL: no per-slot outputs
+  hipLaunchKernelGGL(k_beam_select, dim3(B), dim3(64 * W), 0, 0, m->bpartial, m->nblk, m->sel, W, C, s, idx, m->state, m->cur_tok, anc,
+                     anc_next, Tm, hist, hist_next, Tm, m->fin_tok, m->fin_sum, m->fin_n, m->fin_count, m->complete, out_src, out_tok,
+                     m->b_sum, out_src ? m->b_nlive : nullptr, m->b_fsrc, m->b_fsum, m->b_nfin);
+  m->launches += 1;
+}
+
+}  // namespace
+
+int eioku_whisper_decode_beam(eioku_whisper* m, const int32_t* prompt, int prompt_len, int B, int W, int C, int max_new,
+                              int sync_every, int32_t* tokens_out, int32_t* n_out, int32_t* ended_out, float* sum_logprob,
+                              int32_t* n_hyp, int32_t* best_out, float* no_speech_prob, int32_t* lang_out, int32_t* trace_src,
+                              int32_t* trace_tok) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && prompt && prompt_len >= 1 && max_new >= 1, "bad argument");
+  W_TRY(beam_args(m, B, W, C));
+  EIOKU_REQUIRE(B == m->enc_B, "beam decode of %d windows needs an encode of the same %d windows first", B, m->enc_B);
+  EIOKU_REQUIRE(prompt_len + max_new <= m->cfg.max_target_positions, "prompt %d + %d new tokens exceed max_target_positions %d",
+                prompt_len, max_new, m->cfg.max_target_positions);
+  EIOKU_REQUIRE(tokens_out && n_out && ended_out && sum_logprob && n_hyp && best_out, "NULL output");
+  for (int i = 0; i < prompt_len; ++i) EIOKU_REQUIRE(prompt[i] >= 0 && prompt[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompt[i]);
+  if (sync_every < 1) sync_every = 1;
+  const int L = B * W, Tm = m->cfg.max_target_positions, eot = m->cfg.eot, H = W > C ? W : C;
+  W_TRY(ensure_beam(m, B, L));
+  m->flops = 0;
+  m->launches = 0;
+  m->steps = 0;
+  // slot 0 of every window is live with sum 0, the others are dead; every ancestry row names its own lane
+  std::vector<LaneState> st(L, LaneState{0, -1, -1, -1, 1, kNegInf});
+  for (int b = 0; b < B; ++b) st[(size_t)b * W] = LaneState{0, -1, -1, -1, 0, 0.f};
+  std::vector<uint8_t> ident((size_t)L * Tm);
+  for (int l = 0; l < L; ++l)
+    for (int t = 0; t < Tm; ++t) ident[(size_t)l * Tm + t] = (uint8_t)l;
+  std::vector<int> fill((size_t)L * Tm, eot), zeros(B, 0);
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
+  for (int i = 0; i < 2; ++i) {
+    EIOKU_HIP_CHECK(hipMemcpy(m->anc[i], ident.data(), ident.size(), hipMemcpyHostToDevice));
+    EIOKU_HIP_CHECK(hipMemcpy(m->hist[i], fill.data(), fill.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(m->fin_count, zeros.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->complete, zeros.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  const bool trace = trace_src && trace_tok;
+  if (trace) {
+    EIOKU_HIP_CHECK(hipMemset(m->tr_src, 0xFF, (size_t)L * Tm * sizeof(int)));
+    EIOKU_HIP_CHECK(hipMemset(m->tr_tok, 0xFF, (size_t)L * Tm * sizeof(int)));
+  }
+  int cur = 0;
+  const int last_step = prompt_len - 1 + max_new - 1;
+  std::vector<int> flags(B);
+  for (int s = 0; s <= last_step; ++s) {
+    const bool forced = s < prompt_len;
+    W_TRY(decoder_step(m, L, s, forced ? nullptr : m->cur_tok, 1, forced ? prompt[s] : 0, W, m->anc[cur]));
+    m->steps += 1;
+    const int idx = s - (prompt_len - 1);
+    if (s == 0) {  // no-speech probability and language from the unmasked logits of prompt position 0
+      W_TRY(logits(m, L, 0, nullptr, 0, true));
+      hipLaunchKernelGGL(k_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, 0, 1, m->info, m->nlang,
+                         m->lang_ids, (int*)nullptr, 0, (int*)nullptr, m->nsp, m->lang_out, (float*)nullptr);
+      EIOKU_LAUNCH_CHECK();
+      m->launches += 1;
+    }
+    if (idx < 0) continue;
+    W_TRY(logits_beam(m, L, W + 1));
+    launch_beam_select(m, B, W, C, s, idx, m->anc[cur], m->anc[cur ^ 1], m->hist[cur], m->hist[cur ^ 1],
+                       trace ? m->tr_src + (size_t)idx * L : nullptr, trace ? m->tr_tok + (size_t)idx * L : nullptr);
+    EIOKU_LAUNCH_CHECK();
+    cur ^= 1;
+    if ((idx + 1) % sync_every == 0 && s < last_step) {  // stop once every window is complete
+      EIOKU_HIP_CHECK(hipMemcpy(flags.data(), m->complete, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+      bool all = true;
+      for (int b = 0; b < B; ++b) all = all && flags[b];
+      if (all) break;
+    }
+  }
+  // hypotheses: the finished records, then live slots in slot order while there are fewer than W
+  std::vector<int> hist((size_t)L * Tm), ftok((size_t)B * kMaxFinish * Tm), fn((size_t)B * kMaxFinish), fc(B);
+  std::vector<float> fsum((size_t)B * kMaxFinish), nsp(L);
+  std::vector<int> lang(L);
+  EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(hist.data(), m->hist[cur], hist.size() * sizeof(int), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(ftok.data(), m->fin_tok, ftok.size() * sizeof(int), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(fn.data(), m->fin_n, fn.size() * sizeof(int), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(fsum.data(), m->fin_sum, fsum.size() * sizeof(float), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(fc.data(), m->fin_count, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(nsp.data(), m->nsp, (size_t)L * sizeof(float), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(lang.data(), m->lang_out, (size_t)L * sizeof(int), hipMemcpyDeviceToHost));
+  if (trace) {
+    EIOKU_HIP_CHECK(hipMemcpy(trace_src, m->tr_src, (size_t)max_new * L * sizeof(int), hipMemcpyDeviceToHost));
+    EIOKU_HIP_CHECK(hipMemcpy(trace_tok, m->tr_tok, (size_t)max_new * L * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  for (int b = 0; b < B; ++b) {
+    int rows = 0, best = 0;
+    double best_score = 0;
+    auto put = [&](const int* toks, int n_text, bool ended, float sum) {
+      const size_t row = (size_t)b * H + rows;
+      int32_t* out = tokens_out + row * max_new;
+      for (int t = 0; t < max_new; ++t) out[t] = t < n_text ? toks[t] : eot;
+      n_out[row] = n_text + (ended ? 1 : 0);
+      ended_out[row] = ended ? 1 : 0;
+      sum_logprob[row] = sum;
+      const double score = (double)sum / (n_text > 1 ? n_text : 1);
+      if (rows == 0 || score > best_score) best = rows, best_score = score;
+      ++rows;
+    };
+    const int nfin = fc[b] < C ? fc[b] : C;
+    for (int i = 0; i < nfin && rows < H; ++i) {
+      const size_t r = (size_t)b * kMaxFinish + i;
+      const int n_text = fn[r] < max_new ? fn[r] : max_new;
+      put(ftok.data() + r * Tm, n_text, true, fsum[r]);
+    }
+    for (int j = 0; j < W && rows < W; ++j) {
+      const LaneState& ls = st[(size_t)b * W + j];
+      if (!(ls.sum > kNegInf)) continue;
+      put(hist.data() + ((size_t)b * W + j) * Tm, ls.n < max_new ? ls.n : max_new, false, ls.sum);
+    }
+    n_hyp[b] = rows;
+    best_out[b] = best;
+    for (; rows < H; ++rows) {
+      const size_t row = (size_t)b * H + rows;
+      for (int t = 0; t < max_new; ++t) tokens_out[row * max_new + t] = eot;
+      n_out[row] = 0, ended_out[row] = 0, sum_logprob[row] = kNegInf;
+    }
+    if (no_speech_prob) no_speech_prob[b] = nsp[(size_t)b * W];
+    if (lang_out) lang_out[b] = lang[(size_t)b * W];
+  }
+  return EIOKU_OK;
+}
+
+int eioku_whisper_beam_select(eioku_whisper* m, const float* logits_in, int B, int W, int C, const int32_t* prefix, int prefix_cap,
+                              const int32_t* prefix_len, const float* sums, const int32_t* fin_count, int32_t* src_out,
+                              int32_t* tok_out, float* sum_out, int32_t* n_live, int32_t* fsrc_out, float* fsum_out,
+                              int32_t* n_fin, int32_t* fin_count_out, int32_t* complete_out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && logits_in && prefix_len && sums && fin_count && prefix_cap >= 0, "bad argument");
+  EIOKU_REQUIRE(src_out && tok_out && sum_out && n_live && fsrc_out && fsum_out && n_fin && fin_count_out && complete_out, "NULL output");
+  W_TRY(beam_args(m, B, W, C));
+  const int L = B * W, V = m->cfg.vocab;
+  W_TRY(ensure_beam(m, B, L));
+  std::vector<LaneState> st(L);
+  for (int l = 0; l < L; ++l) {
+    const int n = prefix_len[l];
+    EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
+    st[l] = state_of_prefix(n ? prefix + (size_t)l * prefix_cap : nullptr, n, m->cfg.timestamp_begin);
+    st[l].sum = sums[l];
+    st[l].done = sums[l] > kNegInf ? 0 : 1;
+  }
+  std::vector<int> zeros(B, 0);
+  for (int b = 0; b < B; ++b) EIOKU_REQUIRE(fin_count[b] >= 0 && fin_count[b] < C, "finished count %d outside 0..%d", fin_count[b], C - 1);
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->fin_count, fin_count, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->complete, zeros.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  float* d_in = nullptr;
+  W_TRY(dalloc(&d_in, (size_t)L * V));
+  hipError_t e = hipMemcpy(d_in, logits_in, (size_t)L * V * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL((k_logits<true, true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in, L,
+                       m->sel, m->flags, m->state, 1, m->bpartial, m->nblk, (float*)nullptr, 0LL, (float*)nullptr, (float*)nullptr,
+                       m->nlang, W + 1);
+    launch_beam_select(m, B, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, m->b_src, m->b_tok);
+    e = hipGetLastError();
+    const size_t li = (size_t)L * sizeof(int), bi = (size_t)B * sizeof(int);
+    if (e == hipSuccess) e = hipMemcpy(src_out, m->b_src, li, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(tok_out, m->b_tok, li, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(sum_out, m->b_sum, (size_t)L * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(fsrc_out, m->b_fsrc, li, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(fsum_out, m->b_fsum, (size_t)L * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_live, m->b_nlive, bi, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(n_fin, m->b_nfin, bi, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(fin_count_out, m->fin_count, bi, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(complete_out, m->complete, bi, hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d_in);
   EIOKU_HIP_CHECK(e);
   return EIOKU_OK;
 }

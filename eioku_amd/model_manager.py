@@ -165,7 +165,8 @@ class ModelManager:
         ``readtext_batch(frames) -> per frame [(box, text, confidence)]``.  ``gpu_transcription=True`` enables
         ``transcribe_video`` on the HIP path (Whisper, ``eioku_amd.transcribe``); ``audio_source(path) -> (float32 mono
         samples, sample_rate)`` and ``transcriber_factory(cache_dir, model_name) -> object with transcribe(samples, language,
-        window_mode=, batch_windows=)`` are its seams."""
+        window_mode=, batch_windows=)`` are its seams (``beam_size=`` / ``patience=`` follow only when the task's config sets
+        them)."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -229,8 +230,9 @@ class ModelManager:
     async def transcribe_video(self, video_path: str, config: dict) -> dict:
         """Whisper on the HIP path when the manager was built with ``gpu_transcription=True`` (reference: :406-467, which
         calls faster-whisper on the CPU); otherwise refused as before.  Result: ``{"segments": [{start_ms, end_ms, text,
-        language, confidence: None, words: None}]}``.  Greedy decoding; the deviations from the reference's call are listed
-        in INTEGRATION.md §3."""
+        language, confidence: None, words: None}]}``.  Greedy decoding by default; config ``beam_size`` (1..8; 5 is the
+        reference's call) and ``patience`` switch to beam search, values outside their ranges raise ``ValueError``.  The
+        deviations from the reference's call are listed in INTEGRATION.md §3."""
         if not self._gpu_transcription:
             raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")
         try:

@@ -1,13 +1,14 @@
-"""Transcription on the HIP path: Whisper log-mel (K19) and greedy decode with timestamp rules (K20).
+"""Transcription on the HIP path: Whisper log-mel (K19), greedy decode with timestamp rules (K20) and beam search (K20b).
 
 The reference calls ``faster_whisper.WhisperModel.transcribe`` (``model_manager.py:406-467``), which has no ROCm backend.
 This module keeps its result dict and replaces the arithmetic: the audio goes up once, ``csrc/whisper.hip`` computes the
 log-mel windows, the encoder, and the decoder steps with token selection on the device; the host only cuts the token
 lists into segments (Whisper's seek rule) and turns ids into text (byte-level BPE from ``vocab.json``).
 
-Deviations from the reference's call are listed in INTEGRATION.md §3: greedy instead of ``beam_size=5``, no temperature
-fallback, no compression-ratio check, no conditioning on previous text, ``vad_filter`` accepted but not applied, integer
-millisecond times.  There is no CPU fallback: without the library or a gfx950 device every compute call raises.
+Deviations from the reference's call are listed in INTEGRATION.md §3: greedy by default (``beam_size: 5`` restores the
+reference's beam search), no temperature fallback, no compression-ratio check, no conditioning on previous text,
+``vad_filter`` accepted but not applied, integer millisecond times.  There is no CPU fallback: without the library or a
+gfx950 device every compute call raises.
 """
 
 from __future__ import annotations
@@ -31,6 +32,28 @@ MS_PER_FRAME = 10
 MS_PER_TIMESTAMP = 20     # one timestamp id = two mel frames
 NO_SPEECH_THRESHOLD = 0.6
 LOGPROB_THRESHOLD = -1.0
+MAX_BEAM = 8              # beam slots per window on the device
+MAX_LANES = 64            # windows x beam decoded in lockstep
+MAX_FINISH = 16           # finished hypotheses a window can keep (round(beam x patience))
+
+
+def finish_count(beam_size: int, patience: float) -> int:
+    """Whisper's ``max_candidates``: the number of finished hypotheses that ends a window's beam search."""
+    return max(1, round(beam_size * patience))
+
+
+def check_beam(beam_size, patience) -> tuple[int, float]:
+    """-> (beam_size, patience) or ``ValueError``: the beam is 1..8, patience positive with at most 16 finished hypotheses."""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(beam_size) or int(beam_size) != beam_size or not 1 <= int(beam_size) <= MAX_BEAM:
+        raise ValueError(f"beam_size must be an integer in 1..{MAX_BEAM}, got {beam_size!r}")
+    if isinstance(patience, bool) or not isinstance(patience, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(patience) or not patience > 0:
+        raise ValueError(f"patience must be a positive number, got {patience!r}")
+    patience = float(patience)
+    if finish_count(int(beam_size), patience) > MAX_FINISH:
+        raise ValueError(f"beam_size {beam_size} x patience {patience} keeps more than {MAX_FINISH} finished hypotheses")
+    return int(beam_size), patience
 
 
 # ---- audio input ----------------------------------------------------------------------------------------------------------
@@ -361,6 +384,65 @@ class WhisperTranscriber:
             total.ctypes.data, nsp.ctypes.data, lang.ctypes.data), "eioku_whisper_decode")
         return {"tokens": tokens[:, :n], "n": n_out, "sum_logprob": total, "no_speech_prob": nsp, "lang": lang}
 
+    def decode_beam(self, prompt, n_windows: int, max_new_tokens: int, beam_size: int, patience: float = 1.0,
+                    sync_every: int | None = None, trace: bool = False) -> dict:
+        """Beam search over the last encode.  Per window ``H = max(beam_size, C)`` hypothesis rows (``C`` =
+        :func:`finish_count`): the finished hypotheses in the order they finished, then live beams in slot order while
+        there are fewer than ``beam_size``; ``n_hyp`` rows are in use.  ``tokens`` [B][H][max_new] EOT-filled, ``n`` tokens
+        sampled up to and including EOT, ``ended`` whether the row ended on EOT, ``sum_logprob``, ``best`` the row with the
+        largest ``sum_logprob / max(1, tokens before EOT)``.  ``trace=True`` (tests) adds ``trace_src`` / ``trace_tok``
+        [max_new][B][W]: per sampled step the source slot and token of every next slot (-1: none)."""
+        W, patience = check_beam(beam_size, patience)
+        p = np.ascontiguousarray(prompt, dtype=np.int32)
+        B, n, Cn = int(n_windows), int(max_new_tokens), finish_count(W, patience)
+        H = max(W, Cn)
+        tokens = np.zeros((B, H, max(n, 1)), dtype=np.int32)
+        n_out, ended = np.zeros((B, H), dtype=np.int32), np.zeros((B, H), dtype=np.int32)
+        total = np.zeros((B, H), dtype=np.float32)
+        n_hyp, best, lang = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        nsp = np.zeros(B, dtype=np.float32)
+        tr_src, tr_tok = (np.full((max(n, 1), B, W), -1, dtype=np.int32) for _ in range(2))
+        self._lib_mod.check(self.lib.eioku_whisper_decode_beam(
+            self._h, p.ctypes.data, len(p), B, W, Cn, n, int(sync_every or self.sync_every), tokens.ctypes.data, n_out.ctypes.data,
+            ended.ctypes.data, total.ctypes.data, n_hyp.ctypes.data, best.ctypes.data, nsp.ctypes.data, lang.ctypes.data,
+            tr_src.ctypes.data if trace else None, tr_tok.ctypes.data if trace else None), "eioku_whisper_decode_beam")
+        out = {"tokens": tokens, "n": n_out, "ended": ended, "sum_logprob": total, "n_hyp": n_hyp, "best": best,
+               "no_speech_prob": nsp, "lang": lang}
+        if trace:
+            out["trace_src"], out["trace_tok"] = tr_src, tr_tok
+        return out
+
+    def beam_select(self, logits, prefixes, sums, fin_count, beam_size: int, patience: float = 1.0) -> list[dict]:
+        """Debug: one beam step on supplied logits [B * W][vocab].  ``prefixes`` / ``sums`` per lane (window-major; a sum of
+        -inf is a dead slot), ``fin_count`` per window.  Per window: ``live`` [(src, token, sum)], ``finished`` [(src,
+        sum)] in walk order, ``fin_count`` afterwards, ``complete``."""
+        W, patience = check_beam(beam_size, patience)
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        L = logits.shape[0]
+        B, cap = L // W, max(1, max(len(p) for p in prefixes))
+        if B * W != L or len(prefixes) != L or len(sums) != L or len(fin_count) != B:
+            raise ValueError("logits, prefixes and sums are per lane (windows x beam), fin_count per window")
+        pre = np.zeros((L, cap), dtype=np.int32)
+        for i, q in enumerate(prefixes):
+            pre[i, :len(q)] = q
+        plen = np.asarray([len(q) for q in prefixes], dtype=np.int32)
+        sums = np.ascontiguousarray(sums, dtype=np.float32)
+        fc = np.ascontiguousarray(fin_count, dtype=np.int32)
+        src, tok, fsrc = (np.zeros(L, dtype=np.int32) for _ in range(3))
+        osum, fsum = np.zeros(L, dtype=np.float32), np.zeros(L, dtype=np.float32)
+        n_live, n_fin, fc_out, complete = (np.zeros(B, dtype=np.int32) for _ in range(4))
+        self._lib_mod.check(self.lib.eioku_whisper_beam_select(
+            self._h, logits.ctypes.data, B, W, finish_count(W, patience), pre.ctypes.data, cap, plen.ctypes.data, sums.ctypes.data,
+            fc.ctypes.data, src.ctypes.data, tok.ctypes.data, osum.ctypes.data, n_live.ctypes.data, fsrc.ctypes.data,
+            fsum.ctypes.data, n_fin.ctypes.data, fc_out.ctypes.data, complete.ctypes.data), "eioku_whisper_beam_select")
+        out = []
+        for b in range(B):
+            o = b * W
+            out.append({"live": [(int(src[o + i]), int(tok[o + i]), float(osum[o + i])) for i in range(n_live[b])],
+                        "finished": [(int(fsrc[o + i]), float(fsum[o + i])) for i in range(n_fin[b])],
+                        "fin_count": int(fc_out[b]), "complete": bool(complete[b])})
+        return out
+
     def forced_logits(self, ids) -> np.ndarray:
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         out = np.empty(ids.shape + (self.dims["vocab"],), dtype=np.float32)
@@ -411,14 +493,20 @@ class WhisperTranscriber:
         return prompt
 
     def transcribe(self, samples: np.ndarray, language: str | None = None, *, window_mode: str = "seek",
-                   batch_windows: int = 8, max_new_tokens: int | None = None) -> dict:
+                   batch_windows: int = 8, max_new_tokens: int | None = None, beam_size: int = 1,
+                   patience: float = 1.0) -> dict:
         """-> ``{"segments": [{start_ms, end_ms, text, language, confidence: None, words: None}], "language": code}``.
 
         ``window_mode="seek"``: one window at a time, the next one starts where Whisper's seek rule says.
         ``window_mode="fixed"``: independent back-to-back windows, up to ``batch_windows`` decoded in lockstep; a segment
-        cannot span a window edge."""
+        cannot span a window edge.
+
+        ``beam_size=1`` decodes greedily.  ``beam_size > 1`` runs beam search with Whisper's ``patience`` and keeps each
+        window's best hypothesis by length-normalised log-probability (``faster_whisper``'s call: 5 and 1.0); in ``fixed``
+        mode a batch is split so that windows x beam stays within the device's 64 lanes."""
         if window_mode not in ("seek", "fixed"):
             raise ValueError(f"window_mode must be 'seek' or 'fixed', got {window_mode!r}")
+        beam_size, patience = check_beam(beam_size, patience)
         d = self.dims
         samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
         content_frames = len(samples) // HOP
@@ -436,7 +524,12 @@ class WhisperTranscriber:
             self.encode(len(seeks))
             if lang_id is None and d["lang_ids"]:  # language of the first window: argmax over the language ids after SOT
                 lang_id = int(self.decode([d["sot"]], len(seeks), 0)["lang"][0])
-            return self.decode(self._prompt(lang_id), len(seeks), max_new)
+            if beam_size == 1:
+                return self.decode(self._prompt(lang_id), len(seeks), max_new)
+            res = self.decode_beam(self._prompt(lang_id), len(seeks), max_new, beam_size, patience)
+            pick = np.arange(len(seeks)), np.asarray(res["best"])
+            return {"tokens": np.asarray(res["tokens"])[pick], "sum_logprob": np.asarray(res["sum_logprob"])[pick],
+                    "no_speech_prob": res["no_speech_prob"]}
 
         def emit(res: dict, lane: int, seek: int) -> int:
             size = min(self.window_frames, content_frames - seek)
@@ -460,8 +553,11 @@ class WhisperTranscriber:
                 seek += emit(run([seek]), 0, seek)
         else:
             starts = list(range(0, content_frames, self.window_frames))
-            for i in range(0, len(starts), max(1, int(batch_windows))):
-                batch = starts[i:i + max(1, int(batch_windows))]
+            per_batch = max(1, int(batch_windows))
+            if beam_size > 1:
+                per_batch = min(per_batch, MAX_LANES // beam_size)
+            for i in range(0, len(starts), per_batch):
+                batch = starts[i:i + per_batch]
                 res = run(batch)
                 for lane, s in enumerate(batch):
                     emit(res, lane, s)
@@ -477,17 +573,25 @@ def transcribe_result(raw: dict) -> dict:
 
 def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None) -> dict:
     """``ModelManager.transcribe_video`` body.  Config keys consumed: ``languages`` (string or list: the first entry; None =
-    detect), ``vad_filter`` (accepted, not applied), ``window_mode``, ``batch_windows``; ``model_name`` picks the
-    checkpoint in the caller."""
+    detect), ``vad_filter`` (accepted, not applied), ``window_mode``, ``batch_windows``, ``beam_size`` (1..8, default 1 =
+    greedy; 5 is the reference's call) and ``patience`` (positive, default 1.0); ``model_name`` picks the checkpoint in the
+    caller.  ``beam_size`` / ``patience`` are passed to the transcriber only when the config sets them."""
     config = config or {}
     languages = config.get("languages")
     if isinstance(languages, (list, tuple)):
         languages = languages[0] if languages else None
     if config.get("vad_filter"):
         logger.info("vad_filter is accepted but not applied: Silero VAD is not built; the no-speech rule skips silence")
+    beam = {}
+    if "beam_size" in config or "patience" in config:
+        b, pt = check_beam(config.get("beam_size", 1), config.get("patience", 1.0))
+        if "beam_size" in config:
+            beam["beam_size"] = b
+        if "patience" in config:
+            beam["patience"] = pt
     samples, rate = (audio_source or default_audio_source)(path)
     check_rate(rate)
     raw = transcriber.transcribe(np.asarray(samples, dtype=np.float32), languages,
                                  window_mode=config.get("window_mode", "seek"),
-                                 batch_windows=int(config.get("batch_windows", 8)))
+                                 batch_windows=int(config.get("batch_windows", 8)), **beam)
     return transcribe_result(raw)

@@ -572,7 +572,7 @@ int eioku_thumbs_jpeg(eioku_thumbs_t* t, const uint8_t* rgb, int n, int th, int 
 int eioku_thumbs_read(eioku_thumbs_t* t, uint8_t* out, size_t cap, void* stream);
 int eioku_thumbs_last_ms(eioku_thumbs_t* t, double* ms4);
 
-/* ---- transcription: Whisper log-mel front end (K19) and greedy decode (K20), csrc/whisper.hip --------------------------
+/* ---- transcription: Whisper log-mel front end (K19), greedy decode (K20), beam search (K20b), csrc/whisper.hip --------
  * Fills ModelManager.transcribe_video (the reference calls faster_whisper.WhisperModel.transcribe on the CPU).  fp16
  * weights and activations, fp32 accumulation, fp32 residual stream / LayerNorm / softmax; head dimension 64.  All data
  * pointers are HOST pointers, every call is synchronous on the null stream.  Every dimension and every special-token id
@@ -593,6 +593,19 @@ int eioku_thumbs_last_ms(eioku_thumbs_t* t, double* ms4);
  * select (tests): the rule + argmax stage on supplied logits [B][vocab]; prefix [B][prefix_cap] with prefix_len [B] are the
  *   tokens sampled so far.  token_out [B], logprob_out [B], masked_out [B][vocab] (rules 1-6 applied; may be NULL).
  * encoder_output (tests): the final-LayerNorm output of the last encode, raw fp16 [B][ctx][d_model].
+ * decode_beam: beam search (K20b) over the last encode of B windows: beam W in 1..8, lane b * W + j is slot j of window b,
+ *   B * W <= 64.  n_finish = C, the number of finished hypotheses that ends a window's search (max(1, round(W * patience)),
+ *   1..16).  Per window H = max(W, C) hypothesis rows: first the finished ones in the order they finished, then live
+ *   slots in slot order while fewer than W.  tokens_out [B][H][max_new_tokens] (EOT-filled), n_out [B][H] = tokens
+ *   sampled up to and including EOT, ended_out [B][H] = 1 when the row ended on EOT, sum_logprob [B][H], n_hyp [B] = rows
+ *   in use, best_out [B] = the row with the largest sum_logprob / max(1, tokens before EOT) (ties: the earlier row).  The
+ *   complete flags are read back at most every sync_every sampled steps.  trace_src / trace_tok (tests; may be NULL)
+ *   [max_new_tokens][B][W]: per sampled step the source slot and token of every next slot, -1 where a slot stays
+ *   empty, the window was complete, or the step was not run.
+ * beam_select (tests): one beam step on supplied logits [B * W][vocab]; prefix [B * W][prefix_cap] with prefix_len [B * W]
+ *   and sums [B * W] (-inf = a dead slot) describe the slots, fin_count [B] the finished hypotheses each window has.
+ *   src_out / tok_out / sum_out [B][W] with n_live [B]: the next slots; fsrc_out / fsum_out [B][W] with n_fin [B]: the
+ *   candidates that ended on EOT in walk order; fin_count_out [B] = min(C, fin_count + n_fin); complete_out [B].
  * last_launches: kernel launches of the last decode and its number of decoder steps. */
 typedef struct {
   int n_mels, d_model, heads, enc_layers, dec_layers, enc_ffn, dec_ffn, vocab, max_source_positions, max_target_positions;
@@ -618,6 +631,14 @@ int eioku_whisper_decode(eioku_whisper_t* m, const int32_t* prompt_ids, int prom
 int eioku_whisper_forced_logits(eioku_whisper_t* m, const int32_t* ids, int T, int B, float* logits_out);
 int eioku_whisper_select(eioku_whisper_t* m, const float* logits, int B, const int32_t* prefix, int prefix_cap,
                          const int32_t* prefix_len, int32_t* token_out, float* logprob_out, float* masked_out);
+int eioku_whisper_decode_beam(eioku_whisper_t* m, const int32_t* prompt_ids, int prompt_len, int B, int beam, int n_finish,
+                              int max_new_tokens, int sync_every, int32_t* tokens_out, int32_t* n_out, int32_t* ended_out,
+                              float* sum_logprob, int32_t* n_hyp, int32_t* best_out, float* no_speech_prob,
+                              int32_t* lang_out, int32_t* trace_src, int32_t* trace_tok);
+int eioku_whisper_beam_select(eioku_whisper_t* m, const float* logits, int B, int beam, int n_finish, const int32_t* prefix,
+                              int prefix_cap, const int32_t* prefix_len, const float* sums, const int32_t* fin_count,
+                              int32_t* src_out, int32_t* tok_out, float* sum_out, int32_t* n_live, int32_t* fsrc_out,
+                              float* fsum_out, int32_t* n_fin, int32_t* fin_count_out, int32_t* complete_out);
 int eioku_whisper_encoder_output(eioku_whisper_t* m, void* out_f16, size_t numel);
 int eioku_whisper_last_flops(const eioku_whisper_t* m, double* flops);
 int eioku_whisper_last_launches(const eioku_whisper_t* m, int* launches, int* steps);

@@ -2,12 +2,16 @@
 """Whisper on the HIP path: device time of the log-mel front end, the encoder and a decoder step, with seeded weights.
 
     python tools/whisper_bench.py [--shapes base small] [--windows 64] [--out profiles/whisper.json]
+    python tools/whisper_bench.py --beam 5 [--shapes base]      # adds a beam block to the shapes already in --out
 
 For each shape (the openai `base` and `small` dimensions, vocabulary 51865, ctx 1500): log-mel over `--windows` windows of
 30 s, the encoder per window at batch 8, a decoder step at B = 1, 8 and 32 (greedy, 32 sampled tokens, lanes never end
 early with random weights unless EOT wins), kernel launches per step, and the CPU oracle (tests/whisper_oracle.py, fp32,
 torch-CPU) on the same box for one window and a few steps.  Calls are synchronous, so wall-clock time around them is device
 time plus one launch-queue drain.  No number here is an acceptance bar.
+
+`--beam W` measures beam search only (K20b): a decoder step and the launches per step at B = 1 and 8 windows (W lanes each),
+with the greedy step of the same run next to it, and merges the block into the shape's row of `--out`, leaving the rest.
 """
 from __future__ import annotations
 
@@ -45,12 +49,32 @@ def timed(fn, reps: int = 3) -> float:
     return best * 1e3
 
 
+def beam_block(t, dims: dict, audio: np.ndarray, beam: int, steps: int) -> dict:
+    prompt = [dims["sot"], dims["lang_ids"][0], dims["transcribe"]]
+    t.set_audio(audio)
+    block = {"beam": beam, "patience": 1.0, "sampled_tokens": steps}
+    for b in (1, 8):
+        t.logmel([i * 480000 for i in range(b)], fetch=False)
+        t.encode(b)
+        ms = timed(lambda: t.decode_beam(prompt, b, steps, beam, sync_every=steps))
+        launches, n = t.last_launches()
+        block[f"decode_ms_per_step_b{b}"] = ms / n
+        block[f"decode_steps_b{b}"] = n
+        block[f"launches_per_step_b{b}"] = launches / n
+        ms = timed(lambda: t.decode(prompt, b, steps, sync_every=steps))
+        launches, n = t.last_launches()
+        block[f"greedy_ms_per_step_b{b}"] = ms / n
+        block[f"greedy_launches_per_step_b{b}"] = launches / n
+    return block
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["base", "small"], choices=sorted(SHAPES))
     ap.add_argument("--windows", type=int, default=64)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--beam", type=int, default=0, help="measure beam search at this beam size and merge it into --out")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "whisper.json"))
     args = ap.parse_args()
 
@@ -59,6 +83,25 @@ def main() -> None:
 
     info = _lib.device_info()
     rng = np.random.default_rng(0)
+    if args.beam:
+        out = Path(args.out)
+        result = json.loads(out.read_text()) if out.exists() else {"what": "tools/whisper_bench.py --beam", "device": info, "shapes": []}
+        audio = (0.1 * rng.standard_normal(8 * 480000)).astype(np.float32)
+        for name in args.shapes:
+            dims = dims_for(name)
+            t = WhisperTranscriber(dims, seeded_weights(dims, 1))
+            block = beam_block(t, dims, audio, args.beam, args.steps)
+            t.close()
+            print(json.dumps({"shape": name, **block}))
+            rows = [r for r in result["shapes"] if r.get("shape") == name]
+            if not rows:
+                rows = [{"shape": name, "d_model": dims["d_model"], "layers": dims["enc_layers"]}]
+                result["shapes"].append(rows[0])
+            rows[0]["beam_search"] = block
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text(json.dumps(result, indent=1) + "\n")
+        print("wrote", args.out)
+        return
     audio = (0.1 * rng.standard_normal(args.windows * 480000)).astype(np.float32)
     result = {"what": "tools/whisper_bench.py on one MI355X: seeded weights, wall-clock ms around synchronous calls (best of 3 "
                       "after a warm-up); no number is an acceptance bar", "device": info, "windows": args.windows, "shapes": []}
