@@ -221,6 +221,13 @@ SIGNATURES = {
                                   [C.c_void_p] * 10),
     "eioku_whisper_beam_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] +
                                   [C.c_void_p] * 12),
+    "eioku_whisper_decode_prompted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                                C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "eioku_whisper_decode_beam_prompted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                     C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9),
+    "eioku_whisper_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_float] +
+                             [C.c_void_p] * 4),
+    "eioku_whisper_prefill_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "eioku_whisper_encoder_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "eioku_whisper_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_whisper_last_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -12,6 +12,11 @@
 //   K20b k_logits<., true> / k_beam_select   beam search: per-block top W + 1 text and timestamp ids next to the partials,
 //                       then per window the per-beam merge, the cross-beam walk, and the permuted lane state, ancestry
 //                       table, token history and finished records (DESIGN.md "K20b beam search")
+//   K20c k_logits<., false, true> / k_sample_select   sampling at a temperature: Gumbel-max scores with counter-based noise
+//                       computed next to the mask, per-block best score per class in the partials
+//        k_embed_seq / k_attn<2, false, true> / k_kv_to_cache / k_gather_rows   the one-pass prompt prefill: all prompt
+//                       positions through the M-tiled GEMMs and causal attention, keys / values into the cache layout
+//                       (DESIGN.md "K20c sampling and prompt prefill")
 // Precision points (tests/whisper_oracle.py, fp16=True, rounds at the same places): weights of every linear / conv layer
 // and the token embedding are fp16; biases, LayerNorm parameters and both position tables fp32; the residual stream is
 // fp32; LayerNorm outputs, q / k / v, attention outputs, GELU outputs and the mel input are rounded to fp16.
@@ -241,11 +246,15 @@ __global__ __launch_bounds__(256) void k_embed(const int* __restrict__ toks, int
 // dimension, o = sum_j p_j v[j][lane] (a 128-byte row per key).  Dynamic LDS: 4 QPW (n_keys + 64) floats.
 // Query batch b reads the keys of batch b / kv_div (beam search: the W lanes of a window share its cross-attention K / V).
 // ANC: key j of batch b is row j of batch anc[b * anc_ld + j] (beam search: the lane whose step j is in b's history).
-template <int QPW, bool ANC = false>
+// kvmap (may be NULL): query batch b reads the keys of batch kvmap[b] instead (prompted decode: the row -> window map).
+// CAUSAL (prompt prefill, n_keys == n_q): query qi sees keys 0 .. qi; a wave's loops end at its last query's key, and a
+// wave with no query runs none.
+template <int QPW, bool ANC = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long long q_bs, int q_rs, const h16* __restrict__ Kc,
                                               const h16* __restrict__ Vc, long long kv_bs, int kv_rs, int n_q, int n_keys,
                                               h16* __restrict__ O, long long o_bs, int o_rs, int kv_div,
-                                              const uint8_t* __restrict__ anc, int anc_ld) {
+                                              const uint8_t* __restrict__ anc, int anc_ld,
+                                              const int* __restrict__ kvmap) {
   extern __shared__ float smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, head = blockIdx.y, b = blockIdx.z;
   const int q0 = (blockIdx.x * 4 + wave) * QPW;
@@ -257,14 +266,15 @@ __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long lo
     qs[i * 64 + lane] = qi < n_q ? (float)Q[(size_t)b * q_bs + (size_t)qi * q_rs + head * 64 + lane] : 0.f;
   }
   __syncthreads();
-  const size_t kvb = ANC ? 0 : (size_t)(b / kv_div);
+  const size_t kvb = ANC ? 0 : (size_t)(kvmap ? kvmap[b] : b / kv_div);
+  const int nk = !CAUSAL ? n_keys : (q0 >= n_q ? 0 : (q0 + QPW < n_keys ? q0 + QPW : n_keys));
   const h16* kb = Kc + kvb * kv_bs + head * 64;
   const h16* vb = Vc + kvb * kv_bs + head * 64;
   const uint8_t* an = ANC ? anc + (size_t)b * anc_ld : nullptr;
   float mx[QPW], sum[QPW], o[QPW];
 #pragma unroll
   for (int i = 0; i < QPW; ++i) mx[i] = kNegInf, sum[i] = 0.f, o[i] = 0.f;
-  for (int j = lane; j < n_keys; j += 64) {
+  for (int j = lane; j < nk; j += 64) {
     const uint4* kr = reinterpret_cast<const uint4*>(kb + (ANC ? (size_t)an[j] * kv_bs : 0) + (size_t)j * kv_rs);
     float s[QPW];
 #pragma unroll
@@ -282,6 +292,7 @@ __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long lo
 #pragma unroll
     for (int i = 0; i < QPW; ++i) {
       s[i] *= 0.125f;
+      if (CAUSAL && j > q0 + i) s[i] = kNegInf;
       sc[(size_t)i * n_keys + j] = s[i];
       mx[i] = fmaxf(mx[i], s[i]);
     }
@@ -290,7 +301,7 @@ __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long lo
   for (int i = 0; i < QPW; ++i) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], off, 64));
-    for (int j = lane; j < n_keys; j += 64) {
+    for (int j = lane; j < nk; j += 64) {
       const float p = expf(sc[(size_t)i * n_keys + j] - mx[i]);
       sc[(size_t)i * n_keys + j] = p;
       sum[i] += p;
@@ -299,7 +310,7 @@ __global__ __launch_bounds__(256) void k_attn(const h16* __restrict__ Q, long lo
     for (int off = 32; off > 0; off >>= 1) sum[i] += __shfl_xor(sum[i], off, 64);
   }
   __syncthreads();
-  for (int j = 0; j < n_keys; ++j) {
+  for (int j = 0; j < nk; ++j) {
     const float vf = (float)vb[(ANC ? (size_t)an[j] * kv_bs : 0) + (size_t)j * kv_rs + lane];
 #pragma unroll
     for (int i = 0; i < QPW; ++i) o[i] += sc[(size_t)i * n_keys + j] * vf;
@@ -328,6 +339,17 @@ constexpr int kFlagSuppress = 1, kFlagBegin = 2;  // flags[id]: bit 0 / 1, langu
 // beam search: a beam partial is the kNP values above, then the block's best text ids and best timestamp ids as (value, id)
 // pairs, kNC of each, best first, (-inf, -1) where there are fewer
 constexpr int kMaxBeam = 8, kNC = kMaxBeam + 1, kMaxFinish = 16, kNPB = kNP + 4 * kNC;
+// sampling (K20c): a sample partial is, per class (text ids, then timestamp ids), the block's best perturbed score, its id and
+// that id's unperturbed masked logit, then max_text, max_ts, m_all, s_all, s_ts (relative to max_ts) as above, one unused
+constexpr int kNPS = 12;
+
+// Gumbel noise of sampled-token index idx and id n in the splitmix64 stream `seed`: element i = idx * vocab + n,
+// u = ((z >> 41) + 0.5) * 2^-23 (23 bits: exact in fp32, never 0 or 1), g = -log(-log(u)) with the accurate logf.
+__device__ __forceinline__ float gumbel_at(unsigned long long seed, int idx, int vocab, int n) {
+  const unsigned long long z = splitmix64_at(seed, (unsigned long long)idx * (unsigned long long)vocab + (unsigned long long)n);
+  const float u = ((float)(unsigned)(z >> 41) + 0.5f) * 1.1920928955078125e-07f;
+  return -logf(-logf(u));
+}
 
 __device__ __forceinline__ bool rule_masks(int n, const SelCfg& c, unsigned flag, const LaneState& st) {
   const bool is_ts = n >= c.tb;
@@ -355,18 +377,24 @@ __device__ __forceinline__ bool rule_masks(int n, const SelCfg& c, unsigned flag
 // BEAM: partials of kNPB values; the nc best masked text ids and the nc best masked timestamp ids of the block follow the
 // kNP values.  Thread (lane tid & 15, ids 4 (tid >> 4) ..+ 3) ranks its ids within their class by (value, lower id first):
 // an id's rank is the number of ids of its class that beat it, so every rank is written once and no order of threads matters.
-template <bool SUPPLIED, bool BEAM = false>
+// SAMPLE (never with BEAM): partials of kNPS values.  score = masked logit / temp + gumbel_at(seeds[lane], idx, vocab, id)
+// is computed next to the mask and parked in LDS; the fold keeps the best score of each class (the lower id on equal
+// scores), so no vocabulary-wide value reaches HBM.  idx = sidx[lane] when sidx is given, else sidx_all.
+template <bool SUPPLIED, bool BEAM = false, bool SAMPLE = false>
 __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d, const h16* __restrict__ E,
                                                 const float* __restrict__ supplied, int B, SelCfg c,
                                                 const uint16_t* __restrict__ flags, const LaneState* __restrict__ st, int rules,
                                                 float* __restrict__ partial, int nblk, float* __restrict__ raw_out,
                                                 long long raw_ld, float* __restrict__ masked_out, float* __restrict__ info,
-                                                int nlang, int nc) {
+                                                int nlang, int nc, float temp, const unsigned long long* __restrict__ seeds,
+                                                const int* __restrict__ sidx, int sidx_all) {
+  static_assert(!(BEAM && SAMPLE), "beam search does not sample");
   __shared__ float raw[64][17];
   __shared__ float msk[64][17];
+  __shared__ float scr[SAMPLE ? 64 : 1][17];
   __shared__ float topv[BEAM ? 16 : 1][2][kNC];
   __shared__ int topi[BEAM ? 16 : 1][2][kNC];
-  constexpr int NP = BEAM ? kNPB : kNP;
+  constexpr int NP = BEAM ? kNPB : (SAMPLE ? kNPS : kNP);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, u = lane >> 4;
   const int v0 = blockIdx.x * 64, n0 = v0 + wave * 16;
   for (int bt = 0; bt < B; bt += 16) {
@@ -409,6 +437,8 @@ __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d
       }
       raw[row][r] = rv;
       msk[row][r] = mv;
+      if constexpr (SAMPLE)
+        scr[row][r] = mv > kNegInf ? mv / temp + gumbel_at(seeds[b], sidx ? sidx[b] : sidx_all, c.vocab, n) : kNegInf;
     }
     __syncthreads();
     if constexpr (BEAM) {
@@ -439,6 +469,8 @@ __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d
     if (tid < 16 && bt + tid < B) {
       float max_text = kNegInf, max_ts = kNegInf, m_raw = kNegInf;
       int arg_text = -1, arg_ts = -1;
+      float bs[2] = {kNegInf, kNegInf}, bl[2] = {kNegInf, kNegInf};  // SAMPLE: best score and its logit, text / timestamps
+      int bi[2] = {-1, -1};
       for (int i = 0; i < 64; ++i) {
         const int n = v0 + i;
         const float mv = msk[i][tid];
@@ -447,6 +479,10 @@ __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d
           if (mv > max_text) max_text = mv, arg_text = n;
         } else if (mv > max_ts) {
           max_ts = mv, arg_ts = n;
+        }
+        if constexpr (SAMPLE) {
+          const int q = n < c.tb ? 0 : 1;
+          if (mv > kNegInf && (bi[q] < 0 || scr[i][tid] > bs[q])) bs[q] = scr[i][tid], bi[q] = n, bl[q] = mv;
         }
       }
       const float m_all = fmaxf(max_text, max_ts);
@@ -460,8 +496,13 @@ __global__ __launch_bounds__(256) void k_logits(const h16* __restrict__ H, int d
         if (rv > kNegInf) s_raw += expf(rv - m_raw);
       }
       float* p = partial + ((size_t)(bt + tid) * nblk + blockIdx.x) * NP;
-      p[0] = max_text, p[1] = __int_as_float(arg_text), p[2] = max_ts, p[3] = __int_as_float(arg_ts);
-      p[4] = m_all, p[5] = s_all, p[6] = s_ts, p[7] = m_raw, p[8] = s_raw, p[9] = 0.f;
+      if constexpr (SAMPLE) {
+        p[0] = bs[0], p[1] = __int_as_float(bi[0]), p[2] = bl[0], p[3] = bs[1], p[4] = __int_as_float(bi[1]), p[5] = bl[1];
+        p[6] = max_text, p[7] = max_ts, p[8] = m_all, p[9] = s_all, p[10] = s_ts, p[11] = 0.f;
+      } else {
+        p[0] = max_text, p[1] = __int_as_float(arg_text), p[2] = max_ts, p[3] = __int_as_float(arg_ts);
+        p[4] = m_all, p[5] = s_all, p[6] = s_ts, p[7] = m_raw, p[8] = s_raw, p[9] = 0.f;
+      }
       if constexpr (BEAM) {
         for (int q = 0; q < 2; ++q)
           for (int r = 0; r < kNC; ++r)
@@ -555,6 +596,98 @@ __global__ __launch_bounds__(64) void k_select(const float* __restrict__ partial
   if (tokens) tokens[(size_t)b * tok_ld + idx] = tok;
   if (cur_tok) cur_tok[b] = tok;
   if (logprob_out) logprob_out[b] = lp;
+}
+
+// ---- sampling (K20c) ---------------------------------------------------------------------------------------------------------
+struct SAcc {
+  float bs[2], bl[2];  // per class (text, timestamps): the best perturbed score and that id's masked logit
+  int bi[2];
+  float max_text, max_ts, m_all, s_all, s_ts;
+};
+
+__device__ __forceinline__ void sacc_merge(SAcc& a, const SAcc& p) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    if (p.bi[q] >= 0 && (a.bi[q] < 0 || p.bs[q] > a.bs[q] || (p.bs[q] == a.bs[q] && p.bi[q] < a.bi[q])))
+      a.bs[q] = p.bs[q], a.bi[q] = p.bi[q], a.bl[q] = p.bl[q];
+  a.max_text = fmaxf(a.max_text, p.max_text);
+  lse_merge(a.m_all, a.s_all, p.m_all, p.s_all);
+  lse_merge(a.max_ts, a.s_ts, p.max_ts, p.s_ts);
+}
+
+// grid B, one wave: the fold of k_select over sample partials.  Rule 7 first (timestamp mass above every text id: text is
+// out), then the best perturbed score of what is left, the lower id on equal scores.  The lane's sum gets the UNTEMPERED
+// log-softmax of the masked logits at the token, as Whisper's GreedyDecoder accumulates.
+__global__ __launch_bounds__(64) void k_sample_select(const float* __restrict__ partial, int nblk, SelCfg c, LaneState* __restrict__ st,
+                                                      int idx, int* __restrict__ tokens, int tok_ld, int* __restrict__ cur_tok,
+                                                      float* __restrict__ logprob_out) {
+  __shared__ SAcc sh[64];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  SAcc a = {{kNegInf, kNegInf}, {kNegInf, kNegInf}, {-1, -1}, kNegInf, kNegInf, kNegInf, 0.f, 0.f};
+  for (int k = lane; k < nblk; k += 64) {
+    const float* p = partial + ((size_t)b * nblk + k) * kNPS;
+    const SAcc q = {{p[0], p[3]}, {p[2], p[5]}, {__float_as_int(p[1]), __float_as_int(p[4])}, p[6], p[7], p[8], p[9], p[10]};
+    sacc_merge(a, q);
+  }
+  sh[lane] = a;
+  __syncthreads();
+  if (lane != 0) return;
+  for (int i = 1; i < 64; ++i) sacc_merge(a, sh[i]);
+  LaneState s = st[b];
+  int tok = c.eot;
+  float lp = 0.f;
+  if (!s.done) {
+    const float lse_all = a.m_all + logf(a.s_all);
+    const float lse_ts = a.max_ts > kNegInf ? a.max_ts + logf(a.s_ts) : kNegInf;
+    if (lse_ts > a.max_text) {
+      tok = a.bi[1], lp = a.bl[1] - lse_ts;
+    } else if (a.bi[1] >= 0 && (a.bi[0] < 0 || a.bs[1] > a.bs[0])) {  // a text id is below every timestamp id
+      tok = a.bi[1], lp = a.bl[1] - lse_all;
+    } else {
+      tok = a.bi[0], lp = a.bl[0] - lse_all;
+    }
+    if (tok < 0) tok = c.eot, lp = 0.f;  // every id masked: cannot happen under the rules, end the lane
+    s.sum += lp;
+    s.penult = s.last;
+    s.last = tok;
+    if (tok >= c.tb) s.last_ts = tok;
+    s.n += 1;
+    if (tok == c.eot) s.done = 1;
+    st[b] = s;
+  }
+  if (tokens) tokens[(size_t)b * tok_ld + idx] = tok;
+  if (cur_tok) cur_tok[b] = tok;
+  if (logprob_out) logprob_out[b] = lp;
+}
+
+// ---- prompt prefill ------------------------------------------------------------------------------------------------------------
+// x[(r, t)] = embed[ids[r * P + t]] + pos[t] for R rows of P prompt positions; grid R * P
+__global__ __launch_bounds__(256) void k_embed_seq(const int* __restrict__ ids, int P, int vocab, int d, const h16* __restrict__ emb,
+                                                   const float* __restrict__ pos, float* __restrict__ x) {
+  const size_t row = blockIdx.x;
+  int tok = ids[row];
+  tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
+  const int t = (int)(row % P);
+  for (int i = threadIdx.x; i < d; i += 256) x[row * d + i] = (float)emb[(size_t)tok * d + i] + pos[(size_t)t * d + i];
+}
+
+// the prefill's keys and values [R][P][d] into the self-attention cache of lanes lane0 + r * lstride .. + G - 1 (row t of a
+// lane's Tm rows); grid (P, R * G), 8 halves per thread
+__global__ __launch_bounds__(256) void k_kv_to_cache(const h16* __restrict__ pk, const h16* __restrict__ pv, int P, int d, int G,
+                                                     int lstride, int Tm, h16* __restrict__ ck, h16* __restrict__ cv) {
+  const int t = blockIdx.x, r = blockIdx.y / G, lane = r * lstride + blockIdx.y % G;
+  const size_t src = ((size_t)r * P + t) * d, dst = ((size_t)lane * Tm + t) * d;
+  for (int i = threadIdx.x * 8; i < d; i += 256 * 8) {
+    *reinterpret_cast<uint4*>(ck + dst + i) = *reinterpret_cast<const uint4*>(pk + src + i);
+    *reinterpret_cast<uint4*>(cv + dst + i) = *reinterpret_cast<const uint4*>(pv + src + i);
+  }
+}
+
+// out[l] = h[(l / G) * P + t]: one prefill position of every row, repeated for the G lanes of the row; grid L
+__global__ __launch_bounds__(256) void k_gather_rows(const h16* __restrict__ h, int P, int t, int G, int d, h16* __restrict__ out) {
+  const int l = blockIdx.x;
+  const size_t src = ((size_t)(l / G) * P + t) * d;
+  for (int i = threadIdx.x; i < d; i += 256) out[(size_t)l * d + i] = h[src + i];
 }
 
 // ---- beam search (K20b) ----------------------------------------------------------------------------------------------------
@@ -807,6 +940,13 @@ struct eioku_whisper {
   uint8_t* anc[2] = {nullptr, nullptr};
   int *hist[2] = {nullptr, nullptr}, *fin_tok = nullptr, *fin_n = nullptr, *fin_count = nullptr, *complete = nullptr;
   int *b_src = nullptr, *b_tok = nullptr, *b_fsrc = nullptr, *b_nlive = nullptr, *b_nfin = nullptr, *tr_src = nullptr, *tr_tok = nullptr;
+  // sampling and prompt prefill: per-lane seeds and sample indices, the row -> window maps (rows, then lanes), and the
+  // prefill workspace for prows = rows x prompt positions
+  unsigned long long* d_seeds = nullptr;
+  int *d_sidx = nullptr, *kvmap = nullptr;
+  int prows = 0;
+  float *px = nullptr, *ppartial = nullptr;
+  h16 *ph = nullptr, *pq = nullptr, *pk = nullptr, *pv = nullptr, *pa = nullptr, *pmid = nullptr;
   double flops = 0;
   int launches = 0, steps = 0;
 
@@ -856,18 +996,24 @@ int ln(eioku_whisper* m, const float* x, int M, int d, int g, int b, h16* out) {
 
 template <int QPW>
 int attn(eioku_whisper* m, const h16* Q, long long q_bs, int q_rs, const h16* K, const h16* V, long long kv_bs, int kv_rs, int n_q,
-         int n_keys, int B, h16* O, long long o_bs, int o_rs, int kv_div = 1, const uint8_t* anc = nullptr, int anc_ld = 0) {
+         int n_keys, int B, h16* O, long long o_bs, int o_rs, int kv_div = 1, const uint8_t* anc = nullptr, int anc_ld = 0,
+         const int* kvmap = nullptr, bool causal = false) {
   const size_t lds = (size_t)4 * QPW * (n_keys + 64) * sizeof(float);
   EIOKU_REQUIRE(lds <= 64 * 1024, "attention over %d keys needs %zu bytes of LDS", n_keys, lds);
   const dim3 grid((n_q + 4 * QPW - 1) / (4 * QPW), m->cfg.heads, B);
-  if (anc)
+  if (causal) {
+    EIOKU_REQUIRE(!anc && n_q == n_keys, "causal attention needs as many keys as queries and no ancestry table");
+    hipLaunchKernelGGL((k_attn<QPW, false, true>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs,
+                       o_rs, kv_div, (const uint8_t*)nullptr, 0, kvmap);
+  } else if (anc) {
     hipLaunchKernelGGL((k_attn<QPW, true>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs, o_rs,
-                       kv_div, anc, anc_ld);
-  else
+                       kv_div, anc, anc_ld, (const int*)nullptr);
+  } else {
     hipLaunchKernelGGL((k_attn<QPW, false>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs, o_rs,
-                       kv_div, (const uint8_t*)nullptr, 0);
+                       kv_div, (const uint8_t*)nullptr, 0, kvmap);
+  }
   EIOKU_LAUNCH_CHECK();
-  m->flops += 4.0 * B * m->cfg.heads * (double)n_q * n_keys * 64;
+  m->flops += 4.0 * B * m->cfg.heads * (double)n_q * n_keys * 64 * (causal ? 0.5 : 1.0);
   m->launches += 1;
   return EIOKU_OK;
 }
@@ -886,7 +1032,10 @@ int ensure_lanes(eioku_whisper* m, int L) {
   W_TRY(dalloc(&m->dmid, B * ffn));
   W_TRY(dalloc(&m->selfK, c.dec_layers * B * Tm * d));
   W_TRY(dalloc(&m->selfV, c.dec_layers * B * Tm * d));
-  W_TRY(dalloc(&m->partial, B * m->nblk * kNP));
+  W_TRY(dalloc(&m->partial, B * m->nblk * (kNPS > kNP ? kNPS : kNP)));
+  W_TRY(dalloc(&m->d_seeds, B));
+  W_TRY(dalloc(&m->d_sidx, B));
+  W_TRY(dalloc(&m->kvmap, 2 * B));
   W_TRY(dalloc(&m->info, B * (1 + m->nlang)));
   W_TRY(dalloc(&m->nsp, B));
   W_TRY(dalloc(&m->d_logprob, B));
@@ -972,7 +1121,7 @@ int check_weights(const eioku_whisper* m) {
 // one decoder position s for B lanes: embedding -> layers -> final LayerNorm into m->dh.  Beam search: kv_div lanes share a
 // window's cross-attention K / V, and self-attention reads key t of a lane from the lane anc[lane][t].
 int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, int uniform, int kv_div = 1,
-                 const uint8_t* anc = nullptr) {
+                 const uint8_t* anc = nullptr, const int* kvmap = nullptr) {
   const auto& c = m->cfg;
   const int d = c.d_model, ctx = c.max_source_positions, Tm = c.max_target_positions;
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, 0, toks, tstride, uniform, c.vocab, d, s, m->H(m->emb), m->F(m->dec_pos), m->dx);
@@ -992,7 +1141,7 @@ int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, i
     W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.self.o), d, m->F(L.self.ob), B, d, d, m->dx, d)));
     W_TRY(ln(m, m->dx, B, d, L.cross.ln_g, L.cross.ln_b, m->dh));
     W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.cross.q), d, m->F(L.cross.qb), B, d, d, m->dq, d)));
-    W_TRY((attn<1>(m, m->dq, d, d, ck, cv, (long long)ctx * d, d, 1, ctx, B, m->da, d, d, kv_div)));
+    W_TRY((attn<1>(m, m->dq, d, d, ck, cv, (long long)ctx * d, d, 1, ctx, B, m->da, d, d, kv_div, nullptr, 0, kvmap)));
     W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.cross.o), d, m->F(L.cross.ob), B, d, d, m->dx, d)));
     W_TRY(ln(m, m->dx, B, d, L.ln_g, L.ln_b, m->dh));
     W_TRY((gemm<1, EPI_GELU_F16>(m, m->dh, d, m->H(L.fc1), d, m->F(L.fc1b), B, c.dec_ffn, d, m->dmid, c.dec_ffn)));
@@ -1003,7 +1152,8 @@ int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, i
 
 int logits(eioku_whisper* m, int B, int rules, float* raw_out, long long raw_ld, bool info) {
   hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, B, m->sel,
-                     m->flags, m->state, rules, m->partial, m->nblk, raw_out, raw_ld, nullptr, info ? m->info : nullptr, m->nlang, 0);
+                     m->flags, m->state, rules, m->partial, m->nblk, raw_out, raw_ld, nullptr, info ? m->info : nullptr, m->nlang, 0,
+                     1.f, nullptr, nullptr, 0);
   EIOKU_LAUNCH_CHECK();
   m->flops += 2.0 * B * m->cfg.vocab * m->cfg.d_model;
   m->launches += 1;
@@ -1013,9 +1163,116 @@ int logits(eioku_whisper* m, int B, int rules, float* raw_out, long long raw_ld,
 // beam search: masked logits of L lanes into the beam partials (the block's nc best text and timestamp ids included)
 int logits_beam(eioku_whisper* m, int L, int nc) {
   hipLaunchKernelGGL((k_logits<false, true>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, L, m->sel,
-                     m->flags, m->state, 1, m->bpartial, m->nblk, nullptr, 0LL, nullptr, nullptr, m->nlang, nc);
+                     m->flags, m->state, 1, m->bpartial, m->nblk, nullptr, 0LL, nullptr, nullptr, m->nlang, nc, 1.f, nullptr, nullptr, 0);
   EIOKU_LAUNCH_CHECK();
   m->flops += 2.0 * L * m->cfg.vocab * m->cfg.d_model;
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+// sampling: masked logits of L lanes into sample partials, scores perturbed with each lane's noise at sample index idx
+int logits_sample(eioku_whisper* m, int L, float temp, int idx) {
+  hipLaunchKernelGGL((k_logits<false, false, true>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, L,
+                     m->sel, m->flags, m->state, 1, m->partial, m->nblk, nullptr, 0LL, nullptr, nullptr, m->nlang, 0, temp, m->d_seeds,
+                     nullptr, idx);
+  EIOKU_LAUNCH_CHECK();
+  m->flops += 2.0 * L * m->cfg.vocab * m->cfg.d_model;
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+// the prefill workspace for `rows` = rows x prompt positions
+int ensure_prefill(eioku_whisper* m, int rows) {
+  if (rows <= m->prows) return EIOKU_OK;
+  const size_t n = (size_t)rows, d = m->cfg.d_model;
+  m->prows = 0;
+  W_TRY(dalloc(&m->px, n * d));
+  W_TRY(dalloc(&m->ph, n * d));
+  W_TRY(dalloc(&m->pq, n * d));
+  W_TRY(dalloc(&m->pk, n * d));
+  W_TRY(dalloc(&m->pv, n * d));
+  W_TRY(dalloc(&m->pa, n * d));
+  W_TRY(dalloc(&m->pmid, n * m->cfg.dec_ffn));
+  W_TRY(dalloc(&m->ppartial, n * m->nblk * kNP));
+  m->prows = rows;
+  return EIOKU_OK;
+}
+
+// One pass of the decoder over the P prompt positions of R rows (ids [R][P] on the device): the M-tiled GEMMs of the encoder,
+// causal self-attention, cross-attention against window kvmap[r].  Leaves the final-LayerNorm hidden state of every position
+// in m->ph [R][P][d] and the self-attention keys / values of positions 0 .. P - 1 in the cache of lanes r * lstride .. + G - 1.
+int prefill(eioku_whisper* m, int R, int P, const int* ids, const int* kvmap, int G, int lstride) {
+  const auto& c = m->cfg;
+  const int d = c.d_model, ctx = c.max_source_positions, Tm = c.max_target_positions, M = R * P;
+  const long long bs = (long long)P * d;
+  W_TRY(ensure_prefill(m, M));
+  hipLaunchKernelGGL(k_embed_seq, dim3(M), dim3(256), 0, 0, ids, P, c.vocab, d, m->H(m->emb), m->F(m->dec_pos), m->px);
+  EIOKU_LAUNCH_CHECK();
+  m->launches += 1;
+  for (int l = 0; l < c.dec_layers; ++l) {
+    const Layer& L = m->dec[l];
+    h16* sk = m->selfK + (size_t)l * m->dcap * Tm * d;
+    h16* sv = m->selfV + (size_t)l * m->dcap * Tm * d;
+    const h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
+    const h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
+    W_TRY(ln(m, m->px, M, d, L.self.ln_g, L.self.ln_b, m->ph));
+    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.self.q), d, m->F(L.self.qb), M, d, d, m->pq, d)));
+    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.self.k), d, nullptr, M, d, d, m->pk, d)));
+    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.self.v), d, m->F(L.self.vb), M, d, d, m->pv, d)));
+    hipLaunchKernelGGL(k_kv_to_cache, dim3(P, R * G), dim3(256), 0, 0, m->pk, m->pv, P, d, G, lstride, Tm, sk, sv);
+    EIOKU_LAUNCH_CHECK();
+    m->launches += 1;
+    W_TRY((attn<2>(m, m->pq, bs, d, m->pk, m->pv, bs, d, P, P, R, m->pa, bs, d, 1, nullptr, 0, nullptr, true)));
+    W_TRY((gemm<4, EPI_RESID>(m, m->pa, d, m->H(L.self.o), d, m->F(L.self.ob), M, d, d, m->px, d)));
+    W_TRY(ln(m, m->px, M, d, L.cross.ln_g, L.cross.ln_b, m->ph));
+    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.cross.q), d, m->F(L.cross.qb), M, d, d, m->pq, d)));
+    W_TRY((attn<2>(m, m->pq, bs, d, ck, cv, (long long)ctx * d, d, P, ctx, R, m->pa, bs, d, 1, nullptr, 0, kvmap)));
+    W_TRY((gemm<4, EPI_RESID>(m, m->pa, d, m->H(L.cross.o), d, m->F(L.cross.ob), M, d, d, m->px, d)));
+    W_TRY(ln(m, m->px, M, d, L.ln_g, L.ln_b, m->ph));
+    W_TRY((gemm<4, EPI_GELU_F16>(m, m->ph, d, m->H(L.fc1), d, m->F(L.fc1b), M, c.dec_ffn, d, m->pmid, c.dec_ffn)));
+    W_TRY((gemm<4, EPI_RESID>(m, m->pmid, c.dec_ffn, m->H(L.fc2), c.dec_ffn, m->F(L.fc2b), M, d, c.dec_ffn, m->px, d)));
+  }
+  return ln(m, m->px, M, d, m->dec_ln_g, m->dec_ln_b, m->ph);
+}
+
+// m->dh[l] = the prefill's hidden state of row l / G at position t, for L lanes
+int gather_hidden(eioku_whisper* m, int L, int P, int t, int G) {
+  hipLaunchKernelGGL(k_gather_rows, dim3(L), dim3(256), 0, 0, m->ph, P, t, G, m->cfg.d_model, m->dh);
+  EIOKU_LAUNCH_CHECK();
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+// checks prompts [B][P] and windows [B] (NULL: identity, which needs B == the encoded windows); uploads the prompts to
+// m->d_ids and the row -> window maps to m->kvmap (B rows) and m->kvmap + m->dcap (B * G lanes)
+int prompted_args(eioku_whisper* m, const int32_t* prompts, int P, int sot_index, const int32_t* windows, int B, int G, int max_new) {
+  EIOKU_REQUIRE(prompts && P >= 1 && max_new >= 1, "bad argument");
+  EIOKU_REQUIRE(B > 0 && G >= 1 && B * G <= 64, "%d rows x %d = %d lanes: at most 64 lanes decode in lockstep", B, G, B * G);
+  EIOKU_REQUIRE(sot_index >= 0 && sot_index < P, "sot_index %d outside the prompt of %d tokens", sot_index, P);
+  EIOKU_REQUIRE(P + max_new <= m->cfg.max_target_positions, "prompt %d + %d new tokens exceed max_target_positions %d", P, max_new,
+                m->cfg.max_target_positions);
+  EIOKU_REQUIRE(m->enc_B > 0, "a prompted decode needs an encode first");
+  if (!windows) EIOKU_REQUIRE(B == m->enc_B, "decode of %d rows without a window list needs an encode of the same %d windows", B, m->enc_B);
+  for (int b = 0; windows && b < B; ++b)
+    EIOKU_REQUIRE(windows[b] >= 0 && windows[b] < m->enc_B, "window %d outside the %d encoded windows", windows[b], m->enc_B);
+  for (size_t i = 0; i < (size_t)B * P; ++i)
+    EIOKU_REQUIRE(prompts[i] >= 0 && prompts[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompts[i]);
+  W_TRY(ensure_lanes(m, B * G));
+  std::vector<int> map((size_t)2 * m->dcap, 0);
+  for (int b = 0; b < B; ++b) map[b] = windows ? windows[b] : b;
+  for (int l = 0; l < B * G; ++l) map[(size_t)m->dcap + l] = map[l / G];
+  EIOKU_HIP_CHECK(hipMemcpy(m->kvmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, prompts, (size_t)B * P * sizeof(int), hipMemcpyHostToDevice));
+  return EIOKU_OK;
+}
+
+// the no-speech probability of B rows from the prefill's hidden state at prompt position sot_index, into m->nsp [B]
+int prefill_no_speech(eioku_whisper* m, int B, int P, int sot_index) {
+  W_TRY(gather_hidden(m, B, P, sot_index, 1));
+  W_TRY(logits(m, B, 0, nullptr, 0, true));
+  hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, 0, 1, m->info, m->nlang, m->lang_ids,
+                     (int*)nullptr, 0, (int*)nullptr, m->nsp, m->lang_out, (float*)nullptr);
+  EIOKU_LAUNCH_CHECK();
   m->launches += 1;
   return EIOKU_OK;
 }
@@ -1164,7 +1421,8 @@ void eioku_whisper_destroy(eioku_whisper* m) {
                   m->dh, m->dq, m->da, m->dmid, m->selfK, m->selfV, m->dx, m->partial, m->info, m->nsp, m->d_logprob, m->state,
                   m->tokens, m->cur_tok, m->lang_out, m->d_ids, m->bpartial, m->fin_sum, m->b_sum, m->b_fsum, m->anc[0], m->anc[1],
                   m->hist[0], m->hist[1], m->fin_tok, m->fin_n, m->fin_count, m->complete, m->b_src, m->b_tok, m->b_fsrc,
-                  m->b_nlive, m->b_nfin, m->tr_src, m->tr_tok};
+                  m->b_nlive, m->b_nfin, m->tr_src, m->tr_tok, m->d_seeds, m->d_sidx, m->kvmap, m->px, m->ppartial, m->ph, m->pq,
+                  m->pk, m->pv, m->pa, m->pmid};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete m;
@@ -1394,7 +1652,8 @@ int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const 
   hipError_t e = rc == EIOKU_OK ? hipMemcpy(d_in, logits_in, (size_t)B * V * sizeof(float), hipMemcpyHostToDevice) : hipSuccess;
   if (rc == EIOKU_OK && e == hipSuccess) {
     hipLaunchKernelGGL((k_logits<true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in, B, m->sel,
-                       m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, d_msk, (float*)nullptr, m->nlang, 0);
+                       m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, d_msk, (float*)nullptr, m->nlang, 0, 1.f,
+                       (const unsigned long long*)nullptr, (const int*)nullptr, 0);
     hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, 0, 0, m->info, m->nlang,
                        m->lang_ids, (int*)nullptr, 0, m->cur_tok, m->nsp, m->lang_out, m->d_logprob);
     e = hipGetLastError();
@@ -1427,23 +1686,30 @@ void launch_beam_select(eioku_whisper* m, int B, int W, int C, int s, int idx, c
   m->launches += 1;
 }
 
-}  // namespace
-
-int eioku_whisper_decode_beam(eioku_whisper* m, const int32_t* prompt, int prompt_len, int B, int W, int C, int max_new,
-                              int sync_every, int32_t* tokens_out, int32_t* n_out, int32_t* ended_out, float* sum_logprob,
-                              int32_t* n_hyp, int32_t* best_out, float* no_speech_prob, int32_t* lang_out, int32_t* trace_src,
-                              int32_t* trace_tok) {
+// The beam search behind both entries.  prefill = false: `prompt` [prompt_len] is shared and every lane walks it position by
+// position.  prefill = true: `prompt` is [B][prompt_len], one prefill per window fills slot 0's cache, the ancestry table
+// names that lane for every prompt position, the no-speech probability comes from position sot_index (per window, not per
+// lane), and row b reads encoded window windows[b].
+int beam_impl(eioku_whisper* m, const int32_t* prompt, int prompt_len, bool pre, int sot_index, const int32_t* windows, int B, int W,
+              int C, int max_new, int sync_every, int32_t* tokens_out, int32_t* n_out, int32_t* ended_out, float* sum_logprob,
+              int32_t* n_hyp, int32_t* best_out, float* no_speech_prob, int32_t* lang_out, int32_t* trace_src, int32_t* trace_tok) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && prompt && prompt_len >= 1 && max_new >= 1, "bad argument");
   W_TRY(beam_args(m, B, W, C));
-  EIOKU_REQUIRE(B == m->enc_B, "beam decode of %d windows needs an encode of the same %d windows first", B, m->enc_B);
-  EIOKU_REQUIRE(prompt_len + max_new <= m->cfg.max_target_positions, "prompt %d + %d new tokens exceed max_target_positions %d",
-                prompt_len, max_new, m->cfg.max_target_positions);
+  if (!pre) {
+    EIOKU_REQUIRE(B == m->enc_B, "beam decode of %d windows needs an encode of the same %d windows first", B, m->enc_B);
+    EIOKU_REQUIRE(prompt_len + max_new <= m->cfg.max_target_positions, "prompt %d + %d new tokens exceed max_target_positions %d",
+                  prompt_len, max_new, m->cfg.max_target_positions);
+  }
   EIOKU_REQUIRE(tokens_out && n_out && ended_out && sum_logprob && n_hyp && best_out, "NULL output");
-  for (int i = 0; i < prompt_len; ++i) EIOKU_REQUIRE(prompt[i] >= 0 && prompt[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompt[i]);
+  if (!pre)
+    for (int i = 0; i < prompt_len; ++i)
+      EIOKU_REQUIRE(prompt[i] >= 0 && prompt[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompt[i]);
   if (sync_every < 1) sync_every = 1;
   const int L = B * W, Tm = m->cfg.max_target_positions, eot = m->cfg.eot, H = W > C ? W : C;
   W_TRY(ensure_beam(m, B, L));
+  if (pre) W_TRY(prompted_args(m, prompt, prompt_len, sot_index, windows, B, W, max_new));
+  const int* lane_map = pre ? m->kvmap + m->dcap : nullptr;
   m->flops = 0;
   m->launches = 0;
   m->steps = 0;
@@ -1452,7 +1718,7 @@ int eioku_whisper_decode_beam(eioku_whisper* m, const int32_t* prompt, int promp
   for (int b = 0; b < B; ++b) st[(size_t)b * W] = LaneState{0, -1, -1, -1, 0, 0.f};
   std::vector<uint8_t> ident((size_t)L * Tm);
   for (int l = 0; l < L; ++l)
-    for (int t = 0; t < Tm; ++t) ident[(size_t)l * Tm + t] = (uint8_t)l;
+    for (int t = 0; t < Tm; ++t) ident[(size_t)l * Tm + t] = (uint8_t)((pre && t < prompt_len) ? l / W * W : l);
   std::vector<int> fill((size_t)L * Tm, eot), zeros(B, 0);
   EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
   for (int i = 0; i < 2; ++i) {
@@ -1469,12 +1735,19 @@ int eioku_whisper_decode_beam(eioku_whisper* m, const int32_t* prompt, int promp
   int cur = 0;
   const int last_step = prompt_len - 1 + max_new - 1;
   std::vector<int> flags(B);
-  for (int s = 0; s <= last_step; ++s) {
+  if (pre) {  // the prompt in one pass per window; every slot starts from the window's hidden state at the last prompt position
+    W_TRY(prefill(m, B, prompt_len, m->d_ids, m->kvmap, 1, W));
+    W_TRY(prefill_no_speech(m, B, prompt_len, sot_index));
+    W_TRY(gather_hidden(m, L, prompt_len, prompt_len - 1, W));
+  }
+  for (int s = pre ? prompt_len - 1 : 0; s <= last_step; ++s) {
     const bool forced = s < prompt_len;
-    W_TRY(decoder_step(m, L, s, forced ? nullptr : m->cur_tok, 1, forced ? prompt[s] : 0, W, m->anc[cur]));
-    m->steps += 1;
+    if (!pre || s >= prompt_len) {
+      W_TRY(decoder_step(m, L, s, forced ? nullptr : m->cur_tok, 1, forced ? prompt[s] : 0, W, m->anc[cur], lane_map));
+      m->steps += 1;
+    }
     const int idx = s - (prompt_len - 1);
-    if (s == 0) {  // no-speech probability and language from the unmasked logits of prompt position 0
+    if (s == 0 && !pre) {  // no-speech probability and language from the unmasked logits of prompt position 0
       W_TRY(logits(m, L, 0, nullptr, 0, true));
       hipLaunchKernelGGL(k_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, 0, 1, m->info, m->nlang,
                          m->lang_ids, (int*)nullptr, 0, (int*)nullptr, m->nsp, m->lang_out, (float*)nullptr);
@@ -1542,10 +1815,28 @@ int eioku_whisper_decode_beam(eioku_whisper* m, const int32_t* prompt, int promp
       for (int t = 0; t < max_new; ++t) tokens_out[row * max_new + t] = eot;
       n_out[row] = 0, ended_out[row] = 0, sum_logprob[row] = kNegInf;
     }
-    if (no_speech_prob) no_speech_prob[b] = nsp[(size_t)b * W];
-    if (lang_out) lang_out[b] = lang[(size_t)b * W];
+    if (no_speech_prob) no_speech_prob[b] = nsp[pre ? (size_t)b : (size_t)b * W];
+    if (lang_out) lang_out[b] = lang[pre ? (size_t)b : (size_t)b * W];
   }
   return EIOKU_OK;
+}
+
+}  // namespace
+
+int eioku_whisper_decode_beam(eioku_whisper* m, const int32_t* prompt, int prompt_len, int B, int W, int C, int max_new,
+                              int sync_every, int32_t* tokens_out, int32_t* n_out, int32_t* ended_out, float* sum_logprob,
+                              int32_t* n_hyp, int32_t* best_out, float* no_speech_prob, int32_t* lang_out, int32_t* trace_src,
+                              int32_t* trace_tok) {
+  return beam_impl(m, prompt, prompt_len, false, 0, nullptr, B, W, C, max_new, sync_every, tokens_out, n_out, ended_out, sum_logprob,
+                   n_hyp, best_out, no_speech_prob, lang_out, trace_src, trace_tok);
+}
+
+int eioku_whisper_decode_beam_prompted(eioku_whisper* m, const int32_t* prompts, int P, int sot_index, const int32_t* windows, int B,
+                                       int W, int C, int max_new, int sync_every, int32_t* tokens_out, int32_t* n_out,
+                                       int32_t* ended_out, float* sum_logprob, int32_t* n_hyp, int32_t* best_out, float* no_speech_prob,
+                                       int32_t* trace_src, int32_t* trace_tok) {
+  return beam_impl(m, prompts, P, true, sot_index, windows, B, W, C, max_new, sync_every, tokens_out, n_out, ended_out, sum_logprob,
+                   n_hyp, best_out, no_speech_prob, nullptr, trace_src, trace_tok);
 }
 
 int eioku_whisper_beam_select(eioku_whisper* m, const float* logits_in, int B, int W, int C, const int32_t* prefix, int prefix_cap,
@@ -1577,7 +1868,7 @@ int eioku_whisper_beam_select(eioku_whisper* m, const float* logits_in, int B, i
   if (e == hipSuccess) {
     hipLaunchKernelGGL((k_logits<true, true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in, L,
                        m->sel, m->flags, m->state, 1, m->bpartial, m->nblk, (float*)nullptr, 0LL, (float*)nullptr, (float*)nullptr,
-                       m->nlang, W + 1);
+                       m->nlang, W + 1, 1.f, (const unsigned long long*)nullptr, (const int*)nullptr, 0);
     launch_beam_select(m, B, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, m->b_src, m->b_tok);
     e = hipGetLastError();
     const size_t li = (size_t)L * sizeof(int), bi = (size_t)B * sizeof(int);
@@ -1594,6 +1885,165 @@ int eioku_whisper_beam_select(eioku_whisper* m, const float* logits_in, int B, i
   (void)hipFree(d_in);
   EIOKU_HIP_CHECK(e);
   return EIOKU_OK;
+}
+
+int eioku_whisper_decode_prompted(eioku_whisper* m, const int32_t* prompts, int P, int sot_index, const int32_t* windows, int B, int G,
+                                  float temperature, const uint64_t* seeds, int max_new, int sync_every, int32_t* tokens_out,
+                                  int32_t* n_out, float* sum_logprob, int32_t* best_out, float* no_speech_prob) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m, "NULL model");
+  EIOKU_REQUIRE(temperature >= 0.f && std::isfinite(temperature), "temperature %g must be a finite number >= 0", (double)temperature);
+  if (temperature == 0.f) EIOKU_REQUIRE(G == 1 && !seeds, "temperature 0 is the greedy rule: one row per window and no seeds");
+  else EIOKU_REQUIRE(seeds, "sampling at temperature %g needs a seed per lane", (double)temperature);
+  W_TRY(prompted_args(m, prompts, P, sot_index, windows, B, G, max_new));
+  EIOKU_REQUIRE(tokens_out && n_out && sum_logprob && best_out, "NULL output");
+  if (sync_every < 1) sync_every = 1;
+  const int L = B * G, Tm = m->cfg.max_target_positions;
+  const int* lane_map = m->kvmap + m->dcap;
+  m->flops = 0;
+  m->launches = 0;
+  m->steps = 0;
+  std::vector<LaneState> st(L, LaneState{0, -1, -1, -1, 0, 0.f});
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
+  if (seeds) EIOKU_HIP_CHECK(hipMemcpy(m->d_seeds, seeds, (size_t)L * sizeof(uint64_t), hipMemcpyHostToDevice));
+  W_TRY(prefill(m, B, P, m->d_ids, m->kvmap, G, G));
+  W_TRY(prefill_no_speech(m, B, P, sot_index));
+  W_TRY(gather_hidden(m, L, P, P - 1, G));
+  for (int idx = 0; idx < max_new; ++idx) {
+    if (idx > 0) {
+      W_TRY(decoder_step(m, L, P - 1 + idx, m->cur_tok, 1, 0, 1, nullptr, lane_map));
+      m->steps += 1;
+    }
+    if (temperature == 0.f) {
+      W_TRY(logits(m, L, 1, nullptr, 0, false));
+      hipLaunchKernelGGL(k_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, idx, 0, m->info, m->nlang,
+                         m->lang_ids, m->tokens, Tm, m->cur_tok, m->nsp, m->lang_out, (float*)nullptr);
+    } else {
+      W_TRY(logits_sample(m, L, temperature, idx));
+      hipLaunchKernelGGL(k_sample_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, idx, m->tokens, Tm, m->cur_tok,
+                         (float*)nullptr);
+    }
+    EIOKU_LAUNCH_CHECK();
+    m->launches += 1;
+    if ((idx + 1) % sync_every == 0 && idx + 1 < max_new) {  // read the lane states back: stop once every lane is done
+      EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
+      bool all = true;
+      for (int l = 0; l < L; ++l) all = all && st[l].done;
+      if (all) {  // the rest of every lane is EOT
+        std::vector<int> row(Tm, m->cfg.eot);
+        for (int l = 0; l < L; ++l)
+          EIOKU_HIP_CHECK(hipMemcpy(m->tokens + (size_t)l * Tm + idx + 1, row.data(), (size_t)(max_new - idx - 1) * sizeof(int),
+                                    hipMemcpyHostToDevice));
+        break;
+      }
+    }
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
+  for (int l = 0; l < L; ++l) {
+    EIOKU_HIP_CHECK(hipMemcpy(tokens_out + (size_t)l * max_new, m->tokens + (size_t)l * Tm, (size_t)max_new * sizeof(int),
+                              hipMemcpyDeviceToHost));
+    n_out[l] = st[l].n;
+    sum_logprob[l] = st[l].sum;
+  }
+  for (int b = 0; b < B; ++b) {  // the row with the largest sum / max(1, tokens before EOT), the earlier row on a tie
+    int best = 0;
+    double best_score = 0;
+    for (int g = 0; g < G; ++g) {
+      const LaneState& ls = st[(size_t)b * G + g];
+      const int n_text = ls.n - (ls.done ? 1 : 0);
+      const double score = (double)ls.sum / (n_text > 1 ? n_text : 1);
+      if (g == 0 || score > best_score) best = g, best_score = score;
+    }
+    best_out[b] = best;
+  }
+  if (no_speech_prob) EIOKU_HIP_CHECK(hipMemcpy(no_speech_prob, m->nsp, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
+}
+
+int eioku_whisper_sample(eioku_whisper* m, const float* logits_in, int B, const int32_t* prefix, int prefix_cap,
+                         const int32_t* prefix_len, float temperature, const uint64_t* seeds, const int32_t* idx, int32_t* token_out,
+                         float* logprob_out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && logits_in && B > 0 && B <= 64 && prefix_len && seeds && idx && token_out && logprob_out && prefix_cap >= 0,
+                "bad argument");
+  EIOKU_REQUIRE(temperature > 0.f && std::isfinite(temperature), "temperature %g must be a finite number > 0", (double)temperature);
+  W_TRY(ensure_capacity(m, B));
+  const int V = m->cfg.vocab;
+  std::vector<LaneState> st(B);
+  for (int b = 0; b < B; ++b) {
+    const int n = prefix_len[b];
+    EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
+    EIOKU_REQUIRE(idx[b] >= 0 && idx[b] < m->cfg.max_target_positions, "sample index %d outside 0..%d", idx[b],
+                  m->cfg.max_target_positions - 1);
+    st[b] = state_of_prefix(n ? prefix + (size_t)b * prefix_cap : nullptr, n, m->cfg.timestamp_begin);
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_seeds, seeds, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_sidx, idx, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  float* d_in = nullptr;
+  W_TRY(dalloc(&d_in, (size_t)B * V));
+  hipError_t e = hipMemcpy(d_in, logits_in, (size_t)B * V * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL((k_logits<true, false, true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in,
+                       B, m->sel, m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, (float*)nullptr, (float*)nullptr,
+                       m->nlang, 0, temperature, m->d_seeds, m->d_sidx, 0);
+    hipLaunchKernelGGL(k_sample_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, (int*)nullptr, 0, m->cur_tok,
+                       m->d_logprob);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(token_out, m->cur_tok, (size_t)B * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(logprob_out, m->d_logprob, (size_t)B * sizeof(float), hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(d_in);
+  EIOKU_HIP_CHECK(e);
+  return EIOKU_OK;
+}
+
+int eioku_whisper_prefill_logits(eioku_whisper* m, const int32_t* ids, int T, int B, int n_prefill, float* out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && ids && out && T >= 1 && T <= m->cfg.max_target_positions, "bad argument");
+  EIOKU_REQUIRE(n_prefill >= 1 && n_prefill <= T, "prefill of %d positions outside 1..%d", n_prefill, T);
+  EIOKU_REQUIRE(B > 0 && B == m->enc_B, "prefill_logits of %d lanes needs an encode of the same %d windows first", B, m->enc_B);
+  const int V = m->cfg.vocab, P = n_prefill;
+  for (size_t i = 0; i < (size_t)B * T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < V, "id %d outside the vocabulary", ids[i]);
+  W_TRY(ensure_lanes(m, B));
+  std::vector<int> head((size_t)B * P);
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < P; ++t) head[(size_t)b * P + t] = ids[(size_t)b * T + t];
+  int* d_head = nullptr;
+  float* d_out = nullptr;
+  W_TRY(dalloc(&d_head, head.size()));
+  int rc = dalloc(&d_out, (size_t)B * T * V);
+  std::vector<LaneState> st(B, LaneState{0, -1, -1, -1, 0, 0.f});
+  auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (rc == EIOKU_OK && hipMemcpy(dst, src, bytes, kind) != hipSuccess) {
+      set_error("hipMemcpy failed: %s", hipGetErrorString(hipGetLastError()));
+      rc = EIOKU_EHIP;
+    }
+  };
+  copy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice);
+  copy(m->d_ids, ids, (size_t)B * T * sizeof(int), hipMemcpyHostToDevice);
+  copy(d_head, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice);
+  m->flops = 0;
+  m->launches = 0;
+  m->steps = 0;
+  if (rc == EIOKU_OK) rc = prefill(m, B, P, d_head, nullptr, 1, 1);
+  for (int b = 0; b < B && rc == EIOKU_OK; ++b) {  // the logits of row b's P positions: out[b][0 .. P - 1]
+    hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->ph + (size_t)b * P * m->cfg.d_model, m->cfg.d_model,
+                       m->H(m->emb), nullptr, P, m->sel, m->flags, m->state, 0, m->ppartial, m->nblk, d_out + (size_t)b * T * V,
+                       (long long)V, nullptr, nullptr, m->nlang, 0, 1.f, nullptr, nullptr, 0);
+    if (hipGetLastError() != hipSuccess) {
+      set_error("launch of the prefill logits failed");
+      rc = EIOKU_EHIP;
+    }
+  }
+  for (int s = P; s < T && rc == EIOKU_OK; ++s) {  // the positions after the prefill walk on its keys and values
+    rc = decoder_step(m, B, s, m->d_ids + s, T, 0);
+    if (rc == EIOKU_OK) rc = logits(m, B, 0, d_out + (size_t)s * V, (long long)T * V, false);
+  }
+  copy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(d_head);
+  (void)hipFree(d_out);
+  return rc;
 }
 
 int eioku_whisper_last_flops(const eioku_whisper* m, double* flops) {

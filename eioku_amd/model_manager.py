@@ -231,7 +231,9 @@ class ModelManager:
         """Whisper on the HIP path when the manager was built with ``gpu_transcription=True`` (reference: :406-467, which
         calls faster-whisper on the CPU); otherwise refused as before.  Result: ``{"segments": [{start_ms, end_ms, text,
         language, confidence: None, words: None}]}``.  Greedy decoding by default; config ``beam_size`` (1..8; 5 is the
-        reference's call) and ``patience`` switch to beam search, values outside their ranges raise ``ValueError``.  The
+        reference's call) and ``patience`` switch to beam search, ``temperature`` (a list) with ``best_of`` and the two
+        thresholds adds the temperature fallback, ``condition_on_previous_text`` the previous-text prompts
+        (``transcribe.REFERENCE_CALL`` is the reference's call); values outside their ranges raise ``ValueError``.  The
         deviations from the reference's call are listed in INTEGRATION.md §3."""
         if not self._gpu_transcription:
             raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")

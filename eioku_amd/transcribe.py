@@ -1,4 +1,5 @@
-"""Transcription on the HIP path: Whisper log-mel (K19), greedy decode with timestamp rules (K20) and beam search (K20b).
+"""Transcription on the HIP path: Whisper log-mel (K19), greedy decode with timestamp rules (K20), beam search (K20b),
+sampling at a temperature and the one-pass prompt prefill (K20c).
 
 The reference calls ``faster_whisper.WhisperModel.transcribe`` (``model_manager.py:406-467``), which has no ROCm backend.
 This module keeps its result dict and replaces the arithmetic: the audio goes up once, ``csrc/whisper.hip`` computes the
@@ -6,8 +7,8 @@ log-mel windows, the encoder, and the decoder steps with token selection on the 
 lists into segments (Whisper's seek rule) and turns ids into text (byte-level BPE from ``vocab.json``).
 
 Deviations from the reference's call are listed in INTEGRATION.md §3: greedy by default (``beam_size: 5`` restores the
-reference's beam search), no temperature fallback, no compression-ratio check, no conditioning on previous text,
-``vad_filter`` accepted but not applied, integer millisecond times.  There is no CPU fallback: without the library or a
+reference's beam search), temperature fallback and conditioning on previous text are opt-in config keys
+(:func:`check_fallback`), ``vad_filter`` accepted but not applied, integer millisecond times.  There is no CPU fallback: without the library or a
 gfx950 device every compute call raises.
 """
 
@@ -19,6 +20,7 @@ import logging
 import math
 import struct
 import wave
+import zlib
 from pathlib import Path
 
 import numpy as np
@@ -35,6 +37,105 @@ LOGPROB_THRESHOLD = -1.0
 MAX_BEAM = 8              # beam slots per window on the device
 MAX_LANES = 64            # windows x beam decoded in lockstep
 MAX_FINISH = 16           # finished hypotheses a window can keep (round(beam x patience))
+
+
+MAX_BEST_OF = 8           # sampled rows per window at a temperature > 0
+REFERENCE_TEMPERATURES = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)     # faster-whisper's default schedule
+_M64 = (1 << 64) - 1
+
+
+def _is_number(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)
+
+
+def check_fallback(temperature=0.0, best_of=5, compression_ratio_threshold=2.4, log_prob_threshold=-1.0,
+                   condition_on_previous_text=False, prompt_reset_on_temperature=0.5, seed=0) -> dict:
+    """The temperature-fallback and conditioning keys, normalised, or ``ValueError``.  ``temperature``: a number or a
+    non-empty list of numbers >= 0, tried in turn; ``best_of`` 1..8 rows sampled per window at a temperature > 0;
+    the two thresholds are numbers (the compression ratio's positive) or None = off; ``condition_on_previous_text`` a bool;
+    ``prompt_reset_on_temperature`` a number >= 0; ``seed`` an integer in 0 .. 2^64 - 1."""
+    temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
+    if not temps or not all(_is_number(t) and t >= 0 for t in temps):
+        raise ValueError(f"temperature must be a number >= 0 or a non-empty list of them, got {temperature!r}")
+    if not _is_number(best_of) or int(best_of) != best_of or not 1 <= int(best_of) <= MAX_BEST_OF:
+        raise ValueError(f"best_of must be an integer in 1..{MAX_BEST_OF}, got {best_of!r}")
+    if compression_ratio_threshold is not None and not (_is_number(compression_ratio_threshold) and compression_ratio_threshold > 0):
+        raise ValueError(f"compression_ratio_threshold must be a positive number or None, got {compression_ratio_threshold!r}")
+    if log_prob_threshold is not None and not _is_number(log_prob_threshold):
+        raise ValueError(f"log_prob_threshold must be a number or None, got {log_prob_threshold!r}")
+    if not isinstance(condition_on_previous_text, (bool, np.bool_)):
+        raise ValueError(f"condition_on_previous_text must be a bool, got {condition_on_previous_text!r}")
+    if not _is_number(prompt_reset_on_temperature) or prompt_reset_on_temperature < 0:
+        raise ValueError(f"prompt_reset_on_temperature must be a number >= 0, got {prompt_reset_on_temperature!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) <= _M64:
+        raise ValueError(f"seed must be an integer in 0..2^64-1, got {seed!r}")
+    return {"temperature": tuple(float(t) for t in temps), "best_of": int(best_of),
+            "compression_ratio_threshold": None if compression_ratio_threshold is None else float(compression_ratio_threshold),
+            "log_prob_threshold": None if log_prob_threshold is None else float(log_prob_threshold),
+            "condition_on_previous_text": bool(condition_on_previous_text),
+            "prompt_reset_on_temperature": float(prompt_reset_on_temperature), "seed": int(seed)}
+
+
+FALLBACK_KEYS = tuple(check_fallback())
+
+
+def compression_ratio(text: str) -> float:
+    """Whisper's loop detector: utf-8 bytes of the text over their zlib-compressed length."""
+    raw = text.encode("utf-8")
+    return len(raw) / len(zlib.compress(raw))
+
+
+def _mix64(z: int) -> int:
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def lane_seed(seed: int, start_frame: int, temperature_index: int, row: int) -> int:
+    """The noise stream of one sampled row: a function of the run's seed, the window's first mel frame, the position of the
+    temperature in the schedule and the row among ``best_of`` - and of nothing else, so a window samples the same tokens
+    whatever batch it is decoded in."""
+    z = int(seed) & _M64
+    for v in (start_frame, temperature_index, row):
+        z = _mix64((z + (int(v) + 1) * 0x9E3779B97F4A7C15) & _M64)
+    return z
+
+
+def needs_fallback(avg_logprob: float, ratio: float, no_speech_prob: float, compression_ratio_threshold, log_prob_threshold) -> bool:
+    """Whether a window has to be decoded again at the next temperature: its text loops (compression ratio above the
+    threshold) or its average log-probability is below the threshold - unless it is silence (``no_speech_prob > 0.6`` with
+    the average below the threshold), which no temperature improves."""
+    needs = compression_ratio_threshold is not None and ratio > compression_ratio_threshold
+    low = log_prob_threshold is not None and avg_logprob < log_prob_threshold
+    if no_speech_prob > NO_SPEECH_THRESHOLD and low:
+        return False
+    return bool(needs or low)
+
+
+def pick_fallback(tried: list[dict], compression_ratio_threshold) -> dict:
+    """Every temperature failed: the try with the highest average log-probability, among those within the compression
+    threshold when there are any (faster-whisper's rule; OpenAI's ``transcribe`` keeps the last try instead)."""
+    ok = [r for r in tried if compression_ratio_threshold is None or r["compression_ratio"] <= compression_ratio_threshold]
+    pool = ok or tried
+    best = pool[0]
+    for r in pool[1:]:
+        if r["avg_logprob"] > best["avg_logprob"]:
+            best = r
+    return best
+
+
+def emitted_tokens(tokens, eot: int, timestamp_begin: int) -> list[int]:
+    """The sampled ids that :func:`cut_window` turns into segments, timestamps included, EOT excluded: everything up to the
+    last consecutive timestamp pair when the window is cut there, otherwise everything before EOT."""
+    toks = []
+    for t in tokens:
+        if int(t) == eot:
+            break
+        toks.append(int(t))
+    is_ts = [t >= timestamp_begin for t in toks]
+    single_ending = len(toks) >= 2 and is_ts[-1] and not is_ts[-2]
+    cuts = [i + 1 for i in range(len(toks) - 1) if is_ts[i] and is_ts[i + 1]]
+    return toks[:cuts[-1]] if cuts and not single_ending else toks
 
 
 def finish_count(beam_size: int, patience: float) -> int:
@@ -238,6 +339,8 @@ def whisper_dims(config: dict, generation_config: dict) -> dict:
         "no_timestamps": no_ts, "timestamp_begin": no_ts + 1,
         # <|nospeech|> sits right before <|notimestamps|> in every Whisper vocabulary
         "no_speech": int(gen.get("no_speech_token_id", no_ts - 1)),
+        # <|startofprev|> sits right before <|nospeech|>
+        "sot_prev": int(gen.get("prev_sot_token_id", int(gen.get("no_speech_token_id", no_ts - 1)) - 1)),
         "max_initial_timestamp_index": int(gen.get("max_initial_timestamp_index", 50)),
         "suppress": [int(t) for t in gen.get("suppress_tokens") or []],
         "begin_suppress": [int(t) for t in gen.get("begin_suppress_tokens") or []],
@@ -443,6 +546,87 @@ class WhisperTranscriber:
                         "fin_count": int(fc_out[b]), "complete": bool(complete[b])})
         return out
 
+    def decode_prompted(self, prompts, sot_index: int, max_new_tokens: int, *, windows=None, group: int = 1,
+                        temperature: float = 0.0, seeds=None, sync_every: int | None = None) -> dict:
+        """K20c: rows with prompts ``[B][P]`` (one common length) prefilled in one pass, then ``group`` lanes per row decoded in
+        lockstep.  ``windows[b]``: the encoded window row ``b`` reads (None: identity).  ``temperature == 0`` is the greedy
+        rule (``group`` 1, no seeds); above 0 every lane samples with its own ``seeds[b][g]``.  ``tokens`` [B][G][max_new],
+        ``n`` / ``sum_logprob`` [B][G], ``best`` [B], ``no_speech_prob`` [B] (at prompt position ``sot_index``)."""
+        p = np.ascontiguousarray(prompts, dtype=np.int32)
+        if p.ndim != 2:
+            raise ValueError("prompts must be [rows][P]: one common prompt length")
+        B, P, G, n = p.shape[0], p.shape[1], int(group), int(max_new_tokens)
+        win = None if windows is None else np.ascontiguousarray(windows, dtype=np.int32)
+        if win is not None and win.shape != (B,):
+            raise ValueError("windows names one encoded window per row")
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != B * G:
+            raise ValueError("seeds must hold one value per lane (rows x group)")
+        tokens = np.zeros((B, G, max(n, 1)), dtype=np.int32)
+        n_out, total = np.zeros((B, G), dtype=np.int32), np.zeros((B, G), dtype=np.float32)
+        best, nsp = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)
+        self._lib_mod.check(self.lib.eioku_whisper_decode_prompted(
+            self._h, p.ctypes.data, P, int(sot_index), win.ctypes.data if win is not None else None, B, G, float(temperature),
+            sd.ctypes.data if sd is not None else None, n, int(sync_every or self.sync_every), tokens.ctypes.data,
+            n_out.ctypes.data, total.ctypes.data, best.ctypes.data, nsp.ctypes.data), "eioku_whisper_decode_prompted")
+        return {"tokens": tokens, "n": n_out, "sum_logprob": total, "best": best, "no_speech_prob": nsp}
+
+    def decode_beam_prompted(self, prompts, sot_index: int, max_new_tokens: int, beam_size: int, patience: float = 1.0, *,
+                             windows=None, sync_every: int | None = None, trace: bool = False) -> dict:
+        """:meth:`decode_beam` with per-window prompts ``[B][P]`` prefilled once per window, the no-speech probability at
+        ``sot_index`` and the row -> window map of :meth:`decode_prompted`.  The same outputs, without ``lang``."""
+        W, patience = check_beam(beam_size, patience)
+        p = np.ascontiguousarray(prompts, dtype=np.int32)
+        if p.ndim != 2:
+            raise ValueError("prompts must be [windows][P]: one common prompt length")
+        B, P, n, Cn = p.shape[0], p.shape[1], int(max_new_tokens), finish_count(W, patience)
+        win = None if windows is None else np.ascontiguousarray(windows, dtype=np.int32)
+        if win is not None and win.shape != (B,):
+            raise ValueError("windows names one encoded window per row")
+        H = max(W, Cn)
+        tokens = np.zeros((B, H, max(n, 1)), dtype=np.int32)
+        n_out, ended = np.zeros((B, H), dtype=np.int32), np.zeros((B, H), dtype=np.int32)
+        total = np.zeros((B, H), dtype=np.float32)
+        n_hyp, best = (np.zeros(B, dtype=np.int32) for _ in range(2))
+        nsp = np.zeros(B, dtype=np.float32)
+        tr_src, tr_tok = (np.full((max(n, 1), B, W), -1, dtype=np.int32) for _ in range(2))
+        self._lib_mod.check(self.lib.eioku_whisper_decode_beam_prompted(
+            self._h, p.ctypes.data, P, int(sot_index), win.ctypes.data if win is not None else None, B, W, Cn, n,
+            int(sync_every or self.sync_every), tokens.ctypes.data, n_out.ctypes.data, ended.ctypes.data, total.ctypes.data,
+            n_hyp.ctypes.data, best.ctypes.data, nsp.ctypes.data, tr_src.ctypes.data if trace else None,
+            tr_tok.ctypes.data if trace else None), "eioku_whisper_decode_beam_prompted")
+        out = {"tokens": tokens, "n": n_out, "ended": ended, "sum_logprob": total, "n_hyp": n_hyp, "best": best, "no_speech_prob": nsp}
+        if trace:
+            out["trace_src"], out["trace_tok"] = tr_src, tr_tok
+        return out
+
+    def sample(self, logits, prefixes, temperature: float, seeds, idx) -> tuple[np.ndarray, np.ndarray]:
+        """Debug: rules + Gumbel-max sampling on supplied logits [B][vocab]; per lane a prefix, a seed and a sample index."""
+        logits = np.ascontiguousarray(logits, dtype=np.float32)
+        B, cap = logits.shape[0], max(1, max(len(p) for p in prefixes))
+        pre = np.zeros((B, cap), dtype=np.int32)
+        for b, p in enumerate(prefixes):
+            pre[b, :len(p)] = p
+        plen = np.asarray([len(p) for p in prefixes], dtype=np.int32)
+        sd, ix = np.ascontiguousarray(seeds, dtype=np.uint64), np.ascontiguousarray(idx, dtype=np.int32)
+        if len(prefixes) != B or sd.shape != (B,) or ix.shape != (B,):
+            raise ValueError("prefixes, seeds and idx are per lane")
+        tok, lp = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)
+        self._lib_mod.check(self.lib.eioku_whisper_sample(self._h, logits.ctypes.data, B, pre.ctypes.data, cap, plen.ctypes.data,
+                                                          float(temperature), sd.ctypes.data, ix.ctypes.data, tok.ctypes.data,
+                                                          lp.ctypes.data), "eioku_whisper_sample")
+        return tok, lp
+
+    def prefill_logits(self, ids, n_prefill: int | None = None) -> np.ndarray:
+        """Debug: rule-free logits [B][T][vocab] of ids [B][T]; the first ``n_prefill`` (default: all) positions in one
+        prefill pass, the others position by position on the keys and values it left."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        out = np.empty(ids.shape + (self.dims["vocab"],), dtype=np.float32)
+        self._lib_mod.check(self.lib.eioku_whisper_prefill_logits(
+            self._h, ids.ctypes.data, ids.shape[1], ids.shape[0], int(ids.shape[1] if n_prefill is None else n_prefill),
+            out.ctypes.data), "eioku_whisper_prefill_logits")
+        return out
+
     def forced_logits(self, ids) -> np.ndarray:
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         out = np.empty(ids.shape + (self.dims["vocab"],), dtype=np.float32)
@@ -494,7 +678,7 @@ class WhisperTranscriber:
 
     def transcribe(self, samples: np.ndarray, language: str | None = None, *, window_mode: str = "seek",
                    batch_windows: int = 8, max_new_tokens: int | None = None, beam_size: int = 1,
-                   patience: float = 1.0) -> dict:
+                   patience: float = 1.0, **fallback) -> dict:
         """-> ``{"segments": [{start_ms, end_ms, text, language, confidence: None, words: None}], "language": code}``.
 
         ``window_mode="seek"``: one window at a time, the next one starts where Whisper's seek rule says.
@@ -503,10 +687,28 @@ class WhisperTranscriber:
 
         ``beam_size=1`` decodes greedily.  ``beam_size > 1`` runs beam search with Whisper's ``patience`` and keeps each
         window's best hypothesis by length-normalised log-probability (``faster_whisper``'s call: 5 and 1.0); in ``fixed``
-        mode a batch is split so that windows x beam stays within the device's 64 lanes."""
+        mode a batch is split so that windows x beam stays within the device's 64 lanes.
+
+        ``**fallback``: the keys of :func:`check_fallback`.  With a temperature schedule, a window whose text loops or whose
+        average log-probability is poor is decoded again at the next temperature (``best_of`` sampled rows, the best kept;
+        ``beam_size`` applies at temperature 0 only); when every temperature fails the try with the highest average
+        log-probability is kept, among those within the compression threshold when there are any (faster-whisper's rule).
+        ``condition_on_previous_text`` (``seek`` mode only) puts up to ``max_target_positions // 2 - 1`` previous tokens
+        behind ``<|startofprev|>`` in front of the prompt; a window accepted above ``prompt_reset_on_temperature`` resets
+        them.  Raw segments then also carry ``temperature``, ``avg_logprob`` and ``compression_ratio``, and the raw result a
+        ``windows`` list with the same figures per decoded window.  With none of these keys the device calls are the ones
+        above."""
         if window_mode not in ("seek", "fixed"):
             raise ValueError(f"window_mode must be 'seek' or 'fixed', got {window_mode!r}")
         beam_size, patience = check_beam(beam_size, patience)
+        unknown = sorted(set(fallback) - set(FALLBACK_KEYS))
+        if unknown:
+            raise TypeError(f"transcribe() got unexpected keyword arguments {unknown}")
+        if fallback:
+            fb = check_fallback(**fallback)
+            if fb["condition_on_previous_text"] and window_mode != "seek":
+                raise ValueError("condition_on_previous_text needs window_mode='seek': fixed windows decode in lockstep")
+            return self._transcribe_fallback(samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb)
         d = self.dims
         samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
         content_frames = len(samples) // HOP
@@ -564,6 +766,129 @@ class WhisperTranscriber:
         code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
         return {"segments": segments, "language": code}
 
+    def _transcribe_fallback(self, samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb) -> dict:
+        """:meth:`WhisperTranscriber.transcribe` with the temperature fallback and previous-text prompts."""
+        d = self.dims
+        Tm, eot, tb = d["max_target_positions"], d["eot"], d["timestamp_begin"]
+        samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        content_frames = len(samples) // HOP
+        lang_id = self._language_token(language)
+        if content_frames == 0:
+            return {"segments": [], "language": language}
+        self.set_audio(samples)
+        temps, best_of = fb["temperature"], fb["best_of"]
+        crt, lpt = fb["compression_ratio_threshold"], fb["log_prob_threshold"]
+        sot_prev = d.get("sot_prev")
+        if sot_prev is None:
+            sot_prev = d["no_speech"] - 1   # <|startofprev|> sits right before <|nospeech|> in every Whisper vocabulary
+        segments: list[dict] = []
+        windows_log: list[dict] = []
+        all_tokens: list[int] = []
+        reset = 0
+
+        def build_prompt() -> tuple[list[int], int]:
+            base = self._prompt(lang_id)
+            prev = all_tokens[reset:][-(Tm // 2 - 1):] if fb["condition_on_previous_text"] else []
+            return ([sot_prev] + prev + base, 1 + len(prev)) if prev else (base, 0)
+
+        def describe(tokens, total, nsp, temperature) -> dict:
+            toks = [int(t) for t in tokens]
+            n_text = toks.index(eot) if eot in toks else len(toks)
+            text = self.decoder.decode([t for t in toks[:n_text] if t < eot])
+            return {"tokens": toks, "sum_logprob": float(total), "no_speech_prob": float(nsp), "temperature": float(temperature),
+                    "avg_logprob": float(total) / (n_text + 1), "compression_ratio": compression_ratio(text)}
+
+        def decode_all(seeks: list[int]) -> list[dict]:
+            """One encode of the windows, then the temperature schedule over the windows that still need another try."""
+            nonlocal lang_id
+            self.logmel([s * HOP for s in seeks], fetch=False)
+            self.encode(len(seeks))
+            if lang_id is None and d["lang_ids"]:
+                lang_id = int(self.decode([d["sot"]], len(seeks), 0)["lang"][0])
+            prompt, sot_index = build_prompt()
+            max_new = min(Tm // 2, Tm - len(prompt))
+            if max_new_tokens is not None:
+                max_new = min(max_new, int(max_new_tokens))
+            tried: list[list[dict]] = [[] for _ in seeks]
+            accepted: list[dict | None] = [None] * len(seeks)
+            pending = list(range(len(seeks)))
+            for ti, temp in enumerate(temps):
+                if not pending:
+                    break
+                rows = 1 if temp > 0 else beam_size
+                per_call = max(1, MAX_LANES // (best_of if temp > 0 else rows))
+                for i in range(0, len(pending), per_call):
+                    part = pending[i:i + per_call]
+                    windows = None if part == list(range(len(seeks))) else part
+                    prompts = [prompt] * len(part)
+                    if temp > 0:
+                        seeds = [[lane_seed(fb["seed"], seeks[w], ti, g) for g in range(best_of)] for w in part]
+                        res = self.decode_prompted(prompts, sot_index, max_new, windows=windows, group=best_of, temperature=temp,
+                                                   seeds=seeds)
+                    elif beam_size == 1:
+                        res = self.decode_prompted(prompts, sot_index, max_new, windows=windows)
+                    else:
+                        res = self.decode_beam_prompted(prompts, sot_index, max_new, beam_size, patience, windows=windows)
+                    for k, w in enumerate(part):
+                        row = int(res["best"][k])
+                        tried[w].append(describe(res["tokens"][k][row], res["sum_logprob"][k][row], res["no_speech_prob"][k], temp))
+                still = []
+                for w in pending:
+                    r = tried[w][-1]
+                    if needs_fallback(r["avg_logprob"], r["compression_ratio"], r["no_speech_prob"], crt, lpt):
+                        still.append(w)
+                    else:
+                        accepted[w] = r
+                pending = still
+            for w in pending:
+                accepted[w] = pick_fallback(tried[w], crt)
+            return accepted
+
+        def emit(r: dict, seek: int) -> int:
+            nonlocal reset
+            size = min(self.window_frames, content_frames - seek)
+            windows_log.append({"start_frame": seek, **{k: r[k] for k in ("temperature", "avg_logprob", "compression_ratio",
+                                                                          "no_speech_prob")}})
+            if r["no_speech_prob"] > NO_SPEECH_THRESHOLD and (lpt is None or r["avg_logprob"] < lpt):
+                return size
+            pieces, advance = cut_window(r["tokens"], eot, tb, seek * MS_PER_FRAME, size)
+            code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
+            for start_ms, end_ms, ids in pieces:
+                text = self.decoder.decode(ids)
+                if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
+                    continue
+                segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code, "confidence": None,
+                                 "words": None, "tokens": ids, "temperature": r["temperature"], "avg_logprob": r["avg_logprob"],
+                                 "compression_ratio": r["compression_ratio"]})
+            if fb["condition_on_previous_text"]:
+                all_tokens.extend(emitted_tokens(r["tokens"], eot, tb))
+                if r["temperature"] > fb["prompt_reset_on_temperature"]:
+                    reset = len(all_tokens)
+            return max(1, min(advance, size)) if window_mode == "seek" else size
+
+        if window_mode == "seek":
+            seek = 0
+            while seek < content_frames:
+                seek += emit(decode_all([seek])[0], seek)
+        else:
+            starts = list(range(0, content_frames, self.window_frames))
+            per_batch = max(1, int(batch_windows))
+            if beam_size > 1:
+                per_batch = min(per_batch, MAX_LANES // beam_size)
+            for i in range(0, len(starts), per_batch):
+                batch = starts[i:i + per_batch]
+                for r, s_ in zip(decode_all(batch), batch):
+                    emit(r, s_)
+        code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
+        return {"segments": segments, "language": code, "windows": windows_log}
+
+
+# the config under which transcribe_video decodes as the reference's WhisperModel.transcribe(path, language=..., vad_filter=...)
+# does with faster-whisper's defaults
+REFERENCE_CALL = {"beam_size": 5, "patience": 1.0, "temperature": list(REFERENCE_TEMPERATURES), "best_of": 5,
+                  "compression_ratio_threshold": 2.4, "log_prob_threshold": -1.0, "condition_on_previous_text": True,
+                  "prompt_reset_on_temperature": 0.5}
+
 
 def transcribe_result(raw: dict) -> dict:
     """The reference's result dict (``model_manager.py:449-463``): exactly its six keys per segment."""
@@ -575,7 +900,10 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None)
     """``ModelManager.transcribe_video`` body.  Config keys consumed: ``languages`` (string or list: the first entry; None =
     detect), ``vad_filter`` (accepted, not applied), ``window_mode``, ``batch_windows``, ``beam_size`` (1..8, default 1 =
     greedy; 5 is the reference's call) and ``patience`` (positive, default 1.0); ``model_name`` picks the checkpoint in the
-    caller.  ``beam_size`` / ``patience`` are passed to the transcriber only when the config sets them."""
+    caller.  ``beam_size`` / ``patience`` are passed to the transcriber only when the config sets them, and so are the
+    temperature-fallback and conditioning keys of :func:`check_fallback` (``temperature``, ``best_of``,
+    ``compression_ratio_threshold``, ``log_prob_threshold``, ``condition_on_previous_text``,
+    ``prompt_reset_on_temperature``, ``seed``); the reference's call is :data:`REFERENCE_CALL`."""
     config = config or {}
     languages = config.get("languages")
     if isinstance(languages, (list, tuple)):
@@ -589,9 +917,15 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None)
             beam["beam_size"] = b
         if "patience" in config:
             beam["patience"] = pt
+    given = {k: config[k] for k in FALLBACK_KEYS if k in config}
+    if given:
+        fb = check_fallback(**given)
+        if fb["condition_on_previous_text"] and config.get("window_mode", "seek") != "seek":
+            raise ValueError("condition_on_previous_text needs window_mode 'seek': fixed windows decode in lockstep")
+        given = {k: (list(fb[k]) if k == "temperature" else fb[k]) for k in given}
     samples, rate = (audio_source or default_audio_source)(path)
     check_rate(rate)
     raw = transcriber.transcribe(np.asarray(samples, dtype=np.float32), languages,
                                  window_mode=config.get("window_mode", "seek"),
-                                 batch_windows=int(config.get("batch_windows", 8)), **beam)
+                                 batch_windows=int(config.get("batch_windows", 8)), **beam, **given)
     return transcribe_result(raw)

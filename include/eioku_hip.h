@@ -606,6 +606,22 @@ int eioku_thumbs_last_ms(eioku_thumbs_t* t, double* ms4);
  *   and sums [B * W] (-inf = a dead slot) describe the slots, fin_count [B] the finished hypotheses each window has.
  *   src_out / tok_out / sum_out [B][W] with n_live [B]: the next slots; fsrc_out / fsum_out [B][W] with n_fin [B]: the
  *   candidates that ended on EOT in walk order; fin_count_out [B] = min(C, fin_count + n_fin); complete_out [B].
+ * decode_prompted (K20c): B rows with prompts [B][P] of one common length, each run through the decoder in ONE pass (the
+ *   prompt prefill), then G lanes per row decoded in lockstep, B * G <= 64 and P + max_new_tokens <= max_target_positions.
+ *   Row b reads encoded window windows[b]; windows NULL = identity, which needs B == the encoded windows.  temperature == 0:
+ *   the greedy rule of `decode`, G == 1 and seeds NULL.  temperature > 0: every lane samples by Gumbel-max inside the
+ *   selection path: score = masked logit / temperature - log(-log(u)), u = ((z >> 41) + 0.5) * 2^-23, z = element
+ *   idx * vocab + id of the splitmix64 stream seeds[lane] (idx: the index of the sampled token); the token is the best
+ *   score of the unmasked ids after the timestamp-mass rule, the lower id on equal scores.  sum_logprob adds the
+ *   untempered log-softmax of the masked logits.  tokens_out [B][G][max_new_tokens] (EOT-filled), n_out / sum_logprob
+ *   [B][G], best_out [B] = the row with the largest sum_logprob / max(1, tokens before EOT) (ties: the earlier row),
+ *   no_speech_prob [B] from the logits at prompt position sot_index (may be NULL).
+ * decode_beam_prompted: decode_beam with prompts [B][P], sot_index and windows as above; the prompt is prefilled once per
+ *   window and the ancestry table names slot 0's lane for every prompt position.  Outputs as decode_beam (no language).
+ * sample (tests): the rule + sampling stage on supplied logits [B][vocab] at temperature > 0 with seeds [B] and sample
+ *   indices idx [B]; token_out [B], logprob_out [B].
+ * prefill_logits (tests): rule-free logits [B][T][vocab] for ids [B][T]: positions 0 .. n_prefill - 1 in one prefill pass,
+ *   the others walked position by position on the keys and values the prefill left.
  * last_launches: kernel launches of the last decode and its number of decoder steps. */
 typedef struct {
   int n_mels, d_model, heads, enc_layers, dec_layers, enc_ffn, dec_ffn, vocab, max_source_positions, max_target_positions;
@@ -639,6 +655,19 @@ int eioku_whisper_beam_select(eioku_whisper_t* m, const float* logits, int B, in
                               int prefix_cap, const int32_t* prefix_len, const float* sums, const int32_t* fin_count,
                               int32_t* src_out, int32_t* tok_out, float* sum_out, int32_t* n_live, int32_t* fsrc_out,
                               float* fsum_out, int32_t* n_fin, int32_t* fin_count_out, int32_t* complete_out);
+int eioku_whisper_decode_prompted(eioku_whisper_t* m, const int32_t* prompts, int prompt_len, int sot_index,
+                                  const int32_t* windows, int B, int G, float temperature, const uint64_t* seeds,
+                                  int max_new_tokens, int sync_every, int32_t* tokens_out, int32_t* n_out, float* sum_logprob,
+                                  int32_t* best_out, float* no_speech_prob);
+int eioku_whisper_decode_beam_prompted(eioku_whisper_t* m, const int32_t* prompts, int prompt_len, int sot_index,
+                                       const int32_t* windows, int B, int beam, int n_finish, int max_new_tokens,
+                                       int sync_every, int32_t* tokens_out, int32_t* n_out, int32_t* ended_out,
+                                       float* sum_logprob, int32_t* n_hyp, int32_t* best_out, float* no_speech_prob,
+                                       int32_t* trace_src, int32_t* trace_tok);
+int eioku_whisper_sample(eioku_whisper_t* m, const float* logits, int B, const int32_t* prefix, int prefix_cap,
+                         const int32_t* prefix_len, float temperature, const uint64_t* seeds, const int32_t* idx,
+                         int32_t* token_out, float* logprob_out);
+int eioku_whisper_prefill_logits(eioku_whisper_t* m, const int32_t* ids, int T, int B, int n_prefill, float* logits_out);
 int eioku_whisper_encoder_output(eioku_whisper_t* m, void* out_f16, size_t numel);
 int eioku_whisper_last_flops(const eioku_whisper_t* m, double* flops);
 int eioku_whisper_last_launches(const eioku_whisper_t* m, int* launches, int* steps);

@@ -3,6 +3,7 @@
 
     python tools/whisper_bench.py [--shapes base small] [--windows 64] [--out profiles/whisper.json]
     python tools/whisper_bench.py --beam 5 [--shapes base]      # adds a beam block to the shapes already in --out
+    python tools/whisper_bench.py --prompted [--shapes base]    # adds a prompted block (K20c) in the same way
 
 For each shape (the openai `base` and `small` dimensions, vocabulary 51865, ctx 1500): log-mel over `--windows` windows of
 30 s, the encoder per window at batch 8, a decoder step at B = 1, 8 and 32 (greedy, 32 sampled tokens, lanes never end
@@ -12,6 +13,10 @@ time plus one launch-queue drain.  No number here is an acceptance bar.
 
 `--beam W` measures beam search only (K20b): a decoder step and the launches per step at B = 1 and 8 windows (W lanes each),
 with the greedy step of the same run next to it, and merges the block into the shape's row of `--out`, leaving the rest.
+
+`--prompted` measures K20c only: a 227-token prompt (``<|startofprev|>`` + 223 previous tokens + 3) through the one-pass
+prefill (`decode_prompted`, one new token) against the same prompt walked position by position by `decode` with one new
+token, at 1 and 8 windows; and a sampled step (temperature 1) against a greedy step of the same entry at 8 lanes.
 """
 from __future__ import annotations
 
@@ -68,6 +73,27 @@ def beam_block(t, dims: dict, audio: np.ndarray, beam: int, steps: int) -> dict:
     return block
 
 
+def prompted_block(t, dims: dict, audio: np.ndarray, steps: int) -> dict:
+    base = [dims["sot"], dims["lang_ids"][0], dims["transcribe"]]
+    rng = np.random.default_rng(2)
+    long = [dims["no_speech"] - 1] + [int(v) for v in rng.integers(1000, 40000, size=223)] + base
+    t.set_audio(audio)
+    block = {"prompt_tokens": len(long), "sampled_tokens": steps}
+    for b in (1, 8):
+        t.logmel([i * 480000 for i in range(b)], fetch=False)
+        t.encode(b)
+        block[f"prefill_prompt_ms_b{b}"] = timed(lambda: t.decode_prompted([long] * b, len(long) - 3, 1))
+        block[f"prefill_launches_b{b}"] = t.last_launches()[0]
+        block[f"walked_prompt_ms_b{b}"] = timed(lambda: t.decode(long, b, 1))
+        block[f"walked_launches_b{b}"] = t.last_launches()[0]
+    seeds = np.arange(1, 9, dtype=np.uint64).reshape(8, 1)
+    ms = timed(lambda: t.decode_prompted([base] * 8, 0, steps, sync_every=steps))
+    block["greedy_ms_per_token_b8"] = ms / steps
+    ms = timed(lambda: t.decode_prompted([base] * 8, 0, steps, temperature=1.0, seeds=seeds, sync_every=steps))
+    block["sampled_ms_per_token_b8"] = ms / steps
+    return block
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["base", "small"], choices=sorted(SHAPES))
@@ -75,6 +101,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--beam", type=int, default=0, help="measure beam search at this beam size and merge it into --out")
+    ap.add_argument("--prompted", action="store_true", help="measure the prompt prefill and the sampled step and merge them into --out")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "whisper.json"))
     args = ap.parse_args()
 
@@ -83,21 +110,22 @@ def main() -> None:
 
     info = _lib.device_info()
     rng = np.random.default_rng(0)
-    if args.beam:
+    if args.beam or args.prompted:
         out = Path(args.out)
         result = json.loads(out.read_text()) if out.exists() else {"what": "tools/whisper_bench.py --beam", "device": info, "shapes": []}
         audio = (0.1 * rng.standard_normal(8 * 480000)).astype(np.float32)
         for name in args.shapes:
             dims = dims_for(name)
             t = WhisperTranscriber(dims, seeded_weights(dims, 1))
-            block = beam_block(t, dims, audio, args.beam, args.steps)
+            key = "beam_search" if args.beam else "prompted"
+            block = beam_block(t, dims, audio, args.beam, args.steps) if args.beam else prompted_block(t, dims, audio, args.steps)
             t.close()
             print(json.dumps({"shape": name, **block}))
             rows = [r for r in result["shapes"] if r.get("shape") == name]
             if not rows:
                 rows = [{"shape": name, "d_model": dims["d_model"], "layers": dims["enc_layers"]}]
                 result["shapes"].append(rows[0])
-            rows[0]["beam_search"] = block
+            rows[0][key] = block
         out.parent.mkdir(parents=True, exist_ok=True)
         out.write_text(json.dumps(result, indent=1) + "\n")
         print("wrote", args.out)
