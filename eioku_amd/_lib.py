@@ -229,6 +229,13 @@ SIGNATURES = {
                              [C.c_void_p] * 4),
     "eioku_whisper_prefill_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "eioku_whisper_encoder_output": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "eioku_whisper_set_alignment_heads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "eioku_whisper_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_whisper_align_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "eioku_whisper_dtw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_int)]),
+    "eioku_whisper_last_align_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "eioku_whisper_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_whisper_last_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }

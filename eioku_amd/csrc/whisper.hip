@@ -1,4 +1,4 @@
-// K19 / K20: Whisper transcription on gfx950 (DESIGN.md "K19 / K20").
+// K19 / K20 / K21: Whisper transcription on gfx950 (DESIGN.md "K19 / K20").
 //   K19  k_mel_frames / k_mel_max / k_mel_finish   log-mel spectrogram, DFT and mel product in fp64
 //   K20  k_gemm         C = A . W^T on v_mfma_f32_16x16x32_f16: 16 weight rows per wave against MT tiles of 16 activation
 //                       rows.  MT = 4 for the encoder (M = B * ctx), MT = 1 for the decoder step (M = B <= 16: every
@@ -17,6 +17,10 @@
 //        k_embed_seq / k_attn<2, false, true> / k_kv_to_cache / k_gather_rows   the one-pass prompt prefill: all prompt
 //                       positions through the M-tiled GEMMs and causal attention, keys / values into the cache layout
 //                       (DESIGN.md "K20c sampling and prompt prefill")
+//   K21  k_attn_weights / k_align_stats / k_align_cost / k_dtw / k_align_logits / k_align_prob   word alignment: the
+//                       cross-attention probabilities of the alignment heads from one teacher-forced prefill pass, their
+//                       z-scores, median filter and head mean as a cost, dynamic time warping on an anti-diagonal wavefront
+//                       with a 2-bit trace, and the forced-token probabilities (DESIGN.md "K21 word alignment")
 // Precision points (tests/whisper_oracle.py, fp16=True, rounds at the same places): weights of every linear / conv layer
 // and the token embedding are fp16; biases, LayerNorm parameters and both position tables fp32; the residual stream is
 // fp32; LayerNorm outputs, q / k / v, attention outputs, GELU outputs and the mel input are rounded to fp16.
@@ -887,6 +891,256 @@ __global__ __launch_bounds__(64 * kMaxBeam) void k_beam_select(
   }
 }
 
+// ---- word alignment (K21) ----------------------------------------------------------------------------------------------------
+// Cross-attention probabilities of ONE head for every position of the alignment pass: the score and softmax half of k_attn
+// (the same fp16 q and k, the same fp32 dot in the same order, x 0.125, running max, expf, lane sums folded by the same
+// butterfly), without the V pass.  grid (ceil(n_q / 4), R), 4 waves, wave = query row qi of row b against all n_keys keys of
+// window kvmap[b]; A[b * a_bs + qi * a_rs + f] = p_f / sum for f < nF[b].  Dynamic LDS: 4 (n_keys + 64) floats.
+__global__ __launch_bounds__(256) void k_attn_weights(const h16* __restrict__ Q, long long q_bs, int q_rs, const h16* __restrict__ Kc,
+                                                      long long kv_bs, int kv_rs, int n_q, int n_keys, int head,
+                                                      const int* __restrict__ kvmap, const int* __restrict__ nF,
+                                                      float* __restrict__ A, long long a_bs, long long a_rs) {
+  extern __shared__ float smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.y;
+  const int qi = blockIdx.x * 4 + wave;
+  float* sc = smem + (size_t)wave * n_keys;
+  float* qs = smem + (size_t)4 * n_keys + wave * 64;
+  qs[lane] = qi < n_q ? (float)Q[(size_t)b * q_bs + (size_t)qi * q_rs + head * 64 + lane] : 0.f;
+  __syncthreads();
+  if (qi >= n_q) return;
+  const h16* kb = Kc + (size_t)kvmap[b] * kv_bs + head * 64;
+  float mx = kNegInf, sum = 0.f;
+  for (int j = lane; j < n_keys; j += 64) {
+    const uint4* kr = reinterpret_cast<const uint4*>(kb + (size_t)j * kv_rs);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const half8 kk = __builtin_bit_cast(half8, kr[c]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s += qs[c * 8 + e] * (float)kk[e];
+    }
+    s *= 0.125f;
+    sc[j] = s;
+    mx = fmaxf(mx, s);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  for (int j = lane; j < n_keys; j += 64) {
+    const float p = expf(sc[j] - mx);
+    sc[j] = p;
+    sum += p;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  const int F = nF[b];
+  float* out = A + (size_t)b * a_bs + (size_t)qi * a_rs;
+  for (int j = lane; j < F; j += 64) out[j] = sc[j] / sum;
+}
+
+// Column statistics of A [R][H][T][ldf] over the token rows t < n_tok[r]: stat [R][H][2][ldf] = mean, population std, two
+// passes with t in order.  The sums run in fp64: a frame that no token attends to holds probabilities around 1e-20 and
+// below, whose squared deviations leave the fp32 range, and an fp32 std of such a column is off by a factor, not by an ulp.
+// grid (ceil(ldf / 256), H, R), one thread per frame.
+__global__ __launch_bounds__(256) void k_align_stats(const float* __restrict__ A, int H, int T, int ldf, const int* __restrict__ n_tok,
+                                                     const int* __restrict__ nF, float* __restrict__ stat) {
+  const int f = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y, r = blockIdx.z;
+  if (f >= nF[r]) return;
+  const int n = n_tok[r];
+  const float* a = A + ((size_t)r * H + h) * T * ldf + f;
+  double s = 0.0;
+  for (int t = 0; t < n; ++t) s += (double)a[(size_t)t * ldf];
+  const double mean = s / (double)n;
+  double q = 0.0;
+  for (int t = 0; t < n; ++t) {
+    const double c = (double)a[(size_t)t * ldf] - mean;
+    q += c * c;
+  }
+  float* st = stat + ((size_t)r * H + h) * 2 * ldf;
+  st[f] = (float)mean;
+  st[ldf + f] = (float)sqrt(q / (double)n);
+}
+
+__device__ __forceinline__ void cswap(float& a, float& b) {
+  const float lo = b < a ? b : a, hi = b < a ? a : b;
+  a = lo, b = hi;
+}
+
+// the median of 7 values: the 16-exchange sorting network for 7 inputs, all in registers; a selection, so it adds no error
+__device__ __forceinline__ float median7(float (&w)[7]) {
+  cswap(w[0], w[6]), cswap(w[2], w[3]), cswap(w[4], w[5]);
+  cswap(w[0], w[2]), cswap(w[1], w[4]), cswap(w[3], w[6]);
+  cswap(w[0], w[1]), cswap(w[2], w[5]), cswap(w[3], w[4]);
+  cswap(w[1], w[2]), cswap(w[4], w[6]);
+  cswap(w[2], w[3]), cswap(w[4], w[5]);
+  cswap(w[1], w[2]), cswap(w[3], w[4]), cswap(w[5], w[6]);
+  return w[3];
+}
+
+// cost[r][i][f] = -mean_h median7_f((A[r][h][S + i][.] - mean) / std) for i < n_tok[r] - S - 1, f < nF[r]: normalise, width-7
+// median along f with reflect indexing at both ends (skipped when nF[r] <= 3), heads summed in order and divided by H,
+// negated.  grid (ceil(ldf / 256), Nmax, R), one thread per cost cell.
+__global__ __launch_bounds__(256) void k_align_cost(const float* __restrict__ A, const float* __restrict__ stat, int H, int T, int ldf,
+                                                    int S, const int* __restrict__ n_tok, const int* __restrict__ nF, int Nmax,
+                                                    float* __restrict__ cost) {
+  const int f = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y, r = blockIdx.z;
+  const int F = nF[r], N = n_tok[r] - S - 1;
+  if (f >= F || i >= N) return;
+  float acc = 0.f;
+  for (int h = 0; h < H; ++h) {
+    const float* row = A + (((size_t)r * H + h) * T + S + i) * ldf;
+    const float* mean = stat + ((size_t)r * H + h) * 2 * ldf;
+    const float* sd = mean + ldf;
+    float v;
+    if (F <= 3) {
+      v = (row[f] - mean[f]) / sd[f];
+    } else {
+      float w[7];
+#pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        int g = f + k - 3;
+        g = g < 0 ? -g : (g >= F ? 2 * (F - 1) - g : g);
+        w[k] = (row[g] - mean[g]) / sd[g];
+      }
+      v = median7(w);
+    }
+    acc += v;
+  }
+  cost[((size_t)r * Nmax + i) * ldf + f] = -(acc / (float)H);
+}
+
+// Dynamic time warping of cost [R][ld_n][ldf], one workgroup per row r over its N = nN[r] token rows and F = nF[r] frames.
+// D[i][j] = cost[i][j] + (D[i-1][j-1] if it is below both others, else D[i-1][j] if it is below both others, else
+// D[i][j-1]), D[-1][-1] = 0 and +inf elsewhere outside, fp32, one add per cell.  Token rows go in bands of 256; in a band
+// thread t owns row i = band + t and at step s computes column j = s - t, so the cells of a step lie on one anti-diagonal: its
+// left value stays in a register, the value above comes from thread t - 1 through LDS (double-buffered, one barrier per
+// step) and the value above-left is the one read the step before.  The last row of a band waits in `rowbuf` (dynamic LDS, F
+// floats) for the first row of the next.  The trace takes 2 bits per cell (0 diagonal, 1 up, 2 left), 16 cells per word,
+// trace [R][ld_n][tw] in global memory, each word written once by the thread that owns the row.  Thread 0 then walks back
+// from (N - 1, F - 1): outside the matrix the trace is left along i = -1 and up along j = -1.  jump[r][i] = the frame of the
+// first path cell of row i.  path (may be NULL) [R][2][ld_n + ldf]: the path's token rows, then its frames, last cell first.
+constexpr int kDtwRows = 256;
+__global__ __launch_bounds__(kDtwRows) void k_dtw(const float* __restrict__ cost, int ld_n, int ldf, const int* __restrict__ nN,
+                                                   const int* __restrict__ nF, unsigned* __restrict__ trace, int tw,
+                                                   int* __restrict__ jump, int* __restrict__ path, int* __restrict__ path_len) {
+  extern __shared__ float rowbuf[];
+  __shared__ float ex[2][kDtwRows];
+  const int r = blockIdx.x, t = threadIdx.x, N = nN[r], F = nF[r];
+  const float* C = cost + (size_t)r * ld_n * ldf;
+  unsigned* tr = trace + (size_t)r * ld_n * tw;
+  const float inf = INFINITY;
+  for (int band = 0; band < N; band += kDtwRows) {
+    const int i = band + t, rows = N - band < kDtwRows ? N - band : kDtwRows;
+    float left = inf, diag = i == 0 ? 0.f : inf;
+    unsigned word = 0;
+    for (int s = 0; s < F + rows - 1; ++s) {
+      const int j = s - t;
+      if (t < rows && j >= 0 && j < F) {
+        const float up = t > 0 ? ex[(s - 1) & 1][t - 1] : (band == 0 ? inf : rowbuf[j]);
+        const float c0 = diag, c1 = up, c2 = left;
+        float c;
+        unsigned code;
+        if (c0 < c1 && c0 < c2) c = c0, code = 0;
+        else if (c1 < c0 && c1 < c2) c = c1, code = 1;
+        else c = c2, code = 2;
+        const float v = C[(size_t)i * ldf + j] + c;
+        word |= code << (2 * (j & 15));
+        if ((j & 15) == 15 || j == F - 1) {
+          tr[(size_t)i * tw + (j >> 4)] = word;
+          word = 0;
+        }
+        diag = up, left = v;
+        ex[s & 1][t] = v;
+        if (t == kDtwRows - 1) rowbuf[j] = v;  // read again by thread 0 of the next band only
+      }
+      __syncthreads();
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  if (t != 0) return;
+  int* pt = path ? path + (size_t)r * 2 * (ld_n + ldf) : nullptr;
+  int* pf = path ? pt + ld_n + ldf : nullptr;
+  int i = N, j = F, n = 0;
+  size_t cur = (size_t)-1;
+  unsigned w = 0;
+  while (i > 0 || j > 0) {
+    if (pt) pt[n] = i - 1, pf[n] = j - 1;
+    ++n;
+    unsigned code;
+    if (i == 0) code = 2;
+    else if (j == 0) code = 1;
+    else {
+      const size_t at = (size_t)(i - 1) * tw + ((j - 1) >> 4);
+      if (at != cur) cur = at, w = tr[at];
+      code = (w >> (2 * ((j - 1) & 15))) & 3u;
+    }
+    if (code != 2 && i > 0) jump[(size_t)r * ld_n + i - 1] = j - 1;
+    if (code == 0) --i, --j;
+    else if (code == 1) --i;
+    else --j;
+  }
+  if (path_len) path_len[r] = n;
+}
+
+// Forced-token logits against the tied embedding for M hidden rows H[hrow[b]][.]: grid ceil(eot / 64), the MFMA tile of
+// k_logits; thread b < 16 folds the block's ids < eot in id order into partial [M][nblk][2] = (max, sum of exp relative to
+// it) and, when target[b] is one of the block's ids, writes that logit to tgt[b] (one writer per row: a row's target lies
+// in one block).  The vocabulary-wide logits are never written.
+__global__ __launch_bounds__(256) void k_align_logits(const h16* __restrict__ H, int d, const h16* __restrict__ E,
+                                                      const int* __restrict__ hrow, const int* __restrict__ target, int M, int eot,
+                                                      float* __restrict__ partial, int nblk, float* __restrict__ tgt) {
+  __shared__ float raw[64][17];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, u = lane >> 4;
+  const int v0 = blockIdx.x * 64, n0 = v0 + wave * 16;
+  for (int bt = 0; bt < M; bt += 16) {
+    const int b = bt + r;
+    const bool wl = n0 + r < eot, al = b < M;
+    const h16* wr = E + (size_t)(wl ? n0 + r : 0) * d + 8 * u;
+    const h16* ar = H + (size_t)(al ? hrow[b] : 0) * d + 8 * u;
+    float4v acc = {0.f, 0.f, 0.f, 0.f};
+    const half8 zero = {};
+    for (int k = 0; k < d; k += 32) {
+      const half8 w = wl ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(wr + k)) : zero;
+      const half8 a = al ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(ar + k)) : zero;
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, a, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int n = n0 + 4 * u + t;
+      raw[wave * 16 + 4 * u + t][r] = (b < M && n < eot) ? acc[t] : kNegInf;
+    }
+    __syncthreads();
+    if (tid < 16 && bt + tid < M) {
+      float mx = kNegInf, s = 0.f;
+      for (int i = 0; i < 64; ++i) mx = fmaxf(mx, raw[i][tid]);
+      for (int i = 0; i < 64; ++i)
+        if (raw[i][tid] > kNegInf) s += expf(raw[i][tid] - mx);
+      float* p = partial + ((size_t)(bt + tid) * nblk + blockIdx.x) * 2;
+      p[0] = mx, p[1] = s;
+      const int tg = target[bt + tid];
+      if (tg >= v0 && tg < v0 + 64) tgt[bt + tid] = raw[tg - v0][tid];
+    }
+    __syncthreads();
+  }
+}
+
+// grid M, one wave: prob[oidx[b]] = exp(tgt[b] - logsumexp of the block partials), folded as k_select folds its partials
+__global__ __launch_bounds__(64) void k_align_prob(const float* __restrict__ partial, int nblk, const float* __restrict__ tgt,
+                                                   const int* __restrict__ oidx, float* __restrict__ prob) {
+  __shared__ float shm[64], shs[64];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float mx = kNegInf, s = 0.f;
+  for (int k = lane; k < nblk; k += 64) {
+    const float* p = partial + ((size_t)b * nblk + k) * 2;
+    lse_merge(mx, s, p[0], p[1]);
+  }
+  shm[lane] = mx, shs[lane] = s;
+  __syncthreads();
+  if (lane != 0) return;
+  for (int i = 1; i < 64; ++i) lse_merge(mx, s, shm[i], shs[i]);
+  prob[oidx[b]] = expf(tgt[b] - (mx + logf(s)));
+}
+
 // ---- the model ------------------------------------------------------------------------------------------------------------
 enum { T_F16 = 0, T_F32 = 1, T_CONV = 2 };
 
@@ -947,6 +1201,14 @@ struct eioku_whisper {
   int prows = 0;
   float *px = nullptr, *ppartial = nullptr;
   h16 *ph = nullptr, *pq = nullptr, *pk = nullptr, *pv = nullptr, *pa = nullptr, *pmid = nullptr;
+  // word alignment (K21): the (layer, head) pairs (empty: every head of the upper half of the decoder layers), the
+  // workspace of align() with its capacities in elements, and the device times of the last align() call
+  std::vector<int> align_heads;
+  float *al_A = nullptr, *al_stat = nullptr, *al_cost = nullptr, *al_part = nullptr, *al_tgt = nullptr, *al_prob = nullptr;
+  unsigned* al_trace = nullptr;
+  int *al_jump = nullptr, *al_meta = nullptr, *al_rows = nullptr, *al_path = nullptr;
+  size_t al_cap[11] = {};
+  double align_ms[3] = {0, 0, 0};
   double flops = 0;
   int launches = 0, steps = 0;
 
@@ -1201,7 +1463,16 @@ int ensure_prefill(eioku_whisper* m, int rows) {
 // One pass of the decoder over the P prompt positions of R rows (ids [R][P] on the device): the M-tiled GEMMs of the encoder,
 // causal self-attention, cross-attention against window kvmap[r].  Leaves the final-LayerNorm hidden state of every position
 // in m->ph [R][P][d] and the self-attention keys / values of positions 0 .. P - 1 in the cache of lanes r * lstride .. + G - 1.
-int prefill(eioku_whisper* m, int R, int P, const int* ids, const int* kvmap, int G, int lstride) {
+// cap (word alignment only): in every layer that has alignment heads, the cross-attention probabilities of those heads go
+// to cap->A [R][n heads][P][ldf] right after the cross q projection; the pass itself is unchanged.
+struct AlignCapture {
+  const int* heads;  // n (layer, head) pairs
+  int n, ldf;
+  const int* nF;     // device: frames kept per row
+  float* A;
+};
+
+int prefill(eioku_whisper* m, int R, int P, const int* ids, const int* kvmap, int G, int lstride, const AlignCapture* cap = nullptr) {
   const auto& c = m->cfg;
   const int d = c.d_model, ctx = c.max_source_positions, Tm = c.max_target_positions, M = R * P;
   const long long bs = (long long)P * d;
@@ -1226,6 +1497,16 @@ int prefill(eioku_whisper* m, int R, int P, const int* ids, const int* kvmap, in
     W_TRY((gemm<4, EPI_RESID>(m, m->pa, d, m->H(L.self.o), d, m->F(L.self.ob), M, d, d, m->px, d)));
     W_TRY(ln(m, m->px, M, d, L.cross.ln_g, L.cross.ln_b, m->ph));
     W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.cross.q), d, m->F(L.cross.qb), M, d, d, m->pq, d)));
+    for (int hs = 0; cap && hs < cap->n; ++hs) {
+      if (cap->heads[2 * hs] != l) continue;
+      const size_t lds = (size_t)4 * (ctx + 64) * sizeof(float);
+      hipLaunchKernelGGL(k_attn_weights, dim3((P + 3) / 4, R), dim3(256), lds, 0, m->pq, bs, d, ck, (long long)ctx * d, d, P, ctx,
+                         cap->heads[2 * hs + 1], kvmap, cap->nF, cap->A + (size_t)hs * P * cap->ldf, (long long)cap->n * P * cap->ldf,
+                         (long long)cap->ldf);
+      EIOKU_LAUNCH_CHECK();
+      m->flops += 2.0 * R * (double)P * ctx * 64;
+      m->launches += 1;
+    }
     W_TRY((attn<2>(m, m->pq, bs, d, ck, cv, (long long)ctx * d, d, P, ctx, R, m->pa, bs, d, 1, nullptr, 0, kvmap)));
     W_TRY((gemm<4, EPI_RESID>(m, m->pa, d, m->H(L.cross.o), d, m->F(L.cross.ob), M, d, d, m->px, d)));
     W_TRY(ln(m, m->px, M, d, L.ln_g, L.ln_b, m->ph));
@@ -1422,7 +1703,8 @@ void eioku_whisper_destroy(eioku_whisper* m) {
                   m->tokens, m->cur_tok, m->lang_out, m->d_ids, m->bpartial, m->fin_sum, m->b_sum, m->b_fsum, m->anc[0], m->anc[1],
                   m->hist[0], m->hist[1], m->fin_tok, m->fin_n, m->fin_count, m->complete, m->b_src, m->b_tok, m->b_fsrc,
                   m->b_nlive, m->b_nfin, m->tr_src, m->tr_tok, m->d_seeds, m->d_sidx, m->kvmap, m->px, m->ppartial, m->ph, m->pq,
-                  m->pk, m->pv, m->pa, m->pmid};
+                  m->pk, m->pv, m->pa, m->pmid, m->al_A, m->al_stat, m->al_cost, m->al_part, m->al_tgt, m->al_prob, m->al_trace,
+                  m->al_jump, m->al_meta, m->al_rows, m->al_path};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   delete m;
@@ -2044,6 +2326,211 @@ int eioku_whisper_prefill_logits(eioku_whisper* m, const int32_t* ids, int T, in
   (void)hipFree(d_head);
   (void)hipFree(d_out);
   return rc;
+}
+
+// ---- word alignment (K21) ----------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+
+enum { AL_A = 0, AL_STAT, AL_COST, AL_PART, AL_TGT, AL_PROB, AL_TRACE, AL_JUMP, AL_META, AL_ROWS, AL_PATH };
+constexpr int kMaxDtw = 4096;  // token rows / frames the debug DTW entry takes
+
+template <typename T>
+int al_grow(eioku_whisper* m, T** p, int slot, size_t n) {
+  if (*p && n <= m->al_cap[slot]) return EIOKU_OK;
+  m->al_cap[slot] = 0;
+  W_TRY(dalloc(p, n));
+  m->al_cap[slot] = n;
+  return EIOKU_OK;
+}
+
+// mean / std over the token rows, then the cost; meta on the device: n_tok [R], nF [R]
+int align_cost_launch(eioku_whisper* m, const float* A, int R, int H, int T, int ldf, int S, const int* d_ntok, const int* d_nF,
+                      int Nmax, float* cost) {
+  W_TRY(al_grow(m, &m->al_stat, AL_STAT, (size_t)R * H * 2 * ldf));
+  hipLaunchKernelGGL(k_align_stats, dim3((ldf + 255) / 256, H, R), dim3(256), 0, 0, A, H, T, ldf, d_ntok, d_nF, m->al_stat);
+  EIOKU_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_align_cost, dim3((ldf + 255) / 256, Nmax, R), dim3(256), 0, 0, A, m->al_stat, H, T, ldf, S, d_ntok, d_nF, Nmax,
+                     cost);
+  EIOKU_LAUNCH_CHECK();
+  m->launches += 2;
+  return EIOKU_OK;
+}
+
+int dtw_launch(eioku_whisper* m, const float* cost, int R, int Nmax, int ldf, const int* d_nN, const int* d_nF, int* jump, int* path,
+               int* path_len) {
+  const int tw = (ldf + 15) / 16;
+  W_TRY(al_grow(m, &m->al_trace, AL_TRACE, (size_t)R * Nmax * tw));
+  hipLaunchKernelGGL(k_dtw, dim3(R), dim3(kDtwRows), (size_t)ldf * sizeof(float), 0, cost, Nmax, ldf, d_nN, d_nF, m->al_trace, tw, jump,
+                     path, path_len);
+  EIOKU_LAUNCH_CHECK();
+  m->launches += 1;
+  return EIOKU_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int eioku_whisper_set_alignment_heads(eioku_whisper* m, const int32_t* layer_head_pairs, int n) {
+  EIOKU_REQUIRE(m && n >= 0 && (layer_head_pairs || n == 0), "bad argument");
+  EIOKU_REQUIRE(n <= m->cfg.dec_layers * m->cfg.heads, "%d alignment heads: the decoder has %d", n, m->cfg.dec_layers * m->cfg.heads);
+  for (int i = 0; i < n; ++i) {
+    const int l = layer_head_pairs[2 * i], h = layer_head_pairs[2 * i + 1];
+    EIOKU_REQUIRE(l >= 0 && l < m->cfg.dec_layers && h >= 0 && h < m->cfg.heads,
+                  "alignment head (%d, %d) outside the decoder's %d layers x %d heads", l, h, m->cfg.dec_layers, m->cfg.heads);
+  }
+  m->align_heads.assign(layer_head_pairs, layer_head_pairs + 2 * (size_t)n);
+  return EIOKU_OK;
+}
+
+int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32_t* n_tok, int sot_len, const int32_t* windows,
+                        const int32_t* n_frames, int R, int32_t* jump_out, float* prob_out, float* cost_out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && seq && n_tok && n_frames && jump_out && prob_out && sot_len >= 1, "bad argument");
+  m->flops = 0;
+  m->launches = 0;
+  m->steps = 0;
+  const auto& c = m->cfg;
+  const int ctx = c.max_source_positions, d = c.d_model, S = sot_len;
+  EIOKU_REQUIRE(R > 0 && R <= 64, "%d rows: an alignment pass takes 1..64", R);
+  EIOKU_REQUIRE(T >= 1 && T <= c.max_target_positions, "sequence of %d tokens exceeds max_target_positions %d", T, c.max_target_positions);
+  EIOKU_REQUIRE(m->enc_B > 0, "an alignment needs an encode first");
+  if (!windows) EIOKU_REQUIRE(R == m->enc_B, "alignment of %d rows without a window list needs an encode of the same %d windows", R, m->enc_B);
+  int Fmax = 0;
+  size_t Mp = 0;
+  for (int r = 0; r < R; ++r) {
+    EIOKU_REQUIRE(!windows || (windows[r] >= 0 && windows[r] < m->enc_B), "window %d outside the %d encoded windows", windows[r], m->enc_B);
+    EIOKU_REQUIRE(n_tok[r] >= S + 3 && n_tok[r] <= T, "row %d: %d tokens; an alignment needs sot_len %d + <|notimestamps|> + at least one "
+                  "text token + EOT, within T = %d", r, n_tok[r], S, T);
+    EIOKU_REQUIRE(n_frames[r] >= 2 && n_frames[r] <= 2 * ctx, "row %d: %d mel frames outside 2..%d", r, n_frames[r], 2 * ctx);
+    for (int t = 0; t < T; ++t) {
+      const int id = seq[(size_t)r * T + t];
+      EIOKU_REQUIRE(id >= 0 && id < c.vocab, "id %d outside the vocabulary", id);
+      if (t > S && t < n_tok[r] - 1) EIOKU_REQUIRE(id < c.eot, "row %d position %d: id %d is not a text token (< %d)", r, t, id, c.eot);
+    }
+    Fmax = n_frames[r] / 2 > Fmax ? n_frames[r] / 2 : Fmax;
+    Mp += (size_t)(n_tok[r] - S - 2);
+  }
+  W_TRY(check_weights(m));
+  std::vector<int> heads = m->align_heads;
+  if (heads.empty())
+    for (int l = c.dec_layers / 2; l < c.dec_layers; ++l)
+      for (int h = 0; h < c.heads; ++h) heads.push_back(l), heads.push_back(h);
+  const int Hs = (int)heads.size() / 2, Nmax = T - S - 1, nblk = (c.eot + 63) / 64;
+  EIOKU_REQUIRE(Hs > 0 && nblk > 0, "no alignment heads");
+  W_TRY(ensure_lanes(m, R));
+  // host lists: kvmap [R]; meta = n_tok, nF, nN [R each]; rows = hidden row, target id, output index [Mp each]
+  std::vector<int> map((size_t)R), meta((size_t)3 * R), rows(3 * Mp);
+  size_t k = 0;
+  for (int r = 0; r < R; ++r) {
+    map[r] = windows ? windows[r] : r;
+    meta[r] = n_tok[r], meta[R + r] = n_frames[r] / 2, meta[2 * R + r] = n_tok[r] - S - 1;
+    for (int i = 0; i < n_tok[r] - S - 2; ++i, ++k) {
+      rows[k] = r * T + S + i;
+      rows[Mp + k] = seq[(size_t)r * T + S + i + 1];
+      rows[2 * Mp + k] = r * Nmax + i;
+    }
+  }
+  const size_t nA = (size_t)R * Hs * T * Fmax, nC = (size_t)R * Nmax * Fmax, nJ = (size_t)R * Nmax;
+  W_TRY(al_grow(m, &m->al_A, AL_A, nA));
+  W_TRY(al_grow(m, &m->al_cost, AL_COST, nC));
+  W_TRY(al_grow(m, &m->al_jump, AL_JUMP, nJ));
+  W_TRY(al_grow(m, &m->al_prob, AL_PROB, nJ));
+  W_TRY(al_grow(m, &m->al_meta, AL_META, meta.size()));
+  W_TRY(al_grow(m, &m->al_rows, AL_ROWS, rows.size()));
+  W_TRY(al_grow(m, &m->al_part, AL_PART, Mp * nblk * 2));
+  W_TRY(al_grow(m, &m->al_tgt, AL_TGT, Mp));
+  EIOKU_HIP_CHECK(hipMemcpy(m->kvmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, seq, (size_t)R * T * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->al_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemset(m->al_cost, 0, nC * sizeof(float)));
+  EIOKU_HIP_CHECK(hipMemset(m->al_jump, 0xFF, nJ * sizeof(int)));
+  EIOKU_HIP_CHECK(hipMemset(m->al_prob, 0, nJ * sizeof(float)));
+  const int *d_ntok = m->al_meta, *d_nF = m->al_meta + R, *d_nN = m->al_meta + 2 * R;
+  hipEvent_t ev[4] = {};
+  for (auto& e : ev) EIOKU_HIP_CHECK(hipEventCreate(&e));
+  auto run = [&]() -> int {
+    EIOKU_HIP_CHECK(hipEventRecord(ev[0], 0));
+    const AlignCapture cap{heads.data(), Hs, Fmax, d_nF, m->al_A};
+    W_TRY(prefill(m, R, T, m->d_ids, m->kvmap, 1, 1, &cap));
+    hipLaunchKernelGGL(k_align_logits, dim3(nblk), dim3(256), 0, 0, m->ph, d, m->H(m->emb), m->al_rows, m->al_rows + Mp, (int)Mp, c.eot,
+                       m->al_part, nblk, m->al_tgt);
+    EIOKU_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_align_prob, dim3((unsigned)Mp), dim3(64), 0, 0, m->al_part, nblk, m->al_tgt, m->al_rows + 2 * Mp, m->al_prob);
+    EIOKU_LAUNCH_CHECK();
+    m->flops += 2.0 * (double)Mp * c.eot * d;
+    m->launches += 2;
+    EIOKU_HIP_CHECK(hipEventRecord(ev[1], 0));
+    W_TRY(align_cost_launch(m, m->al_A, R, Hs, T, Fmax, S, d_ntok, d_nF, Nmax, m->al_cost));
+    EIOKU_HIP_CHECK(hipEventRecord(ev[2], 0));
+    W_TRY(dtw_launch(m, m->al_cost, R, Nmax, Fmax, d_nN, d_nF, m->al_jump, nullptr, nullptr));
+    EIOKU_HIP_CHECK(hipEventRecord(ev[3], 0));
+    EIOKU_HIP_CHECK(hipEventSynchronize(ev[3]));
+    for (int i = 0; i < 3; ++i) {
+      float ms = 0.f;
+      EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+      m->align_ms[i] = ms;
+    }
+    EIOKU_HIP_CHECK(hipMemcpy(jump_out, m->al_jump, nJ * sizeof(int), hipMemcpyDeviceToHost));
+    EIOKU_HIP_CHECK(hipMemcpy(prob_out, m->al_prob, nJ * sizeof(float), hipMemcpyDeviceToHost));
+    if (cost_out) EIOKU_HIP_CHECK(hipMemcpy(cost_out, m->al_cost, nC * sizeof(float), hipMemcpyDeviceToHost));
+    return EIOKU_OK;
+  };
+  const int rc = run();
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  return rc;
+}
+
+int eioku_whisper_align_cost(eioku_whisper* m, const float* A, int H, int T, int F, int sot_len, float* cost_out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && A && cost_out, "bad argument");
+  EIOKU_REQUIRE(H >= 1 && H <= 4096 && F >= 1 && F <= kMaxDtw && sot_len >= 0 && T >= sot_len + 2 && T <= kMaxDtw,
+                "align_cost: H %d, T %d, F %d, sot_len %d (T >= sot_len + 2, T and F <= %d)", H, T, F, sot_len, kMaxDtw);
+  m->launches = 0;
+  const int N = T - sot_len - 1;
+  const int meta[2] = {T, F};
+  W_TRY(al_grow(m, &m->al_A, AL_A, (size_t)H * T * F));
+  W_TRY(al_grow(m, &m->al_cost, AL_COST, (size_t)N * F));
+  W_TRY(al_grow(m, &m->al_meta, AL_META, 2));
+  EIOKU_HIP_CHECK(hipMemcpy(m->al_A, A, (size_t)H * T * F * sizeof(float), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta, sizeof(meta), hipMemcpyHostToDevice));
+  W_TRY(align_cost_launch(m, m->al_A, 1, H, T, F, sot_len, m->al_meta, m->al_meta + 1, N, m->al_cost));
+  EIOKU_HIP_CHECK(hipMemcpy(cost_out, m->al_cost, (size_t)N * F * sizeof(float), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
+}
+
+int eioku_whisper_dtw(eioku_whisper* m, const float* cost, int N, int F, int32_t* jump_out, int32_t* text_idx, int32_t* time_idx,
+                      int* path_len) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && cost && jump_out, "bad argument");
+  EIOKU_REQUIRE((text_idx && time_idx && path_len) || (!text_idx && !time_idx && !path_len), "the path outputs come together or not at all");
+  EIOKU_REQUIRE(N >= 1 && N <= kMaxDtw && F >= 1 && F <= kMaxDtw, "dtw of %d token rows x %d frames: both 1..%d", N, F, kMaxDtw);
+  m->launches = 0;
+  const int meta[2] = {N, F};
+  W_TRY(al_grow(m, &m->al_cost, AL_COST, (size_t)N * F));
+  W_TRY(al_grow(m, &m->al_jump, AL_JUMP, (size_t)N));
+  W_TRY(al_grow(m, &m->al_meta, AL_META, 3));
+  W_TRY(al_grow(m, &m->al_path, AL_PATH, (size_t)2 * (N + F)));
+  EIOKU_HIP_CHECK(hipMemcpy(m->al_cost, cost, (size_t)N * F * sizeof(float), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta, sizeof(meta), hipMemcpyHostToDevice));
+  W_TRY(dtw_launch(m, m->al_cost, 1, N, F, m->al_meta, m->al_meta + 1, m->al_jump, m->al_path, m->al_meta + 2));
+  EIOKU_HIP_CHECK(hipMemcpy(jump_out, m->al_jump, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
+  if (path_len) {
+    int n = 0;
+    EIOKU_HIP_CHECK(hipMemcpy(&n, m->al_meta + 2, sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<int> p((size_t)2 * (N + F));
+    EIOKU_HIP_CHECK(hipMemcpy(p.data(), m->al_path, p.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) text_idx[i] = p[n - 1 - i], time_idx[i] = p[(size_t)N + F + n - 1 - i];
+    *path_len = n;
+  }
+  return EIOKU_OK;
+}
+
+int eioku_whisper_last_align_ms(const eioku_whisper* m, double* pass_ms, double* cost_ms, double* dtw_ms) {
+  EIOKU_REQUIRE(m && pass_ms && cost_ms && dtw_ms, "NULL argument");
+  *pass_ms = m->align_ms[0], *cost_ms = m->align_ms[1], *dtw_ms = m->align_ms[2];
+  return EIOKU_OK;
 }
 
 int eioku_whisper_last_flops(const eioku_whisper* m, double* flops) {

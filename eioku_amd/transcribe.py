@@ -1,5 +1,5 @@
 """Transcription on the HIP path: Whisper log-mel (K19), greedy decode with timestamp rules (K20), beam search (K20b),
-sampling at a temperature and the one-pass prompt prefill (K20c).
+sampling at a temperature and the one-pass prompt prefill (K20c), word timestamps from cross-attention DTW (K21).
 
 The reference calls ``faster_whisper.WhisperModel.transcribe`` (``model_manager.py:406-467``), which has no ROCm backend.
 This module keeps its result dict and replaces the arithmetic: the audio goes up once, ``csrc/whisper.hip`` computes the
@@ -18,6 +18,7 @@ import ctypes as C
 import json
 import logging
 import math
+import string
 import struct
 import wave
 import zlib
@@ -243,6 +244,109 @@ class ByteDecoder:
         return raw.decode("utf-8", errors="replace")
 
 
+# ---- words (K21) ------------------------------------------------------------------------------------------------------------
+NO_SPACE_LANGUAGES = ("zh", "ja", "th", "lo", "my", "yue")
+PREPEND_PUNCTUATIONS = "\"'“¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+
+
+def check_word_timestamps(value) -> bool:
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"word_timestamps must be a bool, got {value!r}")
+    return bool(value)
+
+
+def _split_on_unicode(ids, decoder) -> tuple[list[str], list[list[int]]]:
+    """Whisper's ``split_tokens_on_unicode``: grow a group of tokens until its decoded text holds no U+FFFD (or holds one
+    that the text itself has at that place)."""
+    full = decoder.decode(ids)
+    words, groups, current, offset = [], [], [], 0
+    for t in ids:
+        current.append(int(t))
+        decoded = decoder.decode(current)
+        at = decoded.find("\ufffd")
+        if at < 0 or offset + at >= len(full) or full[offset + at] == "\ufffd":
+            words.append(decoded)
+            groups.append(current)
+            current = []
+            offset += len(decoded)
+    return words, groups
+
+
+def split_to_word_tokens(ids, decoder, language: str | None, eot: int) -> tuple[list[str], list[list[int]]]:
+    """Whisper's ``split_to_word_tokens``: (words, the token ids of each).  Always the unicode split; for every language
+    but :data:`NO_SPACE_LANGUAGES` a subword then opens a new word when it starts with a space, is punctuation
+    (``subword.strip() in string.punctuation``) or is a special id (``>= eot``), and joins the previous word otherwise."""
+    subwords, groups = _split_on_unicode(ids, decoder)
+    if language is not None and language.strip("<|>").lower() in NO_SPACE_LANGUAGES:
+        return subwords, groups
+    words, tokens = [], []
+    for sub, grp in zip(subwords, groups):
+        if grp[0] >= eot or sub.startswith(" ") or sub.strip() in string.punctuation or not words:
+            words.append(sub)
+            tokens.append(list(grp))
+        else:
+            words[-1] += sub
+            tokens[-1].extend(grp)
+    return words, tokens
+
+
+def merge_punctuations(words: list[dict], prepend: str = PREPEND_PUNCTUATIONS, append: str = APPEND_PUNCTUATIONS) -> list[dict]:
+    """Whisper's ``merge_punctuations`` on ``[{"word", "tokens"}]``: a word that is a space and one of ``prepend`` goes in
+    front of the next word, a word that is one of ``append`` goes behind the previous one (unless that ends on a space);
+    the emptied entries are dropped.  -> the merged list (new dicts)."""
+    ws = [{"word": w["word"], "tokens": list(w["tokens"])} for w in words]
+    i, j = len(ws) - 2, len(ws) - 1
+    while i >= 0:
+        if ws[i]["word"].startswith(" ") and ws[i]["word"].strip() in prepend:
+            ws[j]["word"] = ws[i]["word"] + ws[j]["word"]
+            ws[j]["tokens"] = ws[i]["tokens"] + ws[j]["tokens"]
+            ws[i]["word"], ws[i]["tokens"] = "", []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(ws):
+        if not ws[i]["word"].endswith(" ") and ws[j]["word"] in append:
+            ws[i]["word"] += ws[j]["word"]
+            ws[i]["tokens"] += ws[j]["tokens"]
+            ws[j]["word"], ws[j]["tokens"] = "", []
+        else:
+            i = j
+        j += 1
+    return [w for w in ws if w["tokens"]]
+
+
+def window_words(pieces: list[list[int]], jump, prob, window_start_ms: int, decoder, language: str | None, eot: int) -> list[list[dict]]:
+    """The words of one aligned window, per segment.  ``pieces``: the text ids of the window's segments in order;
+    ``jump[i]`` the frame index (20 ms) at which token row ``i`` of ``text + [eot]`` starts, ``prob[i]`` the probability of
+    text token ``i``.  A word over token rows ``[a, b)`` starts at row ``a``, ends at row ``b`` (the EOT row ends the last
+    word) and has confidence ``mean(prob[a:b])`` clipped to [0, 1].  Words go to the segments by token count, Whisper's
+    loop: a segment takes words until its text-token count is used up."""
+    text = [int(t) for piece in pieces for t in piece]
+    names, groups = split_to_word_tokens(text, decoder, language, eot)
+    merged = merge_punctuations([{"word": w, "tokens": g} for w, g in zip(names, groups)])
+    words, a = [], 0
+    for w in merged:
+        b = a + len(w["tokens"])
+        start_ms = int(window_start_ms) + MS_PER_TIMESTAMP * int(jump[a])
+        end_ms = int(window_start_ms) + MS_PER_TIMESTAMP * int(jump[b])
+        conf = float(np.clip(np.mean(np.asarray(prob[a:b], dtype=np.float64)), 0.0, 1.0))
+        words.append({"word": w["word"], "start": start_ms / 1000, "end": end_ms / 1000, "confidence": conf,
+                      "start_ms": start_ms, "end_ms": end_ms, "tokens": w["tokens"]})
+        a = b
+    out, k = [], 0
+    for piece in pieces:
+        mine, used = [], 0
+        while k < len(words) and used < len(piece):
+            if words[k]["word"]:
+                mine.append(words[k])
+            used += len(words[k]["tokens"])
+            k += 1
+        out.append(mine)
+    return out
+
+
 # ---- segment cutting and the seek rule ------------------------------------------------------------------------------------
 def cut_window(tokens, eot: int, timestamp_begin: int, window_start_ms: int, window_frames: int):
     """Whisper's segment and seek rule for one window.  ``tokens``: the sampled ids (anything from the first EOT on is
@@ -346,6 +450,8 @@ def whisper_dims(config: dict, generation_config: dict) -> dict:
         "begin_suppress": [int(t) for t in gen.get("begin_suppress_tokens") or []],
         "lang_ids": [int(i) for _, i in langs],
         "lang_codes": [k.strip("<|>") for k, _ in langs],
+        # [[layer, head], ...] or None = every head of the upper half of the decoder layers (Whisper's default)
+        "alignment_heads": [[int(l), int(h)] for l, h in gen["alignment_heads"]] if gen.get("alignment_heads") else None,
     }
 
 
@@ -395,6 +501,8 @@ class WhisperTranscriber:
         _lib.check(self.lib.eioku_whisper_create(C.byref(cfg), C.byref(handle)), "eioku_whisper_create")
         self._h = handle
         self.window_frames = 2 * d["max_source_positions"]
+        if d.get("alignment_heads"):
+            self.set_alignment_heads(d["alignment_heads"])
         self._load(weights)
 
     def _load(self, weights) -> None:
@@ -647,6 +755,61 @@ class WhisperTranscriber:
                                                           tok.ctypes.data, lp.ctypes.data, masked.ctypes.data), "eioku_whisper_select")
         return tok, lp, masked
 
+    def set_alignment_heads(self, pairs) -> None:
+        """K21: the (layer, head) pairs whose cross-attention is aligned; empty or None = the default (upper half)."""
+        p = np.ascontiguousarray(pairs if pairs is not None else [], dtype=np.int32).reshape(-1, 2)
+        self._lib_mod.check(self.lib.eioku_whisper_set_alignment_heads(self._h, p.ctypes.data if len(p) else None, len(p)),
+                            "eioku_whisper_set_alignment_heads")
+
+    def align(self, seqs, n_tok, sot_len: int, n_frames, windows=None, cost: bool = False) -> dict:
+        """K21: one teacher-forced pass over ``seqs`` [R][T] (sot sequence, ``<|notimestamps|>``, text, EOT, EOT padding;
+        true lengths ``n_tok``) against the last encode, then cost, DTW and token probabilities on the device.  ``jump``
+        [R][T - sot_len - 1] (-1 past a row's text + EOT), ``prob`` of the same shape (0 past a row's text), and with
+        ``cost=True`` (tests) ``cost`` [R][T - sot_len - 1][max(n_frames) // 2]."""
+        s = np.ascontiguousarray(seqs, dtype=np.int32)
+        if s.ndim != 2:
+            raise ValueError("seqs must be [rows][T]: pad the rows with EOT to one length")
+        R, T = s.shape
+        nt, nf = np.ascontiguousarray(n_tok, dtype=np.int32), np.ascontiguousarray(n_frames, dtype=np.int32)
+        win = None if windows is None else np.ascontiguousarray(windows, dtype=np.int32)
+        if nt.shape != (R,) or nf.shape != (R,) or (win is not None and win.shape != (R,)):
+            raise ValueError("n_tok, n_frames and windows hold one value per row")
+        N = max(T - int(sot_len) - 1, 1)
+        jump, prob = np.full((R, N), -1, dtype=np.int32), np.zeros((R, N), dtype=np.float32)
+        cst = np.zeros((R, N, max(int(nf.max()) // 2, 1)), dtype=np.float32) if cost else None
+        self._lib_mod.check(self.lib.eioku_whisper_align(
+            self._h, s.ctypes.data, T, nt.ctypes.data, int(sot_len), win.ctypes.data if win is not None else None, nf.ctypes.data, R,
+            jump.ctypes.data, prob.ctypes.data, cst.ctypes.data if cost else None), "eioku_whisper_align")
+        out = {"jump": jump, "prob": prob}
+        if cost:
+            out["cost"] = cst
+        return out
+
+    def align_cost(self, weights, sot_len: int) -> np.ndarray:
+        """Debug: normalise + median filter + head mean on supplied weights [H][T][F] -> cost [T - sot_len - 1][F]."""
+        a = np.ascontiguousarray(weights, dtype=np.float32)
+        H, T, F = a.shape
+        out = np.zeros((max(T - int(sot_len) - 1, 1), F), dtype=np.float32)
+        self._lib_mod.check(self.lib.eioku_whisper_align_cost(self._h, a.ctypes.data, H, T, F, int(sot_len), out.ctypes.data),
+                            "eioku_whisper_align_cost")
+        return out
+
+    def dtw(self, cost) -> dict:
+        """Debug: the warping on a supplied cost [N][F]: ``jump`` [N], and the path as ``text_idx`` / ``time_idx``."""
+        c = np.ascontiguousarray(cost, dtype=np.float32)
+        N, F = c.shape
+        jump, ti, fi = np.zeros(N, dtype=np.int32), np.zeros(N + F, dtype=np.int32), np.zeros(N + F, dtype=np.int32)
+        n = C.c_int(0)
+        self._lib_mod.check(self.lib.eioku_whisper_dtw(self._h, c.ctypes.data, N, F, jump.ctypes.data, ti.ctypes.data, fi.ctypes.data,
+                                                       C.byref(n)), "eioku_whisper_dtw")
+        return {"jump": jump, "text_idx": ti[:n.value].copy(), "time_idx": fi[:n.value].copy()}
+
+    def last_align_ms(self) -> tuple[float, float, float]:
+        """Device milliseconds of the last :meth:`align`: the pass with the probabilities, the cost kernels, the DTW."""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._lib_mod.check(self.lib.eioku_whisper_last_align_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "eioku_whisper_last_align_ms")
+        return a.value, b.value, c.value
+
     def last_launches(self) -> tuple[int, int]:
         a, b = C.c_int(0), C.c_int(0)
         self._lib_mod.check(self.lib.eioku_whisper_last_launches(self._h, C.byref(a), C.byref(b)), "eioku_whisper_last_launches")
@@ -676,9 +839,30 @@ class WhisperTranscriber:
             prompt.append(d["transcribe"])
         return prompt
 
+    def _window_words(self, items: list[tuple[int, int, int, list[list[int]]]], lang_id, code) -> list[list[list[dict]]]:
+        """K21: one :meth:`align` call for the accepted windows of the current encode.  ``items``: per window (encoded window
+        index, first mel frame, content frames, the text ids of its segments).  -> per window, per segment, the words."""
+        d = self.dims
+        sot_seq = self._prompt(lang_id)
+        out: list[list[list[dict]]] = [[[] for _ in pieces] for _, _, _, pieces in items]
+        rows = [k for k, (_, _, size, pieces) in enumerate(items) if size >= 2 and any(pieces)]
+        if not rows:
+            return out
+        seqs = [sot_seq + [d["no_timestamps"]] + [t for piece in items[k][3] for t in piece] + [d["eot"]] for k in rows]
+        T = max(len(q) for q in seqs)
+        if T > d["max_target_positions"]:
+            raise ValueError(f"a window of {T - len(sot_seq) - 2} text tokens does not fit the decoder's "
+                             f"{d['max_target_positions']} positions for the word alignment")
+        res = self.align([q + [d["eot"]] * (T - len(q)) for q in seqs], [len(q) for q in seqs], len(sot_seq),
+                         [items[k][2] for k in rows], windows=[items[k][0] for k in rows])
+        for row, k in enumerate(rows):
+            _, seek, _, pieces = items[k]
+            out[k] = window_words(pieces, res["jump"][row], res["prob"][row], seek * MS_PER_FRAME, self.decoder, code, d["eot"])
+        return out
+
     def transcribe(self, samples: np.ndarray, language: str | None = None, *, window_mode: str = "seek",
                    batch_windows: int = 8, max_new_tokens: int | None = None, beam_size: int = 1,
-                   patience: float = 1.0, **fallback) -> dict:
+                   patience: float = 1.0, word_timestamps: bool = False, **fallback) -> dict:
         """-> ``{"segments": [{start_ms, end_ms, text, language, confidence: None, words: None}], "language": code}``.
 
         ``window_mode="seek"``: one window at a time, the next one starts where Whisper's seek rule says.
@@ -697,7 +881,13 @@ class WhisperTranscriber:
         behind ``<|startofprev|>`` in front of the prompt; a window accepted above ``prompt_reset_on_temperature`` resets
         them.  Raw segments then also carry ``temperature``, ``avg_logprob`` and ``compression_ratio``, and the raw result a
         ``windows`` list with the same figures per decoded window.  With none of these keys the device calls are the ones
-        above."""
+        above.
+
+        ``word_timestamps=True`` (K21) aligns every accepted window's text tokens to its audio on the device (one
+        :meth:`align` call per window in ``seek`` mode, one per batch in ``fixed`` mode) and fills each segment's ``words``
+        with ``{"word", "start", "end", "confidence"}`` (seconds; raw segments also ``start_ms`` / ``end_ms`` / ``tokens``
+        per word).  Segments, text and the seek position are what they are without it."""
+        word_timestamps = check_word_timestamps(word_timestamps)
         if window_mode not in ("seek", "fixed"):
             raise ValueError(f"window_mode must be 'seek' or 'fixed', got {window_mode!r}")
         beam_size, patience = check_beam(beam_size, patience)
@@ -708,7 +898,8 @@ class WhisperTranscriber:
             fb = check_fallback(**fallback)
             if fb["condition_on_previous_text"] and window_mode != "seek":
                 raise ValueError("condition_on_previous_text needs window_mode='seek': fixed windows decode in lockstep")
-            return self._transcribe_fallback(samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb)
+            return self._transcribe_fallback(samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb,
+                                             word_timestamps)
         d = self.dims
         samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
         content_frames = len(samples) // HOP
@@ -733,26 +924,38 @@ class WhisperTranscriber:
             return {"tokens": np.asarray(res["tokens"])[pick], "sum_logprob": np.asarray(res["sum_logprob"])[pick],
                     "no_speech_prob": res["no_speech_prob"]}
 
-        def emit(res: dict, lane: int, seek: int) -> int:
-            size = min(self.window_frames, content_frames - seek)
-            toks = [int(t) for t in res["tokens"][lane]]
-            n_text = toks.index(d["eot"]) if d["eot"] in toks else len(toks)
-            if skip_window(float(res["no_speech_prob"][lane]), float(res["sum_logprob"][lane]), n_text):
-                return size
-            pieces, advance = cut_window(toks, d["eot"], d["timestamp_begin"], seek * MS_PER_FRAME, size)
+        def emit_all(res: dict, seeks: list[int]) -> int:
+            """The segments of the windows of one encode; -> the frames the last of them advances by."""
+            cut = []
+            for lane, seek in enumerate(seeks):
+                size = min(self.window_frames, content_frames - seek)
+                toks = [int(t) for t in res["tokens"][lane]]
+                n_text = toks.index(d["eot"]) if d["eot"] in toks else len(toks)
+                if skip_window(float(res["no_speech_prob"][lane]), float(res["sum_logprob"][lane]), n_text):
+                    cut.append((lane, seek, size, None, size))
+                    continue
+                pieces, advance = cut_window(toks, d["eot"], d["timestamp_begin"], seek * MS_PER_FRAME, size)
+                cut.append((lane, seek, size, pieces, advance))
             code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
-            for start_ms, end_ms, ids in pieces:
-                text = self.decoder.decode(ids)
-                if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
-                    continue  # faster-whisper drops empty and zero-length segments
-                segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code,
-                                 "confidence": None, "words": None, "tokens": ids})
+            kept = [c for c in cut if c[3] is not None]
+            words = None
+            if word_timestamps and kept:
+                words = self._window_words([(lane, seek, size, [ids for _, _, ids in pieces]) for lane, seek, size, pieces, _ in kept],
+                                           lang_id, code)
+            for k, (_, _, _, pieces, _) in enumerate(kept):
+                for n, (start_ms, end_ms, ids) in enumerate(pieces):
+                    text = self.decoder.decode(ids)
+                    if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
+                        continue  # faster-whisper drops empty and zero-length segments
+                    segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code,
+                                     "confidence": None, "words": words[k][n] if words is not None else None, "tokens": ids})
+            _, _, size, _, advance = cut[-1]
             return max(1, min(advance, size)) if window_mode == "seek" else size
 
         if window_mode == "seek":
             seek = 0
             while seek < content_frames:
-                seek += emit(run([seek]), 0, seek)
+                seek += emit_all(run([seek]), [seek])
         else:
             starts = list(range(0, content_frames, self.window_frames))
             per_batch = max(1, int(batch_windows))
@@ -760,13 +963,12 @@ class WhisperTranscriber:
                 per_batch = min(per_batch, MAX_LANES // beam_size)
             for i in range(0, len(starts), per_batch):
                 batch = starts[i:i + per_batch]
-                res = run(batch)
-                for lane, s in enumerate(batch):
-                    emit(res, lane, s)
+                emit_all(run(batch), batch)
         code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
         return {"segments": segments, "language": code}
 
-    def _transcribe_fallback(self, samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb) -> dict:
+    def _transcribe_fallback(self, samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb,
+                             word_timestamps=False) -> dict:
         """:meth:`WhisperTranscriber.transcribe` with the temperature fallback and previous-text prompts."""
         d = self.dims
         Tm, eot, tb = d["max_target_positions"], d["eot"], d["timestamp_begin"]
@@ -844,32 +1046,48 @@ class WhisperTranscriber:
                 accepted[w] = pick_fallback(tried[w], crt)
             return accepted
 
-        def emit(r: dict, seek: int) -> int:
+        def emit_all(accepted: list[dict], seeks: list[int]) -> int:
+            """The segments of the windows of one encode; -> the frames the last of them advances by."""
             nonlocal reset
-            size = min(self.window_frames, content_frames - seek)
-            windows_log.append({"start_frame": seek, **{k: r[k] for k in ("temperature", "avg_logprob", "compression_ratio",
-                                                                          "no_speech_prob")}})
-            if r["no_speech_prob"] > NO_SPEECH_THRESHOLD and (lpt is None or r["avg_logprob"] < lpt):
-                return size
-            pieces, advance = cut_window(r["tokens"], eot, tb, seek * MS_PER_FRAME, size)
             code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
-            for start_ms, end_ms, ids in pieces:
-                text = self.decoder.decode(ids)
-                if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
+            cut = []
+            for w, (r, seek) in enumerate(zip(accepted, seeks)):
+                size = min(self.window_frames, content_frames - seek)
+                if r["no_speech_prob"] > NO_SPEECH_THRESHOLD and (lpt is None or r["avg_logprob"] < lpt):
+                    cut.append((w, seek, size, None, size))
                     continue
-                segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code, "confidence": None,
-                                 "words": None, "tokens": ids, "temperature": r["temperature"], "avg_logprob": r["avg_logprob"],
-                                 "compression_ratio": r["compression_ratio"]})
-            if fb["condition_on_previous_text"]:
-                all_tokens.extend(emitted_tokens(r["tokens"], eot, tb))
-                if r["temperature"] > fb["prompt_reset_on_temperature"]:
-                    reset = len(all_tokens)
+                pieces, advance = cut_window(r["tokens"], eot, tb, seek * MS_PER_FRAME, size)
+                cut.append((w, seek, size, pieces, advance))
+            kept = [c for c in cut if c[3] is not None]
+            words = None
+            if word_timestamps and kept:
+                words = dict(zip((c[0] for c in kept), self._window_words(
+                    [(w, seek, size, [ids for _, _, ids in pieces]) for w, seek, size, pieces, _ in kept], lang_id, code)))
+            for w, seek, size, pieces, advance in cut:
+                r = accepted[w]
+                windows_log.append({"start_frame": seek, **{k: r[k] for k in ("temperature", "avg_logprob", "compression_ratio",
+                                                                              "no_speech_prob")}})
+                if pieces is None:
+                    continue
+                for n, (start_ms, end_ms, ids) in enumerate(pieces):
+                    text = self.decoder.decode(ids)
+                    if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
+                        continue
+                    segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code, "confidence": None,
+                                     "words": words[w][n] if words is not None else None, "tokens": ids,
+                                     "temperature": r["temperature"], "avg_logprob": r["avg_logprob"],
+                                     "compression_ratio": r["compression_ratio"]})
+                if fb["condition_on_previous_text"]:
+                    all_tokens.extend(emitted_tokens(r["tokens"], eot, tb))
+                    if r["temperature"] > fb["prompt_reset_on_temperature"]:
+                        reset = len(all_tokens)
+            _, _, size, _, advance = cut[-1]
             return max(1, min(advance, size)) if window_mode == "seek" else size
 
         if window_mode == "seek":
             seek = 0
             while seek < content_frames:
-                seek += emit(decode_all([seek])[0], seek)
+                seek += emit_all(decode_all([seek]), [seek])
         else:
             starts = list(range(0, content_frames, self.window_frames))
             per_batch = max(1, int(batch_windows))
@@ -877,8 +1095,7 @@ class WhisperTranscriber:
                 per_batch = min(per_batch, MAX_LANES // beam_size)
             for i in range(0, len(starts), per_batch):
                 batch = starts[i:i + per_batch]
-                for r, s_ in zip(decode_all(batch), batch):
-                    emit(r, s_)
+                emit_all(decode_all(batch), batch)
         code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
         return {"segments": segments, "language": code, "windows": windows_log}
 
@@ -892,8 +1109,11 @@ REFERENCE_CALL = {"beam_size": 5, "patience": 1.0, "temperature": list(REFERENCE
 
 def transcribe_result(raw: dict) -> dict:
     """The reference's result dict (``model_manager.py:449-463``): exactly its six keys per segment."""
-    keys = ("start_ms", "end_ms", "text", "language", "confidence", "words")
-    return {"segments": [{k: s[k] for k in keys} for s in raw["segments"]]}
+    keys = ("start_ms", "end_ms", "text", "language", "confidence")
+    word_keys = ("word", "start", "end", "confidence")       # the reference's ``Word`` schema
+    return {"segments": [{**{k: s[k] for k in keys},
+                          "words": None if s["words"] is None else [{k: w[k] for k in word_keys} for w in s["words"]]}
+                         for s in raw["segments"]]}
 
 
 def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None) -> dict:
@@ -903,7 +1123,9 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None)
     caller.  ``beam_size`` / ``patience`` are passed to the transcriber only when the config sets them, and so are the
     temperature-fallback and conditioning keys of :func:`check_fallback` (``temperature``, ``best_of``,
     ``compression_ratio_threshold``, ``log_prob_threshold``, ``condition_on_previous_text``,
-    ``prompt_reset_on_temperature``, ``seed``); the reference's call is :data:`REFERENCE_CALL`."""
+    ``prompt_reset_on_temperature``, ``seed``); the reference's call is :data:`REFERENCE_CALL`.  ``word_timestamps`` (a bool;
+    anything else is a ``ValueError``) fills every segment's ``words`` with ``{"word", "start", "end", "confidence"}`` from the
+    device's cross-attention alignment; it too is passed on only when the config sets it."""
     config = config or {}
     languages = config.get("languages")
     if isinstance(languages, (list, tuple)):
@@ -923,6 +1145,8 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None)
         if fb["condition_on_previous_text"] and config.get("window_mode", "seek") != "seek":
             raise ValueError("condition_on_previous_text needs window_mode 'seek': fixed windows decode in lockstep")
         given = {k: (list(fb[k]) if k == "temperature" else fb[k]) for k in given}
+    if "word_timestamps" in config:
+        given["word_timestamps"] = check_word_timestamps(config["word_timestamps"])
     samples, rate = (audio_source or default_audio_source)(path)
     check_rate(rate)
     raw = transcriber.transcribe(np.asarray(samples, dtype=np.float32), languages,

@@ -622,7 +622,25 @@ int eioku_thumbs_last_ms(eioku_thumbs_t* t, double* ms4);
  *   indices idx [B]; token_out [B], logprob_out [B].
  * prefill_logits (tests): rule-free logits [B][T][vocab] for ids [B][T]: positions 0 .. n_prefill - 1 in one prefill pass,
  *   the others walked position by position on the keys and values the prefill left.
- * last_launches: kernel launches of the last decode and its number of decoder steps. */
+ * last_launches: kernel launches of the last decode and its number of decoder steps.
+ * Word alignment (K21; Whisper's find_alignment on the device):
+ * set_alignment_heads: n (layer, head) pairs, generation_config.json's "alignment_heads"; n == 0 restores the default, every
+ *   head of the upper half of the decoder layers.  A pair outside the decoder is EIOKU_EINVAL.
+ * align: R rows over the last encode.  seq [R][T] = sot sequence (sot_len ids), <|notimestamps|>, the text ids (< eot), EOT,
+ *   padded with EOT to the common T; n_tok [R] the true lengths; row r reads encoded window windows[r] (NULL: identity)
+ *   and keeps F[r] = n_frames[r] / 2 frames.  One teacher-forced causal pass; the cross-attention probabilities of the
+ *   alignment heads are normalised over the n_tok[r] token rows (population std, no guard against 0), median-filtered
+ *   (width 7, reflect; skipped when F[r] <= 3), averaged over the heads and negated into the cost of the N[r] = n_tok[r] -
+ *   sot_len - 1 rows sot_len .. n_tok[r] - 2; dynamic time warping (fp32; diagonal if below both others, else up if below
+ *   both others, else left) gives jump_out [R][Nmax], Nmax = T - sot_len - 1: the frame index of the first path cell of
+ *   each row, -1 past N[r].  prob_out [R][Nmax]: for i < N[r] - 1 the softmax over the ids < eot of the logits at position
+ *   sot_len + i, taken at text id i; 0 elsewhere.  cost_out (tests; may be NULL) [R][Nmax][Fmax], Fmax = max F[r], 0 outside
+ *   a row's N[r] x F[r].  EIOKU_EINVAL before any launch: no encode, R outside 1..64, T > max_target_positions, n_tok[r] <
+ *   sot_len + 3 or > T, n_frames[r] outside 2 .. 2 * max_source_positions, an id outside the vocabulary, a text id >= eot.
+ * align_cost (tests): normalise + filter + head mean on supplied probabilities A [H][T][F] -> cost_out [T - sot_len - 1][F].
+ * dtw (tests): the warping on a supplied cost [N][F] (both 1..4096) -> jump_out [N]; text_idx / time_idx [N + F] with
+ *   path_len: the path from (0, 0) to (N - 1, F - 1) (all three NULL: not wanted).
+ * last_align_ms: device milliseconds of the last align: the pass with the probabilities, the cost kernels, the warping. */
 typedef struct {
   int n_mels, d_model, heads, enc_layers, dec_layers, enc_ffn, dec_ffn, vocab, max_source_positions, max_target_positions;
   int eot, no_timestamps, timestamp_begin, no_speech, max_initial_timestamp_index;
@@ -669,6 +687,14 @@ int eioku_whisper_sample(eioku_whisper_t* m, const float* logits, int B, const i
                          int32_t* token_out, float* logprob_out);
 int eioku_whisper_prefill_logits(eioku_whisper_t* m, const int32_t* ids, int T, int B, int n_prefill, float* logits_out);
 int eioku_whisper_encoder_output(eioku_whisper_t* m, void* out_f16, size_t numel);
+int eioku_whisper_set_alignment_heads(eioku_whisper_t* m, const int32_t* layer_head_pairs, int n);
+int eioku_whisper_align(eioku_whisper_t* m, const int32_t* seq, int T, const int32_t* n_tok, int sot_len,
+                        const int32_t* windows, const int32_t* n_frames, int R, int32_t* jump_out, float* prob_out,
+                        float* cost_out);
+int eioku_whisper_align_cost(eioku_whisper_t* m, const float* A, int H, int T, int F, int sot_len, float* cost_out);
+int eioku_whisper_dtw(eioku_whisper_t* m, const float* cost, int N, int F, int32_t* jump_out, int32_t* text_idx,
+                      int32_t* time_idx, int* path_len);
+int eioku_whisper_last_align_ms(const eioku_whisper_t* m, double* pass_ms, double* cost_ms, double* dtw_ms);
 int eioku_whisper_last_flops(const eioku_whisper_t* m, double* flops);
 int eioku_whisper_last_launches(const eioku_whisper_t* m, int* launches, int* steps);
 

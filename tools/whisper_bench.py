@@ -4,6 +4,7 @@
     python tools/whisper_bench.py [--shapes base small] [--windows 64] [--out profiles/whisper.json]
     python tools/whisper_bench.py --beam 5 [--shapes base]      # adds a beam block to the shapes already in --out
     python tools/whisper_bench.py --prompted [--shapes base]    # adds a prompted block (K20c) in the same way
+    python tools/whisper_bench.py --align [--shapes base]       # adds a word-alignment block (K21) in the same way
 
 For each shape (the openai `base` and `small` dimensions, vocabulary 51865, ctx 1500): log-mel over `--windows` windows of
 30 s, the encoder per window at batch 8, a decoder step at B = 1, 8 and 32 (greedy, 32 sampled tokens, lanes never end
@@ -17,6 +18,10 @@ with the greedy step of the same run next to it, and merges the block into the s
 `--prompted` measures K20c only: a 227-token prompt (``<|startofprev|>`` + 223 previous tokens + 3) through the one-pass
 prefill (`decode_prompted`, one new token) against the same prompt walked position by position by `decode` with one new
 token, at 1 and 8 windows; and a sampled step (temperature 1) against a greedy step of the same entry at 8 lanes.
+
+`--align` measures K21 only: one 30 s window with 224 text tokens (F = 1500 frames, the default alignment heads) through
+`align`: the device time (hipEvent) of the teacher-forced pass with the token probabilities, of the cost kernels and of the
+DTW, the wall-clock time of the whole call, and next to them the greedy decode of 224 tokens on the same window.
 """
 from __future__ import annotations
 
@@ -94,6 +99,31 @@ def prompted_block(t, dims: dict, audio: np.ndarray, steps: int) -> dict:
     return block
 
 
+def align_block(t, dims: dict, audio: np.ndarray, n_text: int = 224) -> dict:
+    base = [dims["sot"], dims["lang_ids"][0], dims["transcribe"]]
+    rng = np.random.default_rng(3)
+    seq = base + [dims["no_timestamps"]] + [int(v) for v in rng.integers(1000, 40000, size=n_text)] + [dims["eot"]]
+    t.set_audio(audio)
+    t.logmel([0], fetch=False)
+    t.encode(1)
+    block = {"windows": 1, "text_tokens": n_text, "frames": dims["max_source_positions"],
+             "alignment_heads": dims["dec_layers"] - dims["dec_layers"] // 2, "heads_per_layer": dims["heads"]}
+    parts = []
+
+    def run():
+        t.align([seq], [len(seq)], len(base), [2 * dims["max_source_positions"]])
+        parts.append(t.last_align_ms())
+
+    block["align_call_ms"] = timed(run)
+    best = min(parts[1:], key=sum)
+    block["pass_device_ms"], block["cost_device_ms"], block["dtw_device_ms"] = best
+    block["align_launches"] = t.last_launches()[0]
+    ms = timed(lambda: t.decode(base, 1, n_text, sync_every=n_text))
+    block["greedy_decode_ms"] = ms
+    block["greedy_decode_steps"] = t.last_launches()[1]
+    return block
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["base", "small"], choices=sorted(SHAPES))
@@ -102,6 +132,7 @@ def main() -> None:
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--beam", type=int, default=0, help="measure beam search at this beam size and merge it into --out")
     ap.add_argument("--prompted", action="store_true", help="measure the prompt prefill and the sampled step and merge them into --out")
+    ap.add_argument("--align", action="store_true", help="measure the word alignment (K21) and merge it into --out")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "whisper.json"))
     args = ap.parse_args()
 
@@ -110,15 +141,18 @@ def main() -> None:
 
     info = _lib.device_info()
     rng = np.random.default_rng(0)
-    if args.beam or args.prompted:
+    if args.beam or args.prompted or args.align:
         out = Path(args.out)
         result = json.loads(out.read_text()) if out.exists() else {"what": "tools/whisper_bench.py --beam", "device": info, "shapes": []}
         audio = (0.1 * rng.standard_normal(8 * 480000)).astype(np.float32)
         for name in args.shapes:
             dims = dims_for(name)
             t = WhisperTranscriber(dims, seeded_weights(dims, 1))
-            key = "beam_search" if args.beam else "prompted"
-            block = beam_block(t, dims, audio, args.beam, args.steps) if args.beam else prompted_block(t, dims, audio, args.steps)
+            key = "beam_search" if args.beam else ("prompted" if args.prompted else "word_alignment")
+            if args.align:
+                block = align_block(t, dims, audio)
+            else:
+                block = beam_block(t, dims, audio, args.beam, args.steps) if args.beam else prompted_block(t, dims, audio, args.steps)
             t.close()
             print(json.dumps({"shape": name, **block}))
             rows = [r for r in result["shapes"] if r.get("shape") == name]
