@@ -238,6 +238,13 @@ SIGNATURES = {
     "eioku_whisper_last_align_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "eioku_whisper_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_whisper_last_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eioku_vad_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "eioku_vad_destroy": (None, [C.c_void_p]),
+    "eioku_vad_num_tensors": (C.c_int, [C.c_void_p]),
+    "eioku_vad_tensor_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eioku_vad_set_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "eioku_vad_probs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]),
+    "eioku_vad_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 

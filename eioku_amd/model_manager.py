@@ -155,7 +155,8 @@ class ModelManager:
 
     def __init__(self, cache_dir: str = "/models", *, frame_source=None, detector_factory=None, batch_size: int = 64,
                  random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
-                 ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None):
+                 ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None,
+                 gpu_vad: bool = False, vad_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
@@ -166,7 +167,9 @@ class ModelManager:
         ``transcribe_video`` on the HIP path (Whisper, ``eioku_amd.transcribe``); ``audio_source(path) -> (float32 mono
         samples, sample_rate)`` and ``transcriber_factory(cache_dir, model_name) -> object with transcribe(samples, language,
         window_mode=, batch_windows=)`` are its seams (``beam_size=`` / ``patience=`` follow only when the task's config sets
-        them)."""
+        them).  ``gpu_vad=True`` runs Silero VAD (``eioku_amd.vad``) in front of the transcription when the task's
+        ``vad_filter`` is on (the reference's default); ``vad_factory(cache_dir) -> object with speech_probs(samples)`` is
+        its seam."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -179,6 +182,8 @@ class ModelManager:
         self._gpu_transcription = bool(gpu_transcription)
         self._audio_source = audio_source
         self._transcriber_factory = transcriber_factory
+        self._gpu_vad = bool(gpu_vad)
+        self._vad_factory = vad_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -233,7 +238,8 @@ class ModelManager:
         language, confidence: None, words: None}]}``.  Greedy decoding by default; config ``beam_size`` (1..8; 5 is the
         reference's call) and ``patience`` switch to beam search, ``temperature`` (a list) with ``best_of`` and the two
         thresholds adds the temperature fallback, ``condition_on_previous_text`` the previous-text prompts
-        (``transcribe.REFERENCE_CALL`` is the reference's call); values outside their ranges raise ``ValueError``.  The
+        (``transcribe.REFERENCE_CALL`` is the reference's call); values outside their ranges raise ``ValueError``.  A manager
+        built with ``gpu_vad=True`` applies ``vad_filter`` (default on) and ``vad_parameters`` through Silero VAD first.  The
         deviations from the reference's call are listed in INTEGRATION.md §3."""
         if not self._gpu_transcription:
             raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")
@@ -247,12 +253,21 @@ class ModelManager:
                 transcriber = self._transcriber_factory(self.cache_dir, model_name)
             else:
                 transcriber = WhisperTranscriber.from_cache(self.cache_dir, model_name, seed=self._seed)
+            vad = None
             try:
-                result = transcribe_video(video_path, config, transcriber=transcriber, audio_source=self._audio_source)
+                if self._gpu_vad and config.get("vad_filter", True):
+                    if self._vad_factory is not None:
+                        vad = self._vad_factory(self.cache_dir)
+                    else:
+                        from .vad import SileroVad
+
+                        vad = SileroVad.from_cache(self.cache_dir, seed=self._seed)
+                result = transcribe_video(video_path, config, transcriber=transcriber, audio_source=self._audio_source, vad=vad)
             finally:
-                close = getattr(transcriber, "close", None)
-                if close:
-                    close()
+                for model in (vad, transcriber):
+                    close = getattr(model, "close", None)
+                    if close:
+                        close()
             logger.info(f"✅ Transcription complete: {len(result['segments'])} segments")
             return result
         except Exception as e:

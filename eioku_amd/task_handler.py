@@ -15,6 +15,8 @@ storage go through two small hooks carried in the arq ``ctx`` dict.
     ctx["gpu_ocr"]      true: run ``ocr`` on the HIP path (ModelManager.extract_ocr); otherwise it is refused as before
     ctx["gpu_transcription"]  true: run ``transcription`` on the HIP path (ModelManager(gpu_transcription=True)
                         .transcribe_video, one "transcript.segment" envelope per segment); otherwise refused as before
+    ctx["gpu_vad"]      true (with gpu_transcription): the manager is built with ``gpu_vad=True``, so a task whose
+                        ``vad_filter`` is on (the default) is gated by Silero VAD on the HIP path
 """
 
 from __future__ import annotations
@@ -158,7 +160,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
         model_cache_dir = os.getenv("MODEL_CACHE_DIR", "/models")
         factory = ctx.get("model_manager_factory", ModelManager)
         if task_type == "transcription" and ctx.get("gpu_transcription"):  # opt-in: the manager is built with the HIP path on
-            model_manager = factory(cache_dir=model_cache_dir, gpu_transcription=True)
+            extra = {"gpu_vad": True} if ctx.get("gpu_vad") else {}
+            model_manager = factory(cache_dir=model_cache_dir, gpu_transcription=True, **extra)
         else:
             model_manager = factory(cache_dir=model_cache_dir)
         if task_type not in KNOWN_TASK_TYPES:

@@ -1116,21 +1116,32 @@ def transcribe_result(raw: dict) -> dict:
                          for s in raw["segments"]]}
 
 
-def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None) -> dict:
+def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None, vad=None) -> dict:
     """``ModelManager.transcribe_video`` body.  Config keys consumed: ``languages`` (string or list: the first entry; None =
-    detect), ``vad_filter`` (accepted, not applied), ``window_mode``, ``batch_windows``, ``beam_size`` (1..8, default 1 =
+    detect), ``vad_filter`` (applied when a ``vad`` object is given, see below), ``window_mode``, ``batch_windows``, ``beam_size`` (1..8, default 1 =
     greedy; 5 is the reference's call) and ``patience`` (positive, default 1.0); ``model_name`` picks the checkpoint in the
     caller.  ``beam_size`` / ``patience`` are passed to the transcriber only when the config sets them, and so are the
     temperature-fallback and conditioning keys of :func:`check_fallback` (``temperature``, ``best_of``,
     ``compression_ratio_threshold``, ``log_prob_threshold``, ``condition_on_previous_text``,
     ``prompt_reset_on_temperature``, ``seed``); the reference's call is :data:`REFERENCE_CALL`.  ``word_timestamps`` (a bool;
     anything else is a ``ValueError``) fills every segment's ``words`` with ``{"word", "start", "end", "confidence"}`` from the
-    device's cross-attention alignment; it too is passed on only when the config sets it."""
+    device's cross-attention alignment; it too is passed on only when the config sets it.
+
+    ``vad``: an object with ``speech_probs(samples) -> probability per 512-sample chunk`` (:class:`eioku_amd.vad.SileroVad`).
+    With it and ``config.get("vad_filter", True)`` (the reference's default), the transcriber sees the concatenation of the
+    speech chunks of :func:`eioku_amd.vad.speech_timestamps` (``vad_parameters``: a dict of its six options) and the times
+    are mapped back to the file; no speech returns no segments without a transcriber call.  Without ``vad`` the filter is
+    logged and not applied."""
     config = config or {}
     languages = config.get("languages")
     if isinstance(languages, (list, tuple)):
         languages = languages[0] if languages else None
-    if config.get("vad_filter"):
+    use_vad = vad is not None and bool(config.get("vad_filter", True))
+    if use_vad:
+        from . import vad as vad_mod
+
+        vad_options = vad_mod.vad_options_from(config.get("vad_parameters"))
+    elif config.get("vad_filter"):
         logger.info("vad_filter is accepted but not applied: Silero VAD is not built; the no-speech rule skips silence")
     beam = {}
     if "beam_size" in config or "patience" in config:
@@ -1149,7 +1160,19 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None)
         given["word_timestamps"] = check_word_timestamps(config["word_timestamps"])
     samples, rate = (audio_source or default_audio_source)(path)
     check_rate(rate)
-    raw = transcriber.transcribe(np.asarray(samples, dtype=np.float32), languages,
+    samples = np.asarray(samples, dtype=np.float32)
+    chunks = None
+    if use_vad:
+        samples = samples.reshape(-1)
+        chunks = vad_mod.speech_timestamps(vad.speech_probs(samples), samples.size, vad_options)
+        logger.info(f"VAD kept {sum(c['end'] - c['start'] for c in chunks) / SAMPLE_RATE:.2f} s of "
+                    f"{samples.size / SAMPLE_RATE:.2f} s in {len(chunks)} chunks")
+        if not chunks:
+            return {"segments": []}
+        samples = vad_mod.collect_chunks(samples, chunks)
+    raw = transcriber.transcribe(samples, languages,
                                  window_mode=config.get("window_mode", "seek"),
                                  batch_windows=int(config.get("batch_windows", 8)), **beam, **given)
+    if chunks is not None:
+        raw = {**raw, "segments": vad_mod.restore_speech_timestamps(raw["segments"], chunks)}
     return transcribe_result(raw)

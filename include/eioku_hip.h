@@ -698,6 +698,28 @@ int eioku_whisper_last_align_ms(const eioku_whisper_t* m, double* pass_ms, doubl
 int eioku_whisper_last_flops(const eioku_whisper_t* m, double* flops);
 int eioku_whisper_last_launches(const eioku_whisper_t* m, int* launches, int* steps);
 
+/* ---- transcription: voice activity (K22), csrc/vad.hip -----------------------------------------------------------------
+ * The 16 kHz branch of Silero VAD v5/v6 in fp32: one speech probability per chunk of 512 samples (the last 64 samples of
+ * the previous chunk are its context, zeros before the first).  A handle owns its stream, its weights and its buffers, and
+ * can live next to any other handle.  Files longer than slab_chunks chunks run slab by slab; the context samples and the
+ * LSTM state are carried on the device, so the result does not depend on slab_chunks.
+ *   tensor_info / set_tensor: fp32, row-major rows x cols, under the names stft.forward_basis_buffer (258 x 256),
+ *     encoder.{0..3}.weight (out x 3 in, the Conv1d weight flattened) / .bias, decoder.rnn.weight_ih / weight_hh (512 x 128,
+ *     gate order i f g o) / bias_ih / bias_hh, decoder.out.weight (1 x 128) / .bias.
+ *   probs: host samples in, host probabilities out.  The audio is padded with 512 - n_samples % 512 zeros (a whole zero
+ *     chunk when n_samples is a multiple of 512), so n_probs = n_samples / 512 + 1; *n_probs is written even when
+ *     n_probs_cap is too small (EIOKU_EINVAL).  Every tensor must have been set.
+ *   last_ms: kernel time of the last probs call, summed over its slabs (batched stages; recurrence). */
+typedef struct eioku_vad eioku_vad_t;
+int eioku_vad_create(int slab_chunks, eioku_vad_t** out);
+void eioku_vad_destroy(eioku_vad_t* v);
+int eioku_vad_num_tensors(const eioku_vad_t* v);
+int eioku_vad_tensor_info(const eioku_vad_t* v, int idx, char* name, size_t name_cap, int* rows, int* cols);
+int eioku_vad_set_tensor(eioku_vad_t* v, int idx, const float* host_data, size_t numel);
+int eioku_vad_probs(eioku_vad_t* v, const float* samples, long long n_samples, float* probs_out, long long n_probs_cap,
+                    long long* n_probs);
+int eioku_vad_last_ms(const eioku_vad_t* v, double* encode_ms, double* lstm_ms);
+
 #ifdef __cplusplus
 }
 #endif
