@@ -19,7 +19,9 @@
 //   k_gemm_f32*       exact-fp32 MFMA GEMMs (v_mfma_f32_32x32x2_f32): the fallback route
 #include "common.h"
 
+#include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include <cmath>
@@ -779,6 +781,36 @@ int find(const eioku_bert* m, const std::string& name) {
 
 const float* tp(const eioku_bert* m, const std::string& name) { return m->tensors[find(m, name)].dev; }
 
+constexpr int kMaxSplit = 4;
+
+// Route log (eioku_debug_bert_routes): which kernel instantiation a launch site of this file started, counted where it
+// is started.  One fixed table of relaxed atomic host counters, one slot per route below (the GEMM families in mixed
+// radix over their template arguments); no device work, no allocation.  splits<n> counts GEMM launches by their
+// split-K factor.
+enum BertRoute {
+  kRouteAttnBf = 0, kRouteAttn8, kRouteAttn1,
+  kRouteGemmBf,                         // + EPI * 4 + (128-row tile) * 2 + AS
+  kRouteGemmF32 = kRouteGemmBf + 8,     // + EPI * 2 + (128-row tile)
+  kRouteGemmF32S = kRouteGemmF32 + 4,   // + EPI
+  kRouteAddLn6 = kRouteGemmF32S + 2, kRouteAddLn12, kRouteAddLn,
+  kRoutePoolG1, kRoutePoolG2,
+  kRouteSplits1,                        // + splits - 1
+  kNumBertRoutes = kRouteSplits1 + 4
+};
+constexpr const char* kBertRouteNames[kNumBertRoutes] = {
+    "attn_bf", "attn8", "attn1",
+    "gemm_bf<EPI0,T64,AS0>", "gemm_bf<EPI0,T64,AS1>", "gemm_bf<EPI0,T128,AS0>", "gemm_bf<EPI0,T128,AS1>",
+    "gemm_bf<EPI1,T64,AS0>", "gemm_bf<EPI1,T64,AS1>", "gemm_bf<EPI1,T128,AS0>", "gemm_bf<EPI1,T128,AS1>",
+    "gemm_f32<EPI0,T64>", "gemm_f32<EPI0,T128>", "gemm_f32<EPI1,T64>", "gemm_f32<EPI1,T128>",
+    "gemm_f32_s<EPI0>", "gemm_f32_s<EPI1>",
+    "add_ln_fixed<6>", "add_ln_fixed<12>", "add_ln",
+    "pool<G1>", "pool<G2>",
+    "splits<1>", "splits<2>", "splits<3>", "splits<4>",
+};
+static_assert(kMaxSplit == 4, "one splits<n> counter per split-K factor");
+std::atomic<unsigned> g_bert_routes[kNumBertRoutes];
+void bert_route_hit(int id) { g_bert_routes[id].fetch_add(1u, std::memory_order_relaxed); }
+
 // Small-M GEMM (M < 8192: the ingest path's 8 segments = 1024 tokens).  With 32-deep k-chunks a 64x64 tile is a
 // chain of K/32 dependent load -> LDS -> MFMA rounds (12 for K = 384) and a launch is ~100-400 workgroups, so the
 // chain length IS the kernel's duration.  Here a stage is 128 deep: 16 loads in flight per thread, 64 MFMAs per
@@ -1063,12 +1095,11 @@ __global__ __launch_bounds__(128 * WGM, WGM == 2 ? 2 : 1) void k_gemm_bf_s(const
   gemm_epilogue<EPI, WMT, WNT, BM>(acc, bias, C, Chi, Clo, ldc, M, m0, n0, wm, wn, lane);
 }
 
-constexpr int kMaxSplit = 4;
-
 void launch_add_ln(const float* a, int nsplit, const float* abias, const float* r, int T, int H, const float* g,
                    const float* b, float eps, float* out, hipStream_t stream, unsigned short* ohi = nullptr,
                    unsigned short* olo = nullptr) {
   const dim3 grid((unsigned)(((size_t)T * 64 + 255) / 256)), block(256);
+  bert_route_hit(H == 384 ? kRouteAddLn6 : H == 768 ? kRouteAddLn12 : kRouteAddLn);
   if (H == 384) hipLaunchKernelGGL(k_add_ln_fixed<6>, grid, block, 0, stream, a, nsplit, abias, r, T, g, b, eps, out, ohi, olo);
   else if (H == 768) hipLaunchKernelGGL(k_add_ln_fixed<12>, grid, block, 0, stream, a, nsplit, abias, r, T, g, b, eps, out, ohi, olo);
   else hipLaunchKernelGGL(k_add_ln, grid, block, 0, stream, a, nsplit, abias, r, T, H, g, b, eps, out, ohi, olo);
@@ -1080,16 +1111,13 @@ void launch_add_ln(const float* a, int nsplit, const float* abias, const float* 
 int pick_splits(int M, int N, int K) {
   if (M >= 8192) return 1;
   const int blocks = ((M + 63) / 64) * (N / 64);
-  if (K % 128 == 0) {  // k_gemm_f32_s: stages of 128; the largest split <= kMaxSplit that divides them evenly
-    const int stages = K / 128;
-    int best = 1;
-    for (int s = 2; s <= kMaxSplit; ++s)
-      if (stages % s == 0 && blocks * best < 2 * num_cus()) best = s;
-    return best;
-  }
-  int s = 1;
-  while (s < kMaxSplit && blocks * s < 2 * num_cus() && (K / kBK) % (2 * s) == 0) s *= 2;
-  return s;
+  // K % 128 == 0 (eioku_bert_create requires it of hidden and ffn): stages of 128, as k_gemm_f32_s and k_gemm_bf_s walk
+  // them; the largest split <= kMaxSplit that divides them evenly
+  const int stages = K / 128;
+  int best = 1;
+  for (int s = 2; s <= kMaxSplit; ++s)
+    if (stages % s == 0 && blocks * best < 2 * num_cus()) best = s;
+  return best;
 }
 
 struct Planes {  // an activation tensor as its two bf16 terms, [rows][ld] each
@@ -1114,6 +1142,7 @@ template <int EPI, int WMT, int WNT, bool AS, int WGM = 2>
 void launch_bf64(dim3 grid, size_t lds, hipStream_t stream, const float* A, int lda, const float* W, const unsigned short* whi,
                  const unsigned short* wlo, const float* bias, float* C, int ldc, int M, int N, int K, int kst, const Planes* ap,
                  const Planes* cp) {
+  bert_route_hit(kRouteGemmBf + EPI * 4 + (WMT == 2) * 2 + AS);
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_bf_s<EPI, WMT, WNT, AS, WGM>),
@@ -1139,6 +1168,7 @@ int gemm(const float* A, int lda, const float* W, const float* bias, float* C, i
   const unsigned short* whi = ws ? ws->hi : nullptr;
   const unsigned short* wlo = ws ? ws->lo : nullptr;
   EIOKU_REQUIRE(!(ap || cp) || (s_route && bf && whi && (!cp || splits == 1)), "planes on a GEMM route that has none");
+  if (splits <= kMaxSplit) bert_route_hit(kRouteSplits1 + splits - 1);
   prof_start(EIOKU_PROF_GEMM, stream);
   // EIOKU_GEMM_BF16=0 / EIOKU_GEMM_S=0 / EIOKU_ATTN_MFMA=0 route the encoder through the fp32-FMA kernels (the
   // numerics cross-check of tests/test_bert_gpu.py::test_fp32_fma_route_matches_the_mfma_route)
@@ -1166,6 +1196,7 @@ int gemm(const float* A, int lda, const float* W, const float* bias, float* C, i
     }
   } else if (M >= 8192 && !(bf && s_route)) {
     dim3 grid((unsigned)((M + 127) / 128), (unsigned)(N / 128), (unsigned)splits);
+    bert_route_hit(kRouteGemmF32 + epi * 2 + 1);
     if (epi == 1) hipLaunchKernelGGL((k_gemm_f32<1, 128, 128>), grid, dim3(256), 0, stream, A, lda, W, bias, C, ldc, M, N, K, kchunks);
     else hipLaunchKernelGGL((k_gemm_f32<0, 128, 128>), grid, dim3(256), 0, stream, A, lda, W, bias, C, ldc, M, N, K, kchunks);
   } else if (s_route) {
@@ -1178,11 +1209,13 @@ int gemm(const float* A, int lda, const float* W, const float* bias, float* C, i
       attr = true;
     }
     const int kstages = K / 128 / splits;
+    bert_route_hit(kRouteGemmF32S + epi);
     // EIOKU_GEMM_BF16=0, or a caller without the handle's weight planes: the exact-fp32 matrix pipe
     if (epi == 1) hipLaunchKernelGGL((k_gemm_f32_s<1>), grid, dim3(256), lds, stream, A, lda, W, bias, C, ldc, M, N, K, kstages);
     else hipLaunchKernelGGL((k_gemm_f32_s<0>), grid, dim3(256), lds, stream, A, lda, W, bias, C, ldc, M, N, K, kstages);
   } else {
     dim3 grid((unsigned)((M + 63) / 64), (unsigned)(N / 64), (unsigned)splits);
+    bert_route_hit(kRouteGemmF32 + epi * 2);
     if (epi == 1) hipLaunchKernelGGL((k_gemm_f32<1, 64, 64>), grid, dim3(256), 0, stream, A, lda, W, bias, C, ldc, M, N, K, kchunks);
     else hipLaunchKernelGGL((k_gemm_f32<0, 64, 64>), grid, dim3(256), 0, stream, A, lda, W, bias, C, ldc, M, N, K, kchunks);
   }
@@ -1404,6 +1437,7 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
     const std::string p = "encoder.layer." + std::to_string(l) + ".";
     if ((rc = gemm(m->x, H, tp(m, p + "attention.self.query.weight"), tp(m, p + "attention.self.query.bias"), m->qkv,
                    3 * H, T, 3 * H, H, 0, 1, stream, &m->wsplit[(size_t)4 * l + 0], xa))) return rc;
+    bert_route_hit(amfma ? kRouteAttnBf : parts == 4 ? kRouteAttn8 : kRouteAttn1);
     if (amfma) {
       hipLaunchKernelGGL(k_attention_bf, dim3(B, m->heads), dim3(256), 0, stream, m->qkv, d_mask, S, H, m->ctx, cP.hi, cP.lo);
     } else {
@@ -1439,6 +1473,7 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
   // two token groups when they fit in a workgroup and in the 1024-float staging arrays
   const int pgroups = (2 * pthreads <= 1024 && S <= 1024) ? 2 : 1;
   EIOKU_REQUIRE(S <= 1024, "sequence length %d exceeds the pooling kernel's mask buffer", S);
+  bert_route_hit(pgroups == 2 ? kRoutePoolG2 : kRoutePoolG1);
   hipLaunchKernelGGL(k_pool_norm, dim3(B), dim3(pgroups * pthreads), 0, stream, m->x, d_mask, S, H, d_out);
   EIOKU_LAUNCH_CHECK();
   m->flops_last = (double)T * m->L * (2.0 * H * 3 * H + 2.0 * H * H + 4.0 * H * m->ffn) +
@@ -1447,6 +1482,30 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
     EIOKU_HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)B * H * 4, hipMemcpyDeviceToHost, stream));
     EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
   }
+  return EIOKU_OK;
+}
+
+// Route log: one line "name count" for EVERY route of the table above, zeros included, counted in this process since the
+// last reset.  Host counters only: needs no device and no eioku_init.
+int eioku_debug_bert_routes(char* buf, size_t cap, int reset) {
+  EIOKU_REQUIRE(buf || cap == 0, "NULL buffer");
+  size_t pos = 0;
+  bool fits = true;
+  for (int i = 0; i < kNumBertRoutes; ++i) {
+    const unsigned c = reset ? g_bert_routes[i].exchange(0u, std::memory_order_relaxed)
+                             : g_bert_routes[i].load(std::memory_order_relaxed);
+    if (!buf) continue;
+    char line[64];
+    const int n = snprintf(line, sizeof line, "%s %u\n", kBertRouteNames[i], c);
+    if (pos + (size_t)n + 1 > cap) {
+      fits = false;
+      continue;
+    }
+    memcpy(buf + pos, line, (size_t)n);
+    pos += (size_t)n;
+  }
+  if (cap) buf[pos] = 0;
+  EIOKU_REQUIRE(fits, "route log does not fit %zu bytes", cap);
   return EIOKU_OK;
 }
 

@@ -86,6 +86,19 @@ def load_state(path: str | Path, cfg: dict) -> dict[str, np.ndarray]:
     return out
 
 
+def routes(reset: bool = False) -> dict[str, int]:
+    """Route log of the encoder: {route name: launches} in this process since the last reset, as counted by the launch
+    code itself (``eioku_debug_bert_routes``).  Every known route is present, zeros included, e.g.
+    ``{"attn_bf": 6, "attn8": 0, ..., "gemm_bf<EPI0,T64,AS1>": 18, ..., "splits<3>": 6}``."""
+    buf = C.create_string_buffer(1 << 12)
+    _lib.check(_lib.load().eioku_debug_bert_routes(buf, len(buf), int(reset)), "eioku_debug_bert_routes")
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, count = line.rsplit(" ", 1)
+        out[name] = int(count)
+    return out
+
+
 class MiniLMEncoder:
     """BERT sentence encoder resident on one GPU."""
 

@@ -338,6 +338,13 @@ int eioku_bert_set_tensor(eioku_bert_t* m, int idx, const float* host_data, size
 int eioku_bert_embed(eioku_bert_t* m, const int32_t* ids, const uint8_t* mask, int B, int S, float* out,
                      int mem, void* stream);
 int eioku_bert_last_flops(const eioku_bert_t* m, double* flops);
+/* Route log of the encoder: one line "name count\n" for EVERY kernel route eioku_bert_embed can launch, zeros included,
+ * counted by the launch sites in this process since the last reset: attn_bf / attn8 / attn1,
+ * gemm_bf<EPI0|1,T64|T128,AS0|1>, gemm_f32<EPI0|1,T64|T128>, gemm_f32_s<EPI0|1>, add_ln_fixed<6> / add_ln_fixed<12> /
+ * add_ln, pool<G1|G2>, and splits<1..4> (GEMM launches by split-K factor).  Host counters only: no device work, no
+ * allocation, no eioku_init.  buf receives the NUL-terminated text (EIOKU_EINVAL when cap is too small; buf NULL with
+ * cap 0 only resets); reset != 0 clears the counters after reading them.  Thread safe. */
+int eioku_debug_bert_routes(char* buf, size_t cap, int reset);
 
 /* as eioku_topk_merge, for lists that carry k_in >= k entries each ([nlists][nq][k_in]) */
 int eioku_topk_merge_ex(const float* d_lists, const int64_t* i_lists, int nlists, int nq, int k_in, int k,
