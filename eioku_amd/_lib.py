@@ -246,6 +246,13 @@ SIGNATURES = {
     "eioku_vad_set_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "eioku_vad_probs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]),
     "eioku_vad_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "eioku_audio_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_void_p)]),
+    "eioku_audio_destroy": (None, [C.c_void_p]),
+    "eioku_audio_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_longlong,
+                                       C.POINTER(C.c_longlong)]),
+    "eioku_audio_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p]),
+    "eioku_audio_tile": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "eioku_audio_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 

@@ -156,7 +156,7 @@ class ModelManager:
     def __init__(self, cache_dir: str = "/models", *, frame_source=None, detector_factory=None, batch_size: int = 64,
                  random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
                  ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None,
-                 gpu_vad: bool = False, vad_factory=None):
+                 gpu_vad: bool = False, vad_factory=None, gpu_audio: bool = False, audio_frontend_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
@@ -169,7 +169,9 @@ class ModelManager:
         window_mode=, batch_windows=)`` are its seams (``beam_size=`` / ``patience=`` follow only when the task's config sets
         them).  ``gpu_vad=True`` runs Silero VAD (``eioku_amd.vad``) in front of the transcription when the task's
         ``vad_filter`` is on (the reference's default); ``vad_factory(cache_dir) -> object with speech_probs(samples)`` is
-        its seam."""
+        its seam.  ``gpu_audio=True`` (with ``gpu_transcription``) reads PCM WAV of any sample rate, width and channel count
+        and resamples it to 16 kHz on the device (``eioku_amd.audio``); ``audio_frontend_factory() -> object with load(path)
+        and resample_float(samples, rate)`` is its seam.  Without it audio that is not 16 kHz raises, as before."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -184,6 +186,8 @@ class ModelManager:
         self._transcriber_factory = transcriber_factory
         self._gpu_vad = bool(gpu_vad)
         self._vad_factory = vad_factory
+        self._gpu_audio = bool(gpu_audio)
+        self._audio_frontend_factory = audio_frontend_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -239,7 +243,8 @@ class ModelManager:
         reference's call) and ``patience`` switch to beam search, ``temperature`` (a list) with ``best_of`` and the two
         thresholds adds the temperature fallback, ``condition_on_previous_text`` the previous-text prompts
         (``transcribe.REFERENCE_CALL`` is the reference's call); values outside their ranges raise ``ValueError``.  A manager
-        built with ``gpu_vad=True`` applies ``vad_filter`` (default on) and ``vad_parameters`` through Silero VAD first.  The
+        built with ``gpu_vad=True`` applies ``vad_filter`` (default on) and ``vad_parameters`` through Silero VAD first; one
+        built with ``gpu_audio=True`` takes PCM WAV of any rate, width and channel count and resamples it on the device.  The
         deviations from the reference's call are listed in INTEGRATION.md §3."""
         if not self._gpu_transcription:
             raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")
@@ -253,8 +258,17 @@ class ModelManager:
                 transcriber = self._transcriber_factory(self.cache_dir, model_name)
             else:
                 transcriber = WhisperTranscriber.from_cache(self.cache_dir, model_name, seed=self._seed)
-            vad = None
+            vad = frontend = None
             try:
+                extra = {}
+                if self._gpu_audio:
+                    if self._audio_frontend_factory is not None:
+                        frontend = self._audio_frontend_factory()
+                    else:
+                        from .audio import AudioFrontEnd
+
+                        frontend = AudioFrontEnd()
+                    extra["audio_frontend"] = frontend
                 if self._gpu_vad and config.get("vad_filter", True):
                     if self._vad_factory is not None:
                         vad = self._vad_factory(self.cache_dir)
@@ -262,9 +276,10 @@ class ModelManager:
                         from .vad import SileroVad
 
                         vad = SileroVad.from_cache(self.cache_dir, seed=self._seed)
-                result = transcribe_video(video_path, config, transcriber=transcriber, audio_source=self._audio_source, vad=vad)
+                result = transcribe_video(video_path, config, transcriber=transcriber, audio_source=self._audio_source, vad=vad,
+                                          **extra)
             finally:
-                for model in (vad, transcriber):
+                for model in (frontend, vad, transcriber):
                     close = getattr(model, "close", None)
                     if close:
                         close()

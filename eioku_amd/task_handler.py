@@ -17,6 +17,8 @@ storage go through two small hooks carried in the arq ``ctx`` dict.
                         .transcribe_video, one "transcript.segment" envelope per segment); otherwise refused as before
     ctx["gpu_vad"]      true (with gpu_transcription): the manager is built with ``gpu_vad=True``, so a task whose
                         ``vad_filter`` is on (the default) is gated by Silero VAD on the HIP path
+    ctx["gpu_audio"]    true (with gpu_transcription): the manager is built with ``gpu_audio=True``, so PCM audio of any
+                        sample rate, width and channel count is decoded and resampled to 16 kHz on the HIP path
 """
 
 from __future__ import annotations
@@ -161,6 +163,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
         factory = ctx.get("model_manager_factory", ModelManager)
         if task_type == "transcription" and ctx.get("gpu_transcription"):  # opt-in: the manager is built with the HIP path on
             extra = {"gpu_vad": True} if ctx.get("gpu_vad") else {}
+            if ctx.get("gpu_audio"):
+                extra["gpu_audio"] = True
             model_manager = factory(cache_dir=model_cache_dir, gpu_transcription=True, **extra)
         else:
             model_manager = factory(cache_dir=model_cache_dir)

@@ -1116,7 +1116,7 @@ def transcribe_result(raw: dict) -> dict:
                          for s in raw["segments"]]}
 
 
-def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None, vad=None) -> dict:
+def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None, vad=None, audio_frontend=None) -> dict:
     """``ModelManager.transcribe_video`` body.  Config keys consumed: ``languages`` (string or list: the first entry; None =
     detect), ``vad_filter`` (applied when a ``vad`` object is given, see below), ``window_mode``, ``batch_windows``, ``beam_size`` (1..8, default 1 =
     greedy; 5 is the reference's call) and ``patience`` (positive, default 1.0); ``model_name`` picks the checkpoint in the
@@ -1131,7 +1131,12 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None,
     With it and ``config.get("vad_filter", True)`` (the reference's default), the transcriber sees the concatenation of the
     speech chunks of :func:`eioku_amd.vad.speech_timestamps` (``vad_parameters``: a dict of its six options) and the times
     are mapped back to the file; no speech returns no segments without a transcriber call.  Without ``vad`` the filter is
-    logged and not applied."""
+    logged and not applied.
+
+    ``audio_frontend``: an object with ``load(path) -> (16 kHz samples, 16000)`` and ``resample_float(samples, rate)``
+    (:class:`eioku_amd.audio.AudioFrontEnd`).  With it and no ``audio_source`` the audio comes from ``load``: PCM WAV of any
+    rate, width and channel count; with both, a source whose rate is not 16000 goes through ``resample_float``.  Everything
+    after it sees 16 kHz samples.  Without it any other rate raises, as before."""
     config = config or {}
     languages = config.get("languages")
     if isinstance(languages, (list, tuple)):
@@ -1158,7 +1163,12 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None,
         given = {k: (list(fb[k]) if k == "temperature" else fb[k]) for k in given}
     if "word_timestamps" in config:
         given["word_timestamps"] = check_word_timestamps(config["word_timestamps"])
-    samples, rate = (audio_source or default_audio_source)(path)
+    if audio_frontend is not None and audio_source is None:
+        samples, rate = audio_frontend.load(path)
+    else:
+        samples, rate = (audio_source or default_audio_source)(path)
+        if audio_frontend is not None and int(rate) != SAMPLE_RATE:
+            samples, rate = audio_frontend.resample_float(samples, rate), SAMPLE_RATE
     check_rate(rate)
     samples = np.asarray(samples, dtype=np.float32)
     chunks = None

@@ -727,6 +727,31 @@ int eioku_vad_probs(eioku_vad_t* v, const float* samples, long long n_samples, f
                     long long* n_probs);
 int eioku_vad_last_ms(const eioku_vad_t* v, double* encode_ms, double* lstm_ms);
 
+/* ---- transcription: audio front end (K23), csrc/audio.hip ---------------------------------------------------------------
+ * Interleaved PCM of any rate -> 16 kHz mono fp32: decode, downmix (fp32 sum in channel order, one IEEE division by the
+ * channel count) and the polyphase form of scipy.signal.resample_poly(x, up, down), up / down = 16000 / rate in lowest
+ * terms.  With half = 10 max(up, down) and L = 2 half + 1 taps h, the bank is B[p][q] = h[p + q up] (zero from L on),
+ * taps_per_phase = ceil(L / up) values per phase, row-major [up][taps_per_phase]; output n is
+ * sum_q B[t mod up][q] x[t div up - q] at t = n down + half, in fp32 from 0 in ascending q with a separate multiply and add.
+ * n_out = ceil(n_frames up / down).  up == down == 1 (taps_per_phase 0, bank NULL) decodes and downmixes only.
+ *   create: copies the bank.  L above 14336, or a bank that leaves no room for a tile's input in 64 KiB of LDS, is
+ *     EIOKU_EINVAL.  slab_out (1..2^26) bounds device memory: longer results run slab by slab, and do not depend on it.
+ *   resample: host PCM in, host samples out; *n_out is written even when n_out_cap is too small (EIOKU_EINVAL).
+ *   plan: slab `slab` of a file of n_frames, host only, as resample walks it: out_start, n_out, first_frame, frames,
+ *     lead, trail (zero frames in front of and behind the input), phase (t mod up of the first output); returns 1 past
+ *     the last slab.  Every position is 64-bit here; the kernel sees the slab-relative ones.
+ *   tile: outputs per workgroup tile.  last_ms: kernel time of the last resample call, summed over its slabs. */
+enum { EIOKU_PCM_U8 = 0, EIOKU_PCM_S16 = 1, EIOKU_PCM_S24 = 2, EIOKU_PCM_S32 = 3, EIOKU_PCM_F32 = 4 };
+typedef struct eioku_audio eioku_audio_t;
+int eioku_audio_create(int up, int down, int taps_per_phase, const float* bank, long long slab_out, eioku_audio_t** out);
+void eioku_audio_destroy(eioku_audio_t* a);
+int eioku_audio_resample(eioku_audio_t* a, const void* pcm, int format, int channels, long long n_frames, float* samples_out,
+                         long long n_out_cap, long long* n_out);
+int eioku_audio_plan(int up, int down, int taps_per_phase, long long slab_out, long long n_frames, long long slab,
+                     long long* plan7);
+int eioku_audio_tile(const eioku_audio_t* a, int* tile);
+int eioku_audio_last_ms(const eioku_audio_t* a, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
