@@ -381,6 +381,7 @@ struct eioku_crnn {
   uint8_t* ignore = nullptr;
   size_t c_img = 0, c_a0 = 0, c_a1 = 0, c_seq = 0, c_gx = 0, c_hid32 = 0, c_logits = 0, c_prob = 0, c_idx = 0, c_offlen = 0;
   std::vector<__half> himg;
+  std::vector<int> hofflen;
   double flops_last = 0;
 };
 
@@ -412,6 +413,29 @@ int up2x(const __half* in, int N, int h, int w, int C, Slice out, hipStream_t st
   return EIOKU_OK;
 }
 
+int im2col_dil(const __half* in, int N, int H, int W, int C, int d, __half* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_im2col_dil, dim3(grid1((long long)N * H * W * 9 * (C / 8))), dim3(256), 0, st, in, N, H, W, C, d, out);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+int ctc_probs(const float* logits, int rows, int C, const uint8_t* ignore, int* idx, float* prob, hipStream_t st) {
+  hipLaunchKernelGGL(k_ctc_probs, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, rows, C, ignore, idx, prob);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+// a caller's DEVICE fp16 NHWC slice of the glue entry points: 16-byte vectors, 32-bit element offsets
+int check_slice(const void* p, int cstride, int coff, int C, long long pixels, const char* what) {
+  EIOKU_REQUIRE(p && ((uintptr_t)p & 15) == 0, "%s: NULL or not 16-byte aligned", what);
+  EIOKU_REQUIRE(C > 0 && C % 8 == 0, "%s: %d channels (a multiple of 8)", what, C);
+  EIOKU_REQUIRE(cstride % 8 == 0 && coff % 8 == 0 && coff >= 0 && coff + C <= cstride,
+                "%s: channels %d..%d of a stride of %d (8-aligned, inside the stride)", what, coff, coff + C, cstride);
+  EIOKU_REQUIRE(pixels * cstride <= (1LL << 31) - 1, "%s: %lld pixels x %d channels exceed 32-bit element offsets", what, pixels,
+                cstride);
+  return EIOKU_OK;
+}
+
 // OpenCV resize INTER_LINEAR taps of one axis (src -> dst): fx = (float)((d + 0.5) * src / dst - 0.5), sx = floor(fx),
 // clamped at both ends with fx = 0; weights saturate_cast<short>((1 - fx) * 2048), saturate_cast<short>(fx * 2048)
 void linear_taps(int src, int dst, int* out) {
@@ -426,6 +450,104 @@ void linear_taps(int src, int dst, int* out) {
     out[3 * d + 1] = (int)std::lrint((1.f - fx) * (1 << kTapBits));
     out[3 * d + 2] = (int)std::lrint(fx * (1 << kTapBits));
   }
+}
+
+// the CRAFT canvas of an h x w frame: the frame itself (copy) or INTER_LINEAR to th x tw, inside H x W (multiples of 32)
+struct Canvas {
+  bool copy;
+  int th, tw, H, W;
+};
+
+int canvas_of(int h, int w, int canvas_size, Canvas* c) {
+  EIOKU_REQUIRE(h > 0 && w > 0 && canvas_size >= 32, "bad argument");
+  const int mx = std::max(h, w);
+  c->copy = mx <= canvas_size;
+  const double ratio = c->copy ? 1.0 : (double)canvas_size / mx;
+  c->th = c->copy ? h : (int)(h * ratio);
+  c->tw = c->copy ? w : (int)(w * ratio);
+  EIOKU_REQUIRE(c->th > 0 && c->tw > 0, "frame %d x %d resizes to nothing", h, w);
+  c->H = (c->th + 31) / 32 * 32;
+  c->W = (c->tw + 31) / 32 * 32;
+  return EIOKU_OK;
+}
+
+// the frames on the device (*d_src: HOST frames are staged in the handle) and, for a resize, its taps in r->taps
+int craft_stage(eioku_craft* r, const uint8_t* bgr, int n, int h, int w, const Canvas& c, int mem, hipStream_t st,
+                const uint8_t** d_src) {
+  *d_src = bgr;
+  if (mem == EIOKU_MEM_HOST) {
+    int rc = grow(&r->src, &r->c_src, (size_t)n * h * w * 3);
+    if (rc) return rc;
+    EIOKU_HIP_CHECK(hipMemcpyAsync(r->src, bgr, (size_t)n * h * w * 3, hipMemcpyHostToDevice, st));
+    *d_src = r->src;
+  }
+  if (!c.copy) {
+    std::vector<int>& taps = r->htaps;  // kept in the handle: the copy below is asynchronous
+    taps.assign((size_t)3 * (c.tw + c.th), 0);
+    linear_taps(w, c.tw, taps.data());
+    linear_taps(h, c.th, taps.data() + 3 * c.tw);
+    int rc = grow(&r->taps, &r->c_taps, taps.size());
+    if (rc) return rc;
+    EIOKU_HIP_CHECK(hipMemcpyAsync(r->taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, st));
+  }
+  return EIOKU_OK;
+}
+
+// the recogniser's buffers from the packed sequences on, for m sequences of `rows` steps in all; off / len (HOST, [m])
+// and `ignore` (HOST, [num_class]) go to the device: r->offlen = [off | len | off[order[.]], the row offsets in the order
+// of the conv passes (zeros without `order`)]
+int tail_reserve(eioku_crnn* r, long long rows, int m, const int* off, const int* len, const int* order, const uint8_t* ignore,
+                 hipStream_t st) {
+  // the input projection holds rows x 2048 fp32 values: callers split larger batches (eioku_amd/ocr.py: 65,536 rows)
+  EIOKU_REQUIRE(rows <= (1 << 18), "%lld sequence steps in one call (at most 262,144: split the crops)", rows);
+  const int C = r->num_class;
+  int rc;
+  if ((rc = grow(&r->seq, &r->c_seq, (size_t)rows * kHid))) return rc;
+  if ((rc = grow(&r->gx, &r->c_gx, (size_t)rows * 8 * kHid))) return rc;
+  if ((rc = grow(&r->hid32, &r->c_hid32, (size_t)rows * 2 * kHid))) return rc;
+  if ((rc = grow(&r->logits, &r->c_logits, (size_t)rows * C))) return rc;
+  if ((rc = grow(&r->prob, &r->c_prob, (size_t)rows))) return rc;
+  if ((rc = grow(&r->idx, &r->c_idx, (size_t)rows))) return rc;
+  if ((rc = grow(&r->offlen, &r->c_offlen, (size_t)3 * m))) return rc;
+  if (!r->ignore) EIOKU_HIP_CHECK(hipMalloc((void**)&r->ignore, (size_t)C));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(r->ignore, ignore, (size_t)C, hipMemcpyHostToDevice, st));
+  std::vector<int>& ol = r->hofflen;  // kept in the handle: the copy below is asynchronous
+  ol.assign(3 * (size_t)m, 0);
+  for (int i = 0; i < m; ++i) ol[i] = off[i], ol[m + i] = len[i];
+  if (order)
+    for (int i = 0; i < m; ++i) ol[2 * m + i] = off[order[i]];
+  EIOKU_HIP_CHECK(hipMemcpyAsync(r->offlen, ol.data(), ol.size() * 4, hipMemcpyHostToDevice, st));
+  return EIOKU_OK;
+}
+
+// r->seq [rows][256] -> two BiLSTMs (input projection: one GEMM for both directions; recurrence; Linear(512, 256)),
+// Prediction, k_ctc_probs -> HOST idx_out, prob_out [rows], logits_out [rows][num_class] (optional).  Synchronises.
+int tail_run(eioku_crnn* r, long long rows, int m, int32_t* idx_out, float* prob_out, float* logits_out, hipStream_t st, double* fl) {
+  const int C = r->num_class;
+  int rc;
+  for (int l = 0; l < 2; ++l) {
+    if ((rc = gemm_f32(r->seq, (int)rows, kHid, r->wih[l], 8 * kHid, r->bih[l], r->gx, st, fl))) return rc;
+    hipLaunchKernelGGL(k_lstm, dim3((unsigned)((m + kSeqTile - 1) / kSeqTile), 2), dim3(kHid), 0, st, r->gx, r->whh[l], r->offlen,
+                       r->offlen + m, m, r->hid32);
+    EIOKU_LAUNCH_CHECK();
+    *fl += 2.0 * 2 * 4 * kHid * kHid * rows;
+    if ((rc = gemm_f32(r->hid32, (int)rows, 2 * kHid, r->wlin[l], kHid, r->blin[l], r->seq, st, fl))) return rc;
+  }
+  if ((rc = gemm_f32(r->seq, (int)rows, kHid, r->wpred, C, r->bpred, r->logits, st, fl))) return rc;
+  if ((rc = ctc_probs(r->logits, (int)rows, C, r->ignore, r->idx, r->prob, st))) return rc;
+  EIOKU_HIP_CHECK(hipMemcpyAsync(idx_out, r->idx, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(prob_out, r->prob, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+  if (logits_out) EIOKU_HIP_CHECK(hipMemcpyAsync(logits_out, r->logits, (size_t)rows * C * 4, hipMemcpyDeviceToHost, st));
+  EIOKU_HIP_CHECK(hipStreamSynchronize(st));
+  return EIOKU_OK;
+}
+
+// N staged frames -> out [N][H][W][8] fp16
+int craft_prep(const eioku_craft* r, const uint8_t* d_src, int N, int h, int w, const Canvas& c, __half* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_craft_prep, dim3(grid1((long long)N * c.H * c.W)), dim3(256), 0, st, d_src, N, h, w, c.th, c.tw, c.H, c.W,
+                     r->taps, c.copy ? 1 : 0, out);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
 }
 
 }  // namespace
@@ -510,41 +632,23 @@ int eioku_craft_set_conv(eioku_craft_t* r, int idx, const float* w, const float*
 int eioku_craft_forward(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int w, int canvas_size, float low_text,
                         float link_threshold, float* text_out, float* link_out, uint8_t* bin_out, int mem, void* stream_) {
   EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(r && n >= 0 && h > 0 && w > 0 && canvas_size >= 32, "bad argument");
+  EIOKU_REQUIRE(r && n >= 0, "bad argument");
   EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
   for (size_t i = 0; i < r->layers.size(); ++i) EIOKU_REQUIRE(r->set[i], "convolution %s has no weights", r->layers[i].name.c_str());
+  Canvas cv;
+  int rc = canvas_of(h, w, canvas_size, &cv);
+  if (rc) return rc;
   if (n == 0) return EIOKU_OK;
   EIOKU_REQUIRE(bgr, "NULL frames");
   hipStream_t st = (hipStream_t)stream_;
-  const int mx = std::max(h, w);
-  const bool copy = mx <= canvas_size;
-  const double ratio = copy ? 1.0 : (double)canvas_size / mx;
-  const int th = copy ? h : (int)(h * ratio), tw = copy ? w : (int)(w * ratio);
-  EIOKU_REQUIRE(th > 0 && tw > 0, "frame %d x %d resizes to nothing", h, w);
-  const int H = (th + 31) / 32 * 32, W = (tw + 31) / 32 * 32;
-  // every interpolate in CRAFT is then an exact 2x (H / 16 -> H / 8 -> H / 4 -> H / 2)
-  EIOKU_REQUIRE(H % 32 == 0 && W % 32 == 0, "canvas %d x %d is not a multiple of 32", H, W);
+  // H, W are multiples of 32: every interpolate in CRAFT is then an exact 2x (H / 16 -> H / 8 -> H / 4 -> H / 2)
+  const int H = cv.H, W = cv.W;
   const long long fpx = (long long)H * W;
   // frames per pass: the widest tensor (64 channels at the full canvas) must stay within 32-bit element offsets
   const int chunk = (int)std::max(1LL, std::min(8LL, ((1LL << 31) - 1) / (fpx * 64)));
-  const uint8_t* d_src = bgr;
-  if (mem == EIOKU_MEM_HOST) {
-    int rc = grow(&r->src, &r->c_src, (size_t)n * h * w * 3);
-    if (rc) return rc;
-    EIOKU_HIP_CHECK(hipMemcpyAsync(r->src, bgr, (size_t)n * h * w * 3, hipMemcpyHostToDevice, st));
-    d_src = r->src;
-  }
-  if (!copy) {
-    std::vector<int>& taps = r->htaps;  // kept in the handle: the copy below is asynchronous
-    taps.assign((size_t)3 * (tw + th), 0);
-    linear_taps(w, tw, taps.data());
-    linear_taps(h, th, taps.data() + 3 * tw);
-    int rc = grow(&r->taps, &r->c_taps, taps.size());
-    if (rc) return rc;
-    EIOKU_HIP_CHECK(hipMemcpyAsync(r->taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, st));
-  }
+  const uint8_t* d_src = nullptr;
+  if ((rc = craft_stage(r, bgr, n, h, w, cv, mem, st, &d_src))) return rc;
   const int cN = std::min(chunk, n);
-  int rc = 0;
   if ((rc = grow(&r->in8, &r->c_in8, (size_t)cN * fpx * 8))) return rc;
   if ((rc = grow(&r->p0, &r->c_p0, (size_t)cN * fpx * 64))) return rc;
   if ((rc = grow(&r->p1, &r->c_p1, (size_t)cN * fpx * 64))) return rc;
@@ -558,9 +662,7 @@ int eioku_craft_forward(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int 
   double fl = 0;
   for (int f0 = 0; f0 < n; f0 += chunk) {
     const int N = std::min(chunk, n - f0);
-    hipLaunchKernelGGL(k_craft_prep, dim3(grid1(N * fpx)), dim3(256), 0, st, d_src + (size_t)f0 * h * w * 3, N, h, w, th, tw, H, W,
-                       r->taps, copy ? 1 : 0, r->in8);
-    EIOKU_LAUNCH_CHECK();
+    if ((rc = craft_prep(r, d_src + (size_t)f0 * h * w * 3, N, h, w, cv, r->in8, st))) return rc;
     int Hc = H, Wc = W;
     __half *P0 = r->p0, *P1 = r->p1;
     // slice1: conv1_1, conv1_2, pool, conv2_1, conv2_2 (+ slice2's in-place ReLU: the skip of upconv4)
@@ -588,8 +690,7 @@ int eioku_craft_forward(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int 
     if ((rc = maxpool(Slice{r->cat1, 1536, 1024}, N, Hc, Wc, 512, 3, 3, 1, 1, 1, 1, Slice{P0, 512, 0}, st, nullptr, nullptr)))
       return rc;
     const long long px16 = (long long)N * Hc * Wc;
-    hipLaunchKernelGGL(k_im2col_dil, dim3(grid1(px16 * 9 * 64)), dim3(256), 0, st, P0, N, Hc, Wc, 512, 6, r->col);
-    EIOKU_LAUNCH_CHECK();
+    if ((rc = im2col_dil(P0, N, Hc, Wc, 512, 6, r->col, st))) return rc;
     if ((rc = conv_forward(L[12], Slice{r->col, 4608, 0}, N, Hc, Wc, Slice{P1, 1024, 0}, nullptr, Slice{}, kActNone, st))) return rc;
     fl += 2.0 * 1024 * 512 * 9 * px16;
     if ((rc = conv(L[13], Slice{P1, 1024, 0}, N, Hc, Wc, Slice{r->cat1, 1536, 0}, nullptr, kActNone, st, &fl))) return rc;
@@ -630,6 +731,66 @@ int eioku_craft_last_flops(const eioku_craft_t* r, double* flops) {
   EIOKU_REQUIRE(r && flops, "NULL argument");
   *flops = r->flops_last;
   return EIOKU_OK;
+}
+
+// Stage: the canvas alone.  n BGR u8 frames (host or device per mem) -> out DEVICE fp16 [n][H][W][8], the network's
+// input as eioku_craft_forward makes it (k_craft_prep with the same taps; channels 3..7 zero).  The handle lends its
+// staging buffers and needs no weights.  Synchronous.
+int eioku_craft_canvas(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int w, int canvas_size, void* out, int mem,
+                       void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(r && n >= 0, "bad argument");
+  EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
+  Canvas cv;
+  int rc = canvas_of(h, w, canvas_size, &cv);
+  if (rc) return rc;
+  if (n == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(bgr, "NULL frames");
+  if ((rc = check_slice(out, 8, 0, 8, (long long)n * cv.H * cv.W, "canvas"))) return rc;
+  hipStream_t st = (hipStream_t)stream_;
+  const uint8_t* d_src = nullptr;
+  if ((rc = craft_stage(r, bgr, n, h, w, cv, mem, st, &d_src))) return rc;
+  if ((rc = craft_prep(r, d_src, n, h, w, cv, (__half*)out, st))) return rc;
+  EIOKU_HIP_CHECK(hipStreamSynchronize(st));
+  return EIOKU_OK;
+}
+
+// Stages: the glue kernels alone, over the caller's DEVICE fp16 NHWC tensors; asynchronous on the stream.
+// in: channels in_coff .. + c of [n][h][w][in_cstride] -> out: channels out_coff .. + c of [n][ho][wo][out_cstride],
+// ho = (h + 2 ph - kh) / sh + 1 (wo alike); padding never wins a maximum
+int eioku_ocr_maxpool_f16(const void* in, int in_cstride, int in_coff, int n, int h, int w, int c, int kh, int kw, int sh, int sw,
+                          int ph, int pw, void* out, int out_cstride, int out_coff, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(n > 0 && h > 0 && w > 0, "bad shape %d x %d x %d", n, h, w);
+  EIOKU_REQUIRE(kh > 0 && kw > 0 && sh > 0 && sw > 0 && ph >= 0 && pw >= 0 && 2 * ph <= kh && 2 * pw <= kw,
+                "bad window %d x %d / (%d, %d) / pad (%d, %d)", kh, kw, sh, sw, ph, pw);
+  EIOKU_REQUIRE(h + 2 * ph >= kh && w + 2 * pw >= kw, "window %d x %d exceeds the padded %d x %d input", kh, kw, h, w);
+  const int ho = (h + 2 * ph - kh) / sh + 1, wo = (w + 2 * pw - kw) / sw + 1;
+  int rc;
+  if ((rc = check_slice(in, in_cstride, in_coff, c, (long long)n * h * w, "max pool input"))) return rc;
+  if ((rc = check_slice(out, out_cstride, out_coff, c, (long long)n * ho * wo, "max pool output"))) return rc;
+  return maxpool(Slice{(__half*)in, in_cstride, in_coff}, n, h, w, c, kh, kw, sh, sw, ph, pw, Slice{(__half*)out, out_cstride, out_coff},
+                 (hipStream_t)stream_, nullptr, nullptr);
+}
+
+// dense in [n][h][w][c] -> dense out [n][h][w][9][c]: the taps of a 3x3 / dilation d / pad d convolution, zero outside
+int eioku_ocr_im2col_dil_f16(const void* in, int n, int h, int w, int c, int d, void* out, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(n > 0 && h > 0 && w > 0 && d > 0 && d <= 1 << 16, "bad shape %d x %d x %d, dilation %d", n, h, w, d);
+  int rc;
+  if ((rc = check_slice(in, c, 0, c, (long long)n * h * w, "im2col input"))) return rc;
+  if ((rc = check_slice(out, c, 0, c, (long long)n * h * w * 9, "im2col output"))) return rc;
+  return im2col_dil((const __half*)in, n, h, w, c, d, (__half*)out, (hipStream_t)stream_);
+}
+
+// dense in [n][h][w][c] -> channels out_coff .. + c of out [n][2h][2w][out_cstride]: bilinear, align_corners=False
+int eioku_ocr_up2x_f16(const void* in, int n, int h, int w, int c, void* out, int out_cstride, int out_coff, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(n > 0 && h > 0 && w > 0 && h <= 1 << 15 && w <= 1 << 15, "bad shape %d x %d x %d", n, h, w);
+  int rc;
+  if ((rc = check_slice(in, c, 0, c, (long long)n * h * w, "upsample input"))) return rc;
+  if ((rc = check_slice(out, out_cstride, out_coff, c, (long long)n * 4 * h * w, "upsample output"))) return rc;
+  return up2x((const __half*)in, n, h, w, c, Slice{(__half*)out, out_cstride, out_coff}, (hipStream_t)stream_);
 }
 
 // ---- K16 -----------------------------------------------------------------------------------------------------------
@@ -762,32 +923,17 @@ int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, in
     ipos += (size_t)64 * widths[i];
     wmax = std::max(wmax, widths[i]);
   }
-  // the input projection holds rows x 2048 fp32 values: callers split larger batches (eioku_amd/ocr.py: 65,536 rows)
-  EIOKU_REQUIRE(rows <= (1 << 18), "%lld sequence steps in one call (at most 262,144: split the crops)", rows);
-  const int C = r->num_class;
   // crops grouped by width (ascending), each group one pass of the convolutions; at most kGroup crops per pass
   std::vector<int> order(m);
   for (int i = 0; i < m; ++i) order[i] = i;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return widths[a] < widths[b]; });
   constexpr int kGroup = 64;
   int rc;
+  if ((rc = tail_reserve(r, rows, m, off.data(), len.data(), order.data(), ignore, st))) return rc;
   const size_t gpx = (size_t)kGroup * 64 * wmax;
   if ((rc = grow(&r->img, &r->c_img, gpx * 8))) return rc;
   if ((rc = grow(&r->a0, &r->c_a0, gpx * 32))) return rc;
   if ((rc = grow(&r->a1, &r->c_a1, gpx * 32))) return rc;
-  if ((rc = grow(&r->seq, &r->c_seq, (size_t)rows * kHid))) return rc;
-  if ((rc = grow(&r->gx, &r->c_gx, (size_t)rows * 8 * kHid))) return rc;
-  if ((rc = grow(&r->hid32, &r->c_hid32, (size_t)rows * 2 * kHid))) return rc;
-  if ((rc = grow(&r->logits, &r->c_logits, (size_t)rows * C))) return rc;
-  if ((rc = grow(&r->prob, &r->c_prob, (size_t)rows))) return rc;
-  if ((rc = grow(&r->idx, &r->c_idx, (size_t)rows))) return rc;
-  if ((rc = grow(&r->offlen, &r->c_offlen, (size_t)3 * m))) return rc;
-  if (!r->ignore) EIOKU_HIP_CHECK(hipMalloc((void**)&r->ignore, (size_t)C));
-  EIOKU_HIP_CHECK(hipMemcpyAsync(r->ignore, ignore, (size_t)C, hipMemcpyHostToDevice, st));
-  std::vector<int> ol(3 * (size_t)m);
-  for (int i = 0; i < m; ++i) ol[i] = off[i], ol[m + i] = len[i];
-  for (int i = 0; i < m; ++i) ol[2 * m + i] = off[order[i]];  // row offsets in width order (the conv passes)
-  EIOKU_HIP_CHECK(hipMemcpyAsync(r->offlen, ol.data(), ol.size() * 4, hipMemcpyHostToDevice, st));
   const auto& L = r->w;
   double fl = 0;
   for (int g0 = 0; g0 < m;) {
@@ -822,25 +968,48 @@ int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, in
     EIOKU_LAUNCH_CHECK();
     g0 = g1;
   }
-  // two BiLSTMs: input projection (one GEMM, both directions), recurrence, Linear(512, 256)
-  for (int l = 0; l < 2; ++l) {
-    if ((rc = gemm_f32(r->seq, (int)rows, kHid, r->wih[l], 8 * kHid, r->bih[l], r->gx, st, &fl))) return rc;
-    hipLaunchKernelGGL(k_lstm, dim3((unsigned)((m + kSeqTile - 1) / kSeqTile), 2), dim3(kHid), 0, st, r->gx, r->whh[l], r->offlen,
-                       r->offlen + m, m, r->hid32);
-    EIOKU_LAUNCH_CHECK();
-    fl += 2.0 * 2 * 4 * kHid * kHid * rows;
-    if ((rc = gemm_f32(r->hid32, (int)rows, 2 * kHid, r->wlin[l], kHid, r->blin[l], r->seq, st, &fl))) return rc;
-  }
-  if ((rc = gemm_f32(r->seq, (int)rows, kHid, r->wpred, C, r->bpred, r->logits, st, &fl))) return rc;
-  hipLaunchKernelGGL(k_ctc_probs, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, r->logits, (int)rows, C, r->ignore, r->idx,
-                     r->prob);
-  EIOKU_LAUNCH_CHECK();
-  EIOKU_HIP_CHECK(hipMemcpyAsync(idx_out, r->idx, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
-  EIOKU_HIP_CHECK(hipMemcpyAsync(prob_out, r->prob, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
-  if (logits_out) EIOKU_HIP_CHECK(hipMemcpyAsync(logits_out, r->logits, (size_t)rows * C * 4, hipMemcpyDeviceToHost, st));
-  EIOKU_HIP_CHECK(hipStreamSynchronize(st));
+  if ((rc = tail_run(r, rows, m, idx_out, prob_out, logits_out, st, &fl))) return rc;
   r->flops_last = fl;
   return EIOKU_OK;
+}
+
+// Stage: the recogniser from its packed sequences on (the first GEMM through k_ctc_probs, as eioku_crnn_forward runs
+// them).  seq HOST fp32 [sum len][256]: m sequences of len[i] >= 1 steps, one after another; ignore, idx_out, prob_out,
+// logits_out as eioku_crnn_forward.  Needs the BiLSTM and "Prediction" weights only.  Synchronous.
+int eioku_crnn_tail(eioku_crnn_t* r, const float* seq, const int* len, int m, const uint8_t* ignore, int32_t* idx_out,
+                    float* prob_out, float* logits_out, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(r && m >= 0, "bad argument");
+  EIOKU_REQUIRE(r->set.back(), "Prediction has no weights");
+  EIOKU_REQUIRE(r->lstm_set[0] && r->lstm_set[1], "BiLSTM layers have no weights");
+  if (m == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(seq && len && ignore && idx_out && prob_out, "NULL buffer");
+  hipStream_t st = (hipStream_t)stream_;
+  std::vector<int> off(m);
+  long long rows = 0;
+  for (int i = 0; i < m; ++i) {
+    EIOKU_REQUIRE(len[i] >= 1 && len[i] < 1 << 14, "sequence %d: %d steps (1 .. 16,383)", i, len[i]);
+    off[i] = (int)rows;
+    rows += len[i];
+  }
+  int rc;
+  if ((rc = tail_reserve(r, rows, m, off.data(), len, nullptr, ignore, st))) return rc;
+  EIOKU_HIP_CHECK(hipMemcpyAsync(r->seq, seq, (size_t)rows * kHid * 4, hipMemcpyHostToDevice, st));
+  double fl = 0;
+  if ((rc = tail_run(r, rows, m, idx_out, prob_out, logits_out, st, &fl))) return rc;
+  r->flops_last = fl;
+  return EIOKU_OK;
+}
+
+// Stage: k_ctc_probs alone.  logits DEVICE fp32 [rows][C], ignore DEVICE u8 [C] (not all set), 2 <= C <= 4096 -> idx_out
+// [rows] int32, prob_out [rows] fp32, DEVICE; asynchronous on the stream.
+int eioku_ctc_probs(const float* logits, int rows, int C, const uint8_t* ignore, int32_t* idx_out, float* prob_out, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(rows >= 0 && C >= 2 && C <= 4096, "bad shape %d x %d (2 <= classes <= 4096)", rows, C);
+  if (rows == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(logits && ignore && idx_out && prob_out, "NULL buffer");
+  EIOKU_REQUIRE((long long)rows * C <= (1LL << 31) - 1, "%d x %d logits exceed 32-bit element offsets", rows, C);
+  return ctc_probs(logits, rows, C, ignore, idx_out, prob_out, (hipStream_t)stream_);
 }
 
 int eioku_crnn_last_flops(const eioku_crnn_t* r, double* flops) {

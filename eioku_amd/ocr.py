@@ -651,6 +651,21 @@ class OcrReader:
                                                  torch.cuda.current_stream(dev).cuda_stream), "eioku_craft_forward")
         return text, link, binm
 
+    def canvas(self, frames_bgr, canvas: int = CANVAS):
+        """Stage (``eioku_craft_canvas``): frames as ``score_maps`` takes them -> the network's input alone, CUDA fp16
+        (n, H, W, 8)."""
+        import torch
+
+        n, h, w, _ = (int(s) for s in frames_bgr.shape)
+        _, _, _, H, W = craft_canvas(h, w, canvas)
+        dev = frames_bgr.device if on_device(frames_bgr) else torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((n, H, W, 8), dtype=torch.float16, device=dev)
+        src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr)
+        _lib.check(self._lib.eioku_craft_canvas(self._d, ptr(src), n, h, w, canvas, ptr(out),
+                                                _lib.MEM_DEVICE if on_device(frames_bgr) else _lib.MEM_HOST,
+                                                torch.cuda.current_stream(dev).cuda_stream), "eioku_craft_canvas")
+        return out
+
     # -- K16 --
     def recognize_raw(self, imgs: list, want_logits: bool = False):
         """Normalised crops float32 (64, width_i) -> per crop ``(idx int32 (T_i,), prob float32 (T_i,)[, logits])``.
@@ -737,3 +752,95 @@ class OcrReader:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+# ---- stage entry points (tests hold each stage to a reference of its own) ------------------------------------------
+class SequenceTail:
+    """K16 from the packed sequences on (``eioku_crnn_tail``): the two BiLSTMs, Prediction and the CTC probabilities of a
+    recogniser state dict.  The VGG convolutions get no weights."""
+
+    def __init__(self, crnn_state: dict):
+        import torch
+
+        self._lib = _lib.load()
+        _lib.init(torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        sd = _np_state(crnn_state)
+        self.num_class = int(sd["Prediction.weight"].shape[0])
+        self._r = C.c_void_p()
+        _lib.check(self._lib.eioku_crnn_create(self.num_class, C.byref(self._r)), "eioku_crnn_create")
+        w, b = (np.ascontiguousarray(sd["Prediction." + k], np.float32) for k in ("weight", "bias"))
+        _lib.check(self._lib.eioku_crnn_set_conv(self._r, self._lib.eioku_crnn_num_convs(self._r) - 1, ptr(w), ptr(b)),
+                   "eioku_crnn_set_conv Prediction")
+        for l in range(2):
+            arrs = lstm_params(sd, l)  # held until the call returns
+            _lib.check(self._lib.eioku_crnn_set_lstm(self._r, l, *(ptr(a) for a in arrs)), "eioku_crnn_set_lstm")
+
+    def __call__(self, seqs: list, ignore_idx=()):
+        """Sequences float32 (T_i, 256) -> per sequence ``(idx int32 (T_i,), prob float32 (T_i,), logits (T_i, classes))``."""
+        lens = np.array([len(s) for s in seqs], np.int32)
+        packed = np.ascontiguousarray(np.concatenate([np.asarray(s, np.float32) for s in seqs]))
+        rows = int(lens.sum())
+        ignore = np.zeros(self.num_class, np.uint8)
+        ignore[list(ignore_idx)] = 1
+        idx, prob = np.empty(rows, np.int32), np.empty(rows, np.float32)
+        logits = np.empty((rows, self.num_class), np.float32)
+        _lib.check(self._lib.eioku_crnn_tail(self._r, ptr(packed), ptr(lens), len(seqs), ptr(ignore), ptr(idx), ptr(prob),
+                                             ptr(logits), None), "eioku_crnn_tail")
+        o = np.concatenate([[0], np.cumsum(lens)])
+        return [(idx[a:b], prob[a:b], logits[a:b]) for a, b in zip(o[:-1], o[1:])]
+
+    def close(self):
+        if getattr(self, "_r", None):
+            self._lib.eioku_crnn_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def ctc_probs(logits, ignore):
+    """``eioku_ctc_probs``: CUDA float32 (rows, C) and uint8 (C,) -> CUDA ``(idx int32 (rows,), prob float32 (rows,))``."""
+    import torch
+
+    rows, nc = (int(s) for s in logits.shape)
+    idx = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    prob = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    _lib.check(_lib.load().eioku_ctc_probs(ptr(logits), rows, nc, ptr(ignore), ptr(idx), ptr(prob),
+                                           torch.cuda.current_stream(logits.device).cuda_stream), "eioku_ctc_probs")
+    return idx, prob
+
+
+def maxpool_f16(x, c_in: tuple, kernel, stride, pad, out, c_out: tuple):
+    """``eioku_ocr_maxpool_f16``: channels ``c_in = (offset, count)`` of CUDA fp16 NHWC ``x`` -> channels ``c_out[0]`` on
+    of ``out`` (written in place, returned)."""
+    import torch
+
+    n, h, w, cs = (int(s) for s in x.shape)
+    _lib.check(_lib.load().eioku_ocr_maxpool_f16(ptr(x), cs, c_in[0], n, h, w, c_in[1], *kernel, *stride, *pad, ptr(out),
+                                                 int(out.shape[3]), c_out[0], torch.cuda.current_stream(x.device).cuda_stream),
+               "eioku_ocr_maxpool_f16")
+    return out
+
+
+def im2col_dil_f16(x, d: int):
+    """``eioku_ocr_im2col_dil_f16``: CUDA fp16 (n, h, w, c) -> (n, h, w, 9, c), the taps of a 3x3 / dilation d / pad d conv."""
+    import torch
+
+    n, h, w, c = (int(s) for s in x.shape)
+    out = torch.empty((n, h, w, 9, c), dtype=torch.float16, device=x.device)
+    _lib.check(_lib.load().eioku_ocr_im2col_dil_f16(ptr(x), n, h, w, c, d, ptr(out), torch.cuda.current_stream(x.device).cuda_stream),
+               "eioku_ocr_im2col_dil_f16")
+    return out
+
+
+def up2x_f16(x, out, c_off: int = 0):
+    """``eioku_ocr_up2x_f16``: CUDA fp16 (n, h, w, c) -> channels ``c_off`` on of ``out`` (n, 2h, 2w, stride), in place."""
+    import torch
+
+    n, h, w, c = (int(s) for s in x.shape)
+    _lib.check(_lib.load().eioku_ocr_up2x_f16(ptr(x), n, h, w, c, ptr(out), int(out.shape[3]), c_off,
+                                              torch.cuda.current_stream(x.device).cuda_stream), "eioku_ocr_up2x_f16")
+    return out

@@ -539,6 +539,31 @@ int eioku_crnn_set_lstm(eioku_crnn_t* r, int layer, const float* w_ih, const flo
 int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, int m, const uint8_t* ignore, int32_t* idx_out,
                        float* prob_out, float* logits_out, void* stream);
 int eioku_crnn_last_flops(const eioku_crnn_t* r, double* flops);
+/* Stage entry points: the code eioku_craft_forward / eioku_crnn_forward run, one stage at a time (tests hold each stage to a
+ * reference of its own).
+ * eioku_craft_canvas: frames (host or device per mem) -> out DEVICE fp16 [n][H][W][8], the network's input (the frame, or
+ *   INTER_LINEAR to canvas_size; zero padded to multiples of 32, then normalised; channels 3..7 zero).  The handle lends its
+ *   staging buffers and needs no weights.  Synchronous.
+ * eioku_crnn_tail: the recogniser from its packed sequences on.  seq HOST fp32 [sum len][256], m sequences of len[i] >= 1
+ *   steps one after another -> two BiLSTMs, Prediction, softmax / ignore / argmax; outputs as eioku_crnn_forward.  Needs the
+ *   BiLSTM and "Prediction" weights only.  Synchronous.
+ * eioku_ctc_probs: logits DEVICE fp32 [rows][C], ignore DEVICE u8 [C] (at least one class kept), 2 <= C <= 4096 -> per row
+ *   the argmax over the kept classes (ties: the lower class) and its probability p / sum of kept p, DEVICE.  Asynchronous.
+ * eioku_ocr_maxpool_f16 / _im2col_dil_f16 / _up2x_f16: CRAFT's glue kernels over caller DEVICE fp16 NHWC tensors (c % 8 == 0;
+ *   a slice = channels coff .. coff + c of a tensor of cstride channels, both 8-aligned; 16-byte aligned pointers; every
+ *   tensor below 2^31 elements).  Max pool: [n][h][w] -> [n][(h + 2 ph - kh) / sh + 1][(w + 2 pw - kw) / sw + 1], padding
+ *   never wins (2 ph <= kh, 2 pw <= kw).  im2col: dense [n][h][w][c] -> dense [n][h][w][9][c], tap (ky, kx) =
+ *   in[y + d (ky - 1)][x + d (kx - 1)] or zero.  up2x: dense [n][h][w][c] -> slice of [n][2h][2w], bilinear with
+ *   align_corners=False, fp32 arithmetic rounded once to fp16.  Asynchronous. */
+int eioku_craft_canvas(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int w, int canvas_size, void* out_nhwc8_dev, int mem,
+                       void* stream);
+int eioku_crnn_tail(eioku_crnn_t* r, const float* seq, const int* len, int m, const uint8_t* ignore, int32_t* idx_out,
+                    float* prob_out, float* logits_out, void* stream);
+int eioku_ctc_probs(const float* logits, int rows, int C, const uint8_t* ignore, int32_t* idx_out, float* prob_out, void* stream);
+int eioku_ocr_maxpool_f16(const void* in, int in_cstride, int in_coff, int n, int h, int w, int c, int kh, int kw, int sh, int sw,
+                          int ph, int pw, void* out, int out_cstride, int out_coff, void* stream);
+int eioku_ocr_im2col_dil_f16(const void* in, int n, int h, int w, int c, int d, void* out, void* stream);
+int eioku_ocr_up2x_f16(const void* in, int n, int h, int w, int c, void* out, int out_cstride, int out_coff, void* stream);
 
 /* ---- topics: KeyBERT keyword selection (csrc/topics.hip, K17) -------------------------------------------------------
  * Fills the topic_extraction stage the reference schedules but never built.  rows: x [n_rows][d] fp32; terms [n_terms][d]
