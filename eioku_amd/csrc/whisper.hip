@@ -1157,6 +1157,53 @@ struct Layer { Attn self, cross; int fc1, fc1b, fc2, fc2b, ln_g, ln_b; };
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+#define W_TRY(expr)                \
+  do {                             \
+    const int _rc = (expr);        \
+    if (_rc != EIOKU_OK) return _rc; \
+  } while (0)
+
+// An owning device buffer of `cap` elements: freed by its destructor, never copied.  grow(n) reallocates (and drops the
+// contents) only when n exceeds the capacity.
+template <typename T>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() {
+    if (p) (void)hipFree(p);
+  }
+  operator T*() const { return p; }
+  int grow(size_t n) {
+    if (p && n <= cap) return EIOKU_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr, cap = 0;
+    if (hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
+      p = nullptr;
+      set_error("hipMalloc of %zu bytes failed", n * sizeof(T));
+      return EIOKU_ENOMEM;
+    }
+    cap = n;
+    return EIOKU_OK;
+  }
+};
+
+// The activations of one pass over a number of token rows: the residual stream x in fp32; the LayerNorm output h, the
+// attention queries q, the attention output a and the MLP's hidden layer mid in fp16.
+struct Work {
+  Buf<float> x;
+  Buf<h16> h, q, a, mid;
+  int grow(size_t rows, size_t d, size_t ffn) {
+    W_TRY(x.grow(rows * d));
+    W_TRY(h.grow(rows * d));
+    W_TRY(q.grow(rows * d));
+    W_TRY(a.grow(rows * d));
+    return mid.grow(rows * ffn);
+  }
+};
+
 }  // namespace
 
 struct eioku_whisper {
@@ -1168,46 +1215,47 @@ struct eioku_whisper {
   int emb = 0, dec_pos = 0, dec_ln_g = 0, dec_ln_b = 0;
   int nlang = 0, nblk = 0, k1pad = 0;
   // constants
-  double *hann = nullptr, *tw_cos = nullptr, *tw_sin = nullptr, *filt = nullptr;
-  uint16_t* flags = nullptr;
-  int* lang_ids = nullptr;
+  Buf<double> hann, tw_cos, tw_sin, filt;
+  Buf<uint16_t> flags;
+  Buf<int> lang_ids;
   // audio + mel
-  float* samples = nullptr;
+  Buf<float> samples;
   long long n_samples = 0;
-  long long* d_off = nullptr;
-  double *mel64 = nullptr, *mel_mx = nullptr;
-  float* mel32 = nullptr;
-  // encoder workspace (capacity cap windows)
+  Buf<long long> d_off;
+  Buf<double> mel64, mel_mx;
+  Buf<float> mel32;
+  // encoder workspace (capacity cap windows; cap is the window stride of crossK / crossV)
   int cap = 0, enc_B = 0;
-  h16 *col1 = nullptr, *h1 = nullptr, *col2 = nullptr, *eh = nullptr, *eq = nullptr, *ek = nullptr, *ev = nullptr, *ea = nullptr,
-      *emid = nullptr, *enc_out = nullptr, *crossK = nullptr, *crossV = nullptr;
-  float* ex = nullptr;
-  // decoder workspace
-  h16 *dh = nullptr, *dq = nullptr, *da = nullptr, *dmid = nullptr, *selfK = nullptr, *selfV = nullptr;
-  float *dx = nullptr, *partial = nullptr, *info = nullptr, *nsp = nullptr, *d_logprob = nullptr;
-  LaneState* state = nullptr;
-  int *tokens = nullptr, *cur_tok = nullptr, *lang_out = nullptr, *d_ids = nullptr;
+  Buf<h16> col1, h1, col2, ek, ev, enc_out, crossK, crossV;
+  Work ew;
+  // decoder workspace (capacity dcap lanes >= cap; dcap is the lane stride of selfK / selfV and the offset of the lane map
+  // in kvmap)
+  int dcap = 0;
+  Work dw;
+  Buf<h16> selfK, selfV;
+  Buf<float> partial, info, nsp, d_logprob;
+  Buf<LaneState> state;
+  Buf<int> tokens, cur_tok, lang_out, d_ids;
   // beam search: lanes = windows * beam; ancestry table and token history double-buffered; finished records per window
-  int dcap = 0;  // capacity of the decoder workspace in lanes (>= cap)
   int beam_lanes = 0, beam_windows = 0;  // capacity of the beam buffers (0 until the first beam call)
-  float *bpartial = nullptr, *fin_sum = nullptr, *b_sum = nullptr, *b_fsum = nullptr;
-  uint8_t* anc[2] = {nullptr, nullptr};
-  int *hist[2] = {nullptr, nullptr}, *fin_tok = nullptr, *fin_n = nullptr, *fin_count = nullptr, *complete = nullptr;
-  int *b_src = nullptr, *b_tok = nullptr, *b_fsrc = nullptr, *b_nlive = nullptr, *b_nfin = nullptr, *tr_src = nullptr, *tr_tok = nullptr;
+  Buf<float> bpartial, fin_sum, b_sum, b_fsum;
+  Buf<uint8_t> anc[2];
+  Buf<int> hist[2], fin_tok, fin_n, fin_count, complete;
+  Buf<int> b_src, b_tok, b_fsrc, b_nlive, b_nfin, tr_src, tr_tok;
   // sampling and prompt prefill: per-lane seeds and sample indices, the row -> window maps (rows, then lanes), and the
   // prefill workspace for prows = rows x prompt positions
-  unsigned long long* d_seeds = nullptr;
-  int *d_sidx = nullptr, *kvmap = nullptr;
+  Buf<unsigned long long> d_seeds;
+  Buf<int> d_sidx, kvmap;
   int prows = 0;
-  float *px = nullptr, *ppartial = nullptr;
-  h16 *ph = nullptr, *pq = nullptr, *pk = nullptr, *pv = nullptr, *pa = nullptr, *pmid = nullptr;
+  Work pw;
+  Buf<h16> pk, pv;
+  Buf<float> ppartial;
   // word alignment (K21): the (layer, head) pairs (empty: every head of the upper half of the decoder layers), the
-  // workspace of align() with its capacities in elements, and the device times of the last align() call
+  // workspace of align(), each buffer grown on its own, and the device times of the last align() call
   std::vector<int> align_heads;
-  float *al_A = nullptr, *al_stat = nullptr, *al_cost = nullptr, *al_part = nullptr, *al_tgt = nullptr, *al_prob = nullptr;
-  unsigned* al_trace = nullptr;
-  int *al_jump = nullptr, *al_meta = nullptr, *al_rows = nullptr, *al_path = nullptr;
-  size_t al_cap[11] = {};
+  Buf<float> al_A, al_stat, al_cost, al_part, al_tgt, al_prob;
+  Buf<unsigned> al_trace;
+  Buf<int> al_jump, al_meta, al_rows, al_path;
   double align_ms[3] = {0, 0, 0};
   double flops = 0;
   int launches = 0, steps = 0;
@@ -1218,24 +1266,14 @@ struct eioku_whisper {
 
 namespace {
 
-template <typename T>
-int dalloc(T** p, size_t n) {
-  if (*p) {
-    (void)hipFree(*p);
-    *p = nullptr;
-  }
-  if (hipMalloc((void**)p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
-    set_error("hipMalloc of %zu bytes failed", n * sizeof(T));
-    return EIOKU_ENOMEM;
-  }
+void reset_counts(eioku_whisper* m) { m->flops = 0, m->launches = 0, m->steps = 0; }
+
+// after a kernel launch: its error check, and the launch count of last_launches()
+int launched(eioku_whisper* m) {
+  EIOKU_LAUNCH_CHECK();
+  m->launches += 1;
   return EIOKU_OK;
 }
-
-#define W_TRY(expr)                \
-  do {                             \
-    const int _rc = (expr);        \
-    if (_rc != EIOKU_OK) return _rc; \
-  } while (0)
 
 template <int MT, int EPI>
 int gemm(eioku_whisper* m, const h16* A, int lda, const h16* W, int ldw, const float* bias, int M, int N, int K, void* out,
@@ -1243,17 +1281,13 @@ int gemm(eioku_whisper* m, const h16* A, int lda, const h16* W, int ldw, const f
   EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0 && ldw % 8 == 0, "GEMM K %d / lda %d / ldw %d misaligned", K, lda, ldw);
   const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
   hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, 0, A, lda, W, ldw, bias, M, N, K, out, ldc, pos, pos_rows);
-  EIOKU_LAUNCH_CHECK();
   m->flops += 2.0 * M * N * K;
-  m->launches += 1;
-  return EIOKU_OK;
+  return launched(m);
 }
 
 int ln(eioku_whisper* m, const float* x, int M, int d, int g, int b, h16* out) {
   hipLaunchKernelGGL(k_ln, dim3((M + 3) / 4), dim3(256), 0, 0, x, M, d, m->F(g), m->F(b), out);
-  EIOKU_LAUNCH_CHECK();
-  m->launches += 1;
-  return EIOKU_OK;
+  return launched(m);
 }
 
 template <int QPW>
@@ -1274,38 +1308,96 @@ int attn(eioku_whisper* m, const h16* Q, long long q_bs, int q_rs, const h16* K,
     hipLaunchKernelGGL((k_attn<QPW, false>), grid, dim3(256), lds, 0, Q, q_bs, q_rs, K, V, kv_bs, kv_rs, n_q, n_keys, O, o_bs, o_rs,
                        kv_div, (const uint8_t*)nullptr, 0, kvmap);
   }
-  EIOKU_LAUNCH_CHECK();
   m->flops += 4.0 * B * m->cfg.heads * (double)n_q * n_keys * 64 * (causal ? 0.5 : 1.0);
-  m->launches += 1;
-  return EIOKU_OK;
+  return launched(m);
 }
 
+// ---- the Whisper layer ------------------------------------------------------------------------------------------------------
+// The sublayers that the encoder, the prompt prefill and the decoder step share, on a working set of M rows with GEMM tile
+// MT.  What differs between the three - where self-attention keys and values go and how they are attended - stays with them.
+
+// the head of an attention sublayer: LayerNorm of the residual stream into w.h, the query projection into w.q
+template <int MT>
+int ln_q(eioku_whisper* m, Work& w, int M, const Attn& A) {
+  const int d = m->cfg.d_model;
+  W_TRY(ln(m, w.x, M, d, A.ln_g, A.ln_b, w.h));
+  return gemm<MT, EPI_F16>(m, w.h, d, m->H(A.q), d, m->F(A.qb), M, d, d, w.q, d);
+}
+
+// the key (no bias) and value projections of M rows of src into k and v, ldc elements from row to row
+template <int MT>
+int kv_proj(eioku_whisper* m, const h16* src, int M, const Attn& A, h16* k, h16* v, long long ldc) {
+  const int d = m->cfg.d_model;
+  W_TRY((gemm<MT, EPI_F16>(m, src, d, m->H(A.k), d, nullptr, M, d, d, k, ldc)));
+  return gemm<MT, EPI_F16>(m, src, d, m->H(A.v), d, m->F(A.vb), M, d, d, v, ldc);
+}
+
+// the end of an attention sublayer: the out-projection of w.a added to the residual stream
+template <int MT>
+int out_proj(eioku_whisper* m, Work& w, int M, const Attn& A) {
+  const int d = m->cfg.d_model;
+  return gemm<MT, EPI_RESID>(m, w.a, d, m->H(A.o), d, m->F(A.ob), M, d, d, w.x, d);
+}
+
+// the MLP sublayer: LayerNorm, fc1 with GELU, fc2 added to the residual stream
+template <int MT>
+int mlp(eioku_whisper* m, Work& w, int M, const Layer& L, int ffn) {
+  const int d = m->cfg.d_model;
+  W_TRY(ln(m, w.x, M, d, L.ln_g, L.ln_b, w.h));
+  W_TRY((gemm<MT, EPI_GELU_F16>(m, w.h, d, m->H(L.fc1), d, m->F(L.fc1b), M, ffn, d, w.mid, ffn)));
+  return gemm<MT, EPI_RESID>(m, w.mid, ffn, m->H(L.fc2), ffn, m->F(L.fc2b), M, d, ffn, w.x, d);
+}
+
+// word alignment only: in every layer that has alignment heads, the cross-attention probabilities of those heads go to
+// A [rows][n heads][positions][ldf] right after the cross q projection; the pass itself is unchanged.
+struct AlignCapture {
+  const int* heads;  // n (layer, head) pairs
+  int n, ldf;
+  const int* nF;     // device: frames kept per row
+  float* A;
+};
+
+// the cross-attention sublayer of decoder layer l for R rows x P positions: row r (kv_div rows to a window, or window
+// kvmap[r]) attends the window's crossK / crossV
+template <int MT, int QPW>
+int cross_attn(eioku_whisper* m, Work& w, int R, int P, int l, int kv_div, const int* kvmap, const AlignCapture* cap = nullptr) {
+  const int d = m->cfg.d_model, ctx = m->cfg.max_source_positions;
+  const long long bs = (long long)P * d;
+  const Attn& A = m->dec[l].cross;
+  const h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
+  const h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
+  W_TRY(ln_q<MT>(m, w, R * P, A));
+  for (int hs = 0; cap && hs < cap->n; ++hs) {
+    if (cap->heads[2 * hs] != l) continue;
+    const size_t lds = (size_t)4 * (ctx + 64) * sizeof(float);
+    hipLaunchKernelGGL(k_attn_weights, dim3((P + 3) / 4, R), dim3(256), lds, 0, w.q, bs, d, ck, (long long)ctx * d, d, P, ctx,
+                       cap->heads[2 * hs + 1], kvmap, cap->nF, cap->A + (size_t)hs * P * cap->ldf, (long long)cap->n * P * cap->ldf,
+                       (long long)cap->ldf);
+    m->flops += 2.0 * R * (double)P * ctx * 64;
+    W_TRY(launched(m));
+  }
+  W_TRY((attn<QPW>(m, w.q, bs, d, ck, cv, (long long)ctx * d, d, P, ctx, R, w.a, bs, d, kv_div, nullptr, 0, kvmap)));
+  return out_proj<MT>(m, w, R * P, A);
+}
+
+// ---- workspaces -------------------------------------------------------------------------------------------------------------
 // the decoder workspace for L lanes (greedy: one lane per window; beam search: beam lanes per window).  Growing it keeps
 // the encoder's results.
 int ensure_lanes(eioku_whisper* m, int L) {
   if (L <= m->dcap) return EIOKU_OK;
   const auto& c = m->cfg;
-  const size_t d = c.d_model, Tm = c.max_target_positions, ffn = c.dec_ffn, B = (size_t)L;
+  const size_t d = c.d_model, Tm = c.max_target_positions, B = (size_t)L;
   m->dcap = 0;
-  W_TRY(dalloc(&m->dx, B * d));
-  W_TRY(dalloc(&m->dh, B * d));
-  W_TRY(dalloc(&m->dq, B * d));
-  W_TRY(dalloc(&m->da, B * d));
-  W_TRY(dalloc(&m->dmid, B * ffn));
-  W_TRY(dalloc(&m->selfK, c.dec_layers * B * Tm * d));
-  W_TRY(dalloc(&m->selfV, c.dec_layers * B * Tm * d));
-  W_TRY(dalloc(&m->partial, B * m->nblk * (kNPS > kNP ? kNPS : kNP)));
-  W_TRY(dalloc(&m->d_seeds, B));
-  W_TRY(dalloc(&m->d_sidx, B));
-  W_TRY(dalloc(&m->kvmap, 2 * B));
-  W_TRY(dalloc(&m->info, B * (1 + m->nlang)));
-  W_TRY(dalloc(&m->nsp, B));
-  W_TRY(dalloc(&m->d_logprob, B));
-  W_TRY(dalloc(&m->state, B));
-  W_TRY(dalloc(&m->tokens, B * Tm));
-  W_TRY(dalloc(&m->cur_tok, B));
-  W_TRY(dalloc(&m->lang_out, B));
-  W_TRY(dalloc(&m->d_ids, B * Tm));
+  W_TRY(m->dw.grow(B, d, c.dec_ffn));
+  for (Buf<h16>* b : {&m->selfK, &m->selfV}) W_TRY(b->grow(c.dec_layers * B * Tm * d));
+  W_TRY(m->partial.grow(B * m->nblk * (kNPS > kNP ? kNPS : kNP)));
+  W_TRY(m->info.grow(B * (1 + m->nlang)));
+  W_TRY(m->kvmap.grow(2 * B));
+  W_TRY(m->d_seeds.grow(B));
+  W_TRY(m->state.grow(B));
+  for (Buf<float>* b : {&m->nsp, &m->d_logprob}) W_TRY(b->grow(B));
+  for (Buf<int>* b : {&m->d_sidx, &m->cur_tok, &m->lang_out}) W_TRY(b->grow(B));
+  for (Buf<int>* b : {&m->tokens, &m->d_ids}) W_TRY(b->grow(B * Tm));
   m->dcap = L;
   return EIOKU_OK;
 }
@@ -1318,129 +1410,47 @@ int ensure_beam(eioku_whisper* m, int B, int L) {
   if (L > m->beam_lanes) {
     const size_t n = (size_t)L;
     m->beam_lanes = 0;
-    W_TRY(dalloc(&m->bpartial, n * m->nblk * kNPB));
+    W_TRY(m->bpartial.grow(n * m->nblk * kNPB));
     for (int i = 0; i < 2; ++i) {
-      W_TRY(dalloc(&m->anc[i], n * Tm));
-      W_TRY(dalloc(&m->hist[i], n * Tm));
+      W_TRY(m->anc[i].grow(n * Tm));
+      W_TRY(m->hist[i].grow(n * Tm));
     }
-    W_TRY(dalloc(&m->b_src, n));
-    W_TRY(dalloc(&m->b_tok, n));
-    W_TRY(dalloc(&m->b_sum, n));
-    W_TRY(dalloc(&m->b_fsrc, n));
-    W_TRY(dalloc(&m->b_fsum, n));
-    W_TRY(dalloc(&m->tr_src, n * Tm));
-    W_TRY(dalloc(&m->tr_tok, n * Tm));
+    for (Buf<int>* b : {&m->b_src, &m->b_tok, &m->b_fsrc}) W_TRY(b->grow(n));
+    for (Buf<float>* b : {&m->b_sum, &m->b_fsum}) W_TRY(b->grow(n));
+    for (Buf<int>* b : {&m->tr_src, &m->tr_tok}) W_TRY(b->grow(n * Tm));
     m->beam_lanes = L;
   }
   if (B > m->beam_windows) {
     const size_t n = (size_t)B;
     m->beam_windows = 0;
-    W_TRY(dalloc(&m->fin_tok, n * kMaxFinish * Tm));
-    W_TRY(dalloc(&m->fin_sum, n * kMaxFinish));
-    W_TRY(dalloc(&m->fin_n, n * kMaxFinish));
-    W_TRY(dalloc(&m->fin_count, n));
-    W_TRY(dalloc(&m->complete, n));
-    W_TRY(dalloc(&m->b_nlive, n));
-    W_TRY(dalloc(&m->b_nfin, n));
+    W_TRY(m->fin_tok.grow(n * kMaxFinish * Tm));
+    W_TRY(m->fin_sum.grow(n * kMaxFinish));
+    W_TRY(m->fin_n.grow(n * kMaxFinish));
+    for (Buf<int>* b : {&m->fin_count, &m->complete, &m->b_nlive, &m->b_nfin}) W_TRY(b->grow(n));
     m->beam_windows = B;
   }
   return EIOKU_OK;
 }
 
+// the encoder workspace for B windows, and the decoder workspace for as many lanes.  Growing it drops the encoder's results.
 int ensure_capacity(eioku_whisper* m, int B) {
   if (B <= m->cap) return ensure_lanes(m, B);
   const auto& c = m->cfg;
   const size_t T2 = 2 * (size_t)c.max_source_positions, ctx = c.max_source_positions, d = c.d_model;
-  const size_t ffn = c.enc_ffn > c.dec_ffn ? c.enc_ffn : c.dec_ffn;
   m->cap = 0;
-  W_TRY(dalloc(&m->d_off, (size_t)B));
-  W_TRY(dalloc(&m->mel64, B * c.n_mels * T2));
-  W_TRY(dalloc(&m->mel_mx, (size_t)B));
-  W_TRY(dalloc(&m->mel32, B * c.n_mels * T2));
-  W_TRY(dalloc(&m->col1, B * T2 * m->k1pad));
-  W_TRY(dalloc(&m->h1, B * T2 * d));
-  W_TRY(dalloc(&m->col2, B * ctx * 3 * d));
-  W_TRY(dalloc(&m->ex, B * ctx * d));
-  W_TRY(dalloc(&m->eh, B * ctx * d));
-  W_TRY(dalloc(&m->eq, B * ctx * d));
-  W_TRY(dalloc(&m->ek, B * ctx * d));
-  W_TRY(dalloc(&m->ev, B * ctx * d));
-  W_TRY(dalloc(&m->ea, B * ctx * d));
-  W_TRY(dalloc(&m->emid, B * ctx * ffn));
-  W_TRY(dalloc(&m->enc_out, B * ctx * d));
-  W_TRY(dalloc(&m->crossK, c.dec_layers * B * ctx * d));
-  W_TRY(dalloc(&m->crossV, c.dec_layers * B * ctx * d));
+  W_TRY(m->d_off.grow((size_t)B));
+  W_TRY(m->mel64.grow(B * c.n_mels * T2));
+  W_TRY(m->mel_mx.grow((size_t)B));
+  W_TRY(m->mel32.grow(B * c.n_mels * T2));
+  W_TRY(m->col1.grow(B * T2 * m->k1pad));
+  W_TRY(m->h1.grow(B * T2 * d));
+  W_TRY(m->col2.grow(B * ctx * 3 * d));
+  W_TRY(m->ew.grow(B * ctx, d, c.enc_ffn > c.dec_ffn ? c.enc_ffn : c.dec_ffn));
+  for (Buf<h16>* b : {&m->ek, &m->ev, &m->enc_out}) W_TRY(b->grow(B * ctx * d));
+  for (Buf<h16>* b : {&m->crossK, &m->crossV}) W_TRY(b->grow(c.dec_layers * B * ctx * d));
   m->cap = B;
   m->enc_B = 0;
   return ensure_lanes(m, B);
-}
-
-int check_weights(const eioku_whisper* m) {
-  for (const auto& t : m->tensors) EIOKU_REQUIRE(t.set, "tensor %s has no weights", t.name.c_str());
-  return EIOKU_OK;
-}
-
-// one decoder position s for B lanes: embedding -> layers -> final LayerNorm into m->dh.  Beam search: kv_div lanes share a
-// window's cross-attention K / V, and self-attention reads key t of a lane from the lane anc[lane][t].
-int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, int uniform, int kv_div = 1,
-                 const uint8_t* anc = nullptr, const int* kvmap = nullptr) {
-  const auto& c = m->cfg;
-  const int d = c.d_model, ctx = c.max_source_positions, Tm = c.max_target_positions;
-  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, 0, toks, tstride, uniform, c.vocab, d, s, m->H(m->emb), m->F(m->dec_pos), m->dx);
-  EIOKU_LAUNCH_CHECK();
-  m->launches += 1;
-  for (int l = 0; l < c.dec_layers; ++l) {
-    const Layer& L = m->dec[l];
-    h16* sk = m->selfK + (size_t)l * m->dcap * Tm * d;
-    h16* sv = m->selfV + (size_t)l * m->dcap * Tm * d;
-    const h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
-    const h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
-    W_TRY(ln(m, m->dx, B, d, L.self.ln_g, L.self.ln_b, m->dh));
-    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.q), d, m->F(L.self.qb), B, d, d, m->dq, d)));
-    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.k), d, nullptr, B, d, d, sk + (size_t)s * d, (long long)Tm * d)));
-    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.self.v), d, m->F(L.self.vb), B, d, d, sv + (size_t)s * d, (long long)Tm * d)));
-    W_TRY((attn<1>(m, m->dq, d, d, sk, sv, (long long)Tm * d, d, 1, s + 1, B, m->da, d, d, 1, anc, Tm)));
-    W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.self.o), d, m->F(L.self.ob), B, d, d, m->dx, d)));
-    W_TRY(ln(m, m->dx, B, d, L.cross.ln_g, L.cross.ln_b, m->dh));
-    W_TRY((gemm<1, EPI_F16>(m, m->dh, d, m->H(L.cross.q), d, m->F(L.cross.qb), B, d, d, m->dq, d)));
-    W_TRY((attn<1>(m, m->dq, d, d, ck, cv, (long long)ctx * d, d, 1, ctx, B, m->da, d, d, kv_div, nullptr, 0, kvmap)));
-    W_TRY((gemm<1, EPI_RESID>(m, m->da, d, m->H(L.cross.o), d, m->F(L.cross.ob), B, d, d, m->dx, d)));
-    W_TRY(ln(m, m->dx, B, d, L.ln_g, L.ln_b, m->dh));
-    W_TRY((gemm<1, EPI_GELU_F16>(m, m->dh, d, m->H(L.fc1), d, m->F(L.fc1b), B, c.dec_ffn, d, m->dmid, c.dec_ffn)));
-    W_TRY((gemm<1, EPI_RESID>(m, m->dmid, c.dec_ffn, m->H(L.fc2), c.dec_ffn, m->F(L.fc2b), B, d, c.dec_ffn, m->dx, d)));
-  }
-  return ln(m, m->dx, B, d, m->dec_ln_g, m->dec_ln_b, m->dh);
-}
-
-int logits(eioku_whisper* m, int B, int rules, float* raw_out, long long raw_ld, bool info) {
-  hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, B, m->sel,
-                     m->flags, m->state, rules, m->partial, m->nblk, raw_out, raw_ld, nullptr, info ? m->info : nullptr, m->nlang, 0,
-                     1.f, nullptr, nullptr, 0);
-  EIOKU_LAUNCH_CHECK();
-  m->flops += 2.0 * B * m->cfg.vocab * m->cfg.d_model;
-  m->launches += 1;
-  return EIOKU_OK;
-}
-
-// beam search: masked logits of L lanes into the beam partials (the block's nc best text and timestamp ids included)
-int logits_beam(eioku_whisper* m, int L, int nc) {
-  hipLaunchKernelGGL((k_logits<false, true>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, L, m->sel,
-                     m->flags, m->state, 1, m->bpartial, m->nblk, nullptr, 0LL, nullptr, nullptr, m->nlang, nc, 1.f, nullptr, nullptr, 0);
-  EIOKU_LAUNCH_CHECK();
-  m->flops += 2.0 * L * m->cfg.vocab * m->cfg.d_model;
-  m->launches += 1;
-  return EIOKU_OK;
-}
-
-// sampling: masked logits of L lanes into sample partials, scores perturbed with each lane's noise at sample index idx
-int logits_sample(eioku_whisper* m, int L, float temp, int idx) {
-  hipLaunchKernelGGL((k_logits<false, false, true>), dim3(m->nblk), dim3(256), 0, 0, m->dh, m->cfg.d_model, m->H(m->emb), nullptr, L,
-                     m->sel, m->flags, m->state, 1, m->partial, m->nblk, nullptr, 0LL, nullptr, nullptr, m->nlang, 0, temp, m->d_seeds,
-                     nullptr, idx);
-  EIOKU_LAUNCH_CHECK();
-  m->flops += 2.0 * L * m->cfg.vocab * m->cfg.d_model;
-  m->launches += 1;
-  return EIOKU_OK;
 }
 
 // the prefill workspace for `rows` = rows x prompt positions
@@ -1448,80 +1458,128 @@ int ensure_prefill(eioku_whisper* m, int rows) {
   if (rows <= m->prows) return EIOKU_OK;
   const size_t n = (size_t)rows, d = m->cfg.d_model;
   m->prows = 0;
-  W_TRY(dalloc(&m->px, n * d));
-  W_TRY(dalloc(&m->ph, n * d));
-  W_TRY(dalloc(&m->pq, n * d));
-  W_TRY(dalloc(&m->pk, n * d));
-  W_TRY(dalloc(&m->pv, n * d));
-  W_TRY(dalloc(&m->pa, n * d));
-  W_TRY(dalloc(&m->pmid, n * m->cfg.dec_ffn));
-  W_TRY(dalloc(&m->ppartial, n * m->nblk * kNP));
+  W_TRY(m->pw.grow(n, d, m->cfg.dec_ffn));
+  for (Buf<h16>* b : {&m->pk, &m->pv}) W_TRY(b->grow(n * d));
+  W_TRY(m->ppartial.grow(n * m->nblk * kNP));
   m->prows = rows;
   return EIOKU_OK;
 }
 
-// One pass of the decoder over the P prompt positions of R rows (ids [R][P] on the device): the M-tiled GEMMs of the encoder,
-// causal self-attention, cross-attention against window kvmap[r].  Leaves the final-LayerNorm hidden state of every position
-// in m->ph [R][P][d] and the self-attention keys / values of positions 0 .. P - 1 in the cache of lanes r * lstride .. + G - 1.
-// cap (word alignment only): in every layer that has alignment heads, the cross-attention probabilities of those heads go
-// to cap->A [R][n heads][P][ldf] right after the cross q projection; the pass itself is unchanged.
-struct AlignCapture {
-  const int* heads;  // n (layer, head) pairs
-  int n, ldf;
-  const int* nF;     // device: frames kept per row
-  float* A;
-};
+int check_weights(const eioku_whisper* m) {
+  for (const auto& t : m->tensors) EIOKU_REQUIRE(t.set, "tensor %s has no weights", t.name.c_str());
+  return EIOKU_OK;
+}
 
-int prefill(eioku_whisper* m, int R, int P, const int* ids, const int* kvmap, int G, int lstride, const AlignCapture* cap = nullptr) {
+// ---- decoder passes ---------------------------------------------------------------------------------------------------------
+// one decoder position s for B lanes: embedding -> layers -> final LayerNorm into m->dw.h.  Self-attention keys and values go
+// straight into the cache at position s.  Beam search: kv_div lanes share a window's cross-attention K / V, and
+// self-attention reads key t of a lane from the lane anc[lane][t].
+int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, int uniform, int kv_div = 1,
+                 const uint8_t* anc = nullptr, const int* kvmap = nullptr) {
   const auto& c = m->cfg;
-  const int d = c.d_model, ctx = c.max_source_positions, Tm = c.max_target_positions, M = R * P;
-  const long long bs = (long long)P * d;
-  W_TRY(ensure_prefill(m, M));
-  hipLaunchKernelGGL(k_embed_seq, dim3(M), dim3(256), 0, 0, ids, P, c.vocab, d, m->H(m->emb), m->F(m->dec_pos), m->px);
-  EIOKU_LAUNCH_CHECK();
-  m->launches += 1;
+  const int d = c.d_model, Tm = c.max_target_positions;
+  Work& w = m->dw;
+  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, 0, toks, tstride, uniform, c.vocab, d, s, m->H(m->emb), m->F(m->dec_pos), w.x);
+  W_TRY(launched(m));
   for (int l = 0; l < c.dec_layers; ++l) {
     const Layer& L = m->dec[l];
     h16* sk = m->selfK + (size_t)l * m->dcap * Tm * d;
     h16* sv = m->selfV + (size_t)l * m->dcap * Tm * d;
-    const h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
-    const h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
-    W_TRY(ln(m, m->px, M, d, L.self.ln_g, L.self.ln_b, m->ph));
-    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.self.q), d, m->F(L.self.qb), M, d, d, m->pq, d)));
-    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.self.k), d, nullptr, M, d, d, m->pk, d)));
-    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.self.v), d, m->F(L.self.vb), M, d, d, m->pv, d)));
-    hipLaunchKernelGGL(k_kv_to_cache, dim3(P, R * G), dim3(256), 0, 0, m->pk, m->pv, P, d, G, lstride, Tm, sk, sv);
-    EIOKU_LAUNCH_CHECK();
-    m->launches += 1;
-    W_TRY((attn<2>(m, m->pq, bs, d, m->pk, m->pv, bs, d, P, P, R, m->pa, bs, d, 1, nullptr, 0, nullptr, true)));
-    W_TRY((gemm<4, EPI_RESID>(m, m->pa, d, m->H(L.self.o), d, m->F(L.self.ob), M, d, d, m->px, d)));
-    W_TRY(ln(m, m->px, M, d, L.cross.ln_g, L.cross.ln_b, m->ph));
-    W_TRY((gemm<4, EPI_F16>(m, m->ph, d, m->H(L.cross.q), d, m->F(L.cross.qb), M, d, d, m->pq, d)));
-    for (int hs = 0; cap && hs < cap->n; ++hs) {
-      if (cap->heads[2 * hs] != l) continue;
-      const size_t lds = (size_t)4 * (ctx + 64) * sizeof(float);
-      hipLaunchKernelGGL(k_attn_weights, dim3((P + 3) / 4, R), dim3(256), lds, 0, m->pq, bs, d, ck, (long long)ctx * d, d, P, ctx,
-                         cap->heads[2 * hs + 1], kvmap, cap->nF, cap->A + (size_t)hs * P * cap->ldf, (long long)cap->n * P * cap->ldf,
-                         (long long)cap->ldf);
-      EIOKU_LAUNCH_CHECK();
-      m->flops += 2.0 * R * (double)P * ctx * 64;
-      m->launches += 1;
-    }
-    W_TRY((attn<2>(m, m->pq, bs, d, ck, cv, (long long)ctx * d, d, P, ctx, R, m->pa, bs, d, 1, nullptr, 0, kvmap)));
-    W_TRY((gemm<4, EPI_RESID>(m, m->pa, d, m->H(L.cross.o), d, m->F(L.cross.ob), M, d, d, m->px, d)));
-    W_TRY(ln(m, m->px, M, d, L.ln_g, L.ln_b, m->ph));
-    W_TRY((gemm<4, EPI_GELU_F16>(m, m->ph, d, m->H(L.fc1), d, m->F(L.fc1b), M, c.dec_ffn, d, m->pmid, c.dec_ffn)));
-    W_TRY((gemm<4, EPI_RESID>(m, m->pmid, c.dec_ffn, m->H(L.fc2), c.dec_ffn, m->F(L.fc2b), M, d, c.dec_ffn, m->px, d)));
+    W_TRY(ln_q<1>(m, w, B, L.self));
+    W_TRY(kv_proj<1>(m, w.h, B, L.self, sk + (size_t)s * d, sv + (size_t)s * d, (long long)Tm * d));
+    W_TRY((attn<1>(m, w.q, d, d, sk, sv, (long long)Tm * d, d, 1, s + 1, B, w.a, d, d, 1, anc, Tm)));
+    W_TRY(out_proj<1>(m, w, B, L.self));
+    W_TRY((cross_attn<1, 1>(m, w, B, 1, l, kv_div, kvmap)));
+    W_TRY(mlp<1>(m, w, B, L, c.dec_ffn));
   }
-  return ln(m, m->px, M, d, m->dec_ln_g, m->dec_ln_b, m->ph);
+  return ln(m, w.x, B, d, m->dec_ln_g, m->dec_ln_b, w.h);
 }
 
-// m->dh[l] = the prefill's hidden state of row l / G at position t, for L lanes
+// One pass of the decoder over the P prompt positions of R rows (ids [R][P] on the device): the M-tiled GEMMs of the encoder,
+// causal self-attention, cross-attention against window kvmap[r].  Leaves the final-LayerNorm hidden state of every position
+// in m->pw.h [R][P][d] and the self-attention keys / values of positions 0 .. P - 1 in the cache of lanes r * lstride .. + G - 1.
+int prefill(eioku_whisper* m, int R, int P, const int* ids, const int* kvmap, int G, int lstride, const AlignCapture* cap = nullptr) {
+  const auto& c = m->cfg;
+  const int d = c.d_model, Tm = c.max_target_positions, M = R * P;
+  const long long bs = (long long)P * d;
+  W_TRY(ensure_prefill(m, M));
+  Work& w = m->pw;
+  hipLaunchKernelGGL(k_embed_seq, dim3(M), dim3(256), 0, 0, ids, P, c.vocab, d, m->H(m->emb), m->F(m->dec_pos), w.x);
+  W_TRY(launched(m));
+  for (int l = 0; l < c.dec_layers; ++l) {
+    const Layer& L = m->dec[l];
+    h16* sk = m->selfK + (size_t)l * m->dcap * Tm * d;
+    h16* sv = m->selfV + (size_t)l * m->dcap * Tm * d;
+    W_TRY(ln_q<4>(m, w, M, L.self));
+    W_TRY(kv_proj<4>(m, w.h, M, L.self, m->pk, m->pv, d));
+    hipLaunchKernelGGL(k_kv_to_cache, dim3(P, R * G), dim3(256), 0, 0, m->pk, m->pv, P, d, G, lstride, Tm, sk, sv);
+    W_TRY(launched(m));
+    W_TRY((attn<2>(m, w.q, bs, d, m->pk, m->pv, bs, d, P, P, R, w.a, bs, d, 1, nullptr, 0, nullptr, true)));
+    W_TRY(out_proj<4>(m, w, M, L.self));
+    W_TRY((cross_attn<4, 2>(m, w, R, P, l, 1, kvmap, cap)));
+    W_TRY(mlp<4>(m, w, M, L, c.dec_ffn));
+  }
+  return ln(m, w.x, M, d, m->dec_ln_g, m->dec_ln_b, w.h);
+}
+
+// m->dw.h[l] = the prefill's hidden state of row l / G at position t, for L lanes
 int gather_hidden(eioku_whisper* m, int L, int P, int t, int G) {
-  hipLaunchKernelGGL(k_gather_rows, dim3(L), dim3(256), 0, 0, m->ph, P, t, G, m->cfg.d_model, m->dh);
-  EIOKU_LAUNCH_CHECK();
-  m->launches += 1;
-  return EIOKU_OK;
+  hipLaunchKernelGGL(k_gather_rows, dim3(L), dim3(256), 0, 0, m->pw.h, P, t, G, m->cfg.d_model, m->dw.h);
+  return launched(m);
+}
+
+// ---- logits and selects -----------------------------------------------------------------------------------------------------
+enum { SEL_GREEDY = 0, SEL_BEAM = 1, SEL_SAMPLE = 2 };
+
+// what one launch of k_logits takes beyond the lanes; the defaults are the rules on the lanes' hidden state m->dw.h
+struct LogitsArgs {
+  const float* supplied = nullptr;  // the debug entries: logits [B][vocab] instead of the hidden state
+  int rules = 1;
+  float *raw_out = nullptr, *masked = nullptr;  // the rule-free logits (raw_ld from lane to lane) and the masked ones
+  long long raw_ld = 0;
+  bool info = false;                // the no-speech and language logits into m->info
+  int nc = 0;                       // beam: candidates per block
+  float temp = 1.f;                 // sample: the temperature, with m->d_seeds and a sample index per lane (sidx) or for all (idx)
+  const int* sidx = nullptr;
+  int idx = 0;
+};
+
+// masked logits of B lanes into the partials of KIND: greedy and sample share m->partial, beam has m->bpartial
+template <int KIND>
+int logits(eioku_whisper* m, int B, const LogitsArgs& a = {}) {
+  constexpr bool BEAM = KIND == SEL_BEAM, SAMPLE = KIND == SEL_SAMPLE;
+  float* partial = BEAM ? m->bpartial.p : m->partial.p;
+  const unsigned long long* seeds = SAMPLE ? m->d_seeds.p : nullptr;
+  float* info = a.info ? m->info.p : nullptr;
+  if (a.supplied) {
+    hipLaunchKernelGGL((k_logits<true, BEAM, SAMPLE>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr,
+                       a.supplied, B, m->sel, m->flags, m->state, a.rules, partial, m->nblk, a.raw_out, a.raw_ld, a.masked, info,
+                       m->nlang, a.nc, a.temp, seeds, a.sidx, a.idx);
+    EIOKU_LAUNCH_CHECK();
+    return EIOKU_OK;
+  }
+  hipLaunchKernelGGL((k_logits<false, BEAM, SAMPLE>), dim3(m->nblk), dim3(256), 0, 0, m->dw.h, m->cfg.d_model, m->H(m->emb), nullptr, B,
+                     m->sel, m->flags, m->state, a.rules, partial, m->nblk, a.raw_out, a.raw_ld, a.masked, info, m->nlang, a.nc,
+                     a.temp, seeds, a.sidx, a.idx);
+  m->flops += 2.0 * B * m->cfg.vocab * m->cfg.d_model;
+  return launched(m);
+}
+
+// the greedy select of L lanes on m->partial.  sample: the token at index idx into tokens [L][Tm] and cur_tok (each may be
+// NULL); info: the no-speech probability and the language into m->nsp / m->lang_out.
+int greedy_select(eioku_whisper* m, int L, bool sample, int idx, bool info, int* tokens, int* cur_tok) {
+  hipLaunchKernelGGL(k_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, sample ? 1 : 0, idx, info ? 1 : 0, m->info,
+                     m->nlang, m->lang_ids, tokens, tokens ? m->cfg.max_target_positions : 0, cur_tok, m->nsp, m->lang_out,
+                     (float*)nullptr);
+  return launched(m);
+}
+
+// no-speech probability and language of L lanes from the rule-free logits of the hidden state in m->dw.h
+int info_pair(eioku_whisper* m, int L, int* tokens = nullptr, int* cur_tok = nullptr) {
+  LogitsArgs a;
+  a.rules = 0, a.info = true;
+  W_TRY(logits<SEL_GREEDY>(m, L, a));
+  return greedy_select(m, L, false, 0, true, tokens, cur_tok);
 }
 
 // checks prompts [B][P] and windows [B] (NULL: identity, which needs B == the encoded windows); uploads the prompts to
@@ -1547,14 +1605,108 @@ int prompted_args(eioku_whisper* m, const int32_t* prompts, int P, int sot_index
   return EIOKU_OK;
 }
 
-// the no-speech probability of B rows from the prefill's hidden state at prompt position sot_index, into m->nsp [B]
-int prefill_no_speech(eioku_whisper* m, int B, int P, int sot_index) {
-  W_TRY(gather_hidden(m, B, P, sot_index, 1));
-  W_TRY(logits(m, B, 0, nullptr, 0, true));
-  hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, 0, 1, m->info, m->nlang, m->lang_ids,
-                     (int*)nullptr, 0, (int*)nullptr, m->nsp, m->lang_out, (float*)nullptr);
-  EIOKU_LAUNCH_CHECK();
-  m->launches += 1;
+// ---- the start of a lockstep decode -----------------------------------------------------------------------------------------
+// How B rows x G lanes get to the hidden state of their last prompt position (in m->dw.h), with the no-speech probability in
+// m->nsp on the way.  Walked: `prompt` [P] is shared, every lane walks its first n_walk positions by decoder_step, and the
+// info pair follows position 0 unless the caller merges it into its first select (info = false); nsp and the language are
+// per lane.  Prefilled: `prompt` is [B][P], uploaded by prompted_args; one prefill per row fills the cache of `fill` lanes of
+// the row, the info pair reads position sot_index, every lane starts from its row's last position; nsp is per row.
+struct Start {
+  const int32_t* prompt;
+  int P;
+  bool pre;
+  int sot_index;
+  int n_walk;
+  bool info;
+  int *tokens, *cur_tok;  // walked: what the info pair's select is handed (it stores nothing)
+};
+
+int start(eioku_whisper* m, const Start& st, int B, int G, int fill, int kv_div = 1, const uint8_t* anc = nullptr) {
+  if (st.pre) {
+    W_TRY(prefill(m, B, st.P, m->d_ids, m->kvmap, fill, G));
+    W_TRY(gather_hidden(m, B, st.P, st.sot_index, 1));
+    W_TRY(info_pair(m, B));
+    return gather_hidden(m, B * G, st.P, st.P - 1, G);
+  }
+  for (int s = 0; s < st.n_walk; ++s) {
+    W_TRY(decoder_step(m, B * G, s, nullptr, 1, st.prompt[s], kv_div, anc));
+    m->steps += 1;
+    if (s == 0 && st.info) W_TRY(info_pair(m, B * G, st.tokens, st.cur_tok));
+  }
+  return EIOKU_OK;
+}
+
+const LaneState kFreshLane{0, -1, -1, -1, 0, 0.f};
+
+// The lockstep decode behind eioku_whisper_decode and eioku_whisper_decode_prompted: after the start, one select per new
+// token - the greedy rule at temperature 0, Gumbel-max sampling with a seed per lane above it - and a decoder step between
+// two selects.  Every sync_every tokens the lane states come back, and once every lane is done the rest is EOT.  Lane l's
+// tokens go to tokens_out [l][max_new], its count and log-probability sum to n_out / sum_logprob, its final state to st.
+int lane_decode(eioku_whisper* m, Start start_at, int B, int G, float temperature, const uint64_t* seeds, int max_new, int sync_every,
+                int32_t* tokens_out, int32_t* n_out, float* sum_logprob, std::vector<LaneState>& st) {
+  if (sync_every < 1) sync_every = 1;
+  const int L = B * G, P = start_at.P, Tm = m->cfg.max_target_positions;
+  const int* lane_map = start_at.pre ? m->kvmap + m->dcap : nullptr;
+  reset_counts(m);
+  st.assign(L, kFreshLane);
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
+  if (seeds) EIOKU_HIP_CHECK(hipMemcpy(m->d_seeds, seeds, (size_t)L * sizeof(uint64_t), hipMemcpyHostToDevice));
+  // a walked one-token prompt that samples: step 0's select samples and reads the info in one launch pair
+  const bool merged = !start_at.pre && P == 1 && max_new > 0;
+  start_at.n_walk = max_new > 0 ? P : 1;
+  start_at.info = !merged;
+  start_at.tokens = m->tokens, start_at.cur_tok = m->cur_tok;
+  W_TRY(start(m, start_at, B, G, G));
+  for (int idx = 0; idx < max_new; ++idx) {
+    if (idx > 0) {
+      W_TRY(decoder_step(m, L, P - 1 + idx, m->cur_tok, 1, 0, 1, nullptr, lane_map));
+      m->steps += 1;
+    }
+    LogitsArgs a;
+    if (temperature == 0.f) {
+      a.info = merged && idx == 0;
+      W_TRY(logits<SEL_GREEDY>(m, L, a));
+      W_TRY(greedy_select(m, L, true, idx, a.info, m->tokens, m->cur_tok));
+    } else {
+      a.temp = temperature, a.idx = idx;
+      W_TRY(logits<SEL_SAMPLE>(m, L, a));
+      hipLaunchKernelGGL(k_sample_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, idx, m->tokens, Tm, m->cur_tok,
+                         (float*)nullptr);
+      W_TRY(launched(m));
+    }
+    if ((idx + 1) % sync_every == 0 && idx + 1 < max_new) {  // read the lane states back: stop once every lane is done
+      EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
+      bool all = true;
+      for (int l = 0; l < L; ++l) all = all && st[l].done;
+      if (all) {  // the rest of every lane is EOT
+        std::vector<int> row(Tm, m->cfg.eot);
+        for (int l = 0; l < L; ++l)
+          EIOKU_HIP_CHECK(hipMemcpy(m->tokens + (size_t)l * Tm + idx + 1, row.data(), (size_t)(max_new - idx - 1) * sizeof(int),
+                                    hipMemcpyHostToDevice));
+        break;
+      }
+    }
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
+  for (int l = 0; l < L && max_new > 0; ++l) {
+    EIOKU_HIP_CHECK(hipMemcpy(tokens_out + (size_t)l * max_new, m->tokens + (size_t)l * Tm, (size_t)max_new * sizeof(int),
+                              hipMemcpyDeviceToHost));
+    n_out[l] = st[l].n;
+    sum_logprob[l] = st[l].sum;
+  }
+  return EIOKU_OK;
+}
+
+// ---- the debug entries' shared parts ----------------------------------------------------------------------------------------
+// positions s0 .. T - 1 of m->d_ids [B][T] walked by decoder_step, the rule-free logits of each into out [B][T][vocab]
+int walked_logits(eioku_whisper* m, int B, int T, int s0, float* out) {
+  LogitsArgs a;
+  a.rules = 0, a.raw_ld = (long long)T * m->cfg.vocab;
+  for (int s = s0; s < T; ++s) {
+    W_TRY(decoder_step(m, B, s, m->d_ids + s, T, 0));
+    a.raw_out = out + (size_t)s * m->cfg.vocab;
+    W_TRY(logits<SEL_GREEDY>(m, B, a));
+  }
   return EIOKU_OK;
 }
 
@@ -1566,6 +1718,38 @@ LaneState state_of_prefix(const int32_t* prefix, int n, int tb) {
     if (prefix[i] >= tb) s.last_ts = prefix[i];
   }
   return s;
+}
+
+// the state of L lanes after their prefixes [L][prefix_cap] (beam: with the lane's sum; -inf is a dead slot), uploaded
+int upload_prefix_states(eioku_whisper* m, int L, const int32_t* prefix, int prefix_cap, const int32_t* prefix_len,
+                         const float* sums = nullptr) {
+  std::vector<LaneState> st(L);
+  for (int l = 0; l < L; ++l) {
+    const int n = prefix_len[l];
+    EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
+    st[l] = state_of_prefix(n ? prefix + (size_t)l * prefix_cap : nullptr, n, m->cfg.timestamp_begin);
+    if (sums) st[l].sum = sums[l], st[l].done = sums[l] > kNegInf ? 0 : 1;
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
+  return EIOKU_OK;
+}
+
+struct Download {
+  void* host;  // NULL: not wanted
+  const void* dev;
+  size_t bytes;
+};
+
+// supplied logits [L][vocab] up, `launch` on the device copy, the small results down
+template <typename F>
+int on_supplied_logits(eioku_whisper* m, const float* logits_in, int L, F launch, std::initializer_list<Download> results) {
+  Buf<float> d_in;
+  W_TRY(d_in.grow((size_t)L * m->cfg.vocab));
+  EIOKU_HIP_CHECK(hipMemcpy(d_in, logits_in, (size_t)L * m->cfg.vocab * sizeof(float), hipMemcpyHostToDevice));
+  W_TRY(launch(d_in.p));
+  for (const Download& r : results)
+    if (r.host) EIOKU_HIP_CHECK(hipMemcpy(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost));
+  return EIOKU_OK;
 }
 
 }  // namespace
@@ -1676,8 +1860,8 @@ int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper** out) {
     }
     flags[c.lang_ids[i]] |= (uint16_t)((i + 1) << 2);
   }
-  if (dalloc(&m->hann, kNfft) || dalloc(&m->tw_cos, kNfft) || dalloc(&m->tw_sin, kNfft) ||
-      dalloc(&m->filt, (size_t)c.n_mels * kBins) || dalloc(&m->flags, (size_t)c.vocab) || dalloc(&m->lang_ids, (size_t)c.n_langs))
+  if (m->hann.grow(kNfft) || m->tw_cos.grow(kNfft) || m->tw_sin.grow(kNfft) || m->filt.grow((size_t)c.n_mels * kBins) ||
+      m->flags.grow((size_t)c.vocab) || m->lang_ids.grow((size_t)c.n_langs))
     return fail(EIOKU_ENOMEM);
   if (hipMemcpy(m->hann, hann.data(), kNfft * 8, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(m->tw_cos, tc.data(), kNfft * 8, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1697,17 +1881,7 @@ void eioku_whisper_destroy(eioku_whisper* m) {
   (void)hipDeviceSynchronize();
   for (auto& t : m->tensors)
     if (t.dev) (void)hipFree(t.dev);
-  void* bufs[] = {m->hann, m->tw_cos, m->tw_sin, m->filt, m->flags, m->lang_ids, m->samples, m->d_off, m->mel64, m->mel_mx, m->mel32,
-                  m->col1, m->h1, m->col2, m->eh, m->eq, m->ek, m->ev, m->ea, m->emid, m->enc_out, m->crossK, m->crossV, m->ex,
-                  m->dh, m->dq, m->da, m->dmid, m->selfK, m->selfV, m->dx, m->partial, m->info, m->nsp, m->d_logprob, m->state,
-                  m->tokens, m->cur_tok, m->lang_out, m->d_ids, m->bpartial, m->fin_sum, m->b_sum, m->b_fsum, m->anc[0], m->anc[1],
-                  m->hist[0], m->hist[1], m->fin_tok, m->fin_n, m->fin_count, m->complete, m->b_src, m->b_tok, m->b_fsrc,
-                  m->b_nlive, m->b_nfin, m->tr_src, m->tr_tok, m->d_seeds, m->d_sidx, m->kvmap, m->px, m->ppartial, m->ph, m->pq,
-                  m->pk, m->pv, m->pa, m->pmid, m->al_A, m->al_stat, m->al_cost, m->al_part, m->al_tgt, m->al_prob, m->al_trace,
-                  m->al_jump, m->al_meta, m->al_rows, m->al_path};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  delete m;
+  delete m;  // every workspace buffer frees itself
 }
 
 int eioku_whisper_num_tensors(const eioku_whisper* m) { return m ? (int)m->tensors.size() : 0; }
@@ -1729,21 +1903,17 @@ int eioku_whisper_set_tensor(eioku_whisper* m, int idx, const float* host, size_
   if (t.kind == T_F32) {
     EIOKU_HIP_CHECK(hipMemcpy(t.dev, host, numel * sizeof(float), hipMemcpyHostToDevice));
   } else {
-    float* stage = nullptr;
-    W_TRY(dalloc(&stage, numel));
-    hipError_t e = hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-      if (t.kind == T_F16) {
-        hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage, numel, (h16*)t.dev);
-      } else {
-        const size_t n = (size_t)t.rows * t.ldk;
-        hipLaunchKernelGGL(k_cvt_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage, t.rows, t.cin, t.ldk, (h16*)t.dev);
-      }
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipDeviceSynchronize();
+    Buf<float> stage;
+    W_TRY(stage.grow(numel));
+    EIOKU_HIP_CHECK(hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice));
+    if (t.kind == T_F16) {
+      hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage, numel, (h16*)t.dev);
+    } else {
+      const size_t n = (size_t)t.rows * t.ldk;
+      hipLaunchKernelGGL(k_cvt_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage, t.rows, t.cin, t.ldk, (h16*)t.dev);
     }
-    (void)hipFree(stage);
-    EIOKU_HIP_CHECK(e);
+    EIOKU_LAUNCH_CHECK();
+    EIOKU_HIP_CHECK(hipDeviceSynchronize());
   }
   t.set = true;
   return EIOKU_OK;
@@ -1752,7 +1922,7 @@ int eioku_whisper_set_tensor(eioku_whisper* m, int idx, const float* host, size_
 int eioku_whisper_set_audio(eioku_whisper* m, const float* samples, long long n) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && n >= 0 && (samples || n == 0), "bad argument");
-  W_TRY(dalloc(&m->samples, (size_t)n));
+  W_TRY(m->samples.grow((size_t)n));
   m->n_samples = n;
   if (n) EIOKU_HIP_CHECK(hipMemcpy(m->samples, samples, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   return EIOKU_OK;
@@ -1788,6 +1958,7 @@ int eioku_whisper_encode(eioku_whisper* m, const float* mel, int B) {
   W_TRY(ensure_capacity(m, B));
   const auto& c = m->cfg;
   const int d = c.d_model, ctx = c.max_source_positions, T2 = 2 * ctx, M = B * ctx;
+  Work& w = m->ew;
   if (mel) EIOKU_HIP_CHECK(hipMemcpy(m->mel32, mel, (size_t)B * c.n_mels * T2 * sizeof(float), hipMemcpyHostToDevice));
   m->flops = 0;
   m->launches = 0;
@@ -1799,28 +1970,20 @@ int eioku_whisper_encode(eioku_whisper* m, const float* mel, int B) {
     W_TRY((gemm<4, EPI_GELU_F16>(m, m->col1, m->k1pad, m->H(m->conv1), m->k1pad, m->F(m->conv1b), B * T2, d, m->k1pad, m->h1, d)));
     hipLaunchKernelGGL(k_im2col_s2, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, 0, m->h1, B, d, T2, m->col2);
     EIOKU_LAUNCH_CHECK();
-    W_TRY((gemm<4, EPI_GELU_POS>(m, m->col2, 3 * d, m->H(m->conv2), 3 * d, m->F(m->conv2b), M, d, 3 * d, m->ex, d, m->F(m->enc_pos), ctx)));
+    W_TRY((gemm<4, EPI_GELU_POS>(m, m->col2, 3 * d, m->H(m->conv2), 3 * d, m->F(m->conv2b), M, d, 3 * d, w.x, d, m->F(m->enc_pos), ctx)));
   }
   for (int l = 0; l < c.enc_layers; ++l) {
     const Layer& L = m->enc[l];
-    W_TRY(ln(m, m->ex, M, d, L.self.ln_g, L.self.ln_b, m->eh));
-    W_TRY((gemm<4, EPI_F16>(m, m->eh, d, m->H(L.self.q), d, m->F(L.self.qb), M, d, d, m->eq, d)));
-    W_TRY((gemm<4, EPI_F16>(m, m->eh, d, m->H(L.self.k), d, nullptr, M, d, d, m->ek, d)));
-    W_TRY((gemm<4, EPI_F16>(m, m->eh, d, m->H(L.self.v), d, m->F(L.self.vb), M, d, d, m->ev, d)));
-    W_TRY((attn<2>(m, m->eq, (long long)ctx * d, d, m->ek, m->ev, (long long)ctx * d, d, ctx, ctx, B, m->ea, (long long)ctx * d, d)));
-    W_TRY((gemm<4, EPI_RESID>(m, m->ea, d, m->H(L.self.o), d, m->F(L.self.ob), M, d, d, m->ex, d)));
-    W_TRY(ln(m, m->ex, M, d, L.ln_g, L.ln_b, m->eh));
-    W_TRY((gemm<4, EPI_GELU_F16>(m, m->eh, d, m->H(L.fc1), d, m->F(L.fc1b), M, c.enc_ffn, d, m->emid, c.enc_ffn)));
-    W_TRY((gemm<4, EPI_RESID>(m, m->emid, c.enc_ffn, m->H(L.fc2), c.enc_ffn, m->F(L.fc2b), M, d, c.enc_ffn, m->ex, d)));
+    W_TRY(ln_q<4>(m, w, M, L.self));
+    W_TRY(kv_proj<4>(m, w.h, M, L.self, m->ek, m->ev, d));
+    W_TRY((attn<2>(m, w.q, (long long)ctx * d, d, m->ek, m->ev, (long long)ctx * d, d, ctx, ctx, B, w.a, (long long)ctx * d, d)));
+    W_TRY(out_proj<4>(m, w, M, L.self));
+    W_TRY(mlp<4>(m, w, M, L, c.enc_ffn));
   }
-  W_TRY(ln(m, m->ex, M, d, m->enc_ln_g, m->enc_ln_b, m->enc_out));
-  for (int l = 0; l < c.dec_layers; ++l) {  // cross-attention keys and values, once per window
-    const Layer& L = m->dec[l];
-    h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
-    h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
-    W_TRY((gemm<4, EPI_F16>(m, m->enc_out, d, m->H(L.cross.k), d, nullptr, M, d, d, ck, d)));
-    W_TRY((gemm<4, EPI_F16>(m, m->enc_out, d, m->H(L.cross.v), d, m->F(L.cross.vb), M, d, d, cv, d)));
-  }
+  W_TRY(ln(m, w.x, M, d, m->enc_ln_g, m->enc_ln_b, m->enc_out));
+  for (int l = 0; l < c.dec_layers; ++l)  // cross-attention keys and values, once per window
+    W_TRY(kv_proj<4>(m, m->enc_out, M, m->dec[l].cross, m->crossK + (size_t)l * m->cap * ctx * d,
+                     m->crossV + (size_t)l * m->cap * ctx * d, d));
   EIOKU_HIP_CHECK(hipDeviceSynchronize());
   m->enc_B = B;
   return EIOKU_OK;
@@ -1844,50 +2007,37 @@ int eioku_whisper_decode(eioku_whisper* m, const int32_t* prompt, int prompt_len
                 prompt_len, max_new, m->cfg.max_target_positions);
   EIOKU_REQUIRE(max_new == 0 || (tokens_out && n_out && sum_logprob), "NULL output");
   for (int i = 0; i < prompt_len; ++i) EIOKU_REQUIRE(prompt[i] >= 0 && prompt[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompt[i]);
-  if (sync_every < 1) sync_every = 1;
-  const int Tm = m->cfg.max_target_positions;
-  m->flops = 0;
-  m->launches = 0;
-  m->steps = 0;
-  std::vector<LaneState> st(B, LaneState{0, -1, -1, -1, 0, 0.f});
-  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
-  const int last_step = max_new > 0 ? prompt_len - 1 + max_new - 1 : 0;
-  for (int s = 0; s <= last_step; ++s) {
-    const bool forced = s < prompt_len;  // the input token is a prompt token
-    W_TRY(decoder_step(m, B, s, forced ? nullptr : m->cur_tok, 1, forced ? prompt[s] : 0));
-    m->steps += 1;
-    const int idx = s - (prompt_len - 1);  // index of the token this step samples
-    const bool sample = idx >= 0 && max_new > 0, info = s == 0;
-    if (!sample && !info) continue;
-    W_TRY(logits(m, B, sample ? 1 : 0, nullptr, 0, info));
-    hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, sample ? 1 : 0, sample ? idx : 0,
-                       info ? 1 : 0, m->info, m->nlang, m->lang_ids, m->tokens, Tm, m->cur_tok, m->nsp, m->lang_out, (float*)nullptr);
-    EIOKU_LAUNCH_CHECK();
-    m->launches += 1;
-    if (sample && (idx + 1) % sync_every == 0 && s < last_step) {  // read the lane states back: stop once every lane is done
-      EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)B * sizeof(LaneState), hipMemcpyDeviceToHost));
-      bool all = true;
-      for (int b = 0; b < B; ++b) all = all && st[b].done;
-      if (all) {  // the rest of every lane is EOT
-        std::vector<int> row(Tm, m->cfg.eot);
-        for (int b = 0; b < B; ++b)
-          EIOKU_HIP_CHECK(hipMemcpy(m->tokens + (size_t)b * Tm + idx + 1, row.data(), (size_t)(max_new - idx - 1) * sizeof(int),
-                                    hipMemcpyHostToDevice));
-        break;
-      }
-    }
-  }
-  EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)B * sizeof(LaneState), hipMemcpyDeviceToHost));
-  for (int b = 0; b < B; ++b) {
-    if (max_new > 0) {
-      EIOKU_HIP_CHECK(hipMemcpy(tokens_out + (size_t)b * max_new, m->tokens + (size_t)b * Tm, (size_t)max_new * sizeof(int),
-                                hipMemcpyDeviceToHost));
-      n_out[b] = st[b].n;
-      sum_logprob[b] = st[b].sum;
-    }
-  }
+  std::vector<LaneState> st;
+  W_TRY(lane_decode(m, Start{prompt, prompt_len, false, 0}, B, 1, 0.f, nullptr, max_new, sync_every, tokens_out, n_out, sum_logprob, st));
   if (no_speech_prob) EIOKU_HIP_CHECK(hipMemcpy(no_speech_prob, m->nsp, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
   if (lang_out) EIOKU_HIP_CHECK(hipMemcpy(lang_out, m->lang_out, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
+}
+
+int eioku_whisper_decode_prompted(eioku_whisper* m, const int32_t* prompts, int P, int sot_index, const int32_t* windows, int B, int G,
+                                  float temperature, const uint64_t* seeds, int max_new, int sync_every, int32_t* tokens_out,
+                                  int32_t* n_out, float* sum_logprob, int32_t* best_out, float* no_speech_prob) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m, "NULL model");
+  EIOKU_REQUIRE(temperature >= 0.f && std::isfinite(temperature), "temperature %g must be a finite number >= 0", (double)temperature);
+  if (temperature == 0.f) EIOKU_REQUIRE(G == 1 && !seeds, "temperature 0 is the greedy rule: one row per window and no seeds");
+  else EIOKU_REQUIRE(seeds, "sampling at temperature %g needs a seed per lane", (double)temperature);
+  W_TRY(prompted_args(m, prompts, P, sot_index, windows, B, G, max_new));
+  EIOKU_REQUIRE(tokens_out && n_out && sum_logprob && best_out, "NULL output");
+  std::vector<LaneState> st;
+  W_TRY(lane_decode(m, Start{prompts, P, true, sot_index}, B, G, temperature, seeds, max_new, sync_every, tokens_out, n_out, sum_logprob, st));
+  for (int b = 0; b < B; ++b) {  // the row with the largest sum / max(1, tokens before EOT), the earlier row on a tie
+    int best = 0;
+    double best_score = 0;
+    for (int g = 0; g < G; ++g) {
+      const LaneState& ls = st[(size_t)b * G + g];
+      const int n_text = ls.n - (ls.done ? 1 : 0);
+      const double score = (double)ls.sum / (n_text > 1 ? n_text : 1);
+      if (g == 0 || score > best_score) best = g, best_score = score;
+    }
+    best_out[b] = best;
+  }
+  if (no_speech_prob) EIOKU_HIP_CHECK(hipMemcpy(no_speech_prob, m->nsp, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
   return EIOKU_OK;
 }
 
@@ -1898,21 +2048,45 @@ int eioku_whisper_forced_logits(eioku_whisper* m, const int32_t* ids, int T, int
   const int V = m->cfg.vocab;
   for (size_t i = 0; i < (size_t)B * T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < V, "id %d outside the vocabulary", ids[i]);
   EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, ids, (size_t)B * T * sizeof(int), hipMemcpyHostToDevice));
-  float* d_out = nullptr;
-  W_TRY(dalloc(&d_out, (size_t)B * T * V));
-  std::vector<LaneState> st(B, LaneState{0, -1, -1, -1, 0, 0.f});
-  int rc = EIOKU_OK;
-  if (hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice) != hipSuccess) rc = EIOKU_EHIP;
-  for (int s = 0; s < T && rc == EIOKU_OK; ++s) {
-    rc = decoder_step(m, B, s, m->d_ids + s, T, 0);
-    if (rc == EIOKU_OK) rc = logits(m, B, 0, d_out + (size_t)s * V, (long long)T * V, false);
+  Buf<float> d_out;
+  W_TRY(d_out.grow((size_t)B * T * V));
+  const std::vector<LaneState> st(B, kFreshLane);
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
+  W_TRY(walked_logits(m, B, T, 0, d_out));
+  EIOKU_HIP_CHECK(hipMemcpy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
+}
+
+int eioku_whisper_prefill_logits(eioku_whisper* m, const int32_t* ids, int T, int B, int n_prefill, float* out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && ids && out && T >= 1 && T <= m->cfg.max_target_positions, "bad argument");
+  EIOKU_REQUIRE(n_prefill >= 1 && n_prefill <= T, "prefill of %d positions outside 1..%d", n_prefill, T);
+  EIOKU_REQUIRE(B > 0 && B == m->enc_B, "prefill_logits of %d lanes needs an encode of the same %d windows first", B, m->enc_B);
+  const int V = m->cfg.vocab, P = n_prefill;
+  for (size_t i = 0; i < (size_t)B * T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < V, "id %d outside the vocabulary", ids[i]);
+  W_TRY(ensure_lanes(m, B));
+  std::vector<int> head((size_t)B * P);
+  for (int b = 0; b < B; ++b)
+    for (int t = 0; t < P; ++t) head[(size_t)b * P + t] = ids[(size_t)b * T + t];
+  Buf<int> d_head;
+  Buf<float> d_out;
+  W_TRY(d_head.grow(head.size()));
+  W_TRY(d_out.grow((size_t)B * T * V));
+  const std::vector<LaneState> st(B, kFreshLane);
+  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, ids, (size_t)B * T * sizeof(int), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(d_head, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice));
+  reset_counts(m);
+  W_TRY(prefill(m, B, P, d_head, nullptr, 1, 1));
+  for (int b = 0; b < B; ++b) {  // the logits of row b's P positions: out[b][0 .. P - 1]; outside the launch and flop counts
+    hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->pw.h + (size_t)b * P * m->cfg.d_model, m->cfg.d_model,
+                       m->H(m->emb), nullptr, P, m->sel, m->flags, m->state, 0, m->ppartial, m->nblk, d_out + (size_t)b * T * V,
+                       (long long)V, nullptr, nullptr, m->nlang, 0, 1.f, nullptr, nullptr, 0);
+    EIOKU_LAUNCH_CHECK();
   }
-  if (rc == EIOKU_OK && hipMemcpy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("hipMemcpy of the logits failed: %s", hipGetErrorString(hipGetLastError()));
-    rc = EIOKU_EHIP;
-  }
-  (void)hipFree(d_out);
-  return rc;
+  W_TRY(walked_logits(m, B, T, P, d_out));  // the positions after the prefill walk on its keys and values
+  EIOKU_HIP_CHECK(hipMemcpy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
 }
 
 int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const int32_t* prefix, int prefix_cap,
@@ -1920,34 +2094,47 @@ int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const 
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && logits_in && B > 0 && B <= 64 && prefix_len && token_out && logprob_out && prefix_cap >= 0, "bad argument");
   W_TRY(ensure_capacity(m, B));
-  const int V = m->cfg.vocab;
-  std::vector<LaneState> st(B);
-  for (int b = 0; b < B; ++b) {
-    const int n = prefix_len[b];
-    EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
-    st[b] = state_of_prefix(n ? prefix + (size_t)b * prefix_cap : nullptr, n, m->cfg.timestamp_begin);
-  }
-  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
-  float *d_in = nullptr, *d_msk = nullptr;
-  W_TRY(dalloc(&d_in, (size_t)B * V));
-  int rc = masked_out ? dalloc(&d_msk, (size_t)B * V) : EIOKU_OK;
-  hipError_t e = rc == EIOKU_OK ? hipMemcpy(d_in, logits_in, (size_t)B * V * sizeof(float), hipMemcpyHostToDevice) : hipSuccess;
-  if (rc == EIOKU_OK && e == hipSuccess) {
-    hipLaunchKernelGGL((k_logits<true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in, B, m->sel,
-                       m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, d_msk, (float*)nullptr, m->nlang, 0, 1.f,
-                       (const unsigned long long*)nullptr, (const int*)nullptr, 0);
-    hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, 0, 0, m->info, m->nlang,
-                       m->lang_ids, (int*)nullptr, 0, m->cur_tok, m->nsp, m->lang_out, m->d_logprob);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(token_out, m->cur_tok, (size_t)B * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(logprob_out, m->d_logprob, (size_t)B * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && masked_out) e = hipMemcpy(masked_out, d_msk, (size_t)B * V * sizeof(float), hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d_in);
-  if (d_msk) (void)hipFree(d_msk);
-  W_TRY(rc);
-  EIOKU_HIP_CHECK(e);
-  return EIOKU_OK;
+  W_TRY(upload_prefix_states(m, B, prefix, prefix_cap, prefix_len));
+  const size_t V = m->cfg.vocab;
+  Buf<float> d_msk;
+  if (masked_out) W_TRY(d_msk.grow(B * V));
+  auto launch = [&](const float* d_in) -> int {
+    LogitsArgs a;
+    a.supplied = d_in, a.masked = d_msk;
+    W_TRY(logits<SEL_GREEDY>(m, B, a));
+    hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, 0, 0, m->info, m->nlang, m->lang_ids,
+                       (int*)nullptr, 0, m->cur_tok, m->nsp, m->lang_out, m->d_logprob);
+    EIOKU_LAUNCH_CHECK();
+    return EIOKU_OK;
+  };
+  return on_supplied_logits(m, logits_in, B, launch, {{token_out, m->cur_tok, B * sizeof(int)}, {logprob_out, m->d_logprob, B * sizeof(float)},
+                                                      {masked_out, d_msk, B * V * sizeof(float)}});
+}
+
+int eioku_whisper_sample(eioku_whisper* m, const float* logits_in, int B, const int32_t* prefix, int prefix_cap,
+                         const int32_t* prefix_len, float temperature, const uint64_t* seeds, const int32_t* idx, int32_t* token_out,
+                         float* logprob_out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && logits_in && B > 0 && B <= 64 && prefix_len && seeds && idx && token_out && logprob_out && prefix_cap >= 0,
+                "bad argument");
+  EIOKU_REQUIRE(temperature > 0.f && std::isfinite(temperature), "temperature %g must be a finite number > 0", (double)temperature);
+  W_TRY(ensure_capacity(m, B));
+  for (int b = 0; b < B; ++b)
+    EIOKU_REQUIRE(idx[b] >= 0 && idx[b] < m->cfg.max_target_positions, "sample index %d outside 0..%d", idx[b],
+                  m->cfg.max_target_positions - 1);
+  W_TRY(upload_prefix_states(m, B, prefix, prefix_cap, prefix_len));
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_seeds, seeds, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(m->d_sidx, idx, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+  auto launch = [&](const float* d_in) -> int {
+    LogitsArgs a;
+    a.supplied = d_in, a.temp = temperature, a.sidx = m->d_sidx;
+    W_TRY(logits<SEL_SAMPLE>(m, B, a));
+    hipLaunchKernelGGL(k_sample_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, (int*)nullptr, 0, m->cur_tok,
+                       m->d_logprob);
+    EIOKU_LAUNCH_CHECK();
+    return EIOKU_OK;
+  };
+  return on_supplied_logits(m, logits_in, B, launch, {{token_out, m->cur_tok, B * sizeof(int)}, {logprob_out, m->d_logprob, B * sizeof(float)}});
 }
 
 namespace {
@@ -1959,13 +2146,13 @@ int beam_args(const eioku_whisper* m, int B, int W, int C) {
   return EIOKU_OK;
 }
 
-void launch_beam_select(eioku_whisper* m, int B, int W, int C, int s, int idx, const uint8_t* anc, uint8_t* anc_next,
-                        const int* hist, int* hist_next, int* out_src, int* out_tok) {
+int beam_select(eioku_whisper* m, int B, int W, int C, int s, int idx, const uint8_t* anc, uint8_t* anc_next, const int* hist,
+                int* hist_next, int* out_src, int* out_tok) {
   const int Tm = m->cfg.max_target_positions;  // out_src / out_tok NULL: no per-slot outputs
   hipLaunchKernelGGL(k_beam_select, dim3(B), dim3(64 * W), 0, 0, m->bpartial, m->nblk, m->sel, W, C, s, idx, m->state, m->cur_tok, anc,
                      anc_next, Tm, hist, hist_next, Tm, m->fin_tok, m->fin_sum, m->fin_n, m->fin_count, m->complete, out_src, out_tok,
-                     m->b_sum, out_src ? m->b_nlive : nullptr, m->b_fsrc, m->b_fsum, m->b_nfin);
-  m->launches += 1;
+                     m->b_sum, out_src ? m->b_nlive.p : nullptr, m->b_fsrc, m->b_fsum, m->b_nfin);
+  return launched(m);
 }
 
 // The beam search behind both entries.  prefill = false: `prompt` [prompt_len] is shared and every lane walks it position by
@@ -1992,12 +2179,10 @@ int beam_impl(eioku_whisper* m, const int32_t* prompt, int prompt_len, bool pre,
   W_TRY(ensure_beam(m, B, L));
   if (pre) W_TRY(prompted_args(m, prompt, prompt_len, sot_index, windows, B, W, max_new));
   const int* lane_map = pre ? m->kvmap + m->dcap : nullptr;
-  m->flops = 0;
-  m->launches = 0;
-  m->steps = 0;
+  reset_counts(m);
   // slot 0 of every window is live with sum 0, the others are dead; every ancestry row names its own lane
   std::vector<LaneState> st(L, LaneState{0, -1, -1, -1, 1, kNegInf});
-  for (int b = 0; b < B; ++b) st[(size_t)b * W] = LaneState{0, -1, -1, -1, 0, 0.f};
+  for (int b = 0; b < B; ++b) st[(size_t)b * W] = kFreshLane;
   std::vector<uint8_t> ident((size_t)L * Tm);
   for (int l = 0; l < L; ++l)
     for (int t = 0; t < Tm; ++t) ident[(size_t)l * Tm + t] = (uint8_t)((pre && t < prompt_len) ? l / W * W : l);
@@ -2015,34 +2200,22 @@ int beam_impl(eioku_whisper* m, const int32_t* prompt, int prompt_len, bool pre,
     EIOKU_HIP_CHECK(hipMemset(m->tr_tok, 0xFF, (size_t)L * Tm * sizeof(int)));
   }
   int cur = 0;
-  const int last_step = prompt_len - 1 + max_new - 1;
   std::vector<int> flags(B);
-  if (pre) {  // the prompt in one pass per window; every slot starts from the window's hidden state at the last prompt position
-    W_TRY(prefill(m, B, prompt_len, m->d_ids, m->kvmap, 1, W));
-    W_TRY(prefill_no_speech(m, B, prompt_len, sot_index));
-    W_TRY(gather_hidden(m, L, prompt_len, prompt_len - 1, W));
-  }
-  for (int s = pre ? prompt_len - 1 : 0; s <= last_step; ++s) {
-    const bool forced = s < prompt_len;
-    if (!pre || s >= prompt_len) {
-      W_TRY(decoder_step(m, L, s, forced ? nullptr : m->cur_tok, 1, forced ? prompt[s] : 0, W, m->anc[cur], lane_map));
+  // prefilled: the prompt in one pass per window; every slot starts from the window's hidden state at the last prompt position
+  W_TRY(start(m, Start{prompt, prompt_len, pre, sot_index, prompt_len, true, nullptr, nullptr}, B, W, 1, W, m->anc[cur]));
+  LogitsArgs beam;
+  beam.nc = W + 1;
+  for (int idx = 0; idx < max_new; ++idx) {
+    const int s = prompt_len - 1 + idx;
+    if (idx > 0) {
+      W_TRY(decoder_step(m, L, s, m->cur_tok, 1, 0, W, m->anc[cur], lane_map));
       m->steps += 1;
     }
-    const int idx = s - (prompt_len - 1);
-    if (s == 0 && !pre) {  // no-speech probability and language from the unmasked logits of prompt position 0
-      W_TRY(logits(m, L, 0, nullptr, 0, true));
-      hipLaunchKernelGGL(k_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, 0, 1, m->info, m->nlang,
-                         m->lang_ids, (int*)nullptr, 0, (int*)nullptr, m->nsp, m->lang_out, (float*)nullptr);
-      EIOKU_LAUNCH_CHECK();
-      m->launches += 1;
-    }
-    if (idx < 0) continue;
-    W_TRY(logits_beam(m, L, W + 1));
-    launch_beam_select(m, B, W, C, s, idx, m->anc[cur], m->anc[cur ^ 1], m->hist[cur], m->hist[cur ^ 1],
-                       trace ? m->tr_src + (size_t)idx * L : nullptr, trace ? m->tr_tok + (size_t)idx * L : nullptr);
-    EIOKU_LAUNCH_CHECK();
+    W_TRY(logits<SEL_BEAM>(m, L, beam));
+    W_TRY(beam_select(m, B, W, C, s, idx, m->anc[cur], m->anc[cur ^ 1], m->hist[cur], m->hist[cur ^ 1],
+                      trace ? m->tr_src + (size_t)idx * L : nullptr, trace ? m->tr_tok + (size_t)idx * L : nullptr));
     cur ^= 1;
-    if ((idx + 1) % sync_every == 0 && s < last_step) {  // stop once every window is complete
+    if ((idx + 1) % sync_every == 0 && idx + 1 < max_new) {  // stop once every window is complete
       EIOKU_HIP_CHECK(hipMemcpy(flags.data(), m->complete, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
       bool all = true;
       for (int b = 0; b < B; ++b) all = all && flags[b];
@@ -2097,6 +2270,7 @@ int beam_impl(eioku_whisper* m, const int32_t* prompt, int prompt_len, bool pre,
       for (int t = 0; t < max_new; ++t) tokens_out[row * max_new + t] = eot;
       n_out[row] = 0, ended_out[row] = 0, sum_logprob[row] = kNegInf;
     }
+    // the prefilled start leaves one no-speech probability per window, the walked one per lane: slot 0's
     if (no_speech_prob) no_speech_prob[b] = nsp[pre ? (size_t)b : (size_t)b * W];
     if (lang_out) lang_out[b] = lang[pre ? (size_t)b : (size_t)b * W];
   }
@@ -2129,225 +2303,36 @@ int eioku_whisper_beam_select(eioku_whisper* m, const float* logits_in, int B, i
   EIOKU_REQUIRE(m && logits_in && prefix_len && sums && fin_count && prefix_cap >= 0, "bad argument");
   EIOKU_REQUIRE(src_out && tok_out && sum_out && n_live && fsrc_out && fsum_out && n_fin && fin_count_out && complete_out, "NULL output");
   W_TRY(beam_args(m, B, W, C));
-  const int L = B * W, V = m->cfg.vocab;
+  const int L = B * W;
   W_TRY(ensure_beam(m, B, L));
-  std::vector<LaneState> st(L);
-  for (int l = 0; l < L; ++l) {
-    const int n = prefix_len[l];
-    EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
-    st[l] = state_of_prefix(n ? prefix + (size_t)l * prefix_cap : nullptr, n, m->cfg.timestamp_begin);
-    st[l].sum = sums[l];
-    st[l].done = sums[l] > kNegInf ? 0 : 1;
-  }
-  std::vector<int> zeros(B, 0);
   for (int b = 0; b < B; ++b) EIOKU_REQUIRE(fin_count[b] >= 0 && fin_count[b] < C, "finished count %d outside 0..%d", fin_count[b], C - 1);
-  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
+  W_TRY(upload_prefix_states(m, L, prefix, prefix_cap, prefix_len, sums));
+  const std::vector<int> zeros(B, 0);
   EIOKU_HIP_CHECK(hipMemcpy(m->fin_count, fin_count, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->complete, zeros.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-  float* d_in = nullptr;
-  W_TRY(dalloc(&d_in, (size_t)L * V));
-  hipError_t e = hipMemcpy(d_in, logits_in, (size_t)L * V * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((k_logits<true, true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in, L,
-                       m->sel, m->flags, m->state, 1, m->bpartial, m->nblk, (float*)nullptr, 0LL, (float*)nullptr, (float*)nullptr,
-                       m->nlang, W + 1, 1.f, (const unsigned long long*)nullptr, (const int*)nullptr, 0);
-    launch_beam_select(m, B, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, m->b_src, m->b_tok);
-    e = hipGetLastError();
-    const size_t li = (size_t)L * sizeof(int), bi = (size_t)B * sizeof(int);
-    if (e == hipSuccess) e = hipMemcpy(src_out, m->b_src, li, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(tok_out, m->b_tok, li, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(sum_out, m->b_sum, (size_t)L * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(fsrc_out, m->b_fsrc, li, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(fsum_out, m->b_fsum, (size_t)L * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_live, m->b_nlive, bi, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(n_fin, m->b_nfin, bi, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(fin_count_out, m->fin_count, bi, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(complete_out, m->complete, bi, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d_in);
-  EIOKU_HIP_CHECK(e);
-  return EIOKU_OK;
-}
-
-int eioku_whisper_decode_prompted(eioku_whisper* m, const int32_t* prompts, int P, int sot_index, const int32_t* windows, int B, int G,
-                                  float temperature, const uint64_t* seeds, int max_new, int sync_every, int32_t* tokens_out,
-                                  int32_t* n_out, float* sum_logprob, int32_t* best_out, float* no_speech_prob) {
-  EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(m, "NULL model");
-  EIOKU_REQUIRE(temperature >= 0.f && std::isfinite(temperature), "temperature %g must be a finite number >= 0", (double)temperature);
-  if (temperature == 0.f) EIOKU_REQUIRE(G == 1 && !seeds, "temperature 0 is the greedy rule: one row per window and no seeds");
-  else EIOKU_REQUIRE(seeds, "sampling at temperature %g needs a seed per lane", (double)temperature);
-  W_TRY(prompted_args(m, prompts, P, sot_index, windows, B, G, max_new));
-  EIOKU_REQUIRE(tokens_out && n_out && sum_logprob && best_out, "NULL output");
-  if (sync_every < 1) sync_every = 1;
-  const int L = B * G, Tm = m->cfg.max_target_positions;
-  const int* lane_map = m->kvmap + m->dcap;
-  m->flops = 0;
-  m->launches = 0;
-  m->steps = 0;
-  std::vector<LaneState> st(L, LaneState{0, -1, -1, -1, 0, 0.f});
-  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)L * sizeof(LaneState), hipMemcpyHostToDevice));
-  if (seeds) EIOKU_HIP_CHECK(hipMemcpy(m->d_seeds, seeds, (size_t)L * sizeof(uint64_t), hipMemcpyHostToDevice));
-  W_TRY(prefill(m, B, P, m->d_ids, m->kvmap, G, G));
-  W_TRY(prefill_no_speech(m, B, P, sot_index));
-  W_TRY(gather_hidden(m, L, P, P - 1, G));
-  for (int idx = 0; idx < max_new; ++idx) {
-    if (idx > 0) {
-      W_TRY(decoder_step(m, L, P - 1 + idx, m->cur_tok, 1, 0, 1, nullptr, lane_map));
-      m->steps += 1;
-    }
-    if (temperature == 0.f) {
-      W_TRY(logits(m, L, 1, nullptr, 0, false));
-      hipLaunchKernelGGL(k_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, idx, 0, m->info, m->nlang,
-                         m->lang_ids, m->tokens, Tm, m->cur_tok, m->nsp, m->lang_out, (float*)nullptr);
-    } else {
-      W_TRY(logits_sample(m, L, temperature, idx));
-      hipLaunchKernelGGL(k_sample_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, idx, m->tokens, Tm, m->cur_tok,
-                         (float*)nullptr);
-    }
-    EIOKU_LAUNCH_CHECK();
-    m->launches += 1;
-    if ((idx + 1) % sync_every == 0 && idx + 1 < max_new) {  // read the lane states back: stop once every lane is done
-      EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
-      bool all = true;
-      for (int l = 0; l < L; ++l) all = all && st[l].done;
-      if (all) {  // the rest of every lane is EOT
-        std::vector<int> row(Tm, m->cfg.eot);
-        for (int l = 0; l < L; ++l)
-          EIOKU_HIP_CHECK(hipMemcpy(m->tokens + (size_t)l * Tm + idx + 1, row.data(), (size_t)(max_new - idx - 1) * sizeof(int),
-                                    hipMemcpyHostToDevice));
-        break;
-      }
-    }
-  }
-  EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
-  for (int l = 0; l < L; ++l) {
-    EIOKU_HIP_CHECK(hipMemcpy(tokens_out + (size_t)l * max_new, m->tokens + (size_t)l * Tm, (size_t)max_new * sizeof(int),
-                              hipMemcpyDeviceToHost));
-    n_out[l] = st[l].n;
-    sum_logprob[l] = st[l].sum;
-  }
-  for (int b = 0; b < B; ++b) {  // the row with the largest sum / max(1, tokens before EOT), the earlier row on a tie
-    int best = 0;
-    double best_score = 0;
-    for (int g = 0; g < G; ++g) {
-      const LaneState& ls = st[(size_t)b * G + g];
-      const int n_text = ls.n - (ls.done ? 1 : 0);
-      const double score = (double)ls.sum / (n_text > 1 ? n_text : 1);
-      if (g == 0 || score > best_score) best = g, best_score = score;
-    }
-    best_out[b] = best;
-  }
-  if (no_speech_prob) EIOKU_HIP_CHECK(hipMemcpy(no_speech_prob, m->nsp, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
-  return EIOKU_OK;
-}
-
-int eioku_whisper_sample(eioku_whisper* m, const float* logits_in, int B, const int32_t* prefix, int prefix_cap,
-                         const int32_t* prefix_len, float temperature, const uint64_t* seeds, const int32_t* idx, int32_t* token_out,
-                         float* logprob_out) {
-  EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(m && logits_in && B > 0 && B <= 64 && prefix_len && seeds && idx && token_out && logprob_out && prefix_cap >= 0,
-                "bad argument");
-  EIOKU_REQUIRE(temperature > 0.f && std::isfinite(temperature), "temperature %g must be a finite number > 0", (double)temperature);
-  W_TRY(ensure_capacity(m, B));
-  const int V = m->cfg.vocab;
-  std::vector<LaneState> st(B);
-  for (int b = 0; b < B; ++b) {
-    const int n = prefix_len[b];
-    EIOKU_REQUIRE(n >= 0 && n <= prefix_cap && (n == 0 || prefix), "bad prefix length %d", n);
-    EIOKU_REQUIRE(idx[b] >= 0 && idx[b] < m->cfg.max_target_positions, "sample index %d outside 0..%d", idx[b],
-                  m->cfg.max_target_positions - 1);
-    st[b] = state_of_prefix(n ? prefix + (size_t)b * prefix_cap : nullptr, n, m->cfg.timestamp_begin);
-  }
-  EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
-  EIOKU_HIP_CHECK(hipMemcpy(m->d_seeds, seeds, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice));
-  EIOKU_HIP_CHECK(hipMemcpy(m->d_sidx, idx, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
-  float* d_in = nullptr;
-  W_TRY(dalloc(&d_in, (size_t)B * V));
-  hipError_t e = hipMemcpy(d_in, logits_in, (size_t)B * V * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL((k_logits<true, false, true>), dim3(m->nblk), dim3(256), 0, 0, (const h16*)nullptr, 0, (const h16*)nullptr, d_in,
-                       B, m->sel, m->flags, m->state, 1, m->partial, m->nblk, (float*)nullptr, 0LL, (float*)nullptr, (float*)nullptr,
-                       m->nlang, 0, temperature, m->d_seeds, m->d_sidx, 0);
-    hipLaunchKernelGGL(k_sample_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, (int*)nullptr, 0, m->cur_tok,
-                       m->d_logprob);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(token_out, m->cur_tok, (size_t)B * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(logprob_out, m->d_logprob, (size_t)B * sizeof(float), hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d_in);
-  EIOKU_HIP_CHECK(e);
-  return EIOKU_OK;
-}
-
-int eioku_whisper_prefill_logits(eioku_whisper* m, const int32_t* ids, int T, int B, int n_prefill, float* out) {
-  EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(m && ids && out && T >= 1 && T <= m->cfg.max_target_positions, "bad argument");
-  EIOKU_REQUIRE(n_prefill >= 1 && n_prefill <= T, "prefill of %d positions outside 1..%d", n_prefill, T);
-  EIOKU_REQUIRE(B > 0 && B == m->enc_B, "prefill_logits of %d lanes needs an encode of the same %d windows first", B, m->enc_B);
-  const int V = m->cfg.vocab, P = n_prefill;
-  for (size_t i = 0; i < (size_t)B * T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < V, "id %d outside the vocabulary", ids[i]);
-  W_TRY(ensure_lanes(m, B));
-  std::vector<int> head((size_t)B * P);
-  for (int b = 0; b < B; ++b)
-    for (int t = 0; t < P; ++t) head[(size_t)b * P + t] = ids[(size_t)b * T + t];
-  int* d_head = nullptr;
-  float* d_out = nullptr;
-  W_TRY(dalloc(&d_head, head.size()));
-  int rc = dalloc(&d_out, (size_t)B * T * V);
-  std::vector<LaneState> st(B, LaneState{0, -1, -1, -1, 0, 0.f});
-  auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    if (rc == EIOKU_OK && hipMemcpy(dst, src, bytes, kind) != hipSuccess) {
-      set_error("hipMemcpy failed: %s", hipGetErrorString(hipGetLastError()));
-      rc = EIOKU_EHIP;
-    }
+  auto launch = [&](const float* d_in) -> int {
+    LogitsArgs a;
+    a.supplied = d_in, a.nc = W + 1;
+    W_TRY(logits<SEL_BEAM>(m, L, a));
+    return beam_select(m, B, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, m->b_src, m->b_tok);
   };
-  copy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice);
-  copy(m->d_ids, ids, (size_t)B * T * sizeof(int), hipMemcpyHostToDevice);
-  copy(d_head, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice);
-  m->flops = 0;
-  m->launches = 0;
-  m->steps = 0;
-  if (rc == EIOKU_OK) rc = prefill(m, B, P, d_head, nullptr, 1, 1);
-  for (int b = 0; b < B && rc == EIOKU_OK; ++b) {  // the logits of row b's P positions: out[b][0 .. P - 1]
-    hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->ph + (size_t)b * P * m->cfg.d_model, m->cfg.d_model,
-                       m->H(m->emb), nullptr, P, m->sel, m->flags, m->state, 0, m->ppartial, m->nblk, d_out + (size_t)b * T * V,
-                       (long long)V, nullptr, nullptr, m->nlang, 0, 1.f, nullptr, nullptr, 0);
-    if (hipGetLastError() != hipSuccess) {
-      set_error("launch of the prefill logits failed");
-      rc = EIOKU_EHIP;
-    }
-  }
-  for (int s = P; s < T && rc == EIOKU_OK; ++s) {  // the positions after the prefill walk on its keys and values
-    rc = decoder_step(m, B, s, m->d_ids + s, T, 0);
-    if (rc == EIOKU_OK) rc = logits(m, B, 0, d_out + (size_t)s * V, (long long)T * V, false);
-  }
-  copy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(d_head);
-  (void)hipFree(d_out);
-  return rc;
+  const size_t li = (size_t)L * sizeof(int), lf = (size_t)L * sizeof(float), bi = (size_t)B * sizeof(int);
+  return on_supplied_logits(m, logits_in, L, launch,
+                            {{src_out, m->b_src, li}, {tok_out, m->b_tok, li}, {sum_out, m->b_sum, lf}, {fsrc_out, m->b_fsrc, li},
+                             {fsum_out, m->b_fsum, lf}, {n_live, m->b_nlive, bi}, {n_fin, m->b_nfin, bi},
+                             {fin_count_out, m->fin_count, bi}, {complete_out, m->complete, bi}});
 }
 
 // ---- word alignment (K21) ----------------------------------------------------------------------------------------------------
 extern "C++" {
 namespace {
 
-enum { AL_A = 0, AL_STAT, AL_COST, AL_PART, AL_TGT, AL_PROB, AL_TRACE, AL_JUMP, AL_META, AL_ROWS, AL_PATH };
 constexpr int kMaxDtw = 4096;  // token rows / frames the debug DTW entry takes
-
-template <typename T>
-int al_grow(eioku_whisper* m, T** p, int slot, size_t n) {
-  if (*p && n <= m->al_cap[slot]) return EIOKU_OK;
-  m->al_cap[slot] = 0;
-  W_TRY(dalloc(p, n));
-  m->al_cap[slot] = n;
-  return EIOKU_OK;
-}
 
 // mean / std over the token rows, then the cost; meta on the device: n_tok [R], nF [R]
 int align_cost_launch(eioku_whisper* m, const float* A, int R, int H, int T, int ldf, int S, const int* d_ntok, const int* d_nF,
                       int Nmax, float* cost) {
-  W_TRY(al_grow(m, &m->al_stat, AL_STAT, (size_t)R * H * 2 * ldf));
+  W_TRY(m->al_stat.grow((size_t)R * H * 2 * ldf));
   hipLaunchKernelGGL(k_align_stats, dim3((ldf + 255) / 256, H, R), dim3(256), 0, 0, A, H, T, ldf, d_ntok, d_nF, m->al_stat);
   EIOKU_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_align_cost, dim3((ldf + 255) / 256, Nmax, R), dim3(256), 0, 0, A, m->al_stat, H, T, ldf, S, d_ntok, d_nF, Nmax,
@@ -2360,13 +2345,27 @@ int align_cost_launch(eioku_whisper* m, const float* A, int R, int H, int T, int
 int dtw_launch(eioku_whisper* m, const float* cost, int R, int Nmax, int ldf, const int* d_nN, const int* d_nF, int* jump, int* path,
                int* path_len) {
   const int tw = (ldf + 15) / 16;
-  W_TRY(al_grow(m, &m->al_trace, AL_TRACE, (size_t)R * Nmax * tw));
+  W_TRY(m->al_trace.grow((size_t)R * Nmax * tw));
   hipLaunchKernelGGL(k_dtw, dim3(R), dim3(kDtwRows), (size_t)ldf * sizeof(float), 0, cost, Nmax, ldf, d_nN, d_nF, m->al_trace, tw, jump,
                      path, path_len);
-  EIOKU_LAUNCH_CHECK();
-  m->launches += 1;
-  return EIOKU_OK;
+  return launched(m);
 }
+
+// the four events that bracket the three stages of align(): destroyed with the scope
+struct StageEvents {
+  hipEvent_t ev[4] = {};
+  StageEvents() = default;
+  StageEvents(const StageEvents&) = delete;
+  StageEvents& operator=(const StageEvents&) = delete;
+  ~StageEvents() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int create() {
+    for (auto& e : ev) EIOKU_HIP_CHECK(hipEventCreate(&e));
+    return EIOKU_OK;
+  }
+};
 
 }  // namespace
 }  // extern "C++"
@@ -2387,9 +2386,7 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
                         const int32_t* n_frames, int R, int32_t* jump_out, float* prob_out, float* cost_out) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && seq && n_tok && n_frames && jump_out && prob_out && sot_len >= 1, "bad argument");
-  m->flops = 0;
-  m->launches = 0;
-  m->steps = 0;
+  reset_counts(m);
   const auto& c = m->cfg;
   const int ctx = c.max_source_positions, d = c.d_model, S = sot_len;
   EIOKU_REQUIRE(R > 0 && R <= 64, "%d rows: an alignment pass takes 1..64", R);
@@ -2432,14 +2429,14 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
     }
   }
   const size_t nA = (size_t)R * Hs * T * Fmax, nC = (size_t)R * Nmax * Fmax, nJ = (size_t)R * Nmax;
-  W_TRY(al_grow(m, &m->al_A, AL_A, nA));
-  W_TRY(al_grow(m, &m->al_cost, AL_COST, nC));
-  W_TRY(al_grow(m, &m->al_jump, AL_JUMP, nJ));
-  W_TRY(al_grow(m, &m->al_prob, AL_PROB, nJ));
-  W_TRY(al_grow(m, &m->al_meta, AL_META, meta.size()));
-  W_TRY(al_grow(m, &m->al_rows, AL_ROWS, rows.size()));
-  W_TRY(al_grow(m, &m->al_part, AL_PART, Mp * nblk * 2));
-  W_TRY(al_grow(m, &m->al_tgt, AL_TGT, Mp));
+  W_TRY(m->al_A.grow(nA));
+  W_TRY(m->al_cost.grow(nC));
+  W_TRY(m->al_jump.grow(nJ));
+  W_TRY(m->al_prob.grow(nJ));
+  W_TRY(m->al_meta.grow(meta.size()));
+  W_TRY(m->al_rows.grow(rows.size()));
+  W_TRY(m->al_part.grow(Mp * nblk * 2));
+  W_TRY(m->al_tgt.grow(Mp));
   EIOKU_HIP_CHECK(hipMemcpy(m->kvmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, seq, (size_t)R * T * sizeof(int), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -2448,38 +2445,34 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
   EIOKU_HIP_CHECK(hipMemset(m->al_jump, 0xFF, nJ * sizeof(int)));
   EIOKU_HIP_CHECK(hipMemset(m->al_prob, 0, nJ * sizeof(float)));
   const int *d_ntok = m->al_meta, *d_nF = m->al_meta + R, *d_nN = m->al_meta + 2 * R;
-  hipEvent_t ev[4] = {};
-  for (auto& e : ev) EIOKU_HIP_CHECK(hipEventCreate(&e));
-  auto run = [&]() -> int {
-    EIOKU_HIP_CHECK(hipEventRecord(ev[0], 0));
-    const AlignCapture cap{heads.data(), Hs, Fmax, d_nF, m->al_A};
-    W_TRY(prefill(m, R, T, m->d_ids, m->kvmap, 1, 1, &cap));
-    hipLaunchKernelGGL(k_align_logits, dim3(nblk), dim3(256), 0, 0, m->ph, d, m->H(m->emb), m->al_rows, m->al_rows + Mp, (int)Mp, c.eot,
-                       m->al_part, nblk, m->al_tgt);
-    EIOKU_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_align_prob, dim3((unsigned)Mp), dim3(64), 0, 0, m->al_part, nblk, m->al_tgt, m->al_rows + 2 * Mp, m->al_prob);
-    EIOKU_LAUNCH_CHECK();
-    m->flops += 2.0 * (double)Mp * c.eot * d;
-    m->launches += 2;
-    EIOKU_HIP_CHECK(hipEventRecord(ev[1], 0));
-    W_TRY(align_cost_launch(m, m->al_A, R, Hs, T, Fmax, S, d_ntok, d_nF, Nmax, m->al_cost));
-    EIOKU_HIP_CHECK(hipEventRecord(ev[2], 0));
-    W_TRY(dtw_launch(m, m->al_cost, R, Nmax, Fmax, d_nN, d_nF, m->al_jump, nullptr, nullptr));
-    EIOKU_HIP_CHECK(hipEventRecord(ev[3], 0));
-    EIOKU_HIP_CHECK(hipEventSynchronize(ev[3]));
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      m->align_ms[i] = ms;
-    }
-    EIOKU_HIP_CHECK(hipMemcpy(jump_out, m->al_jump, nJ * sizeof(int), hipMemcpyDeviceToHost));
-    EIOKU_HIP_CHECK(hipMemcpy(prob_out, m->al_prob, nJ * sizeof(float), hipMemcpyDeviceToHost));
-    if (cost_out) EIOKU_HIP_CHECK(hipMemcpy(cost_out, m->al_cost, nC * sizeof(float), hipMemcpyDeviceToHost));
-    return EIOKU_OK;
-  };
-  const int rc = run();
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  return rc;
+  StageEvents stage;
+  W_TRY(stage.create());
+  hipEvent_t* ev = stage.ev;
+  EIOKU_HIP_CHECK(hipEventRecord(ev[0], 0));
+  const AlignCapture cap{heads.data(), Hs, Fmax, d_nF, m->al_A};
+  W_TRY(prefill(m, R, T, m->d_ids, m->kvmap, 1, 1, &cap));
+  hipLaunchKernelGGL(k_align_logits, dim3(nblk), dim3(256), 0, 0, m->pw.h, d, m->H(m->emb), m->al_rows, m->al_rows + Mp, (int)Mp, c.eot,
+                     m->al_part, nblk, m->al_tgt);
+  EIOKU_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_align_prob, dim3((unsigned)Mp), dim3(64), 0, 0, m->al_part, nblk, m->al_tgt, m->al_rows + 2 * Mp, m->al_prob);
+  EIOKU_LAUNCH_CHECK();
+  m->flops += 2.0 * (double)Mp * c.eot * d;
+  m->launches += 2;
+  EIOKU_HIP_CHECK(hipEventRecord(ev[1], 0));
+  W_TRY(align_cost_launch(m, m->al_A, R, Hs, T, Fmax, S, d_ntok, d_nF, Nmax, m->al_cost));
+  EIOKU_HIP_CHECK(hipEventRecord(ev[2], 0));
+  W_TRY(dtw_launch(m, m->al_cost, R, Nmax, Fmax, d_nN, d_nF, m->al_jump, nullptr, nullptr));
+  EIOKU_HIP_CHECK(hipEventRecord(ev[3], 0));
+  EIOKU_HIP_CHECK(hipEventSynchronize(ev[3]));
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.f;
+    EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+    m->align_ms[i] = ms;
+  }
+  EIOKU_HIP_CHECK(hipMemcpy(jump_out, m->al_jump, nJ * sizeof(int), hipMemcpyDeviceToHost));
+  EIOKU_HIP_CHECK(hipMemcpy(prob_out, m->al_prob, nJ * sizeof(float), hipMemcpyDeviceToHost));
+  if (cost_out) EIOKU_HIP_CHECK(hipMemcpy(cost_out, m->al_cost, nC * sizeof(float), hipMemcpyDeviceToHost));
+  return EIOKU_OK;
 }
 
 int eioku_whisper_align_cost(eioku_whisper* m, const float* A, int H, int T, int F, int sot_len, float* cost_out) {
@@ -2490,9 +2483,9 @@ int eioku_whisper_align_cost(eioku_whisper* m, const float* A, int H, int T, int
   m->launches = 0;
   const int N = T - sot_len - 1;
   const int meta[2] = {T, F};
-  W_TRY(al_grow(m, &m->al_A, AL_A, (size_t)H * T * F));
-  W_TRY(al_grow(m, &m->al_cost, AL_COST, (size_t)N * F));
-  W_TRY(al_grow(m, &m->al_meta, AL_META, 2));
+  W_TRY(m->al_A.grow((size_t)H * T * F));
+  W_TRY(m->al_cost.grow((size_t)N * F));
+  W_TRY(m->al_meta.grow(2));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_A, A, (size_t)H * T * F * sizeof(float), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta, sizeof(meta), hipMemcpyHostToDevice));
   W_TRY(align_cost_launch(m, m->al_A, 1, H, T, F, sot_len, m->al_meta, m->al_meta + 1, N, m->al_cost));
@@ -2508,10 +2501,10 @@ int eioku_whisper_dtw(eioku_whisper* m, const float* cost, int N, int F, int32_t
   EIOKU_REQUIRE(N >= 1 && N <= kMaxDtw && F >= 1 && F <= kMaxDtw, "dtw of %d token rows x %d frames: both 1..%d", N, F, kMaxDtw);
   m->launches = 0;
   const int meta[2] = {N, F};
-  W_TRY(al_grow(m, &m->al_cost, AL_COST, (size_t)N * F));
-  W_TRY(al_grow(m, &m->al_jump, AL_JUMP, (size_t)N));
-  W_TRY(al_grow(m, &m->al_meta, AL_META, 3));
-  W_TRY(al_grow(m, &m->al_path, AL_PATH, (size_t)2 * (N + F)));
+  W_TRY(m->al_cost.grow((size_t)N * F));
+  W_TRY(m->al_jump.grow((size_t)N));
+  W_TRY(m->al_meta.grow(3));
+  W_TRY(m->al_path.grow((size_t)2 * (N + F)));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_cost, cost, (size_t)N * F * sizeof(float), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta, sizeof(meta), hipMemcpyHostToDevice));
   W_TRY(dtw_launch(m, m->al_cost, 1, N, F, m->al_meta, m->al_meta + 1, m->al_jump, m->al_path, m->al_meta + 2));
@@ -2547,3 +2540,4 @@ int eioku_whisper_last_launches(const eioku_whisper* m, int* launches, int* step
 }
 
 }  // extern "C"
+

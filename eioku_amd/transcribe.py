@@ -22,6 +22,7 @@ import string
 import struct
 import wave
 import zlib
+from itertools import takewhile
 from pathlib import Path
 
 import numpy as np
@@ -606,22 +607,33 @@ class WhisperTranscriber:
         W, patience = check_beam(beam_size, patience)
         p = np.ascontiguousarray(prompt, dtype=np.int32)
         B, n, Cn = int(n_windows), int(max_new_tokens), finish_count(W, patience)
-        H = max(W, Cn)
-        tokens = np.zeros((B, H, max(n, 1)), dtype=np.int32)
-        n_out, ended = np.zeros((B, H), dtype=np.int32), np.zeros((B, H), dtype=np.int32)
-        total = np.zeros((B, H), dtype=np.float32)
-        n_hyp, best, lang = (np.zeros(B, dtype=np.int32) for _ in range(3))
-        nsp = np.zeros(B, dtype=np.float32)
-        tr_src, tr_tok = (np.full((max(n, 1), B, W), -1, dtype=np.int32) for _ in range(2))
+        out, tr, tr_ptrs = self._beam_outputs(B, W, Cn, n, trace)
+        lang = np.zeros(B, dtype=np.int32)
         self._lib_mod.check(self.lib.eioku_whisper_decode_beam(
-            self._h, p.ctypes.data, len(p), B, W, Cn, n, int(sync_every or self.sync_every), tokens.ctypes.data, n_out.ctypes.data,
-            ended.ctypes.data, total.ctypes.data, n_hyp.ctypes.data, best.ctypes.data, nsp.ctypes.data, lang.ctypes.data,
-            tr_src.ctypes.data if trace else None, tr_tok.ctypes.data if trace else None), "eioku_whisper_decode_beam")
-        out = {"tokens": tokens, "n": n_out, "ended": ended, "sum_logprob": total, "n_hyp": n_hyp, "best": best,
-               "no_speech_prob": nsp, "lang": lang}
-        if trace:
-            out["trace_src"], out["trace_tok"] = tr_src, tr_tok
-        return out
+            self._h, p.ctypes.data, len(p), B, W, Cn, n, int(sync_every or self.sync_every), *(a.ctypes.data for a in out.values()),
+            lang.ctypes.data, *tr_ptrs), "eioku_whisper_decode_beam")
+        return {**out, "lang": lang, **tr}
+
+    @staticmethod
+    def _beam_outputs(B: int, W: int, Cn: int, n: int, trace: bool) -> tuple[dict, dict, tuple]:
+        """The output arrays of a beam decode, in the order the library takes them: the hypothesis rows, then (with
+        ``trace``) the trace arrays, and what the library is handed for the trace (NULL without one)."""
+        H = max(W, Cn)
+        out = {"tokens": np.zeros((B, H, max(n, 1)), dtype=np.int32), "n": np.zeros((B, H), dtype=np.int32),
+               "ended": np.zeros((B, H), dtype=np.int32), "sum_logprob": np.zeros((B, H), dtype=np.float32),
+               "n_hyp": np.zeros(B, dtype=np.int32), "best": np.zeros(B, dtype=np.int32),
+               "no_speech_prob": np.zeros(B, dtype=np.float32)}
+        tr = {k: np.full((max(n, 1), B, W), -1, dtype=np.int32) for k in ("trace_src", "trace_tok")} if trace else {}
+        return out, tr, tuple(a.ctypes.data for a in tr.values()) if trace else (None, None)
+
+    @staticmethod
+    def _pad_prefixes(prefixes, rows: int) -> tuple[np.ndarray, int, np.ndarray]:
+        """Per-lane prefixes as the debug entries take them: [rows][cap] zero-padded, cap, and the lengths."""
+        cap = max(1, max(len(p) for p in prefixes))
+        pre = np.zeros((rows, cap), dtype=np.int32)
+        for i, p in enumerate(prefixes):
+            pre[i, :len(p)] = p
+        return pre, cap, np.asarray([len(p) for p in prefixes], dtype=np.int32)
 
     def beam_select(self, logits, prefixes, sums, fin_count, beam_size: int, patience: float = 1.0) -> list[dict]:
         """Debug: one beam step on supplied logits [B * W][vocab].  ``prefixes`` / ``sums`` per lane (window-major; a sum of
@@ -630,13 +642,10 @@ class WhisperTranscriber:
         W, patience = check_beam(beam_size, patience)
         logits = np.ascontiguousarray(logits, dtype=np.float32)
         L = logits.shape[0]
-        B, cap = L // W, max(1, max(len(p) for p in prefixes))
+        B = L // W
         if B * W != L or len(prefixes) != L or len(sums) != L or len(fin_count) != B:
             raise ValueError("logits, prefixes and sums are per lane (windows x beam), fin_count per window")
-        pre = np.zeros((L, cap), dtype=np.int32)
-        for i, q in enumerate(prefixes):
-            pre[i, :len(q)] = q
-        plen = np.asarray([len(q) for q in prefixes], dtype=np.int32)
+        pre, cap, plen = self._pad_prefixes(prefixes, L)
         sums = np.ascontiguousarray(sums, dtype=np.float32)
         fc = np.ascontiguousarray(fin_count, dtype=np.int32)
         src, tok, fsrc = (np.zeros(L, dtype=np.int32) for _ in range(3))
@@ -691,31 +700,17 @@ class WhisperTranscriber:
         win = None if windows is None else np.ascontiguousarray(windows, dtype=np.int32)
         if win is not None and win.shape != (B,):
             raise ValueError("windows names one encoded window per row")
-        H = max(W, Cn)
-        tokens = np.zeros((B, H, max(n, 1)), dtype=np.int32)
-        n_out, ended = np.zeros((B, H), dtype=np.int32), np.zeros((B, H), dtype=np.int32)
-        total = np.zeros((B, H), dtype=np.float32)
-        n_hyp, best = (np.zeros(B, dtype=np.int32) for _ in range(2))
-        nsp = np.zeros(B, dtype=np.float32)
-        tr_src, tr_tok = (np.full((max(n, 1), B, W), -1, dtype=np.int32) for _ in range(2))
+        out, tr, tr_ptrs = self._beam_outputs(B, W, Cn, n, trace)
         self._lib_mod.check(self.lib.eioku_whisper_decode_beam_prompted(
             self._h, p.ctypes.data, P, int(sot_index), win.ctypes.data if win is not None else None, B, W, Cn, n,
-            int(sync_every or self.sync_every), tokens.ctypes.data, n_out.ctypes.data, ended.ctypes.data, total.ctypes.data,
-            n_hyp.ctypes.data, best.ctypes.data, nsp.ctypes.data, tr_src.ctypes.data if trace else None,
-            tr_tok.ctypes.data if trace else None), "eioku_whisper_decode_beam_prompted")
-        out = {"tokens": tokens, "n": n_out, "ended": ended, "sum_logprob": total, "n_hyp": n_hyp, "best": best, "no_speech_prob": nsp}
-        if trace:
-            out["trace_src"], out["trace_tok"] = tr_src, tr_tok
-        return out
+            int(sync_every or self.sync_every), *(a.ctypes.data for a in out.values()), *tr_ptrs), "eioku_whisper_decode_beam_prompted")
+        return {**out, **tr}
 
     def sample(self, logits, prefixes, temperature: float, seeds, idx) -> tuple[np.ndarray, np.ndarray]:
         """Debug: rules + Gumbel-max sampling on supplied logits [B][vocab]; per lane a prefix, a seed and a sample index."""
         logits = np.ascontiguousarray(logits, dtype=np.float32)
-        B, cap = logits.shape[0], max(1, max(len(p) for p in prefixes))
-        pre = np.zeros((B, cap), dtype=np.int32)
-        for b, p in enumerate(prefixes):
-            pre[b, :len(p)] = p
-        plen = np.asarray([len(p) for p in prefixes], dtype=np.int32)
+        B = logits.shape[0]
+        pre, cap, plen = self._pad_prefixes(prefixes, B)
         sd, ix = np.ascontiguousarray(seeds, dtype=np.uint64), np.ascontiguousarray(idx, dtype=np.int32)
         if len(prefixes) != B or sd.shape != (B,) or ix.shape != (B,):
             raise ValueError("prefixes, seeds and idx are per lane")
@@ -745,11 +740,8 @@ class WhisperTranscriber:
     def select(self, logits, prefixes) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Debug: rules + argmax on supplied logits [B][vocab]; ``prefixes``: per lane the tokens sampled so far."""
         logits = np.ascontiguousarray(logits, dtype=np.float32)
-        B, cap = logits.shape[0], max(1, max(len(p) for p in prefixes))
-        pre = np.zeros((B, cap), dtype=np.int32)
-        for b, p in enumerate(prefixes):
-            pre[b, :len(p)] = p
-        plen = np.asarray([len(p) for p in prefixes], dtype=np.int32)
+        B = logits.shape[0]
+        pre, cap, plen = self._pad_prefixes(prefixes, B)
         tok, lp, masked = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32), np.empty_like(logits)
         self._lib_mod.check(self.lib.eioku_whisper_select(self._h, logits.ctypes.data, B, pre.ctypes.data, cap, plen.ctypes.data,
                                                           tok.ctypes.data, lp.ctypes.data, masked.ctypes.data), "eioku_whisper_select")
@@ -894,82 +886,9 @@ class WhisperTranscriber:
         unknown = sorted(set(fallback) - set(FALLBACK_KEYS))
         if unknown:
             raise TypeError(f"transcribe() got unexpected keyword arguments {unknown}")
-        if fallback:
-            fb = check_fallback(**fallback)
-            if fb["condition_on_previous_text"] and window_mode != "seek":
-                raise ValueError("condition_on_previous_text needs window_mode='seek': fixed windows decode in lockstep")
-            return self._transcribe_fallback(samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb,
-                                             word_timestamps)
-        d = self.dims
-        samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
-        content_frames = len(samples) // HOP
-        max_new = int(max_new_tokens) if max_new_tokens is not None else d["max_target_positions"] // 2
-        max_new = min(max_new, d["max_target_positions"] - 3)
-        segments: list[dict] = []
-        lang_id = self._language_token(language)
-        if content_frames == 0:
-            return {"segments": [], "language": language}
-        self.set_audio(samples)
-
-        def run(seeks: list[int]) -> dict:
-            nonlocal lang_id
-            self.logmel([s * HOP for s in seeks], fetch=False)
-            self.encode(len(seeks))
-            if lang_id is None and d["lang_ids"]:  # language of the first window: argmax over the language ids after SOT
-                lang_id = int(self.decode([d["sot"]], len(seeks), 0)["lang"][0])
-            if beam_size == 1:
-                return self.decode(self._prompt(lang_id), len(seeks), max_new)
-            res = self.decode_beam(self._prompt(lang_id), len(seeks), max_new, beam_size, patience)
-            pick = np.arange(len(seeks)), np.asarray(res["best"])
-            return {"tokens": np.asarray(res["tokens"])[pick], "sum_logprob": np.asarray(res["sum_logprob"])[pick],
-                    "no_speech_prob": res["no_speech_prob"]}
-
-        def emit_all(res: dict, seeks: list[int]) -> int:
-            """The segments of the windows of one encode; -> the frames the last of them advances by."""
-            cut = []
-            for lane, seek in enumerate(seeks):
-                size = min(self.window_frames, content_frames - seek)
-                toks = [int(t) for t in res["tokens"][lane]]
-                n_text = toks.index(d["eot"]) if d["eot"] in toks else len(toks)
-                if skip_window(float(res["no_speech_prob"][lane]), float(res["sum_logprob"][lane]), n_text):
-                    cut.append((lane, seek, size, None, size))
-                    continue
-                pieces, advance = cut_window(toks, d["eot"], d["timestamp_begin"], seek * MS_PER_FRAME, size)
-                cut.append((lane, seek, size, pieces, advance))
-            code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
-            kept = [c for c in cut if c[3] is not None]
-            words = None
-            if word_timestamps and kept:
-                words = self._window_words([(lane, seek, size, [ids for _, _, ids in pieces]) for lane, seek, size, pieces, _ in kept],
-                                           lang_id, code)
-            for k, (_, _, _, pieces, _) in enumerate(kept):
-                for n, (start_ms, end_ms, ids) in enumerate(pieces):
-                    text = self.decoder.decode(ids)
-                    if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
-                        continue  # faster-whisper drops empty and zero-length segments
-                    segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code,
-                                     "confidence": None, "words": words[k][n] if words is not None else None, "tokens": ids})
-            _, _, size, _, advance = cut[-1]
-            return max(1, min(advance, size)) if window_mode == "seek" else size
-
-        if window_mode == "seek":
-            seek = 0
-            while seek < content_frames:
-                seek += emit_all(run([seek]), [seek])
-        else:
-            starts = list(range(0, content_frames, self.window_frames))
-            per_batch = max(1, int(batch_windows))
-            if beam_size > 1:
-                per_batch = min(per_batch, MAX_LANES // beam_size)
-            for i in range(0, len(starts), per_batch):
-                batch = starts[i:i + per_batch]
-                emit_all(run(batch), batch)
-        code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
-        return {"segments": segments, "language": code}
-
-    def _transcribe_fallback(self, samples, language, window_mode, batch_windows, max_new_tokens, beam_size, patience, fb,
-                             word_timestamps=False) -> dict:
-        """:meth:`WhisperTranscriber.transcribe` with the temperature fallback and previous-text prompts."""
+        fb = check_fallback(**fallback) if fallback else None
+        if fb and fb["condition_on_previous_text"] and window_mode != "seek":
+            raise ValueError("condition_on_previous_text needs window_mode='seek': fixed windows decode in lockstep")
         d = self.dims
         Tm, eot, tb = d["max_target_positions"], d["eot"], d["timestamp_begin"]
         samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
@@ -978,36 +897,45 @@ class WhisperTranscriber:
         if content_frames == 0:
             return {"segments": [], "language": language}
         self.set_audio(samples)
-        temps, best_of = fb["temperature"], fb["best_of"]
-        crt, lpt = fb["compression_ratio_threshold"], fb["log_prob_threshold"]
-        sot_prev = d.get("sot_prev")
-        if sot_prev is None:
-            sot_prev = d["no_speech"] - 1   # <|startofprev|> sits right before <|nospeech|> in every Whisper vocabulary
         segments: list[dict] = []
+        # the no-speech rule skips a window on no_speech_prob > 0.6 with the average log-probability below this (None: on the
+        # probability alone)
+        threshold = fb["log_prob_threshold"] if fb else LOGPROB_THRESHOLD
+        # fallback only: the figures of every decoded window, the tokens emitted so far and where the previous text starts
         windows_log: list[dict] = []
         all_tokens: list[int] = []
         reset = 0
 
-        def build_prompt() -> tuple[list[int], int]:
-            base = self._prompt(lang_id)
-            prev = all_tokens[reset:][-(Tm // 2 - 1):] if fb["condition_on_previous_text"] else []
-            return ([sot_prev] + prev + base, 1 + len(prev)) if prev else (base, 0)
-
-        def describe(tokens, total, nsp, temperature) -> dict:
+        def record(tokens, total, nsp, **extra) -> dict:
+            """One window's accepted decode; the average runs over the sampled tokens and the closing EOT, as in Whisper."""
             toks = [int(t) for t in tokens]
             n_text = toks.index(eot) if eot in toks else len(toks)
-            text = self.decoder.decode([t for t in toks[:n_text] if t < eot])
-            return {"tokens": toks, "sum_logprob": float(total), "no_speech_prob": float(nsp), "temperature": float(temperature),
-                    "avg_logprob": float(total) / (n_text + 1), "compression_ratio": compression_ratio(text)}
+            return {"tokens": toks, "sum_logprob": float(total), "no_speech_prob": float(nsp),
+                    "avg_logprob": float(total) / (n_text + 1), **extra}
 
-        def decode_all(seeks: list[int]) -> list[dict]:
-            """One encode of the windows, then the temperature schedule over the windows that still need another try."""
-            nonlocal lang_id
-            self.logmel([s * HOP for s in seeks], fetch=False)
-            self.encode(len(seeks))
-            if lang_id is None and d["lang_ids"]:
-                lang_id = int(self.decode([d["sot"]], len(seeks), 0)["lang"][0])
-            prompt, sot_index = build_prompt()
+        def decode_plain(seeks: list[int]) -> list[dict]:
+            """The windows of the last encode, decoded once: greedy, or the best hypothesis of a beam search."""
+            max_new = min(int(max_new_tokens) if max_new_tokens is not None else Tm // 2, Tm - 3)
+            if beam_size == 1:
+                res = self.decode(self._prompt(lang_id), len(seeks), max_new)
+                rows, sums = res["tokens"], res["sum_logprob"]
+            else:
+                res = self.decode_beam(self._prompt(lang_id), len(seeks), max_new, beam_size, patience)
+                pick = np.arange(len(seeks)), np.asarray(res["best"])
+                rows, sums = np.asarray(res["tokens"])[pick], np.asarray(res["sum_logprob"])[pick]
+            return [record(rows[k], sums[k], res["no_speech_prob"][k]) for k in range(len(seeks))]
+
+        def decode_fallback(seeks: list[int]) -> list[dict]:
+            """The temperature schedule over the windows of the last encode that still need another try."""
+            temps, best_of = fb["temperature"], fb["best_of"]
+            crt, lpt = fb["compression_ratio_threshold"], fb["log_prob_threshold"]
+            sot_prev = d.get("sot_prev")
+            if sot_prev is None:
+                sot_prev = d["no_speech"] - 1   # <|startofprev|> sits right before <|nospeech|> in every Whisper vocabulary
+            prompt, sot_index = self._prompt(lang_id), 0
+            prev = all_tokens[reset:][-(Tm // 2 - 1):] if fb["condition_on_previous_text"] else []
+            if prev:
+                prompt, sot_index = [sot_prev] + prev + prompt, 1 + len(prev)
             max_new = min(Tm // 2, Tm - len(prompt))
             if max_new_tokens is not None:
                 max_new = min(max_new, int(max_new_tokens))
@@ -1033,7 +961,9 @@ class WhisperTranscriber:
                         res = self.decode_beam_prompted(prompts, sot_index, max_new, beam_size, patience, windows=windows)
                     for k, w in enumerate(part):
                         row = int(res["best"][k])
-                        tried[w].append(describe(res["tokens"][k][row], res["sum_logprob"][k][row], res["no_speech_prob"][k], temp))
+                        r = record(res["tokens"][k][row], res["sum_logprob"][k][row], res["no_speech_prob"][k], temperature=float(temp))
+                        text = self.decoder.decode([t for t in takewhile(lambda t: t != eot, r["tokens"]) if t < eot])
+                        tried[w].append({**r, "compression_ratio": compression_ratio(text)})
                 still = []
                 for w in pending:
                     r = tried[w][-1]
@@ -1053,7 +983,7 @@ class WhisperTranscriber:
             cut = []
             for w, (r, seek) in enumerate(zip(accepted, seeks)):
                 size = min(self.window_frames, content_frames - seek)
-                if r["no_speech_prob"] > NO_SPEECH_THRESHOLD and (lpt is None or r["avg_logprob"] < lpt):
+                if r["no_speech_prob"] > NO_SPEECH_THRESHOLD and (threshold is None or r["avg_logprob"] < threshold):
                     cut.append((w, seek, size, None, size))
                     continue
                 pieces, advance = cut_window(r["tokens"], eot, tb, seek * MS_PER_FRAME, size)
@@ -1065,39 +995,45 @@ class WhisperTranscriber:
                     [(w, seek, size, [ids for _, _, ids in pieces]) for w, seek, size, pieces, _ in kept], lang_id, code)))
             for w, seek, size, pieces, advance in cut:
                 r = accepted[w]
-                windows_log.append({"start_frame": seek, **{k: r[k] for k in ("temperature", "avg_logprob", "compression_ratio",
-                                                                              "no_speech_prob")}})
+                figures = {k: r[k] for k in ("temperature", "avg_logprob", "compression_ratio")} if fb else {}
+                if fb:
+                    windows_log.append({"start_frame": seek, **figures, "no_speech_prob": r["no_speech_prob"]})
                 if pieces is None:
                     continue
                 for n, (start_ms, end_ms, ids) in enumerate(pieces):
                     text = self.decoder.decode(ids)
                     if start_ms == end_ms or (self.decoder._tokens and text.strip() == "") or not ids:
-                        continue
-                    segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code, "confidence": None,
-                                     "words": words[w][n] if words is not None else None, "tokens": ids,
-                                     "temperature": r["temperature"], "avg_logprob": r["avg_logprob"],
-                                     "compression_ratio": r["compression_ratio"]})
-                if fb["condition_on_previous_text"]:
+                        continue  # faster-whisper drops empty and zero-length segments
+                    segments.append({"start_ms": int(start_ms), "end_ms": int(end_ms), "text": text, "language": code,
+                                     "confidence": None, "words": words[w][n] if words is not None else None, "tokens": ids, **figures})
+                if fb and fb["condition_on_previous_text"]:
                     all_tokens.extend(emitted_tokens(r["tokens"], eot, tb))
                     if r["temperature"] > fb["prompt_reset_on_temperature"]:
                         reset = len(all_tokens)
             _, _, size, _, advance = cut[-1]
             return max(1, min(advance, size)) if window_mode == "seek" else size
 
+        def run(seeks: list[int]) -> int:
+            nonlocal lang_id
+            self.logmel([s * HOP for s in seeks], fetch=False)
+            self.encode(len(seeks))
+            if lang_id is None and d["lang_ids"]:  # language of the first window: argmax over the language ids after SOT
+                lang_id = int(self.decode([d["sot"]], len(seeks), 0)["lang"][0])
+            return emit_all((decode_fallback if fb else decode_plain)(seeks), seeks)
+
         if window_mode == "seek":
             seek = 0
             while seek < content_frames:
-                seek += emit_all(decode_all([seek]), [seek])
+                seek += run([seek])
         else:
             starts = list(range(0, content_frames, self.window_frames))
             per_batch = max(1, int(batch_windows))
             if beam_size > 1:
                 per_batch = min(per_batch, MAX_LANES // beam_size)
             for i in range(0, len(starts), per_batch):
-                batch = starts[i:i + per_batch]
-                emit_all(decode_all(batch), batch)
+                run(starts[i:i + per_batch])
         code = d["lang_codes"][d["lang_ids"].index(lang_id)] if lang_id in d["lang_ids"] else language
-        return {"segments": segments, "language": code, "windows": windows_log}
+        return {"segments": segments, "language": code, **({"windows": windows_log} if fb else {})}
 
 
 # the config under which transcribe_video decodes as the reference's WhisperModel.transcribe(path, language=..., vad_filter=...)
