@@ -260,6 +260,22 @@ SIGNATURES = {
     "eioku_audio_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p]),
     "eioku_audio_tile": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "eioku_audio_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_spk_create": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "eioku_spk_destroy": (None, [C.c_void_p]),
+    "eioku_spk_num_convs": (C.c_int, [C.c_void_p]),
+    "eioku_spk_conv_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eioku_spk_set_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eioku_spk_set_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_spk_set_audio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    "eioku_spk_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_spk_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "eioku_spk_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eioku_spk_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "eioku_spk_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eioku_spk_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                   C.c_void_p]),
 }
 
 

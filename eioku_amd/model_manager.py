@@ -156,7 +156,8 @@ class ModelManager:
     def __init__(self, cache_dir: str = "/models", *, frame_source=None, detector_factory=None, batch_size: int = 64,
                  random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
                  ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None,
-                 gpu_vad: bool = False, vad_factory=None, gpu_audio: bool = False, audio_frontend_factory=None):
+                 gpu_vad: bool = False, vad_factory=None, gpu_audio: bool = False, audio_frontend_factory=None,
+                 gpu_speakers: bool = False, speaker_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
@@ -171,7 +172,10 @@ class ModelManager:
         ``vad_filter`` is on (the reference's default); ``vad_factory(cache_dir) -> object with speech_probs(samples)`` is
         its seam.  ``gpu_audio=True`` (with ``gpu_transcription``) reads PCM WAV of any sample rate, width and channel count
         and resamples it to 16 kHz on the device (``eioku_amd.audio``); ``audio_frontend_factory() -> object with load(path)
-        and resample_float(samples, rate)`` is its seam.  Without it audio that is not 16 kHz raises, as before."""
+        and resample_float(samples, rate)`` is its seam.  Without it audio that is not 16 kHz raises, as before.
+        ``gpu_speakers=True`` (with ``gpu_transcription``) labels the segments' speakers (``eioku_amd.speakers``) when the
+        task's ``speaker_labels`` is true; ``speaker_factory(cache_dir, model_name) -> object with label(samples, segments,
+        eps=, min_samples=, assign_max=)`` is its seam (``speaker_model`` in the task's config names the checkpoint)."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -188,6 +192,8 @@ class ModelManager:
         self._vad_factory = vad_factory
         self._gpu_audio = bool(gpu_audio)
         self._audio_frontend_factory = audio_frontend_factory
+        self._gpu_speakers = bool(gpu_speakers)
+        self._speaker_factory = speaker_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -244,7 +250,8 @@ class ModelManager:
         thresholds adds the temperature fallback, ``condition_on_previous_text`` the previous-text prompts
         (``transcribe.REFERENCE_CALL`` is the reference's call); values outside their ranges raise ``ValueError``.  A manager
         built with ``gpu_vad=True`` applies ``vad_filter`` (default on) and ``vad_parameters`` through Silero VAD first; one
-        built with ``gpu_audio=True`` takes PCM WAV of any rate, width and channel count and resamples it on the device.  The
+        built with ``gpu_audio=True`` takes PCM WAV of any rate, width and channel count and resamples it on the device; one
+        built with ``gpu_speakers=True`` adds a ``speaker`` key to every segment when ``speaker_labels`` is true.  The
         deviations from the reference's call are listed in INTEGRATION.md §3."""
         if not self._gpu_transcription:
             raise NotImplementedError(f"transcribe_video {OUT_OF_SCOPE}")
@@ -258,7 +265,7 @@ class ModelManager:
                 transcriber = self._transcriber_factory(self.cache_dir, model_name)
             else:
                 transcriber = WhisperTranscriber.from_cache(self.cache_dir, model_name, seed=self._seed)
-            vad = frontend = None
+            vad = frontend = speakers = None
             try:
                 extra = {}
                 if self._gpu_audio:
@@ -276,10 +283,19 @@ class ModelManager:
                         from .vad import SileroVad
 
                         vad = SileroVad.from_cache(self.cache_dir, seed=self._seed)
+                if self._gpu_speakers and config.get("speaker_labels") is True:
+                    speaker_model = config.get("speaker_model", "voxceleb_resnet34_LM")
+                    if self._speaker_factory is not None:
+                        speakers = self._speaker_factory(self.cache_dir, speaker_model)
+                    else:
+                        from .speakers import SpeakerLabeller
+
+                        speakers = SpeakerLabeller.from_cache(self.cache_dir, speaker_model, seed=self._seed)
+                    extra["speakers"] = speakers
                 result = transcribe_video(video_path, config, transcriber=transcriber, audio_source=self._audio_source, vad=vad,
                                           **extra)
             finally:
-                for model in (frontend, vad, transcriber):
+                for model in (frontend, vad, speakers, transcriber):
                     close = getattr(model, "close", None)
                     if close:
                         close()

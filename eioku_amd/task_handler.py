@@ -19,6 +19,8 @@ storage go through two small hooks carried in the arq ``ctx`` dict.
                         ``vad_filter`` is on (the default) is gated by Silero VAD on the HIP path
     ctx["gpu_audio"]    true (with gpu_transcription): the manager is built with ``gpu_audio=True``, so PCM audio of any
                         sample rate, width and channel count is decoded and resampled to 16 kHz on the HIP path
+    ctx["gpu_speakers"] true (with gpu_transcription): the manager is built with ``gpu_speakers=True``, so a task whose
+                        ``speaker_labels`` is true gets a ``speaker`` key in every "transcript.segment" payload
 """
 
 from __future__ import annotations
@@ -165,6 +167,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             extra = {"gpu_vad": True} if ctx.get("gpu_vad") else {}
             if ctx.get("gpu_audio"):
                 extra["gpu_audio"] = True
+            if ctx.get("gpu_speakers"):
+                extra["gpu_speakers"] = True
             model_manager = factory(cache_dir=model_cache_dir, gpu_transcription=True, **extra)
         else:
             model_manager = factory(cache_dir=model_cache_dir)

@@ -1052,7 +1052,8 @@ def transcribe_result(raw: dict) -> dict:
                          for s in raw["segments"]]}
 
 
-def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None, vad=None, audio_frontend=None) -> dict:
+def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None, vad=None, audio_frontend=None,
+                     speakers=None) -> dict:
     """``ModelManager.transcribe_video`` body.  Config keys consumed: ``languages`` (string or list: the first entry; None =
     detect), ``vad_filter`` (applied when a ``vad`` object is given, see below), ``window_mode``, ``batch_windows``, ``beam_size`` (1..8, default 1 =
     greedy; 5 is the reference's call) and ``patience`` (positive, default 1.0); ``model_name`` picks the checkpoint in the
@@ -1072,8 +1073,24 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None,
     ``audio_frontend``: an object with ``load(path) -> (16 kHz samples, 16000)`` and ``resample_float(samples, rate)``
     (:class:`eioku_amd.audio.AudioFrontEnd`).  With it and no ``audio_source`` the audio comes from ``load``: PCM WAV of any
     rate, width and channel count; with both, a source whose rate is not 16000 goes through ``resample_float``.  Everything
-    after it sees 16 kHz samples.  Without it any other rate raises, as before."""
+    after it sees 16 kHz samples.  Without it any other rate raises, as before.
+
+    ``speakers``: an object with ``label(samples, segments, eps=, min_samples=, assign_max=) -> one label or None per
+    segment`` (:class:`eioku_amd.speakers.SpeakerLabeller`).  With it and ``config["speaker_labels"]`` true (a bool; anything
+    else is a ``ValueError``) every segment gains a ``"speaker"`` key (``speaker_001`` ... by first appearance, ``None`` for a
+    segment too short to embed or one no cluster claims); ``speaker_eps`` in (0, 2), ``speaker_min_samples`` >= 1 and
+    ``speaker_assign_max`` in [0, 2] tune the clustering.  The labeller sees the file's own 16 kHz samples and file-time
+    segments, also under VAD.  Without either the result is the reference's six keys and no speaker code runs."""
     config = config or {}
+    use_speakers = False
+    if "speaker_labels" in config:
+        if not isinstance(config["speaker_labels"], bool):
+            raise ValueError(f"speaker_labels must be a bool, got {config['speaker_labels']!r}")
+        use_speakers = config["speaker_labels"] and speakers is not None
+    if use_speakers:
+        from .speakers import SPEAKER_KEYS, check_speaker_options
+
+        speaker_options = check_speaker_options(**{k: config[k] for k in SPEAKER_KEYS if k in config})
     languages = config.get("languages")
     if isinstance(languages, (list, tuple)):
         languages = languages[0] if languages else None
@@ -1107,6 +1124,7 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None,
             samples, rate = audio_frontend.resample_float(samples, rate), SAMPLE_RATE
     check_rate(rate)
     samples = np.asarray(samples, dtype=np.float32)
+    file_samples = samples
     chunks = None
     if use_vad:
         samples = samples.reshape(-1)
@@ -1121,4 +1139,11 @@ def transcribe_video(path: str, config: dict, *, transcriber, audio_source=None,
                                  batch_windows=int(config.get("batch_windows", 8)), **beam, **given)
     if chunks is not None:
         raw = {**raw, "segments": vad_mod.restore_speech_timestamps(raw["segments"], chunks)}
-    return transcribe_result(raw)
+    result = transcribe_result(raw)
+    if use_speakers:
+        labels = speakers.label(file_samples.reshape(-1), raw["segments"], **speaker_options)
+        if len(labels) != len(result["segments"]):
+            raise ValueError(f"{len(labels)} speaker labels for {len(result['segments'])} segments")
+        for seg, label in zip(result["segments"], labels):
+            seg["speaker"] = label
+    return result

@@ -777,6 +777,43 @@ int eioku_audio_plan(int up, int down, int taps_per_phase, long long slab_out, l
 int eioku_audio_tile(const eioku_audio_t* a, int* tile);
 int eioku_audio_last_ms(const eioku_audio_t* a, double* kernel_ms);
 
+/* ---- transcription: speaker labels (K24), csrc/speakers.hip ---------------------------------------------------------------
+ * WeSpeaker ResNet speaker embeddings per window of a transcript segment, clustered per video by K14 (dbscan_cosine).
+ * [PUBLIC-LIB]: restated from the public WeSpeaker / Kaldi sources.  A window is (first sample, valid frames) over the
+ * uploaded 16 kHz audio: frame t covers samples first + 160 t .. + 399, valid <= win_frames.
+ *   create: depths = BasicBlocks per stage (r18 2,2,2,2; r34 3,4,6,3), base width 32; win_frames a multiple of 8, >= 16;
+ *     window HOST fp64 [400] (Povey), mel HOST fp64 [80][256] (Kaldi triangles over FFT bins 0..255).
+ *   conv_info / set_conv: conv1, layer<L>.<b>.conv1 / .conv2 / .shortcut.0; weight HOST fp32 [cout][cin][k][k] with the
+ *     BatchNorm that follows folded in, bias HOST fp32 [cout].
+ *   set_head: seg_1, weight HOST fp32 [256][5120] with columns in the device's order (means, then standard deviations,
+ *     each at frequency * 256 + channel), bias [256].
+ *   set_audio: the video's samples (host or device per mem), kept on the device.
+ *   features: plan HOST int32 [m][2], m <= 64 -> fp16 [m][80][win][8] (NHWC: mel bin, frame, channel 0) and, optionally,
+ *     the fp32 values before that rounding [m][80][win]; frames at or past valid are 0.  Device outputs.
+ *   forward: the network on such features, m <= 64; upto_block >= 0 -> that block's NHWC fp16 output; otherwise the 5120
+ *     pooled statistics (optional) and the unnormalised 256-vectors over the first ceil(valid / 8) columns (valid >= 9).
+ *   embed: features + network + pooling + seg_1 for any m, in passes of 64 -> device [m][256].
+ *   segments: mean of each segment's window rows (seg_first HOST [n_seg + 1]) in row order, L2 normalised -> device.
+ *   assign: centroid per DBSCAN label (normalised sum of its rows in row order); a noise row takes the nearest centroid's
+ *     label when 1 - cos <= assign_max (ties: the smaller label).  Device in and out; *n_labels = labels seen.
+ *   last_ms: device time of the last embed (features, network, pooling + seg_1), summed over its passes. */
+typedef struct eioku_spk eioku_spk_t;
+int eioku_spk_create(const int* depths, int win_frames, const double* window, const double* mel, eioku_spk_t** out);
+void eioku_spk_destroy(eioku_spk_t* s);
+int eioku_spk_num_convs(const eioku_spk_t* s);
+int eioku_spk_conv_info(const eioku_spk_t* s, int idx, char* name, size_t name_cap, int* cout, int* cin, int* ksize, int* stride);
+int eioku_spk_set_conv(eioku_spk_t* s, int idx, const float* weight_oihw, const float* bias);
+int eioku_spk_set_head(eioku_spk_t* s, const float* weight, const float* bias);
+int eioku_spk_set_audio(eioku_spk_t* s, const float* samples, long long n_samples, int mem, void* stream);
+int eioku_spk_features(eioku_spk_t* s, const int* plan, int m, void* out_f16, float* out_f32, void* stream);
+int eioku_spk_forward(eioku_spk_t* s, const void* in_f16, const int* valid, int m, int upto_block, void* act_out, float* stats_out,
+                      float* emb_out, void* stream);
+int eioku_spk_embed(eioku_spk_t* s, const int* plan, int m, float* emb_out, void* stream);
+int eioku_spk_last_ms(const eioku_spk_t* s, double* features_ms, double* network_ms, double* head_ms);
+int eioku_spk_segments(const float* win_emb, const int* seg_first, int n_seg, float* out, void* stream);
+int eioku_spk_assign(const float* emb, int n, const int32_t* labels, float assign_max, int32_t* labels_out, float* centroids_out,
+                     int* n_labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
