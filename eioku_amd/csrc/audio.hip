@@ -140,10 +140,9 @@ struct eioku_audio {
   unsigned dinv = 0;          // (down mod up)^-1 mod up: phase p sits at j = p * dinv mod up
   long long slab = 0;         // outputs per slab, after the 31-bit clamp
   hipStream_t st = nullptr;
-  float* bank = nullptr;      // W [T][up]
-  float* out = nullptr;       // slab
-  uint32_t* raw = nullptr;    // the slab's input frames
-  size_t raw_cap = 0;
+  DevBuf<float> bank;         // W [T][up]
+  DevBuf<float> out;          // slab
+  DevBuf<uint32_t> raw;       // the slab's input frames
   std::vector<hipEvent_t> ev;   // 2 per slab of the last call
   double ms = 0;
 };
@@ -164,11 +163,9 @@ int eioku_audio_plan(int up, int down, int taps_per_phase, long long slab_out, l
 void eioku_audio_destroy(eioku_audio* a) {
   if (!a) return;
   if (a->st) (void)hipStreamSynchronize(a->st);
-  for (void* b : {(void*)a->bank, (void*)a->out, (void*)a->raw})
-    if (b) (void)hipFree(b);
   for (hipEvent_t e : a->ev) (void)hipEventDestroy(e);
   if (a->st) (void)hipStreamDestroy(a->st);
-  delete a;
+  delete a;  // every buffer frees itself
 }
 
 int eioku_audio_create(int up, int down, int taps_per_phase, const float* bank, long long slab_out, eioku_audio** out) {
@@ -210,14 +207,13 @@ int eioku_audio_create(int up, int down, int taps_per_phase, const float* bank, 
     h->st = nullptr;
     return fail(EIOKU_EHIP, "hipStreamCreate");
   }
-  if (hipMalloc(&h->out, (size_t)h->slab * sizeof(float)) != hipSuccess) return fail(EIOKU_ENOMEM, "hipMalloc");
+  if (h->out.grow((size_t)h->slab)) return fail(EIOKU_ENOMEM, "hipMalloc");
   if (!pass) {
     std::vector<float> w((size_t)up * T);    // W[q][j] = B[(j * d) mod up][q]
     const unsigned d = (unsigned)(down % up);
     for (int q = 0; q < T; ++q)
       for (unsigned j = 0; j < (unsigned)up; ++j) w[(size_t)q * up + j] = bank[(size_t)((j * d) % (unsigned)up) * T + q];
-    if (hipMalloc(&h->bank, w.size() * sizeof(float)) != hipSuccess) return fail(EIOKU_ENOMEM, "hipMalloc");
-    if (hipMemcpy(h->bank, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(EIOKU_EHIP, "hipMemcpy");
+    if (const int rc = h->bank.upload(w.data(), w.size())) return fail(rc, rc == EIOKU_ENOMEM ? "hipMalloc" : "hipMemcpy");
   }
   *out = h;
   return EIOKU_OK;
@@ -252,15 +248,9 @@ int eioku_audio_resample(eioku_audio* a, const void* pcm, int format, int channe
   EIOKU_REQUIRE(slab >= 1, "a slab of one output does not fit 2^31 bytes");
   const long long n_slabs = (total + slab - 1) / slab;
   const size_t need = (size_t)((slab * a->down + a->up) / a->up + T + 1) * fb + 16;
-  if (need > a->raw_cap) {
+  if (need > a->raw.cap * 4) {
     EIOKU_HIP_CHECK(hipStreamSynchronize(a->st));
-    if (a->raw) (void)hipFree(a->raw);
-    a->raw = nullptr, a->raw_cap = 0;
-    if (hipMalloc(&a->raw, need) != hipSuccess) {
-      set_error("eioku_audio_resample: hipMalloc of %zu bytes failed", need);
-      return EIOKU_ENOMEM;
-    }
-    a->raw_cap = need;
+    EIOKU_TRY(a->raw.grow((need + 3) / 4));
   }
   while ((long long)a->ev.size() < 2 * n_slabs) {
     hipEvent_t e;
@@ -273,19 +263,19 @@ int eioku_audio_resample(eioku_audio* a, const void* pcm, int format, int channe
     Plan pl{};
     EIOKU_REQUIRE(audio_plan(a->up, a->down, T, slab, n_frames, k, &pl), "slab %lld is past the end", k);
     const size_t bytes = (size_t)pl.frames * fb;
-    EIOKU_REQUIRE(pl.n_out <= a->slab && bytes + 16 <= a->raw_cap && pl.lead + pl.frames < (1LL << 31), "slab %lld does not fit its buffers", k);
+    EIOKU_REQUIRE(pl.n_out <= a->slab && bytes + 16 <= a->raw.cap * 4 && pl.lead + pl.frames < (1LL << 31), "slab %lld does not fit its buffers", k);
     if (bytes)
-      EIOKU_HIP_CHECK(hipMemcpyAsync(a->raw, (const char*)pcm + (size_t)pl.first_frame * fb, bytes, hipMemcpyHostToDevice, st));
+      EIOKU_HIP_CHECK(hipMemcpyAsync(a->raw.p, (const char*)pcm + (size_t)pl.first_frame * fb, bytes, hipMemcpyHostToDevice, st));
     const Src src{a->raw, (unsigned)pl.lead, (unsigned)pl.frames, format, channels};
     EIOKU_HIP_CHECK(hipEventRecord(a->ev[2 * k], st));
     if (a->T) {
       const unsigned tiles = (unsigned)((pl.n_out + a->tile - 1) / a->tile);
       const unsigned grid = tiles < 2u * cus ? tiles : 2u * cus;     // two 64 KiB workgroups per CU
-      hipLaunchKernelGGL(k_audio_resample, dim3(grid), dim3(kThreads), 0, st, src, a->bank, a->up, a->down, a->T, a->tile,
-                         (unsigned)pl.phase, (unsigned)((unsigned long long)pl.phase * a->dinv % a->up), (unsigned)pl.n_out, a->out);
+      hipLaunchKernelGGL(k_audio_resample, dim3(grid), dim3(kThreads), 0, st, src, a->bank.p, a->up, a->down, a->T, a->tile,
+                         (unsigned)pl.phase, (unsigned)((unsigned long long)pl.phase * a->dinv % a->up), (unsigned)pl.n_out, a->out.p);
     } else {
       hipLaunchKernelGGL(k_audio_decode, dim3((unsigned)((pl.n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, src,
-                         (unsigned)pl.n_out, a->out);
+                         (unsigned)pl.n_out, a->out.p);
     }
     EIOKU_LAUNCH_CHECK();
     EIOKU_HIP_CHECK(hipEventRecord(a->ev[2 * k + 1], st));

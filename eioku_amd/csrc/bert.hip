@@ -728,7 +728,8 @@ struct eioku_bert {
   struct Tensor {
     std::string name;
     std::vector<int> shape;
-    float* dev = nullptr;
+    DevBuf<float> own;     // the entry's allocation; a layer's query entry owns its key and value too (one [3H][H] operand)
+    float* dev = nullptr;  // where the tensor lives: own, or inside the query entry's
     bool set = false;
     size_t numel() const {
       size_t n = 1;
@@ -738,40 +739,22 @@ struct eioku_bert {
   };
   std::vector<Tensor> tensors;
   // workspace
-  int32_t* d_ids = nullptr; size_t ids_cap = 0;
-  uint8_t* d_mask = nullptr; size_t mask_cap = 0;
-  float* x = nullptr; float* y = nullptr; float* qkv = nullptr; float* ctx = nullptr; float* mid = nullptr;
-  size_t x_cap = 0, y_cap = 0, qkv_cap = 0, ctx_cap = 0, mid_cap = 0;
-  float* d_out = nullptr; size_t out_cap = 0;
+  DevBuf<int32_t> d_ids;
+  DevBuf<uint8_t> d_mask;
+  DevBuf<float> x, y, qkv, ctx, mid, d_out;
   // activations as bf16 hi | lo planes for the GEMMs that read them (x, ctx, mid): [2][T][width] each
-  unsigned short* xp = nullptr; unsigned short* cp = nullptr; unsigned short* mp = nullptr;
-  size_t xp_cap = 0, cp_cap = 0, mp_cap = 0;
+  DevBuf<unsigned short> xp, cp, mp;
   double flops_last = 0;
   // GEMM weights pre-split into bf16 hi / lo planes (same RNE split the kernel applies on the fly), per layer
   // [qkv | out | ffn1 | ffn2]; rebuilt lazily after set_tensor
   struct SplitW {
-    unsigned short* hi = nullptr;
-    unsigned short* lo = nullptr;
+    DevBuf<unsigned short> hi, lo;
   };
   std::vector<SplitW> wsplit;  // 4 per layer
   bool wsplit_dirty = true;
 };
 
 namespace {
-
-template <typename T>
-int grow(T** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return EIOKU_OK;
-  if (*p) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
-  EIOKU_HIP_CHECK(hipMalloc((void**)p, bytes));
-  *cap = bytes;
-  return EIOKU_OK;
-}
 
 int find(const eioku_bert* m, const std::string& name) {
   for (size_t i = 0; i < m->tensors.size(); ++i)
@@ -1243,7 +1226,7 @@ int eioku_bert_create(int vocab, int hidden, int layers, int heads, int ffn, int
     eioku_bert::Tensor t;
     t.name = n;
     t.shape = std::move(shape);
-    m->tensors.push_back(t);
+    m->tensors.push_back(std::move(t));
   };
   const int H = hidden;
   add("embeddings.word_embeddings.weight", {vocab, H});
@@ -1278,19 +1261,19 @@ int eioku_bert_create(int vocab, int hidden, int layers, int heads, int ffn, int
     const bool qb = t.name.find("attention.self.query.bias") != std::string::npos;
     if (qw || qb) {
       const size_t n = t.numel();
-      float* base = nullptr;
-      if (hipMalloc((void**)&base, 3 * n * sizeof(float)) != hipSuccess) {
-        set_error("hipMalloc failed for %s", t.name.c_str());
+      if (t.own.grow(3 * n)) {
+        eioku_bert_destroy(m);
         return EIOKU_ENOMEM;
       }
-      m->tensors[i].dev = base;
-      m->tensors[i + 1].dev = base + n;
-      m->tensors[i + 2].dev = base + 2 * n;
+      m->tensors[i].dev = t.own;
+      m->tensors[i + 1].dev = t.own + n;
+      m->tensors[i + 2].dev = t.own + 2 * n;
     } else if (!t.dev) {
-      if (hipMalloc((void**)&t.dev, t.numel() * sizeof(float)) != hipSuccess) {
-        set_error("hipMalloc failed for %s", t.name.c_str());
+      if (t.own.grow(t.numel())) {
+        eioku_bert_destroy(m);
         return EIOKU_ENOMEM;
       }
+      t.dev = t.own;
     }
   }
   *out = m;
@@ -1300,18 +1283,6 @@ int eioku_bert_create(int vocab, int hidden, int layers, int heads, int ffn, int
 void eioku_bert_destroy(eioku_bert* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (size_t i = 0; i < m->tensors.size(); ++i) {
-    const auto& n = m->tensors[i].name;
-    const bool sub = n.find("self.key.") != std::string::npos || n.find("self.value.") != std::string::npos;
-    if (!sub && m->tensors[i].dev) (void)hipFree(m->tensors[i].dev);
-  }
-  for (auto& w : m->wsplit) {
-    if (w.hi) (void)hipFree(w.hi);
-    if (w.lo) (void)hipFree(w.lo);
-  }
-  void* bufs[] = {m->d_ids, m->d_mask, m->x, m->y, m->qkv, m->ctx, m->mid, m->d_out, m->xp, m->cp, m->mp};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
   delete m;
 }
 
@@ -1359,13 +1330,11 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
       const size_t numel[4] = {(size_t)3 * H * H, (size_t)H * H, (size_t)m->ffn * H, (size_t)H * m->ffn};
       for (int k = 0; k < 4; ++k) {
         auto& w = m->wsplit[(size_t)4 * l + k];
-        if (!w.hi) {
-          EIOKU_HIP_CHECK(hipMalloc((void**)&w.hi, numel[k] * 2));
-          EIOKU_HIP_CHECK(hipMalloc((void**)&w.lo, numel[k] * 2));
-        }
+        EIOKU_TRY(w.hi.grow(numel[k]));
+        EIOKU_TRY(w.lo.grow(numel[k]));
         const size_t npairs = numel[k] / 2;
         hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, tp(m, p + names[k]),
-                           npairs, (unsigned*)w.hi, (unsigned*)w.lo);
+                           npairs, (unsigned*)w.hi.p, (unsigned*)w.lo.p);
       }
     }
     EIOKU_LAUNCH_CHECK();
@@ -1376,9 +1345,9 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
   float* d_out = out;
   if (mem == EIOKU_MEM_HOST) {
     for (int i = 0; i < T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < m->vocab, "token id %d at %d outside the vocabulary", ids[i], i);
-    if ((rc = grow(&m->d_ids, &m->ids_cap, (size_t)T * 4))) return rc;
-    if ((rc = grow(&m->d_mask, &m->mask_cap, (size_t)T))) return rc;
-    if ((rc = grow(&m->d_out, &m->out_cap, (size_t)B * H * 4))) return rc;
+    EIOKU_TRY(grow_synced(m->d_ids, (size_t)T));
+    EIOKU_TRY(grow_synced(m->d_mask, (size_t)T));
+    EIOKU_TRY(grow_synced(m->d_out, (size_t)B * H));
     EIOKU_HIP_CHECK(hipMemcpyAsync(m->d_ids, ids, (size_t)T * 4, hipMemcpyHostToDevice, stream));
     EIOKU_HIP_CHECK(hipMemcpyAsync(m->d_mask, mask, (size_t)T, hipMemcpyHostToDevice, stream));
     d_ids = m->d_ids;
@@ -1392,31 +1361,31 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
   // function of the same values, so the embeddings must be the same bytes: tests/test_bert_gpu.py)
   static const bool planes_on = !env_off("EIOKU_GEMM_PLANES");
   const bool planes = planes_on && gemm_takes_planes(H, 1) && gemm_takes_planes(H, sp_o) && gemm_takes_planes(m->ffn, sp_f);
-  if ((rc = grow(&m->x, &m->x_cap, (size_t)T * H * 4))) return rc;
-  if ((rc = grow(&m->y, &m->y_cap, (size_t)kMaxSplit * T * H * 4))) return rc;
-  if ((rc = grow(&m->qkv, &m->qkv_cap, (size_t)T * 3 * H * 4))) return rc;
+  EIOKU_TRY(grow_synced(m->x, (size_t)T * H));
+  EIOKU_TRY(grow_synced(m->y, (size_t)kMaxSplit * T * H));
+  EIOKU_TRY(grow_synced(m->qkv, (size_t)T * 3 * H));
   Planes xP, cP, mP;
   if (planes) {
-    if ((rc = grow(&m->xp, &m->xp_cap, (size_t)2 * T * H * 2))) return rc;
-    if ((rc = grow(&m->cp, &m->cp_cap, (size_t)2 * T * H * 2))) return rc;
-    if ((rc = grow(&m->mp, &m->mp_cap, (size_t)2 * T * m->ffn * 2))) return rc;
+    EIOKU_TRY(grow_synced(m->xp, (size_t)2 * T * H));
+    EIOKU_TRY(grow_synced(m->cp, (size_t)2 * T * H));
+    EIOKU_TRY(grow_synced(m->mp, (size_t)2 * T * m->ffn));
     xP.hi = m->xp; xP.lo = m->xp + (size_t)T * H;
     cP.hi = m->cp; cP.lo = m->cp + (size_t)T * H;
     mP.hi = m->mp; mP.lo = m->mp + (size_t)T * m->ffn;
   } else {
-    if ((rc = grow(&m->mid, &m->mid_cap, (size_t)T * m->ffn * 4))) return rc;
+    EIOKU_TRY(grow_synced(m->mid, (size_t)T * m->ffn));
   }
   static const bool amfma_on = !env_off("EIOKU_ATTN_MFMA");
   const bool amfma = amfma_on && S <= 128 && H == m->heads * 32;
   // the other attention kernels write fp32 ctx (split afterwards by k_split_planes when the GEMMs take planes)
   if (!planes || !amfma)
-    if ((rc = grow(&m->ctx, &m->ctx_cap, (size_t)T * H * 4))) return rc;
+    EIOKU_TRY(grow_synced(m->ctx, (size_t)T * H));
 
   const unsigned tok_blocks = (unsigned)(((size_t)T * 64 + 255) / 256);
   hipLaunchKernelGGL(k_embed_ln, dim3(tok_blocks), dim3(256), 0, stream, d_ids, T, S, H, m->vocab,
                      tp(m, "embeddings.word_embeddings.weight"), tp(m, "embeddings.position_embeddings.weight"),
                      tp(m, "embeddings.token_type_embeddings.weight"), tp(m, "embeddings.LayerNorm.weight"),
-                     tp(m, "embeddings.LayerNorm.bias"), m->eps, m->x, xP.hi, xP.lo);
+                     tp(m, "embeddings.LayerNorm.bias"), m->eps, m->x.p, xP.hi, xP.lo);
   EIOKU_LAUNCH_CHECK();
   const int parts = S <= 256 ? 4 : 1;
   const int qsplit = parts == 4 ? (S + 31) / 32 : 1;  // 32 queries x 4 lanes = 2 waves per workgroup
@@ -1439,15 +1408,15 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
                    3 * H, T, 3 * H, H, 0, 1, stream, &m->wsplit[(size_t)4 * l + 0], xa))) return rc;
     bert_route_hit(amfma ? kRouteAttnBf : parts == 4 ? kRouteAttn8 : kRouteAttn1);
     if (amfma) {
-      hipLaunchKernelGGL(k_attention_bf, dim3(B, m->heads), dim3(256), 0, stream, m->qkv, d_mask, S, H, m->ctx, cP.hi, cP.lo);
+      hipLaunchKernelGGL(k_attention_bf, dim3(B, m->heads), dim3(256), 0, stream, m->qkv.p, d_mask, S, H, m->ctx.p, cP.hi, cP.lo);
     } else {
       if (parts == 4)
-        hipLaunchKernelGGL(k_attention8, dim3(B, m->heads, qsplit), dim3(256), alds, stream, m->qkv, d_mask, S, H, m->ctx);
+        hipLaunchKernelGGL(k_attention8, dim3(B, m->heads, qsplit), dim3(256), alds, stream, m->qkv.p, d_mask, S, H, m->ctx.p);
       else
-        hipLaunchKernelGGL(k_attention<1>, dim3(B, m->heads), dim3(athreads), alds, stream, m->qkv, d_mask, S, H, m->ctx);
+        hipLaunchKernelGGL(k_attention<1>, dim3(B, m->heads), dim3(athreads), alds, stream, m->qkv.p, d_mask, S, H, m->ctx.p);
       if (planes) {
         const size_t npairs = (size_t)T * H / 2;
-        hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, m->ctx, npairs,
+        hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, m->ctx.p, npairs,
                            (unsigned*)cP.hi, (unsigned*)cP.lo);
       }
     }
@@ -1474,7 +1443,7 @@ int eioku_bert_embed(eioku_bert* m, const int32_t* ids, const uint8_t* mask, int
   const int pgroups = (2 * pthreads <= 1024 && S <= 1024) ? 2 : 1;
   EIOKU_REQUIRE(S <= 1024, "sequence length %d exceeds the pooling kernel's mask buffer", S);
   bert_route_hit(pgroups == 2 ? kRoutePoolG2 : kRoutePoolG1);
-  hipLaunchKernelGGL(k_pool_norm, dim3(B), dim3(pgroups * pthreads), 0, stream, m->x, d_mask, S, H, d_out);
+  hipLaunchKernelGGL(k_pool_norm, dim3(B), dim3(pgroups * pthreads), 0, stream, m->x.p, d_mask, S, H, d_out);
   EIOKU_LAUNCH_CHECK();
   m->flops_last = (double)T * m->L * (2.0 * H * 3 * H + 2.0 * H * H + 4.0 * H * m->ffn) +
                   (double)B * m->heads * m->L * 4.0 * S * S * 32;

@@ -106,7 +106,8 @@ __global__ void k_unpack_answers(const long long* __restrict__ in, int world, lo
 struct eioku_comm {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
-  // per-communicator workspace, grown on demand
+  // per-communicator workspace, grown on demand (raw pointers on purpose: this file cannot be exercised on one card, so
+  // it keeps the ownership code it was tested with)
   float* Dloc = nullptr; long long* Iloc = nullptr; size_t loc_cap = 0;
   long long* send = nullptr; long long* recv = nullptr; size_t msg_cap = 0;
   float* dl = nullptr; long long* il = nullptr; size_t list_cap = 0;

@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/eioku_hip.h"
 
@@ -63,7 +65,66 @@ double env_num(const char* name, double dflt);
 // Launch-error check that does not synchronise.
 #define EIOKU_LAUNCH_CHECK() EIOKU_HIP_CHECK(hipGetLastError())
 
+// Pass a callee's error code up unchanged.
+#define EIOKU_TRY(expr)                \
+  do {                                 \
+    const int _rc = (expr);            \
+    if (_rc != EIOKU_OK) return _rc;   \
+  } while (0)
+
 namespace eioku {
+
+// An owning device buffer of `cap` elements: freed by its destructor, moved but never copied.  grow(n) reallocates (and
+// drops the contents) only when n exceeds the capacity; it does not synchronise.  A failed allocation leaves the buffer
+// empty (p == nullptr, cap == 0), so the handle that holds it can be used again or destroyed.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  operator T*() const { return p; }
+  void reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr, cap = 0;
+  }
+  int grow(size_t n) {
+    if (p && n <= cap) return EIOKU_OK;
+    reset();
+    if (hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
+      p = nullptr;
+      set_error("hipMalloc of %zu bytes failed", n * sizeof(T));
+      return EIOKU_ENOMEM;
+    }
+    cap = n;
+    return EIOKU_OK;
+  }
+  // allocate on first use, then a synchronous copy of n host elements
+  int upload(const T* host, size_t n) {
+    EIOKU_TRY(grow(n));
+    if (n) EIOKU_HIP_CHECK(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
+    return EIOKU_OK;
+  }
+};
+
+// For handles whose launches may still be in flight when a call regrows a buffer: wait for the device before the old
+// memory is freed.  No-op, and no wait, while the buffer is large enough.
+template <typename T>
+int grow_synced(DevBuf<T>& b, size_t n) {
+  if (b.p && b.cap < n) (void)hipDeviceSynchronize();
+  return b.grow(n);
+}
+
+static_assert(!std::is_copy_constructible<DevBuf<int>>::value, "DevBuf owns its memory");
+static_assert(std::is_nothrow_move_constructible<DevBuf<int>>::value, "DevBuf lives in std::vector");
 
 __device__ __forceinline__ unsigned long long splitmix64_at(unsigned long long seed,
                                                             unsigned long long i) {

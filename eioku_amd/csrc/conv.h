@@ -25,16 +25,22 @@ struct ConvWeights {
   int nf = 1;       // 16-wide cout fragments per workgroup tile
   int ntiles = 0;   // cout tiles = ceil(cout / (16*nf))
   int nchunks = 0;  // 32-channel input chunks = ceil(cin / 32)
-  __half* d_w = nullptr;  // [ntiles][nchunks][taps][16*nf][32] fp16, zero padded
-  float* d_b = nullptr;   // [ntiles*16*nf] fp32, zero padded
+  DevBuf<__half> d_w;  // [ntiles][nchunks][taps][16*nf][32] fp16, zero padded
+  DevBuf<float> d_b;   // [ntiles*16*nf] fp32, zero padded
   double flops_per_pixel() const { return 2.0 * cout * cin * ks * ks; }
 };
 
 // Packs torch-layout fp32 weights [cout][cin][ks][ks] (+ bias[cout], may be null) for the kernel
-// and uploads them.  Values are rounded to fp16 (RNE) exactly as `tensor.half()` does.
+// and uploads them.  Values are rounded to fp16 (RNE) exactly as `tensor.half()` does.  A `cw` that already holds
+// weights is replaced; the object frees its two buffers itself.
 int conv_weights_create(ConvWeights* cw, int cout, int cin, int ks, int stride, const float* w,
                         const float* b);
-void conv_weights_destroy(ConvWeights* cw);
+// The same for a first layer whose input tensor carries 8 channels of which only the leading `cin` are real (weights
+// [cout][cin][ks][ks]): the other channels get zero weights.
+int conv_weights_create_cin8(ConvWeights* cw, int cout, int cin, int ks, int stride, const float* w, const float* b);
+// The same for a 1x1 of stride `stride` (weights [cout][cin]), run as the 3x3 of that stride that has them on its
+// centre tap: the same sums, and the 3x3 kernels take a stride.
+int conv_weights_create_centre(ConvWeights* cw, int cout, int cin, int stride, const float* w, const float* b);
 
 // kActReLU: relu(conv + bias) [then + res]; kActResReLU: relu(fp16(conv + bias) + res) - the torchvision BasicBlock's
 // order (the activation follows the residual sum); the two ReLU modes serve the ResNet18 of classify_places

@@ -2239,18 +2239,24 @@ int conv_weights_create(ConvWeights* cw, int cout, int cin, int ks, int stride, 
   std::vector<float> pb((size_t)cw->ntiles * tile, 0.f);
   if (b)
     for (int co = 0; co < cout; ++co) pb[co] = b[co];
-  EIOKU_HIP_CHECK(hipMalloc((void**)&cw->d_w, wn * sizeof(_Float16)));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&cw->d_b, pb.size() * sizeof(float)));
-  EIOKU_HIP_CHECK(hipMemcpy(cw->d_w, pw.data(), wn * sizeof(_Float16), hipMemcpyHostToDevice));
-  EIOKU_HIP_CHECK(hipMemcpy(cw->d_b, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
-  return EIOKU_OK;
+  EIOKU_TRY(cw->d_w.upload(reinterpret_cast<const __half*>(pw.data()), wn));
+  return cw->d_b.upload(pb.data(), pb.size());
 }
 
-void conv_weights_destroy(ConvWeights* cw) {
-  if (cw->d_w) (void)hipFree(cw->d_w);
-  if (cw->d_b) (void)hipFree(cw->d_b);
-  cw->d_w = nullptr;
-  cw->d_b = nullptr;
+int conv_weights_create_cin8(ConvWeights* cw, int cout, int cin, int ks, int stride, const float* w, const float* b) {
+  EIOKU_REQUIRE(cin > 0 && cin <= 8, "bad conv shape cout=%d cin=%d", cout, cin);
+  const int taps = ks * ks;
+  std::vector<float> w8((size_t)cout * 8 * taps, 0.f);
+  for (int co = 0; co < cout; ++co)
+    for (int ci = 0; ci < cin; ++ci)
+      for (int t = 0; t < taps; ++t) w8[((size_t)co * 8 + ci) * taps + t] = w[((size_t)co * cin + ci) * taps + t];
+  return conv_weights_create(cw, cout, 8, ks, stride, w8.data(), b);
+}
+
+int conv_weights_create_centre(ConvWeights* cw, int cout, int cin, int stride, const float* w, const float* b) {
+  std::vector<float> w3((size_t)cout * cin * 9, 0.f);
+  for (size_t i = 0; i < (size_t)cout * cin; ++i) w3[i * 9 + 4] = w[i];
+  return conv_weights_create(cw, cout, cin, 3, stride, w3.data(), b);
 }
 
 // EIOKU_CONV_EPI=0: k_conv3x3_flat runs store_frag's generic epilogue everywhere (byte-identity tests,
@@ -2341,7 +2347,7 @@ int conv_chain_forward(const ConvWeights& ca, const ConvWeights& cb, Slice in, i
                 "tensor exceeds 32-bit element offsets -- split the batch");
   ConvArgs a{};
   a.in = in.ptr + in.coff;
-  a.wgt = reinterpret_cast<const uint4*>(ca.d_w);
+  a.wgt = reinterpret_cast<const uint4*>(ca.d_w.p);
   a.bias = ca.d_b;
   a.res = residual ? a.in : nullptr;  // the Bottleneck's shortcut is its own input: read from the staged patch
   a.N = N;
@@ -2357,7 +2363,7 @@ int conv_chain_forward(const ConvWeights& ca, const ConvWeights& cb, Slice in, i
   a.tiles_h = (H + kTH - 1) / kTH;
   a.nchunks = 1;
   a.act = act_a;
-  a.post_w = reinterpret_cast<const uint4*>(cb.d_w);
+  a.post_w = reinterpret_cast<const uint4*>(cb.d_w.p);
   a.post_bias = cb.d_b;
   a.post_out = out.ptr ? out.ptr + out.coff : nullptr;
   a.post_out_cs = out.cstride;
@@ -2365,7 +2371,7 @@ int conv_chain_forward(const ConvWeights& ca, const ConvWeights& cb, Slice in, i
   a.post_act = act_b;
   ChainCat cc{};
   if (cat_w) {
-    cc.w = reinterpret_cast<const uint4*>(cat_w->d_w);
+    cc.w = reinterpret_cast<const uint4*>(cat_w->d_w.p);
     cc.bias = cat_w->d_b;
     cc.out = cat_out.ptr + cat_out.coff;
     cc.out_cs = cat_out.cstride;
@@ -2413,7 +2419,7 @@ int conv_stem_chain_forward(const ConvWeights& stem, const ConvWeights& c1, cons
   if (N == 0) return EIOKU_OK;
   EIOKU_REQUIRE((long long)N * (H / 4) * (W / 4) * out.cstride < (1ll << 31), "tensor exceeds 32-bit element offsets -- split the batch");
   ConvArgs a{};
-  a.wgt = reinterpret_cast<const uint4*>(c1.d_w);
+  a.wgt = reinterpret_cast<const uint4*>(c1.d_w.p);
   a.bias = c1.d_b;
   a.N = N;
   a.H = conv_out_dim(H, 3, 2);  // model.1's input = the stem's output map
@@ -2426,7 +2432,7 @@ int conv_stem_chain_forward(const ConvWeights& stem, const ConvWeights& c1, cons
   a.tiles_h = (a.Ho + kTH - 1) / kTH;
   a.nchunks = 1;
   a.act = act1;
-  a.post_w = reinterpret_cast<const uint4*>(post.d_w);
+  a.post_w = reinterpret_cast<const uint4*>(post.d_w.p);
   a.post_bias = post.d_b;
   a.post_out = out.ptr + out.coff;
   a.post_out_cs = out.cstride;
@@ -2434,7 +2440,7 @@ int conv_stem_chain_forward(const ConvWeights& stem, const ConvWeights& c1, cons
   a.post_act = act2;
   a.x_out = ext_of(out.ptr, (size_t)N * a.Ho * a.Wo * out.cstride * 2);
   a.x_img = ext_of(f.bgr, (size_t)N * f.src_h * f.src_w * 3);
-  StemArgs st{reinterpret_cast<const uint4*>(stem.d_w), stem.d_b, act0, H, W};
+  StemArgs st{reinterpret_cast<const uint4*>(stem.d_w.p), stem.d_b, act0, H, W};
   FusedSrc fs{f.bgr, f.src_h, f.src_w, f.new_h, f.new_w, f.top, f.left, f.step, f.off};
   static bool attr_set = false;
   if (!attr_set) {
@@ -2493,7 +2499,7 @@ int conv_forward(const ConvWeights& cw, Slice in, int N, int H, int W, Slice out
   }
   ConvArgs a;
   a.in = in.ptr ? in.ptr + in.coff : nullptr;
-  a.wgt = reinterpret_cast<const uint4*>(cw.d_w);
+  a.wgt = reinterpret_cast<const uint4*>(cw.d_w.p);
   a.bias = cw.d_b;
   a.out = out.ptr ? out.ptr + out.coff : nullptr;
   a.out_f32 = out_f32;
@@ -2513,8 +2519,8 @@ int conv_forward(const ConvWeights& cw, Slice in, int N, int H, int W, Slice out
   a.nchunks = cw.nchunks;
   a.act = act;
   a.epi = conv_epi_on() ? 1 : 0;
-  a.post_w = post ? reinterpret_cast<const uint4*>(post->d_w) : nullptr;
-  a.post_bias = post ? post->d_b : nullptr;
+  a.post_w = post ? reinterpret_cast<const uint4*>(post->d_w.p) : nullptr;
+  a.post_bias = post ? post->d_b.p : nullptr;
   a.post_out = post ? a.out : nullptr;  // `out` is the 1x1's output slice
   a.post_out_cs = out.cstride;
   a.post_cout = post ? post->cout : 0;
@@ -2613,15 +2619,14 @@ int eioku_debug_bounds(int* violations, int* line, int reset, int selftest) {
 #ifdef EIOKU_BOUNDS_CHECK
   EIOKU_REQUIRE_INIT();
   if (selftest) {
-    unsigned* buf = nullptr;
-    EIOKU_HIP_CHECK(hipMalloc((void**)&buf, 64));
+    DevBuf<unsigned> buf;
+    EIOKU_TRY(buf.grow(16));
     EIOKU_HIP_CHECK(hipMemset(buf, 0, 64));
     hipLaunchKernelGGL(k_bc_selftest, dim3(1), dim3(1), 0, 0, buf + 4, ext_of(buf + 4, 16), buf + 12);
     EIOKU_LAUNCH_CHECK();
     EIOKU_HIP_CHECK(hipDeviceSynchronize());
     unsigned sink = 1;
     EIOKU_HIP_CHECK(hipMemcpy(&sink, buf + 12, 4, hipMemcpyDeviceToHost));
-    (void)hipFree(buf);
     EIOKU_REQUIRE(sink == 0, "the bounds-check store went through (%u)", sink);
   }
   EIOKU_HIP_CHECK(hipDeviceSynchronize());
@@ -2706,7 +2711,6 @@ int eioku_conv2d_f16(const void* in_nhwc, int n, int h, int w, int in_cstride, i
       rc = EIOKU_EHIP;
     }
   }
-  conv_weights_destroy(&cw);
   return rc;
 }
 

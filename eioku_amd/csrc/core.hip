@@ -13,6 +13,7 @@ thread_local char g_err[512] = "";
 bool g_init = false;
 int g_device = -1;
 int g_cus = 0;
+// raw pointers on purpose: eioku_shutdown frees them; a static destructor would do so after the runtime is gone
 void* g_scratch[kNumSlots] = {};
 size_t g_scratch_bytes[kNumSlots] = {};
 bool g_prof = false;

@@ -27,7 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "conv.h"
+#include "convnet.h"
 
 using namespace eioku;
 
@@ -351,11 +351,6 @@ __global__ __launch_bounds__(256) void k_border(const unsigned* __restrict__ adj
   if (lane == 0) labels[row] = best == INT_MAX ? -1 : best;
 }
 
-struct Layer {
-  std::string name;
-  int cout, cin, k, stride;
-};
-
 struct Block {
   int conv1, conv2, down;  // layer indices (down = -1: identity shortcut)
   int cin, cout, stride;
@@ -366,23 +361,19 @@ struct Block {
 
 struct eioku_iresnet {
   int depths[4] = {};
-  std::vector<Layer> layers;
+  ConvStack convs;
   std::vector<Block> blocks;
-  std::vector<ConvWeights> w;
-  std::vector<bool> set;
-  std::vector<float*> prelu;   // [1 + blocks]: the stem's, then each block's (device, cout floats)
-  std::vector<float*> bn;      // [blocks] x (scale | shift) of each block's leading bn1 (device, 2 x cin floats)
-  __half* fc_w = nullptr;      // [512][25088] fp16, NHWC column order
-  float* fc_b = nullptr;
-  int cap = 0;                 // faces the activation buffers hold
-  __half* crop = nullptr;      // [cap][112][112][8]
-  __half* buf[5] = {};         // [cap][112][112][64] each
-  float* partial = nullptr;    // [kFcSplit][cap][512]
-  float* emb = nullptr;        // [cap][512] (host outputs)
-  uint8_t* src = nullptr;      // staged host frames
-  size_t src_cap = 0;
-  int* taps = nullptr;         // [m][2][112][2] + slot [m]
-  size_t taps_cap = 0;
+  std::vector<DevBuf<float>> prelu;  // [1 + blocks]: the stem's, then each block's (cout floats)
+  std::vector<DevBuf<float>> bn;     // [blocks] x (scale | shift) of each block's leading bn1 (2 x cin floats)
+  DevBuf<__half> fc_w;               // [512][25088] fp16, NHWC column order
+  DevBuf<float> fc_b;
+  // activations, grown to the most faces seen in one pass
+  DevBuf<__half> crop;               // [m][112][112][8]
+  DevBuf<__half> buf[5];             // [m][112][112][64] each
+  DevBuf<float> partial;             // [kFcSplit][m][512]
+  DevBuf<float> emb;                 // [m][512] (host outputs)
+  DevBuf<uint8_t> src;               // staged host frames
+  DevBuf<int> taps;                  // [m][2][112][2] + slot [m]
   std::vector<int> htaps;
   double flops_last = 0;
 };
@@ -390,17 +381,10 @@ struct eioku_iresnet {
 namespace {
 
 int ensure_cap(eioku_iresnet* r, int m) {
-  if (m <= r->cap) return EIOKU_OK;
-  for (void* p : {(void*)r->crop, (void*)r->buf[0], (void*)r->buf[1], (void*)r->buf[2], (void*)r->buf[3], (void*)r->buf[4],
-                  (void*)r->partial, (void*)r->emb})
-    if (p) (void)hipFree(p);
-  r->cap = 0;
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->crop, (size_t)m * kCrop * kCrop * 8 * 2));
-  for (int i = 0; i < 5; ++i) EIOKU_HIP_CHECK(hipMalloc((void**)&r->buf[i], (size_t)m * kCrop * kCrop * 64 * 2));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->partial, (size_t)kFcSplit * m * kFeat * 4));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->emb, (size_t)m * kFeat * 4));
-  r->cap = m;
-  return EIOKU_OK;
+  EIOKU_TRY(r->crop.grow((size_t)m * kCrop * kCrop * 8));
+  for (auto& b : r->buf) EIOKU_TRY(b.grow((size_t)m * kCrop * kCrop * 64));
+  EIOKU_TRY(r->partial.grow((size_t)kFcSplit * m * kFeat));
+  return r->emb.grow((size_t)m * kFeat);
 }
 
 int chan_ops(const __half* in, long long pixels, int C, const float* slope, __half* out_act, const float* bn, __half* out_bn,
@@ -422,13 +406,14 @@ int pick(int a, int b = -1, int c = -1) {
 // the network on r->crop ([m][112][112][8]) -> emb_out [m][512] fp32 (device).  upto_block >= 0: stop after that block
 // and copy its output (NHWC fp16) to act_out instead.
 int run_iresnet(eioku_iresnet* r, int m, int upto_block, void* act_out, float* emb_out, hipStream_t stream) {
-  for (size_t i = 0; i < r->layers.size(); ++i) EIOKU_REQUIRE(r->set[i], "convolution %s has no weights", r->layers[i].name.c_str());
+  EIOKU_TRY(r->convs.all_set());
+  const auto& W = r->convs.w;
   for (size_t i = 0; i < r->prelu.size(); ++i) EIOKU_REQUIRE(r->prelu[i], "PReLU %zu has no slopes", i);
   for (size_t i = 0; i < r->bn.size(); ++i) EIOKU_REQUIRE(r->bn[i], "%s.bn1 has no parameters", r->blocks[i].name.c_str());
   EIOKU_REQUIRE(r->fc_w, "head has no weights");
   double flops = 0;
   int H = kCrop;
-  int rc = conv_forward(r->w[0], Slice{r->crop, 8, 0}, m, H, H, Slice{r->buf[0], 64, 0}, nullptr, Slice{}, kActNone, stream);
+  int rc = conv_forward(W[0], Slice{r->crop, 8, 0}, m, H, H, Slice{r->buf[0], 64, 0}, nullptr, Slice{}, kActNone, stream);
   if (rc) return rc;
   flops += 2.0 * 64 * 3 * 9 * H * H * m;
   rc = chan_ops(r->buf[0], (long long)m * H * H, 64, r->prelu[0], r->buf[0], r->bn[0], r->buf[1], stream);
@@ -438,25 +423,25 @@ int run_iresnet(eioku_iresnet* r, int m, int upto_block, void* act_out, float* e
     const Block& b = r->blocks[bi];
     const int Ho = conv_out_dim(H, 3, b.stride);
     const int u = pick(x, t);
-    rc = conv_forward(r->w[b.conv1], Slice{r->buf[t], b.cin, 0}, m, H, H, Slice{r->buf[u], b.cout, 0}, nullptr, Slice{}, kActNone,
+    rc = conv_forward(W[b.conv1], Slice{r->buf[t], b.cin, 0}, m, H, H, Slice{r->buf[u], b.cout, 0}, nullptr, Slice{}, kActNone,
                       stream);
     if (rc) return rc;
-    flops += r->w[b.conv1].flops_per_pixel() * m * H * H;
+    flops += W[b.conv1].flops_per_pixel() * m * H * H;
     rc = chan_ops(r->buf[u], (long long)m * H * H, b.cout, r->prelu[bi + 1], r->buf[u], nullptr, nullptr, stream);
     if (rc) return rc;
     int res = x;
     if (b.down >= 0) {
       res = pick(x, u);
-      rc = conv_forward(r->w[b.down], Slice{r->buf[x], b.cin, 0}, m, H, H, Slice{r->buf[res], b.cout, 0}, nullptr, Slice{},
+      rc = conv_forward(W[b.down], Slice{r->buf[x], b.cin, 0}, m, H, H, Slice{r->buf[res], b.cout, 0}, nullptr, Slice{},
                         kActNone, stream);
       if (rc) return rc;
       flops += 2.0 * b.cout * b.cin * m * Ho * Ho;  // algorithmic: a 1x1
     }
     const int y = pick(x, u, res);
-    rc = conv_forward(r->w[b.conv2], Slice{r->buf[u], b.cout, 0}, m, H, H, Slice{r->buf[y], b.cout, 0}, nullptr,
+    rc = conv_forward(W[b.conv2], Slice{r->buf[u], b.cout, 0}, m, H, H, Slice{r->buf[y], b.cout, 0}, nullptr,
                       Slice{r->buf[res], b.cout, 0}, kActNone, stream);
     if (rc) return rc;
-    flops += r->w[b.conv2].flops_per_pixel() * m * Ho * Ho;
+    flops += W[b.conv2].flops_per_pixel() * m * Ho * Ho;
     x = y;
     H = Ho;
     if ((int)bi == upto_block) {
@@ -470,10 +455,10 @@ int run_iresnet(eioku_iresnet* r, int m, int upto_block, void* act_out, float* e
       if (rc) return rc;
     }
   }
-  hipLaunchKernelGGL(k_face_fc, dim3(kFeat / 64, (unsigned)((m + 15) / 16), kFcSplit), dim3(256), 0, stream, r->buf[x], m, r->fc_w,
-                     r->partial);
+  hipLaunchKernelGGL(k_face_fc, dim3(kFeat / 64, (unsigned)((m + 15) / 16), kFcSplit), dim3(256), 0, stream, r->buf[x].p, m, r->fc_w.p,
+                     r->partial.p);
   EIOKU_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_face_norm, dim3((unsigned)m), dim3(256), 0, stream, r->partial, m, r->fc_b, emb_out);
+  hipLaunchKernelGGL(k_face_norm, dim3((unsigned)m), dim3(256), 0, stream, r->partial.p, m, r->fc_b.p, emb_out);
   EIOKU_LAUNCH_CHECK();
   flops += 2.0 * kFcK * kFeat * m;
   r->flops_last = flops;
@@ -500,24 +485,6 @@ void axis_taps(double lo, double hi, double side, int size, int* out) {
   }
 }
 
-// frames (host or device) -> r->crop for faces [c0, c0 + mc); all taps are uploaded by the caller (d_taps, d_slot)
-int stage_frames(eioku_iresnet* r, const uint8_t* bgr, int n, int h, int w, int mem, hipStream_t stream, const uint8_t** d_src) {
-  *d_src = bgr;
-  if (mem == EIOKU_MEM_HOST) {
-    const size_t sb = (size_t)n * h * w * 3;
-    if (r->src_cap < sb) {
-      if (r->src) (void)hipFree(r->src);
-      r->src = nullptr;
-      r->src_cap = 0;
-      EIOKU_HIP_CHECK(hipMalloc((void**)&r->src, sb));
-      r->src_cap = sb;
-    }
-    EIOKU_HIP_CHECK(hipMemcpyAsync(r->src, bgr, sb, hipMemcpyHostToDevice, stream));
-    *d_src = r->src;
-  }
-  return EIOKU_OK;
-}
-
 int upload_taps(eioku_iresnet* r, int n, int h, int w, const float* boxes, int m, hipStream_t stream, int** d_taps, int** d_slot) {
   const size_t per = (size_t)4 * kCrop;
   r->htaps.assign(per * m + m, 0);
@@ -535,13 +502,7 @@ int upload_taps(eioku_iresnet* r, int n, int h, int w, const float* boxes, int m
     r->htaps[per * m + i] = slot;
   }
   const size_t tb = r->htaps.size() * 4;
-  if (r->taps_cap < tb) {
-    if (r->taps) (void)hipFree(r->taps);
-    r->taps = nullptr;
-    r->taps_cap = 0;
-    EIOKU_HIP_CHECK(hipMalloc((void**)&r->taps, tb));
-    r->taps_cap = tb;
-  }
+  EIOKU_TRY(r->taps.grow(r->htaps.size()));
   EIOKU_HIP_CHECK(hipMemcpyAsync(r->taps, r->htaps.data(), tb, hipMemcpyHostToDevice, stream));
   *d_taps = r->taps;
   *d_slot = r->taps + per * m;
@@ -555,7 +516,8 @@ int launch_crop(const uint8_t* d_src, int h, int w, const int* d_slot, const int
   return EIOKU_OK;
 }
 
-// DBSCAN workspace: one per process, grown on demand (the 65,536-point bitmask is 512 MiB); calls are serialised
+// DBSCAN workspace: one per process, grown on demand (the 65,536-point bitmask is 512 MiB); calls are serialised.  A raw
+// pointer on purpose: it lives as long as the process, and a static destructor would free it after the runtime is gone
 std::mutex g_db_mu;
 void* g_db_ws = nullptr;
 size_t g_db_bytes = 0;
@@ -569,7 +531,8 @@ int eioku_iresnet_create(const int* depths, eioku_iresnet_t** out) {
   EIOKU_REQUIRE(out && depths, "NULL argument");
   for (int s = 0; s < 4; ++s) EIOKU_REQUIRE(depths[s] >= 1 && depths[s] <= 64, "stage %d depth %d outside [1, 64]", s + 1, depths[s]);
   auto* r = new eioku_iresnet();
-  r->layers.push_back({"conv1", 64, 3, 3, 1});
+  ConvStack& cs = r->convs;
+  cs.add({"conv1", 64, 3, 3, 1});
   const int widths[4] = {64, 128, 256, 512};
   int inplanes = 64;
   for (int s = 0; s < 4; ++s) {
@@ -578,21 +541,16 @@ int eioku_iresnet_create(const int* depths, eioku_iresnet_t** out) {
     for (int b = 0; b < depths[s]; ++b) {
       const std::string p = "layer" + std::to_string(s + 1) + "." + std::to_string(b);
       const int cin = b == 0 ? inplanes : planes, stride = b == 0 ? 2 : 1;
-      Block blk{(int)r->layers.size(), (int)r->layers.size() + 1, -1, cin, planes, stride, p};
-      r->layers.push_back({p + ".conv1", planes, cin, 3, 1});
-      r->layers.push_back({p + ".conv2", planes, planes, 3, stride});
-      if (b == 0) {  // every stage opens with a stride 2: always a downsample branch
-        blk.down = (int)r->layers.size();
-        r->layers.push_back({p + ".downsample.0", planes, cin, 1, 2});
-      }
+      Block blk{cs.size(), cs.size() + 1, -1, cin, planes, stride, p};
+      cs.add({p + ".conv1", planes, cin, 3, 1});
+      cs.add({p + ".conv2", planes, planes, 3, stride});
+      if (b == 0) blk.down = cs.add({p + ".downsample.0", planes, cin, 1, 2});  // every stage opens with a stride 2
       r->blocks.push_back(blk);
     }
     inplanes = planes;
   }
-  r->w.resize(r->layers.size());
-  r->set.assign(r->layers.size(), false);
-  r->prelu.assign(r->blocks.size() + 1, nullptr);
-  r->bn.assign(r->blocks.size(), nullptr);
+  r->prelu.resize(r->blocks.size() + 1);
+  r->bn.resize(r->blocks.size());
   *out = r;
   return EIOKU_OK;
 }
@@ -600,56 +558,29 @@ int eioku_iresnet_create(const int* depths, eioku_iresnet_t** out) {
 void eioku_iresnet_destroy(eioku_iresnet_t* r) {
   if (!r) return;
   (void)hipDeviceSynchronize();
-  for (auto& w : r->w) conv_weights_destroy(&w);
-  for (float* p : r->prelu)
-    if (p) (void)hipFree(p);
-  for (float* p : r->bn)
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)r->fc_w, (void*)r->fc_b, (void*)r->crop, (void*)r->buf[0], (void*)r->buf[1], (void*)r->buf[2],
-                  (void*)r->buf[3], (void*)r->buf[4], (void*)r->partial, (void*)r->emb, (void*)r->src, (void*)r->taps})
-    if (p) (void)hipFree(p);
   delete r;
 }
 
-int eioku_iresnet_num_convs(const eioku_iresnet_t* r) { return r ? (int)r->layers.size() : 0; }
+int eioku_iresnet_num_convs(const eioku_iresnet_t* r) { return r ? r->convs.size() : 0; }
 
 int eioku_iresnet_num_blocks(const eioku_iresnet_t* r) { return r ? (int)r->blocks.size() : 0; }
 
 int eioku_iresnet_conv_info(const eioku_iresnet_t* r, int idx, char* name, size_t cap, int* cout, int* cin, int* ksize,
                             int* stride) {
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size(), "bad convolution index %d", idx);
-  const Layer& l = r->layers[idx];
-  if (name && cap) snprintf(name, cap, "%s", l.name.c_str());
-  if (cout) *cout = l.cout;
-  if (cin) *cin = l.cin;
-  if (ksize) *ksize = l.k;
-  if (stride) *stride = l.stride;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(r, "bad convolution index %d", idx);
+  return r->convs.info(idx, name, cap, cout, cin, ksize, stride);
 }
 
 // weight HOST fp32 [cout][cin][k][k] with the following BatchNorm folded in, bias HOST fp32 [cout]
 int eioku_iresnet_set_conv(eioku_iresnet_t* r, int idx, const float* w, const float* b) {
   EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size() && w && b, "bad argument");
-  const Layer& l = r->layers[idx];
-  conv_weights_destroy(&r->w[idx]);
-  int rc;
-  if (idx == 0) {  // stem: 3 -> 8 input channels (the crop's zero channels get zero weights)
-    std::vector<float> w8((size_t)64 * 8 * 9, 0.f);
-    for (int co = 0; co < 64; ++co)
-      for (int ci = 0; ci < 3; ++ci)
-        for (int t = 0; t < 9; ++t) w8[((size_t)co * 8 + ci) * 9 + t] = w[((size_t)co * 3 + ci) * 9 + t];
-    rc = conv_weights_create(&r->w[idx], 64, 8, 3, 1, w8.data(), b);
-  } else if (l.k == 1) {  // stride-2 1x1 -> 3x3 / s2 with the weights on the centre tap
-    std::vector<float> w3((size_t)l.cout * l.cin * 9, 0.f);
-    for (size_t i = 0; i < (size_t)l.cout * l.cin; ++i) w3[i * 9 + 4] = w[i];
-    rc = conv_weights_create(&r->w[idx], l.cout, l.cin, 3, l.stride, w3.data(), b);
-  } else {
-    rc = conv_weights_create(&r->w[idx], l.cout, l.cin, l.k, l.stride, w, b);
-  }
-  if (rc) return rc;
-  r->set[idx] = true;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(r && idx >= 0 && idx < r->convs.size() && w && b, "bad argument");
+  const ConvLayer& l = r->convs.layers[idx];
+  ConvWeights* cw = &r->convs.w[idx];
+  // the stem reads the crop's 8 channels; a stride-2 1x1 runs as a 3x3 / s2 with the weights on the centre tap
+  return r->convs.mark(idx, idx == 0   ? conv_weights_create_cin8(cw, l.cout, l.cin, l.k, l.stride, w, b)
+                            : l.k == 1 ? conv_weights_create_centre(cw, l.cout, l.cin, l.stride, w, b)
+                                       : conv_weights_create(cw, l.cout, l.cin, l.k, l.stride, w, b));
 }
 
 // unit 0: the stem's PReLU (64 slopes); unit 1 + b: block b's PReLU (its cout slopes).  HOST fp32.
@@ -657,9 +588,7 @@ int eioku_iresnet_set_prelu(eioku_iresnet_t* r, int unit, const float* slope) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(r && slope && unit >= 0 && unit <= (int)r->blocks.size(), "bad PReLU unit %d", unit);
   const int c = unit == 0 ? 64 : r->blocks[unit - 1].cout;
-  if (!r->prelu[unit]) EIOKU_HIP_CHECK(hipMalloc((void**)&r->prelu[unit], (size_t)c * 4));
-  EIOKU_HIP_CHECK(hipMemcpy(r->prelu[unit], slope, (size_t)c * 4, hipMemcpyHostToDevice));
-  return EIOKU_OK;
+  return r->prelu[unit].upload(slope, (size_t)c);
 }
 
 // block b's leading bn1 as y = x * scale + shift per input channel (HOST fp32, cin each)
@@ -667,7 +596,7 @@ int eioku_iresnet_set_bn(eioku_iresnet_t* r, int block, const float* scale, cons
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(r && scale && shift && block >= 0 && block < (int)r->blocks.size(), "bad block %d", block);
   const int c = r->blocks[block].cin;
-  if (!r->bn[block]) EIOKU_HIP_CHECK(hipMalloc((void**)&r->bn[block], (size_t)c * 8));
+  EIOKU_TRY(r->bn[block].grow((size_t)c * 2));
   EIOKU_HIP_CHECK(hipMemcpy(r->bn[block], scale, (size_t)c * 4, hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(r->bn[block] + c, shift, (size_t)c * 4, hipMemcpyHostToDevice));
   return EIOKU_OK;
@@ -680,11 +609,8 @@ int eioku_iresnet_set_head(eioku_iresnet_t* r, const float* w, const float* b) {
   EIOKU_REQUIRE(r && w && b, "bad argument");
   std::vector<_Float16> hw((size_t)kFeat * kFcK);
   for (size_t i = 0; i < hw.size(); ++i) hw[i] = (_Float16)w[i];
-  if (!r->fc_w) EIOKU_HIP_CHECK(hipMalloc((void**)&r->fc_w, hw.size() * 2));
-  if (!r->fc_b) EIOKU_HIP_CHECK(hipMalloc((void**)&r->fc_b, kFeat * 4));
-  EIOKU_HIP_CHECK(hipMemcpy(r->fc_w, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
-  EIOKU_HIP_CHECK(hipMemcpy(r->fc_b, b, kFeat * 4, hipMemcpyHostToDevice));
-  return EIOKU_OK;
+  EIOKU_TRY(r->fc_w.upload(reinterpret_cast<const __half*>(hw.data()), hw.size()));
+  return r->fc_b.upload(b, kFeat);
 }
 
 // K13a alone (parity helper): n BGR u8 frames (h x w; host or device per mem), boxes HOST fp32 [m][5] = (frame slot, x1,
@@ -701,7 +627,7 @@ int eioku_iresnet_crop(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int
   int rc = upload_taps(r, n, h, w, boxes, m, stream, &d_taps, &d_slot);
   if (rc) return rc;
   const uint8_t* d_src;
-  rc = stage_frames(r, bgr, n, h, w, mem, stream, &d_src);
+  rc = stage_host(r->src, bgr, (size_t)n * h * w * 3, mem, stream, &d_src);
   if (rc) return rc;
   rc = launch_crop(d_src, h, w, d_slot, d_taps, m, (__half*)out_f16, stream);
   if (rc) return rc;
@@ -743,7 +669,7 @@ int eioku_iresnet_embed(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, in
   int rc = upload_taps(r, n, h, w, boxes, m, stream, &d_taps, &d_slot);
   if (rc) return rc;
   const uint8_t* d_src;
-  rc = stage_frames(r, bgr, n, h, w, mem, stream, &d_src);
+  rc = stage_host(r->src, bgr, (size_t)n * h * w * 3, mem, stream, &d_src);
   if (rc) return rc;
   rc = ensure_cap(r, std::min(m, kChunk));
   if (rc) return rc;

@@ -1230,33 +1230,28 @@ __global__ __launch_bounds__(256) void k_remove_ids(const long long* __restrict_
 // ---------------------------------------------------------------------------------------------
 struct eioku_index {
   int d = 0;
-  long long n = 0, cap = 0;
-  float* x = nullptr;      // owned unless attached
-  float* norms = nullptr;  // owned
-  long long norms_cap = 0;
+  long long n = 0;
+  DevBuf<float> x_own;     // the rows, unless attached
+  float* x = nullptr;      // x_own, or the attached buffer
+  DevBuf<float> norms;
   bool attached = false;
+  long long cap() const { return attached ? n : (long long)(x_own.cap / d); }  // rows x holds
   // search workspace
-  float* qbuf = nullptr; size_t qcap = 0;
-  float* qnorm = nullptr; size_t qncap = 0;
-  float* pd = nullptr; size_t pdcap = 0;
-  int* pi = nullptr; size_t picap = 0;
-  float* dout = nullptr; size_t dcap = 0;
-  long long* iout = nullptr; size_t icap = 0;
+  DevBuf<float> qbuf, qnorm, pd, dout;
+  DevBuf<int> pi;
+  DevBuf<long long> iout;
   // scan path (see k_l2_scan): fragment-tiled bf16 plane of the rows, built lazily and extended on add()
-  unsigned char* xh = nullptr; size_t xhcap = 0;
-  float* hnorm = nullptr; size_t hncap = 0;
-  float* tmax = nullptr; size_t tmcap = 0;
-  float* xmax = nullptr;  // [1] max |x| over all rows (the norm-proportional slack of the scan's bound)
+  DevBuf<unsigned char> xh;
+  DevBuf<float> hnorm, tmax;
+  DevBuf<float> xmax;          // [1] max |x| over all rows (the norm-proportional slack of the scan's bound)
   long long planes_n = 0;      // rows covered by the plane
-  unsigned char* qh = nullptr; size_t qhcap = 0;
-  unsigned* wl = nullptr; size_t wlcap = 0;
-  int* wl_cnt = nullptr; size_t wlccap = 0;
-  float* tau = nullptr; size_t taucap = 0;
-  long long* tau_i = nullptr; size_t tauicap = 0;
-  float* tau1 = nullptr; size_t tau1cap = 0;       // the strided pre-scan's exact top-k (its last column tightens tau)
-  long long* tau1_i = nullptr; size_t tau1icap = 0;
-  int* cand_i = nullptr; size_t cicap = 0;
-  int* cnt = nullptr; size_t cntcap = 0;  // [nq] counters + 1 overflow word
+  DevBuf<unsigned char> qh;
+  DevBuf<unsigned> wl;
+  DevBuf<int> wl_cnt;
+  DevBuf<float> tau, tau1;     // tau1: the strided pre-scan's exact top-k (its last column tightens tau)
+  DevBuf<long long> tau_i, tau1_i;
+  DevBuf<int> cand_i;
+  DevBuf<int> cnt;             // [nq] counters + 1 overflow word
   // parameters (eioku_index_set_param)
   int scan_mode = 1;           // 0: register-tile kernels only; 1: scan path for wide searches over large indexes
   int scan_cap = 4096;         // candidate slots per query
@@ -1269,34 +1264,20 @@ struct eioku_index {
   int scan_prescan = 32;       // stride of the pre-scan's row tiles (0: no pre-scan, the sample alone bounds the scan)
   int scan_rt = 2;             // row tiles per wave: 2 (8 waves per workgroup; 2-3 % faster at 10 M x 384) or 1 (12 waves)
   // K9f: removal and row selectors
-  unsigned* live = nullptr; size_t live_words = 0;  // NULL until the first removal: every row is live
-  int* removed_dev = nullptr;                       // [1] rows removed so far
-  long long removed = 0;                            // its host copy (eioku_index_remove_ids drains the stream)
-  long long* idbuf = nullptr; size_t idcap = 0;     // staged host ids
-  unsigned* selbuf = nullptr; size_t selcap = 0;    // staged host selector
-  unsigned* ew = nullptr; size_t ewcap = 0;         // effective words of the running search
-  int* tlist = nullptr; size_t tlcap = 0;           // its non-empty tiles
-  int* bcount = nullptr; size_t bccap = 0;
-  int* meta = nullptr;                              // [4] {entries, gate of the tile-list route, gate of the masked route}
+  DevBuf<unsigned> live;       // empty until the first removal: every row is live
+  DevBuf<int> removed_dev;     // [1] rows removed so far
+  long long removed = 0;       // its host copy (eioku_index_remove_ids drains the stream)
+  DevBuf<long long> idbuf;     // staged host ids
+  DevBuf<unsigned> selbuf;     // staged host selector
+  DevBuf<unsigned> ew;         // effective words of the running search
+  DevBuf<int> tlist;           // its non-empty tiles
+  DevBuf<int> bcount;
+  DevBuf<int> meta;            // [4] {entries, gate of the tile-list route, gate of the masked route}
   int sel_list_ppm = 32000;    // tile-list route when non-empty tiles * 1e6 <= sel_list_ppm * tiles: the crossover of
                                // profiles/knn_filtered.json at 10 M x 384 (DESIGN.md K9f has the table)
 };
 
 namespace {
-
-template <typename T>
-int grow(T** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return EIOKU_OK;
-  if (*p) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
-  EIOKU_HIP_CHECK(hipMalloc((void**)p, bytes));
-  *cap = bytes;
-  return EIOKU_OK;
-}
 
 int norms_for(const float* x, long long n, int d, float* out, hipStream_t stream) {
   if (n == 0) return EIOKU_OK;
@@ -1354,12 +1335,6 @@ int eioku_index_flat_create(int d, eioku_index** out) {
 void eioku_index_destroy(eioku_index* ix) {
   if (!ix) return;
   (void)hipDeviceSynchronize();
-  if (ix->x && !ix->attached) (void)hipFree(ix->x);
-  void* bufs[] = {ix->norms, ix->qbuf, ix->qnorm, ix->pd, ix->pi, ix->dout, ix->iout, ix->xh, ix->hnorm,
-                  ix->tmax, ix->xmax, ix->qh, ix->wl, ix->wl_cnt, ix->tau, ix->tau_i, ix->tau1, ix->tau1_i, ix->cand_i, ix->cnt,
-                  ix->live, ix->removed_dev, ix->idbuf, ix->selbuf, ix->ew, ix->tlist, ix->bcount, ix->meta};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
   delete ix;
 }
 
@@ -1375,9 +1350,7 @@ namespace {
 void forget_removals(eioku_index* ix) {
   if (ix->live) {
     (void)hipDeviceSynchronize();
-    (void)hipFree(ix->live);
-    ix->live = nullptr;
-    ix->live_words = 0;
+    ix->live.reset();
   }
   ix->removed = 0;
 }
@@ -1392,7 +1365,6 @@ int eioku_index_reset(eioku_index* ix) {
   if (ix->attached) {
     ix->x = nullptr;
     ix->attached = false;
-    ix->cap = 0;
   }
   ix->n = 0;
   ix->planes_n = 0;
@@ -1407,48 +1379,32 @@ int eioku_index_add(eioku_index* ix, const float* x, long long n, int mem, void*
   if (n == 0) return EIOKU_OK;
   hipStream_t stream = (hipStream_t)stream_;
   const long long need = ix->n + n;
-  if (need > ix->cap) {
-    long long ncap = ix->cap ? ix->cap : 1024;
+  if (need > ix->cap()) {
+    long long ncap = ix->cap() ? ix->cap() : 1024;
     while (ncap < need) ncap *= 2;
     // Earlier add() calls queued their copy + norms kernel on the caller's stream, which may be a
     // non-blocking one the NULL stream does not wait for: move the old rows ON that stream and drain it
     // before the old buffers are freed (a blocking hipMemcpy here could read rows that have not landed).
-    float* nx = nullptr;
-    float* nn = nullptr;
-    EIOKU_HIP_CHECK(hipMalloc((void**)&nx, (size_t)ncap * ix->d * sizeof(float)));
-    if (hipMalloc((void**)&nn, (size_t)ncap * sizeof(float)) != hipSuccess) {
-      (void)hipFree(nx);
-      set_error("hipMalloc of %lld norms failed", ncap);
-      return EIOKU_ENOMEM;
-    }
+    DevBuf<float> nx, nn;
+    DevBuf<unsigned> nl;
+    EIOKU_TRY(nx.grow((size_t)ncap * ix->d));
+    EIOKU_TRY(nn.grow((size_t)ncap));
     if (ix->n) {
       EIOKU_HIP_CHECK(hipMemcpyAsync(nx, ix->x, (size_t)ix->n * ix->d * sizeof(float), hipMemcpyDeviceToDevice, stream));
       EIOKU_HIP_CHECK(hipMemcpyAsync(nn, ix->norms, (size_t)ix->n * sizeof(float), hipMemcpyDeviceToDevice, stream));
     }
-    unsigned* nl = nullptr;
-    const size_t nlw = (size_t)((ncap + 31) / 32);
     if (ix->live) {  // rows were removed: the live words grow with the rows, new rows are live (bits beyond n stay set)
-      if (hipMalloc((void**)&nl, nlw * sizeof(unsigned)) != hipSuccess) {
-        (void)hipFree(nx);
-        (void)hipFree(nn);
-        set_error("hipMalloc of %zu live words failed", nlw);
-        return EIOKU_ENOMEM;
-      }
+      const size_t nlw = (size_t)((ncap + 31) / 32);
+      EIOKU_TRY(nl.grow(nlw));
       EIOKU_HIP_CHECK(hipMemsetAsync(nl, 0xFF, nlw * sizeof(unsigned), stream));
-      EIOKU_HIP_CHECK(hipMemcpyAsync(nl, ix->live, ix->live_words * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+      EIOKU_HIP_CHECK(hipMemcpyAsync(nl, ix->live, ix->live.cap * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
     }
     EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
-    if (ix->x) (void)hipFree(ix->x);
-    if (ix->norms) (void)hipFree(ix->norms);
-    if (nl) {
-      (void)hipFree(ix->live);
-      ix->live = nl;
-      ix->live_words = nlw;
-    }
-    ix->x = nx;
-    ix->norms = nn;
-    ix->norms_cap = ncap;
-    ix->cap = ncap;
+    // the old buffers leave with nx, nn and nl
+    ix->x_own = std::move(nx);
+    ix->norms = std::move(nn);
+    if (nl) ix->live = std::move(nl);
+    ix->x = ix->x_own;
   }
   float* dst = ix->x + (size_t)ix->n * ix->d;
   EIOKU_HIP_CHECK(hipMemcpyAsync(dst, x, (size_t)n * ix->d * sizeof(float),
@@ -1464,19 +1420,13 @@ int eioku_index_attach(eioku_index* ix, float* x_dev, long long n, void* stream_
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(ix && x_dev && n >= 0, "bad argument");
   EIOKU_REQUIRE(((uintptr_t)x_dev & 15) == 0, "attached buffer must be 16-byte aligned");
-  if (ix->x && !ix->attached) (void)hipFree(ix->x);
+  ix->x_own.reset();
   forget_removals(ix);
   ix->x = x_dev;
   ix->attached = true;
   ix->n = n;
-  ix->cap = n;
   ix->planes_n = 0;  // rebuilt by the next wide search
-  if (ix->norms_cap < n) {
-    if (ix->norms) (void)hipFree(ix->norms);
-    ix->norms = nullptr;
-    EIOKU_HIP_CHECK(hipMalloc((void**)&ix->norms, (size_t)(n ? n : 1) * sizeof(float)));
-    ix->norms_cap = n;
-  }
+  EIOKU_TRY(ix->norms.grow((size_t)n));
   return norms_for(x_dev, n, ix->d, ix->norms, (hipStream_t)stream_);
 }
 
@@ -1530,9 +1480,9 @@ int legacy_search(eioku_index* ix, const float* dq, int nq, int k, const float* 
   }
   EIOKU_REQUIRE(rpb < (1ll << 31), "slab too large");
   const size_t pn = (size_t)ygroups * (wide ? kWaves : 1) * slabs * kQT * K;
-  int rc = grow(&ix->pd, &ix->pdcap, pn * sizeof(float));
+  int rc = grow_synced(ix->pd, pn);
   if (rc) return rc;
-  rc = grow(&ix->pi, &ix->picap, pn * sizeof(int));
+  rc = grow_synced(ix->pi, pn);
   if (rc) return rc;
   KnnArgs a;
   a.db = ix->x;
@@ -1615,20 +1565,18 @@ int split_planes(int d, const float* x, long long n, long long first_tile, long 
 
 // a buffer that keeps its contents when it grows (the plane is extended on add())
 template <typename T>
-int grow_keep(T** p, size_t* cap, size_t bytes, size_t keep, hipStream_t stream) {
-  if (*cap >= bytes) return EIOKU_OK;
-  size_t want = *cap ? *cap : bytes;
-  while (want < bytes) want += want / 2 + 1;
-  T* np = nullptr;
-  EIOKU_HIP_CHECK(hipMalloc((void**)&np, want));
-  if (*p) {
-    if (keep) EIOKU_HIP_CHECK(hipMemcpyAsync(np, *p, keep, hipMemcpyDeviceToDevice, stream));
+int grow_keep(DevBuf<T>& b, size_t n, size_t keep, hipStream_t stream) {
+  if (b.cap >= n) return EIOKU_OK;
+  size_t want = b.cap ? b.cap : n;
+  while (want < n) want += want / 2 + 1;
+  DevBuf<T> nb;
+  EIOKU_TRY(nb.grow(want));
+  if (b) {
+    if (keep) EIOKU_HIP_CHECK(hipMemcpyAsync(nb, b, keep * sizeof(T), hipMemcpyDeviceToDevice, stream));
     EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
     (void)hipDeviceSynchronize();
-    (void)hipFree(*p);
   }
-  *p = np;
-  *cap = want;
+  b = std::move(nb);  // the old memory leaves with nb
   return EIOKU_OK;
 }
 
@@ -1651,16 +1599,13 @@ int ensure_planes(eioku_index* ix, hipStream_t stream) {
   const size_t tile_b = (size_t)d * 32 * 2;  // bytes per 32-row tile
   const long long ntiles = (ix->n + 31) / 32;
   const long long keep_tiles = ix->planes_n / 32;  // complete tiles stay valid
-  int rc = grow_keep(&ix->xh, &ix->xhcap, (size_t)ntiles * tile_b, (size_t)keep_tiles * tile_b, stream);
-  if (rc) return rc;
-  rc = grow_keep(&ix->hnorm, &ix->hncap, (size_t)ntiles * 32 * sizeof(float), (size_t)keep_tiles * 32 * sizeof(float), stream);
-  if (rc) return rc;
-  rc = grow_keep(&ix->tmax, &ix->tmcap, (size_t)ntiles * sizeof(float), (size_t)keep_tiles * sizeof(float), stream);
-  if (rc) return rc;
+  EIOKU_TRY(grow_keep(ix->xh, (size_t)ntiles * tile_b, (size_t)keep_tiles * tile_b, stream));
+  EIOKU_TRY(grow_keep(ix->hnorm, (size_t)ntiles * 32, (size_t)keep_tiles * 32, stream));
+  EIOKU_TRY(grow_keep(ix->tmax, (size_t)ntiles, (size_t)keep_tiles, stream));
   if (ix->planes_n != ix->n) {
-    rc = split_planes(d, ix->x, ix->n, keep_tiles, ntiles - keep_tiles, ix->norms, ix->xh, ix->hnorm, ix->tmax, false, stream);
+    int rc = split_planes(d, ix->x, ix->n, keep_tiles, ntiles - keep_tiles, ix->norms, ix->xh, ix->hnorm, ix->tmax, false, stream);
     if (rc) return rc;
-    if (!ix->xmax) EIOKU_HIP_CHECK(hipMalloc((void**)&ix->xmax, sizeof(float)));
+    EIOKU_TRY(ix->xmax.grow(1));
     hipLaunchKernelGGL(k_max_f32, dim3(1), dim3(1024), 0, stream, ix->tmax, ntiles, ix->xmax);
     EIOKU_LAUNCH_CHECK();
     ix->planes_n = ix->n;
@@ -1689,9 +1634,9 @@ int launch_scan(eioku_index* ix, ScanArgs& a, int rt, long long* grid_out, hipSt
   long long wl_cap = ((64ll << 20) / 8) / grid;
   if (wl_cap > (1 << 20)) wl_cap = 1 << 20;
   if (ix->scan_cap < 256) wl_cap = ix->scan_cap;  // tests shrink both kinds of list to force the overflow paths
-  int rc = grow(&ix->wl, &ix->wlcap, (size_t)grid * wl_cap * 8);
+  int rc = grow_synced(ix->wl, (size_t)grid * wl_cap * 2);
   if (rc) return rc;
-  rc = grow(&ix->wl_cnt, &ix->wlccap, (size_t)grid * sizeof(int));
+  rc = grow_synced(ix->wl_cnt, (size_t)grid);
   if (rc) return rc;
   a.wl = ix->wl;
   a.wl_cnt = ix->wl_cnt;
@@ -1725,16 +1670,16 @@ int scan_search(eioku_index* ix, const float* dq, int nq, int k, float* dD, long
   int rc = ensure_planes(ix, stream);
   if (rc) return rc;
   const int nqt = (nq + 31) / 32;
-  rc = grow(&ix->qh, &ix->qhcap, (size_t)nqt * d * 32 * 2);
+  rc = grow_synced(ix->qh, (size_t)nqt * d * 32 * 2);
   if (rc) return rc;
-  rc = grow(&ix->tau, &ix->taucap, (size_t)nq * k * sizeof(float));
+  rc = grow_synced(ix->tau, (size_t)nq * k);
   if (rc) return rc;
-  rc = grow(&ix->tau_i, &ix->tauicap, (size_t)nq * k * sizeof(long long));
+  rc = grow_synced(ix->tau_i, (size_t)nq * k);
   if (rc) return rc;
   const int cap = ix->scan_cap;
-  rc = grow(&ix->cand_i, &ix->cicap, (size_t)nq * cap * sizeof(int));
+  rc = grow_synced(ix->cand_i, (size_t)nq * cap);
   if (rc) return rc;
-  rc = grow(&ix->cnt, &ix->cntcap, ((size_t)nq + 1) * sizeof(int));
+  rc = grow_synced(ix->cnt, (size_t)nq + 1);
   if (rc) return rc;
   int* overflow = ix->cnt + nq;
   EIOKU_HIP_CHECK(hipMemsetAsync(ix->cnt, 0, ((size_t)nq + 1) * sizeof(int), stream));
@@ -1765,11 +1710,11 @@ int scan_search(eioku_index* ix, const float* dq, int nq, int k, float* dD, long
   rc = legacy_search(ix, dq, nq, k, nullptr, nullptr, ix->tau, ix->tau_i, nullptr, sslabs, srows, false, stream);
   if (rc) return rc;
   ScanArgs a;
-  a.xh = (const u32x4k*)ix->xh;
+  a.xh = (const u32x4k*)ix->xh.p;
   a.hnorm = ix->hnorm;
   a.tmax = ix->tmax;
   a.xmax = ix->xmax;
-  a.qh = (const u32x4k*)ix->qh;
+  a.qh = (const u32x4k*)ix->qh.p;
   a.qnorm = ix->qnorm;
   a.tau = ix->tau;
   a.tau_k = k;
@@ -1799,9 +1744,9 @@ int scan_search(eioku_index* ix, const float* dq, int nq, int k, float* dD, long
     }
   };
   if (stride > 0) {
-    rc = grow(&ix->tau1, &ix->tau1cap, (size_t)nq * k * sizeof(float));
+    rc = grow_synced(ix->tau1, (size_t)nq * k);
     if (rc) return rc;
-    rc = grow(&ix->tau1_i, &ix->tau1icap, (size_t)nq * k * sizeof(long long));
+    rc = grow_synced(ix->tau1_i, (size_t)nq * k);
     if (rc) return rc;
     // a pre-scan list that overflows is merely truncated: the k best of the entries that did fit are k real rows, so
     // their k-th distance is still a valid bound (fewer than k entries: FLT_MAX, and the sample's bound stands).  Its
@@ -1825,18 +1770,18 @@ int prepare_selector(eioku_index* ix, const unsigned* sel, int sel_mem, hipStrea
   int rc;
   const unsigned* dsel = sel;
   if (sel_mem == EIOKU_MEM_HOST) {
-    rc = grow(&ix->selbuf, &ix->selcap, (size_t)nwords * sizeof(unsigned));
+    rc = grow_synced(ix->selbuf, (size_t)nwords);
     if (rc) return rc;
     EIOKU_HIP_CHECK(hipMemcpyAsync(ix->selbuf, sel, (size_t)nwords * sizeof(unsigned), hipMemcpyHostToDevice, stream));
     dsel = ix->selbuf;
   }
-  rc = grow(&ix->ew, &ix->ewcap, (size_t)nwords * sizeof(unsigned));
+  rc = grow_synced(ix->ew, (size_t)nwords);
   if (rc) return rc;
-  rc = grow(&ix->tlist, &ix->tlcap, (size_t)nwords * sizeof(int));
+  rc = grow_synced(ix->tlist, (size_t)nwords);
   if (rc) return rc;
-  rc = grow(&ix->bcount, &ix->bccap, (size_t)nblocks * sizeof(int));
+  rc = grow_synced(ix->bcount, (size_t)nblocks);
   if (rc) return rc;
-  if (!ix->meta) EIOKU_HIP_CHECK(hipMalloc((void**)&ix->meta, 4 * sizeof(int)));
+  EIOKU_TRY(ix->meta.grow(4));
   hipLaunchKernelGGL(k_sel_words, dim3(nblocks), dim3(1024), 0, stream, dsel, (const unsigned*)ix->live, ix->n, nwords, ix->ew,
                      ix->bcount);
   EIOKU_LAUNCH_CHECK();
@@ -1865,12 +1810,12 @@ int search_impl(eioku_index* ix, const float* q, int nq, int k, const float* lbD
   if (mem == EIOKU_MEM_HOST) {
     const size_t qb = (((size_t)nq * d * sizeof(float)) + 255) & ~(size_t)255;
     const size_t lb = lbD ? (size_t)nq * (sizeof(float) + sizeof(long long)) + 256 : 0;
-    rc = grow(&ix->qbuf, &ix->qcap, qb + lb);
+    rc = grow_synced(ix->qbuf, (qb + lb) / sizeof(float));
     if (rc) return rc;
     EIOKU_HIP_CHECK(hipMemcpyAsync(ix->qbuf, q, (size_t)nq * d * sizeof(float), hipMemcpyHostToDevice, stream));
     dq = ix->qbuf;
     if (lbD) {
-      long long* li = (long long*)((unsigned char*)ix->qbuf + qb);
+      long long* li = (long long*)((unsigned char*)ix->qbuf.p + qb);
       float* ld = (float*)(li + nq);
       EIOKU_HIP_CHECK(hipMemcpyAsync(li, lbI, (size_t)nq * sizeof(long long), hipMemcpyHostToDevice, stream));
       EIOKU_HIP_CHECK(hipMemcpyAsync(ld, lbD, (size_t)nq * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -1879,16 +1824,16 @@ int search_impl(eioku_index* ix, const float* q, int nq, int k, const float* lbD
     }
   }
   EIOKU_REQUIRE(((uintptr_t)dq & 15) == 0, "queries must be 16-byte aligned");
-  rc = grow(&ix->qnorm, &ix->qncap, (size_t)nq * sizeof(float));
+  rc = grow_synced(ix->qnorm, (size_t)nq);
   if (rc) return rc;
   rc = norms_for(dq, nq, d, ix->qnorm, stream);
   if (rc) return rc;
   float* dD = D;
   long long* dI = (long long*)I;
   if (mem == EIOKU_MEM_HOST) {
-    rc = grow(&ix->dout, &ix->dcap, (size_t)nq * k * sizeof(float));
+    rc = grow_synced(ix->dout, (size_t)nq * k);
     if (rc) return rc;
-    rc = grow(&ix->iout, &ix->icap, (size_t)nq * k * sizeof(long long));
+    rc = grow_synced(ix->iout, (size_t)nq * k);
     if (rc) return rc;
     dD = ix->dout;
     dI = ix->iout;
@@ -1963,17 +1908,16 @@ int eioku_index_remove_ids(eioku_index* ix, const int64_t* ids, long long n_ids,
   if (n_ids == 0 || ix->n == 0) return EIOKU_OK;
   hipStream_t stream = (hipStream_t)stream_;
   if (!ix->live) {
-    const long long rows = ix->cap > ix->n ? ix->cap : ix->n;
+    const long long rows = ix->cap() > ix->n ? ix->cap() : ix->n;
     const size_t words = (size_t)((rows + 31) / 32);
-    EIOKU_HIP_CHECK(hipMalloc((void**)&ix->live, words * sizeof(unsigned)));
-    ix->live_words = words;
+    EIOKU_TRY(ix->live.grow(words));
     EIOKU_HIP_CHECK(hipMemsetAsync(ix->live, 0xFF, words * sizeof(unsigned), stream));
   }
-  if (!ix->removed_dev) EIOKU_HIP_CHECK(hipMalloc((void**)&ix->removed_dev, sizeof(int)));
+  EIOKU_TRY(ix->removed_dev.grow(1));
   EIOKU_HIP_CHECK(hipMemsetAsync(ix->removed_dev, 0, sizeof(int), stream));
   const long long* dids = (const long long*)ids;
   if (mem == EIOKU_MEM_HOST) {
-    int rc = grow(&ix->idbuf, &ix->idcap, (size_t)n_ids * sizeof(long long));
+    int rc = grow_synced(ix->idbuf, (size_t)n_ids);
     if (rc) return rc;
     EIOKU_HIP_CHECK(hipMemcpyAsync(ix->idbuf, ids, (size_t)n_ids * sizeof(long long), hipMemcpyHostToDevice, stream));
     dids = ix->idbuf;

@@ -29,7 +29,7 @@
 #include <string>
 #include <vector>
 
-#include "conv.h"
+#include "convnet.h"
 
 using namespace eioku;
 
@@ -312,29 +312,6 @@ __global__ __launch_bounds__(256) void k_ctc_probs(const float* __restrict__ log
 
 int grid1(long long work) { return (int)((work + 255) / 256); }
 
-struct Layer {
-  std::string name;
-  int cout, cin, k;
-};
-
-template <typename T>
-int grow(T** p, size_t* cap, size_t n) {
-  if (n <= *cap) return EIOKU_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  EIOKU_HIP_CHECK(hipMalloc((void**)p, n * sizeof(T)));
-  *cap = n;
-  return EIOKU_OK;
-}
-
-// n floats HOST -> *dst (device, allocated on first use; the size of a given slot never changes)
-int upload_f32(float** dst, const float* src, size_t n) {
-  if (!*dst) EIOKU_HIP_CHECK(hipMalloc((void**)dst, n * 4));
-  EIOKU_HIP_CHECK(hipMemcpy(*dst, src, n * 4, hipMemcpyHostToDevice));
-  return EIOKU_OK;
-}
-
 int gemm_f32(const float* A, int M, int K, const float* W, int N, const float* bias, float* Cout, hipStream_t st, double* fl) {
   if (M == 0) return EIOKU_OK;
   hipLaunchKernelGGL(k_gemm_f32, dim3((unsigned)((N + 63) / 64), (unsigned)((M + 15) / 16)), dim3(256), 0, st, A, M, K, W, N, bias,
@@ -348,17 +325,11 @@ int gemm_f32(const float* A, int M, int K, const float* W, int N, const float* b
 
 // ---- K15: CRAFT --------------------------------------------------------------------------------------------------
 struct eioku_craft {
-  std::vector<Layer> layers;
-  std::vector<ConvWeights> w;
-  std::vector<bool> set;
-  __half *in8 = nullptr, *p0 = nullptr, *p1 = nullptr, *cat1 = nullptr, *cat2 = nullptr, *cat3 = nullptr, *cat4 = nullptr,
-         *col = nullptr;
-  float* y = nullptr;
-  size_t c_in8 = 0, c_p0 = 0, c_p1 = 0, c_cat1 = 0, c_cat2 = 0, c_cat3 = 0, c_cat4 = 0, c_col = 0, c_y = 0;
-  uint8_t* src = nullptr;
-  size_t c_src = 0;
-  int* taps = nullptr;
-  size_t c_taps = 0;
+  ConvStack convs;
+  DevBuf<__half> in8, p0, p1, cat1, cat2, cat3, cat4, col;
+  DevBuf<float> y;
+  DevBuf<uint8_t> src;  // staged host frames
+  DevBuf<int> taps;
   std::vector<int> htaps;
   double flops_last = 0;
 };
@@ -366,20 +337,16 @@ struct eioku_craft {
 // ---- K16: CRNN ---------------------------------------------------------------------------------------------------
 struct eioku_crnn {
   int num_class = 0;
-  std::vector<Layer> layers;  // 7 VGG convs + "Prediction"
-  std::vector<ConvWeights> w;
-  std::vector<bool> set;
-  // fp32, device, PyTorch layouts: per BiLSTM layer the input projection [2 * 1024][256] + (b_ih + b_hh) and the
-  // Linear [256][512] + bias; Prediction [num_class][256] + bias
-  float *wih[2] = {}, *bih[2] = {}, *wlin[2] = {}, *blin[2] = {}, *wpred = nullptr, *bpred = nullptr;
-  float* whh[2] = {};          // [2][256][1024] transposed
+  ConvStack convs;  // 7 VGG convs + "Prediction"
+  // fp32, PyTorch layouts: per BiLSTM layer the input projection [2 * 1024][256] + (b_ih + b_hh) and the Linear [256][512]
+  // + bias; Prediction [num_class][256] + bias
+  DevBuf<float> wih[2], bih[2], wlin[2], blin[2], wpred, bpred;
+  DevBuf<float> whh[2];  // [2][256][1024] transposed
   bool lstm_set[2] = {};
-  __half *img = nullptr, *a0 = nullptr, *a1 = nullptr;
-  float* seq = nullptr;
-  float *gx = nullptr, *hid32 = nullptr, *logits = nullptr, *prob = nullptr;
-  int *idx = nullptr, *offlen = nullptr;
-  uint8_t* ignore = nullptr;
-  size_t c_img = 0, c_a0 = 0, c_a1 = 0, c_seq = 0, c_gx = 0, c_hid32 = 0, c_logits = 0, c_prob = 0, c_idx = 0, c_offlen = 0;
+  DevBuf<__half> img, a0, a1;
+  DevBuf<float> seq, gx, hid32, logits, prob;
+  DevBuf<int> idx, offlen;
+  DevBuf<uint8_t> ignore;
   std::vector<__half> himg;
   std::vector<int> hofflen;
   double flops_last = 0;
@@ -474,20 +441,13 @@ int canvas_of(int h, int w, int canvas_size, Canvas* c) {
 // the frames on the device (*d_src: HOST frames are staged in the handle) and, for a resize, its taps in r->taps
 int craft_stage(eioku_craft* r, const uint8_t* bgr, int n, int h, int w, const Canvas& c, int mem, hipStream_t st,
                 const uint8_t** d_src) {
-  *d_src = bgr;
-  if (mem == EIOKU_MEM_HOST) {
-    int rc = grow(&r->src, &r->c_src, (size_t)n * h * w * 3);
-    if (rc) return rc;
-    EIOKU_HIP_CHECK(hipMemcpyAsync(r->src, bgr, (size_t)n * h * w * 3, hipMemcpyHostToDevice, st));
-    *d_src = r->src;
-  }
+  EIOKU_TRY(stage_host(r->src, bgr, (size_t)n * h * w * 3, mem, st, d_src));
   if (!c.copy) {
     std::vector<int>& taps = r->htaps;  // kept in the handle: the copy below is asynchronous
     taps.assign((size_t)3 * (c.tw + c.th), 0);
     linear_taps(w, c.tw, taps.data());
     linear_taps(h, c.th, taps.data() + 3 * c.tw);
-    int rc = grow(&r->taps, &r->c_taps, taps.size());
-    if (rc) return rc;
+    EIOKU_TRY(r->taps.grow(taps.size()));
     EIOKU_HIP_CHECK(hipMemcpyAsync(r->taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice, st));
   }
   return EIOKU_OK;
@@ -501,15 +461,14 @@ int tail_reserve(eioku_crnn* r, long long rows, int m, const int* off, const int
   // the input projection holds rows x 2048 fp32 values: callers split larger batches (eioku_amd/ocr.py: 65,536 rows)
   EIOKU_REQUIRE(rows <= (1 << 18), "%lld sequence steps in one call (at most 262,144: split the crops)", rows);
   const int C = r->num_class;
-  int rc;
-  if ((rc = grow(&r->seq, &r->c_seq, (size_t)rows * kHid))) return rc;
-  if ((rc = grow(&r->gx, &r->c_gx, (size_t)rows * 8 * kHid))) return rc;
-  if ((rc = grow(&r->hid32, &r->c_hid32, (size_t)rows * 2 * kHid))) return rc;
-  if ((rc = grow(&r->logits, &r->c_logits, (size_t)rows * C))) return rc;
-  if ((rc = grow(&r->prob, &r->c_prob, (size_t)rows))) return rc;
-  if ((rc = grow(&r->idx, &r->c_idx, (size_t)rows))) return rc;
-  if ((rc = grow(&r->offlen, &r->c_offlen, (size_t)3 * m))) return rc;
-  if (!r->ignore) EIOKU_HIP_CHECK(hipMalloc((void**)&r->ignore, (size_t)C));
+  EIOKU_TRY(r->seq.grow((size_t)rows * kHid));
+  EIOKU_TRY(r->gx.grow((size_t)rows * 8 * kHid));
+  EIOKU_TRY(r->hid32.grow((size_t)rows * 2 * kHid));
+  EIOKU_TRY(r->logits.grow((size_t)rows * C));
+  EIOKU_TRY(r->prob.grow((size_t)rows));
+  EIOKU_TRY(r->idx.grow((size_t)rows));
+  EIOKU_TRY(r->offlen.grow((size_t)3 * m));
+  EIOKU_TRY(r->ignore.grow((size_t)C));
   EIOKU_HIP_CHECK(hipMemcpyAsync(r->ignore, ignore, (size_t)C, hipMemcpyHostToDevice, st));
   std::vector<int>& ol = r->hofflen;  // kept in the handle: the copy below is asynchronous
   ol.assign(3 * (size_t)m, 0);
@@ -527,8 +486,8 @@ int tail_run(eioku_crnn* r, long long rows, int m, int32_t* idx_out, float* prob
   int rc;
   for (int l = 0; l < 2; ++l) {
     if ((rc = gemm_f32(r->seq, (int)rows, kHid, r->wih[l], 8 * kHid, r->bih[l], r->gx, st, fl))) return rc;
-    hipLaunchKernelGGL(k_lstm, dim3((unsigned)((m + kSeqTile - 1) / kSeqTile), 2), dim3(kHid), 0, st, r->gx, r->whh[l], r->offlen,
-                       r->offlen + m, m, r->hid32);
+    hipLaunchKernelGGL(k_lstm, dim3((unsigned)((m + kSeqTile - 1) / kSeqTile), 2), dim3(kHid), 0, st, r->gx.p, r->whh[l].p, r->offlen.p,
+                       r->offlen + m, m, r->hid32.p);
     EIOKU_LAUNCH_CHECK();
     *fl += 2.0 * 2 * 4 * kHid * kHid * rows;
     if ((rc = gemm_f32(r->hid32, (int)rows, 2 * kHid, r->wlin[l], kHid, r->blin[l], r->seq, st, fl))) return rc;
@@ -545,7 +504,7 @@ int tail_run(eioku_crnn* r, long long rows, int m, int32_t* idx_out, float* prob
 // N staged frames -> out [N][H][W][8] fp16
 int craft_prep(const eioku_craft* r, const uint8_t* d_src, int N, int h, int w, const Canvas& c, __half* out, hipStream_t st) {
   hipLaunchKernelGGL(k_craft_prep, dim3(grid1((long long)N * c.H * c.W)), dim3(256), 0, st, d_src, N, h, w, c.th, c.tw, c.H, c.W,
-                     r->taps, c.copy ? 1 : 0, out);
+                     r->taps.p, c.copy ? 1 : 0, out);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
 }
@@ -560,17 +519,15 @@ int eioku_craft_create(eioku_craft_t** out) {
   auto* r = new eioku_craft();
   // state dict prefixes of EasyOCR's craft.CRAFT (vgg16_bn basenet, U-Net, conv_cls); fc6's 3x3 / dilation 6 runs as
   // a 4608-channel 1x1 over an im2col (cin reported as 512, ksize 3)
-  r->layers = {{"basenet.slice1.0", 64, 3, 3},     {"basenet.slice1.3", 64, 64, 3},    {"basenet.slice1.7", 128, 64, 3},
-               {"basenet.slice1.10", 128, 128, 3}, {"basenet.slice2.14", 256, 128, 3}, {"basenet.slice2.17", 256, 256, 3},
-               {"basenet.slice3.20", 256, 256, 3}, {"basenet.slice3.24", 512, 256, 3}, {"basenet.slice3.27", 512, 512, 3},
-               {"basenet.slice4.30", 512, 512, 3}, {"basenet.slice4.34", 512, 512, 3}, {"basenet.slice4.37", 512, 512, 3},
-               {"basenet.slice5.1", 1024, 512, 3}, {"basenet.slice5.2", 1024, 1024, 1}, {"upconv1.conv.0", 512, 1536, 1},
-               {"upconv1.conv.3", 256, 512, 3},    {"upconv2.conv.0", 256, 768, 1},    {"upconv2.conv.3", 128, 256, 3},
-               {"upconv3.conv.0", 128, 384, 1},    {"upconv3.conv.3", 64, 128, 3},     {"upconv4.conv.0", 64, 192, 1},
-               {"upconv4.conv.3", 32, 64, 3},      {"conv_cls.0", 32, 32, 3},          {"conv_cls.2", 32, 32, 3},
-               {"conv_cls.4", 16, 32, 3},          {"conv_cls.6", 16, 16, 1},          {"conv_cls.8", 2, 16, 1}};
-  r->w.resize(r->layers.size());
-  r->set.assign(r->layers.size(), false);
+  r->convs.add_all({{"basenet.slice1.0", 64, 3, 3},     {"basenet.slice1.3", 64, 64, 3},    {"basenet.slice1.7", 128, 64, 3},
+                    {"basenet.slice1.10", 128, 128, 3}, {"basenet.slice2.14", 256, 128, 3}, {"basenet.slice2.17", 256, 256, 3},
+                    {"basenet.slice3.20", 256, 256, 3}, {"basenet.slice3.24", 512, 256, 3}, {"basenet.slice3.27", 512, 512, 3},
+                    {"basenet.slice4.30", 512, 512, 3}, {"basenet.slice4.34", 512, 512, 3}, {"basenet.slice4.37", 512, 512, 3},
+                    {"basenet.slice5.1", 1024, 512, 3}, {"basenet.slice5.2", 1024, 1024, 1}, {"upconv1.conv.0", 512, 1536, 1},
+                    {"upconv1.conv.3", 256, 512, 3},    {"upconv2.conv.0", 256, 768, 1},    {"upconv2.conv.3", 128, 256, 3},
+                    {"upconv3.conv.0", 128, 384, 1},    {"upconv3.conv.3", 64, 128, 3},     {"upconv4.conv.0", 64, 192, 1},
+                    {"upconv4.conv.3", 32, 64, 3},      {"conv_cls.0", 32, 32, 3},          {"conv_cls.2", 32, 32, 3},
+                    {"conv_cls.4", 16, 32, 3},          {"conv_cls.6", 16, 16, 1},          {"conv_cls.8", 2, 16, 1}});
   *out = r;
   return EIOKU_OK;
 }
@@ -578,51 +535,30 @@ int eioku_craft_create(eioku_craft_t** out) {
 void eioku_craft_destroy(eioku_craft_t* r) {
   if (!r) return;
   (void)hipDeviceSynchronize();
-  for (auto& w : r->w) conv_weights_destroy(&w);
-  for (void* p : {(void*)r->in8, (void*)r->p0, (void*)r->p1, (void*)r->cat1, (void*)r->cat2, (void*)r->cat3, (void*)r->cat4,
-                  (void*)r->col, (void*)r->y, (void*)r->src, (void*)r->taps})
-    if (p) (void)hipFree(p);
   delete r;
 }
 
-int eioku_craft_num_convs(const eioku_craft_t* r) { return r ? (int)r->layers.size() : 0; }
+int eioku_craft_num_convs(const eioku_craft_t* r) { return r ? r->convs.size() : 0; }
 
 int eioku_craft_conv_info(const eioku_craft_t* r, int idx, char* name, size_t cap, int* cout, int* cin, int* ksize) {
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size(), "bad convolution index %d", idx);
-  const Layer& l = r->layers[idx];
-  if (name && cap) snprintf(name, cap, "%s", l.name.c_str());
-  if (cout) *cout = l.cout;
-  if (cin) *cin = l.cin;
-  if (ksize) *ksize = l.k;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(r, "bad convolution index %d", idx);
+  return r->convs.info(idx, name, cap, cout, cin, ksize, nullptr);
 }
 
 // weight HOST fp32 [cout][cin][k][k] with the following BatchNorm folded in, bias HOST fp32 [cout]
 int eioku_craft_set_conv(eioku_craft_t* r, int idx, const float* w, const float* b) {
   EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size() && w && b, "bad argument");
-  const Layer& l = r->layers[idx];
-  conv_weights_destroy(&r->w[idx]);
-  r->set[idx] = false;
-  int rc;
-  if (idx == 0) {  // 3 -> 8 input channels (the canvas' zero channels get zero weights)
-    std::vector<float> w8((size_t)l.cout * 8 * 9, 0.f);
-    for (int co = 0; co < l.cout; ++co)
-      for (int ci = 0; ci < 3; ++ci)
-        for (int t = 0; t < 9; ++t) w8[((size_t)co * 8 + ci) * 9 + t] = w[((size_t)co * 3 + ci) * 9 + t];
-    rc = conv_weights_create(&r->w[idx], l.cout, 8, 3, 1, w8.data(), b);
-  } else if (l.name == "basenet.slice5.1") {  // fc6: [o][c][ky][kx] -> 1x1 over im2col channel (ky * 3 + kx) * 512 + c
-    std::vector<float> wc((size_t)l.cout * 9 * l.cin);
-    for (int o = 0; o < l.cout; ++o)
-      for (int c = 0; c < l.cin; ++c)
-        for (int t = 0; t < 9; ++t) wc[((size_t)o * 9 + t) * l.cin + c] = w[((size_t)o * l.cin + c) * 9 + t];
-    rc = conv_weights_create(&r->w[idx], l.cout, 9 * l.cin, 1, 1, wc.data(), b);
-  } else {
-    rc = conv_weights_create(&r->w[idx], l.cout, l.cin, l.k, 1, w, b);
-  }
-  if (rc) return rc;
-  r->set[idx] = true;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(r && idx >= 0 && idx < r->convs.size() && w && b, "bad argument");
+  const ConvLayer& l = r->convs.layers[idx];
+  ConvWeights* cw = &r->convs.w[idx];
+  if (idx == 0) return r->convs.mark(idx, conv_weights_create_cin8(cw, l.cout, l.cin, 3, 1, w, b));  // the canvas has 8 channels
+  if (l.name != "basenet.slice5.1") return r->convs.mark(idx, conv_weights_create(cw, l.cout, l.cin, l.k, 1, w, b));
+  // fc6: [o][c][ky][kx] -> 1x1 over im2col channel (ky * 3 + kx) * 512 + c
+  std::vector<float> wc((size_t)l.cout * 9 * l.cin);
+  for (int o = 0; o < l.cout; ++o)
+    for (int c = 0; c < l.cin; ++c)
+      for (int t = 0; t < 9; ++t) wc[((size_t)o * 9 + t) * l.cin + c] = w[((size_t)o * l.cin + c) * 9 + t];
+  return r->convs.mark(idx, conv_weights_create(cw, l.cout, 9 * l.cin, 1, 1, wc.data(), b));
 }
 
 // n BGR u8 frames h x w (host or device per mem) -> per frame the CRAFT score maps at half the canvas: text_out,
@@ -634,7 +570,7 @@ int eioku_craft_forward(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int 
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(r && n >= 0, "bad argument");
   EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
-  for (size_t i = 0; i < r->layers.size(); ++i) EIOKU_REQUIRE(r->set[i], "convolution %s has no weights", r->layers[i].name.c_str());
+  EIOKU_TRY(r->convs.all_set());
   Canvas cv;
   int rc = canvas_of(h, w, canvas_size, &cv);
   if (rc) return rc;
@@ -649,16 +585,16 @@ int eioku_craft_forward(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int 
   const uint8_t* d_src = nullptr;
   if ((rc = craft_stage(r, bgr, n, h, w, cv, mem, st, &d_src))) return rc;
   const int cN = std::min(chunk, n);
-  if ((rc = grow(&r->in8, &r->c_in8, (size_t)cN * fpx * 8))) return rc;
-  if ((rc = grow(&r->p0, &r->c_p0, (size_t)cN * fpx * 64))) return rc;
-  if ((rc = grow(&r->p1, &r->c_p1, (size_t)cN * fpx * 64))) return rc;
-  if ((rc = grow(&r->cat4, &r->c_cat4, (size_t)cN * fpx / 4 * 192))) return rc;
-  if ((rc = grow(&r->cat3, &r->c_cat3, (size_t)cN * fpx / 16 * 384))) return rc;
-  if ((rc = grow(&r->cat2, &r->c_cat2, (size_t)cN * fpx / 64 * 768))) return rc;
-  if ((rc = grow(&r->cat1, &r->c_cat1, (size_t)cN * fpx / 256 * 1536))) return rc;
-  if ((rc = grow(&r->col, &r->c_col, (size_t)cN * fpx / 256 * 4608))) return rc;
-  if ((rc = grow(&r->y, &r->c_y, (size_t)cN * fpx / 4 * 2))) return rc;
-  const auto& L = r->w;
+  EIOKU_TRY(r->in8.grow((size_t)cN * fpx * 8));
+  EIOKU_TRY(r->p0.grow((size_t)cN * fpx * 64));
+  EIOKU_TRY(r->p1.grow((size_t)cN * fpx * 64));
+  EIOKU_TRY(r->cat4.grow((size_t)cN * fpx / 4 * 192));
+  EIOKU_TRY(r->cat3.grow((size_t)cN * fpx / 16 * 384));
+  EIOKU_TRY(r->cat2.grow((size_t)cN * fpx / 64 * 768));
+  EIOKU_TRY(r->cat1.grow((size_t)cN * fpx / 256 * 1536));
+  EIOKU_TRY(r->col.grow((size_t)cN * fpx / 256 * 4608));
+  EIOKU_TRY(r->y.grow((size_t)cN * fpx / 4 * 2));
+  const auto& L = r->convs.w;
   double fl = 0;
   for (int f0 = 0; f0 < n; f0 += chunk) {
     const int N = std::min(chunk, n - f0);
@@ -718,7 +654,7 @@ int eioku_craft_forward(eioku_craft_t* r, const uint8_t* bgr, int n, int h, int 
     if ((rc = conv(L[25], Slice{P0, 32, 0}, N, Hc, Wc, Slice{P1, 32, 0}, nullptr, kActReLU, st, &fl))) return rc;
     if ((rc = conv(L[26], Slice{P1, 32, 0}, N, Hc, Wc, Slice{}, r->y, kActNone, st, &fl))) return rc;
     const long long hpx = (long long)Hc * Wc, off = (long long)f0 * hpx;
-    hipLaunchKernelGGL(k_craft_maps, dim3(grid1(N * hpx)), dim3(256), 0, st, r->y, N * hpx, low_text, link_threshold,
+    hipLaunchKernelGGL(k_craft_maps, dim3(grid1(N * hpx)), dim3(256), 0, st, r->y.p, N * hpx, low_text, link_threshold,
                        text_out ? text_out + off : nullptr, link_out ? link_out + off : nullptr, bin_out ? bin_out + off : nullptr);
     EIOKU_LAUNCH_CHECK();
   }
@@ -801,12 +737,10 @@ int eioku_crnn_create(int num_class, eioku_crnn_t** out) {
   auto* r = new eioku_crnn();
   r->num_class = num_class;
   // vgg_model.VGG_FeatureExtractor(1, 256) state dict prefixes (BatchNorm folded into ConvNet.11 / .14), then Prediction
-  r->layers = {{"FeatureExtraction.ConvNet.0", 32, 1, 3},     {"FeatureExtraction.ConvNet.3", 64, 32, 3},
-               {"FeatureExtraction.ConvNet.6", 128, 64, 3},   {"FeatureExtraction.ConvNet.8", 128, 128, 3},
-               {"FeatureExtraction.ConvNet.11", 256, 128, 3}, {"FeatureExtraction.ConvNet.14", 256, 256, 3},
-               {"FeatureExtraction.ConvNet.18", 256, 256, 2}, {"Prediction", num_class, kHid, 1}};
-  r->w.resize(r->layers.size());
-  r->set.assign(r->layers.size(), false);
+  r->convs.add_all({{"FeatureExtraction.ConvNet.0", 32, 1, 3},     {"FeatureExtraction.ConvNet.3", 64, 32, 3},
+                    {"FeatureExtraction.ConvNet.6", 128, 64, 3},   {"FeatureExtraction.ConvNet.8", 128, 128, 3},
+                    {"FeatureExtraction.ConvNet.11", 256, 128, 3}, {"FeatureExtraction.ConvNet.14", 256, 256, 3},
+                    {"FeatureExtraction.ConvNet.18", 256, 256, 2}, {"Prediction", num_class, kHid, 1}});
   *out = r;
   return EIOKU_OK;
 }
@@ -814,58 +748,35 @@ int eioku_crnn_create(int num_class, eioku_crnn_t** out) {
 void eioku_crnn_destroy(eioku_crnn_t* r) {
   if (!r) return;
   (void)hipDeviceSynchronize();
-  for (auto& w : r->w) conv_weights_destroy(&w);
-  for (int l = 0; l < 2; ++l) {
-    for (float* p : {r->wih[l], r->bih[l], r->wlin[l], r->blin[l]})
-      if (p) (void)hipFree(p);
-    if (r->whh[l]) (void)hipFree(r->whh[l]);
-  }
-  for (void* p : {(void*)r->img, (void*)r->a0, (void*)r->a1, (void*)r->seq, (void*)r->wpred, (void*)r->bpred, (void*)r->gx, (void*)r->hid32,
-                  (void*)r->logits, (void*)r->prob, (void*)r->idx, (void*)r->offlen, (void*)r->ignore})
-    if (p) (void)hipFree(p);
   delete r;
 }
 
-int eioku_crnn_num_convs(const eioku_crnn_t* r) { return r ? (int)r->layers.size() : 0; }
+int eioku_crnn_num_convs(const eioku_crnn_t* r) { return r ? r->convs.size() : 0; }
 
 int eioku_crnn_conv_info(const eioku_crnn_t* r, int idx, char* name, size_t cap, int* cout, int* cin, int* ksize) {
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size(), "bad convolution index %d", idx);
-  const Layer& l = r->layers[idx];
-  if (name && cap) snprintf(name, cap, "%s", l.name.c_str());
-  if (cout) *cout = l.cout;
-  if (cin) *cin = l.cin;
-  if (ksize) *ksize = l.k;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(r, "bad convolution index %d", idx);
+  return r->convs.info(idx, name, cap, cout, cin, ksize, nullptr);
 }
 
 // weight HOST fp32 [cout][cin][k][k] (BatchNorm folded in), bias HOST fp32 [cout]; "Prediction": [num_class][256]
 int eioku_crnn_set_conv(eioku_crnn_t* r, int idx, const float* w, const float* b) {
   EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size() && w && b, "bad argument");
-  const Layer& l = r->layers[idx];
-  conv_weights_destroy(&r->w[idx]);
-  r->set[idx] = false;
-  int rc;
-  if (idx == 0) {  // cin 1 -> 8 (the crop's zero channels get zero weights)
-    std::vector<float> w8((size_t)l.cout * 8 * 9, 0.f);
-    for (int co = 0; co < l.cout; ++co)
-      for (int t = 0; t < 9; ++t) w8[(size_t)co * 8 * 9 + t] = w[(size_t)co * 9 + t];
-    rc = conv_weights_create(&r->w[idx], l.cout, 8, 3, 1, w8.data(), b);
-  } else if (l.k == 2) {  // 2x2 valid -> 3x3 / pad 1 with the weights in the bottom-right 2x2
-    std::vector<float> w3((size_t)l.cout * l.cin * 9, 0.f);
-    for (size_t i = 0; i < (size_t)l.cout * l.cin; ++i)
-      for (int ky = 0; ky < 2; ++ky)
-        for (int kx = 0; kx < 2; ++kx) w3[i * 9 + (ky + 1) * 3 + kx + 1] = w[i * 4 + ky * 2 + kx];
-    rc = conv_weights_create(&r->w[idx], l.cout, l.cin, 3, 1, w3.data(), b);
-  } else if (l.name == "Prediction") {  // fp32 GEMM operand
-    rc = upload_f32(&r->wpred, w, (size_t)l.cout * l.cin);
-    if (!rc) rc = upload_f32(&r->bpred, b, (size_t)l.cout);
-  } else {
-    rc = conv_weights_create(&r->w[idx], l.cout, l.cin, l.k, 1, w, b);
+  EIOKU_REQUIRE(r && idx >= 0 && idx < r->convs.size() && w && b, "bad argument");
+  const ConvLayer& l = r->convs.layers[idx];
+  ConvWeights* cw = &r->convs.w[idx];
+  if (idx == 0) return r->convs.mark(idx, conv_weights_create_cin8(cw, l.cout, l.cin, 3, 1, w, b));  // the crop has 8 channels
+  if (l.name == "Prediction") {  // fp32 GEMM operand
+    int rc = r->wpred.upload(w, (size_t)l.cout * l.cin);
+    if (!rc) rc = r->bpred.upload(b, (size_t)l.cout);
+    return r->convs.mark(idx, rc);
   }
-  if (rc) return rc;
-  r->set[idx] = true;
-  return EIOKU_OK;
+  if (l.k != 2) return r->convs.mark(idx, conv_weights_create(cw, l.cout, l.cin, l.k, 1, w, b));
+  // 2x2 valid -> 3x3 / pad 1 with the weights in the bottom-right 2x2
+  std::vector<float> w3((size_t)l.cout * l.cin * 9, 0.f);
+  for (size_t i = 0; i < (size_t)l.cout * l.cin; ++i)
+    for (int ky = 0; ky < 2; ++ky)
+      for (int kx = 0; kx < 2; ++kx) w3[i * 9 + (ky + 1) * 3 + kx + 1] = w[i * 4 + ky * 2 + kx];
+  return r->convs.mark(idx, conv_weights_create(cw, l.cout, l.cin, 3, 1, w3.data(), b));
 }
 
 // BiLSTM layer (0 or 1) of SequenceModeling: nn.LSTM(256, 256, bidirectional) + Linear(512, 256), HOST fp32, PyTorch
@@ -879,17 +790,15 @@ int eioku_crnn_set_lstm(eioku_crnn_t* r, int layer, const float* w_ih, const flo
   std::vector<float> b(2 * G);
   for (int i = 0; i < 2 * G; ++i) b[i] = b_ih[i] + b_hh[i];
   r->lstm_set[layer] = false;
-  int rc;
-  if ((rc = upload_f32(&r->wih[layer], w_ih, (size_t)2 * G * kHid))) return rc;
-  if ((rc = upload_f32(&r->bih[layer], b.data(), (size_t)2 * G))) return rc;
-  if ((rc = upload_f32(&r->wlin[layer], w_lin, (size_t)kHid * 2 * kHid))) return rc;
-  if ((rc = upload_f32(&r->blin[layer], b_lin, (size_t)kHid))) return rc;
+  EIOKU_TRY(r->wih[layer].upload(w_ih, (size_t)2 * G * kHid));
+  EIOKU_TRY(r->bih[layer].upload(b.data(), (size_t)2 * G));
+  EIOKU_TRY(r->wlin[layer].upload(w_lin, (size_t)kHid * 2 * kHid));
+  EIOKU_TRY(r->blin[layer].upload(b_lin, (size_t)kHid));
   std::vector<float> t((size_t)2 * kHid * G);
   for (int d = 0; d < 2; ++d)
     for (int g = 0; g < G; ++g)
       for (int k = 0; k < kHid; ++k) t[((size_t)d * kHid + k) * G + g] = w_hh[((size_t)d * G + g) * kHid + k];
-  if (!r->whh[layer]) EIOKU_HIP_CHECK(hipMalloc((void**)&r->whh[layer], t.size() * 4));
-  EIOKU_HIP_CHECK(hipMemcpy(r->whh[layer], t.data(), t.size() * 4, hipMemcpyHostToDevice));
+  EIOKU_TRY(r->whh[layer].upload(t.data(), t.size()));
   r->lstm_set[layer] = true;
   return EIOKU_OK;
 }
@@ -903,7 +812,7 @@ int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, in
                        float* prob_out, float* logits_out, void* stream_) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(r && m >= 0, "bad argument");
-  for (size_t i = 0; i < r->layers.size(); ++i) EIOKU_REQUIRE(r->set[i], "%s has no weights", r->layers[i].name.c_str());
+  for (int i = 0; i < r->convs.size(); ++i) EIOKU_REQUIRE(r->convs.set[i], "%s has no weights", r->convs.layers[i].name.c_str());
   EIOKU_REQUIRE(r->lstm_set[0] && r->lstm_set[1], "BiLSTM layers have no weights");
   if (m == 0) return EIOKU_OK;
   EIOKU_REQUIRE(imgs && widths && ignore && idx_out && prob_out, "NULL buffer");
@@ -931,10 +840,10 @@ int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, in
   int rc;
   if ((rc = tail_reserve(r, rows, m, off.data(), len.data(), order.data(), ignore, st))) return rc;
   const size_t gpx = (size_t)kGroup * 64 * wmax;
-  if ((rc = grow(&r->img, &r->c_img, gpx * 8))) return rc;
-  if ((rc = grow(&r->a0, &r->c_a0, gpx * 32))) return rc;
-  if ((rc = grow(&r->a1, &r->c_a1, gpx * 32))) return rc;
-  const auto& L = r->w;
+  EIOKU_TRY(r->img.grow(gpx * 8));
+  EIOKU_TRY(r->a0.grow(gpx * 32));
+  EIOKU_TRY(r->a1.grow(gpx * 32));
+  const auto& L = r->convs.w;
   double fl = 0;
   for (int g0 = 0; g0 < m;) {
     const int wp = widths[order[g0]];
@@ -964,7 +873,7 @@ int eioku_crnn_forward(eioku_crnn_t* r, const float* imgs, const int* widths, in
     if ((rc = conv(L[6], Slice{B, 256, 0}, N, Hc, Wc, Slice{A, 256, 0}, nullptr, kActReLU, st, &fl))) return rc;
     fl += 2.0 * 256 * 256 * 4 * N * (Hc - 1) * (Wc - 1) - L[6].flops_per_pixel() * N * Hc * Wc;  // algorithmic: 2x2 valid
     hipLaunchKernelGGL(k_row_mean, dim3(grid1((long long)N * (Wc - 1) * kHid)), dim3(256), 0, st, A, N, Wc, kHid,
-                       r->offlen + 2 * m + g0, r->seq);
+                       r->offlen + 2 * m + g0, r->seq.p);
     EIOKU_LAUNCH_CHECK();
     g0 = g1;
   }
@@ -980,7 +889,7 @@ int eioku_crnn_tail(eioku_crnn_t* r, const float* seq, const int* len, int m, co
                     float* prob_out, float* logits_out, void* stream_) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(r && m >= 0, "bad argument");
-  EIOKU_REQUIRE(r->set.back(), "Prediction has no weights");
+  EIOKU_REQUIRE(r->convs.set.back(), "Prediction has no weights");
   EIOKU_REQUIRE(r->lstm_set[0] && r->lstm_set[1], "BiLSTM layers have no weights");
   if (m == 0) return EIOKU_OK;
   EIOKU_REQUIRE(seq && len && ignore && idx_out && prob_out, "NULL buffer");

@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "conv.h"
+#include "convnet.h"
 
 using namespace eioku;
 
@@ -284,118 +284,82 @@ __global__ __launch_bounds__(256) void k_places_head(const __half* __restrict__ 
   }
 }
 
-struct Layer {
-  std::string name;
-  int cout, cin, k, stride;
-};
-
-std::vector<Layer> resnet18_layers() {
-  std::vector<Layer> L;
-  L.push_back({"conv1", 64, 3, 7, 2});
+void resnet18_layers(ConvStack* cs) {
+  cs->add({"conv1", 64, 3, 7, 2});
   const int widths[4] = {64, 128, 256, 512};
   for (int li = 0; li < 4; ++li) {
     const int c = widths[li], s = li == 0 ? 1 : 2, cin0 = li == 0 ? 64 : c / 2;
     for (int b = 0; b < 2; ++b) {
       const int st = b == 0 ? s : 1, ci = b == 0 ? cin0 : c;
       const std::string p = "layer" + std::to_string(li + 1) + "." + std::to_string(b);
-      L.push_back({p + ".conv1", c, ci, 3, st});
-      L.push_back({p + ".conv2", c, c, 3, 1});
-      if (b == 0 && (st != 1 || ci != c)) L.push_back({p + ".downsample.0", c, ci, 1, st});
+      cs->add({p + ".conv1", c, ci, 3, st});
+      cs->add({p + ".conv2", c, c, 3, 1});
+      if (b == 0 && (st != 1 || ci != c)) cs->add({p + ".downsample.0", c, ci, 1, st});
     }
   }
-  return L;
 }
 
 }  // namespace
 
 struct eioku_resnet {
   int nc = 365;
-  std::vector<Layer> layers;
-  std::vector<ConvWeights> w;   // index = layer (0 unused: the stem has its own packing)
-  std::vector<bool> set;
-  uint4* stem_w = nullptr;
-  float* stem_b = nullptr;
-  __half* fc_w = nullptr;
-  float* fc_b = nullptr;
+  ConvStack convs;           // w[0] unused: the stem has its own packing
+  DevBuf<uint4> stem_w;
+  DevBuf<float> stem_b;
+  DevBuf<__half> fc_w;
+  DevBuf<float> fc_b;
   bool fc_set = false;
-  // activations for the current batch size
-  int cap_n = 0;
-  __half* in224 = nullptr;   // [N][224][224][4]
-  __half* a112 = nullptr;    // [N][112][112][64]
-  __half* buf[4] = {};       // [N][56][56][64] each (the largest block tensor)
-  uint8_t* tmp = nullptr;    // resize intermediate [N][h][224][3]
-  size_t tmp_cap = 0;
-  uint8_t* src = nullptr;    // staged host frames
-  size_t src_cap = 0;
-  int* tables = nullptr;     // xbounds | xk | ybounds | yk
-  size_t tables_cap = 0;
-  float* logits = nullptr;   // [N][nc]
-  float* probs = nullptr;    // [N][nc]
-  int* idx = nullptr;
+  // activations, grown to the largest batch seen
+  DevBuf<__half> in224;      // [N][224][224][4]
+  DevBuf<__half> a112;       // [N][112][112][64]
+  DevBuf<__half> buf[4];     // [N][56][56][64] each (the largest block tensor)
+  DevBuf<uint8_t> tmp;       // resize intermediate [N][h][224][3]
+  DevBuf<uint8_t> src;       // staged host frames
+  DevBuf<int> tables;        // xbounds | xk | ybounds | yk
+  DevBuf<float> logits;      // [N][nc]
+  DevBuf<float> probs;       // [N][nc]
+  DevBuf<int> idx;
   double flops_last = 0;
 };
 
 namespace {
 
 int ensure_batch(eioku_resnet* r, int N) {
-  if (N <= r->cap_n) return EIOKU_OK;
-  for (void* p : {(void*)r->in224, (void*)r->a112, (void*)r->buf[0], (void*)r->buf[1], (void*)r->buf[2], (void*)r->buf[3],
-                  (void*)r->logits, (void*)r->probs, (void*)r->idx})
-    if (p) (void)hipFree(p);
-  r->cap_n = 0;
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->in224, (size_t)N * kIn * kIn * 4 * 2));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->a112, (size_t)N * 112 * 112 * 64 * 2));
-  for (int i = 0; i < 4; ++i) EIOKU_HIP_CHECK(hipMalloc((void**)&r->buf[i], (size_t)N * 56 * 56 * 64 * 2));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->logits, (size_t)N * r->nc * 4));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->probs, (size_t)N * 512 * 4));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&r->idx, (size_t)N * 512 * 4));
-  r->cap_n = N;
-  return EIOKU_OK;
+  EIOKU_TRY(r->in224.grow((size_t)N * kIn * kIn * 4));
+  EIOKU_TRY(r->a112.grow((size_t)N * 112 * 112 * 64));
+  for (auto& b : r->buf) EIOKU_TRY(b.grow((size_t)N * 56 * 56 * 64));
+  EIOKU_TRY(r->logits.grow((size_t)N * r->nc));
+  EIOKU_TRY(r->probs.grow((size_t)N * 512));
+  return r->idx.grow((size_t)N * 512);
 }
 
 // the network on r->in224 -> (logits, sorted probabilities, classes) in the handle's buffers
 int run_network(eioku_resnet* r, int N, int top_k, hipStream_t stream) {
-  for (size_t i = 0; i < r->layers.size(); ++i) EIOKU_REQUIRE(r->set[i], "convolution %s has no weights", r->layers[i].name.c_str());
+  EIOKU_TRY(r->convs.all_set());
   EIOKU_REQUIRE(r->fc_set, "fc has no weights");
   double flops = 0;
-  hipLaunchKernelGGL(k_stem7x7, dim3(112 / kSTW, 112 / kSTH, (unsigned)N), dim3(256), 0, stream, r->in224, N, r->stem_w, r->stem_b,
+  hipLaunchKernelGGL(k_stem7x7, dim3(112 / kSTW, 112 / kSTH, (unsigned)N), dim3(256), 0, stream, r->in224.p, N, r->stem_w.p, r->stem_b.p,
                      r->a112);
   EIOKU_LAUNCH_CHECK();
   flops += 2.0 * 64 * 3 * 49 * 112 * 112 * N;
   {
     const long long work = (long long)N * 56 * 56 * 8;
-    hipLaunchKernelGGL(k_maxpool3s2, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, r->a112, N, 112, 112, 64, r->buf[0]);
+    hipLaunchKernelGGL(k_maxpool3s2, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, r->a112.p, N, 112, 112, 64, r->buf[0].p);
     EIOKU_LAUNCH_CHECK();
   }
-  int x = 0, H = 56;  // buf[x] holds the block input at H x H
-  size_t li = 1;
-  for (int stage = 0; stage < 4; ++stage)
-    for (int b = 0; b < 2; ++b) {
-      const Layer& c1 = r->layers[li];
-      const Layer& c2 = r->layers[li + 1];
-      const bool down = li + 2 < r->layers.size() && r->layers[li + 2].name.find("downsample") != std::string::npos &&
-                        r->layers[li + 2].name.compare(0, 8, c1.name, 0, 8) == 0;
-      const int t = (x + 1) & 3, idn = (x + 2) & 3, y = (x + 3) & 3;
-      const int Ho = conv_out_dim(H, 3, c1.stride);
-      Slice in{r->buf[x], c1.cin, 0}, mid{r->buf[t], c1.cout, 0}, out{r->buf[y], c2.cout, 0}, res = in;
-      int rc = conv_forward(r->w[li], in, N, H, H, mid, nullptr, Slice{}, kActReLU, stream);
-      if (rc) return rc;
-      flops += r->w[li].flops_per_pixel() * N * Ho * Ho;
-      if (down) {
-        res = Slice{r->buf[idn], c2.cout, 0};
-        rc = conv_forward(r->w[li + 2], in, N, H, H, res, nullptr, Slice{}, kActNone, stream);
-        if (rc) return rc;
-        flops += 2.0 * c1.cout * c1.cin * N * Ho * Ho;  // algorithmic: a 1x1
-      }
-      rc = conv_forward(r->w[li + 1], mid, N, Ho, Ho, out, nullptr, res, kActResReLU, stream);
-      if (rc) return rc;
-      flops += r->w[li + 1].flops_per_pixel() * N * Ho * Ho;
-      x = y;
-      H = Ho;
-      li += down ? 3 : 2;
-    }
-  hipLaunchKernelGGL(k_places_head, dim3((unsigned)N), dim3(256), 0, stream, r->buf[x], H * H, r->fc_w, r->fc_b, r->nc, top_k,
-                     r->logits, r->probs, r->idx);
+  int x = 0, H = 56, W = 56;  // buf[x] holds the block input at H x W
+  const ConvStack& cs = r->convs;
+  for (int li = 1; li < cs.size();) {
+    const ConvLayer& c1 = cs.layers[li];
+    const bool down = li + 2 < cs.size() && cs.layers[li + 2].name.find("downsample") != std::string::npos &&
+                      cs.layers[li + 2].name.compare(0, 8, c1.name, 0, 8) == 0;
+    EIOKU_TRY(basic_block(cs.w[li], cs.w[li + 1], down ? &cs.w[li + 2] : nullptr, r->buf, &x, N, &H, &W, stream));
+    flops += (cs.w[li].flops_per_pixel() + cs.w[li + 1].flops_per_pixel()) * N * H * W;
+    if (down) flops += 2.0 * c1.cout * c1.cin * N * H * W;  // algorithmic: a 1x1
+    li += down ? 3 : 2;
+  }
+  hipLaunchKernelGGL(k_places_head, dim3((unsigned)N), dim3(256), 0, stream, r->buf[x].p, H * W, r->fc_w.p, r->fc_b.p, r->nc, top_k,
+                     r->logits.p, r->probs.p, r->idx.p);
   EIOKU_LAUNCH_CHECK();
   flops += 2.0 * 512 * r->nc * N;
   r->flops_last = flops;
@@ -411,9 +375,7 @@ int eioku_resnet18_create(int num_classes, eioku_resnet_t** out) {
   EIOKU_REQUIRE(out && num_classes >= 1 && num_classes <= 512, "bad argument");
   auto* r = new eioku_resnet();
   r->nc = num_classes;
-  r->layers = resnet18_layers();
-  r->w.resize(r->layers.size());
-  r->set.assign(r->layers.size(), false);
+  resnet18_layers(&r->convs);
   *out = r;
   return EIOKU_OK;
 }
@@ -421,33 +383,22 @@ int eioku_resnet18_create(int num_classes, eioku_resnet_t** out) {
 void eioku_resnet18_destroy(eioku_resnet_t* r) {
   if (!r) return;
   (void)hipDeviceSynchronize();
-  for (auto& w : r->w) conv_weights_destroy(&w);
-  for (void* p : {(void*)r->stem_w, (void*)r->stem_b, (void*)r->fc_w, (void*)r->fc_b, (void*)r->in224, (void*)r->a112,
-                  (void*)r->buf[0], (void*)r->buf[1], (void*)r->buf[2], (void*)r->buf[3], (void*)r->tmp, (void*)r->src,
-                  (void*)r->tables, (void*)r->logits, (void*)r->probs, (void*)r->idx})
-    if (p) (void)hipFree(p);
   delete r;
 }
 
-int eioku_resnet18_num_convs(const eioku_resnet_t* r) { return r ? (int)r->layers.size() : 0; }
+int eioku_resnet18_num_convs(const eioku_resnet_t* r) { return r ? r->convs.size() : 0; }
 
 int eioku_resnet18_conv_info(const eioku_resnet_t* r, int idx, char* name, size_t cap, int* cout, int* cin, int* ksize,
                              int* stride) {
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size(), "bad convolution index %d", idx);
-  const Layer& l = r->layers[idx];
-  if (name && cap) snprintf(name, cap, "%s", l.name.c_str());
-  if (cout) *cout = l.cout;
-  if (cin) *cin = l.cin;
-  if (ksize) *ksize = l.k;
-  if (stride) *stride = l.stride;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(r, "bad convolution index %d", idx);
+  return r->convs.info(idx, name, cap, cout, cin, ksize, stride);
 }
 
 // weight: HOST fp32 [cout][cin][k][k] with BatchNorm already folded in, bias HOST fp32 [cout]
 int eioku_resnet18_set_conv(eioku_resnet_t* r, int idx, const float* w, const float* b) {
   EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(r && idx >= 0 && idx < (int)r->layers.size() && w && b, "bad argument");
-  const Layer& l = r->layers[idx];
+  EIOKU_REQUIRE(r && idx >= 0 && idx < r->convs.size() && w && b, "bad argument");
+  const ConvLayer& l = r->convs.layers[idx];
   if (idx == 0) {
     // stem: A operand of (k-step s, fragment f, lane (row, u)) = cout f*16 + row, k = 8u .. 8u + 7 = taps 8s + 2u, + 1 x
     // 4 channels (channel 3 and taps >= 49 are zero)
@@ -461,24 +412,13 @@ int eioku_resnet18_set_conv(eioku_resnet_t* r, int idx, const float* w, const fl
             if (tap < 49 && ch < 3) pw[(((size_t)s * 4 + f) * 64 + lane) * 8 + e] = (_Float16)w[((size_t)co * 3 + ch) * 49 + tap];
           }
         }
-    if (!r->stem_w) EIOKU_HIP_CHECK(hipMalloc((void**)&r->stem_w, pw.size() * 2));
-    if (!r->stem_b) EIOKU_HIP_CHECK(hipMalloc((void**)&r->stem_b, 64 * 4));
-    EIOKU_HIP_CHECK(hipMemcpy(r->stem_w, pw.data(), pw.size() * 2, hipMemcpyHostToDevice));
-    EIOKU_HIP_CHECK(hipMemcpy(r->stem_b, b, 64 * 4, hipMemcpyHostToDevice));
-  } else {
-    conv_weights_destroy(&r->w[idx]);
-    int rc;
-    if (l.k == 1) {  // stride-2 1x1 -> 3x3 / s2 with the weights on the centre tap
-      std::vector<float> w3((size_t)l.cout * l.cin * 9, 0.f);
-      for (size_t i = 0; i < (size_t)l.cout * l.cin; ++i) w3[i * 9 + 4] = w[i];
-      rc = conv_weights_create(&r->w[idx], l.cout, l.cin, 3, l.stride, w3.data(), b);
-    } else {
-      rc = conv_weights_create(&r->w[idx], l.cout, l.cin, l.k, l.stride, w, b);
-    }
-    if (rc) return rc;
+    EIOKU_TRY(r->stem_w.upload(reinterpret_cast<const uint4*>(pw.data()), pw.size() / 8));
+    EIOKU_TRY(r->stem_b.upload(b, 64));
+    return r->convs.mark(idx, EIOKU_OK);
   }
-  r->set[idx] = true;
-  return EIOKU_OK;
+  // a stride-2 1x1 runs as a 3x3 / s2 with the weights on the centre tap
+  return r->convs.mark(idx, l.k == 1 ? conv_weights_create_centre(&r->convs.w[idx], l.cout, l.cin, l.stride, w, b)
+                                     : conv_weights_create(&r->convs.w[idx], l.cout, l.cin, l.k, l.stride, w, b));
 }
 
 int eioku_resnet18_set_fc(eioku_resnet_t* r, const float* w, const float* b) {
@@ -486,10 +426,8 @@ int eioku_resnet18_set_fc(eioku_resnet_t* r, const float* w, const float* b) {
   EIOKU_REQUIRE(r && w && b, "bad argument");
   std::vector<_Float16> hw((size_t)r->nc * 512);
   for (size_t i = 0; i < hw.size(); ++i) hw[i] = (_Float16)w[i];
-  if (!r->fc_w) EIOKU_HIP_CHECK(hipMalloc((void**)&r->fc_w, hw.size() * 2));
-  if (!r->fc_b) EIOKU_HIP_CHECK(hipMalloc((void**)&r->fc_b, (size_t)r->nc * 4));
-  EIOKU_HIP_CHECK(hipMemcpy(r->fc_w, hw.data(), hw.size() * 2, hipMemcpyHostToDevice));
-  EIOKU_HIP_CHECK(hipMemcpy(r->fc_b, b, (size_t)r->nc * 4, hipMemcpyHostToDevice));
+  EIOKU_TRY(r->fc_w.upload(reinterpret_cast<const __half*>(hw.data()), hw.size()));
+  EIOKU_TRY(r->fc_b.upload(b, (size_t)r->nc));
   r->fc_set = true;
   return EIOKU_OK;
 }
@@ -507,12 +445,7 @@ int eioku_places_preprocess(eioku_resnet_t* r, const uint8_t* bgr, int n, int h,
   if (n == 0) return EIOKU_OK;
   EIOKU_REQUIRE(bgr, "NULL frames");
   hipStream_t stream = (hipStream_t)stream_;
-  const size_t tb = (size_t)kIn * (2 + kx + 2 + ky) * 4;
-  if (r->tables_cap < tb) {
-    if (r->tables) (void)hipFree(r->tables);
-    EIOKU_HIP_CHECK(hipMalloc((void**)&r->tables, tb));
-    r->tables_cap = tb;
-  }
+  EIOKU_TRY(r->tables.grow((size_t)kIn * (2 + kx + 2 + ky)));
   int* d_xb = r->tables;
   int* d_xk = d_xb + kIn * 2;
   int* d_yb = d_xk + kIn * kx;
@@ -521,26 +454,12 @@ int eioku_places_preprocess(eioku_resnet_t* r, const uint8_t* bgr, int n, int h,
   EIOKU_HIP_CHECK(hipMemcpyAsync(d_xk, xk, (size_t)kIn * kx * 4, hipMemcpyHostToDevice, stream));
   EIOKU_HIP_CHECK(hipMemcpyAsync(d_yb, ybounds, kIn * 2 * 4, hipMemcpyHostToDevice, stream));
   EIOKU_HIP_CHECK(hipMemcpyAsync(d_yk, yk, (size_t)kIn * ky * 4, hipMemcpyHostToDevice, stream));
-  const uint8_t* d_src = bgr;
-  const size_t sb = (size_t)n * h * w * 3;
-  if (mem == EIOKU_MEM_HOST) {
-    if (r->src_cap < sb) {
-      if (r->src) (void)hipFree(r->src);
-      EIOKU_HIP_CHECK(hipMalloc((void**)&r->src, sb));
-      r->src_cap = sb;
-    }
-    EIOKU_HIP_CHECK(hipMemcpyAsync(r->src, bgr, sb, hipMemcpyHostToDevice, stream));
-    d_src = r->src;
-  }
-  const size_t tmpb = (size_t)n * h * kIn * 3;
-  if (r->tmp_cap < tmpb) {
-    if (r->tmp) (void)hipFree(r->tmp);
-    EIOKU_HIP_CHECK(hipMalloc((void**)&r->tmp, tmpb));
-    r->tmp_cap = tmpb;
-  }
+  const uint8_t* d_src;
+  EIOKU_TRY(stage_host(r->src, bgr, (size_t)n * h * w * 3, mem, stream, &d_src));
+  EIOKU_TRY(r->tmp.grow((size_t)n * h * kIn * 3));
   const long long w1 = (long long)n * h * kIn, w2 = (long long)n * kIn * kIn;
-  hipLaunchKernelGGL(k_pil_resize_h, dim3((unsigned)((w1 + 255) / 256)), dim3(256), 0, stream, d_src, n, h, w, d_xb, d_xk, kx, r->tmp);
-  hipLaunchKernelGGL(k_pil_resize_v, dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, stream, r->tmp, n, h, d_yb, d_yk, ky,
+  hipLaunchKernelGGL(k_pil_resize_h, dim3((unsigned)((w1 + 255) / 256)), dim3(256), 0, stream, d_src, n, h, w, d_xb, d_xk, kx, r->tmp.p);
+  hipLaunchKernelGGL(k_pil_resize_v, dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, stream, r->tmp.p, n, h, d_yb, d_yk, ky,
                      (__half*)out_f16, out_rgb_u8);
   EIOKU_LAUNCH_CHECK();
   if (mem == EIOKU_MEM_HOST) EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // the staged host buffer may be reused by the caller

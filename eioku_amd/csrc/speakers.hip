@@ -23,7 +23,7 @@
 #include <string>
 #include <vector>
 
-#include "conv.h"
+#include "convnet.h"
 
 using namespace eioku;
 
@@ -212,11 +212,6 @@ __global__ __launch_bounds__(256) void k_spk_assign(const float* __restrict__ e,
   if (lane == 0) out[row] = lab;
 }
 
-struct Layer {
-  std::string name;
-  int cout, cin, k, stride;
-};
-
 struct Block {
   int conv1, conv2, down;  // layer indices (down = -1: identity shortcut)
   int cin, cout, stride;
@@ -227,23 +222,23 @@ struct Block {
 struct eioku_spk {
   int depths[4] = {};
   int win = 0;
-  std::vector<Layer> layers;
+  ConvStack convs;
   std::vector<Block> blocks;
-  std::vector<ConvWeights> w;
-  std::vector<bool> set;
-  float* seg_w = nullptr;      // [256][5120] fp32, device column order
-  float* seg_b = nullptr;
+  DevBuf<float> seg_w;         // [256][5120] fp32, device column order
+  DevBuf<float> seg_b;
   bool seg_set = false;
-  double* tables = nullptr;    // window [400] | cosine [512] | mel [80][256]
-  int* mel_range = nullptr;    // [80][2]
-  float* audio = nullptr;      // the video's 16 kHz samples
-  long long n_audio = 0, audio_cap = 0;
-  int cap = 0;                 // windows the pass buffers hold
-  double* logmel = nullptr;    // [cap][80][win]
-  __half* in16 = nullptr;      // [cap][80][win][8]
-  __half* buf[4] = {};         // [cap][80][win][32] each
-  float* stats = nullptr;      // [cap][5120]
-  int* plan = nullptr;         // [cap][2] | valid [cap]
+  DevBuf<double> tables;       // window [400] | cosine [512] | mel [80][256]
+  DevBuf<int> mel_range;       // [80][2]
+  DevBuf<float> audio;         // the video's 16 kHz samples
+  long long n_audio = 0;
+  // pass buffers, grown to the most windows seen in one pass
+  DevBuf<double> logmel;       // [m][80][win]
+  DevBuf<__half> in16;         // [m][80][win][8]
+  DevBuf<__half> buf[4];       // [m][80][win][32] each
+  DevBuf<float> stats;         // [m][5120]
+  DevBuf<int> plan;            // [cap][2] | valid [cap], cap = plan.cap / 3 windows
+  int* valid() const { return plan.p + plan.cap / 3 * 2; }
+  // events stay raw handles: created in eioku_spk_create, destroyed in eioku_spk_destroy
   hipEvent_t ev[4] = {};
   double ms[3] = {};           // features, network, pooling + head of the last embed
 };
@@ -251,24 +246,12 @@ struct eioku_spk {
 namespace {
 
 int ensure_cap(eioku_spk* s, int m) {
-  if (m <= s->cap) return EIOKU_OK;
-  for (void* p : {(void*)s->logmel, (void*)s->in16, (void*)s->buf[0], (void*)s->buf[1], (void*)s->buf[2], (void*)s->buf[3],
-                  (void*)s->stats, (void*)s->plan})
-    if (p) (void)hipFree(p);
-  s->cap = 0;
-  s->logmel = nullptr;
-  s->in16 = nullptr;
-  s->stats = nullptr;
-  s->plan = nullptr;
-  for (auto& b : s->buf) b = nullptr;
   const size_t px = (size_t)m * kMel * s->win;
-  EIOKU_HIP_CHECK(hipMalloc((void**)&s->logmel, px * 8));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&s->in16, px * 8 * 2));
-  for (int i = 0; i < 4; ++i) EIOKU_HIP_CHECK(hipMalloc((void**)&s->buf[i], px * 32 * 2));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&s->stats, (size_t)m * kStat * 4));
-  EIOKU_HIP_CHECK(hipMalloc((void**)&s->plan, (size_t)m * 3 * 4));
-  s->cap = m;
-  return EIOKU_OK;
+  EIOKU_TRY(s->logmel.grow(px));
+  EIOKU_TRY(s->in16.grow(px * 8));
+  for (auto& b : s->buf) EIOKU_TRY(b.grow(px * 32));
+  EIOKU_TRY(s->stats.grow((size_t)m * kStat));
+  return s->plan.grow((size_t)m * 3);
 }
 
 // plan rows (first sample, valid) against the window length and the uploaded audio
@@ -285,10 +268,10 @@ int check_plan(const eioku_spk* s, const int* plan, int m) {
 
 // features of mc windows (device plan rows d_plan) -> s->in16 (and f32 when given)
 int run_features(eioku_spk* s, const int* d_plan, int mc, float* f32, __half* out, hipStream_t stream) {
-  hipLaunchKernelGGL(k_spk_fbank, dim3((unsigned)s->win, (unsigned)mc), dim3(256), 0, stream, s->audio, d_plan, s->win, s->tables,
-                     s->tables + kFrame, s->tables + kFrame + kFft, s->mel_range, s->logmel);
+  hipLaunchKernelGGL(k_spk_fbank, dim3((unsigned)s->win, (unsigned)mc), dim3(256), 0, stream, s->audio.p, d_plan, s->win, s->tables.p,
+                     s->tables + kFrame, s->tables + kFrame + kFft, s->mel_range.p, s->logmel.p);
   EIOKU_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_spk_cmn, dim3((unsigned)((mc * kMel + 255) / 256)), dim3(256), 0, stream, s->logmel, d_plan, mc, s->win, f32,
+  hipLaunchKernelGGL(k_spk_cmn, dim3((unsigned)((mc * kMel + 255) / 256)), dim3(256), 0, stream, s->logmel.p, d_plan, mc, s->win, f32,
                      out);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
@@ -297,28 +280,14 @@ int run_features(eioku_spk* s, const int* d_plan, int mc, float* f32, __half* ou
 // the network on s->in16 ([m][80][win][8]); upto_block >= 0: stop after that block and copy its output to act_out;
 // otherwise buf[*x_out] holds the last map [m][10][win / 8][256]
 int run_network(eioku_spk* s, int m, int upto_block, void* act_out, int* x_out, hipStream_t stream) {
-  for (size_t i = 0; i < s->layers.size(); ++i) EIOKU_REQUIRE(s->set[i], "convolution %s has no weights", s->layers[i].name.c_str());
+  EIOKU_TRY(s->convs.all_set());
+  const auto& cw = s->convs.w;
   int H = kMel, W = s->win;
-  int rc = conv_forward(s->w[0], Slice{s->in16, 8, 0}, m, H, W, Slice{s->buf[0], 32, 0}, nullptr, Slice{}, kActReLU, stream);
-  if (rc) return rc;
+  EIOKU_TRY(conv_forward(cw[0], Slice{s->in16, 8, 0}, m, H, W, Slice{s->buf[0], 32, 0}, nullptr, Slice{}, kActReLU, stream));
   int x = 0;
   for (size_t bi = 0; bi < s->blocks.size(); ++bi) {
     const Block& b = s->blocks[bi];
-    const int t = (x + 1) & 3, idn = (x + 2) & 3, y = (x + 3) & 3;
-    const int Ho = conv_out_dim(H, 3, b.stride), Wo = conv_out_dim(W, 3, b.stride);
-    Slice in{s->buf[x], b.cin, 0}, mid{s->buf[t], b.cout, 0}, out{s->buf[y], b.cout, 0}, res = in;
-    rc = conv_forward(s->w[b.conv1], in, m, H, W, mid, nullptr, Slice{}, kActReLU, stream);
-    if (rc) return rc;
-    if (b.down >= 0) {
-      res = Slice{s->buf[idn], b.cout, 0};
-      rc = conv_forward(s->w[b.down], in, m, H, W, res, nullptr, Slice{}, kActNone, stream);
-      if (rc) return rc;
-    }
-    rc = conv_forward(s->w[b.conv2], mid, m, Ho, Wo, out, nullptr, res, kActResReLU, stream);
-    if (rc) return rc;
-    x = y;
-    H = Ho;
-    W = Wo;
+    EIOKU_TRY(basic_block(cw[b.conv1], cw[b.conv2], b.down >= 0 ? &cw[b.down] : nullptr, s->buf, &x, m, &H, &W, stream));
     if ((int)bi == upto_block) {
       EIOKU_HIP_CHECK(hipMemcpyAsync(act_out, s->buf[x], (size_t)m * H * W * b.cout * 2, hipMemcpyDeviceToDevice, stream));
       return EIOKU_OK;
@@ -330,9 +299,9 @@ int run_network(eioku_spk* s, int m, int upto_block, void* act_out, int* x_out, 
 
 int run_pool_head(eioku_spk* s, int m, int x, const int* d_valid, float* emb_out, hipStream_t stream) {
   EIOKU_REQUIRE(s->seg_set, "seg_1 has no weights");
-  hipLaunchKernelGGL(k_spk_pool, dim3(kFreq, (unsigned)m), dim3(256), 0, stream, s->buf[x], d_valid, s->win / 8, s->stats);
+  hipLaunchKernelGGL(k_spk_pool, dim3(kFreq, (unsigned)m), dim3(256), 0, stream, s->buf[x].p, d_valid, s->win / 8, s->stats.p);
   EIOKU_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_spk_head, dim3(kEmb), dim3(256), 0, stream, s->stats, m, s->seg_w, s->seg_b, emb_out);
+  hipLaunchKernelGGL(k_spk_head, dim3(kEmb), dim3(256), 0, stream, s->stats.p, m, s->seg_w.p, s->seg_b.p, emb_out);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
 }
@@ -351,7 +320,8 @@ int eioku_spk_create(const int* depths, int win_frames, const double* window, co
   for (int st = 0; st < 4; ++st) EIOKU_REQUIRE(depths[st] >= 1 && depths[st] <= 64, "stage %d depth %d outside [1, 64]", st + 1, depths[st]);
   auto* s = new eioku_spk();
   s->win = win_frames;
-  s->layers.push_back({"conv1", 32, 1, 3, 1});
+  ConvStack& cs = s->convs;
+  cs.add({"conv1", 32, 1, 3, 1});
   const int widths[4] = {32, 64, 128, 256};
   int inplanes = 32;
   for (int st = 0; st < 4; ++st) {
@@ -360,19 +330,14 @@ int eioku_spk_create(const int* depths, int win_frames, const double* window, co
     for (int b = 0; b < depths[st]; ++b) {
       const std::string p = "layer" + std::to_string(st + 1) + "." + std::to_string(b);
       const int cin = b == 0 ? inplanes : planes, stride = b == 0 && st > 0 ? 2 : 1;
-      Block blk{(int)s->layers.size(), (int)s->layers.size() + 1, -1, cin, planes, stride};
-      s->layers.push_back({p + ".conv1", planes, cin, 3, stride});
-      s->layers.push_back({p + ".conv2", planes, planes, 3, 1});
-      if (stride != 1 || cin != planes) {
-        blk.down = (int)s->layers.size();
-        s->layers.push_back({p + ".shortcut.0", planes, cin, 1, stride});
-      }
+      Block blk{cs.size(), cs.size() + 1, -1, cin, planes, stride};
+      cs.add({p + ".conv1", planes, cin, 3, stride});
+      cs.add({p + ".conv2", planes, planes, 3, 1});
+      if (stride != 1 || cin != planes) blk.down = cs.add({p + ".shortcut.0", planes, cin, 1, stride});
       s->blocks.push_back(blk);
     }
     inplanes = planes;
   }
-  s->w.resize(s->layers.size());
-  s->set.assign(s->layers.size(), false);
   std::vector<double> tab((size_t)kFrame + kFft + (size_t)kMel * kBins);
   std::copy(window, window + kFrame, tab.begin());
   for (int i = 0; i < kFft; ++i) tab[kFrame + i] = std::cos(2.0 * M_PI * (double)i / (double)kFft);
@@ -388,18 +353,13 @@ int eioku_spk_create(const int* depths, int win_frames, const double* window, co
     range[2 * j] = std::min(lo, hi);
     range[2 * j + 1] = hi;
   }
-  int rc = EIOKU_OK;
-  auto fail = [&](hipError_t e) {
-    if (e == hipSuccess || rc) return;
-    set_error("eioku_spk_create: %s", hipGetErrorString(e));
-    rc = EIOKU_EHIP;
-  };
-  fail(hipMalloc((void**)&s->tables, tab.size() * 8));
-  fail(hipMalloc((void**)&s->mel_range, range.size() * 4));
-  if (!rc) fail(hipMemcpy(s->tables, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-  if (!rc) fail(hipMemcpy(s->mel_range, range.data(), range.size() * 4, hipMemcpyHostToDevice));
+  int rc = s->tables.upload(tab.data(), tab.size());
+  if (!rc) rc = s->mel_range.upload(range.data(), range.size());
   for (auto& e : s->ev)
-    if (!rc) fail(hipEventCreate(&e));
+    if (!rc && hipEventCreate(&e) != hipSuccess) {
+      set_error("eioku_spk_create: hipEventCreate failed");
+      rc = EIOKU_EHIP;
+    }
   if (rc) {
     eioku_spk_destroy(s);
     return rc;
@@ -411,62 +371,36 @@ int eioku_spk_create(const int* depths, int win_frames, const double* window, co
 void eioku_spk_destroy(eioku_spk_t* s) {
   if (!s) return;
   (void)hipDeviceSynchronize();
-  for (auto& w : s->w) conv_weights_destroy(&w);
-  for (void* p : {(void*)s->seg_w, (void*)s->seg_b, (void*)s->tables, (void*)s->mel_range, (void*)s->audio, (void*)s->logmel,
-                  (void*)s->in16, (void*)s->buf[0], (void*)s->buf[1], (void*)s->buf[2], (void*)s->buf[3], (void*)s->stats,
-                  (void*)s->plan})
-    if (p) (void)hipFree(p);
   for (auto& e : s->ev)
     if (e) (void)hipEventDestroy(e);
   delete s;
 }
 
-int eioku_spk_num_convs(const eioku_spk_t* s) { return s ? (int)s->layers.size() : 0; }
+int eioku_spk_num_convs(const eioku_spk_t* s) { return s ? s->convs.size() : 0; }
 
 int eioku_spk_conv_info(const eioku_spk_t* s, int idx, char* name, size_t cap, int* cout, int* cin, int* ksize, int* stride) {
-  EIOKU_REQUIRE(s && idx >= 0 && idx < (int)s->layers.size(), "bad convolution index %d", idx);
-  const Layer& l = s->layers[idx];
-  if (name && cap) snprintf(name, cap, "%s", l.name.c_str());
-  if (cout) *cout = l.cout;
-  if (cin) *cin = l.cin;
-  if (ksize) *ksize = l.k;
-  if (stride) *stride = l.stride;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(s, "bad convolution index %d", idx);
+  return s->convs.info(idx, name, cap, cout, cin, ksize, stride);
 }
 
 // weight HOST fp32 [cout][cin][k][k] with the following BatchNorm folded in, bias HOST fp32 [cout]
 int eioku_spk_set_conv(eioku_spk_t* s, int idx, const float* w, const float* b) {
   EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(s && idx >= 0 && idx < (int)s->layers.size() && w && b, "bad argument");
-  const Layer& l = s->layers[idx];
-  conv_weights_destroy(&s->w[idx]);
-  s->set[idx] = false;
-  int rc;
-  if (idx == 0) {  // stem: 1 -> 8 input channels (the features' zero channels get zero weights)
-    std::vector<float> w8((size_t)32 * 8 * 9, 0.f);
-    for (int co = 0; co < 32; ++co)
-      for (int t = 0; t < 9; ++t) w8[((size_t)co * 8) * 9 + t] = w[(size_t)co * 9 + t];
-    rc = conv_weights_create(&s->w[idx], 32, 8, 3, 1, w8.data(), b);
-  } else if (l.k == 1) {  // 1x1 shortcut -> 3x3 of the same stride with the weights on the centre tap
-    std::vector<float> w3((size_t)l.cout * l.cin * 9, 0.f);
-    for (size_t i = 0; i < (size_t)l.cout * l.cin; ++i) w3[i * 9 + 4] = w[i];
-    rc = conv_weights_create(&s->w[idx], l.cout, l.cin, 3, l.stride, w3.data(), b);
-  } else {
-    rc = conv_weights_create(&s->w[idx], l.cout, l.cin, l.k, l.stride, w, b);
-  }
-  if (rc) return rc;
-  s->set[idx] = true;
-  return EIOKU_OK;
+  EIOKU_REQUIRE(s && idx >= 0 && idx < s->convs.size() && w && b, "bad argument");
+  const ConvLayer& l = s->convs.layers[idx];
+  ConvWeights* cw = &s->convs.w[idx];
+  // the stem reads the features' 8 channels; a 1x1 shortcut runs as a 3x3 of its stride with the weights on the centre tap
+  return s->convs.mark(idx, idx == 0   ? conv_weights_create_cin8(cw, l.cout, l.cin, l.k, l.stride, w, b)
+                            : l.k == 1 ? conv_weights_create_centre(cw, l.cout, l.cin, l.stride, w, b)
+                                       : conv_weights_create(cw, l.cout, l.cin, l.k, l.stride, w, b));
 }
 
 // seg_1: weight HOST fp32 [256][5120], columns in the device's order (mean | std, each f * 256 + c), bias HOST fp32 [256]
 int eioku_spk_set_head(eioku_spk_t* s, const float* w, const float* b) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(s && w && b, "bad argument");
-  if (!s->seg_w) EIOKU_HIP_CHECK(hipMalloc((void**)&s->seg_w, (size_t)kEmb * kStat * 4));
-  if (!s->seg_b) EIOKU_HIP_CHECK(hipMalloc((void**)&s->seg_b, kEmb * 4));
-  EIOKU_HIP_CHECK(hipMemcpy(s->seg_w, w, (size_t)kEmb * kStat * 4, hipMemcpyHostToDevice));
-  EIOKU_HIP_CHECK(hipMemcpy(s->seg_b, b, kEmb * 4, hipMemcpyHostToDevice));
+  EIOKU_TRY(s->seg_w.upload(w, (size_t)kEmb * kStat));
+  EIOKU_TRY(s->seg_b.upload(b, kEmb));
   s->seg_set = true;
   return EIOKU_OK;
 }
@@ -479,13 +413,7 @@ int eioku_spk_set_audio(eioku_spk_t* s, const float* samples, long long n, int m
   EIOKU_REQUIRE(n == 0 || samples, "NULL buffer");
   hipStream_t stream = (hipStream_t)stream_;
   s->n_audio = 0;
-  if (s->audio_cap < n) {
-    if (s->audio) (void)hipFree(s->audio);
-    s->audio = nullptr;
-    s->audio_cap = 0;
-    EIOKU_HIP_CHECK(hipMalloc((void**)&s->audio, (size_t)n * 4));
-    s->audio_cap = n;
-  }
+  EIOKU_TRY(s->audio.grow((size_t)n));
   if (n)
     EIOKU_HIP_CHECK(hipMemcpyAsync(s->audio, samples, (size_t)n * 4, mem == EIOKU_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                                    stream));
@@ -534,7 +462,7 @@ int eioku_spk_forward(eioku_spk_t* s, const void* in_f16, const int* valid, int 
   rc = run_network(s, m, upto_block, act_out, &x, stream);
   if (rc) return rc;
   if (upto_block < 0) {
-    int* d_valid = s->plan + 2 * (size_t)s->cap;
+    int* d_valid = s->valid();
     EIOKU_HIP_CHECK(hipMemcpyAsync(d_valid, valid, (size_t)m * 4, hipMemcpyHostToDevice, stream));
     rc = run_pool_head(s, m, x, d_valid, emb_out, stream);
     if (rc) return rc;
@@ -564,7 +492,7 @@ int eioku_spk_embed(eioku_spk_t* s, const int* plan, int m, float* emb_out, void
     std::copy(plan + 2 * (size_t)c0, plan + 2 * (size_t)(c0 + mc), pv.begin());
     for (int i = 0; i < mc; ++i) pv[2 * (size_t)kPass + i] = plan[2 * (size_t)(c0 + i) + 1];
     EIOKU_HIP_CHECK(hipMemcpyAsync(s->plan, pv.data(), (size_t)mc * 8, hipMemcpyHostToDevice, stream));
-    EIOKU_HIP_CHECK(hipMemcpyAsync(s->plan + 2 * (size_t)s->cap, pv.data() + 2 * (size_t)kPass, (size_t)mc * 4, hipMemcpyHostToDevice,
+    EIOKU_HIP_CHECK(hipMemcpyAsync(s->valid(), pv.data() + 2 * (size_t)kPass, (size_t)mc * 4, hipMemcpyHostToDevice,
                                    stream));
     EIOKU_HIP_CHECK(hipEventRecord(s->ev[0], stream));
     rc = run_features(s, s->plan, mc, nullptr, s->in16, stream);
@@ -574,7 +502,7 @@ int eioku_spk_embed(eioku_spk_t* s, const int* plan, int m, float* emb_out, void
     rc = run_network(s, mc, -1, nullptr, &x, stream);
     if (rc) return rc;
     EIOKU_HIP_CHECK(hipEventRecord(s->ev[2], stream));
-    rc = run_pool_head(s, mc, x, s->plan + 2 * (size_t)s->cap, emb_out + (size_t)c0 * kEmb, stream);
+    rc = run_pool_head(s, mc, x, s->valid(), emb_out + (size_t)c0 * kEmb, stream);
     if (rc) return rc;
     EIOKU_HIP_CHECK(hipEventRecord(s->ev[3], stream));
     EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // pv and the plan buffer are reused by the next pass

@@ -358,34 +358,18 @@ void huff_fill(const uint8_t* bits, const uint8_t* vals, unsigned* table) {
   }
 }
 
-template <typename T>
-int grow(T*& p, size_t& cap, size_t bytes) {
-  if (cap >= bytes) return EIOKU_OK;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  EIOKU_HIP_CHECK(hipMalloc((void**)&p, bytes));
-  cap = bytes;
-  return EIOKU_OK;
-}
-
 enum { kEvResize0, kEvResize1, kEvJpeg0, kEvBlocks, kEvEntropy, kEvRead0, kEvRead1, kNumEvents };
 
 }  // namespace
 
 struct eioku_thumbs {
-  unsigned* huff = nullptr;
-  int* tables = nullptr;
-  size_t tables_cap = 0;
-  uint8_t* tmp = nullptr;  // the resize's 8-bit intermediate
-  size_t tmp_cap = 0;
-  uint16_t* qtab = nullptr;
-  int16_t* coef = nullptr;
-  size_t coef_cap = 0;
-  unsigned* len = nullptr;  // [n][nblk] bit lengths, then [n][nblk] offsets, [n] totals, [n] word offsets
-  size_t len_cap = 0;
-  unsigned* bits = nullptr;
-  size_t bits_cap = 0;
+  eioku::DevBuf<unsigned> huff;
+  eioku::DevBuf<int> tables;
+  eioku::DevBuf<uint8_t> tmp;  // the resize's 8-bit intermediate
+  eioku::DevBuf<uint16_t> qtab;
+  eioku::DevBuf<int16_t> coef;
+  eioku::DevBuf<unsigned> len;  // [n][nblk] bit lengths, then [n][nblk] offsets, [n] totals, [n] word offsets
+  eioku::DevBuf<unsigned> bits;
   size_t bits_bytes = 0;  // of the last eioku_thumbs_jpeg call
   hipEvent_t ev[kNumEvents] = {};
   bool timed[3] = {false, false, false};  // resize, jpeg, read have run since create
@@ -403,14 +387,16 @@ int eioku_thumbs_create(eioku_thumbs_t** out) {
   huff_fill(kDcChromaBits, kDcVals, h.data() + kDcOff + 12);
   huff_fill(kAcLumaBits, kAcLumaVals, h.data() + kAcOff);
   huff_fill(kAcChromaBits, kAcChromaVals, h.data() + kAcOff + 256);
-  hipError_t e = hipMalloc((void**)&t->huff, kHuffEntries * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&t->qtab, 128 * 2);
-  if (e == hipSuccess) e = hipMemcpy(t->huff, h.data(), kHuffEntries * 4, hipMemcpyHostToDevice);
-  for (int i = 0; i < kNumEvents && e == hipSuccess; ++i) e = hipEventCreate(&t->ev[i]);
-  if (e != hipSuccess) {
-    ::eioku::set_error("eioku_thumbs_create: %s", hipGetErrorString(e));
+  int rc = t->huff.upload(h.data(), kHuffEntries);
+  if (!rc) rc = t->qtab.grow(128);
+  for (int i = 0; i < kNumEvents && !rc; ++i)
+    if (hipEventCreate(&t->ev[i]) != hipSuccess) {
+      ::eioku::set_error("eioku_thumbs_create: hipEventCreate failed");
+      rc = EIOKU_EHIP;
+    }
+  if (rc) {
     eioku_thumbs_destroy(t);
-    return EIOKU_EHIP;
+    return rc;
   }
   *out = t;
   return EIOKU_OK;
@@ -418,8 +404,6 @@ int eioku_thumbs_create(eioku_thumbs_t** out) {
 
 void eioku_thumbs_destroy(eioku_thumbs_t* t) {
   if (!t) return;
-  for (void* p : {(void*)t->huff, (void*)t->tables, (void*)t->tmp, (void*)t->qtab, (void*)t->coef, (void*)t->len, (void*)t->bits})
-    if (p) (void)hipFree(p);
   for (hipEvent_t e : t->ev)
     if (e) (void)hipEventDestroy(e);
   delete t;
@@ -443,10 +427,8 @@ int eioku_thumbs_resize(eioku_thumbs_t* t, const uint8_t* bgr, int n, int h, int
   EIOKU_REQUIRE(bgr && rgb_out, "NULL buffer");
   hipStream_t stream = (hipStream_t)stream_;
   const size_t xb_n = (size_t)tw * 2, xk_n = (size_t)tw * kx, yb_n = (size_t)th * 2, yk_n = (size_t)th * ky;
-  int rc = grow(t->tables, t->tables_cap, (xb_n + xk_n + yb_n + yk_n) * 4);
-  if (rc) return rc;
-  rc = grow(t->tmp, t->tmp_cap, (size_t)n * h * tw * 3);
-  if (rc) return rc;
+  EIOKU_TRY(t->tables.grow(xb_n + xk_n + yb_n + yk_n));
+  EIOKU_TRY(t->tmp.grow((size_t)n * h * tw * 3));
   int* d_xb = t->tables;
   int* d_xk = d_xb + xb_n;
   int* d_yb = d_xk + xk_n;
@@ -457,8 +439,8 @@ int eioku_thumbs_resize(eioku_thumbs_t* t, const uint8_t* bgr, int n, int h, int
   EIOKU_HIP_CHECK(hipMemcpyAsync(d_yk, yk, yk_n * 4, hipMemcpyHostToDevice, stream));
   const long long w1 = (long long)n * h * tw, w2 = (long long)n * th * tw;
   EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvResize0], stream));
-  hipLaunchKernelGGL(k_thumb_resize_h, dim3((unsigned)((w1 + 255) / 256)), dim3(256), 0, stream, bgr, w1, w, tw, d_xb, d_xk, kx, t->tmp);
-  hipLaunchKernelGGL(k_thumb_resize_v, dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, stream, t->tmp, w2, h, th, tw, d_yb, d_yk, ky,
+  hipLaunchKernelGGL(k_thumb_resize_h, dim3((unsigned)((w1 + 255) / 256)), dim3(256), 0, stream, bgr, w1, w, tw, d_xb, d_xk, kx, t->tmp.p);
+  hipLaunchKernelGGL(k_thumb_resize_v, dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, stream, t->tmp.p, w2, h, th, tw, d_yb, d_yk, ky,
                      rgb_out);
   EIOKU_LAUNCH_CHECK();
   EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvResize1], stream));
@@ -480,20 +462,18 @@ int eioku_thumbs_jpeg(eioku_thumbs_t* t, const uint8_t* rgb, int n, int th, int 
   hipStream_t stream = (hipStream_t)stream_;
   const int mx = (tw + 15) / 16, my = (th + 15) / 16, nblk = mx * my * 6;
   const size_t nb = (size_t)n * nblk;
-  int rc = grow(t->coef, t->coef_cap, nb * 64 * 2);
-  if (rc) return rc;
-  rc = grow(t->len, t->len_cap, (2 * nb + 2 * (size_t)n) * 4);
-  if (rc) return rc;
+  EIOKU_TRY(t->coef.grow(nb * 64));
+  EIOKU_TRY(t->len.grow(2 * nb + 2 * (size_t)n));
   unsigned* d_len = t->len;
   unsigned* d_off = d_len + nb;
   unsigned* d_total = d_off + nb;
   unsigned* d_word = d_total + n;
   EIOKU_HIP_CHECK(hipMemcpyAsync(t->qtab, qtab, 128 * 2, hipMemcpyHostToDevice, stream));
   EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvJpeg0], stream));
-  hipLaunchKernelGGL(k_jpeg_blocks, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream, rgb, n, th, tw, mx, my, t->qtab, t->coef);
+  hipLaunchKernelGGL(k_jpeg_blocks, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream, rgb, n, th, tw, mx, my, t->qtab.p, t->coef.p);
   EIOKU_LAUNCH_CHECK();
   EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvBlocks], stream));
-  hipLaunchKernelGGL(k_jpeg_bitlen, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, t->coef, n, nblk, t->huff, d_len);
+  hipLaunchKernelGGL(k_jpeg_bitlen, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, t->coef.p, n, nblk, t->huff.p, d_len);
   hipLaunchKernelGGL(k_jpeg_scan, dim3((unsigned)n), dim3(kScanThreads), 0, stream, d_len, nblk, d_off, d_total);
   EIOKU_LAUNCH_CHECK();
   uint32_t totals[kMaxN];
@@ -507,12 +487,11 @@ int eioku_thumbs_jpeg(eioku_thumbs_t* t, const uint8_t* rgb, int n, int th, int 
     words += ((size_t)totals[i] + 31) / 32;
     nbits_out[i] = totals[i];
   }
-  rc = grow(t->bits, t->bits_cap, words * 4);
-  if (rc) return rc;
+  EIOKU_TRY(t->bits.grow(words));
   EIOKU_HIP_CHECK(hipMemcpyAsync(d_word, word_off, (size_t)n * 4, hipMemcpyHostToDevice, stream));
   EIOKU_HIP_CHECK(hipMemsetAsync(t->bits, 0, words * 4, stream));
-  hipLaunchKernelGGL(k_jpeg_emit, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, t->coef, n, nblk, t->huff, d_off, d_word,
-                     t->bits);
+  hipLaunchKernelGGL(k_jpeg_emit, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, t->coef.p, n, nblk, t->huff.p, d_off, d_word,
+                     t->bits.p);
   EIOKU_LAUNCH_CHECK();
   EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvEntropy], stream));
   if (coef_out) EIOKU_HIP_CHECK(hipMemcpyAsync(coef_out, t->coef, nb * 64 * 2, hipMemcpyDeviceToHost, stream));

@@ -183,6 +183,8 @@ __global__ __launch_bounds__(kThreads) void k_keyword_select(const float* __rest
   if (tid == 0) count_out[row] = npick;
 }
 
+// a raw pointer on purpose: the workspace lives as long as the process, and a static destructor would free it after
+// the runtime is gone
 std::mutex g_ks_mu;
 void* g_ks_ws = nullptr;
 size_t g_ks_bytes = 0;

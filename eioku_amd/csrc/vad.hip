@@ -259,7 +259,7 @@ __global__ __launch_bounds__(512) void k_vad_lstm(const float* __restrict__ gx, 
 struct VTensor {
   const char* name;
   int rows, cols;
-  float* dev = nullptr;
+  DevBuf<float> dev;
   bool set = false;
 };
 
@@ -278,10 +278,10 @@ struct eioku_vad {
                       {"decoder.rnn.weight_ih", kGates, kHid}, {"decoder.rnn.weight_hh", kGates, kHid},
                       {"decoder.rnn.bias_ih", kGates, 1},   {"decoder.rnn.bias_hh", kGates, 1},
                       {"decoder.out.weight", 1, kHid},      {"decoder.out.bias", 1, 1}};
-  float* audio = nullptr;   // kCtx + slab * 512
-  float* gx = nullptr;      // slab * 512
-  float* probs = nullptr;   // slab
-  float* state = nullptr;   // h [128], c [128]
+  DevBuf<float> audio;      // kCtx + slab * 512
+  DevBuf<float> gx;         // slab * 512
+  DevBuf<float> probs;      // slab
+  DevBuf<float> state;      // h [128], c [128]
   std::vector<hipEvent_t> ev;   // 3 per slab of the last call
   double encode_ms = 0, lstm_ms = 0;
 };
@@ -291,13 +291,9 @@ extern "C" {
 void eioku_vad_destroy(eioku_vad* v) {
   if (!v) return;
   if (v->st) (void)hipStreamSynchronize(v->st);
-  for (auto& t : v->t)
-    if (t.dev) (void)hipFree(t.dev);
-  for (void* b : {(void*)v->audio, (void*)v->gx, (void*)v->probs, (void*)v->state})
-    if (b) (void)hipFree(b);
   for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
   if (v->st) (void)hipStreamDestroy(v->st);
-  delete v;
+  delete v;  // every buffer frees itself
 }
 
 int eioku_vad_create(int slab_chunks, eioku_vad** out) {
@@ -315,12 +311,11 @@ int eioku_vad_create(int slab_chunks, eioku_vad** out) {
     v->st = nullptr;
     return fail(EIOKU_EHIP, "hipStreamCreate");
   }
+  int rc = EIOKU_OK;
   for (auto& t : v->t)
-    if (hipMalloc(&t.dev, (size_t)t.rows * t.cols * sizeof(float)) != hipSuccess) return fail(EIOKU_ENOMEM, "hipMalloc");
+    if (!rc) rc = t.dev.grow((size_t)t.rows * t.cols);
   const size_t s = (size_t)slab_chunks;
-  if (hipMalloc(&v->audio, (kCtx + s * kChunk) * sizeof(float)) != hipSuccess ||
-      hipMalloc(&v->gx, s * kGates * sizeof(float)) != hipSuccess || hipMalloc(&v->probs, s * sizeof(float)) != hipSuccess ||
-      hipMalloc(&v->state, 2 * kHid * sizeof(float)) != hipSuccess)
+  if (rc || v->audio.grow(kCtx + s * kChunk) || v->gx.grow(s * kGates) || v->probs.grow(s) || v->state.grow(2 * kHid))
     return fail(EIOKU_ENOMEM, "hipMalloc");
   *out = v;
   return EIOKU_OK;
@@ -352,7 +347,7 @@ int eioku_vad_set_tensor(eioku_vad* v, int idx, const float* host, size_t numel)
     src = tr.data();
   }
   EIOKU_HIP_CHECK(hipStreamSynchronize(v->st));
-  EIOKU_HIP_CHECK(hipMemcpy(t.dev, src, want * sizeof(float), hipMemcpyHostToDevice));
+  EIOKU_HIP_CHECK(hipMemcpy(t.dev.p, src, want * sizeof(float), hipMemcpyHostToDevice));
   t.set = true;
   return EIOKU_OK;
 }
@@ -391,11 +386,11 @@ int eioku_vad_probs(eioku_vad* v, const float* samples, long long n_samples, flo
     if (have < (long long)m * kChunk)
       EIOKU_HIP_CHECK(hipMemsetAsync(v->audio + kCtx + have, 0, (size_t)((long long)m * kChunk - have) * sizeof(float), st));
     EIOKU_HIP_CHECK(hipEventRecord(v->ev[3 * s], st));
-    hipLaunchKernelGGL(k_vad_encode, dim3((unsigned)((m + kTile - 1) / kTile)), dim3(256), 0, st, v->audio, m, W, v->gx);
+    hipLaunchKernelGGL(k_vad_encode, dim3((unsigned)((m + kTile - 1) / kTile)), dim3(256), 0, st, v->audio.p, m, W, v->gx.p);
     EIOKU_LAUNCH_CHECK();
     EIOKU_HIP_CHECK(hipEventRecord(v->ev[3 * s + 1], st));
-    hipLaunchKernelGGL(k_vad_lstm, dim3(1), dim3(kGates), 0, st, v->gx, m, v->t[V_WHH].dev, v->t[V_WOUT].dev, v->t[V_BOUT].dev,
-                       v->state, v->probs);
+    hipLaunchKernelGGL(k_vad_lstm, dim3(1), dim3(kGates), 0, st, v->gx.p, m, v->t[V_WHH].dev.p, v->t[V_WOUT].dev.p, v->t[V_BOUT].dev.p,
+                       v->state.p, v->probs.p);
     EIOKU_LAUNCH_CHECK();
     EIOKU_HIP_CHECK(hipEventRecord(v->ev[3 * s + 2], st));
     // the next slab reuses audio, gx and probs: stream order keeps its copies behind this slab's kernels and read-back

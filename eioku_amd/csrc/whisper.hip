@@ -1147,7 +1147,7 @@ enum { T_F16 = 0, T_F32 = 1, T_CONV = 2 };
 struct Tensor {
   std::string name;
   int rows = 0, cols = 0, kind = T_F16, cin = 0, ldk = 0;
-  void* dev = nullptr;
+  DevBuf<uint8_t> dev;
   bool set = false;
   size_t numel() const { return (size_t)rows * cols; }
 };
@@ -1157,49 +1157,16 @@ struct Layer { Attn self, cross; int fc1, fc1b, fc2, fc2b, ln_g, ln_b; };
 
 int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-#define W_TRY(expr)                \
-  do {                             \
-    const int _rc = (expr);        \
-    if (_rc != EIOKU_OK) return _rc; \
-  } while (0)
-
-// An owning device buffer of `cap` elements: freed by its destructor, never copied.  grow(n) reallocates (and drops the
-// contents) only when n exceeds the capacity.
-template <typename T>
-struct Buf {
-  T* p = nullptr;
-  size_t cap = 0;
-  Buf() = default;
-  Buf(const Buf&) = delete;
-  Buf& operator=(const Buf&) = delete;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  operator T*() const { return p; }
-  int grow(size_t n) {
-    if (p && n <= cap) return EIOKU_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr, cap = 0;
-    if (hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)) != hipSuccess) {
-      p = nullptr;
-      set_error("hipMalloc of %zu bytes failed", n * sizeof(T));
-      return EIOKU_ENOMEM;
-    }
-    cap = n;
-    return EIOKU_OK;
-  }
-};
-
 // The activations of one pass over a number of token rows: the residual stream x in fp32; the LayerNorm output h, the
 // attention queries q, the attention output a and the MLP's hidden layer mid in fp16.
 struct Work {
-  Buf<float> x;
-  Buf<h16> h, q, a, mid;
+  DevBuf<float> x;
+  DevBuf<h16> h, q, a, mid;
   int grow(size_t rows, size_t d, size_t ffn) {
-    W_TRY(x.grow(rows * d));
-    W_TRY(h.grow(rows * d));
-    W_TRY(q.grow(rows * d));
-    W_TRY(a.grow(rows * d));
+    EIOKU_TRY(x.grow(rows * d));
+    EIOKU_TRY(h.grow(rows * d));
+    EIOKU_TRY(q.grow(rows * d));
+    EIOKU_TRY(a.grow(rows * d));
     return mid.grow(rows * ffn);
   }
 };
@@ -1215,53 +1182,53 @@ struct eioku_whisper {
   int emb = 0, dec_pos = 0, dec_ln_g = 0, dec_ln_b = 0;
   int nlang = 0, nblk = 0, k1pad = 0;
   // constants
-  Buf<double> hann, tw_cos, tw_sin, filt;
-  Buf<uint16_t> flags;
-  Buf<int> lang_ids;
+  DevBuf<double> hann, tw_cos, tw_sin, filt;
+  DevBuf<uint16_t> flags;
+  DevBuf<int> lang_ids;
   // audio + mel
-  Buf<float> samples;
+  DevBuf<float> samples;
   long long n_samples = 0;
-  Buf<long long> d_off;
-  Buf<double> mel64, mel_mx;
-  Buf<float> mel32;
+  DevBuf<long long> d_off;
+  DevBuf<double> mel64, mel_mx;
+  DevBuf<float> mel32;
   // encoder workspace (capacity cap windows; cap is the window stride of crossK / crossV)
   int cap = 0, enc_B = 0;
-  Buf<h16> col1, h1, col2, ek, ev, enc_out, crossK, crossV;
+  DevBuf<h16> col1, h1, col2, ek, ev, enc_out, crossK, crossV;
   Work ew;
   // decoder workspace (capacity dcap lanes >= cap; dcap is the lane stride of selfK / selfV and the offset of the lane map
   // in kvmap)
   int dcap = 0;
   Work dw;
-  Buf<h16> selfK, selfV;
-  Buf<float> partial, info, nsp, d_logprob;
-  Buf<LaneState> state;
-  Buf<int> tokens, cur_tok, lang_out, d_ids;
+  DevBuf<h16> selfK, selfV;
+  DevBuf<float> partial, info, nsp, d_logprob;
+  DevBuf<LaneState> state;
+  DevBuf<int> tokens, cur_tok, lang_out, d_ids;
   // beam search: lanes = windows * beam; ancestry table and token history double-buffered; finished records per window
   int beam_lanes = 0, beam_windows = 0;  // capacity of the beam buffers (0 until the first beam call)
-  Buf<float> bpartial, fin_sum, b_sum, b_fsum;
-  Buf<uint8_t> anc[2];
-  Buf<int> hist[2], fin_tok, fin_n, fin_count, complete;
-  Buf<int> b_src, b_tok, b_fsrc, b_nlive, b_nfin, tr_src, tr_tok;
+  DevBuf<float> bpartial, fin_sum, b_sum, b_fsum;
+  DevBuf<uint8_t> anc[2];
+  DevBuf<int> hist[2], fin_tok, fin_n, fin_count, complete;
+  DevBuf<int> b_src, b_tok, b_fsrc, b_nlive, b_nfin, tr_src, tr_tok;
   // sampling and prompt prefill: per-lane seeds and sample indices, the row -> window maps (rows, then lanes), and the
   // prefill workspace for prows = rows x prompt positions
-  Buf<unsigned long long> d_seeds;
-  Buf<int> d_sidx, kvmap;
+  DevBuf<unsigned long long> d_seeds;
+  DevBuf<int> d_sidx, kvmap;
   int prows = 0;
   Work pw;
-  Buf<h16> pk, pv;
-  Buf<float> ppartial;
+  DevBuf<h16> pk, pv;
+  DevBuf<float> ppartial;
   // word alignment (K21): the (layer, head) pairs (empty: every head of the upper half of the decoder layers), the
   // workspace of align(), each buffer grown on its own, and the device times of the last align() call
   std::vector<int> align_heads;
-  Buf<float> al_A, al_stat, al_cost, al_part, al_tgt, al_prob;
-  Buf<unsigned> al_trace;
-  Buf<int> al_jump, al_meta, al_rows, al_path;
+  DevBuf<float> al_A, al_stat, al_cost, al_part, al_tgt, al_prob;
+  DevBuf<unsigned> al_trace;
+  DevBuf<int> al_jump, al_meta, al_rows, al_path;
   double align_ms[3] = {0, 0, 0};
   double flops = 0;
   int launches = 0, steps = 0;
 
-  const h16* H(int i) const { return (const h16*)tensors[i].dev; }
-  const float* F(int i) const { return i < 0 ? nullptr : (const float*)tensors[i].dev; }
+  const h16* H(int i) const { return (const h16*)tensors[i].dev.p; }
+  const float* F(int i) const { return i < 0 ? nullptr : (const float*)tensors[i].dev.p; }
 };
 
 namespace {
@@ -1320,7 +1287,7 @@ int attn(eioku_whisper* m, const h16* Q, long long q_bs, int q_rs, const h16* K,
 template <int MT>
 int ln_q(eioku_whisper* m, Work& w, int M, const Attn& A) {
   const int d = m->cfg.d_model;
-  W_TRY(ln(m, w.x, M, d, A.ln_g, A.ln_b, w.h));
+  EIOKU_TRY(ln(m, w.x, M, d, A.ln_g, A.ln_b, w.h));
   return gemm<MT, EPI_F16>(m, w.h, d, m->H(A.q), d, m->F(A.qb), M, d, d, w.q, d);
 }
 
@@ -1328,7 +1295,7 @@ int ln_q(eioku_whisper* m, Work& w, int M, const Attn& A) {
 template <int MT>
 int kv_proj(eioku_whisper* m, const h16* src, int M, const Attn& A, h16* k, h16* v, long long ldc) {
   const int d = m->cfg.d_model;
-  W_TRY((gemm<MT, EPI_F16>(m, src, d, m->H(A.k), d, nullptr, M, d, d, k, ldc)));
+  EIOKU_TRY((gemm<MT, EPI_F16>(m, src, d, m->H(A.k), d, nullptr, M, d, d, k, ldc)));
   return gemm<MT, EPI_F16>(m, src, d, m->H(A.v), d, m->F(A.vb), M, d, d, v, ldc);
 }
 
@@ -1343,8 +1310,8 @@ int out_proj(eioku_whisper* m, Work& w, int M, const Attn& A) {
 template <int MT>
 int mlp(eioku_whisper* m, Work& w, int M, const Layer& L, int ffn) {
   const int d = m->cfg.d_model;
-  W_TRY(ln(m, w.x, M, d, L.ln_g, L.ln_b, w.h));
-  W_TRY((gemm<MT, EPI_GELU_F16>(m, w.h, d, m->H(L.fc1), d, m->F(L.fc1b), M, ffn, d, w.mid, ffn)));
+  EIOKU_TRY(ln(m, w.x, M, d, L.ln_g, L.ln_b, w.h));
+  EIOKU_TRY((gemm<MT, EPI_GELU_F16>(m, w.h, d, m->H(L.fc1), d, m->F(L.fc1b), M, ffn, d, w.mid, ffn)));
   return gemm<MT, EPI_RESID>(m, w.mid, ffn, m->H(L.fc2), ffn, m->F(L.fc2b), M, d, ffn, w.x, d);
 }
 
@@ -1366,7 +1333,7 @@ int cross_attn(eioku_whisper* m, Work& w, int R, int P, int l, int kv_div, const
   const Attn& A = m->dec[l].cross;
   const h16* ck = m->crossK + (size_t)l * m->cap * ctx * d;
   const h16* cv = m->crossV + (size_t)l * m->cap * ctx * d;
-  W_TRY(ln_q<MT>(m, w, R * P, A));
+  EIOKU_TRY(ln_q<MT>(m, w, R * P, A));
   for (int hs = 0; cap && hs < cap->n; ++hs) {
     if (cap->heads[2 * hs] != l) continue;
     const size_t lds = (size_t)4 * (ctx + 64) * sizeof(float);
@@ -1374,9 +1341,9 @@ int cross_attn(eioku_whisper* m, Work& w, int R, int P, int l, int kv_div, const
                        cap->heads[2 * hs + 1], kvmap, cap->nF, cap->A + (size_t)hs * P * cap->ldf, (long long)cap->n * P * cap->ldf,
                        (long long)cap->ldf);
     m->flops += 2.0 * R * (double)P * ctx * 64;
-    W_TRY(launched(m));
+    EIOKU_TRY(launched(m));
   }
-  W_TRY((attn<QPW>(m, w.q, bs, d, ck, cv, (long long)ctx * d, d, P, ctx, R, w.a, bs, d, kv_div, nullptr, 0, kvmap)));
+  EIOKU_TRY((attn<QPW>(m, w.q, bs, d, ck, cv, (long long)ctx * d, d, P, ctx, R, w.a, bs, d, kv_div, nullptr, 0, kvmap)));
   return out_proj<MT>(m, w, R * P, A);
 }
 
@@ -1388,16 +1355,16 @@ int ensure_lanes(eioku_whisper* m, int L) {
   const auto& c = m->cfg;
   const size_t d = c.d_model, Tm = c.max_target_positions, B = (size_t)L;
   m->dcap = 0;
-  W_TRY(m->dw.grow(B, d, c.dec_ffn));
-  for (Buf<h16>* b : {&m->selfK, &m->selfV}) W_TRY(b->grow(c.dec_layers * B * Tm * d));
-  W_TRY(m->partial.grow(B * m->nblk * (kNPS > kNP ? kNPS : kNP)));
-  W_TRY(m->info.grow(B * (1 + m->nlang)));
-  W_TRY(m->kvmap.grow(2 * B));
-  W_TRY(m->d_seeds.grow(B));
-  W_TRY(m->state.grow(B));
-  for (Buf<float>* b : {&m->nsp, &m->d_logprob}) W_TRY(b->grow(B));
-  for (Buf<int>* b : {&m->d_sidx, &m->cur_tok, &m->lang_out}) W_TRY(b->grow(B));
-  for (Buf<int>* b : {&m->tokens, &m->d_ids}) W_TRY(b->grow(B * Tm));
+  EIOKU_TRY(m->dw.grow(B, d, c.dec_ffn));
+  for (DevBuf<h16>* b : {&m->selfK, &m->selfV}) EIOKU_TRY(b->grow(c.dec_layers * B * Tm * d));
+  EIOKU_TRY(m->partial.grow(B * m->nblk * (kNPS > kNP ? kNPS : kNP)));
+  EIOKU_TRY(m->info.grow(B * (1 + m->nlang)));
+  EIOKU_TRY(m->kvmap.grow(2 * B));
+  EIOKU_TRY(m->d_seeds.grow(B));
+  EIOKU_TRY(m->state.grow(B));
+  for (DevBuf<float>* b : {&m->nsp, &m->d_logprob}) EIOKU_TRY(b->grow(B));
+  for (DevBuf<int>* b : {&m->d_sidx, &m->cur_tok, &m->lang_out}) EIOKU_TRY(b->grow(B));
+  for (DevBuf<int>* b : {&m->tokens, &m->d_ids}) EIOKU_TRY(b->grow(B * Tm));
   m->dcap = L;
   return EIOKU_OK;
 }
@@ -1405,28 +1372,28 @@ int ensure_lanes(eioku_whisper* m, int L) {
 // beam search only: the decoder workspace for L lanes and the beam buffers for L lanes / B windows, made on the first beam
 // call and grown as needed
 int ensure_beam(eioku_whisper* m, int B, int L) {
-  W_TRY(ensure_lanes(m, L));
+  EIOKU_TRY(ensure_lanes(m, L));
   const size_t Tm = m->cfg.max_target_positions;
   if (L > m->beam_lanes) {
     const size_t n = (size_t)L;
     m->beam_lanes = 0;
-    W_TRY(m->bpartial.grow(n * m->nblk * kNPB));
+    EIOKU_TRY(m->bpartial.grow(n * m->nblk * kNPB));
     for (int i = 0; i < 2; ++i) {
-      W_TRY(m->anc[i].grow(n * Tm));
-      W_TRY(m->hist[i].grow(n * Tm));
+      EIOKU_TRY(m->anc[i].grow(n * Tm));
+      EIOKU_TRY(m->hist[i].grow(n * Tm));
     }
-    for (Buf<int>* b : {&m->b_src, &m->b_tok, &m->b_fsrc}) W_TRY(b->grow(n));
-    for (Buf<float>* b : {&m->b_sum, &m->b_fsum}) W_TRY(b->grow(n));
-    for (Buf<int>* b : {&m->tr_src, &m->tr_tok}) W_TRY(b->grow(n * Tm));
+    for (DevBuf<int>* b : {&m->b_src, &m->b_tok, &m->b_fsrc}) EIOKU_TRY(b->grow(n));
+    for (DevBuf<float>* b : {&m->b_sum, &m->b_fsum}) EIOKU_TRY(b->grow(n));
+    for (DevBuf<int>* b : {&m->tr_src, &m->tr_tok}) EIOKU_TRY(b->grow(n * Tm));
     m->beam_lanes = L;
   }
   if (B > m->beam_windows) {
     const size_t n = (size_t)B;
     m->beam_windows = 0;
-    W_TRY(m->fin_tok.grow(n * kMaxFinish * Tm));
-    W_TRY(m->fin_sum.grow(n * kMaxFinish));
-    W_TRY(m->fin_n.grow(n * kMaxFinish));
-    for (Buf<int>* b : {&m->fin_count, &m->complete, &m->b_nlive, &m->b_nfin}) W_TRY(b->grow(n));
+    EIOKU_TRY(m->fin_tok.grow(n * kMaxFinish * Tm));
+    EIOKU_TRY(m->fin_sum.grow(n * kMaxFinish));
+    EIOKU_TRY(m->fin_n.grow(n * kMaxFinish));
+    for (DevBuf<int>* b : {&m->fin_count, &m->complete, &m->b_nlive, &m->b_nfin}) EIOKU_TRY(b->grow(n));
     m->beam_windows = B;
   }
   return EIOKU_OK;
@@ -1438,16 +1405,16 @@ int ensure_capacity(eioku_whisper* m, int B) {
   const auto& c = m->cfg;
   const size_t T2 = 2 * (size_t)c.max_source_positions, ctx = c.max_source_positions, d = c.d_model;
   m->cap = 0;
-  W_TRY(m->d_off.grow((size_t)B));
-  W_TRY(m->mel64.grow(B * c.n_mels * T2));
-  W_TRY(m->mel_mx.grow((size_t)B));
-  W_TRY(m->mel32.grow(B * c.n_mels * T2));
-  W_TRY(m->col1.grow(B * T2 * m->k1pad));
-  W_TRY(m->h1.grow(B * T2 * d));
-  W_TRY(m->col2.grow(B * ctx * 3 * d));
-  W_TRY(m->ew.grow(B * ctx, d, c.enc_ffn > c.dec_ffn ? c.enc_ffn : c.dec_ffn));
-  for (Buf<h16>* b : {&m->ek, &m->ev, &m->enc_out}) W_TRY(b->grow(B * ctx * d));
-  for (Buf<h16>* b : {&m->crossK, &m->crossV}) W_TRY(b->grow(c.dec_layers * B * ctx * d));
+  EIOKU_TRY(m->d_off.grow((size_t)B));
+  EIOKU_TRY(m->mel64.grow(B * c.n_mels * T2));
+  EIOKU_TRY(m->mel_mx.grow((size_t)B));
+  EIOKU_TRY(m->mel32.grow(B * c.n_mels * T2));
+  EIOKU_TRY(m->col1.grow(B * T2 * m->k1pad));
+  EIOKU_TRY(m->h1.grow(B * T2 * d));
+  EIOKU_TRY(m->col2.grow(B * ctx * 3 * d));
+  EIOKU_TRY(m->ew.grow(B * ctx, d, c.enc_ffn > c.dec_ffn ? c.enc_ffn : c.dec_ffn));
+  for (DevBuf<h16>* b : {&m->ek, &m->ev, &m->enc_out}) EIOKU_TRY(b->grow(B * ctx * d));
+  for (DevBuf<h16>* b : {&m->crossK, &m->crossV}) EIOKU_TRY(b->grow(c.dec_layers * B * ctx * d));
   m->cap = B;
   m->enc_B = 0;
   return ensure_lanes(m, B);
@@ -1458,9 +1425,9 @@ int ensure_prefill(eioku_whisper* m, int rows) {
   if (rows <= m->prows) return EIOKU_OK;
   const size_t n = (size_t)rows, d = m->cfg.d_model;
   m->prows = 0;
-  W_TRY(m->pw.grow(n, d, m->cfg.dec_ffn));
-  for (Buf<h16>* b : {&m->pk, &m->pv}) W_TRY(b->grow(n * d));
-  W_TRY(m->ppartial.grow(n * m->nblk * kNP));
+  EIOKU_TRY(m->pw.grow(n, d, m->cfg.dec_ffn));
+  for (DevBuf<h16>* b : {&m->pk, &m->pv}) EIOKU_TRY(b->grow(n * d));
+  EIOKU_TRY(m->ppartial.grow(n * m->nblk * kNP));
   m->prows = rows;
   return EIOKU_OK;
 }
@@ -1480,17 +1447,17 @@ int decoder_step(eioku_whisper* m, int B, int s, const int* toks, int tstride, i
   const int d = c.d_model, Tm = c.max_target_positions;
   Work& w = m->dw;
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, 0, toks, tstride, uniform, c.vocab, d, s, m->H(m->emb), m->F(m->dec_pos), w.x);
-  W_TRY(launched(m));
+  EIOKU_TRY(launched(m));
   for (int l = 0; l < c.dec_layers; ++l) {
     const Layer& L = m->dec[l];
     h16* sk = m->selfK + (size_t)l * m->dcap * Tm * d;
     h16* sv = m->selfV + (size_t)l * m->dcap * Tm * d;
-    W_TRY(ln_q<1>(m, w, B, L.self));
-    W_TRY(kv_proj<1>(m, w.h, B, L.self, sk + (size_t)s * d, sv + (size_t)s * d, (long long)Tm * d));
-    W_TRY((attn<1>(m, w.q, d, d, sk, sv, (long long)Tm * d, d, 1, s + 1, B, w.a, d, d, 1, anc, Tm)));
-    W_TRY(out_proj<1>(m, w, B, L.self));
-    W_TRY((cross_attn<1, 1>(m, w, B, 1, l, kv_div, kvmap)));
-    W_TRY(mlp<1>(m, w, B, L, c.dec_ffn));
+    EIOKU_TRY(ln_q<1>(m, w, B, L.self));
+    EIOKU_TRY(kv_proj<1>(m, w.h, B, L.self, sk + (size_t)s * d, sv + (size_t)s * d, (long long)Tm * d));
+    EIOKU_TRY((attn<1>(m, w.q, d, d, sk, sv, (long long)Tm * d, d, 1, s + 1, B, w.a, d, d, 1, anc, Tm)));
+    EIOKU_TRY(out_proj<1>(m, w, B, L.self));
+    EIOKU_TRY((cross_attn<1, 1>(m, w, B, 1, l, kv_div, kvmap)));
+    EIOKU_TRY(mlp<1>(m, w, B, L, c.dec_ffn));
   }
   return ln(m, w.x, B, d, m->dec_ln_g, m->dec_ln_b, w.h);
 }
@@ -1502,22 +1469,22 @@ int prefill(eioku_whisper* m, int R, int P, const int* ids, const int* kvmap, in
   const auto& c = m->cfg;
   const int d = c.d_model, Tm = c.max_target_positions, M = R * P;
   const long long bs = (long long)P * d;
-  W_TRY(ensure_prefill(m, M));
+  EIOKU_TRY(ensure_prefill(m, M));
   Work& w = m->pw;
   hipLaunchKernelGGL(k_embed_seq, dim3(M), dim3(256), 0, 0, ids, P, c.vocab, d, m->H(m->emb), m->F(m->dec_pos), w.x);
-  W_TRY(launched(m));
+  EIOKU_TRY(launched(m));
   for (int l = 0; l < c.dec_layers; ++l) {
     const Layer& L = m->dec[l];
     h16* sk = m->selfK + (size_t)l * m->dcap * Tm * d;
     h16* sv = m->selfV + (size_t)l * m->dcap * Tm * d;
-    W_TRY(ln_q<4>(m, w, M, L.self));
-    W_TRY(kv_proj<4>(m, w.h, M, L.self, m->pk, m->pv, d));
+    EIOKU_TRY(ln_q<4>(m, w, M, L.self));
+    EIOKU_TRY(kv_proj<4>(m, w.h, M, L.self, m->pk, m->pv, d));
     hipLaunchKernelGGL(k_kv_to_cache, dim3(P, R * G), dim3(256), 0, 0, m->pk, m->pv, P, d, G, lstride, Tm, sk, sv);
-    W_TRY(launched(m));
-    W_TRY((attn<2>(m, w.q, bs, d, m->pk, m->pv, bs, d, P, P, R, w.a, bs, d, 1, nullptr, 0, nullptr, true)));
-    W_TRY(out_proj<4>(m, w, M, L.self));
-    W_TRY((cross_attn<4, 2>(m, w, R, P, l, 1, kvmap, cap)));
-    W_TRY(mlp<4>(m, w, M, L, c.dec_ffn));
+    EIOKU_TRY(launched(m));
+    EIOKU_TRY((attn<2>(m, w.q, bs, d, m->pk, m->pv, bs, d, P, P, R, w.a, bs, d, 1, nullptr, 0, nullptr, true)));
+    EIOKU_TRY(out_proj<4>(m, w, M, L.self));
+    EIOKU_TRY((cross_attn<4, 2>(m, w, R, P, l, 1, kvmap, cap)));
+    EIOKU_TRY(mlp<4>(m, w, M, L, c.dec_ffn));
   }
   return ln(m, w.x, M, d, m->dec_ln_g, m->dec_ln_b, w.h);
 }
@@ -1578,7 +1545,7 @@ int greedy_select(eioku_whisper* m, int L, bool sample, int idx, bool info, int*
 int info_pair(eioku_whisper* m, int L, int* tokens = nullptr, int* cur_tok = nullptr) {
   LogitsArgs a;
   a.rules = 0, a.info = true;
-  W_TRY(logits<SEL_GREEDY>(m, L, a));
+  EIOKU_TRY(logits<SEL_GREEDY>(m, L, a));
   return greedy_select(m, L, false, 0, true, tokens, cur_tok);
 }
 
@@ -1596,7 +1563,7 @@ int prompted_args(eioku_whisper* m, const int32_t* prompts, int P, int sot_index
     EIOKU_REQUIRE(windows[b] >= 0 && windows[b] < m->enc_B, "window %d outside the %d encoded windows", windows[b], m->enc_B);
   for (size_t i = 0; i < (size_t)B * P; ++i)
     EIOKU_REQUIRE(prompts[i] >= 0 && prompts[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompts[i]);
-  W_TRY(ensure_lanes(m, B * G));
+  EIOKU_TRY(ensure_lanes(m, B * G));
   std::vector<int> map((size_t)2 * m->dcap, 0);
   for (int b = 0; b < B; ++b) map[b] = windows ? windows[b] : b;
   for (int l = 0; l < B * G; ++l) map[(size_t)m->dcap + l] = map[l / G];
@@ -1623,15 +1590,15 @@ struct Start {
 
 int start(eioku_whisper* m, const Start& st, int B, int G, int fill, int kv_div = 1, const uint8_t* anc = nullptr) {
   if (st.pre) {
-    W_TRY(prefill(m, B, st.P, m->d_ids, m->kvmap, fill, G));
-    W_TRY(gather_hidden(m, B, st.P, st.sot_index, 1));
-    W_TRY(info_pair(m, B));
+    EIOKU_TRY(prefill(m, B, st.P, m->d_ids, m->kvmap, fill, G));
+    EIOKU_TRY(gather_hidden(m, B, st.P, st.sot_index, 1));
+    EIOKU_TRY(info_pair(m, B));
     return gather_hidden(m, B * G, st.P, st.P - 1, G);
   }
   for (int s = 0; s < st.n_walk; ++s) {
-    W_TRY(decoder_step(m, B * G, s, nullptr, 1, st.prompt[s], kv_div, anc));
+    EIOKU_TRY(decoder_step(m, B * G, s, nullptr, 1, st.prompt[s], kv_div, anc));
     m->steps += 1;
-    if (s == 0 && st.info) W_TRY(info_pair(m, B * G, st.tokens, st.cur_tok));
+    if (s == 0 && st.info) EIOKU_TRY(info_pair(m, B * G, st.tokens, st.cur_tok));
   }
   return EIOKU_OK;
 }
@@ -1656,23 +1623,23 @@ int lane_decode(eioku_whisper* m, Start start_at, int B, int G, float temperatur
   start_at.n_walk = max_new > 0 ? P : 1;
   start_at.info = !merged;
   start_at.tokens = m->tokens, start_at.cur_tok = m->cur_tok;
-  W_TRY(start(m, start_at, B, G, G));
+  EIOKU_TRY(start(m, start_at, B, G, G));
   for (int idx = 0; idx < max_new; ++idx) {
     if (idx > 0) {
-      W_TRY(decoder_step(m, L, P - 1 + idx, m->cur_tok, 1, 0, 1, nullptr, lane_map));
+      EIOKU_TRY(decoder_step(m, L, P - 1 + idx, m->cur_tok, 1, 0, 1, nullptr, lane_map));
       m->steps += 1;
     }
     LogitsArgs a;
     if (temperature == 0.f) {
       a.info = merged && idx == 0;
-      W_TRY(logits<SEL_GREEDY>(m, L, a));
-      W_TRY(greedy_select(m, L, true, idx, a.info, m->tokens, m->cur_tok));
+      EIOKU_TRY(logits<SEL_GREEDY>(m, L, a));
+      EIOKU_TRY(greedy_select(m, L, true, idx, a.info, m->tokens, m->cur_tok));
     } else {
       a.temp = temperature, a.idx = idx;
-      W_TRY(logits<SEL_SAMPLE>(m, L, a));
+      EIOKU_TRY(logits<SEL_SAMPLE>(m, L, a));
       hipLaunchKernelGGL(k_sample_select, dim3(L), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, idx, m->tokens, Tm, m->cur_tok,
                          (float*)nullptr);
-      W_TRY(launched(m));
+      EIOKU_TRY(launched(m));
     }
     if ((idx + 1) % sync_every == 0 && idx + 1 < max_new) {  // read the lane states back: stop once every lane is done
       EIOKU_HIP_CHECK(hipMemcpy(st.data(), m->state, (size_t)L * sizeof(LaneState), hipMemcpyDeviceToHost));
@@ -1703,9 +1670,9 @@ int walked_logits(eioku_whisper* m, int B, int T, int s0, float* out) {
   LogitsArgs a;
   a.rules = 0, a.raw_ld = (long long)T * m->cfg.vocab;
   for (int s = s0; s < T; ++s) {
-    W_TRY(decoder_step(m, B, s, m->d_ids + s, T, 0));
+    EIOKU_TRY(decoder_step(m, B, s, m->d_ids + s, T, 0));
     a.raw_out = out + (size_t)s * m->cfg.vocab;
-    W_TRY(logits<SEL_GREEDY>(m, B, a));
+    EIOKU_TRY(logits<SEL_GREEDY>(m, B, a));
   }
   return EIOKU_OK;
 }
@@ -1743,10 +1710,10 @@ struct Download {
 // supplied logits [L][vocab] up, `launch` on the device copy, the small results down
 template <typename F>
 int on_supplied_logits(eioku_whisper* m, const float* logits_in, int L, F launch, std::initializer_list<Download> results) {
-  Buf<float> d_in;
-  W_TRY(d_in.grow((size_t)L * m->cfg.vocab));
+  DevBuf<float> d_in;
+  EIOKU_TRY(d_in.grow((size_t)L * m->cfg.vocab));
   EIOKU_HIP_CHECK(hipMemcpy(d_in, logits_in, (size_t)L * m->cfg.vocab * sizeof(float), hipMemcpyHostToDevice));
-  W_TRY(launch(d_in.p));
+  EIOKU_TRY(launch(d_in.p));
   for (const Download& r : results)
     if (r.host) EIOKU_HIP_CHECK(hipMemcpy(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost));
   return EIOKU_OK;
@@ -1784,7 +1751,7 @@ int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper** out) {
     Tensor t;
     t.name = n, t.rows = rows, t.cols = cols, t.kind = kind, t.cin = cin;
     t.ldk = kind == T_CONV ? round_up(cols, 32) : cols;
-    m->tensors.push_back(t);
+    m->tensors.push_back(std::move(t));
     return (int)m->tensors.size() - 1;
   };
   auto add_attn = [&](const std::string& p, const std::string& lnp) {
@@ -1835,10 +1802,7 @@ int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper** out) {
   };
   for (auto& t : m->tensors) {
     const size_t bytes = (size_t)t.rows * t.ldk * (t.kind == T_F32 ? 4 : 2);
-    if (hipMalloc(&t.dev, bytes) != hipSuccess) {
-      set_error("hipMalloc failed for %s", t.name.c_str());
-      return fail(EIOKU_ENOMEM);
-    }
+    if (t.dev.grow(bytes)) return fail(EIOKU_ENOMEM);
   }
   // constants: periodic Hann window, DFT twiddles, mel filterbank, per-id flags
   std::vector<double> hann(kNfft), tc(kNfft), ts(kNfft);
@@ -1879,9 +1843,7 @@ int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper** out) {
 void eioku_whisper_destroy(eioku_whisper* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (auto& t : m->tensors)
-    if (t.dev) (void)hipFree(t.dev);
-  delete m;  // every workspace buffer frees itself
+  delete m;  // every buffer frees itself
 }
 
 int eioku_whisper_num_tensors(const eioku_whisper* m) { return m ? (int)m->tensors.size() : 0; }
@@ -1901,16 +1863,16 @@ int eioku_whisper_set_tensor(eioku_whisper* m, int idx, const float* host, size_
   auto& t = m->tensors[idx];
   EIOKU_REQUIRE(numel == t.numel(), "%s: expected %zu elements, got %zu", t.name.c_str(), t.numel(), numel);
   if (t.kind == T_F32) {
-    EIOKU_HIP_CHECK(hipMemcpy(t.dev, host, numel * sizeof(float), hipMemcpyHostToDevice));
+    EIOKU_HIP_CHECK(hipMemcpy(t.dev.p, host, numel * sizeof(float), hipMemcpyHostToDevice));
   } else {
-    Buf<float> stage;
-    W_TRY(stage.grow(numel));
+    DevBuf<float> stage;
+    EIOKU_TRY(stage.grow(numel));
     EIOKU_HIP_CHECK(hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice));
     if (t.kind == T_F16) {
-      hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage, numel, (h16*)t.dev);
+      hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage, numel, (h16*)t.dev.p);
     } else {
       const size_t n = (size_t)t.rows * t.ldk;
-      hipLaunchKernelGGL(k_cvt_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage, t.rows, t.cin, t.ldk, (h16*)t.dev);
+      hipLaunchKernelGGL(k_cvt_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage, t.rows, t.cin, t.ldk, (h16*)t.dev.p);
     }
     EIOKU_LAUNCH_CHECK();
     EIOKU_HIP_CHECK(hipDeviceSynchronize());
@@ -1922,7 +1884,7 @@ int eioku_whisper_set_tensor(eioku_whisper* m, int idx, const float* host, size_
 int eioku_whisper_set_audio(eioku_whisper* m, const float* samples, long long n) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && n >= 0 && (samples || n == 0), "bad argument");
-  W_TRY(m->samples.grow((size_t)n));
+  EIOKU_TRY(m->samples.grow((size_t)n));
   m->n_samples = n;
   if (n) EIOKU_HIP_CHECK(hipMemcpy(m->samples, samples, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   return EIOKU_OK;
@@ -1933,7 +1895,7 @@ int eioku_whisper_logmel(eioku_whisper* m, const long long* offsets, int B, floa
   EIOKU_REQUIRE(m && offsets && B > 0 && B <= 64, "bad argument (1 <= B <= 64)");
   EIOKU_REQUIRE(m->samples, "no audio: call eioku_whisper_set_audio first");
   for (int b = 0; b < B; ++b) EIOKU_REQUIRE(offsets[b] >= 0, "negative window offset");
-  W_TRY(ensure_capacity(m, B));
+  EIOKU_TRY(ensure_capacity(m, B));
   const auto& c = m->cfg;
   const int T = 2 * c.max_source_positions;
   const long long per = (long long)c.n_mels * T, total = per * B;
@@ -1953,9 +1915,9 @@ int eioku_whisper_logmel(eioku_whisper* m, const long long* offsets, int B, floa
 int eioku_whisper_encode(eioku_whisper* m, const float* mel, int B) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && B > 0 && B <= 64, "bad argument (1 <= B <= 64)");
-  W_TRY(check_weights(m));
+  EIOKU_TRY(check_weights(m));
   EIOKU_REQUIRE(mel || B <= m->cap, "no log-mel result for %d windows", B);
-  W_TRY(ensure_capacity(m, B));
+  EIOKU_TRY(ensure_capacity(m, B));
   const auto& c = m->cfg;
   const int d = c.d_model, ctx = c.max_source_positions, T2 = 2 * ctx, M = B * ctx;
   Work& w = m->ew;
@@ -1967,22 +1929,22 @@ int eioku_whisper_encode(eioku_whisper* m, const float* mel, int B) {
     const size_t n1 = (size_t)B * T2 * m->k1pad, n2 = (size_t)M * 3 * d;
     hipLaunchKernelGGL(k_im2col_mel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, 0, m->mel32, B, c.n_mels, T2, m->k1pad, m->col1);
     EIOKU_LAUNCH_CHECK();
-    W_TRY((gemm<4, EPI_GELU_F16>(m, m->col1, m->k1pad, m->H(m->conv1), m->k1pad, m->F(m->conv1b), B * T2, d, m->k1pad, m->h1, d)));
+    EIOKU_TRY((gemm<4, EPI_GELU_F16>(m, m->col1, m->k1pad, m->H(m->conv1), m->k1pad, m->F(m->conv1b), B * T2, d, m->k1pad, m->h1, d)));
     hipLaunchKernelGGL(k_im2col_s2, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, 0, m->h1, B, d, T2, m->col2);
     EIOKU_LAUNCH_CHECK();
-    W_TRY((gemm<4, EPI_GELU_POS>(m, m->col2, 3 * d, m->H(m->conv2), 3 * d, m->F(m->conv2b), M, d, 3 * d, w.x, d, m->F(m->enc_pos), ctx)));
+    EIOKU_TRY((gemm<4, EPI_GELU_POS>(m, m->col2, 3 * d, m->H(m->conv2), 3 * d, m->F(m->conv2b), M, d, 3 * d, w.x, d, m->F(m->enc_pos), ctx)));
   }
   for (int l = 0; l < c.enc_layers; ++l) {
     const Layer& L = m->enc[l];
-    W_TRY(ln_q<4>(m, w, M, L.self));
-    W_TRY(kv_proj<4>(m, w.h, M, L.self, m->ek, m->ev, d));
-    W_TRY((attn<2>(m, w.q, (long long)ctx * d, d, m->ek, m->ev, (long long)ctx * d, d, ctx, ctx, B, w.a, (long long)ctx * d, d)));
-    W_TRY(out_proj<4>(m, w, M, L.self));
-    W_TRY(mlp<4>(m, w, M, L, c.enc_ffn));
+    EIOKU_TRY(ln_q<4>(m, w, M, L.self));
+    EIOKU_TRY(kv_proj<4>(m, w.h, M, L.self, m->ek, m->ev, d));
+    EIOKU_TRY((attn<2>(m, w.q, (long long)ctx * d, d, m->ek, m->ev, (long long)ctx * d, d, ctx, ctx, B, w.a, (long long)ctx * d, d)));
+    EIOKU_TRY(out_proj<4>(m, w, M, L.self));
+    EIOKU_TRY(mlp<4>(m, w, M, L, c.enc_ffn));
   }
-  W_TRY(ln(m, w.x, M, d, m->enc_ln_g, m->enc_ln_b, m->enc_out));
+  EIOKU_TRY(ln(m, w.x, M, d, m->enc_ln_g, m->enc_ln_b, m->enc_out));
   for (int l = 0; l < c.dec_layers; ++l)  // cross-attention keys and values, once per window
-    W_TRY(kv_proj<4>(m, m->enc_out, M, m->dec[l].cross, m->crossK + (size_t)l * m->cap * ctx * d,
+    EIOKU_TRY(kv_proj<4>(m, m->enc_out, M, m->dec[l].cross, m->crossK + (size_t)l * m->cap * ctx * d,
                      m->crossV + (size_t)l * m->cap * ctx * d, d));
   EIOKU_HIP_CHECK(hipDeviceSynchronize());
   m->enc_B = B;
@@ -2008,7 +1970,7 @@ int eioku_whisper_decode(eioku_whisper* m, const int32_t* prompt, int prompt_len
   EIOKU_REQUIRE(max_new == 0 || (tokens_out && n_out && sum_logprob), "NULL output");
   for (int i = 0; i < prompt_len; ++i) EIOKU_REQUIRE(prompt[i] >= 0 && prompt[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompt[i]);
   std::vector<LaneState> st;
-  W_TRY(lane_decode(m, Start{prompt, prompt_len, false, 0}, B, 1, 0.f, nullptr, max_new, sync_every, tokens_out, n_out, sum_logprob, st));
+  EIOKU_TRY(lane_decode(m, Start{prompt, prompt_len, false, 0}, B, 1, 0.f, nullptr, max_new, sync_every, tokens_out, n_out, sum_logprob, st));
   if (no_speech_prob) EIOKU_HIP_CHECK(hipMemcpy(no_speech_prob, m->nsp, (size_t)B * sizeof(float), hipMemcpyDeviceToHost));
   if (lang_out) EIOKU_HIP_CHECK(hipMemcpy(lang_out, m->lang_out, (size_t)B * sizeof(int), hipMemcpyDeviceToHost));
   return EIOKU_OK;
@@ -2022,10 +1984,10 @@ int eioku_whisper_decode_prompted(eioku_whisper* m, const int32_t* prompts, int 
   EIOKU_REQUIRE(temperature >= 0.f && std::isfinite(temperature), "temperature %g must be a finite number >= 0", (double)temperature);
   if (temperature == 0.f) EIOKU_REQUIRE(G == 1 && !seeds, "temperature 0 is the greedy rule: one row per window and no seeds");
   else EIOKU_REQUIRE(seeds, "sampling at temperature %g needs a seed per lane", (double)temperature);
-  W_TRY(prompted_args(m, prompts, P, sot_index, windows, B, G, max_new));
+  EIOKU_TRY(prompted_args(m, prompts, P, sot_index, windows, B, G, max_new));
   EIOKU_REQUIRE(tokens_out && n_out && sum_logprob && best_out, "NULL output");
   std::vector<LaneState> st;
-  W_TRY(lane_decode(m, Start{prompts, P, true, sot_index}, B, G, temperature, seeds, max_new, sync_every, tokens_out, n_out, sum_logprob, st));
+  EIOKU_TRY(lane_decode(m, Start{prompts, P, true, sot_index}, B, G, temperature, seeds, max_new, sync_every, tokens_out, n_out, sum_logprob, st));
   for (int b = 0; b < B; ++b) {  // the row with the largest sum / max(1, tokens before EOT), the earlier row on a tie
     int best = 0;
     double best_score = 0;
@@ -2048,11 +2010,11 @@ int eioku_whisper_forced_logits(eioku_whisper* m, const int32_t* ids, int T, int
   const int V = m->cfg.vocab;
   for (size_t i = 0; i < (size_t)B * T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < V, "id %d outside the vocabulary", ids[i]);
   EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, ids, (size_t)B * T * sizeof(int), hipMemcpyHostToDevice));
-  Buf<float> d_out;
-  W_TRY(d_out.grow((size_t)B * T * V));
+  DevBuf<float> d_out;
+  EIOKU_TRY(d_out.grow((size_t)B * T * V));
   const std::vector<LaneState> st(B, kFreshLane);
   EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
-  W_TRY(walked_logits(m, B, T, 0, d_out));
+  EIOKU_TRY(walked_logits(m, B, T, 0, d_out));
   EIOKU_HIP_CHECK(hipMemcpy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost));
   return EIOKU_OK;
 }
@@ -2064,27 +2026,27 @@ int eioku_whisper_prefill_logits(eioku_whisper* m, const int32_t* ids, int T, in
   EIOKU_REQUIRE(B > 0 && B == m->enc_B, "prefill_logits of %d lanes needs an encode of the same %d windows first", B, m->enc_B);
   const int V = m->cfg.vocab, P = n_prefill;
   for (size_t i = 0; i < (size_t)B * T; ++i) EIOKU_REQUIRE(ids[i] >= 0 && ids[i] < V, "id %d outside the vocabulary", ids[i]);
-  W_TRY(ensure_lanes(m, B));
+  EIOKU_TRY(ensure_lanes(m, B));
   std::vector<int> head((size_t)B * P);
   for (int b = 0; b < B; ++b)
     for (int t = 0; t < P; ++t) head[(size_t)b * P + t] = ids[(size_t)b * T + t];
-  Buf<int> d_head;
-  Buf<float> d_out;
-  W_TRY(d_head.grow(head.size()));
-  W_TRY(d_out.grow((size_t)B * T * V));
+  DevBuf<int> d_head;
+  DevBuf<float> d_out;
+  EIOKU_TRY(d_head.grow(head.size()));
+  EIOKU_TRY(d_out.grow((size_t)B * T * V));
   const std::vector<LaneState> st(B, kFreshLane);
   EIOKU_HIP_CHECK(hipMemcpy(m->state, st.data(), (size_t)B * sizeof(LaneState), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, ids, (size_t)B * T * sizeof(int), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(d_head, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice));
   reset_counts(m);
-  W_TRY(prefill(m, B, P, d_head, nullptr, 1, 1));
+  EIOKU_TRY(prefill(m, B, P, d_head, nullptr, 1, 1));
   for (int b = 0; b < B; ++b) {  // the logits of row b's P positions: out[b][0 .. P - 1]; outside the launch and flop counts
     hipLaunchKernelGGL((k_logits<false>), dim3(m->nblk), dim3(256), 0, 0, m->pw.h + (size_t)b * P * m->cfg.d_model, m->cfg.d_model,
                        m->H(m->emb), nullptr, P, m->sel, m->flags, m->state, 0, m->ppartial, m->nblk, d_out + (size_t)b * T * V,
                        (long long)V, nullptr, nullptr, m->nlang, 0, 1.f, nullptr, nullptr, 0);
     EIOKU_LAUNCH_CHECK();
   }
-  W_TRY(walked_logits(m, B, T, P, d_out));  // the positions after the prefill walk on its keys and values
+  EIOKU_TRY(walked_logits(m, B, T, P, d_out));  // the positions after the prefill walk on its keys and values
   EIOKU_HIP_CHECK(hipMemcpy(out, d_out, (size_t)B * T * V * sizeof(float), hipMemcpyDeviceToHost));
   return EIOKU_OK;
 }
@@ -2093,15 +2055,15 @@ int eioku_whisper_select(eioku_whisper* m, const float* logits_in, int B, const 
                          const int32_t* prefix_len, int32_t* token_out, float* logprob_out, float* masked_out) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && logits_in && B > 0 && B <= 64 && prefix_len && token_out && logprob_out && prefix_cap >= 0, "bad argument");
-  W_TRY(ensure_capacity(m, B));
-  W_TRY(upload_prefix_states(m, B, prefix, prefix_cap, prefix_len));
+  EIOKU_TRY(ensure_capacity(m, B));
+  EIOKU_TRY(upload_prefix_states(m, B, prefix, prefix_cap, prefix_len));
   const size_t V = m->cfg.vocab;
-  Buf<float> d_msk;
-  if (masked_out) W_TRY(d_msk.grow(B * V));
+  DevBuf<float> d_msk;
+  if (masked_out) EIOKU_TRY(d_msk.grow(B * V));
   auto launch = [&](const float* d_in) -> int {
     LogitsArgs a;
     a.supplied = d_in, a.masked = d_msk;
-    W_TRY(logits<SEL_GREEDY>(m, B, a));
+    EIOKU_TRY(logits<SEL_GREEDY>(m, B, a));
     hipLaunchKernelGGL(k_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 1, 0, 0, m->info, m->nlang, m->lang_ids,
                        (int*)nullptr, 0, m->cur_tok, m->nsp, m->lang_out, m->d_logprob);
     EIOKU_LAUNCH_CHECK();
@@ -2118,17 +2080,17 @@ int eioku_whisper_sample(eioku_whisper* m, const float* logits_in, int B, const 
   EIOKU_REQUIRE(m && logits_in && B > 0 && B <= 64 && prefix_len && seeds && idx && token_out && logprob_out && prefix_cap >= 0,
                 "bad argument");
   EIOKU_REQUIRE(temperature > 0.f && std::isfinite(temperature), "temperature %g must be a finite number > 0", (double)temperature);
-  W_TRY(ensure_capacity(m, B));
+  EIOKU_TRY(ensure_capacity(m, B));
   for (int b = 0; b < B; ++b)
     EIOKU_REQUIRE(idx[b] >= 0 && idx[b] < m->cfg.max_target_positions, "sample index %d outside 0..%d", idx[b],
                   m->cfg.max_target_positions - 1);
-  W_TRY(upload_prefix_states(m, B, prefix, prefix_cap, prefix_len));
+  EIOKU_TRY(upload_prefix_states(m, B, prefix, prefix_cap, prefix_len));
   EIOKU_HIP_CHECK(hipMemcpy(m->d_seeds, seeds, (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->d_sidx, idx, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
   auto launch = [&](const float* d_in) -> int {
     LogitsArgs a;
     a.supplied = d_in, a.temp = temperature, a.sidx = m->d_sidx;
-    W_TRY(logits<SEL_SAMPLE>(m, B, a));
+    EIOKU_TRY(logits<SEL_SAMPLE>(m, B, a));
     hipLaunchKernelGGL(k_sample_select, dim3(B), dim3(64), 0, 0, m->partial, m->nblk, m->sel, m->state, 0, (int*)nullptr, 0, m->cur_tok,
                        m->d_logprob);
     EIOKU_LAUNCH_CHECK();
@@ -2164,7 +2126,7 @@ int beam_impl(eioku_whisper* m, const int32_t* prompt, int prompt_len, bool pre,
               int32_t* n_hyp, int32_t* best_out, float* no_speech_prob, int32_t* lang_out, int32_t* trace_src, int32_t* trace_tok) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && prompt && prompt_len >= 1 && max_new >= 1, "bad argument");
-  W_TRY(beam_args(m, B, W, C));
+  EIOKU_TRY(beam_args(m, B, W, C));
   if (!pre) {
     EIOKU_REQUIRE(B == m->enc_B, "beam decode of %d windows needs an encode of the same %d windows first", B, m->enc_B);
     EIOKU_REQUIRE(prompt_len + max_new <= m->cfg.max_target_positions, "prompt %d + %d new tokens exceed max_target_positions %d",
@@ -2176,8 +2138,8 @@ int beam_impl(eioku_whisper* m, const int32_t* prompt, int prompt_len, bool pre,
       EIOKU_REQUIRE(prompt[i] >= 0 && prompt[i] < m->cfg.vocab, "prompt id %d outside the vocabulary", prompt[i]);
   if (sync_every < 1) sync_every = 1;
   const int L = B * W, Tm = m->cfg.max_target_positions, eot = m->cfg.eot, H = W > C ? W : C;
-  W_TRY(ensure_beam(m, B, L));
-  if (pre) W_TRY(prompted_args(m, prompt, prompt_len, sot_index, windows, B, W, max_new));
+  EIOKU_TRY(ensure_beam(m, B, L));
+  if (pre) EIOKU_TRY(prompted_args(m, prompt, prompt_len, sot_index, windows, B, W, max_new));
   const int* lane_map = pre ? m->kvmap + m->dcap : nullptr;
   reset_counts(m);
   // slot 0 of every window is live with sum 0, the others are dead; every ancestry row names its own lane
@@ -2202,17 +2164,17 @@ int beam_impl(eioku_whisper* m, const int32_t* prompt, int prompt_len, bool pre,
   int cur = 0;
   std::vector<int> flags(B);
   // prefilled: the prompt in one pass per window; every slot starts from the window's hidden state at the last prompt position
-  W_TRY(start(m, Start{prompt, prompt_len, pre, sot_index, prompt_len, true, nullptr, nullptr}, B, W, 1, W, m->anc[cur]));
+  EIOKU_TRY(start(m, Start{prompt, prompt_len, pre, sot_index, prompt_len, true, nullptr, nullptr}, B, W, 1, W, m->anc[cur]));
   LogitsArgs beam;
   beam.nc = W + 1;
   for (int idx = 0; idx < max_new; ++idx) {
     const int s = prompt_len - 1 + idx;
     if (idx > 0) {
-      W_TRY(decoder_step(m, L, s, m->cur_tok, 1, 0, W, m->anc[cur], lane_map));
+      EIOKU_TRY(decoder_step(m, L, s, m->cur_tok, 1, 0, W, m->anc[cur], lane_map));
       m->steps += 1;
     }
-    W_TRY(logits<SEL_BEAM>(m, L, beam));
-    W_TRY(beam_select(m, B, W, C, s, idx, m->anc[cur], m->anc[cur ^ 1], m->hist[cur], m->hist[cur ^ 1],
+    EIOKU_TRY(logits<SEL_BEAM>(m, L, beam));
+    EIOKU_TRY(beam_select(m, B, W, C, s, idx, m->anc[cur], m->anc[cur ^ 1], m->hist[cur], m->hist[cur ^ 1],
                       trace ? m->tr_src + (size_t)idx * L : nullptr, trace ? m->tr_tok + (size_t)idx * L : nullptr));
     cur ^= 1;
     if ((idx + 1) % sync_every == 0 && idx + 1 < max_new) {  // stop once every window is complete
@@ -2302,18 +2264,18 @@ int eioku_whisper_beam_select(eioku_whisper* m, const float* logits_in, int B, i
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && logits_in && prefix_len && sums && fin_count && prefix_cap >= 0, "bad argument");
   EIOKU_REQUIRE(src_out && tok_out && sum_out && n_live && fsrc_out && fsum_out && n_fin && fin_count_out && complete_out, "NULL output");
-  W_TRY(beam_args(m, B, W, C));
+  EIOKU_TRY(beam_args(m, B, W, C));
   const int L = B * W;
-  W_TRY(ensure_beam(m, B, L));
+  EIOKU_TRY(ensure_beam(m, B, L));
   for (int b = 0; b < B; ++b) EIOKU_REQUIRE(fin_count[b] >= 0 && fin_count[b] < C, "finished count %d outside 0..%d", fin_count[b], C - 1);
-  W_TRY(upload_prefix_states(m, L, prefix, prefix_cap, prefix_len, sums));
+  EIOKU_TRY(upload_prefix_states(m, L, prefix, prefix_cap, prefix_len, sums));
   const std::vector<int> zeros(B, 0);
   EIOKU_HIP_CHECK(hipMemcpy(m->fin_count, fin_count, (size_t)B * sizeof(int), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->complete, zeros.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
   auto launch = [&](const float* d_in) -> int {
     LogitsArgs a;
     a.supplied = d_in, a.nc = W + 1;
-    W_TRY(logits<SEL_BEAM>(m, L, a));
+    EIOKU_TRY(logits<SEL_BEAM>(m, L, a));
     return beam_select(m, B, W, C, 0, 0, nullptr, nullptr, nullptr, nullptr, m->b_src, m->b_tok);
   };
   const size_t li = (size_t)L * sizeof(int), lf = (size_t)L * sizeof(float), bi = (size_t)B * sizeof(int);
@@ -2332,7 +2294,7 @@ constexpr int kMaxDtw = 4096;  // token rows / frames the debug DTW entry takes
 // mean / std over the token rows, then the cost; meta on the device: n_tok [R], nF [R]
 int align_cost_launch(eioku_whisper* m, const float* A, int R, int H, int T, int ldf, int S, const int* d_ntok, const int* d_nF,
                       int Nmax, float* cost) {
-  W_TRY(m->al_stat.grow((size_t)R * H * 2 * ldf));
+  EIOKU_TRY(m->al_stat.grow((size_t)R * H * 2 * ldf));
   hipLaunchKernelGGL(k_align_stats, dim3((ldf + 255) / 256, H, R), dim3(256), 0, 0, A, H, T, ldf, d_ntok, d_nF, m->al_stat);
   EIOKU_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_align_cost, dim3((ldf + 255) / 256, Nmax, R), dim3(256), 0, 0, A, m->al_stat, H, T, ldf, S, d_ntok, d_nF, Nmax,
@@ -2345,7 +2307,7 @@ int align_cost_launch(eioku_whisper* m, const float* A, int R, int H, int T, int
 int dtw_launch(eioku_whisper* m, const float* cost, int R, int Nmax, int ldf, const int* d_nN, const int* d_nF, int* jump, int* path,
                int* path_len) {
   const int tw = (ldf + 15) / 16;
-  W_TRY(m->al_trace.grow((size_t)R * Nmax * tw));
+  EIOKU_TRY(m->al_trace.grow((size_t)R * Nmax * tw));
   hipLaunchKernelGGL(k_dtw, dim3(R), dim3(kDtwRows), (size_t)ldf * sizeof(float), 0, cost, Nmax, ldf, d_nN, d_nF, m->al_trace, tw, jump,
                      path, path_len);
   return launched(m);
@@ -2408,14 +2370,14 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
     Fmax = n_frames[r] / 2 > Fmax ? n_frames[r] / 2 : Fmax;
     Mp += (size_t)(n_tok[r] - S - 2);
   }
-  W_TRY(check_weights(m));
+  EIOKU_TRY(check_weights(m));
   std::vector<int> heads = m->align_heads;
   if (heads.empty())
     for (int l = c.dec_layers / 2; l < c.dec_layers; ++l)
       for (int h = 0; h < c.heads; ++h) heads.push_back(l), heads.push_back(h);
   const int Hs = (int)heads.size() / 2, Nmax = T - S - 1, nblk = (c.eot + 63) / 64;
   EIOKU_REQUIRE(Hs > 0 && nblk > 0, "no alignment heads");
-  W_TRY(ensure_lanes(m, R));
+  EIOKU_TRY(ensure_lanes(m, R));
   // host lists: kvmap [R]; meta = n_tok, nF, nN [R each]; rows = hidden row, target id, output index [Mp each]
   std::vector<int> map((size_t)R), meta((size_t)3 * R), rows(3 * Mp);
   size_t k = 0;
@@ -2429,14 +2391,14 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
     }
   }
   const size_t nA = (size_t)R * Hs * T * Fmax, nC = (size_t)R * Nmax * Fmax, nJ = (size_t)R * Nmax;
-  W_TRY(m->al_A.grow(nA));
-  W_TRY(m->al_cost.grow(nC));
-  W_TRY(m->al_jump.grow(nJ));
-  W_TRY(m->al_prob.grow(nJ));
-  W_TRY(m->al_meta.grow(meta.size()));
-  W_TRY(m->al_rows.grow(rows.size()));
-  W_TRY(m->al_part.grow(Mp * nblk * 2));
-  W_TRY(m->al_tgt.grow(Mp));
+  EIOKU_TRY(m->al_A.grow(nA));
+  EIOKU_TRY(m->al_cost.grow(nC));
+  EIOKU_TRY(m->al_jump.grow(nJ));
+  EIOKU_TRY(m->al_prob.grow(nJ));
+  EIOKU_TRY(m->al_meta.grow(meta.size()));
+  EIOKU_TRY(m->al_rows.grow(rows.size()));
+  EIOKU_TRY(m->al_part.grow(Mp * nblk * 2));
+  EIOKU_TRY(m->al_tgt.grow(Mp));
   EIOKU_HIP_CHECK(hipMemcpy(m->kvmap, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->d_ids, seq, (size_t)R * T * sizeof(int), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -2446,11 +2408,11 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
   EIOKU_HIP_CHECK(hipMemset(m->al_prob, 0, nJ * sizeof(float)));
   const int *d_ntok = m->al_meta, *d_nF = m->al_meta + R, *d_nN = m->al_meta + 2 * R;
   StageEvents stage;
-  W_TRY(stage.create());
+  EIOKU_TRY(stage.create());
   hipEvent_t* ev = stage.ev;
   EIOKU_HIP_CHECK(hipEventRecord(ev[0], 0));
   const AlignCapture cap{heads.data(), Hs, Fmax, d_nF, m->al_A};
-  W_TRY(prefill(m, R, T, m->d_ids, m->kvmap, 1, 1, &cap));
+  EIOKU_TRY(prefill(m, R, T, m->d_ids, m->kvmap, 1, 1, &cap));
   hipLaunchKernelGGL(k_align_logits, dim3(nblk), dim3(256), 0, 0, m->pw.h, d, m->H(m->emb), m->al_rows, m->al_rows + Mp, (int)Mp, c.eot,
                      m->al_part, nblk, m->al_tgt);
   EIOKU_LAUNCH_CHECK();
@@ -2459,9 +2421,9 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
   m->flops += 2.0 * (double)Mp * c.eot * d;
   m->launches += 2;
   EIOKU_HIP_CHECK(hipEventRecord(ev[1], 0));
-  W_TRY(align_cost_launch(m, m->al_A, R, Hs, T, Fmax, S, d_ntok, d_nF, Nmax, m->al_cost));
+  EIOKU_TRY(align_cost_launch(m, m->al_A, R, Hs, T, Fmax, S, d_ntok, d_nF, Nmax, m->al_cost));
   EIOKU_HIP_CHECK(hipEventRecord(ev[2], 0));
-  W_TRY(dtw_launch(m, m->al_cost, R, Nmax, Fmax, d_nN, d_nF, m->al_jump, nullptr, nullptr));
+  EIOKU_TRY(dtw_launch(m, m->al_cost, R, Nmax, Fmax, d_nN, d_nF, m->al_jump, nullptr, nullptr));
   EIOKU_HIP_CHECK(hipEventRecord(ev[3], 0));
   EIOKU_HIP_CHECK(hipEventSynchronize(ev[3]));
   for (int i = 0; i < 3; ++i) {
@@ -2483,12 +2445,12 @@ int eioku_whisper_align_cost(eioku_whisper* m, const float* A, int H, int T, int
   m->launches = 0;
   const int N = T - sot_len - 1;
   const int meta[2] = {T, F};
-  W_TRY(m->al_A.grow((size_t)H * T * F));
-  W_TRY(m->al_cost.grow((size_t)N * F));
-  W_TRY(m->al_meta.grow(2));
+  EIOKU_TRY(m->al_A.grow((size_t)H * T * F));
+  EIOKU_TRY(m->al_cost.grow((size_t)N * F));
+  EIOKU_TRY(m->al_meta.grow(2));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_A, A, (size_t)H * T * F * sizeof(float), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta, sizeof(meta), hipMemcpyHostToDevice));
-  W_TRY(align_cost_launch(m, m->al_A, 1, H, T, F, sot_len, m->al_meta, m->al_meta + 1, N, m->al_cost));
+  EIOKU_TRY(align_cost_launch(m, m->al_A, 1, H, T, F, sot_len, m->al_meta, m->al_meta + 1, N, m->al_cost));
   EIOKU_HIP_CHECK(hipMemcpy(cost_out, m->al_cost, (size_t)N * F * sizeof(float), hipMemcpyDeviceToHost));
   return EIOKU_OK;
 }
@@ -2501,13 +2463,13 @@ int eioku_whisper_dtw(eioku_whisper* m, const float* cost, int N, int F, int32_t
   EIOKU_REQUIRE(N >= 1 && N <= kMaxDtw && F >= 1 && F <= kMaxDtw, "dtw of %d token rows x %d frames: both 1..%d", N, F, kMaxDtw);
   m->launches = 0;
   const int meta[2] = {N, F};
-  W_TRY(m->al_cost.grow((size_t)N * F));
-  W_TRY(m->al_jump.grow((size_t)N));
-  W_TRY(m->al_meta.grow(3));
-  W_TRY(m->al_path.grow((size_t)2 * (N + F)));
+  EIOKU_TRY(m->al_cost.grow((size_t)N * F));
+  EIOKU_TRY(m->al_jump.grow((size_t)N));
+  EIOKU_TRY(m->al_meta.grow(3));
+  EIOKU_TRY(m->al_path.grow((size_t)2 * (N + F)));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_cost, cost, (size_t)N * F * sizeof(float), hipMemcpyHostToDevice));
   EIOKU_HIP_CHECK(hipMemcpy(m->al_meta, meta, sizeof(meta), hipMemcpyHostToDevice));
-  W_TRY(dtw_launch(m, m->al_cost, 1, N, F, m->al_meta, m->al_meta + 1, m->al_jump, m->al_path, m->al_meta + 2));
+  EIOKU_TRY(dtw_launch(m, m->al_cost, 1, N, F, m->al_meta, m->al_meta + 1, m->al_jump, m->al_path, m->al_meta + 2));
   EIOKU_HIP_CHECK(hipMemcpy(jump_out, m->al_jump, (size_t)N * sizeof(int), hipMemcpyDeviceToHost));
   if (path_len) {
     int n = 0;

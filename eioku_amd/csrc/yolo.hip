@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "convnet.h"
 #include "yolo_ops.h"
 
 #include <cstdlib>
@@ -27,8 +28,7 @@ constexpr int kRegMax = 16;
 struct Buf {
   int level;  // 0 = input resolution, k = H / 2^k
   int ch;
-  __half* ptr = nullptr;
-  size_t cap = 0;  // bytes
+  DevBuf<__half> ptr;
 };
 
 enum OpKind { kConv, kPool, kUp };
@@ -51,41 +51,31 @@ struct Op {
 
 struct eioku_yolo {
   int ch[5], depth[4], nc;
-  std::vector<std::string> names;
-  std::vector<std::array<int, 4>> shapes;  // cout, cin, k, stride
-  std::vector<ConvWeights> weights;
-  std::vector<bool> set;
+  ConvStack convs;
   std::vector<Buf> bufs;
   std::vector<Op> ops;
   int in_buf = -1;
   int head_src[3];
   // per-shape workspace
   int cur_n = 0, cur_h = 0, cur_w = 0;
-  float* head[6] = {};  // box P3,P4,P5 ; cls P3,P4,P5 (fp32)
-  size_t head_cap[6] = {};
-  unsigned long long* clsmax[3] = {};  // per anchor (argmax << 32 | max-logit bits): detect()'s class branch output
-  size_t clsmax_cap[3] = {};
-  int32_t* lvl = nullptr;  // lazy box branch: [N][A] per-level lists of passing anchors, then [N][3] counts
-  size_t lvl_cap = 0;
+  DevBuf<float> head[6];  // box P3,P4,P5 ; cls P3,P4,P5 (fp32)
+  DevBuf<unsigned long long> clsmax[3];  // per anchor (argmax << 32 | max-logit bits): detect()'s class branch output
+  DevBuf<int32_t> lvl;  // lazy box branch: [N][A] per-level lists of passing anchors, then [N][3] counts
   // deep lazy box branch: flat pixel lists [N*A] (anchors) + [9*N*A] (their neighbourhoods) + 6 counters, and the
   // share of anchors that passed in the last finished call (pinned host copy, written by the GPU, read without a
   // sync: it only steers lazy vs dense evaluation of the branch's 3x3 layers -- both give the same bytes)
-  int32_t* flat = nullptr;
-  size_t flat_cap = 0;
+  DevBuf<int32_t> flat;
+  // pinned host memory and the event stay raw: made on first use in eioku_yolo_detect, released in eioku_yolo_destroy
   int32_t* pass_host = nullptr;  // [4]: cnt1[3], N*A of that call
   hipEvent_t pass_event = nullptr;  // recorded behind the copy into pass_host; the word is read only once it has fired
   bool pass_pending = false;
   long long pass_seen[2] = {0, 0};  // last completed {passed, total}: what the decision uses until newer history lands
   int deep_idx[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};  // op indices of cv2.l.0 / cv2.l.1
-  Cand* cands = nullptr;  // dense [N][A] followed by keys [N][A]
-  size_t cands_cap = 0;
-  int32_t* counts = nullptr;  // [N] cand counts + [N] det counts
-  size_t counts_cap = 0;
-  Det* dets = nullptr;
-  size_t dets_cap = 0;
+  DevBuf<Cand> cands;  // dense [N][A] followed by 64-bit keys [N][A]
+  DevBuf<int32_t> counts;  // [N] cand counts + [N] det counts
+  DevBuf<Det> dets;
   // letterbox tables
-  void* lb_tables = nullptr;
-  size_t lb_cap = 0;
+  DevBuf<char> lb_tables;
   unsigned long long lb_key = 0;   // FNV-1a of the bilinear tables currently resident in lb_tables
   void* lb_key_ptr = nullptr;
   __half* lb_out = nullptr;  // == bufs[in_buf].ptr
@@ -95,14 +85,12 @@ struct eioku_yolo {
 namespace {
 
 int add_buf(eioku_yolo* y, int level, int ch) {
-  y->bufs.push_back(Buf{level, ch});
+  y->bufs.push_back(Buf{level, ch, {}});
   return (int)y->bufs.size() - 1;
 }
 
 int add_conv_w(eioku_yolo* y, const std::string& name, int cout, int cin, int k, int s) {
-  y->names.push_back(name);
-  y->shapes.push_back({cout, cin, k, s});
-  return (int)y->names.size() - 1;
+  return y->convs.add({name, cout, cin, k, s});
 }
 
 void add_conv(eioku_yolo* y, const std::string& name, int cin, int cout, int k, int s, int in_buf, int in_off,
@@ -209,8 +197,6 @@ void build_graph(eioku_yolo* y) {
     add_conv(y, "model.22.cv3." + i + ".1.conv", cc, cc, 3, 1, k1, 0, k2, 0);
     add_conv(y, "model.22.cv3." + i + ".2", cc, y->nc, 1, 1, k2, 0, -1, 0, -1, 0, kActNone, 3 + l);
   }
-  y->weights.resize(y->names.size());
-  y->set.assign(y->names.size(), false);
   // box branch per level: cv2.l.0 -> cv2.l.1 -> cv2.l.2 (f32_out = l); remember the two 3x3 ops
   for (size_t i = 0; i < y->ops.size(); ++i) {
     const Op& o2 = y->ops[i];
@@ -240,7 +226,7 @@ void build_graph(eioku_yolo* y) {
     }
     if (readers != 1 || consumer < (int)i) continue;
     Op& c = y->ops[consumer];
-    if (c.kind == kConv && y->shapes[c.conv][2] == 1 && c.in_off == 0 && c.in_ch >= up.in_ch && up.in_ch % 32 == 0) {
+    if (c.kind == kConv && y->convs.layers[c.conv].k == 1 && c.in_off == 0 && c.in_ch >= up.in_ch && up.in_ch % 32 == 0) {
       up.up_consumer = consumer;
       c.up_from = (int)i;
     }
@@ -256,10 +242,10 @@ void build_graph(eioku_yolo* y) {
     int writers = 0;
     for (const Op& o : y->ops) writers += (o.f32_out < 0 && o.out_buf == op.out_buf);
     op.sole_consumer = readers == 1 && writers == 1 && nx.in_buf == op.out_buf && nx.res_buf != op.out_buf &&
-                       y->bufs[op.out_buf].ch == y->shapes[op.conv][0];
+                       y->bufs[op.out_buf].ch == y->convs.layers[op.conv].cout;
     // weaker than sole_consumer: the buffer may be reused (C2f's tmp is shared by its bottlenecks) as long as every
     // read of it is the op right after the write it consumes
-    bool priv = nx.in_buf == op.out_buf && nx.in_off == op.out_off && y->bufs[op.out_buf].ch == y->shapes[op.conv][0];
+    bool priv = nx.in_buf == op.out_buf && nx.in_off == op.out_off && y->bufs[op.out_buf].ch == y->convs.layers[op.conv].cout;
     for (size_t j = 0; j < y->ops.size() && priv; ++j) {
       const Op& o = y->ops[j];
       if (o.res_buf == op.out_buf) priv = false;
@@ -277,20 +263,6 @@ int level_dim(int x, int level) {
   return x;
 }
 
-template <typename T>
-int ensure(T** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return EIOKU_OK;
-  if (*p) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-  }
-  EIOKU_HIP_CHECK(hipMalloc((void**)p, bytes));
-  *cap = bytes;
-  return EIOKU_OK;
-}
-
 int prepare(eioku_yolo* y, int n, int h, int w) {
   EIOKU_REQUIRE(h % 32 == 0 && w % 32 == 0, "network input %dx%d must be a multiple of 32", h, w);
   // the conv kernels address activations with 32-bit element offsets and decode tile / pixel indices below 2^24
@@ -301,30 +273,20 @@ int prepare(eioku_yolo* y, int n, int h, int w) {
                   "batch of %d frames at %dx%d: an activation tensor of %lld x %d channels exceeds one launch's 32-bit "
                   "offsets -- split the batch", n, h, w, px, b.ch);
   }
-  for (auto& b : y->bufs) {
-    const size_t bytes = (size_t)n * level_dim(h, b.level) * level_dim(w, b.level) * b.ch * sizeof(__half);
-    int rc = ensure(&b.ptr, &b.cap, bytes);
-    if (rc) return rc;
-  }
-  int A = 0;
+  for (auto& b : y->bufs) EIOKU_TRY(grow_synced(b.ptr, (size_t)n * level_dim(h, b.level) * level_dim(w, b.level) * b.ch));
+  size_t A = 0;
   for (int l = 0; l < 3; ++l) {
     const size_t px = (size_t)n * level_dim(h, 3 + l) * level_dim(w, 3 + l);
-    A += level_dim(h, 3 + l) * level_dim(w, 3 + l);
-    int rc = ensure(&y->head[l], &y->head_cap[l], px * 4 * kRegMax * sizeof(float));
-    if (rc) return rc;
-    rc = ensure(&y->head[3 + l], &y->head_cap[3 + l], px * y->nc * sizeof(float));
-    if (rc) return rc;
-    rc = ensure(&y->clsmax[l], &y->clsmax_cap[l], px * sizeof(unsigned long long));
-    if (rc) return rc;
+    A += px;
+    EIOKU_TRY(grow_synced(y->head[l], px * 4 * kRegMax));
+    EIOKU_TRY(grow_synced(y->head[3 + l], px * y->nc));
+    EIOKU_TRY(grow_synced(y->clsmax[l], px));
   }
-  int rc = ensure(&y->cands, &y->cands_cap, (size_t)n * A * (sizeof(Cand) + sizeof(unsigned long long)));
-  if (rc) return rc;
-  rc = ensure(&y->counts, &y->counts_cap, (size_t)n * 2 * sizeof(int32_t));
-  if (rc) return rc;
-  rc = ensure(&y->lvl, &y->lvl_cap, ((size_t)n * A + (size_t)n * 3) * sizeof(int32_t));
-  if (rc) return rc;
-  rc = ensure(&y->flat, &y->flat_cap, ((size_t)10 * n * A + 16) * sizeof(int32_t));
-  if (rc) return rc;
+  // A = anchors of the whole batch; one Cand is as large as four keys
+  EIOKU_TRY(grow_synced(y->cands, A + (A + 3) / 4));
+  EIOKU_TRY(grow_synced(y->counts, (size_t)n * 2));
+  EIOKU_TRY(grow_synced(y->lvl, A + (size_t)n * 3));
+  EIOKU_TRY(grow_synced(y->flat, 10 * A + 16));
   y->cur_n = n;
   y->cur_h = h;
   y->cur_w = w;
@@ -351,7 +313,7 @@ __global__ void k_pass_record(const int32_t* counts, int n, int total, int32_t* 
 
 int record_pass_rate(eioku_yolo* y, int n, int A, hipStream_t stream) {
   int32_t* dev = y->flat + (size_t)10 * n * A + 8;
-  hipLaunchKernelGGL(k_pass_record, dim3(1), dim3(256), 0, stream, y->counts, n, n * A, dev);
+  hipLaunchKernelGGL(k_pass_record, dim3(1), dim3(256), 0, stream, y->counts.p, n, n * A, dev);
   EIOKU_HIP_CHECK(hipMemcpyAsync(y->pass_host, dev, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
   EIOKU_HIP_CHECK(hipEventRecord(y->pass_event, stream));
   y->pass_pending = true;
@@ -379,7 +341,7 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
     Slice in{ib.ptr, ib.ch, op.in_off};
     int rc = EIOKU_OK;
     if (op.kind == kConv) {
-      const ConvWeights& cw = y->weights[op.conv];
+      const ConvWeights& cw = y->convs.w[op.conv];
       Slice out{}, res{};
       float* f32 = nullptr;
       if (op.f32_out >= 0) {
@@ -394,7 +356,7 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
       const Op* nx = (&op + 1 <= &y->ops.back()) ? &op + 1 : nullptr;
       const bool pair = !first && nx && nx->kind == kConv && op.f32_out < 0 && op.res_buf < 0 && nx->res_buf < 0 &&
                         nx->f32_out < 0 && nx->in_buf == op.out_buf && nx->in_off == op.out_off && op.sole_consumer &&
-                        conv_post_ok(cw, y->weights[nx->conv]);
+                        conv_post_ok(cw, y->convs.w[nx->conv]);
       // fused-letterbox stem -> model.1 -> model.2.cv1 (YOLOv8n, copy-mode frames): one launch
       if (first && fused && y->ops.size() > 2) {
         const Op& o1 = y->ops[1];
@@ -403,10 +365,10 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
                            o1.res_buf < 0 && o2.f32_out < 0 && o2.res_buf < 0 && o1.in_buf == op.out_buf &&
                            o1.in_off == op.out_off && op.sole_consumer && o2.in_buf == o1.out_buf && o2.in_off == o1.out_off &&
                            o1.sole_consumer &&
-                           conv_stem_chain_ok(cw, y->weights[o1.conv], y->weights[o2.conv], *fused, W);
+                           conv_stem_chain_ok(cw, y->convs.w[o1.conv], y->convs.w[o2.conv], *fused, W);
         if (front) {
-          const ConvWeights& w1 = y->weights[o1.conv];
-          const ConvWeights& w2 = y->weights[o2.conv];
+          const ConvWeights& w1 = y->convs.w[o1.conv];
+          const ConvWeights& w2 = y->convs.w[o2.conv];
           const Buf& ob2 = y->bufs[o2.out_buf];
           rc = conv_stem_chain_forward(cw, w1, w2, *fused, n, H, W, Slice{ob2.ptr, ob2.ch, o2.out_off}, op.act, o1.act, o2.act,
                                        stream);
@@ -420,17 +382,17 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
       }
       // C2f Bottleneck (3x3 -> 3x3 [+ x]) on the shallow levels: one launch, the intermediate stays in LDS
       const bool chain = !first && nx && nx->kind == kConv && op.f32_out < 0 && op.res_buf < 0 && nx->f32_out < 0 &&
-                         op.chain_next && conv_chain_ok(cw, y->weights[nx->conv]) &&
+                         op.chain_next && conv_chain_ok(cw, y->convs.w[nx->conv]) &&
                          (nx->res_buf < 0 || (nx->res_buf == op.in_buf && nx->res_off == op.in_off));
       if (chain) {
-        const ConvWeights& bw = y->weights[nx->conv];
+        const ConvWeights& bw = y->convs.w[nx->conv];
         const Buf& ob2 = y->bufs[nx->out_buf];
         // ... and the C2f's closing 1x1 when this is its LAST Bottleneck: concat = [y0 | y1 | .. | y_out], y_out = this
         // pair's output (the concat's last slice, read by that 1x1 alone), the pair's input = the slice before it
         const Op* n2 = (&op + 2 <= &y->ops.back()) ? &op + 2 : nullptr;
         bool cat = n2 && n2->kind == kConv && n2->f32_out < 0 && n2->res_buf < 0 && n2->in_buf == nx->out_buf &&
                    n2->in_off == 0 && op.in_buf == nx->out_buf && nx->out_off == op.in_off + cw.cin &&
-                   n2->in_ch == nx->out_off + cw.cin && ob2.ch == n2->in_ch && conv_chain_cat_ok(cw, bw, y->weights[n2->conv]);
+                   n2->in_ch == nx->out_off + cw.cin && ob2.ch == n2->in_ch && conv_chain_cat_ok(cw, bw, y->convs.w[n2->conv]);
         for (size_t j = 0; j < y->ops.size() && cat; ++j) {  // nobody else reads y2
           const Op& o = y->ops[j];
           if (&o == n2) continue;
@@ -438,7 +400,7 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
           if (o.res_buf == nx->out_buf && o.res_off >= nx->out_off) cat = false;
         }
         if (cat) {
-          const ConvWeights& w2 = y->weights[n2->conv];
+          const ConvWeights& w2 = y->convs.w[n2->conv];
           const Buf& ob3 = y->bufs[n2->out_buf];
           rc = conv_chain_forward(cw, bw, in, n, H, W, Slice{}, nx->res_buf >= 0, op.act, nx->act, stream, &w2,
                                   Slice{ob2.ptr, ob2.ch, 0}, Slice{ob3.ptr, ob3.ch, n2->out_off}, n2->act);
@@ -455,7 +417,7 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
         continue;
       }
       if (pair) {
-        const ConvWeights& pw = y->weights[nx->conv];
+        const ConvWeights& pw = y->convs.w[nx->conv];
         const Buf& ob2 = y->bufs[nx->out_buf];
         rc = conv_forward(cw, in, n, H, W, Slice{ob2.ptr, ob2.ch, nx->out_off}, nullptr, Slice{}, op.act, stream, nullptr,
                           &pw, nx->act);
@@ -521,8 +483,8 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
 
 int run_network(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedInput* fused = nullptr,
                 bool clsmax = false, bool lazybox = false, bool lazydeep = false) {
-  for (size_t i = 0; i < y->set.size(); ++i)
-    EIOKU_REQUIRE(y->set[i], "conv %zu (%s) has no weights", i, y->names[i].c_str());
+  for (size_t i = 0; i < y->convs.set.size(); ++i)
+    EIOKU_REQUIRE(y->convs.set[i], "conv %zu (%s) has no weights", i, y->convs.layers[i].name.c_str());
   // (replaying the forward as a hipGraph was built and measured on ROCm 7.2 / MI355X: 3.07 ms per bench step against
   // 3.03 ms for plain launches -- the gaps between dependent kernels are the GPU's, not the host's -- and removed)
   return run_ops(y, n, h, w, stream, fused, &y->conv_flops_last, clsmax, lazybox, lazydeep);
@@ -550,46 +512,25 @@ int eioku_yolo_create(const int* ch5, const int* depth4, int nc, eioku_yolo** ou
 void eioku_yolo_destroy(eioku_yolo* y) {
   if (!y) return;
   (void)hipDeviceSynchronize();
-  for (auto& w : y->weights) conv_weights_destroy(&w);
-  for (auto& b : y->bufs)
-    if (b.ptr) (void)hipFree(b.ptr);
-  for (int i = 0; i < 6; ++i)
-    if (y->head[i]) (void)hipFree(y->head[i]);
-  for (int i = 0; i < 3; ++i)
-    if (y->clsmax[i]) (void)hipFree(y->clsmax[i]);
-  if (y->lvl) (void)hipFree(y->lvl);
-  if (y->flat) (void)hipFree(y->flat);
   if (y->pass_host) (void)hipHostFree(y->pass_host);
   if (y->pass_event) (void)hipEventDestroy(y->pass_event);
-  if (y->cands) (void)hipFree(y->cands);
-  if (y->counts) (void)hipFree(y->counts);
-  if (y->dets) (void)hipFree(y->dets);
-  if (y->lb_tables) (void)hipFree(y->lb_tables);
   delete y;
 }
 
-int eioku_yolo_num_convs(const eioku_yolo* y) { return y ? (int)y->names.size() : 0; }
+int eioku_yolo_num_convs(const eioku_yolo* y) { return y ? y->convs.size() : 0; }
 
 int eioku_yolo_conv_info(const eioku_yolo* y, int idx, char* name, size_t cap, int* cout, int* cin, int* k,
                          int* stride) {
-  EIOKU_REQUIRE(y && idx >= 0 && idx < (int)y->names.size(), "bad conv index %d", idx);
-  if (name && cap) snprintf(name, cap, "%s", y->names[idx].c_str());
-  if (cout) *cout = y->shapes[idx][0];
-  if (cin) *cin = y->shapes[idx][1];
-  if (k) *k = y->shapes[idx][2];
-  if (stride) *stride = y->shapes[idx][3];
-  return EIOKU_OK;
+  EIOKU_REQUIRE(y && idx >= 0 && idx < y->convs.size(), "bad conv index %d", idx);
+  return y->convs.info(idx, name, cap, cout, cin, k, stride);
 }
 
 int eioku_yolo_set_conv(eioku_yolo* y, int idx, const float* w_oihw, const float* bias) {
   EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(y && idx >= 0 && idx < (int)y->names.size(), "bad conv index %d", idx);
+  EIOKU_REQUIRE(y && idx >= 0 && idx < y->convs.size(), "bad conv index %d", idx);
   EIOKU_REQUIRE(w_oihw, "NULL weights");
-  const auto& s = y->shapes[idx];
-  if (y->set[idx]) conv_weights_destroy(&y->weights[idx]);
-  int rc = conv_weights_create(&y->weights[idx], s[0], s[1], s[2], s[3], w_oihw, bias);
-  y->set[idx] = rc == EIOKU_OK;
-  return rc;
+  const ConvLayer& l = y->convs.layers[idx];
+  return y->convs.mark(idx, conv_weights_create(&y->convs.w[idx], l.cout, l.cin, l.k, l.stride, w_oihw, bias));
 }
 
 int eioku_yolo_forward(eioku_yolo* y, const void* in_nhwc8, int n, int h, int w, float* const* box_out,
@@ -654,9 +595,8 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   if (rc) return rc;
   // tables -> device
   const size_t tb = (size_t)p.new_w * 4 + (size_t)p.new_h * 4 + (size_t)p.new_w * 4 + (size_t)p.new_h * 4;
-  rc = ensure(&y->lb_tables, &y->lb_cap, tb + 64);
-  if (rc) return rc;
-  char* t = (char*)y->lb_tables;
+  EIOKU_TRY(grow_synced(y->lb_tables, tb + 64));
+  char* t = y->lb_tables;
   p.xofs = (const int32_t*)t;
   p.yofs = (const int32_t*)(t + (size_t)p.new_w * 4);
   p.xalpha = (const int16_t*)(t + (size_t)p.new_w * 4 + (size_t)p.new_h * 4);
@@ -715,7 +655,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   const Op& op0 = y->ops.front();
   static const bool no_fuse = env_off("EIOKU_STEM_FUSE");
   const bool fuse = !no_fuse && op0.kind == kConv && op0.in_buf == y->in_buf && op0.res_buf < 0 && op0.f32_out < 0 &&
-                    fused_input_ok(y->weights[op0.conv], fi, Slice{}, nullptr);
+                    fused_input_ok(y->convs.w[op0.conv], fi, Slice{}, nullptr);
   if (!fuse) {
     rc = letterbox_forward(d_bgr, n, p, y->bufs[y->in_buf].ptr, stream);
     if (rc) return rc;
@@ -724,7 +664,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   // last conv can (one cout tile: nc <= 128)
   bool cm = true;
   for (const Op& op : y->ops)
-    if (op.kind == kConv && op.f32_out >= 3) cm = cm && conv_clsmax_ok(y->weights[op.conv], op.act);
+    if (op.kind == kConv && op.f32_out >= 3) cm = cm && conv_clsmax_ok(y->convs.w[op.conv], op.act);
   // ... and then only the anchors that pass the threshold need their 64 DFL logits: the box branch's last 1x1 conv
   // is evaluated by decode for those (one 64-row weight tile, whole 32-channel chunks)
   static const bool lazy_off = env_off("EIOKU_LAZY_BOX");
@@ -732,11 +672,11 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   LazyBox lbx{};
   for (const Op& op : y->ops)
     if (op.kind == kConv && op.f32_out >= 0 && op.f32_out < 3) {
-      const ConvWeights& cw = y->weights[op.conv];
+      const ConvWeights& cw = y->convs.w[op.conv];
       lazy = lazy && cw.ks == 1 && cw.ntiles == 1 && cw.nf == 4 && cw.cout == 64 && cw.cin % 32 == 0 && op.act == kActNone &&
              op.res_buf < 0 && (lbx.in_cs == 0 || (lbx.in_cs == y->bufs[op.in_buf].ch && lbx.nchunks == cw.nchunks));
       lbx.in[op.f32_out] = y->bufs[op.in_buf].ptr + op.in_off;
-      lbx.wgt[op.f32_out] = reinterpret_cast<const uint4*>(cw.d_w);
+      lbx.wgt[op.f32_out] = reinterpret_cast<const uint4*>(cw.d_w.p);
       lbx.bias[op.f32_out] = cw.d_b;
       lbx.in_cs = y->bufs[op.in_buf].ch;
       lbx.nchunks = cw.nchunks;
@@ -779,8 +719,8 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
       }
       const Op& o0 = y->ops[i0];
       const Op& o1 = y->ops[i1];
-      const ConvWeights& w0 = y->weights[o0.conv];
-      const ConvWeights& w1 = y->weights[o1.conv];
+      const ConvWeights& w0 = y->convs.w[o0.conv];
+      const ConvWeights& w1 = y->convs.w[o1.conv];
       auto ok3 = [](const ConvWeights& w, const Op& o) {
         return w.ks == 3 && w.stride == 1 && w.cout == 64 && w.cin % 32 == 0 && o.act == kActSiLU && o.res_buf < 0 && o.f32_out < 0;
       };
@@ -789,10 +729,10 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
         break;
       }
       lbx.c0[l] = LazyConv3{y->bufs[o0.in_buf].ptr + o0.in_off, y->bufs[o0.in_buf].ch, w0.nchunks,
-                            reinterpret_cast<const uint4*>(w0.d_w), 16 * w0.nf, w0.d_b,
+                            reinterpret_cast<const uint4*>(w0.d_w.p), 16 * w0.nf, w0.d_b,
                             y->bufs[o0.out_buf].ptr + o0.out_off, y->bufs[o0.out_buf].ch};
       lbx.c1[l] = LazyConv3{y->bufs[o1.in_buf].ptr + o1.in_off, y->bufs[o1.in_buf].ch, w1.nchunks,
-                            reinterpret_cast<const uint4*>(w1.d_w), 16 * w1.nf, w1.d_b,
+                            reinterpret_cast<const uint4*>(w1.d_w.p), 16 * w1.nf, w1.d_b,
                             y->bufs[o1.out_buf].ptr + o1.out_off, y->bufs[o1.out_buf].ch};
       lbx.flat1[l] = f + off1;
       lbx.flat0[l] = f + off0;
@@ -812,7 +752,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
     Wl[l] = level_dim(p.out_w, 3 + l);
     A += Hl[l] * Wl[l];
   }
-  rc = ensure(&y->dets, &y->dets_cap, (size_t)n * max_det * sizeof(Det));
+  rc = grow_synced(y->dets, (size_t)n * max_det);
   if (rc) return rc;
   EIOKU_HIP_CHECK(hipMemsetAsync(y->counts, 0, (size_t)n * 2 * sizeof(int32_t), stream));
   const float* box[3] = {y->head[0], y->head[1], y->head[2]};
