@@ -18,6 +18,8 @@ from pathlib import Path
 
 import numpy as np
 
+from ._handle import Handle
+
 SAMPLE_RATE = 16000
 MAX_TAPS = 14336             # 56 KiB of fp32: bank and a tile's input share 64 KiB of LDS
 MAX_CHANNELS = 8
@@ -192,26 +194,19 @@ class AudioFrontEnd:
         self.slab_out = int(slab_out)
         if not 1 <= self.slab_out <= 1 << 26:
             raise ValueError(f"slab_out must be in 1..2^26, got {slab_out!r}")
-        self._handles: dict[tuple[int, int], C.c_void_p] = {}
+        self._handles: dict[tuple[int, int], Handle] = {}
         self._last = None
-        self._lib_mod = self.lib = None
+        self.lib = None  # the library is loaded with the first handle, not before
 
-    def _handle(self, rate, up: int, down: int):
-        if self.lib is None:
-            from . import _lib
-
-            self._lib_mod, self.lib = _lib, _lib.load()
-            _lib.init()
+    def _handle(self, rate, up: int, down: int) -> Handle:
         h = self._handles.get((up, down))
         if h is None:
-            h = C.c_void_p()
             if up == down:
-                rc = self.lib.eioku_audio_create(1, 1, 0, None, self.slab_out, C.byref(h))
+                h = Handle("audio", 1, 1, 0, None, self.slab_out)
             else:
                 bank = filter_bank(rate)
-                rc = self.lib.eioku_audio_create(up, down, bank.shape[1], bank.ctypes.data, self.slab_out, C.byref(h))
-            self._lib_mod.check(rc, "eioku_audio_create")
-            self._handles[(up, down)] = h
+                h = Handle("audio", up, down, bank.shape[1], bank.ctypes.data, self.slab_out)
+            self._handles[(up, down)], self.lib = h, h.lib
         return h
 
     def resample(self, raw, fmt: str, channels: int, rate: int) -> np.ndarray:
@@ -224,8 +219,8 @@ class AudioFrontEnd:
             return out
         h = self._handle(rate, up, down)
         n = C.c_longlong(0)
-        self._lib_mod.check(self.lib.eioku_audio_resample(h, raw.ctypes.data, code, int(channels), frames, out.ctypes.data, out.size,
-                                                          C.byref(n)), "eioku_audio_resample")
+        h.check(h.eioku_audio_resample(raw.ctypes.data, code, int(channels), frames, out.ctypes.data, out.size, C.byref(n)),
+                "eioku_audio_resample")
         assert n.value == out.size
         self._last = h
         return out
@@ -255,25 +250,15 @@ class AudioFrontEnd:
         up, down = resample_ratio(rate)
         t = C.c_int(0)
         h = self._handle(rate, up, down)
-        self._lib_mod.check(self.lib.eioku_audio_tile(h, C.byref(t)), "eioku_audio_tile")
+        h.check(h.eioku_audio_tile(C.byref(t)), "eioku_audio_tile")
         return t.value
 
     def last_ms(self) -> float:
         """Kernel milliseconds of the last :meth:`resample`, summed over its slabs."""
-        if self._last is None:
-            return 0.0
-        ms = C.c_double(0)
-        self._lib_mod.check(self.lib.eioku_audio_last_ms(self._last, C.byref(ms)), "eioku_audio_last_ms")
-        return ms.value
+        return 0.0 if self._last is None else self._last.doubles("last_ms")[0]
 
     def close(self) -> None:
-        for h in getattr(self, "_handles", {}).values():
-            self.lib.eioku_audio_destroy(h)
+        for h in self._handles.values():
+            h.close()
         self._handles = {}
         self._last = None
-
-    def __del__(self):  # noqa: D105
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _lib, weights as W
 from ._buffers import current_stream, on_device, ptr
+from ._handle import Handle
 
 DET_DTYPE = np.dtype([("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4"), ("conf", "<f4"),
                       ("cls", "<i4"), ("anchor", "<i4"), ("pad", "<i4")])
@@ -114,20 +115,16 @@ class Yolov8Detector:
     """A YOLOv8 network resident on one GPU (``eioku_yolo_t``)."""
 
     def __init__(self, variant: str = "n", nc: int = 80, state: dict | None = None, names: dict | None = None):
-        lib = _lib.load()
-        _lib.init()
-        self._lib = lib
         self.variant, self.nc = variant, nc
         self.names = names if names is not None else (dict(enumerate(W.COCO_NAMES)) if nc == 80 else
                                                       {i: str(i) for i in range(nc)})
         ch, depth = W.YOLO_VARIANTS[variant]
-        h = C.c_void_p()
-        _lib.check(lib.eioku_yolo_create((C.c_int * 5)(*ch), (C.c_int * 4)(*depth), nc, C.byref(h)),
-                   "eioku_yolo_create")
-        self._h = h
-        self._table = self._conv_table()
-        expect = [(n, co, (8 if n == "model.0.conv" else ci), k, s) for n, co, ci, k, s in W.conv_table(variant, nc)]
-        if self._table != expect:
+        self._h = Handle("yolo", (C.c_int * 5)(*ch), (C.c_int * 4)(*depth), nc)
+        self._h.or_close(self._load, state)
+
+    def _load(self, state):
+        expect = [(n, co, (8 if n == "model.0.conv" else ci), k, s) for n, co, ci, k, s in W.conv_table(self.variant, self.nc)]
+        if self._h.convs() != expect:
             raise RuntimeError("library graph and weights.conv_table disagree")
         if state is not None:
             self.load_state(state)
@@ -144,41 +141,17 @@ class Yolov8Detector:
                 names = own  # result.names of THIS checkpoint (a custom-trained model), not the COCO table
         return cls(variant, nc, state, names)
 
-    def _conv_table(self):
-        lib, out = self._lib, []
-        for i in range(lib.eioku_yolo_num_convs(self._h)):
-            name = C.create_string_buffer(128)
-            co, ci, k, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-            _lib.check(lib.eioku_yolo_conv_info(self._h, i, name, 128, C.byref(co), C.byref(ci), C.byref(k),
-                                                C.byref(s)), "eioku_yolo_conv_info")
-            out.append((name.value.decode(), co.value, ci.value, k.value, s.value))
-        return out
-
     def load_state(self, state: dict) -> None:
-        self._state = dict(state)
-        for i, (name, cout, cin, k, _) in enumerate(self._table):
-            w, b = state[name]
-            w = np.asarray(w, dtype=np.float32)
-            if name == "model.0.conv":  # RGB -> 8-channel pixels, zero weights on the padding channels
-                w8 = np.zeros((cout, 8, k, k), dtype=np.float32)
-                w8[:, :3] = w
-                w = w8
-            if w.shape != (cout, cin, k, k):
-                raise ValueError(f"{name}: weight shape {w.shape} != {(cout, cin, k, k)}")
-            w = np.ascontiguousarray(w)
-            b = np.ascontiguousarray(b, dtype=np.float32)
-            _lib.check(self._lib.eioku_yolo_set_conv(self._h, i, ptr(w), ptr(b)), f"eioku_yolo_set_conv({name})")
+        self._state, padded = dict(state), dict(state)
+        if "model.0.conv" in state:  # RGB -> 8-channel pixels, zero weights on the padding channels
+            w, b = np.asarray(state["model.0.conv"][0], dtype=np.float32), state["model.0.conv"][1]
+            w8 = np.zeros((w.shape[0], 8, *w.shape[2:]), dtype=np.float32)
+            w8[:, :3] = w
+            padded["model.0.conv"] = (w8, b)
+        self._h.set_convs(padded)
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_yolo_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h.close()
 
     # ---- raw network (parity tests, bench) ------------------------------------------------------
     def forward_raw(self, x_nhwc8):
@@ -191,14 +164,12 @@ class Yolov8Detector:
         cls = [torch.empty((n, h // s, w // s, self.nc), dtype=torch.float32, device=x_nhwc8.device) for s in (8, 16, 32)]
         bp = (C.c_void_p * 3)(*[t.data_ptr() for t in box])
         cp = (C.c_void_p * 3)(*[t.data_ptr() for t in cls])
-        _lib.check(self._lib.eioku_yolo_forward(self._h, ptr(x_nhwc8), n, h, w, bp, cp, current_stream(x_nhwc8)),
+        _lib.check(self._h.eioku_yolo_forward(ptr(x_nhwc8), n, h, w, bp, cp, current_stream(x_nhwc8)),
                    "eioku_yolo_forward")
         return box, cls
 
     def last_conv_flops(self) -> float:
-        f = C.c_double(0)
-        _lib.check(self._lib.eioku_yolo_last_conv_flops(self._h, C.byref(f)), "eioku_yolo_last_conv_flops")
-        return f.value
+        return self._h.doubles("last_conv_flops")[0]
 
     def calibrate_random_head(self, frames_bgr, frac: float = 0.01, conf: float = 0.25):
         """Random-init models only (bench): rescale the six Detect output convs so that, on these
@@ -242,10 +213,10 @@ class Yolov8Detector:
             dets = np.zeros((n, max_det), dtype=DET_DTYPE)
             counts = np.zeros((n,), dtype=np.int32)
         geom = plan.geom()
-        _lib.check(self._lib.eioku_yolo_detect(
-            self._h, ptr(frames_bgr), n, h, w, ptr(geom), ptr(plan.xofs), ptr(plan.yofs), ptr(plan.xalpha),
-            ptr(plan.ybeta), float(np.float32(plan.gain)), float(conf), float(iou), int(max_det), ptr(dets),
-            ptr(counts), _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(frames_bgr)), "eioku_yolo_detect")
+        _lib.check(self._h.eioku_yolo_detect(
+            ptr(frames_bgr), n, h, w, ptr(geom), ptr(plan.xofs), ptr(plan.yofs), ptr(plan.xalpha), ptr(plan.ybeta),
+            float(np.float32(plan.gain)), float(conf), float(iou), int(max_det), ptr(dets), ptr(counts),
+            _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(frames_bgr)), "eioku_yolo_detect")
         if dev and not keep_on_device:
             dets = dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det)
             counts = counts.cpu().numpy()

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, on_device, ptr
+from ._handle import Handle
 
 MINILM_L6_V2 = dict(vocab=30522, hidden=384, layers=6, heads=12, ffn=1536, max_pos=512, type_vocab=2, ln_eps=1e-12)
 
@@ -103,27 +104,14 @@ class MiniLMEncoder:
     """BERT sentence encoder resident on one GPU."""
 
     def __init__(self, state: dict[str, np.ndarray] | None = None, cfg: dict = MINILM_L6_V2, tokenizer=None):
-        lib = _lib.load()
-        _lib.init()
-        self._lib, self.cfg, self.tokenizer = lib, dict(cfg), tokenizer
-        h = C.c_void_p()
-        _lib.check(lib.eioku_bert_create(cfg["vocab"], cfg["hidden"], cfg["layers"], cfg["heads"], cfg["ffn"],
-                                         cfg["max_pos"], cfg["type_vocab"], float(cfg["ln_eps"]), C.byref(h)),
-                   "eioku_bert_create")
-        self._h = h
+        self.cfg, self.tokenizer = dict(cfg), tokenizer
+        self._h = Handle("bert", cfg["vocab"], cfg["hidden"], cfg["layers"], cfg["heads"], cfg["ffn"], cfg["max_pos"],
+                         cfg["type_vocab"], float(cfg["ln_eps"]))
         if state is not None:
-            self.load_state(state)
+            self._h.or_close(self.load_state, state)
 
     def load_state(self, state: dict[str, np.ndarray]) -> None:
-        lib = self._lib
-        for i in range(lib.eioku_bert_num_tensors(self._h)):
-            name = C.create_string_buffer(160)
-            r, c = C.c_int(), C.c_int()
-            _lib.check(lib.eioku_bert_tensor_info(self._h, i, name, 160, C.byref(r), C.byref(c)), "eioku_bert_tensor_info")
-            a = np.ascontiguousarray(state[name.value.decode()], dtype=np.float32)
-            if a.size != r.value * c.value:
-                raise ValueError(f"{name.value.decode()}: {a.shape} does not have {r.value}x{c.value} elements")
-            _lib.check(lib.eioku_bert_set_tensor(self._h, i, ptr(a), a.size), f"eioku_bert_set_tensor({name.value.decode()})")
+        self._h.set_tensors(state)
 
     def encode_ids(self, ids, mask):
         """int32 ids / uint8 mask ``(B,S)`` -> float32 ``(B,hidden)`` unit vectors (numpy in -> numpy out)."""
@@ -140,8 +128,8 @@ class MiniLMEncoder:
             ids = np.ascontiguousarray(ids, dtype=np.int32)
             mask = np.ascontiguousarray(mask, dtype=np.uint8)
             out = np.empty((B, H), dtype=np.float32)
-        _lib.check(self._lib.eioku_bert_embed(self._h, ptr(ids), ptr(mask), B, S, ptr(out),
-                                              _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(ids)),
+        _lib.check(self._h.eioku_bert_embed(ptr(ids), ptr(mask), B, S, ptr(out),
+                                            _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(ids)),
                    "eioku_bert_embed")
         return out
 
@@ -157,20 +145,11 @@ class MiniLMEncoder:
         return self.encode_ids(enc["input_ids"].astype(np.int32), enc["attention_mask"].astype(np.uint8))
 
     def last_flops(self) -> float:
-        f = C.c_double(0)
-        _lib.check(self._lib.eioku_bert_last_flops(self._h, C.byref(f)), "eioku_bert_last_flops")
-        return f.value
+        return self._h.doubles("last_flops")[0]
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_bert_destroy(self._h)
-            self._h = None
+        self._h.close()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 class SegmentBatcher:
     """Collects tokenised transcript segments on the device and encodes them ``batch_segments`` at a time.

@@ -10,18 +10,20 @@ There is no landmark alignment: the face detector exposes no keypoints.  No CPU 
 from __future__ import annotations
 
 import ctypes as C
+from functools import partial
 from pathlib import Path
 
 import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, on_device, ptr
+from ._handle import Handle
+from ._state import bn_scale_shift, fold_conv_bn, np_state, rand_bn, rand_conv, resnet_depths, tensor
 
 CROP = 112
 FEAT = 512
 TAP_BITS = 11
 WIDTHS = (64, 128, 256, 512)
-_BN_EPS = 1e-5
 DEPTHS = {"r18": (2, 2, 2, 2), "r34": (3, 4, 6, 3), "r50": (3, 4, 14, 3), "r100": (3, 13, 30, 3)}
 
 
@@ -52,44 +54,7 @@ def crop_taps(box, h: int, w: int):
 # ---- arcface_torch state dict -> folded parameters -------------------------------------------------------------------
 def depths_from_state(sd: dict) -> tuple:
     """Blocks per stage from the ``layer<L>.<b>.conv1.weight`` keys (r18 [2,2,2,2], r50 [3,4,14,3], r100 [3,13,30,3])."""
-    depths = []
-    for li in range(1, 5):
-        b = 0
-        while f"layer{li}.{b}.conv1.weight" in sd:
-            b += 1
-        if b == 0:
-            raise KeyError(f"state dict has no layer{li}.0.conv1.weight (not an arcface_torch iresnet)")
-        depths.append(b)
-    return tuple(depths)
-
-
-def _np_state(state_dict: dict) -> dict:
-    sd = state_dict.get("state_dict", state_dict)
-    return {k.replace("module.", ""): np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in sd.items()}
-
-
-def _bn(sd, name, c):
-    out = []
-    for f in ("weight", "bias", "running_mean", "running_var"):
-        key = f"{name}.{f}"
-        if key not in sd:
-            raise KeyError(f"state dict has no {key}")
-        v = sd[key].astype(np.float64)
-        if v.shape != (c,):
-            raise ValueError(f"{key}: expected shape {(c,)}, got {v.shape}")
-        out.append(v)
-    g, b, mu, var = out
-    s = g / np.sqrt(var + _BN_EPS)
-    return s, b - mu * s
-
-
-def _tensor(sd, key, shape):
-    if key not in sd:
-        raise KeyError(f"state dict has no {key}")
-    v = sd[key]
-    if tuple(v.shape) != tuple(shape):
-        raise ValueError(f"{key}: expected shape {tuple(shape)}, got {tuple(v.shape)}")
-    return v.astype(np.float64)
+    return resnet_depths(sd, "an arcface_torch iresnet")
 
 
 def fold_state(state_dict: dict) -> dict:
@@ -98,35 +63,33 @@ def fold_state(state_dict: dict) -> dict:
     with every BatchNorm that follows a conv folded into it, and ``bn2 -> fc -> features`` folded into one fc whose
     columns are permuted from torch's NCHW flatten (``c * 49 + y * 7 + x``) to the device's NHWC (``(y * 7 + x) * 512 + c``).
     A missing or misshapen tensor raises."""
-    sd = _np_state(state_dict)
+    sd = np_state(state_dict)
     depths = depths_from_state(sd)
     convs, prelu, bns = {}, [], []
 
     def fold(conv, bn, cout, cin, k):
-        w = _tensor(sd, conv + ".weight", (cout, cin, k, k))
-        s, t = _bn(sd, bn, cout)
-        return (w * s[:, None, None, None]).astype(np.float32), t.astype(np.float32)
+        return fold_conv_bn(sd, conv, bn, (cout, cin, k, k))
 
     convs["conv1"] = fold("conv1", "bn1", 64, 3, 3)
-    prelu.append(_tensor(sd, "prelu.weight", (64,)).astype(np.float32))
+    prelu.append(tensor(sd, "prelu.weight", (64,)).astype(np.float32))
     inplanes = 64
     for li, (planes, depth) in enumerate(zip(WIDTHS, depths), start=1):
         for b in range(depth):
             p = f"layer{li}.{b}"
             cin = inplanes if b == 0 else planes
-            s, t = _bn(sd, p + ".bn1", cin)
+            s, t = bn_scale_shift(sd, p + ".bn1", cin)
             bns.append((s.astype(np.float32), t.astype(np.float32)))
             convs[p + ".conv1"] = fold(p + ".conv1", p + ".bn2", planes, cin, 3)
-            prelu.append(_tensor(sd, p + ".prelu.weight", (planes,)).astype(np.float32))
+            prelu.append(tensor(sd, p + ".prelu.weight", (planes,)).astype(np.float32))
             convs[p + ".conv2"] = fold(p + ".conv2", p + ".bn3", planes, planes, 3)
             if b == 0:
                 convs[p + ".downsample.0"] = fold(p + ".downsample.0", p + ".downsample.1", planes, cin, 1)
         inplanes = planes
     # fc(bn2(x)) = W (s2 * x + t2) + b, then features: a * (z - mu) + beta  (all exact: no padding is involved)
-    s2, t2 = _bn(sd, "bn2", 512)
-    W = _tensor(sd, "fc.weight", (FEAT, 512 * 49))
-    fb = _tensor(sd, "fc.bias", (FEAT,))
-    sf, tf = _bn(sd, "features", FEAT)
+    s2, t2 = bn_scale_shift(sd, "bn2", 512)
+    W = tensor(sd, "fc.weight", (FEAT, 512 * 49))
+    fb = tensor(sd, "fc.bias", (FEAT,))
+    sf, tf = bn_scale_shift(sd, "features", FEAT)
     s2x = np.repeat(s2, 49)  # NCHW flatten: channel c covers columns c * 49 .. c * 49 + 48
     t2x = np.repeat(t2, 49)
     Wf = sf[:, None] * (W * s2x[None, :])
@@ -145,16 +108,7 @@ def random_state_dict(seed: int = 3, depths=DEPTHS["r18"]) -> dict:
     benchmarks and tests (no checkpoint is reachable offline)."""
     rng = np.random.default_rng(seed)
     sd = {}
-
-    def conv(name, cout, cin, k, gain=1.0):
-        sd[name + ".weight"] = (gain * rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
-
-    def bn(name, c):
-        sd[name + ".weight"] = rng.uniform(0.7, 1.3, c).astype(np.float32)
-        sd[name + ".bias"] = (0.1 * rng.standard_normal(c)).astype(np.float32)
-        sd[name + ".running_mean"] = (0.1 * rng.standard_normal(c)).astype(np.float32)
-        sd[name + ".running_var"] = rng.uniform(0.6, 1.4, c).astype(np.float32)
-        sd[name + ".num_batches_tracked"] = np.array(0, np.int64)
+    conv, bn = partial(rand_conv, rng, sd), partial(rand_bn, rng, sd)
 
     def prelu(name, c):
         sd[name + ".weight"] = rng.uniform(0.15, 0.35, c).astype(np.float32)
@@ -226,37 +180,26 @@ class FaceEmbedder:
     """arcface_torch ``iresnet`` (``backbone.pth``) + the crop / normalisation of its inference script, on the device."""
 
     def __init__(self, state: dict):
-        self._lib = _lib.load()
-        _lib.init()
         self.depths = tuple(int(v) for v in state["depths"])
-        h = C.c_void_p()
-        _lib.check(self._lib.eioku_iresnet_create((C.c_int * 4)(*self.depths), C.byref(h)), "eioku_iresnet_create")
-        self._h = h
-        for i in range(self._lib.eioku_iresnet_num_convs(h)):
-            name = C.create_string_buffer(64)
-            co, ci, k, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-            _lib.check(self._lib.eioku_iresnet_conv_info(h, i, name, 64, C.byref(co), C.byref(ci), C.byref(k), C.byref(s)),
-                       "eioku_iresnet_conv_info")
-            n = name.value.decode()
-            if n not in state["convs"]:
-                raise KeyError(f"state has no weights for {n}")
-            w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state["convs"][n])
-            if w.shape != (co.value, ci.value, k.value, k.value) or b.shape != (co.value,):
-                raise ValueError(f"{n}: expected weight {(co.value, ci.value, k.value, k.value)}, got {w.shape}")
-            _lib.check(self._lib.eioku_iresnet_set_conv(h, i, ptr(w), ptr(b)), f"eioku_iresnet_set_conv({n})")
-        nb = self._lib.eioku_iresnet_num_blocks(h)
+        self._h = Handle("iresnet", (C.c_int * 4)(*self.depths))
+        self._h.or_close(self._load, state)
+
+    def _load(self, state: dict) -> None:
+        h = self._h
+        h.set_convs(state["convs"])
+        nb = h.eioku_iresnet_num_blocks()
         if len(state["prelu"]) != nb + 1 or len(state["bn"]) != nb:
             raise ValueError(f"state has {len(state['prelu'])} PReLUs / {len(state['bn'])} bn1s for {nb} blocks")
         for u, a in enumerate(state["prelu"]):
             a = np.ascontiguousarray(a, dtype=np.float32)
-            _lib.check(self._lib.eioku_iresnet_set_prelu(h, u, ptr(a)), "eioku_iresnet_set_prelu")
+            _lib.check(h.eioku_iresnet_set_prelu(u, ptr(a)), "eioku_iresnet_set_prelu")
         for b, (s, t) in enumerate(state["bn"]):
             s, t = np.ascontiguousarray(s, dtype=np.float32), np.ascontiguousarray(t, dtype=np.float32)
-            _lib.check(self._lib.eioku_iresnet_set_bn(h, b, ptr(s), ptr(t)), "eioku_iresnet_set_bn")
+            _lib.check(h.eioku_iresnet_set_bn(b, ptr(s), ptr(t)), "eioku_iresnet_set_bn")
         w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state["head"])
         if w.shape != (FEAT, 512 * 49) or b.shape != (FEAT,):
             raise ValueError(f"head: expected weight {(FEAT, 512 * 49)}, got {w.shape}")
-        _lib.check(self._lib.eioku_iresnet_set_head(h, ptr(w), ptr(b)), "eioku_iresnet_set_head")
+        _lib.check(h.eioku_iresnet_set_head(ptr(w), ptr(b)), "eioku_iresnet_set_head")
 
     @classmethod
     def from_cache(cls, cache_dir, model_name: str = "arcface_r18.pth", seed: int | None = None):
@@ -283,8 +226,8 @@ class FaceEmbedder:
         dev = frames_bgr.device if on_device(frames_bgr) else torch.device("cuda", torch.cuda.current_device())
         out = torch.empty((len(b), CROP, CROP, 8), dtype=torch.float16, device=dev)
         src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr, dtype=np.uint8)
-        _lib.check(self._lib.eioku_iresnet_crop(self._h, ptr(src), n, h, w, ptr(b), len(b), ptr(out),
-                                                _lib.MEM_DEVICE if on_device(src) else _lib.MEM_HOST, current_stream(out)),
+        _lib.check(self._h.eioku_iresnet_crop(ptr(src), n, h, w, ptr(b), len(b), ptr(out),
+                                              _lib.MEM_DEVICE if on_device(src) else _lib.MEM_HOST, current_stream(out)),
                    "eioku_iresnet_crop")
         return out
 
@@ -305,11 +248,11 @@ class FaceEmbedder:
                     break
                 k += d
             out = torch.empty((m, hw, hw, c), dtype=torch.float16, device=crops.device)
-            _lib.check(self._lib.eioku_iresnet_forward(self._h, ptr(crops), m, int(upto_block), ptr(out), None, current_stream(crops)),
+            _lib.check(self._h.eioku_iresnet_forward(ptr(crops), m, int(upto_block), ptr(out), None, current_stream(crops)),
                        "eioku_iresnet_forward")
             return out
         out = torch.empty((m, FEAT), dtype=torch.float32, device=crops.device)
-        _lib.check(self._lib.eioku_iresnet_forward(self._h, ptr(crops), m, -1, None, ptr(out), current_stream(crops)),
+        _lib.check(self._h.eioku_iresnet_forward(ptr(crops), m, -1, None, ptr(out), current_stream(crops)),
                    "eioku_iresnet_forward")
         return out
 
@@ -328,10 +271,10 @@ class FaceEmbedder:
             import torch
 
             dout = torch.empty((len(b), FEAT), dtype=torch.float32, device=src.device)
-            _lib.check(self._lib.eioku_iresnet_embed(self._h, ptr(src), n, h, w, ptr(b), len(b), ptr(dout), _lib.MEM_DEVICE,
-                                                     current_stream(src)), "eioku_iresnet_embed")
+            _lib.check(self._h.eioku_iresnet_embed(ptr(src), n, h, w, ptr(b), len(b), ptr(dout), _lib.MEM_DEVICE,
+                                                   current_stream(src)), "eioku_iresnet_embed")
             return dout.cpu().numpy()
-        _lib.check(self._lib.eioku_iresnet_embed(self._h, ptr(src), n, h, w, ptr(b), len(b), ptr(out), _lib.MEM_HOST, None),
+        _lib.check(self._h.eioku_iresnet_embed(ptr(src), n, h, w, ptr(b), len(b), ptr(out), _lib.MEM_HOST, None),
                    "eioku_iresnet_embed")
         return out
 
@@ -341,20 +284,10 @@ class FaceEmbedder:
         return labels.cpu().numpy() if on_device(labels) else labels
 
     def last_flops(self) -> float:
-        f = C.c_double(0)
-        _lib.check(self._lib.eioku_iresnet_last_flops(self._h, C.byref(f)), "eioku_iresnet_last_flops")
-        return f.value
+        return self._h.doubles("last_flops")[0]
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_iresnet_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h.close()
 
 
 class FaceClusterer:

@@ -17,7 +17,6 @@ that width.  English only.  No CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
 import json
 import math
 from pathlib import Path
@@ -26,12 +25,13 @@ import numpy as np
 
 from . import _lib
 from ._buffers import on_device, ptr
+from ._handle import Handle
+from ._state import BN_EPS as _BN_EPS, np_state as _np_state, tensor
 
 CANVAS = 2560
 MODEL_H = 64
 MAX_ROWS = 65536  # sequence steps per recogniser call (its input projection: 512 MiB of fp32 at this size)
 TAP_BITS = 11
-_BN_EPS = 1e-5
 SUPPORTED_LANGUAGES = ("en",)
 # readtext's defaults (easyocr.py, Reader.readtext)
 DEFAULTS = dict(min_size=20, text_threshold=0.7, low_text=0.4, link_threshold=0.4, slope_ths=0.1, ycenter_ths=0.5,
@@ -79,16 +79,10 @@ def confidence(idx, prob) -> float:
 
 
 # ---- weights -------------------------------------------------------------------------------------------------------
-def _np_state(state_dict: dict) -> dict:
-    sd = state_dict.get("state_dict", state_dict)
-    return {k[len("module."):] if k.startswith("module.") else k: np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
-            for k, v in sd.items()}
-
-
 def fold_conv(sd: dict, name: str):
     """Conv ``name`` (``<prefix>.<i>``) -> fp32 (weight, bias) with the BatchNorm ``<prefix>.<i + 1>`` folded in when the
     state dict has one (``y = (conv(x) + b - mean) * g / sqrt(var + eps) + beta``); a missing bias is zero."""
-    w = sd[name + ".weight"].astype(np.float64)
+    w = tensor(sd, name + ".weight")
     b = sd[name + ".bias"].astype(np.float64) if name + ".bias" in sd else np.zeros(w.shape[0])
     head, _, idx = name.rpartition(".")
     bn = f"{head}.{int(idx) + 1}" if idx.isdigit() else None
@@ -584,41 +578,35 @@ def align_collate(crop: np.ndarray, width: int, adjust_contrast: float = 0.0, im
 
 
 # ---- the reader ----------------------------------------------------------------------------------------------------
+def _set_lstms(crnn: Handle, sd: dict) -> None:
+    for l in range(2):
+        arrs = lstm_params(sd, l)  # held until the call returns
+        _lib.check(crnn.eioku_crnn_set_lstm(l, *(ptr(a) for a in arrs)), "eioku_crnn_set_lstm")
+
+
 class OcrReader:
     """CRAFT (K15) + english_g2 (K16) from state dicts; ``readtext_batch(frames)`` is ``readtext`` per frame."""
 
     def __init__(self, craft_state: dict, crnn_state: dict):
         import torch
 
-        self._lib = _lib.load()
-        _lib.init(torch.cuda.current_device() if torch.cuda.is_available() else 0)
         self.characters, self.ignore_idx = charset()
         sd_d, sd_r = _np_state(craft_state), _np_state(crnn_state)
-        nc = int(sd_r["Prediction.weight"].shape[0])
+        nc = int(tensor(sd_r, "Prediction.weight").shape[0])
         if nc != len(self.characters) + 1:
             raise ValueError(f"Prediction has {nc} classes; english_g2 needs {len(self.characters) + 1}")
         self.num_class = nc
         self._ignore = np.zeros(nc, np.uint8)
         self._ignore[self.ignore_idx] = 1
-        self._d, self._r = C.c_void_p(), C.c_void_p()
-        _lib.check(self._lib.eioku_craft_create(C.byref(self._d)), "eioku_craft_create")
-        _lib.check(self._lib.eioku_crnn_create(nc, C.byref(self._r)), "eioku_crnn_create")
-        self._load(sd_d, sd_r)
-
-    def _set_convs(self, handle, prefix: str, sd: dict):
-        """Every convolution the handle names (``eioku_<prefix>_conv_info``) from ``sd``, BatchNorm folded."""
-        lib, name = self._lib, C.create_string_buffer(128)
-        for i in range(getattr(lib, f"eioku_{prefix}_num_convs")(handle)):
-            _lib.check(getattr(lib, f"eioku_{prefix}_conv_info")(handle, i, name, 128, None, None, None), f"eioku_{prefix}_conv_info")
-            w, b = fold_conv(sd, name.value.decode())
-            _lib.check(getattr(lib, f"eioku_{prefix}_set_conv")(handle, i, ptr(w), ptr(b)), f"eioku_{prefix}_set_conv {name.value.decode()}")
+        device = torch.cuda.current_device() if torch.cuda.is_available() else 0
+        self._d = Handle("craft", device=device)
+        self._r = self._d.or_close(Handle, "crnn", nc, device=device)
+        self._d.or_close(self._r.or_close, self._load, sd_d, sd_r)
 
     def _load(self, sd_d, sd_r):
-        self._set_convs(self._d, "craft", sd_d)
-        self._set_convs(self._r, "crnn", sd_r)
-        for l in range(2):
-            arrs = lstm_params(sd_r, l)
-            _lib.check(self._lib.eioku_crnn_set_lstm(self._r, l, *(ptr(a) for a in arrs)), "eioku_crnn_set_lstm")
+        self._d.set_convs(lambda name, *_: fold_conv(sd_d, name))
+        self._r.set_convs(lambda name, *_: fold_conv(sd_r, name))
+        _set_lstms(self._r, sd_r)
 
     @classmethod
     def from_cache(cls, cache_dir, seed: int | None = None):
@@ -646,9 +634,9 @@ class OcrReader:
         link = torch.empty_like(text) if want_link else None
         binm = torch.empty((n, H // 2, W // 2), dtype=torch.uint8, device=dev)
         src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr)
-        _lib.check(self._lib.eioku_craft_forward(self._d, ptr(src), n, h, w, canvas, low_text, link_threshold, ptr(text), ptr(link),
-                                                 ptr(binm), _lib.MEM_DEVICE if on_device(frames_bgr) else _lib.MEM_HOST,
-                                                 torch.cuda.current_stream(dev).cuda_stream), "eioku_craft_forward")
+        _lib.check(self._d.eioku_craft_forward(ptr(src), n, h, w, canvas, low_text, link_threshold, ptr(text), ptr(link),
+                                               ptr(binm), _lib.MEM_DEVICE if on_device(frames_bgr) else _lib.MEM_HOST,
+                                               torch.cuda.current_stream(dev).cuda_stream), "eioku_craft_forward")
         return text, link, binm
 
     def canvas(self, frames_bgr, canvas: int = CANVAS):
@@ -661,9 +649,9 @@ class OcrReader:
         dev = frames_bgr.device if on_device(frames_bgr) else torch.device("cuda", torch.cuda.current_device())
         out = torch.empty((n, H, W, 8), dtype=torch.float16, device=dev)
         src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr)
-        _lib.check(self._lib.eioku_craft_canvas(self._d, ptr(src), n, h, w, canvas, ptr(out),
-                                                _lib.MEM_DEVICE if on_device(frames_bgr) else _lib.MEM_HOST,
-                                                torch.cuda.current_stream(dev).cuda_stream), "eioku_craft_canvas")
+        _lib.check(self._d.eioku_craft_canvas(ptr(src), n, h, w, canvas, ptr(out),
+                                              _lib.MEM_DEVICE if on_device(frames_bgr) else _lib.MEM_HOST,
+                                              torch.cuda.current_stream(dev).cuda_stream), "eioku_craft_canvas")
         return out
 
     # -- K16 --
@@ -688,8 +676,8 @@ class OcrReader:
         rows = int(T.sum())
         idx, prob = np.empty(rows, np.int32), np.empty(rows, np.float32)
         logits = np.empty((rows, self.num_class), np.float32) if want_logits else None
-        _lib.check(self._lib.eioku_crnn_forward(self._r, ptr(packed), ptr(widths), m, ptr(self._ignore), ptr(idx), ptr(prob),
-                                                ptr(logits), None), "eioku_crnn_forward")
+        _lib.check(self._r.eioku_crnn_forward(ptr(packed), ptr(widths), m, ptr(self._ignore), ptr(idx), ptr(prob),
+                                              ptr(logits), None), "eioku_crnn_forward")
         out, o = [], 0
         for t in T:
             out.append((idx[o:o + t], prob[o:o + t]) + ((logits[o:o + t],) if want_logits else ()))
@@ -734,24 +722,11 @@ class OcrReader:
         return out
 
     def last_flops(self) -> tuple:
-        d, r = C.c_double(), C.c_double()
-        _lib.check(self._lib.eioku_craft_last_flops(self._d, C.byref(d)), "eioku_craft_last_flops")
-        _lib.check(self._lib.eioku_crnn_last_flops(self._r, C.byref(r)), "eioku_crnn_last_flops")
-        return d.value, r.value
+        return self._d.doubles("last_flops")[0], self._r.doubles("last_flops")[0]
 
     def close(self):
-        if getattr(self, "_d", None):
-            self._lib.eioku_craft_destroy(self._d)
-            self._d = None
-        if getattr(self, "_r", None):
-            self._lib.eioku_crnn_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._d.close()
+        self._r.close()
 
 
 # ---- stage entry points (tests hold each stage to a reference of its own) ------------------------------------------
@@ -762,18 +737,15 @@ class SequenceTail:
     def __init__(self, crnn_state: dict):
         import torch
 
-        self._lib = _lib.load()
-        _lib.init(torch.cuda.current_device() if torch.cuda.is_available() else 0)
         sd = _np_state(crnn_state)
-        self.num_class = int(sd["Prediction.weight"].shape[0])
-        self._r = C.c_void_p()
-        _lib.check(self._lib.eioku_crnn_create(self.num_class, C.byref(self._r)), "eioku_crnn_create")
+        self.num_class = int(tensor(sd, "Prediction.weight").shape[0])
+        self._r = Handle("crnn", self.num_class, device=torch.cuda.current_device() if torch.cuda.is_available() else 0)
+        self._r.or_close(self._load, sd)
+
+    def _load(self, sd):
         w, b = (np.ascontiguousarray(sd["Prediction." + k], np.float32) for k in ("weight", "bias"))
-        _lib.check(self._lib.eioku_crnn_set_conv(self._r, self._lib.eioku_crnn_num_convs(self._r) - 1, ptr(w), ptr(b)),
-                   "eioku_crnn_set_conv Prediction")
-        for l in range(2):
-            arrs = lstm_params(sd, l)  # held until the call returns
-            _lib.check(self._lib.eioku_crnn_set_lstm(self._r, l, *(ptr(a) for a in arrs)), "eioku_crnn_set_lstm")
+        _lib.check(self._r.eioku_crnn_set_conv(self._r.eioku_crnn_num_convs() - 1, ptr(w), ptr(b)), "eioku_crnn_set_conv Prediction")
+        _set_lstms(self._r, sd)
 
     def __call__(self, seqs: list, ignore_idx=()):
         """Sequences float32 (T_i, 256) -> per sequence ``(idx int32 (T_i,), prob float32 (T_i,), logits (T_i, classes))``."""
@@ -784,21 +756,13 @@ class SequenceTail:
         ignore[list(ignore_idx)] = 1
         idx, prob = np.empty(rows, np.int32), np.empty(rows, np.float32)
         logits = np.empty((rows, self.num_class), np.float32)
-        _lib.check(self._lib.eioku_crnn_tail(self._r, ptr(packed), ptr(lens), len(seqs), ptr(ignore), ptr(idx), ptr(prob),
-                                             ptr(logits), None), "eioku_crnn_tail")
+        _lib.check(self._r.eioku_crnn_tail(ptr(packed), ptr(lens), len(seqs), ptr(ignore), ptr(idx), ptr(prob),
+                                           ptr(logits), None), "eioku_crnn_tail")
         o = np.concatenate([[0], np.cumsum(lens)])
         return [(idx[a:b], prob[a:b], logits[a:b]) for a, b in zip(o[:-1], o[1:])]
 
     def close(self):
-        if getattr(self, "_r", None):
-            self._lib.eioku_crnn_destroy(self._r)
-            self._r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._r.close()
 
 
 def ctc_probs(logits, ignore):

@@ -9,18 +9,19 @@ everything else runs on the device behind ``eioku_resnet18_classify``.  No CPU f
 """
 from __future__ import annotations
 
-import ctypes as C
+from functools import partial
 from pathlib import Path
 
 import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, on_device, ptr
+from ._handle import Handle
+from ._state import fold_conv_bn, np_state
 
 SIZE = 224
 NUM_CLASSES = 365
 PRECISION_BITS = 22  # Pillow Resample.c: 32 - 8 - 2 for 8-bit pixels
-_BN_EPS = 1e-5
 
 
 def resize_tables(in_size: int, out_size: int = SIZE):
@@ -73,15 +74,9 @@ def fold_state(state_dict: dict) -> dict:
     """torchvision ``resnet18`` state dict (optionally under ``"state_dict"`` and with ``module.`` prefixes, as the
     Places365 release ships it: ``model_manager.py:612-621``) -> ``{conv name: (weight, bias)}`` with each BatchNorm
     folded into its convolution, plus ``"fc": (weight, bias)``."""
-    sd = state_dict.get("state_dict", state_dict)
-    sd = {k.replace("module.", ""): np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in sd.items()}
+    sd = np_state(state_dict)
     out = {}
-
-    def fold(conv, bn):
-        w = sd[conv + ".weight"].astype(np.float64)
-        s = sd[bn + ".weight"].astype(np.float64) / np.sqrt(sd[bn + ".running_var"].astype(np.float64) + _BN_EPS)
-        b = sd[bn + ".bias"].astype(np.float64) - sd[bn + ".running_mean"].astype(np.float64) * s
-        return (w * s[:, None, None, None]).astype(np.float32), b.astype(np.float32)
+    fold = partial(fold_conv_bn, sd)
 
     out["conv1"] = fold("conv1", "bn1")
     for li in range(1, 5):
@@ -106,21 +101,13 @@ def random_state(seed: int = 3) -> dict:
     """Seeded random folded weights of the exact architecture (benchmarks, tests: no checkpoint is reachable offline)."""
     rng = np.random.default_rng(seed)
     st = {}
-    lib = _lib.load()
-    _lib.init()
-    h = C.c_void_p()
-    _lib.check(lib.eioku_resnet18_create(NUM_CLASSES, C.byref(h)), "eioku_resnet18_create")
-    try:
-        for i in range(lib.eioku_resnet18_num_convs(h)):
-            name = C.create_string_buffer(64)
-            co, ci, k, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-            _lib.check(lib.eioku_resnet18_conv_info(h, i, name, 64, C.byref(co), C.byref(ci), C.byref(k), C.byref(s)), "conv_info")
-            n = name.value.decode()
-            gain = 0.7 if n.endswith("conv2") else 1.4
-            st[n] = ((gain * rng.standard_normal((co.value, ci.value, k.value, k.value)) / np.sqrt(ci.value * k.value * k.value)).astype(np.float32),
-                     (0.05 * rng.standard_normal(co.value)).astype(np.float32))
-    finally:
-        lib.eioku_resnet18_destroy(h)
+    h = Handle("resnet18", NUM_CLASSES)
+    convs = h.or_close(h.convs)
+    h.close()
+    for n, co, ci, k, _ in convs:
+        gain = 0.7 if n.endswith("conv2") else 1.4
+        st[n] = ((gain * rng.standard_normal((co, ci, k, k)) / np.sqrt(ci * k * k)).astype(np.float32),
+                 (0.05 * rng.standard_normal(co)).astype(np.float32))
     st["fc"] = ((4.0 * rng.standard_normal((NUM_CLASSES, 512)) / np.sqrt(512)).astype(np.float32),
                 (0.1 * rng.standard_normal(NUM_CLASSES)).astype(np.float32))
     return st
@@ -131,29 +118,17 @@ class Places365Classifier:
     softmax / sort of ``classify_places`` (``model_manager.py:609-640,666-687``)."""
 
     def __init__(self, state: dict, labels: list[str] | None = None):
-        self._lib = _lib.load()
-        _lib.init()
         self.labels = list(labels) if labels is not None else [f"place_{i}" for i in range(NUM_CLASSES)]
-        h = C.c_void_p()
-        _lib.check(self._lib.eioku_resnet18_create(NUM_CLASSES, C.byref(h)), "eioku_resnet18_create")
-        self._h = h
         self._tables = {}
-        for i in range(self._lib.eioku_resnet18_num_convs(h)):
-            name = C.create_string_buffer(64)
-            co, ci, k, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-            _lib.check(self._lib.eioku_resnet18_conv_info(h, i, name, 64, C.byref(co), C.byref(ci), C.byref(k), C.byref(s)),
-                       "eioku_resnet18_conv_info")
-            n = name.value.decode()
-            if n not in state:
-                raise KeyError(f"state has no weights for {n}")
-            w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state[n])
-            if w.shape != (co.value, ci.value, k.value, k.value) or b.shape != (co.value,):
-                raise ValueError(f"{n}: expected weight {(co.value, ci.value, k.value, k.value)}, got {w.shape}")
-            _lib.check(self._lib.eioku_resnet18_set_conv(h, i, ptr(w), ptr(b)), f"eioku_resnet18_set_conv({n})")
+        self._h = Handle("resnet18", NUM_CLASSES)
+        self._h.or_close(self._load, state)
+
+    def _load(self, state: dict) -> None:
+        self._h.set_convs(state)
         w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state["fc"])
         if w.shape != (NUM_CLASSES, 512):
             raise ValueError(f"fc: expected weight {(NUM_CLASSES, 512)}, got {w.shape}")
-        _lib.check(self._lib.eioku_resnet18_set_fc(h, ptr(w), ptr(b)), "eioku_resnet18_set_fc")
+        _lib.check(self._h.eioku_resnet18_set_fc(ptr(w), ptr(b)), "eioku_resnet18_set_fc")
 
     @classmethod
     def from_cache(cls, cache_dir, seed: int | None = None):
@@ -182,9 +157,9 @@ class Places365Classifier:
         dev = frames_bgr.device if on_device(frames_bgr) else torch.device("cuda", torch.cuda.current_device())
         x = torch.empty((n, SIZE, SIZE, 4), dtype=torch.float16, device=dev)
         u8 = torch.empty((n, SIZE, SIZE, 3), dtype=torch.uint8, device=dev)
-        _lib.check(self._lib.eioku_places_preprocess(self._h, ptr(frames_bgr), n, h, w, ptr(xb), ptr(xk), kx, ptr(yb), ptr(yk), ky,
-                                                     ptr(x), ptr(u8), _lib.MEM_DEVICE if on_device(frames_bgr) else _lib.MEM_HOST,
-                                                     current_stream(x)), "eioku_places_preprocess")
+        _lib.check(self._h.eioku_places_preprocess(ptr(frames_bgr), n, h, w, ptr(xb), ptr(xk), kx, ptr(yb), ptr(yk), ky,
+                                                   ptr(x), ptr(u8), _lib.MEM_DEVICE if on_device(frames_bgr) else _lib.MEM_HOST,
+                                                   current_stream(x)), "eioku_places_preprocess")
         return x, u8
 
     def forward_raw(self, x):
@@ -193,7 +168,7 @@ class Places365Classifier:
 
         n = int(x.shape[0])
         out = torch.empty((n, NUM_CLASSES), dtype=torch.float32, device=x.device)
-        _lib.check(self._lib.eioku_resnet18_forward(self._h, ptr(x.contiguous()), n, ptr(out), current_stream(x)), "eioku_resnet18_forward")
+        _lib.check(self._h.eioku_resnet18_forward(ptr(x.contiguous()), n, ptr(out), current_stream(x)), "eioku_resnet18_forward")
         return out
 
     def classify(self, frames_bgr, top_k: int = 5, with_logits: bool = False):
@@ -216,9 +191,9 @@ class Places365Classifier:
             probs = np.empty((n, top_k), np.float32)
             cls = np.empty((n, top_k), np.int32)
             logits = np.empty((n, NUM_CLASSES), np.float32) if with_logits else None
-        _lib.check(self._lib.eioku_resnet18_classify(self._h, ptr(frames_bgr), n, h, w, ptr(xb), ptr(xk), kx, ptr(yb), ptr(yk), ky,
-                                                     top_k, ptr(probs), ptr(cls), ptr(logits),
-                                                     _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(frames_bgr)),
+        _lib.check(self._h.eioku_resnet18_classify(ptr(frames_bgr), n, h, w, ptr(xb), ptr(xk), kx, ptr(yb), ptr(yk), ky,
+                                                   top_k, ptr(probs), ptr(cls), ptr(logits),
+                                                   _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(frames_bgr)),
                    "eioku_resnet18_classify")
         if dev:
             probs, cls = probs.cpu().numpy(), cls.cpu().numpy()
@@ -226,17 +201,7 @@ class Places365Classifier:
         return (probs, cls, logits) if with_logits else (probs, cls)
 
     def last_flops(self) -> float:
-        f = C.c_double(0)
-        _lib.check(self._lib.eioku_resnet18_last_flops(self._h, C.byref(f)), "eioku_resnet18_last_flops")
-        return f.value
+        return self._h.doubles("last_flops")[0]
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_resnet18_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h.close()

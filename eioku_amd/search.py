@@ -13,12 +13,11 @@ every rank merges the ``world*k`` candidates locally (``eioku_topk_merge``).
 
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, on_device, ptr
+from ._handle import Handle
 
 
 class RowSelector:
@@ -67,23 +66,18 @@ class IndexFlatL2:
     """Exact squared-L2 index resident in HBM (d in {64,128,256,384,512}, k <= 32)."""
 
     def __init__(self, d: int):
-        lib = _lib.load()
-        _lib.init()
-        self._lib = lib
         self.d = int(d)
-        h = C.c_void_p()
-        _lib.check(lib.eioku_index_flat_create(self.d, C.byref(h)), "eioku_index_flat_create")
-        self._h = h
+        self._h = Handle("index", self.d, create="eioku_index_flat_create")
         self._attached = None  # keeps an attached tensor alive
 
     @property
     def ntotal(self) -> int:
-        return int(self._lib.eioku_index_ntotal(self._h))
+        return int(self._h.eioku_index_ntotal())
 
     @property
     def nlive(self) -> int:
         """Rows a search can return: ``ntotal`` minus the rows taken out by :meth:`remove_ids`."""
-        return int(self._lib.eioku_index_nlive(self._h))
+        return int(self._h.eioku_index_nlive())
 
     def remove_ids(self, ids) -> int:
         """Take rows out of every later search without rebuilding anything; returns how many were live until now.
@@ -100,7 +94,7 @@ class IndexFlatL2:
             ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
             n_ids, mem = int(ids.shape[0]), _lib.MEM_HOST
         if n_ids:
-            _lib.check(self._lib.eioku_index_remove_ids(self._h, ptr(ids), n_ids, mem, current_stream(ids)),
+            _lib.check(self._h.eioku_index_remove_ids(ptr(ids), n_ids, mem, current_stream(ids)),
                        "eioku_index_remove_ids")
         return before - self.nlive
 
@@ -138,19 +132,19 @@ class IndexFlatL2:
             raise ValueError(f"expected dimension {self.d}, got {d}")
         if not on_device(x):
             x = np.ascontiguousarray(x, dtype=np.float32)
-        _lib.check(self._lib.eioku_index_add(self._h, ptr(x), n, _lib.MEM_DEVICE if on_device(x) else _lib.MEM_HOST,
-                                             current_stream(x)), "eioku_index_add")
+        _lib.check(self._h.eioku_index_add(ptr(x), n, _lib.MEM_DEVICE if on_device(x) else _lib.MEM_HOST,
+                                           current_stream(x)), "eioku_index_add")
 
     def attach(self, x_cuda) -> None:
         """Search an existing CUDA float32 ``(n,d)`` tensor in place (no copy; the tensor must outlive the index)."""
         n, d = (int(s) for s in x_cuda.shape)
         if d != self.d or not on_device(x_cuda):
             raise ValueError("attach() needs a CUDA tensor of shape (n, d)")
-        _lib.check(self._lib.eioku_index_attach(self._h, ptr(x_cuda), n, current_stream(x_cuda)), "eioku_index_attach")
+        _lib.check(self._h.eioku_index_attach(ptr(x_cuda), n, current_stream(x_cuda)), "eioku_index_attach")
         self._attached = x_cuda
 
     def reset(self) -> None:
-        _lib.check(self._lib.eioku_index_reset(self._h), "eioku_index_reset")
+        _lib.check(self._h.eioku_index_reset(), "eioku_index_reset")
         self._attached = None
 
     def search(self, q, k: int, sel=None):
@@ -176,7 +170,7 @@ class IndexFlatL2:
             D = np.empty((nq, k), dtype=np.float32)
             I = np.empty((nq, k), dtype=np.int64)
             mem = _lib.MEM_HOST
-        _lib.check(self._lib.eioku_index_search(self._h, ptr(q), nq, int(k), ptr(D), ptr(I), mem, current_stream(q)),
+        _lib.check(self._h.eioku_index_search(ptr(q), nq, int(k), ptr(D), ptr(I), mem, current_stream(q)),
                    "eioku_index_search")
         return D, I
 
@@ -201,10 +195,10 @@ class IndexFlatL2:
             D = np.empty((nq, k), dtype=np.float32)
             I = np.empty((nq, k), dtype=np.int64)
             mem = _lib.MEM_HOST
-        _lib.check(self._lib.eioku_index_search_sel(self._h, ptr(q), nq, int(k), sel_ptr, sel_mem,
-                                                    None if after_D is None else ptr(after_D),
-                                                    None if after_I is None else ptr(after_I), ptr(D), ptr(I), mem,
-                                                    current_stream(q)), "eioku_index_search_sel")
+        _lib.check(self._h.eioku_index_search_sel(ptr(q), nq, int(k), sel_ptr, sel_mem,
+                                                  None if after_D is None else ptr(after_D),
+                                                  None if after_I is None else ptr(after_I), ptr(D), ptr(I), mem,
+                                                  current_stream(q)), "eioku_index_search_sel")
         del keep
         return D, I
 
@@ -231,8 +225,8 @@ class IndexFlatL2:
             D = np.empty((nq, k), dtype=np.float32)
             I = np.empty((nq, k), dtype=np.int64)
             mem = _lib.MEM_HOST
-        _lib.check(self._lib.eioku_index_search_after(self._h, ptr(q), nq, int(k), ptr(after_D), ptr(after_I), ptr(D),
-                                                      ptr(I), mem, current_stream(q)), "eioku_index_search_after")
+        _lib.check(self._h.eioku_index_search_after(ptr(q), nq, int(k), ptr(after_D), ptr(after_I), ptr(D),
+                                                    ptr(I), mem, current_stream(q)), "eioku_index_search_after")
         return D, I
 
     def search_many(self, q, k: int, sel=None):
@@ -268,18 +262,10 @@ class IndexFlatL2:
 
     def set_param(self, name: str, value: int) -> None:
         """Knobs of the search paths (``eioku_index_set_param``): scan_mode, scan_cap, scan_min_rows, ..., sel_list_ppm."""
-        _lib.check(self._lib.eioku_index_set_param(self._h, name.encode(), int(value)), f"eioku_index_set_param({name})")
+        _lib.check(self._h.eioku_index_set_param(name.encode(), int(value)), f"eioku_index_set_param({name})")
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_index_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h.close()
 
 
 def merge_topk(d_lists, i_lists, k: int):
@@ -345,36 +331,20 @@ class RcclComm:
     ID_BYTES = 128
 
     def __init__(self, unique_id: bytes, rank: int, world: int):
-        import ctypes as C
-
         if len(unique_id) != self.ID_BYTES:
             raise ValueError(f"unique id must be {self.ID_BYTES} bytes, got {len(unique_id)}")
-        self._lib = _lib.load()
-        _lib.init()
-        h = C.c_void_p()
-        buf = C.create_string_buffer(bytes(unique_id), self.ID_BYTES)
-        _lib.check(self._lib.eioku_comm_create(C.cast(buf, C.c_void_p), int(rank), int(world), C.byref(h)), "eioku_comm_create")
-        self._h, self.rank, self.world = h, int(rank), int(world)
+        uid = np.frombuffer(bytes(unique_id), np.uint8)  # held until the create call returns
+        self._h = Handle("comm", ptr(uid), int(rank), int(world))
+        self.rank, self.world = int(rank), int(world)
 
     @staticmethod
     def unique_id() -> bytes:
-        import ctypes as C
-
-        lib = _lib.load()
-        buf = C.create_string_buffer(RcclComm.ID_BYTES)
-        _lib.check(lib.eioku_comm_unique_id(C.cast(buf, C.c_void_p)), "eioku_comm_unique_id")
-        return buf.raw
+        buf = np.zeros(RcclComm.ID_BYTES, np.uint8)
+        _lib.check(_lib.load().eioku_comm_unique_id(ptr(buf)), "eioku_comm_unique_id")
+        return buf.tobytes()
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_comm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h.close()
 
 
 class CommShardedFlatL2:
@@ -395,6 +365,6 @@ class CommShardedFlatL2:
         q = q.contiguous()
         D = torch.empty((nq, k), dtype=torch.float32, device=q.device)
         I = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-        _lib.check(self.local._lib.eioku_index_search_sharded(self.local._h, self.comm._h, self.id_base, ptr(q), nq, int(k),
-                                                              ptr(D), ptr(I), current_stream(q)), "eioku_index_search_sharded")
+        _lib.check(self.local._h.eioku_index_search_sharded(self.comm._h.ptr, self.id_base, ptr(q), nq, int(k),
+                                                            ptr(D), ptr(I), current_stream(q)), "eioku_index_search_sharded")
         return D, I

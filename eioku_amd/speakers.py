@@ -16,12 +16,15 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from functools import partial
 from pathlib import Path
 
 import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, on_device, ptr
+from ._handle import Handle
+from ._state import fold_conv_bn, np_state, rand_bn, rand_conv, resnet_depths, tensor
 
 SAMPLE_RATE = 16000
 FRAME = 400            # 25 ms
@@ -39,7 +42,7 @@ N_STAT = 2 * WIDTHS[3] * (N_MEL // 8)   # 5120
 PASS = 64              # windows per network pass
 MAX_SEGMENTS = 65536   # K14's limit
 DEPTHS = {"r18": (2, 2, 2, 2), "r34": (3, 4, 6, 3)}
-_BN_EPS = 1e-5
+_STRIP = ("module.", "resnet.")
 # picked, not tuned: no checkpoint was available to validate them against
 DEFAULT_EPS = 0.25
 DEFAULT_MIN_SAMPLES = 2
@@ -94,43 +97,9 @@ def kaldi_mel_banks(low: float = 20.0, high: float = SAMPLE_RATE / 2) -> np.ndar
 
 
 # ---- WeSpeaker state dict -> folded parameters --------------------------------------------------------------------------
-def _np_state(state_dict: dict) -> dict:
-    sd = state_dict.get("state_dict", state_dict)
-    out = {}
-    for k, v in sd.items():
-        while k.startswith(("module.", "resnet.")):
-            k = k.split(".", 1)[1]
-        out[k] = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
-    return out
-
-
 def depths_from_state(sd: dict) -> tuple:
     """Blocks per stage from the ``layer<L>.<b>.conv1.weight`` keys (r18 (2,2,2,2), r34 (3,4,6,3)); prefixes are stripped."""
-    sd = _np_state(sd)
-    depths = []
-    for li in range(1, 5):
-        b = 0
-        while f"layer{li}.{b}.conv1.weight" in sd:
-            b += 1
-        if b == 0:
-            raise KeyError(f"state dict has no layer{li}.0.conv1.weight (not a WeSpeaker ResNet)")
-        depths.append(b)
-    return tuple(depths)
-
-
-def _tensor(sd, key, shape):
-    if key not in sd:
-        raise KeyError(f"state dict has no {key}")
-    v = sd[key]
-    if tuple(v.shape) != tuple(shape):
-        raise ValueError(f"{key}: expected shape {tuple(shape)}, got {tuple(v.shape)}")
-    return v.astype(np.float64)
-
-
-def _bn(sd, name, c):
-    g, b, mu, var = (_tensor(sd, f"{name}.{f}", (c,)) for f in ("weight", "bias", "running_mean", "running_var"))
-    s = g / np.sqrt(var + _BN_EPS)
-    return s, b - mu * s
+    return resnet_depths(np_state(sd, _STRIP), "a WeSpeaker ResNet")
 
 
 def torch_to_device_columns(w: np.ndarray) -> np.ndarray:
@@ -150,14 +119,12 @@ def fold_state(state_dict: dict) -> dict:
     """WeSpeaker ``ResNet`` state dict (optionally under ``"state_dict"`` / with ``module.`` / ``resnet.`` prefixes) ->
     ``{"depths", "convs": {name: (w, b)}, "head": (w, b)}``: every BatchNorm folded into the conv before it, ``seg_1``'s
     columns permuted to the device's order.  A missing or misshapen tensor raises."""
-    sd = _np_state(state_dict)
+    sd = np_state(state_dict, _STRIP)
     depths = depths_from_state(sd)
     convs = {}
 
     def fold(conv, bn, cout, cin, k):
-        w = _tensor(sd, conv + ".weight", (cout, cin, k, k))
-        s, t = _bn(sd, bn, cout)
-        return (w * s[:, None, None, None]).astype(np.float32), t.astype(np.float32)
+        return fold_conv_bn(sd, conv, bn, (cout, cin, k, k))
 
     convs["conv1"] = fold("conv1", "bn1", WIDTHS[0], 1, 3)
     inplanes = WIDTHS[0]
@@ -170,8 +137,8 @@ def fold_state(state_dict: dict) -> dict:
             if b == 0 and li > 1:
                 convs[p + ".shortcut.0"] = fold(p + ".shortcut.0", p + ".shortcut.1", planes, cin, 1)
         inplanes = planes
-    w = _tensor(sd, "seg_1.weight", (FEAT, N_STAT))
-    b = _tensor(sd, "seg_1.bias", (FEAT,))
+    w = tensor(sd, "seg_1.weight", (FEAT, N_STAT))
+    b = tensor(sd, "seg_1.bias", (FEAT,))
     return {"depths": depths, "convs": convs, "head": (torch_to_device_columns(w).astype(np.float32), b.astype(np.float32))}
 
 
@@ -181,17 +148,7 @@ def random_state_dict(seed: int = 3, depths=DEPTHS["r34"]) -> dict:
     activations of an r34 far inside fp16, which plain He initialisation does not."""
     rng = np.random.default_rng(seed)
     sd = {}
-
-    def conv(name, cout, cin, k, gain=1.0):
-        sd[name + ".weight"] = (gain * rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
-
-    def bn(name, c):
-        sd[name + ".weight"] = rng.uniform(0.7, 1.3, c).astype(np.float32)
-        sd[name + ".bias"] = (0.1 * rng.standard_normal(c)).astype(np.float32)
-        sd[name + ".running_mean"] = (0.1 * rng.standard_normal(c)).astype(np.float32)
-        sd[name + ".running_var"] = rng.uniform(0.6, 1.4, c).astype(np.float32)
-        sd[name + ".num_batches_tracked"] = np.array(0, np.int64)
-
+    conv, bn = partial(rand_conv, rng, sd), partial(rand_bn, rng, sd)
     conv("conv1", WIDTHS[0], 1, 3, 1.4)
     bn("bn1", WIDTHS[0])
     inplanes = WIDTHS[0]
@@ -276,41 +233,20 @@ class SpeakerLabeller:
     """WeSpeaker ResNet (``avg_model.pt``) with its Kaldi fbank front end and the per-video clustering, on the device."""
 
     def __init__(self, state: dict, win_frames: int = WIN):
-        self._lib = _lib.load()
-        _lib.init()
         self.depths = tuple(int(v) for v in state["depths"])
         self.win = int(win_frames)
         if self.win < 16 or self.win % 8:
             raise ValueError(f"win_frames must be a multiple of 8, at least 16, got {win_frames!r}")
         window, mel = povey_window(), np.ascontiguousarray(kaldi_mel_banks())
-        h = C.c_void_p()
-        _lib.check(self._lib.eioku_spk_create((C.c_int * 4)(*self.depths), self.win, ptr(window), ptr(mel), C.byref(h)),
-                   "eioku_spk_create")
-        self._h = h
-        try:
-            self._load(state)
-        except Exception:
-            self.close()
-            raise
+        self._h = Handle("spk", (C.c_int * 4)(*self.depths), self.win, ptr(window), ptr(mel))
+        self._h.or_close(self._load, state)
 
     def _load(self, state: dict) -> None:
-        h = self._h
-        for i in range(self._lib.eioku_spk_num_convs(h)):
-            name = C.create_string_buffer(64)
-            co, ci, k, s = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-            _lib.check(self._lib.eioku_spk_conv_info(h, i, name, 64, C.byref(co), C.byref(ci), C.byref(k), C.byref(s)),
-                       "eioku_spk_conv_info")
-            n = name.value.decode()
-            if n not in state["convs"]:
-                raise KeyError(f"state has no weights for {n}")
-            w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state["convs"][n])
-            if w.shape != (co.value, ci.value, k.value, k.value) or b.shape != (co.value,):
-                raise ValueError(f"{n}: expected weight {(co.value, ci.value, k.value, k.value)}, got {w.shape}")
-            _lib.check(self._lib.eioku_spk_set_conv(h, i, ptr(w), ptr(b)), f"eioku_spk_set_conv({n})")
+        self._h.set_convs(state["convs"])
         w, b = (np.ascontiguousarray(a, dtype=np.float32) for a in state["head"])
         if w.shape != (FEAT, N_STAT) or b.shape != (FEAT,):
             raise ValueError(f"head: expected weight {(FEAT, N_STAT)}, got {w.shape}")
-        _lib.check(self._lib.eioku_spk_set_head(h, ptr(w), ptr(b)), "eioku_spk_set_head")
+        _lib.check(self._h.eioku_spk_set_head(ptr(w), ptr(b)), "eioku_spk_set_head")
 
     @classmethod
     def from_cache(cls, cache_dir, model_name: str = "voxceleb_resnet34_LM", seed: int | None = None, **kw):
@@ -339,8 +275,8 @@ class SpeakerLabeller:
         else:
             s = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
         n = int(s.shape[0])
-        _lib.check(self._lib.eioku_spk_set_audio(self._h, ptr(s) if n else None, n, _lib.MEM_DEVICE if on_device(s) else _lib.MEM_HOST,
-                                                 current_stream(s)), "eioku_spk_set_audio")
+        _lib.check(self._h.eioku_spk_set_audio(ptr(s) if n else None, n, _lib.MEM_DEVICE if on_device(s) else _lib.MEM_HOST,
+                                               current_stream(s)), "eioku_spk_set_audio")
 
     @staticmethod
     def _plan(plan) -> np.ndarray:
@@ -356,7 +292,7 @@ class SpeakerLabeller:
         dev = self._device()
         f16 = torch.empty((len(p), N_MEL, self.win, 8), dtype=torch.float16, device=dev)
         f32 = torch.empty((len(p), N_MEL, self.win), dtype=torch.float32, device=dev)
-        _lib.check(self._lib.eioku_spk_features(self._h, ptr(p), len(p), ptr(f16), ptr(f32), current_stream(f16)), "eioku_spk_features")
+        _lib.check(self._h.eioku_spk_features(ptr(p), len(p), ptr(f16), ptr(f32), current_stream(f16)), "eioku_spk_features")
         return f16, f32
 
     def block_shape(self, upto_block: int) -> tuple:
@@ -382,15 +318,15 @@ class SpeakerLabeller:
             raise ValueError(f"expected fp16 (m, {N_MEL}, {self.win}, 8) features")
         if upto_block >= 0:
             out = torch.empty((m, *self.block_shape(upto_block)), dtype=torch.float16, device=feats.device)
-            _lib.check(self._lib.eioku_spk_forward(self._h, ptr(feats), None, m, int(upto_block), ptr(out), None, None,
-                                                   current_stream(feats)), "eioku_spk_forward")
+            _lib.check(self._h.eioku_spk_forward(ptr(feats), None, m, int(upto_block), ptr(out), None, None,
+                                                 current_stream(feats)), "eioku_spk_forward")
             return out
         v = np.ascontiguousarray(valid, dtype=np.int32).reshape(-1)
         if len(v) != m:
             raise ValueError(f"{m} windows but {len(v)} valid counts")
         out = torch.empty((m, FEAT), dtype=torch.float32, device=feats.device)
         st = torch.empty((m, N_STAT), dtype=torch.float32, device=feats.device) if stats else None
-        _lib.check(self._lib.eioku_spk_forward(self._h, ptr(feats), ptr(v), m, -1, None, ptr(st), ptr(out), current_stream(feats)),
+        _lib.check(self._h.eioku_spk_forward(ptr(feats), ptr(v), m, -1, None, ptr(st), ptr(out), current_stream(feats)),
                    "eioku_spk_forward")
         return (out, st) if stats else out
 
@@ -402,8 +338,8 @@ class SpeakerLabeller:
         self.set_audio(samples)
         p = self._plan(plan)
         out = torch.empty((len(p), FEAT), dtype=torch.float32, device=self._device())
-        _lib.check(self._lib.eioku_spk_embed(self._h, ptr(p) if len(p) else None, len(p), ptr(out) if len(p) else None,
-                                             current_stream(out)), "eioku_spk_embed")
+        _lib.check(self._h.eioku_spk_embed(ptr(p) if len(p) else None, len(p), ptr(out) if len(p) else None,
+                                           current_stream(out)), "eioku_spk_embed")
         return out
 
     def segment_vectors(self, window_vectors, seg_first):
@@ -418,7 +354,7 @@ class SpeakerLabeller:
             raise ValueError("seg_first does not cover the window vectors")
         out = torch.empty((max(n, 0), FEAT), dtype=torch.float32, device=wv.device)
         if n > 0:
-            _lib.check(self._lib.eioku_spk_segments(ptr(wv), ptr(first), n, ptr(out), current_stream(wv)), "eioku_spk_segments")
+            _lib.check(self._h.lib.eioku_spk_segments(ptr(wv), ptr(first), n, ptr(out), current_stream(wv)), "eioku_spk_segments")
         return out
 
     def embed_segments(self, samples, segments):
@@ -454,17 +390,7 @@ class SpeakerLabeller:
 
     def last_ms(self) -> tuple[float, float, float]:
         """Device milliseconds of the last ``embed_windows``: (features, network, pooling + seg_1)."""
-        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
-        _lib.check(self._lib.eioku_spk_last_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "eioku_spk_last_ms")
-        return a.value, b.value, c.value
+        return self._h.doubles("last_ms", 3)
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_spk_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h.close()

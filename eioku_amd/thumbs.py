@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, on_device, ptr
+from ._handle import Handle
 
 PRECISION_BITS = 22  # Pillow Resample.c: 32 - 8 - 2 for 8-bit pixels
 MAX_SIDE = 1024      # per thumbnail side (eioku_thumbs_*)
@@ -160,14 +161,10 @@ class ThumbnailEncoder:
     device.  ``size`` is the bounding box ``(width, height)``; a frame that fits inside it keeps its size."""
 
     def __init__(self, size=(320, 180), quality: int = 75):
-        self._lib = _lib.load()
-        _lib.init()
         self.size = (int(size[0]), int(size[1]))
         self.quality = int(quality)
         self._tables = {}
-        h = C.c_void_p()
-        _lib.check(self._lib.eioku_thumbs_create(C.byref(h)), "eioku_thumbs_create")
-        self._h = h
+        self._h = Handle("thumbs")
 
     def _device(self, x):
         import torch
@@ -198,8 +195,8 @@ class ThumbnailEncoder:
         else:  # the library refuses the size before it reads a table
             xb = xk = yb = yk = np.zeros((1, 2), np.int32)
             kx = ky = 1
-        _lib.check(self._lib.eioku_thumbs_resize(self._h, ptr(src), n, h, w, th, tw, ptr(xb), ptr(xk), kx, ptr(yb), ptr(yk), ky,
-                                                 ptr(out), current_stream(src)), "eioku_thumbs_resize")
+        _lib.check(self._h.eioku_thumbs_resize(ptr(src), n, h, w, th, tw, ptr(xb), ptr(xk), kx, ptr(yb), ptr(yk), ky,
+                                               ptr(out), current_stream(src)), "eioku_thumbs_resize")
         return out
 
     def jpeg(self, rgb, quality: int | None = None, with_coef: bool = False):
@@ -213,10 +210,10 @@ class ThumbnailEncoder:
         nbits = np.zeros(max(n, 1), np.uint32)
         total = C.c_uint64(0)
         coef = np.empty((n, -(-th // 16) * -(-tw // 16), 6, 64), np.int16) if with_coef else None
-        _lib.check(self._lib.eioku_thumbs_jpeg(self._h, ptr(src), n, th, tw, ptr(qtab), ptr(coef), ptr(nbits), C.byref(total),
-                                               current_stream(src)), "eioku_thumbs_jpeg")
+        _lib.check(self._h.eioku_thumbs_jpeg(ptr(src), n, th, tw, ptr(qtab), ptr(coef), ptr(nbits), C.byref(total),
+                                             current_stream(src)), "eioku_thumbs_jpeg")
         packed = np.empty(max(total.value, 1), np.uint8)
-        _lib.check(self._lib.eioku_thumbs_read(self._h, ptr(packed), total.value, current_stream(src)), "eioku_thumbs_read")
+        _lib.check(self._h.eioku_thumbs_read(ptr(packed), total.value, current_stream(src)), "eioku_thumbs_read")
         streams, pos = [], 0
         for i in range(n):
             nb = int(nbits[i])
@@ -239,19 +236,11 @@ class ThumbnailEncoder:
     def last_ms(self) -> dict:
         """Device milliseconds of the last resize, block stage, entropy stage and bitstream read."""
         ms = np.zeros(4, np.float64)
-        _lib.check(self._lib.eioku_thumbs_last_ms(self._h, ptr(ms)), "eioku_thumbs_last_ms")
+        _lib.check(self._h.eioku_thumbs_last_ms(ptr(ms)), "eioku_thumbs_last_ms")
         return dict(zip(("resize", "blocks", "entropy", "d2h"), (float(v) for v in ms)))
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.eioku_thumbs_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._h.close()
 
 
 # ---- which frame, which segment -----------------------------------------------------------------------------------

@@ -27,6 +27,8 @@ from pathlib import Path
 
 import numpy as np
 
+from ._handle import Handle
+
 logger = logging.getLogger(__name__)
 
 SAMPLE_RATE = 16000
@@ -482,8 +484,6 @@ class WhisperTranscriber:
         from . import _lib
 
         self._lib_mod = _lib
-        self.lib = _lib.load()
-        _lib.init()
         self.dims = dict(dims)
         self.sync_every = int(sync_every)
         self.decoder = ByteDecoder(vocab or {})
@@ -498,31 +498,14 @@ class WhisperTranscriber:
         cfg.max_initial_timestamp_index = -1 if mi is None else int(mi)
         cfg.n_suppress, cfg.n_begin_suppress, cfg.n_langs = (len(a) for a in self._keep[:3])
         cfg.suppress, cfg.begin_suppress, cfg.lang_ids, cfg.mel_filters = (a.ctypes.data for a in self._keep)
-        handle = C.c_void_p()
-        _lib.check(self.lib.eioku_whisper_create(C.byref(cfg), C.byref(handle)), "eioku_whisper_create")
-        self._h = handle
+        self._h = Handle("whisper", C.byref(cfg))
         self.window_frames = 2 * d["max_source_positions"]
-        if d.get("alignment_heads"):
-            self.set_alignment_heads(d["alignment_heads"])
-        self._load(weights)
+        self._h.or_close(self._load, weights)
 
     def _load(self, weights) -> None:
-        lib, check = self.lib, self._lib_mod.check
-        name = C.create_string_buffer(256)
-        rows, cols = C.c_int(0), C.c_int(0)
-        for i in range(lib.eioku_whisper_num_tensors(self._h)):
-            check(lib.eioku_whisper_tensor_info(self._h, i, name, 256, C.byref(rows), C.byref(cols)), "eioku_whisper_tensor_info")
-            n = name.value.decode()
-            if callable(weights):
-                arr = weights(n, rows.value, cols.value)
-            elif n in weights:
-                arr = weights[n]
-            else:
-                raise KeyError(f"checkpoint has no tensor {n}")
-            arr = np.ascontiguousarray(np.asarray(arr, dtype=np.float32)).reshape(-1)
-            if arr.size != rows.value * cols.value:
-                raise ValueError(f"{n}: expected {rows.value * cols.value} elements, checkpoint has {arr.size}")
-            check(lib.eioku_whisper_set_tensor(self._h, i, arr.ctypes.data, arr.size), f"eioku_whisper_set_tensor({n})")
+        if self.dims.get("alignment_heads"):
+            self.set_alignment_heads(self.dims["alignment_heads"])
+        self._h.set_tensors(weights)
 
     @classmethod
     def from_cache(cls, cache_dir: str | Path, model_name: str = "base", seed: int | None = None, **kw):
@@ -547,26 +530,19 @@ class WhisperTranscriber:
         return cls(dims, weights, vocab, **kw)
 
     def close(self) -> None:
-        if getattr(self, "_h", None):
-            self.lib.eioku_whisper_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # noqa: D105
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        if getattr(self, "_h", None):  # subclasses that script the device calls never create one
+            self._h.close()
 
     # -- device calls
     def set_audio(self, samples: np.ndarray) -> None:
         self._samples = np.ascontiguousarray(samples, dtype=np.float32)
-        self._lib_mod.check(self.lib.eioku_whisper_set_audio(self._h, self._samples.ctypes.data, self._samples.size),
+        self._lib_mod.check(self._h.eioku_whisper_set_audio(self._samples.ctypes.data, self._samples.size),
                             "eioku_whisper_set_audio")
 
     def logmel(self, offsets, fetch: bool = True):
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         out = np.empty((len(off), self.dims["n_mels"], self.window_frames), dtype=np.float32) if fetch else None
-        self._lib_mod.check(self.lib.eioku_whisper_logmel(self._h, off.ctypes.data, len(off), out.ctypes.data if fetch else None),
+        self._lib_mod.check(self._h.eioku_whisper_logmel(off.ctypes.data, len(off), out.ctypes.data if fetch else None),
                             "eioku_whisper_logmel")
         return out
 
@@ -575,12 +551,12 @@ class WhisperTranscriber:
             mel = np.ascontiguousarray(mel, dtype=np.float32)
             if mel.shape != (n_windows, self.dims["n_mels"], self.window_frames):
                 raise ValueError(f"mel must be {(n_windows, self.dims['n_mels'], self.window_frames)}, got {mel.shape}")
-        self._lib_mod.check(self.lib.eioku_whisper_encode(self._h, mel.ctypes.data if mel is not None else None, n_windows),
+        self._lib_mod.check(self._h.eioku_whisper_encode(mel.ctypes.data if mel is not None else None, n_windows),
                             "eioku_whisper_encode")
 
     def encoder_output(self, n_windows: int) -> np.ndarray:
         out = np.empty((n_windows, self.dims["max_source_positions"], self.dims["d_model"]), dtype=np.float16)
-        self._lib_mod.check(self.lib.eioku_whisper_encoder_output(self._h, out.ctypes.data, out.size), "eioku_whisper_encoder_output")
+        self._lib_mod.check(self._h.eioku_whisper_encoder_output(out.ctypes.data, out.size), "eioku_whisper_encoder_output")
         return out
 
     def decode(self, prompt, n_windows: int, max_new_tokens: int, sync_every: int | None = None) -> dict:
@@ -591,8 +567,8 @@ class WhisperTranscriber:
         lang = np.zeros(B, dtype=np.int32)
         total = np.zeros(B, dtype=np.float32)
         nsp = np.zeros(B, dtype=np.float32)
-        self._lib_mod.check(self.lib.eioku_whisper_decode(
-            self._h, p.ctypes.data, len(p), B, n, int(sync_every or self.sync_every), tokens.ctypes.data, n_out.ctypes.data,
+        self._lib_mod.check(self._h.eioku_whisper_decode(
+            p.ctypes.data, len(p), B, n, int(sync_every or self.sync_every), tokens.ctypes.data, n_out.ctypes.data,
             total.ctypes.data, nsp.ctypes.data, lang.ctypes.data), "eioku_whisper_decode")
         return {"tokens": tokens[:, :n], "n": n_out, "sum_logprob": total, "no_speech_prob": nsp, "lang": lang}
 
@@ -609,8 +585,8 @@ class WhisperTranscriber:
         B, n, Cn = int(n_windows), int(max_new_tokens), finish_count(W, patience)
         out, tr, tr_ptrs = self._beam_outputs(B, W, Cn, n, trace)
         lang = np.zeros(B, dtype=np.int32)
-        self._lib_mod.check(self.lib.eioku_whisper_decode_beam(
-            self._h, p.ctypes.data, len(p), B, W, Cn, n, int(sync_every or self.sync_every), *(a.ctypes.data for a in out.values()),
+        self._lib_mod.check(self._h.eioku_whisper_decode_beam(
+            p.ctypes.data, len(p), B, W, Cn, n, int(sync_every or self.sync_every), *(a.ctypes.data for a in out.values()),
             lang.ctypes.data, *tr_ptrs), "eioku_whisper_decode_beam")
         return {**out, "lang": lang, **tr}
 
@@ -651,8 +627,8 @@ class WhisperTranscriber:
         src, tok, fsrc = (np.zeros(L, dtype=np.int32) for _ in range(3))
         osum, fsum = np.zeros(L, dtype=np.float32), np.zeros(L, dtype=np.float32)
         n_live, n_fin, fc_out, complete = (np.zeros(B, dtype=np.int32) for _ in range(4))
-        self._lib_mod.check(self.lib.eioku_whisper_beam_select(
-            self._h, logits.ctypes.data, B, W, finish_count(W, patience), pre.ctypes.data, cap, plen.ctypes.data, sums.ctypes.data,
+        self._lib_mod.check(self._h.eioku_whisper_beam_select(
+            logits.ctypes.data, B, W, finish_count(W, patience), pre.ctypes.data, cap, plen.ctypes.data, sums.ctypes.data,
             fc.ctypes.data, src.ctypes.data, tok.ctypes.data, osum.ctypes.data, n_live.ctypes.data, fsrc.ctypes.data,
             fsum.ctypes.data, n_fin.ctypes.data, fc_out.ctypes.data, complete.ctypes.data), "eioku_whisper_beam_select")
         out = []
@@ -682,8 +658,8 @@ class WhisperTranscriber:
         tokens = np.zeros((B, G, max(n, 1)), dtype=np.int32)
         n_out, total = np.zeros((B, G), dtype=np.int32), np.zeros((B, G), dtype=np.float32)
         best, nsp = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)
-        self._lib_mod.check(self.lib.eioku_whisper_decode_prompted(
-            self._h, p.ctypes.data, P, int(sot_index), win.ctypes.data if win is not None else None, B, G, float(temperature),
+        self._lib_mod.check(self._h.eioku_whisper_decode_prompted(
+            p.ctypes.data, P, int(sot_index), win.ctypes.data if win is not None else None, B, G, float(temperature),
             sd.ctypes.data if sd is not None else None, n, int(sync_every or self.sync_every), tokens.ctypes.data,
             n_out.ctypes.data, total.ctypes.data, best.ctypes.data, nsp.ctypes.data), "eioku_whisper_decode_prompted")
         return {"tokens": tokens, "n": n_out, "sum_logprob": total, "best": best, "no_speech_prob": nsp}
@@ -701,8 +677,8 @@ class WhisperTranscriber:
         if win is not None and win.shape != (B,):
             raise ValueError("windows names one encoded window per row")
         out, tr, tr_ptrs = self._beam_outputs(B, W, Cn, n, trace)
-        self._lib_mod.check(self.lib.eioku_whisper_decode_beam_prompted(
-            self._h, p.ctypes.data, P, int(sot_index), win.ctypes.data if win is not None else None, B, W, Cn, n,
+        self._lib_mod.check(self._h.eioku_whisper_decode_beam_prompted(
+            p.ctypes.data, P, int(sot_index), win.ctypes.data if win is not None else None, B, W, Cn, n,
             int(sync_every or self.sync_every), *(a.ctypes.data for a in out.values()), *tr_ptrs), "eioku_whisper_decode_beam_prompted")
         return {**out, **tr}
 
@@ -715,9 +691,9 @@ class WhisperTranscriber:
         if len(prefixes) != B or sd.shape != (B,) or ix.shape != (B,):
             raise ValueError("prefixes, seeds and idx are per lane")
         tok, lp = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32)
-        self._lib_mod.check(self.lib.eioku_whisper_sample(self._h, logits.ctypes.data, B, pre.ctypes.data, cap, plen.ctypes.data,
-                                                          float(temperature), sd.ctypes.data, ix.ctypes.data, tok.ctypes.data,
-                                                          lp.ctypes.data), "eioku_whisper_sample")
+        self._lib_mod.check(self._h.eioku_whisper_sample(logits.ctypes.data, B, pre.ctypes.data, cap, plen.ctypes.data,
+                                                         float(temperature), sd.ctypes.data, ix.ctypes.data, tok.ctypes.data,
+                                                         lp.ctypes.data), "eioku_whisper_sample")
         return tok, lp
 
     def prefill_logits(self, ids, n_prefill: int | None = None) -> np.ndarray:
@@ -725,15 +701,15 @@ class WhisperTranscriber:
         prefill pass, the others position by position on the keys and values it left."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         out = np.empty(ids.shape + (self.dims["vocab"],), dtype=np.float32)
-        self._lib_mod.check(self.lib.eioku_whisper_prefill_logits(
-            self._h, ids.ctypes.data, ids.shape[1], ids.shape[0], int(ids.shape[1] if n_prefill is None else n_prefill),
+        self._lib_mod.check(self._h.eioku_whisper_prefill_logits(
+            ids.ctypes.data, ids.shape[1], ids.shape[0], int(ids.shape[1] if n_prefill is None else n_prefill),
             out.ctypes.data), "eioku_whisper_prefill_logits")
         return out
 
     def forced_logits(self, ids) -> np.ndarray:
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         out = np.empty(ids.shape + (self.dims["vocab"],), dtype=np.float32)
-        self._lib_mod.check(self.lib.eioku_whisper_forced_logits(self._h, ids.ctypes.data, ids.shape[1], ids.shape[0], out.ctypes.data),
+        self._lib_mod.check(self._h.eioku_whisper_forced_logits(ids.ctypes.data, ids.shape[1], ids.shape[0], out.ctypes.data),
                             "eioku_whisper_forced_logits")
         return out
 
@@ -743,14 +719,14 @@ class WhisperTranscriber:
         B = logits.shape[0]
         pre, cap, plen = self._pad_prefixes(prefixes, B)
         tok, lp, masked = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.float32), np.empty_like(logits)
-        self._lib_mod.check(self.lib.eioku_whisper_select(self._h, logits.ctypes.data, B, pre.ctypes.data, cap, plen.ctypes.data,
-                                                          tok.ctypes.data, lp.ctypes.data, masked.ctypes.data), "eioku_whisper_select")
+        self._lib_mod.check(self._h.eioku_whisper_select(logits.ctypes.data, B, pre.ctypes.data, cap, plen.ctypes.data,
+                                                         tok.ctypes.data, lp.ctypes.data, masked.ctypes.data), "eioku_whisper_select")
         return tok, lp, masked
 
     def set_alignment_heads(self, pairs) -> None:
         """K21: the (layer, head) pairs whose cross-attention is aligned; empty or None = the default (upper half)."""
         p = np.ascontiguousarray(pairs if pairs is not None else [], dtype=np.int32).reshape(-1, 2)
-        self._lib_mod.check(self.lib.eioku_whisper_set_alignment_heads(self._h, p.ctypes.data if len(p) else None, len(p)),
+        self._lib_mod.check(self._h.eioku_whisper_set_alignment_heads(p.ctypes.data if len(p) else None, len(p)),
                             "eioku_whisper_set_alignment_heads")
 
     def align(self, seqs, n_tok, sot_len: int, n_frames, windows=None, cost: bool = False) -> dict:
@@ -769,8 +745,8 @@ class WhisperTranscriber:
         N = max(T - int(sot_len) - 1, 1)
         jump, prob = np.full((R, N), -1, dtype=np.int32), np.zeros((R, N), dtype=np.float32)
         cst = np.zeros((R, N, max(int(nf.max()) // 2, 1)), dtype=np.float32) if cost else None
-        self._lib_mod.check(self.lib.eioku_whisper_align(
-            self._h, s.ctypes.data, T, nt.ctypes.data, int(sot_len), win.ctypes.data if win is not None else None, nf.ctypes.data, R,
+        self._lib_mod.check(self._h.eioku_whisper_align(
+            s.ctypes.data, T, nt.ctypes.data, int(sot_len), win.ctypes.data if win is not None else None, nf.ctypes.data, R,
             jump.ctypes.data, prob.ctypes.data, cst.ctypes.data if cost else None), "eioku_whisper_align")
         out = {"jump": jump, "prob": prob}
         if cost:
@@ -782,7 +758,7 @@ class WhisperTranscriber:
         a = np.ascontiguousarray(weights, dtype=np.float32)
         H, T, F = a.shape
         out = np.zeros((max(T - int(sot_len) - 1, 1), F), dtype=np.float32)
-        self._lib_mod.check(self.lib.eioku_whisper_align_cost(self._h, a.ctypes.data, H, T, F, int(sot_len), out.ctypes.data),
+        self._lib_mod.check(self._h.eioku_whisper_align_cost(a.ctypes.data, H, T, F, int(sot_len), out.ctypes.data),
                             "eioku_whisper_align_cost")
         return out
 
@@ -792,25 +768,21 @@ class WhisperTranscriber:
         N, F = c.shape
         jump, ti, fi = np.zeros(N, dtype=np.int32), np.zeros(N + F, dtype=np.int32), np.zeros(N + F, dtype=np.int32)
         n = C.c_int(0)
-        self._lib_mod.check(self.lib.eioku_whisper_dtw(self._h, c.ctypes.data, N, F, jump.ctypes.data, ti.ctypes.data, fi.ctypes.data,
-                                                       C.byref(n)), "eioku_whisper_dtw")
+        self._lib_mod.check(self._h.eioku_whisper_dtw(c.ctypes.data, N, F, jump.ctypes.data, ti.ctypes.data, fi.ctypes.data,
+                                                      C.byref(n)), "eioku_whisper_dtw")
         return {"jump": jump, "text_idx": ti[:n.value].copy(), "time_idx": fi[:n.value].copy()}
 
     def last_align_ms(self) -> tuple[float, float, float]:
         """Device milliseconds of the last :meth:`align`: the pass with the probabilities, the cost kernels, the DTW."""
-        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
-        self._lib_mod.check(self.lib.eioku_whisper_last_align_ms(self._h, C.byref(a), C.byref(b), C.byref(c)), "eioku_whisper_last_align_ms")
-        return a.value, b.value, c.value
+        return self._h.doubles("last_align_ms", 3)
 
     def last_launches(self) -> tuple[int, int]:
         a, b = C.c_int(0), C.c_int(0)
-        self._lib_mod.check(self.lib.eioku_whisper_last_launches(self._h, C.byref(a), C.byref(b)), "eioku_whisper_last_launches")
+        self._lib_mod.check(self._h.eioku_whisper_last_launches(C.byref(a), C.byref(b)), "eioku_whisper_last_launches")
         return a.value, b.value
 
     def last_flops(self) -> float:
-        f = C.c_double(0)
-        self._lib_mod.check(self.lib.eioku_whisper_last_flops(self._h, C.byref(f)), "eioku_whisper_last_flops")
-        return f.value
+        return self._h.doubles("last_flops")[0]
 
     # -- the host loop
     def _language_token(self, language: str | None):

@@ -19,6 +19,8 @@ from pathlib import Path
 
 import numpy as np
 
+from ._handle import Handle
+
 SAMPLE_RATE = 16000
 WINDOW = 512                 # new samples per chunk (32 ms)
 CONTEXT = 64                 # samples carried over from the previous chunk
@@ -266,38 +268,9 @@ class SileroVad:
     memory: longer files run slab by slab with the context samples and the LSTM state carried on the device."""
 
     def __init__(self, weights, *, slab_chunks: int = DEFAULT_SLAB_CHUNKS):
-        from . import _lib
-
-        self._lib_mod = _lib
-        self.lib = _lib.load()
-        _lib.init()
         self.slab_chunks = int(slab_chunks)
-        handle = C.c_void_p()
-        _lib.check(self.lib.eioku_vad_create(self.slab_chunks, C.byref(handle)), "eioku_vad_create")
-        self._h = handle
-        try:
-            self._load(weights)
-        except Exception:
-            self.close()
-            raise
-
-    def _load(self, weights) -> None:
-        lib, check = self.lib, self._lib_mod.check
-        name = C.create_string_buffer(256)
-        rows, cols = C.c_int(0), C.c_int(0)
-        for i in range(lib.eioku_vad_num_tensors(self._h)):
-            check(lib.eioku_vad_tensor_info(self._h, i, name, 256, C.byref(rows), C.byref(cols)), "eioku_vad_tensor_info")
-            n = name.value.decode()
-            if callable(weights):
-                arr = weights(n, rows.value, cols.value)
-            elif n in weights:
-                arr = weights[n]
-            else:
-                raise KeyError(f"checkpoint has no tensor {n}")
-            arr = np.ascontiguousarray(np.asarray(arr, dtype=np.float32)).reshape(-1)
-            if arr.size != rows.value * cols.value:
-                raise ValueError(f"{n}: expected {rows.value * cols.value} elements, checkpoint has {arr.size}")
-            check(lib.eioku_vad_set_tensor(self._h, i, arr.ctypes.data, arr.size), f"eioku_vad_set_tensor({n})")
+        self._h = Handle("vad", self.slab_chunks)
+        self._h.or_close(self._h.set_tensors, weights)
 
     @classmethod
     def from_cache(cls, cache_dir: str | Path, seed: int | None = None, **kw):
@@ -313,27 +286,17 @@ class SileroVad:
         return cls(read_safetensors(path), **kw)
 
     def close(self) -> None:
-        if getattr(self, "_h", None):
-            self.lib.eioku_vad_destroy(self._h)
-            self._h = None
-
-    def __del__(self):  # noqa: D105
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        self._h.close()
 
     def speech_probs(self, samples: np.ndarray) -> np.ndarray:
         samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
         out = np.empty(num_chunks(samples.size), dtype=np.float32)
         n = C.c_longlong(0)
-        self._lib_mod.check(self.lib.eioku_vad_probs(self._h, samples.ctypes.data, samples.size, out.ctypes.data, out.size,
-                                                     C.byref(n)), "eioku_vad_probs")
+        self._h.check(self._h.eioku_vad_probs(samples.ctypes.data, samples.size, out.ctypes.data, out.size,
+                                              C.byref(n)), "eioku_vad_probs")
         assert n.value == out.size
         return out
 
     def last_ms(self) -> tuple[float, float]:
         """Kernel milliseconds of the last ``speech_probs``: (batched stages, recurrence)."""
-        a, b = C.c_double(0), C.c_double(0)
-        self._lib_mod.check(self.lib.eioku_vad_last_ms(self._h, C.byref(a), C.byref(b)), "eioku_vad_last_ms")
-        return a.value, b.value
+        return self._h.doubles("last_ms", 2)

@@ -2,6 +2,8 @@
 (tests/ocr_stage_oracle.py) through the stage entry points - bit for bit where the arithmetic is exact - and the batch
 edges of both networks (width groups of more than 64 crops, the MAX_ROWS split, CRAFT's chunks of 8 frames) through
 the public API."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -210,8 +212,8 @@ def test_crnn_tail_against_float64_torch(tail, name):
 
 
 def test_crnn_tail_needs_no_vgg_weights_but_needs_its_own(gpu):
-    lib, r = _lib.load(), ocr.C.c_void_p()
-    _lib.check(lib.eioku_crnn_create(97, ocr.C.byref(r)), "eioku_crnn_create")
+    lib, r = _lib.load(), C.c_void_p()
+    _lib.check(lib.eioku_crnn_create(97, C.byref(r)), "eioku_crnn_create")
     seq, ln, ign = np.zeros((1, 256), np.float32), np.ones(1, np.int32), np.zeros(97, np.uint8)
     idx, prob = np.zeros(1, np.int32), np.zeros(1, np.float32)
     rc = lib.eioku_crnn_tail(r, seq.ctypes.data, ln.ctypes.data, 1, ign.ctypes.data, idx.ctypes.data, prob.ctypes.data, None, None)

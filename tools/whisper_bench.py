@@ -197,17 +197,12 @@ def main() -> None:
 
             weights = {}
             make = seeded_weights(dims, 1)
-            import ctypes as C
-
-            nm, rows, cols = C.create_string_buffer(256), C.c_int(0), C.c_int(0)
-            for i in range(t.lib.eioku_whisper_num_tensors(t._h)):
-                t.lib.eioku_whisper_tensor_info(t._h, i, nm, 256, C.byref(rows), C.byref(cols))
-                n = nm.value.decode()
-                arr = torch.from_numpy(make(n, rows.value, cols.value).copy())
+            for n, rows, cols in t._h.tensors():
+                arr = torch.from_numpy(make(n, rows, cols).copy())
                 if "conv" in n and n.endswith(".weight"):
-                    arr = arr.view(rows.value, cols.value // 3, 3)
+                    arr = arr.view(rows, cols // 3, 3)
                 elif not (n.endswith(".bias") or "layer_norm" in n):
-                    arr = arr.view(rows.value, cols.value)
+                    arr = arr.view(rows, cols)
                 weights[n] = arr
             oracle = wo.Oracle(dims, weights, fp16=False)
             mel = wo.log_mel(audio, 0, 3000, 80)[None]
