@@ -15,6 +15,7 @@
 //
 // The coarse assignment / probe selection reuses K9 (k_flat_l2 with k = 1 / nprobe).
 #include "common.h"
+#include "select.h"
 
 #include <cfloat>
 #include <cstdlib>
@@ -116,38 +117,6 @@ __global__ __launch_bounds__(256) void k_ivf_scatter(const long long* __restrict
 }
 
 // ---- scan -------------------------------------------------------------------------------------------
-template <int K>
-struct SmallTop {
-  float v[K];
-  long long id[K];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int p = 0; p < K; ++p) {
-      v[p] = FLT_MAX;
-      id[p] = -1;
-    }
-  }
-  __device__ __forceinline__ bool better(float x, long long i, float y, long long j) const {
-    return x < y || (x == y && (j < 0 || i < j));
-  }
-  __device__ __forceinline__ void insert(float x, long long i) {
-    if (!better(x, i, v[K - 1], id[K - 1])) return;
-#pragma unroll
-    for (int p = K - 1; p > 0; --p) {
-      const bool shift = better(x, i, v[p - 1], id[p - 1]);
-      const bool here = !shift && better(x, i, v[p], id[p]);
-      const float nv = shift ? v[p - 1] : (here ? x : v[p]);
-      const long long ni = shift ? id[p - 1] : (here ? i : id[p]);
-      v[p] = nv;
-      id[p] = ni;
-    }
-    if (better(x, i, v[0], id[0])) {
-      v[0] = x;
-      id[0] = i;
-    }
-  }
-};
-
 // FAISS' precomputed-table decomposition of the ADC look-up table (IndexIVFPQ::use_precomputed_table = 1):
 //   || (q - c_l)_j - p_jc ||^2 = || (q - c_l)_j ||^2  +  ( ||p_jc||^2 + 2 c_l,j . p_jc )  +  ( -2 q_j . p_jc )
 // the middle term depends on (list, j, c) only - one table per index, built once - the last on (query, j, c) only -
@@ -592,19 +561,6 @@ int eioku_ivfpq_scan_tables(const float* q_dev, int nq, int d, int m, const long
 // =====================================================================================================================
 namespace {
 
-typedef unsigned u32x4k __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2k __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
-
-__device__ __forceinline__ unsigned bf16_rne_bits(float f) {  // finite inputs
-  unsigned u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-
 // pq [m][256][8] fp32 -> pqh [m * 256] 16-byte units of 8 bf16 (round to nearest)
 __global__ __launch_bounds__(256) void k_pq_bf16(const float* __restrict__ pq, int nent, u32x4k* __restrict__ pqh) {
   const int e = blockIdx.x * 256 + threadIdx.x;
@@ -974,27 +930,6 @@ __global__ __launch_bounds__(NW * 64) void k_lscan(LScanArgs a) {
   if (tid == 0) a.wl_cnt[blockIdx.x] = *s_cnt;
 }
 
-// workgroup lists -> per-query candidate lists
-__global__ __launch_bounds__(256) void k_lbin(const unsigned* __restrict__ wl, const int* __restrict__ wl_cnt, int wl_cap,
-                                              const int* __restrict__ lq_q, int* __restrict__ cand, int* __restrict__ cnt,
-                                              int cap, int* __restrict__ overflow) {
-  int c = wl_cnt[blockIdx.x];
-  if (c > wl_cap) {
-    if (threadIdx.x == 0) atomicOr(overflow, 1);
-    c = wl_cap;
-  }
-  const unsigned* list = wl + (size_t)blockIdx.x * wl_cap * 2;
-  for (int i = threadIdx.x; i < c; i += 256) {
-    const unsigned slot = list[2 * i], row = list[2 * i + 1];
-    const int qi = lq_q[slot];
-    const int pos = atomicAdd(cnt + qi, 1);
-    if (pos < cap) {
-      cand[((size_t)qi * cap + pos) * 2] = (int)slot;
-      cand[((size_t)qi * cap + pos) * 2 + 1] = (int)row;
-    }
-  }
-}
-
 // one workgroup per query: the candidates' ADC distances with the query-major kernel's arithmetic
 // (sum_j (T2[l][j][c] + T3[q][j][c]) in j order, + t1), then the k best by (distance, id).  Candidates are scored in
 // chunks of kRChunk; the best k so far ride along as extra entries of the next chunk, so the list a query may hold is
@@ -1013,7 +948,7 @@ __global__ __launch_bounds__(256) void k_lrerank(const int* __restrict__ cand, c
   float* s_d = reinterpret_cast<float*>(s_id + kRChunk + 32);   // [kRChunk + 32]
   __shared__ float s_bv[4], s_kv[32];
   __shared__ long long s_bi[4], s_ki[32];
-  const int qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qi = blockIdx.x, tid = threadIdx.x;
   int c = cnt[qi];
   if (tid == 0) {
     atomicMax(overflow + 2, c);
@@ -1067,41 +1002,11 @@ __global__ __launch_bounds__(256) void k_lrerank(const int* __restrict__ cand, c
     long long li = -1;
     int found = 0;
     for (int r = 0; r < k; ++r) {
-      float bv = FLT_MAX;
-      long long bi = 0x7FFFFFFFFFFFFFFFll;
-      for (int j = tid; j < tot; j += 256) {
-        const float v = s_d[j];
-        const long long i = s_id[j];
-        const bool after = v > lv || (v == lv && i > li);
-        if (after && (v < bv || (v == bv && i < bi))) {
-          bv = v;
-          bi = i;
-        }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const long long oi = __shfl_xor(bi, o, 64);
-        if (ov < bv || (ov == bv && oi < bi)) {
-          bv = ov;
-          bi = oi;
-        }
-      }
-      if (lane == 0) {
-        s_bv[wave] = bv;
-        s_bi[wave] = bi;
-      }
-      __syncthreads();
-      bv = s_bv[0];
-      bi = s_bi[0];
-#pragma unroll
-      for (int w = 1; w < 4; ++w)
-        if (s_bv[w] < bv || (s_bv[w] == bv && s_bi[w] < bi)) {
-          bv = s_bv[w];
-          bi = s_bi[w];
-        }
-      __syncthreads();
-      const bool none = bi == 0x7FFFFFFFFFFFFFFFll;
+      float bv;
+      long long bi;
+      next_after(lv, li, tid, tot, 256, s_d, s_id, bv, bi);
+      block_argmin4(bv, bi, s_bv, s_bi);
+      const bool none = bi == eioku::none<long long>();
       if (tid == 0) {
         if (last) {
           Dout[(size_t)qi * k + r] = none ? FLT_MAX : bv;
@@ -1112,8 +1017,7 @@ __global__ __launch_bounds__(256) void k_lrerank(const int* __restrict__ cand, c
         }
       }
       if (!none) found = r + 1;
-      lv = none ? FLT_MAX : bv;
-      li = none ? 0x7FFFFFFFFFFFFFFFll : bi;
+      advance(lv, li, bv, bi);
     }
     kept = found;
     __syncthreads();
@@ -1131,35 +1035,21 @@ __global__ __launch_bounds__(64) void k_probe_merge(const float* __restrict__ pd
   float lv = -__builtin_inff();
   long long li = -1;
   for (int r = 0; r < k; ++r) {
-    float bv = FLT_MAX;
-    long long bi = 0x7FFFFFFFFFFFFFFFll;
-    for (int e = lane; e < n; e += 64) {
+    float bv;
+    long long bi;
+    next_after(lv, li, lane, n, 64, [=](int e, float& v, long long& i) {
       const int pr = e / K, x = e - pr * K;
-      const float v = pd[((size_t)pr * nq + qi) * K + x];
-      const long long i = pi[((size_t)pr * nq + qi) * K + x];
-      if (i < 0) continue;
-      const bool after = v > lv || (v == lv && i > li);
-      if (after && (v < bv || (v == bv && i < bi))) {
-        bv = v;
-        bi = i;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const long long oi = __shfl_xor(bi, o, 64);
-      if (ov < bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    const bool none = bi == 0x7FFFFFFFFFFFFFFFll;
+      v = pd[((size_t)pr * nq + qi) * K + x];
+      i = pi[((size_t)pr * nq + qi) * K + x];
+      return i >= 0;
+    }, bv, bi);
+    wave_argmin(bv, bi);
+    const bool none = bi == eioku::none<long long>();
     if (lane == 0) {
       Dout[(size_t)qi * k + r] = none ? FLT_MAX : bv;
       Iout[(size_t)qi * k + r] = none ? -1 : bi;
     }
-    lv = none ? FLT_MAX : bv;
-    li = none ? 0x7FFFFFFFFFFFFFFFll : bi;
+    advance(lv, li, bv, bi);
   }
 }
 
@@ -1352,7 +1242,8 @@ int eioku_ivfpq_search_lists(const float* q_dev, int nq, int d, int m, const lon
   }
   prof_stop(EIOKU_PROF_IVFPQ, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_lbin, dim3((unsigned)w.grid), dim3(256), 0, stream, wl, wl_cnt, w.wl_cap, lq_q, cand, cnt, cap, overflow);
+  hipLaunchKernelGGL((k_bin_pairs<true>), dim3((unsigned)w.grid), dim3(256), 0, stream, wl, wl_cnt, w.wl_cap, lq_q, cand,
+                     cnt, cap, overflow);
   {
     static size_t attr_lds = 0;
     if (rr_lds > attr_lds) {

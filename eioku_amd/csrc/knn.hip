@@ -16,6 +16,7 @@
 //
 // Algorithmic bytes: N*d*4 per 32-query pass; FLOPs 2*nq*N*d.
 #include "common.h"
+#include "select.h"
 
 #include <cstdlib>
 
@@ -24,8 +25,6 @@
 using namespace eioku;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kQT = 32;        // queries per wave tile (MFMA N)
 constexpr int kRT = 32;        // database rows per MFMA tile (MFMA M)
@@ -345,10 +344,6 @@ __global__ __launch_bounds__(256, 1) void k_flat_l2(KnnArgs a) {
 // rows are split by the staging threads on their way into LDS (hi and lo planes, 16-byte units of 8 dims).
 // Norms stay the fp32 ones.
 // ---------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4k __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2k __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ void split_bf16x2(float a, float b, unsigned& hi, unsigned& lo) {
   const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
   hi = (ua >> 16) | (ub & 0xFFFF0000u);  // truncation: the remainder below is then exact in fp32
@@ -574,11 +569,8 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* pd, const int* p
   if (gate && *gate == 0) return;
   const int q = blockIdx.x, lane = threadIdx.x;
   // partial layout: [qtile][list][kQT][kin] when qstride_lists > 0 (search partials), else [list][nq][kin]
-  TopK<K> top;
+  SmallTop<K> top;
   top.init();
-  long long gid[K];
-#pragma unroll
-  for (int p = 0; p < K; ++p) gid[p] = -1;
   for (int l = lane; l < L; l += 64) {
     size_t base;
     if (qstride_lists > 0) base = ((((size_t)(q / kQT) * L + l) * kQT) + (q % kQT)) * kin;
@@ -592,41 +584,17 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* pd, const int* p
         id = li < 0 ? -1 : (long long)li + (list_base ? list_base[l] : (long long)l * rows_per_list);
       }
       if (id < 0) break;  // lists are sorted: the rest is padding
-      // TopK keeps 31-bit ids for the tie rule; carry the 64-bit id alongside via the slot it lands in
-      const bool better_tail = (v < top.v[K - 1]) || (v == top.v[K - 1] && id < gid[K - 1]) || gid[K - 1] < 0;
-      if (!better_tail) break;  // ascending list: nothing later can enter either
-#pragma unroll
-      for (int s = K - 1; s > 0; --s) {
-        const bool shift = gid[s - 1] < 0 || (top.v[s - 1] > v) || (top.v[s - 1] == v && gid[s - 1] > id);
-        const bool here = !shift && (gid[s] < 0 || (top.v[s] > v) || (top.v[s] == v && gid[s] > id));
-        const float nv = shift ? top.v[s - 1] : (here ? v : top.v[s]);
-        const long long ni = shift ? gid[s - 1] : (here ? id : gid[s]);
-        top.v[s] = nv;
-        gid[s] = ni;
-      }
-      if (gid[0] < 0 || (top.v[0] > v) || (top.v[0] == v && gid[0] > id)) {
-        top.v[0] = v;
-        gid[0] = id;
-      }
+      if (!top.better(v, id, top.v[K - 1], top.id[K - 1])) break;  // ascending list: nothing later can enter either
+      top.insert(v, id);
     }
   }
   // K rounds of wave argmin over the list heads
   for (int r = 0; r < k; ++r) {
-    float bv = gid[0] < 0 ? FLT_MAX : top.v[0];
-    long long bi = gid[0] < 0 ? 0x7FFFFFFFFFFFFFFFll : gid[0];
+    float bv = top.id[0] < 0 ? FLT_MAX : top.v[0];
+    long long bi = top.id[0] < 0 ? none<long long>() : top.id[0];
     int bl = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const long long oi = __shfl_xor(bi, off, 64);
-      const int ol = __shfl_xor(bl, off, 64);
-      if (ov < bv || (ov == bv && oi < bi) || (ov == bv && oi == bi && ol < bl)) {
-        bv = ov;
-        bi = oi;
-        bl = ol;
-      }
-    }
-    const bool found = bi != 0x7FFFFFFFFFFFFFFFll;
+    wave_argmin(bv, bi, bl);
+    const bool found = bi != none<long long>();
     if (lane == 0) {
       D[(size_t)q * k + r] = found ? bv : FLT_MAX;
       I[(size_t)q * k + r] = found ? bi : -1;
@@ -635,14 +603,13 @@ __global__ __launch_bounds__(64) void k_topk_merge(const float* pd, const int* p
 #pragma unroll
       for (int s = 0; s < K - 1; ++s) {
         top.v[s] = top.v[s + 1];
-        gid[s] = gid[s + 1];
+        top.id[s] = top.id[s + 1];
       }
       top.v[K - 1] = FLT_MAX;
-      gid[K - 1] = -1;
+      top.id[K - 1] = -1;
     }
   }
 }
-
 
 // The same merge for L <= 64 SORTED lists of 32-bit ids (every search partial is one): a lane owns one list and only ever
 // looks at its head, so nothing is inserted - k rounds of wave argmin over the heads, the winner advances (its next
@@ -671,20 +638,10 @@ __global__ __launch_bounds__(64) void k_topk_merge_heads(const float* __restrict
   }
   for (int r = 0; r < k; ++r) {
     float bv = ci < 0 ? FLT_MAX : cv;
-    long long bi = ci < 0 ? 0x7FFFFFFFFFFFFFFFll : (long long)ci + idb;
+    long long bi = ci < 0 ? none<long long>() : (long long)ci + idb;
     int bl = lane;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const long long oi = __shfl_xor(bi, off, 64);
-      const int ol = __shfl_xor(bl, off, 64);
-      if (ov < bv || (ov == bv && oi < bi) || (ov == bv && oi == bi && ol < bl)) {
-        bv = ov;
-        bi = oi;
-        bl = ol;
-      }
-    }
-    const bool found = bi != 0x7FFFFFFFFFFFFFFFll;
+    wave_argmin(bv, bi, bl);
+    const bool found = bi != none<long long>();
     if (lane == 0) {
       D[(size_t)q * k + r] = found ? bv : FLT_MAX;
       I[(size_t)q * k + r] = found ? bi : -1;
@@ -716,7 +673,7 @@ __global__ __launch_bounds__(64) void k_topk_merge_heads(const float* __restrict
 // A row-stationary wave meets every query, so per-query top-k lists cannot live in its registers.  Instead a
 // per-query upper bound tau_q on the k-th distance comes from an exact search of a strided SAMPLE of the rows
 // (the k-th best of any subset bounds the k-th best of the whole), the scan keeps every (query, row) whose
-// distance may be <= tau_q (expected k * N / S pairs per query), k_scan_bin sorts them into per-query lists and
+// distance may be <= tau_q (expected k * N / S pairs per query), k_bin_pairs sorts them into per-query lists and
 // k_scan_select re-computes their distances in fp32 from the fp32 rows and picks the k best.  A list that
 // overflows raises a device flag and the launch of the register-tile kernels that follows - gated on that flag -
 // recomputes the search (tested by forcing tiny lists).
@@ -733,15 +690,6 @@ __global__ __launch_bounds__(64) void k_topk_merge_heads(const float* __restrict
 // at +1.2, the query DMA at +1.15 and the LDS fragment reads at +0.7 (they add almost linearly: the 12 waves of a
 // workgroup run their phases in lockstep behind the one barrier per query tile).
 // ---------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
-
-__device__ __forceinline__ unsigned bf16_rne_bits(float f) {  // finite inputs
-  unsigned u = __float_as_uint(f);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-
 // rows [n][D] fp32 -> fragment-tiled bf16 plane: unit ((tile * NS + s) * 2 + half) * 32 + r holds dims
 // 16 s + 8 half + [0, 8) of row 32 tile + r (the 32x32x16 A / B operand of lane 32 half + r), rounded to nearest.
 // Optional per-row half norms (0.5 |x|^2, +inf for rows >= n) and per-tile max |x| (over valid rows).
@@ -798,7 +746,7 @@ struct ScanArgs {
   long long tstride;     // 1: every tile; > 1: the strided subset that tightens the bound first (scan_search)
   int nq, nqt;
   // candidates leave the scan as (query, row) pairs in a list private to the workgroup (an LDS counter hands out the
-  // slots: no global atomic, nothing to wait for); k_scan_bin sorts them into the per-query lists afterwards
+  // slots: no global atomic, nothing to wait for); k_bin_pairs sorts them into the per-query lists afterwards
   unsigned* wl;          // [gridDim.x][wl_cap][2]
   int* wl_cnt;           // [gridDim.x]
   int wl_cap;
@@ -1023,23 +971,6 @@ __global__ __launch_bounds__(NW * 64) void k_l2_scan(ScanArgs a) {
   if (tid == 0) a.wl_cnt[blockIdx.x] = *s_cnt;
 }
 
-// (query, row) pairs of the scan's workgroup lists -> per-query candidate lists.  One workgroup per list.
-__global__ __launch_bounds__(256) void k_scan_bin(const unsigned* __restrict__ wl, const int* __restrict__ wl_cnt, int wl_cap,
-                                                  int* __restrict__ cand_i, int* __restrict__ cnt, int cap,
-                                                  int* __restrict__ overflow) {
-  int c = wl_cnt[blockIdx.x];
-  if (c > wl_cap) {
-    if (threadIdx.x == 0) atomicOr(overflow, 1);
-    c = wl_cap;
-  }
-  const unsigned* list = wl + (size_t)blockIdx.x * wl_cap * 2;
-  for (int i = threadIdx.x; i < c; i += 256) {
-    const int qi = (int)list[2 * i], row = (int)list[2 * i + 1];
-    const int pos = atomicAdd(cnt + qi, 1);
-    if (pos < cap) cand_i[(size_t)qi * cap + pos] = row;
-  }
-}
-
 // One workgroup per query: fp32 distances of its candidates, sum (q_i - x_i)^2 from the fp32 rows (no
 // |q|^2 + |x|^2 - 2 q.x cancellation: an exact copy of the query scores exactly 0), then the k best by (dist, id).
 template <int D>
@@ -1052,7 +983,7 @@ __global__ __launch_bounds__(256) void k_scan_select(const float* __restrict__ d
   int* si = reinterpret_cast<int*>(sd + cap);      // [cap]
   __shared__ float s_bv[4];
   __shared__ int s_bi[4];
-  const int qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   int c = cnt[qi];
   if (c > cap) {
     if (tid == 0) atomicOr(overflow, 1);
@@ -1098,47 +1029,15 @@ __global__ __launch_bounds__(256) void k_scan_select(const float* __restrict__ d
   float lv = -1.f;
   int li = -1;  // last emitted (dist, id): distances are >= 0
   for (int r = 0; r < k; ++r) {
-    float bv = FLT_MAX;
-    int bi = 0x7FFFFFFF;
-    for (int j = tid; j < c; j += 256) {
-      const float v = sd[j];
-      const int i = si[j];
-      const bool after = v > lv || (v == lv && i > li);
-      if (after && (v < bv || (v == bv && i < bi))) {
-        bv = v;
-        bi = i;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (ov < bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      s_bv[wave] = bv;
-      s_bi[wave] = bi;
-    }
-    __syncthreads();
-    bv = s_bv[0];
-    bi = s_bi[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (s_bv[w] < bv || (s_bv[w] == bv && s_bi[w] < bi)) {
-        bv = s_bv[w];
-        bi = s_bi[w];
-      }
-    __syncthreads();
+    float bv;
+    int bi;
+    next_after(lv, li, tid, c, 256, sd, si, bv, bi);
+    block_argmin4(bv, bi, s_bv, s_bi);
     if (tid == 0) {
-      Dout[(size_t)qi * k + r] = bi == 0x7FFFFFFF ? FLT_MAX : bv;
-      Iout[(size_t)qi * k + r] = bi == 0x7FFFFFFF ? -1 : (long long)bi;
+      Dout[(size_t)qi * k + r] = bi == none<int>() ? FLT_MAX : bv;
+      Iout[(size_t)qi * k + r] = bi == none<int>() ? -1 : (long long)bi;
     }
-    lv = bv;
-    li = bi;
-    if (bi == 0x7FFFFFFF) lv = FLT_MAX;  // exhausted: the remaining rounds emit padding
+    advance(lv, li, bv, bi);
   }
 }
 
@@ -1734,8 +1633,8 @@ int scan_search(eioku_index* ix, const float* dq, int nq, int k, float* dD, long
     }
     if (prof) prof_stop(EIOKU_PROF_KNN, stream);
     if (r) return r;
-    hipLaunchKernelGGL(k_scan_bin, dim3((unsigned)sgrid), dim3(256), 0, stream, ix->wl, ix->wl_cnt, a.wl_cap, ix->cand_i,
-                       ix->cnt, cap, oflow);
+    hipLaunchKernelGGL((k_bin_pairs<false>), dim3((unsigned)sgrid), dim3(256), 0, stream, ix->wl, ix->wl_cnt, a.wl_cap,
+                       (const int*)nullptr, ix->cand_i, ix->cnt, cap, oflow);
     EIOKU_LAUNCH_CHECK();
     switch (d) {
       case 128: return launch_select<128>(ix, dq, nq, cap, k, outD, outI, oflow, stream);

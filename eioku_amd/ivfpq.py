@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from ._buffers import current_stream, ptr
-from .search import IndexFlatL2, RowSelector
+from .search import IndexFlatL2, RowSelector, empty_results, selector_words
 
 NITER = 25
 MAX_K = 32  # results per query of one search (the partial lists of the scans are 16 or 32 wide)
@@ -219,14 +219,7 @@ class IndexIVFPQ:
             packed = self._allreduce(packed.contiguous(), group)  # (m, 256, dsub + 1): one collective for all sub-quantisers
             pq = torch.stack([ops.finalize(packed[j], pq[j].contiguous()) for j in range(self.m)]).contiguous()
         self.pq = pq
-        self._list_tables = None
-        self._aux = None
-        if self._lib is not None:
-            if self._quantizer is not None:
-                self._quantizer.close()
-            self._quantizer = IndexFlatL2(self.d)
-            self._quantizer.attach(self.coarse)
-        self.is_trained = True
+        self._codebooks_changed()
 
     def set_codebooks(self, coarse, pq) -> None:
         """Install trained quantisers (e.g. broadcast from rank 0): coarse (nlist,d), pq (m,256,dsub)."""
@@ -234,12 +227,22 @@ class IndexIVFPQ:
 
         self.coarse = torch.as_tensor(coarse, dtype=torch.float32).to(self.device).contiguous()
         self.pq = torch.as_tensor(pq, dtype=torch.float32).to(self.device).contiguous()
-        self._list_tables = None
+        self._codebooks_changed()
+
+    def _invalidate(self, tables: bool) -> None:
+        """New rows outdate the pack, new codebooks (``tables``) the per-list tables; both outdate the pack's aux planes."""
         self._aux = None
-        if self._quantizer is not None:
-            self._quantizer.close()
-        self._quantizer = IndexFlatL2(self.d)
-        self._quantizer.attach(self.coarse)
+        if tables:
+            self._list_tables = None
+        else:
+            self._packed = None
+
+    def _codebooks_changed(self) -> None:
+        self._invalidate(tables=True)
+        if self._lib is not None:  # the coarse quantiser: a flat index over the new centroids (HIP ops only)
+            self.close()
+            self._quantizer = IndexFlatL2(self.d)
+            self._quantizer.attach(self.coarse)
         self.is_trained = True
 
     # ---- add / search --------------------------------------------------------------------------------
@@ -259,8 +262,7 @@ class IndexIVFPQ:
                                              None, current_stream(x)), "eioku_pq_assign(encode)")
         self._pending.append((lst, codes, self.ntotal))
         self.ntotal += n
-        self._packed = None
-        self._aux = None
+        self._invalidate(tables=False)
         if self._live is not None:  # fresh ids are live; the bits beyond ntotal in the last word are kept set
             grow = (self.ntotal + 31) // 32 - int(self._live.numel())
             if grow > 0:
@@ -326,8 +328,7 @@ class IndexIVFPQ:
         selector, else ``ntotal``."""
         import torch
 
-        # the selector forms and the ValueError texts of the flat index
-        words, _, mem = IndexFlatL2._selector(self, sel, None)
+        words, _, mem = selector_words(sel, self.ntotal)  # the selector forms and the ValueError texts of the flat index
         if words is None or self.ntotal == 0:
             return (self._live, self.ntotal) if self._live is not None and self.ntotal else (None, 0)
         cap = self.ntotal
@@ -375,15 +376,11 @@ class IndexIVFPQ:
         nq = q.shape[0]
         nprobe = min(self.nprobe, self.nlist)
         keep, cap = self._keep(sel)
-        offsets, sizes, list_codes, list_ids = self._pack()
+        pack = self._pack()
         _, probes = self._quantizer.search_many(q, nprobe)  # nprobe > 32: chained rounds of 32 (search_after)
         probes = probes.contiguous()
-        K = 16 if k <= 16 else 32
         lists = (self.scan_mode == "lists" and self.use_precomputed_table and self.dsub == 8
                  and self.d in (64, 128, 256, 384) and self.ntotal > 0)
-        if not lists:
-            pd = torch.empty((nprobe, nq, K), dtype=torch.float32, device=self.device)
-            pi = torch.empty((nprobe, nq, K), dtype=torch.int64, device=self.device)
         if self.use_precomputed_table:
             # FAISS' decomposition: the per-list half of every look-up table is part of the index (nlist x m x 1 KB, built
             # on the first search after the codebooks change), the per-query half is built once per search
@@ -399,25 +396,29 @@ class IndexIVFPQ:
             self.last_view = None
         else:  # the scans below run unchanged on the eligible rows of the probed lists
             if lists:
-                hx = self._lists_aux(q, offsets, sizes, list_codes)[1]
-            (offsets, sizes, list_codes, list_ids), hx = self._select_view(q, probes, nprobe, (offsets, sizes, list_codes, list_ids),
-                                                                           keep, cap, hx)
+                hx = self._lists_aux(q, *pack[:3])[1]
+            pack, hx = self._select_view(q, probes, nprobe, pack, keep, cap, hx)
+        head, tail = self._scan_args(q, probes, nprobe, pack)
+        if lists:
+            return self._search_lists(q, k, nprobe, head, tail, pack, qt, hx)
+        K = 16 if k <= 16 else 32
+        pd = torch.empty((nprobe, nq, K), dtype=torch.float32, device=self.device)
+        pi = torch.empty((nprobe, nq, K), dtype=torch.int64, device=self.device)
         if self.use_precomputed_table:
-            if lists:
-                return self._search_lists(q, k, probes, nprobe, qt, offsets, sizes, list_codes, list_ids, hx)
-            _lib.check(self._lib.eioku_ivfpq_scan_tables(ptr(q), nq, self.d, self.m, ptr(probes), nprobe, ptr(self.coarse),
-                                                         ptr(self.pq), ptr(offsets), ptr(sizes), ptr(list_codes), ptr(list_ids),
-                                                         ptr(self._list_tables), ptr(qt), k, ptr(pd), ptr(pi),
+            _lib.check(self._lib.eioku_ivfpq_scan_tables(*head, *tail, ptr(self._list_tables), ptr(qt), k, ptr(pd), ptr(pi),
                                                          current_stream(q)), "eioku_ivfpq_scan_tables")
         else:
-            _lib.check(self._lib.eioku_ivfpq_scan(ptr(q), nq, self.d, self.m, ptr(probes), nprobe, ptr(self.coarse), ptr(self.pq),
-                                                  ptr(offsets), ptr(sizes), ptr(list_codes), ptr(list_ids), k, ptr(pd), ptr(pi),
-                                                  current_stream(q)), "eioku_ivfpq_scan")
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+            _lib.check(self._lib.eioku_ivfpq_scan(*head, *tail, k, ptr(pd), ptr(pi), current_stream(q)), "eioku_ivfpq_scan")
+        D, I = empty_results(q, nq, k)
         _lib.check(self._lib.eioku_topk_merge_ex(ptr(pd), ptr(pi), nprobe, nq, K, k, ptr(D), ptr(I), current_stream(q)),
                    "eioku_topk_merge_ex")
         return D, I
+
+    def _scan_args(self, q, probes, nprobe, pack):
+        """The arguments every scan entry point takes, in their order: (q, nq, d, m, probes, nprobe) and (coarse, pq, the
+        four tensors of the pack); ``eioku_ivfpq_search_lists`` puts nlist and ntotal between the two."""
+        return ((ptr(q), int(q.shape[0]), self.d, self.m, ptr(probes), nprobe),
+                (ptr(self.coarse), ptr(self.pq), *(ptr(t) for t in pack)))
 
     def search_many(self, q, k: int, sel=None):
         """:meth:`search` behind the protocol ``VectorStore`` speaks (``IndexFlatL2.search_many``): numpy queries give
@@ -457,14 +458,14 @@ class IndexIVFPQ:
             self._aux = (pqh, hx, pmax2)
         return self._aux
 
-    def _search_lists(self, q, k, probes, nprobe, qt, offsets, sizes, list_codes, list_ids, view_hx=None):
+    def _search_lists(self, q, k, nprobe, head, tail, pack, qt, view_hx=None):
         """The list-major scan (``eioku_ivfpq_search_lists``): one C call enqueues the whole search.  ``view_hx``: the
         lists are a selected view and this is its ``hx`` (``pqh`` and ``pmax2`` stay the pack's)."""
         import torch
 
         nq = int(q.shape[0])
         if view_hx is None:
-            pqh, hx, pmax2 = self._lists_aux(q, offsets, sizes, list_codes)
+            pqh, hx, pmax2 = self._lists_aux(q, *pack[:3])
         else:
             pqh, _, pmax2 = self._aux
             hx = view_hx
@@ -473,14 +474,12 @@ class IndexIVFPQ:
             raise _lib.EiokuHipError("eioku_ivfpq_lists_workspace: bad argument")
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        D = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        D, I = empty_results(q, nq, k)
         stats = torch.zeros((6,), dtype=torch.int32, device=self.device)
-        _lib.check(self._lib.eioku_ivfpq_search_lists(ptr(q), nq, self.d, self.m, ptr(probes), nprobe, self.nlist, self.ntotal, ptr(self.coarse),
-                                                      ptr(self.pq), ptr(offsets), ptr(sizes), ptr(list_codes), ptr(list_ids),
-                                                      ptr(self._list_tables), ptr(qt), ptr(pqh), ptr(hx), ptr(pmax2), k,
-                                                      self.cand_cap, ptr(self._ws), self._ws.numel(), ptr(D), ptr(I), ptr(stats),
-                                                      current_stream(q)), "eioku_ivfpq_search_lists")
+        _lib.check(self._lib.eioku_ivfpq_search_lists(*head, self.nlist, self.ntotal, *tail, ptr(self._list_tables), ptr(qt),
+                                                      ptr(pqh), ptr(hx), ptr(pmax2), k, self.cand_cap, ptr(self._ws),
+                                                      self._ws.numel(), ptr(D), ptr(I), ptr(stats), current_stream(q)),
+                   "eioku_ivfpq_search_lists")
         self.last_stats = stats
         return D, I
 

@@ -16,7 +16,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from ._buffers import current_stream, on_device, ptr
+from ._buffers import current_stream, mem_flag, on_device, ptr
 from ._handle import Handle
 
 
@@ -62,6 +62,44 @@ class RowSelector:
         return int(self.to_mask().sum())
 
 
+def selector_words(sel, ntotal: int):
+    """-> (keep-alive object, pointer, mem flag) of a selector argument, length-checked against ``ntotal`` rows."""
+    if sel is None:
+        return None, None, _lib.MEM_HOST
+    nwords = (ntotal + 31) // 32
+    if isinstance(sel, RowSelector):
+        if sel.n != ntotal:
+            raise ValueError(f"selector covers {sel.n} rows, the index holds {ntotal}")
+        sel = sel.words
+    if on_device(sel):
+        import torch
+
+        if sel.dtype not in (torch.int32, torch.uint32) or sel.dim() != 1 or not sel.is_contiguous():
+            raise ValueError("a device selector is a contiguous 1-d int32 / uint32 tensor of packed words")
+        if int(sel.numel()) != nwords:
+            raise ValueError(f"a selector over {ntotal} rows has {nwords} words, got {int(sel.numel())}")
+        return sel, ptr(sel), _lib.MEM_DEVICE
+    sel = np.asarray(sel)
+    if sel.dtype != np.uint32 or sel.ndim != 1:
+        raise ValueError("a host selector is a 1-d uint32 array of packed words (see RowSelector)")
+    if sel.shape[0] != nwords:
+        raise ValueError(f"a selector over {ntotal} rows has {nwords} words, got {sel.shape[0]}")
+    sel = np.ascontiguousarray(sel)
+    if nwords == 0:
+        return None, None, _lib.MEM_HOST
+    return sel, ptr(sel), _lib.MEM_HOST
+
+
+def empty_results(q, nq: int, k: int):
+    """Uninitialised ``(D, I)``, float32 and int64 ``(nq, k)``, on the side of PCIe that ``q`` is on."""
+    if on_device(q):
+        import torch
+
+        return (torch.empty((nq, k), dtype=torch.float32, device=q.device),
+                torch.empty((nq, k), dtype=torch.int64, device=q.device))
+    return np.empty((nq, k), dtype=np.float32), np.empty((nq, k), dtype=np.int64)
+
+
 class IndexFlatL2:
     """Exact squared-L2 index resident in HBM (d in {64,128,256,384,512}, k <= 32)."""
 
@@ -98,33 +136,6 @@ class IndexFlatL2:
                        "eioku_index_remove_ids")
         return before - self.nlive
 
-    def _selector(self, sel, q):
-        """-> (keep-alive object, pointer, mem flag) of a selector argument, length-checked against ``ntotal``."""
-        if sel is None:
-            return None, None, _lib.MEM_HOST
-        nwords = (self.ntotal + 31) // 32
-        if isinstance(sel, RowSelector):
-            if sel.n != self.ntotal:
-                raise ValueError(f"selector covers {sel.n} rows, the index holds {self.ntotal}")
-            sel = sel.words
-        if on_device(sel):
-            import torch
-
-            if sel.dtype not in (torch.int32, torch.uint32) or sel.dim() != 1 or not sel.is_contiguous():
-                raise ValueError("a device selector is a contiguous 1-d int32 / uint32 tensor of packed words")
-            if int(sel.numel()) != nwords:
-                raise ValueError(f"a selector over {self.ntotal} rows has {nwords} words, got {int(sel.numel())}")
-            return sel, ptr(sel), _lib.MEM_DEVICE
-        sel = np.asarray(sel)
-        if sel.dtype != np.uint32 or sel.ndim != 1:
-            raise ValueError("a host selector is a 1-d uint32 array of packed words (see RowSelector)")
-        if sel.shape[0] != nwords:
-            raise ValueError(f"a selector over {self.ntotal} rows has {nwords} words, got {sel.shape[0]}")
-        sel = np.ascontiguousarray(sel)
-        if nwords == 0:
-            return None, None, _lib.MEM_HOST
-        return sel, ptr(sel), _lib.MEM_HOST
-
     def add(self, x) -> None:
         """Append vectors: float32 ``(n,d)`` numpy (staged over PCIe) or CUDA tensor (device copy)."""
         n, d = (int(s) for s in x.shape)
@@ -159,30 +170,20 @@ class IndexFlatL2:
             raise ValueError(f"expected dimension {self.d}, got {d}")
         if sel is not None:
             return self._search_sel(q, k, sel, None, None)
-        if on_device(q):
-            import torch
-
-            D = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-            mem = _lib.MEM_DEVICE
-        else:
+        if not on_device(q):
             q = np.ascontiguousarray(q, dtype=np.float32)
-            D = np.empty((nq, k), dtype=np.float32)
-            I = np.empty((nq, k), dtype=np.int64)
-            mem = _lib.MEM_HOST
-        _lib.check(self._h.eioku_index_search(ptr(q), nq, int(k), ptr(D), ptr(I), mem, current_stream(q)),
+        D, I = empty_results(q, nq, k)
+        _lib.check(self._h.eioku_index_search(ptr(q), nq, int(k), ptr(D), ptr(I), mem_flag(q), current_stream(q)),
                    "eioku_index_search")
         return D, I
 
     def _search_sel(self, q, k: int, sel, after_D, after_I):
         """``eioku_index_search_sel``: selector and (optional) ``search_after`` bound in one call."""
         nq = int(q.shape[0])
-        keep, sel_ptr, sel_mem = self._selector(sel, q)
+        keep, sel_ptr, sel_mem = selector_words(sel, self.ntotal)
         if on_device(q):
             import torch
 
-            D = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=q.device)
             if after_D is not None:
                 after_D = after_D.to(torch.float32).contiguous()
                 after_I = after_I.to(torch.int64).contiguous()
@@ -192,9 +193,8 @@ class IndexFlatL2:
             if after_D is not None:
                 after_D = np.ascontiguousarray(after_D, dtype=np.float32)
                 after_I = np.ascontiguousarray(after_I, dtype=np.int64)
-            D = np.empty((nq, k), dtype=np.float32)
-            I = np.empty((nq, k), dtype=np.int64)
             mem = _lib.MEM_HOST
+        D, I = empty_results(q, nq, k)
         _lib.check(self._h.eioku_index_search_sel(ptr(q), nq, int(k), sel_ptr, sel_mem,
                                                   None if after_D is None else ptr(after_D),
                                                   None if after_I is None else ptr(after_I), ptr(D), ptr(I), mem,
@@ -213,8 +213,6 @@ class IndexFlatL2:
         if on_device(q):
             import torch
 
-            D = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-            I = torch.empty((nq, k), dtype=torch.int64, device=q.device)
             after_D = after_D.to(torch.float32).contiguous()
             after_I = after_I.to(torch.int64).contiguous()
             mem = _lib.MEM_DEVICE
@@ -222,9 +220,8 @@ class IndexFlatL2:
             q = np.ascontiguousarray(q, dtype=np.float32)
             after_D = np.ascontiguousarray(after_D, dtype=np.float32)
             after_I = np.ascontiguousarray(after_I, dtype=np.int64)
-            D = np.empty((nq, k), dtype=np.float32)
-            I = np.empty((nq, k), dtype=np.int64)
             mem = _lib.MEM_HOST
+        D, I = empty_results(q, nq, k)
         _lib.check(self._h.eioku_index_search_after(ptr(q), nq, int(k), ptr(after_D), ptr(after_I), ptr(D),
                                                     ptr(I), mem, current_stream(q)), "eioku_index_search_after")
         return D, I
@@ -270,16 +267,13 @@ class IndexFlatL2:
 
 def merge_topk(d_lists, i_lists, k: int):
     """HIP merge of per-shard results: CUDA ``(L,nq,k)`` float32 / int64 (global ids) -> ``(nq,k)``."""
-    import torch
-
     if not on_device(d_lists):
         raise _lib.EiokuHipError("merge_topk runs on the GPU (eioku_topk_merge); got host tensors")
     lib = _lib.load()
     _lib.init()
     L, nq, kk = (int(s) for s in d_lists.shape)
     assert kk == k and tuple(i_lists.shape) == (L, nq, k)
-    D = torch.empty((nq, k), dtype=torch.float32, device=d_lists.device)
-    I = torch.empty((nq, k), dtype=torch.int64, device=d_lists.device)
+    D, I = empty_results(d_lists, nq, k)
     _lib.check(lib.eioku_topk_merge(ptr(d_lists.contiguous()), ptr(i_lists.contiguous()), L, nq, k, ptr(D), ptr(I),
                                     current_stream(d_lists)), "eioku_topk_merge")
     return D, I
@@ -355,16 +349,13 @@ class CommShardedFlatL2:
         self.local, self.id_base, self.comm = local, int(id_base), comm
 
     def search(self, q, k: int):
-        import torch
-
         if not on_device(q):
             raise _lib.EiokuHipError("eioku_index_search_sharded takes device queries")
         nq, d = (int(s) for s in q.shape)
         if d != self.local.d:
             raise ValueError(f"expected dimension {self.local.d}, got {d}")
         q = q.contiguous()
-        D = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        I = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+        D, I = empty_results(q, nq, k)
         _lib.check(self.local._h.eioku_index_search_sharded(self.comm._h.ptr, self.id_base, ptr(q), nq, int(k),
                                                             ptr(D), ptr(I), current_stream(q)), "eioku_index_search_sharded")
         return D, I

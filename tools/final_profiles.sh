@@ -33,7 +33,7 @@ python3 $R/tools/ivfpq_bench.py 10000000 1024 > $O/${TAG}_ivfpq_10M.json 2> $O/i
 tail -c 400 $O/${TAG}_ivfpq_10M.json
 rm -rf /tmp/prof
 IVFPQ_LISTS_ONLY=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- python3 $R/tools/ivfpq_bench.py 10000000 1024 > /tmp/ivf.json 2>/tmp/ivf.err || exit 1
-python3 $R/tools/kstats.py /tmp/prof 22 60 | grep -E "k_lscan|k_lrerank|k_ivfpq_scan|k_flat_l2<32|topk_merge_heads|k_ivfpq_tables|k_lbin|k_term1|k_inv_|k_lq_fill|k_q_prep|k_tau_probe|k_probe_merge" > $O/${TAG}_ivfpq_search_kernels.txt
+python3 $R/tools/kstats.py /tmp/prof 22 60 | grep -E "k_lscan|k_lrerank|k_ivfpq_scan|k_flat_l2<32|topk_merge_heads|k_ivfpq_tables|k_bin_pairs|k_term1|k_inv_|k_lq_fill|k_q_prep|k_tau_probe|k_probe_merge" > $O/${TAG}_ivfpq_search_kernels.txt
 cat $O/${TAG}_ivfpq_search_kernels.txt
 export IVFPQ_LISTS_ONLY=1
 bash $R/tools/pmc.sh k_lscan $O/${TAG}_pmc_ivfpq_scan.txt -- $R/tools/ivfpq_bench.py 10000000 1024 > /dev/null 2>&1
