@@ -63,6 +63,7 @@ SIGNATURES = {
     "eioku_debug_bounds": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int]),
     "eioku_debug_conv_routes": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int]),
     "eioku_debug_conv_epi": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
+    "eioku_debug_conv_plan": (C.c_int, [C.c_int] * 9 + [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "eioku_yolo_create": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "eioku_yolo_destroy": (None, [C.c_void_p]),
     "eioku_yolo_num_convs": (C.c_int, [C.c_void_p]),

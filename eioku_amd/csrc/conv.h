@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "conv_plan.h"
 
 namespace eioku {
 
@@ -96,51 +97,7 @@ int conv_stem_chain_forward(const ConvWeights& stem, const ConvWeights& c1, cons
 // (argmax channel << 32 | float bits of max_c(conv + bias)); ties go to the lower channel.
 bool conv_clsmax_ok(const ConvWeights& cw, int act);
 
-inline int conv_out_dim(int x, int ks, int stride) { return (x + 2 * (ks / 2) - ks) / stride + 1; }
-
-// Route log (eioku_debug_conv_routes): which conv-family instantiation a launch site started, counted where it is
-// started.  One fixed table of relaxed atomic counters; a slot is (family, template arguments) in mixed radix, the
-// names are formatted only when the log is read.  No device work, no allocation, safe from any number of host threads.
-enum RouteFamily { kRouteIgemm = 0, kRouteFlat, kRoutePersist, kRouteChain, kRouteC8, kRouteStemChain, kRoute1x1, kRouteGather,
-                   kNumRouteFamilies };
-struct RouteFamilyDesc {
-  const char* name;
-  int nfields;
-  const char* field[6];
-  int radix[6];  // a field's values are 0 .. radix - 1
-};
-constexpr RouteFamilyDesc kRouteFamilies[kNumRouteFamilies] = {
-    {"igemm", 3, {"NF", "K", "S"}, {9, 4, 3}},
-    {"flat", 4, {"NF", "S", "MT", "NS"}, {9, 3, 3, 9}},
-    {"persist", 6, {"NF", "S", "NCH", "DB", "POST", "NWV"}, {9, 3, 4, 2, 2, 9}},
-    {"chain", 4, {"NF", "DB", "CAT", "NFCAT"}, {3, 2, 4, 5}},
-    {"c8", 3, {"NF", "S", "SRC"}, {9, 3, 4}},
-    {"stem_chain", 1, {"MODE"}, {3}},
-    {"1x1", 4, {"NF", "UP", "NWV", "CLSMAX"}, {9, 2, 9, 2}},
-    {"gather", 0, {}, {}},
-};
-constexpr int route_family_slots(int fam) {
-  int n = 1;
-  for (int i = 0; i < kRouteFamilies[fam].nfields; ++i) n *= kRouteFamilies[fam].radix[i];
-  return n;
-}
-constexpr int route_family_base(int fam) {
-  int b = 0;
-  for (int f = 0; f < fam; ++f) b += route_family_slots(f);
-  return b;
-}
-constexpr int kRouteSlots = route_family_base(kNumRouteFamilies);
-// slot of (family, field values in the family's order); -1 when a value is outside its radix
-template <typename... V>
-constexpr int route_id(int fam, V... v) {
-  const int vals[] = {0, (int)v...};
-  int id = 0;
-  for (int i = 0; i < (int)sizeof...(V); ++i) {
-    if (vals[i + 1] < 0 || vals[i + 1] >= kRouteFamilies[fam].radix[i]) return -1;
-    id = id * kRouteFamilies[fam].radix[i] + vals[i + 1];
-  }
-  return (int)sizeof...(V) == kRouteFamilies[fam].nfields ? route_family_base(fam) + id : -1;
-}
+// conv_out_dim, the route table (RouteFamily, route_id), the kernels' LDS layouts and the plan: conv_plan.h (no HIP types)
 void route_hit(int id);
 
 }  // namespace eioku

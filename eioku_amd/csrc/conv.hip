@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <mutex>
 #include <type_traits>
 
 namespace eioku {
@@ -35,8 +36,6 @@ namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float float4v __attribute__((ext_vector_type(4)));
-
-constexpr int kTH = 8, kTW = 16;
 
 // ---- bounds-check build (`make bc` -> libeioku_hip_bc.so, -DEIOKU_BOUNDS_CHECK) -------------------
 // Round 2's GPU memory fault was an over-read past the end of a tensor that only faulted when the allocation ended on a
@@ -517,20 +516,19 @@ __device__ __forceinline__ void mma_taps(const uint4* patch, const uint4* wt_lan
 template <int NF, int KS, int S>
 __global__ __launch_bounds__(256) void k_conv_igemm(ConvArgs a) {
   static_assert(KS == 3, "the generic kernel serves 3x3 layers; 1x1 layers have k_conv1x1");
-  constexpr int PH = (kTH - 1) * S + KS;
-  constexpr int PW = (kTW - 1) * S + KS;
-  constexpr int PWH = (PW + 1) / 2;            // S == 2: columns stored de-interleaved (even | odd)
-  constexpr int PWS = (S == 2) ? 2 * PWH : PW;  // LDS row pitch in pixels
+  constexpr Patch G = patch_of(kTH, S);
+  constexpr TileLds L = igemm_layout(NF, S);
+  constexpr int PH = G.ph, PW = G.pw, PWH = G.pwh, PWS = G.pws;
   constexpr int TAPS = KS * KS;
   constexpr int PAD = KS / 2;
-  constexpr int PATCH_U = PH * PWS * 4;  // uint4 units
-  constexpr int WT_U = TAPS * 16 * NF * 4;
+  constexpr int PATCH_U = L.spare;  // uint4 units; the spare unit behind them: where idle slots park their store
+  constexpr int WT_U = wt_units(NF);
   constexpr int R = (PH * PW * 4 + 255) / 256;  // patch units staged per thread and chunk
   constexpr int WREG = (WT_U + 255) / 256;
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* patch = reinterpret_cast<uint4*>(smem);
-  uint4* wt = patch + PATCH_U + 4;  // + one spare unit: where idle slots park their store
+  uint4* wt = patch + L.wt;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int bx = blockIdx.x;
@@ -552,7 +550,7 @@ __global__ __launch_bounds__(256) void k_conv_igemm(ConvArgs a) {
     const int ih = ih0 + py, iw = iw0 + px;
     const bool in_patch = idx < PH * PW * 4;
     const bool ok = in_patch && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-    const int col = (S == 2) ? ((px & 1) * PWH + (px >> 1)) : px;
+    const int col = EIOKU_PATCH_COL(px, PWH, S);
     const int p = py * PWS + col;
     s_g[j] = ok ? ((n * a.H + ih) * a.W + iw) * a.in_cs + unit * 8 : 0;
     s_l[j] = in_patch ? p * 4 + (unit ^ ((p >> 1) & 3)) : PATCH_U;
@@ -592,7 +590,7 @@ __global__ __launch_bounds__(256) void k_conv_igemm(ConvArgs a) {
     for (int m = 0; m < 2; ++m) {
       const int py = (wave * 2 + m) * S + tap / KS;
       const int px = (lane & 15) * S + tap % KS;
-      const int col = (S == 2) ? ((px & 1) * PWH + (px >> 1)) : px;
+      const int col = EIOKU_PATCH_COL(px, PWH, S);
       const int p = py * PWS + col;
       bpos[tap][m] = p * 4 + ((lane >> 4) ^ ((p >> 1) & 3));
     }
@@ -632,16 +630,17 @@ __global__ __launch_bounds__(256) void k_conv_igemm(ConvArgs a) {
 template <int NF, int S, int MT, int NS>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_flat(ConvArgs a, int npix, int PR, int PW) {
   constexpr int TAPS = 9, KS = 3;
-  constexpr int WT_U = TAPS * 16 * NF * 4;
+  constexpr int WT_U = wt_units(NF);
   constexpr int WREG = (WT_U + 255) / 256;
   constexpr int TPX = 64 * MT;
-  const int PWH = (PW + 1) / 2;
-  const int PWS = (S == 2) ? 2 * PWH : PW;
-  const int DUMMY = PR * PWS * 4;  // one spare unit: where slots that carry nothing park their store
+  const TileLds L = flat_layout(NF, S, PR, PW);
+  const int PWH = patch_half(PW);
+  const int PWS = patch_pitch(PW, S);
+  const int DUMMY = L.spare;  // one spare unit: where slots that carry nothing park their store
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* patch = reinterpret_cast<uint4*>(smem);
-  uint4* wt = patch + DUMMY + 4;
+  uint4* wt = patch + L.wt;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int P0 = blockIdx.x * TPX;
@@ -667,7 +666,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_flat(ConvArgs a, int npix, i
     const int v = v_lo + pr;
     const int n = fast_div(v, VH, r_vh), y = v - n * VH - 1, x = pc - 1;
     const bool ok = idx < rows * PW * 4 && y >= 0 && n < a.N && (unsigned)x < (unsigned)a.W;
-    const int col = (S == 2) ? ((pc & 1) * PWH + (pc >> 1)) : pc;
+    const int col = EIOKU_PATCH_COL(pc, PWH, S);
     const int p = pr * PWS + col;
     s_g[j] = ok ? ((n * a.H + y) * a.W + x) * a.in_cs + unit * 8 : 0;
     s_l[j] = ok ? p * 4 + (unit ^ ((p >> 1) & 3)) : DUMMY;
@@ -716,7 +715,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_flat(ConvArgs a, int npix, i
 #pragma unroll
     for (int tap = 0; tap < TAPS; ++tap) {
       const int pc = xo * S + tap % KS;
-      const int col = (S == 2) ? ((pc & 1) * PWH + (pc >> 1)) : pc;
+      const int col = EIOKU_PATCH_COL(pc, PWH, S);
       const int p = (pr0 + tap / KS) * PWS + col;
       bpos[tap][m] = p * 4 + ((lane >> 4) ^ ((p >> 1) & 3));
     }
@@ -795,26 +794,25 @@ __global__ __launch_bounds__(64 * NWV) void k_conv3x3_persist(ConvArgs a, int to
   // NWV waves per workgroup, two output rows each: 8x16 tiles (4 waves) or, for the layers whose weight block leaves
   // room for one workgroup per CU only, 16x16 tiles (8 waves: two waves per SIMD instead of one)
   constexpr int KS = 3, TAPS = 9, PAD = 1, kTH = 2 * NWV, NT = 64 * NWV;
-  constexpr int PH = (kTH - 1) * S + KS;
-  constexpr int PW = (kTW - 1) * S + KS;
-  constexpr int PWH = (PW + 1) / 2;
-  constexpr int PWS = (S == 2) ? 2 * PWH : PW;
-  constexpr int PATCH_U = PH * PWS * 4;           // per chunk
-  constexpr int WT_U = TAPS * 16 * NF * 4;        // per chunk
+  constexpr Patch G = patch_of(kTH, S);
+  constexpr PersistLds L = persist_layout(NF, S, NCH, DB, POST, NWV);
+  constexpr int PH = G.ph, PW = G.pw, PWH = G.pwh, PWS = G.pws;
+  constexpr int PATCH_U = L.patch_u;              // per chunk
+  constexpr int WT_U = wt_units(NF);              // per chunk
   constexpr int NLOAD = PH * PW * 4 * NCH;        // staged units per tile
   constexpr int R = (NLOAD + NT - 1) / NT;          // per thread
   static_assert(R <= 32, "slot mask is one 32-bit word");
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* wt = reinterpret_cast<uint4*>(smem);                 // [NCH][WT_U]
-  uint4* patch = wt + NCH * WT_U;                             // [DB ? 2 : 1][NCH][PATCH_U] (+ 1 spare unit)
+  uint4* patch = wt + L.patch;                                // [DB ? 2 : 1][NCH][PATCH_U] (+ 1 spare unit)
   // POST: the 1x1 that consumes this conv's output runs here, on the tile still in registers (the intermediate
   // tensor is never written): its weights [NCH2][16*NF][4 units] and a per-wave [32 px][2*NF units] staging tile
   constexpr int U1 = 2 * NF;          // 16-byte units per pixel of the intermediate (16*NF channels)
   constexpr int NCH2 = (NF + 1) / 2;  // 32-channel chunks of the 1x1's K axis
   static_assert(!POST || NF % 2 == 0, "fused 1x1 needs a multiple of 32 intermediate channels");
-  uint4* wt2 = patch + (DB ? 2 : 1) * NCH * PATCH_U + 1;     // [NCH2][16*NF][4]
-  uint4* tbuf = wt2 + NCH2 * 16 * NF * 4;                     // [NWV waves][32][U1]
+  uint4* wt2 = wt + L.wt2;                                    // [NCH2][16*NF][4]
+  uint4* tbuf = wt + L.tbuf;                                  // [NWV waves][32][U1]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int co_tile = blockIdx.y;
@@ -830,10 +828,10 @@ __global__ __launch_bounds__(64 * NWV) void k_conv3x3_persist(ConvArgs a, int to
     const int cc = idx / (PH * PW * 4), rem = idx - cc * (PH * PW * 4);
     const int pix = rem >> 2, unit = rem & 3;
     const int py = pix / PW, px = pix - py * PW;
-    const int col = (S == 2) ? ((px & 1) * PWH + (px >> 1)) : px;
+    const int col = EIOKU_PATCH_COL(px, PWH, S);
     const int p = py * PWS + col;
     const bool in_patch = idx < NLOAD;
-    s_off[j] = in_patch ? cc * PATCH_U + p * 4 + (unit ^ ((p >> 1) & 3)) : (DB ? 2 : 1) * NCH * PATCH_U;
+    s_off[j] = in_patch ? cc * PATCH_U + p * 4 + (unit ^ ((p >> 1) & 3)) : L.spare;
     s_py[j] = py;
     s_px[j] = px;
     s_rel[j] = (py * a.W + px) * a.in_cs + cc * 32 + unit * 8;
@@ -870,7 +868,7 @@ __global__ __launch_bounds__(64 * NWV) void k_conv3x3_persist(ConvArgs a, int to
     for (int m = 0; m < 2; ++m) {
       const int py = (wave * 2 + m) * S + tap / KS;
       const int px = (lane & 15) * S + tap % KS;
-      const int col = (S == 2) ? ((px & 1) * PWH + (px >> 1)) : px;
+      const int col = EIOKU_PATCH_COL(px, PWH, S);
       const int p = py * PWS + col;
       bpos[tap][m] = p * 4 + ((lane >> 4) ^ ((p >> 1) & 3));
     }
@@ -1054,8 +1052,10 @@ template <int NF, bool DB, int CAT = 0, int NF2 = 2>
 __global__ __launch_bounds__(256) void k_conv3x3_chain(ConvArgs a, ChainCat cc, int total_tiles) {
   constexpr int XH = kTH + 4, XW = kTW + 4;  // input patch
   constexpr int PH = kTH + 2, PW = kTW + 2;  // intermediate patch
-  constexpr int X_U = XH * XW * 4, P_U = PH * PW * 4;
-  constexpr int WT_U = 9 * 16 * NF * 4;
+  constexpr ChainLds L = chain_layout(NF, DB, CAT, NF2);
+  constexpr int X_U = L.x_u, P_U = L.p_u;
+  static_assert(X_U == XH * XW * 4 && P_U == PH * PW * 4, "the layout's patches are this kernel's");
+  constexpr int WT_U = wt_units(NF);
   constexpr int NLOAD = X_U;
   constexpr int R = (NLOAD + 255) / 256;
   constexpr int NPA = PH * PW;           // conv A pixels per tile
@@ -1064,11 +1064,11 @@ __global__ __launch_bounds__(256) void k_conv3x3_chain(ConvArgs a, ChainCat cc, 
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* wtA = reinterpret_cast<uint4*>(smem);
-  uint4* wtB = wtA + WT_U;
-  uint4* xbuf = wtB + WT_U;                     // [DB ? 2 : 1][X_U] + 4 spare units
-  uint4* p1 = xbuf + (DB ? 2 : 1) * X_U + 4;    // [P_U] + 4 spare units (stores of the last fragment's tail)
-  uint4* wt2 = p1 + P_U + 4;                    // CAT: [(CAT + 1)][16*NF2][4]
-  constexpr int W2_U = CAT > 0 ? (CAT + 1) * 16 * NF2 * 4 : 0;
+  uint4* wtB = wtA + L.wtB;
+  uint4* xbuf = wtA + L.xbuf;                   // [DB ? 2 : 1][X_U] + 4 spare units
+  uint4* p1 = wtA + L.p1;                       // [P_U] + 4 spare units (stores of the last fragment's tail)
+  uint4* wt2 = wtA + L.wt2;                     // CAT: [(CAT + 1)][16*NF2][4]
+  constexpr int W2_U = L.w2_u;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int s_off[R], s_py[R], s_px[R], s_rel[R];
@@ -1343,11 +1343,10 @@ struct FusedSrc {
 template <int NF, int S, int SRC>
 __global__ __launch_bounds__(256) void k_conv3x3_c8(ConvArgs a, FusedSrc fs, int total_tiles) {
   constexpr int KS = 3, PAD = 1;
-  constexpr int PH = (kTH - 1) * S + KS;
-  constexpr int PW = (kTW - 1) * S + KS;
-  constexpr int PWH = (PW + 1) / 2;
-  constexpr int PWS = (S == 2) ? 2 * PWH : PW;
-  constexpr int PATCH_U = PH * PWS + 1;  // one unit per pixel (+ spare for idle slots)
+  constexpr Patch G = patch_of(kTH, S);
+  constexpr C8Lds L = c8_layout(NF, S);
+  constexpr int PH = G.ph, PW = G.pw, PWH = G.pwh, PWS = G.pws;
+  constexpr int PATCH_U = L.patch_u;  // one unit per pixel (+ spare for idle slots)
   constexpr int NPIX = PH * PW;
   constexpr int R = (NPIX + 255) / 256;
   constexpr int ROWS = 16 * NF;
@@ -1360,7 +1359,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_c8(ConvArgs a, FusedSrc fs, int
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* wt = reinterpret_cast<uint4*>(smem);  // [3 k-steps][ROWS][4 taps] swizzled per row
-  uint4* patch = wt + 3 * ROWS * 4;            // [2][PATCH_U]
+  uint4* patch = wt + L.patch;                 // [2][PATCH_U]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int co_tile = blockIdx.y;
@@ -1380,7 +1379,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_c8(ConvArgs a, FusedSrc fs, int
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int px = g_x + i;
-      const int col = (S == 2) ? ((px & 1) * PWH + (px >> 1)) : px;
+      const int col = EIOKU_PATCH_COL(px, PWH, S);
       g_off[i] = (tid < PH * GPR && px >= 0 && px < PW) ? g_py * PWS + col : PATCH_U - 1;
     }
   }
@@ -1390,7 +1389,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_c8(ConvArgs a, FusedSrc fs, int
   for (int j = 0; j < R; ++j) {
     const int idx = tid + 256 * j;
     const int py = idx / PW, px = idx - py * PW;
-    const int col = (S == 2) ? ((px & 1) * PWH + (px >> 1)) : px;
+    const int col = EIOKU_PATCH_COL(px, PWH, S);
     s_off[j] = idx < NPIX ? py * PWS + col : PATCH_U - 1;
     s_py[j] = py;
     s_px[j] = px;
@@ -1484,7 +1483,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_c8(ConvArgs a, FusedSrc fs, int
       if (tap > 8) tap = 8;
       const int py = (wave * 2 + m) * S + tap / KS;
       const int px = (lane & 15) * S + tap % KS;
-      const int col = (S == 2) ? ((px & 1) * PWH + (px >> 1)) : px;
+      const int col = EIOKU_PATCH_COL(px, PWH, S);
       bpos[j][m] = py * PWS + col;
     }
   const uint4* wt_lane = wt + (lane & 15) * 4 + ((lane >> 4) ^ ((lane >> 1) & 3));
@@ -1579,13 +1578,6 @@ struct StemArgs {
   int act;
   int H0, W0;         // network input (letterboxed) size
 };
-
-constexpr int kSX_H = 35, kSX_WH = 34, kSX_WS = 68, kSX_PX = kSX_H * kSX_WS;  // image patch, pixels (8 B each)
-constexpr int kSP_H = 17, kSP_W = 33, kSP_WH = 17, kSP_WS = 34, kSP_SLOTS = kSP_H * kSP_WS;  // P1, 32 B slots
-constexpr int kSC_WT1 = 9 * 32 * 4, kSC_WT2 = 32 * 4, kSC_T = 4 * 32 * 4;
-constexpr int kSC_P1_U = (kSP_SLOTS + 1) * 2;       // + one spare slot
-constexpr int kSC_XS_U = (kSX_PX + 2) / 2 + 1;      // + spare pixel, 16 B units
-constexpr size_t kStemChainLds = (size_t)(kSC_WT1 + kSC_WT2 + kSC_T + kSC_P1_U + kSC_XS_U) * 16;
 
 // DECIM: the image region is a strided sampling of the source (FusedInput::step / off: 1080p -> 360 x 640 is step 3,
 // off 1): the 4 pixels of a group are 4 unaligned dword loads (3 bytes each + one ignored) instead of one dwordx3
@@ -1875,342 +1867,177 @@ __global__ __launch_bounds__(256) void k_conv_stem_chain(ConvArgs a, StemArgs st
   }
 }
 
-template <int NF, int S, int SRC>
-int launch_c8(const ConvArgs& a, const FusedSrc& fs, int ntiles, hipStream_t stream) {
-  constexpr int PH = (kTH - 1) * S + 3, PW = (kTW - 1) * S + 3;
-  constexpr int PWS = (S == 2) ? 2 * ((PW + 1) / 2) : PW;
-  constexpr size_t lds = ((size_t)3 * 16 * NF * 4 + 2 * (PH * PWS + 1)) * 16;
-  const int total = a.tiles_w * a.tiles_h * a.N;
-  int bx = num_cus() * 6 / ntiles;  // small LDS footprint: ~6 workgroups per CU keep the byte loads in flight
-  if (bx < 1) bx = 1;
-  if (bx > total) bx = total;
-  route_hit(route_id(kRouteC8, NF, S, SRC));
-  hipLaunchKernelGGL((k_conv3x3_c8<NF, S, SRC>), dim3((unsigned)bx, (unsigned)ntiles), dim3(256), lds, stream, a, fs, total);
+// ---- launching: layouts and routes come from conv_plan.h, everything that touches the device is here ----------------
+// Workgroups of `Kernel` that can be RESIDENT on one CU, registers included: a persistent grid sized from LDS alone
+// runs its surplus workgroups as a second, half-empty round (k_conv3x3_chain<1,...,1,2>: 174 VGPRs = two waves per
+// SIMD = two workgroups per CU, launched three per CU because three fit its LDS).  Asked once per kernel.
+template <auto Kernel>
+int resident_per_cu(int threads, size_t lds) {
+  static const int occ = [&] {
+    int n = 0;
+    const bool ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, Kernel, threads, lds) == hipSuccess && n >= 1;
+    if (!ok) (void)hipGetLastError();
+    return ok ? n : 1;
+  }();
+  return occ;
+}
+// Workgroups per CU of a persistent grid: as many `lds`-byte ones as fit `budget` bytes of the CU's LDS, at least one,
+// at most `limit` and, where the caller asked the occupancy (`occ` > 0), no more than are resident.
+int wg_per_cu(size_t budget, size_t lds, int limit, int occ = 0) {
+  const int n = std::max(1, std::min((int)(budget / lds), limit));
+  return occ > 0 ? std::min(n, occ) : n;
+}
+// x extent of that grid: `per_cu` workgroups on every CU, shared among the `ntiles` cout tiles (grid y), never more than
+// there are tiles to walk
+unsigned persistent_grid(int per_cu, int ntiles, long long total) {
+  const long long bx = std::max(1ll, (long long)num_cus() * per_cu / ntiles);
+  return (unsigned)std::min(bx, total);
+}
+// Every launch of the family: lift the kernel's dynamic-LDS ceiling where `lds` needs more than the default 64 KB (per
+// kernel, the largest value set so far: an instantiation whose LDS varies at run time is raised again by a larger layer
+// and never lowered by a smaller one; host threads meet in the atomic and, to raise, behind one mutex), count the route,
+// launch, check.
+std::mutex g_lds_attr_mutex;
+template <auto Kernel, typename... A>
+int launch_kernel(int route, dim3 grid, int threads, size_t lds, hipStream_t stream, const A&... args) {
+  static std::atomic<size_t> raised{0};
+  if (lds > 64 * 1024 && lds > raised.load(std::memory_order_acquire)) {
+    std::lock_guard<std::mutex> lock(g_lds_attr_mutex);
+    if (lds > raised.load(std::memory_order_relaxed)) {
+      EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)lds));
+      raised.store(lds, std::memory_order_release);
+    }
+  }
+  route_hit(route);
+  hipLaunchKernelGGL(Kernel, grid, dim3((unsigned)threads), lds, stream, args...);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
 }
 
-template <int S>
-int launch_c8_dispatch(int nf, int src, const ConvArgs& a, const FusedSrc& fs, int ntiles, hipStream_t stream, bool* handled) {
-  *handled = true;
-#define EIOKU_C8(NF_)                                                            \
-  if (nf == NF_) {                                                                \
-    if (src == 0) return launch_c8<NF_, S, 0>(a, fs, ntiles, stream);              \
-    if (src == 1) return launch_c8<NF_, S, 1>(a, fs, ntiles, stream);              \
-    if (src == 3) return launch_c8<NF_, S, 3>(a, fs, ntiles, stream);              \
-    return launch_c8<NF_, S, 2>(a, fs, ntiles, stream);                            \
-  }
-  EIOKU_C8(1) EIOKU_C8(2) EIOKU_C8(3) EIOKU_C8(4) EIOKU_C8(5)
-#undef EIOKU_C8
-  *handled = false;
-  return EIOKU_OK;
+template <int NF, int S, int SRC>
+int launch_c8(const ConvPlan& p, const ConvArgs& a, const FusedSrc& fs, int ntiles, hipStream_t stream) {
+  const int total = a.tiles_w * a.tiles_h * a.N;
+  // small LDS footprint: ~6 workgroups per CU keep the byte loads in flight
+  const dim3 grid(persistent_grid(6, ntiles, total), (unsigned)ntiles);
+  return launch_kernel<k_conv3x3_c8<NF, S, SRC>>(route_id(kRouteC8, NF, S, SRC), grid, p.threads, p.lds, stream, a, fs, total);
 }
 
-// Workgroups of `kernel` that can be RESIDENT on one CU, registers included: a persistent grid sized from LDS alone
-// runs its surplus workgroups as a second, half-empty round (k_conv3x3_chain<1,...,1,2>: 174 VGPRs = two waves per
-// SIMD = two workgroups per CU, launched three per CU because three fit its LDS).
-template <typename K>
-int resident_per_cu(K kernel, int threads, size_t lds) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, lds) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    n = 1;
-  }
-  return n;
-}
-
-template <int NF, int S, int NCH, bool DB, bool POST = false, int NWV = 4>
-int launch_persist(const ConvArgs& a_in, int ntiles, hipStream_t stream) {
-  constexpr int TH = 2 * NWV;
-  constexpr int PH = (TH - 1) * S + 3, PW = (kTW - 1) * S + 3;
-  constexpr int PWS = (S == 2) ? 2 * ((PW + 1) / 2) : PW;
-  constexpr size_t post_units = POST ? (size_t)((NF + 1) / 2) * 16 * NF * 4 + NWV * 32 * 2 * NF : 0;
-  constexpr size_t lds = ((size_t)NCH * 9 * 16 * NF * 4 + (DB ? 2 : 1) * (size_t)NCH * PH * PWS * 4 + 1 + post_units) * 16;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_persist<NF, S, NCH, DB, POST, NWV>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
-  ConvArgs a = a_in;
-  a.tiles_h = (a.Ho + TH - 1) / TH;
+template <int NF, int S, int NCH, bool DB, bool POST, int NWV>
+int launch_persist(const ConvPlan& p, ConvArgs a, int ntiles, hipStream_t stream) {
+  constexpr auto K = k_conv3x3_persist<NF, S, NCH, DB, POST, NWV>;
+  a.tiles_h = (a.Ho + 2 * NWV - 1) / (2 * NWV);
   const int total = a.tiles_w * a.tiles_h * a.N;
   // 160 KB of LDS per CU: two 78 KB workgroups do fit (measured on model.22.cv3.0.0, 68 -> 57 us)
-  int per_cu = (int)((size_t)160 * 1024 / lds);
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 4) per_cu = 4;
-  static const int occ = resident_per_cu(k_conv3x3_persist<NF, S, NCH, DB, POST, NWV>, 64 * NWV, lds);
-  if (per_cu > occ) per_cu = occ;
-  int bx = num_cus() * per_cu / ntiles;
-  if (bx < 1) bx = 1;
-  if (bx > total) bx = total;
-  route_hit(route_id(kRoutePersist, NF, S, NCH, DB, POST, NWV));
-  hipLaunchKernelGGL((k_conv3x3_persist<NF, S, NCH, DB, POST, NWV>), dim3((unsigned)bx, (unsigned)ntiles), dim3(64 * NWV), lds,
-                     stream, a, total);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
+  const int per_cu = wg_per_cu(160 * 1024, p.lds, 4, resident_per_cu<K>(p.threads, p.lds));
+  const dim3 grid(persistent_grid(per_cu, ntiles, total), (unsigned)ntiles);
+  return launch_kernel<K>(route_id(kRoutePersist, NF, S, NCH, DB, POST, NWV), grid, p.threads, p.lds, stream, a, total);
 }
 
-// LDS bytes of the persistent variant
-size_t persist_lds(int nf, int s, int nch, bool db, int th = kTH) {
-  const int ph = (th - 1) * s + 3, pw = (kTW - 1) * s + 3;
-  const int pws = s == 2 ? 2 * ((pw + 1) / 2) : pw;
-  return ((size_t)nch * 9 * 16 * nf * 4 + (db ? 2 : 1) * (size_t)nch * ph * pws * 4 + 1) * 16;
-}
-
-template <int S>
-int launch_persist_dispatch(int nf, int nch, bool db, const ConvArgs& a, int ntiles, hipStream_t stream, bool* handled) {
-  *handled = true;
-  // weight block too large for two workgroups per CU: one 8-wave workgroup with a 16x16 tile (two waves per SIMD)
-  if (S == 1 && !db && nf == 3 && nch == 3 && persist_lds(nf, S, nch, false) > 80 * 1024 &&
-      persist_lds(nf, S, nch, false, 16) <= 160 * 1024 && a.Ho > 8)
-    return launch_persist<3, S, 3, false, false, 8>(a, ntiles, stream);
-  if (S == 1 && !db && nf == 5 && nch == 2 && a.Ho > 8) return launch_persist<5, S, 2, false, false, 8>(a, ntiles, stream);
-#define EIOKU_P(NF_, NCH_)                                                                    \
-  if (nf == NF_ && nch == NCH_)                                                                \
-    return db ? launch_persist<NF_, S, NCH_, true>(a, ntiles, stream) : launch_persist<NF_, S, NCH_, false>(a, ntiles, stream);
-  EIOKU_P(1, 1) EIOKU_P(2, 1) EIOKU_P(3, 1) EIOKU_P(4, 1) EIOKU_P(5, 1) EIOKU_P(6, 1)
-  EIOKU_P(1, 2) EIOKU_P(2, 2) EIOKU_P(3, 2) EIOKU_P(4, 2) EIOKU_P(5, 2)
-  EIOKU_P(1, 3) EIOKU_P(2, 3) EIOKU_P(3, 3) EIOKU_P(4, 3) EIOKU_P(5, 3)
-#undef EIOKU_P
-  *handled = false;
-  return EIOKU_OK;
-}
-
-// 3x3 + following 1x1 in one launch (the intermediate tensor never exists).  Instantiated for the two shapes the
-// YOLOv8 backbone has (stride-2 conv -> C2f.cv1 with 32 / 64 channels) and their stride-1 twins.
-template <int S>
-int launch_persist_post_dispatch(int nf, int nch, bool db, const ConvArgs& a, hipStream_t stream, bool* handled) {
-  *handled = true;
-  // stride-2, 64 couts (model.3 -> model.4.cv1): 98 KB of LDS = one 4-wave workgroup per CU.  An 8-wave 16x16-tile
-  // variant (149 KB, two waves on every SIMD) measured 54 -> 50 us alone but a slower overlapped step (41.8 vs 42.2 k
-  // frames/s: 149 KB leave no LDS for the other streams' workgroups) and was removed.
-#define EIOKU_PP(NF_, NCH_)                                                                             \
-  if (nf == NF_ && nch == NCH_)                                                                          \
-    return db ? launch_persist<NF_, S, NCH_, true, true>(a, 1, stream) : launch_persist<NF_, S, NCH_, false, true>(a, 1, stream);
-  EIOKU_PP(2, 1) EIOKU_PP(4, 1) EIOKU_PP(2, 2) EIOKU_PP(4, 2)
-#undef EIOKU_PP
-  *handled = false;
-  return EIOKU_OK;
-}
-
-size_t chain_lds(int nf, bool db, int cat_units = 0) {
-  return ((size_t)2 * 9 * 16 * nf * 4 + (db ? 2 : 1) * (size_t)(kTH + 4) * (kTW + 4) * 4 + 4 + (size_t)(kTH + 2) * (kTW + 2) * 4 + 4 +
-          cat_units) * 16;
-}
-
-template <int NF, bool DB, int CAT = 0, int NF2 = 2>
+template <int NF, int CAT, int NF2>
 int launch_chain(const ConvArgs& a, const ChainCat& cc, hipStream_t stream) {
-  const size_t lds = chain_lds(NF, DB, CAT > 0 ? (CAT + 1) * 16 * NF2 * 4 : 0);
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_chain<NF, DB, CAT, NF2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
+  // (a second patch buffer was measured against an extra workgroup per CU: 77 vs 69 us at 160^2; single-buffered it is)
+  constexpr auto K = k_conv3x3_chain<NF, false, CAT, NF2>;
+  constexpr size_t lds = lds_bytes(chain_layout(NF, false, CAT, NF2).total);
   const int total = a.tiles_w * a.tiles_h * a.N;
-  int per_cu = (int)(160 * 1024 / lds);  // two 80.3 KB workgroups (32-channel C2f + its closing 1x1) share a CU
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 4) per_cu = 4;
-  static const int occ = resident_per_cu(k_conv3x3_chain<NF, DB, CAT, NF2>, 256, lds);
-  if (per_cu > occ) per_cu = occ;
-  int bx = num_cus() * per_cu;
-  if (bx > total) bx = total;
-  route_hit(route_id(kRouteChain, NF, DB, CAT, NF2));
-  hipLaunchKernelGGL((k_conv3x3_chain<NF, DB, CAT, NF2>), dim3((unsigned)bx), dim3(256), lds, stream, a, cc, total);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
-}
-
-// Flattened-pixel deep-K launch: geometry of the worst-case patch, then the largest tile whose staging
-// fits the per-thread slot budget.  *handled = false leaves the layer to the generic kernel.
-struct FlatGeom {
-  int PR, PW, slots;
-  size_t lds;
-};
-template <int S>
-FlatGeom flat_geom(const ConvArgs& a, int nf, int mt) {
-  const int tpx = 64 * mt;
-  const int r_o = (a.Wo - 2 + tpx) / a.Wo + 1;
-  int cross = (tpx - 1) / (a.Ho * a.Wo) + 1;
-  if (cross > r_o - 1) cross = r_o - 1;
-  const int extra = (a.H + 1) - a.Ho * S;
-  FlatGeom g;
-  g.PR = (r_o - 1) * S + 3 + cross * (extra > 0 ? extra : 0);
-  g.PW = (a.Wo - 1) * S + 3;
-  const int pws = (S == 2) ? 2 * ((g.PW + 1) / 2) : g.PW;
-  g.slots = (g.PR * g.PW * 4 + 255) / 256;
-  g.lds = ((size_t)g.PR * pws * 4 + 4 + 9 * 16 * nf * 4) * 16;
-  return g;
+  // two 80.3 KB workgroups (32-channel C2f + its closing 1x1) share a CU
+  const int per_cu = wg_per_cu(160 * 1024, lds, 4, resident_per_cu<K>(256, lds));
+  const dim3 grid(persistent_grid(per_cu, 1, total));  // one cout tile: the whole chip walks the pixel tiles
+  return launch_kernel<K>(route_id(kRouteChain, NF, 0, CAT, NF2), grid, 256, lds, stream, a, cc, total);
 }
 
 template <int NF, int S, int MT, int NS>
-int launch_flat(const ConvArgs& a, const FlatGeom& g, int ntiles, hipStream_t stream) {
-  static size_t attr = 0;
-  if (g.lds > 64 * 1024 && g.lds > attr) {
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_flat<NF, S, MT, NS>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
-    attr = g.lds;
-  }
-  const int npix = a.N * a.Ho * a.Wo;
-  const int tpx = 64 * MT;
-  route_hit(route_id(kRouteFlat, NF, S, MT, NS));
+int launch_flat(const ConvPlan& p, const ConvArgs& a, int ntiles, hipStream_t stream) {
+  const int npix = a.N * a.Ho * a.Wo, tpx = 64 * MT;
   // the kernel's own test (epi_variant) for the first cout tile: this launch runs the straight-line epilogue somewhere
   if (a.epi && !a.out_f32 && (a.Cout & 3) == 0 && a.Cout >= 16 * NF && (a.act == kActSiLU || a.act == kActNone))
     g_epi_launches.fetch_add(1u, std::memory_order_relaxed);
-  hipLaunchKernelGGL((k_conv3x3_flat<NF, S, MT, NS>), dim3((unsigned)((npix + tpx - 1) / tpx), (unsigned)ntiles),
-                     dim3(256), g.lds, stream, a, npix, g.PR, g.PW);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
+  const dim3 grid((unsigned)((npix + tpx - 1) / tpx), (unsigned)ntiles);
+  return launch_kernel<k_conv3x3_flat<NF, S, MT, NS>>(route_id(kRouteFlat, NF, S, MT, NS), grid, p.threads, p.lds, stream, a, npix,
+                                                      p.pr, p.pw);
 }
 
-template <int S>
-int launch_flat_dispatch(int nf, const ConvArgs& a, int ntiles, hipStream_t stream, bool* handled) {
-  *handled = false;
-  // 32-bit element offsets; pixel / virtual-row indices below 2^24 (fast_div)
-  if ((long long)a.N * a.H * a.W * a.in_cs >= (1ll << 31) || (long long)a.N * (a.H + 1) * (a.W + 2) >= (1ll << 24)) return EIOKU_OK;
-  int mt = 2;
-  FlatGeom g = flat_geom<S>(a, nf, mt);
-  if (g.slots > 8 || g.lds > 80 * 1024) {
-    mt = 1;
-    g = flat_geom<S>(a, nf, mt);
-  }
-  if (g.slots > 8 || g.lds > 150 * 1024) return EIOKU_OK;
-  *handled = true;
-#define EIOKU_F(NF_)                                                                                             \
-  if (nf == NF_) {                                                                                                \
-    if (g.slots <= 4)                                                                                             \
-      return mt == 2 ? launch_flat<NF_, S, 2, 4>(a, g, ntiles, stream) : launch_flat<NF_, S, 1, 4>(a, g, ntiles, stream); \
-    return mt == 2 ? launch_flat<NF_, S, 2, 8>(a, g, ntiles, stream) : launch_flat<NF_, S, 1, 8>(a, g, ntiles, stream);   \
-  }
-  EIOKU_F(2) EIOKU_F(3) EIOKU_F(4) EIOKU_F(5) EIOKU_F(6)
-#undef EIOKU_F
-  *handled = false;
-  return EIOKU_OK;
+template <int NF, int S>
+int launch_igemm(const ConvPlan& p, const ConvArgs& a, int ntiles, hipStream_t stream) {
+  const dim3 grid((unsigned)(a.tiles_w * a.tiles_h * a.N), (unsigned)ntiles);
+  return launch_kernel<k_conv_igemm<NF, 3, S>>(route_id(kRouteIgemm, NF, 3, S), grid, p.threads, p.lds, stream, a);
 }
 
-template <int NF, int KS, int S>
-int launch(const ConvArgs& a, int ntiles, hipStream_t stream) {
-  constexpr int PH = (kTH - 1) * S + KS;
-  constexpr int PW = (kTW - 1) * S + KS;
-  constexpr int PWS = (S == 2) ? 2 * ((PW + 1) / 2) : PW;
-  constexpr size_t lds = (size_t)(PH * PWS * 4 + 4 + KS * KS * 16 * NF * 4) * 16;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_igemm<NF, KS, S>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
-  dim3 grid((unsigned)(a.tiles_w * a.tiles_h * a.N), (unsigned)ntiles);
-  route_hit(route_id(kRouteIgemm, NF, KS, S));
-  hipLaunchKernelGGL((k_conv_igemm<NF, KS, S>), grid, dim3(256), lds, stream, a);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
+template <int NF, bool UP>
+int launch_1x1(const ConvPlan& p, const ConvArgs& a, int ntiles, hipStream_t stream) {
+  constexpr int NWV = 4;
+  const long long npix = (long long)a.N * a.H * a.W, groups = (npix + 31) / 32;
+  // one pixel group per wave at the most; grid-stride beyond wg_cu workgroups per CU
+  const dim3 grid(persistent_grid(p.wg_cu, ntiles, std::max(1ll, (groups + NWV - 1) / NWV)), (unsigned)ntiles);
+  return launch_kernel<k_conv1x1<NF, UP, NWV>>(route_id(kRoute1x1, NF, UP, NWV, a.clsmax != nullptr), grid, p.threads, p.lds, stream, a,
+                                               npix);
 }
 
-template <int KS, int S>
-int launch_nf(int nf, const ConvArgs& a, int ntiles, hipStream_t stream) {
-  switch (nf) {
-    case 1: return launch<1, KS, S>(a, ntiles, stream);
-    case 2: return launch<2, KS, S>(a, ntiles, stream);
-    case 3: return launch<3, KS, S>(a, ntiles, stream);
-    case 4: return launch<4, KS, S>(a, ntiles, stream);
-    case 5: return launch<5, KS, S>(a, ntiles, stream);
-    case 6: return launch<6, KS, S>(a, ntiles, stream);
-    case 8: return launch<8, KS, S>(a, ntiles, stream);
+// The one way a run-time integer becomes a template argument: f(std::integral_constant<int, V>) for the V of the list
+// that equals v, and what f returns; false when none does.  Nested, the lists spell out the instantiated kernels.
+template <int... Vs, typename F>
+bool with_const(int v, F&& f) {
+  return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
+}
+#define CV(x) decltype(x)::value  // the constant with_const handed to a lambda as x
+
+// Launches the instantiation a plan names.  The lists are the set of instantiated kernels: a plan outside them is an
+// error, never another kernel.
+int launch_plan(const ConvPlan& p, const ConvArgs& a, const FusedSrc& fs, int ntiles, hipStream_t stream) {
+  const int* t = p.t;
+  int rc = EIOKU_OK;
+  bool hit = false;
+  auto s12 = [&](auto&& f) { return with_const<1, 2>(t[1], f); };
+  if (p.family == kRouteC8) {
+    hit = t[1] == 2 && with_const<1, 2, 3, 4, 5>(t[0], [&](auto nf) {
+      return with_const<0, 1, 2, 3>(t[2], [&](auto src) { return rc = launch_c8<CV(nf), 2, CV(src)>(p, a, fs, ntiles, stream), true; });
+    });
+  } else if (p.family == kRoutePersist) {
+    const int key = t[0] * 10 + t[2];  // NF, NCH
+    auto s_db = [&](auto k, auto post) {
+      return s12([&](auto s) {
+        return with_const<0, 1>(t[3], [&](auto db) {
+          return rc = launch_persist<CV(k) / 10, CV(s), CV(k) % 10, CV(db) != 0, CV(post) != 0, 4>(p, a, ntiles, stream), true;
+        });
+      });
+    };
+    if (t[5] == 8)
+      hit = !t[3] && !t[4] && with_const<33, 52>(key, [&](auto k) {
+        return s12([&](auto s) { return rc = launch_persist<CV(k) / 10, CV(s), CV(k) % 10, false, false, 8>(p, a, ntiles, stream), true; });
+      });
+    else if (t[5] == 4 && t[4])
+      hit = with_const<21, 41, 22, 42>(key, [&](auto k) { return s_db(k, std::true_type{}); });
+    else if (t[5] == 4)
+      hit = with_const<11, 21, 31, 41, 51, 61, 12, 22, 32, 42, 52, 13, 23, 33, 43, 53>(key, [&](auto k) { return s_db(k, std::false_type{}); });
+  } else if (p.family == kRouteFlat) {
+    hit = with_const<2, 3, 4, 5, 6>(t[0], [&](auto nf) {
+      return s12([&](auto s) {
+        return with_const<1, 2>(t[2], [&](auto mt) {
+          return with_const<4, 8>(t[3], [&](auto ns) { return rc = launch_flat<CV(nf), CV(s), CV(mt), CV(ns)>(p, a, ntiles, stream), true; });
+        });
+      });
+    });
+  } else if (p.family == kRouteIgemm) {
+    hit = t[1] == 3 && with_const<1, 2, 3, 4, 5, 6, 8>(t[0], [&](auto nf) {
+      return with_const<1, 2>(t[2], [&](auto s) { return rc = launch_igemm<CV(nf), CV(s)>(p, a, ntiles, stream), true; });
+    });
+  } else if (p.family == kRoute1x1) {
+    hit = t[2] == 4 && with_const<1, 2, 3, 4, 5, 6, 8>(t[0], [&](auto nf) {
+      return with_const<0, 1>(t[1], [&](auto up) { return rc = launch_1x1<CV(nf), CV(up) != 0>(p, a, ntiles, stream), true; });
+    });
   }
-  set_error("unsupported nf %d", nf);
+  if (hit) return rc;
+  char name[160] = "?";
+  if (p.ok()) route_name(name, sizeof name, p.family, t);
+  set_error("no kernel is instantiated for the planned route %s", name);
   return EIOKU_EINVAL;
 }
-
-template <int NF, bool UP, int NWV>
-int launch1x1_impl(const ConvArgs& a, int ntiles, int wg_cu, hipStream_t stream) {
-  const size_t lds = (size_t)a.nchunks * 16 * NF * 64;
-  static size_t attr = 0;
-  if (lds > 64 * 1024 && lds > attr) {
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv1x1<NF, UP, NWV>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr = lds;
-  }
-  const long long npix = (long long)a.N * a.H * a.W;
-  const long long groups = (npix + 31) / 32;
-  long long bx = (groups + NWV - 1) / NWV;
-  const long long cap = (long long)num_cus() * wg_cu / ntiles;  // grid-stride beyond that many workgroups per CU
-  if (bx > cap) bx = cap;
-  if (bx < 1) bx = 1;
-  route_hit(route_id(kRoute1x1, NF, UP, NWV, a.clsmax != nullptr));
-  hipLaunchKernelGGL((k_conv1x1<NF, UP, NWV>), dim3((unsigned)bx, (unsigned)ntiles), dim3(64 * NWV), lds, stream, a, npix);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
-}
-
-// Workgroups per CU: few and persistent.  Measured on the 64-frame forward (19 1x1 layers, 8 -> 2 workgroups per
-// CU: 625 -> 555 us): every workgroup pays the weight-tile copy and its dispatch, and one-group-per-wave grids
-// (800 workgroups at 40x40) never reach the grid-stride loop that hides the load latency.  The widest tiles (NF = 8:
-// 64 MFMAs per pixel group and wave) are best with ONE workgroup per CU.
-template <int NF>
-int launch1x1(const ConvArgs& a, int ntiles, hipStream_t stream) {
-  const int wg = (NF >= 8 || (size_t)a.nchunks * 16 * NF * 64 > 80 * 1024) ? 1 : 2;
-  return a.in2 ? launch1x1_impl<NF, true, 4>(a, ntiles, wg, stream) : launch1x1_impl<NF, false, 4>(a, ntiles, wg, stream);
-}
-
-int launch1x1_nf(int nf, const ConvArgs& a, int ntiles, hipStream_t stream) {
-  switch (nf) {
-    case 1: return launch1x1<1>(a, ntiles, stream);
-    case 2: return launch1x1<2>(a, ntiles, stream);
-    case 3: return launch1x1<3>(a, ntiles, stream);
-    case 4: return launch1x1<4>(a, ntiles, stream);
-    case 5: return launch1x1<5>(a, ntiles, stream);
-    case 6: return launch1x1<6>(a, ntiles, stream);
-    case 8: return launch1x1<8>(a, ntiles, stream);
-  }
-  set_error("unsupported nf %d", nf);
-  return EIOKU_EINVAL;
-}
-
-// Fewest padded channels first, then the widest tile (fewer re-reads of the input patch).
-int pick_nf(int cout, int ks, int nchunks, int stride) {
-  const int frags = (cout + 15) / 16;
-  // (64 -> 80, the class branch's first conv at P3, as ONE 5-fragment 8-wave workgroup of 134 KB instead of 48 + 32
-  // couts in two 78 KB workgroups measured no gain: 56.2 vs 56.7 us alone, 41.3 vs 41.3 k frames/s overlapped)
-  if (ks == 3 && nchunks <= 3) {
-    // persistent kernel: largest tile (<= 4 fragments, no padding waste beyond one fragment) that still fits
-    // two workgroups per CU with a single-buffered patch; otherwise fall through to the generic rule
-    for (int nf : {4, 3, 2, 1}) {
-      const int waste = ((frags + nf - 1) / nf) * nf - frags;
-      constexpr int lim_kb = 79;  // two workgroups per 160 KB CU
-      if (waste <= (frags >= 4 ? 1 : 0) && persist_lds(nf, stride, nchunks, false) <= (size_t)lim_kb * 1024) {
-        // a 1-fragment tile re-reads the halo patch once per 16 couts and is LDS-read bound (3 reads per 2
-        // MFMAs): with >= 5 fragments take 3 per tile even if only one workgroup then fits per CU
-        if (nf == 1 && frags >= 5 && persist_lds(3, stride, nchunks, false) <= 150 * 1024) return 3;
-        return nf;
-      }
-    }
-  }
-  const int cands[] = {8, 6, 5, 4, 3, 2, 1};
-  int best = 1, best_waste = 1 << 30;
-  for (int nf : cands) {
-    if (ks == 3 && nf > 6) continue;  // LDS: 9 taps x 16*NF x 64 B
-    // 64 KB: with 96-128 KB tiles (NF = 8, 8 waves) the 384/512-channel 1x1 layers are 2-4 us faster each in an
-    // isolated trace (-26 us per forward) but the overlapped step is not (40.5 vs 40.4 k frames/s) and the serial
-    // profiled step is slower: a workgroup holding most of a CU's LDS keeps the other streams' kernels off that CU
-    // beyond 16 chunks (Cin > 512: YOLOv8m / l / x only) a 16-cout tile would re-read the whole input once per 16 couts
-    // (Cin = 1152 -> 576: 36 times): up to 128 KB there, one workgroup per CU
-    const int lim1 = nchunks > 16 ? 128 : 64;
-    if (ks == 1 && nf * nchunks > lim1 && nf > 1) continue;  // 1x1: the whole Cin x tile weight block lives in LDS (nf*nchunks KB)
-    int waste = ((frags + nf - 1) / nf) * nf - frags;
-    if (waste < best_waste) {
-      best_waste = waste;
-      best = nf;
-    }
-  }
-  return best;
-}
+#undef CV
 
 }  // namespace
 
-int conv_weights_create(ConvWeights* cw, int cout, int cin, int ks, int stride, const float* w,
-                        const float* b) {
+// the shape half of conv_weights_create: what the plan needs of a layer's weights, no device
+static int conv_tiling(ConvWeights* cw, int cout, int cin, int ks, int stride) {
   EIOKU_REQUIRE(cout > 0 && cin > 0, "bad conv shape cout=%d cin=%d", cout, cin);
   EIOKU_REQUIRE(ks == 1 || ks == 3, "kernel size %d not supported (1 or 3)", ks);
   EIOKU_REQUIRE((stride == 1) || (stride == 2 && ks == 3), "stride %d with k=%d not supported", stride, ks);
@@ -2221,8 +2048,14 @@ int conv_weights_create(ConvWeights* cw, int cout, int cin, int ks, int stride, 
   cw->stride = stride;
   cw->nchunks = (cin + 31) / 32;
   cw->nf = pick_nf(cout, ks, cw->nchunks, stride);
+  cw->ntiles = (cout + 16 * cw->nf - 1) / (16 * cw->nf);
+  return EIOKU_OK;
+}
+
+int conv_weights_create(ConvWeights* cw, int cout, int cin, int ks, int stride, const float* w,
+                        const float* b) {
+  EIOKU_TRY(conv_tiling(cw, cout, cin, ks, stride));
   const int tile = 16 * cw->nf;
-  cw->ntiles = (cout + tile - 1) / tile;
   const int taps = ks * ks;
   const size_t wn = (size_t)cw->ntiles * cw->nchunks * taps * tile * 32;
   std::vector<_Float16> pw(wn, (_Float16)0.f);
@@ -2277,9 +2110,7 @@ bool conv_post_ok(const ConvWeights& cw, const ConvWeights& post) {
   const bool shape = cw.ks == 3 && cw.cin != 8 && cw.nchunks <= 2 && cw.ntiles == 1 && cw.cout == 16 * cw.nf &&
                      (cw.nf == 2 || cw.nf == 4) && post.ks == 1 && post.cin == cw.cout && post.ntiles == 1 &&
                      post.nf == cw.nf && post.cout == 16 * post.nf;
-  if (!shape) return false;
-  const size_t extra = ((size_t)((cw.nf + 1) / 2) * 16 * cw.nf * 4 + 4 * 32 * 2 * cw.nf) * 16;
-  return persist_lds(cw.nf, cw.stride, cw.nchunks, false) + extra <= 150 * 1024;
+  return shape && lds_bytes(persist_layout(cw.nf, cw.stride, cw.nchunks, false, true).total) <= 150 * 1024;
 }
 
 // The 64-channel pairs run as two launches: a one-launch kernel with the weights in registers (r3) was measured slower
@@ -2329,6 +2160,34 @@ void set_extents(ConvArgs& a, Slice in, Slice res, Slice out, const float* out_f
   a.x_in2 = up ? ext_of(up->src.ptr, (size_t)a.N * (a.H / 2) * (a.W / 2) * up->src.cstride * 2) : BcExt{};
   a.x_img = fused ? ext_of(fused->bgr, (size_t)a.N * fused->src_h * fused->src_w * 3) : BcExt{};
 }
+// What every launch of the family is told: layer `cw` on N x H x W input pixels read from `in` and, where a second layer
+// `post` runs in the same launch, that layer and its output slice.  Everything else is zero until a caller sets it.
+ConvArgs conv_args(const ConvWeights& cw, Slice in, int N, int H, int W, int act, const ConvWeights* post, Slice post_out,
+                   int post_act) {
+  ConvArgs a{};
+  a.in = in.ptr ? in.ptr + in.coff : nullptr;
+  a.in_cs = in.cstride;
+  a.wgt = reinterpret_cast<const uint4*>(cw.d_w.p);
+  a.bias = cw.d_b;
+  a.N = N;
+  a.H = H;
+  a.W = W;
+  a.Cin = cw.cin;
+  a.Ho = conv_out_dim(H, cw.ks, cw.stride);
+  a.Wo = conv_out_dim(W, cw.ks, cw.stride);
+  a.Cout = cw.cout;
+  a.tiles_w = (a.Wo + kTW - 1) / kTW;
+  a.tiles_h = (a.Ho + kTH - 1) / kTH;
+  a.nchunks = cw.nchunks;
+  a.act = act;
+  a.post_w = post ? reinterpret_cast<const uint4*>(post->d_w.p) : nullptr;
+  a.post_bias = post ? post->d_b.p : nullptr;
+  a.post_out = post && post_out.ptr ? post_out.ptr + post_out.coff : nullptr;
+  a.post_out_cs = post_out.cstride;
+  a.post_cout = post ? post->cout : 0;
+  a.post_act = post_act;
+  return a;
+}
 }  // namespace
 
 int conv_chain_forward(const ConvWeights& ca, const ConvWeights& cb, Slice in, int N, int H, int W, Slice out,
@@ -2345,30 +2204,9 @@ int conv_chain_forward(const ConvWeights& ca, const ConvWeights& cb, Slice in, i
                     (long long)N * H * W * (out.cstride > cat_out.cstride ? out.cstride : cat_out.cstride) < (1ll << 31) &&
                     (long long)N * H * W * cat_in.cstride < (1ll << 31),
                 "tensor exceeds 32-bit element offsets -- split the batch");
-  ConvArgs a{};
-  a.in = in.ptr + in.coff;
-  a.wgt = reinterpret_cast<const uint4*>(ca.d_w.p);
-  a.bias = ca.d_b;
+  ConvArgs a = conv_args(ca, in, N, H, W, act_a, &cb, out, act_b);
   a.res = residual ? a.in : nullptr;  // the Bottleneck's shortcut is its own input: read from the staged patch
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.Cin = ca.cin;
-  a.in_cs = in.cstride;
-  a.Ho = H;
-  a.Wo = W;
-  a.Cout = ca.cout;
   a.res_cs = in.cstride;
-  a.tiles_w = (W + kTW - 1) / kTW;
-  a.tiles_h = (H + kTH - 1) / kTH;
-  a.nchunks = 1;
-  a.act = act_a;
-  a.post_w = reinterpret_cast<const uint4*>(cb.d_w.p);
-  a.post_bias = cb.d_b;
-  a.post_out = out.ptr ? out.ptr + out.coff : nullptr;
-  a.post_out_cs = out.cstride;
-  a.post_cout = cb.cout;
-  a.post_act = act_b;
   ChainCat cc{};
   if (cat_w) {
     cc.w = reinterpret_cast<const uint4*>(cat_w->d_w.p);
@@ -2384,15 +2222,13 @@ int conv_chain_forward(const ConvWeights& ca, const ConvWeights& cb, Slice in, i
   a.x_in = a.x_res = ext_of(in.ptr, (size_t)N * H * W * in.cstride * 2);
   a.x_out = ext_of(out.ptr, (size_t)N * H * W * out.cstride * 2);
   prof_start(EIOKU_PROF_CONV, stream);
-  // (a second patch buffer was measured against an extra workgroup per CU: 77 vs 69 us at 160^2; single-buffered it is)
-  int rc;
-  if (cat_w) {
-    const int cat = chain_cat_chunks(ca, *cat_w);
-    rc = cat == 1 ? launch_chain<1, false, 1, 2>(a, cc, stream)
-                  : (cat == 2 ? launch_chain<2, false, 2, 4>(a, cc, stream) : launch_chain<2, false, 3, 4>(a, cc, stream));
-  }
-  else if (ca.nf == 1) rc = launch_chain<1, false>(a, cc, stream);
-  else rc = launch_chain<2, false>(a, cc, stream);
+  // NF, CAT and the closing 1x1's NF of the five instantiations (chain_cat_chunks admits no other)
+  const int cat = cat_w ? chain_cat_chunks(ca, *cat_w) : 0;
+  int rc = EIOKU_OK;
+  with_const<112, 224, 234, 102, 202>(ca.nf * 100 + cat * 10 + (cat ? cat_w->nf : 2), [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    return rc = launch_chain<K / 100, K / 10 % 10, K % 10>(a, cc, stream), true;
+  });
   prof_stop(EIOKU_PROF_CONV, stream);
   return rc;
 }
@@ -2418,57 +2254,37 @@ int conv_stem_chain_forward(const ConvWeights& stem, const ConvWeights& c1, cons
   EIOKU_REQUIRE(out.ptr && out.cstride % 4 == 0 && out.coff % 4 == 0, "bad output slice");
   if (N == 0) return EIOKU_OK;
   EIOKU_REQUIRE((long long)N * (H / 4) * (W / 4) * out.cstride < (1ll << 31), "tensor exceeds 32-bit element offsets -- split the batch");
-  ConvArgs a{};
-  a.wgt = reinterpret_cast<const uint4*>(c1.d_w.p);
-  a.bias = c1.d_b;
-  a.N = N;
-  a.H = conv_out_dim(H, 3, 2);  // model.1's input = the stem's output map
-  a.W = conv_out_dim(W, 3, 2);
-  a.Cin = c1.cin;
-  a.Ho = conv_out_dim(a.H, 3, 2);
-  a.Wo = conv_out_dim(a.W, 3, 2);
-  a.Cout = c1.cout;
-  a.tiles_w = (a.Wo + kTW - 1) / kTW;
-  a.tiles_h = (a.Ho + kTH - 1) / kTH;
-  a.nchunks = 1;
-  a.act = act1;
-  a.post_w = reinterpret_cast<const uint4*>(post.d_w.p);
-  a.post_bias = post.d_b;
-  a.post_out = out.ptr + out.coff;
-  a.post_out_cs = out.cstride;
-  a.post_cout = post.cout;
-  a.post_act = act2;
+  // model.1's input = the stem's output map
+  ConvArgs a = conv_args(c1, Slice{}, N, conv_out_dim(H, 3, 2), conv_out_dim(W, 3, 2), act1, &post, out, act2);
   a.x_out = ext_of(out.ptr, (size_t)N * a.Ho * a.Wo * out.cstride * 2);
   a.x_img = ext_of(f.bgr, (size_t)N * f.src_h * f.src_w * 3);
   StemArgs st{reinterpret_cast<const uint4*>(stem.d_w.p), stem.d_b, act0, H, W};
   FusedSrc fs{f.bgr, f.src_h, f.src_w, f.new_h, f.new_w, f.top, f.left, f.step, f.off};
-  static bool attr_set = false;
-  if (!attr_set) {
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_stem_chain<0>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStemChainLds));
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_stem_chain<1>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStemChainLds));
-    EIOKU_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_stem_chain<2>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStemChainLds));
-    attr_set = true;
-  }
   const int total = a.tiles_w * a.tiles_h * N;
-  const int per_cu = (int)(150 * 1024 / kStemChainLds);
-  int bx = num_cus() * per_cu;
-  if (bx > total) bx = total;
+  // as many workgroups as fit 150 KB of a CU's LDS, no occupancy clamp
+  const dim3 grid(persistent_grid(wg_per_cu(150 * 1024, kStemChainLds, 1 << 30), 1, total));
   prof_start(EIOKU_PROF_CONV, stream);
-  route_hit(route_id(kRouteStemChain, f.mode == 2 ? 2 : (f.step > 1 ? 1 : 0)));
-  if (f.mode == 2) hipLaunchKernelGGL(k_conv_stem_chain<2>, dim3((unsigned)bx), dim3(256), kStemChainLds, stream, a, st, fs, total);
-  else if (f.step > 1) hipLaunchKernelGGL(k_conv_stem_chain<1>, dim3((unsigned)bx), dim3(256), kStemChainLds, stream, a, st, fs, total);
-  else hipLaunchKernelGGL(k_conv_stem_chain<0>, dim3((unsigned)bx), dim3(256), kStemChainLds, stream, a, st, fs, total);
-  EIOKU_LAUNCH_CHECK();
+  int rc = EIOKU_OK;
+  with_const<0, 1, 2>(f.mode == 2 ? 2 : (f.step > 1 ? 1 : 0), [&](auto mode) {
+    constexpr int MODE = decltype(mode)::value;
+    return rc = launch_kernel<k_conv_stem_chain<MODE>>(route_id(kRouteStemChain, MODE), grid, 256, kStemChainLds, stream, a, st, fs, total), true;
+  });
   prof_stop(EIOKU_PROF_CONV, stream);
-  return EIOKU_OK;
+  return rc;
 }
 
 bool fused_input_ok(const ConvWeights& cw, const FusedInput& f, Slice res, const float* out_f32) {
   return cw.ks == 3 && cw.cin == 8 && cw.stride == 2 && cw.nf <= 5 && !res.ptr && !out_f32 && (f.mode == 0 || f.mode == 2) &&
          f.bgr != nullptr;
+}
+
+// element offsets are 32-bit in every kernel: input, output and residual tensors of pixels x channel stride elements
+static int conv_fits_32bit(const ConvWeights& cw, int N, int H, int W, int in_cs, int out_cs, int res_cs) {
+  const long long px_in = (long long)N * H * W, px_out = (long long)N * conv_out_dim(H, cw.ks, cw.stride) * conv_out_dim(W, cw.ks, cw.stride);
+  EIOKU_REQUIRE(px_in * (in_cs > 8 ? in_cs : 8) < (1ll << 31) && px_out * (out_cs > 1 ? out_cs : 1) < (1ll << 31) &&
+                    px_out * (res_cs > 1 ? res_cs : 1) < (1ll << 31),
+                "tensor of %lld pixels exceeds the kernels' 32-bit element offsets -- split the batch", px_in);
+  return EIOKU_OK;
 }
 
 int conv_forward(const ConvWeights& cw, Slice in, int N, int H, int W, Slice out, float* out_f32,
@@ -2490,102 +2306,36 @@ int conv_forward(const ConvWeights& cw, Slice in, int N, int H, int W, Slice out
   EIOKU_REQUIRE(!res.ptr || cw.cout < 4 || (res.cstride % 4 == 0 && res.coff % 4 == 0),
                 "residual slice must be 4-channel aligned");
   if (N == 0) return EIOKU_OK;
-  {
-    const long long px_in = (long long)N * H * W, px_out = (long long)N * conv_out_dim(H, cw.ks, cw.stride) * conv_out_dim(W, cw.ks, cw.stride);
-    const int ocs = out_f32 ? cw.cout : out.cstride;
-    EIOKU_REQUIRE(px_in * (in.cstride > 8 ? in.cstride : 8) < (1ll << 31) && px_out * (ocs > 1 ? ocs : 1) < (1ll << 31) &&
-                      px_out * (res.cstride > 1 ? res.cstride : 1) < (1ll << 31),
-                  "tensor of %lld pixels exceeds the kernels' 32-bit element offsets -- split the batch", px_in);
+  EIOKU_TRY(conv_fits_32bit(cw, N, H, W, in.cstride, out_f32 ? cw.cout : out.cstride, res.cstride));
+  // the letterbox a fused stem reads: its geometry and which of k_conv3x3_c8's staging loops (SRC) can read it
+  FusedSrc fs{};
+  int src = 0;
+  if (fused) {
+    fs = FusedSrc{fused->bgr, fused->src_h, fused->src_w, fused->new_h, fused->new_w, fused->top, fused->left,
+                  fused->mode == 0 ? fused->step : 1, fused->mode == 0 ? fused->off : 0};
+    src = fused->mode == 0 ? 1 : 2;
+    // copy mode with 4-pixel aligned rows and padding: 12-byte group loads instead of byte loads
+    if (src == 1 && fused->step == 1 && fused->src_w % 4 == 0 && fused->left % 4 == 0 && fused->new_w % 4 == 0 && W % 4 == 0 &&
+        ((uintptr_t)fused->bgr & 3) == 0)
+      src = 3;
   }
-  ConvArgs a;
-  a.in = in.ptr ? in.ptr + in.coff : nullptr;
-  a.wgt = reinterpret_cast<const uint4*>(cw.d_w.p);
-  a.bias = cw.d_b;
-  a.out = out.ptr ? out.ptr + out.coff : nullptr;
+  const ConvPlan p = plan_conv(PlanLayer{cw.ks, cw.stride, cw.cin, cw.cout, cw.nf, cw.nchunks, N, H, W, in.cstride, res.ptr != nullptr,
+                                         out_f32 != nullptr, post != nullptr, up != nullptr, clsmax != nullptr, fused != nullptr, src});
+  EIOKU_REQUIRE(p.ok(), "%s", p.err);
+  ConvArgs a = conv_args(cw, in, N, H, W, act, post, out, post_act);
+  a.out = out.ptr ? out.ptr + out.coff : nullptr;  // with `post`: the 1x1's output slice (conv_args' post_out)
   a.out_f32 = out_f32;
   a.res = res.ptr ? res.ptr + res.coff : nullptr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.Cin = cw.cin;
-  a.in_cs = in.cstride;
-  a.Ho = conv_out_dim(H, cw.ks, cw.stride);
-  a.Wo = conv_out_dim(W, cw.ks, cw.stride);
-  a.Cout = cw.cout;
   a.out_cs = out.cstride;
   a.res_cs = res.cstride;
-  a.tiles_w = (a.Wo + kTW - 1) / kTW;
-  a.tiles_h = (a.Ho + kTH - 1) / kTH;
-  a.nchunks = cw.nchunks;
-  a.act = act;
   a.epi = conv_epi_on() ? 1 : 0;
-  a.post_w = post ? reinterpret_cast<const uint4*>(post->d_w.p) : nullptr;
-  a.post_bias = post ? post->d_b.p : nullptr;
-  a.post_out = post ? a.out : nullptr;  // `out` is the 1x1's output slice
-  a.post_out_cs = out.cstride;
-  a.post_cout = post ? post->cout : 0;
-  a.post_act = post_act;
   a.clsmax = clsmax;
   a.in2 = up ? up->src.ptr + up->src.coff : nullptr;
   a.in2_cs = up ? up->src.cstride : 0;
   a.c_split = up ? up->c_split : 0;
   set_extents(a, in, res, out, out_f32, clsmax, up, fused);
   prof_start(EIOKU_PROF_CONV, stream);
-  int rc = EIOKU_OK;
-  bool handled = false;
-  if (cw.ks == 3 && cw.cin == 8 && cw.stride == 2 && !res.ptr && !out_f32) {
-    FusedSrc fs{};
-    int src = 0;
-    if (fused) {
-      fs = FusedSrc{fused->bgr, fused->src_h, fused->src_w, fused->new_h, fused->new_w, fused->top, fused->left,
-                    fused->mode == 0 ? fused->step : 1, fused->mode == 0 ? fused->off : 0};
-      src = fused->mode == 0 ? 1 : 2;
-      // copy mode with 4-pixel aligned rows and padding: 12-byte group loads instead of byte loads
-      if (src == 1 && fused->step == 1 && fused->src_w % 4 == 0 && fused->left % 4 == 0 && fused->new_w % 4 == 0 && W % 4 == 0 &&
-          ((uintptr_t)fused->bgr & 3) == 0)
-        src = 3;
-    }
-    rc = launch_c8_dispatch<2>(cw.nf, src, a, fs, cw.ntiles, stream, &handled);
-  }
-  if (!handled && fused) {
-    set_error("no fused-input kernel for this stem (nf %d)", cw.nf);
-    rc = EIOKU_EINVAL;
-    handled = true;
-  }
-  // maps too small for 8x16 tiles (20x20: 52 % of a tiling is outside the map): flattened-pixel tiles whatever
-  // the depth.  Measured: 80->80 @20 19.8 -> 13.8 us, 64->64 @20 13.2 -> 10.5; at 40x40 resident weights still
-  // win (64->64 20.7 vs 25.8 us), hence the 24-pixel cut.
-  constexpr int flat_wo = 24;
-  if (!handled && cw.ks == 3 && cw.nchunks >= 2 && cw.nchunks <= 3 && a.Wo <= flat_wo)
-    rc = cw.stride == 1 ? launch_flat_dispatch<1>(cw.nf, a, cw.ntiles, stream, &handled)
-                        : launch_flat_dispatch<2>(cw.nf, a, cw.ntiles, stream, &handled);
-  if (!handled && post) {
-    const size_t extra = ((size_t)((cw.nf + 1) / 2) * 16 * cw.nf * 4 + 4 * 32 * 2 * cw.nf) * 16;
-    const bool db = persist_lds(cw.nf, cw.stride, cw.nchunks, true) + extra <= 75 * 1024;
-    rc = cw.stride == 1 ? launch_persist_post_dispatch<1>(cw.nf, cw.nchunks, db, a, stream, &handled)
-                        : launch_persist_post_dispatch<2>(cw.nf, cw.nchunks, db, a, stream, &handled);
-    if (!handled) {
-      set_error("no fused 3x3+1x1 kernel for nf %d nchunks %d", cw.nf, cw.nchunks);
-      rc = EIOKU_EINVAL;
-      handled = true;
-    }
-  }
-  if (!handled && cw.ks == 3 && cw.nchunks <= 3) {
-    // double-buffer the patch only when that still leaves two workgroups per CU
-    const bool db = persist_lds(cw.nf, cw.stride, cw.nchunks, true) <= 75 * 1024;
-    if (persist_lds(cw.nf, cw.stride, cw.nchunks, db) <= 150 * 1024)
-      rc = cw.stride == 1 ? launch_persist_dispatch<1>(cw.nf, cw.nchunks, db, a, cw.ntiles, stream, &handled)
-                          : launch_persist_dispatch<2>(cw.nf, cw.nchunks, db, a, cw.ntiles, stream, &handled);
-  }
-  // (YOLOv8m's 96 / 192-channel stride-2 convs at 80 / 40-wide maps have no persistent instantiation and fall through to
-  // the generic kernel, 200 TFLOP/s; sending them here with 16 staging slots measured the same: 370 vs 404 us)
-  if (!handled && cw.ks == 3 && cw.nchunks > 3 && a.Wo <= 48)
-    rc = cw.stride == 1 ? launch_flat_dispatch<1>(cw.nf, a, cw.ntiles, stream, &handled)
-                        : launch_flat_dispatch<2>(cw.nf, a, cw.ntiles, stream, &handled);
-  if (handled) {
-  } else if (cw.ks == 3 && cw.stride == 1) rc = launch_nf<3, 1>(cw.nf, a, cw.ntiles, stream);
-  else if (cw.ks == 3 && cw.stride == 2) rc = launch_nf<3, 2>(cw.nf, a, cw.ntiles, stream);
-  else rc = launch1x1_nf(cw.nf, a, cw.ntiles, stream);
+  const int rc = launch_plan(p, a, fs, cw.ntiles, stream);
   prof_stop(EIOKU_PROF_CONV, stream);
   return rc;
 }
@@ -2661,14 +2411,13 @@ int eioku_debug_conv_routes(char* buf, size_t cap, int reset) {
                                : g_route_counts[base + i].load(std::memory_order_relaxed);
       if (!c || !buf) continue;
       char line[160];
-      int n = snprintf(line, sizeof line, "%s", d.name);
       int vals[6], rest = i;
       for (int f = d.nfields - 1; f >= 0; --f) {
         vals[f] = rest % d.radix[f];
         rest /= d.radix[f];
       }
-      for (int f = 0; f < d.nfields; ++f) n += snprintf(line + n, sizeof line - n, "%s%s%d", f ? "," : "<", d.field[f], vals[f]);
-      n += snprintf(line + n, sizeof line - n, "%s %u\n", d.nfields ? ">" : "", c);
+      int n = route_name(line, sizeof line, fam, vals);
+      n += snprintf(line + n, sizeof line - n, " %u\n", c);
       if (pos + (size_t)n + 1 > cap) {
         fits = false;
         continue;
@@ -2687,6 +2436,26 @@ int eioku_debug_conv_routes(char* buf, size_t cap, int reset) {
 int eioku_debug_conv_epi(int* launches, int reset) {
   EIOKU_REQUIRE(launches, "NULL argument");
   *launches = (int)(reset ? g_epi_launches.exchange(0u, std::memory_order_relaxed) : g_epi_launches.load(std::memory_order_relaxed));
+  return EIOKU_OK;
+}
+
+// The plan of one layer as eioku_conv2d_f16 would run it on dense tensors: the route in the route log's format and the
+// dynamic LDS bytes of the launch, or the error that call would end with.  Host arithmetic only: needs no device and no
+// eioku_init.
+int eioku_debug_conv_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int has_residual, int out_f32,
+                          char* route, size_t cap, size_t* lds_bytes) {
+  EIOKU_REQUIRE(route && cap > 0 && lds_bytes, "NULL output");
+  EIOKU_REQUIRE(n > 0 && h > 0 && w > 0, "empty tensor n=%d h=%d w=%d", n, h, w);
+  ConvWeights cw;
+  EIOKU_TRY(conv_tiling(&cw, cout, cin, ksize, stride));
+  EIOKU_TRY(conv_fits_32bit(cw, n, h, w, cin, cout, has_residual ? cout : 0));
+  const ConvPlan p = plan_conv(PlanLayer{ksize, stride, cin, cout, cw.nf, cw.nchunks, n, h, w, cin, has_residual != 0, out_f32 != 0,
+                                         false, false, false, false, 0});
+  EIOKU_REQUIRE(p.ok(), "%s", p.err);
+  char name[160];
+  EIOKU_REQUIRE((size_t)route_name(name, sizeof name, p.family, p.t) < cap, "route name does not fit %zu bytes", cap);
+  strcpy(route, name);
+  *lds_bytes = p.lds;
   return EIOKU_OK;
 }
 

@@ -58,6 +58,17 @@ def conv_routes(reset: bool = False) -> dict[str, int]:
     return routes
 
 
+def conv_plan(n: int, h: int, w: int, cin: int, cout: int, k: int, stride: int, *, residual: bool = False,
+              out_f32: bool = False) -> tuple[str, int]:
+    """(route, dynamic LDS bytes) ``conv2d_f16`` would launch for a dense layer of this shape, decided on the host
+    (``eioku_debug_conv_plan``): no launch, no device.  Raises ``EiokuHipError`` where ``conv2d_f16`` would."""
+    buf = C.create_string_buffer(160)
+    lds = C.c_size_t(0)
+    _lib.check(_lib.load().eioku_debug_conv_plan(n, h, w, cin, cout, k, stride, int(residual), int(out_f32), buf, len(buf),
+                                                 C.byref(lds)), "eioku_debug_conv_plan")
+    return buf.value.decode(), lds.value
+
+
 def conv_epi_launches(reset: bool = False) -> int:
     """Launches of k_conv3x3_flat in this process since the last reset that took the straight-line epilogue on at least
     their first cout tile (``eioku_debug_conv_epi``); 0 with ``EIOKU_CONV_EPI=0``."""

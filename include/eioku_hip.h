@@ -177,6 +177,12 @@ int eioku_debug_bounds(int* violations, int* line, int reset, int selftest);
  * the NUL-terminated text (EIOKU_EINVAL when cap is too small; buf NULL with cap 0 only resets); reset != 0 clears the
  * counters after reading them.  Thread safe; needs no eioku_init. */
 int eioku_debug_conv_routes(char* buf, size_t cap, int reset);
+/* The plan of one layer as eioku_conv2d_f16 would run it on dense tensors of this shape (with / without a residual, fp16 or
+ * fp32 output): `route` receives the instantiation in the route log's format ("persist<NF3,S1,NCH3,DB0,POST0,NWV8>"),
+ * *lds_bytes the dynamic LDS of its launch.  A shape no kernel runs returns the error eioku_conv2d_f16 would return and
+ * no route.  Host arithmetic only: launches nothing, needs no device and no eioku_init. */
+int eioku_debug_conv_plan(int n, int h, int w, int cin, int cout, int ksize, int stride, int has_residual, int out_f32,
+                          char* route, size_t cap, size_t* lds_bytes);
 /* k_conv3x3_flat launches since the last reset whose straight-line epilogue (EIOKU_CONV_EPI) ran on at least the first cout tile */
 int eioku_debug_conv_epi(int* launches, int reset);
 

@@ -2,8 +2,9 @@
 same fp16-rounded operands.  Tolerance: the fp32 accumulation order differs (MFMA vs CPU), and the
 result is rounded to fp16 once, so outputs agree to 1 fp16 ulp (rel 2**-10) + tiny absolute slack.
 
-Which ``__global__`` instantiation a shape runs on is decided on the host (pick_nf, conv_forward, the launch_*_dispatch
-functions).  Every case here names the instantiation ("route") it is there for, and the test reads the route back from
+Which ``__global__`` instantiation a shape runs on is decided on the host (pick_nf and plan_conv of csrc/conv_plan.h;
+tests/test_conv_plan_host.py holds the plan to this file's table without a GPU).  Every case here names the
+instantiation ("route") it is there for, and the test reads the route back from
 the launch code's own log (``ops.conv_routes``): a retune that moves a shape elsewhere fails with both names instead
 of leaving an instantiation untested."""
 import numpy as np
@@ -156,6 +157,37 @@ def test_conv_matches_torch_cpu(gpu, n, h, w, cin, cout, k, stride):
     frac = bar_fraction(got, want)
     print(f"{ROUTE_OF[case]} {case}: worst error {frac:.3f} of the bar")
     assert frac <= 1.0, float(np.abs(got.astype(np.float32) - want.astype(np.float32)).max())
+
+
+# ---- one instantiation whose LDS size varies at run time: below the 64 KB default, above it, below it again --------------
+# (route, small layer, large layer).  The launch code lifts a kernel's dynamic-LDS ceiling once per larger request and keeps
+# it; the sizes come from the plan (ops.conv_plan), so the cases stay on either side of 64 KB or fail saying so.  1x1: 6 KB
+# and 108 KB of weights.  flat: no smaller pair exists on one instantiation -- the large layer's three 1 x 48 frames make
+# the 9-row patch of a tile that crosses two frame borders, 192 bytes above 64 KB.
+LDS_STEPS = [
+    ("1x1<NF3,UP0,NWV4,CLSMAX0>", (1, 7, 9, 40, 48, 1, 1), (1, 7, 9, 1152, 576, 1, 1)),
+    ("flat<NF4,S1,MT2,NS8>", (2, 24, 24, 104, 64, 3, 1), (3, 1, 48, 104, 64, 3, 1)),
+]
+
+
+@pytest.mark.parametrize("route,small,large", LDS_STEPS, ids=[s[0] for s in LDS_STEPS])
+def test_lds_ceiling_follows_small_large_small_launches(gpu, route, small, large):
+    import torch
+
+    assert ops.conv_plan(*small)[0] == route and ops.conv_plan(*small)[1] <= 64 * 1024
+    assert ops.conv_plan(*large)[0] == route and ops.conv_plan(*large)[1] > 64 * 1024
+    want = {}
+    for case in (small, large, small):
+        stride = case[6]
+        x, wgt, b = operands(case, 77)
+        if case not in want:
+            want[case] = ref_conv(x, wgt, b, stride, True)
+        ops.conv_routes(reset=True)
+        got = ops.conv2d_f16(torch.from_numpy(x).to(gpu), wgt, b, stride=stride, silu=True).cpu().numpy()
+        assert ops.conv_routes(reset=True) == {route: 1}
+        frac = bar_fraction(got, want[case])
+        print(f"{route} {case} ({ops.conv_plan(*case)[1]} B of LDS): worst error {frac:.3f} of the bar")
+        assert got.shape == want[case].shape and frac <= 1.0
 
 
 # ---- epilogues, slices and canaries ----------------------------------------------------------------------------------
