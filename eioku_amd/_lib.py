@@ -277,6 +277,22 @@ SIGNATURES = {
     "eioku_spk_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "eioku_spk_assign": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                    C.c_void_p]),
+    "eioku_timesformer_create": (C.c_int, [C.c_int] * 8 + [C.c_float, C.POINTER(C.c_void_p)]),
+    "eioku_timesformer_destroy": (None, [C.c_void_p]),
+    "eioku_timesformer_num_tensors": (C.c_int, [C.c_void_p]),
+    "eioku_timesformer_tensor_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int)]),
+    "eioku_timesformer_set_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "eioku_timesformer_set_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_timesformer_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_timesformer_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_timesformer_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p]),
+    "eioku_timesformer_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_timesformer_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_timesformer_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 

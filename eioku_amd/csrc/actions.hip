@@ -1,0 +1,835 @@
+// K25: action recognition on gfx950 - TimeSformer with divided space-time attention (DESIGN.md "K25 action recognition").
+//   k_clip_resize_h / k_clip_resize_v   Pillow's two-pass 8-bit bilinear resample of the centre-crop region only (22-bit
+//                       fixed-point taps from the host, uint8 rounding between the passes), then BGR -> RGB,
+//                       (v * (1 / 255) - mean) / std in fp32 and one rounding to fp16, written as patch rows
+//                       [clip][patch][frame][c * 256 + ky * 16 + kx]: the patch embedding is one GEMM, no im2col pass
+//   k_gemm<., EPI_POS>  (gemm_f16.h) patch projection + bias + (position + time) table into the fp32 residual stream
+//   k_ln_eps            LayerNorm with an eps argument, fp32 row -> fp16
+//   k_attn_time         temporal attention: T <= 96 keys of one (clip, patch, head) per one-wave workgroup, q / k / v in LDS,
+//                       fp32 scores
+//   k_attn_space        spatial attention: 1 + P keys of one (clip, frame, head); 64 queries per workgroup, keys / values
+//                       staged through LDS 128 at a time, QK^T and PV on v_mfma_f32_16x16x32_f16 with an online softmax
+//   k_cls_mean          the CLS rule: mean over the frames (t = 0 .. T - 1, fp32) of the projected CLS outputs, added to CLS
+//   k_action_head       softmax and top-k of the logits, ties to the smaller class index
+// Residual stream x, fp32: the B P T patch rows first, row (b P + p) T + t, then the B CLS rows.  The temporal GEMMs see the
+// first B P T rows as one dense matrix, the spatial qkv and the MLP all B (P T + 1) rows; the CLS row of a clip goes
+// through LayerNorm and qkv once for all its T frames.
+// Precision points (tests/actions_oracle.py, fp16=True, rounds at the same places): linear / conv weights fp16; biases,
+// LayerNorm parameters and the embedding tables fp32; the residual stream fp32; LayerNorm outputs, q / k / v, attention
+// outputs, the temporal out-projection, GELU outputs and the patch rows are rounded to fp16; the spatial kernel rounds
+// its softmax numerators exp(s - max) to fp16 for the PV MFMA.
+#include "common.h"
+#include "gemm_f16.h"
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace eioku;
+
+namespace {
+
+constexpr int kPrec = 22;      // Pillow Resample.c PRECISION_BITS for 8-bit pixels
+constexpr int kPatch = 16, kPatchK = 3 * kPatch * kPatch;
+constexpr int kMaxFrames = 96, kMaxImage = 448;
+constexpr int kKC = 128;       // keys per LDS stage of k_attn_space
+constexpr int kKStride = 72;   // halfs per staged key row (64 + 8: 144 B, 16-byte aligned, spreads the banks)
+constexpr int kVStride = kKC + 2;  // halfs per staged value column (65 words: a column starts one bank after its neighbour)
+
+// ---- clip preprocessing ---------------------------------------------------------------------------------------------------
+// bounds [S][2] = {first input index, taps}; kk [S][ksize] int32 taps scaled by 2^22: the rows of Pillow's tables for the
+// resized axis that the centre crop keeps.  horizontal: src [N][h][w][3] u8, rows y0 .. y0 + rows - 1 only -> tmp
+// [N][rows][S][3] u8; one thread per (row, output column)
+__global__ __launch_bounds__(256) void k_clip_resize_h(const uint8_t* __restrict__ src, int N, int h, int w, int y0, int rows, int S,
+                                                       const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
+                                                       uint8_t* __restrict__ tmp) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)N * rows * S) return;
+  const int xx = (int)(i % S);
+  const long long row = i / S;
+  const int y = (int)(row % rows), n = (int)(row / rows);
+  const int lo = bounds[2 * xx], cnt = bounds[2 * xx + 1];
+  const uint8_t* p = src + (((size_t)n * h + y0 + y) * w + lo) * 3;
+  int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
+  for (int t = 0; t < cnt; ++t) {
+    const int k = kk[xx * ksize + t];
+    s0 += p[3 * t] * k;
+    s1 += p[3 * t + 1] * k;
+    s2 += p[3 * t + 2] * k;
+  }
+  auto clip8 = [](int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); };
+  uint8_t* o = tmp + (size_t)i * 3;
+  o[0] = clip8(s0 >> kPrec);
+  o[1] = clip8(s1 >> kPrec);
+  o[2] = clip8(s2 >> kPrec);
+}
+
+struct Norm3 {
+  float mean[3], std[3];  // R, G, B
+};
+
+// vertical + rescale + normalise: tmp [N][rows][S][3] u8 (B, G, R), N = clips * T frames -> patches
+// [clip][patch][frame][c * 256 + ky * 16 + kx] fp16 (c = R, G, B) and / or out_u8 [N][S][S][3] (R, G, B)
+__global__ __launch_bounds__(256) void k_clip_resize_v(const uint8_t* __restrict__ tmp, int N, int T, int y0, int rows, int S,
+                                                       const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
+                                                       Norm3 nrm, h16* __restrict__ patches, uint8_t* __restrict__ out_u8) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)N * S * S) return;
+  const int x = (int)(i % S);
+  const int yy = (int)((i / S) % S);
+  const int n = (int)(i / ((long long)S * S));
+  const int lo = bounds[2 * yy] - y0, cnt = bounds[2 * yy + 1];
+  const uint8_t* p = tmp + (((size_t)n * rows + lo) * S + x) * 3;
+  int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
+  for (int t = 0; t < cnt; ++t) {
+    const int k = kk[yy * ksize + t];
+    s0 += p[(size_t)t * S * 3] * k;
+    s1 += p[(size_t)t * S * 3 + 1] * k;
+    s2 += p[(size_t)t * S * 3 + 2] * k;
+  }
+  auto clip8 = [](int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); };
+  const int rgb[3] = {clip8(s2 >> kPrec), clip8(s1 >> kPrec), clip8(s0 >> kPrec)};
+  if (out_u8) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out_u8[(size_t)i * 3 + c] = (uint8_t)rgb[c];
+  }
+  if (patches) {
+    const int side = S / kPatch, P = side * side, clip = n / T, t = n % T;
+    const int patch = (yy / kPatch) * side + x / kPatch;
+    h16* o = patches + (((size_t)clip * P + patch) * T + t) * kPatchK + (yy % kPatch) * kPatch + x % kPatch;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c * kPatch * kPatch] = (h16)(((float)rgb[c] * (1.0f / 255.0f) - nrm.mean[c]) / nrm.std[c]);
+  }
+}
+
+// ---- small kernels ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cvt_f16(const float* __restrict__ src, size_t n, h16* __restrict__ dst) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = (h16)src[i];
+}
+
+// the embedding tables the GEMM epilogue and the CLS rows read: postime[p T + t] = position[1 + p] + time[t],
+// cls = cls_token + position[0]
+__global__ __launch_bounds__(256) void k_embed_tables(const float* __restrict__ pos, const float* __restrict__ time,
+                                                      const float* __restrict__ cls_token, int P, int T, int d,
+                                                      float* __restrict__ postime, float* __restrict__ cls) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t n = (size_t)P * T * d;
+  if (i < n) {
+    const int c = (int)(i % d);
+    const size_t row = i / d;
+    const int t = (int)(row % T), p = (int)(row / T);
+    postime[i] = pos[(size_t)(1 + p) * d + c] + time[(size_t)t * d + c];
+  } else if (i < n + d) {
+    const int c = (int)(i - n);
+    cls[c] = cls_token[c] + pos[c];
+  }
+}
+
+// x[first + b][:] = cls[:] for b < B
+__global__ __launch_bounds__(256) void k_cls_rows(const float* __restrict__ cls, int B, int d, float* __restrict__ x) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < (size_t)B * d) x[i] = cls[i % d];
+}
+
+// LayerNorm: fp32 row -> fp16, one wave per row
+__global__ __launch_bounds__(256) void k_ln_eps(const float* __restrict__ x, int M, int d, const float* __restrict__ g,
+                                                const float* __restrict__ b, float eps, h16* __restrict__ out) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const float* xr = x + (size_t)row * d;
+  float s = 0.f;
+  for (int i = lane; i < d; i += 64) s += xr[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  const float mean = s / (float)d;
+  float q = 0.f;
+  for (int i = lane; i < d; i += 64) {
+    const float c = xr[i] - mean;
+    q += c * c;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  const float inv = 1.f / sqrtf(q / (float)d + eps);
+  for (int i = lane; i < d; i += 64) out[(size_t)row * d + i] = (h16)((xr[i] - mean) * inv * g[i] + b[i]);
+}
+
+// the CLS rule: x_cls[b] += (sum over t = 0 .. T - 1 of proj[b T + t]) / T, in fp32 and in frame order
+__global__ __launch_bounds__(256) void k_cls_mean(const float* __restrict__ proj, int B, int T, int d, float* __restrict__ x_cls) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)B * d) return;
+  const int c = (int)(i % d), b = (int)(i / d);
+  float s = 0.f;
+  for (int t = 0; t < T; ++t) s += proj[((size_t)b * T + t) * d + c];
+  x_cls[i] += s / (float)T;
+}
+
+// hidden_out [B][1 + P T][d] in the model's token order (CLS, then patch p at frame t in row 1 + p T + t) from the stream
+__global__ __launch_bounds__(256) void k_hidden_out(const float* __restrict__ x, int B, int PT, int d, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)B * (PT + 1) * d) return;
+  const int c = (int)(i % d);
+  const size_t row = i / d;
+  const int tok = (int)(row % (PT + 1)), b = (int)(row / (PT + 1));
+  const size_t src = tok == 0 ? (size_t)B * PT + b : (size_t)b * PT + tok - 1;
+  out[i] = x[src * d + c];
+}
+
+// ---- temporal attention -----------------------------------------------------------------------------------------------------
+// qkv [rows][3 d] fp16 (q | k | v, head h in columns 64 h .. 64 h + 63 of each third); sequence s = rows s T .. s T + T - 1.
+// grid (n_seq * heads), one wave = one (sequence, head).  q / k / v of the problem sit in LDS (rows of 66 halfs: lane j
+// reads key row j without bank conflicts); per query, lane j scores keys j and j + 64, the wave reduces max and sum, and
+// lane c accumulates output dimension c.  Dynamic LDS: 3 T 66 halfs + 96 floats (38.4 KB at T = 96).  out [rows][d] fp16.
+__global__ __launch_bounds__(64) void k_attn_time(const h16* __restrict__ qkv, int T, int heads, h16* __restrict__ out) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int head = (int)(blockIdx.x % heads);
+  const size_t row0 = (size_t)(blockIdx.x / heads) * T;
+  const int d = heads * 64;
+  h16* sq = reinterpret_cast<h16*>(smem_raw);
+  h16* sk = sq + T * 66;
+  h16* sv = sk + T * 66;
+  float* sp = reinterpret_cast<float*>(sv + T * 66);
+  for (int i = lane; i < 3 * T * 8; i += 64) {  // 16-byte pieces: (third, row, piece)
+    const int piece = i & 7, t = (i >> 3) % T, third = (i >> 3) / T;
+    const uint4 v = *reinterpret_cast<const uint4*>(qkv + (row0 + t) * 3 * d + (size_t)third * d + head * 64 + piece * 8);
+    unsigned* dst = reinterpret_cast<unsigned*>(sq + (third * T + t) * 66 + piece * 8);  // 4-byte aligned: 66 and 8 are even
+    dst[0] = v.x, dst[1] = v.y, dst[2] = v.z, dst[3] = v.w;
+  }
+  __syncthreads();
+  for (int qi = 0; qi < T; ++qi) {
+    float s[2], mx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int j = lane + 64 * e;
+      s[e] = -INFINITY;
+      if (j < T) {
+        float acc = 0.f;
+        for (int c = 0; c < 64; ++c) acc += (float)sq[qi * 66 + c] * (float)sk[j * 66 + c];
+        s[e] = acc * 0.125f;
+      }
+      mx = fmaxf(mx, s[e]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int j = lane + 64 * e;
+      if (j < T) {
+        const float p = expf(s[e] - mx);
+        sp[j] = p;
+        sum += p;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+    __syncthreads();
+    float o = 0.f;
+    for (int j = 0; j < T; ++j) o += sp[j] * (float)sv[j * 66 + lane];
+    out[(row0 + qi) * d + head * 64 + lane] = (h16)(o / sum);
+    __syncthreads();  // sp is rewritten by the next query
+  }
+}
+
+// ---- spatial attention ------------------------------------------------------------------------------------------------------
+// qkv [B P T + B][3 d] fp16 in the stream's row order.  Problem (b, t, head): token 0 is the clip's CLS row B P T + b, token
+// 1 + p the patch row (b P + p) T + t; n = 1 + P queries and keys.  grid (ceil(n / 64), heads, B T), 4 waves of 16 queries.
+// Keys and values go through LDS kKC at a time (keys [key][72], values transposed [dim][kKC + 2]).  Per 32 keys and wave:
+// S^T = K Q^T in two 16-key MFMA tiles (lane (r, u): query r, keys 4u .. 4u + 3 of each tile), the online softmax per
+// query across the lanes r, r + 16, r + 32, r + 48, then O^T += V^T P^T with the 32 keys in the order the lanes already
+// hold them (slot 8u + t: key 4u + t of the first tile, slot 8u + 4 + t: of the second), p = exp(s - max) rounded to fp16.
+// Patch outputs go to out_patch [B P T][d], the CLS output of frame t to out_cls [b T + t][d].
+__global__ __launch_bounds__(256) void k_attn_space(const h16* __restrict__ qkv, int B, int P, int T, int heads,
+                                                    h16* __restrict__ out_patch, h16* __restrict__ out_cls) {
+  __shared__ __align__(16) h16 sk[kKC * kKStride];
+  __shared__ __align__(16) h16 svt[64 * kVStride];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, u = lane >> 4;
+  const int head = blockIdx.y, b = blockIdx.z / T, t = blockIdx.z % T;
+  const int d = heads * 64, n = 1 + P;
+  const size_t ld = (size_t)3 * d;
+  auto token_row = [&](int tok) -> size_t { return tok == 0 ? (size_t)B * P * T + b : ((size_t)b * P + tok - 1) * T + t; };
+  const int q = blockIdx.x * 64 + wave * 16 + r;  // this lane's query token
+  half8 q0 = {}, q1 = {};
+  if (q < n) {
+    const h16* qr = qkv + token_row(q) * ld + head * 64 + 8 * u;
+    q0 = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(qr));
+    q1 = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(qr + 32));
+  }
+  float4v acc[4];
+#pragma unroll
+  for (int f = 0; f < 4; ++f) acc[f] = float4v{0.f, 0.f, 0.f, 0.f};
+  float mx = -INFINITY, sum = 0.f;  // sum: this lane's share, joined over u at the end
+  for (int k0 = 0; k0 < n; k0 += kKC) {
+    const int nk = n - k0 < kKC ? n - k0 : kKC, nk32 = (nk + 31) & ~31;
+    __syncthreads();  // the previous stage has been read
+    for (int i = threadIdx.x; i < nk32 * 8; i += 256) {
+      const int piece = i & 7, key = i >> 3;
+      uint4 kv = {0, 0, 0, 0}, vv = {0, 0, 0, 0};  // keys past the end: zeros (masked below; 0 * value adds nothing)
+      if (key < nk) {
+        const h16* row = qkv + token_row(k0 + key) * ld + head * 64 + piece * 8;
+        kv = *reinterpret_cast<const uint4*>(row + d);
+        vv = *reinterpret_cast<const uint4*>(row + 2 * d);
+      }
+      *reinterpret_cast<uint4*>(sk + key * kKStride + piece * 8) = kv;
+      const half8 vh = __builtin_bit_cast(half8, vv);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) svt[(piece * 8 + e) * kVStride + key] = vh[e];
+    }
+    __syncthreads();
+    for (int j0 = 0; j0 < nk32; j0 += 32) {
+      float4v s[2];
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const h16* kr = sk + (j0 + 16 * e + r) * kKStride + 8 * u;
+        const half8 ka = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(kr));
+        const half8 kb = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(kr + 32));
+        s[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka, q0, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        s[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kb, q1, s[e], 0, 0, 0);
+      }
+      float m_new = mx;
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int key = j0 + 16 * e + 4 * u + i;
+          s[e][i] = key < nk ? s[e][i] * 0.125f : -INFINITY;
+          m_new = fmaxf(m_new, s[e][i]);
+        }
+      m_new = fmaxf(m_new, __shfl_xor(m_new, 16, 64));
+      m_new = fmaxf(m_new, __shfl_xor(m_new, 32, 64));  // finite from the first 32 keys on: key 0 is never masked
+      const float alpha = expf(mx - m_new);
+      mx = m_new;
+      half8 p;
+      float ps = 0.f;
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const h16 ph = (h16)expf(s[e][i] - m_new);
+          p[4 * e + i] = ph;
+          ps += (float)ph;
+        }
+      sum = sum * alpha + ps;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        const h16* vr = svt + (16 * f + r) * kVStride + j0 + 4 * u;
+        const unsigned* va = reinterpret_cast<const unsigned*>(vr);  // 4-byte aligned: kVStride, j0 and 4u are even
+        const uint4 v4 = {va[0], va[1], va[8], va[9]};
+        acc[f] = acc[f] * alpha;
+        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, v4), p, acc[f], 0, 0, 0);
+      }
+    }
+  }
+  sum += __shfl_xor(sum, 16, 64);
+  sum += __shfl_xor(sum, 32, 64);
+  if (q >= n) return;
+  h16* o = (q == 0 ? out_cls + ((size_t)b * T + t) * d : out_patch + token_row(q) * d) + head * 64 + 4 * u;
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[16 * f + i] = (h16)(acc[f][i] / sum);
+}
+
+// ---- head ---------------------------------------------------------------------------------------------------------------
+// one workgroup per clip: probs = softmax(logits) in fp32 (each exponential and their sum computed in fp64 and rounded to
+// fp32 once, so neither depends on the order of the sum or on the exp of a math library; one fp32 division), then top_k
+// picks of the largest remaining probability, the smaller class index on a tie.  Dynamic LDS: nc floats.
+__global__ __launch_bounds__(256) void k_action_head(const float* __restrict__ logits, int nc, int top_k, float* __restrict__ prob_out,
+                                                     int* __restrict__ idx_out) {
+  extern __shared__ float s_p[];
+  __shared__ float s_f[4];
+  __shared__ double s_d[4];
+  __shared__ int s_i[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* lg = logits + (size_t)b * nc;
+  float m = -INFINITY;
+  for (int j = tid; j < nc; j += 256) m = fmaxf(m, lg[j]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if (lane == 0) s_f[wave] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(s_f[0], s_f[1]), fmaxf(s_f[2], s_f[3]));
+  double sum = 0.0;
+  for (int j = tid; j < nc; j += 256) {
+    const float e = (float)exp((double)(lg[j] - m));  // the correctly rounded fp32 exponential
+    s_p[j] = e;
+    sum += (double)e;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if (lane == 0) s_d[wave] = sum;
+  __syncthreads();
+  const float total = (float)((s_d[0] + s_d[1]) + (s_d[2] + s_d[3]));
+  for (int j = tid; j < nc; j += 256) s_p[j] = s_p[j] / total;
+  __syncthreads();
+  for (int k = 0; k < top_k; ++k) {
+    float bv = -1.f;  // below every probability; taken entries are set to -2
+    int bi = 0x7fffffff;
+    for (int j = tid; j < nc; j += 256) {
+      const float v = s_p[j];
+      if (v > bv) bv = v, bi = j;  // ascending j: the first of equal values stays
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
+    }
+    if (lane == 0) s_f[wave] = bv, s_i[wave] = bi;
+    __syncthreads();
+    bv = s_f[0], bi = s_i[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (s_f[w] > bv || (s_f[w] == bv && s_i[w] < bi)) bv = s_f[w], bi = s_i[w];
+    if (bi >= nc) bi = 0;  // NaN logits compare false everywhere
+    if (tid == 0) {
+      prob_out[(size_t)b * top_k + k] = bv;
+      idx_out[(size_t)b * top_k + k] = bi;
+      s_p[bi] = -2.f;
+    }
+    __syncthreads();
+  }
+}
+
+// ---- the model ------------------------------------------------------------------------------------------------------------
+enum { T_F16 = 0, T_F32 = 1 };
+
+struct Tensor {
+  std::string name;
+  int rows = 0, cols = 0, kind = T_F16;
+  DevBuf<uint8_t> dev;
+  bool set = false;
+  size_t numel() const { return (size_t)rows * cols; }
+};
+
+struct Lin { int w, b; };
+struct LNorm { int g, b; };
+struct Layer {
+  LNorm t_ln, s_ln, m_ln;
+  Lin t_qkv, t_out, t_dense, s_qkv, s_out, fc1, fc2;
+};
+
+}  // namespace
+
+struct eioku_timesformer {
+  int image = 0, frames = 0, d = 0, layers = 0, heads = 0, ffn = 0, labels = 0;
+  int side = 0, P = 0;
+  float eps = 1e-6f;
+  Norm3 nrm{{0.45f, 0.45f, 0.45f}, {0.225f, 0.225f, 0.225f}};
+  std::vector<Tensor> tensors;
+  std::vector<Layer> L;
+  int cls_token = 0, pos = 0, time = 0;
+  Lin proj{}, classifier{};
+  LNorm final_ln{};
+  bool tables_ready = false;
+  DevBuf<float> postime, cls;
+  // preprocessing
+  DevBuf<int> tables;
+  DevBuf<uint8_t> src, tmp;
+  DevBuf<h16> patches;
+  // activations of one pass over B clips
+  DevBuf<float> x, cls_proj, logits, probs;
+  DevBuf<h16> h, qkv, a, mid;
+  DevBuf<int> ids;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool timed[3] = {false, false, false};  // which of preprocess / encoder / head the last call ran
+  double flops = 0;
+
+  const h16* H(int i) const { return (const h16*)tensors[i].dev.p; }
+  const float* F(int i) const { return (const float*)tensors[i].dev.p; }
+};
+
+namespace {
+
+typedef eioku_timesformer Model;
+
+template <int MT, int EPI>
+int gemm(Model* m, hipStream_t st, const h16* A, int lda, const Lin& w, int M, int N, int K, void* out, long long ldc,
+         const float* pos = nullptr, int pos_rows = 1) {
+  EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0, "GEMM K %d / lda %d misaligned", K, lda);
+  if (M == 0) return EIOKU_OK;
+  const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
+  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, st, A, lda, m->H(w.w), K, m->F(w.b), M, N, K, out, ldc, pos, pos_rows);
+  m->flops += 2.0 * M * N * K;
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+int ln(Model* m, hipStream_t st, const float* x, int M, const LNorm& p, h16* out) {
+  hipLaunchKernelGGL(k_ln_eps, dim3((M + 3) / 4), dim3(256), 0, st, x, M, m->d, m->F(p.g), m->F(p.b), m->eps, out);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+int check_weights(const Model* m) {
+  for (const auto& t : m->tensors) EIOKU_REQUIRE(t.set, "tensor %s has no weights", t.name.c_str());
+  return EIOKU_OK;
+}
+
+int ensure_batch(Model* m, int B) {
+  const size_t PT = (size_t)m->P * m->frames, M = (size_t)B * (PT + 1), d = m->d;
+  EIOKU_TRY(grow_synced(m->x, M * d));
+  EIOKU_TRY(grow_synced(m->h, M * d));
+  EIOKU_TRY(grow_synced(m->qkv, M * 3 * d));
+  EIOKU_TRY(grow_synced(m->a, ((size_t)B * PT + (size_t)B * m->frames) * d));
+  EIOKU_TRY(grow_synced(m->mid, M * m->ffn));
+  EIOKU_TRY(grow_synced(m->cls_proj, (size_t)B * m->frames * d));
+  EIOKU_TRY(grow_synced(m->logits, (size_t)B * m->labels));
+  EIOKU_TRY(grow_synced(m->probs, (size_t)B * m->labels));
+  return grow_synced(m->ids, (size_t)B * m->labels);
+}
+
+// patches [B P T][768] fp16 (device) -> the residual stream after every layer in m->x, the logits in m->logits
+int run_encoder(Model* m, const h16* patches, int B, hipStream_t st) {
+  const int d = m->d, T = m->frames, P = m->P, PT = P * T, Mp = B * PT, M = Mp + B;
+  if (!m->tables_ready) {
+    const size_t n = (size_t)PT * d + d;
+    hipLaunchKernelGGL(k_embed_tables, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->F(m->pos), m->F(m->time),
+                       m->F(m->cls_token), P, T, d, m->postime.p, m->cls.p);
+    EIOKU_LAUNCH_CHECK();
+    m->tables_ready = true;
+  }
+  float* x = m->x;
+  float* x_cls = x + (size_t)Mp * d;
+  EIOKU_TRY((gemm<4, EPI_POS>(m, st, patches, kPatchK, m->proj, Mp, d, kPatchK, x, d, m->postime, PT)));
+  hipLaunchKernelGGL(k_cls_rows, dim3((unsigned)(((size_t)B * d + 255) / 256)), dim3(256), 0, st, m->cls.p, B, d, x_cls);
+  EIOKU_LAUNCH_CHECK();
+  h16* a_cls = m->a.p + (size_t)Mp * d;
+  for (const Layer& L : m->L) {
+    // temporal: patch rows only
+    EIOKU_TRY(ln(m, st, x, Mp, L.t_ln, m->h));
+    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->h, d, L.t_qkv, Mp, 3 * d, d, m->qkv.p, 3 * d)));
+    {
+      const long long probs = (long long)B * P * m->heads;
+      const size_t lds = (size_t)3 * T * 66 * sizeof(h16) + 96 * sizeof(float);
+      hipLaunchKernelGGL(k_attn_time, dim3((unsigned)probs), dim3(64), lds, st, m->qkv.p, T, m->heads, m->a.p);
+      EIOKU_LAUNCH_CHECK();
+      m->flops += 4.0 * probs * T * T * 64;
+    }
+    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->a, d, L.t_out, Mp, d, d, m->h.p, d)));
+    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->h, d, L.t_dense, Mp, d, d, x, d)));
+    // spatial: every row; the CLS row of a clip is normalised and projected once for its T frames
+    EIOKU_TRY(ln(m, st, x, M, L.s_ln, m->h));
+    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->h, d, L.s_qkv, M, 3 * d, d, m->qkv.p, 3 * d)));
+    {
+      const int n = 1 + P;
+      hipLaunchKernelGGL(k_attn_space, dim3((n + 63) / 64, m->heads, B * T), dim3(256), 0, st, m->qkv.p, B, P, T, m->heads, m->a.p, a_cls);
+      EIOKU_LAUNCH_CHECK();
+      m->flops += 4.0 * B * T * m->heads * (double)n * n * 64;
+    }
+    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->a, d, L.s_out, Mp, d, d, x, d)));
+    EIOKU_TRY((gemm<4, EPI_F32>(m, st, a_cls, d, L.s_out, B * T, d, d, m->cls_proj.p, d)));
+    hipLaunchKernelGGL(k_cls_mean, dim3((unsigned)(((size_t)B * d + 255) / 256)), dim3(256), 0, st, m->cls_proj.p, B, T, d, x_cls);
+    EIOKU_LAUNCH_CHECK();
+    // MLP
+    EIOKU_TRY(ln(m, st, x, M, L.m_ln, m->h));
+    EIOKU_TRY((gemm<4, EPI_GELU_F16>(m, st, m->h, d, L.fc1, M, m->ffn, d, m->mid.p, m->ffn)));
+    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->mid, m->ffn, L.fc2, M, d, m->ffn, x, d)));
+  }
+  return EIOKU_OK;
+}
+
+// final LayerNorm and classifier on the CLS rows; top_k > 0 adds softmax and selection
+int run_head(Model* m, int B, int top_k, hipStream_t st) {
+  const int d = m->d;
+  const float* x_cls = m->x.p + (size_t)B * m->P * m->frames * d;
+  EIOKU_TRY(ln(m, st, x_cls, B, m->final_ln, m->h));
+  EIOKU_TRY((gemm<1, EPI_F32>(m, st, m->h, d, m->classifier, B, m->labels, d, m->logits.p, m->labels)));
+  if (top_k > 0) {
+    hipLaunchKernelGGL(k_action_head, dim3(B), dim3(256), (size_t)m->labels * sizeof(float), st, m->logits.p, m->labels, top_k,
+                       m->probs.p, m->ids.p);
+    EIOKU_LAUNCH_CHECK();
+  }
+  return EIOKU_OK;
+}
+
+int check_tables(const int32_t* bounds, int S, int k, int extent, const char* axis) {
+  for (int i = 0; i < S; ++i) {
+    const int lo = bounds[2 * i], cnt = bounds[2 * i + 1];
+    EIOKU_REQUIRE(lo >= 0 && cnt >= 0 && cnt <= k && lo + cnt <= extent, "%s table row %d reads [%d, %d) of %d pixels with %d taps",
+                  axis, i, lo, lo + cnt, extent, k);
+  }
+  return EIOKU_OK;
+}
+
+int preprocess(Model* m, const uint8_t* bgr, int n_clips, int h, int w, const int32_t* xbounds, const int32_t* xk, int kx,
+               const int32_t* ybounds, const int32_t* yk, int ky, h16* patches, uint8_t* out_u8, int mem, hipStream_t stream) {
+  const int S = m->image, N = n_clips * m->frames;
+  EIOKU_TRY(check_tables(xbounds, S, kx, w, "x"));
+  EIOKU_TRY(check_tables(ybounds, S, ky, h, "y"));
+  int y0 = h, y1 = 0;  // the source rows the vertical pass reads
+  for (int i = 0; i < S; ++i) {
+    if (!ybounds[2 * i + 1]) continue;
+    y0 = ybounds[2 * i] < y0 ? ybounds[2 * i] : y0;
+    y1 = ybounds[2 * i] + ybounds[2 * i + 1] > y1 ? ybounds[2 * i] + ybounds[2 * i + 1] : y1;
+  }
+  EIOKU_REQUIRE(y1 > y0, "empty y table");
+  const int rows = y1 - y0;
+  EIOKU_TRY(grow_synced(m->tables, (size_t)S * (2 + kx + 2 + ky)));
+  int* d_xb = m->tables;
+  int* d_xk = d_xb + S * 2;
+  int* d_yb = d_xk + (size_t)S * kx;
+  int* d_yk = d_yb + S * 2;
+  EIOKU_HIP_CHECK(hipMemcpyAsync(d_xb, xbounds, (size_t)S * 2 * 4, hipMemcpyHostToDevice, stream));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(d_xk, xk, (size_t)S * kx * 4, hipMemcpyHostToDevice, stream));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(d_yb, ybounds, (size_t)S * 2 * 4, hipMemcpyHostToDevice, stream));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(d_yk, yk, (size_t)S * ky * 4, hipMemcpyHostToDevice, stream));
+  const uint8_t* d_src = bgr;
+  if (mem == EIOKU_MEM_HOST) {
+    const size_t bytes = (size_t)N * h * w * 3;
+    EIOKU_TRY(grow_synced(m->src, bytes));
+    EIOKU_HIP_CHECK(hipMemcpyAsync(m->src, bgr, bytes, hipMemcpyHostToDevice, stream));
+    d_src = m->src;
+  }
+  EIOKU_TRY(grow_synced(m->tmp, (size_t)N * rows * S * 3));
+  const long long w1 = (long long)N * rows * S, w2 = (long long)N * S * S;
+  hipLaunchKernelGGL(k_clip_resize_h, dim3((unsigned)((w1 + 255) / 256)), dim3(256), 0, stream, d_src, N, h, w, y0, rows, S, d_xb, d_xk,
+                     kx, m->tmp.p);
+  EIOKU_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_clip_resize_v, dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, stream, m->tmp.p, N, m->frames, y0, rows, S, d_yb,
+                     d_yk, ky, m->nrm, patches, out_u8);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eioku_timesformer_create(int image, int patch, int frames, int hidden, int layers, int heads, int ffn, int labels, float ln_eps,
+                             eioku_timesformer** out) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(out, "NULL argument");
+  EIOKU_REQUIRE(hidden > 0 && heads > 0 && heads * 64 == hidden, "head_dim must be 64 (hidden %d / heads %d)", hidden, heads);
+  EIOKU_REQUIRE(patch == kPatch, "patch_size must be 16 (got %d)", patch);
+  EIOKU_REQUIRE(image > 0 && image % kPatch == 0 && image <= kMaxImage, "image_size must be a multiple of 16, at most %d (got %d)",
+                kMaxImage, image);
+  EIOKU_REQUIRE(frames >= 1 && frames <= kMaxFrames, "num_frames must be in [1, %d] (got %d)", kMaxFrames, frames);
+  EIOKU_REQUIRE(layers >= 0 && ffn > 0 && ffn % 32 == 0 && labels > 0 && labels <= 16000 && ln_eps > 0.f,
+                "bad config (layers %d, ffn %d a multiple of 32, labels %d at most 16000, ln_eps %g)", layers, ffn, labels, (double)ln_eps);
+  auto* m = new eioku_timesformer();
+  m->image = image, m->frames = frames, m->d = hidden, m->layers = layers, m->heads = heads, m->ffn = ffn, m->labels = labels;
+  m->side = image / kPatch, m->P = m->side * m->side, m->eps = ln_eps;
+  const int d = hidden;
+  auto add = [&](const std::string& n, int rows, int cols, int kind) {
+    Tensor t;
+    t.name = n, t.rows = rows, t.cols = cols, t.kind = kind;
+    m->tensors.push_back(std::move(t));
+    return (int)m->tensors.size() - 1;
+  };
+  auto lin = [&](const std::string& p, int rows, int cols) {
+    Lin l;
+    l.w = add(p + ".weight", rows, cols, T_F16);
+    l.b = add(p + ".bias", rows, 1, T_F32);
+    return l;
+  };
+  auto lnorm = [&](const std::string& p) {
+    LNorm l;
+    l.g = add(p + ".weight", d, 1, T_F32);
+    l.b = add(p + ".bias", d, 1, T_F32);
+    return l;
+  };
+  const std::string e = "timesformer.embeddings.";
+  m->cls_token = add(e + "cls_token", 1, d, T_F32);
+  m->pos = add(e + "position_embeddings", 1 + m->P, d, T_F32);
+  m->time = add(e + "time_embeddings", frames, d, T_F32);
+  m->proj = lin(e + "patch_embeddings.projection", d, kPatchK);
+  for (int l = 0; l < layers; ++l) {
+    const std::string p = "timesformer.encoder.layer." + std::to_string(l) + ".";
+    Layer L;
+    L.t_ln = lnorm(p + "temporal_layernorm");
+    L.t_qkv = lin(p + "temporal_attention.attention.qkv", 3 * d, d);
+    L.t_out = lin(p + "temporal_attention.output.dense", d, d);
+    L.t_dense = lin(p + "temporal_dense", d, d);
+    L.s_ln = lnorm(p + "layernorm_before");
+    L.s_qkv = lin(p + "attention.attention.qkv", 3 * d, d);
+    L.s_out = lin(p + "attention.output.dense", d, d);
+    L.m_ln = lnorm(p + "layernorm_after");
+    L.fc1 = lin(p + "intermediate.dense", ffn, d);
+    L.fc2 = lin(p + "output.dense", d, ffn);
+    m->L.push_back(L);
+  }
+  m->final_ln = lnorm("timesformer.layernorm");
+  m->classifier = lin("classifier", labels, d);
+  auto fail = [&](int rc) {
+    eioku_timesformer_destroy(m);
+    return rc;
+  };
+  for (auto& t : m->tensors)
+    if (t.dev.grow(t.numel() * (t.kind == T_F32 ? 4 : 2))) return fail(EIOKU_ENOMEM);
+  if (m->postime.grow((size_t)m->P * frames * d) || m->cls.grow((size_t)d)) return fail(EIOKU_ENOMEM);
+  for (auto& ev : m->ev)
+    if (hipEventCreate(&ev) != hipSuccess) {
+      ev = nullptr;
+      set_error("hipEventCreate failed");
+      return fail(EIOKU_EHIP);
+    }
+  *out = m;
+  return EIOKU_OK;
+}
+
+void eioku_timesformer_destroy(eioku_timesformer* m) {
+  if (!m) return;
+  (void)hipDeviceSynchronize();
+  for (auto ev : m->ev)
+    if (ev) (void)hipEventDestroy(ev);
+  delete m;  // every buffer frees itself
+}
+
+int eioku_timesformer_num_tensors(const eioku_timesformer* m) { return m ? (int)m->tensors.size() : 0; }
+
+int eioku_timesformer_tensor_info(const eioku_timesformer* m, int idx, char* name, size_t cap, int* rows, int* cols) {
+  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size(), "bad tensor index %d", idx);
+  const auto& t = m->tensors[idx];
+  if (name && cap) snprintf(name, cap, "%s", t.name.c_str());
+  if (rows) *rows = t.rows;
+  if (cols) *cols = t.cols;
+  return EIOKU_OK;
+}
+
+int eioku_timesformer_set_tensor(eioku_timesformer* m, int idx, const float* host, size_t numel) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size() && host, "bad argument");
+  auto& t = m->tensors[idx];
+  EIOKU_REQUIRE(numel == t.numel(), "%s: expected %zu elements, got %zu", t.name.c_str(), t.numel(), numel);
+  EIOKU_HIP_CHECK(hipDeviceSynchronize());  // no pass may still read the old value
+  if (t.kind == T_F32) {
+    EIOKU_HIP_CHECK(hipMemcpy(t.dev.p, host, numel * sizeof(float), hipMemcpyHostToDevice));
+  } else {
+    DevBuf<float> stage;
+    EIOKU_TRY(stage.grow(numel));
+    EIOKU_HIP_CHECK(hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage.p, numel, (h16*)t.dev.p);
+    EIOKU_LAUNCH_CHECK();
+    EIOKU_HIP_CHECK(hipDeviceSynchronize());
+  }
+  t.set = true;
+  m->tables_ready = false;
+  return EIOKU_OK;
+}
+
+int eioku_timesformer_set_norm(eioku_timesformer* m, const float* mean_rgb, const float* std_rgb) {
+  EIOKU_REQUIRE(m && mean_rgb && std_rgb, "NULL argument");
+  for (int c = 0; c < 3; ++c) {
+    EIOKU_REQUIRE(std_rgb[c] > 0.f, "image_std must be positive");
+    m->nrm.mean[c] = mean_rgb[c], m->nrm.std[c] = std_rgb[c];
+  }
+  return EIOKU_OK;
+}
+
+// n_clips clips of T BGR u8 frames (h x w, [clip][frame][h][w][3], host or device) -> patches_out [n_clips P T][768] fp16
+// (device, optional) and / or out_rgb_u8 [n_clips T][S][S][3] (device, optional: the resized and cropped RGB image).  Tables
+// from the host (eioku_amd/actions.py): the S rows of Pillow's tables that the centre crop keeps, per axis.
+int eioku_timesformer_preprocess(eioku_timesformer* m, const uint8_t* bgr, int n_clips, int h, int w, const int32_t* xbounds,
+                                 const int32_t* xk, int kx, const int32_t* ybounds, const int32_t* yk, int ky, void* patches_out,
+                                 uint8_t* out_rgb_u8, int mem, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && n_clips >= 0 && h > 0 && w > 0 && kx > 0 && ky > 0 && xbounds && xk && ybounds && yk, "bad argument");
+  EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
+  if (n_clips == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(bgr, "NULL frames");
+  hipStream_t stream = (hipStream_t)stream_;
+  EIOKU_TRY(preprocess(m, bgr, n_clips, h, w, xbounds, xk, kx, ybounds, yk, ky, (h16*)patches_out, out_rgb_u8, mem, stream));
+  if (mem == EIOKU_MEM_HOST) EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // the caller may reuse its host buffer
+  return EIOKU_OK;
+}
+
+// The raw network: patches [n_clips P T][768] fp16 (device) -> logits_out [n_clips][labels] fp32 (device), and optionally
+// hidden_out [n_clips][1 + P T][hidden] fp32 (device): the residual stream before the final LayerNorm, in the model's token
+// order.  Asynchronous.
+int eioku_timesformer_forward(eioku_timesformer* m, const void* patches, int n_clips, float* logits_out, float* hidden_out,
+                              void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && n_clips >= 0, "bad argument");
+  if (n_clips == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(patches && logits_out, "NULL buffer");
+  EIOKU_TRY(check_weights(m));
+  hipStream_t st = (hipStream_t)stream_;
+  EIOKU_TRY(ensure_batch(m, n_clips));
+  m->flops = 0;
+  m->timed[0] = false, m->timed[1] = m->timed[2] = true;
+  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  EIOKU_TRY(run_encoder(m, (const h16*)patches, n_clips, st));
+  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
+  EIOKU_TRY(run_head(m, n_clips, 0, st));
+  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(logits_out, m->logits, (size_t)n_clips * m->labels * 4, hipMemcpyDeviceToDevice, st));
+  if (hidden_out) {
+    const int PT = m->P * m->frames;
+    const size_t n = (size_t)n_clips * (PT + 1) * m->d;
+    hipLaunchKernelGGL(k_hidden_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->x.p, n_clips, PT, m->d, hidden_out);
+    EIOKU_LAUNCH_CHECK();
+  }
+  return EIOKU_OK;
+}
+
+// detect_actions' per-clip arithmetic on n_clips clips (host or device): resize / crop / normalise -> network -> softmax ->
+// top_k by (probability desc, class asc) -> prob_out [n_clips][top_k] fp32, class_out [n_clips][top_k] int32 (HOST when mem
+// == EIOKU_MEM_HOST, else device); logits_out optional ([n_clips][labels], same side).  Host outputs synchronise the stream.
+int eioku_timesformer_classify(eioku_timesformer* m, const uint8_t* bgr, int n_clips, int h, int w, const int32_t* xbounds,
+                               const int32_t* xk, int kx, const int32_t* ybounds, const int32_t* yk, int ky, int top_k,
+                               float* prob_out, int32_t* class_out, float* logits_out, int mem, void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && n_clips >= 0 && h > 0 && w > 0 && kx > 0 && ky > 0 && xbounds && xk && ybounds && yk, "bad argument");
+  EIOKU_REQUIRE(top_k >= 1 && top_k <= m->labels, "bad argument (top_k %d of %d labels)", top_k, m->labels);
+  EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
+  if (n_clips == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(bgr && prob_out && class_out, "NULL buffer");
+  EIOKU_TRY(check_weights(m));
+  hipStream_t st = (hipStream_t)stream_;
+  EIOKU_TRY(ensure_batch(m, n_clips));
+  EIOKU_TRY(grow_synced(m->patches, (size_t)n_clips * m->P * m->frames * kPatchK));
+  m->flops = 0;
+  m->timed[0] = m->timed[1] = m->timed[2] = true;
+  EIOKU_HIP_CHECK(hipEventRecord(m->ev[0], st));
+  EIOKU_TRY(preprocess(m, bgr, n_clips, h, w, xbounds, xk, kx, ybounds, yk, ky, m->patches.p, nullptr, mem, st));
+  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  EIOKU_TRY(run_encoder(m, m->patches.p, n_clips, st));
+  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
+  EIOKU_TRY(run_head(m, n_clips, top_k, st));
+  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  const hipMemcpyKind kind = mem == EIOKU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  EIOKU_HIP_CHECK(hipMemcpyAsync(prob_out, m->probs, (size_t)n_clips * top_k * 4, kind, st));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(class_out, m->ids, (size_t)n_clips * top_k * 4, kind, st));
+  if (logits_out) EIOKU_HIP_CHECK(hipMemcpyAsync(logits_out, m->logits, (size_t)n_clips * m->labels * 4, kind, st));
+  if (mem == EIOKU_MEM_HOST) EIOKU_HIP_CHECK(hipStreamSynchronize(st));
+  return EIOKU_OK;
+}
+
+// softmax and top_k of logits [n][labels] fp32 (device) -> prob_out [n][top_k], class_out [n][top_k] (device): the head's
+// selection on its own (parity helper).  Asynchronous.
+int eioku_timesformer_topk(eioku_timesformer* m, const float* logits, int n, int top_k, float* prob_out, int32_t* class_out,
+                           void* stream_) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(m && n >= 0 && top_k >= 1 && top_k <= m->labels, "bad argument (top_k %d of %d labels)", top_k, m ? m->labels : 0);
+  if (n == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(logits && prob_out && class_out, "NULL buffer");
+  hipLaunchKernelGGL(k_action_head, dim3(n), dim3(256), (size_t)m->labels * sizeof(float), (hipStream_t)stream_, logits, m->labels, top_k,
+                     prob_out, class_out);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+int eioku_timesformer_last_flops(const eioku_timesformer* m, double* flops) {
+  EIOKU_REQUIRE(m && flops, "NULL argument");
+  *flops = m->flops;
+  return EIOKU_OK;
+}
+
+// device milliseconds of the last forward / classify call per stage (0 for a stage that call did not run); waits for it
+int eioku_timesformer_last_ms(const eioku_timesformer* m, double* preprocess_ms, double* encoder_ms, double* head_ms) {
+  EIOKU_REQUIRE(m && preprocess_ms && encoder_ms && head_ms, "NULL argument");
+  double* out[3] = {preprocess_ms, encoder_ms, head_ms};
+  for (int i = 0; i < 3; ++i) {
+    *out[i] = 0.0;
+    if (!m->timed[i]) continue;
+    float ms = 0.f;
+    EIOKU_HIP_CHECK(hipEventSynchronize(m->ev[i + 1]));
+    EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, m->ev[i], m->ev[i + 1]));
+    *out[i] = ms;
+  }
+  return EIOKU_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,77 @@
+// The fp16 GEMM of the transformer models (K20 Whisper, K25 TimeSformer): C = A . W^T on v_mfma_f32_16x16x32_f16 with fused
+// epilogues.  Included by whisper.hip and actions.hip; everything here has internal linkage.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace {
+
+typedef _Float16 h16;
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float float4v __attribute__((ext_vector_type(4)));
+
+// ---- GEMM ---------------------------------------------------------------------------------------------------------------
+enum { EPI_F16 = 0, EPI_GELU_F16 = 1, EPI_RESID = 2, EPI_GELU_POS = 3, EPI_F32 = 4, EPI_POS = 5 };
+
+__device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+
+// out[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]).  grid (ceil(N / 64), ceil(M / (16 MT))), 4 waves: wave w owns weight
+// rows n0 = 64 bx + 16 w .. + 15.  MFMA 16x16x32: A operand = weight rows (lane (r, u): row r, k 8u .. 8u + 7), B operand =
+// activation rows; lane holds D[n0 + 4u + t][m0 + r].  K % 32 == 0, lda / ldw % 8 == 0.  Each output element is one
+// k-ordered sum whatever M is, so a lane's result does not depend on the batch around it.
+//   EPI_F16      out fp16 [m * ldc + n]            EPI_GELU_F16  the same after GELU
+//   EPI_RESID    out fp32 [m * ldc + n] += value   EPI_GELU_POS  out fp32 = GELU(value) + pos[m % pos_rows][n]
+//   EPI_F32      out fp32 [m * ldc + n] = value    EPI_POS       out fp32 = value + pos[m % pos_rows][n]
+template <int MT, int EPI>
+__global__ __launch_bounds__(256) void k_gemm(const h16* __restrict__ A, int lda, const h16* __restrict__ W, int ldw,
+                                              const float* __restrict__ bias, int M, int N, int K, void* __restrict__ out,
+                                              long long ldc, const float* __restrict__ pos, int pos_rows) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, u = lane >> 4;
+  const int n0 = (blockIdx.x * 4 + wave) * 16, m0 = blockIdx.y * 16 * MT;
+  if (n0 >= N) return;
+  const bool wl = n0 + r < N;
+  const h16* wr = W + (size_t)(wl ? n0 + r : 0) * ldw + 8 * u;
+  const h16* ar[MT];
+  bool al[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const int mm = m0 + 16 * i + r;
+    al[i] = mm < M;
+    ar[i] = A + (size_t)(al[i] ? mm : 0) * lda + 8 * u;
+  }
+  float4v acc[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) acc[i] = float4v{0.f, 0.f, 0.f, 0.f};
+  const half8 zero = {};
+  for (int k = 0; k < K; k += 32) {
+    const half8 w = wl ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(wr + k)) : zero;
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const half8 a = al[i] ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(ar[i] + k)) : zero;
+      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, a, acc[i], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const int mm = m0 + 16 * i + r;
+    if (mm >= M) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int n = n0 + 4 * u + t;
+      if (n >= N) continue;
+      const float v = acc[i][t] + (bias ? bias[n] : 0.f);
+      const size_t o = (size_t)mm * (size_t)ldc + n;
+      if (EPI == EPI_F16) reinterpret_cast<h16*>(out)[o] = (h16)v;
+      if (EPI == EPI_GELU_F16) reinterpret_cast<h16*>(out)[o] = (h16)gelu(v);
+      if (EPI == EPI_RESID) reinterpret_cast<float*>(out)[o] += v;
+      if (EPI == EPI_GELU_POS) reinterpret_cast<float*>(out)[o] = gelu(v) + pos[(size_t)(mm % pos_rows) * N + n];
+      if (EPI == EPI_F32) reinterpret_cast<float*>(out)[o] = v;
+      if (EPI == EPI_POS) reinterpret_cast<float*>(out)[o] = v + pos[(size_t)(mm % pos_rows) * N + n];
+    }
+  }
+}
+
+}  // namespace

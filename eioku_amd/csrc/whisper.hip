@@ -1,6 +1,6 @@
 // K19 / K20 / K21: Whisper transcription on gfx950 (DESIGN.md "K19 / K20").
 //   K19  k_mel_frames / k_mel_max / k_mel_finish   log-mel spectrogram, DFT and mel product in fp64
-//   K20  k_gemm         C = A . W^T on v_mfma_f32_16x16x32_f16: 16 weight rows per wave against MT tiles of 16 activation
+//   K20  k_gemm         (gemm_f16.h, shared with actions.hip) C = A . W^T on v_mfma_f32_16x16x32_f16: 16 weight rows per wave against MT tiles of 16 activation
 //                       rows.  MT = 4 for the encoder (M = B * ctx), MT = 1 for the decoder step (M = B <= 16: every
 //                       weight element is read once and used once per lane: a weight-streaming GEMM)
 //        k_attn         softmax(q k^T / 8) v for head dimension 64 and any number of keys (encoder self-attention over ctx
@@ -25,6 +25,7 @@
 // and the token embedding are fp16; biases, LayerNorm parameters and both position tables fp32; the residual stream is
 // fp32; LayerNorm outputs, q / k / v, attention outputs, GELU outputs and the mel input are rounded to fp16.
 #include "common.h"
+#include "gemm_f16.h"
 
 #include <hip/hip_fp16.h>
 
@@ -35,10 +36,6 @@
 using namespace eioku;
 
 namespace {
-
-typedef _Float16 h16;
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
 
 constexpr int kNfft = 400, kHop = 160, kBins = 201, kPad = 200;
 constexpr float kNegInf = -INFINITY;
@@ -153,64 +150,6 @@ __global__ __launch_bounds__(256) void k_im2col_s2(const h16* __restrict__ h, in
   const int t = (int)(row % Tout), b = (int)(row / Tout);
   const int tap = k / C, c = k % C, ts = 2 * t + tap - 1;
   col[i] = (ts >= 0 && ts < Tin) ? h[((size_t)b * Tin + ts) * C + c] : (h16)0.f;
-}
-
-// ---- GEMM ---------------------------------------------------------------------------------------------------------------
-enum { EPI_F16 = 0, EPI_GELU_F16 = 1, EPI_RESID = 2, EPI_GELU_POS = 3 };
-
-__device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
-
-// out[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]).  grid (ceil(N / 64), ceil(M / (16 MT))), 4 waves: wave w owns weight
-// rows n0 = 64 bx + 16 w .. + 15.  MFMA 16x16x32: A operand = weight rows (lane (r, u): row r, k 8u .. 8u + 7), B operand =
-// activation rows; lane holds D[n0 + 4u + t][m0 + r].  K % 32 == 0, lda / ldw % 8 == 0.  Each output element is one
-// k-ordered sum whatever M is, so a lane's result does not depend on the batch around it.
-//   EPI_F16      out fp16 [m * ldc + n]            EPI_GELU_F16  the same after GELU
-//   EPI_RESID    out fp32 [m * ldc + n] += value   EPI_GELU_POS  out fp32 = GELU(value) + pos[m % pos_rows][n]
-template <int MT, int EPI>
-__global__ __launch_bounds__(256) void k_gemm(const h16* __restrict__ A, int lda, const h16* __restrict__ W, int ldw,
-                                              const float* __restrict__ bias, int M, int N, int K, void* __restrict__ out,
-                                              long long ldc, const float* __restrict__ pos, int pos_rows) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, u = lane >> 4;
-  const int n0 = (blockIdx.x * 4 + wave) * 16, m0 = blockIdx.y * 16 * MT;
-  if (n0 >= N) return;
-  const bool wl = n0 + r < N;
-  const h16* wr = W + (size_t)(wl ? n0 + r : 0) * ldw + 8 * u;
-  const h16* ar[MT];
-  bool al[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int mm = m0 + 16 * i + r;
-    al[i] = mm < M;
-    ar[i] = A + (size_t)(al[i] ? mm : 0) * lda + 8 * u;
-  }
-  float4v acc[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) acc[i] = float4v{0.f, 0.f, 0.f, 0.f};
-  const half8 zero = {};
-  for (int k = 0; k < K; k += 32) {
-    const half8 w = wl ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(wr + k)) : zero;
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const half8 a = al[i] ? __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(ar[i] + k)) : zero;
-      acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, a, acc[i], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int mm = m0 + 16 * i + r;
-    if (mm >= M) continue;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int n = n0 + 4 * u + t;
-      if (n >= N) continue;
-      const float v = acc[i][t] + (bias ? bias[n] : 0.f);
-      const size_t o = (size_t)mm * (size_t)ldc + n;
-      if (EPI == EPI_F16) reinterpret_cast<h16*>(out)[o] = (h16)v;
-      if (EPI == EPI_GELU_F16) reinterpret_cast<h16*>(out)[o] = (h16)gelu(v);
-      if (EPI == EPI_RESID) reinterpret_cast<float*>(out)[o] += v;
-      if (EPI == EPI_GELU_POS) reinterpret_cast<float*>(out)[o] = gelu(v) + pos[(size_t)(mm % pos_rows) * N + n];
-    }
-  }
 }
 
 // ---- LayerNorm: fp32 row -> fp16, one wave per row ------------------------------------------------------------------------

@@ -14,6 +14,8 @@ ffmpeg / OpenCV / Ultralytics on the CPU.
                                            language, polygon}], "language"}           (ref :469-558)
     generate_thumbnails(video_path, config) -> {"thumbnails": [{scene_index, start_ms, end_ms, timestamp_ms,
                                            frame_index, width, height, thumbnail_path, bytes}]}   (design only)
+    detect_actions(video_path, config) -> {"actions": [{frame_index, timestamp_ms, start_ms, end_ms,
+                                           labels[top_k], scores[top_k]}]}             (design only)
 
 What changes underneath (and nothing else): sampled frames are detected in batches instead of one
 ``model(frame)`` call each, and the scene score is computed by K1/K2 instead of an ffmpeg child
@@ -83,6 +85,15 @@ def _stack_rows(rows):
     import torch
 
     return (torch.stack(rows) if len(rows) > 1 else rows[0][None]).contiguous()
+
+
+def _stack_frames(items):
+    """Frames or clips of one kind (host arrays, or device tensors) -> one batch along a new first axis."""
+    if isinstance(items[0], np.ndarray):
+        return np.stack(items)
+    import torch
+
+    return torch.stack(list(items))
 
 
 class _DetectionLane:
@@ -157,7 +168,7 @@ class ModelManager:
                  random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
                  ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None,
                  gpu_vad: bool = False, vad_factory=None, gpu_audio: bool = False, audio_frontend_factory=None,
-                 gpu_speakers: bool = False, speaker_factory=None):
+                 gpu_speakers: bool = False, speaker_factory=None, action_recognizer_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
@@ -194,6 +205,8 @@ class ModelManager:
         self._audio_frontend_factory = audio_frontend_factory
         self._gpu_speakers = bool(gpu_speakers)
         self._speaker_factory = speaker_factory
+        # (cache_dir, model_name) -> object with classify(clips, top_k), labels, frames and optionally upload(frames)
+        self._action_recognizer_factory = action_recognizer_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -495,6 +508,84 @@ class ModelManager:
             return {"classifications": classifications}
         except Exception as e:
             logger.error(f"Place detection failed: {e}", exc_info=True)
+            raise
+
+    # ---- actions: TimeSformer on windows of the sampled frames (design.md §1.8; the reference never builds it) ----
+    def _load_action_recognizer(self, model_name: str):
+        """``<cache>/timesformer/<model_name>/`` (``eioku_amd.actions``), per job like the other stages."""
+        if self._action_recognizer_factory is not None:
+            return self._action_recognizer_factory(self.cache_dir, model_name)
+        from .actions import ActionRecognizer
+
+        return ActionRecognizer.from_cache(self.cache_dir, model_name, seed=self._seed)
+
+    async def detect_actions(self, video_path: str, config: dict) -> dict:
+        """Recognise actions on the HIP path: every ``max(1, int(fps * frame_interval))``-th frame is sampled, clip c is
+        sampled frames ``[c * clip_stride, c * clip_stride + T)`` (T from the checkpoint, ``clip_stride`` defaults to T), a
+        trailing partial window is dropped, and a video with no full window is one clip padded with its last frame.
+        -> ``{"actions": [{frame_index, timestamp_ms, start_ms, end_ms, labels, scores}]}``: the clip's first sampled
+        frame, the span up to its last real sampled frame, and the ``top_k`` labels in descending probability."""
+        from .actions import action_settings
+
+        try:
+            logger.info(f"Action detection: {video_path} (device: {self._get_device()})")
+            recognizer = self._load_action_recognizer(action_settings(config)["model_name"])
+            actions: list[dict] = []
+            try:
+                T, names = int(recognizer.frames), recognizer.labels
+                settings = action_settings(config, T, len(names))
+                stride, top_k = settings["clip_stride"], settings["top_k"]
+                cap = self._open(video_path)
+                try:
+                    fps = cap.fps or 30
+                    interval = _frame_interval(fps, settings["frame_interval"])
+                    upload = getattr(recognizer, "upload", None)
+                    held, first, seen, start = [], 0, 0, 0  # held[i]: (meta, batch, row) of sampled frame first + i
+
+                    def run(windows):
+                        """``[(first, last real)]`` windows over the held frames -> their action dicts"""
+                        if not windows:
+                            return
+                        clips = []
+                        for a, b in windows:
+                            rows = [held[min(i, b) - first] for i in range(a, a + T)]  # past the last real frame: repeat it
+                            batch, lo = rows[0][1], rows[0][2]
+                            if all(r[1] is batch and r[2] == lo + j for j, r in enumerate(rows)):
+                                clips.append(batch[lo:lo + T])  # one batch, consecutive rows: a view
+                            else:
+                                clips.append(_stack_frames([r[1][r[2]] for r in rows]))
+                        probs, ids = recognizer.classify(_stack_frames(clips), top_k)
+                        for (a, b), p, i in zip(windows, probs, ids):
+                            (frame_idx, ts), (_, end_ts) = held[a - first][0], held[b - first][0]
+                            actions.append({"frame_index": frame_idx, "timestamp_ms": ts, "start_ms": ts, "end_ms": end_ts,
+                                            "labels": [names[int(c)] for c in i], "scores": [float(np.float32(v)) for v in p]})
+
+                    for meta, frames in _sampled_batches(cap, fps, interval, self._batch_size):
+                        batch = np.stack(frames)
+                        batch = upload(batch) if upload else batch  # the one upload of these frames
+                        held.extend((m, batch, j) for j, m in enumerate(meta))
+                        seen += len(meta)
+                        windows = []
+                        while start + T <= seen:
+                            windows.append((start, start + T - 1))
+                            start += stride
+                        run(windows)
+                        drop = min(start, seen) - first  # frames no later window reads
+                        if drop > 0:
+                            del held[:drop]
+                            first += drop
+                    if 0 < seen < T:  # no full window at all: one clip, padded with the last frame
+                        run([(0, seen - 1)])
+                finally:
+                    cap.release()
+            finally:
+                close = getattr(recognizer, "close", None)
+                if close:
+                    close()
+            logger.info(f"✅ Action detection complete: {len(actions)} clips")
+            return {"actions": actions}
+        except Exception as e:
+            logger.error(f"Action detection failed: {e}", exc_info=True)
             raise
 
     async def detect_objects(self, video_path: str, config: dict) -> dict:

@@ -38,17 +38,20 @@ logger = logging.getLogger(__name__)
 TASK_TO_ARTIFACT_TYPE = {"object_detection": "object.detection", "face_detection": "face.detection",
                          "scene_detection": "scene", "segment_embedding": "segment.embedding",
                          "place_detection": "place.classification", "ocr": "ocr.text", "topic_extraction": "topic",
-                         "thumbnail_generation": "scene.thumbnail", "transcription": "transcript.segment"}
+                         "thumbnail_generation": "scene.thumbnail", "transcription": "transcript.segment",
+                         "action_detection": "action.detection"}
 TASK_TO_RESULT_KEY = {"object_detection": "detections", "face_detection": "detections", "scene_detection": "scenes",
                       "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections",
-                      "topic_extraction": "topics", "thumbnail_generation": "thumbnails", "transcription": "segments"}
+                      "topic_extraction": "topics", "thumbnail_generation": "thumbnails", "transcription": "segments",
+                      "action_detection": "actions"}
 # the reference's seven (task_handler.py:92-127) + the one its semantic-search design adds after transcription
 # (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them; and the topic stage its
 # worker configs schedule (config/*.json "topic_extraction"; tasks.md 12.1-12.3): KeyBERT keywords of the segments; and the
-# thumbnail worker the design runs behind scene detection (design.md:276-297): one JPEG per scene
+# thumbnail worker the design runs behind scene detection (design.md:276-297): one JPEG per scene; and the design's "Action
+# Detector" (design.md §1.8), which the reference never schedules: one "action.detection" envelope per clip
 KNOWN_TASK_TYPES = ("object_detection", "face_detection", "transcription", "ocr", "place_detection",
                     "scene_detection", "metadata_extraction", "segment_embedding", "topic_extraction",
-                    "thumbnail_generation")
+                    "thumbnail_generation", "action_detection")
 
 
 @dataclass
@@ -189,6 +192,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             result = await model_manager.transcribe_video(video_path, config or {})
         elif task_type == "thumbnail_generation":  # one "scene.thumbnail" envelope per scene, spanning the scene
             result = await model_manager.generate_thumbnails(video_path, config or {})
+        elif task_type == "action_detection":  # one "action.detection" envelope per clip, spanning the clip's frames
+            result = await model_manager.detect_actions(video_path, config or {})
         elif task_type in ("segment_embedding", "topic_extraction"):
             # segments: the transcription task's output for this video.  The reference would read them back from its
             # artifact table; without a database they arrive in the job config or through ctx["segment_source"](video_id)

@@ -820,6 +820,50 @@ int eioku_spk_segments(const float* win_emb, const int* seg_first, int n_seg, fl
 int eioku_spk_assign(const float* emb, int n, const int32_t* labels, float assign_max, int32_t* labels_out, float* centroids_out,
                      int* n_labels, void* stream);
 
+/* ---- action recognition (K25), csrc/actions.hip ----------------------------------------------------------------------------
+ * Hugging Face TimesformerForVideoClassification with attention_type "divided_space_time" on clips of `frames` frames:
+ * fp16 weights and activations, fp32 residual stream and accumulators.  [PUBLIC-LIB]: restated from the public
+ * transformers / TimeSformer sources.  P = (image / 16)^2 patches; token 0 is CLS, patch p at frame t is token 1 + p T + t.
+ *   create: head dimension (hidden / heads) 64, patch 16, image a multiple of 16 up to 448, 1 <= frames <= 96, ffn a
+ *     multiple of 32; anything else is EIOKU_EINVAL.  layers may be 0 (embedding and head only).
+ *   tensor_info / set_tensor: fp32, row-major rows x cols, under the names of the model's state_dict():
+ *     timesformer.embeddings.cls_token (1 x hidden), .position_embeddings (1 + P x hidden), .time_embeddings (frames x
+ *     hidden), .patch_embeddings.projection.weight (hidden x 768, column c 256 + ky 16 + kx) / .bias, per layer
+ *     timesformer.encoder.layer.<l>.{temporal_layernorm, temporal_attention.attention.qkv, temporal_attention.output.dense,
+ *     temporal_dense, layernorm_before, attention.attention.qkv, attention.output.dense, layernorm_after,
+ *     intermediate.dense, output.dense}.{weight, bias}, then timesformer.layernorm and classifier.  Biases are rows x 1.
+ *   set_norm: per-channel (R, G, B) mean and std of the preprocessing; 0.45 and 0.225 until set.
+ *   preprocess: n_clips x frames BGR u8 frames of h x w (host or device per mem) -> Pillow's antialiased bilinear resize
+ *     and centre crop to image x image, BGR -> RGB, (v * (1 / 255) - mean) / std, as fp16 patch rows
+ *     [clip][patch][frame][c 256 + ky 16 + kx] (device, optional), and / or the cropped RGB u8 image [clip frame][image]
+ *     [image][3] (device, optional).  Tables: HOST int32, the `image` rows of Pillow's coefficient tables (bounds [.][2] =
+ *     first source index, taps; k [.][kx] taps x 2^22) that the crop keeps, per axis.
+ *   forward: patch rows -> logits [n_clips][labels] fp32 and optionally hidden_out [n_clips][1 + P frames][hidden] fp32,
+ *     the residual stream before the final LayerNorm in token order.  Device buffers, asynchronous.
+ *   classify: preprocess + forward + softmax + the top_k classes by (probability descending, class ascending); outputs on
+ *     the side `mem` names ([n_clips][top_k]; logits optional).  topk: that selection alone, on device logits.
+ *   last_flops: GEMM and attention FLOPs of the last forward / classify.  last_ms: its device time per stage. */
+typedef struct eioku_timesformer eioku_timesformer_t;
+int eioku_timesformer_create(int image, int patch, int frames, int hidden, int layers, int heads, int ffn, int labels, float ln_eps,
+                             eioku_timesformer_t** out);
+void eioku_timesformer_destroy(eioku_timesformer_t* m);
+int eioku_timesformer_num_tensors(const eioku_timesformer_t* m);
+int eioku_timesformer_tensor_info(const eioku_timesformer_t* m, int idx, char* name, size_t name_cap, int* rows, int* cols);
+int eioku_timesformer_set_tensor(eioku_timesformer_t* m, int idx, const float* host_data, size_t numel);
+int eioku_timesformer_set_norm(eioku_timesformer_t* m, const float* mean_rgb, const float* std_rgb);
+int eioku_timesformer_preprocess(eioku_timesformer_t* m, const uint8_t* bgr, int n_clips, int h, int w, const int32_t* xbounds,
+                                 const int32_t* xk, int kx, const int32_t* ybounds, const int32_t* yk, int ky, void* patches_out,
+                                 uint8_t* out_rgb_u8, int mem, void* stream);
+int eioku_timesformer_forward(eioku_timesformer_t* m, const void* patches, int n_clips, float* logits_out, float* hidden_out,
+                              void* stream);
+int eioku_timesformer_classify(eioku_timesformer_t* m, const uint8_t* bgr, int n_clips, int h, int w, const int32_t* xbounds,
+                               const int32_t* xk, int kx, const int32_t* ybounds, const int32_t* yk, int ky, int top_k,
+                               float* prob_out, int32_t* class_out, float* logits_out, int mem, void* stream);
+int eioku_timesformer_topk(eioku_timesformer_t* m, const float* logits, int n, int top_k, float* prob_out, int32_t* class_out,
+                           void* stream);
+int eioku_timesformer_last_flops(const eioku_timesformer_t* m, double* flops);
+int eioku_timesformer_last_ms(const eioku_timesformer_t* m, double* preprocess_ms, double* encoder_ms, double* head_ms);
+
 #ifdef __cplusplus
 }
 #endif
