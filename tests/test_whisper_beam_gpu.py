@@ -8,7 +8,6 @@ the supplied-logits test only.  Beams 3 and 5; 15 lanes and 20 lanes (past k_log
 The figures these tests print, as measured on an MI355X, are in DESIGN.md "K20b beam search".
 """
 import asyncio
-import json
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import pytest
 import whisper_beam_cases as cases
 import whisper_beam_oracle as wb
 import whisper_oracle as wo
+from whisper_testlib import recomputed_sums as _recomputed_sums, write_checkpoint as _write_checkpoint
 
 pytestmark = pytest.mark.gpu
 
@@ -116,28 +116,6 @@ def test_more_than_64_lanes_is_an_argument_error(model):
 
 
 # ---- 2. every hypothesis is self-consistent ----------------------------------------------------------------------------------------
-def _recomputed_sums(m: BeamModel, mel, rows):
-    """rows: [(window, tokens sampled incl. a closing EOT)].  Teacher-forces prompt + tokens on the device and sums the
-    log-probabilities of the tokens under the oracle's rules and log-softmax in float64."""
-    cfg, P = m.cfg, len(m.prompt)
-    T = P + max(len(t) for _, t in rows) - 1
-    ids = np.full((len(rows), T), cfg["eot"], dtype=np.int32)
-    for r, (_, toks) in enumerate(rows):
-        ids[r, :P + len(toks) - 1] = (m.prompt + list(toks))[:-1]
-    m.dev.encode(len(rows), mel[[b for b, _ in rows]])
-    logits = m.dev.forced_logits(ids).astype(np.float64)
-    sums = []
-    for r, (_, toks) in enumerate(rows):
-        total = 0.0
-        for i, t in enumerate(toks):
-            z = wo.apply_rules(logits[r, P - 1 + i], list(toks[:i]), cfg)
-            if wo.text_suppressed(z, cfg):
-                z[:cfg["timestamp_begin"]] = -np.inf
-            total += z[t] - wo._lse(z)
-        sums.append(total)
-    return sums
-
-
 def test_every_hypothesis_and_the_greedy_yardstick_are_self_consistent(either_model):
     m = either_model
     W, mel = 5, m.mel("w5_b4")
@@ -372,30 +350,6 @@ def test_end_to_end_segments_equal_the_cutter_on_the_oracles_best_hypotheses(mod
     limit = log[1][2][0] // 16 if len(log) > 1 else 10 ** 9      # ms at which the second window starts
     first = [s for s in want["segments"] if s["end_ms"] <= limit]
     assert len(first) >= 1 and got["segments"][:len(first)] == first
-
-
-def _write_checkpoint(root, cfg, weights):
-    root.mkdir(parents=True)
-    (root / "config.json").write_text(json.dumps({
-        "d_model": cfg["d_model"], "encoder_attention_heads": cfg["heads"], "decoder_attention_heads": cfg["heads"],
-        "encoder_layers": cfg["enc_layers"], "decoder_layers": cfg["dec_layers"], "encoder_ffn_dim": cfg["enc_ffn"],
-        "decoder_ffn_dim": cfg["dec_ffn"], "vocab_size": cfg["vocab"], "num_mel_bins": cfg["n_mels"],
-        "max_source_positions": cfg["max_source_positions"], "max_target_positions": cfg["max_target_positions"],
-        "decoder_start_token_id": cfg["sot"], "eos_token_id": cfg["eot"]}))
-    (root / "generation_config.json").write_text(json.dumps({
-        "no_timestamps_token_id": cfg["no_timestamps"], "no_speech_token_id": cfg["no_speech"],
-        "lang_to_id": {f"<|{c}|>": i for c, i in zip(cfg["lang_codes"], cfg["lang_ids"])},
-        "task_to_id": {"transcribe": cfg["transcribe"], "translate": cfg["translate"]}, "suppress_tokens": cfg["suppress"],
-        "begin_suppress_tokens": cfg["begin_suppress"], "max_initial_timestamp_index": cfg["max_initial_timestamp_index"]}))
-    (root / "vocab.json").write_text(json.dumps({f"Ġw{i}": i for i in range(cfg["eot"])}))
-    header, blobs, off = {}, [], 0
-    for k, v in weights.items():
-        raw = v.numpy().astype("<f4").tobytes()
-        header[k] = {"dtype": "F32", "shape": list(v.shape), "data_offsets": [off, off + len(raw)]}
-        blobs.append(raw)
-        off += len(raw)
-    h = json.dumps(header).encode()
-    (root / "model.safetensors").write_bytes(len(h).to_bytes(8, "little") + h + b"".join(blobs))
 
 
 def test_transcribe_video_with_beam_size_5_through_model_manager(model, tmp_path):

@@ -6,13 +6,13 @@ vocabulary tail).  Model B: the same widths with the real layout, 51865 ids and 
 Measured on an MI355X (printed by the tests, copied into DESIGN.md "K19 / K20"): see the table there.
 """
 import asyncio
-import json
 
 import numpy as np
 import pytest
 import torch
 
 import whisper_oracle as wo
+from whisper_testlib import write_checkpoint as _write_checkpoint
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +34,13 @@ def _dims(cfg: dict) -> dict:
 class Model:
     """One test model: the device transcriber, both oracles, and the oracle's greedy decode of the fixture audio."""
 
-    def __init__(self, cfg, seed, audio_seeds, seconds):
+    def __init__(self, cfg, seed, audio_seeds, seconds, new_tokens=NEW_TOKENS, qk_scale=4.0):
         from eioku_amd.transcribe import WhisperTranscriber
 
-        self.cfg = cfg
+        self.cfg, self.new_tokens = cfg, new_tokens
         tb = cfg["timestamp_begin"]
         boost = {cfg["eot"]: BOOST, **{tb + i: BOOST for i in range(cfg["vocab"] - tb)}}
-        self.weights = wo.random_weights(cfg, seed, boost)
+        self.weights = wo.random_weights(cfg, seed, boost, qk_scale)
         self.o32 = wo.Oracle(cfg, self.weights, fp16=False)
         self.o16 = wo.Oracle(cfg, self.weights, fp16=True)
         self.dev = WhisperTranscriber(_dims(cfg), {k: v.numpy() for k, v in self.weights.items()})
@@ -50,7 +50,7 @@ class Model:
         self.mel = np.stack([wo.log_mel(a, 0, self.frames, cfg["n_mels"]) for a in self.audios])
         self.enc32 = self.o32.encode(self.mel)
         self.enc16 = self.o16.encode(self.mel)
-        self.greedy16 = self.o16.greedy(self.enc16, self.prompt, NEW_TOKENS)
+        self.greedy16 = self.o16.greedy(self.enc16, self.prompt, new_tokens)
         self._drift = None
 
     def position_drift(self) -> np.ndarray:
@@ -91,7 +91,7 @@ def _fixture_is_useful(m: Model):
     for i in range(len(toks)):
         for j in range(i + 1, len(toks)):
             same = sum(a == b for a, b in zip(toks[i], toks[j]))
-            assert same < NEW_TOKENS / 2, f"audios {i} and {j} agree in {same} positions"
+            assert same < m.new_tokens / 2, f"audios {i} and {j} agree in {same} positions"
 
 
 def test_fixtures_decode_varied_audio_dependent_tokens(model_a, model_b):
@@ -360,30 +360,6 @@ def test_end_to_end_segments_equal_the_cutter_on_the_oracles_tokens(model_a, mod
 
 
 # ---- smoke: the public entry point -----------------------------------------------------------------------------------------------
-def _write_checkpoint(root, cfg, weights):
-    root.mkdir(parents=True)
-    (root / "config.json").write_text(json.dumps({
-        "d_model": cfg["d_model"], "encoder_attention_heads": cfg["heads"], "decoder_attention_heads": cfg["heads"],
-        "encoder_layers": cfg["enc_layers"], "decoder_layers": cfg["dec_layers"], "encoder_ffn_dim": cfg["enc_ffn"],
-        "decoder_ffn_dim": cfg["dec_ffn"], "vocab_size": cfg["vocab"], "num_mel_bins": cfg["n_mels"],
-        "max_source_positions": cfg["max_source_positions"], "max_target_positions": cfg["max_target_positions"],
-        "decoder_start_token_id": cfg["sot"], "eos_token_id": cfg["eot"]}))
-    (root / "generation_config.json").write_text(json.dumps({
-        "no_timestamps_token_id": cfg["no_timestamps"], "no_speech_token_id": cfg["no_speech"],
-        "lang_to_id": {f"<|{c}|>": i for c, i in zip(cfg["lang_codes"], cfg["lang_ids"])},
-        "task_to_id": {"transcribe": cfg["transcribe"], "translate": cfg["translate"]}, "suppress_tokens": cfg["suppress"],
-        "begin_suppress_tokens": cfg["begin_suppress"], "max_initial_timestamp_index": cfg["max_initial_timestamp_index"]}))
-    (root / "vocab.json").write_text(json.dumps({f"Ġw{i}": i for i in range(cfg["eot"])}))
-    header, blobs, off = {}, [], 0
-    for k, v in weights.items():
-        raw = v.numpy().astype("<f4").tobytes()
-        header[k] = {"dtype": "F32", "shape": list(v.shape), "data_offsets": [off, off + len(raw)]}
-        blobs.append(raw)
-        off += len(raw)
-    h = json.dumps(header).encode()
-    (root / "model.safetensors").write_bytes(len(h).to_bytes(8, "little") + h + b"".join(blobs))
-
-
 def test_smoke_transcribe_video_through_model_manager(model_a, tmp_path):
     from eioku_amd.model_manager import ModelManager
 

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 N_FFT, HOP, N_BINS = 400, 160, 201
 
 
-# ---- configs of the two test models -------------------------------------------------------------------------------------
+# ---- configs of the four test models ------------------------------------------------------------------------------------
 def model_a_config() -> dict:
     """d 128, 2 heads, 2 + 2 layers, ffn 512, ctx 100 (200-frame windows), 1003 ids with a layout of its own."""
     return {"n_mels": 80, "d_model": 128, "heads": 2, "enc_layers": 2, "dec_layers": 2, "enc_ffn": 512, "dec_ffn": 512,
@@ -37,6 +37,26 @@ def model_b_config() -> dict:
             "suppress": [1, 2, 7, 8, 9, 10, 14, 25, 26, 27, 28, 29, 31, 58, 59, 60, 61, 62, 63, 90, 91, 92, 93, 359, 503, 522,
                          50258, 50358, 50359, 50360, 50361, 50362] + list(range(50259, 50358)),
             "begin_suppress": [220, 50257]}
+
+
+def model_c_config() -> dict:
+    """The large-v3 id layout (51866 ids, 100 languages, 128 mel bins, every special id one above model B's) at the narrowest
+    real width: d 384 (256 threads take a second, partial trip over it), 6 heads, 2 + 3 layers, ffn 1536 / 768, ctx 200."""
+    return {"n_mels": 128, "d_model": 384, "heads": 6, "enc_layers": 2, "dec_layers": 3, "enc_ffn": 1536, "dec_ffn": 768,
+            "vocab": 51866, "max_source_positions": 200, "max_target_positions": 448,
+            "sot": 50258, "eot": 50257, "lang_ids": list(range(50259, 50359)),
+            "lang_codes": ["en"] + [f"l{i}" for i in range(1, 100)],
+            "translate": 50359, "transcribe": 50360, "no_speech": 50363, "no_timestamps": 50364, "timestamp_begin": 50365,
+            "max_initial_timestamp_index": 50,
+            "suppress": [t for t in model_b_config()["suppress"] if t < 50257] + [50258, 50359, 50360, 50361, 50362, 50363]
+                        + list(range(50259, 50359)),
+            "begin_suppress": [220, 50257]}
+
+
+def model_d_config() -> dict:
+    """Model A's id layout and ctx at large-v3's widths: d 1280, 20 heads, 128 mel bins, 1 + 1 layers, ffn 5120."""
+    return {**model_a_config(), "n_mels": 128, "d_model": 1280, "heads": 20, "enc_layers": 1, "dec_layers": 1,
+            "enc_ffn": 5120, "dec_ffn": 5120}
 
 
 # ---- log-mel ------------------------------------------------------------------------------------------------------------
@@ -88,10 +108,11 @@ def sinusoids(length: int, channels: int) -> torch.Tensor:
     return torch.cat([t.sin(), t.cos()], dim=1)
 
 
-def random_weights(cfg: dict, seed: int, boost: dict | None = None) -> dict:
+def random_weights(cfg: dict, seed: int, boost: dict | None = None, qk_scale: float = 4.0) -> dict:
     """He-scaled linear weights, embeddings std 0.1, q / k projections x 4, LayerNorm gains 1 +- 0.1, biases std 0.1 - the
     recipe under which random weights decode audio-dependent, varied tokens.  ``boost`` {id: amount} raises embedding rows
-    along the final LayerNorm's bias direction, which makes those ids (EOT, timestamps) likelier at every step."""
+    along the final LayerNorm's bias direction, which makes those ids (EOT, timestamps) likelier at every step.  ``qk_scale``
+    below 4 softens every softmax: rounding errors of q and k are amplified less."""
     g = torch.Generator().manual_seed(seed)
     d = cfg["d_model"]
     w: dict[str, torch.Tensor] = {}
@@ -106,8 +127,8 @@ def random_weights(cfg: dict, seed: int, boost: dict | None = None) -> dict:
         w[name + ".bias"] = torch.randn(d, generator=g) * 0.1
 
     def attn(p, lnp):
-        lin(p + "q_proj", d, d, scale=4.0)
-        lin(p + "k_proj", d, d, bias=False, scale=4.0)
+        lin(p + "q_proj", d, d, scale=qk_scale)
+        lin(p + "k_proj", d, d, bias=False, scale=qk_scale)
         lin(p + "v_proj", d, d)
         lin(p + "out_proj", d, d)
         lnorm(lnp)
