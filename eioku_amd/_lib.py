@@ -65,6 +65,7 @@ SIGNATURES = {
     "eioku_debug_conv_epi": (C.c_int, [C.POINTER(C.c_int), C.c_int]),
     "eioku_debug_conv_plan": (C.c_int, [C.c_int] * 9 + [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "eioku_yolo_create": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
+    "eioku_yolo_create_pose": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "eioku_yolo_destroy": (None, [C.c_void_p]),
     "eioku_yolo_num_convs": (C.c_int, [C.c_void_p]),
     "eioku_yolo_conv_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int),
@@ -72,10 +73,19 @@ SIGNATURES = {
     "eioku_yolo_set_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "eioku_yolo_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_void_p), C.c_void_p]),
+    "eioku_yolo_forward_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]),
     "eioku_yolo_last_conv_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_yolo_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_yolo_detect_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eioku_yolo_postprocess_pose": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
+                                              C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_float, C.c_float,
+                                              C.c_int, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eioku_letterbox_f16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eioku_yolo_postprocess": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int),
@@ -163,6 +173,10 @@ SIGNATURES = {
     "eioku_iresnet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eioku_iresnet_embed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                       C.c_void_p]),
+    "eioku_iresnet_crop_aligned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_iresnet_embed_aligned": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "eioku_iresnet_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_craft_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "eioku_craft_destroy": (None, [C.c_void_p]),

@@ -6,6 +6,10 @@
 //                    outside-frame samples 0.  Tap positions / weights come from the host (float64, 11-bit fixed
 //                    point); the kernel is integer only (u8 result, rounded), then arcface_torch's (v / 255 - 0.5) / 0.5
 //                    in fp32 -> fp16 NHWC8 (R, G, B, 5 zero channels)
+//   k_face_warp      K13c: the aligned crop - cv2.warpAffine(frame, M, (112, 112), INTER_LINEAR, borderValue = 0) in
+//                    OpenCV's fixed point (M inverted in float64 without FMA contraction, coordinates in 1/1024 rounded
+//                    to 1/32, four taps with 5-bit weights), then K13a's normalisation and output format.  M is the
+//                    similarity transform of the detector's five landmarks onto ArcFace's template (faces.py)
 //   the IBasicBlocks K13b: K4's 3x3 kernels (conv.hip) with BatchNorm folded into each conv that precedes it; the 1x1 / s2
 //                    downsample as the centre tap of a 3x3 / s2 (as resnet.hip).  Two things do not fold: the block's
 //                    leading bn1 sits before a zero-padded conv (folding its shift is wrong on the border), and PReLU
@@ -80,6 +84,82 @@ __global__ __launch_bounds__(256) void k_face_crop(const uint8_t* __restrict__ b
 #pragma unroll
   for (int j = 3; j < 8; ++j) v[j] = (_Float16)0.f;
   *reinterpret_cast<uint4*>(out + (size_t)i * 8) = __builtin_bit_cast(uint4, v);
+}
+
+// ---- K13c: warpAffine onto the 112 x 112 template + normalise --------------------------------------------------------
+// round-half-to-even to int32, saturating; NaN -> 0 (defined for every double, and restated so by the oracle)
+__device__ __forceinline__ int rne_i32(double v) {
+  v = rint(v);
+  if (!(v == v)) return 0;
+  return (int)fmin(fmax(v, -2147483648.0), 2147483647.0);
+}
+
+// OpenCV's own inversion of the 2 x 3 matrix (imgproc/imgwarp.cpp, warpAffine without WARP_INVERSE_MAP): every product
+// and sum is rounded on its own.  The pragma takes the `contract` flag off the operations of this function, so they stay
+// separate v_mul_f64 / v_add_f64 wherever it is inlined (hipcc's default is -ffp-contract=fast).
+__device__ __forceinline__ void warp_invert(const double* __restrict__ m, double* __restrict__ o) {
+#pragma clang fp contract(off)
+  double M0 = m[0], M1 = m[1], M2 = m[2], M3 = m[3], M4 = m[4], M5 = m[5];
+  double D = M0 * M4 - M1 * M3;
+  D = D != 0 ? 1.0 / D : 0.0;
+  const double A11 = M4 * D, A22 = M0 * D;
+  M0 = A11;
+  M1 *= -D;
+  M3 *= -D;
+  M4 = A22;
+  const double b1 = -M0 * M2 - M1 * M5, b2 = -M3 * M2 - M4 * M5;
+  o[0] = M0; o[1] = M1; o[2] = b1; o[3] = M3; o[4] = M4; o[5] = b2;
+}
+
+// source position of output pixel (x, y) in 1/32 pixels: (X0 + adelta[x]) >> 5 of OpenCV's WarpAffineInvoker
+__device__ __forceinline__ void warp_coord(const double* __restrict__ inv, int x, int y, long long* X, long long* Y) {
+#pragma clang fp contract(off)
+  const int adelta = rne_i32(inv[0] * x * 1024.0), bdelta = rne_i32(inv[3] * x * 1024.0);
+  const int X0 = rne_i32((inv[1] * y + inv[2]) * 1024.0), Y0 = rne_i32((inv[4] * y + inv[5]) * 1024.0);
+  *X = ((long long)X0 + 16 + adelta) >> 5;
+  *Y = ((long long)Y0 + 16 + bdelta) >> 5;
+}
+
+// grid (ceil(112 * 112 / 256), m): one grid row per face, so the face's slot, flag and matrix are uniform in a workgroup.
+// mats [m][6] float64 (the forward matrix M: frame -> crop); use_box (optional) [m]: non-zero = this face keeps the crop
+// K13a wrote
+__global__ __launch_bounds__(256) void k_face_warp(const uint8_t* __restrict__ bgr, int h, int w, const int* __restrict__ slot,
+                                                   const double* __restrict__ mats, const int* __restrict__ use_box,
+                                                   __half* __restrict__ out) {
+  const int c = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= kCrop * kCrop || (use_box && use_box[c])) return;
+  const int ox = p % kCrop, oy = p / kCrop;
+  double inv[6];
+  warp_invert(mats + (size_t)6 * c, inv);
+  long long X, Y;
+  warp_coord(inv, ox, oy, &X, &Y);
+  const int sx = (int)min(max(X >> 5, -32768ll), 32767ll), sy = (int)min(max(Y >> 5, -32768ll), 32767ll);
+  const int fx = (int)(X & 31), fy = (int)(Y & 31);
+  const uint8_t* f = bgr + (size_t)slot[c] * h * w * 3;
+  int acc0 = 512, acc1 = 512, acc2 = 512;
+#pragma unroll
+  for (int dy = 0; dy < 2; ++dy) {
+    const int yy = sy + dy, wy = dy ? fy : 32 - fy;
+    if ((unsigned)yy >= (unsigned)h) continue;
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+      const int xx = sx + dx, wx = dx ? fx : 32 - fx;
+      if ((unsigned)xx >= (unsigned)w) continue;
+      const uint8_t* q = f + ((size_t)yy * w + xx) * 3;
+      const int k = wy * wx;
+      acc0 += k * q[0];
+      acc1 += k * q[1];
+      acc2 += k * q[2];
+    }
+  }
+  const int b = acc0 >> 10, g = acc1 >> 10, r = acc2 >> 10;
+  half8 v;
+  v[0] = (_Float16)(((float)r / 255.0f - 0.5f) / 0.5f);
+  v[1] = (_Float16)(((float)g / 255.0f - 0.5f) / 0.5f);
+  v[2] = (_Float16)(((float)b / 255.0f - 0.5f) / 0.5f);
+#pragma unroll
+  for (int j = 3; j < 8; ++j) v[j] = (_Float16)0.f;
+  *reinterpret_cast<uint4*>(out + ((size_t)c * kCrop * kCrop + p) * 8) = __builtin_bit_cast(uint4, v);
 }
 
 // ---- per-channel passes over NHWC fp16 (C % 8 == 0) -----------------------------------------------------------------
@@ -374,7 +454,10 @@ struct eioku_iresnet {
   DevBuf<float> emb;                 // [m][512] (host outputs)
   DevBuf<uint8_t> src;               // staged host frames
   DevBuf<int> taps;                  // [m][2][112][2] + slot [m]
+  DevBuf<double> mats;               // K13c: [m][6] forward matrices
+  DevBuf<int> warp_ix;               // K13c: slot [m] + box flag [m]
   std::vector<int> htaps;
+  std::vector<int32_t> hslots;       // K13c: the slots of an embed_aligned call (kept until its copy has run)
   double flops_last = 0;
 };
 
@@ -513,6 +596,78 @@ int launch_crop(const uint8_t* d_src, int h, int w, const int* d_slot, const int
   const long long work = (long long)mc * kCrop * kCrop;
   hipLaunchKernelGGL(k_face_crop, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, d_src, h, w, d_slot, d_taps, mc, out);
   EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+// K13c's per-face inputs -> device: slots (checked against n) and matrices (finite wherever the face is warped)
+int upload_warp(eioku_iresnet* r, int n, const int32_t* slots, const double* M, const int32_t* use_box, int m, hipStream_t stream) {
+  for (int i = 0; i < m; ++i) {
+    EIOKU_REQUIRE(slots[i] >= 0 && slots[i] < n, "face %d: frame slot %d outside [0, %d)", i, slots[i], n);
+    if (use_box && use_box[i]) continue;
+    for (int k = 0; k < 6; ++k) EIOKU_REQUIRE(std::isfinite(M[(size_t)6 * i + k]), "face %d: matrix entry %d is not finite", i, k);
+  }
+  EIOKU_TRY(r->mats.grow((size_t)6 * m));
+  EIOKU_TRY(r->warp_ix.grow((size_t)2 * m));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(r->mats, M, (size_t)6 * m * sizeof(double), hipMemcpyHostToDevice, stream));
+  EIOKU_HIP_CHECK(hipMemcpyAsync(r->warp_ix, slots, (size_t)m * 4, hipMemcpyHostToDevice, stream));
+  if (use_box) EIOKU_HIP_CHECK(hipMemcpyAsync(r->warp_ix + m, use_box, (size_t)m * 4, hipMemcpyHostToDevice, stream));
+  return EIOKU_OK;
+}
+
+// faces [c0, c0 + mc) of the uploaded lists -> out rows 0 .. mc - 1
+int launch_warp(eioku_iresnet* r, const uint8_t* d_src, int h, int w, int m, int c0, int mc, bool flags, __half* out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_face_warp, dim3((kCrop * kCrop + 255) / 256, (unsigned)mc), dim3(256), 0, stream, d_src, h, w,
+                     r->warp_ix.p + c0, r->mats.p + (size_t)6 * c0, flags ? r->warp_ix.p + m + c0 : nullptr, out);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+// eioku_iresnet_embed / _embed_aligned: M == nullptr is the box-crop path, launch for launch what it always was
+int embed_faces(eioku_iresnet* r, const uint8_t* bgr, int n, int h, int w, const float* boxes, const double* M,
+                const int32_t* use_box, int m, float* out, int mem, hipStream_t stream) {
+  EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(r && n >= 0 && h > 0 && w > 0 && m >= 0, "bad argument");
+  EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
+  if (m == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(bgr && boxes && out && n > 0, "NULL buffer");
+  int *d_taps, *d_slot;
+  int rc = upload_taps(r, n, h, w, boxes, m, stream, &d_taps, &d_slot);
+  if (rc) return rc;
+  if (M) {
+    r->hslots.resize((size_t)m);
+    for (int i = 0; i < m; ++i) r->hslots[i] = (int32_t)boxes[(size_t)5 * i];  // (upload_taps has checked them)
+    rc = upload_warp(r, n, r->hslots.data(), M, use_box, m, stream);
+    if (rc) return rc;
+  }
+  const uint8_t* d_src;
+  rc = stage_host(r->src, bgr, (size_t)n * h * w * 3, mem, stream, &d_src);
+  if (rc) return rc;
+  rc = ensure_cap(r, std::min(m, kChunk));
+  if (rc) return rc;
+  double flops = 0;
+  for (int c0 = 0; c0 < m; c0 += kChunk) {
+    const int mc = std::min(kChunk, m - c0);
+    bool any_box = !M, any_warp = false;
+    for (int i = c0; M && i < c0 + mc; ++i) (use_box[i] ? any_box : any_warp) = true;
+    if (any_box) {
+      rc = launch_crop(d_src, h, w, d_slot + c0, d_taps + (size_t)c0 * 4 * kCrop, mc, r->crop, stream);
+      if (rc) return rc;
+    }
+    if (any_warp) {  // after K13a on the same stream: the warped faces' rows are overwritten whole
+      rc = launch_warp(r, d_src, h, w, m, c0, mc, true, r->crop, stream);
+      if (rc) return rc;
+    }
+    float* dst = mem == EIOKU_MEM_HOST ? r->emb : out + (size_t)c0 * kFeat;
+    rc = run_iresnet(r, mc, -1, nullptr, dst, stream);
+    if (rc) return rc;
+    flops += r->flops_last;
+    if (mem == EIOKU_MEM_HOST) {
+      EIOKU_HIP_CHECK(hipMemcpyAsync(out + (size_t)c0 * kFeat, r->emb, (size_t)mc * kFeat * 4, hipMemcpyDeviceToHost, stream));
+      EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // r->emb is reused by the next pass
+    }
+  }
+  r->flops_last = flops;
+  EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
   return EIOKU_OK;
 }
 
@@ -659,37 +814,35 @@ int eioku_iresnet_forward(eioku_iresnet_t* r, const void* in_f16, int m, int upt
 // Synchronous.
 int eioku_iresnet_embed(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const float* boxes, int m, float* out,
                         int mem, void* stream_) {
+  return embed_faces(r, bgr, n, h, w, boxes, nullptr, nullptr, m, out, mem, (hipStream_t)stream_);
+}
+
+// K13c alone (parity helper): faces warped by M HOST float64 [m][6] (frame -> 112 x 112 crop, cv2.warpAffine's M) from
+// frame slots HOST int32 [m] -> out_f16 [m][112][112][8] fp16 (device).  Synchronous.
+int eioku_iresnet_crop_aligned(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const int32_t* slots, const double* M,
+                               int m, void* out_f16, int mem, void* stream_) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(r && n >= 0 && h > 0 && w > 0 && m >= 0, "bad argument");
   EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
   if (m == 0) return EIOKU_OK;
-  EIOKU_REQUIRE(bgr && boxes && out && n > 0, "NULL buffer");
+  EIOKU_REQUIRE(bgr && slots && M && out_f16 && n > 0, "NULL buffer");
   hipStream_t stream = (hipStream_t)stream_;
-  int *d_taps, *d_slot;
-  int rc = upload_taps(r, n, h, w, boxes, m, stream, &d_taps, &d_slot);
-  if (rc) return rc;
+  EIOKU_TRY(upload_warp(r, n, slots, M, nullptr, m, stream));
   const uint8_t* d_src;
-  rc = stage_host(r->src, bgr, (size_t)n * h * w * 3, mem, stream, &d_src);
-  if (rc) return rc;
-  rc = ensure_cap(r, std::min(m, kChunk));
-  if (rc) return rc;
-  double flops = 0;
-  for (int c0 = 0; c0 < m; c0 += kChunk) {
-    const int mc = std::min(kChunk, m - c0);
-    rc = launch_crop(d_src, h, w, d_slot + c0, d_taps + (size_t)c0 * 4 * kCrop, mc, r->crop, stream);
-    if (rc) return rc;
-    float* dst = mem == EIOKU_MEM_HOST ? r->emb : out + (size_t)c0 * kFeat;
-    rc = run_iresnet(r, mc, -1, nullptr, dst, stream);
-    if (rc) return rc;
-    flops += r->flops_last;
-    if (mem == EIOKU_MEM_HOST) {
-      EIOKU_HIP_CHECK(hipMemcpyAsync(out + (size_t)c0 * kFeat, r->emb, (size_t)mc * kFeat * 4, hipMemcpyDeviceToHost, stream));
-      EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // r->emb is reused by the next pass
-    }
-  }
-  r->flops_last = flops;
+  EIOKU_TRY(stage_host(r->src, bgr, (size_t)n * h * w * 3, mem, stream, &d_src));
+  for (int c0 = 0; c0 < m; c0 += 32768)  // a grid's y extent is 65535
+    EIOKU_TRY(launch_warp(r, d_src, h, w, m, c0, std::min(32768, m - c0), false, (__half*)out_f16 + (size_t)c0 * kCrop * kCrop * 8, stream));
   EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
   return EIOKU_OK;
+}
+
+// eioku_iresnet_embed with aligned crops: face i is warped by M[i] (K13c) unless use_box[i] != 0 (HOST int32 [m]), which
+// keeps the box crop of boxes[i] (K13a) - the fallback for faces whose landmarks give no usable transform.  The frame
+// slot of every face is boxes[i][0].  Same passes of 256, same outputs.  Synchronous.
+int eioku_iresnet_embed_aligned(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const float* boxes, const double* M,
+                                const int32_t* use_box, int m, float* out, int mem, void* stream_) {
+  EIOKU_REQUIRE(m <= 0 || (M && use_box), "NULL buffer");
+  return embed_faces(r, bgr, n, h, w, boxes, M, use_box, m, out, mem, (hipStream_t)stream_);
 }
 
 int eioku_iresnet_last_flops(const eioku_iresnet_t* r, double* flops) {

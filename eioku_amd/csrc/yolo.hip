@@ -8,6 +8,9 @@
 //   10 Up 11 Cat(10,6) 12 C2f(c5+c4,c4,d0) 13 Up 14 Cat(13,4) 15 C2f(c4+c3,c3,d0)
 //   16 Conv(c3,c3,3,2) 17 Cat(16,12) 18 C2f(c3+c4,c4,d0) 19 Conv(c4,c4,3,2) 20 Cat(19,9)
 //   21 C2f(c4+c5,c5,d0) 22 Detect(nc; P3=15,P4=18,P5=21)
+// A Pose head (eioku_yolo_create_pose, nk = K * 3 > 0; yolov8n-face's five landmarks) adds per level
+//   cv4[l] = Conv(cx,c4,3) -> Conv(c4,c4,3) -> Conv2d(c4,nk,1), c4 = max(c3 / 4, nk), to fp32 maps [N,Hl,Wl,nk]
+// as nine more dense conv ops behind the Detect ones; K6p (yolo_ops.hip) decodes them for the kept detections only.
 #include <algorithm>
 #include <array>
 #include <memory>
@@ -40,7 +43,8 @@ struct Op {
   int out_buf, out_off;
   int res_buf = -1, res_off = 0;
   int act = kActSiLU;
-  int f32_out = -1;  // index into head outputs (0..5) or -1
+  int f32_out = -1;  // index into head outputs (0..5; 6..8 the keypoint maps) or -1
+  bool pose = false;  // a cv4 (keypoint branch) op: runs only when the caller asks for keypoints
   bool chain_next = false;     // this op's output is read by the NEXT op only, before anything overwrites it (C2f's shared tmp)
   bool sole_consumer = false;  // the NEXT op is the only reader of this op's output buffer (set by build_graph)
   int up_consumer = -1;        // kUp: index of the 1x1 conv that can read the low-resolution source in place
@@ -50,7 +54,7 @@ struct Op {
 }  // namespace
 
 struct eioku_yolo {
-  int ch[5], depth[4], nc;
+  int ch[5], depth[4], nc, nk = 0;  // nk: keypoint channels (K * 3) of a Pose head, 0 = Detect
   ConvStack convs;
   std::vector<Buf> bufs;
   std::vector<Op> ops;
@@ -58,7 +62,8 @@ struct eioku_yolo {
   int head_src[3];
   // per-shape workspace
   int cur_n = 0, cur_h = 0, cur_w = 0;
-  DevBuf<float> head[6];  // box P3,P4,P5 ; cls P3,P4,P5 (fp32)
+  DevBuf<float> head[9];  // box P3,P4,P5 ; cls P3,P4,P5 ; keypoints P3,P4,P5 (fp32)
+  DevBuf<float> kpts;     // [N][max_det][nk] decoded keypoints of the kept detections
   DevBuf<unsigned long long> clsmax[3];  // per anchor (argmax << 32 | max-logit bits): detect()'s class branch output
   DevBuf<int32_t> lvl;  // lazy box branch: [N][A] per-level lists of passing anchors, then [N][3] counts
   // deep lazy box branch: flat pixel lists [N*A] (anchors) + [9*N*A] (their neighbourhoods) + 6 counters, and the
@@ -197,6 +202,19 @@ void build_graph(eioku_yolo* y) {
     add_conv(y, "model.22.cv3." + i + ".1.conv", cc, cc, 3, 1, k1, 0, k2, 0);
     add_conv(y, "model.22.cv3." + i + ".2", cc, y->nc, 1, 1, k2, 0, -1, 0, -1, 0, kActNone, 3 + l);
   }
+  // Pose: the keypoint branch, behind every Detect op so that those keep their indices and their launch order
+  if (y->nk > 0) {
+    const int c4k = std::max(c3 / 4, y->nk), c4p = (c4k + 7) / 8 * 8;  // buffers hold whole 16-byte units
+    for (int l = 0; l < 3; ++l) {
+      const std::string i = std::to_string(l);
+      const int p1 = add_buf(y, 3 + l, c4p), p2 = add_buf(y, 3 + l, c4p);
+      const size_t first = y->ops.size();
+      add_conv(y, "model.22.cv4." + i + ".0.conv", srcc[l], c4k, 3, 1, src[l], 0, p1, 0);
+      add_conv(y, "model.22.cv4." + i + ".1.conv", c4k, c4k, 3, 1, p1, 0, p2, 0);
+      add_conv(y, "model.22.cv4." + i + ".2", c4k, y->nk, 1, 1, p2, 0, -1, 0, -1, 0, kActNone, 6 + l);
+      for (size_t j = first; j < y->ops.size(); ++j) y->ops[j].pose = true;
+    }
+  }
   // box branch per level: cv2.l.0 -> cv2.l.1 -> cv2.l.2 (f32_out = l); remember the two 3x3 ops
   for (size_t i = 0; i < y->ops.size(); ++i) {
     const Op& o2 = y->ops[i];
@@ -281,6 +299,7 @@ int prepare(eioku_yolo* y, int n, int h, int w) {
     EIOKU_TRY(grow_synced(y->head[l], px * 4 * kRegMax));
     EIOKU_TRY(grow_synced(y->head[3 + l], px * y->nc));
     EIOKU_TRY(grow_synced(y->clsmax[l], px));
+    if (y->nk > 0) EIOKU_TRY(grow_synced(y->head[6 + l], px * y->nk));
   }
   // A = anchors of the whole batch; one Cand is as large as four keys
   EIOKU_TRY(grow_synced(y->cands, A + (A + 3) / 4));
@@ -321,7 +340,7 @@ int record_pass_rate(eioku_yolo* y, int n, int A, hipStream_t stream) {
 }
 
 int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedInput* fused, double* flops_out,
-            bool clsmax = false, bool lazybox = false, bool lazydeep = false) {
+            bool clsmax = false, bool lazybox = false, bool lazydeep = false, bool kpts = false) {
   // EIOKU_UP_FUSE=0: upsample2x writes the upsampled tensor and the 1x1 reads it (byte-identity test of the fusion)
   static const bool up_off = env_off("EIOKU_UP_FUSE");
   double flops = 0;
@@ -336,6 +355,7 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
       skip_next = false;
       continue;
     }
+    if (op.pose && !kpts) continue;  // the keypoint branch: nobody reads it in this call
     const Buf& ib = y->bufs[op.in_buf];
     const int H = level_dim(h, ib.level), W = level_dim(w, ib.level);
     Slice in{ib.ptr, ib.ch, op.in_off};
@@ -442,7 +462,7 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
         if (rc) return rc;
         continue;
       }
-      if (clsmax && op.f32_out >= 3 && conv_clsmax_ok(cw, op.act))  // class branch: max / argmax words, no logit map
+      if (clsmax && op.f32_out >= 3 && op.f32_out < 6 && conv_clsmax_ok(cw, op.act))  // class branch: max / argmax words, no logit map
         rc = conv_forward(cw, in, n, H, W, Slice{}, nullptr, Slice{}, op.act, stream, nullptr, nullptr, kActNone,
                           y->clsmax[op.f32_out - 3]);
       else
@@ -482,12 +502,12 @@ int run_ops(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedI
 }
 
 int run_network(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const FusedInput* fused = nullptr,
-                bool clsmax = false, bool lazybox = false, bool lazydeep = false) {
+                bool clsmax = false, bool lazybox = false, bool lazydeep = false, bool kpts = false) {
   for (size_t i = 0; i < y->convs.set.size(); ++i)
     EIOKU_REQUIRE(y->convs.set[i], "conv %zu (%s) has no weights", i, y->convs.layers[i].name.c_str());
   // (replaying the forward as a hipGraph was built and measured on ROCm 7.2 / MI355X: 3.07 ms per bench step against
   // 3.03 ms for plain launches -- the gaps between dependent kernels are the GPU's, not the host's -- and removed)
-  return run_ops(y, n, h, w, stream, fused, &y->conv_flops_last, clsmax, lazybox, lazydeep);
+  return run_ops(y, n, h, w, stream, fused, &y->conv_flops_last, clsmax, lazybox, lazydeep, kpts);
 }
 
 }  // namespace
@@ -495,15 +515,22 @@ int run_network(eioku_yolo* y, int n, int h, int w, hipStream_t stream, const Fu
 extern "C" {
 
 int eioku_yolo_create(const int* ch5, const int* depth4, int nc, eioku_yolo** out) {
+  return eioku_yolo_create_pose(ch5, depth4, nc, 0, out);
+}
+
+// nk = K * 3 keypoint channels (x, y, visibility per keypoint; K <= 17) of an Ultralytics Pose head; 0 = a Detect head
+int eioku_yolo_create_pose(const int* ch5, const int* depth4, int nc, int nk, eioku_yolo** out) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(ch5 && depth4 && out, "NULL argument");
   EIOKU_REQUIRE(nc >= 1 && nc <= 1024, "nc %d out of range", nc);
+  EIOKU_REQUIRE(nk >= 0 && nk % 3 == 0 && nk <= 51, "nk %d must be 3 per keypoint for at most 17 keypoints", nk);
   for (int i = 0; i < 5; ++i) EIOKU_REQUIRE(ch5[i] >= 16 && ch5[i] % 16 == 0, "width ch[%d]=%d must be a multiple of 16", i, ch5[i]);
   for (int i = 0; i < 4; ++i) EIOKU_REQUIRE(depth4[i] >= 1 && depth4[i] <= 12, "depth[%d]=%d out of range", i, depth4[i]);
   auto* y = new eioku_yolo();
   for (int i = 0; i < 5; ++i) y->ch[i] = ch5[i];
   for (int i = 0; i < 4; ++i) y->depth[i] = depth4[i];
   y->nc = nc;
+  y->nk = nk;
   build_graph(y);
   *out = y;
   return EIOKU_OK;
@@ -530,22 +557,47 @@ int eioku_yolo_set_conv(eioku_yolo* y, int idx, const float* w_oihw, const float
   EIOKU_REQUIRE(y && idx >= 0 && idx < y->convs.size(), "bad conv index %d", idx);
   EIOKU_REQUIRE(w_oihw, "NULL weights");
   const ConvLayer& l = y->convs.layers[idx];
-  return y->convs.mark(idx, conv_weights_create(&y->convs.w[idx], l.cout, l.cin, l.k, l.stride, w_oihw, bias));
+  // The keypoint branch's width c4 = max(c3 / 4, nk) need not be a whole number of 8-channel units: its layers then run
+  // with zero weights (and zero bias: SiLU(0) = 0) on the padding channels, as model.0.conv does on channels 3..7
+  const int cin_p = (l.cin + 7) / 8 * 8;
+  int cout_p = l.cout;
+  for (const Op& o : y->ops)
+    if (o.kind == kConv && o.conv == idx && o.pose && o.f32_out < 0) cout_p = (l.cout + 7) / 8 * 8;
+  if (cin_p == l.cin && cout_p == l.cout)
+    return y->convs.mark(idx, conv_weights_create(&y->convs.w[idx], l.cout, l.cin, l.k, l.stride, w_oihw, bias));
+  const int taps = l.k * l.k;
+  std::vector<float> wp((size_t)cout_p * cin_p * taps, 0.f), bp((size_t)cout_p, 0.f);
+  for (int co = 0; co < l.cout; ++co) {
+    for (int ci = 0; ci < l.cin; ++ci)
+      for (int t = 0; t < taps; ++t) wp[((size_t)co * cin_p + ci) * taps + t] = w_oihw[((size_t)co * l.cin + ci) * taps + t];
+    if (bias) bp[co] = bias[co];
+  }
+  return y->convs.mark(idx, conv_weights_create(&y->convs.w[idx], cout_p, cin_p, l.k, l.stride, wp.data(), bp.data()));
 }
 
 int eioku_yolo_forward(eioku_yolo* y, const void* in_nhwc8, int n, int h, int w, float* const* box_out,
                        float* const* cls_out, void* stream_) {
+  return eioku_yolo_forward_pose(y, in_nhwc8, n, h, w, box_out, cls_out, nullptr, stream_);
+}
+
+// eioku_yolo_forward plus the three raw keypoint maps kpt_out[l] [n,h/s,w/s,nk] (fp32, device) of a Pose handle; with
+// kpt_out == NULL the keypoint branch does not run
+int eioku_yolo_forward_pose(eioku_yolo* y, const void* in_nhwc8, int n, int h, int w, float* const* box_out,
+                            float* const* cls_out, float* const* kpt_out, void* stream_) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(y && in_nhwc8, "NULL argument");
+  EIOKU_REQUIRE(!kpt_out || y->nk > 0, "this detector has no keypoint head");
   hipStream_t stream = (hipStream_t)stream_;
   int rc = prepare(y, n, h, w);
   if (rc) return rc;
   EIOKU_HIP_CHECK(hipMemcpyAsync(y->bufs[y->in_buf].ptr, in_nhwc8, (size_t)n * h * w * 8 * sizeof(__half),
                                  hipMemcpyDeviceToDevice, stream));
-  rc = run_network(y, n, h, w, stream);
+  rc = run_network(y, n, h, w, stream, nullptr, false, false, false, kpt_out != nullptr);
   if (rc) return rc;
   for (int l = 0; l < 3; ++l) {
     const size_t px = (size_t)n * level_dim(h, 3 + l) * level_dim(w, 3 + l);
+    if (kpt_out && kpt_out[l])
+      EIOKU_HIP_CHECK(hipMemcpyAsync(kpt_out[l], y->head[6 + l], px * y->nk * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (box_out && box_out[l])
       EIOKU_HIP_CHECK(hipMemcpyAsync(box_out[l], y->head[l], px * 64 * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (cls_out && cls_out[l])
@@ -568,8 +620,20 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
                       const int32_t* xofs, const int32_t* yofs, const int16_t* xalpha, const int16_t* ybeta,
                       float gain, float conf, float iou, int max_det, void* dets_out, int32_t* counts_out,
                       int mem, void* stream_) {
+  return eioku_yolo_detect_pose(y, bgr, n, h, w, lb_geom, xofs, yofs, xalpha, ybeta, gain, conf, iou, max_det, dets_out,
+                                counts_out, mem, stream_, nullptr);
+}
+
+// eioku_yolo_detect on a Pose handle, plus kpts_out [n][max_det][nk] fp32 (same side as dets_out): keypoint k of a kept
+// detection as (x, y, confidence) in original-frame pixels (K6p), rows past counts[i] zero.  kpts_out == NULL is
+// eioku_yolo_detect itself: the keypoint branch does not run, the launches are those of a Detect handle.
+int eioku_yolo_detect_pose(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, const int32_t* lb_geom,
+                           const int32_t* xofs, const int32_t* yofs, const int16_t* xalpha, const int16_t* ybeta,
+                           float gain, float conf, float iou, int max_det, void* dets_out, int32_t* counts_out,
+                           int mem, void* stream_, float* kpts_out) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(y && lb_geom, "NULL argument");
+  EIOKU_REQUIRE(!kpts_out || y->nk > 0, "this detector has no keypoint head");
   EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
   EIOKU_REQUIRE(n >= 0 && h > 0 && w > 0, "bad frame shape");
   if (n == 0) return EIOKU_OK;
@@ -664,7 +728,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   // last conv can (one cout tile: nc <= 128)
   bool cm = true;
   for (const Op& op : y->ops)
-    if (op.kind == kConv && op.f32_out >= 3) cm = cm && conv_clsmax_ok(y->convs.w[op.conv], op.act);
+    if (op.kind == kConv && op.f32_out >= 3 && op.f32_out < 6) cm = cm && conv_clsmax_ok(y->convs.w[op.conv], op.act);
   // ... and then only the anchors that pass the threshold need their 64 DFL logits: the box branch's last 1x1 conv
   // is evaluated by decode for those (one 64-row weight tile, whole 32-channel chunks)
   static const bool lazy_off = env_off("EIOKU_LAZY_BOX");
@@ -743,7 +807,7 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
     lbx.deep = deep;
   }
   // the counters are needed (for the next call's decision) whenever the lazy path runs
-  rc = run_network(y, n, p.out_h, p.out_w, stream, fuse ? &fi : nullptr, cm, lazy, deep);
+  rc = run_network(y, n, p.out_h, p.out_w, stream, fuse ? &fi : nullptr, cm, lazy, deep, kpts_out != nullptr);
   if (rc) return rc;
 
   int Hl[3], Wl[3], A = 0;
@@ -778,6 +842,16 @@ int eioku_yolo_detect(eioku_yolo* y, const uint8_t* bgr, int n, int h, int w, co
   rc = nms_forward(y->cands, y->counts, n, A, iou, max_det, 7680.0f, sp, y->dets, y->counts + n, stream);
   if (rc) return rc;
   const hipMemcpyKind kind = mem == EIOKU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (kpts_out) {
+    const float* kp[3] = {y->head[6], y->head[7], y->head[8]};
+    // unrounded padding: scale_coords, unlike scale_boxes, does not round it
+    const ScaleParams kps{gain, (float)(((double)p.out_w - (double)w * (double)gain) / 2), (float)(((double)p.out_h - (double)h * (double)gain) / 2),
+                          (float)w, (float)h};
+    EIOKU_TRY(grow_synced(y->kpts, (size_t)n * max_det * y->nk));
+    rc = kpts_decode_forward(kp, y->dets, y->counts + n, n, Hl, Wl, y->nk, max_det, kps, y->kpts, stream);
+    if (rc) return rc;
+    EIOKU_HIP_CHECK(hipMemcpyAsync(kpts_out, y->kpts, (size_t)n * max_det * y->nk * sizeof(float), kind, stream));
+  }
   EIOKU_HIP_CHECK(hipMemcpyAsync(dets_out, y->dets, (size_t)n * max_det * sizeof(Det), kind, stream));
   EIOKU_HIP_CHECK(hipMemcpyAsync(counts_out, y->counts + n, (size_t)n * sizeof(int32_t), kind, stream));
   if (mem == EIOKU_MEM_HOST) EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
@@ -822,7 +896,18 @@ int eioku_letterbox_f16(const uint8_t* bgr_dev, int n, int h, int w, const int32
 int eioku_yolo_postprocess(const float* const* box_dev, const float* const* cls_dev, int n, const int* hl,
                            const int* wl, int nc, float conf, float iou, int max_det, float gain, int pad_x,
                            int pad_y, int src_w, int src_h, void* dets_dev, int32_t* counts_dev, void* stream_) {
+  return eioku_yolo_postprocess_pose(box_dev, cls_dev, nullptr, n, hl, wl, nc, 0, conf, iou, max_det, gain, pad_x, pad_y, 0.f,
+                                     0.f, src_w, src_h, dets_dev, counts_dev, nullptr, stream_);
+}
+
+// K6 + K7 + K6p alone: eioku_yolo_postprocess plus the keypoint maps kpt_dev[l] [n,hl,wl,nk] -> kpts_dev [n][max_det][nk]
+// (device).  kpad_x / kpad_y: scale_coords' unrounded padding (pad_x / pad_y stay scale_boxes' rounded one)
+int eioku_yolo_postprocess_pose(const float* const* box_dev, const float* const* cls_dev, const float* const* kpt_dev, int n,
+                                const int* hl, const int* wl, int nc, int nk, float conf, float iou, int max_det, float gain,
+                                int pad_x, int pad_y, float kpad_x, float kpad_y, int src_w, int src_h, void* dets_dev,
+                                int32_t* counts_dev, float* kpts_dev, void* stream_) {
   EIOKU_REQUIRE_INIT();
+  EIOKU_REQUIRE(!kpts_dev || (kpt_dev && nk > 0 && nk % 3 == 0), "keypoint output without keypoint maps");
   EIOKU_REQUIRE(box_dev && cls_dev && hl && wl && dets_dev && counts_dev, "NULL argument");
   hipStream_t stream = (hipStream_t)stream_;
   if (n == 0) return EIOKU_OK;
@@ -837,7 +922,11 @@ int eioku_yolo_postprocess(const float* const* box_dev, const float* const* cls_
   int rc = decode_forward(box, cls, n, hl, wl, nc, conf, cands, counts, A, stream);
   if (rc) return rc;
   ScaleParams sp{gain, (float)pad_x, (float)pad_y, (float)src_w, (float)src_h};
-  return nms_forward(cands, counts, n, A, iou, max_det, 7680.0f, sp, (Det*)dets_dev, counts_dev, stream);
+  rc = nms_forward(cands, counts, n, A, iou, max_det, 7680.0f, sp, (Det*)dets_dev, counts_dev, stream);
+  if (rc || !kpts_dev) return rc;
+  const float* kp[3] = {kpt_dev[0], kpt_dev[1], kpt_dev[2]};
+  const ScaleParams kps{gain, kpad_x, kpad_y, (float)src_w, (float)src_h};
+  return kpts_decode_forward(kp, (const Det*)dets_dev, counts_dev, n, hl, wl, nk, max_det, kps, kpts_dev, stream);
 }
 
 }  // extern "C"

@@ -97,4 +97,10 @@ int nms_forward(const Cand* cands, const int32_t* counts, int N, int max_cand, f
                 int max_det, float max_wh, ScaleParams sp, Det* dets, int32_t* det_counts,
                 hipStream_t stream);
 
+// K6p. Keypoints of the kept detections (a Pose head): kpt[l] fp32 [N,Hl,Wl,nk] raw maps, dets / det_counts as K7 wrote
+// them -> out [N][max_det][nk] (x, y in original-frame pixels, confidence), slots past the count zero.  sp carries
+// scale_coords' parameters: the same gain, the UNROUNDED padding.
+int kpts_decode_forward(const float* const kpt[3], const Det* dets, const int32_t* det_counts, int N, const int Hl[3],
+                        const int Wl[3], int nk, int max_det, ScaleParams sp, float* out, hipStream_t stream);
+
 }  // namespace eioku

@@ -606,6 +606,45 @@ __global__ __launch_bounds__(256) void k_nms(NmsArgs a) {
   if (lane == 0) a.det_counts[n] = kept;
 }
 
+// ---------------------------------------------------------------------------------------------
+// K6p keypoint decode: one thread per (image, detection slot, keypoint), after NMS.  Det.anchor names the level, row and
+// column the detection came from; its nk raw values are Ultralytics' Pose.kpts_decode ((r * 2 + (anchor - 0.5)) *
+// stride, sigmoid on the third) followed by scale_coords (unrounded padding, / gain, clip to the frame).  Slots past
+// the image's count are zeroed.
+// ---------------------------------------------------------------------------------------------
+struct KptArgs {
+  const float* map[3];
+  int H[3], W[3];
+  const Det* dets;
+  const int32_t* counts;
+  int nk, max_det;
+  ScaleParams sp;
+  float* out;
+  long long total;  // N * max_det * (nk / 3)
+};
+
+__global__ __launch_bounds__(256) void k_kpts_decode(KptArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.total) return;
+  const int K = a.nk / 3, k = (int)(i % K), d = (int)((i / K) % a.max_det), n = (int)(i / ((long long)K * a.max_det));
+  float* o = a.out + ((size_t)n * a.max_det + d) * a.nk + 3 * k;
+  const int A0 = a.H[0] * a.W[0], A1 = A0 + a.H[1] * a.W[1], A2 = A1 + a.H[2] * a.W[2];
+  int an = d < a.counts[n] ? a.dets[(size_t)n * a.max_det + d].anchor : -1;
+  if (an < 0 || an >= A2) {  // an empty slot (or an index no map has: never read)
+    o[0] = 0.f; o[1] = 0.f; o[2] = 0.f;
+    return;
+  }
+  const int l = an < A0 ? 0 : (an < A1 ? 1 : 2);
+  an -= l == 0 ? 0 : (l == 1 ? A0 : A1);
+  const int gy = an / a.W[l], gx = an % a.W[l];
+  const float stride = (float)(8 << l);
+  const float* r = a.map[l] + ((size_t)n * a.H[l] * a.W[l] + an) * a.nk + 3 * k;
+  const float x = (r[0] * 2.0f + (float)gx) * stride, y = (r[1] * 2.0f + (float)gy) * stride;
+  o[0] = fminf(fmaxf((x - a.sp.pad_x) / a.sp.gain, 0.f), a.sp.src_w);
+  o[1] = fminf(fmaxf((y - a.sp.pad_y) / a.sp.gain, 0.f), a.sp.src_h);
+  o[2] = 1.0f / (1.0f + expf(-r[2]));
+}
+
 inline unsigned blocks_for(long long total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
@@ -893,6 +932,29 @@ int nms_forward(const Cand* cands, const int32_t* counts, int N, int max_cand, f
   a.dets = dets;
   a.det_counts = det_counts;
   hipLaunchKernelGGL(k_nms, dim3(N), dim3(256), lds, stream, a);
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
+}
+
+int kpts_decode_forward(const float* const kpt[3], const Det* dets, const int32_t* det_counts, int N, const int Hl[3],
+                        const int Wl[3], int nk, int max_det, ScaleParams sp, float* out, hipStream_t stream) {
+  if (N == 0) return EIOKU_OK;
+  EIOKU_REQUIRE(nk > 0 && nk % 3 == 0 && max_det > 0, "bad keypoint layout nk=%d max_det=%d", nk, max_det);
+  EIOKU_REQUIRE(kpt[0] && kpt[1] && kpt[2] && dets && det_counts && out, "NULL argument");
+  KptArgs a;
+  for (int l = 0; l < 3; ++l) {
+    a.map[l] = kpt[l];
+    a.H[l] = Hl[l];
+    a.W[l] = Wl[l];
+  }
+  a.dets = dets;
+  a.counts = det_counts;
+  a.nk = nk;
+  a.max_det = max_det;
+  a.sp = sp;
+  a.out = out;
+  a.total = (long long)N * max_det * (nk / 3);
+  hipLaunchKernelGGL(k_kpts_decode, dim3(blocks_for(a.total)), dim3(256), 0, stream, a);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
 }

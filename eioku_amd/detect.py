@@ -114,27 +114,40 @@ def letterbox_plan(h: int, w: int, imgsz: int = 640, stride: int = 32, auto: boo
 class Yolov8Detector:
     """A YOLOv8 network resident on one GPU (``eioku_yolo_t``)."""
 
-    def __init__(self, variant: str = "n", nc: int = 80, state: dict | None = None, names: dict | None = None):
+    def __init__(self, variant: str = "n", nc: int = 80, state: dict | None = None, names: dict | None = None,
+                 nk: int | None = None):
+        """``nk``: keypoint channels of a Pose head (``K * 3``); by default what ``state`` carries (0 without one)."""
         self.variant, self.nc = variant, nc
+        self.nk = W.check_nk(nk) if nk is not None else (W.nk_of_state(state) if state is not None else 0)
         self.names = names if names is not None else (dict(enumerate(W.COCO_NAMES)) if nc == 80 else
                                                       {i: str(i) for i in range(nc)})
         ch, depth = W.YOLO_VARIANTS[variant]
-        self._h = Handle("yolo", (C.c_int * 5)(*ch), (C.c_int * 4)(*depth), nc)
+        if self.nk:
+            self._h = Handle("yolo", (C.c_int * 5)(*ch), (C.c_int * 4)(*depth), nc, self.nk, create="eioku_yolo_create_pose")
+        else:
+            self._h = Handle("yolo", (C.c_int * 5)(*ch), (C.c_int * 4)(*depth), nc)
         self._h.or_close(self._load, state)
 
     def _load(self, state):
-        expect = [(n, co, (8 if n == "model.0.conv" else ci), k, s) for n, co, ci, k, s in W.conv_table(self.variant, self.nc)]
+        expect = [(n, co, (8 if n == "model.0.conv" else ci), k, s)
+                  for n, co, ci, k, s in W.conv_table(self.variant, self.nc, self.nk)]
         if self._h.convs() != expect:
             raise RuntimeError("library graph and weights.conv_table disagree")
         if state is not None:
             self.load_state(state)
 
+    @property
+    def kpt_shape(self) -> tuple[int, int] | None:
+        """Ultralytics' ``kpt_shape`` ``(K, 3)`` of a Pose checkpoint, ``None`` for a Detect one."""
+        return (self.nk // 3, 3) if self.nk else None
+
     @classmethod
-    def from_model_name(cls, model_name: str, path=None, seed: int | None = None):
-        """``yolov8s.pt`` / ``yolov8n-face.pt``: weights from ``path``, or random-init when ``seed`` is given."""
+    def from_model_name(cls, model_name: str, path=None, seed: int | None = None, keypoints: int = 0):
+        """``yolov8s.pt`` / ``yolov8n-face.pt``: weights from ``path`` (a Pose checkpoint brings its keypoint head), or
+        random-init when ``seed`` is given (then with ``keypoints`` keypoints)."""
         variant, nc, names = W.variant_from_model_name(model_name)
         if seed is not None:
-            state = W.random_state(variant, nc, seed)
+            state = W.random_state(variant, nc, seed, nk=3 * int(keypoints))
         else:
             state, own = W.load_checkpoint(path, variant, nc)
             if own is not None and len(own) == nc:
@@ -168,6 +181,21 @@ class Yolov8Detector:
                    "eioku_yolo_forward")
         return box, cls
 
+    def forward_raw_pose(self, x_nhwc8):
+        """``forward_raw`` of a Pose handle plus its raw keypoint maps: ``(box, cls, [kpt P3,P4,P5])``, kpt ``(n,h/s,w/s,nk)``."""
+        import torch
+
+        if not self.nk:
+            raise ValueError("this detector has no keypoint head")
+        n, h, w, c = (int(s) for s in x_nhwc8.shape)
+        assert c == 8 and x_nhwc8.dtype == torch.float16
+        maps = [[torch.empty((n, h // s, w // s, ch), dtype=torch.float32, device=x_nhwc8.device) for s in (8, 16, 32)]
+                for ch in (64, self.nc, self.nk)]
+        ptrs = [(C.c_void_p * 3)(*[t.data_ptr() for t in m]) for m in maps]
+        _lib.check(self._h.eioku_yolo_forward_pose(ptr(x_nhwc8), n, h, w, *ptrs, current_stream(x_nhwc8)),
+                   "eioku_yolo_forward_pose")
+        return tuple(maps)
+
     def last_conv_flops(self) -> float:
         return self._h.doubles("last_conv_flops")[0]
 
@@ -193,12 +221,16 @@ class Yolov8Detector:
 
     # ---- frames -> detections ------------------------------------------------------------------
     def detect(self, frames_bgr, conf: float = 0.25, iou: float = 0.7, max_det: int = 300, imgsz: int = 640,
-               keep_on_device: bool = False):
+               keep_on_device: bool = False, with_kpts: bool = False):
         """uint8 BGR frames ``(n,h,w,3)`` (numpy = host staging, CUDA tensor = zero copy).
 
         Returns ``(dets, counts)``: structured array ``(n,max_det)`` of :data:`DET_DTYPE` and int32 ``(n,)``;
         with ``keep_on_device`` the raw CUDA tensors (uint8 view / int32) so the call stays asynchronous.
+        ``with_kpts`` (a Pose handle): ``(dets, counts, kpts)``, ``kpts`` float32 ``(n,max_det,K,3)`` = (x, y, confidence)
+        per keypoint in original-frame pixels, zero past ``counts``; ``dets`` and ``counts`` are what they are without it.
         """
+        if with_kpts and not self.nk:
+            raise ValueError("this detector has no keypoint head")
         n, h, w, c = (int(s) for s in frames_bgr.shape)
         if c != 3:
             raise ValueError("expected (n,h,w,3) BGR frames")
@@ -209,20 +241,26 @@ class Yolov8Detector:
 
             dets = torch.empty((n, max_det, 32), dtype=torch.uint8, device=frames_bgr.device)
             counts = torch.empty((n,), dtype=torch.int32, device=frames_bgr.device)
+            kpts = torch.empty((n, max_det, self.nk // 3, 3), dtype=torch.float32, device=frames_bgr.device) if with_kpts else None
         else:
             dets = np.zeros((n, max_det), dtype=DET_DTYPE)
             counts = np.zeros((n,), dtype=np.int32)
+            kpts = np.zeros((n, max_det, self.nk // 3, 3), dtype=np.float32) if with_kpts else None
         geom = plan.geom()
-        _lib.check(self._h.eioku_yolo_detect(
-            ptr(frames_bgr), n, h, w, ptr(geom), ptr(plan.xofs), ptr(plan.yofs), ptr(plan.xalpha), ptr(plan.ybeta),
-            float(np.float32(plan.gain)), float(conf), float(iou), int(max_det), ptr(dets), ptr(counts),
-            _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(frames_bgr)), "eioku_yolo_detect")
+        args = (ptr(frames_bgr), n, h, w, ptr(geom), ptr(plan.xofs), ptr(plan.yofs), ptr(plan.xalpha), ptr(plan.ybeta),
+                float(np.float32(plan.gain)), float(conf), float(iou), int(max_det), ptr(dets), ptr(counts),
+                _lib.MEM_DEVICE if dev else _lib.MEM_HOST, current_stream(frames_bgr))
+        if with_kpts:
+            _lib.check(self._h.eioku_yolo_detect_pose(*args, ptr(kpts)), "eioku_yolo_detect_pose")
+        else:
+            _lib.check(self._h.eioku_yolo_detect(*args), "eioku_yolo_detect")
         if dev and not keep_on_device:
             dets = dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det)
             counts = counts.cpu().numpy()
+            kpts = kpts.cpu().numpy() if with_kpts else None
         if not (dev and keep_on_device):
             _clear_unused_rows(dets, counts)
-        return dets, counts
+        return (dets, counts, kpts) if with_kpts else (dets, counts)
 
 
 class PipelinedDetector:
@@ -238,9 +276,10 @@ class PipelinedDetector:
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.names = first.names
+        self.nk, self.kpt_shape = first.nk, first.kpt_shape
         self._handles = [first]
         for _ in range(1, depth):
-            d = Yolov8Detector(first.variant, first.nc, None, first.names)
+            d = Yolov8Detector(first.variant, first.nc, None, first.names, nk=first.nk)
             d.load_state(first._state)
             self._handles.append(d)
         self._device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -254,7 +293,7 @@ class PipelinedDetector:
             torch.cuda.Stream(device=self._device, priority=-1) for _ in self._handles]
         if len(self._streams) != len(self._handles):
             raise ValueError("one stream per handle")
-        self._pending = []  # (dets, counts, event, frames kept alive)
+        self._pending = []  # (dets, counts, event, frames kept alive, kpts or None)
         self._n = 0
 
     @property
@@ -264,7 +303,10 @@ class PipelinedDetector:
     def in_flight(self) -> int:
         return len(self._pending)
 
-    def submit(self, frames_bgr, conf: float = 0.25, iou: float = 0.7, max_det: int = 300, imgsz: int = 640) -> None:
+    def submit(self, frames_bgr, conf: float = 0.25, iou: float = 0.7, max_det: int = 300, imgsz: int = 640,
+               with_kpts: bool = False) -> None:
+        """``with_kpts`` (Pose handles): the batch also decodes its keypoints, for ``result_with_kpts`` /
+        ``result_with_frames_and_kpts``; the other result methods drop them."""
         import torch
 
         j = self._n % len(self._handles)
@@ -275,29 +317,48 @@ class PipelinedDetector:
         with torch.cuda.stream(s):
             f = frames_bgr if on_device(frames_bgr) else torch.from_numpy(np.ascontiguousarray(frames_bgr)).to(
                 self._device, non_blocking=True)
-            dets, counts = self._handles[j].detect(f, conf=conf, iou=iou, max_det=max_det, imgsz=imgsz, keep_on_device=True)
+            kpts = None
+            if with_kpts:
+                dets, counts, kpts = self._handles[j].detect(f, conf=conf, iou=iou, max_det=max_det, imgsz=imgsz,
+                                                             keep_on_device=True, with_kpts=True)
+            else:
+                dets, counts = self._handles[j].detect(f, conf=conf, iou=iou, max_det=max_det, imgsz=imgsz, keep_on_device=True)
             ev = torch.cuda.Event()
             ev.record(s)
-        self._pending.append((dets, counts, ev, f))
+        self._pending.append((dets, counts, ev, f, kpts))
 
     def result(self):
         """Oldest submitted batch: ``(dets structured (n,max_det), counts int32 (n,))`` on the host."""
-        dets, counts, ev, _ = self._pending.pop(0)
+        dets, counts, ev, _, _ = self._pending.pop(0)
         ev.synchronize()
         n, max_det = int(dets.shape[0]), int(dets.shape[1])
         return dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy()
 
+    def result_with_kpts(self):
+        """``result()`` plus the batch's keypoints, float32 ``(n,max_det,K,3)`` on the host (submitted ``with_kpts``)."""
+        dets, counts, _, kpts = self.result_with_frames_and_kpts()
+        return dets, counts, kpts
+
+    def result_with_frames_and_kpts(self):
+        """``result_with_frames()`` plus the batch's keypoints: ``(dets, counts, frames, kpts)``."""
+        if self._pending[0][4] is None:
+            raise ValueError("this batch was submitted without with_kpts")
+        dets, counts, ev, f, kpts = self._pending.pop(0)
+        ev.synchronize()
+        n, max_det = int(dets.shape[0]), int(dets.shape[1])
+        return dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy(), f, kpts.cpu().numpy()
+
     def result_with_frames(self):
         """``result()`` plus the device copy of that batch's frames (CUDA uint8 ``(n,h,w,3)``, the tensor the detector read;
         complete: the batch's event has been waited for) - the face-clustering crops read it instead of a second upload."""
-        dets, counts, ev, f = self._pending.pop(0)
+        dets, counts, ev, f, _ = self._pending.pop(0)
         ev.synchronize()
         n, max_det = int(dets.shape[0]), int(dets.shape[1])
         return dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy(), f
 
     def result_on_device(self):
         """Oldest submitted batch as the raw CUDA tensors plus the event that marks them complete."""
-        dets, counts, ev, _ = self._pending.pop(0)
+        dets, counts, ev, _, _ = self._pending.pop(0)
         return dets, counts, ev
 
     def close(self):
@@ -354,3 +415,35 @@ def postprocess(box_maps, cls_maps, plan: LetterboxPlan, conf: float, iou: float
     dets, counts = dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy()
     _clear_unused_rows(dets, counts)
     return dets, counts
+
+
+def kpt_pad(plan: LetterboxPlan) -> tuple[float, float]:
+    """``scale_coords``' padding of a plan, as float32 values: ``((out_w - src_w * gain) / 2, (out_h - src_h * gain) / 2)``
+    with the float32 gain the library is given - unrounded, where ``scale_boxes`` (``pad_x`` / ``pad_y``) rounds."""
+    g = float(np.float32(plan.gain))
+    return float(np.float32((plan.out_w - plan.src_w * g) / 2)), float(np.float32((plan.out_h - plan.src_h * g) / 2))
+
+
+def postprocess_pose(box_maps, cls_maps, kpt_maps, plan: LetterboxPlan, conf: float, iou: float = 0.7, max_det: int = 300):
+    """K6 + K7 + K6p alone on CUDA fp32 Pose maps (NHWC) -> (dets structured array, counts, kpts float32 (n,max_det,K,3))."""
+    import torch
+
+    lib = _lib.load()
+    _lib.init()
+    n = int(box_maps[0].shape[0])
+    nc, nk = int(cls_maps[0].shape[-1]), int(kpt_maps[0].shape[-1])
+    hl = (C.c_int * 3)(*[int(b.shape[1]) for b in box_maps])
+    wl = (C.c_int * 3)(*[int(b.shape[2]) for b in box_maps])
+    dev = box_maps[0].device
+    dets = torch.empty((n, max_det, 32), dtype=torch.uint8, device=dev)
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    kpts = torch.empty((n, max_det, nk // 3, 3), dtype=torch.float32, device=dev)
+    bp, cp, kp = ((C.c_void_p * 3)(*[t.contiguous().data_ptr() for t in m]) for m in (box_maps, cls_maps, kpt_maps))
+    kx, ky = kpt_pad(plan)
+    _lib.check(lib.eioku_yolo_postprocess_pose(bp, cp, kp, n, hl, wl, nc, nk, float(conf), float(iou), int(max_det),
+                                               float(np.float32(plan.gain)), plan.pad_x, plan.pad_y, kx, ky, plan.src_w,
+                                               plan.src_h, ptr(dets), ptr(counts), ptr(kpts), current_stream(box_maps[0])),
+               "eioku_yolo_postprocess_pose")
+    dets, counts = dets.cpu().numpy().view(DET_DTYPE).reshape(n, max_det), counts.cpu().numpy()
+    _clear_unused_rows(dets, counts)
+    return dets, counts, kpts.cpu().numpy()

@@ -2,10 +2,13 @@
 ``csrc/faces.hip``.
 
 Fills the ``cluster_id`` that ``ModelManager.detect_faces`` returns (``cluster_faces`` config key).  Per face the device
-crops a square of side ``max(w, h, 1)`` centred on the detector's box, resamples it bilinearly to 112 x 112 (K13a),
-normalises it as arcface_torch's inference does (``(v / 255 - 0.5) / 0.5``) and runs the IResNet (K13b) to a unit
-512-vector; once per video the vectors are clustered by DBSCAN on cosine distance with scikit-learn's labels (K14).
-There is no landmark alignment: the face detector exposes no keypoints.  No CPU fallback.
+produces a 112 x 112 crop, normalises it as arcface_torch's inference does (``(v / 255 - 0.5) / 0.5``) and runs the IResNet
+(K13b) to a unit 512-vector; once per video the vectors are clustered by DBSCAN on cosine distance with scikit-learn's
+labels (K14).  The crop is the aligned one ArcFace networks are trained on when the detector is a Pose checkpoint with
+five landmarks: their similarity transform onto insightface's template (``align_matrices``, Umeyama on the host) and
+``cv2.warpAffine`` in OpenCV's fixed point on the device (K13c).  Without landmarks, or for a face whose landmarks give no
+usable transform, it is a square of side ``max(w, h, 1)`` centred on the detector's box, resampled bilinearly (K13a).
+No CPU fallback.
 """
 from __future__ import annotations
 
@@ -49,6 +52,47 @@ def crop_taps(box, h: int, w: int):
     x1, y1, x2, y2 = (float(np.float32(v)) for v in box)
     side = max(max(x2 - x1, y2 - y1), 1.0)
     return (*axis_taps(x1, x2, side, w), *axis_taps(y1, y2, side, h))
+
+
+# ---- host side of K13c: landmarks -> similarity transform ---------------------------------------------------------------
+# insightface face_align.arcface_dst: left eye, right eye, nose, left and right mouth corner in the 112 x 112 crop
+ARCFACE_DST = np.array([[38.2946, 51.6963], [73.5318, 51.5014], [56.0252, 71.7366], [41.5493, 92.3655], [70.7299, 92.2041]],
+                       dtype=np.float64)
+
+
+def align_matrices(landmarks_xy):
+    """``landmarks_xy`` ``(m, 5, 2)`` (frame pixels, ``ARCFACE_DST``'s order) -> ``(M, fallback)``: ``M`` float64 ``(m, 2, 3)``,
+    the matrix ``cv2.warpAffine`` takes (frame -> crop), and ``fallback`` bool ``(m,)``, set where ``M`` is not usable (a
+    non-finite entry or a scale <= 0: all five landmarks coincide) and the face keeps its box crop.
+
+    ``M`` is scikit-image's ``SimilarityTransform.estimate(landmarks, ARCFACE_DST)`` (insightface's ``estimate_norm``):
+    Umeyama's least-squares similarity with scale, here for all faces at once on stacked ``np.linalg.svd``, with its
+    reflection rule (``det(A) < 0`` flips the last singular direction) and its rank-1 rule (collinear landmarks)."""
+    src = np.asarray(landmarks_xy, dtype=np.float64).reshape(-1, 5, 2)
+    m = src.shape[0]
+    if m == 0:
+        return np.zeros((0, 2, 3)), np.zeros(0, bool)
+    dst_mean = ARCFACE_DST.mean(axis=0)
+    dst_d = ARCFACE_DST - dst_mean
+    src_mean = src.mean(axis=1)
+    src_d = src - src_mean[:, None, :]
+    with np.errstate(all="ignore"):
+        A = np.matmul(dst_d.T, src_d) / 5  # (m, 2, 2)
+        d = np.ones((m, 2))
+        d[np.linalg.det(A) < 0, 1] = -1
+        U, S, Vt = np.linalg.svd(A)
+        rank = (S > S.max(axis=1, keepdims=True) * (2 * np.finfo(np.float64).eps)).sum(axis=1)  # np.linalg.matrix_rank
+        dr = d.copy()
+        # rank 1: the sign comes from det(U) det(V) instead of det(A) (which is 0 up to rounding there)
+        one = rank == 1
+        dr[one, 1] = np.where(np.linalg.det(U[one]) * np.linalg.det(Vt[one]) > 0, 1.0, -1.0)
+        R = np.matmul(U * dr[:, None, :], Vt)
+        scale = 1.0 / src_d.var(axis=1).sum(axis=1) * (S * d).sum(axis=1)
+        t = dst_mean - scale[:, None] * np.matmul(R, src_mean[:, :, None])[:, :, 0]
+        M = np.concatenate([R * scale[:, None, None], t[:, :, None]], axis=2)
+        M[rank == 0] = np.nan
+        fallback = ~np.isfinite(M).all(axis=(1, 2)) | ~(scale > 0)
+    return M, fallback
 
 
 # ---- arcface_torch state dict -> folded parameters -------------------------------------------------------------------
@@ -231,6 +275,24 @@ class FaceEmbedder:
                    "eioku_iresnet_crop")
         return out
 
+    def crop_aligned(self, frames_bgr, slots, M):
+        """K13c alone: BGR uint8 ``(n,h,w,3)`` + frame slots ``(m,)`` + matrices float64 ``(m,2,3)`` (frame -> crop, as
+        ``cv2.warpAffine`` takes them) -> fp16 ``(m,112,112,8)`` CUDA."""
+        import torch
+
+        n, h, w, _ = (int(s) for s in frames_bgr.shape)
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        mats = np.ascontiguousarray(M, dtype=np.float64).reshape(-1, 6)
+        if len(sl) != len(mats):
+            raise ValueError("one frame slot per matrix")
+        dev = frames_bgr.device if on_device(frames_bgr) else torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((len(sl), CROP, CROP, 8), dtype=torch.float16, device=dev)
+        src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr, dtype=np.uint8)
+        _lib.check(self._h.eioku_iresnet_crop_aligned(ptr(src), n, h, w, ptr(sl), ptr(mats), len(sl), ptr(out),
+                                                      _lib.MEM_DEVICE if on_device(src) else _lib.MEM_HOST, current_stream(out)),
+                   "eioku_iresnet_crop_aligned")
+        return out
+
     def forward_raw(self, crops, upto_block: int = -1):
         """fp16 ``(m,112,112,8)`` CUDA crops (m <= 256) -> float32 ``(m,512)`` embeddings, or (``upto_block >= 0``) that
         block's NHWC fp16 output (CUDA)."""
@@ -259,24 +321,46 @@ class FaceEmbedder:
     def embed(self, frames_bgr, boxes) -> np.ndarray:
         """BGR uint8 ``(n,h,w,3)`` frames (numpy: staged once; CUDA tensor: read in place) + ``boxes`` float32 ``(m,5)``
         rows ``(frame slot, x1, y1, x2, y2)`` -> float32 ``(m,512)`` unit embeddings (numpy)."""
+        return self._embed(frames_bgr, boxes, None)
+
+    def embed_aligned(self, frames_bgr, boxes, landmarks) -> np.ndarray:
+        """``embed`` on aligned crops: ``landmarks`` ``(m,5,2)`` (or ``(m,5,3)`` with a confidence that is not used), frame
+        pixels in ``ARCFACE_DST``'s order.  A face whose landmarks give no usable transform (``align_matrices``' mask)
+        is embedded from its box crop, exactly as ``embed`` does."""
+        lm = np.asarray(landmarks, dtype=np.float64)
+        if lm.ndim != 3 or lm.shape[1] != 5 or lm.shape[2] not in (2, 3):
+            raise ValueError(f"expected (m,5,2) landmarks, got {lm.shape}")
+        return self._embed(frames_bgr, boxes, align_matrices(lm[:, :, :2]))
+
+    def _embed(self, frames_bgr, boxes, aligned) -> np.ndarray:
         n, h, w, c = (int(s) for s in frames_bgr.shape)
         if c != 3:
             raise ValueError("expected (n,h,w,3) BGR frames")
         b = self._boxes(boxes)
         out = np.empty((len(b), FEAT), np.float32)
+        if aligned is not None and len(aligned[0]) != len(b):
+            raise ValueError("one landmark set per box")
         if len(b) == 0:
             return out
         src = frames_bgr if on_device(frames_bgr) else np.ascontiguousarray(frames_bgr, dtype=np.uint8)
-        if on_device(src):
+        dev = on_device(src)
+        if dev:
             import torch
 
-            dout = torch.empty((len(b), FEAT), dtype=torch.float32, device=src.device)
-            _lib.check(self._h.eioku_iresnet_embed(ptr(src), n, h, w, ptr(b), len(b), ptr(dout), _lib.MEM_DEVICE,
-                                                   current_stream(src)), "eioku_iresnet_embed")
-            return dout.cpu().numpy()
-        _lib.check(self._h.eioku_iresnet_embed(ptr(src), n, h, w, ptr(b), len(b), ptr(out), _lib.MEM_HOST, None),
-                   "eioku_iresnet_embed")
-        return out
+            dst = torch.empty((len(b), FEAT), dtype=torch.float32, device=src.device)
+        else:
+            dst = out
+        mem, stream = (_lib.MEM_DEVICE, current_stream(src)) if dev else (_lib.MEM_HOST, None)
+        if aligned is None:
+            _lib.check(self._h.eioku_iresnet_embed(ptr(src), n, h, w, ptr(b), len(b), ptr(dst), mem, stream),
+                       "eioku_iresnet_embed")
+        else:
+            M, fallback = aligned
+            mats = np.ascontiguousarray(np.where(fallback[:, None, None], 0.0, M), dtype=np.float64).reshape(-1, 6)
+            flags = np.ascontiguousarray(fallback, dtype=np.int32)
+            _lib.check(self._h.eioku_iresnet_embed_aligned(ptr(src), n, h, w, ptr(b), ptr(mats), ptr(flags), len(b), ptr(dst),
+                                                           mem, stream), "eioku_iresnet_embed_aligned")
+        return dst.cpu().numpy() if dev else out
 
     def cluster(self, embeddings, eps: float, min_samples: int):
         """DBSCAN on cosine distance (``dbscan_cosine``) -> int32 labels, numpy."""
@@ -301,12 +385,18 @@ class FaceClusterer:
         self._dets: list[dict] = []
         self._emb: list[np.ndarray] = []
 
-    def add(self, frames_bgr, boxes, dets: list) -> None:
+    def add(self, frames_bgr, boxes, dets: list, landmarks=None) -> None:
         """``frames_bgr`` the batch the detector saw (device copy or host), ``boxes`` ``(slot, x1, y1, x2, y2)`` rows for
-        ``dets`` (the detection dicts, in emission order)."""
+        ``dets`` (the detection dicts, in emission order).  ``landmarks`` ``(m,5,2)``: the faces' five landmarks, embedded
+        from aligned crops (``embed_aligned``); without them the box crops, through ``embed`` as ever."""
         if not dets:
             return
-        self._emb.append(np.asarray(self.embedder.embed(frames_bgr, np.asarray(boxes, np.float32).reshape(-1, 5)), np.float32))
+        b = np.asarray(boxes, np.float32).reshape(-1, 5)
+        if landmarks is None or not hasattr(self.embedder, "embed_aligned"):  # (an embedder fake may have ``embed`` only)
+            emb = self.embedder.embed(frames_bgr, b)
+        else:
+            emb = self.embedder.embed_aligned(frames_bgr, b, landmarks)
+        self._emb.append(np.asarray(emb, np.float32))
         self._dets.extend(dets)
 
     def embeddings(self) -> np.ndarray:

@@ -102,19 +102,35 @@ class _DetectionLane:
     ``cluster_id``) come out in ``out``.  With a ``PipelinedDetector`` two batches are in flight and results are taken in
     submission order, so the list is the one the synchronous ``detector.detect`` path produces."""
 
-    def __init__(self, detector, face: bool, conf: float, pipe=None, cluster=None):
+    def __init__(self, detector, face: bool, conf: float, pipe=None, cluster=None, alignment="auto"):
+        """``alignment`` (the ``face_alignment`` config key): ``"auto"`` embeds aligned crops when the detector has exactly
+        five keypoints, ``False`` keeps the box crops, ``True`` insists (``ValueError`` without five keypoints)."""
         self.detector, self.pipe = detector, pipe
         self.face, self.conf, self.names = face, conf, detector.names
         self.cluster = cluster  # FaceClusterer or None
+        nk = int(getattr(detector, "nk", 0) or 0)
+        self.kpts = face and nk > 0  # a Pose checkpoint: every face carries "landmarks"
+        if alignment not in ("auto", True, False):
+            raise ValueError(f"face_alignment must be \"auto\", True or False, not {alignment!r}")
+        if alignment is True and not (face and nk == 15):
+            raise ValueError(f"face_alignment needs a face detector with 5 keypoints; this one has {nk // 3}")
+        self.align = self.kpts and nk == 15 and alignment is not False
         self.metas: list[list[tuple[int, int]]] = []  # the batches in flight, oldest first
         self.out: list[dict] = []
 
     def submit(self, meta, frames) -> None:
         """``frames``: the stacked batch (host ndarray or device tensor), ``meta``: its ``(frame_index, timestamp_ms)``."""
         if self.pipe is None:
-            self._emit(meta, *self.detector.detect(frames, conf=self.conf), frames)
+            if self.kpts:
+                dets, counts, kpts = self.detector.detect(frames, conf=self.conf, with_kpts=True)
+                self._emit(meta, dets, counts, frames, kpts)
+            else:
+                self._emit(meta, *self.detector.detect(frames, conf=self.conf), frames)
             return
-        self.pipe.submit(frames, conf=self.conf)
+        if self.kpts:
+            self.pipe.submit(frames, conf=self.conf, with_kpts=True)
+        else:
+            self.pipe.submit(frames, conf=self.conf)
         self.metas.append(meta)
         self._drain(self.pipe.depth - 1)
 
@@ -136,13 +152,16 @@ class _DetectionLane:
 
     def _drain(self, keep: int) -> None:
         while self.pipe.in_flight() > keep:  # the clusterer crops the faces from the batch's device copy
-            result = self.pipe.result_with_frames() if self.cluster is not None else self.pipe.result()
+            if self.kpts:
+                result = self.pipe.result_with_frames_and_kpts()
+            else:
+                result = self.pipe.result_with_frames() if self.cluster is not None else self.pipe.result()
             self._emit(self.metas.pop(0), *result)
 
-    def _emit(self, meta, dets, counts, frames=None) -> None:
-        boxes, batch = [], []
+    def _emit(self, meta, dets, counts, frames=None, kpts=None) -> None:
+        boxes, batch, marks = [], [], []
         for slot, ((frame_idx, timestamp_ms), row, cnt) in enumerate(zip(meta, dets, counts)):
-            for d in row[: int(cnt)]:
+            for i, d in enumerate(row[: int(cnt)]):
                 x1, y1, x2, y2 = (np.float32(d[k]) for k in ("x1", "y1", "x2", "y2"))
                 confidence = float(np.float32(d["conf"]))  # float32 -> Python float, as float(tensor)
                 if self.face and confidence < self.conf:
@@ -153,12 +172,19 @@ class _DetectionLane:
                                 "width": float(np.float32(x2 - x1)), "height": float(np.float32(y2 - y1))}}
                 if self.face:
                     det["cluster_id"] = None
+                    if kpts is not None:  # original-image pixels, in the checkpoint's keypoint order
+                        det["landmarks"] = [{"x": float(x), "y": float(y), "confidence": float(c)} for x, y, c in kpts[slot][i]]
                     if self.cluster is not None:
                         boxes.append((slot, x1, y1, x2, y2))
                         batch.append(det)
+                        if self.align:
+                            marks.append(np.asarray(kpts[slot][i], np.float64)[:, :2])
                 self.out.append(det)
         if self.cluster is not None:
-            self.cluster.add(frames, boxes, batch)
+            if self.align:
+                self.cluster.add(frames, boxes, batch, landmarks=np.asarray(marks, np.float64).reshape(-1, 5, 2))
+            else:
+                self.cluster.add(frames, boxes, batch)
 
 
 class ModelManager:
@@ -385,15 +411,16 @@ class ModelManager:
 
         return open_video(video_path)
 
-    def _load_detector(self, model_name: str):
-        """``YOLO(cache_dir/ultralytics/model_name); model.to(device)`` (ref :252-254): per job, like the reference."""
+    def _load_detector(self, model_name: str, keypoints: int = 0):
+        """``YOLO(cache_dir/ultralytics/model_name); model.to(device)`` (ref :252-254): per job, like the reference.
+        ``keypoints`` (the face task's config key of that name) shapes seeded weights only: a checkpoint has its own head."""
         if self._detector_factory is not None:
             return self._detector_factory(model_name, self.cache_dir)
         from .detect import Yolov8Detector
 
         path = self.cache_dir / "ultralytics" / model_name
         if self._seed is not None and not path.exists():
-            return Yolov8Detector.from_model_name(model_name, seed=self._seed)
+            return Yolov8Detector.from_model_name(model_name, seed=self._seed, keypoints=keypoints)
         return Yolov8Detector.from_model_name(model_name, path=path)
 
     def _lanes(self, task: str, depth: int = 2):
@@ -443,14 +470,14 @@ class ModelManager:
             frames_to_process = (total_frames + frame_interval - 1) // frame_interval
             logger.info(f"Processing every {frame_interval} frames (every {frame_interval_seconds}s at {fps} FPS, "
                         f"~{frames_to_process} frames to process)")
-            detector = self._load_detector(model_name)
+            detector = self._load_detector(model_name, int(config.get("keypoints", 0)) if face else 0)
 
             # Two batches in flight on the HIP path (PipelinedDetector: second handle + stream); test stubs run synchronously
             from .detect import PipelinedDetector, Yolov8Detector
 
             pipe = (PipelinedDetector(detector, depth=2, streams=self._lanes(task))
                     if isinstance(detector, Yolov8Detector) else None)
-            lane = _DetectionLane(detector, face, confidence_threshold, pipe, cluster)
+            lane = _DetectionLane(detector, face, confidence_threshold, pipe, cluster, config.get("face_alignment", "auto"))
             try:
                 for meta, frames in _sampled_batches(cap, fps, frame_interval, self._batch_size):
                     lane.submit(meta, np.stack(frames))
@@ -596,7 +623,10 @@ class ModelManager:
         """Detect faces in video using YOLOv8-face on the HIP path (reference: :308-407).  With
         ``config["cluster_faces"]`` every face that passes the confidence filter is embedded (ArcFace IResNet,
         ``face_embedding_model`` under ``<cache>/insightface/``) and the video's faces are clustered once by cosine DBSCAN
-        (``cluster_eps``, ``cluster_min_samples``): ``cluster_id`` = ``face_cluster_001``, ... or None for noise."""
+        (``cluster_eps``, ``cluster_min_samples``): ``cluster_id`` = ``face_cluster_001``, ... or None for noise.
+        A Pose checkpoint (the community ``yolov8n-face.pt``: five landmarks) adds ``"landmarks": [{"x", "y", "confidence"}]``
+        to every face, and the embeddings then come from crops aligned on them unless ``face_alignment`` is False
+        (INTEGRATION.md section 3)."""
         return self._detect_loop("face_detection", video_path, config)
 
     # ---- single pass: one decode, one upload, three stages (SURVEY.md 8f rank 1) ------------------------------
@@ -645,11 +675,11 @@ class ModelManager:
                 continue
             cfg = configs[task] or {}
             model_name, conf, seconds, face = _detect_settings(task, cfg)
-            detector = self._load_detector(model_name)
+            detector = self._load_detector(model_name, int(cfg.get("keypoints", 0)) if face else 0)
             interval = _frame_interval(fps, seconds)
             pipe = PipelinedDetector(detector, depth=2, streams=self._lanes(task))
-            lanes[task] = (_DetectionLane(detector, face, conf, pipe, self._face_clusterer(cfg) if face else None),
-                           interval, [], [])
+            lanes[task] = (_DetectionLane(detector, face, conf, pipe, self._face_clusterer(cfg) if face else None,
+                                          cfg.get("face_alignment", "auto")), interval, [], [])
         want_scenes = "scene_detection" in configs
         scfg = configs.get("scene_detection") or {}
         content = scfg.get("detector", "ffmpeg") == "content"

@@ -49,8 +49,21 @@ def variant_from_model_name(model_name: str) -> tuple[str, int, dict[int, str]]:
     return m.group(1), 80, dict(enumerate(COCO_NAMES))
 
 
-def conv_table(variant: str, nc: int) -> list[tuple[str, int, int, int, int]]:
-    """(name, cout, cin, k, stride) of every convolution in module order (mirrors csrc/yolo.hip)."""
+MAX_KEYPOINTS = 17  # COCO pose; the face checkpoints have 5
+
+
+def check_nk(nk: int) -> int:
+    """``nk`` = keypoint channels of a Pose head (3 per keypoint: x, y, visibility), 0 for a Detect head."""
+    nk = int(nk)
+    if nk < 0 or nk % 3 or nk // 3 > MAX_KEYPOINTS:
+        raise ValueError(f"keypoint head with {nk} channels: expected 3 per keypoint for at most {MAX_KEYPOINTS} keypoints")
+    return nk
+
+
+def conv_table(variant: str, nc: int, nk: int = 0) -> list[tuple[str, int, int, int, int]]:
+    """(name, cout, cin, k, stride) of every convolution in module order (mirrors csrc/yolo.hip).  ``nk > 0``: an
+    Ultralytics ``Pose`` head, whose keypoint branch ``cv4`` (width ``c4 = max(c3 // 4, nk)``) follows every other row."""
+    nk = check_nk(nk)
     ch, depth = YOLO_VARIANTS[variant]
     c1, c2, c3, c4, c5 = ch
     d0, d1, d2, d3 = depth
@@ -90,7 +103,22 @@ def conv_table(variant: str, nc: int) -> list[tuple[str, int, int, int, int]]:
         t.append((f"model.22.cv3.{l}.0.conv", cc, cx, 3, 1))
         t.append((f"model.22.cv3.{l}.1.conv", cc, cc, 3, 1))
         t.append((f"model.22.cv3.{l}.2", nc, cc, 1, 1))
+    if nk > 0:
+        c4k = max(c3 // 4, nk)
+        for l, cx in enumerate((c3, c4, c5)):
+            t.append((f"model.22.cv4.{l}.0.conv", c4k, cx, 3, 1))
+            t.append((f"model.22.cv4.{l}.1.conv", c4k, c4k, 3, 1))
+            t.append((f"model.22.cv4.{l}.2", nk, c4k, 1, 1))
     return t
+
+
+KPT_KEY = "model.22.cv4.0.2.weight"  # present in a Pose checkpoint only; its first dimension is nk
+
+
+def nk_of_state(state: dict) -> int:
+    """Keypoint channels of a fused state ``{name: (w, b)}``: 0 without a ``cv4`` branch."""
+    wb = state.get("model.22.cv4.0.2")
+    return 0 if wb is None else check_nk(np.asarray(wb[0]).shape[0])
 
 
 # variance-preserving init gains, found by bisection on the head-logit spread of each graph
@@ -98,21 +126,22 @@ _INIT_GAIN = {"n": 3.2, "s": 3.27, "m": 2.75, "l": 2.55, "x": 2.55}
 
 
 def random_state(variant: str, nc: int, seed: int, gain: float | None = None, head_gain: float = 12.0,
-                 cls_bias: float = -6.0) -> dict[str, tuple[np.ndarray, np.ndarray]]:
+                 cls_bias: float = -6.0, nk: int = 0) -> dict[str, tuple[np.ndarray, np.ndarray]]:
     """Random-init fused weights ``{name: (w[cout,cin,k,k], b[cout])}`` (fp32) of the exact shapes.
 
     ``std = sqrt(gain / fan_in)`` keeps activations O(1) through the SiLU stack (per-variant gain,
     ``_INIT_GAIN``); the three Detect output convs get ``head_gain`` so logits have O(1) spread, and
     the class-logit bias is pushed negative so that, as with a trained model, only a few percent of
-    the anchors pass ``conf``.
+    the anchors pass ``conf``.  ``nk > 0`` adds the keypoint branch, drawn after every other layer: the tensors of the
+    ``nk = 0`` state of the same seed are unchanged.
     """
     if gain is None:
         gain = _INIT_GAIN[variant]
     rng = np.random.default_rng(seed)
     out = {}
-    for name, cout, cin, k, _ in conv_table(variant, nc):
+    for name, cout, cin, k, _ in conv_table(variant, nc, nk):
         fan_in = cin * k * k
-        head =re.match(r"model\.22\.cv[23]\.\d\.2$", name) is not None
+        head = re.match(r"model\.22\.cv[234]\.\d\.2$", name) is not None
         w = (rng.standard_normal((cout, cin, k, k)) * np.sqrt((head_gain if head else gain) / fan_in)).astype(np.float32)
         b = (0.05 * rng.standard_normal(cout)).astype(np.float32)
         if re.match(r"model\.22\.cv3\.\d\.2$", name):
@@ -127,10 +156,10 @@ def fold_batchnorm(w, gamma, beta, mean, var, eps=1e-3):
     return (w * scale[:, None, None, None]).astype(np.float32), (beta - mean * scale).astype(np.float32)
 
 
-def state_from_tensors(tensors: dict[str, np.ndarray], variant: str, nc: int) -> dict[str, tuple[np.ndarray, np.ndarray]]:
+def state_from_tensors(tensors: dict[str, np.ndarray], variant: str, nc: int, nk: int = 0) -> dict[str, tuple[np.ndarray, np.ndarray]]:
     """Ultralytics ``state_dict`` (fused or not) -> fused ``{prefix: (w, b)}`` for :func:`conv_table`."""
     out = {}
-    for name, cout, cin, k, _ in conv_table(variant, nc):
+    for name, cout, cin, k, _ in conv_table(variant, nc, nk):
         wkey = f"{name}.weight"
         if wkey not in tensors:
             raise KeyError(f"checkpoint has no {wkey}")
@@ -249,7 +278,9 @@ def load_checkpoint(path: str | Path, variant: str, nc: int):
 
 
 def load_state(path: str | Path, variant: str, nc: int, _names_out: dict | None = None) -> dict[str, tuple[np.ndarray, np.ndarray]]:
-    """Read ``.pt`` (Ultralytics checkpoint or plain state_dict), ``.safetensors`` or ``.npz``."""
+    """Read ``.pt`` (Ultralytics checkpoint or plain state_dict), ``.safetensors`` or ``.npz``.  A Pose checkpoint (one that
+    has ``model.22.cv4.0.2.weight``; its first dimension is ``nk``) yields the keypoint branch's rows as well:
+    :func:`nk_of_state` tells which kind came back."""
     path = Path(path)
     if not path.exists():
         raise FileNotFoundError(f"model weights not found: {path}")
@@ -279,4 +310,5 @@ def load_state(path: str | Path, variant: str, nc: int, _names_out: dict | None 
             raise ValueError(f"no tensors found in {path}")
     tensors = {re.sub(r"^(module\.|model\.model\.)", lambda m: "" if m.group(1) == "module." else "model.", k): v
                for k, v in tensors.items()}
-    return state_from_tensors(tensors, variant, nc)
+    nk = check_nk(np.asarray(tensors[KPT_KEY]).shape[0]) if KPT_KEY in tensors else 0
+    return state_from_tensors(tensors, variant, nc, nk)

@@ -198,6 +198,10 @@ int eioku_debug_conv_epi(int* launches, int reset);
  */
 typedef struct eioku_yolo eioku_yolo_t;
 int eioku_yolo_create(const int* ch5, const int* depth4, int nc, eioku_yolo_t** out);
+/* The same with an Ultralytics Pose head (the community yolov8n-face.pt: kpt_shape [5, 3]): nk = K * 3 keypoint channels
+ * (x, y, visibility; K <= 17), nine more convolutions "model.22.cv4.<l>.{0.conv,1.conv,2}" behind the Detect ones, of width
+ * c4 = max(c3 / 4, nk).  nk = 0 is eioku_yolo_create. */
+int eioku_yolo_create_pose(const int* ch5, const int* depth4, int nc, int nk, eioku_yolo_t** out);
 void eioku_yolo_destroy(eioku_yolo_t* y);
 int eioku_yolo_num_convs(const eioku_yolo_t* y);
 int eioku_yolo_conv_info(const eioku_yolo_t* y, int idx, char* name, size_t name_cap, int* cout, int* cin,
@@ -209,6 +213,10 @@ int eioku_yolo_set_conv(eioku_yolo_t* y, int idx, const float* weight_oihw, cons
  * are skipped.  Asynchronous on `stream`. */
 int eioku_yolo_forward(eioku_yolo_t* y, const void* in_nhwc8_f16, int n, int h, int w,
                        float* const* box_out, float* const* cls_out, void* stream);
+/* ... plus the raw keypoint maps of a Pose handle, kpt_out[l] [n,h/s,w/s,nk] (device fp32).  kpt_out == NULL: the
+ * keypoint branch does not run (eioku_yolo_forward). */
+int eioku_yolo_forward_pose(eioku_yolo_t* y, const void* in_nhwc8_f16, int n, int h, int w,
+                            float* const* box_out, float* const* cls_out, float* const* kpt_out, void* stream);
 /* Algorithmic conv FLOPs (2*Cout*Cin*k*k per output pixel, unpadded) of the last forward. */
 int eioku_yolo_last_conv_flops(const eioku_yolo_t* y, double* flops);
 
@@ -235,6 +243,14 @@ int eioku_yolo_detect(eioku_yolo_t* y, const uint8_t* bgr, int n, int h, int w, 
                       const int32_t* xofs, const int32_t* yofs, const int16_t* xalpha,
                       const int16_t* ybeta, float gain, float conf, float iou, int max_det,
                       void* dets_out, int32_t* counts_out, int mem, void* stream);
+/* The same on a Pose handle, plus kpts_out [n][max_det][nk] fp32 (host or device per `mem`): per kept detection its K
+ * keypoints as (x, y, confidence), decoded after NMS from the anchor the detection came from (K6p: Ultralytics'
+ * kpts_decode, then scale_coords with the unrounded padding, clipped to the frame); rows past counts_out[i] are zero.
+ * kpts_out == NULL is eioku_yolo_detect: the keypoint branch does not run. */
+int eioku_yolo_detect_pose(eioku_yolo_t* y, const uint8_t* bgr, int n, int h, int w, const int32_t* lb_geom,
+                           const int32_t* xofs, const int32_t* yofs, const int16_t* xalpha,
+                           const int16_t* ybeta, float gain, float conf, float iou, int max_det,
+                           void* dets_out, int32_t* counts_out, int mem, void* stream, float* kpts_out);
 
 /* Stage entry points (device pointers, asynchronous): K3 alone and K6+K7 alone.
  * eioku_letterbox_f16: BGR u8 frames -> fp16 NHWC8 (n x out_h x out_w x 8) network input.
@@ -247,6 +263,12 @@ int eioku_yolo_postprocess(const float* const* box_dev, const float* const* cls_
                            const int* wl, int nc, float conf, float iou, int max_det, float gain,
                            int pad_x, int pad_y, int src_w, int src_h, void* dets_dev,
                            int32_t* counts_dev, void* stream);
+/* K6 + K7 + K6p alone: ... plus the three keypoint maps kpt_dev[l] [n,hl,wl,nk] -> kpts_dev [n][max_det][nk] (device).
+ * kpad_x / kpad_y: scale_coords' unrounded padding ((out_w - src_w * gain) / 2, (out_h - src_h * gain) / 2). */
+int eioku_yolo_postprocess_pose(const float* const* box_dev, const float* const* cls_dev, const float* const* kpt_dev,
+                                int n, const int* hl, const int* wl, int nc, int nk, float conf, float iou, int max_det,
+                                float gain, int pad_x, int pad_y, float kpad_x, float kpad_y, int src_w, int src_h,
+                                void* dets_dev, int32_t* counts_dev, float* kpts_dev, void* stream);
 
 /* ---- semantic search: exact kNN (FAISS IndexFlatL2 semantics) -----------------------------
  * The reference holds intent only for this stage (.kiro/specs/semantic-video-search/design.md:
@@ -506,6 +528,15 @@ int eioku_iresnet_forward(eioku_iresnet_t* r, const void* in_f16, int m, int upt
 /* n BGR frames (host or device) + m boxes -> out [m][512] fp32 unit vectors on the side `mem` names */
 int eioku_iresnet_embed(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const float* boxes, int m, float* out,
                         int mem, void* stream);
+/* K13c, the aligned crop, alone: face i of frame slots[i] (HOST int32 [m]) warped by M[i] (HOST float64 [m][6], the
+ * matrix cv2.warpAffine takes: frame -> 112 x 112 crop) as cv2.warpAffine(frame, M, (112, 112), flags = INTER_LINEAR,
+ * borderValue = 0) computes it in fixed point, then eioku_iresnet_crop's normalisation and layout */
+int eioku_iresnet_crop_aligned(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const int32_t* slots, const double* M,
+                               int m, void* out_f16, int mem, void* stream);
+/* eioku_iresnet_embed on aligned crops: face i is warped by M[i] unless use_box[i] != 0 (HOST int32 [m]), which keeps the
+ * box crop of boxes[i]; the frame slot is boxes[i][0] either way */
+int eioku_iresnet_embed_aligned(eioku_iresnet_t* r, const uint8_t* bgr, int n, int h, int w, const float* boxes, const double* M,
+                                const int32_t* use_box, int m, float* out, int mem, void* stream);
 int eioku_iresnet_last_flops(const eioku_iresnet_t* r, double* flops);
 /* scikit-learn DBSCAN(eps, min_samples, metric="cosine") on unit-norm rows emb [n][d] fp32: j is a neighbour of i iff
  * 1 - e_i . e_j <= eps (i is its own), core iff >= min_samples neighbours, clusters = components of the core-core graph

@@ -1,8 +1,11 @@
 """Face clustering throughput on one GPU, as one JSON object: K13 embed (crop + ArcFace r18 on seeded random weights) at
 m = 256 crops - faces/s and achieved TF/s from ``last_flops`` - and K14 DBSCAN milliseconds at n = 1 k, 10 k and 65,536
-(d = 512, clustered unit vectors: ~33 points per cluster, 5 % noise, eps 0.3, min_samples 5).
+(d = 512, clustered unit vectors: ~33 points per cluster, 5 % noise, eps 0.3, min_samples 5).  With alignment: the same m
+faces through K13c (``crop_aligned`` / ``embed_aligned``) against K13a (``crop`` / ``embed``), and ``detect`` of a seeded
+``yolov8n-face`` on 64 x 1080p frames without a keypoint head, with one that does not run (``detect()`` on a Pose handle)
+and with one that does (``with_kpts``: the dense cv4 branch + K6p).  The object is also written to ``--out``.
 
-    python tools/faces_bench.py [--reps 5]
+    python tools/faces_bench.py [--reps 5] [--out profiles/faces.json]
 """
 import argparse
 import json
@@ -28,6 +31,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--m", type=int, default=256)
+    ap.add_argument("--out", default=str(Path(__file__).resolve().parent.parent / "profiles" / "faces.json"))
     args = ap.parse_args()
     import torch
 
@@ -52,7 +56,45 @@ def main():
     flops = emb.last_flops()
     out = {"embed": {"m": args.m, "ms": round(t_embed * 1e3, 3), "faces_per_s": round(args.m / t_embed, 1),
                      "gflop_per_face": round(flops / args.m / 1e9, 3), "tflops": round(flops / t_embed / 1e12, 2)}}
+
+    def timed(fn):
+        fn()  # warm-up
+        ts = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t)
+        return round(float(np.median(ts)) * 1e3, 3)
+
+    # the same faces, aligned: five landmarks inside each box (the template scaled to the box, tilted by up to 30 degrees)
+    ang = rng.uniform(-np.pi / 6, np.pi / 6, args.m)
+    R = np.stack([np.cos(ang), -np.sin(ang), np.sin(ang), np.cos(ang)], 1).reshape(-1, 2, 2)
+    lm = np.einsum("mij,kj->mki", R, faces.ARCFACE_DST - 56.0) * (side / 112.0)[:, None, None] + (boxes[:, 1:3] + side[:, None] / 2)[:, None, :]
+    M, fallback = faces.align_matrices(lm)
+    slots = boxes[:, 0].astype(np.int32)
+    out["align"] = {"m": args.m, "fallback": int(fallback.sum()),
+                    "crop_box_ms": timed(lambda: emb.crop(frames, boxes)), "crop_aligned_ms": timed(lambda: emb.crop_aligned(frames, slots, M)),
+                    "embed_box_ms": timed(lambda: emb.embed(frames, boxes)), "embed_aligned_ms": timed(lambda: emb.embed_aligned(frames, boxes, lm)),
+                    "note": "crop_*: the synchronous entry points, host time around one launch (taps / matrices upload included)"}
     emb.close()
+
+    from eioku_amd import detect as D, weights as W
+
+    hd = torch.from_numpy(rng.integers(0, 256, (64, 1080, 1920, 3), dtype=np.uint8)).to(dev)
+    pose_state = W.random_state("n", 1, 7, nk=15)
+    det0 = D.Yolov8Detector("n", 1, {k: v for k, v in pose_state.items() if ".cv4." not in k})
+    det5 = D.Yolov8Detector("n", 1, pose_state)
+    for d in (det0, det5):
+        d.calibrate_random_head(hd[:2])
+    out["detect_64x1080p"] = {
+        "detect_nk0_ms": timed(lambda: det0.detect(hd, conf=0.25, keep_on_device=True)),
+        "detect_pose_handle_without_kpts_ms": timed(lambda: det5.detect(hd, conf=0.25, keep_on_device=True)),
+        "detect_pose_with_kpts_ms": timed(lambda: det5.detect(hd, conf=0.25, keep_on_device=True, with_kpts=True))}
+    det0.close()
+    det5.close()
+    del hd
     db = {}
     for n in (1000, 10000, 65536):
         e = torch.from_numpy(clustered(n, n, 512, max(1, n // 33), 0.1, n // 20)).to(dev)
@@ -69,6 +111,7 @@ def main():
     out["dbscan"] = db
     out["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(out))
+    Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
 
 
 if __name__ == "__main__":
