@@ -307,6 +307,21 @@ SIGNATURES = {
     "eioku_timesformer_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eioku_timesformer_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_timesformer_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "eioku_clip_create": (C.c_int, [C.c_int] * 13 + [C.c_float, C.c_int, C.POINTER(C.c_void_p)]),
+    "eioku_clip_destroy": (None, [C.c_void_p]),
+    "eioku_clip_num_tensors": (C.c_int, [C.c_void_p]),
+    "eioku_clip_tensor_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eioku_clip_set_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "eioku_clip_set_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_clip_preprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_clip_encode_patches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_clip_encode_images": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "eioku_clip_encode_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_void_p]),
+    "eioku_clip_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_clip_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 

@@ -1,6 +1,6 @@
 // K25: action recognition on gfx950 - TimeSformer with divided space-time attention (DESIGN.md "K25 action recognition").
-//   k_clip_resize_h / k_clip_resize_v   Pillow's two-pass 8-bit bilinear resample of the centre-crop region only (22-bit
-//                       fixed-point taps from the host, uint8 rounding between the passes), then BGR -> RGB,
+//   k_clip_resize_h / k_clip_resize_v   (clip_resize.h, shared with clip.hip) Pillow's two-pass 8-bit bilinear resample of the
+//                       centre-crop region only (22-bit fixed-point taps from the host, uint8 rounding between the passes), then BGR -> RGB,
 //                       (v * (1 / 255) - mean) / std in fp32 and one rounding to fp16, written as patch rows
 //                       [clip][patch][frame][c * 256 + ky * 16 + kx]: the patch embedding is one GEMM, no im2col pass
 //   k_gemm<., EPI_POS>  (gemm_f16.h) patch projection + bias + (position + time) table into the fp32 residual stream
@@ -18,6 +18,7 @@
 // LayerNorm parameters and the embedding tables fp32; the residual stream fp32; LayerNorm outputs, q / k / v, attention
 // outputs, the temporal out-projection, GELU outputs and the patch rows are rounded to fp16; the spatial kernel rounds
 // its softmax numerators exp(s - max) to fp16 for the PV MFMA.
+#include "clip_resize.h"
 #include "common.h"
 #include "gemm_f16.h"
 
@@ -29,78 +30,13 @@ using namespace eioku;
 
 namespace {
 
-constexpr int kPrec = 22;      // Pillow Resample.c PRECISION_BITS for 8-bit pixels
 constexpr int kPatch = 16, kPatchK = 3 * kPatch * kPatch;
 constexpr int kMaxFrames = 96, kMaxImage = 448;
 constexpr int kKC = 128;       // keys per LDS stage of k_attn_space
 constexpr int kKStride = 72;   // halfs per staged key row (64 + 8: 144 B, 16-byte aligned, spreads the banks)
 constexpr int kVStride = kKC + 2;  // halfs per staged value column (65 words: a column starts one bank after its neighbour)
 
-// ---- clip preprocessing ---------------------------------------------------------------------------------------------------
-// bounds [S][2] = {first input index, taps}; kk [S][ksize] int32 taps scaled by 2^22: the rows of Pillow's tables for the
-// resized axis that the centre crop keeps.  horizontal: src [N][h][w][3] u8, rows y0 .. y0 + rows - 1 only -> tmp
-// [N][rows][S][3] u8; one thread per (row, output column)
-__global__ __launch_bounds__(256) void k_clip_resize_h(const uint8_t* __restrict__ src, int N, int h, int w, int y0, int rows, int S,
-                                                       const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
-                                                       uint8_t* __restrict__ tmp) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)N * rows * S) return;
-  const int xx = (int)(i % S);
-  const long long row = i / S;
-  const int y = (int)(row % rows), n = (int)(row / rows);
-  const int lo = bounds[2 * xx], cnt = bounds[2 * xx + 1];
-  const uint8_t* p = src + (((size_t)n * h + y0 + y) * w + lo) * 3;
-  int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
-  for (int t = 0; t < cnt; ++t) {
-    const int k = kk[xx * ksize + t];
-    s0 += p[3 * t] * k;
-    s1 += p[3 * t + 1] * k;
-    s2 += p[3 * t + 2] * k;
-  }
-  auto clip8 = [](int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); };
-  uint8_t* o = tmp + (size_t)i * 3;
-  o[0] = clip8(s0 >> kPrec);
-  o[1] = clip8(s1 >> kPrec);
-  o[2] = clip8(s2 >> kPrec);
-}
-
-struct Norm3 {
-  float mean[3], std[3];  // R, G, B
-};
-
-// vertical + rescale + normalise: tmp [N][rows][S][3] u8 (B, G, R), N = clips * T frames -> patches
-// [clip][patch][frame][c * 256 + ky * 16 + kx] fp16 (c = R, G, B) and / or out_u8 [N][S][S][3] (R, G, B)
-__global__ __launch_bounds__(256) void k_clip_resize_v(const uint8_t* __restrict__ tmp, int N, int T, int y0, int rows, int S,
-                                                       const int* __restrict__ bounds, const int* __restrict__ kk, int ksize,
-                                                       Norm3 nrm, h16* __restrict__ patches, uint8_t* __restrict__ out_u8) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)N * S * S) return;
-  const int x = (int)(i % S);
-  const int yy = (int)((i / S) % S);
-  const int n = (int)(i / ((long long)S * S));
-  const int lo = bounds[2 * yy] - y0, cnt = bounds[2 * yy + 1];
-  const uint8_t* p = tmp + (((size_t)n * rows + lo) * S + x) * 3;
-  int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
-  for (int t = 0; t < cnt; ++t) {
-    const int k = kk[yy * ksize + t];
-    s0 += p[(size_t)t * S * 3] * k;
-    s1 += p[(size_t)t * S * 3 + 1] * k;
-    s2 += p[(size_t)t * S * 3 + 2] * k;
-  }
-  auto clip8 = [](int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); };
-  const int rgb[3] = {clip8(s2 >> kPrec), clip8(s1 >> kPrec), clip8(s0 >> kPrec)};
-  if (out_u8) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out_u8[(size_t)i * 3 + c] = (uint8_t)rgb[c];
-  }
-  if (patches) {
-    const int side = S / kPatch, P = side * side, clip = n / T, t = n % T;
-    const int patch = (yy / kPatch) * side + x / kPatch;
-    h16* o = patches + (((size_t)clip * P + patch) * T + t) * kPatchK + (yy % kPatch) * kPatch + x % kPatch;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o[c * kPatch * kPatch] = (h16)(((float)rgb[c] * (1.0f / 255.0f) - nrm.mean[c]) / nrm.std[c]);
-  }
-}
+// ---- clip preprocessing: k_clip_resize_h / k_clip_resize_v and their launch, clip_resize.h ----------------------------------
 
 // ---- small kernels ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_cvt_f16(const float* __restrict__ src, size_t n, h16* __restrict__ dst) {
@@ -544,53 +480,10 @@ int run_head(Model* m, int B, int top_k, hipStream_t st) {
   return EIOKU_OK;
 }
 
-int check_tables(const int32_t* bounds, int S, int k, int extent, const char* axis) {
-  for (int i = 0; i < S; ++i) {
-    const int lo = bounds[2 * i], cnt = bounds[2 * i + 1];
-    EIOKU_REQUIRE(lo >= 0 && cnt >= 0 && cnt <= k && lo + cnt <= extent, "%s table row %d reads [%d, %d) of %d pixels with %d taps",
-                  axis, i, lo, lo + cnt, extent, k);
-  }
-  return EIOKU_OK;
-}
-
 int preprocess(Model* m, const uint8_t* bgr, int n_clips, int h, int w, const int32_t* xbounds, const int32_t* xk, int kx,
                const int32_t* ybounds, const int32_t* yk, int ky, h16* patches, uint8_t* out_u8, int mem, hipStream_t stream) {
-  const int S = m->image, N = n_clips * m->frames;
-  EIOKU_TRY(check_tables(xbounds, S, kx, w, "x"));
-  EIOKU_TRY(check_tables(ybounds, S, ky, h, "y"));
-  int y0 = h, y1 = 0;  // the source rows the vertical pass reads
-  for (int i = 0; i < S; ++i) {
-    if (!ybounds[2 * i + 1]) continue;
-    y0 = ybounds[2 * i] < y0 ? ybounds[2 * i] : y0;
-    y1 = ybounds[2 * i] + ybounds[2 * i + 1] > y1 ? ybounds[2 * i] + ybounds[2 * i + 1] : y1;
-  }
-  EIOKU_REQUIRE(y1 > y0, "empty y table");
-  const int rows = y1 - y0;
-  EIOKU_TRY(grow_synced(m->tables, (size_t)S * (2 + kx + 2 + ky)));
-  int* d_xb = m->tables;
-  int* d_xk = d_xb + S * 2;
-  int* d_yb = d_xk + (size_t)S * kx;
-  int* d_yk = d_yb + S * 2;
-  EIOKU_HIP_CHECK(hipMemcpyAsync(d_xb, xbounds, (size_t)S * 2 * 4, hipMemcpyHostToDevice, stream));
-  EIOKU_HIP_CHECK(hipMemcpyAsync(d_xk, xk, (size_t)S * kx * 4, hipMemcpyHostToDevice, stream));
-  EIOKU_HIP_CHECK(hipMemcpyAsync(d_yb, ybounds, (size_t)S * 2 * 4, hipMemcpyHostToDevice, stream));
-  EIOKU_HIP_CHECK(hipMemcpyAsync(d_yk, yk, (size_t)S * ky * 4, hipMemcpyHostToDevice, stream));
-  const uint8_t* d_src = bgr;
-  if (mem == EIOKU_MEM_HOST) {
-    const size_t bytes = (size_t)N * h * w * 3;
-    EIOKU_TRY(grow_synced(m->src, bytes));
-    EIOKU_HIP_CHECK(hipMemcpyAsync(m->src, bgr, bytes, hipMemcpyHostToDevice, stream));
-    d_src = m->src;
-  }
-  EIOKU_TRY(grow_synced(m->tmp, (size_t)N * rows * S * 3));
-  const long long w1 = (long long)N * rows * S, w2 = (long long)N * S * S;
-  hipLaunchKernelGGL(k_clip_resize_h, dim3((unsigned)((w1 + 255) / 256)), dim3(256), 0, stream, d_src, N, h, w, y0, rows, S, d_xb, d_xk,
-                     kx, m->tmp.p);
-  EIOKU_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_clip_resize_v, dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, stream, m->tmp.p, N, m->frames, y0, rows, S, d_yb,
-                     d_yk, ky, m->nrm, patches, out_u8);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
+  return clip_resize(bgr, n_clips * m->frames, m->frames, h, w, m->image, xbounds, xk, kx, ybounds, yk, ky, m->nrm, kPatch, 0, kPatchK,
+                     patches, out_u8, mem, m->tables, m->src, m->tmp, stream);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
-// The fp16 GEMM of the transformer models (K20 Whisper, K25 TimeSformer): C = A . W^T on v_mfma_f32_16x16x32_f16 with fused
-// epilogues.  Included by whisper.hip and actions.hip; everything here has internal linkage.
+// The fp16 GEMM of the transformer models (K20 Whisper, K25 TimeSformer, K26 CLIP): C = A . W^T on v_mfma_f32_16x16x32_f16 with fused
+// epilogues.  Included by whisper.hip, actions.hip and clip.hip; everything here has internal linkage.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,9 +14,10 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float float4v __attribute__((ext_vector_type(4)));
 
 // ---- GEMM ---------------------------------------------------------------------------------------------------------------
-enum { EPI_F16 = 0, EPI_GELU_F16 = 1, EPI_RESID = 2, EPI_GELU_POS = 3, EPI_F32 = 4, EPI_POS = 5 };
+enum { EPI_F16 = 0, EPI_GELU_F16 = 1, EPI_RESID = 2, EPI_GELU_POS = 3, EPI_F32 = 4, EPI_POS = 5, EPI_QGELU_F16 = 6 };
 
 __device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752f)); }
+__device__ __forceinline__ float quick_gelu(float v) { return v / (1.f + expf(-1.702f * v)); }  // v * sigmoid(1.702 v)
 
 // out[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]).  grid (ceil(N / 64), ceil(M / (16 MT))), 4 waves: wave w owns weight
 // rows n0 = 64 bx + 16 w .. + 15.  MFMA 16x16x32: A operand = weight rows (lane (r, u): row r, k 8u .. 8u + 7), B operand =
@@ -25,6 +26,7 @@ __device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.f + erff(v
 //   EPI_F16      out fp16 [m * ldc + n]            EPI_GELU_F16  the same after GELU
 //   EPI_RESID    out fp32 [m * ldc + n] += value   EPI_GELU_POS  out fp32 = GELU(value) + pos[m % pos_rows][n]
 //   EPI_F32      out fp32 [m * ldc + n] = value    EPI_POS       out fp32 = value + pos[m % pos_rows][n]
+//   EPI_QGELU_F16  out fp16 after v * sigmoid(1.702 v) (CLIP's quick_gelu)
 template <int MT, int EPI>
 __global__ __launch_bounds__(256) void k_gemm(const h16* __restrict__ A, int lda, const h16* __restrict__ W, int ldw,
                                               const float* __restrict__ bias, int M, int N, int K, void* __restrict__ out,
@@ -70,6 +72,7 @@ __global__ __launch_bounds__(256) void k_gemm(const h16* __restrict__ A, int lda
       if (EPI == EPI_GELU_POS) reinterpret_cast<float*>(out)[o] = gelu(v) + pos[(size_t)(mm % pos_rows) * N + n];
       if (EPI == EPI_F32) reinterpret_cast<float*>(out)[o] = v;
       if (EPI == EPI_POS) reinterpret_cast<float*>(out)[o] = v + pos[(size_t)(mm % pos_rows) * N + n];
+      if (EPI == EPI_QGELU_F16) reinterpret_cast<h16*>(out)[o] = (h16)quick_gelu(v);
     }
   }
 }

@@ -16,6 +16,8 @@ ffmpeg / OpenCV / Ultralytics on the CPU.
                                            frame_index, width, height, thumbnail_path, bytes}]}   (design only)
     detect_actions(video_path, config) -> {"actions": [{frame_index, timestamp_ms, start_ms, end_ms,
                                            labels[top_k], scores[top_k]}]}             (design only)
+    embed_frames(video_path, config)   -> {"embeddings": [{frame_index, timestamp_ms,
+                                           embedding[projection_dim]}]}                (design only)
 
 What changes underneath (and nothing else): sampled frames are detected in batches instead of one
 ``model(frame)`` call each, and the scene score is computed by K1/K2 instead of an ffmpeg child
@@ -194,7 +196,7 @@ class ModelManager:
                  random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
                  ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None,
                  gpu_vad: bool = False, vad_factory=None, gpu_audio: bool = False, audio_frontend_factory=None,
-                 gpu_speakers: bool = False, speaker_factory=None, action_recognizer_factory=None):
+                 gpu_speakers: bool = False, speaker_factory=None, action_recognizer_factory=None, clip_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
@@ -212,7 +214,9 @@ class ModelManager:
         and resample_float(samples, rate)`` is its seam.  Without it audio that is not 16 kHz raises, as before.
         ``gpu_speakers=True`` (with ``gpu_transcription``) labels the segments' speakers (``eioku_amd.speakers``) when the
         task's ``speaker_labels`` is true; ``speaker_factory(cache_dir, model_name) -> object with label(samples, segments,
-        eps=, min_samples=, assign_max=)`` is its seam (``speaker_model`` in the task's config names the checkpoint)."""
+        eps=, min_samples=, assign_max=)`` is its seam (``speaker_model`` in the task's config names the checkpoint).
+        ``clip_factory(cache_dir, model_name) -> object with encode_images(frames)`` and optionally ``upload(frames)`` and
+        ``close()`` is the seam of ``embed_frames``."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -233,6 +237,7 @@ class ModelManager:
         self._speaker_factory = speaker_factory
         # (cache_dir, model_name) -> object with classify(clips, top_k), labels, frames and optionally upload(frames)
         self._action_recognizer_factory = action_recognizer_factory
+        self._clip_factory = clip_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -613,6 +618,51 @@ class ModelManager:
             return {"actions": actions}
         except Exception as e:
             logger.error(f"Action detection failed: {e}", exc_info=True)
+            raise
+
+    # ---- frame embeddings: CLIP's image tower on the sampled frames (eioku_amd.visual) ----
+    def _load_clip(self, model_name: str):
+        """``<cache>/clip/<model_name>/`` (``eioku_amd.visual``), per job like the other stages."""
+        if self._clip_factory is not None:
+            return self._clip_factory(self.cache_dir, model_name)
+        from .visual import ClipModel
+
+        return ClipModel.from_cache(self.cache_dir, model_name, seed=self._seed)
+
+    async def embed_frames(self, video_path: str, config: dict) -> dict:
+        """Embed frames on the HIP path: every ``max(1, int(fps * frame_interval))``-th frame (``frame_interval`` defaults
+        to 1.0 s) goes through CLIP's image tower (``model_name`` defaults to ``clip-vit-base-patch32``), each batch uploaded
+        once -> ``{"embeddings": [{frame_index, timestamp_ms, embedding: [float] * projection_dim}]}``, unit vectors."""
+        from .visual import embedding_settings
+
+        try:
+            logger.info(f"Frame embedding: {video_path} (device: {self._get_device()})")
+            settings = embedding_settings(config)
+            clip = self._load_clip(settings["model_name"])
+            embeddings: list[dict] = []
+            try:
+                cap = self._open(video_path)
+                try:
+                    fps = cap.fps or 30
+                    interval = _frame_interval(fps, settings["frame_interval"])
+                    upload = getattr(clip, "upload", None)
+                    for meta, frames in _sampled_batches(cap, fps, interval, self._batch_size):
+                        batch = np.stack(frames)
+                        vectors = clip.encode_images(upload(batch) if upload else batch)  # the one upload of these frames
+                        vectors = vectors if isinstance(vectors, np.ndarray) else vectors.cpu().numpy()
+                        for (frame_idx, timestamp_ms), v in zip(meta, vectors):
+                            embeddings.append({"frame_index": frame_idx, "timestamp_ms": timestamp_ms,
+                                               "embedding": [float(x) for x in v]})
+                finally:
+                    cap.release()
+            finally:
+                close = getattr(clip, "close", None)
+                if close:
+                    close()
+            logger.info(f"✅ Frame embedding complete: {len(embeddings)} frames")
+            return {"embeddings": embeddings}
+        except Exception as e:
+            logger.error(f"Frame embedding failed: {e}", exc_info=True)
             raise
 
     async def detect_objects(self, video_path: str, config: dict) -> dict:

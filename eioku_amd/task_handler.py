@@ -19,6 +19,8 @@ storage go through two small hooks carried in the arq ``ctx`` dict.
                         ``vad_filter`` is on (the default) is gated by Silero VAD on the HIP path
     ctx["gpu_audio"]    true (with gpu_transcription): the manager is built with ``gpu_audio=True``, so PCM audio of any
                         sample rate, width and channel count is decoded and resampled to 16 kHz on the HIP path
+    ctx["visual_search_engine"]  optional ``eioku_amd.visual.VisualSearchEngine``: a ``frame_embedding`` task also indexes its
+                        vectors there (replacing the video's earlier rows)
     ctx["gpu_speakers"] true (with gpu_transcription): the manager is built with ``gpu_speakers=True``, so a task whose
                         ``speaker_labels`` is true gets a ``speaker`` key in every "transcript.segment" payload
 """
@@ -39,19 +41,21 @@ TASK_TO_ARTIFACT_TYPE = {"object_detection": "object.detection", "face_detection
                          "scene_detection": "scene", "segment_embedding": "segment.embedding",
                          "place_detection": "place.classification", "ocr": "ocr.text", "topic_extraction": "topic",
                          "thumbnail_generation": "scene.thumbnail", "transcription": "transcript.segment",
-                         "action_detection": "action.detection"}
+                         "action_detection": "action.detection", "frame_embedding": "frame.embedding"}
 TASK_TO_RESULT_KEY = {"object_detection": "detections", "face_detection": "detections", "scene_detection": "scenes",
                       "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections",
                       "topic_extraction": "topics", "thumbnail_generation": "thumbnails", "transcription": "segments",
-                      "action_detection": "actions"}
+                      "action_detection": "actions", "frame_embedding": "embeddings"}
 # the reference's seven (task_handler.py:92-127) + the one its semantic-search design adds after transcription
 # (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them; and the topic stage its
 # worker configs schedule (config/*.json "topic_extraction"; tasks.md 12.1-12.3): KeyBERT keywords of the segments; and the
 # thumbnail worker the design runs behind scene detection (design.md:276-297): one JPEG per scene; and the design's "Action
-# Detector" (design.md §1.8), which the reference never schedules: one "action.detection" envelope per clip
+# Detector" (design.md §1.8), which the reference never schedules: one "action.detection" envelope per clip; and the frame
+# embeddings that let "search my video library using natural language" reach what a video shows: one "frame.embedding"
+# envelope per sampled frame
 KNOWN_TASK_TYPES = ("object_detection", "face_detection", "transcription", "ocr", "place_detection",
                     "scene_detection", "metadata_extraction", "segment_embedding", "topic_extraction",
-                    "thumbnail_generation", "action_detection")
+                    "thumbnail_generation", "action_detection", "frame_embedding")
 
 
 @dataclass
@@ -194,6 +198,12 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             result = await model_manager.generate_thumbnails(video_path, config or {})
         elif task_type == "action_detection":  # one "action.detection" envelope per clip, spanning the clip's frames
             result = await model_manager.detect_actions(video_path, config or {})
+        elif task_type == "frame_embedding":  # one "frame.embedding" envelope per sampled frame
+            result = await model_manager.embed_frames(video_path, config or {})
+            if ctx.get("visual_search_engine") is not None:
+                from .visual import index_frame_embeddings
+
+                index_frame_embeddings(ctx["visual_search_engine"], video_id, result["embeddings"], config)
         elif task_type in ("segment_embedding", "topic_extraction"):
             # segments: the transcription task's output for this video.  The reference would read them back from its
             # artifact table; without a database they arrive in the job config or through ctx["segment_source"](video_id)

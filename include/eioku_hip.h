@@ -895,6 +895,47 @@ int eioku_timesformer_topk(eioku_timesformer_t* m, const float* logits, int n, i
 int eioku_timesformer_last_flops(const eioku_timesformer_t* m, double* flops);
 int eioku_timesformer_last_ms(const eioku_timesformer_t* m, double* preprocess_ms, double* encoder_ms, double* head_ms);
 
+/* ---- CLIP frame and text embeddings (K26), csrc/clip.hip -------------------------------------------------------------------
+ * Hugging Face CLIPModel (openai/clip-vit-base-patch32, -patch16, -large-patch14 and checkpoints converted to that layout):
+ * fp16 matrix weights and activations, fp32 residual stream, accumulators, projection and outputs.  [PUBLIC-LIB]: restated
+ * from the public transformers / CLIP sources.  P = (image / patch)^2 patches; vision token 0 is CLS.
+ *   create: both head dimensions (hidden / heads) 64, image a multiple of patch and at most 448, positions at most 77, both
+ *     ffn multiples of 32, act 0 = quick_gelu, 1 = gelu; anything else is EIOKU_EINVAL.  layers may be 0.
+ *   tensor_info / set_tensor: fp32, row-major rows x cols, under the names and in the order of the model's state_dict()
+ *     (text_model.*, vision_model.*, visual_projection.weight, text_projection.weight; no logit_scale, no position_ids).
+ *     q_proj / k_proj / v_proj are stored as one packed [3 hidden][hidden] weight; patch_embedding.weight is hidden x 3 p p
+ *     (column c p p + ky p + kx), stored with its rows zero-padded to a multiple of 32.  Biases are rows x 1.
+ *   set_norm: per-channel (R, G, B) mean and std of the preprocessing; OpenAI's CLIP values until set.
+ *   preprocess: n BGR u8 frames of h x w (host or device per mem) -> Pillow's bicubic resize and centre crop to image x
+ *     image, BGR -> RGB, (v * (1 / 255) - mean) / std, as fp16 patch rows [frame][1 + P][Kp] with token 0 and the columns
+ *     past 3 p p zero (Kp = 3 p p rounded up to 32; device, optional), and / or the cropped RGB u8 image [frame][image]
+ *     [image][3] (device, optional).  Tables: HOST int32, as for eioku_timesformer_preprocess, from the bicubic filter.
+ *   encode_patches: patch rows -> unit vectors [n][projection_dim] fp32 and optionally hidden_out [n][1 + P][hidden] fp32,
+ *     the residual stream before post_layernorm.  Device buffers, asynchronous.
+ *   encode_images: preprocess + encode_patches; the vectors arrive on the side `mem` names.
+ *   encode_text: HOST ids [n_texts][positions] and eot [n_texts] (the pooled position of each text); positions 0 .. n - 1
+ *     are run under the causal mask (every eot < n <= positions) -> unit vectors and optionally hidden_out [n_texts][n]
+ *     [hidden] (before final_layer_norm), on the side `mem` names.
+ *   last_flops: GEMM and attention FLOPs of the last encode call.  last_ms: its device time per stage. */
+typedef struct eioku_clip eioku_clip_t;
+int eioku_clip_create(int image, int patch, int v_hidden, int v_layers, int v_heads, int v_ffn, int vocab, int positions, int t_hidden,
+                      int t_layers, int t_heads, int t_ffn, int projection_dim, float ln_eps, int act, eioku_clip_t** out);
+void eioku_clip_destroy(eioku_clip_t* m);
+int eioku_clip_num_tensors(const eioku_clip_t* m);
+int eioku_clip_tensor_info(const eioku_clip_t* m, int idx, char* name, size_t name_cap, int* rows, int* cols);
+int eioku_clip_set_tensor(eioku_clip_t* m, int idx, const float* host_data, size_t numel);
+int eioku_clip_set_norm(eioku_clip_t* m, const float* mean_rgb, const float* std_rgb);
+int eioku_clip_preprocess(eioku_clip_t* m, const uint8_t* bgr, int n, int h, int w, const int32_t* xbounds, const int32_t* xk, int kx,
+                          const int32_t* ybounds, const int32_t* yk, int ky, void* patches_out, uint8_t* out_rgb_u8, int mem,
+                          void* stream);
+int eioku_clip_encode_patches(eioku_clip_t* m, const void* patches, int n, float* out, float* hidden_out, void* stream);
+int eioku_clip_encode_images(eioku_clip_t* m, const uint8_t* bgr, int n, int h, int w, const int32_t* xbounds, const int32_t* xk,
+                             int kx, const int32_t* ybounds, const int32_t* yk, int ky, float* out, int mem, void* stream);
+int eioku_clip_encode_text(eioku_clip_t* m, const int32_t* ids, const int32_t* eot, int n_texts, int n, float* out,
+                           float* hidden_out, int mem, void* stream);
+int eioku_clip_last_flops(const eioku_clip_t* m, double* flops);
+int eioku_clip_last_ms(const eioku_clip_t* m, double* preprocess_ms, double* encoder_ms, double* head_ms);
+
 #ifdef __cplusplus
 }
 #endif
