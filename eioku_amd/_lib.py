@@ -322,6 +322,15 @@ SIGNATURES = {
                                          C.c_void_p]),
     "eioku_clip_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_clip_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "eioku_nomic_create": (C.c_int, [C.c_int] * 7 + [C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
+    "eioku_nomic_destroy": (None, [C.c_void_p]),
+    "eioku_nomic_num_tensors": (C.c_int, [C.c_void_p]),
+    "eioku_nomic_tensor_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eioku_nomic_set_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "eioku_nomic_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p]),
+    "eioku_nomic_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_nomic_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 

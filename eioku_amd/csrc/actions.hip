@@ -386,7 +386,7 @@ int gemm(Model* m, hipStream_t st, const h16* A, int lda, const Lin& w, int M, i
   EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0, "GEMM K %d / lda %d misaligned", K, lda);
   if (M == 0) return EIOKU_OK;
   const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
-  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, st, A, lda, m->H(w.w), K, m->F(w.b), M, N, K, out, ldc, pos, pos_rows);
+  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, st, A, lda, m->H(w.w), K, m->F(w.b), M, N, K, out, ldc, pos, pos_rows, nullptr);
   m->flops += 2.0 * M * N * K;
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;

@@ -283,7 +283,7 @@ int gemm(Model* m, hipStream_t st, const h16* A, int lda, int w, int bias, int M
   if (M == 0) return EIOKU_OK;
   const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
   hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, st, A, lda, m->H(w), K, bias >= 0 ? m->F(bias) : nullptr, M, N, K, out, ldc,
-                     pos, pos_rows);
+                     pos, pos_rows, nullptr);
   m->flops += 2.0 * M * N * K;
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;

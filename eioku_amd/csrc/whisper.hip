@@ -1186,7 +1186,7 @@ int gemm(eioku_whisper* m, const h16* A, int lda, const h16* W, int ldw, const f
          long long ldc, const float* pos = nullptr, int pos_rows = 1) {
   EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0 && ldw % 8 == 0, "GEMM K %d / lda %d / ldw %d misaligned", K, lda, ldw);
   const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
-  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, 0, A, lda, W, ldw, bias, M, N, K, out, ldc, pos, pos_rows);
+  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, 0, A, lda, W, ldw, bias, M, N, K, out, ldc, pos, pos_rows, nullptr);
   m->flops += 2.0 * M * N * K;
   return launched(m);
 }

@@ -66,30 +66,56 @@ class WordPieceTokenizer:
 
 
 class EmbeddingGenerator:
-    """design.md 2.1: text -> 384-d unit vector (K8).  ``encoder``: a loaded :class:`eioku_amd.embed.MiniLMEncoder`."""
+    """design.md 2.1: text -> unit vector.  ``encoder``: a loaded :class:`eioku_amd.embed.MiniLMEncoder` (K8, 384-d) or
+    :class:`eioku_amd.embed.NomicEncoder` (K27).  ``document_prefix`` / ``query_prefix`` / ``clustering_prefix`` go in front of
+    a text of that ``kind`` before it is tokenised (nomic-embed-text's task prefixes); empty prefixes change nothing."""
 
-    def __init__(self, encoder, tokenizer: WordPieceTokenizer, max_seq_length: int = 256, batch_size: int = 512):
+    def __init__(self, encoder, tokenizer: WordPieceTokenizer, max_seq_length: int = 256, batch_size: int = 512,
+                 document_prefix: str = "", query_prefix: str = "", clustering_prefix: str = ""):
         self.encoder, self.tokenizer = encoder, tokenizer
         self.max_seq_length, self.batch_size = max_seq_length, batch_size
+        self.prefixes = {"document": document_prefix, "query": query_prefix, "clustering": clustering_prefix}
 
     @classmethod
-    def from_directory(cls, model_dir: str | Path, **kw):
-        """``model_dir``: the all-MiniLM-L6-v2 snapshot (``model.safetensors`` / ``pytorch_model.bin`` + ``vocab.txt``)."""
+    def from_directory(cls, model_dir: str | Path, state=None, matryoshka_dim: int | None = 512, **kw):
+        """``model_dir``: a model snapshot (``model.safetensors`` / ``pytorch_model.bin`` + ``vocab.txt``).  A ``config.json``
+        whose ``model_type`` is ``nomic_bert`` builds nomic-embed-text: the model card's task prefixes, ``max_seq_length`` 2048
+        (or the config's ``max_position_embeddings`` if smaller) and vectors cut to ``matryoshka_dim`` (512 fits
+        ``IndexFlatL2``; ``None``, or a model no wider than that, keeps the full width).  Any other directory is
+        all-MiniLM-L6-v2.  ``state``: weights to use instead of the directory's file."""
         from . import embed
 
         model_dir = Path(model_dir)
-        return cls(embed.MiniLMEncoder(embed.load_state(model_dir, embed.MINILM_L6_V2)), WordPieceTokenizer(model_dir / "vocab.txt"), **kw)
+        tokenizer = WordPieceTokenizer(model_dir / "vocab.txt")
+        config = json.loads((model_dir / "config.json").read_text(encoding="utf-8")) if (model_dir / "config.json").exists() else {}
+        if config.get("model_type") == "nomic_bert":
+            cfg = embed.nomic_config(config)
+            if matryoshka_dim is not None and matryoshka_dim >= cfg["hidden"]:
+                matryoshka_dim = None
+            enc = embed.NomicEncoder(state if state is not None else embed.nomic_load_state(model_dir, cfg), cfg, tokenizer, matryoshka_dim)
+            p = embed.NOMIC_PREFIXES
+            kw = {"max_seq_length": min(2048, cfg["max_pos"]), "document_prefix": p["document"], "query_prefix": p["query"],
+                  "clustering_prefix": p["clustering"], **kw}
+            return cls(enc, tokenizer, **kw)
+        return cls(embed.MiniLMEncoder(state if state is not None else embed.load_state(model_dir, embed.MINILM_L6_V2)), tokenizer, **kw)
 
-    def generate_batch_embeddings(self, texts: list[str]) -> np.ndarray:
+    def tokenize(self, texts: list[str], kind: str = "document"):
+        """-> (ids int32 (B,S), mask uint8 (B,S)) of ``prefix(kind) + text``, truncated at ``max_seq_length``"""
+        if kind not in self.prefixes:
+            raise ValueError(f"kind must be one of {sorted(self.prefixes)}, got {kind!r}")
+        prefix = self.prefixes[kind]
+        return self.tokenizer.encode_batch([prefix + t for t in texts] if prefix else texts, self.max_seq_length)
+
+    def generate_batch_embeddings(self, texts: list[str], kind: str = "document") -> np.ndarray:
         out = []
         for lo in range(0, len(texts), self.batch_size):
-            ids, mask = self.tokenizer.encode_batch(texts[lo:lo + self.batch_size], self.max_seq_length)
+            ids, mask = self.tokenize(texts[lo:lo + self.batch_size], kind)
             out.append(np.asarray(self.encoder.encode_ids(ids, mask)))
         H = self.encoder.cfg["hidden"]
         return np.concatenate(out) if out else np.zeros((0, H), np.float32)
 
-    def generate_embedding(self, text: str) -> np.ndarray:
-        return self.generate_batch_embeddings([text])[0]
+    def generate_embedding(self, text: str, kind: str = "query") -> np.ndarray:
+        return self.generate_batch_embeddings([text], kind)[0]
 
 
 @dataclass
@@ -352,7 +378,7 @@ class SemanticSearchEngine:
         ``start`` / ``end`` seconds (or ``start_ms`` / ``end_ms``); optional ``file_created_at`` / ``video_duration`` make
         the segment filterable by date and duration (see :class:`VectorStore`)."""
         texts = [s["text"] for s in segments]
-        emb = self.generator.generate_batch_embeddings(texts)
+        emb = self.generator.generate_batch_embeddings(texts)  # kind "document", the generator's default
         meta = []
         for i, s in enumerate(segments):
             start = s["start_ms"] / 1000.0 if "start_ms" in s else float(s.get("start", 0.0))
@@ -365,7 +391,7 @@ class SemanticSearchEngine:
         return self.store.index_segments([f"{video_id}_seg{i}" for i in range(len(segments))], emb, meta)
 
     def search(self, query: str, filters: dict | None = None, top_k: int = 10) -> list[SearchResult]:
-        q = self.generator.generate_embedding(query)
+        q = self.generator.generate_embedding(query, kind="query")
         return [SearchResult(m["video_id"], m["segment_id"], m["start_time"], m["end_time"], 1.0 - dist / 2.0, m["text"],
                              m.get("thumbnail_path")) for dist, m in self.store.search(q, top_k, filters)]
 

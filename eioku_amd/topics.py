@@ -183,7 +183,9 @@ def aggregate_topics(per_video: dict) -> list[dict]:
 
 class TopicExtractor:
     """KeyBERT keywords and topics for one video's transcript on the GPU.  ``generator``: an
-    :class:`eioku_amd.semantic.EmbeddingGenerator` (its K8 encoder and WordPiece tokenizer)."""
+    :class:`eioku_amd.semantic.EmbeddingGenerator` (its encoder and WordPiece tokenizer).  Segment texts and candidate terms
+    are tokenised as kind ``"clustering"``: with a nomic-embed-text generator both carry the ``"clustering: "`` task prefix,
+    with K8 the prefix is empty."""
 
     def __init__(self, generator):
         self.generator = generator
@@ -200,7 +202,7 @@ class TopicExtractor:
         g = self.generator
         out = []
         for lo in range(0, len(texts), g.batch_size):
-            ids, mask = g.tokenizer.encode_batch(texts[lo:lo + g.batch_size], g.max_seq_length)
+            ids, mask = g.tokenize(texts[lo:lo + g.batch_size], "clustering")
             out.append(self._encode(ids, mask, dev))
         return torch.cat(out) if out else torch.zeros((0, g.encoder.cfg["hidden"]), dtype=torch.float32, device=dev)
 
@@ -214,7 +216,7 @@ class TopicExtractor:
         calls = []
         if not terms:
             return emb, calls
-        ids, mask = g.tokenizer.encode_batch(terms, g.max_seq_length)
+        ids, mask = g.tokenize(terms, "clustering")
         lens = mask.sum(1).astype(np.int64)
         for L in np.unique(lens):
             rows = np.flatnonzero(lens == L)

@@ -936,6 +936,34 @@ int eioku_clip_encode_text(eioku_clip_t* m, const int32_t* ids, const int32_t* e
 int eioku_clip_last_flops(const eioku_clip_t* m, double* flops);
 int eioku_clip_last_ms(const eioku_clip_t* m, double* preprocess_ms, double* encoder_ms, double* head_ms);
 
+/* ---- nomic-embed-text sentence vectors over packed sequences (K27), csrc/nomic.hip ------------------------------------------
+ * Hugging Face NomicBertModel (nomic-ai/nomic-embed-text-v1.5): no position table, rotary q / k (rotate_half, head_dim 64),
+ * post-LN layers, SwiGLU, no Linear bias; fp16 matrix weights and activations, fp32 tables, residual stream, pooling and
+ * outputs.  [PUBLIC-LIB]: restated from the public transformers sources.
+ *   create: head_dim (hidden / heads) 64, hidden <= 8192, ffn a multiple of 32, max_pos in [1, 8192], plain RoPE with base
+ *     rope_theta; anything else is EIOKU_EINVAL.  layers may be 0.
+ *   tensor_info / set_tensor: fp32, row-major rows x cols, under the names and in the order of the model's state_dict()
+ *     (embeddings.*, layers.N.*).  q_proj / k_proj / v_proj are stored as one packed [3 hidden][hidden] weight with the rows of
+ *     q and k permuted inside each head (stored row 2j = row j, 2j + 1 = row j + 32); gate_proj / up_proj as one interleaved
+ *     [2 ffn][hidden] weight.  LayerNorm parameters are rows x 1.
+ *   encode: ids [T] and cu [B + 1] int32 (sequence b = rows cu[b] .. cu[b + 1] - 1, cu[0] = 0, T = cu[B]); every length in
+ *     [1, max_pos], every id inside the vocabulary, else EIOKU_EINVAL.  -> out [B][dim] fp32: the token mean, then for
+ *     matryoshka_dim > 0 the affine-free LayerNorm (eps 1e-5) over the full width and the first matryoshka_dim columns, then
+ *     L2-normalised (dim = matryoshka_dim, or hidden when it is 0); optionally hidden_out [T][hidden] fp32, the last hidden
+ *     state.  All four buffers on the side `mem` names.  Synchronises the stream.
+ *   last_flops: GEMM and attention FLOPs of the last encode call.  last_ms: its device time. */
+typedef struct eioku_nomic eioku_nomic_t;
+int eioku_nomic_create(int vocab, int hidden, int layers, int heads, int ffn, int max_pos, int type_vocab, float ln_eps, float rope_theta,
+                       eioku_nomic_t** out);
+void eioku_nomic_destroy(eioku_nomic_t* m);
+int eioku_nomic_num_tensors(const eioku_nomic_t* m);
+int eioku_nomic_tensor_info(const eioku_nomic_t* m, int idx, char* name, size_t name_cap, int* rows, int* cols);
+int eioku_nomic_set_tensor(eioku_nomic_t* m, int idx, const float* host_data, size_t numel);
+int eioku_nomic_encode(eioku_nomic_t* m, const int32_t* ids, const int32_t* cu, int B, int matryoshka_dim, float* out, float* hidden_out,
+                       int mem, void* stream);
+int eioku_nomic_last_flops(const eioku_nomic_t* m, double* flops);
+int eioku_nomic_last_ms(const eioku_nomic_t* m, double* ms);
+
 #ifdef __cplusplus
 }
 #endif
