@@ -4,11 +4,12 @@
 //                       (v * (1 / 255) - mean) / std in fp32 and one rounding to fp16, written as patch rows
 //                       [clip][patch][frame][c * 256 + ky * 16 + kx]: the patch embedding is one GEMM, no im2col pass
 //   k_gemm<., EPI_POS>  (gemm_f16.h) patch projection + bias + (position + time) table into the fp32 residual stream
-//   k_ln_eps            LayerNorm with an eps argument, fp32 row -> fp16
+//   k_ln<h16>           (layernorm.h) LayerNorm, fp32 row -> fp16
 //   k_attn_time         temporal attention: T <= 96 keys of one (clip, patch, head) per one-wave workgroup, q / k / v in LDS,
 //                       fp32 scores
-//   k_attn_space        spatial attention: 1 + P keys of one (clip, frame, head); 64 queries per workgroup, keys / values
-//                       staged through LDS 128 at a time, QK^T and PV on v_mfma_f32_16x16x32_f16 with an online softmax
+//   k_attn_tiles<SpaceTimeSeq, false>  (attn_f16.h) spatial attention: 1 + P keys of one (clip, frame, head); 64 queries per
+//                       workgroup, keys / values staged through LDS 128 at a time, QK^T and PV on v_mfma_f32_16x16x32_f16
+//                       with an online softmax
 //   k_cls_mean          the CLS rule: mean over the frames (t = 0 .. T - 1, fp32) of the projected CLS outputs, added to CLS
 //   k_action_head       softmax and top-k of the logits, ties to the smaller class index
 // Residual stream x, fp32: the B P T patch rows first, row (b P + p) T + t, then the B CLS rows.  The temporal GEMMs see the
@@ -18,9 +19,12 @@
 // LayerNorm parameters and the embedding tables fp32; the residual stream fp32; LayerNorm outputs, q / k / v, attention
 // outputs, the temporal out-projection, GELU outputs and the patch rows are rounded to fp16; the spatial kernel rounds
 // its softmax numerators exp(s - max) to fp16 for the PV MFMA.
+#include "attn_f16.h"
 #include "clip_resize.h"
 #include "common.h"
 #include "gemm_f16.h"
+#include "layernorm.h"
+#include "tensors.h"
 
 #include <cmath>
 #include <string>
@@ -32,18 +36,10 @@ namespace {
 
 constexpr int kPatch = 16, kPatchK = 3 * kPatch * kPatch;
 constexpr int kMaxFrames = 96, kMaxImage = 448;
-constexpr int kKC = 128;       // keys per LDS stage of k_attn_space
-constexpr int kKStride = 72;   // halfs per staged key row (64 + 8: 144 B, 16-byte aligned, spreads the banks)
-constexpr int kVStride = kKC + 2;  // halfs per staged value column (65 words: a column starts one bank after its neighbour)
 
 // ---- clip preprocessing: k_clip_resize_h / k_clip_resize_v and their launch, clip_resize.h ----------------------------------
 
 // ---- small kernels ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_cvt_f16(const float* __restrict__ src, size_t n, h16* __restrict__ dst) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dst[i] = (h16)src[i];
-}
-
 // the embedding tables the GEMM epilogue and the CLS rows read: postime[p T + t] = position[1 + p] + time[t],
 // cls = cls_token + position[0]
 __global__ __launch_bounds__(256) void k_embed_tables(const float* __restrict__ pos, const float* __restrict__ time,
@@ -66,28 +62,6 @@ __global__ __launch_bounds__(256) void k_embed_tables(const float* __restrict__ 
 __global__ __launch_bounds__(256) void k_cls_rows(const float* __restrict__ cls, int B, int d, float* __restrict__ x) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < (size_t)B * d) x[i] = cls[i % d];
-}
-
-// LayerNorm: fp32 row -> fp16, one wave per row
-__global__ __launch_bounds__(256) void k_ln_eps(const float* __restrict__ x, int M, int d, const float* __restrict__ g,
-                                                const float* __restrict__ b, float eps, h16* __restrict__ out) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const float* xr = x + (size_t)row * d;
-  float s = 0.f;
-  for (int i = lane; i < d; i += 64) s += xr[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  const float mean = s / (float)d;
-  float q = 0.f;
-  for (int i = lane; i < d; i += 64) {
-    const float c = xr[i] - mean;
-    q += c * c;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  const float inv = 1.f / sqrtf(q / (float)d + eps);
-  for (int i = lane; i < d; i += 64) out[(size_t)row * d + i] = (h16)((xr[i] - mean) * inv * g[i] + b[i]);
 }
 
 // the CLS rule: x_cls[b] += (sum over t = 0 .. T - 1 of proj[b T + t]) / T, in fp32 and in frame order
@@ -168,105 +142,6 @@ __global__ __launch_bounds__(64) void k_attn_time(const h16* __restrict__ qkv, i
   }
 }
 
-// ---- spatial attention ------------------------------------------------------------------------------------------------------
-// qkv [B P T + B][3 d] fp16 in the stream's row order.  Problem (b, t, head): token 0 is the clip's CLS row B P T + b, token
-// 1 + p the patch row (b P + p) T + t; n = 1 + P queries and keys.  grid (ceil(n / 64), heads, B T), 4 waves of 16 queries.
-// Keys and values go through LDS kKC at a time (keys [key][72], values transposed [dim][kKC + 2]).  Per 32 keys and wave:
-// S^T = K Q^T in two 16-key MFMA tiles (lane (r, u): query r, keys 4u .. 4u + 3 of each tile), the online softmax per
-// query across the lanes r, r + 16, r + 32, r + 48, then O^T += V^T P^T with the 32 keys in the order the lanes already
-// hold them (slot 8u + t: key 4u + t of the first tile, slot 8u + 4 + t: of the second), p = exp(s - max) rounded to fp16.
-// Patch outputs go to out_patch [B P T][d], the CLS output of frame t to out_cls [b T + t][d].
-__global__ __launch_bounds__(256) void k_attn_space(const h16* __restrict__ qkv, int B, int P, int T, int heads,
-                                                    h16* __restrict__ out_patch, h16* __restrict__ out_cls) {
-  __shared__ __align__(16) h16 sk[kKC * kKStride];
-  __shared__ __align__(16) h16 svt[64 * kVStride];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, u = lane >> 4;
-  const int head = blockIdx.y, b = blockIdx.z / T, t = blockIdx.z % T;
-  const int d = heads * 64, n = 1 + P;
-  const size_t ld = (size_t)3 * d;
-  auto token_row = [&](int tok) -> size_t { return tok == 0 ? (size_t)B * P * T + b : ((size_t)b * P + tok - 1) * T + t; };
-  const int q = blockIdx.x * 64 + wave * 16 + r;  // this lane's query token
-  half8 q0 = {}, q1 = {};
-  if (q < n) {
-    const h16* qr = qkv + token_row(q) * ld + head * 64 + 8 * u;
-    q0 = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(qr));
-    q1 = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(qr + 32));
-  }
-  float4v acc[4];
-#pragma unroll
-  for (int f = 0; f < 4; ++f) acc[f] = float4v{0.f, 0.f, 0.f, 0.f};
-  float mx = -INFINITY, sum = 0.f;  // sum: this lane's share, joined over u at the end
-  for (int k0 = 0; k0 < n; k0 += kKC) {
-    const int nk = n - k0 < kKC ? n - k0 : kKC, nk32 = (nk + 31) & ~31;
-    __syncthreads();  // the previous stage has been read
-    for (int i = threadIdx.x; i < nk32 * 8; i += 256) {
-      const int piece = i & 7, key = i >> 3;
-      uint4 kv = {0, 0, 0, 0}, vv = {0, 0, 0, 0};  // keys past the end: zeros (masked below; 0 * value adds nothing)
-      if (key < nk) {
-        const h16* row = qkv + token_row(k0 + key) * ld + head * 64 + piece * 8;
-        kv = *reinterpret_cast<const uint4*>(row + d);
-        vv = *reinterpret_cast<const uint4*>(row + 2 * d);
-      }
-      *reinterpret_cast<uint4*>(sk + key * kKStride + piece * 8) = kv;
-      const half8 vh = __builtin_bit_cast(half8, vv);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) svt[(piece * 8 + e) * kVStride + key] = vh[e];
-    }
-    __syncthreads();
-    for (int j0 = 0; j0 < nk32; j0 += 32) {
-      float4v s[2];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const h16* kr = sk + (j0 + 16 * e + r) * kKStride + 8 * u;
-        const half8 ka = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(kr));
-        const half8 kb = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(kr + 32));
-        s[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka, q0, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        s[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kb, q1, s[e], 0, 0, 0);
-      }
-      float m_new = mx;
-#pragma unroll
-      for (int e = 0; e < 2; ++e)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int key = j0 + 16 * e + 4 * u + i;
-          s[e][i] = key < nk ? s[e][i] * 0.125f : -INFINITY;
-          m_new = fmaxf(m_new, s[e][i]);
-        }
-      m_new = fmaxf(m_new, __shfl_xor(m_new, 16, 64));
-      m_new = fmaxf(m_new, __shfl_xor(m_new, 32, 64));  // finite from the first 32 keys on: key 0 is never masked
-      const float alpha = expf(mx - m_new);
-      mx = m_new;
-      half8 p;
-      float ps = 0.f;
-#pragma unroll
-      for (int e = 0; e < 2; ++e)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const h16 ph = (h16)expf(s[e][i] - m_new);
-          p[4 * e + i] = ph;
-          ps += (float)ph;
-        }
-      sum = sum * alpha + ps;
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        const h16* vr = svt + (16 * f + r) * kVStride + j0 + 4 * u;
-        const unsigned* va = reinterpret_cast<const unsigned*>(vr);  // 4-byte aligned: kVStride, j0 and 4u are even
-        const uint4 v4 = {va[0], va[1], va[8], va[9]};
-        acc[f] = acc[f] * alpha;
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, v4), p, acc[f], 0, 0, 0);
-      }
-    }
-  }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
-  if (q >= n) return;
-  h16* o = (q == 0 ? out_cls + ((size_t)b * T + t) * d : out_patch + token_row(q) * d) + head * 64 + 4 * u;
-#pragma unroll
-  for (int f = 0; f < 4; ++f)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[16 * f + i] = (h16)(acc[f][i] / sum);
-}
-
 // ---- head ---------------------------------------------------------------------------------------------------------------
 // one workgroup per clip: probs = softmax(logits) in fp32 (each exponential and their sum computed in fp64 and rounded to
 // fp32 once, so neither depends on the order of the sum or on the exp of a math library; one fp32 division), then top_k
@@ -329,18 +204,6 @@ __global__ __launch_bounds__(256) void k_action_head(const float* __restrict__ l
 }
 
 // ---- the model ------------------------------------------------------------------------------------------------------------
-enum { T_F16 = 0, T_F32 = 1 };
-
-struct Tensor {
-  std::string name;
-  int rows = 0, cols = 0, kind = T_F16;
-  DevBuf<uint8_t> dev;
-  bool set = false;
-  size_t numel() const { return (size_t)rows * cols; }
-};
-
-struct Lin { int w, b; };
-struct LNorm { int g, b; };
 struct Layer {
   LNorm t_ln, s_ln, m_ln;
   Lin t_qkv, t_out, t_dense, s_qkv, s_out, fc1, fc2;
@@ -348,12 +211,11 @@ struct Layer {
 
 }  // namespace
 
-struct eioku_timesformer {
+struct eioku_timesformer : TensorTable {
   int image = 0, frames = 0, d = 0, layers = 0, heads = 0, ffn = 0, labels = 0;
   int side = 0, P = 0;
   float eps = 1e-6f;
   Norm3 nrm{{0.45f, 0.45f, 0.45f}, {0.225f, 0.225f, 0.225f}};
-  std::vector<Tensor> tensors;
   std::vector<Layer> L;
   int cls_token = 0, pos = 0, time = 0;
   Lin proj{}, classifier{};
@@ -371,9 +233,6 @@ struct eioku_timesformer {
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool timed[3] = {false, false, false};  // which of preprocess / encoder / head the last call ran
   double flops = 0;
-
-  const h16* H(int i) const { return (const h16*)tensors[i].dev.p; }
-  const float* F(int i) const { return (const float*)tensors[i].dev.p; }
 };
 
 namespace {
@@ -383,23 +242,12 @@ typedef eioku_timesformer Model;
 template <int MT, int EPI>
 int gemm(Model* m, hipStream_t st, const h16* A, int lda, const Lin& w, int M, int N, int K, void* out, long long ldc,
          const float* pos = nullptr, int pos_rows = 1) {
-  EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0, "GEMM K %d / lda %d misaligned", K, lda);
-  if (M == 0) return EIOKU_OK;
-  const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
-  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, st, A, lda, m->H(w.w), K, m->F(w.b), M, N, K, out, ldc, pos, pos_rows, nullptr);
-  m->flops += 2.0 * M * N * K;
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
+  return launch_gemm<MT, EPI>(st, A, lda, m->H(w.w), K, m->F(w.b), M, N, K, out, ldc, pos, pos_rows, nullptr, &m->flops);
 }
 
 int ln(Model* m, hipStream_t st, const float* x, int M, const LNorm& p, h16* out) {
-  hipLaunchKernelGGL(k_ln_eps, dim3((M + 3) / 4), dim3(256), 0, st, x, M, m->d, m->F(p.g), m->F(p.b), m->eps, out);
+  hipLaunchKernelGGL(k_ln<h16>, dim3((M + 3) / 4), dim3(256), 0, st, x, M, m->d, m->F(p.g), m->F(p.b), m->eps, (const int*)nullptr, out);
   EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
-}
-
-int check_weights(const Model* m) {
-  for (const auto& t : m->tensors) EIOKU_REQUIRE(t.set, "tensor %s has no weights", t.name.c_str());
   return EIOKU_OK;
 }
 
@@ -450,8 +298,7 @@ int run_encoder(Model* m, const h16* patches, int B, hipStream_t st) {
     EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->h, d, L.s_qkv, M, 3 * d, d, m->qkv.p, 3 * d)));
     {
       const int n = 1 + P;
-      hipLaunchKernelGGL(k_attn_space, dim3((n + 63) / 64, m->heads, B * T), dim3(256), 0, st, m->qkv.p, B, P, T, m->heads, m->a.p, a_cls);
-      EIOKU_LAUNCH_CHECK();
+      EIOKU_TRY(launch_attn<false>(st, m->qkv.p, SpaceTimeSeq{B, P, T, d, m->a.p, a_cls}, n, m->heads, B * T));
       m->flops += 4.0 * B * T * m->heads * (double)n * n * 64;
     }
     EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->a, d, L.s_out, Mp, d, d, x, d)));
@@ -505,52 +352,33 @@ int eioku_timesformer_create(int image, int patch, int frames, int hidden, int l
   m->image = image, m->frames = frames, m->d = hidden, m->layers = layers, m->heads = heads, m->ffn = ffn, m->labels = labels;
   m->side = image / kPatch, m->P = m->side * m->side, m->eps = ln_eps;
   const int d = hidden;
-  auto add = [&](const std::string& n, int rows, int cols, int kind) {
-    Tensor t;
-    t.name = n, t.rows = rows, t.cols = cols, t.kind = kind;
-    m->tensors.push_back(std::move(t));
-    return (int)m->tensors.size() - 1;
-  };
-  auto lin = [&](const std::string& p, int rows, int cols) {
-    Lin l;
-    l.w = add(p + ".weight", rows, cols, T_F16);
-    l.b = add(p + ".bias", rows, 1, T_F32);
-    return l;
-  };
-  auto lnorm = [&](const std::string& p) {
-    LNorm l;
-    l.g = add(p + ".weight", d, 1, T_F32);
-    l.b = add(p + ".bias", d, 1, T_F32);
-    return l;
-  };
   const std::string e = "timesformer.embeddings.";
-  m->cls_token = add(e + "cls_token", 1, d, T_F32);
-  m->pos = add(e + "position_embeddings", 1 + m->P, d, T_F32);
-  m->time = add(e + "time_embeddings", frames, d, T_F32);
-  m->proj = lin(e + "patch_embeddings.projection", d, kPatchK);
+  m->cls_token = m->add(e + "cls_token", 1, d, T_F32);
+  m->pos = m->add(e + "position_embeddings", 1 + m->P, d, T_F32);
+  m->time = m->add(e + "time_embeddings", frames, d, T_F32);
+  m->proj = m->lin(e + "patch_embeddings.projection", d, kPatchK);
   for (int l = 0; l < layers; ++l) {
     const std::string p = "timesformer.encoder.layer." + std::to_string(l) + ".";
     Layer L;
-    L.t_ln = lnorm(p + "temporal_layernorm");
-    L.t_qkv = lin(p + "temporal_attention.attention.qkv", 3 * d, d);
-    L.t_out = lin(p + "temporal_attention.output.dense", d, d);
-    L.t_dense = lin(p + "temporal_dense", d, d);
-    L.s_ln = lnorm(p + "layernorm_before");
-    L.s_qkv = lin(p + "attention.attention.qkv", 3 * d, d);
-    L.s_out = lin(p + "attention.output.dense", d, d);
-    L.m_ln = lnorm(p + "layernorm_after");
-    L.fc1 = lin(p + "intermediate.dense", ffn, d);
-    L.fc2 = lin(p + "output.dense", d, ffn);
+    L.t_ln = m->lnorm(p + "temporal_layernorm", d);
+    L.t_qkv = m->lin(p + "temporal_attention.attention.qkv", 3 * d, d);
+    L.t_out = m->lin(p + "temporal_attention.output.dense", d, d);
+    L.t_dense = m->lin(p + "temporal_dense", d, d);
+    L.s_ln = m->lnorm(p + "layernorm_before", d);
+    L.s_qkv = m->lin(p + "attention.attention.qkv", 3 * d, d);
+    L.s_out = m->lin(p + "attention.output.dense", d, d);
+    L.m_ln = m->lnorm(p + "layernorm_after", d);
+    L.fc1 = m->lin(p + "intermediate.dense", ffn, d);
+    L.fc2 = m->lin(p + "output.dense", d, ffn);
     m->L.push_back(L);
   }
-  m->final_ln = lnorm("timesformer.layernorm");
-  m->classifier = lin("classifier", labels, d);
+  m->final_ln = m->lnorm("timesformer.layernorm", d);
+  m->classifier = m->lin("classifier", labels, d);
   auto fail = [&](int rc) {
     eioku_timesformer_destroy(m);
     return rc;
   };
-  for (auto& t : m->tensors)
-    if (t.dev.grow(t.numel() * (t.kind == T_F32 ? 4 : 2))) return fail(EIOKU_ENOMEM);
+  if (const int rc = m->finish()) return fail(rc);
   if (m->postime.grow((size_t)m->P * frames * d) || m->cls.grow((size_t)d)) return fail(EIOKU_ENOMEM);
   for (auto& ev : m->ev)
     if (hipEventCreate(&ev) != hipSuccess) {
@@ -570,34 +398,14 @@ void eioku_timesformer_destroy(eioku_timesformer* m) {
   delete m;  // every buffer frees itself
 }
 
-int eioku_timesformer_num_tensors(const eioku_timesformer* m) { return m ? (int)m->tensors.size() : 0; }
+int eioku_timesformer_num_tensors(const eioku_timesformer* m) { return TensorTable::count(m); }
 
 int eioku_timesformer_tensor_info(const eioku_timesformer* m, int idx, char* name, size_t cap, int* rows, int* cols) {
-  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size(), "bad tensor index %d", idx);
-  const auto& t = m->tensors[idx];
-  if (name && cap) snprintf(name, cap, "%s", t.name.c_str());
-  if (rows) *rows = t.rows;
-  if (cols) *cols = t.cols;
-  return EIOKU_OK;
+  return TensorTable::info(m, idx, name, cap, rows, cols);
 }
 
 int eioku_timesformer_set_tensor(eioku_timesformer* m, int idx, const float* host, size_t numel) {
-  EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size() && host, "bad argument");
-  auto& t = m->tensors[idx];
-  EIOKU_REQUIRE(numel == t.numel(), "%s: expected %zu elements, got %zu", t.name.c_str(), t.numel(), numel);
-  EIOKU_HIP_CHECK(hipDeviceSynchronize());  // no pass may still read the old value
-  if (t.kind == T_F32) {
-    EIOKU_HIP_CHECK(hipMemcpy(t.dev.p, host, numel * sizeof(float), hipMemcpyHostToDevice));
-  } else {
-    DevBuf<float> stage;
-    EIOKU_TRY(stage.grow(numel));
-    EIOKU_HIP_CHECK(hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage.p, numel, (h16*)t.dev.p);
-    EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipDeviceSynchronize());
-  }
-  t.set = true;
+  EIOKU_TRY(TensorTable::set(m, idx, host, numel));
   m->tables_ready = false;
   return EIOKU_OK;
 }
@@ -637,7 +445,7 @@ int eioku_timesformer_forward(eioku_timesformer* m, const void* patches, int n_c
   EIOKU_REQUIRE(m && n_clips >= 0, "bad argument");
   if (n_clips == 0) return EIOKU_OK;
   EIOKU_REQUIRE(patches && logits_out, "NULL buffer");
-  EIOKU_TRY(check_weights(m));
+  EIOKU_TRY(m->check());
   hipStream_t st = (hipStream_t)stream_;
   EIOKU_TRY(ensure_batch(m, n_clips));
   m->flops = 0;
@@ -669,7 +477,7 @@ int eioku_timesformer_classify(eioku_timesformer* m, const uint8_t* bgr, int n_c
   EIOKU_REQUIRE(mem == EIOKU_MEM_HOST || mem == EIOKU_MEM_DEVICE, "bad mem flag %d", mem);
   if (n_clips == 0) return EIOKU_OK;
   EIOKU_REQUIRE(bgr && prob_out && class_out, "NULL buffer");
-  EIOKU_TRY(check_weights(m));
+  EIOKU_TRY(m->check());
   hipStream_t st = (hipStream_t)stream_;
   EIOKU_TRY(ensure_batch(m, n_clips));
   EIOKU_TRY(grow_synced(m->patches, (size_t)n_clips * m->P * m->frames * kPatchK));

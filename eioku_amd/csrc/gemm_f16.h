@@ -1,9 +1,11 @@
 // The fp16 GEMM of the transformer models (K20 Whisper, K25 TimeSformer, K26 CLIP, K27 nomic-embed-text): C = A . W^T on
-// v_mfma_f32_16x16x32_f16 with fused epilogues.  Included by whisper.hip, actions.hip, clip.hip and nomic.hip; everything here
-// has internal linkage.
+// v_mfma_f32_16x16x32_f16 with fused epilogues, and its one launcher.  The models' other shared parts sit next to it:
+// layernorm.h (the wave-per-row LayerNorm), attn_f16.h (the tiled MFMA attention and its sequence policies) and tensors.h (the
+// named-tensor table behind *_num_tensors / *_tensor_info / *_set_tensor).  Included by whisper.hip, actions.hip, clip.hip and
+// nomic.hip; everything here has internal linkage.
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "common.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -114,6 +116,21 @@ __global__ __launch_bounds__(256) void k_gemm(const h16* __restrict__ A, int lda
       if (EPI == EPI_QGELU_F16) reinterpret_cast<h16*>(out)[o] = (h16)quick_gelu(v);
     }
   }
+}
+
+// The launch of k_gemm<MT, EPI> with the alignment the kernel assumes checked; *flops grows by 2 M N K.  M == 0 launches nothing.
+template <int MT, int EPI>
+int launch_gemm(hipStream_t st, const h16* A, int lda, const h16* W, int ldw, const float* bias, int M, int N, int K, void* out,
+                long long ldc, const float* pos, int pos_rows, const int* row_pos, double* flops) {
+  EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0 && ldw % 8 == 0, "GEMM K %d / lda %d / ldw %d misaligned", K, lda, ldw);
+  if (EPI == EPI_ROPE_F16 || EPI == EPI_SWIGLU_F16)
+    EIOKU_REQUIRE(N % 16 == 0 && ldc % 4 == 0, "GEMM K %d / N %d / ldc %lld misaligned", K, N, ldc);
+  if (M == 0) return EIOKU_OK;
+  const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
+  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, st, A, lda, W, ldw, bias, M, N, K, out, ldc, pos, pos_rows, row_pos);
+  *flops += 2.0 * M * N * K;
+  EIOKU_LAUNCH_CHECK();
+  return EIOKU_OK;
 }
 
 }  // namespace

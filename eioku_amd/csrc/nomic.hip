@@ -5,12 +5,11 @@
 //                       cos | sin table and the row's position, v is stored as it is.  q_proj / k_proj rows are permuted when
 //                       they are set (stored row 2j of a head = dimension j, 2j + 1 = dimension j + 32), so both partners of a
 //                       rotation sit in one lane; q . k is the same under a permutation both carry, v and o_proj never see it
-//   k_attn_ragged       k_attn_seq<false> of clip.hip with the sequence's first row and length read from cu[]: 64 queries per
-//                       workgroup, keys / values through LDS 128 at a time, online softmax on v_mfma_f32_16x16x32_f16.  A sibling
-//                       and not a shared header, so that CLIP's kernel stays byte for byte what its tests pinned
+//   k_attn_tiles<RaggedSeq, false>  (attn_f16.h) the tiled MFMA attention with the sequence's first row and length read from
+//                       cu[]: 64 queries per workgroup, keys / values through LDS 128 at a time, online softmax
 //   k_gemm<., EPI_RESID>       o_proj and down_proj into the fp32 stream
 //   k_post_ln           post-LN: normalises the fp32 stream IN PLACE (the normalised value is the residual stream) and writes
-//                       the fp16 operand of the next GEMM
+//                       the fp16 operand of the next GEMM; like k_nomic_embed_ln over row_stats (layernorm.h)
 //   k_gemm<., EPI_SWIGLU_F16>  one packed [2 F][d] GEMM (stored row 2i = gate_proj row i, 2i + 1 = up_proj row i) that writes
 //                       silu(gate) * up as [T][F] fp16; the [T][2 F] intermediate never exists
 //   k_nomic_pool        one workgroup per sequence: the token mean in row order, the optional affine-free LayerNorm (eps 1e-5)
@@ -19,8 +18,11 @@
 // batch around it.  Precision points (tests/nomic_oracle.py, fp16=True): matrix weights fp16; the tables, LayerNorm parameters and
 // the residual stream fp32; q / k / v, the attention output, the SwiGLU output and the LayerNorm operands rounded once to fp16;
 // softmax numerators fp16; pooling and norms fp32.
+#include "attn_f16.h"
 #include "common.h"
 #include "gemm_f16.h"
+#include "layernorm.h"
+#include "tensors.h"
 
 #include <cmath>
 #include <string>
@@ -31,36 +33,6 @@ using namespace eioku;
 namespace {
 
 constexpr int kMaxPos = 8192, kMaxHidden = 8192;
-constexpr int kKC = 128;           // keys per LDS stage of k_attn_ragged
-constexpr int kKStride = 72;       // halfs per staged key row (64 + 8: 144 B, 16-byte aligned, spreads the banks)
-constexpr int kVStride = kKC + 2;  // halfs per staged value column (65 words: a column starts one bank after its neighbour)
-
-enum { ROWS_PLAIN = 0, ROWS_ROPE = 1, ROWS_EVEN = 2, ROWS_ODD = 3 };
-
-// where source row i of a weight lands in its packed device tensor
-__device__ __forceinline__ size_t stored_row(int i, int mode) {
-  if (mode == ROWS_ROPE) {
-    const int j = i & 63;
-    return (size_t)(i - j) + (j < 32 ? 2 * j : 2 * (j - 32) + 1);
-  }
-  if (mode == ROWS_EVEN) return (size_t)2 * i;
-  if (mode == ROWS_ODD) return (size_t)2 * i + 1;
-  return (size_t)i;
-}
-
-// src [rows][cols] fp32 -> rows stored_row(i) of dst [.][cols] fp16
-__global__ __launch_bounds__(256) void k_cvt_rows(const float* __restrict__ src, int rows, int cols, int mode, h16* __restrict__ dst) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows * cols) return;
-  const int c = (int)(i % cols);
-  dst[stored_row((int)(i / cols), mode) * cols + c] = (h16)src[i];
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // x[row][:] = LayerNorm(word[ids[row]][:] + type0[:]) in fp32, h[row][:] its fp16 rounding; one wave per row
 __global__ __launch_bounds__(256) void k_nomic_embed_ln(const int* __restrict__ ids, int T, int d, const float* __restrict__ word,
@@ -69,17 +41,9 @@ __global__ __launch_bounds__(256) void k_nomic_embed_ln(const int* __restrict__ 
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= T) return;
   const float* wr = word + (size_t)ids[row] * d;
-  float s = 0.f;
-  for (int i = lane; i < d; i += 64) s += wr[i] + type0[i];
-  const float mean = wave_sum(s) / (float)d;
-  float q = 0.f;
+  const RowStats st = row_stats(lane, d, eps, [&](int i) { return wr[i] + type0[i]; });
   for (int i = lane; i < d; i += 64) {
-    const float c = wr[i] + type0[i] - mean;
-    q += c * c;
-  }
-  const float inv = 1.f / sqrtf(wave_sum(q) / (float)d + eps);
-  for (int i = lane; i < d; i += 64) {
-    const float v = (wr[i] + type0[i] - mean) * inv * g[i] + b[i];
+    const float v = (wr[i] + type0[i] - st.mean) * st.inv * g[i] + b[i];
     x[(size_t)row * d + i] = v;
     h[(size_t)row * d + i] = (h16)v;
   }
@@ -91,120 +55,12 @@ __global__ __launch_bounds__(256) void k_post_ln(float* __restrict__ x, int T, i
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= T) return;
   float* xr = x + (size_t)row * d;
-  float s = 0.f;
-  for (int i = lane; i < d; i += 64) s += xr[i];
-  const float mean = wave_sum(s) / (float)d;
-  float q = 0.f;
+  const RowStats st = row_stats(lane, d, eps, [&](int i) { return xr[i]; });
   for (int i = lane; i < d; i += 64) {
-    const float c = xr[i] - mean;
-    q += c * c;
-  }
-  const float inv = 1.f / sqrtf(wave_sum(q) / (float)d + eps);
-  for (int i = lane; i < d; i += 64) {
-    const float v = (xr[i] - mean) * inv * g[i] + b[i];
+    const float v = (xr[i] - st.mean) * st.inv * g[i] + b[i];
     xr[i] = v;
     h[(size_t)row * d + i] = (h16)v;
   }
-}
-
-// ---- attention over packed sequences ----------------------------------------------------------------------------------------
-// qkv [T][3 d] fp16 (q | k | v, head h in columns 64 h .. 64 h + 63 of each third; q and k rotated, in the stored order),
-// sequence b = rows cu[b] .. cu[b + 1] - 1.  grid (ceil(longest / 64), heads, B), 4 waves of 16 queries; a workgroup whose first
-// query is at or past its sequence's length leaves before any barrier.  Otherwise k_attn_seq<false> (clip.hip): keys and values
-// through LDS kKC at a time up to the sequence's length, per 32 keys S^T = K Q^T in two MFMA tiles, the online softmax, then O^T
-// += V^T P^T with p = exp(s - max) rounded to fp16.  Keys at or past the length score -inf before the running maximum; groups
-// start at multiples of 32 below the length, so every visited group holds a live key.  A query tile starts at a multiple of 64
-// of its OWN sequence, so it never straddles two.  out [T][d] fp16.
-__global__ __launch_bounds__(256) void k_attn_ragged(const h16* __restrict__ qkv, const int* __restrict__ cu, int heads,
-                                                     h16* __restrict__ out) {
-  __shared__ __align__(16) h16 sk[kKC * kKStride];
-  __shared__ __align__(16) h16 svt[64 * kVStride];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, u = lane >> 4;
-  const int head = blockIdx.y;
-  const int d = heads * 64;
-  const size_t ld = (size_t)3 * d, row0 = (size_t)cu[blockIdx.z];
-  const int n = cu[blockIdx.z + 1] - cu[blockIdx.z];
-  if ((int)blockIdx.x * 64 >= n) return;
-  const int q = blockIdx.x * 64 + wave * 16 + r;  // this lane's query token
-  half8 q0 = {}, q1 = {};
-  if (q < n) {
-    const h16* qr = qkv + (row0 + q) * ld + head * 64 + 8 * u;
-    q0 = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(qr));
-    q1 = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(qr + 32));
-  }
-  float4v acc[4];
-#pragma unroll
-  for (int f = 0; f < 4; ++f) acc[f] = float4v{0.f, 0.f, 0.f, 0.f};
-  float mx = -INFINITY, sum = 0.f;  // sum: this lane's share, joined over u at the end
-  for (int k0 = 0; k0 < n; k0 += kKC) {
-    const int nk = n - k0 < kKC ? n - k0 : kKC, nk32 = (nk + 31) & ~31;
-    __syncthreads();  // the previous stage has been read
-    for (int i = threadIdx.x; i < nk32 * 8; i += 256) {
-      const int piece = i & 7, key = i >> 3;
-      uint4 kv = {0, 0, 0, 0}, vv = {0, 0, 0, 0};  // keys past the end: zeros (masked below; 0 * value adds nothing)
-      if (key < nk) {
-        const h16* row = qkv + (row0 + k0 + key) * ld + head * 64 + piece * 8;
-        kv = *reinterpret_cast<const uint4*>(row + d);
-        vv = *reinterpret_cast<const uint4*>(row + 2 * d);
-      }
-      *reinterpret_cast<uint4*>(sk + key * kKStride + piece * 8) = kv;
-      const half8 vh = __builtin_bit_cast(half8, vv);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) svt[(piece * 8 + e) * kVStride + key] = vh[e];
-    }
-    __syncthreads();
-    for (int j0 = 0; j0 < nk32; j0 += 32) {
-      float4v s[2];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const h16* kr = sk + (j0 + 16 * e + r) * kKStride + 8 * u;
-        const half8 ka = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(kr));
-        const half8 kb = __builtin_bit_cast(half8, *reinterpret_cast<const uint4*>(kr + 32));
-        s[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka, q0, float4v{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        s[e] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kb, q1, s[e], 0, 0, 0);
-      }
-      float m_new = mx;
-#pragma unroll
-      for (int e = 0; e < 2; ++e)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int key = j0 + 16 * e + 4 * u + i;
-          s[e][i] = key < nk ? s[e][i] * 0.125f : -INFINITY;
-          m_new = fmaxf(m_new, s[e][i]);
-        }
-      m_new = fmaxf(m_new, __shfl_xor(m_new, 16, 64));
-      m_new = fmaxf(m_new, __shfl_xor(m_new, 32, 64));  // finite: the group's first key is below the length
-      const float alpha = expf(mx - m_new);
-      mx = m_new;
-      half8 p;
-      float ps = 0.f;
-#pragma unroll
-      for (int e = 0; e < 2; ++e)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const h16 ph = (h16)expf(s[e][i] - m_new);
-          p[4 * e + i] = ph;
-          ps += (float)ph;
-        }
-      sum = sum * alpha + ps;
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        const h16* vr = svt + (16 * f + r) * kVStride + j0 + 4 * u;
-        const unsigned* va = reinterpret_cast<const unsigned*>(vr);  // 4-byte aligned: kVStride, j0 and 4u are even
-        const uint4 v4 = {va[0], va[1], va[8], va[9]};
-        acc[f] = acc[f] * alpha;
-        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, v4), p, acc[f], 0, 0, 0);
-      }
-    }
-  }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
-  if (q >= n) return;
-  h16* o = out + (row0 + q) * d + head * 64 + 4 * u;
-#pragma unroll
-  for (int f = 0; f < 4; ++f)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[16 * f + i] = (h16)(acc[f][i] / sum);
 }
 
 // ---- pooling ------------------------------------------------------------------------------------------------------------------
@@ -250,20 +106,6 @@ __global__ __launch_bounds__(256) void k_nomic_pool(const float* __restrict__ x,
 }
 
 // ---- the model ------------------------------------------------------------------------------------------------------------------
-enum { T_F16 = 0, T_F32 = 1 };
-
-// A named tensor of the state_dict().  Its device value is `dev`, or rows of tensor `into` starting at row0, placed by `mode`.
-struct Tensor {
-  std::string name;
-  int rows = 0, cols = 0, kind = T_F16;
-  int into = -1, row0 = 0, mode = ROWS_PLAIN;
-  bool listed = true;  // packed targets are not part of the state_dict()
-  DevBuf<uint8_t> dev;
-  bool set = false;
-  size_t numel() const { return (size_t)rows * cols; }
-};
-
-struct LNorm { int g, b; };
 struct Layer {
   LNorm ln_attn, ln_mlp;
   int qkv, o, gate_up, down;
@@ -271,11 +113,9 @@ struct Layer {
 
 }  // namespace
 
-struct eioku_nomic {
+struct eioku_nomic : TensorTable {
   int vocab = 0, d = 0, layers = 0, heads = 0, ffn = 0, max_pos = 0, type_vocab = 0;
   float eps = 1e-12f, theta = 1000.f;
-  std::vector<Tensor> tensors;
-  std::vector<int> listed;  // indices of the state_dict() tensors, in order
   int word = -1, type = -1;
   LNorm emb_ln{};
   std::vector<Layer> L;
@@ -288,13 +128,6 @@ struct eioku_nomic {
   hipEvent_t ev[2] = {nullptr, nullptr};
   bool timed = false;
   double flops = 0;
-
-  const uint8_t* base(int i) const {
-    const Tensor& t = tensors[i];
-    return t.into < 0 ? t.dev.p : tensors[t.into].dev.p + (size_t)t.row0 * t.cols * 2;  // only fp16 weights are packed
-  }
-  const h16* H(int i) const { return (const h16*)base(i); }
-  const float* F(int i) const { return (const float*)base(i); }
 };
 
 namespace {
@@ -304,13 +137,7 @@ typedef eioku_nomic Model;
 template <int EPI>
 int gemm(Model* m, hipStream_t st, const h16* A, int w, int M, int N, int K, void* out, long long ldc, const float* table = nullptr,
          int table_rows = 1, const int* row_pos = nullptr) {
-  EIOKU_REQUIRE(K % 32 == 0 && N % 16 == 0 && ldc % 4 == 0, "GEMM K %d / N %d / ldc %lld misaligned", K, N, ldc);
-  const dim3 grid((N + 63) / 64, (M + 63) / 64);
-  hipLaunchKernelGGL((k_gemm<4, EPI>), grid, dim3(256), 0, st, A, K, m->H(w), K, (const float*)nullptr, M, N, K, out, ldc, table,
-                     table_rows, row_pos);
-  m->flops += 2.0 * M * N * K;
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
+  return launch_gemm<4, EPI>(st, A, K, m->H(w), K, nullptr, M, N, K, out, ldc, table, table_rows, row_pos, &m->flops);
 }
 
 // ids / cu / pos on the device, T rows, B sequences, the longest `longest` rows -> m->x after every layer, m->unit [B][dim]
@@ -322,8 +149,7 @@ int run(Model* m, int T, int B, int longest, int dim, int layer_norm, hipStream_
   EIOKU_LAUNCH_CHECK();
   for (const Layer& L : m->L) {
     EIOKU_TRY((gemm<EPI_ROPE_F16>(m, st, m->h, L.qkv, T, 3 * d, d, m->qkv.p, 3 * d, m->rope.p, m->max_pos, m->pos.p)));
-    hipLaunchKernelGGL(k_attn_ragged, dim3((longest + 63) / 64, m->heads, B), dim3(256), 0, st, m->qkv.p, m->cu.p, m->heads, m->a.p);
-    EIOKU_LAUNCH_CHECK();
+    EIOKU_TRY(launch_attn<false>(st, m->qkv.p, RaggedSeq{m->cu.p, d, m->a.p}, longest, m->heads, B));
     EIOKU_TRY((gemm<EPI_RESID>(m, st, m->a, L.o, T, d, d, m->x.p, d)));
     hipLaunchKernelGGL(k_post_ln, rows, dim3(256), 0, st, m->x.p, T, d, m->F(L.ln_attn.g), m->F(L.ln_attn.b), m->eps, m->h.p);
     EIOKU_LAUNCH_CHECK();
@@ -356,58 +182,31 @@ int eioku_nomic_create(int vocab, int hidden, int layers, int heads, int ffn, in
   m->vocab = vocab, m->d = hidden, m->layers = layers, m->heads = heads, m->ffn = ffn, m->max_pos = max_pos, m->type_vocab = type_vocab;
   m->eps = ln_eps, m->theta = rope_theta;
   const int d = hidden;
-  auto add = [&](const std::string& n, int rows, int cols, int kind) {
-    Tensor t;
-    t.name = n, t.rows = rows, t.cols = cols, t.kind = kind;
-    m->tensors.push_back(std::move(t));
-    return (int)m->tensors.size() - 1;
-  };
-  auto packed = [&](const std::string& n, int rows, int cols) {
-    const int i = add(n, rows, cols, T_F16);
-    m->tensors[i].listed = false;
-    return i;
-  };
-  auto part = [&](const std::string& n, int rows, int cols, int into, int row0, int mode) {
-    const int i = add(n, rows, cols, T_F16);
-    m->tensors[i].into = into, m->tensors[i].row0 = row0, m->tensors[i].mode = mode;
-    return i;
-  };
-  auto lnorm = [&](const std::string& p) {
-    LNorm l;
-    l.g = add(p + ".weight", d, 1, T_F32);
-    l.b = add(p + ".bias", d, 1, T_F32);
-    return l;
-  };
   // the order of NomicBertModel.state_dict()
-  m->word = add("embeddings.word_embeddings.weight", vocab, d, T_F32);
-  m->type = add("embeddings.token_type_embeddings.weight", type_vocab, d, T_F32);
-  m->emb_ln = lnorm("embeddings.LayerNorm");
+  m->word = m->add("embeddings.word_embeddings.weight", vocab, d, T_F32);
+  m->type = m->add("embeddings.token_type_embeddings.weight", type_vocab, d, T_F32);
+  m->emb_ln = m->lnorm("embeddings.LayerNorm", d);
   for (int l = 0; l < layers; ++l) {
     const std::string p = "layers." + std::to_string(l) + ".";
     Layer L;
-    L.ln_attn = lnorm(p + "post_attention_layernorm");
-    L.gate_up = packed(p + "mlp.gate_up.weight", 2 * ffn, d);
-    part(p + "mlp.gate_proj.weight", ffn, d, L.gate_up, 0, ROWS_EVEN);
-    part(p + "mlp.up_proj.weight", ffn, d, L.gate_up, 0, ROWS_ODD);
-    L.down = add(p + "mlp.down_proj.weight", d, ffn, T_F16);
-    L.qkv = packed(p + "self_attn.qkv.weight", 3 * d, d);
-    part(p + "self_attn.q_proj.weight", d, d, L.qkv, 0, ROWS_ROPE);
-    part(p + "self_attn.k_proj.weight", d, d, L.qkv, d, ROWS_ROPE);
-    part(p + "self_attn.v_proj.weight", d, d, L.qkv, 2 * d, ROWS_PLAIN);
-    L.o = add(p + "self_attn.o_proj.weight", d, d, T_F16);
-    L.ln_mlp = lnorm(p + "post_mlp_layernorm");
+    L.ln_attn = m->lnorm(p + "post_attention_layernorm", d);
+    L.gate_up = m->packed(p + "mlp.gate_up.weight", 2 * ffn, d, T_F16);
+    m->part(p + "mlp.gate_proj.weight", ffn, d, L.gate_up, 0, ROWS_EVEN);
+    m->part(p + "mlp.up_proj.weight", ffn, d, L.gate_up, 0, ROWS_ODD);
+    L.down = m->add(p + "mlp.down_proj.weight", d, ffn, T_F16);
+    L.qkv = m->packed(p + "self_attn.qkv.weight", 3 * d, d, T_F16);
+    m->part(p + "self_attn.q_proj.weight", d, d, L.qkv, 0, ROWS_ROPE);
+    m->part(p + "self_attn.k_proj.weight", d, d, L.qkv, d, ROWS_ROPE);
+    m->part(p + "self_attn.v_proj.weight", d, d, L.qkv, 2 * d, ROWS_PLAIN);
+    L.o = m->add(p + "self_attn.o_proj.weight", d, d, T_F16);
+    L.ln_mlp = m->lnorm(p + "post_mlp_layernorm", d);
     m->L.push_back(L);
   }
   auto fail = [&](int rc) {
     eioku_nomic_destroy(m);
     return rc;
   };
-  for (size_t i = 0; i < m->tensors.size(); ++i) {
-    Tensor& t = m->tensors[i];
-    if (t.listed) m->listed.push_back((int)i);
-    if (t.into >= 0) continue;
-    if (t.dev.grow(t.numel() * (t.kind == T_F32 ? 4 : 2))) return fail(EIOKU_ENOMEM);
-  }
+  if (const int rc = m->finish()) return fail(rc);
   // the rotary table in fp32, as transformers computes it: inv_freq[j] = 1 / theta^(2j / 64), angle = pos * inv_freq[j]
   std::vector<float> table((size_t)max_pos * 64);
   for (int j = 0; j < 32; ++j) {
@@ -437,37 +236,13 @@ void eioku_nomic_destroy(eioku_nomic* m) {
   delete m;  // every buffer frees itself
 }
 
-int eioku_nomic_num_tensors(const eioku_nomic* m) { return m ? (int)m->listed.size() : 0; }
+int eioku_nomic_num_tensors(const eioku_nomic* m) { return TensorTable::count(m); }
 
 int eioku_nomic_tensor_info(const eioku_nomic* m, int idx, char* name, size_t cap, int* rows, int* cols) {
-  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->listed.size(), "bad tensor index %d", idx);
-  const auto& t = m->tensors[m->listed[idx]];
-  if (name && cap) snprintf(name, cap, "%s", t.name.c_str());
-  if (rows) *rows = t.rows;
-  if (cols) *cols = t.cols;
-  return EIOKU_OK;
+  return TensorTable::info(m, idx, name, cap, rows, cols);
 }
 
-int eioku_nomic_set_tensor(eioku_nomic* m, int idx, const float* host, size_t numel) {
-  EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->listed.size() && host, "bad argument");
-  auto& t = m->tensors[m->listed[idx]];
-  EIOKU_REQUIRE(numel == t.numel(), "%s: expected %zu elements, got %zu", t.name.c_str(), t.numel(), numel);
-  EIOKU_HIP_CHECK(hipDeviceSynchronize());  // no pass may still read the old value
-  void* dst = const_cast<uint8_t*>(m->base(m->listed[idx]));
-  if (t.kind == T_F32) {
-    EIOKU_HIP_CHECK(hipMemcpy(dst, host, numel * sizeof(float), hipMemcpyHostToDevice));
-  } else {
-    DevBuf<float> stage;
-    EIOKU_TRY(stage.grow(numel));
-    EIOKU_HIP_CHECK(hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_cvt_rows, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage.p, t.rows, t.cols, t.mode, (h16*)dst);
-    EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipDeviceSynchronize());
-  }
-  t.set = true;
-  return EIOKU_OK;
-}
+int eioku_nomic_set_tensor(eioku_nomic* m, int idx, const float* host, size_t numel) { return TensorTable::set(m, idx, host, numel); }
 
 // ids [T] and cu [B + 1] int32 on the side `mem` names (cu[0] = 0, T = cu[B]) -> out [B][dim] fp32 unit vectors and optionally
 // hidden_out [T][hidden] fp32 (the stream after the last layer) on that side.  dim = matryoshka_dim, or hidden when that is 0.
@@ -481,7 +256,7 @@ int eioku_nomic_encode(eioku_nomic* m, const int32_t* ids, const int32_t* cu, in
                 matryoshka_dim);
   if (B == 0) return EIOKU_OK;
   EIOKU_REQUIRE(ids && cu && out, "NULL buffer");
-  for (int i : m->listed) EIOKU_REQUIRE(m->tensors[i].set, "tensor %s has no weights", m->tensors[i].name.c_str());
+  EIOKU_TRY(m->check());
   hipStream_t st = (hipStream_t)stream_;
   const bool dev = mem == EIOKU_MEM_DEVICE;
   if (dev) EIOKU_HIP_CHECK(hipStreamSynchronize(st));  // whatever on the caller's stream still writes ids / cu

@@ -26,6 +26,8 @@
 // fp32; LayerNorm outputs, q / k / v, attention outputs, GELU outputs and the mel input are rounded to fp16.
 #include "common.h"
 #include "gemm_f16.h"
+#include "layernorm.h"
+#include "tensors.h"
 
 #include <hip/hip_fp16.h>
 
@@ -105,25 +107,6 @@ __global__ __launch_bounds__(256) void k_mel_finish(const double* __restrict__ v
   out[i] = (float)((fmax(v[i], floor_) + 4.0) / 4.0);
 }
 
-// ---- weight conversion -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_cvt_f16(const float* __restrict__ src, size_t n, h16* __restrict__ dst) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dst[i] = (h16)src[i];
-}
-
-// conv weight [rows][cin][3] fp32 -> [rows][ldk] fp16 with column tap * cin + c (columns past 3 cin stay 0)
-__global__ __launch_bounds__(256) void k_cvt_conv(const float* __restrict__ src, int rows, int cin, int ldk, h16* __restrict__ dst) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)rows * ldk) return;
-  const int n = (int)(i / ldk), col = (int)(i % ldk);
-  float v = 0.f;
-  if (col < 3 * cin) {
-    const int tap = col / cin, c = col % cin;
-    v = src[((size_t)n * cin + c) * 3 + tap];
-  }
-  dst[i] = (h16)v;
-}
-
 // ---- im2col for the two k3 p1 convolutions ------------------------------------------------------------------------------
 // mel [B][C][Tin] fp32 -> col [B * Tin][ldk] fp16, col[(b, t)][tap * C + c] = mel[b][c][t + tap - 1]
 __global__ __launch_bounds__(256) void k_im2col_mel(const float* __restrict__ mel, int B, int C, int Tin, int ldk, h16* __restrict__ col) {
@@ -150,28 +133,6 @@ __global__ __launch_bounds__(256) void k_im2col_s2(const h16* __restrict__ h, in
   const int t = (int)(row % Tout), b = (int)(row / Tout);
   const int tap = k / C, c = k % C, ts = 2 * t + tap - 1;
   col[i] = (ts >= 0 && ts < Tin) ? h[((size_t)b * Tin + ts) * C + c] : (h16)0.f;
-}
-
-// ---- LayerNorm: fp32 row -> fp16, one wave per row ------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_ln(const float* __restrict__ x, int M, int d, const float* __restrict__ g,
-                                            const float* __restrict__ b, h16* __restrict__ out) {
-  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const float* xr = x + (size_t)row * d;
-  float s = 0.f;
-  for (int i = lane; i < d; i += 64) s += xr[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  const float mean = s / (float)d;
-  float q = 0.f;
-  for (int i = lane; i < d; i += 64) {
-    const float c = xr[i] - mean;
-    q += c * c;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  const float inv = 1.f / sqrtf(q / (float)d + 1e-5f);
-  for (int i = lane; i < d; i += 64) out[(size_t)row * d + i] = (h16)((xr[i] - mean) * inv * g[i] + b[i]);
 }
 
 // decoder input: x[b] = embed[token][:] + pos[s][:].  token = toks ? toks[b * tstride] : uniform
@@ -1081,16 +1042,6 @@ __global__ __launch_bounds__(64) void k_align_prob(const float* __restrict__ par
 }
 
 // ---- the model ------------------------------------------------------------------------------------------------------------
-enum { T_F16 = 0, T_F32 = 1, T_CONV = 2 };
-
-struct Tensor {
-  std::string name;
-  int rows = 0, cols = 0, kind = T_F16, cin = 0, ldk = 0;
-  DevBuf<uint8_t> dev;
-  bool set = false;
-  size_t numel() const { return (size_t)rows * cols; }
-};
-
 struct Attn { int q, qb, k, v, vb, o, ob, ln_g, ln_b; };
 struct Layer { Attn self, cross; int fc1, fc1b, fc2, fc2b, ln_g, ln_b; };
 
@@ -1112,10 +1063,9 @@ struct Work {
 
 }  // namespace
 
-struct eioku_whisper {
+struct eioku_whisper : TensorTable {
   eioku_whisper_cfg_t cfg{};
   SelCfg sel{};
-  std::vector<Tensor> tensors;
   std::vector<Layer> enc, dec;
   int conv1 = 0, conv1b = 0, conv2 = 0, conv2b = 0, enc_pos = 0, enc_ln_g = 0, enc_ln_b = 0;
   int emb = 0, dec_pos = 0, dec_ln_g = 0, dec_ln_b = 0;
@@ -1165,9 +1115,6 @@ struct eioku_whisper {
   double align_ms[3] = {0, 0, 0};
   double flops = 0;
   int launches = 0, steps = 0;
-
-  const h16* H(int i) const { return (const h16*)tensors[i].dev.p; }
-  const float* F(int i) const { return i < 0 ? nullptr : (const float*)tensors[i].dev.p; }
 };
 
 namespace {
@@ -1184,15 +1131,13 @@ int launched(eioku_whisper* m) {
 template <int MT, int EPI>
 int gemm(eioku_whisper* m, const h16* A, int lda, const h16* W, int ldw, const float* bias, int M, int N, int K, void* out,
          long long ldc, const float* pos = nullptr, int pos_rows = 1) {
-  EIOKU_REQUIRE(K % 32 == 0 && lda % 8 == 0 && ldw % 8 == 0, "GEMM K %d / lda %d / ldw %d misaligned", K, lda, ldw);
-  const dim3 grid((N + 63) / 64, (M + 16 * MT - 1) / (16 * MT));
-  hipLaunchKernelGGL((k_gemm<MT, EPI>), grid, dim3(256), 0, 0, A, lda, W, ldw, bias, M, N, K, out, ldc, pos, pos_rows, nullptr);
-  m->flops += 2.0 * M * N * K;
-  return launched(m);
+  EIOKU_TRY((launch_gemm<MT, EPI>(0, A, lda, W, ldw, bias, M, N, K, out, ldc, pos, pos_rows, nullptr, &m->flops)));
+  m->launches += 1;
+  return EIOKU_OK;
 }
 
 int ln(eioku_whisper* m, const float* x, int M, int d, int g, int b, h16* out) {
-  hipLaunchKernelGGL(k_ln, dim3((M + 3) / 4), dim3(256), 0, 0, x, M, d, m->F(g), m->F(b), out);
+  hipLaunchKernelGGL(k_ln<h16>, dim3((M + 3) / 4), dim3(256), 0, 0, x, M, d, m->F(g), m->F(b), 1e-5f, (const int*)nullptr, out);
   return launched(m);
 }
 
@@ -1368,11 +1313,6 @@ int ensure_prefill(eioku_whisper* m, int rows) {
   for (DevBuf<h16>* b : {&m->pk, &m->pv}) EIOKU_TRY(b->grow(n * d));
   EIOKU_TRY(m->ppartial.grow(n * m->nblk * kNP));
   m->prows = rows;
-  return EIOKU_OK;
-}
-
-int check_weights(const eioku_whisper* m) {
-  for (const auto& t : m->tensors) EIOKU_REQUIRE(t.set, "tensor %s has no weights", t.name.c_str());
   return EIOKU_OK;
 }
 
@@ -1686,31 +1626,24 @@ int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper** out) {
   m->nblk = (c.vocab + 63) / 64;
   m->k1pad = round_up(3 * c.n_mels, 32);
   const int d = c.d_model;
-  auto add = [&](const std::string& n, int rows, int cols, int kind, int cin = 0) {
-    Tensor t;
-    t.name = n, t.rows = rows, t.cols = cols, t.kind = kind, t.cin = cin;
-    t.ldk = kind == T_CONV ? round_up(cols, 32) : cols;
-    m->tensors.push_back(std::move(t));
-    return (int)m->tensors.size() - 1;
-  };
   auto add_attn = [&](const std::string& p, const std::string& lnp) {
     Attn a;
-    a.q = add(p + "q_proj.weight", d, d, T_F16);
-    a.qb = add(p + "q_proj.bias", d, 1, T_F32);
-    a.k = add(p + "k_proj.weight", d, d, T_F16);
-    a.v = add(p + "v_proj.weight", d, d, T_F16);
-    a.vb = add(p + "v_proj.bias", d, 1, T_F32);
-    a.o = add(p + "out_proj.weight", d, d, T_F16);
-    a.ob = add(p + "out_proj.bias", d, 1, T_F32);
-    a.ln_g = add(lnp + ".weight", d, 1, T_F32);
-    a.ln_b = add(lnp + ".bias", d, 1, T_F32);
+    a.q = m->add(p + "q_proj.weight", d, d, T_F16);
+    a.qb = m->add(p + "q_proj.bias", d, 1, T_F32);
+    a.k = m->add(p + "k_proj.weight", d, d, T_F16);
+    a.v = m->add(p + "v_proj.weight", d, d, T_F16);
+    a.vb = m->add(p + "v_proj.bias", d, 1, T_F32);
+    a.o = m->add(p + "out_proj.weight", d, d, T_F16);
+    a.ob = m->add(p + "out_proj.bias", d, 1, T_F32);
+    a.ln_g = m->add(lnp + ".weight", d, 1, T_F32);
+    a.ln_b = m->add(lnp + ".bias", d, 1, T_F32);
     return a;
   };
-  m->conv1 = add("model.encoder.conv1.weight", d, c.n_mels * 3, T_CONV, c.n_mels);
-  m->conv1b = add("model.encoder.conv1.bias", d, 1, T_F32);
-  m->conv2 = add("model.encoder.conv2.weight", d, d * 3, T_CONV, d);
-  m->conv2b = add("model.encoder.conv2.bias", d, 1, T_F32);
-  m->enc_pos = add("model.encoder.embed_positions.weight", c.max_source_positions, d, T_F32);
+  m->conv1 = m->add("model.encoder.conv1.weight", d, c.n_mels * 3, T_CONV);
+  m->conv1b = m->add("model.encoder.conv1.bias", d, 1, T_F32);
+  m->conv2 = m->add("model.encoder.conv2.weight", d, d * 3, T_CONV);
+  m->conv2b = m->add("model.encoder.conv2.bias", d, 1, T_F32);
+  m->enc_pos = m->add("model.encoder.embed_positions.weight", c.max_source_positions, d, T_F32);
   for (int l = 0; l < c.enc_layers + c.dec_layers; ++l) {
     const bool is_dec = l >= c.enc_layers;
     const std::string p = std::string("model.") + (is_dec ? "decoder" : "encoder") + ".layers." +
@@ -1719,30 +1652,27 @@ int eioku_whisper_create(const eioku_whisper_cfg_t* cfg, eioku_whisper** out) {
     Layer L{};
     L.self = add_attn(p + "self_attn.", p + "self_attn_layer_norm");
     if (is_dec) L.cross = add_attn(p + "encoder_attn.", p + "encoder_attn_layer_norm");
-    L.fc1 = add(p + "fc1.weight", ffn, d, T_F16);
-    L.fc1b = add(p + "fc1.bias", ffn, 1, T_F32);
-    L.fc2 = add(p + "fc2.weight", d, ffn, T_F16);
-    L.fc2b = add(p + "fc2.bias", d, 1, T_F32);
-    L.ln_g = add(p + "final_layer_norm.weight", d, 1, T_F32);
-    L.ln_b = add(p + "final_layer_norm.bias", d, 1, T_F32);
+    L.fc1 = m->add(p + "fc1.weight", ffn, d, T_F16);
+    L.fc1b = m->add(p + "fc1.bias", ffn, 1, T_F32);
+    L.fc2 = m->add(p + "fc2.weight", d, ffn, T_F16);
+    L.fc2b = m->add(p + "fc2.bias", d, 1, T_F32);
+    L.ln_g = m->add(p + "final_layer_norm.weight", d, 1, T_F32);
+    L.ln_b = m->add(p + "final_layer_norm.bias", d, 1, T_F32);
     (is_dec ? m->dec : m->enc).push_back(L);
     if (l == c.enc_layers - 1) {
-      m->enc_ln_g = add("model.encoder.layer_norm.weight", d, 1, T_F32);
-      m->enc_ln_b = add("model.encoder.layer_norm.bias", d, 1, T_F32);
-      m->emb = add("model.decoder.embed_tokens.weight", c.vocab, d, T_F16);
-      m->dec_pos = add("model.decoder.embed_positions.weight", c.max_target_positions, d, T_F32);
+      m->enc_ln_g = m->add("model.encoder.layer_norm.weight", d, 1, T_F32);
+      m->enc_ln_b = m->add("model.encoder.layer_norm.bias", d, 1, T_F32);
+      m->emb = m->add("model.decoder.embed_tokens.weight", c.vocab, d, T_F16);
+      m->dec_pos = m->add("model.decoder.embed_positions.weight", c.max_target_positions, d, T_F32);
     }
   }
-  m->dec_ln_g = add("model.decoder.layer_norm.weight", d, 1, T_F32);
-  m->dec_ln_b = add("model.decoder.layer_norm.bias", d, 1, T_F32);
+  m->dec_ln_g = m->add("model.decoder.layer_norm.weight", d, 1, T_F32);
+  m->dec_ln_b = m->add("model.decoder.layer_norm.bias", d, 1, T_F32);
   auto fail = [&](int rc) {
     eioku_whisper_destroy(m);
     return rc;
   };
-  for (auto& t : m->tensors) {
-    const size_t bytes = (size_t)t.rows * t.ldk * (t.kind == T_F32 ? 4 : 2);
-    if (t.dev.grow(bytes)) return fail(EIOKU_ENOMEM);
-  }
+  if (const int rc = m->finish()) return fail(rc);
   // constants: periodic Hann window, DFT twiddles, mel filterbank, per-id flags
   std::vector<double> hann(kNfft), tc(kNfft), ts(kNfft);
   const double two_pi = 6.283185307179586476925286766559;
@@ -1785,40 +1715,13 @@ void eioku_whisper_destroy(eioku_whisper* m) {
   delete m;  // every buffer frees itself
 }
 
-int eioku_whisper_num_tensors(const eioku_whisper* m) { return m ? (int)m->tensors.size() : 0; }
+int eioku_whisper_num_tensors(const eioku_whisper* m) { return TensorTable::count(m); }
 
 int eioku_whisper_tensor_info(const eioku_whisper* m, int idx, char* name, size_t cap, int* rows, int* cols) {
-  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size(), "bad tensor index %d", idx);
-  const auto& t = m->tensors[idx];
-  if (name && cap) snprintf(name, cap, "%s", t.name.c_str());
-  if (rows) *rows = t.rows;
-  if (cols) *cols = t.cols;
-  return EIOKU_OK;
+  return TensorTable::info(m, idx, name, cap, rows, cols);
 }
 
-int eioku_whisper_set_tensor(eioku_whisper* m, int idx, const float* host, size_t numel) {
-  EIOKU_REQUIRE_INIT();
-  EIOKU_REQUIRE(m && idx >= 0 && idx < (int)m->tensors.size() && host, "bad argument");
-  auto& t = m->tensors[idx];
-  EIOKU_REQUIRE(numel == t.numel(), "%s: expected %zu elements, got %zu", t.name.c_str(), t.numel(), numel);
-  if (t.kind == T_F32) {
-    EIOKU_HIP_CHECK(hipMemcpy(t.dev.p, host, numel * sizeof(float), hipMemcpyHostToDevice));
-  } else {
-    DevBuf<float> stage;
-    EIOKU_TRY(stage.grow(numel));
-    EIOKU_HIP_CHECK(hipMemcpy(stage, host, numel * sizeof(float), hipMemcpyHostToDevice));
-    if (t.kind == T_F16) {
-      hipLaunchKernelGGL(k_cvt_f16, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, 0, stage, numel, (h16*)t.dev.p);
-    } else {
-      const size_t n = (size_t)t.rows * t.ldk;
-      hipLaunchKernelGGL(k_cvt_conv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, stage, t.rows, t.cin, t.ldk, (h16*)t.dev.p);
-    }
-    EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipDeviceSynchronize());
-  }
-  t.set = true;
-  return EIOKU_OK;
-}
+int eioku_whisper_set_tensor(eioku_whisper* m, int idx, const float* host, size_t numel) { return TensorTable::set(m, idx, host, numel); }
 
 int eioku_whisper_set_audio(eioku_whisper* m, const float* samples, long long n) {
   EIOKU_REQUIRE_INIT();
@@ -1854,7 +1757,7 @@ int eioku_whisper_logmel(eioku_whisper* m, const long long* offsets, int B, floa
 int eioku_whisper_encode(eioku_whisper* m, const float* mel, int B) {
   EIOKU_REQUIRE_INIT();
   EIOKU_REQUIRE(m && B > 0 && B <= 64, "bad argument (1 <= B <= 64)");
-  EIOKU_TRY(check_weights(m));
+  EIOKU_TRY(m->check());
   EIOKU_REQUIRE(mel || B <= m->cap, "no log-mel result for %d windows", B);
   EIOKU_TRY(ensure_capacity(m, B));
   const auto& c = m->cfg;
@@ -2309,7 +2212,7 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
     Fmax = n_frames[r] / 2 > Fmax ? n_frames[r] / 2 : Fmax;
     Mp += (size_t)(n_tok[r] - S - 2);
   }
-  EIOKU_TRY(check_weights(m));
+  EIOKU_TRY(m->check());
   std::vector<int> heads = m->align_heads;
   if (heads.empty())
     for (int l = c.dec_layers / 2; l < c.dec_layers; ++l)
