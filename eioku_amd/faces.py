@@ -1,5 +1,5 @@
 """Face clustering: ArcFace embeddings (insightface ``arcface_torch`` IResNet) and cosine DBSCAN on the HIP kernels of
-``csrc/faces.hip``.
+``csrc/faces.hip``; HDBSCAN, the clustering without an ``eps`` (``face_cluster_method="hdbscan"``), is ``hdbscan.py``.
 
 Fills the ``cluster_id`` that ``ModelManager.detect_faces`` returns (``cluster_faces`` config key).  Per face the device
 produces a 112 x 112 crop, normalises it as arcface_torch's inference does (``(v / 255 - 0.5) / 0.5``) and runs the IResNet
@@ -367,6 +367,14 @@ class FaceEmbedder:
         labels = dbscan_cosine(embeddings, eps, min_samples)
         return labels.cpu().numpy() if on_device(labels) else labels
 
+    def cluster_hdbscan(self, embeddings, min_cluster_size: int, min_samples: int, selection_epsilon: float = 0.0):
+        """HDBSCAN on cosine distance (``hdbscan.hdbscan_cosine``, K14h) -> ``(int32 labels, float64 probabilities)``,
+        numpy: no ``eps`` to choose, and a membership strength per face."""
+        from .hdbscan import hdbscan_cosine
+
+        return hdbscan_cosine(embeddings, min_cluster_size=min_cluster_size, min_samples=min_samples,
+                              cluster_selection_epsilon=selection_epsilon)
+
     def last_flops(self) -> float:
         return self._h.doubles("last_flops")[0]
 
@@ -374,14 +382,23 @@ class FaceEmbedder:
         self._h.close()
 
 
+CLUSTER_METHODS = ("dbscan", "hdbscan")
+
+
 class FaceClusterer:
     """Per-video collector shared by ``detect_faces`` and ``analyze_video``: embeddings of the faces that pass the face
-    path's confidence filter, batch by batch, then one DBSCAN at the end that fills each face's ``cluster_id``."""
+    path's confidence filter, batch by batch, then one clustering at the end that fills each face's ``cluster_id``:
+    DBSCAN (``method="dbscan"``: ``eps``, ``min_samples``) or HDBSCAN (``"hdbscan"``: ``min_cluster_size``, ``min_samples``
+    and, only if given, ``eps`` as its ``cluster_selection_epsilon``), which also fills ``cluster_probability``."""
 
-    def __init__(self, embedder, eps: float, min_samples: int):
+    def __init__(self, embedder, eps, min_samples: int, method: str = "dbscan", min_cluster_size: int = 5):
+        if method not in CLUSTER_METHODS:
+            raise ValueError(f"face_cluster_method must be one of {CLUSTER_METHODS}, got {method!r}")
         self.embedder = embedder
-        self.eps = float(eps)
+        self.method = method
+        self.eps = None if eps is None else float(eps)
         self.min_samples = int(min_samples)
+        self.min_cluster_size = int(min_cluster_size)
         self._dets: list[dict] = []
         self._emb: list[np.ndarray] = []
 
@@ -404,6 +421,13 @@ class FaceClusterer:
 
     def finish(self) -> None:
         if not self._dets:
+            return
+        if self.method == "hdbscan":
+            labels, prob = self.embedder.cluster_hdbscan(self.embeddings(), self.min_cluster_size, self.min_samples,
+                                                         0.0 if self.eps is None else self.eps)
+            for det, cid, p in zip(self._dets, cluster_ids(labels), prob):
+                det["cluster_id"] = cid
+                det["cluster_probability"] = float(p) if cid is not None else 0.0
             return
         labels = self.embedder.cluster(self.embeddings(), self.eps, self.min_samples)
         for det, cid in zip(self._dets, cluster_ids(labels)):

@@ -442,14 +442,18 @@ class ModelManager:
     # ---- face clustering (opt-in: config["cluster_faces"]) ---------------------------------------------
     CLUSTER_EPS = 0.5         # cosine distance (1 - similarity) of two unit ArcFace embeddings; INTEGRATION.md
     CLUSTER_MIN_SAMPLES = 3   # faces (the point itself included) that make a core point
+    CLUSTER_MIN_SIZE = 5      # face_cluster_method "hdbscan": the fewest faces that make a person
 
     def _face_clusterer(self, config: dict):
         """The per-video ``FaceClusterer`` of a face-detection config, or None without ``cluster_faces`` (then no
         embedder is loaded and every ``cluster_id`` stays None, as in the reference)."""
         if not config.get("cluster_faces", False):
             return None
-        from .faces import FaceClusterer
+        from .faces import CLUSTER_METHODS, FaceClusterer
 
+        method = config.get("face_cluster_method", "dbscan")
+        if method not in CLUSTER_METHODS:
+            raise ValueError(f"face_cluster_method must be one of {CLUSTER_METHODS}, got {method!r}")
         model_name = config.get("face_embedding_model", "arcface_r18.pth")
         if self._face_embedder_factory is not None:
             embedder = self._face_embedder_factory(self.cache_dir, model_name)
@@ -457,8 +461,11 @@ class ModelManager:
             from .faces import FaceEmbedder
 
             embedder = FaceEmbedder.from_cache(self.cache_dir, model_name, seed=self._seed)
-        return FaceClusterer(embedder, config.get("cluster_eps", self.CLUSTER_EPS),
-                             config.get("cluster_min_samples", self.CLUSTER_MIN_SAMPLES))
+        min_samples = config.get("cluster_min_samples", self.CLUSTER_MIN_SAMPLES)
+        if method == "hdbscan":  # no density threshold: cluster_eps, only if given, is its cluster_selection_epsilon
+            return FaceClusterer(embedder, config.get("cluster_eps"), min_samples, method,
+                                 config.get("cluster_min_size", self.CLUSTER_MIN_SIZE))
+        return FaceClusterer(embedder, config.get("cluster_eps", self.CLUSTER_EPS), min_samples)
 
     # ---- objects / faces: one skeleton, as in the reference --------------------------------------------
     def _detect_loop(self, task: str, video_path: str, config: dict) -> dict:
@@ -674,6 +681,8 @@ class ModelManager:
         ``config["cluster_faces"]`` every face that passes the confidence filter is embedded (ArcFace IResNet,
         ``face_embedding_model`` under ``<cache>/insightface/``) and the video's faces are clustered once by cosine DBSCAN
         (``cluster_eps``, ``cluster_min_samples``): ``cluster_id`` = ``face_cluster_001``, ... or None for noise.
+        ``face_cluster_method="hdbscan"`` clusters by HDBSCAN instead (``cluster_min_size``, ``cluster_min_samples``; no
+        ``eps``) and adds ``cluster_probability`` to every clustered face's record (0.0 for noise).
         A Pose checkpoint (the community ``yolov8n-face.pt``: five landmarks) adds ``"landmarks": [{"x", "y", "confidence"}]``
         to every face, and the embeddings then come from crops aligned on them unless ``face_alignment`` is False
         (INTEGRATION.md section 3)."""

@@ -543,6 +543,19 @@ int eioku_iresnet_last_flops(const eioku_iresnet_t* r, double* flops);
  * numbered by smallest core index, a border point takes the smallest label among its core neighbours, -1 = noise.
  * n <= 65536, d % 32 == 0, eps in [0, 2], min_samples >= 1; labels_out [n] int32 on the side `mem` names. */
 int eioku_dbscan_cosine(const float* emb, int n, int d, float eps, int min_samples, int32_t* labels_out, int mem, void* stream);
+/* K14h, the device half of HDBSCAN(metric="cosine") (csrc/hdbscan.hip; the tree code is eioku_amd/hdbscan.py): rows emb
+ * [n][d] fp32 are taken to float64 and normalised, d_ij = 1 - x_i . x_j in float64 (clipped to [0, 2], 0 on the diagonal),
+ * core_out[i] = the min_samples-th smallest d_ij of row i (i itself included), and the n - 1 edges are a minimum spanning
+ * tree of the weights max(core_i, core_j, d_ij) under the total order (w, min(i, j), max(i, j)), found by Boruvka rounds on
+ * the device, in no particular order.  n in [0, 65536] (n <= 1: no edges), d % 32 == 0, 1 <= min_samples <= min(n, 32).
+ * core_out [n] f64 and edge_u / edge_v int32 / edge_w f64 [n - 1] on the side `mem` names; rounds_out HOST: the rounds
+ * taken, at most ceil(log2 n) + 1 -- with components left after that many the call fails rather than going on.
+ * Synchronous; its own grow-only workspace. */
+int eioku_hdbscan_mst_cosine(const float* emb, int n, int d, int min_samples, double* core_out, int32_t* edge_u, int32_t* edge_v,
+                             double* edge_w, int32_t* rounds_out, int mem, void* stream);
+/* device milliseconds of the last eioku_hdbscan_mst_cosine call: ms_out[0] the core-distance pass, ms_out[1 + r] Boruvka
+ * round r; returns the number of stages (it may exceed cap; at most cap are written) */
+int eioku_hdbscan_last_stage_ms(double* ms_out, int cap);
 
 /* ---- OCR: EasyOCR's CRAFT detector and english_g2 CRNN recogniser (csrc/ocr.hip) -------------------------------------
  * Fills ModelManager.extract_ocr.  Convolutions are named as the state dicts' prefixes ("basenet.slice1.0", ...,
