@@ -177,7 +177,12 @@ __global__ __launch_bounds__(256) void k_chan_ops(const __half* in, long long pi
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float x = (float)v[j];
-      v[j] = (_Float16)(x > 0.f ? x : x * slope[c0 + j]);
+      float p = x * slope[c0 + j];
+      // The product stays an fp32 value of its own.  Left to itself the compiler selects v_fma_mixlo_f16 (x * slope + 0.0 rounded
+      // to fp16) for the multiply and the conversion together: the added +0 turns a -0 product into +0, and the sum is rounded
+      // once, not to fp32 and then to fp16 (tests/test_convnet_glue_gpu.py found both).
+      asm volatile("" : "+v"(p));
+      v[j] = (_Float16)(x > 0.f ? x : p);
     }
     if (out_act) *reinterpret_cast<uint4*>(out_act + (size_t)i * 8) = __builtin_bit_cast(uint4, v);
   }

@@ -131,6 +131,58 @@ def iresnet(state_dict: dict):
     return net.eval()
 
 
+def _bn_scale_shift(sd, name):
+    g, b, mu, var = (np.asarray(sd[f"{name}.{k}"], np.float64) for k in ("weight", "bias", "running_mean", "running_var"))
+    s = g / np.sqrt(var + BN_EPS)
+    return s, b - mu * s
+
+
+def forward_blocks(state_dict: dict, crops_f16: np.ndarray, upto: int, fp16: bool = False) -> np.ndarray:
+    """fp16 NHWC8 crops -> NHWC float64 output of block ``upto`` (0 = layer1.0, counting through the stages).
+
+    ``fp16=False``: the torch fp32 network.  ``fp16=True``: its twin in the device's arithmetic - every BatchNorm that follows
+    a conv folded into it (folded here, in float64, not by the package), weights rounded to fp16, fp32 accumulation, and one
+    rounding to fp16 wherever the device stores a tensor: each conv's output, the PReLU's, the leading bn1's
+    (``fp16(fp16(x) * scale + shift)``) and the shortcut sum ``fp16(fp16(conv2) + shortcut)``."""
+    import torch
+    import torch.nn.functional as F
+
+    x = torch.from_numpy(crops_f16[..., :3].astype(np.float32)).permute(0, 3, 1, 2)
+    depths = faces.depths_from_state(state_dict)
+    names = [f"layer{li}.{b}" for li, d in enumerate(depths, start=1) for b in range(d)]
+    with torch.no_grad():
+        if not fp16:
+            net = iresnet(state_dict)
+            x = net.stem(x)
+            for name in names[:upto + 1]:
+                li, b = name[5:].split(".")
+                x = getattr(net, f"layer{li}")[int(b)](x)
+            return x.permute(0, 2, 3, 1).numpy().astype(np.float64)
+
+        def h(t):
+            return t.half().float()
+
+        def conv(c, bn, t, stride):
+            s, sh = _bn_scale_shift(state_dict, bn)
+            w = np.asarray(state_dict[c + ".weight"], np.float64) * s[:, None, None, None]
+            w = h(torch.from_numpy(w.astype(np.float32)))
+            return h(F.conv2d(t, w, torch.from_numpy(sh.astype(np.float32)), stride=stride, padding=w.shape[-1] // 2))
+
+        def prelu(name, t):
+            return h(torch.where(t > 0, t, t * torch.from_numpy(np.asarray(state_dict[name + ".weight"], np.float32))[None, :, None, None]))
+
+        x = prelu("prelu", conv("conv1", "bn1", x, 1))
+        for name in names[:upto + 1]:
+            s, sh = (torch.from_numpy(v.astype(np.float32))[None, :, None, None] for v in _bn_scale_shift(state_dict, name + ".bn1"))
+            t = h(x * s + sh)
+            u = prelu(name + ".prelu", conv(name + ".conv1", name + ".bn2", t, 1))
+            down = name + ".downsample.0.weight" in state_dict
+            stride = 2 if down else 1
+            res = conv(name + ".downsample.0", name + ".downsample.1", x, stride) if down else x
+            x = h(conv(name + ".conv2", name + ".bn3", u, stride) + res)
+    return x.permute(0, 2, 3, 1).numpy().astype(np.float64)
+
+
 def embed_fp32(net, crops_f16: np.ndarray) -> np.ndarray:
     """fp16 NHWC8 crops -> unit fp32 embeddings of the torch network (``F.normalize`` of its output)."""
     import torch

@@ -160,11 +160,44 @@ def resnet(state_dict: dict):
     return net.eval()
 
 
-def forward_blocks(net, x_f16: np.ndarray, upto: int | None = None):
-    """fp16 NHWC8 input -> ``(NHWC float64 output of block `upto` (None: the last), largest |activation| on the way)``."""
+def _twin_blocks(net, x, upto):
+    """The network of ``net`` in the device's arithmetic: every BatchNorm folded into the conv before it (folded here, in
+    float64, from the modules' own parameters), weights rounded to fp16, fp32 accumulation, and one rounding to fp16 wherever
+    the device stores a tensor: relu(conv) of the stem and of conv1, the shortcut conv, and
+    ``fp16(relu(fp16(conv2) + shortcut))``."""
+    import torch
+    import torch.nn.functional as F
+
+    def h(t):
+        return t.half().float()
+
+    def conv(c, bn, t):
+        s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+        w = h((c.weight.double() * s[:, None, None, None]).float())
+        return h(F.conv2d(t, w, (bn.bias.double() - bn.running_mean.double() * s).float(), stride=c.stride, padding=c.padding))
+
+    x = h(F.relu(conv(net.conv1, net.bn1, x)))
+    peak = float(x.abs().max())
+    for i, blk in enumerate(net.blocks()):
+        mid = h(F.relu(conv(blk.conv1, blk.bn1, x)))
+        res = conv(blk.shortcut[0], blk.shortcut[1], x) if len(blk.shortcut) else x
+        x = h(F.relu(conv(blk.conv2, blk.bn2, mid) + res))
+        peak = max(peak, float(x.abs().max()))
+        if i == upto:
+            break
+    return x, peak
+
+
+def forward_blocks(net, x_f16: np.ndarray, upto: int | None = None, fp16: bool = False):
+    """fp16 NHWC8 input -> ``(NHWC float64 output of block `upto` (None: the last), largest |activation| on the way)``.
+    ``fp16=True``: the twin in the device's arithmetic (:func:`_twin_blocks`) instead of torch fp32."""
     import torch
 
     x = torch.from_numpy(x_f16[..., 0].astype(np.float32))[:, None]
+    if fp16:
+        with torch.no_grad():
+            x, peak = _twin_blocks(net, x, upto)
+        return x.permute(0, 2, 3, 1).numpy().astype(np.float64), peak
     with torch.no_grad():
         x = net.stem(x)
         peak = float(x.abs().max())

@@ -6,6 +6,7 @@ import json
 import numpy as np
 import pytest
 
+import block_stats
 import face_oracle as fo
 from conftest import GOLDEN
 from eioku_amd import _lib, faces
@@ -54,24 +55,25 @@ def _torch_net(sd):
     return fo.iresnet(sd)
 
 
-@pytest.mark.parametrize("upto", [0, 1])
+@pytest.mark.parametrize("upto", [0, 1, 2, 7])
 def test_ibasicblock_matches_torch_fp32(gpu, r18, upto):
-    """Stem + layer1.0 (downsample branch) and + layer1.1 (identity shortcut) on the device against torch-CPU fp32."""
+    """Stem + layer1.0 (downsample branch), + layer1.1 (identity shortcut), through layer2.0 (index depths[0]: the first block
+    that halves a map the stem did not produce) and through the last block, on the device against torch-CPU fp32.  Besides the
+    whole tensor: every channel against its own RMS and the border against the interior, each at most 2 x what the oracle's
+    fp16 twin shows at the same point (tests/block_stats.py)."""
     import torch
 
     sd, emb = r18
+    assert emb.depths[0] == 2 and sum(emb.depths) - 1 == 7
     frames = _frames(2, 3, 120, 160)
     crops = fo.crop_input(frames, BOXES[:6])
     got = emb.forward_raw(torch.from_numpy(crops).to(gpu), upto_block=upto).cpu().numpy().astype(np.float64)
-    net = _torch_net(sd)
-    with torch.no_grad():
-        x = net.stem(torch.from_numpy(crops[..., :3].astype(np.float32)).permute(0, 3, 1, 2))
-        for b in range(upto + 1):
-            x = net.layer1[b](x)
-    want = x.permute(0, 2, 3, 1).numpy().astype(np.float64)
+    want = fo.forward_blocks(sd, crops, upto)  # torch-CPU fp32: net.stem, then the blocks in order
     rms = float(np.sqrt((want ** 2).mean()))
     err = np.abs(got - want)
+    print(f"iresnet block {upto}: rms {rms:.3f} mean {err.mean() / rms:.2e} max {err.max() / rms:.2e}")
     assert rms > 0.1 and err.mean() <= FP32_MEAN * rms and err.max() <= FP32_MAX * rms, (err.mean() / rms, err.max() / rms)
+    block_stats.check(f"iresnet block {upto}", got, fo.forward_blocks(sd, crops, upto, fp16=True), want)
 
 
 def test_r18_embeddings_match_torch_fp32(gpu, r18):

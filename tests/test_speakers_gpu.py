@@ -6,6 +6,7 @@ import json
 import numpy as np
 import pytest
 
+import block_stats
 import face_oracle as fo
 import speaker_oracle as so
 from eioku_amd import faces, speakers
@@ -109,6 +110,9 @@ def test_blocks_match_torch_fp32(case, gpu, which):
     rms, mean, mx = _rel(got, want)
     print(f"{which} win={case['win']} depths={case['depths']}: rms {rms:.3f} mean {mean:.2e} max {mx:.2e}")
     assert rms > 0.1 and mean <= FP32_MEAN and mx <= FP32_MAX
+    # every channel against its own RMS and the border against the interior: at most 2 x the oracle's fp16 twin at this point
+    twin, _ = so.forward_blocks(case["net"], case["x16"], upto, fp16=True)
+    block_stats.check(f"speakers {which} win={case['win']} depths={case['depths']}", got, twin, want)
 
 
 # ---- 3. statistics and embeddings ----------------------------------------------------------------------------------------------
@@ -174,6 +178,21 @@ def test_bad_windows_are_refused(small, audio):
     for plan in ([(len(audio) - 400 - 160 * 39 + 1, 40)], [(-1, 40)], [(0, 41)], [(0, 0)], [(0, 8)]):
         with pytest.raises(EiokuHipError):
             small.embed_windows(audio, plan)
+    # Under 9 frames the pooling has one column and no standard deviation (tests/test_convnet_glue_host.py pins the NaN): both
+    # pooling paths refuse every such window and name it; the features alone still accept a single frame.
+    import torch
+
+    x16 = torch.zeros((3, 80, 40, 8), dtype=torch.float16, device="cuda")
+    for valid in range(1, 9):
+        with pytest.raises(EiokuHipError, match=rf"window 1: {valid} valid frames"):
+            small.embed_windows(audio, [(0, 40), (0, valid), (0, 9)])
+        with pytest.raises(EiokuHipError, match=rf"window 1: {valid} valid frames"):
+            small.forward_raw(x16, [40, valid, 9])
+        f16, f32 = small.features(audio, [(0, valid)])
+        assert np.isfinite(f32.cpu().numpy()).all() and not f32.cpu().numpy()[0, :, valid:].any()
+    assert small.forward_raw(x16, [40, 1, 9], upto_block=0).shape[0] == 3  # a block output pools nothing: any valid goes
+    emb = small.embed_windows(audio, [(0, 9)]).cpu().numpy()
+    assert emb.shape == (1, 256) and np.isfinite(emb).all()
 
 
 # ---- 5. segments -------------------------------------------------------------------------------------------------------------
