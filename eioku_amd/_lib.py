@@ -334,6 +334,15 @@ SIGNATURES = {
                                      C.c_void_p]),
     "eioku_nomic_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "eioku_nomic_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_mjpeg_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "eioku_mjpeg_destroy": (None, [C.c_void_p]),
+    "eioku_mjpeg_set_subseq_bits": (C.c_int, [C.c_void_p, C.c_int]),
+    "eioku_mjpeg_set_batch_frames": (C.c_int, [C.c_void_p, C.c_int]),
+    "eioku_mjpeg_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] +
+                           [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_mjpeg_coefficients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] +
+                                 [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_mjpeg_last": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 

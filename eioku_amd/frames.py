@@ -3,9 +3,13 @@
 The reference reads frames with ``cv2.VideoCapture(video_path)`` - ``get(CAP_PROP_FPS)``,
 ``get(CAP_PROP_FRAME_COUNT)``, ``read()``, ``grab()``, ``release()``
 (``/root/reference/ml-service/src/services/model_manager.py:237-299``) - and scene detection shells
-out to ffmpeg.  Video *decode* is outside this round's scope, so this module
-only provides the same small surface over what is available:
+out to ffmpeg.  Of the compressed formats, one is decoded here, on the device: Motion-JPEG (SURVEY.md §8f rank 1;
+inter-frame codecs stay out of scope).  This module provides the same small surface over what is available:
 
+  * Motion-JPEG in AVI (``.avi``, OpenDML included), raw ``.mjpeg`` / ``.mjpg`` streams and ``.jpg`` / ``.jpeg`` stills:
+    ``mjpeg.MjpegSource``, tried before ``cv2``.  Baseline JPEG frames are decoded by K28 (``csrc/mjpeg.hip``) to the
+    pixels libjpeg-turbo produces; ``grab()`` skips a frame without reading it.  An ``.avi`` with another codec falls
+    through to ``cv2``;
   * ``cv2`` itself when the deployment image has it (the reference's container does): BGR frames for the
     detectors and the decoder's luma plane for the scene stage (``Cv2FrameSource.luma_planes``);
   * ``.npy`` raw clips ``(n,h,w,3)`` uint8 BGR, memory mapped, with an optional ``<file>.json``
@@ -295,6 +299,12 @@ def open_video(path: str) -> FrameSource:
         return NpyFrameSource(p)
     if p.endswith(".y4m"):
         return Y4mSource(p)
+    if p.lower().endswith((".avi", ".mjpeg", ".mjpg", ".jpg", ".jpeg")):
+        from .mjpeg import open_mjpeg
+
+        src = open_mjpeg(p)  # None: an .avi whose video stream is another codec goes on to cv2 as before
+        if src is not None:
+            return src
     try:
         return Cv2FrameSource(p)
     except ImportError as e:

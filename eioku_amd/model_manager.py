@@ -59,27 +59,33 @@ def _timestamp_ms(frame_idx: int, fps) -> int:
     return int((frame_idx / fps) * 1000)
 
 
-def _sampled_batches(cap, fps, interval: int, batch_size: int):
+def _sampled_batches(cap, fps, interval: int, batch_size: int, device_decode: bool = False):
     """The reference's frame loop, batched: ``read()`` the sampled frames, ``grab()`` the others, stop at the first
     failure.  Yields ``(meta, frames)`` with ``meta`` the ``(frame_index, timestamp_ms)`` of each frame, a full batch
-    before the next frame is read, then the rest."""
+    before the next frame is read, then the rest.
+
+    ``device_decode``: on a source that hands out its frames undecoded (``read_encoded`` / ``decode``: Motion-JPEG) the
+    sampled frames are gathered as file bytes and ``frames`` is ONE device tensor ``(n, h, w, 3)`` from one decode call per
+    batch; no pixel crosses PCIe.  Every other source yields the list of host frames as before."""
+    encoded = device_decode and hasattr(cap, "read_encoded")
+    read = cap.read_encoded if encoded else cap.read
     meta, frames = [], []
     frame_idx = 0
     while True:
         if frame_idx % interval == 0:
-            ret, frame = cap.read()
+            ret, frame = read()
             if not ret:
                 break
             frames.append(frame)
             meta.append((frame_idx, _timestamp_ms(frame_idx, fps)))
             if len(frames) >= batch_size:
-                yield meta, frames
+                yield meta, (cap.decode(frames) if encoded else frames)
                 meta, frames = [], []
         elif not cap.grab():
             break
         frame_idx += 1
     if frames:
-        yield meta, frames
+        yield meta, (cap.decode(frames) if encoded else frames)
 
 
 def _stack_rows(rows):
@@ -491,8 +497,8 @@ class ModelManager:
                     if isinstance(detector, Yolov8Detector) else None)
             lane = _DetectionLane(detector, face, confidence_threshold, pipe, cluster, config.get("face_alignment", "auto"))
             try:
-                for meta, frames in _sampled_batches(cap, fps, frame_interval, self._batch_size):
-                    lane.submit(meta, np.stack(frames))
+                for meta, frames in _sampled_batches(cap, fps, frame_interval, self._batch_size, device_decode=True):
+                    lane.submit(meta, np.stack(frames) if isinstance(frames, list) else frames)
                 detections = lane.finish()
             finally:
                 cap.release()
@@ -750,8 +756,10 @@ class ModelManager:
             done = False
             while not done:
                 host = []
+                encoded = yuv is None and hasattr(src, "read_encoded")  # Motion-JPEG: file bytes in, decoded on the device
+                read = src.read_yuv if yuv else (src.read_encoded if encoded else src.read)
                 while len(host) < chunk_n:
-                    ret, frame = src.read_yuv() if yuv else src.read()
+                    ret, frame = read()
                     if not ret:
                         done = True
                         break
@@ -759,25 +767,30 @@ class ModelManager:
                 if not host:
                     break
                 n = len(host)
+                if encoded:
+                    host = src.decode(host)  # one decode call per chunk; the chunk is born in HBM
                 h, w = host[0].shape[:2]
                 fshape = (h, w) if yuv else (h, w, 3)
                 if yuv:
                     h = h * 2 // 3
                 npx = h * w
-                if pinned[slot] is None or tuple(pinned[slot].shape[1:]) != fshape:
-                    pinned = [torch.empty((chunk_n, *fshape), dtype=torch.uint8).pin_memory() for _ in range(2)]
-                    copied = [None, None]
-                if copied[slot] is not None:
-                    copied[slot].synchronize()  # the upload that last used this pinned buffer has finished
-                buf = pinned[slot][:n]
-                view = buf.numpy()  # the pinned buffer as an ndarray: frames are copied in without wrapping (possibly
-                for i, f in enumerate(host):  # read-only, memory-mapped) source arrays as tensors
-                    view[i] = f
-                chunk = buf.to(dev, non_blocking=True)  # the one trip over PCIe
-                ev = torch.cuda.Event()
-                ev.record()
-                copied[slot] = ev
-                slot ^= 1
+                if encoded:
+                    chunk = host
+                else:
+                    if pinned[slot] is None or tuple(pinned[slot].shape[1:]) != fshape:
+                        pinned = [torch.empty((chunk_n, *fshape), dtype=torch.uint8).pin_memory() for _ in range(2)]
+                        copied = [None, None]
+                    if copied[slot] is not None:
+                        copied[slot].synchronize()  # the upload that last used this pinned buffer has finished
+                    buf = pinned[slot][:n]
+                    view = buf.numpy()  # the pinned buffer as an ndarray: frames are copied in without wrapping (possibly
+                    for i, f in enumerate(host):  # read-only, memory-mapped) source arrays as tensors
+                        view[i] = f
+                    chunk = buf.to(dev, non_blocking=True)  # the one trip over PCIe
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    copied[slot] = ev
+                    slot ^= 1
                 planes = None
                 if yuv:
                     planes = chunk
@@ -858,7 +871,10 @@ class ModelManager:
                 while lo < n:
                     want = min(chunk, n - lo)
                     try:
-                        y = np.ascontiguousarray(src.luma_planes(lo, want))
+                        if hasattr(src, "luma_planes_device"):  # Motion-JPEG: the Y planes are decoded into HBM and stay there
+                            y = src.luma_planes_device(lo, want)
+                        else:
+                            y = np.ascontiguousarray(src.luma_planes(lo, want))
                     except EndOfStream:
                         break  # the header's frame count was an estimate: the stream ended early
                     sad.append(scene.luma_sad(y, prev))
@@ -964,6 +980,9 @@ class ModelManager:
         frames = getattr(src, "frames", None)
         if frames is not None:
             return np.ascontiguousarray(frames[lo:lo + count])
+        if hasattr(src, "read_encoded"):  # Motion-JPEG: one decode call per chunk, a device tensor
+            out = [src.read_encoded()[1] for _ in range(count)]
+            return src.decode([f for f in out if f is not None])
         out = []
         for _ in range(count):
             ok, f = src.read()

@@ -533,7 +533,20 @@ class VisualSearchEngine:
         return self._results(self.clip.encode_text([query])[0], filters, top_k)
 
     def search_by_image(self, frame_bgr, filters: dict | None = None, top_k: int = 10) -> list[dict]:
-        vec = self.clip.encode_images(frame_bgr[None] if len(frame_bgr.shape) == 3 else frame_bgr)
+        """``frame_bgr``: a BGR frame (host array or device tensor), or a baseline JPEG as ``bytes`` or as a ``str`` / ``Path``
+        naming the file; the JPEG is decoded on the device (K28, ``eioku_amd.mjpeg``)."""
+        if isinstance(frame_bgr, (str, bytes, bytearray)) or hasattr(frame_bgr, "__fspath__"):
+            from pathlib import Path
+
+            from .mjpeg import MjpegDecoder
+
+            data = bytes(frame_bgr) if isinstance(frame_bgr, (bytes, bytearray)) else Path(frame_bgr).read_bytes()
+            decoder = MjpegDecoder()
+            try:
+                frame_bgr = decoder.decode([data], "bgr")
+            finally:
+                decoder.close()
+        vec =self.clip.encode_images(frame_bgr[None] if len(frame_bgr.shape) == 3 else frame_bgr)
         vec = vec.cpu().numpy() if on_device(vec) else vec
         return self._results(vec[0], filters, top_k)
 

@@ -977,6 +977,41 @@ int eioku_nomic_encode(eioku_nomic_t* m, const int32_t* ids, const int32_t* cu, 
 int eioku_nomic_last_flops(const eioku_nomic_t* m, double* flops);
 int eioku_nomic_last_ms(const eioku_nomic_t* m, double* ms);
 
+/* ---- Motion-JPEG: baseline JPEG decode (csrc/mjpeg.hip, K28) -----------------------------------------------------------
+ * n frames of one geometry from their entropy-coded bytes to pixels in device memory, bit for bit libjpeg's default
+ * decode ("islow" IDCT, fancy upsampling, 16-bit colour tables).  The host (eioku_amd/mjpeg.py) parses the markers.
+ *   entropy (HOST, entropy_bytes % 4 == 0): the restart segments of all frames, unstuffed (FF 00 -> FF), each starting
+ *     on a 4-byte boundary.  seg (HOST) [nseg][5] = {frame, first MCU, MCU count, byte offset, bit length}: frames in
+ *     order, and the segments of a frame own its MCUs in order and without gaps.
+ *   qtab (HOST) [n][4][64] divisors 1..255 in natural order; huff (HOST) [n][4][16 + 256]: the tables DC 0, DC 1, AC 0,
+ *     AC 1 as DHT carries them (16 counts, then the symbols; unused tables all zero); comp (HOST) [n][3][3] = per
+ *     component {quantisation table, DC table, AC table}.  Tables may differ from frame to frame.
+ *   h, w in [1, 8192]; ncomp 1, or 3 with luma sampling hs x vs of 1x1, 2x1 or 2x2 and 1x1 chroma; n <= 4096.
+ *   decode: -> out (DEVICE) [n][h][w][3] u8 for EIOKU_MJPEG_BGR / _RGB, [n][h][w] for _LUMA (the decoded Y plane; chroma
+ *     is not touched).  status (HOST) [n]: non-zero where a segment of the frame closed fewer blocks than it owns.
+ *   coefficients: -> coef (HOST) [n][blocks][64] int16 in natural order, DC already predicted; blocks in scan order
+ *     (MCU by MCU, luma blocks row by row, then Cb, Cr).
+ *   set_subseq_bits: the size of the subsequences one thread decodes, a multiple of 32 in [32, 4096].
+ *   set_batch_frames: frames per internal sub-batch (0: as many as a 96 MiB coefficient buffer holds).  The results do
+ *     not depend on either setting.
+ *   last: device milliseconds of the last call's upload, synchronisation rounds, coefficient write (scan, write, DC),
+ *     IDCT and colour stage, and the number of synchronisation rounds that decoded something (the largest over the
+ *     sub-batches).
+ * Anything outside the limits is EIOKU_EINVAL before the device is touched; the handle stays usable.  Synchronous. */
+typedef struct eioku_mjpeg eioku_mjpeg_t;
+enum { EIOKU_MJPEG_BGR = 0, EIOKU_MJPEG_RGB = 1, EIOKU_MJPEG_LUMA = 2 };
+int eioku_mjpeg_create(eioku_mjpeg_t** out);
+void eioku_mjpeg_destroy(eioku_mjpeg_t* m);
+int eioku_mjpeg_set_subseq_bits(eioku_mjpeg_t* m, int bits);
+int eioku_mjpeg_set_batch_frames(eioku_mjpeg_t* m, int frames);
+int eioku_mjpeg_decode(eioku_mjpeg_t* m, const uint8_t* entropy, size_t entropy_bytes, const uint32_t* seg, int nseg,
+                       const uint16_t* qtab, const uint8_t* huff, const uint8_t* comp, int n, int h, int w, int ncomp, int hs, int vs,
+                       int fmt, uint8_t* out, int32_t* status, void* stream);
+int eioku_mjpeg_coefficients(eioku_mjpeg_t* m, const uint8_t* entropy, size_t entropy_bytes, const uint32_t* seg, int nseg,
+                             const uint16_t* qtab, const uint8_t* huff, const uint8_t* comp, int n, int h, int w, int ncomp, int hs,
+                             int vs, int16_t* coef, int32_t* status, void* stream);
+int eioku_mjpeg_last(eioku_mjpeg_t* m, double* ms5, int* rounds);
+
 #ifdef __cplusplus
 }
 #endif
