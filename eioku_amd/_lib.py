@@ -343,6 +343,19 @@ SIGNATURES = {
     "eioku_mjpeg_coefficients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] +
                                  [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "eioku_mjpeg_last": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "eioku_ast_create": (C.c_int, [C.c_int] * 9 + [C.c_float, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
+    "eioku_ast_destroy": (None, [C.c_void_p]),
+    "eioku_ast_num_tensors": (C.c_int, [C.c_void_p]),
+    "eioku_ast_tensor_info": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "eioku_ast_set_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "eioku_ast_set_audio": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
+    "eioku_ast_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_ast_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_ast_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eioku_ast_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p]),
+    "eioku_ast_last_flops": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "eioku_ast_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 

@@ -1,6 +1,6 @@
 // The tiled MFMA attention of the transformer models with 64-wide heads (K25 TimeSformer's spatial attention, K26 CLIP, K27
 // nomic-embed-text): one kernel, and per model a policy that says which rows of qkv form a sequence and where its outputs go.
-// Included by actions.hip, clip.hip and nomic.hip; everything here has internal linkage.
+// Included by actions.hip, clip.hip, nomic.hip and sounds.hip; everything here has internal linkage.
 #pragma once
 
 #include "common.h"

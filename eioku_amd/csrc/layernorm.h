@@ -1,5 +1,5 @@
 // The wave-per-row LayerNorm of the transformer models (K20 Whisper, K25 TimeSformer, K26 CLIP, K27 nomic-embed-text).
-// Included by whisper.hip, actions.hip, clip.hip and nomic.hip; everything here has internal linkage.
+// Included by whisper.hip, actions.hip, clip.hip, nomic.hip and sounds.hip; everything here has internal linkage.
 #pragma once
 
 #include "gemm_f16.h"

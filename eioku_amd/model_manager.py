@@ -18,6 +18,8 @@ ffmpeg / OpenCV / Ultralytics on the CPU.
                                            labels[top_k], scores[top_k]}]}             (design only)
     embed_frames(video_path, config)   -> {"embeddings": [{frame_index, timestamp_ms,
                                            embedding[projection_dim]}]}                (design only)
+    detect_sounds(video_path, config)  -> {"sounds": [{start_ms, end_ms, timestamp_ms, labels[<= top_k],
+                                           scores[<= top_k]}]}                         (not in the reference)
 
 What changes underneath (and nothing else): sampled frames are detected in batches instead of one
 ``model(frame)`` call each, and the scene score is computed by K1/K2 instead of an ffmpeg child
@@ -202,7 +204,8 @@ class ModelManager:
                  random_init_seed: int | None = None, place_classifier_factory=None, face_embedder_factory=None,
                  ocr_reader_factory=None, gpu_transcription: bool = False, audio_source=None, transcriber_factory=None,
                  gpu_vad: bool = False, vad_factory=None, gpu_audio: bool = False, audio_frontend_factory=None,
-                 gpu_speakers: bool = False, speaker_factory=None, action_recognizer_factory=None, clip_factory=None):
+                 gpu_speakers: bool = False, speaker_factory=None, action_recognizer_factory=None, clip_factory=None,
+                 sound_tagger_factory=None):
         """``cache_dir`` as in the reference (:12-21).  Keyword-only extras are seams for tests and bench:
         ``frame_source(path) -> FrameSource``, ``detector_factory(model_name, cache_dir) -> detector`` with
         ``detect(frames, conf=...) -> (dets, counts)`` and ``names``; ``random_init_seed`` builds random
@@ -222,7 +225,9 @@ class ModelManager:
         task's ``speaker_labels`` is true; ``speaker_factory(cache_dir, model_name) -> object with label(samples, segments,
         eps=, min_samples=, assign_max=)`` is its seam (``speaker_model`` in the task's config names the checkpoint).
         ``clip_factory(cache_dir, model_name) -> object with encode_images(frames)`` and optionally ``upload(frames)`` and
-        ``close()`` is the seam of ``embed_frames``."""
+        ``close()`` is the seam of ``embed_frames``; ``sound_tagger_factory(cache_dir, model_name) -> object with
+        classify(samples, plan, top_k, batch_windows=)``, ``labels``, ``max_length`` and ``window_samples`` that of
+        ``detect_sounds``."""
         self.cache_dir = Path(cache_dir)
         self.cache_dir.mkdir(parents=True, exist_ok=True)
         self.models = {}
@@ -244,6 +249,7 @@ class ModelManager:
         # (cache_dir, model_name) -> object with classify(clips, top_k), labels, frames and optionally upload(frames)
         self._action_recognizer_factory = action_recognizer_factory
         self._clip_factory = clip_factory
+        self._sound_tagger_factory = sound_tagger_factory
         self._batch_size = int(batch_size)
         self._lane_streams = {}  # task -> the two HIP streams its detector lanes run on (created once per manager)
         self._seed = random_init_seed
@@ -631,6 +637,72 @@ class ModelManager:
             return {"actions": actions}
         except Exception as e:
             logger.error(f"Action detection failed: {e}", exc_info=True)
+            raise
+
+    # ---- sounds: the Audio Spectrogram Transformer on windows of the audio track (eioku_amd.sounds) ----
+    def _load_sound_tagger(self, model_name: str):
+        """``<cache>/ast/<model_name>/`` (``eioku_amd.sounds``), per job like the other stages."""
+        if self._sound_tagger_factory is not None:
+            return self._sound_tagger_factory(self.cache_dir, model_name)
+        from .sounds import SoundTagger
+
+        return SoundTagger.from_cache(self.cache_dir, model_name, seed=self._seed)
+
+    async def detect_sounds(self, video_path: str, config: dict) -> dict:
+        """Tag non-speech sounds (music, applause, barking, ...) on the HIP path: windows of the checkpoint's length (10.24 s)
+        every ``window_stride`` seconds (default 10.0) over the 16 kHz audio, which is found as ``transcribe_video`` finds it
+        (the manager's ``audio_source``, else the path or its sibling ``.wav``; with ``gpu_audio=True`` any PCM WAV, resampled
+        on the device; otherwise another rate raises ``ValueError``).  -> ``{"sounds": [{start_ms, end_ms, timestamp_ms,
+        labels, scores}]}``, one item per window: the ``top_k`` (default 5) labels in descending score, the sigmoid scores,
+        entries below ``min_score`` dropped.  A file shorter than one frame (400 samples) has no windows."""
+        from .sounds import SAMPLE_RATE, plan_windows, sound_settings
+        from .transcribe import check_rate, default_audio_source
+
+        try:
+            config = config or {}
+            logger.info(f"Sound detection: {video_path} (device: {self._get_device()})")
+            tagger = self._load_sound_tagger(sound_settings(config)["model_name"])
+            frontend = None
+            sounds: list[dict] = []
+            try:
+                names = tagger.labels
+                settings = sound_settings(config, len(names))
+                if self._gpu_audio:
+                    if self._audio_frontend_factory is not None:
+                        frontend = self._audio_frontend_factory()
+                    else:
+                        from .audio import AudioFrontEnd
+
+                        frontend = AudioFrontEnd()
+                if frontend is not None and self._audio_source is None:
+                    samples, rate = frontend.load(video_path)
+                else:
+                    samples, rate = (self._audio_source or default_audio_source)(video_path)
+                    if frontend is not None and int(rate) != SAMPLE_RATE:
+                        samples, rate = frontend.resample_float(samples, rate), SAMPLE_RATE
+                check_rate(rate)
+                samples = np.asarray(samples, dtype=np.float32).reshape(-1)
+                n = int(samples.shape[0])
+                span = int(tagger.window_samples)
+                stride = max(1, int(round(settings["window_stride"] * SAMPLE_RATE)))
+                plan = plan_windows(n, int(tagger.max_length), stride)
+                if plan:
+                    scores, ids = tagger.classify(samples, plan, settings["top_k"], batch_windows=settings["batch_windows"])[:2]
+                    for (first, _), sc, idx in zip(plan, scores, ids):
+                        start_ms = first * 1000 // SAMPLE_RATE
+                        keep = [(names[int(c)], float(np.float32(v))) for c, v in zip(idx, sc) if float(v) >= settings["min_score"]]
+                        sounds.append({"start_ms": start_ms, "end_ms": min(n, first + span) * 1000 // SAMPLE_RATE,
+                                       "timestamp_ms": start_ms, "labels": [str(k) for k, _ in keep],
+                                       "scores": [v for _, v in keep]})
+            finally:
+                for model in (frontend, tagger):
+                    close = getattr(model, "close", None)
+                    if close:
+                        close()
+            logger.info(f"✅ Sound detection complete: {len(sounds)} windows")
+            return {"sounds": sounds}
+        except Exception as e:
+            logger.error(f"Sound detection failed: {e}", exc_info=True)
             raise
 
     # ---- frame embeddings: CLIP's image tower on the sampled frames (eioku_amd.visual) ----

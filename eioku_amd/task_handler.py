@@ -41,21 +41,23 @@ TASK_TO_ARTIFACT_TYPE = {"object_detection": "object.detection", "face_detection
                          "scene_detection": "scene", "segment_embedding": "segment.embedding",
                          "place_detection": "place.classification", "ocr": "ocr.text", "topic_extraction": "topic",
                          "thumbnail_generation": "scene.thumbnail", "transcription": "transcript.segment",
-                         "action_detection": "action.detection", "frame_embedding": "frame.embedding"}
+                         "action_detection": "action.detection", "frame_embedding": "frame.embedding",
+                         "sound_detection": "sound.detection"}
 TASK_TO_RESULT_KEY = {"object_detection": "detections", "face_detection": "detections", "scene_detection": "scenes",
                       "segment_embedding": "embeddings", "place_detection": "classifications", "ocr": "detections",
                       "topic_extraction": "topics", "thumbnail_generation": "thumbnails", "transcription": "segments",
-                      "action_detection": "actions", "frame_embedding": "embeddings"}
+                      "action_detection": "actions", "frame_embedding": "embeddings", "sound_detection": "sounds"}
 # the reference's seven (task_handler.py:92-127) + the one its semantic-search design adds after transcription
 # (.kiro/specs/semantic-video-search/tasks.md:297-302): embed the transcript segments, index them; and the topic stage its
 # worker configs schedule (config/*.json "topic_extraction"; tasks.md 12.1-12.3): KeyBERT keywords of the segments; and the
 # thumbnail worker the design runs behind scene detection (design.md:276-297): one JPEG per scene; and the design's "Action
 # Detector" (design.md §1.8), which the reference never schedules: one "action.detection" envelope per clip; and the frame
 # embeddings that let "search my video library using natural language" reach what a video shows: one "frame.embedding"
-# envelope per sampled frame
+# envelope per sampled frame; and the sounds of the audio track (music, applause, barking: what neither the transcript nor
+# the frames hold): one "sound.detection" envelope per window
 KNOWN_TASK_TYPES = ("object_detection", "face_detection", "transcription", "ocr", "place_detection",
                     "scene_detection", "metadata_extraction", "segment_embedding", "topic_extraction",
-                    "thumbnail_generation", "action_detection", "frame_embedding")
+                    "thumbnail_generation", "action_detection", "frame_embedding", "sound_detection")
 
 
 @dataclass
@@ -198,6 +200,8 @@ async def process_ml_task(ctx, task_id: str, task_type: str, video_id: str, vide
             result = await model_manager.generate_thumbnails(video_path, config or {})
         elif task_type == "action_detection":  # one "action.detection" envelope per clip, spanning the clip's frames
             result = await model_manager.detect_actions(video_path, config or {})
+        elif task_type == "sound_detection":  # one "sound.detection" envelope per window of the audio track
+            result = await model_manager.detect_sounds(video_path, config or {})
         elif task_type == "frame_embedding":  # one "frame.embedding" envelope per sampled frame
             result = await model_manager.embed_frames(video_path, config or {})
             if ctx.get("visual_search_engine") is not None:

@@ -1012,6 +1012,50 @@ int eioku_mjpeg_coefficients(eioku_mjpeg_t* m, const uint8_t* entropy, size_t en
                              int vs, int16_t* coef, int32_t* status, void* stream);
 int eioku_mjpeg_last(eioku_mjpeg_t* m, double* ms5, int* rounds);
 
+/* ---- sound tagging (K29), csrc/sounds.hip ------------------------------------------------------------------------------------
+ * Hugging Face ASTForAudioClassification (MIT/ast-finetuned-audioset-10-10-0.4593) on windows of 16 kHz audio: fp16 matrix
+ * weights and activations, fp32 residual stream, accumulators and head.  [PUBLIC-LIB]: restated from the public transformers
+ * sources.  A window is max_length frames of 400 samples, 160 apart; its spectrogram [max_length][num_mel_bins] is cut into
+ * P = f t overlapping 16 x 16 patches, f = (num_mel_bins - 16) / fstride + 1, t = (max_length - 16) / tstride + 1, patch
+ * fi t + ti (frequency-major); the tokens are CLS, the distillation token, then the patches.
+ *   create: head dimension (hidden / heads) 64, 16 <= num_mel_bins <= 128, max_length >= 16 and at most 4094 tokens, both
+ *     strides in [1, 16], labels in [1, 8192], ffn a multiple of 32; anything else is EIOKU_EINVAL, each with its own message.
+ *     layers may be 0.  window HOST fp64 [400] (symmetric Hann), mel HOST fp64 [257][num_mel_bins] (Kaldi-scale triangles),
+ *     mean and std of the normalisation (x - mean) / (2 std).
+ *   tensor_info / set_tensor: fp32, row-major rows x cols, under the names and in the order of the model's state_dict():
+ *     audio_spectrogram_transformer.embeddings.{cls_token, distillation_token (1 x hidden), position_embeddings (P + 2 x
+ *     hidden), patch_embeddings.projection.weight (hidden x 256, column 16 df + dt) / .bias}, per layer
+ *     audio_spectrogram_transformer.layers.<l>.{attention.q_proj, .k_proj, .v_proj (stored as one packed [3 hidden][hidden]
+ *     weight), attention.o_proj, layernorm_before, layernorm_after, mlp.fc1, mlp.fc2}.{weight, bias}, then
+ *     audio_spectrogram_transformer.layernorm, classifier.layernorm and classifier.dense.  Biases are rows x 1.
+ *   set_audio: the file's mono samples in [-1, 1] (host or device per mem), kept on the device.  Synchronous.
+ *   features: HOST plan [n_windows][2] = (first sample, valid frames in [1, max_length]) -> the normalised log-mel
+ *     spectrogram [n_windows][max_length][num_mel_bins] fp32 (fp64 arithmetic, one rounding; rows from the valid frames on
+ *     hold the normalised zero) and / or the patch rows [n_windows][P][256] fp16, element 16 df + dt = spec[tstride ti + dt]
+ *     [fstride fi + df].  Device buffers, each optional.  Synchronous.
+ *   forward: patch rows -> logits [n_windows][labels] fp32 and optionally hidden_out [n_windows][P + 2][hidden] fp32, the
+ *     residual stream before the final LayerNorm.  Device buffers, asynchronous.
+ *   topk: sigmoid scores and labels of the top_k largest logits (logit descending, label ascending), on device logits.
+ *   classify: features + forward + topk for n_windows windows of the uploaded audio; outputs on the side `mem` names
+ *     ([n_windows][top_k]; logits and hidden optional).
+ *   At most 64 windows per features / forward / classify call.
+ *   last_flops: GEMM, attention and head FLOPs of the last forward / classify.  last_ms: its device time per stage. */
+typedef struct eioku_ast eioku_ast_t;
+int eioku_ast_create(int num_mel_bins, int max_length, int fstride, int tstride, int hidden, int layers, int heads, int ffn, int labels,
+                     float ln_eps, const double* window, const double* mel, double mean, double std, eioku_ast_t** out);
+void eioku_ast_destroy(eioku_ast_t* m);
+int eioku_ast_num_tensors(const eioku_ast_t* m);
+int eioku_ast_tensor_info(const eioku_ast_t* m, int idx, char* name, size_t name_cap, int* rows, int* cols);
+int eioku_ast_set_tensor(eioku_ast_t* m, int idx, const float* host_data, size_t numel);
+int eioku_ast_set_audio(eioku_ast_t* m, const float* samples, long long n, int mem, void* stream);
+int eioku_ast_features(eioku_ast_t* m, const int32_t* plan, int n_windows, float* spec_out, void* patches_out, void* stream);
+int eioku_ast_forward(eioku_ast_t* m, const void* patches, int n_windows, float* logits_out, float* hidden_out, void* stream);
+int eioku_ast_topk(eioku_ast_t* m, const float* logits, int n, int top_k, float* score_out, int32_t* id_out, void* stream);
+int eioku_ast_classify(eioku_ast_t* m, const int32_t* plan, int n_windows, int top_k, float* score_out, int32_t* id_out,
+                       float* logits_out, float* hidden_out, int mem, void* stream);
+int eioku_ast_last_flops(const eioku_ast_t* m, double* flops);
+int eioku_ast_last_ms(const eioku_ast_t* m, double* features_ms, double* encoder_ms, double* head_ms);
+
 #ifdef __cplusplus
 }
 #endif
