@@ -11,7 +11,8 @@
 //                       workgroup, keys / values staged through LDS 128 at a time, QK^T and PV on v_mfma_f32_16x16x32_f16
 //                       with an online softmax
 //   k_cls_mean          the CLS rule: mean over the frames (t = 0 .. T - 1, fp32) of the projected CLS outputs, added to CLS
-//   k_action_head       softmax and top-k of the logits, ties to the smaller class index
+//   k_action_head       softmax and top-k of the logits (block_argmax_256, layernorm.h), ties to the smaller class index
+// The launch wrappers, the activation buffers and the MLP sublayer (LN -> fc1 + GELU -> fc2 EPI_RESID) are encoder.h's.
 // Residual stream x, fp32: the B P T patch rows first, row (b P + p) T + t, then the B CLS rows.  The temporal GEMMs see the
 // first B P T rows as one dense matrix, the spatial qkv and the MLP all B (P T + 1) rows; the CLS row of a clip goes
 // through LayerNorm and qkv once for all its T frames.
@@ -19,12 +20,9 @@
 // LayerNorm parameters and the embedding tables fp32; the residual stream fp32; LayerNorm outputs, q / k / v, attention
 // outputs, the temporal out-projection, GELU outputs and the patch rows are rounded to fp16; the spatial kernel rounds
 // its softmax numerators exp(s - max) to fp16 for the PV MFMA.
-#include "attn_f16.h"
 #include "clip_resize.h"
 #include "common.h"
-#include "gemm_f16.h"
-#include "layernorm.h"
-#include "tensors.h"
+#include "encoder.h"
 
 #include <cmath>
 #include <string>
@@ -175,29 +173,12 @@ __global__ __launch_bounds__(256) void k_action_head(const float* __restrict__ l
   for (int j = tid; j < nc; j += 256) s_p[j] = s_p[j] / total;
   __syncthreads();
   for (int k = 0; k < top_k; ++k) {
-    float bv = -1.f;  // below every probability; taken entries are set to -2
-    int bi = 0x7fffffff;
-    for (int j = tid; j < nc; j += 256) {
-      const float v = s_p[j];
-      if (v > bv) bv = v, bi = j;  // ascending j: the first of equal values stays
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
-    }
-    if (lane == 0) s_f[wave] = bv, s_i[wave] = bi;
-    __syncthreads();
-    bv = s_f[0], bi = s_i[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (s_f[w] > bv || (s_f[w] == bv && s_i[w] < bi)) bv = s_f[w], bi = s_i[w];
-    if (bi >= nc) bi = 0;  // NaN logits compare false everywhere
+    Best best = block_argmax_256(s_p, nc, -1.f, s_f, s_i);  // -1: below every probability; taken entries are set to -2
+    if (best.i >= nc) best.i = 0;  // NaN logits compare false everywhere
     if (tid == 0) {
-      prob_out[(size_t)b * top_k + k] = bv;
-      idx_out[(size_t)b * top_k + k] = bi;
-      s_p[bi] = -2.f;
+      prob_out[(size_t)b * top_k + k] = best.v;
+      idx_out[(size_t)b * top_k + k] = best.i;
+      s_p[best.i] = -2.f;
     }
     __syncthreads();
   }
@@ -205,8 +186,9 @@ __global__ __launch_bounds__(256) void k_action_head(const float* __restrict__ l
 
 // ---- the model ------------------------------------------------------------------------------------------------------------
 struct Layer {
-  LNorm t_ln, s_ln, m_ln;
-  Lin t_qkv, t_out, t_dense, s_qkv, s_out, fc1, fc2;
+  LNorm t_ln;
+  Lin t_qkv, t_out, t_dense;
+  EncLayer s;  // spatial attention (ln1, qkv, out) and the MLP (ln2, fc1, fc2)
 };
 
 }  // namespace
@@ -227,11 +209,10 @@ struct eioku_timesformer : TensorTable {
   DevBuf<uint8_t> src, tmp;
   DevBuf<h16> patches;
   // activations of one pass over B clips
-  DevBuf<float> x, cls_proj, logits, probs;
-  DevBuf<h16> h, qkv, a, mid;
+  EncWork work;  // a: the B P T patch rows, then the B T per-frame CLS rows
+  DevBuf<float> cls_proj, logits, probs;
   DevBuf<int> ids;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool timed[3] = {false, false, false};  // which of preprocess / encoder / head the last call ran
+  StageClock<3> clock;  // preprocess / encoder / head
   double flops = 0;
 };
 
@@ -239,33 +220,19 @@ namespace {
 
 typedef eioku_timesformer Model;
 
-template <int MT, int EPI>
-int gemm(Model* m, hipStream_t st, const h16* A, int lda, const Lin& w, int M, int N, int K, void* out, long long ldc,
-         const float* pos = nullptr, int pos_rows = 1) {
-  return launch_gemm<MT, EPI>(st, A, lda, m->H(w.w), K, m->F(w.b), M, N, K, out, ldc, pos, pos_rows, nullptr, &m->flops);
-}
-
-int ln(Model* m, hipStream_t st, const float* x, int M, const LNorm& p, h16* out) {
-  hipLaunchKernelGGL(k_ln<h16>, dim3((M + 3) / 4), dim3(256), 0, st, x, M, m->d, m->F(p.g), m->F(p.b), m->eps, (const int*)nullptr, out);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
-}
-
 int ensure_batch(Model* m, int B) {
-  const size_t PT = (size_t)m->P * m->frames, M = (size_t)B * (PT + 1), d = m->d;
-  EIOKU_TRY(grow_synced(m->x, M * d));
-  EIOKU_TRY(grow_synced(m->h, M * d));
-  EIOKU_TRY(grow_synced(m->qkv, M * 3 * d));
-  EIOKU_TRY(grow_synced(m->a, ((size_t)B * PT + (size_t)B * m->frames) * d));
-  EIOKU_TRY(grow_synced(m->mid, M * m->ffn));
+  const size_t PT = (size_t)m->P * m->frames, d = m->d;
+  EIOKU_TRY(m->work.grow((size_t)B * (PT + 1), d, m->ffn, (size_t)B * PT + (size_t)B * m->frames));
   EIOKU_TRY(grow_synced(m->cls_proj, (size_t)B * m->frames * d));
   EIOKU_TRY(grow_synced(m->logits, (size_t)B * m->labels));
   EIOKU_TRY(grow_synced(m->probs, (size_t)B * m->labels));
   return grow_synced(m->ids, (size_t)B * m->labels);
 }
 
-// patches [B P T][768] fp16 (device) -> the residual stream after every layer in m->x, the logits in m->logits
+// patches [B P T][768] fp16 (device) -> the residual stream after every layer in m->work.x
 int run_encoder(Model* m, const h16* patches, int B, hipStream_t st) {
+  const Enc enc{m, st, m->d, m->eps, &m->flops};
+  EncWork& w = m->work;
   const int d = m->d, T = m->frames, P = m->P, PT = P * T, Mp = B * PT, M = Mp + B;
   if (!m->tables_ready) {
     const size_t n = (size_t)PT * d + d;
@@ -274,51 +241,49 @@ int run_encoder(Model* m, const h16* patches, int B, hipStream_t st) {
     EIOKU_LAUNCH_CHECK();
     m->tables_ready = true;
   }
-  float* x = m->x;
+  float* x = w.x;
   float* x_cls = x + (size_t)Mp * d;
-  EIOKU_TRY((gemm<4, EPI_POS>(m, st, patches, kPatchK, m->proj, Mp, d, kPatchK, x, d, m->postime, PT)));
+  EIOKU_TRY((enc.gemm<4, EPI_POS>(patches, kPatchK, m->proj, Mp, d, kPatchK, x, d, m->postime, PT)));
   hipLaunchKernelGGL(k_cls_rows, dim3((unsigned)(((size_t)B * d + 255) / 256)), dim3(256), 0, st, m->cls.p, B, d, x_cls);
   EIOKU_LAUNCH_CHECK();
-  h16* a_cls = m->a.p + (size_t)Mp * d;
+  h16* a_cls = w.a.p + (size_t)Mp * d;
   for (const Layer& L : m->L) {
     // temporal: patch rows only
-    EIOKU_TRY(ln(m, st, x, Mp, L.t_ln, m->h));
-    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->h, d, L.t_qkv, Mp, 3 * d, d, m->qkv.p, 3 * d)));
+    EIOKU_TRY(enc.ln<h16>(x, Mp, L.t_ln, w.h.p));
+    EIOKU_TRY((enc.gemm<4, EPI_F16>(w.h, d, L.t_qkv, Mp, 3 * d, d, w.qkv.p, 3 * d)));
     {
       const long long probs = (long long)B * P * m->heads;
       const size_t lds = (size_t)3 * T * 66 * sizeof(h16) + 96 * sizeof(float);
-      hipLaunchKernelGGL(k_attn_time, dim3((unsigned)probs), dim3(64), lds, st, m->qkv.p, T, m->heads, m->a.p);
+      hipLaunchKernelGGL(k_attn_time, dim3((unsigned)probs), dim3(64), lds, st, w.qkv.p, T, m->heads, w.a.p);
       EIOKU_LAUNCH_CHECK();
       m->flops += 4.0 * probs * T * T * 64;
     }
-    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->a, d, L.t_out, Mp, d, d, m->h.p, d)));
-    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->h, d, L.t_dense, Mp, d, d, x, d)));
+    EIOKU_TRY((enc.gemm<4, EPI_F16>(w.a, d, L.t_out, Mp, d, d, w.h.p, d)));
+    EIOKU_TRY((enc.gemm<4, EPI_RESID>(w.h, d, L.t_dense, Mp, d, d, x, d)));
     // spatial: every row; the CLS row of a clip is normalised and projected once for its T frames
-    EIOKU_TRY(ln(m, st, x, M, L.s_ln, m->h));
-    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->h, d, L.s_qkv, M, 3 * d, d, m->qkv.p, 3 * d)));
+    EIOKU_TRY(enc.ln<h16>(x, M, L.s.ln1, w.h.p));
+    EIOKU_TRY((enc.gemm<4, EPI_F16>(w.h, d, L.s.qkv, M, 3 * d, d, w.qkv.p, 3 * d)));
     {
       const int n = 1 + P;
-      EIOKU_TRY(launch_attn<false>(st, m->qkv.p, SpaceTimeSeq{B, P, T, d, m->a.p, a_cls}, n, m->heads, B * T));
+      EIOKU_TRY(launch_attn<false>(st, w.qkv.p, SpaceTimeSeq{B, P, T, d, w.a.p, a_cls}, n, m->heads, B * T));
       m->flops += 4.0 * B * T * m->heads * (double)n * n * 64;
     }
-    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->a, d, L.s_out, Mp, d, d, x, d)));
-    EIOKU_TRY((gemm<4, EPI_F32>(m, st, a_cls, d, L.s_out, B * T, d, d, m->cls_proj.p, d)));
+    EIOKU_TRY((enc.gemm<4, EPI_RESID>(w.a, d, L.s.out, Mp, d, d, x, d)));
+    EIOKU_TRY((enc.gemm<4, EPI_F32>(a_cls, d, L.s.out, B * T, d, d, m->cls_proj.p, d)));
     hipLaunchKernelGGL(k_cls_mean, dim3((unsigned)(((size_t)B * d + 255) / 256)), dim3(256), 0, st, m->cls_proj.p, B, T, d, x_cls);
     EIOKU_LAUNCH_CHECK();
-    // MLP
-    EIOKU_TRY(ln(m, st, x, M, L.m_ln, m->h));
-    EIOKU_TRY((gemm<4, EPI_GELU_F16>(m, st, m->h, d, L.fc1, M, m->ffn, d, m->mid.p, m->ffn)));
-    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->mid, m->ffn, L.fc2, M, d, m->ffn, x, d)));
+    EIOKU_TRY(mlp_sublayer(enc, w, M, L.s.ln2, L.s.fc1, L.s.fc2, m->ffn, false));
   }
   return EIOKU_OK;
 }
 
 // final LayerNorm and classifier on the CLS rows; top_k > 0 adds softmax and selection
 int run_head(Model* m, int B, int top_k, hipStream_t st) {
+  const Enc enc{m, st, m->d, m->eps, &m->flops};
   const int d = m->d;
-  const float* x_cls = m->x.p + (size_t)B * m->P * m->frames * d;
-  EIOKU_TRY(ln(m, st, x_cls, B, m->final_ln, m->h));
-  EIOKU_TRY((gemm<1, EPI_F32>(m, st, m->h, d, m->classifier, B, m->labels, d, m->logits.p, m->labels)));
+  const float* x_cls = m->work.x.p + (size_t)B * m->P * m->frames * d;
+  EIOKU_TRY(enc.ln<h16>(x_cls, B, m->final_ln, m->work.h.p));
+  EIOKU_TRY((enc.gemm<1, EPI_F32>(m->work.h, d, m->classifier, B, m->labels, d, m->logits.p, m->labels)));
   if (top_k > 0) {
     hipLaunchKernelGGL(k_action_head, dim3(B), dim3(256), (size_t)m->labels * sizeof(float), st, m->logits.p, m->labels, top_k,
                        m->probs.p, m->ids.p);
@@ -364,12 +329,12 @@ int eioku_timesformer_create(int image, int patch, int frames, int hidden, int l
     L.t_qkv = m->lin(p + "temporal_attention.attention.qkv", 3 * d, d);
     L.t_out = m->lin(p + "temporal_attention.output.dense", d, d);
     L.t_dense = m->lin(p + "temporal_dense", d, d);
-    L.s_ln = m->lnorm(p + "layernorm_before", d);
-    L.s_qkv = m->lin(p + "attention.attention.qkv", 3 * d, d);
-    L.s_out = m->lin(p + "attention.output.dense", d, d);
-    L.m_ln = m->lnorm(p + "layernorm_after", d);
-    L.fc1 = m->lin(p + "intermediate.dense", ffn, d);
-    L.fc2 = m->lin(p + "output.dense", d, ffn);
+    L.s.ln1 = m->lnorm(p + "layernorm_before", d);
+    L.s.qkv = m->lin(p + "attention.attention.qkv", 3 * d, d);
+    L.s.out = m->lin(p + "attention.output.dense", d, d);
+    L.s.ln2 = m->lnorm(p + "layernorm_after", d);
+    L.s.fc1 = m->lin(p + "intermediate.dense", ffn, d);
+    L.s.fc2 = m->lin(p + "output.dense", d, ffn);
     m->L.push_back(L);
   }
   m->final_ln = m->lnorm("timesformer.layernorm", d);
@@ -380,12 +345,7 @@ int eioku_timesformer_create(int image, int patch, int frames, int hidden, int l
   };
   if (const int rc = m->finish()) return fail(rc);
   if (m->postime.grow((size_t)m->P * frames * d) || m->cls.grow((size_t)d)) return fail(EIOKU_ENOMEM);
-  for (auto& ev : m->ev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      ev = nullptr;
-      set_error("hipEventCreate failed");
-      return fail(EIOKU_EHIP);
-    }
+  if (const int rc = m->clock.create()) return fail(rc);
   *out = m;
   return EIOKU_OK;
 }
@@ -393,9 +353,7 @@ int eioku_timesformer_create(int image, int patch, int frames, int hidden, int l
 void eioku_timesformer_destroy(eioku_timesformer* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (auto ev : m->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete m;  // every buffer frees itself
+  delete m;  // every buffer and event frees itself
 }
 
 int eioku_timesformer_num_tensors(const eioku_timesformer* m) { return TensorTable::count(m); }
@@ -449,17 +407,17 @@ int eioku_timesformer_forward(eioku_timesformer* m, const void* patches, int n_c
   hipStream_t st = (hipStream_t)stream_;
   EIOKU_TRY(ensure_batch(m, n_clips));
   m->flops = 0;
-  m->timed[0] = false, m->timed[1] = m->timed[2] = true;
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  m->clock.begin(0b110);
+  EIOKU_TRY(m->clock.mark(1, st));
   EIOKU_TRY(run_encoder(m, (const h16*)patches, n_clips, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
+  EIOKU_TRY(m->clock.mark(2, st));
   EIOKU_TRY(run_head(m, n_clips, 0, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  EIOKU_TRY(m->clock.mark(3, st));
   EIOKU_HIP_CHECK(hipMemcpyAsync(logits_out, m->logits, (size_t)n_clips * m->labels * 4, hipMemcpyDeviceToDevice, st));
   if (hidden_out) {
     const int PT = m->P * m->frames;
     const size_t n = (size_t)n_clips * (PT + 1) * m->d;
-    hipLaunchKernelGGL(k_hidden_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->x.p, n_clips, PT, m->d, hidden_out);
+    hipLaunchKernelGGL(k_hidden_out, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->work.x.p, n_clips, PT, m->d, hidden_out);
     EIOKU_LAUNCH_CHECK();
   }
   return EIOKU_OK;
@@ -482,14 +440,14 @@ int eioku_timesformer_classify(eioku_timesformer* m, const uint8_t* bgr, int n_c
   EIOKU_TRY(ensure_batch(m, n_clips));
   EIOKU_TRY(grow_synced(m->patches, (size_t)n_clips * m->P * m->frames * kPatchK));
   m->flops = 0;
-  m->timed[0] = m->timed[1] = m->timed[2] = true;
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[0], st));
+  m->clock.begin(0b111);
+  EIOKU_TRY(m->clock.mark(0, st));
   EIOKU_TRY(preprocess(m, bgr, n_clips, h, w, xbounds, xk, kx, ybounds, yk, ky, m->patches.p, nullptr, mem, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  EIOKU_TRY(m->clock.mark(1, st));
   EIOKU_TRY(run_encoder(m, m->patches.p, n_clips, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
+  EIOKU_TRY(m->clock.mark(2, st));
   EIOKU_TRY(run_head(m, n_clips, top_k, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  EIOKU_TRY(m->clock.mark(3, st));
   const hipMemcpyKind kind = mem == EIOKU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   EIOKU_HIP_CHECK(hipMemcpyAsync(prob_out, m->probs, (size_t)n_clips * top_k * 4, kind, st));
   EIOKU_HIP_CHECK(hipMemcpyAsync(class_out, m->ids, (size_t)n_clips * top_k * 4, kind, st));
@@ -521,16 +479,8 @@ int eioku_timesformer_last_flops(const eioku_timesformer* m, double* flops) {
 // device milliseconds of the last forward / classify call per stage (0 for a stage that call did not run); waits for it
 int eioku_timesformer_last_ms(const eioku_timesformer* m, double* preprocess_ms, double* encoder_ms, double* head_ms) {
   EIOKU_REQUIRE(m && preprocess_ms && encoder_ms && head_ms, "NULL argument");
-  double* out[3] = {preprocess_ms, encoder_ms, head_ms};
-  for (int i = 0; i < 3; ++i) {
-    *out[i] = 0.0;
-    if (!m->timed[i]) continue;
-    float ms = 0.f;
-    EIOKU_HIP_CHECK(hipEventSynchronize(m->ev[i + 1]));
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, m->ev[i], m->ev[i + 1]));
-    *out[i] = ms;
-  }
-  return EIOKU_OK;
+  double* const out[3] = {preprocess_ms, encoder_ms, head_ms};
+  return m->clock.last_ms(out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // The tiled MFMA attention of the transformer models with 64-wide heads (K25 TimeSformer's spatial attention, K26 CLIP, K27
-// nomic-embed-text): one kernel, and per model a policy that says which rows of qkv form a sequence and where its outputs go.
-// Included by actions.hip, clip.hip, nomic.hip and sounds.hip; everything here has internal linkage.
+// nomic-embed-text, K29 AST): one kernel, and per model a policy that says which rows of qkv form a sequence and where its
+// outputs go.  Included by nomic.hip and probe/transformer_probe.hip, and through encoder.h by actions.hip, clip.hip and
+// sounds.hip; everything here has internal linkage.
 #pragma once
 
 #include "common.h"

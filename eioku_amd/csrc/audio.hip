@@ -143,7 +143,7 @@ struct eioku_audio {
   DevBuf<float> bank;         // W [T][up]
   DevBuf<float> out;          // slab
   DevBuf<uint32_t> raw;       // the slab's input frames
-  std::vector<hipEvent_t> ev;   // 2 per slab of the last call
+  DevEvents ev;               // 2 per slab of the last call
   double ms = 0;
 };
 
@@ -163,9 +163,8 @@ int eioku_audio_plan(int up, int down, int taps_per_phase, long long slab_out, l
 void eioku_audio_destroy(eioku_audio* a) {
   if (!a) return;
   if (a->st) (void)hipStreamSynchronize(a->st);
-  for (hipEvent_t e : a->ev) (void)hipEventDestroy(e);
   if (a->st) (void)hipStreamDestroy(a->st);
-  delete a;  // every buffer frees itself
+  delete a;  // every buffer and event frees itself
 }
 
 int eioku_audio_create(int up, int down, int taps_per_phase, const float* bank, long long slab_out, eioku_audio** out) {
@@ -252,11 +251,7 @@ int eioku_audio_resample(eioku_audio* a, const void* pcm, int format, int channe
     EIOKU_HIP_CHECK(hipStreamSynchronize(a->st));
     EIOKU_TRY(a->raw.grow((need + 3) / 4));
   }
-  while ((long long)a->ev.size() < 2 * n_slabs) {
-    hipEvent_t e;
-    EIOKU_HIP_CHECK(hipEventCreate(&e));
-    a->ev.push_back(e);
-  }
+  EIOKU_TRY(a->ev.ensure((size_t)(2 * n_slabs)));
   hipStream_t st = a->st;
   static const int cus = num_cus();
   for (long long k = 0; k < n_slabs; ++k) {
@@ -267,7 +262,7 @@ int eioku_audio_resample(eioku_audio* a, const void* pcm, int format, int channe
     if (bytes)
       EIOKU_HIP_CHECK(hipMemcpyAsync(a->raw.p, (const char*)pcm + (size_t)pl.first_frame * fb, bytes, hipMemcpyHostToDevice, st));
     const Src src{a->raw, (unsigned)pl.lead, (unsigned)pl.frames, format, channels};
-    EIOKU_HIP_CHECK(hipEventRecord(a->ev[2 * k], st));
+    EIOKU_TRY(a->ev.record(2 * k, st));
     if (a->T) {
       const unsigned tiles = (unsigned)((pl.n_out + a->tile - 1) / a->tile);
       const unsigned grid = tiles < 2u * cus ? tiles : 2u * cus;     // two 64 KiB workgroups per CU
@@ -278,14 +273,14 @@ int eioku_audio_resample(eioku_audio* a, const void* pcm, int format, int channe
                          (unsigned)pl.n_out, a->out.p);
     }
     EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipEventRecord(a->ev[2 * k + 1], st));
+    EIOKU_TRY(a->ev.record(2 * k + 1, st));
     // the next slab reuses raw and out: stream order keeps its copy behind this slab's kernel and read-back
     EIOKU_HIP_CHECK(hipMemcpyAsync(samples_out + pl.out_start, a->out, (size_t)pl.n_out * sizeof(float), hipMemcpyDeviceToHost, st));
   }
   EIOKU_HIP_CHECK(hipStreamSynchronize(st));
   for (long long k = 0; k < n_slabs; ++k) {
-    float t = 0;
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&t, a->ev[2 * k], a->ev[2 * k + 1]));
+    double t = 0;
+    EIOKU_TRY(a->ev.ms(2 * k, 2 * k + 1, &t));
     a->ms += t;
   }
   return EIOKU_OK;

@@ -11,19 +11,16 @@
 //                       of 16), keys / values staged through LDS 128 at a time, QK^T and PV on v_mfma_f32_16x16x32_f16 with an
 //                       online softmax; CAUSAL: query i sees keys 0 .. i, a wave's key loop ends at its last query's key
 //   k_l2norm            the projected rows to unit length in fp32
-// Layers are pre-LN: LN -> packed qkv GEMM -> attention -> out-projection (EPI_RESID) -> LN -> fc1 with the activation
-// epilogue -> fc2 (EPI_RESID).  The text tower runs n = max(eot + 1) positions per text: under the causal mask no row up
+// Layers are pre-LN, attn_sublayer and mlp_sublayer of encoder.h: LN -> packed qkv GEMM -> attention -> out-projection
+// (EPI_RESID) -> LN -> fc1 with the activation epilogue -> fc2 (EPI_RESID).  The text tower runs n = max(eot + 1) positions per text: under the causal mask no row up
 // to EOT reads a later one, so the 77 - n pad positions are never computed.
 // Precision points (tests/clip_oracle.py, fp16=True, rounds at the same places): matrix weights fp16; biases, LayerNorm
 // parameters, the embedding and position tables fp32; the residual stream fp32 (pre_layrnorm writes it unrounded); LayerNorm
 // outputs, q / k / v, attention outputs, activation outputs and the patch rows are rounded to fp16; the softmax numerators
 // exp(s - max) are rounded to fp16 for the PV MFMA; the projection, the norm and the outputs are fp32.
-#include "attn_f16.h"
 #include "clip_resize.h"
 #include "common.h"
-#include "gemm_f16.h"
-#include "layernorm.h"
-#include "tensors.h"
+#include "encoder.h"
 
 #include <cmath>
 #include <string>
@@ -69,14 +66,9 @@ __global__ __launch_bounds__(256) void k_l2norm(const float* __restrict__ v, int
 // ---- the model ------------------------------------------------------------------------------------------------------------
 enum { VISION = 0, TEXT = 1 };
 
-struct Layer {
-  LNorm ln1, ln2;
-  Lin qkv, out, fc1, fc2;
-};
-
 struct Tower {
   int d = 0, layers = 0, heads = 0, ffn = 0;
-  std::vector<Layer> L;
+  std::vector<EncLayer> L;
   LNorm final_ln{};
   int proj = -1;  // [projection_dim][d], no bias
 };
@@ -98,12 +90,12 @@ struct eioku_clip : TensorTable {  // tag: the tower
   DevBuf<uint8_t> src, tmp;
   DevBuf<h16> patches;
   // activations of one pass
-  DevBuf<float> x, x0, pooled, unit;
-  DevBuf<h16> h, qkv, a, mid, hp;
+  EncWork work;
+  DevBuf<float> x0, pooled, unit;
+  DevBuf<h16> hp;
   DevBuf<int> ids, pick;
   std::vector<int> ids_host, pick_host;  // what the asynchronous uploads read: alive until the next call
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool timed[3] = {false, false, false};  // which of preprocess / encoder / head the last call ran
+  StageClock<3> clock;  // preprocess / encoder / head
   double flops = 0;
 };
 
@@ -111,53 +103,27 @@ namespace {
 
 typedef eioku_clip Model;
 
-template <int MT, int EPI>
-int gemm(Model* m, hipStream_t st, const h16* A, int lda, int w, int bias, int M, int N, int K, void* out, long long ldc,
-         const float* pos = nullptr, int pos_rows = 1) {
-  return launch_gemm<MT, EPI>(st, A, lda, m->H(w), K, m->F(bias), M, N, K, out, ldc, pos, pos_rows, nullptr, &m->flops);
-}
-
-template <typename OUT>
-int ln(Model* m, hipStream_t st, const float* x, int M, int d, const LNorm& p, const int* pick, OUT* out) {
-  if (M == 0) return EIOKU_OK;
-  hipLaunchKernelGGL(k_ln<OUT>, dim3((M + 3) / 4), dim3(256), 0, st, x, M, d, m->F(p.g), m->F(p.b), m->eps, pick, out);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
-}
+Enc enc_of(Model* m, int tower, hipStream_t st) { return Enc{m, st, m->tw[tower].d, m->eps, &m->flops}; }
 
 int ensure_rows(Model* m, int tower, size_t M, int B) {
   const Tower& t = m->tw[tower];
   const size_t d = t.d;
-  EIOKU_TRY(grow_synced(m->x, M * d));
+  EIOKU_TRY(m->work.grow(M, d, t.ffn));
   if (tower == VISION) EIOKU_TRY(grow_synced(m->x0, M * d));  // the embedded stream before pre_layrnorm
-  EIOKU_TRY(grow_synced(m->h, M * d));
-  EIOKU_TRY(grow_synced(m->qkv, M * 3 * d));
-  EIOKU_TRY(grow_synced(m->a, M * d));
-  EIOKU_TRY(grow_synced(m->mid, M * t.ffn));
   EIOKU_TRY(grow_synced(m->hp, (size_t)B * d));
   EIOKU_TRY(grow_synced(m->pick, (size_t)B));
   EIOKU_TRY(grow_synced(m->pooled, (size_t)B * m->proj_dim));
   return grow_synced(m->unit, (size_t)B * m->proj_dim);
 }
 
-// the residual stream m->x [B n][d] through the tower's layers
+// the residual stream m->work.x [B n][d] through the tower's layers
 template <bool CAUSAL>
 int run_layers(Model* m, int tower, int B, int n, hipStream_t st) {
   const Tower& t = m->tw[tower];
-  const int d = t.d, M = B * n;
-  float* x = m->x;
-  for (const Layer& L : t.L) {
-    EIOKU_TRY(ln<h16>(m, st, x, M, d, L.ln1, nullptr, m->h.p));
-    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->h, d, L.qkv.w, L.qkv.b, M, 3 * d, d, m->qkv.p, 3 * d)));
-    EIOKU_TRY(launch_attn<CAUSAL>(st, m->qkv.p, DenseSeq{n, d, m->a.p}, n, t.heads, B));
-    m->flops += 4.0 * B * t.heads * (double)n * n * 64 * (CAUSAL ? 0.5 : 1.0);
-    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->a, d, L.out.w, L.out.b, M, d, d, x, d)));
-    EIOKU_TRY(ln<h16>(m, st, x, M, d, L.ln2, nullptr, m->h.p));
-    if (m->act == 0)
-      EIOKU_TRY((gemm<4, EPI_QGELU_F16>(m, st, m->h, d, L.fc1.w, L.fc1.b, M, t.ffn, d, m->mid.p, t.ffn)));
-    else
-      EIOKU_TRY((gemm<4, EPI_GELU_F16>(m, st, m->h, d, L.fc1.w, L.fc1.b, M, t.ffn, d, m->mid.p, t.ffn)));
-    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->mid, t.ffn, L.fc2.w, L.fc2.b, M, d, t.ffn, x, d)));
+  const Enc enc = enc_of(m, tower, st);
+  for (const EncLayer& L : t.L) {
+    EIOKU_TRY(attn_sublayer<CAUSAL>(enc, m->work, L, B, n, t.heads));
+    EIOKU_TRY(mlp_sublayer(enc, m->work, B * n, L.ln2, L.fc1, L.fc2, t.ffn, m->act == 0));
   }
   return EIOKU_OK;
 }
@@ -165,33 +131,34 @@ int run_layers(Model* m, int tower, int B, int n, hipStream_t st) {
 // rows pick_host[b] of the stream -> final LayerNorm -> projection -> unit vectors in m->unit [B][projection_dim]
 int run_head(Model* m, int tower, int B, const int* pick_host, hipStream_t st) {
   const Tower& t = m->tw[tower];
+  const Enc enc = enc_of(m, tower, st);
   EIOKU_HIP_CHECK(hipMemcpyAsync(m->pick, pick_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  EIOKU_TRY(ln<h16>(m, st, m->x, B, t.d, t.final_ln, m->pick.p, m->hp.p));
-  EIOKU_TRY((gemm<1, EPI_F32>(m, st, m->hp, t.d, t.proj, -1, B, m->proj_dim, t.d, m->pooled.p, m->proj_dim)));
+  EIOKU_TRY(enc.ln<h16>(m->work.x, B, t.final_ln, m->hp.p, m->pick.p));
+  EIOKU_TRY((enc.gemm<1, EPI_F32>(m->hp, t.d, Lin{t.proj, -1}, B, m->proj_dim, t.d, m->pooled.p, m->proj_dim)));
   hipLaunchKernelGGL(k_l2norm, dim3((B + 3) / 4), dim3(256), 0, st, m->pooled.p, B, m->proj_dim, m->unit.p);
   EIOKU_LAUNCH_CHECK();
   return EIOKU_OK;
 }
 
-// patch rows [B][1 + P][Kp] fp16 (device) -> m->x after every layer, m->unit
+// patch rows [B][1 + P][Kp] fp16 (device) -> m->work.x after every layer, m->unit
 int run_vision(Model* m, const h16* patches, int B, hipStream_t st) {
-  const Tower& t = m->tw[VISION];
-  const int d = t.d, n = 1 + m->P, M = B * n;
+  const Enc enc = enc_of(m, VISION, st);
+  const int d = enc.d, n = 1 + m->P, M = B * n;
   if (!m->table_ready) {
     const size_t e = (size_t)n * d;
     hipLaunchKernelGGL(k_vision_table, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, st, m->F(m->cls), m->F(m->vpos), n, d, m->vtable.p);
     EIOKU_LAUNCH_CHECK();
     m->table_ready = true;
   }
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
-  EIOKU_TRY((gemm<4, EPI_POS>(m, st, patches, m->Kp, m->patch_w, -1, M, d, m->Kp, m->x0.p, d, m->vtable, n)));
-  EIOKU_TRY(ln<float>(m, st, m->x0, M, d, m->pre_ln, nullptr, m->x.p));
+  EIOKU_TRY(m->clock.mark(1, st));
+  EIOKU_TRY((enc.gemm<4, EPI_POS>(patches, m->Kp, Lin{m->patch_w, -1}, M, d, m->Kp, m->x0.p, d, m->vtable, n)));
+  EIOKU_TRY(enc.ln<float>(m->x0, M, m->pre_ln, m->work.x.p));
   EIOKU_TRY(run_layers<false>(m, VISION, B, n, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
+  EIOKU_TRY(m->clock.mark(2, st));
   m->pick_host.resize(B);
   for (int b = 0; b < B; ++b) m->pick_host[b] = b * n;
   EIOKU_TRY(run_head(m, VISION, B, m->pick_host.data(), st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  EIOKU_TRY(m->clock.mark(3, st));
   return EIOKU_OK;
 }
 
@@ -237,7 +204,7 @@ int eioku_clip_create(int image, int patch, int v_hidden, int v_layers, int v_he
   auto layers = [&](const std::string& model, Tower& t) {
     for (int l = 0; l < t.layers; ++l) {
       const std::string p = model + ".encoder.layers." + std::to_string(l) + ".";
-      Layer L;
+      EncLayer L;
       L.qkv.w = m->packed(p + "self_attn.qkv.weight", 3 * t.d, t.d, T_F16);
       L.qkv.b = m->packed(p + "self_attn.qkv.bias", 3 * t.d, 1, T_F32);
       const char* names[3] = {"k_proj", "v_proj", "q_proj"};  // state_dict() order; packed as q | k | v
@@ -281,12 +248,7 @@ int eioku_clip_create(int image, int patch, int v_hidden, int v_layers, int v_he
   };
   if (const int rc = m->finish()) return fail(rc);
   if (m->vtable.grow((size_t)(1 + m->P) * v_hidden)) return fail(EIOKU_ENOMEM);
-  for (auto& ev : m->ev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      ev = nullptr;
-      set_error("hipEventCreate failed");
-      return fail(EIOKU_EHIP);
-    }
+  if (const int rc = m->clock.create()) return fail(rc);
   *out = m;
   return EIOKU_OK;
 }
@@ -294,9 +256,7 @@ int eioku_clip_create(int image, int patch, int v_hidden, int v_layers, int v_he
 void eioku_clip_destroy(eioku_clip* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (auto ev : m->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete m;  // every buffer frees itself
+  delete m;  // every buffer and event frees itself
 }
 
 int eioku_clip_num_tensors(const eioku_clip* m) { return TensorTable::count(m); }
@@ -350,10 +310,10 @@ int eioku_clip_encode_patches(eioku_clip* m, const void* patches, int n, float* 
   const size_t M = (size_t)n * (1 + m->P);
   EIOKU_TRY(ensure_rows(m, VISION, M, n));
   m->flops = 0;
-  m->timed[0] = false, m->timed[1] = m->timed[2] = true;
+  m->clock.begin(0b110);
   EIOKU_TRY(run_vision(m, (const h16*)patches, n, st));
   EIOKU_TRY(copy_out(m->unit, (size_t)n * m->proj_dim, out, EIOKU_MEM_DEVICE, st));
-  if (hidden_out) EIOKU_TRY(copy_out(m->x, M * m->tw[VISION].d, hidden_out, EIOKU_MEM_DEVICE, st));
+  if (hidden_out) EIOKU_TRY(copy_out(m->work.x, M * m->tw[VISION].d, hidden_out, EIOKU_MEM_DEVICE, st));
   return EIOKU_OK;
 }
 
@@ -372,8 +332,8 @@ int eioku_clip_encode_images(eioku_clip* m, const uint8_t* bgr, int n, int h, in
   EIOKU_TRY(ensure_rows(m, VISION, M, n));
   EIOKU_TRY(grow_synced(m->patches, M * m->Kp));
   m->flops = 0;
-  m->timed[0] = m->timed[1] = m->timed[2] = true;
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[0], st));
+  m->clock.begin(0b111);
+  EIOKU_TRY(m->clock.mark(0, st));
   EIOKU_TRY(preprocess(m, bgr, n, h, w, xbounds, xk, kx, ybounds, yk, ky, m->patches.p, nullptr, mem, st));
   EIOKU_TRY(run_vision(m, m->patches.p, n, st));
   EIOKU_TRY(copy_out(m->unit, (size_t)n * m->proj_dim, out, mem, st));
@@ -407,21 +367,21 @@ int eioku_clip_encode_text(eioku_clip* m, const int32_t* ids, const int32_t* eot
   EIOKU_TRY(ensure_rows(m, TEXT, M, n_texts));
   EIOKU_TRY(grow_synced(m->ids, (size_t)n_texts * m->positions));
   m->flops = 0;
-  m->timed[0] = false, m->timed[1] = m->timed[2] = true;
+  m->clock.begin(0b110);
   m->ids_host.assign(ids, ids + (size_t)n_texts * m->positions);
   EIOKU_HIP_CHECK(hipMemcpyAsync(m->ids, m->ids_host.data(), m->ids_host.size() * 4, hipMemcpyHostToDevice, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  EIOKU_TRY(m->clock.mark(1, st));
   hipLaunchKernelGGL(k_text_embed, dim3((unsigned)((M * t.d + 255) / 256)), dim3(256), 0, st, m->ids.p, n_texts, n, m->positions, t.d,
-                     m->F(m->tok), m->F(m->tpos), m->x.p);
+                     m->F(m->tok), m->F(m->tpos), m->work.x.p);
   EIOKU_LAUNCH_CHECK();
   EIOKU_TRY(run_layers<true>(m, TEXT, n_texts, n, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
+  EIOKU_TRY(m->clock.mark(2, st));
   m->pick_host.resize(n_texts);
   for (int b = 0; b < n_texts; ++b) m->pick_host[b] = b * n + eot[b];
   EIOKU_TRY(run_head(m, TEXT, n_texts, m->pick_host.data(), st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  EIOKU_TRY(m->clock.mark(3, st));
   EIOKU_TRY(copy_out(m->unit, (size_t)n_texts * m->proj_dim, out, mem, st));
-  if (hidden_out) EIOKU_TRY(copy_out(m->x, M * t.d, hidden_out, mem, st));
+  if (hidden_out) EIOKU_TRY(copy_out(m->work.x, M * t.d, hidden_out, mem, st));
   if (mem == EIOKU_MEM_HOST) EIOKU_HIP_CHECK(hipStreamSynchronize(st));
   return EIOKU_OK;
 }
@@ -435,16 +395,8 @@ int eioku_clip_last_flops(const eioku_clip* m, double* flops) {
 // device milliseconds of the last encode call per stage (0 for a stage that call did not run); waits for it
 int eioku_clip_last_ms(const eioku_clip* m, double* preprocess_ms, double* encoder_ms, double* head_ms) {
   EIOKU_REQUIRE(m && preprocess_ms && encoder_ms && head_ms, "NULL argument");
-  double* out[3] = {preprocess_ms, encoder_ms, head_ms};
-  for (int i = 0; i < 3; ++i) {
-    *out[i] = 0.0;
-    if (!m->timed[i]) continue;
-    float ms = 0.f;
-    EIOKU_HIP_CHECK(hipEventSynchronize(m->ev[i + 1]));
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, m->ev[i], m->ev[i + 1]));
-    *out[i] = ms;
-  }
-  return EIOKU_OK;
+  double* const out[3] = {preprocess_ms, encoder_ms, head_ms};
+  return m->clock.last_ms(out);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 #include "../../include/eioku_hip.h"
 
@@ -125,6 +126,61 @@ int grow_synced(DevBuf<T>& b, size_t n) {
 
 static_assert(!std::is_copy_constructible<DevBuf<int>>::value, "DevBuf owns its memory");
 static_assert(std::is_nothrow_move_constructible<DevBuf<int>>::value, "DevBuf lives in std::vector");
+
+// An owning set of timing events: ensure(n) creates what is missing of the first n, the destructor destroys them all, and
+// the set is never copied.  The handle that holds it synchronises before it is deleted, as for its buffers.
+struct DevEvents {
+  std::vector<hipEvent_t> ev;
+  DevEvents() = default;
+  DevEvents(const DevEvents&) = delete;
+  DevEvents& operator=(const DevEvents&) = delete;
+  ~DevEvents() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  int ensure(size_t n) {
+    while (ev.size() < n) {
+      hipEvent_t e;
+      if (hipEventCreate(&e) != hipSuccess) {
+        set_error("hipEventCreate failed");
+        return EIOKU_EHIP;
+      }
+      ev.push_back(e);
+    }
+    return EIOKU_OK;
+  }
+  int record(size_t i, hipStream_t stream) const {
+    EIOKU_HIP_CHECK(hipEventRecord(ev[i], stream));
+    return EIOKU_OK;
+  }
+  // device milliseconds from event a to event b; waits for b
+  int ms(size_t a, size_t b, double* out) const {
+    float v = 0.f;
+    EIOKU_HIP_CHECK(hipEventSynchronize(ev[b]));
+    EIOKU_HIP_CHECK(hipEventElapsedTime(&v, ev[a], ev[b]));
+    *out = v;
+    return EIOKU_OK;
+  }
+};
+
+// The N consecutive stages of a model's call between N + 1 events: stage i runs from mark(i) to mark(i + 1).  begin(mask)
+// says which stages this call runs (bit i = stage i); last_ms reports 0 for the others and waits for the rest.
+template <int N>
+struct StageClock {
+  DevEvents ev;
+  bool ran[N] = {};
+  int create() { return ev.ensure(N + 1); }
+  void begin(unsigned mask) {
+    for (int i = 0; i < N; ++i) ran[i] = (mask >> i & 1u) != 0;
+  }
+  int mark(int i, hipStream_t stream) const { return ev.record((size_t)i, stream); }
+  int last_ms(double* const out[N]) const {
+    for (int i = 0; i < N; ++i) {
+      *out[i] = 0.0;
+      if (ran[i]) EIOKU_TRY(ev.ms((size_t)i, (size_t)i + 1, out[i]));
+    }
+    return EIOKU_OK;
+  }
+};
 
 __device__ __forceinline__ unsigned long long splitmix64_at(unsigned long long seed,
                                                             unsigned long long i) {

@@ -1,8 +1,9 @@
-// The fp16 GEMM of the transformer models (K20 Whisper, K25 TimeSformer, K26 CLIP, K27 nomic-embed-text): C = A . W^T on
-// v_mfma_f32_16x16x32_f16 with fused epilogues, and its one launcher.  The models' other shared parts sit next to it:
-// layernorm.h (the wave-per-row LayerNorm), attn_f16.h (the tiled MFMA attention and its sequence policies) and tensors.h (the
-// named-tensor table behind *_num_tensors / *_tensor_info / *_set_tensor).  Included by whisper.hip, actions.hip, clip.hip,
-// nomic.hip and sounds.hip; everything here has internal linkage.
+// The fp16 GEMM of the transformer models (K20 Whisper, K25 TimeSformer, K26 CLIP, K27 nomic-embed-text, K29 AST): C = A . W^T
+// on v_mfma_f32_16x16x32_f16 with fused epilogues, and its one launcher.  The models' other shared parts sit next to it:
+// layernorm.h (the wave-per-row LayerNorm), attn_f16.h (the tiled MFMA attention and its sequence policies), tensors.h (the
+// named-tensor table behind *_num_tensors / *_tensor_info / *_set_tensor) and encoder.h (the pre-LN layer's host side).
+// Included by whisper.hip, nomic.hip and probe/transformer_probe.hip, and through encoder.h by actions.hip, clip.hip and
+// sounds.hip; everything here has internal linkage.
 #pragma once
 
 #include "common.h"

@@ -364,7 +364,7 @@ struct eioku_mjpeg {
   eioku::DevBuf<uint8_t> comp_q, yplane, cplane;
   eioku::DevBuf<int16_t> coef;
   eioku::DevBuf<int> status;
-  hipEvent_t ev[kNumEvents] = {};
+  eioku::DevEvents ev;  // kNumEvents
   int subseq_bits = kDefaultSubseqBits;
   int batch_frames = 0;  // 0: as many as the coefficient budget allows
   double ms[5] = {0, 0, 0, 0, 0};
@@ -449,8 +449,8 @@ int validate(Call& c, int S) {
 }
 
 int add_ms(eioku_mjpeg* m, int stage, int a, int b) {
-  float ms = 0.f;
-  EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, m->ev[a], m->ev[b]));
+  double ms = 0.0;
+  EIOKU_TRY(m->ev.ms(a, b, &ms));
   m->ms[stage] += ms;
   return EIOKU_OK;
 }
@@ -506,7 +506,7 @@ int run_batch(eioku_mjpeg* m, const Call& c, int f0, int f1, uint8_t* out, int16
   for (int f = 0; f < nf; ++f)
     for (int k = 0; k < 3; ++k) comp_q[f * 3 + k] = c.comp[(size_t)(f0 + f) * 9 + k * 3];
 
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[kEvStart], stream));
+  EIOKU_TRY(m->ev.record(kEvStart, stream));
   if (f0 == 0) {  // the whole call's entropy bytes, once, and two zero words behind them
     EIOKU_HIP_CHECK(hipMemcpyAsync(m->words, c.entropy, nwords * 4, hipMemcpyHostToDevice, stream));
     EIOKU_HIP_CHECK(hipMemsetAsync(m->words.p + nwords, 0, 8, stream));
@@ -520,7 +520,7 @@ int run_batch(eioku_mjpeg* m, const Call& c, int f0, int f1, uint8_t* out, int16
   EIOKU_HIP_CHECK(hipMemcpyAsync(m->comp_q, comp_q.data(), comp_q.size(), hipMemcpyHostToDevice, stream));
   EIOKU_HIP_CHECK(hipMemsetAsync(m->coef, 0, ncoef * 2, stream));
   EIOKU_HIP_CHECK(hipMemsetAsync(m->status, 0, 4 * (size_t)nf, stream));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[kEvUploaded], stream));
+  EIOKU_TRY(m->ev.record(kEvUploaded, stream));
 
   // synchronisation rounds: the fixed point is reached when a round decodes nothing
   uint4* ex[2] = {m->exits.p, m->exits.p + nsub};
@@ -546,14 +546,14 @@ int run_batch(eioku_mjpeg* m, const Call& c, int f0, int f1, uint8_t* out, int16
     }
   }
   m->rounds = std::max(m->rounds, rounds);
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[kEvSynced], stream));
+  EIOKU_TRY(m->ev.record(kEvSynced, stream));
 
   hipLaunchKernelGGL(k_sub_scan, dim3((unsigned)nseg), dim3(kScanThreads), 0, stream, m->segs.p, ex[cur], m->first.p, m->status.p);
   hipLaunchKernelGGL(k_write, dim3(nwg), dim3(kEntThreads), 0, stream, m->words.p, m->segs.p, m->sub_seg.p, m->wg.p, m->frame_sub_end.p,
                      m->tables.p, S, ex[cur], m->first.p, g.blocks, m->coef.p);
   hipLaunchKernelGGL(k_dc_scan, dim3((unsigned)(nseg * g.ncomp)), dim3(64), 0, stream, m->segs.p, g, m->coef.p);
   EIOKU_LAUNCH_CHECK();
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[kEvWritten], stream));
+  EIOKU_TRY(m->ev.record(kEvWritten, stream));
 
   if (coef_out) {
     EIOKU_HIP_CHECK(hipMemcpyAsync(coef_out + (size_t)f0 * g.blocks * 64, m->coef, ncoef * 2, hipMemcpyDeviceToHost, stream));
@@ -563,7 +563,7 @@ int run_batch(eioku_mjpeg* m, const Call& c, int f0, int f1, uint8_t* out, int16
     hipLaunchKernelGGL(k_idct, dim3((unsigned)((nblk + 63) / 64)), dim3(64), 0, stream, m->coef.p, nblk, g, m->qtab.p, m->comp_q.p, luma ? 1 : 0,
                        m->yplane.p, m->cplane.p);
     EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipEventRecord(m->ev[kEvIdct], stream));
+    EIOKU_TRY(m->ev.record(kEvIdct, stream));
     if (luma) {
       const long long px = (long long)nf * g.h * g.w;
       hipLaunchKernelGGL(k_luma, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, m->yplane.p, px, g, out + (size_t)f0 * g.h * g.w);
@@ -573,7 +573,7 @@ int run_batch(eioku_mjpeg* m, const Call& c, int f0, int f1, uint8_t* out, int16
                          c.fmt == EIOKU_MJPEG_RGB ? 1 : 0, out + (size_t)f0 * g.h * g.w * 3);
     }
     EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipEventRecord(m->ev[kEvColour], stream));
+    EIOKU_TRY(m->ev.record(kEvColour, stream));
   }
   EIOKU_HIP_CHECK(hipMemcpyAsync(status + f0, m->status, 4 * (size_t)nf, hipMemcpyDeviceToHost, stream));
   EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // the host vectors above have been read; status and coef_out are filled
@@ -612,20 +612,16 @@ int eioku_mjpeg_create(eioku_mjpeg_t** out) {
   EIOKU_REQUIRE(out, "NULL out");
   *out = nullptr;
   eioku_mjpeg* m = new eioku_mjpeg();
-  for (int i = 0; i < kNumEvents; ++i)
-    if (hipEventCreate(&m->ev[i]) != hipSuccess) {
-      ::eioku::set_error("eioku_mjpeg_create: hipEventCreate failed");
-      eioku_mjpeg_destroy(m);
-      return EIOKU_EHIP;
-    }
+  if (const int rc = m->ev.ensure(kNumEvents)) {
+    eioku_mjpeg_destroy(m);
+    return rc;
+  }
   *out = m;
   return EIOKU_OK;
 }
 
 void eioku_mjpeg_destroy(eioku_mjpeg_t* m) {
   if (!m) return;
-  for (hipEvent_t e : m->ev)
-    if (e) (void)hipEventDestroy(e);
   delete m;
 }
 

@@ -125,8 +125,7 @@ struct eioku_nomic : TensorTable {
   DevBuf<h16> h, qkv, a, mid;
   DevBuf<int> ids, cu, pos;
   std::vector<int> ids_host, cu_host, pos_host;  // what the asynchronous uploads read: alive until the next call
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool timed = false;
+  StageClock<1> clock;  // the encode, from the first kernel to the pooled vectors
   double flops = 0;
 };
 
@@ -218,12 +217,7 @@ int eioku_nomic_create(int vocab, int hidden, int layers, int heads, int ffn, in
     }
   }
   if (m->rope.upload(table.data(), table.size())) return fail(EIOKU_ENOMEM);
-  for (auto& ev : m->ev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      ev = nullptr;
-      set_error("hipEventCreate failed");
-      return fail(EIOKU_EHIP);
-    }
+  if (const int rc = m->clock.create()) return fail(rc);
   *out = m;
   return EIOKU_OK;
 }
@@ -231,9 +225,7 @@ int eioku_nomic_create(int vocab, int hidden, int layers, int heads, int ffn, in
 void eioku_nomic_destroy(eioku_nomic* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (auto ev : m->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete m;  // every buffer frees itself
+  delete m;  // every buffer and event frees itself
 }
 
 int eioku_nomic_num_tensors(const eioku_nomic* m) { return TensorTable::count(m); }
@@ -298,10 +290,10 @@ int eioku_nomic_encode(eioku_nomic* m, const int32_t* ids, const int32_t* cu, in
   EIOKU_HIP_CHECK(hipMemcpyAsync(m->ids, m->ids_host.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
   EIOKU_HIP_CHECK(hipMemcpyAsync(m->pos, m->pos_host.data(), (size_t)T * 4, hipMemcpyHostToDevice, st));
   EIOKU_HIP_CHECK(hipMemcpyAsync(m->cu, m->cu_host.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[0], st));
+  EIOKU_TRY(m->clock.mark(0, st));
   EIOKU_TRY(run(m, T, B, longest, dim, matryoshka_dim != 0, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
-  m->timed = true;
+  EIOKU_TRY(m->clock.mark(1, st));
+  m->clock.begin(1);
   const hipMemcpyKind back = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   EIOKU_HIP_CHECK(hipMemcpyAsync(out, m->unit, (size_t)B * dim * 4, back, st));
   if (hidden_out) EIOKU_HIP_CHECK(hipMemcpyAsync(hidden_out, m->x, T * d * 4, back, st));
@@ -318,13 +310,8 @@ int eioku_nomic_last_flops(const eioku_nomic* m, double* flops) {
 // device milliseconds of the last encode call, from the first kernel to the pooled vectors (0 before any call)
 int eioku_nomic_last_ms(const eioku_nomic* m, double* ms) {
   EIOKU_REQUIRE(m && ms, "NULL argument");
-  *ms = 0.0;
-  if (!m->timed) return EIOKU_OK;
-  float v = 0.f;
-  EIOKU_HIP_CHECK(hipEventSynchronize(m->ev[1]));
-  EIOKU_HIP_CHECK(hipEventElapsedTime(&v, m->ev[0], m->ev[1]));
-  *ms = v;
-  return EIOKU_OK;
+  double* const out[1] = {ms};
+  return m->clock.last_ms(out);
 }
 
 }  // extern "C"

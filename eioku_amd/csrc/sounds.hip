@@ -9,19 +9,18 @@
 //                       launch per window (a window's patch rows start two rows into its tokens)
 //   k_ast_tokens        the CLS and distillation rows: token + position 0 / 1
 //   k_ln<h16>           (layernorm.h) LayerNorm, fp32 row -> fp16
-//   k_attn_tiles<DenseSeq, false>  (attn_f16.h) attention over the n = P + 2 tokens of a window
+//   k_attn_tiles<DenseSeq, false>  (attn_f16.h) attention over the n = P + 2 tokens of a window; a layer is attn_sublayer and
+//                       mlp_sublayer of encoder.h
 //   k_ast_head          K29c: one workgroup per window: the encoder's final LayerNorm on rows 0 and 1 only, their mean, the
-//                       classifier's LayerNorm, dense -> logits fp32; sigmoid; top-k by logit, ties to the smaller index
+//                       classifier's LayerNorm, dense -> logits fp32; sigmoid; top-k by logit (block_argmax_256,
+//                       layernorm.h), ties to the smaller index
 // Residual stream x, fp32, in the model's token order: row b n + tok, tok = cls, distillation, then the P patches.
 // Precision points (tests/sounds_oracle.py, fp16=True, rounds at the same places): linear / conv weights fp16; biases,
 // LayerNorm parameters, the tokens and the position table fp32; the residual stream fp32; the patch rows, LayerNorm outputs
 // that feed a GEMM (the classifier's included), q / k / v, attention outputs and GELU outputs are rounded to fp16; the
 // attention kernel rounds its softmax numerators exp(s - max) to fp16 for the PV MFMA.
-#include "attn_f16.h"
 #include "common.h"
-#include "gemm_f16.h"
-#include "layernorm.h"
-#include "tensors.h"
+#include "encoder.h"
 
 #include <cmath>
 #include <string>
@@ -170,38 +169,16 @@ __global__ __launch_bounds__(256) void k_ast_head(const float* __restrict__ x, i
   }
   __syncthreads();
   for (int k = 0; k < top_k; ++k) {
-    float bv = -INFINITY;  // taken entries are set to NaN, which compares false
-    int bi = 0x7fffffff;
-    for (int j = tid; j < labels; j += 256) {
-      const float v = s_l[j];
-      if (v > bv || (v == bv && j < bi)) bv = v, bi = j;  // ascending j: the first of equal values stays
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > bv || (ov == bv && oi < bi)) bv = ov, bi = oi;
-    }
-    if (lane == 0) s_f[wave] = bv, s_i[wave] = bi;
-    __syncthreads();
-    bv = s_f[0], bi = s_i[0];
-#pragma unroll
-    for (int wv = 1; wv < 4; ++wv)
-      if (s_f[wv] > bv || (s_f[wv] == bv && s_i[wv] < bi)) bv = s_f[wv], bi = s_i[wv];
-    if (bi >= labels) bi = 0;  // only NaN logits are left
+    Best best = block_argmax_256(s_l, labels, -INFINITY, s_f, s_i);  // taken entries are set to NaN, which compares false
+    if (best.i >= labels) best.i = 0;  // only NaN logits are left
     if (tid == 0) {
-      score_out[(size_t)b * top_k + k] = (float)(1.0 / (1.0 + exp(-(double)bv)));
-      id_out[(size_t)b * top_k + k] = bi;
-      s_l[bi] = NAN;
+      score_out[(size_t)b * top_k + k] = (float)(1.0 / (1.0 + exp(-(double)best.v)));
+      id_out[(size_t)b * top_k + k] = best.i;
+      s_l[best.i] = NAN;
     }
     __syncthreads();
   }
 }
-
-struct Layer {
-  LNorm ln1, ln2;
-  Lin qkv, out, fc1, fc2;
-};
 
 }  // namespace
 
@@ -210,7 +187,7 @@ struct eioku_ast : TensorTable {
   int d = 0, layers = 0, heads = 0, ffn = 0, labels = 0;
   float eps = 1e-12f, pad = 0.f;
   double mean = 0, std = 1;
-  std::vector<Layer> L;
+  std::vector<EncLayer> L;
   int cls_token = 0, dist_token = 0, pos = 0;
   Lin proj{}, dense{};
   LNorm final_ln{}, cls_ln{};
@@ -221,11 +198,10 @@ struct eioku_ast : TensorTable {
   DevBuf<int> plan;
   DevBuf<float> spec;
   DevBuf<h16> patches;
-  DevBuf<float> x, logits, scores;
-  DevBuf<h16> h, qkv, a, mid;
+  EncWork work;
+  DevBuf<float> logits, scores;
   DevBuf<int> ids;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool timed[3] = {false, false, false};  // which of features / encoder / head the last call ran
+  StageClock<3> clock;  // features / encoder / head
   double flops = 0;
 };
 
@@ -233,25 +209,8 @@ namespace {
 
 typedef eioku_ast Model;
 
-template <int MT, int EPI>
-int gemm(Model* m, hipStream_t st, const h16* A, int lda, const Lin& w, int M, int N, int K, void* out, long long ldc,
-         const float* pos = nullptr, int pos_rows = 1) {
-  return launch_gemm<MT, EPI>(st, A, lda, m->H(w.w), K, m->F(w.b), M, N, K, out, ldc, pos, pos_rows, nullptr, &m->flops);
-}
-
-int ln(Model* m, hipStream_t st, const float* x, int M, const LNorm& p, h16* out) {
-  hipLaunchKernelGGL(k_ln<h16>, dim3((M + 3) / 4), dim3(256), 0, st, x, M, m->d, m->F(p.g), m->F(p.b), m->eps, (const int*)nullptr, out);
-  EIOKU_LAUNCH_CHECK();
-  return EIOKU_OK;
-}
-
 int ensure_batch(Model* m, int B) {
-  const size_t M = (size_t)B * m->n, d = m->d;
-  EIOKU_TRY(grow_synced(m->x, M * d));
-  EIOKU_TRY(grow_synced(m->h, M * d));
-  EIOKU_TRY(grow_synced(m->qkv, M * 3 * d));
-  EIOKU_TRY(grow_synced(m->a, M * d));
-  EIOKU_TRY(grow_synced(m->mid, M * m->ffn));
+  EIOKU_TRY(m->work.grow((size_t)B * m->n, m->d, m->ffn));
   EIOKU_TRY(grow_synced(m->logits, (size_t)B * m->labels));
   EIOKU_TRY(grow_synced(m->scores, (size_t)B * m->labels));
   return grow_synced(m->ids, (size_t)B * m->labels);
@@ -289,25 +248,20 @@ int run_features(Model* m, const int* plan, int B, hipStream_t st) {
   return EIOKU_OK;
 }
 
-// patches [B P][256] fp16 (device) -> the residual stream after every layer in m->x
+// patches [B P][256] fp16 (device) -> the residual stream after every layer in m->work.x
 int run_encoder(Model* m, const h16* patches, int B, hipStream_t st) {
-  const int d = m->d, n = m->n, P = m->P, M = B * n;
-  float* x = m->x;
+  const Enc enc{m, st, m->d, m->eps, &m->flops};
+  const int d = m->d, n = m->n, P = m->P;
+  float* x = m->work.x;
   for (int b = 0; b < B; ++b)
-    EIOKU_TRY((gemm<4, EPI_POS>(m, st, patches + (size_t)b * P * kPatchK, kPatchK, m->proj, P, d, kPatchK, x + ((size_t)b * n + 2) * d, d,
-                                m->F(m->pos) + (size_t)2 * d, P)));
+    EIOKU_TRY((enc.gemm<4, EPI_POS>(patches + (size_t)b * P * kPatchK, kPatchK, m->proj, P, d, kPatchK, x + ((size_t)b * n + 2) * d, d,
+                                    m->F(m->pos) + (size_t)2 * d, P)));
   hipLaunchKernelGGL(k_ast_tokens, dim3((unsigned)(((size_t)B * 2 * d + 255) / 256)), dim3(256), 0, st, m->F(m->cls_token),
                      m->F(m->dist_token), m->F(m->pos), B, n, d, x);
   EIOKU_LAUNCH_CHECK();
-  for (const Layer& L : m->L) {
-    EIOKU_TRY(ln(m, st, x, M, L.ln1, m->h));
-    EIOKU_TRY((gemm<4, EPI_F16>(m, st, m->h, d, L.qkv, M, 3 * d, d, m->qkv.p, 3 * d)));
-    EIOKU_TRY(launch_attn<false>(st, m->qkv.p, DenseSeq{n, d, m->a.p}, n, m->heads, B));
-    m->flops += 4.0 * B * m->heads * (double)n * n * 64;
-    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->a, d, L.out, M, d, d, x, d)));
-    EIOKU_TRY(ln(m, st, x, M, L.ln2, m->h));
-    EIOKU_TRY((gemm<4, EPI_GELU_F16>(m, st, m->h, d, L.fc1, M, m->ffn, d, m->mid.p, m->ffn)));
-    EIOKU_TRY((gemm<4, EPI_RESID>(m, st, m->mid, m->ffn, L.fc2, M, d, m->ffn, x, d)));
+  for (const EncLayer& L : m->L) {
+    EIOKU_TRY(attn_sublayer<false>(enc, m->work, L, B, n, m->heads));
+    EIOKU_TRY(mlp_sublayer(enc, m->work, B * n, L.ln2, L.fc1, L.fc2, m->ffn, false));
   }
   return EIOKU_OK;
 }
@@ -357,7 +311,7 @@ int eioku_ast_create(int num_mel_bins, int max_length, int fstride, int tstride,
   m->proj = m->lin(e + "patch_embeddings.projection", d, kPatchK);
   for (int l = 0; l < layers; ++l) {
     const std::string p = a + "layers." + std::to_string(l) + ".";
-    Layer L;
+    EncLayer L;
     L.qkv.w = m->packed(p + "attention.qkv.weight", 3 * d, d, T_F16);
     L.qkv.b = m->packed(p + "attention.qkv.bias", 3 * d, 1, T_F32);
     const char* names[3] = {"q_proj", "k_proj", "v_proj"};
@@ -385,12 +339,7 @@ int eioku_ast_create(int num_mel_bins, int max_length, int fstride, int tstride,
   for (int i = 0; i < kFft; ++i) tab[kFrame + i] = std::cos(2.0 * M_PI * (double)i / (double)kFft);
   std::copy(mel, mel + (size_t)kBins * num_mel_bins, tab.begin() + kFrame + kFft);
   if (const int rc = m->tables.upload(tab.data(), tab.size())) return fail(rc);
-  for (auto& ev : m->ev)
-    if (hipEventCreate(&ev) != hipSuccess) {
-      ev = nullptr;
-      set_error("hipEventCreate failed");
-      return fail(EIOKU_EHIP);
-    }
+  if (const int rc = m->clock.create()) return fail(rc);
   *out = m;
   return EIOKU_OK;
 }
@@ -398,9 +347,7 @@ int eioku_ast_create(int num_mel_bins, int max_length, int fstride, int tstride,
 void eioku_ast_destroy(eioku_ast* m) {
   if (!m) return;
   (void)hipDeviceSynchronize();
-  for (auto ev : m->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete m;  // every buffer frees itself
+  delete m;  // every buffer and event frees itself
 }
 
 int eioku_ast_num_tensors(const eioku_ast* m) { return TensorTable::count(m); }
@@ -439,10 +386,10 @@ int eioku_ast_features(eioku_ast* m, const int32_t* plan, int n_windows, float* 
   hipStream_t st = (hipStream_t)stream_;
   EIOKU_TRY(ensure_features(m, n_windows));
   m->flops = 0;
-  m->timed[0] = true, m->timed[1] = m->timed[2] = false;
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[0], st));
+  m->clock.begin(0b001);
+  EIOKU_TRY(m->clock.mark(0, st));
   EIOKU_TRY(run_features(m, plan, n_windows, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  EIOKU_TRY(m->clock.mark(1, st));
   if (spec_out)
     EIOKU_HIP_CHECK(hipMemcpyAsync(spec_out, m->spec, (size_t)n_windows * m->T * m->bins * 4, hipMemcpyDeviceToDevice, st));
   if (patches_out)
@@ -463,15 +410,15 @@ int eioku_ast_forward(eioku_ast* m, const void* patches, int n_windows, float* l
   hipStream_t st = (hipStream_t)stream_;
   EIOKU_TRY(ensure_batch(m, n_windows));
   m->flops = 0;
-  m->timed[0] = false, m->timed[1] = m->timed[2] = true;
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  m->clock.begin(0b110);
+  EIOKU_TRY(m->clock.mark(1, st));
   EIOKU_TRY(run_encoder(m, (const h16*)patches, n_windows, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
-  EIOKU_TRY(launch_head(m, m->x, m->logits, n_windows, 0, nullptr, nullptr, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  EIOKU_TRY(m->clock.mark(2, st));
+  EIOKU_TRY(launch_head(m, m->work.x, m->logits, n_windows, 0, nullptr, nullptr, st));
+  EIOKU_TRY(m->clock.mark(3, st));
   EIOKU_HIP_CHECK(hipMemcpyAsync(logits_out, m->logits, (size_t)n_windows * m->labels * 4, hipMemcpyDeviceToDevice, st));
   if (hidden_out)
-    EIOKU_HIP_CHECK(hipMemcpyAsync(hidden_out, m->x, (size_t)n_windows * m->n * m->d * 4, hipMemcpyDeviceToDevice, st));
+    EIOKU_HIP_CHECK(hipMemcpyAsync(hidden_out, m->work.x, (size_t)n_windows * m->n * m->d * 4, hipMemcpyDeviceToDevice, st));
   return EIOKU_OK;
 }
 
@@ -504,19 +451,19 @@ int eioku_ast_classify(eioku_ast* m, const int32_t* plan, int n_windows, int top
   EIOKU_TRY(ensure_features(m, n_windows));
   EIOKU_TRY(ensure_batch(m, n_windows));
   m->flops = 0;
-  m->timed[0] = m->timed[1] = m->timed[2] = true;
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[0], st));
+  m->clock.begin(0b111);
+  EIOKU_TRY(m->clock.mark(0, st));
   EIOKU_TRY(run_features(m, plan, n_windows, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[1], st));
+  EIOKU_TRY(m->clock.mark(1, st));
   EIOKU_TRY(run_encoder(m, m->patches.p, n_windows, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[2], st));
-  EIOKU_TRY(launch_head(m, m->x, m->logits, n_windows, top_k, m->scores, m->ids, st));
-  EIOKU_HIP_CHECK(hipEventRecord(m->ev[3], st));
+  EIOKU_TRY(m->clock.mark(2, st));
+  EIOKU_TRY(launch_head(m, m->work.x, m->logits, n_windows, top_k, m->scores, m->ids, st));
+  EIOKU_TRY(m->clock.mark(3, st));
   const hipMemcpyKind kind = mem == EIOKU_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   EIOKU_HIP_CHECK(hipMemcpyAsync(score_out, m->scores, (size_t)n_windows * top_k * 4, kind, st));
   EIOKU_HIP_CHECK(hipMemcpyAsync(id_out, m->ids, (size_t)n_windows * top_k * 4, kind, st));
   if (logits_out) EIOKU_HIP_CHECK(hipMemcpyAsync(logits_out, m->logits, (size_t)n_windows * m->labels * 4, kind, st));
-  if (hidden_out) EIOKU_HIP_CHECK(hipMemcpyAsync(hidden_out, m->x, (size_t)n_windows * m->n * m->d * 4, kind, st));
+  if (hidden_out) EIOKU_HIP_CHECK(hipMemcpyAsync(hidden_out, m->work.x, (size_t)n_windows * m->n * m->d * 4, kind, st));
   if (mem == EIOKU_MEM_HOST) EIOKU_HIP_CHECK(hipStreamSynchronize(st));
   return EIOKU_OK;
 }
@@ -530,16 +477,8 @@ int eioku_ast_last_flops(const eioku_ast* m, double* flops) {
 // device milliseconds of the last features / forward / classify call per stage (0 for a stage that call did not run); waits
 int eioku_ast_last_ms(const eioku_ast* m, double* features_ms, double* encoder_ms, double* head_ms) {
   EIOKU_REQUIRE(m && features_ms && encoder_ms && head_ms, "NULL argument");
-  double* out[3] = {features_ms, encoder_ms, head_ms};
-  for (int i = 0; i < 3; ++i) {
-    *out[i] = 0.0;
-    if (!m->timed[i]) continue;
-    float ms = 0.f;
-    EIOKU_HIP_CHECK(hipEventSynchronize(m->ev[i + 1]));
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, m->ev[i], m->ev[i + 1]));
-    *out[i] = ms;
-  }
-  return EIOKU_OK;
+  double* const out[3] = {features_ms, encoder_ms, head_ms};
+  return m->clock.last_ms(out);
 }
 
 }  // extern "C"

@@ -238,8 +238,7 @@ struct eioku_spk {
   DevBuf<float> stats;         // [m][5120]
   DevBuf<int> plan;            // [cap][2] | valid [cap], cap = plan.cap / 3 windows
   int* valid() const { return plan.p + plan.cap / 3 * 2; }
-  // events stay raw handles: created in eioku_spk_create, destroyed in eioku_spk_destroy
-  hipEvent_t ev[4] = {};
+  DevEvents ev;                // 4: around features, network, pooling + head of one pass
   double ms[3] = {};           // features, network, pooling + head of the last embed
 };
 
@@ -355,11 +354,7 @@ int eioku_spk_create(const int* depths, int win_frames, const double* window, co
   }
   int rc = s->tables.upload(tab.data(), tab.size());
   if (!rc) rc = s->mel_range.upload(range.data(), range.size());
-  for (auto& e : s->ev)
-    if (!rc && hipEventCreate(&e) != hipSuccess) {
-      set_error("eioku_spk_create: hipEventCreate failed");
-      rc = EIOKU_EHIP;
-    }
+  if (!rc) rc = s->ev.ensure(4);
   if (rc) {
     eioku_spk_destroy(s);
     return rc;
@@ -371,8 +366,6 @@ int eioku_spk_create(const int* depths, int win_frames, const double* window, co
 void eioku_spk_destroy(eioku_spk_t* s) {
   if (!s) return;
   (void)hipDeviceSynchronize();
-  for (auto& e : s->ev)
-    if (e) (void)hipEventDestroy(e);
   delete s;
 }
 
@@ -494,21 +487,21 @@ int eioku_spk_embed(eioku_spk_t* s, const int* plan, int m, float* emb_out, void
     EIOKU_HIP_CHECK(hipMemcpyAsync(s->plan, pv.data(), (size_t)mc * 8, hipMemcpyHostToDevice, stream));
     EIOKU_HIP_CHECK(hipMemcpyAsync(s->valid(), pv.data() + 2 * (size_t)kPass, (size_t)mc * 4, hipMemcpyHostToDevice,
                                    stream));
-    EIOKU_HIP_CHECK(hipEventRecord(s->ev[0], stream));
+    EIOKU_TRY(s->ev.record(0, stream));
     rc = run_features(s, s->plan, mc, nullptr, s->in16, stream);
     if (rc) return rc;
-    EIOKU_HIP_CHECK(hipEventRecord(s->ev[1], stream));
+    EIOKU_TRY(s->ev.record(1, stream));
     int x = 0;
     rc = run_network(s, mc, -1, nullptr, &x, stream);
     if (rc) return rc;
-    EIOKU_HIP_CHECK(hipEventRecord(s->ev[2], stream));
+    EIOKU_TRY(s->ev.record(2, stream));
     rc = run_pool_head(s, mc, x, s->valid(), emb_out + (size_t)c0 * kEmb, stream);
     if (rc) return rc;
-    EIOKU_HIP_CHECK(hipEventRecord(s->ev[3], stream));
+    EIOKU_TRY(s->ev.record(3, stream));
     EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // pv and the plan buffer are reused by the next pass
     for (int k = 0; k < 3; ++k) {
-      float t = 0.f;
-      EIOKU_HIP_CHECK(hipEventElapsedTime(&t, s->ev[k], s->ev[k + 1]));
+      double t = 0.0;
+      EIOKU_TRY(s->ev.ms(k, k + 1, &t));
       s->ms[k] += t;
     }
   }

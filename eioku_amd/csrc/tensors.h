@@ -1,7 +1,7 @@
-// The named-tensor table of the transformer models (K20 Whisper, K25 TimeSformer, K26 CLIP, K27 nomic-embed-text): the tensors
-// of a state_dict() in its order, their device copies, and what *_num_tensors / *_tensor_info / *_set_tensor do with them.
-// A model's handle derives from TensorTable and lists its tensors in its create function.  Included by whisper.hip,
-// actions.hip, clip.hip, nomic.hip and sounds.hip; everything here has internal linkage.
+// The named-tensor table of the transformer models (K20 Whisper, K25 TimeSformer, K26 CLIP, K27 nomic-embed-text, K29 AST): the
+// tensors of a state_dict() in its order, their device copies, and what *_num_tensors / *_tensor_info / *_set_tensor do with
+// them.  A model's handle derives from TensorTable and lists its tensors in its create function.  Included by whisper.hip and
+// nomic.hip, and through encoder.h by actions.hip, clip.hip and sounds.hip; everything here has internal linkage.
 #pragma once
 
 #include "common.h"

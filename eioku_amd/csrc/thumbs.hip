@@ -371,7 +371,7 @@ struct eioku_thumbs {
   eioku::DevBuf<unsigned> len;  // [n][nblk] bit lengths, then [n][nblk] offsets, [n] totals, [n] word offsets
   eioku::DevBuf<unsigned> bits;
   size_t bits_bytes = 0;  // of the last eioku_thumbs_jpeg call
-  hipEvent_t ev[kNumEvents] = {};
+  eioku::DevEvents ev;    // kNumEvents
   bool timed[3] = {false, false, false};  // resize, jpeg, read have run since create
 };
 
@@ -389,11 +389,7 @@ int eioku_thumbs_create(eioku_thumbs_t** out) {
   huff_fill(kAcChromaBits, kAcChromaVals, h.data() + kAcOff + 256);
   int rc = t->huff.upload(h.data(), kHuffEntries);
   if (!rc) rc = t->qtab.grow(128);
-  for (int i = 0; i < kNumEvents && !rc; ++i)
-    if (hipEventCreate(&t->ev[i]) != hipSuccess) {
-      ::eioku::set_error("eioku_thumbs_create: hipEventCreate failed");
-      rc = EIOKU_EHIP;
-    }
+  if (!rc) rc = t->ev.ensure(kNumEvents);
   if (rc) {
     eioku_thumbs_destroy(t);
     return rc;
@@ -404,8 +400,6 @@ int eioku_thumbs_create(eioku_thumbs_t** out) {
 
 void eioku_thumbs_destroy(eioku_thumbs_t* t) {
   if (!t) return;
-  for (hipEvent_t e : t->ev)
-    if (e) (void)hipEventDestroy(e);
   delete t;
 }
 
@@ -438,12 +432,12 @@ int eioku_thumbs_resize(eioku_thumbs_t* t, const uint8_t* bgr, int n, int h, int
   EIOKU_HIP_CHECK(hipMemcpyAsync(d_yb, ybounds, yb_n * 4, hipMemcpyHostToDevice, stream));
   EIOKU_HIP_CHECK(hipMemcpyAsync(d_yk, yk, yk_n * 4, hipMemcpyHostToDevice, stream));
   const long long w1 = (long long)n * h * tw, w2 = (long long)n * th * tw;
-  EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvResize0], stream));
+  EIOKU_TRY(t->ev.record(kEvResize0, stream));
   hipLaunchKernelGGL(k_thumb_resize_h, dim3((unsigned)((w1 + 255) / 256)), dim3(256), 0, stream, bgr, w1, w, tw, d_xb, d_xk, kx, t->tmp.p);
   hipLaunchKernelGGL(k_thumb_resize_v, dim3((unsigned)((w2 + 255) / 256)), dim3(256), 0, stream, t->tmp.p, w2, h, th, tw, d_yb, d_yk, ky,
                      rgb_out);
   EIOKU_LAUNCH_CHECK();
-  EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvResize1], stream));
+  EIOKU_TRY(t->ev.record(kEvResize1, stream));
   t->timed[0] = true;
   return EIOKU_OK;
 }
@@ -469,10 +463,10 @@ int eioku_thumbs_jpeg(eioku_thumbs_t* t, const uint8_t* rgb, int n, int th, int 
   unsigned* d_total = d_off + nb;
   unsigned* d_word = d_total + n;
   EIOKU_HIP_CHECK(hipMemcpyAsync(t->qtab, qtab, 128 * 2, hipMemcpyHostToDevice, stream));
-  EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvJpeg0], stream));
+  EIOKU_TRY(t->ev.record(kEvJpeg0, stream));
   hipLaunchKernelGGL(k_jpeg_blocks, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream, rgb, n, th, tw, mx, my, t->qtab.p, t->coef.p);
   EIOKU_LAUNCH_CHECK();
-  EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvBlocks], stream));
+  EIOKU_TRY(t->ev.record(kEvBlocks, stream));
   hipLaunchKernelGGL(k_jpeg_bitlen, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, t->coef.p, n, nblk, t->huff.p, d_len);
   hipLaunchKernelGGL(k_jpeg_scan, dim3((unsigned)n), dim3(kScanThreads), 0, stream, d_len, nblk, d_off, d_total);
   EIOKU_LAUNCH_CHECK();
@@ -493,7 +487,7 @@ int eioku_thumbs_jpeg(eioku_thumbs_t* t, const uint8_t* rgb, int n, int th, int 
   hipLaunchKernelGGL(k_jpeg_emit, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, stream, t->coef.p, n, nblk, t->huff.p, d_off, d_word,
                      t->bits.p);
   EIOKU_LAUNCH_CHECK();
-  EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvEntropy], stream));
+  EIOKU_TRY(t->ev.record(kEvEntropy, stream));
   if (coef_out) EIOKU_HIP_CHECK(hipMemcpyAsync(coef_out, t->coef, nb * 64 * 2, hipMemcpyDeviceToHost, stream));
   EIOKU_HIP_CHECK(hipStreamSynchronize(stream));  // word_off (stack) has been read; coef_out is filled
   t->bits_bytes = words * 4;
@@ -509,9 +503,9 @@ int eioku_thumbs_read(eioku_thumbs_t* t, uint8_t* out, size_t cap, void* stream_
   if (t->bits_bytes == 0) return EIOKU_OK;
   EIOKU_REQUIRE(out, "NULL buffer");
   hipStream_t stream = (hipStream_t)stream_;
-  EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvRead0], stream));
+  EIOKU_TRY(t->ev.record(kEvRead0, stream));
   EIOKU_HIP_CHECK(hipMemcpyAsync(out, t->bits, t->bits_bytes, hipMemcpyDeviceToHost, stream));
-  EIOKU_HIP_CHECK(hipEventRecord(t->ev[kEvRead1], stream));
+  EIOKU_TRY(t->ev.record(kEvRead1, stream));
   EIOKU_HIP_CHECK(hipStreamSynchronize(stream));
   t->timed[2] = true;
   return EIOKU_OK;
@@ -524,10 +518,7 @@ int eioku_thumbs_last_ms(eioku_thumbs_t* t, double* ms4) {
   for (int i = 0; i < 4; ++i) {
     ms4[i] = 0.0;
     if (!t->timed[pairs[i][2]]) continue;
-    EIOKU_HIP_CHECK(hipEventSynchronize(t->ev[pairs[i][1]]));
-    float ms = 0.f;
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, t->ev[pairs[i][0]], t->ev[pairs[i][1]]));
-    ms4[i] = ms;
+    EIOKU_TRY(t->ev.ms(pairs[i][0], pairs[i][1], &ms4[i]));
   }
   return EIOKU_OK;
 }

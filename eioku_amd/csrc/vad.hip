@@ -282,7 +282,7 @@ struct eioku_vad {
   DevBuf<float> gx;         // slab * 512
   DevBuf<float> probs;      // slab
   DevBuf<float> state;      // h [128], c [128]
-  std::vector<hipEvent_t> ev;   // 3 per slab of the last call
+  DevEvents ev;             // 3 per slab of the last call
   double encode_ms = 0, lstm_ms = 0;
 };
 
@@ -291,9 +291,8 @@ extern "C" {
 void eioku_vad_destroy(eioku_vad* v) {
   if (!v) return;
   if (v->st) (void)hipStreamSynchronize(v->st);
-  for (hipEvent_t e : v->ev) (void)hipEventDestroy(e);
   if (v->st) (void)hipStreamDestroy(v->st);
-  delete v;  // every buffer frees itself
+  delete v;  // every buffer and event frees itself
 }
 
 int eioku_vad_create(int slab_chunks, eioku_vad** out) {
@@ -362,11 +361,7 @@ int eioku_vad_probs(eioku_vad* v, const float* samples, long long n_samples, flo
   *n_probs = n;
   EIOKU_REQUIRE(probs_out && n_probs_cap >= n, "probs_out holds %lld values, %lld samples give %lld", n_probs_cap, n_samples, n);
   const long long n_slabs = (n + v->slab - 1) / v->slab;
-  while ((long long)v->ev.size() < 3 * n_slabs) {
-    hipEvent_t e;
-    EIOKU_HIP_CHECK(hipEventCreate(&e));
-    v->ev.push_back(e);
-  }
+  EIOKU_TRY(v->ev.ensure((size_t)(3 * n_slabs)));
   const EncW W{v->t[V_BASIS].dev, v->t[V_W0].dev, v->t[V_B0].dev, v->t[V_W1].dev, v->t[V_B1].dev, v->t[V_W2].dev, v->t[V_B2].dev,
                v->t[V_W3].dev,    v->t[V_B3].dev, v->t[V_WIH].dev, v->t[V_BIH].dev, v->t[V_BHH].dev};
   hipStream_t st = v->st;
@@ -385,22 +380,22 @@ int eioku_vad_probs(eioku_vad* v, const float* samples, long long n_samples, flo
     if (have) EIOKU_HIP_CHECK(hipMemcpyAsync(v->audio + kCtx, samples + a0, (size_t)have * sizeof(float), hipMemcpyHostToDevice, st));
     if (have < (long long)m * kChunk)
       EIOKU_HIP_CHECK(hipMemsetAsync(v->audio + kCtx + have, 0, (size_t)((long long)m * kChunk - have) * sizeof(float), st));
-    EIOKU_HIP_CHECK(hipEventRecord(v->ev[3 * s], st));
+    EIOKU_TRY(v->ev.record(3 * s, st));
     hipLaunchKernelGGL(k_vad_encode, dim3((unsigned)((m + kTile - 1) / kTile)), dim3(256), 0, st, v->audio.p, m, W, v->gx.p);
     EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipEventRecord(v->ev[3 * s + 1], st));
+    EIOKU_TRY(v->ev.record(3 * s + 1, st));
     hipLaunchKernelGGL(k_vad_lstm, dim3(1), dim3(kGates), 0, st, v->gx.p, m, v->t[V_WHH].dev.p, v->t[V_WOUT].dev.p, v->t[V_BOUT].dev.p,
                        v->state.p, v->probs.p);
     EIOKU_LAUNCH_CHECK();
-    EIOKU_HIP_CHECK(hipEventRecord(v->ev[3 * s + 2], st));
+    EIOKU_TRY(v->ev.record(3 * s + 2, st));
     // the next slab reuses audio, gx and probs: stream order keeps its copies behind this slab's kernels and read-back
     EIOKU_HIP_CHECK(hipMemcpyAsync(probs_out + first, v->probs, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, st));
   }
   EIOKU_HIP_CHECK(hipStreamSynchronize(st));
   for (long long s = 0; s < n_slabs; ++s) {
-    float a = 0, b = 0;
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&a, v->ev[3 * s], v->ev[3 * s + 1]));
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&b, v->ev[3 * s + 1], v->ev[3 * s + 2]));
+    double a = 0, b = 0;
+    EIOKU_TRY(v->ev.ms(3 * s, 3 * s + 1, &a));
+    EIOKU_TRY(v->ev.ms(3 * s + 1, 3 * s + 2, &b));
     v->encode_ms += a;
     v->lstm_ms += b;
   }

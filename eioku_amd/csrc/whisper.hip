@@ -2155,22 +2155,6 @@ int dtw_launch(eioku_whisper* m, const float* cost, int R, int Nmax, int ldf, co
   return launched(m);
 }
 
-// the four events that bracket the three stages of align(): destroyed with the scope
-struct StageEvents {
-  hipEvent_t ev[4] = {};
-  StageEvents() = default;
-  StageEvents(const StageEvents&) = delete;
-  StageEvents& operator=(const StageEvents&) = delete;
-  ~StageEvents() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int create() {
-    for (auto& e : ev) EIOKU_HIP_CHECK(hipEventCreate(&e));
-    return EIOKU_OK;
-  }
-};
-
 }  // namespace
 }  // extern "C++"
 
@@ -2249,10 +2233,9 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
   EIOKU_HIP_CHECK(hipMemset(m->al_jump, 0xFF, nJ * sizeof(int)));
   EIOKU_HIP_CHECK(hipMemset(m->al_prob, 0, nJ * sizeof(float)));
   const int *d_ntok = m->al_meta, *d_nF = m->al_meta + R, *d_nN = m->al_meta + 2 * R;
-  StageEvents stage;
-  EIOKU_TRY(stage.create());
-  hipEvent_t* ev = stage.ev;
-  EIOKU_HIP_CHECK(hipEventRecord(ev[0], 0));
+  DevEvents ev;  // the four events that bracket the three stages: destroyed with the scope
+  EIOKU_TRY(ev.ensure(4));
+  EIOKU_TRY(ev.record(0, 0));
   const AlignCapture cap{heads.data(), Hs, Fmax, d_nF, m->al_A};
   EIOKU_TRY(prefill(m, R, T, m->d_ids, m->kvmap, 1, 1, &cap));
   hipLaunchKernelGGL(k_align_logits, dim3(nblk), dim3(256), 0, 0, m->pw.h, d, m->H(m->emb), m->al_rows, m->al_rows + Mp, (int)Mp, c.eot,
@@ -2262,17 +2245,12 @@ int eioku_whisper_align(eioku_whisper* m, const int32_t* seq, int T, const int32
   EIOKU_LAUNCH_CHECK();
   m->flops += 2.0 * (double)Mp * c.eot * d;
   m->launches += 2;
-  EIOKU_HIP_CHECK(hipEventRecord(ev[1], 0));
+  EIOKU_TRY(ev.record(1, 0));
   EIOKU_TRY(align_cost_launch(m, m->al_A, R, Hs, T, Fmax, S, d_ntok, d_nF, Nmax, m->al_cost));
-  EIOKU_HIP_CHECK(hipEventRecord(ev[2], 0));
+  EIOKU_TRY(ev.record(2, 0));
   EIOKU_TRY(dtw_launch(m, m->al_cost, R, Nmax, Fmax, d_nN, d_nF, m->al_jump, nullptr, nullptr));
-  EIOKU_HIP_CHECK(hipEventRecord(ev[3], 0));
-  EIOKU_HIP_CHECK(hipEventSynchronize(ev[3]));
-  for (int i = 0; i < 3; ++i) {
-    float ms = 0.f;
-    EIOKU_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-    m->align_ms[i] = ms;
-  }
+  EIOKU_TRY(ev.record(3, 0));
+  for (int i = 0; i < 3; ++i) EIOKU_TRY(ev.ms(i, i + 1, &m->align_ms[i]));  // waits for each stage's end
   EIOKU_HIP_CHECK(hipMemcpy(jump_out, m->al_jump, nJ * sizeof(int), hipMemcpyDeviceToHost));
   EIOKU_HIP_CHECK(hipMemcpy(prob_out, m->al_prob, nJ * sizeof(float), hipMemcpyDeviceToHost));
   if (cost_out) EIOKU_HIP_CHECK(hipMemcpy(cost_out, m->al_cost, nC * sizeof(float), hipMemcpyDeviceToHost));

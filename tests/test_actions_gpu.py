@@ -171,6 +171,20 @@ def test_head_ties_go_to_the_smaller_index(model_w):
     _check_topk(model_w.dev, logits, 6)
 
 
+def test_head_picks_probabilities_of_zero_in_index_order(model_s):
+    """-inf logits give probabilities of exactly 0, above the selection's floor of -1: they are picked after every positive
+    one, in index order, and a pick that was taken (-2) never comes back."""
+    logits = np.array([[-np.inf, 0.5, -np.inf, 0.5, -1.0, -np.inf, -np.inf]], np.float32)
+    assert ao.softmax_topk(logits, 7)[1].tolist() == [[1, 3, 4, 0, 2, 5, 6]]
+    probs, ids = (t.cpu().numpy() for t in model_s.dev.topk(torch.from_numpy(logits).cuda(), 7))
+    assert ids.tolist() == [[1, 3, 4, 0, 2, 5, 6]]
+    assert probs[0, 0] == probs[0, 1] and (probs[0, 3:] == 0.0).all()
+    _check_topk(model_s.dev, logits, 7)
+    # the sum: 2 ulp per probability as in _check_topk, and 2^-24 each for the oracle's rounded total and quotients
+    want_p = ao.softmax_topk(logits, 7)[0]
+    assert abs(probs.astype(np.float64).sum() - 1.0) <= 2 * np.spacing(want_p).astype(np.float64).sum() + 2.0 ** -23
+
+
 def test_classify_end_to_end_w(gpu):
     """BGR frames -> labels, against the fp32 oracle on the oracle's own preprocessing.  The comparison is only meaningful
     while the oracle's six best logits are further apart than the device may drift, so that condition is asserted, not

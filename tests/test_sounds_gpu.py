@@ -258,6 +258,17 @@ def test_head_ties_go_to_the_smaller_index(model_w):
     _check_topk(model_w.dev, logits, 527)
 
 
+def test_head_picks_logits_at_the_floor_in_index_order(model_s):
+    """-inf is the selection's floor: such logits are picked after every finite one, in index order, with a score of 0, and a
+    pick that was taken (NaN) never comes back."""
+    logits = np.array([[-np.inf, 0.5, -np.inf, 0.5, -1.0, -np.inf, -np.inf]], np.float32)
+    assert so.sigmoid_topk(logits, 7)[1].tolist() == [[1, 3, 4, 0, 2, 5, 6]]
+    scores, ids = (t.cpu().numpy() for t in model_s.dev.topk(torch.from_numpy(logits).cuda(), 7))
+    assert ids.tolist() == [[1, 3, 4, 0, 2, 5, 6]]
+    assert (scores[0, 3:] == 0.0).all()
+    _check_topk(model_s.dev, logits, 7)
+
+
 # ---- 5. end to end ---------------------------------------------------------------------------------------------------------------
 E2E_SEED, E2E_AUDIO_SEED = 48, 41
 

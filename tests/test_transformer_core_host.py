@@ -144,12 +144,17 @@ def test_the_unrounded_sum_is_caught_by_the_case_built_for_it():
 def _instantiations(path):
     """The (MT, EPI) of every launch_gemm<MT, EPI> a model source instantiates.  The sources reach it through function
     templates (gemm<MT, EPI>, mlp<MT>, cross_attn<MT, QPW> ...): a call with literal arguments instantiates its callee, a call
-    inside a function template instantiates it once per instantiation of that template, to a fixed point."""
-    text = re.sub(r"//[^\n]*", "", path.read_text())
+    inside a function template instantiates it once per instantiation of that template, to a fixed point.  A source that
+    includes encoder.h is read together with it (Enc::gemm and the sublayers are defined there); a definition ends at the
+    closing brace of its own indentation, so a member template ends inside its struct."""
+    text = path.read_text()
+    if '#include "encoder.h"' in text:
+        text += (CSRC / "encoder.h").read_text()
+    text = re.sub(r"//[^\n]*", "", text)
     defs = {}
-    for m in re.finditer(r"template <([^>]*)>\s*int (\w+)\(", text):
-        params = [p.split()[-1] for p in m.group(1).split(",")]
-        defs[m.group(2)] = (params, m.end(), text.index("\n}\n", m.end()))
+    for m in re.finditer(r"^([ \t]*)template <([^>]*)>\s*int (\w+)\(", text, re.M):
+        params = [p.split()[-1] for p in m.group(2).split(",")]
+        defs[m.group(3)] = (params, m.end(), text.index("\n" + m.group(1) + "}\n", m.end()))
     calls = []  # (callee, arguments, enclosing function template or None)
     for m in re.finditer(r"\b(\w+)<([\w\s,]+)>\s*\(", text):
         if m.group(1) in defs or m.group(1) == "launch_gemm":
@@ -170,7 +175,7 @@ def _instantiations(path):
 
 
 def test_probe_dispatch_table_is_the_models_instantiations():
-    found = set().union(*(_instantiations(CSRC / f) for f in ("whisper.hip", "actions.hip", "clip.hip", "nomic.hip")))
+    found = set().union(*(_instantiations(CSRC / f) for f in ("whisper.hip", "actions.hip", "clip.hip", "nomic.hip", "sounds.hip")))
     assert len(found) >= 13 and all(epi in o.EPI_NAMES for _, epi in found), found
     probe = (CSRC / "probe" / "transformer_probe.hip").read_text()
     table = {(int(mt), epi) for mt, epi in re.findall(r"^\s*X\((\d+), (EPI_\w+)\)", probe, re.M)}
