@@ -187,5 +187,10 @@ def test_probe_dispatch_table_is_the_models_instantiations():
 
 
 def test_product_does_not_reference_the_probe():
+    sources = sorted((CSRC / "probe").glob("*.hip"))
+    assert {"whisper_probe.hip", "actions_probe.hip", "transformer_probe.hip"} <= {p.name for p in sources}
+    names = [n for p in sources for n in re.findall(r"int (eioku_probe_\w+)\(", p.read_text())] + [p.stem for p in sources]
+    assert "eioku_probe_wh_attn" in names and "eioku_probe_attn_time" in names
     for path in list((ROOT / "eioku_amd").glob("*.py")) + [ROOT / "include" / "eioku_hip.h", ROOT / "bench.py"]:
         assert "libeioku_hip_probe" not in path.read_text() and "eioku_probe_" not in path.read_text(), path
+        assert not any(n in path.read_text() for n in names), path
